@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
-"""bench.py -- LMC chain-iterations/s on MI355X (BASELINE.json metric), with the HBM roofline of the
+"""bench.py -- LMC chain-iterations/s on MI355X (BASELINE.json metric); with --full also the HBM roofline of the
 fused step kernel and the CPU oracle timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--tv-warm]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--repeats R] [--tv-warm] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up steps, times ONE region of exactly K steps and prints the result line (`value`, `ms_per_step`).
+`--full` adds what takes runs of its own: R = 3 timed regions by default (median reported), the event-timed roofline leg, the HBM
+copy probe, the chain as the reference is configured (TV rtol = 1e-4) and the CPU oracle baseline.  `--dump-outputs DIR` writes what
+the timed path computed in its last step (see dump_outputs) for output-by-output comparison of two builds.
 
 A "step" is one MYULA iteration (algs.py:569) of every chain resident on the GPU.  Workload at
 N = 1: BASELINE.json configs[2] -- 512x512 deblurring (5x5 uniform box blur as prox_lmc_deconv.py:55-58,
@@ -14,7 +19,7 @@ global id, and the only collective is one RCCL all-reduce of the posterior momen
 timed region.  Inputs are synthetic and resident in HBM before the timed region starts.
 
 Protocol: W warm-up steps, then the timed region of EXACTLY K steps (barrier + synchronize on both sides, max over
-ranks) is run R = 3 times back to back and the MEDIAN region is reported (`repeats`, `ms_per_step_all`); the step kernel's launch time
+ranks) is run R times back to back and the MEDIAN region is reported (`repeats`, `ms_per_step_all`); with --full the step kernel's launch time
 is the HIP-event average over the launches of that median region, on the launch stream.  `roofline` carries the spec peak, the
 bandwidth a state-shaped copy measures on this device in this process (`peak_measured`), and a `valu` block (vector-ALU busy
 fraction of the same kernel from the committed rocprofv3 counters): at K = 10 the update is bound by VALU issue, not by HBM.
@@ -108,6 +113,40 @@ def cpu_baseline(H, W, h, y, sigma, prior, label, mask=None, chains=4, iters=20,
                          "sample": f"{chains} chains x {iters} (C, {t_c1:.1f} s) / {max(1, iters // 2)} (numpy, {t_np:.1f} s) iterations"}}
 
 
+DUMP_BYTES = 64_000_000        # --dump-outputs: the files together stay below 64 MB
+
+
+def dump_outputs(out_dir, smp, moments):
+    """What a caller of the timed path receives after its last step (the many-chain MYULAResult, algs.py): `mean.npy`, `var.npy`
+    (posterior moments over the kept iterations of the last timed region, float64 [H, W]; `moments` = (sum, sumsq, count) or None),
+    `energy_f.npy`, `energy_g.npy` (per-chain f(x), g(x) of the final states, float64 [C]) and `state_sample.npy` (final states of a fixed
+    sample of chains, float32 [k, H, W]: the whole state is 1 GiB at the headline size).  The chains are drawn by default_rng(0) and their
+    ids written as `state_sample_chains.npy` (float64), so two builds run with the same arguments are compared on the same chains."""
+    import torch
+    from lmc_atomi_amd import mean_var_from_moments
+    os.makedirs(out_dir, exist_ok=True)
+    H, W = smp.dims
+    C = smp.n_chains
+    arrays = {}
+    if moments is not None:
+        s1, s2, cnt = moments
+        mean, var = mean_var_from_moments(s1, s2, max(cnt, 1))
+        arrays["mean"], arrays["var"] = mean.cpu().numpy(), var.cpu().numpy()
+    f, g = smp.energies()
+    arrays["energy_f"], arrays["energy_g"] = f.cpu().numpy(), g.cpu().numpy()
+    used = sum(a.nbytes for a in arrays.values()) + 16 * 8 + 6 * 128        # + the chain ids and the six .npy headers
+    k = min(C, 16, (DUMP_BYTES - used) // (H * W * 4))
+    if k < 1:
+        raise SystemExit(f"--dump-outputs: the moments of a {H}x{W} image alone exceed {DUMP_BYTES} bytes")
+    chains = np.sort(np.random.default_rng(0).choice(C, size=k, replace=False))
+    state = smp.get_state()
+    arrays["state_sample"] = state[torch.as_tensor(chains, device=state.device)].cpu().numpy()
+    arrays["state_sample_chains"] = chains.astype(np.float64)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -132,7 +171,12 @@ def main():
     ap.add_argument("--ncvx-iters", type=int, default=None, help="inner TV-prox iterations of the ME-TV term (default: --tv-iters; the reference uses niter_l2 = 50)")
     ap.add_argument("--noise", default="philox", choices=["philox", "none"], help="noise source (experiments)")
     ap.add_argument("--tau-scale", type=float, default=1.0, help="multiplies the step size tau = 0.2 sigma^2 (MYMALA acceptance experiments)")
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps steps; the median is reported (SURVEY 8(d))")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps steps; the median is reported (default 1; 3 with --full, SURVEY 8(d))")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: 3 timed regions, the event-timed roofline leg, the HBM probe, "
+                         "the chain as the reference is configured and the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--tv-warm", action="store_true",
                     help="warm-dual TV (SURVEY 8(d) C3 variant; build extension): carry the TV dual between MYULA iterations, "
                          "--tv-iters in {1, 2, 3} per iteration (+16 B/px of HBM traffic, quoted as `actual_bytes_per_launch`)")
@@ -148,6 +192,8 @@ def main():
     ap.add_argument("--cpu-chains", type=int, default=4)
     ap.add_argument("--cpu-iters", type=int, default=20)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
     if args.config == 2:
         args.size, args.chains, args.prior = 256, 128, "l2"
     elif args.config == 5:
@@ -248,13 +294,14 @@ def main():
                 reduce_fn(smp)
                 collective = f"torch.distributed all-reduce of the packed accumulators (C-ABI collective unavailable: {exc})"
         smp.reset_moments()
-    # one HIP-event pair per step-kernel launch (the roofline leg) -- except on small configurations, where the two event records cost
+    # --full: one HIP-event pair per step-kernel launch (the roofline leg) -- except on small configurations, where the two event records cost
     # 6 us of a 40 us iteration (measured at 256 x 256 x 128) and would be what the bench measures: there the launch time is wall / steps
-    timed_launches = args.alg == "myula" and os.environ.get("LMC_BENCH_NO_TIMING") != "1" and H * W * C > (1 << 25)
+    timed_launches = args.full and args.alg == "myula" and os.environ.get("LMC_BENCH_NO_TIMING") != "1" and H * W * C > (1 << 25)
     # Round 3: `value` is measured as the sampler runs by default -- posterior-moment reductions on a side stream under the next step kernel --
-    # and the step kernel's own launch time (the roofline leg) in ONE MORE region of K steps after the timed ones, with per-launch HIP events
+    # and (--full) the step kernel's own launch time (the roofline leg) in ONE MORE region of K steps after the timed ones, with per-launch HIP events
     # switched on, which also takes the reductions back in line so that the kernel is timed alone.
     regions = []                                     # (elapsed s of K steps, step-kernel ms summed over its launches, launches)
+    job_moments = None
     for _ in range(max(1, args.repeats)):
         if not args.no_moments:
             smp.reset_moments()
@@ -262,7 +309,7 @@ def main():
         t0 = time.perf_counter()
         smp.step(args.steps)
         if use_dist and not args.no_moments:
-            s1, s2, cnt = reduce_fn(smp)                     # RCCL over xGMI: posterior mean/var accumulators of the whole job
+            job_moments = reduce_fn(smp)                     # RCCL over xGMI: posterior mean/var accumulators of the whole job
         sync_all()
         el = time.perf_counter() - t0
         if use_dist:
@@ -272,6 +319,10 @@ def main():
         regions.append((el, el * 1e3, args.steps))   # ULPDA / MYMALA are sequences of launches per iteration, small configurations are not event-timed: the whole iteration
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     elapsed, kern_ms, launches = regions[order[len(order) // 2]]          # the median region
+    if args.dump_outputs and rank == 0:              # before the roofline leg below steps the chains further
+        if not args.no_moments and job_moments is None:
+            job_moments = smp.moments()
+        dump_outputs(args.dump_outputs, smp, job_moments)
     if timed_launches:           # the roofline leg: the same K steps once more, every step-kernel launch between its own pair of HIP events
         smp.enable_timing(True)
         sync_all()
@@ -281,41 +332,7 @@ def main():
         smp.enable_timing(False)
 
     if rank == 0:
-        # HBM bytes per launch from the committed rocprofv3 PMC passes (they cannot be collected inside this process);
-        # only quoted when the profile is of this kernel on this workload
-        traffic, valu = None, None
-        want = {"H": H, "W": W, "C": C, "prior": args.prior, "data": args.data, "tv_iters": args.tv_iters, "ncvx": args.ncvx}
-        if args.blur_k != 5:
-            want["blur_k"] = args.blur_k
-        if args.tv_rtol:
-            want["tv_rtol"] = args.tv_rtol
-        if args.ncvx_rtol:
-            want["ncvx_rtol"] = args.ncvx_rtol
-        if args.tv_warm:
-            want["tv_warm"] = True
-        if args.tv_lagged:
-            want["tv_lagged"] = True
-        counters_from = None
-        src_hash = kernel_source_hash()
-        try:             # the newest committed counters of this kernel on this workload -- only while the kernel sources are the ones they were taken on
-            for ent in json.load(open(os.path.join(ROOT, "profiles", "r03_counters.json")))["entries"]:
-                if ent["workload"] == want and ent["kernel"] == smp.kernel_name and traffic is None and ent.get("source_hash") == src_hash:
-                    traffic = ent["traffic_bytes_per_launch"]
-                    counters_from = {"file": ent.get("source"), "source_hash": ent.get("source_hash"), "commit": ent.get("commit")}
-                    if "valu" in ent:
-                        valu = dict(ent["valu"], source=ent.get("source"))
-        except Exception:
-            pass
-        peak_measured = None
-        if not args.no_hbm_probe:
-            import ctypes
-            g = ctypes.c_float()
-            la._capi.check(la._dev.lib().lmc_hbm_copy_probe(1 << 30, 3, ctypes.byref(g), None))     # 1 GiB read + 1 GiB written, as a state pass
-            peak_measured = float(g.value)
         value = C * world * args.steps / elapsed
-        per_launch_ms = kern_ms / launches
-        its_per_launch = args.steps / launches if timed_launches else 1.0      # 2 where a launch advances every chain by two iterations
-        achieved = BYTES_PER_PIXEL_STEP * H * W * C * its_per_launch / (per_launch_ms * 1e-3) / 1e9
         prior_desc = (f"isotropic TV prox K={args.tv_iters}{' warm-dual' if args.tv_warm else ''}{' lagged output' if args.tv_lagged else ''}{f' early exit rtol={args.tv_rtol:g}' if args.tv_rtol else ''} (tau_reg={tau_reg})" if args.prior == "tv"
                       else f"{args.prior} prior")
         out = {
@@ -340,12 +357,49 @@ def main():
                             + ("no moments" if args.no_moments else f"posterior moments every {args.thin} it"),
                 "image": [H, W], "chains_per_gpu": C, "chains_total": C * world, "tv_iters": args.tv_iters,
                 "sampler": "MYULA (algs.py:477-587)" if args.alg == "myula" else "MYMALA (Metropolis-adjusted MYULA, generalises prox_lmc.py:134-158)" if args.alg == "mymala" else f"ULPDA (algs.py:295-474), implicit step by CG: at most {args.cg_iters} iterations, stops at |r| <= 1e-6 |b| for every chain (the reference solver's rule, algs.py:250)", "parallelism": f"chains sharded x{world}",
-                "moment_reductions": ("none" if args.no_moments else "every kept iterate, on a side stream under the next step kernel (lmc_sampler_step default; "
-                                      "roofline.launch_ms is measured in a separate event-timed region with the reductions in line, i.e. the kernel alone)"),
+                "moment_reductions": ("none" if args.no_moments else "every kept iterate, on a side stream under the next step kernel (lmc_sampler_step default"
+                                      + ("; roofline.launch_ms is measured in a separate event-timed region with the reductions in line, i.e. the kernel alone)"
+                                         if args.full else ")")),
                 "iterations_per_s": args.steps / elapsed,
                 "collective": collective,
             },
-            "roofline": {
+        }
+        if args.full:
+            # HBM bytes per launch from the committed rocprofv3 PMC passes (they cannot be collected inside this process);
+            # only quoted when the profile is of this kernel on this workload
+            traffic, valu = None, None
+            want = {"H": H, "W": W, "C": C, "prior": args.prior, "data": args.data, "tv_iters": args.tv_iters, "ncvx": args.ncvx}
+            if args.blur_k != 5:
+                want["blur_k"] = args.blur_k
+            if args.tv_rtol:
+                want["tv_rtol"] = args.tv_rtol
+            if args.ncvx_rtol:
+                want["ncvx_rtol"] = args.ncvx_rtol
+            if args.tv_warm:
+                want["tv_warm"] = True
+            if args.tv_lagged:
+                want["tv_lagged"] = True
+            counters_from = None
+            src_hash = kernel_source_hash()
+            try:             # the newest committed counters of this kernel on this workload -- only while the kernel sources are the ones they were taken on
+                for ent in json.load(open(os.path.join(ROOT, "profiles", "r03_counters.json")))["entries"]:
+                    if ent["workload"] == want and ent["kernel"] == smp.kernel_name and traffic is None and ent.get("source_hash") == src_hash:
+                        traffic = ent["traffic_bytes_per_launch"]
+                        counters_from = {"file": ent.get("source"), "source_hash": ent.get("source_hash"), "commit": ent.get("commit")}
+                        if "valu" in ent:
+                            valu = dict(ent["valu"], source=ent.get("source"))
+            except Exception:
+                pass
+            peak_measured = None
+            if not args.no_hbm_probe:
+                import ctypes
+                g = ctypes.c_float()
+                la._capi.check(la._dev.lib().lmc_hbm_copy_probe(1 << 30, 3, ctypes.byref(g), None))     # 1 GiB read + 1 GiB written, as a state pass
+                peak_measured = float(g.value)
+            per_launch_ms = kern_ms / launches
+            its_per_launch = args.steps / launches if timed_launches else 1.0      # 2 where a launch advances every chain by two iterations
+            achieved = BYTES_PER_PIXEL_STEP * H * W * C * its_per_launch / (per_launch_ms * 1e-3) / 1e9
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": smp.kernel_name,
                 "achieved": achieved,
@@ -366,12 +420,12 @@ def main():
                 # (SQ_ACTIVE_INST_VALU quad-cycles x 4 / (SIMDs x kernel cycles), profiles/): ~1 means VALU-issue bound
                 "valu": valu,
                 "limiter": ("valu" if (valu and valu.get("busy_frac", 0) > 0.6 and achieved / HBM_PEAK_GBS < 0.3) else "hbm"),
-            },
-        }
-        if args.tv_warm:      # the un-fused variant reports its ACTUAL bytes beside the algorithmic 8 B/px
+            }
+        if args.tv_warm:
+            out["config"]["tv_warm"] = True
+        if args.full and args.tv_warm:      # the un-fused variant reports its ACTUAL bytes beside the algorithmic 8 B/px
             out["roofline"]["actual_bytes_per_launch"] = (BYTES_PER_PIXEL_STEP + 16) * H * W * C
             out["roofline"]["actual_gbs"] = (BYTES_PER_PIXEL_STEP + 16) * H * W * C / (per_launch_ms * 1e-3) / 1e9
-            out["config"]["tv_warm"] = True
         if args.tv_rtol and args.prior == "tv" and args.alg == "myula":
             try:
                 ps, rr = smp.tv_exit_stats("prior")
@@ -386,14 +440,14 @@ def main():
             out["config"]["ncvx_exit"] = {"passes_histogram_last_iteration": pc.tolist(), "reruns_after_round_1_2_3_4": rr}
         headline = (args.prior == "tv" and args.alg == "myula" and args.ncvx == "none" and args.data == "blur" and args.tv_iters == 10 and not args.tv_warm
                     and not args.tv_lagged and H == 512 and W == 512)
-        if headline and not args.tv_rtol:
+        if args.full and headline and not args.tv_rtol:
             # what binds the K = 10 kernel is the vector ALU, not HBM: the bound of ITS instruction stream (VALU issue slots from the counters)
             out["roofline"]["valu_bound_ms"] = {
                 "perfectly_balanced": 1.16 * C / 1024.0, "whole_waves_on_simds": 1.29 * C / 1024.0,
                 "how": "SQ_ACTIVE_INST_VALU (4-cycle issue slots) of the shipped kernel and of free-running single-role builds (profiles/r03_pipe_role_counters.txt): "
                        "per tick L 165, T1 159, T2..T5 190.5 each, C 52, N 163 = 1281 slots per CU; 320 per SIMD (541 ns at 2.37 GHz) if it could be split evenly; with "
                        "whole waves on SIMDs the busiest pair (L beside a two-stage TV wave, whatever the pairing) carries 355.5 (600 ns); x 536 ticks x 4 rounds of 256 workgroups"}
-        if headline and not args.tv_rtol and world == 1 and os.environ.get("LMC_BENCH_AS_CONFIGURED", "1") != "0":
+        if args.full and headline and not args.tv_rtol and world == 1 and os.environ.get("LMC_BENCH_AS_CONFIGURED", "1") != "0":
             # beside the headline (fixed K = 10 passes): the same chain AS THE REFERENCE IS CONFIGURED -- pyproximal.TV's default rtol = 1e-4, which
             # prox_lmc_deconv.py:122 leaves in force; the exit is decided on the device, chain by chain.  60 warm-up iterations: the pass counts
             # fall 10 -> 4 over the first ~30 iterations from x0 = 0, every change a re-run of the chains concerned.
@@ -416,7 +470,7 @@ def main():
         if args.alg == "mymala":
             out["config"]["acceptance_rate_mean"] = float(smp.acceptance_rate().mean())
             out["config"]["tau_scale"] = args.tau_scale
-        if world == 1 and not args.no_cpu_baseline and args.alg == "myula" and args.ncvx == "none" and not args.tv_warm:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.alg == "myula" and args.ncvx == "none" and not args.tv_warm:
             oprior = {"tv": {"kind": "tv", "sigma": tau_reg, "niter": args.tv_iters - (1 if args.tv_lagged else 0), "t": gamma, "rtol": args.tv_rtol},
                       "l2": {"kind": "l2", "sigma": 0.05, "t": gamma}, "l1": {"kind": "l1", "sigma": tau_reg, "t": gamma},
                       "haar": {"kind": "haar", "sigma": tau_reg, "t": gamma}}[args.prior]

@@ -3,7 +3,7 @@ import sys, json, subprocess, os
 for (H, W, C) in [(512, 512, 1024), (512, 256, 2048), (512, 128, 4096), (512, 64, 8192)]:
     for v in ["split", "stream"]:
         env = dict(os.environ, LMC_VARIANT=v)
-        out = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-moments",
+        out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-moments",
                               "--size", str(H), "--width", str(W), "--chains", str(C)], env=env, capture_output=True, text=True)
         try:
             d = json.loads(out.stdout.strip().splitlines()[-1])

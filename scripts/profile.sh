@@ -15,12 +15,12 @@ export LMC_MOMENTS_OVERLAP=${LMC_MOMENTS_OVERLAP:-0}
 args="--steps 10 --warmup 2 --repeats 1 --no-cpu-baseline --no-hbm-probe $*"
 targs="--steps 60 --warmup 10 --repeats 1 --no-cpu-baseline --no-hbm-probe $*"   # long enough for clocks to settle: the average must agree with bench.py
 cd $root
-rocprofv3 --kernel-trace --stats -d $out/trace --output-format csv -- python3 bench.py $targs > $out/bench_trace.json 2> $out/trace.log
+rocprofv3 --kernel-trace --stats -d $out/trace --output-format csv -- python3 bench.py --full $targs > $out/bench_trace.json 2> $out/trace.log
 for pass in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" \
             "SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_INST_CYCLES_SALU SQ_LDS_BANK_CONFLICT" \
             "FETCH_SIZE GRBM_GUI_ACTIVE" "WRITE_SIZE GRBM_COUNT"; do
   name=$(echo $pass | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --pmc $pass -d $out/pmc_$name --output-format csv -- python3 bench.py $args > /dev/null 2> $out/pmc_$name.log
+  rocprofv3 --pmc $pass -d $out/pmc_$name --output-format csv -- python3 bench.py --full $args > /dev/null 2> $out/pmc_$name.log
 done
 python3 - $out "$tag" "$*" <<'PY' | tee $out/summary.txt
 import csv, glob, sys, os, collections, json

@@ -10,5 +10,5 @@ objs=$(ls build/obj/*.o | grep -v lmc_step_pipe.o)
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $d/liblmc_atomi.so $objs $d/pipe.o -ldl || exit 1
 export LMC_ATOMI_LIB=$d/liblmc_atomi.so
 timeout -k 10 300 python -m pytest tests/test_gpu_pipe.py -m gpu -q -x > $out/pytest.log 2>&1; echo "$tag pytest rc=$? $(tail -1 $out/pytest.log)"
-timeout -k 10 200 python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-hbm-probe > $out/bench.json 2> $out/bench.err
+timeout -k 10 200 python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-hbm-probe > $out/bench.json 2> $out/bench.err
 python -c "import json;d=json.load(open('$out/bench.json'));print('$tag', 'launch_ms', round(d['roofline']['launch_ms'],4), 'ms/step', [round(x,4) for x in d['ms_per_step_all']])"

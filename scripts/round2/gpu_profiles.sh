@@ -23,5 +23,5 @@ else
 fi
 for t in $tags; do echo "=== $t"; head -6 gpurun_out/prof_r02_$t/summary.txt | cut -c1-200; grep -E "VALU busy|FETCH_SIZE|WRITE_SIZE" gpurun_out/prof_r02_$t/summary.txt | head -8; done
 if [ $part = a ]; then
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline | python -c "import json,sys; d=json.load(sys.stdin); print('peak_measured', d['roofline']['peak_measured'], 'launch_ms', d['roofline']['launch_ms'])"
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline | python -c "import json,sys; d=json.load(sys.stdin); print('peak_measured', d['roofline']['peak_measured'], 'launch_ms', d['roofline']['launch_ms'])"
 fi

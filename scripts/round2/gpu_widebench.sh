@@ -2,7 +2,7 @@
 # einstein-size (667 x 877, prox_lmc_deconv.py:44-46) and 1024 x 1024 images: fast kernels against the previous fallbacks
 set -e
 o=gpurun_out/r02wide; mkdir -p $o
-run() { tag=$1; shift; timeout -k 10 300 python bench.py --no-hbm-probe --no-cpu-baseline --steps 30 --warmup 5 "$@" > $o/$tag.json 2> $o/$tag.err; python - $o/$tag.json $tag <<'PY'
+run() { tag=$1; shift; timeout -k 10 300 python bench.py --full --no-hbm-probe --no-cpu-baseline --steps 30 --warmup 5 "$@" > $o/$tag.json 2> $o/$tag.err; python - $o/$tag.json $tag <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]
 print(sys.argv[2], "ms/step %.3f" % d["ms_per_step"], "launch_ms", r.get("launch_ms"), r.get("kernel"), "frac %.3f" % (r.get("frac") or 0))

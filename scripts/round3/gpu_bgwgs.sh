@@ -2,7 +2,7 @@
 # moment reduction beside an HBM-heavy step kernel (single rows launches): in line, and on the side stream with 256 .. 2048 / full-speed workgroups
 set -o pipefail
 out=gpurun_out/r3_bgwgs; mkdir -p $out
-B="python bench.py --steps 60 --warmup 20 --no-hbm-probe --no-cpu-baseline --prior l2"
+B="python bench.py --full --steps 60 --warmup 20 --no-hbm-probe --no-cpu-baseline --prior l2"
 for k in 5 7; do
   P=""; [ $k = 5 ] && P="LMC_ROWS_PAIR=0"
   env $P LMC_MOMENTS_OVERLAP=0 $B --blur-k $k > $out/k${k}_inline.json 2> $out/k${k}_inline.err || exit 1

@@ -2,7 +2,7 @@
 # round 3, first GPU call: the reference's 6x6 / 7x7 model blurs and config 5 as specified, before any kernel change
 set -o pipefail
 out=gpurun_out/r3_blurk; mkdir -p $out
-B="python bench.py --steps 40 --warmup 10 --no-cpu-baseline"
+B="python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline"
 for k in 5 6 7; do
   $B --blur-k $k > $out/tv_k$k.json 2> $out/tv_k$k.err || exit 1
   $B --blur-k $k --prior l2 > $out/l2_k$k.json 2> $out/l2_k$k.err || exit 1

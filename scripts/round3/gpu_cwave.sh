@@ -5,7 +5,7 @@ out=gpurun_out/r3_cwave; mkdir -p $out
 timeout -k 10 600 python -m pytest tests/test_gpu_pipe.py tests/test_gpu_parity.py tests/test_gpu_rtol.py tests/test_gpu_ncvx.py tests/test_gpu_mymala.py tests/test_gpu_wide.py -x -q -m gpu > $out/tests.log 2>&1; rc=$?
 tail -5 $out/tests.log
 [ $rc -eq 0 ] || exit $rc
-B="python bench.py --steps 60 --warmup 20 --no-hbm-probe --no-cpu-baseline"
+B="python bench.py --full --steps 60 --warmup 20 --no-hbm-probe --no-cpu-baseline"
 LMC_MOMENTS_OVERLAP=0 $B > $out/tv_inline.json 2> $out/tv_inline.err || exit 1
 $B > $out/tv.json 2> $out/tv.err || exit 1
 LMC_BENCH_AS_CONFIGURED=0 $B --ncvx mc > $out/mc.json 2> $out/mc.err || exit 1

@@ -5,7 +5,7 @@ out=gpurun_out/r3_full; mkdir -p $out
 timeout -k 10 1000 python -m pytest tests -x -q -m gpu --durations=15 > $out/tests.log 2>&1; rc=$?
 tail -30 $out/tests.log
 [ $rc -eq 0 ] || exit $rc
-B="python bench.py --steps 40 --warmup 60 --no-cpu-baseline --no-hbm-probe"
+B="python bench.py --full --steps 40 --warmup 60 --no-cpu-baseline --no-hbm-probe"
 $B > $out/tv_fixed.json 2> $out/tv_fixed.err || exit 1
 $B --tv-rtol 1e-4 > $out/tv_rtol.json 2> $out/tv_rtol.err || exit 1
 $B --ncvx mc > $out/mc.json 2> $out/mc.err || exit 1

@@ -5,7 +5,7 @@ out=gpurun_out/r3_full2; mkdir -p $out
 timeout -k 10 1000 python -m pytest tests -x -q -m gpu > $out/tests.log 2>&1; rc=$?
 tail -8 $out/tests.log
 [ $rc -eq 0 ] || exit $rc
-B="python bench.py --steps 60 --warmup 20 --no-cpu-baseline --no-hbm-probe"
+B="python bench.py --full --steps 60 --warmup 20 --no-cpu-baseline --no-hbm-probe"
 $B > $out/tv.json 2> $out/tv.err || exit 1
 LMC_MOMENTS_OVERLAP=0 $B > $out/tv_inline.json 2> $out/tv_inline.err || exit 1
 $B --prior l2 > $out/l2.json 2> $out/l2.err || exit 1

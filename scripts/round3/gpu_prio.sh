@@ -2,7 +2,7 @@
 # s_setprio of the pipe kernel's roles (L C T N) after the new role pairing: A = 3 3 1 0 (shipped), B 3 3 2 0, C 3 3 1 1, D 2 3 1 0, E 3 2 1 0, F 0 0 0 0, G 3 3 0 0, H 1 1 3 0
 set -o pipefail
 out=gpurun_out/r3_prio; mkdir -p $out
-B="python bench.py --steps 40 --warmup 10 --no-hbm-probe --no-cpu-baseline"
+B="python bench.py --full --steps 40 --warmup 10 --no-hbm-probe --no-cpu-baseline"
 export LMC_BENCH_AS_CONFIGURED=0 LMC_MOMENTS_OVERLAP=0
 for rep in 1 2; do
 for v in A B C D E F G H; do

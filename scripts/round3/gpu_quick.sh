@@ -5,7 +5,7 @@ timeout -k 10 600 python -m pytest tests/test_gpu_pipe.py tests/test_gpu_parity.
 tail -5 $out/tests.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 600 python -m pytest tests/test_gpu_r4.py -x -q -m gpu -s -k "configured or north_star" 2>&1 | grep -E "R4|passed|failed" | tee $out/r4.log
-B="python bench.py --steps 60 --warmup 20 --no-hbm-probe"
+B="python bench.py --full --steps 60 --warmup 20 --no-hbm-probe"
 LMC_MOMENTS_OVERLAP=0 $B --no-cpu-baseline > $out/tv_inline.json 2> $out/tv_inline.err || exit 1
 $B > $out/tv.json 2> $out/tv.err || exit 1
 $B --no-cpu-baseline --ncvx mc --tv-rtol 1e-4 --warmup 60 > $out/mc_rtol.json 2> $out/mc_rtol.err || exit 1

@@ -11,7 +11,7 @@ for v in base NB L C N T1 T2 T5 P04 P15 P26 P37; do
               "SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_INST_CYCLES_SALU SQ_LDS_BANK_CONFLICT" \
               "GRBM_GUI_ACTIVE"; do
     i=$((i+1))
-    rocprofv3 --pmc $pass -d $out/${v}_p$i --output-format csv -- python3 bench.py $args > /dev/null 2> $out/${v}_p$i.log || { echo "fail $v $i"; exit 1; }
+    rocprofv3 --pmc $pass -d $out/${v}_p$i --output-format csv -- python3 bench.py --full $args > /dev/null 2> $out/${v}_p$i.log || { echo "fail $v $i"; exit 1; }
   done
   echo "$v done"
 done

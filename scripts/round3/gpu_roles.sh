@@ -3,7 +3,7 @@
 # which role, alone or with the wave it shares a SIMD with, needs how long for its 4 x 536 ticks.  Variants are built on the host into build/var/.
 set -o pipefail
 out=gpurun_out/r3_roles; mkdir -p $out
-B="python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-hbm-probe"
+B="python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline --no-hbm-probe"
 export LMC_BENCH_AS_CONFIGURED=0 LMC_MOMENTS_OVERLAP=0
 $B > $out/base.json 2> $out/base.err || exit 1
 for v in NB LCN TV L C N T1 P04 P15 P26 P37; do

@@ -2,7 +2,7 @@
 # rows kernel at 7 taps x 8 pixels per lane: prefetch depths that fit the register file (A: PF 1 / y 1 ahead, B: PF 1 / y 0, C: PF 2 / y 0)
 set -o pipefail
 out=gpurun_out/r3_rows7; mkdir -p $out
-B="python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-hbm-probe"
+B="python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-hbm-probe"
 for v in A B C; do
   export LMC_ATOMI_LIB=$PWD/build/var/liblmc_atomi_$v.so
   for k in 6 7; do

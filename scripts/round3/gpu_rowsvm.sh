@@ -5,7 +5,7 @@ out=gpurun_out/r3_rowsvm; mkdir -p $out
 timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_ulpda.py tests/test_gpu_wide.py tests/test_gpu_eprox_prior.py tests/test_gpu_haar.py tests/test_gpu_epsg_array.py tests/test_gpu_abi2.py -x -q -m gpu > $out/tests.log 2>&1; rc=$?
 tail -4 $out/tests.log
 [ $rc -eq 0 ] || exit $rc
-B="python bench.py --steps 60 --warmup 20 --no-hbm-probe --no-cpu-baseline"
+B="python bench.py --full --steps 60 --warmup 20 --no-hbm-probe --no-cpu-baseline"
 LMC_ROWS_PAIR=0 $B --prior l2 > $out/l2_single.json 2> $out/l2_single.err || exit 1
 $B --prior l2 > $out/l2_pair.json 2> $out/l2_pair.err || exit 1
 $B --prior l2 --blur-k 7 > $out/l2_k7.json 2> $out/l2_k7.err || exit 1

@@ -2,7 +2,7 @@
 # role -> SIMD mapping of the per-chain-exit kernel for chains with <= 4 live stages: M0 (shipped) against two others (build/var, -DLMC_RT_MAP)
 set -o pipefail
 out=gpurun_out/r3_rtmap; mkdir -p $out
-B="python bench.py --steps 60 --warmup 60 --no-cpu-baseline --no-hbm-probe --tv-rtol 1e-4"
+B="python bench.py --full --steps 60 --warmup 60 --no-cpu-baseline --no-hbm-probe --tv-rtol 1e-4"
 export LMC_BENCH_AS_CONFIGURED=0
 for rep in 1 2; do
 for v in M0 M1 M2; do

@@ -5,7 +5,7 @@ out=gpurun_out/r3_rtol; mkdir -p $out
 timeout -k 10 600 python -m pytest tests/test_gpu_rtol.py tests/test_gpu_abi2.py -x -q -m gpu > $out/tests.log 2>&1; rc=$?
 tail -15 $out/tests.log
 [ $rc -eq 0 ] || exit $rc
-B="python bench.py --steps 40 --warmup 20 --no-cpu-baseline"
+B="python bench.py --full --steps 40 --warmup 20 --no-cpu-baseline"
 $B > $out/tv_fixed.json 2> $out/tv_fixed.err || exit 1
 $B --tv-rtol 1e-4 > $out/tv_rtol.json 2> $out/tv_rtol.err || exit 1
 $B --blur-k 7 --tv-rtol 1e-4 > $out/tv_rtol_k7.json 2> $out/tv_rtol_k7.err || exit 1

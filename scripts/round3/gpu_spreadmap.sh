@@ -1,7 +1,7 @@
 #!/bin/bash
 set -o pipefail
 out=gpurun_out/r3_spreadmap; mkdir -p $out
-B="python bench.py --steps 60 --warmup 60 --no-hbm-probe --no-cpu-baseline --tv-rtol 1e-4"
+B="python bench.py --full --steps 60 --warmup 60 --no-hbm-probe --no-cpu-baseline --tv-rtol 1e-4"
 export LMC_BENCH_AS_CONFIGURED=0
 for rep in 1 2; do
 for v in S3 S4 S5; do
