@@ -158,7 +158,7 @@ typedef struct lmc_problem {
    *      closed-form prior, mask + Haar; two Chebyshev iterations of the implicit step); 1 = always one; 2 = wherever covered (tests).
    *  moments_overlap  (LMC_MOMENTS_OVERLAP): posterior-moment reductions on a side stream under the next step kernel: 0 = on (default), 1 = on, -1 = off.
    *  moments_bg_workgroups  (LMC_MOMENTS_BG_WGS): workgroups of that background reduction, 0 = by size.
-   *  graph_replay  (LMC_GRAPH): 1 = replay captured hipGraphs of 8 iterations. */
+   *  graph_replay: 0 or 1, no effect (the hipGraph replay it selected was removed; the field keeps the layout). */
   int32_t iterations_per_launch;
   int32_t moments_overlap;
   int32_t moments_bg_workgroups;

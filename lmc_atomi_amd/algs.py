@@ -64,7 +64,7 @@ class MYULASampler:
         if tv_warm is not None:
             opts["tv_warm"] = bool(tv_warm)
         # launch policy of this sampler (lmc_problem, ABI 3): dict with any of iterations_per_launch (0 auto / 1 / 2), moments_overlap (0 auto /
-        # 1 / -1), moments_bg_workgroups, graph_replay, tv_exit_path (1 = the pass-by-pass early exit)
+        # 1 / -1), moments_bg_workgroups, tv_exit_path (1 = the pass-by-pass early exit); graph_replay is accepted and has no effect
         opts.update(policy or {})
         self.epsg = epsg
         if np.asarray(epsg).size > 1:      # array-valued epsg (algs.py:509,539-542): the prox parameter epsg * gamma is an array that the prox broadcasts

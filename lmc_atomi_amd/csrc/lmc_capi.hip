@@ -77,7 +77,7 @@ struct Problem {
   float tv_rtol = 0.f;      // > 0: pyproximal.TV's per-image early exit (device path tv_prox_rt, or the pass-by-pass path tv_prox_rtol)
   float ncvx_rtol = 0.f;    // > 0: the same for the inner prox of the ME-TV term (device path only)
   int tv_exit_path = 0;     // 1: always pass by pass
-  int iters_per_launch = 0, moments_overlap = 0, moments_bg_wgs = 0, graph_replay = 0;   // launch policy (0 = library decides; fixed at sampler creation)
+  int iters_per_launch = 0, moments_overlap = 0, moments_bg_wgs = 0;   // launch policy (0 = library decides; fixed at sampler creation)
   int cheb_pair = 1;        // two Chebyshev iterations per launch: 0 never, 1 where they pay, 2 wherever covered
   int eprox_kind = 0, eprox_mask = 0;   // LMC_PRIOR_EPROX: closed form, which parameters scale with the prox parameter
   float eprox_p0 = 0.f, eprox_p1 = 0.f;
@@ -277,7 +277,7 @@ int load_problem(const lmc_problem* p, Problem& q) {
   if (p->moments_overlap < -1 || p->moments_overlap > 1) return fail(LMC_E_INVALID, "moments_overlap must be 0 (auto), 1 (on) or -1 (off)");
   if (p->moments_bg_workgroups < 0 || p->graph_replay < 0 || p->graph_replay > 1) return fail(LMC_E_INVALID, "bad moments_bg_workgroups / graph_replay");
   q.iters_per_launch = p->iterations_per_launch; q.moments_overlap = p->moments_overlap;
-  q.moments_bg_wgs = p->moments_bg_workgroups; q.graph_replay = p->graph_replay;
+  q.moments_bg_wgs = p->moments_bg_workgroups;   // (graph_replay: validated, no effect)
   {
     const char* e = getenv("LMC_CHEB_PAIR");
     const char* e2 = getenv("LMC_ITERS_PER_LAUNCH");
@@ -841,6 +841,10 @@ int tv_prior_rt_mode(const Problem& q, const lmc::StepArgs& A_probe, float pt) {
 }
 
 int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+
+// batches of side-stream moment reductions one lmc_sampler_step call keeps in flight (the default policies have two at a time; one more
+// first waits for the oldest)
+constexpr int kSideBatches = 4;
 }  // namespace
 
 struct lmc_sampler {
@@ -869,7 +873,6 @@ struct lmc_sampler {
   int pol_blockpair = 1;     // 0 / 1: two or four iterations per launch on the block kernel
   int pol_overlap = 0;       // 0 by size, 1 on, -1 off
   int pol_bg_wgs = -1;       // workgroups of the background reduction, -1 by size
-  int pol_graph = 0;
   int pol_side_lowprio = 1;
   bool pol_ulpda_dual_rhs = false;   // ULPDA, opt-in experiment (LMC_ULPDA_DUAL_RHS=1 at creation): dual update fused with the next right-hand side
   Problem prob;
@@ -883,12 +886,8 @@ struct lmc_sampler {
   uint64_t count = 0;
   float* x[2] = {nullptr, nullptr};
   float* xspare = nullptr;    // third state array of the two-iterations-per-launch MYULA path (allocated at its first use)
-  // Moment reductions of the pair launches on the side stream: the iterate in between goes to one of two arrays of its own (a pair launch two
-  // launches later is the first that may write where launch n's reductions read: ev_pair[n & 1] orders that)
+  // kept iterates in between of pair launches whose reductions run on the side stream: arrays of their own, alternating by launch
   float* xmid[2] = {nullptr, nullptr};
-  hipEvent_t ev_pair[2] = {nullptr, nullptr};
-  bool pair_pending[2] = {false, false};
-  uint64_t pair_n = 0;
   int cur = 0;
   double* s1 = nullptr;
   double* s2 = nullptr;
@@ -900,19 +899,10 @@ struct lmc_sampler {
   int* flag = nullptr;
   unsigned long long* nacc = nullptr;
   bool mala_fresh = false;               // mx / U match x[cur]
-  // moment reductions on a side stream, overlapping the next step kernel (HBM-bound reduction under a VALU-bound step kernel)
+  // moment reductions on a side stream, overlapping the next step kernel (HBM-bound reduction under a VALU-bound step kernel); which of them are
+  // still running is known only inside one lmc_sampler_step call (SideMoments), which joins them all before it returns
   hipStream_t side = nullptr;
-  hipEvent_t ev_step = nullptr;              // "the step that wrote x[cur] is done" (recorded on the caller's stream)
-  hipEvent_t ev_mom[2] = {nullptr, nullptr}; // "the reduction that reads x[i] is done" (recorded on the side stream)
-  bool mom_pending[2] = {false, false};
-  // hipGraph replay of kGraphIters iterations at a time (small configurations, where launch gaps and the serial moment reduction
-  // are a large part of an iteration): step kernels on the caller's stream, the moment reduction of iteration k on a captured side
-  // branch under the step kernel of iteration k + 1; the Philox iteration word comes from device memory (StepArgs.iter_dev)
-  hipGraphExec_t gexec[2] = {nullptr, nullptr};   // by `cur` at the start of the block of iterations
-  uint32_t* iter_dev = nullptr;
-  hipStream_t gmain = nullptr, gside = nullptr;   // capture streams (the caller's stream may be the legacy default stream, which cannot capture)
-  std::vector<hipEvent_t> gev;
-  bool plain_done = false;      // at least one ordinary launch has happened (function attributes set, kernel known)
+  hipEvent_t side_ev[1 + kSideBatches] = {};   // [0]: "the launch is done" (caller's stream); [1 + i]: "batch i of reductions is done" (side stream)
   std::vector<hipEvent_t> ev;   // pairs (begin, end) around each step-kernel launch of the last step() call
   bool timing = false;
   bool timed = false;
@@ -1256,9 +1246,8 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     s->pol_blockpair = ipl == 1 ? 0 : (ipl == 2 ? 1 : (env_int("LMC_BLOCK_PAIR", 1) != 0));
     s->pol_overlap = q.moments_overlap ? q.moments_overlap : (getenv("LMC_MOMENTS_OVERLAP") ? (env_int("LMC_MOMENTS_OVERLAP", 0) ? 1 : -1) : 0);
     s->pol_bg_wgs = q.moments_bg_wgs > 0 ? q.moments_bg_wgs : env_int("LMC_MOMENTS_BG_WGS", -1);
-    s->pol_graph = q.graph_replay ? 1 : (env_int("LMC_GRAPH", 0) == 1);
     s->pol_side_lowprio = env_int("LMC_MOMENTS_SIDE_PRIO", 1) != 0;
-    if (q.prox_scale) { s->pol_pair = 0; s->pol_blockpair = 0; s->pol_graph = 0; }   // array-valued epsg: the prox is its own launch before every step
+    if (q.prox_scale) { s->pol_pair = 0; s->pol_blockpair = 0; }   // array-valued epsg: the prox is its own launch before every step
   }
   if (e == hipSuccess && s->prob.tv_warm) {
     lmc::StepArgs probe = s->base;
@@ -1310,15 +1299,8 @@ void lmc_sampler_destroy(lmc_sampler* s) {
   if (s->s2) (void)hipFree(s->s2);
   if (s->packed) (void)hipFree(s->packed);
   for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
-  for (hipEvent_t e : s->gev) (void)hipEventDestroy(e);
-  for (hipGraphExec_t g : s->gexec) if (g) (void)hipGraphExecDestroy(g);
-  if (s->gside) (void)hipStreamDestroy(s->gside);
-  if (s->gmain) (void)hipStreamDestroy(s->gmain);
-  if (s->iter_dev) (void)hipFree(s->iter_dev);
   if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }
-  if (s->ev_step) (void)hipEventDestroy(s->ev_step);
-  for (hipEvent_t e : s->ev_mom) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : s->ev_pair) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : s->side_ev) if (e) (void)hipEventDestroy(e);
   delete s;
 }
 
@@ -1357,6 +1339,19 @@ static int sampler_energies_at(lmc_sampler* s, const float* x, double* f_out_dev
   return LMC_OK;
 }
 
+// an iterate the posterior-moment accumulators keep: after burn-in, every thin-th
+static bool kept(const lmc_sampler* s, int64_t it) { return s->moments && it >= s->burn_in && (it - s->burn_in) % s->thin == 0; }
+
+// ME-TV: the inner prox of the Moreau-envelope term at A.x_in, which the fused step then takes as its extra gradient term
+static int me_tv_extra(lmc_sampler* s, lmc::StepArgs& A, hipStream_t st) {
+  if (s->prob.ncvx_kind != LMC_NCVX_ME_TV) return LMC_OK;
+  int rc = me_tv_prox(s->prob, A.x_in, s->extra, s->C, s->tvstate[0], s->tvstate[1], st, &s->rt_me);
+  if (rc) return rc;
+  A.extra = s->extra;
+  A.extra_coef = -s->prob.ncvx_lambda / s->prob.ncvx_gamma;
+  return LMC_OK;
+}
+
 // out = base update of `x_in` with the sampler's coefficients; noise_scale 0 gives the proposal mean m(x_in)
 static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool with_noise, const float* noise, uint32_t iteration,
                           hipStream_t st, const char** kname, double* f_out = nullptr, double* g_out = nullptr, bool* fused = nullptr) {
@@ -1378,110 +1373,207 @@ static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool 
   A.noise = noise;
   if (!with_noise) { A.s = 0.f; A.noise_mode = LMC_NOISE_NONE; A.noise = nullptr; }
   sanitize_pointers(A);
-  if (s->prob.ncvx_kind == LMC_NCVX_ME_TV) {   // inner prox of the Moreau-envelope term, then the fused step
-    int rc = me_tv_prox(s->prob, A.x_in, s->extra, s->C, s->tvstate[0], s->tvstate[1], st, &s->rt_me);
-    if (rc) return rc;
-    A.extra = s->extra;
-    A.extra_coef = -s->prob.ncvx_lambda / s->prob.ncvx_gamma;
-  }
+  int rc = me_tv_extra(s, A, st);   // inner prox of the Moreau-envelope term, then the fused step
+  if (rc) return rc;
   hipError_t e = launch_step(A, variant_of(s->prob), st, kname, s->tvstate[0], s->tvstate[1], s->pxbuf);
   if (e == hipErrorInvalidConfiguration) return fail(LMC_E_UNSUPPORTED, "no step-kernel variant covers this configuration");
   HIP_TRY(e);
   return LMC_OK;
 }
 
+// ---- MYULA steps ----------------------------------------------------------------------------------------------------------------
+// Posterior-moment reductions of one lmc_sampler_step call.  A kept iterate is reduced in line on the caller's stream, or on the sampler's
+// side stream under the launches that follow.  The side stream runs its batches in the order they were enqueued, so the pending batches form
+// a queue and waiting for one waits for every earlier one.  Three rules order them against the launches:
+//  - a launch that writes an array first waits for every pending batch that reads it, whatever that launch keeps;
+//  - an in-line reduction first waits for every pending batch (the accumulators are shared);
+//  - the call joins every pending batch before it returns: nothing is in flight between calls.
+struct SideMoments {
+  lmc_sampler* s;
+  hipStream_t st;             // the caller's stream
+  bool overlap;               // reductions may go to the side stream in this call
+  int bg_wgs;                 // workgroups of a side-stream reduction
+  const float* reads[kSideBatches][2] = {};   // by slot: the arrays the batch in that slot reads; its end event is s->side_ev[1 + slot]
+  int head = 0, n = 0;                        // pending batches: slots head .. head + n - 1 (mod kSideBatches), oldest first
 
-// ---- hipGraph replay of MYULA iterations (small configurations) -------------------------------------------------------------------
-constexpr int kGraphIters = 8;     // iterations per graph launch (even: the ping-pong buffers are back in place)
-
-static bool graph_wanted(const lmc_sampler* s) {
-  // Opt-in (lmc_problem.graph_replay / LMC_GRAPH=1, fixed when the sampler is created).  Measured on ROCm 7.2 / MI355X at BASELINE config 2 (256 x 256 x 128, rows kernel 25 us + reduction 15.6 us): plain
-  // launches 40.2 us per iteration -- the queue is never empty, there are no launch gaps to recover -- graph replay 42.0 us (the side branch
-  // does not run under the next step kernel); what does help is the reduction on a second HIP stream (LMC_MOMENTS_OVERLAP, default for small
-  // configurations): 37.1 us.  Kept because the replay is exact (tests/test_gpu_graph.py) and may pay on another runtime.
-  return s->pol_graph != 0;
-}
-
-// Captures kGraphIters iterations starting from buffer s->cur into an executable graph.
-static int build_graph(lmc_sampler* s) {
-  if (!s->iter_dev) {
-    HIP_TRY(hipMalloc(&s->iter_dev, sizeof(uint32_t)));
-    HIP_TRY(hipStreamCreateWithFlags(&s->gmain, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&s->gside, hipStreamNonBlocking));
-    s->gev.resize(2 * kGraphIters);
-    for (hipEvent_t& e : s->gev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipError_t wait_through(int i) {            // the caller's stream waits for pending batch i (0 = the oldest), hence for batches 0 .. i
+    const int slot = (head + i) % kSideBatches;
+    head = (slot + 1) % kSideBatches;
+    n -= i + 1;
+    return hipStreamWaitEvent(st, s->side_ev[1 + slot], 0);
   }
-  const bool mom = s->moments != 0;
-  int cur = s->cur;
-  hipStream_t st = s->gmain;           // nothing runs here: the launches below are recorded, the graph is replayed on the caller's stream
-  HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-  int rc = LMC_OK;
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < kGraphIters && e == hipSuccess; ++k) {
-    lmc::StepArgs A = s->base;
-    A.x_in = s->x[cur];
-    A.x_out = s->x[cur ^ 1];
-    A.iteration = (uint32_t)k;
-    A.iter_dev = s->iter_dev;
-    A.noise = nullptr;
-    sanitize_pointers(A);
-    if (mom && k >= 2) e = hipStreamWaitEvent(st, s->gev[2 * (k - 2) + 1], 0);     // this step overwrites what reduction k - 2 reads
-    const char* kname = nullptr;
-    if (e == hipSuccess) e = launch_step(A, variant_of(s->prob), st, &kname, s->tvstate[0], s->tvstate[1], s->pxbuf);
-    cur ^= 1;
-    if (mom && e == hipSuccess) {       // reduction of the new state on the side branch, under the next step kernel
-      e = hipEventRecord(s->gev[2 * k], st);
-      if (e == hipSuccess) e = hipStreamWaitEvent(s->gside, s->gev[2 * k], 0);
-      if (e == hipSuccess) e = lmc::launch_moments(s->x[cur], s->C, s->prob.H, s->prob.W, s->s1, s->s2, s->gside);
-      if (e == hipSuccess) e = hipEventRecord(s->gev[2 * k + 1], s->gside);
+  hipError_t before_write(const float* a, const float* b = nullptr) {   // the launch about to be enqueued writes a and b (b may be NULL)
+    for (int i = n - 1; i >= 0; --i)
+      for (const float* r : reads[(head + i) % kSideBatches])
+        if (r && (r == a || r == b)) return wait_through(i);
+    return hipSuccess;
+  }
+  hipError_t join() { return n ? wait_through(n - 1) : hipSuccess; }
+  // the kept iterates a and b (either may be NULL) that the launch just enqueued wrote: into the accumulators, beside later launches or in line
+  int keep(const float* a, const float* b, bool beside) {
+    if (!a && !b) return LMC_OK;
+    if (beside) {
+      if (n == kSideBatches) HIP_TRY(wait_through(0));
+      const int slot = (head + n) % kSideBatches;
+      HIP_TRY(hipEventRecord(s->side_ev[0], st));
+      HIP_TRY(hipStreamWaitEvent(s->side, s->side_ev[0], 0));
+      for (const float* x : {a, b})
+        if (x) HIP_TRY(lmc::launch_moments_bg(x, s->C, s->prob.H, s->prob.W, s->s1, s->s2, bg_wgs, s->side));
+      HIP_TRY(hipEventRecord(s->side_ev[1 + slot], s->side));
+      reads[slot][0] = a;
+      reads[slot][1] = b;
+      ++n;
+    } else {
+      HIP_TRY(join());
+      for (const float* x : {a, b})
+        if (x) HIP_TRY(lmc::launch_moments(x, s->C, s->prob.H, s->prob.W, s->s1, s->s2, st));
     }
+    s->count += (uint64_t)s->C * ((a ? 1 : 0) + (b ? 1 : 0));
+    return LMC_OK;
   }
-  if (mom && e == hipSuccess) {         // join: the last two reductions (the earlier ones were waited for by later steps)
-    for (int k = kGraphIters - 2; k < kGraphIters && e == hipSuccess; ++k) e = hipStreamWaitEvent(st, s->gev[2 * k + 1], 0);
-  }
-  if (e == hipSuccess) e = lmc::launch_bump_u32(s->iter_dev, (uint32_t)kGraphIters, st);
-  hipGraph_t graph = nullptr;
-  const hipError_t e2 = hipStreamEndCapture(st, &graph);       // always end the capture, also after a failed launch
-  if (e != hipSuccess || e2 != hipSuccess) {
-    if (graph) (void)hipGraphDestroy(graph);
-    rc = fail(LMC_E_HIP, "graph capture failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-    return rc;
-  }
-  hipGraphExec_t exec = nullptr;
-  e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  if (e != hipSuccess) return fail(LMC_E_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
-  s->gexec[s->cur] = exec;
-  return LMC_OK;
+};
+
+// The array of its own for a kept iterate in between whose reduction runs under the next launch (alternating by launch).
+static hipError_t xmid_array(lmc_sampler* s, float** out) {
+  float*& xm = s->xmid[s->last_launches & 1];
+  const hipError_t e = xm ? hipSuccess : hipMalloc(&xm, sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W);
+  *out = xm;
+  return e;
 }
 
-int lmc_sampler_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, void* stream) {
-  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
-  DeviceGuard dg(s->device);
-  if (s->kind == 2) {
-    if (n_iters < 0) return fail(LMC_E_INVALID, "n_iters < 0");
-    if (s->noise_mode == LMC_NOISE_INJECTED && !noise_dev && n_iters > 0)
-      return fail(LMC_E_INVALID, "noise_mode is INJECTED but noise_dev is NULL");
-    if (s->noise_mode != LMC_NOISE_INJECTED && noise_dev)
-      return fail(LMC_E_INVALID, "noise_dev given but noise_mode is not INJECTED");
-    if (s->iteration + n_iters > 0xFFFFFFFFLL) return fail(LMC_E_STATE, "iteration counter would exceed 32 bits");
-    return mymala_step(s, n_iters, noise_dev, S(stream));
+// The launch helpers below return the iterations they ran (0: they do not cover the next ones) or a negative lmc_status.
+
+// Two MYULA iterations per launch (lmc_step_rows_pair.hip) where that kernel covers the configuration and the launch is large enough for its
+// long bands: x_{k+2} goes to a third array (neighbouring bands re-read x_k), x_{k+1} is stored only when the moment accumulators keep it.
+// lmc_problem.iterations_per_launch / LMC_ROWS_PAIR: 0 = never, 2 = wherever covered (tests), default = where it pays (n_chains * H >= 2^17).
+static int myula_rows_pair(lmc_sampler* s, SideMoments& m, int left) {
+  if (!s->pol_pair || left < 2 || s->tvwarm[0] || s->rtmp || s->prob.ncvx_kind != LMC_NCVX_NONE ||
+      (variant_of(s->prob) != 0 && variant_of(s->prob) != 6) || (s->pol_pair != 2 && (long long)s->C * s->prob.H < (1 << 17)))
+    return 0;
+  lmc::StepArgs A = s->base;
+  A.x_in = s->x[s->cur];
+  A.iteration = (uint32_t)s->iteration;
+  A.noise = nullptr;
+  sanitize_pointers(A);
+  if (!lmc::rows_pair_supported(A)) return 0;
+  if (!s->xspare) HIP_TRY(hipMalloc(&s->xspare, sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W));
+  const bool keep_mid = kept(s, s->iteration), keep_out = kept(s, s->iteration + 1);
+  float* mid = keep_mid ? s->x[s->cur ^ 1] : nullptr;
+  if (keep_mid && m.overlap) HIP_TRY(xmid_array(s, &mid));
+  HIP_TRY(m.before_write(s->xspare, mid));
+  A.x_out = s->xspare;
+  if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches], m.st));
+  HIP_TRY(lmc::launch_step_rows_pair(A, mid, m.st));
+  if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches + 1], m.st));
+  s->kernel_name = "myula_step_rows_pair_kernel";
+  int rc = m.keep(mid, keep_out ? s->xspare : nullptr, m.overlap);
+  if (rc) return rc;
+  std::swap(s->x[s->cur], s->xspare);        // x[cur] = x_{k+2}; the array that held x_k is the spare now
+  s->iteration += 2;
+  ++s->last_launches;
+  return 2;
+}
+
+// Two iterations per launch on the register-block kernel (Haar prior, stencil-free data term: BASELINE config 5): the update never leaves a
+// thread's 8 x 8 block, so the second iteration runs on the block while it is on chip; x_{k+1} is written (in place, over x_k) only when the
+// moment accumulators keep it.  LMC_BLOCK_PAIR=0 turns it off.  Same arithmetic, same noise: bit-identical to two launches.
+static int myula_block_pair(lmc_sampler* s, SideMoments& m, int left) {
+  if (!s->pol_blockpair || left < 2 || s->tvwarm[0] || s->rtmp || s->prob.ncvx_kind != LMC_NCVX_NONE ||
+      (variant_of(s->prob) != 0 && variant_of(s->prob) != 5))
+    return 0;
+  lmc::StepArgs A = s->base;
+  A.x_in = s->x[s->cur];
+  A.x_out = s->x[s->cur ^ 1];
+  A.iteration = (uint32_t)s->iteration;
+  A.noise = nullptr;
+  sanitize_pointers(A);
+  if (!lmc::block_pair_supported(A)) return 0;
+  // four iterations on chip when none of the three iterates in between is kept (moments off, burn-in, thinning by >= 4)
+  const bool four = left >= 4 && !kept(s, s->iteration) && !kept(s, s->iteration + 1) && !kept(s, s->iteration + 2);
+  const int nf = four ? 4 : 2;
+  const bool keep_mid = !four && kept(s, s->iteration), keep_out = kept(s, s->iteration + nf - 1);
+  A.fused_iters = nf;
+  A.x_mid = keep_mid ? s->x[s->cur] : nullptr;              // in place over x_k (the update is block-local) ...
+  if (keep_mid && m.overlap) HIP_TRY(xmid_array(s, &A.x_mid));   // ... unless its reduction runs under the next launch, which writes x_{k+3} there
+  HIP_TRY(m.before_write(A.x_out, A.x_mid));
+  if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches], m.st));
+  HIP_TRY(lmc::launch_step_block(A, m.st));
+  if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches + 1], m.st));
+  s->kernel_name = four ? "myula_step_block_kernel(4 iterations)" : "myula_step_block_kernel(2 iterations)";
+  int rc = m.keep(A.x_mid, keep_out ? A.x_out : nullptr, m.overlap);
+  if (rc) return rc;
+  s->cur ^= 1;
+  s->iteration += nf;
+  ++s->last_launches;
+  return nf;
+}
+
+// One iteration per launch: every configuration, and the only path for injected noise, the ME-TV term, the warm-started TV prox, the early
+// exits of the TV prox and array-valued epsg.  `last`: the call's last iteration, whose reduction runs in line.
+static int myula_single(lmc_sampler* s, SideMoments& m, const float* noise, bool last) {
+  hipStream_t st = m.st;
+  lmc::StepArgs A = s->base;
+  A.x_in = s->x[s->cur];
+  A.x_out = s->x[s->cur ^ 1];
+  A.iteration = (uint32_t)s->iteration;
+  A.noise = noise;
+  sanitize_pointers(A);
+  int rc = me_tv_extra(s, A, st);   // inner prox of the Moreau-envelope term, then the fused step
+  if (rc) return rc;
+  HIP_TRY(m.before_write(A.x_out));
+  if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches], st));
+  const char* kname = nullptr;
+  hipError_t e;
+  bool stepped = false;
+  if (s->rt_tv.kc && A.prior_kind == LMC_PRIOR_TV_ISO) {   // early exit of the TV prox decided on the device: inside the fused launch, or the prox alone first
+    rc = tv_prior_rt(s->prob, s->epsg * s->gamma, A, s->rt_tv, s->pxbuf, s->tvstate[0], s->tvstate[1], st);
+    if (rc < 0) return rc;
+    if (rc == 2) return fail(LMC_E_STATE, "the device-side early exit no longer covers this sampler");
+    if (rc == 1) { stepped = true; kname = "myula_step_pipe_kernel(per-chain exit)"; }
   }
-  if (s->kind == 1) {
-    if (n_iters < 0) return fail(LMC_E_INVALID, "n_iters < 0");
-    if (s->noise_mode == LMC_NOISE_INJECTED && !noise_dev && n_iters > 0)
-      return fail(LMC_E_INVALID, "noise_mode is INJECTED but noise_dev is NULL");
-    if (s->noise_mode != LMC_NOISE_INJECTED && noise_dev)
-      return fail(LMC_E_INVALID, "noise_dev given but noise_mode is not INJECTED");
-    return ulpda_step(s, n_iters, noise_dev, S(stream));
+  if (s->rtmp && A.prior_kind == LMC_PRIOR_TV_ISO) {   // early-exit TV prox first (exact pass-by-pass path), consumed as a ready-made prox
+    rc = tv_prox_rtol(s->prob, s->epsg * s->gamma, A.x_in, s->pxbuf, s->rtmp, s->robj, s->rflag, s->C, s->tvstate[0], s->tvstate[1], st);
+    if (rc) return rc;
+    A.prior_kind = LMC_PRIOR_NONE;
+    A.prox_ext = s->pxbuf;
   }
-  if (n_iters < 0) return fail(LMC_E_INVALID, "n_iters < 0");
-  if (s->noise_mode == LMC_NOISE_INJECTED && !noise_dev && n_iters > 0)
-    return fail(LMC_E_INVALID, "noise_mode is INJECTED but noise_dev is NULL");
-  if (s->noise_mode != LMC_NOISE_INJECTED && noise_dev)
-    return fail(LMC_E_INVALID, "noise_dev given but noise_mode is not INJECTED");
-  if (s->iteration + n_iters > 0xFFFFFFFFLL) return fail(LMC_E_STATE, "iteration counter would exceed 32 bits");
-  hipStream_t st = S(stream);
+  if (s->prob.prox_scale && A.prior_kind != LMC_PRIOR_NONE) {   // array-valued epsg: prox_{epsg[c,i] gamma g} first, consumed as a ready-made prox
+    const Problem& q = s->prob;
+    HIP_TRY(lmc::launch_prior_prox_scaled(q.prior_kind, q.eprox_kind, A.x_in, s->pxbuf, s->C, (int64_t)q.H * q.W, q.prox_scale, q.prox_scale_cs, q.prox_scale_ps,
+                                          s->epsg * s->gamma, q.prior_sigma, q.eprox_p0, q.eprox_p1, q.eprox_mask, st));
+    A.prior_kind = LMC_PRIOR_NONE;
+    A.prox_ext = s->pxbuf;
+  }
+  if (stepped) {
+    e = hipSuccess;
+  } else if (s->tvwarm[0]) {     // warm-started TV prox: the dual of the previous iteration in, this iteration's out
+    A.tv_in = s->tvwarm[s->wcur];
+    A.tv_out = s->tvwarm[s->wcur ^ 1];
+    e = lmc::launch_step_pipe_warm(A, st);
+    kname = "myula_step_pipe_kernel(warm)";
+    s->wcur ^= 1;
+  } else {
+    e = launch_step(A, variant_of(s->prob), st, &kname, s->tvstate[0], s->tvstate[1], s->pxbuf);
+  }
+  if (e == hipErrorInvalidConfiguration) return fail(LMC_E_UNSUPPORTED, "no step-kernel variant covers this configuration");
+  HIP_TRY(e);
+  if (kname) s->kernel_name = kname;
+  if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches + 1], st));
+  s->cur ^= 1;
+  if (kept(s, s->iteration)) {
+    // beside the next launch unless the step kernel is a single launch of an HBM-heavy closed-form-prior kernel at full size: the two then share the memory
+    // system and the reduction outlasts the kernel whatever its workgroup count (blur + l2, 512 x 512 x 1024: in line 0.714 ms per iteration, beside it 0.73-0.83)
+    const bool beside = m.overlap && !last &&
+                        (s->pol_overlap > 0 || s->base.prior_kind == LMC_PRIOR_TV_ISO || (long long)s->C * s->prob.H * s->prob.W <= (1LL << 25));
+    rc = m.keep(s->x[s->cur], nullptr, beside);
+    if (rc) return rc;
+  }
+  ++s->iteration;
+  ++s->last_launches;
+  return 1;
+}
+
+static int myula_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, hipStream_t st) {
   const size_t per_iter = (size_t)s->C * s->prob.H * s->prob.W;
   s->timed = false;
   s->last_launches = 0;
@@ -1493,256 +1585,50 @@ int lmc_sampler_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, vo
       s->ev.push_back(e);
     }
   }
-  // LMC_MOMENTS_OVERLAP=1: the moment reductions run on a side stream under the following step kernel (0: serially on the caller's stream).
-  // Default: on for small configurations (<= 32 Mi pixel-updates per iteration; BASELINE config 2 at 256 x 256 x 128: the 15 us reduction is
-  // 40 % of a serial iteration, 40.2 -> 35.9 us per iteration with 128 background workgroups), off for large ones: at the headline size the
-  // reduction under the step kernel costs that kernel 6 % (1.76 -> 1.89 ms per launch) and saves its own 0.22 ms -- 1.976 -> 1.90-1.92 ms per
-  // iteration with 256 workgroups (16: 3.19, 64: 2.07, 128: 1.92, 256: 1.90, 512: 1.94, 1024: 1.98 ms; too few and the reduction outlasts the
-  // step kernel) -- a 3.5 % gain that is left opt-in so that the step kernel's launch time in bench.py / profiles/ is that of the kernel alone.
-  // (policy: lmc_problem.moments_overlap / moments_bg_workgroups, LMC_MOMENTS_OVERLAP / LMC_MOMENTS_BG_WGS as defaults; fixed at creation)
-  // Round 3: on by default at every size -- what bench.py's `value` measures -- and off while the launches are being event-timed
-  // (lmc_sampler_enable_timing: the roofline leg wants the step kernel alone).
-  const bool want_overlap = !s->timing && (s->pol_overlap ? s->pol_overlap > 0 : true);
-  const int bg_wgs = s->pol_bg_wgs >= 0 ? s->pol_bg_wgs : ((long long)s->C * s->prob.H * s->prob.W <= (1LL << 25) ? 128 : 256);   // 0: the full-speed kernel
-  bool overlap = want_overlap && s->moments && n_iters > 1;
+  // Moment reductions on the side stream under the following launches (lmc_problem.moments_overlap / LMC_MOMENTS_OVERLAP): on at every size --
+  // what bench.py's `value` measures -- and off while the launches are being event-timed (lmc_sampler_enable_timing: the roofline leg wants the
+  // step kernel alone).  BASELINE config 2 (256 x 256 x 128): the 15 us reduction is 40 % of a serial iteration, 40.2 -> 35.9 us per iteration
+  // with 128 background workgroups.  Headline size: the reduction under the step kernel costs that kernel 6 % (1.76 -> 1.89 ms per launch) and
+  // saves its own 0.22 ms -- 1.976 -> 1.90-1.92 ms per iteration with 256 workgroups (16: 3.19, 64: 2.07, 128: 1.92, 256: 1.90, 512: 1.94,
+  // 1024: 1.98 ms; too few and the reduction outlasts the step kernel).  (lmc_problem.moments_bg_workgroups / LMC_MOMENTS_BG_WGS: fixed at creation)
+  const bool overlap = !s->timing && s->pol_overlap >= 0 && s->moments && n_iters > 1;
+  const int bg_wgs = s->pol_bg_wgs >= 0 ? s->pol_bg_wgs : ((long long)per_iter <= (1LL << 25) ? 128 : 256);   // 0: the full-speed kernel
   if (overlap && !s->side) {
     int prio_least = 0, prio_greatest = 0;     // lowest priority: the step kernel's workgroups go first
     HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    const bool low_prio = s->pol_side_lowprio != 0;
-    if (low_prio) HIP_TRY(hipStreamCreateWithPriority(&s->side, hipStreamNonBlocking, prio_least));
+    if (s->pol_side_lowprio) HIP_TRY(hipStreamCreateWithPriority(&s->side, hipStreamNonBlocking, prio_least));
     else HIP_TRY(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&s->ev_step, hipEventDisableTiming));
-    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&s->ev_mom[i], hipEventDisableTiming));
-    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&s->ev_pair[i], hipEventDisableTiming));
+    for (hipEvent_t& e : s->side_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
-  // the same for launches that advance two iterations: both iterates are reduced on the side stream under the NEXT pair launch
-  auto pair_wait = [&](int p) -> int {        // the pair launch about to be enqueued writes where launch n - 2's reductions read
-    if (s->pair_pending[p]) { HIP_TRY(hipStreamWaitEvent(st, s->ev_pair[p], 0)); s->pair_pending[p] = false; }
-    return LMC_OK;
-  };
-  auto pair_reduce = [&](int p, const float* mid, const float* outp) -> int {   // after the pair launch: its kept iterates, on the side stream
-    HIP_TRY(hipEventRecord(s->ev_step, st));
-    HIP_TRY(hipStreamWaitEvent(s->side, s->ev_step, 0));
-    if (mid) HIP_TRY(lmc::launch_moments_bg(mid, s->C, s->prob.H, s->prob.W, s->s1, s->s2, bg_wgs, s->side));
-    if (outp) HIP_TRY(lmc::launch_moments_bg(outp, s->C, s->prob.H, s->prob.W, s->s1, s->s2, bg_wgs, s->side));
-    HIP_TRY(hipEventRecord(s->ev_pair[p], s->side));
-    s->pair_pending[p] = true;
-    return LMC_OK;
-  };
-  // graph replay: whole blocks of kGraphIters iterations whose every iteration is kept by the moment accumulators (or none is)
-  const bool graph_ok = !s->timing && (!overlap || s->pol_graph) && !noise_dev && s->noise_mode != LMC_NOISE_INJECTED && s->prob.ncvx_kind != LMC_NCVX_ME_TV &&
-                        !s->tvwarm[0] && !s->rtmp && !s->rt_tv.kc && (!s->moments || s->thin == 1) && graph_wanted(s);
-  bool graph_enabled = false;
-  const int pair_mode = s->pol_pair;
-  const bool blockpair_on = s->pol_blockpair != 0;
-  for (int k = 0; k < n_iters; ++k) {
-    if (graph_ok && s->plain_done && n_iters - k >= kGraphIters && (!s->moments || s->iteration >= s->burn_in) &&
-        (s->kernel_name == "myula_step_rows_kernel" || s->kernel_name == "myula_step_block_kernel" || s->kernel_name == "myula_step_pipe_kernel")) {
-      if (!s->gexec[s->cur]) { int rc = build_graph(s); if (rc) return rc; }
-      if (!graph_enabled) {             // the device-side iteration base of this call
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->iter_dev), (int)(uint32_t)s->iteration, 1, st));
-        graph_enabled = true;
-      }
-      for (int i = 0; i < 2; ++i)         // reductions still running on the side stream read buffers the replay overwrites
-        if (s->mom_pending[i]) { HIP_TRY(hipStreamWaitEvent(st, s->ev_mom[i], 0)); s->mom_pending[i] = false; }
-      HIP_TRY(hipGraphLaunch(s->gexec[s->cur], st));
-      s->iteration += kGraphIters;
-      if (s->moments) s->count += (uint64_t)s->C * kGraphIters;
-      s->last_launches += kGraphIters;
-      k += kGraphIters - 1;
-      continue;
+  SideMoments m{s, st, overlap, bg_wgs};
+  for (int k = 0; k < n_iters;) {
+    int done = 0;
+    if (!noise_dev) done = myula_rows_pair(s, m, n_iters - k);        // the pair launches draw Philox noise
+    if (!noise_dev && !done) done = myula_block_pair(s, m, n_iters - k);
+    if (!done) done = myula_single(s, m, noise_dev ? noise_dev + (size_t)k * per_iter : nullptr, k + 1 == n_iters);
+    if (done < 0) {
+      (void)m.join();
+      return done;
     }
-    if (graph_enabled) {   // plain launches after graph replays take their iteration word by value again: nothing to do (iter_dev is unused)
-    }
-    // Two MYULA iterations per launch (lmc_step_rows_pair.hip) where that kernel covers the configuration and the launch is large enough for its
-    // long bands: x_{k+2} goes to a third array (neighbouring bands re-read x_k), x_{k+1} is stored only when the moment accumulators keep it.
-    // lmc_problem.iterations_per_launch / LMC_ROWS_PAIR: 0 = never, 2 = wherever covered (tests), default = where it pays (n_chains * H >= 2^17).
-    if (pair_mode && n_iters - k >= 2 && !noise_dev && !graph_ok && !s->tvwarm[0] && !s->rtmp && s->prob.ncvx_kind == LMC_NCVX_NONE &&
-        (variant_of(s->prob) == 0 || variant_of(s->prob) == 6) && (pair_mode == 2 || (long long)s->C * s->prob.H >= (1 << 17))) {
-      lmc::StepArgs A = s->base;
-      A.x_in = s->x[s->cur];
-      A.iteration = (uint32_t)s->iteration;
-      A.noise = nullptr;
-      sanitize_pointers(A);
-      if (lmc::rows_pair_supported(A)) {
-        if (!s->xspare) {
-          HIP_TRY(hipMalloc(&s->xspare, sizeof(float) * per_iter));
-        }
-        auto kept = [&](int64_t it) { return s->moments && it >= s->burn_in && (it - s->burn_in) % s->thin == 0; };
-        const bool keep_mid = kept(s->iteration), keep_out = kept(s->iteration + 1);
-        const int pp = (int)(s->pair_n & 1);
-        float* mid = keep_mid ? s->x[s->cur ^ 1] : nullptr;
-        if (overlap && (keep_mid || keep_out)) {     // the reductions of this launch run under the next one: the iterate in between gets an array of its own
-          if (keep_mid) {
-            if (!s->xmid[pp]) HIP_TRY(hipMalloc(&s->xmid[pp], sizeof(float) * per_iter));
-            mid = s->xmid[pp];
-          }
-          int rc = pair_wait(pp);
-          if (rc) return rc;
-        }
-        for (int i = 0; i < 2; ++i)                 // (single launches of this call that ran before: their side-stream reductions read x[0] / x[1])
-          if (s->mom_pending[i]) { HIP_TRY(hipStreamWaitEvent(st, s->ev_mom[i], 0)); s->mom_pending[i] = false; }
-        A.x_out = s->xspare;
-        if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches], st));
-        HIP_TRY(lmc::launch_step_rows_pair(A, mid, st));
-        if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches + 1], st));
-        s->kernel_name = "myula_step_rows_pair_kernel";
-        s->plain_done = true;
-        if (overlap && (keep_mid || keep_out)) {
-          int rc = pair_reduce(pp, keep_mid ? mid : nullptr, keep_out ? s->xspare : nullptr);
-          if (rc) return rc;
-          s->count += (uint64_t)s->C * ((keep_mid ? 1 : 0) + (keep_out ? 1 : 0));
-        } else {
-          if (keep_mid) { HIP_TRY(lmc::launch_moments(mid, s->C, s->prob.H, s->prob.W, s->s1, s->s2, st)); s->count += (uint64_t)s->C; }
-          if (keep_out) { HIP_TRY(lmc::launch_moments(s->xspare, s->C, s->prob.H, s->prob.W, s->s1, s->s2, st)); s->count += (uint64_t)s->C; }
-        }
-        ++s->pair_n;
-        std::swap(s->x[s->cur], s->xspare);        // x[cur] = x_{k+2}; the array that held x_k is the spare now
-        for (int i = 0; i < 2; ++i)                // captured graphs hold the old pointers
-          if (s->gexec[i]) { (void)hipGraphExecDestroy(s->gexec[i]); s->gexec[i] = nullptr; }
-        s->iteration += 2;
-        ++s->last_launches;
-        ++k;
-        continue;
-      }
-    }
-    // Two iterations per launch on the register-block kernel (Haar prior, stencil-free data term: BASELINE config 5): the update never leaves a
-    // thread's 8 x 8 block, so the second iteration runs on the block while it is on chip; x_{k+1} is written (in place, over x_k) only when the
-    // moment accumulators keep it.  LMC_BLOCK_PAIR=0 turns it off.  Same arithmetic, same noise: bit-identical to two launches.
-    if (blockpair_on && n_iters - k >= 2 && !noise_dev && !graph_ok && !s->tvwarm[0] && !s->rtmp && s->prob.ncvx_kind == LMC_NCVX_NONE &&
-        (variant_of(s->prob) == 0 || variant_of(s->prob) == 5)) {
-      lmc::StepArgs A = s->base;
-      A.x_in = s->x[s->cur];
-      A.x_out = s->x[s->cur ^ 1];
-      A.iteration = (uint32_t)s->iteration;
-      A.noise = nullptr;
-      sanitize_pointers(A);
-      if (lmc::block_pair_supported(A)) {
-        auto kept = [&](int64_t it) { return s->moments && it >= s->burn_in && (it - s->burn_in) % s->thin == 0; };
-        // four iterations on chip when none of the three iterates in between is kept (moments off, burn-in, thinning by >= 4)
-        const bool four = n_iters - k >= 4 && !kept(s->iteration) && !kept(s->iteration + 1) && !kept(s->iteration + 2);
-        const int nf = four ? 4 : 2;
-        const bool keep_mid = !four && kept(s->iteration), keep_out = kept(s->iteration + nf - 1);
-        A.fused_iters = nf;
-        A.x_mid = keep_mid ? s->x[s->cur] : nullptr;          // in place over x_k (the update is block-local) ...
-        const int pp = (int)(s->pair_n & 1);
-        const bool side_red = overlap && (keep_mid || keep_out);
-        if (side_red) {                                       // ... unless its reduction runs under the next launch, which writes x_{k+3} there
-          if (keep_mid) {
-            if (!s->xmid[pp]) HIP_TRY(hipMalloc(&s->xmid[pp], sizeof(float) * per_iter));
-            A.x_mid = s->xmid[pp];
-          }
-          int rc = pair_wait(pp);
-          if (rc) return rc;
-        }
-        for (int i = 0; i < 2; ++i)
-          if (s->mom_pending[i]) { HIP_TRY(hipStreamWaitEvent(st, s->ev_mom[i], 0)); s->mom_pending[i] = false; }
-        if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches], st));
-        HIP_TRY(lmc::launch_step_block(A, st));
-        if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches + 1], st));
-        s->kernel_name = four ? "myula_step_block_kernel(4 iterations)" : "myula_step_block_kernel(2 iterations)";
-        s->plain_done = true;
-        if (side_red) {
-          int rc = pair_reduce(pp, keep_mid ? A.x_mid : nullptr, keep_out ? s->x[s->cur ^ 1] : nullptr);
-          if (rc) return rc;
-          s->count += (uint64_t)s->C * ((keep_mid ? 1 : 0) + (keep_out ? 1 : 0));
-          s->cur ^= 1;
-        } else {
-          if (keep_mid) { HIP_TRY(lmc::launch_moments(s->x[s->cur], s->C, s->prob.H, s->prob.W, s->s1, s->s2, st)); s->count += (uint64_t)s->C; }
-          s->cur ^= 1;
-          if (keep_out) { HIP_TRY(lmc::launch_moments(s->x[s->cur], s->C, s->prob.H, s->prob.W, s->s1, s->s2, st)); s->count += (uint64_t)s->C; }
-        }
-        ++s->pair_n;
-        s->iteration += nf;
-        ++s->last_launches;
-        k += nf - 1;
-        continue;
-      }
-    }
-    lmc::StepArgs A = s->base;
-    A.x_in = s->x[s->cur];
-    A.x_out = s->x[s->cur ^ 1];
-    A.iteration = (uint32_t)s->iteration;
-    A.noise = noise_dev ? noise_dev + (size_t)k * per_iter : nullptr;
-    sanitize_pointers(A);
-    if (s->prob.ncvx_kind == LMC_NCVX_ME_TV) {   // inner prox of the Moreau-envelope term, then the fused step
-      int rc = me_tv_prox(s->prob, A.x_in, s->extra, s->C, s->tvstate[0], s->tvstate[1], st, &s->rt_me);
-      if (rc) return rc;
-      A.extra = s->extra;
-      A.extra_coef = -s->prob.ncvx_lambda / s->prob.ncvx_gamma;
-    }
-    for (int i = 0; i < 2; ++i)          // reductions of earlier pair launches of this call may still read the array this step writes
-      if (s->pair_pending[i]) { HIP_TRY(hipStreamWaitEvent(st, s->ev_pair[i], 0)); s->pair_pending[i] = false; }
-    if (s->mom_pending[s->cur ^ 1]) {   // this step overwrites x[cur ^ 1]: the reduction that still reads it must be done
-      HIP_TRY(hipStreamWaitEvent(st, s->ev_mom[s->cur ^ 1], 0));
-      s->mom_pending[s->cur ^ 1] = false;
-    }
-    if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches], st));
-    const char* kname = nullptr;
-    hipError_t e;
-    bool stepped = false;
-    if (s->rt_tv.kc && A.prior_kind == LMC_PRIOR_TV_ISO) {   // early exit of the TV prox decided on the device: inside the fused launch, or the prox alone first
-      const int rc = tv_prior_rt(s->prob, s->epsg * s->gamma, A, s->rt_tv, s->pxbuf, s->tvstate[0], s->tvstate[1], st);
-      if (rc < 0) return rc;
-      if (rc == 2) return fail(LMC_E_STATE, "the device-side early exit no longer covers this sampler");
-      if (rc == 1) { stepped = true; kname = "myula_step_pipe_kernel(per-chain exit)"; }
-    }
-    if (s->rtmp && A.prior_kind == LMC_PRIOR_TV_ISO) {   // early-exit TV prox first (exact pass-by-pass path), consumed as a ready-made prox
-      int rc = tv_prox_rtol(s->prob, s->epsg * s->gamma, A.x_in, s->pxbuf, s->rtmp, s->robj, s->rflag, s->C, s->tvstate[0], s->tvstate[1], st);
-      if (rc) return rc;
-      A.prior_kind = LMC_PRIOR_NONE;
-      A.prox_ext = s->pxbuf;
-    }
-    if (s->prob.prox_scale && A.prior_kind != LMC_PRIOR_NONE) {   // array-valued epsg: prox_{epsg[c,i] gamma g} first, consumed as a ready-made prox
-      const Problem& q = s->prob;
-      HIP_TRY(lmc::launch_prior_prox_scaled(q.prior_kind, q.eprox_kind, A.x_in, s->pxbuf, s->C, (int64_t)q.H * q.W, q.prox_scale, q.prox_scale_cs, q.prox_scale_ps,
-                                            s->epsg * s->gamma, q.prior_sigma, q.eprox_p0, q.eprox_p1, q.eprox_mask, st));
-      A.prior_kind = LMC_PRIOR_NONE;
-      A.prox_ext = s->pxbuf;
-    }
-    if (stepped) {
-      e = hipSuccess;
-    } else if (s->tvwarm[0]) {     // warm-started TV prox: the dual of the previous iteration in, this iteration's out
-      A.tv_in = s->tvwarm[s->wcur];
-      A.tv_out = s->tvwarm[s->wcur ^ 1];
-      e = lmc::launch_step_pipe_warm(A, st);
-      kname = "myula_step_pipe_kernel(warm)";
-      s->wcur ^= 1;
-    } else {
-      e = launch_step(A, variant_of(s->prob), st, &kname, s->tvstate[0], s->tvstate[1], s->pxbuf);
-    }
-    if (e == hipErrorInvalidConfiguration) return fail(LMC_E_UNSUPPORTED, "no step-kernel variant covers this configuration");
-    HIP_TRY(e);
-    if (kname) s->kernel_name = kname;
-    s->plain_done = true;
-    if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches + 1], st));
-    s->cur ^= 1;
-    if (s->moments && s->iteration >= s->burn_in && (s->iteration - s->burn_in) % s->thin == 0) {
-      // ... unless the step kernel is a single launch of an HBM-heavy closed-form-prior kernel at full size: the two then share the memory system and the
-      // reduction outlasts the kernel whatever its workgroup count (blur + l2, 512 x 512 x 1024: in line 0.714 ms per iteration, beside it 0.73-0.83)
-      const bool beside = overlap && (s->pol_overlap > 0 || s->base.prior_kind == LMC_PRIOR_TV_ISO || (long long)per_iter <= (1LL << 25));
-      if (beside && k + 1 < n_iters) {   // reduce x[cur] on the side stream while the next step kernel runs
-        HIP_TRY(hipEventRecord(s->ev_step, st));
-        HIP_TRY(hipStreamWaitEvent(s->side, s->ev_step, 0));
-        HIP_TRY(lmc::launch_moments_bg(s->x[s->cur], s->C, s->prob.H, s->prob.W, s->s1, s->s2, bg_wgs, s->side));
-        HIP_TRY(hipEventRecord(s->ev_mom[s->cur], s->side));
-        s->mom_pending[s->cur] = true;
-      } else {
-        for (int i = 0; i < 2; ++i)       // accumulators are shared: stay behind the side stream's reductions
-          if (s->mom_pending[i]) { HIP_TRY(hipStreamWaitEvent(st, s->ev_mom[i], 0)); s->mom_pending[i] = false; }
-        HIP_TRY(lmc::launch_moments(s->x[s->cur], s->C, s->prob.H, s->prob.W, s->s1, s->s2, st));
-      }
-      s->count += (uint64_t)s->C;
-    }
-    ++s->iteration;
-    ++s->last_launches;
+    k += done;
   }
-  for (int i = 0; i < 2; ++i) {           // everything this call enqueued is ordered before whatever the caller enqueues next
-    if (s->mom_pending[i]) { HIP_TRY(hipStreamWaitEvent(st, s->ev_mom[i], 0)); s->mom_pending[i] = false; }
-    if (s->pair_pending[i]) { HIP_TRY(hipStreamWaitEvent(st, s->ev_pair[i], 0)); s->pair_pending[i] = false; }
-  }
+  HIP_TRY(m.join());   // everything this call enqueued is ordered before whatever the caller enqueues next
   s->timed = s->timing;
   return LMC_OK;
+}
+
+int lmc_sampler_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (n_iters < 0) return fail(LMC_E_INVALID, "n_iters < 0");
+  if (s->noise_mode == LMC_NOISE_INJECTED && !noise_dev && n_iters > 0)
+    return fail(LMC_E_INVALID, "noise_mode is INJECTED but noise_dev is NULL");
+  if (s->noise_mode != LMC_NOISE_INJECTED && noise_dev)
+    return fail(LMC_E_INVALID, "noise_dev given but noise_mode is not INJECTED");
+  if (s->iteration + n_iters > 0xFFFFFFFFLL) return fail(LMC_E_STATE, "iteration counter would exceed 32 bits");
+  if (s->kind == 2) return mymala_step(s, n_iters, noise_dev, S(stream));
+  if (s->kind == 1) return ulpda_step(s, n_iters, noise_dev, S(stream));
+  return myula_step(s, n_iters, noise_dev, S(stream));
 }
 
 // ---- MYMALA: Metropolis-adjusted MYULA at image scale (generalises prox_lmc.py:134-158) -------------------------------
@@ -1816,7 +1702,7 @@ static int mymala_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, 
     // state back -- was measured: 3.0 instead of 3.7 ms at 98 % acceptance, but 3.7 instead of 3.0 ms at 48 %; the choice would have to
     // follow the acceptance rate, which the host does not see without a synchronisation.)
     HIP_TRY(lmc::mala_select(s->flag, x, s->mx, s->xp, s->mxp, C, img, 1, st));
-    if (s->moments && s->iteration >= s->burn_in && (s->iteration - s->burn_in) % s->thin == 0) {
+    if (kept(s, s->iteration)) {
       HIP_TRY(lmc::launch_moments(x, C, s->prob.H, s->prob.W, s->s1, s->s2, st));
       s->count += (uint64_t)C;
     }
@@ -1852,7 +1738,6 @@ static int ulpda_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, h
   const int iso = s->prob.prior_kind == LMC_PRIOR_TV_ISO;
   s->timed = false;
   s->last_launches = 0;
-  if (s->iteration + n_iters > 0xFFFFFFFFLL) return fail(LMC_E_STATE, "iteration counter would exceed 32 bits");
   // gfirst = false: finish and dual update as ONE row-streaming pass (x ping-pongs between two buffers, xhat stays in registers; 28 instead
   // of 36 B per pixel).  Opt-in (LMC_ULPDA_FUSE=1): measured at 512 x 512 x 1024 the fused pass takes 1.85 ms (4.1 TB/s; software-pipelined
   // loads: the same) against 0.76 + 0.94 ms for the two flat passes (5.6 TB/s each) -- 8.0 ms per iteration either way.  Exact (test_gpu_ulpda.py).
@@ -1931,7 +1816,7 @@ static int ulpda_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, h
         HIP_TRY(lmc::ulpda_dual_update(s->xhat, s->ydual, C, H, W, s->mu, s->prob.prior_sigma, iso, st));
       }
     }
-    if (s->moments && s->iteration >= s->burn_in && (s->iteration - s->burn_in) % s->thin == 0) {
+    if (kept(s, s->iteration)) {
       HIP_TRY(lmc::launch_moments(x, s->C, H, W, s->s1, s->s2, st));
       s->count += (uint64_t)s->C;
     }

@@ -754,7 +754,7 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
     // In the tick of row 4q + NI the normals of pixels NI*PXL/4 .. of quad q + 1 are drawn into the other half of the slab
     // (spread evenly over the ticks: a burst every 4th tick would stall every wave at the barrier).
     float* const slab = lds + L::o_slab + lane;        // normal (row q of the quad, pixel k) at slab[(q*PXL + k)*64]
-    const uint32_t iter = A.iteration + (A.iter_dev ? *A.iter_dev : 0u);     // uniform; graph replays advance *iter_dev
+    const uint32_t iter = A.iteration;
     auto tick = [&](auto uu, const int t) __attribute__((always_inline)) {
       constexpr int U = decltype(uu)::value;
       constexpr int NI = ((U - D) % 4 + 4) % 4;        // == o & 3  (t = 4m + U)

@@ -126,7 +126,7 @@ __device__ __forceinline__ void rows_body(const StepArgs& P, const int band_rows
   float* __restrict__ xout = P.x_out + (size_t)chain * img;
   const float* __restrict__ uv = P.blur.h;              // u[0..KT) then v[0..KT) at h[kMaxBlur..], centred, zero padded
   const int i_first = r0 - LAG;
-  const uint32_t iter = P.iteration + (P.iter_dev ? *P.iter_dev : 0u);      // uniform scalar load; graph replays advance *iter_dev
+  const uint32_t iter = P.iteration;
 
   // 8 px / lane: the 32 normals of a quad row-group wait in a wave-private LDS slab (each lane reads back only what it
   // wrote, so no barrier) instead of 32 VGPRs -- the register file is the limit at 2 waves / SIMD.

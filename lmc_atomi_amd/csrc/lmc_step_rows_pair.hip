@@ -46,7 +46,7 @@ __device__ __forceinline__ void rows_pair_body(const StepArgs& P, float* __restr
   float* __restrict__ xmid = x_mid ? x_mid + (size_t)chain * img : nullptr;
   float* __restrict__ xout = P.x_out + (size_t)chain * img;
   const float cbox = P.blur.h[0] * P.blur.h[kMaxBlur];                     // c_u c_v of the uniform 5-tap box
-  const uint32_t iter = P.iteration + (P.iter_dev ? *P.iter_dev : 0u) + (uint32_t)stage;
+  const uint32_t iter = P.iteration + (uint32_t)stage;
   float* const myU = ringU + lane * PXL;
 
   float xr[8][PXL], A[8][PXL], G[8][PXL], Vs[PXL], Ws[PXL], yq[2][PXL];
