@@ -133,7 +133,7 @@ typedef struct lmc_problem {
    * Not with tv_warm or MYMALA. */
   float tv_rtol;
   /* Step-kernel variant for launches configured from this problem: 0 = the library default (lmc_set_step_variant, itself "auto"
-   * unless changed), 1..7 as listed at lmc_set_step_variant. */
+   * unless changed), 1..8 as listed at lmc_set_step_variant. */
   int32_t step_variant;
   /* Relative residual |r| <= tol |b| of the implicit data step (lmc_l2_prox, ULPDA): 0 = the library default
    * (lmc_set_cg_tolerance, itself 1e-6 unless changed), > 0 explicit, < 0 disabled (always all iterations, CG). */
@@ -394,8 +394,12 @@ float lmc_set_cg_tolerance(float tol);
  * 8 x 8 blocks: Haar-l1 / l2 / l1 / none; H, W multiples of 8), 6 = barrier-free row streaming (separable blur + closed-form
  * prior; any width: column strips above 512 columns, dword-aligned 16-byte accesses when W % 4 != 0), 7 = stage-parallel full-width TV pipeline
  * (isotropic TV with 10, 20, ... 60 dual iterations, separable blur or no data term, W > 128; any width for these counts, other counts -- 2, 6, 8, 9,
- * warm-dual 1, 2, 3 -- need W % 4 == 0 up to 256 columns and W % 8 == 0 above: the default of the headline configuration).  Returns the previous setting (>= 0) or a
- * negative lmc_status.  All variants compute the same update; the switch exists for A/B tests and profiles. */
+ * warm-dual 1, 2, 3 -- need W % 4 == 0 up to 256 columns and W % 8 == 0 above), in its one-team layout (8 waves of up to 8 pixels per lane),
+ * 8 = the same pipeline in its two-team layout (16 waves of 4 pixels per lane, each team on half the width; one launch of 10 dual iterations,
+ * 5 x 5 blur, 264 <= W <= 512 with W % 8 == 0, no energy by-products or non-convex term; other configurations: LMC_E_UNSUPPORTED; bit-identical
+ * to 7).  Auto picks the two-team layout where it covers the configuration (the headline one) and the one-team layout elsewhere.  The value 8
+ * is accepted since this ABI revision (additive).  Returns the previous setting (>= 0) or a negative lmc_status.  All variants compute the same update; the
+ * switch exists for A/B tests and profiles. */
 int lmc_set_step_variant(int32_t variant);
 
 #ifdef __cplusplus

@@ -150,7 +150,7 @@ _SIGNATURES = {
     "lmc_allreduce_moments": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_uint64), _P]),
 }
 RCCL_UNIQUE_ID_BYTES = 128
-VARIANTS = ["auto", "tile", "(removed)", "split", "point", "block", "rows", "pipe"]
+VARIANTS = ["auto", "tile", "(removed)", "split", "point", "block", "rows", "pipe", "pipe2"]
 
 _lib = None
 _lock = threading.Lock()

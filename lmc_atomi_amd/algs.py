@@ -51,7 +51,7 @@ class MYULASampler:
 
     def __init__(self, proxf, proxg, dims, n_chains=1, tau=None, gamma=0.1, epsg=1.0, seed=0,
                  chain_offset=0, noise="philox", moments=False, burn_in=0, thin=1, device=None, variant=None, tv_warm=None, policy=None):
-        """``variant``: step-kernel variant of THIS sampler ('auto' | 'tile' | 'split' | 'point' | 'block' | 'rows' | 'pipe'; None = the
+        """``variant``: step-kernel variant of THIS sampler ('auto' | 'tile' | 'split' | 'point' | 'block' | 'rows' | 'pipe' | 'pipe2'; None = the
         library default, :func:`set_step_variant`).  ``tv_warm``: carry the TV dual between iterations (see :class:`TV`; None = as
         ``proxg.warm`` says).  Every call on the sampler runs on ``device`` whatever the current device is."""
         if tau is None:
@@ -557,8 +557,8 @@ def set_cg_tolerance(tol=1e-6):
 
 
 def set_step_variant(variant="auto"):
-    """Library-wide DEFAULT of the step-kernel variant ('auto' | 'tile' | 'split' | 'point' | 'block' | 'rows' | 'pipe'); returns the previous
-    one.  Process-global, for A/B tests and profiles; a sampler's own ``variant=`` argument takes precedence.  All compute the same update."""
+    """Library-wide DEFAULT of the step-kernel variant ('auto' | 'tile' | 'split' | 'point' | 'block' | 'rows' | 'pipe' | 'pipe2'; 'pipe' is the
+    pipeline in its one-team layout, 'pipe2' in its two-team layout); returns the previous one.  Process-global, for A/B tests and profiles; a sampler's own ``variant=`` argument takes precedence.  All compute the same update."""
     names = _capi.VARIANTS
     if variant not in names or variant.startswith("("):
         raise ValueError(f"unknown step-kernel variant {variant!r} (the one-group 'stream' kernel of ABI 1 was removed)")

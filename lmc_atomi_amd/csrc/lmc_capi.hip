@@ -284,8 +284,8 @@ int load_problem(const lmc_problem* p, Problem& q) {
     const int ipl = q.iters_per_launch ? q.iters_per_launch : (e2 ? atoi(e2) : 0);
     q.cheb_pair = ipl == 1 ? 0 : (ipl == 2 ? 2 : (e ? atoi(e) : 1));
   }
-  if (p->step_variant < 0 || p->step_variant > 7 || p->step_variant == 2)
-    return fail(LMC_E_INVALID, "step_variant %d: 0 (library default), 1 tile, 3 split, 4 point, 5 block, 6 rows, 7 pipe", p->step_variant);
+  if (p->step_variant < 0 || p->step_variant > 8 || p->step_variant == 2)
+    return fail(LMC_E_INVALID, "step_variant %d: 0 (library default), 1 tile, 3 split, 4 point, 5 block, 6 rows, 7 pipe, 8 pipe2", p->step_variant);
   q.variant = p->step_variant;
   if (p->prox_scale) {
     if (p->prior_kind != LMC_PRIOR_L2 && p->prior_kind != LMC_PRIOR_L1 && p->prior_kind != LMC_PRIOR_EPROX)
@@ -344,7 +344,7 @@ void sanitize_pointers(lmc::StepArgs& A) {
 
 // Library-wide DEFAULTS only (lmc_set_step_variant / lmc_set_cg_tolerance): every launch takes its variant and tolerance from the
 // lmc_problem it was configured from (step_variant / implicit_tol) and falls back to these when that field is 0.
-int g_variant = 0;  // 0 auto, 1 tile, (2: removed) 3 split, 4 point, 5 block, 6 rows, 7 pipe
+int g_variant = 0;  // 0 auto, 1 tile, (2: removed) 3 split, 4 point, 5 block, 6 rows, 7 pipe (one team), 8 pipe2 (two teams)
 float g_cg_tol = 1e-6f;   // relative residual at which the inner solver stops (0: always cg_niter iterations)
 int variant_of(const Problem& q) { return q.variant ? q.variant : g_variant; }
 float tol_of(const Problem& q) { return q.implicit_tol > 0.f ? q.implicit_tol : (q.implicit_tol < 0.f ? 0.f : g_cg_tol); }
@@ -386,15 +386,16 @@ hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, c
     return lmc::launch_step_rows(A, st);
   }
   if (v == 6) return hipErrorInvalidConfiguration;
-  // TV K = 10 on a 264..512-wide image with a separable blur: the stage-parallel full-width pipeline
-  if (v == 0 || v == 7) {
+  // TV K = 10 on a 264..512-wide image with a separable blur: the stage-parallel full-width pipeline (auto: its two-team layout where that
+  // covers the configuration, else one team; 7: one team; 8: the two-team layout or nothing)
+  if (v == 0 || v == 7 || v == 8) {
     const int links = lmc::pipe_links(A);
-    if (links == 1 || (links > 1 && state0 && state1)) {
+    if (links == 1 || (links > 1 && state0 && state1 && v != 8)) {
       if (name) *name = "myula_step_pipe_kernel";
-      return lmc::launch_step_pipe(A, st, state0, state1);
+      return lmc::launch_step_pipe(A, st, state0, state1, v == 7 ? 1 : v == 8 ? 2 : 0);
     }
   }
-  if (v == 7) return hipErrorInvalidConfiguration;
+  if (v == 7 || v == 8) return hipErrorInvalidConfiguration;
   // auto: split pipeline when it covers the configuration (W <= 512); for wider images the tiled kernels:
   // "point" for closed-form priors with a separable blur, else the general LDS-tiled kernel
   // a closed-form elementwise prior (LMC_PRIOR_EPROX) that reaches this point (a non-log-concave term, or a blur the row kernel does not cover): the split and
@@ -2115,8 +2116,8 @@ float lmc_set_cg_tolerance(float tol) {
 }
 
 int lmc_set_step_variant(int32_t variant) {
-  if (variant < 0 || variant > 7 || variant == 2)
-    return fail(LMC_E_INVALID, "variant must be 0 (auto), 1 (tile), 3 (split), 4 (point), 5 (block), 6 (rows) or 7 (pipe); 2 (the one-group "
+  if (variant < 0 || variant > 8 || variant == 2)
+    return fail(LMC_E_INVALID, "variant must be 0 (auto), 1 (tile), 3 (split), 4 (point), 5 (block), 6 (rows), 7 (pipe) or 8 (pipe2); 2 (the one-group "
                 "streaming kernel of ABI 1) was removed");
   const int prev = g_variant;
   g_variant = variant;

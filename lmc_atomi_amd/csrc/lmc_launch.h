@@ -78,7 +78,8 @@ int centred_blur_taps(const BlurTaps& T, float* uc, float* vc);
 // TV stages spread over the waves of a workgroup, one wave = full image width (lmc_step_pipe.hip)
 bool pipe_supported(const StepArgs& a);                  // one launch covers it (10 dual iterations)
 int pipe_links(const StepArgs& a);                       // launches needed (20 .. 60 iterations: chained through HBM state), 0 = not covered
-hipError_t launch_step_pipe(StepArgs a, hipStream_t st, float* state0 = nullptr, float* state1 = nullptr);
+hipError_t launch_step_pipe(StepArgs a, hipStream_t st, float* state0 = nullptr, float* state1 = nullptr, int teams = 0);   // teams: 0 auto, 1 one-team, 2 two-team
+bool pipe_teams_covered(const StepArgs& a, int KT);
 // warm-started TV prox: a.tv_in / a.tv_out = [C][2][H][W] projected dual of the previous / this MYULA iteration
 bool pipe_warm_supported(const StepArgs& a);
 hipError_t launch_step_pipe_warm(StepArgs a, hipStream_t st);

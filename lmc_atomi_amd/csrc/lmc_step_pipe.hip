@@ -70,11 +70,23 @@ hipError_t launch_step_pipe_warm(StepArgs a, hipStream_t st) {
   return pipe_dispatch_chain(a, a.tv.niter, KT, st);
 }
 
+// The two-team layout (myula_step_pipe2_kernel) covers one launch of 10 dual iterations with the 5-tap blur on an image 264 to 512 columns
+// wide, W % 8 == 0, that returns the update alone: no energy by-products, no non-convex term (their seam columns are not exchanged).
+bool pipe_teams_covered(const StepArgs& a, int KT) {
+  return a.tv.niter == 10 && KT == 5 && a.W >= 264 && a.W <= 512 && (a.W & 7) == 0 && !a.f_out && !a.g_out &&
+         a.ncvx_kind == LMC_NCVX_NONE && !a.extra;
+}
+
 // state0 / state1: [C][4][H][W] ping-pong buffers for the dual state between links (needed when a.tv.niter > 10)
-hipError_t launch_step_pipe(StepArgs a, hipStream_t st, float* state0, float* state1) {
+// teams: 0 = the library's choice (two teams where covered: 1.70 against 1.80 ms per step at 512 x 512 x 1024, bit-identical),
+// 1 = one team, 2 = two teams (hipErrorInvalidConfiguration where not covered)
+hipError_t launch_step_pipe(StepArgs a, hipStream_t st, float* state0, float* state1, int teams) {
   const int links = pipe_links(a);
   if (links == 0 || (links > 1 && (!state0 || !state1))) return hipErrorInvalidConfiguration;
   const int KT = pipe_taps(a);
+  const bool two = links == 1 && pipe_teams_covered(a, KT);
+  if (teams == 2 && !two) return hipErrorInvalidConfiguration;
+  if (two && teams != 1) return pipe_launch_teams<10, 5>(a, st);
   if (links == 1) {
     switch (a.tv.niter) {
       case 2: return pipe_dispatch_k<2, false>(a, KT, st);

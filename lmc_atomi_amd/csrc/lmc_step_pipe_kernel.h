@@ -50,18 +50,24 @@ struct PipeGeom {
   static constexpr int NT = (K + 1) / 2;                        // TV waves (two stages each; odd K: the last one runs stage K alone)
 };
 
-template <int K, int PXL, bool CHAIN = false>
+template <int K, int PXL, bool CHAIN = false, int TEAMS = 1>
 struct PipeLds {
   static constexpr int BW = 64 * PXL;
-  static constexpr int o_x = 0;                                        // [RB][BW]
-  static constexpr int o_hand = o_x + PipeGeom<K>::RB * BW;            // [NT][2][4][BW]: rr, ss, p, q of the wave's last stage
+  // two-team layout (TEAMS = 2): the teams' copies of a row sit side by side (row pitch RP = 2 BW), so that a wave reaches the other
+  // team's copy of the row it works on at a fixed distance of BW floats -- a constant offset of the same address
+  static constexpr int RP = TEAMS * BW;
+  static constexpr int o_x = 0;                                        // [RB][RP]
+  static constexpr int o_hand = o_x + PipeGeom<K>::RB * RP;            // [NT][2][4][RP]: rr, ss, p, q of the wave's last stage
   // chained launches (more than K dual iterations): the last boundary (T_NT -> C) carries rr, ss only, [2][2][BW], and the 8*BW
   // saved hold the dual state of the previous launch for stage 1, [2][4][BW] (LDS budget: 160 KB)
-  static constexpr int o_hand_last = o_hand + (PipeGeom<K>::NT - 1) * 8 * BW;
-  static constexpr int o_hand0 = o_hand_last + 4 * BW;
-  static constexpr int o_g = CHAIN ? o_hand0 + 8 * BW : o_hand + PipeGeom<K>::NT * 2 * 4 * BW;    // [2][BW] gradient of the output row
-  static constexpr int o_slab = o_g + 2 * BW;                          // [2][4][PXL][64] normals of this and the next quad row-group
-  static constexpr int total = o_slab + 2 * 4 * PXL * 64;
+  static constexpr int o_hand_last = o_hand + (PipeGeom<K>::NT - 1) * 8 * RP;
+  static constexpr int o_hand0 = o_hand_last + 4 * RP;
+  static constexpr int o_g = CHAIN ? o_hand0 + 8 * RP : o_hand + PipeGeom<K>::NT * 2 * 4 * RP;    // [2][RP] gradient of the output row
+  static constexpr int SLAB = 2 * 4 * PXL * 64;
+  static constexpr int o_slab = o_g + 2 * RP;                          // [TEAMS][2][4][PXL][64] normals of this and the next quad row-group
+  // seam records of the two-team layout (PipeSeam below), zero-filled with the rows
+  static constexpr int o_seam = o_slab + TEAMS * SLAB;
+  static constexpr int total = o_seam + (TEAMS == 2 ? 64 : 0);
 };
 
 // LDS rows are stored so that every 16-byte access of a wave is contiguous: pixel k of lane l at (k>>2)*256 + 4*l + (k&3).
@@ -106,6 +112,16 @@ __device__ __forceinline__ void pairs_store(float* row, int lane, const v2f (&v)
 template <int NP>
 struct DualRow { v2f rr[NP], ss[NP], p[NP], q[NP]; };
 
+// Wave shifts whose vacant lane takes `edge` instead of 0 (DPP without bound_ctrl: the lane with no source keeps the old value).  The
+// two-team layout puts a team's seam column in lane 63 (left team) or lane 0 (right team), so the neighbour across the seam enters with
+// the same one instruction as the neighbour inside the wave.
+__device__ __forceinline__ float wave_from_left(float v, float edge) {    // lane i <- v[i-1]; lane 0 <- edge
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float wave_from_right(float v, float edge) {   // lane i <- v[i+1]; lane 63 <- edge
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
+}
+
 // One FGP dual iteration on NP pixel pairs per lane.  r1, s1 = (rr, ss)^{k-1} on row a; in0 = (rr, ss, p, q)^{k-1} on row
 // b = a-1; solb = sol^k on row b (in) -> sol^k on row a (out); out = (rr, ss, p, q)^k on row b.
 // The horizontal step coefficient per pixel: -c, and 0 for the pixel in the last image column (no difference across it).  LASTLANE: the image
@@ -127,12 +143,14 @@ struct StageObj { v2f sq, tv; };
 template <int NP>
 struct ObjMask { float md; v2f mlast; };     // 1 / 0: the row below exists; the column to the right of the lane's last pair exists
 
-template <int NP, bool LASTLANE = true, bool OBJ = false>
+// SEAML / SEAMR (two-team layout): lane 0's left neighbour of s1 / lane 63's right neighbour of solb is the other team's, `ssl_edge` / `solr_edge`.
+template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAML = false, bool SEAMR = false>
 __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[NP], const v2f (&s1)[NP], const DualRow<NP>& in0,
                                            v2f (&solb)[NP], float gam, float cdown, const PipeCr<NP>& cr, float beta,
-                                           DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP>* om = nullptr) {
+                                           DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP>* om = nullptr,
+                                           float ssl_edge = 0.f, float solr_edge = 0.f) {
   v2f sol[NP];
-  const float ssl0 = dpp_left0(s1[NP - 1].y);
+  const float ssl0 = SEAML ? wave_from_left(s1[NP - 1].y, ssl_edge) : dpp_left0(s1[NP - 1].y);
   const v2f ngam = pk_set(-gam), ncd = pk_set(-cdown), vb = pk_set(beta);
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
@@ -141,7 +159,7 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
     sol[i] = pk_fma(ngam, T, xa[i]);
     if constexpr (OBJ) ob->sq = i == 0 ? T * T : pk_fma(T, T, ob->sq);
   }
-  const float solr_last = dpp_right0(solb[0].x);
+  const float solr_last = SEAMR ? wave_from_right(solb[0].x, solr_edge) : dpp_right0(solb[0].x);
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const v2f solr = v2f{solb[i].y, i == NP - 1 ? solr_last : solb[i + 1].x};
@@ -172,10 +190,11 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
 
 // Stage 1 of a launch that starts from the zero dual state: (rr, ss, p, q)^0 = 0, so sol^1 = x and the differences with the previous
 // iterate vanish.  Bit-identical to pipe_stage() fed with zeros (x - 0 = x, fma(c, d, 0) = c*d), at ~60 % of its instructions.
-template <int NP, bool LASTLANE = true, bool OBJ = false>
+template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAMR = false>
 __device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb)[NP], float cdown, const PipeCr<NP>& cr, float beta,
-                                                 DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP>* om = nullptr) {
-  const float solr_last = dpp_right0(solb[0].x);
+                                                 DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP>* om = nullptr,
+                                                 float solr_edge = 0.f) {
+  const float solr_last = SEAMR ? wave_from_right(solb[0].x, solr_edge) : dpp_right0(solb[0].x);
   const v2f ncd = pk_set(-cdown), vb = pk_set(beta);
   if constexpr (OBJ) ob->sq = pk_set(0.f);       // sol^0 = x
 #pragma unroll
@@ -281,18 +300,38 @@ __host__ __device__ constexpr int pipe_halo(int K, int KT, int PXL) {
 // at 168 VGPRs, 128-184 spilled.  In the combine wave: its conditional stores make the compiler wait for every load in flight each tick, 4.05 ms per iteration.  In the
 // Philox wave, sums in registers, loads 4 / 8 ticks ahead: 2.41 / 2.32 ms against 1.92 with the reduction on a side stream -- and with the loads alone, no arithmetic,
 // still 2.61 against 2.05 with the arithmetic alone: the CU's outstanding-miss capacity is what the scattered reads take from the L wave's row prefetches.)
-template <int K, int PXL, int KT, bool CHAIN = false, bool WARM = false, bool AL = true, bool RT = false>
-__global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM ? LMC_WARM_MIN_WAVES : 1) : 2) void myula_step_pipe_kernel(const StepArgs A) {
+// TEAMS = 2 (myula_step_pipe2_kernel below): the image width is split between two teams of waves, each a complete set of roles on its half
+// -- 4 pixels per lane, so sixteen waves, four per SIMD, are resident in the LDS and register budget of one 8-pixel team.  The left team's
+// lanes are right-aligned (its last column is lane 63's last pixel; lanes left of column 0 compute on zeros and store nothing), the right
+// team's start at lane 0, so every neighbour across the seam enters through the wave shift the stage makes anyway, with the other team's
+// value in the vacant lane (wave_from_left / wave_from_right).  Those values are in LDS already (ring rows, hand-off rows: the other team's
+// copy sits BW floats away) or are published once per wave per tick into a small record (o_seam):
+//   SA [2][2 (NT + 1)]  left team, lane 63: stage k1's ss edge (slot 2j - 1) and stage k2's = the hand-off's (slot 2j) of wave j
+//   SB [2][2 NT]        right team, lane 0: sol1, sol2 of wave j's first column (slots 2j - 2, 2j - 1)
+//   SR [2][4]           residual edge columns of the blur wave: left team lane 63's last HW (0, 1), right team lane 0's first HW (2, 3)
+// A T wave reads one 8-byte record per tick; the blur wave forms the residual row one tick before its adjoint (the row's seam columns
+// travel through SR).  Every pixel runs the arithmetic of the one-team kernel on the same operands: the results are bit-identical.
+#ifndef LMC_PIPE2_ROLES
+// role of hardware wave w = nibble w: team << 3 | role (0 L, 1..NT T, NT + 1 C, NT + 2 N).  Waves w, w + 4, w + 8, w + 12 share a SIMD: two
+// two-stage T waves beside L + C of one team, or beside N + T1 of one team, on each SIMD
+#define LMC_PIPE2_ROLES 0x5D3BC4A291E6F780ull
+#endif
+template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS>
+__device__ __forceinline__ void pipe_body(const StepArgs& A) {
   static_assert(!WARM || CHAIN, "the warm dual uses the state hand-over of the chained launches");
   static_assert(!RT || (AL && !WARM && (K & 1) == 0), "per-chain exit: aligned rows, cold start, even K");
+  static_assert(TEAMS == 1 || (TEAMS == 2 && K == 10 && PXL == 4 && KT == 5 && AL && !CHAIN && !WARM && !RT),
+                "two teams: one fixed-count launch, 5 taps, aligned rows, 4 pixels per lane");
   using G = PipeGeom<K>;
-  using L = PipeLds<K, PXL, CHAIN>;
-  constexpr int D = G::D, E = G::E, RB = G::RB, NT = G::NT, BW = L::BW, HW = KT > 0 ? (KT - 1) / 2 : 0;
+  using L = PipeLds<K, PXL, CHAIN, TEAMS>;
+  constexpr int D = G::D, E = G::E, RB = G::RB, NT = G::NT, BW = L::BW, RP = L::RP, HW = KT > 0 ? (KT - 1) / 2 : 0;
+  constexpr int LAGT = TEAMS == 2 ? 1 : 0;     // two teams: the residual row is formed one tick before its horizontal adjoint (seam columns via SR)
   static_assert(K >= 1, "at least one dual iteration");
-  static_assert(D >= KT + 1, "the blur pipeline reads ring rows at least one tick old");
-  extern __shared__ float lds[];
+  static_assert(D >= KT + 1 + LAGT, "the blur pipeline reads ring rows at least one tick old");
+  extern __shared__ float lds_all[];
   const int lane = threadIdx.x & 63;
   const int hw_wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int team = 0;
   const int chain = blockIdx.x;
   const int H = A.H, W = A.W;
   // per-chain exit: live stages of this launch, and whether this link only advances the dual state of this chain (it leaves in a later link)
@@ -313,7 +352,11 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
   // wave w is nibble w of the code): fixed K = 10: L + T2 | T1 + T3 | T4 + C | T5 + N 1.736 ms against 1.775 for the plain order and 2.07 for the worst
   // (L + C or L + N with two TV waves together); per-chain exit with one live stage per wave: by live count, below.
   int wave = hw_wave;
-  if constexpr (K == 10 && !RT && !CHAIN) {   // 7 taps: L + C | T1 + T2 | T3 + T5 | T4 + N (1.838 vs 1.875); with the MC-TV term in the combine wave: L + T5 | T1 + T3 | T2 + C | T4 + N (1.962 vs 1.983)
+  if constexpr (TEAMS == 2) {
+    const unsigned nib = (unsigned)(LMC_PIPE2_ROLES >> (4 * hw_wave)) & 15u;
+    team = nib >> 3;
+    wave = nib & 7;
+  } else if constexpr (K == 10 && !RT && !CHAIN) {   // 7 taps: L + C | T1 + T2 | T3 + T5 | T4 + N (1.838 vs 1.875); with the MC-TV term in the combine wave: L + T5 | T1 + T3 | T2 + C | T4 + N (1.962 vs 1.983)
     const unsigned code = A.ncvx_kind == LMC_NCVX_MC_TV ? 0x76354210u : (KT == 7 ? 0x75264310u : 0x76325410u);
     wave = (code >> (4 * hw_wave)) & 15;
   }
@@ -338,25 +381,41 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
     else wave = hw_wave == 4 ? 6 : hw_wave == 6 ? 4 : hw_wave;        // more live stages: L + C | T1 + T5 | T2 + T4 | T3 + N
   }
 #ifdef LMC_EXP_PERM   // timing experiment (scripts/round3/perm_search.py): role of hardware wave w = nibble w of A.PH (the tile kernel's field, unused here)
-  if (A.PH && (LMC_EXP_PERM == 1 || CHAIN)) wave = (A.PH >> (4 * hw_wave)) & 15;      // LMC_EXP_PERM=2: the chained links only
+  if (TEAMS == 1 && A.PH && (LMC_EXP_PERM == 1 || CHAIN)) wave = (A.PH >> (4 * hw_wave)) & 15;      // LMC_EXP_PERM=2: the chained links only
 #endif
   // column strip of this workgroup (blockIdx.y; one strip = the whole row when W <= 64 PXL): c0 is a GLOBAL column, LDS rows are indexed by lane
   constexpr int HALO = pipe_halo(K, KT, PXL);
   const int strip = blockIdx.y;
   const int strip_u = gridDim.y > 1 ? BW - 2 * HALO : W;
-  const int c0 = (strip ? strip * strip_u - HALO : 0) + lane * PXL;
-  const int st_lo = strip * strip_u, st_hi = min(W, st_lo + strip_u);       // columns this workgroup writes
+  int c0 = (strip ? strip * strip_u - HALO : 0) + lane * PXL;
+  int st_lo = strip * strip_u, st_hi = min(W, st_lo + strip_u);       // columns this workgroup writes
+  if constexpr (TEAMS == 2) {          // left team [0, W/2), lanes right-aligned; right team [W/2, W) from lane 0 (one strip)
+    const int Wt = W >> 1;
+    c0 = team ? Wt + lane * PXL : Wt - BW + lane * PXL;
+    st_lo = team ? Wt : 0;
+    st_hi = team ? W : Wt;
+  }
+  // the lane's columns are image columns of its team (two teams; one group of 4 pixels per lane), and the column its global loads start at
+  const bool cok = c0 >= st_lo && c0 < st_hi;
+  const int cl = TEAMS == 2 ? (cok ? c0 : 0) : c0;
+  auto col_in = [&](int k) __attribute__((always_inline)) -> bool { return TEAMS == 2 ? cok : c0 + k < W; };
   constexpr bool al = AL;                                                    // rows are 16-byte aligned (strip_u and HALO are multiples of 4)
   const size_t img = (size_t)H * W;
   const float* __restrict__ xin = A.x_in + (size_t)chain * img;
   float* __restrict__ xout = A.x_out + (size_t)chain * img;
 
-  for (int e = threadIdx.x; e < L::o_slab; e += blockDim.x) lds[e] = 0.f;   // ring rows < 0, hand-offs of tick -1, g
+  // ring rows < 0, hand-offs of tick -1, g (two teams: and the seam records)
+  for (int e = threadIdx.x; e < (TEAMS == 2 ? L::total : L::o_slab); e += blockDim.x) lds_all[e] = 0.f;
   __syncthreads();
+  float* const lds = lds_all + team * BW;                   // this team's copy of every row (row pitch RP)
+  float* const slab_base = lds_all + L::o_slab + team * L::SLAB;
+  float* const seam = lds_all + L::o_seam;
+  constexpr int SA = 0, SB = 4 * (NT + 1), SR = SB + 4 * NT;  // seam records (see above), [2 parities] each
+  static_assert(TEAMS == 1 || SR + 8 <= L::total - L::o_seam, "seam records");
 
   const int T_end = (H + D + 3) & ~3;          // ticks, rounded up to the unroll factor (extra ticks write nothing)
   float* const xring = lds + L::o_x;
-  auto ring_row = [&](int row) -> float* { return xring + ((unsigned)(row + RB) % (unsigned)RB) * BW; };   // row >= -RB
+  auto ring_row = [&](int row) -> float* { return xring + ((unsigned)(row + RB) % (unsigned)RB) * RP; };   // row >= -RB
 
 #ifdef LMC_EXP_SKIP   // timing experiment (with LMC_EXP_NOBARRIER): the waves in the bitmask leave at once (results are wrong)
   if ((LMC_EXP_SKIP >> wave) & 1) return;
@@ -374,6 +433,9 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
   else if (wave == NT + 1) __builtin_amdgcn_s_setprio(LMC_PRIO_C);
   else if (wave <= NT) __builtin_amdgcn_s_setprio(LMC_PRIO_T);
   else __builtin_amdgcn_s_setprio(LMC_PRIO_N);
+  // the roles, once per team (two teams: the seam code of each team is static)
+  auto roles = [&](auto team_tag) __attribute__((always_inline)) {
+  constexpr int TM = decltype(team_tag)::value;
   if (wave == 0) {
     // ---------------- L: loader + blur gradient -------------------------------------------------------------
     const float* __restrict__ uv = A.blur.h;   // centred taps: u[0..KT) then v[0..KT) at h[kMaxBlur..]
@@ -384,21 +446,23 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
     // x rows: fetched kXPF ticks ahead, slot (tick & 3) (8 ahead was measured: no gain, +50 VGPRs)
     constexpr int kXPF = 4;
     float xpre[kXPF][PXL], hxw[NWIN][PXL], hrw[NWIN][PXL], ypre[4][PXL];   // y rows: fetched kYPF ticks ahead, slot (tick & 3)
-    constexpr int kYPF = KT == 7 ? 2 : 3;     // 7 taps: the windows already take 96 registers
+    // 7 taps: the windows already take 96 registers; two teams: 112 VGPRs per wave, so that a wave of the side-stream moment reduction (64)
+    // still fits beside the four of a workgroup on each SIMD (at 120 it waited for whole CUs: 2.08 against 1.80 ms per step)
+    constexpr int kYPF = (KT == 7 || TEAMS == 2) ? 2 : 3;
 #pragma unroll
     for (int a = 0; a < NWIN; ++a)
 #pragma unroll
       for (int k = 0; k < PXL; ++k) { hxw[a][k] = 0.f; hrw[a][k] = 0.f; }
 #pragma unroll
-    for (int u = 0; u < kXPF; ++u) gload_raw<PXL>(xpre[u], xin + (size_t)min(u, H - 1) * W, c0, W, al);
+    for (int u = 0; u < kXPF; ++u) gload_raw<PXL>(xpre[u], xin + (size_t)min(u, H - 1) * W, cl, W, al);
     // Vector-memory loads return in order: waiting for a load also waits for every load issued before it.  So the loads a tick
     // consumes must be the OLDEST in flight: y rows are requested three ticks ahead and, inside a tick, before the x row that is only
     // needed four ticks later (with y one tick ahead and issued after x, every tick waited for a fresh HBM access: ~2000 cycles).
     if constexpr (KT > 0) {   // observation rows of the first kYPF residual rows
 #pragma unroll
       for (int u = 0; u < kYPF; ++u) {
-        const int r = u + 1 - D + (KT - 1) - HW;
-        gload_raw<PXL>(ypre[u], A.y + (size_t)min(max(r, 0), H - 1) * W, c0, W, al);
+        const int r = u + 1 - D + (KT - 1) - HW + LAGT;
+        gload_raw<PXL>(ypre[u], A.y + (size_t)min(max(r, 0), H - 1) * W, cl, W, al);
       }
     }
     // Without a blur: pointwise data terms (identity, diagonal mask).  Their gradient sigma_f m (m x - y) of row t + 1 - D -- the row the
@@ -440,11 +504,14 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
       }
     }
     double facc = 0.0;        // sum of squared residuals (A.f_out)
+    float Rprev[TEAMS == 2 ? PXL : 1];      // two teams: last tick's residual row (LAGT)
+#pragma unroll
+    for (int k = 0; k < (TEAMS == 2 ? PXL : 1); ++k) Rprev[k] = 0.f;
     auto tick = [&](auto uu, const int t) __attribute__((always_inline)) {
       constexpr int U = decltype(uu)::value, P = U & 1;
       if constexpr (KT > 0) {   // observation row of the residual row kYPF ticks from now
-        const int r3 = t + kYPF + 1 - D + (KT - 1) - HW;
-        gload_raw<PXL>(ypre[(U + kYPF) & 3], A.y + (size_t)min(max(r3, 0), H - 1) * W, c0, W, al);
+        const int r3 = t + kYPF + 1 - D + (KT - 1) - HW + LAGT;
+        gload_raw<PXL>(ypre[(U + kYPF) & 3], A.y + (size_t)min(max(r3, 0), H - 1) * W, cl, W, al);
       } else if (pw_id || pw_mask) {
         const size_t ro = (size_t)min(max(t + kYPF + 1 - D, 0), H - 1) * W;
         gload_raw<PXL>(ypre[(U + kYPF) & 3], A.y + ro, c0, W, al);
@@ -454,12 +521,12 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
         float xv[PXL];
         gfix_raw<PXL, AL>(xpre[U], c0, W);
 #pragma unroll
-        for (int k = 0; k < PXL; ++k) xv[k] = (t < H && c0 + k < W) ? xpre[U][k] : 0.f;
+        for (int k = 0; k < PXL; ++k) xv[k] = (t < H && col_in(k)) ? xpre[U][k] : 0.f;
         prow_store<PXL>(ring_row(t), lane, xv);
-        gload_raw<PXL>(xpre[U], xin + (size_t)min(t + kXPF, H - 1) * W, c0, W, al);
+        gload_raw<PXL>(xpre[U], xin + (size_t)min(t + kXPF, H - 1) * W, cl, W, al);
       }
       if constexpr (CHAIN) {   // dual state row t - E - 1 of the previous link -> stage 1's hand-off slot P (read next tick)
-        float* hb = lds + L::o_hand0 + P * 4 * BW;
+        float* hb = lds + L::o_hand0 + P * 4 * RP;
         constexpr int SP = U & (kSPF - 1);
         const int rh = t - E - 1;                                  // the row fetched kSPF ticks ago
         const bool rowok_h = sin && rh >= 0 && rh < H;
@@ -469,7 +536,7 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
           float sv[PXL];
 #pragma unroll
           for (int k = 0; k < PXL; ++k) sv[k] = (rowok_h && c0 + (AL ? (k & ~3) : k) < W) ? spre[SP][f][k] : 0.f;
-          prow_store<PXL>(hb + f * BW, lane, sv);
+          prow_store<PXL>(hb + f * RP, lane, sv);
         }
         const int rs = t + kSPF - E - 1;
 #pragma unroll
@@ -477,17 +544,19 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
           gload_raw<PXL>(spre[SP][f], sin ? sin + (size_t)f * img + (size_t)min(max(rs, 0), H - 1) * W : xin, c0, W, al);
       }
       if constexpr (KT > 0) {
-      const int i = t + 1 - D + (KT - 1);       // blur input row (<= t-1: published in an earlier tick)
+      const int i = t + 1 - D + (KT - 1) + LAGT;       // blur input row (<= t-1: published in an earlier tick)
       float hxn[PXL];
       {
         float xi[PXL], e[PXL + 2 * HW];
-        prow_load<PXL>(xi, ring_row(i), lane);
+        const float* const xr = ring_row(i);
+        prow_load<PXL>(xi, xr, lane);
+        // two teams: across the seam, the other team's copy of the same ring row (the left team's last HW columns end its row)
 #pragma unroll
-        for (int m = 0; m < HW; ++m) e[m] = dpp_left0(xi[PXL - HW + m]);
+        for (int m = 0; m < HW; ++m) e[m] = (TEAMS == 2 && TM == 1) ? wave_from_left(xi[PXL - HW + m], xr[m - HW]) : dpp_left0(xi[PXL - HW + m]);
 #pragma unroll
         for (int k = 0; k < PXL; ++k) e[HW + k] = xi[k];
 #pragma unroll
-        for (int m = 0; m < HW; ++m) e[HW + PXL + m] = dpp_right0(xi[m]);
+        for (int m = 0; m < HW; ++m) e[HW + PXL + m] = (TEAMS == 2 && TM == 0) ? wave_from_right(xi[m], xr[BW + m]) : dpp_right0(xi[m]);
 #pragma unroll
         for (int k = 0; k < PXL; ++k) {
           float acc = uv[kMaxBlur] * e[k + 2 * HW];
@@ -509,9 +578,9 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
           for (int a = 1; a < KT; ++a) acc = fmaf(uv[a], hxw[kRing4 ? ((U - a) & 3) : a - 1][k], acc);
           // masked by a factor, not a select: a select on (row, column) turns into one exec-masked block per pixel (8 per tick: the wave's longest
           // stretch of unpacked arithmetic and half of its scalar instructions); every operand is finite (clamped rows, zeroed ring rows)
-          R[k] = (acc - ypre[U & 3][k]) * ((AL ? c0 < W : c0 + k < W) ? rmask : 0.f);
+          R[k] = (acc - ypre[U & 3][k]) * ((TEAMS == 2 ? cok : AL ? c0 < W : c0 + k < W) ? rmask : 0.f);
         }
-        if (A.f_out) {
+        if (TEAMS == 1 && A.f_out) {     // (the energy by-products are not built for two teams: pipe_teams_covered)
 #pragma unroll
           for (int k = 0; k < PXL; ++k) facc = fma((double)R[k], (double)R[k], facc);
         }
@@ -524,14 +593,23 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
 #pragma unroll
         for (int k = 0; k < PXL; ++k) hxw[kRing4 ? (U & 3) : 0][k] = hxn[k];
       }
+      if constexpr (TEAMS == 2) {   // publish this row's seam columns for the other team; the adjoint below runs on LAST tick's row
+        if (TM == 0 ? lane == 63 : lane == 0) {
+#pragma unroll
+          for (int m = 0; m < HW; ++m) seam[SR + P * 4 + 2 * TM + m] = R[TM == 0 ? PXL - HW + m : m];
+        }
+#pragma unroll
+        for (int k = 0; k < PXL; ++k) { const float tmp = R[k]; R[k] = Rprev[k]; Rprev[k] = tmp; }
+      }
       {   // horizontal adjoint, then G[r - HW] = sum_a u[a] hR[r - 2HW + a]
         float e[PXL + 2 * HW], gout[PXL];
+        const float* const sr = seam + SR + (P ^ 1) * 4;          // two teams: the other team's seam columns of the row
 #pragma unroll
-        for (int m = 0; m < HW; ++m) e[m] = dpp_left0(R[PXL - HW + m]);
+        for (int m = 0; m < HW; ++m) e[m] = (TEAMS == 2 && TM == 1) ? wave_from_left(R[PXL - HW + m], sr[m]) : dpp_left0(R[PXL - HW + m]);
 #pragma unroll
         for (int k = 0; k < PXL; ++k) e[HW + k] = R[k];
 #pragma unroll
-        for (int m = 0; m < HW; ++m) e[HW + PXL + m] = dpp_right0(R[m]);
+        for (int m = 0; m < HW; ++m) e[HW + PXL + m] = (TEAMS == 2 && TM == 0) ? wave_from_right(R[m], sr[2 + m]) : dpp_right0(R[m]);
 #pragma unroll
         for (int k = 0; k < PXL; ++k) {
           float hrn = uv[kMaxBlur] * e[k];
@@ -547,7 +625,7 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
           hrw[kRing4 ? (U & 3) : 0][k] = hrn;
           gout[k] = A.sigma_f * acc;
         }
-        prow_store<PXL>(lds + L::o_g + P * BW, lane, gout);      // row t + 1 - D, read by C next tick
+        prow_store<PXL>(lds + L::o_g + P * RP, lane, gout);      // row t + 1 - D, read by C next tick
       }
       }   // KT > 0
       if constexpr (KT == 0) {
@@ -567,13 +645,13 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
             }
             gout[k] = g;
           }
-          prow_store<PXL>(lds + L::o_g + P * BW, lane, gout);      // row t + 1 - D, read by C next tick
+          prow_store<PXL>(lds + L::o_g + P * RP, lane, gout);      // row t + 1 - D, read by C next tick
         }
       }
       PIPE_TICK_SYNC();
     };
     for (int t = 0; t < T_end; t += 4) static_for<0, 4>([&](auto uu) { tick(uu, t + decltype(uu)::value); });
-    if (A.f_out) {
+    if (TEAMS == 1 && A.f_out) {
       const double tot = wave_sum(facc);
       if (lane == 0) unsafeAtomicAdd(&A.f_out[chain], 0.5 * (double)A.sigma_f * tot);
     }
@@ -594,13 +672,13 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
     const float beta1 = A.tv.betas[g1 - 1], beta2 = SINGLE ? 0.f : A.tv.betas[g2 - 1];
     PipeCr<PXL / 2> crc;                                              // see PipeCr: AL kernels need W % PXL == 0 (host check), the others take any W
     crc.cstep = cstep;
-    crc.cr_last = (c0 + PXL - 1 == W - 1) ? 0.f : cstep;
+    crc.cr_last = (c0 + PXL - 1 == W - 1 || (TEAMS == 2 && !cok)) ? 0.f : cstep;   // (two teams: ss stays 0 left of column 0)
 #pragma unroll
     for (int i = 0; i < PXL / 2; ++i) crc.ncrv[i] = v2f{c0 + 2 * i == W - 1 ? 0.f : -cstep, c0 + 2 * i + 1 == W - 1 ? 0.f : -cstep};
-    float* const hout = lds + L::o_hand + (wave - 1) * 8 * BW;       // this wave's hand-off [2][4][BW] ([2][2][BW] for the last one if CHAIN)
+    float* const hout = lds + L::o_hand + (wave - 1) * 8 * RP;       // this wave's hand-off [2][4][BW] ([2][2][BW] for the last one if CHAIN)
     const bool from_state = CHAIN && wave == 1 && A.tv_in != nullptr;
     constexpr bool warm = WARM;
-    const float* const hin = from_state ? lds + L::o_hand0 : hout - 8 * BW;   // the previous wave's / the previous link's state
+    const float* const hin = from_state ? lds + L::o_hand0 : hout - 8 * RP;   // the previous wave's / the previous link's state
     constexpr int nof = warm ? 2 : 4;                                // fields per pixel of the outgoing state
     float* const sout = CHAIN && wave == NT && A.tv_out && (!RT || state_only) ? A.tv_out + (size_t)chain * nof * img : nullptr;
     constexpr int NP = PXL / 2;
@@ -627,29 +705,29 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
     // chained launch, to HBM for the next link (all four fields) or the next MYULA iteration (warm dual: p, q)
     auto emit = [&](const DualRow<NP>& out, const int P, const int brow, const bool live) __attribute__((always_inline)) {
       if (RT && !live) {             // pass-through: only (rr, ss) travel on (the combine wave's operands); same slots in both hand-off layouts
-        float* hb = hout + P * ((!CHAIN || wave < NT) ? 4 : 2) * BW;
+        float* hb = hout + P * ((!CHAIN || wave < NT) ? 4 : 2) * RP;
         pairs_store<NP>(hb, lane, out.rr);
-        pairs_store<NP>(hb + BW, lane, out.ss);
+        pairs_store<NP>(hb + RP, lane, out.ss);
       } else if (!CHAIN || wave < NT) {
-        float* hb = hout + P * 4 * BW;
+        float* hb = hout + P * 4 * RP;
 #ifdef LMC_EXP_NO_HSTORE     // timing experiment: the hand-off stores never execute (results are wrong), the arithmetic stays alive
         if (A.tv.niter == 12345)
 #endif
         {
         pairs_store<NP>(hb, lane, out.rr);
-        pairs_store<NP>(hb + BW, lane, out.ss);
+        pairs_store<NP>(hb + RP, lane, out.ss);
 #ifdef LMC_EXP_HALF_HSTORE   // timing experiment: half the hand-off stores
         if (A.tv.niter == 12345)
 #endif
         if (wave < NT) {     // the combine wave reads rr, ss only: the last TV wave (which shares its SIMD with T1) skips half of its hand-off stores
-        pairs_store<NP>(hb + 2 * BW, lane, out.p);
-        pairs_store<NP>(hb + 3 * BW, lane, out.q);
+        pairs_store<NP>(hb + 2 * RP, lane, out.p);
+        pairs_store<NP>(hb + 3 * RP, lane, out.q);
         }
         }
       } else {
-        float* hb = hout + P * 2 * BW;                   // last boundary of a chained launch: rr, ss for the final primal step ...
+        float* hb = hout + P * 2 * RP;                   // last boundary of a chained launch: rr, ss for the final primal step ...
         pairs_store<NP>(hb, lane, out.rr);
-        pairs_store<NP>(hb + BW, lane, out.ss);
+        pairs_store<NP>(hb + RP, lane, out.ss);
         if (sout && brow >= 0 && brow < H) {             // ... and the dual state of row brow for the next link / iteration
 #pragma unroll
           for (int g = 0; g < NP / 2; ++g) {
@@ -668,16 +746,24 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
         }
       }
     };
+    // two teams: the neighbours across the seam, published by the other team one tick ago (left team: sol1, sol2 of the right team's
+    // first column, for solr; right team: the left team's ss edges of stage k1 of the previous wave's hand-off and of this wave's stage k1, for ssl)
+    constexpr bool SL = TEAMS == 2 && TM == 1, SRt = TEAMS == 2 && TM == 0;
+    const float* const seam_in = seam + (TM == 1 ? SA + 2 * wave - 2 : SB + 2 * (wave - 1));
+    float* const seam_out = seam + (TM == 0 ? SA + 2 * wave - 1 : SB + 2 * (wave - 1));
     auto tick = [&](auto uu, const int t) __attribute__((always_inline)) {
       constexpr int P = decltype(uu)::value & 1;
       const int a2 = t - E - 2 * k2, a1 = t - E - 2 * k1;
+      float2 edge = make_float2(0.f, 0.f);     // (k1, k2): ssl edges (right team) or solr edges (left team)
+      if constexpr (TEAMS == 2) edge = *reinterpret_cast<const float2*>(seam_in + (P ^ 1) * (TM == 1 ? 2 * (NT + 1) : 2 * NT));
+      float ss2_edge = 0.f;
       if constexpr (!SINGLE) {   // stage k2 on row a2: inputs are this wave's stage k1, one tick (row a2) and two ticks (row a2-1) old
         const float cdown = ((unsigned)(a2 - 1) >= (unsigned)(H - 1)) ? 0.f : cstep;
         DualRow<NP> out;
         if (live2) {
           StageObj ob;
           om.md = cdown != 0.f ? 1.f : 0.f;
-          pipe_stage<NP, AL, RT>(xk[P], o1[P ^ 1].rr, o1[P ^ 1].ss, o1[P], sol2, gam, cdown, crc, beta2, out, &ob, &om);
+          pipe_stage<NP, AL, RT, SL, SRt>(xk[P], o1[P ^ 1].rr, o1[P ^ 1].ss, o1[P], sol2, gam, cdown, crc, beta2, out, &ob, &om, edge.y, edge.y);
           if constexpr (RT) { osq2 += (double)(ob.sq.x + ob.sq.y); otv2 += (double)(ob.tv.x + ob.tv.y); }
         } else {                 // pass-through: the state of row a2 - 1 as stage k1 left it
 #pragma unroll
@@ -688,19 +774,20 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
           }
         }
         emit(out, P, a2 - 1, live2 || fullpass2);
+        ss2_edge = out.ss[NP - 1].y;
       }
       {   // stage k1 on row a1: inputs from the previous wave's hand-off (row a1) and the one read a tick earlier (row a1-1)
         if constexpr (!FIRST) {
           if (k1 > 1 || from_state) {
-            const float* hb = hin + (P ^ 1) * 4 * BW;
+            const float* hb = hin + (P ^ 1) * 4 * RP;
             pairs_load<NP>(inb[P].rr, hb, lane);
-            pairs_load<NP>(inb[P].ss, hb + BW, lane);
+            pairs_load<NP>(inb[P].ss, hb + RP, lane);
             if (from_state && warm) {     // warm dual: the state IS the projected iterate (beta_1 = 0 makes its role as p_old void)
 #pragma unroll
               for (int k = 0; k < NP; ++k) { inb[P].p[k] = inb[P].rr[k]; inb[P].q[k] = inb[P].ss[k]; }
             } else if (live1) {           // (a pass-through stage moves rr, ss only)
-              pairs_load<NP>(inb[P].p, hb + 2 * BW, lane);
-              pairs_load<NP>(inb[P].q, hb + 3 * BW, lane);
+              pairs_load<NP>(inb[P].p, hb + 2 * RP, lane);
+              pairs_load<NP>(inb[P].q, hb + 3 * RP, lane);
             }
           }
         }
@@ -709,14 +796,21 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
           const float cdown = ((unsigned)(a1 - 1) >= (unsigned)(H - 1)) ? 0.f : cstep;
           StageObj ob;
           om.md = cdown != 0.f ? 1.f : 0.f;
-          if constexpr (FIRST) pipe_stage_first<NP, AL, RT>(xk[P], sol1, cdown, crc, beta1, o1[P], &ob, &om);
-          else pipe_stage<NP, AL, RT>(xk[P], inb[P].rr, inb[P].ss, inb[P ^ 1], sol1, gam, cdown, crc, beta1, o1[P], &ob, &om);
+          if constexpr (FIRST) pipe_stage_first<NP, AL, RT, SRt>(xk[P], sol1, cdown, crc, beta1, o1[P], &ob, &om, edge.x);
+          else pipe_stage<NP, AL, RT, SL, SRt>(xk[P], inb[P].rr, inb[P].ss, inb[P ^ 1], sol1, gam, cdown, crc, beta1, o1[P], &ob, &om, edge.x, edge.x);
           if constexpr (RT) { osq1 += (double)(ob.sq.x + ob.sq.y); otv1 += (double)(ob.tv.x + ob.tv.y); }
         } else {                 // pass-through: the state of row a1 - 1, read one tick ago
 #pragma unroll
           for (int k = 0; k < NP; ++k) { o1[P].rr[k] = inb[P ^ 1].rr[k]; o1[P].ss[k] = inb[P ^ 1].ss[k]; }
         }
         if constexpr (SINGLE) emit(o1[P], P, a1 - 1, live1);
+      }
+      if constexpr (TEAMS == 2) {   // this tick's seam values for the other team's next tick: one record per wave, from the seam lane
+        float* const so = seam_out + P * (TM == 0 ? 2 * (NT + 1) : 2 * NT);
+        if (TM == 0 ? lane == 63 : lane == 0) {
+          so[0] = TM == 0 ? o1[P].ss[NP - 1].y : sol1[0].x;
+          so[1] = TM == 0 ? ss2_edge : sol2[0].x;
+        }
       }
       PIPE_TICK_SYNC();
     };
@@ -753,7 +847,7 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
     // ---------------- N: Philox normals, one quad row-group ahead of C -------------------------------------
     // In the tick of row 4q + NI the normals of pixels NI*PXL/4 .. of quad q + 1 are drawn into the other half of the slab
     // (spread evenly over the ticks: a burst every 4th tick would stall every wave at the barrier).
-    float* const slab = lds + L::o_slab + lane;        // normal (row q of the quad, pixel k) at slab[(q*PXL + k)*64]
+    float* const slab = slab_base + lane;              // normal (row q of the quad, pixel k) at slab[(q*PXL + k)*64]
     const uint32_t iter = A.iteration;
     auto tick = [&](auto uu, const int t) __attribute__((always_inline)) {
       constexpr int U = decltype(uu)::value;
@@ -785,9 +879,9 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
     auto c_role = [&](auto vm_tag) __attribute__((always_inline)) {
     constexpr bool VM = decltype(vm_tag)::value;
     const float gam = A.tv.gamma;
-    const float* const hin = lds + L::o_hand + (NT - 1) * 8 * BW;      // [2][4][BW], or [2][2][BW] in a chained launch
-    constexpr int HSTR = CHAIN ? 2 * BW : 4 * BW;
-    float* const slab = lds + L::o_slab + lane;        // normal (row q of the quad, pixel k) at slab[(q*PXL + k)*64]
+    const float* const hin = lds + L::o_hand + (NT - 1) * 8 * RP;      // [2][4][BW], or [2][2][BW] in a chained launch
+    constexpr int HSTR = CHAIN ? 2 * RP : 4 * RP;
+    float* const slab = slab_base + lane;              // normal (row q of the quad, pixel k) at slab[(q*PXL + k)*64]
     double gacc = 0.0;        // sum |grad x_in| (A.g_out)
     float crr[2][PXL], xprev[PXL];
 #pragma unroll
@@ -806,11 +900,12 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
     for (int u = 0; u < 4; ++u)
 #pragma unroll
       for (int k = 0; k < PXL; ++k) exq[u][k] = 0.f;
-    if (VM && A.extra) {
+    constexpr bool XT = TEAMS == 1;      // the ME-TV / MC-TV terms and the energy by-products (one team only: pipe_teams_covered)
+    if (XT && VM && A.extra) {
 #pragma unroll
       for (int u = 0; u < 3; ++u) {
         const int r = u - D;
-        gload_raw<PXL>(exq[u], A.extra + (size_t)chain * img + (size_t)min(max(r, 0), H - 1) * W, c0, W, al);
+        gload_raw<PXL>(exq[u], A.extra + (size_t)chain * img + (size_t)min(max(r, 0), H - 1) * W, cl, W, al);
       }
     }
     auto tick = [&](auto uu, const int t) __attribute__((always_inline)) {
@@ -818,21 +913,22 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
       constexpr int NI = ((U - D) % 4 + 4) % 4;        // == o & 3  (t = 4m + U)
       const int o = t - D;
       if (state_only) { PIPE_TICK_SYNC(); return; }     // this link only advances the dual state (of this chain)
-      if (VM && A.extra) {
+      if (XT && VM && A.extra) {
         const int r3 = o + 3;
-        gload_raw<PXL>(exq[(U + 3) & 3], A.extra + (size_t)chain * img + (size_t)min(max(r3, 0), H - 1) * W, c0, W, al);
+        gload_raw<PXL>(exq[(U + 3) & 3], A.extra + (size_t)chain * img + (size_t)min(max(r3, 0), H - 1) * W, cl, W, al);
       }
       float css[PXL], xo[PXL], gv[PXL], prox[PXL];
       prow_load<PXL>(crr[P], hin + (P ^ 1) * HSTR, lane);            // rr^K on row o (written last tick)
-      prow_load<PXL>(css, hin + (P ^ 1) * HSTR + BW, lane);
+      prow_load<PXL>(css, hin + (P ^ 1) * HSTR + RP, lane);
       prow_load<PXL>(xo, ring_row(o), lane);
       if (KT > 0 || A.data_kind == LMC_DATA_IDENTITY || A.data_kind == LMC_DATA_MASK) {
-        prow_load<PXL>(gv, lds + L::o_g + (P ^ 1) * BW, lane);
+        prow_load<PXL>(gv, lds + L::o_g + (P ^ 1) * RP, lane);
       } else {                                  // no data term: o_g is never written (stale LDS could hold NaN bit patterns)
 #pragma unroll
         for (int j = 0; j < PXL; ++j) gv[j] = 0.f;
       }
-      const float ssl0 = dpp_left0(css[PXL - 1]);
+      // two teams, right team: the left team's ss^K edge, published with its hand-off row (SA slot 2 NT)
+      const float ssl0 = (TEAMS == 2 && TM == 1) ? wave_from_left(css[PXL - 1], seam[SA + (P ^ 1) * 2 * (NT + 1) + 2 * NT]) : dpp_left0(css[PXL - 1]);
       float dvs = 0.f;
 #pragma unroll
       for (int j = 0; j < PXL; ++j) {
@@ -859,7 +955,7 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
           for (int j = 0; j < PXL; ++j) pprev[j] = prox[j];
         }
       }
-      if (A.ncvx_kind == LMC_NCVX_MC_TV) {   // - lambda * A^T(A x / max(|A x|, gamma))  (algs.py:273-277, 291), added to the gradient
+      if (XT && A.ncvx_kind == LMC_NCVX_MC_TV) {   // - lambda * A^T(A x / max(|A x|, gamma))  (algs.py:273-277, 291), added to the gradient
         // v = A x / max(|A x|, gamma) is formed ONCE per pixel, row by row: (vx, vy) of row o from ring rows o, o + 1; A^T v at (o, j) = -((vx[o][j] -
         // vx[o-1][j]) + (vy[o][j] - vy[o][j-1])) with vx of the previous row kept in registers.  The same values, operation for operation, as
         // mc_tv_grad (lmc_device.h) recomputes per pixel for its three weights -- a third of the square roots and reciprocals (round 3: the
@@ -889,7 +985,7 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
           xprev[j] = vx[j];          // (xprev: vx of the previous row)
         }
       }
-      if (A.g_out && o >= 0 && o < H) {   // isotropic TV of the input image, row o: forward differences, zero across the last row / column
+      if (XT && A.g_out && o >= 0 && o < H) {   // isotropic TV of the input image, row o: forward differences, zero across the last row / column
         float xq[PXL];
         prow_load<PXL>(xq, ring_row(o + 1), lane);
         const float xr_last = dpp_right0(xo[0]);
@@ -918,7 +1014,7 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
                 xi[0] = v.x; xi[1] = v.y; xi[2] = v.z; xi[3] = v.w;
               } else load4_dword_aligned(xi[0], xi[1], xi[2], xi[3], nrow, c0 + 4 * g, W);
             }
-            if (VM && A.extra) {
+            if (XT && VM && A.extra) {
               ex[0] = exq[U][4 * g]; ex[1] = exq[U][4 * g + 1]; ex[2] = exq[U][4 * g + 2]; ex[3] = exq[U][4 * g + 3];
               if constexpr (!AL) unshift4_dword_aligned(ex[0], ex[1], ex[2], ex[3], c0 + 4 * g, W);
             }
@@ -927,7 +1023,7 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
             for (int q = 0; q < 4; ++q) {
               const float x = xo[4 * g + q];
               float gr = gv[4 * g + q];
-              if (VM && A.extra) gr = fmaf(A.extra_coef, x - ex[q], gr);
+              if (XT && VM && A.extra) gr = fmaf(A.extra_coef, x - ex[q], gr);
               ov[q] = fmaf(A.a, x, fmaf(-A.t, gr, fmaf(A.b, prox[4 * g + q], A.s * xi[q])));
             }
             gstore4(xout + go, c0 + 4 * g, st_lo, st_hi, al, ov[0], ov[1], ov[2], ov[3]);
@@ -937,7 +1033,7 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
       PIPE_TICK_SYNC();
     };
     for (int t = 0; t < T_end; t += 4) static_for<0, 4>([&](auto uu) { tick(uu, t + decltype(uu)::value); });
-    if (A.g_out) {
+    if (XT && A.g_out) {
       const double tot = wave_sum(gacc);
       if (lane == 0) unsafeAtomicAdd(&A.g_out[chain], (double)A.g_scale * tot);
     }
@@ -957,6 +1053,24 @@ __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM
     if (A.extra != nullptr || A.noise_mode == LMC_NOISE_INJECTED) c_role(std::true_type{});
     else c_role(std::false_type{});
   }
+  };   // roles
+  if constexpr (TEAMS == 2) {
+    if (team) roles(std::integral_constant<int, 1>{});
+    else roles(std::integral_constant<int, 0>{});
+  } else {
+    roles(std::integral_constant<int, 0>{});
+  }
+}
+
+template <int K, int PXL, int KT, bool CHAIN = false, bool WARM = false, bool AL = true, bool RT = false>
+__global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM ? LMC_WARM_MIN_WAVES : 1) : 2) void myula_step_pipe_kernel(const StepArgs A) {
+  pipe_body<K, PXL, KT, CHAIN, WARM, AL, RT, 1>(A);
+}
+
+// the two-team layout (pipe_body, TEAMS = 2): 16 waves of 4 pixels per lane, four per SIMD (at most 128 VGPRs)
+template <int K, int KT>
+__global__ __launch_bounds__(128 * ((K + 1) / 2 + 3), 4) void myula_step_pipe2_kernel(const StepArgs A) {
+  pipe_body<K, 4, KT, false, false, true, false, 2>(A);
 }
 
 
@@ -985,6 +1099,25 @@ static hipError_t pipe_launch_one(const StepArgs& a, hipStream_t st) {
   return hipGetLastError();
 #endif
   hipLaunchKernelGGL(kern, dim3(a.C, nstrips), dim3(64 * ((K + 1) / 2 + 3)), lb, st, a);
+  return hipGetLastError();
+}
+
+// the two-team kernel (one launch, K = 10, 5 taps, 264 <= W <= 512, W % 8 == 0: pipe_teams_covered)
+template <int K, int KT>
+static hipError_t pipe_launch_teams(const StepArgs& a, hipStream_t st) {
+  auto kern = myula_step_pipe2_kernel<K, KT>;
+  constexpr size_t lb = sizeof(float) * (size_t)PipeLds<K, 4, false, 2>::total;
+  static_assert(lb <= 160 * 1024, "LDS of one workgroup");
+  static bool attr_set[64] = {};
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
+    if (e != hipSuccess) return e;
+    if (dev >= 0 && dev < 64) attr_set[dev] = true;
+  }
+  hipLaunchKernelGGL(kern, dim3(a.C), dim3(128 * ((K + 1) / 2 + 3)), lb, st, a);
   return hipGetLastError();
 }
 
