@@ -1,0 +1,222 @@
+// Internals of the C-ABI host code, shared by its translation units (not installed):
+//   lmc_capi.hip        the stateless extern "C" entry points, the last error, the stateless scratch
+//   lmc_problem.hip     lmc_problem -> Problem, StepArgs of an update, the step-kernel dispatch, the library defaults
+//   lmc_solve.hip       the implicit step (I + ts H^T H) u = rhs: Chebyshev, CG
+//   lmc_tv_exit.hip     the early exits of the TV prox, the ME-TV inner prox and envelope
+//   lmc_sampler.hip     the MYULA, MYMALA and ULPDA samplers
+//   lmc_rccl.hip        the dlopen'd RCCL and the moment all-reduce
+#pragma once
+#include <string>
+#include <vector>
+
+#include "lmc_launch.h"
+
+namespace lmc::host {
+
+// Records the message lmc_last_error returns and passes `code` on.
+int fail(int code, const char* fmt, ...);
+
+#define HIP_TRY(expr)                                                                          \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess) return fail(LMC_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Validated, self-contained copy of an lmc_problem.
+struct Problem {
+  int H = 0, W = 0;
+  int data_kind = 0;
+  float sigma_f = 0.f;
+  const float* y = nullptr;
+  const float* mask = nullptr;
+  lmc::BlurTaps taps{};
+  int prior_kind = 0;
+  float prior_sigma = 0.f;
+  int tv_niter = 0;
+  float tv_step = 0.125f;
+  float betas[lmc::kMaxTvIters] = {};
+  int ncvx_kind = 0;
+  float ncvx_lambda = 0.f, ncvx_gamma = 1.f;
+  int ncvx_niter = 0;
+  int ncvx_aniso = 0;       // ME-TV: the 1-D TV of the flattened image (LMC_NCVX_ME_TV_ANISO)
+  int tv_warm = 0;
+  float tv_rtol = 0.f;      // > 0: pyproximal.TV's per-image early exit (device path tv_prox_rt, or the pass-by-pass path tv_prox_rtol)
+  float ncvx_rtol = 0.f;    // > 0: the same for the inner prox of the ME-TV term (device path only)
+  int tv_exit_path = 0;     // 1: always pass by pass
+  int iters_per_launch = 0, moments_overlap = 0, moments_bg_wgs = 0;   // launch policy (0 = library decides; fixed at sampler creation)
+  int cheb_pair = 1;        // two Chebyshev iterations per launch: 0 never, 1 where they pay, 2 wherever covered
+  int eprox_kind = 0, eprox_mask = 0;   // LMC_PRIOR_EPROX: closed form, which parameters scale with the prox parameter
+  float eprox_p0 = 0.f, eprox_p1 = 0.f;
+  const float* prox_scale = nullptr;   // array-valued epsg: per-chain / per-pixel multiplier of the prox parameter (closed-form priors of MYULA only)
+  int64_t prox_scale_cs = 0, prox_scale_ps = 0;
+  int variant = 0;          // 0: the library default (g_variant)
+  float implicit_tol = 0.f; // 0: the library default (g_cg_tol); < 0: disabled
+};
+
+// Buffers of the device-side early exit of a TV prox (tv_prox_rt): per chain the pass count of the current round (kc; -1 = settled), the pass it left
+// in at the previous call (pred: the prediction of the next one), the primal objectives of the iterates [n][stride], and three counters of re-runs.
+struct RtState {
+  int* kc = nullptr;
+  int* start = nullptr;
+  int* pred = nullptr;
+  double* obj = nullptr;
+  unsigned long long* reruns = nullptr;     // [4]: chains that had to run again after rounds 1 .. 4 (the last stays 0 by construction)
+  int stride = 0;
+  size_t n = 0;
+  hipError_t need(size_t n_img, int niter) {
+    if (n_img <= n && niter + 1 <= stride) return hipSuccess;
+    release();
+    hipError_t e = hipMalloc(&kc, sizeof(int) * n_img);
+    if (e == hipSuccess) e = hipMalloc(&start, sizeof(int) * n_img);
+    if (e == hipSuccess) e = hipMalloc(&pred, sizeof(int) * n_img);
+    if (e == hipSuccess) e = hipMalloc(&obj, sizeof(double) * n_img * (size_t)(niter + 1));
+    if (e == hipSuccess) e = hipMalloc(&reruns, sizeof(unsigned long long) * 4);
+    if (e == hipSuccess) e = hipMemset(pred, 0, sizeof(int) * n_img);           // 0 = no prediction yet: the first call runs every pass
+    if (e == hipSuccess) e = hipMemset(reruns, 0, sizeof(unsigned long long) * 4);
+    if (e == hipSuccess) { n = n_img; stride = niter + 1; }
+    return e;
+  }
+  void release() {
+    if (kc) (void)hipFree(kc);
+    if (start) (void)hipFree(start);
+    if (pred) (void)hipFree(pred);
+    if (obj) (void)hipFree(obj);
+    if (reruns) (void)hipFree(reruns);
+    kc = start = pred = nullptr; obj = nullptr; reruns = nullptr; n = 0; stride = 0;
+  }
+};
+
+// Device scratch for the stateless entry points (grown on demand and never freed: it lives for the life of the process; calls are
+// serialised by the caller, see lmc_atomi.h).  Samplers own their buffers instead.
+struct Scratch {
+  float* state[2] = {nullptr, nullptr};   // TV dual state ping-pong, [n][4][H][W] each
+  float* extra = nullptr;                 // ME-TV inner prox, [n][H][W]
+  float* prox = nullptr;                  // Haar-l1 prox / early-exit TV prox, [n][H][W]
+  float* rtmp = nullptr;                  // early-exit TV prox: the iterate of the current pass, [n][H][W]
+  double* dbl = nullptr;                  // 2*n doubles
+  RtState rt_tv, rt_me;                   // device-side early exit of the TV prior's prox / of the ME-TV inner prox
+  size_t n_state[2] = {0, 0}, n_extra = 0, n_prox = 0, n_rtmp = 0, n_dbl = 0;   // elements allocated
+  // p holds at least n elements afterwards; what it held is not kept when it grows
+  template <class T>
+  static hipError_t grow(T*& p, size_t& have, size_t n) {
+    if (n <= have) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr; have = 0;
+    hipError_t e = hipMalloc(&p, sizeof(T) * n);
+    if (e == hipSuccess) have = n;
+    return e;
+  }
+  hipError_t need_state(size_t n) {
+    hipError_t e = grow(state[0], n_state[0], n);
+    return e == hipSuccess ? grow(state[1], n_state[1], n) : e;
+  }
+  hipError_t need_extra(size_t n) { return grow(extra, n_extra, n); }
+  hipError_t need_prox(size_t n) { return grow(prox, n_prox, n); }
+  hipError_t need_rtmp(size_t n) { return grow(rtmp, n_rtmp, n); }
+  hipError_t need_dbl(size_t n) { return grow(dbl, n_dbl, n); }
+};
+// The scratch of the current device: a process may drive several GPUs (one sampler handle each); the stateless entry points run on the current device.
+Scratch& scratch_here();
+
+// Makes `dev` the current device for the duration of a call on a handle that lives there, and restores the caller's device.
+struct DeviceGuard {
+  int prev = -1;
+  bool switched = false;
+  explicit DeviceGuard(int dev) {
+    if (dev < 0) return;
+    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
+  }
+  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
+};
+
+// batches of side-stream moment reductions one lmc_sampler_step call keeps in flight (the default policies have two at a time; one more
+// first waits for the oldest)
+constexpr int kSideBatches = 4;
+
+// ---- lmc_problem.hip ----
+int fill_taps(lmc::BlurTaps& T, const float* h, int kh, int kw, int oy, int ox);
+void default_betas(float* b, int n);
+int load_problem(const lmc_problem* p, Problem& q);
+int make_step_args(const Problem& q, float a, float t, float b, float pt, float s, lmc::StepArgs& A);
+void sanitize_pointers(lmc::StepArgs& A);
+int variant_of(const Problem& q);
+float tol_of(const Problem& q);
+hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0 = nullptr,
+                       float* state1 = nullptr, float* pxbuf = nullptr);
+
+// ---- lmc_solve.hip ----
+int cg_solve_fused(const Problem& q, float ts, float* u, const float* rhs, float* r, float* p, float* qq, double* scal,
+                   int64_t C, int niter, const float* zero_y, hipStream_t st, float* alt_out = nullptr, float** result = nullptr);
+
+// ---- lmc_tv_exit.hip ----
+bool needs_tv_state(const Problem& q);
+int tv_prox_rtol(const Problem& q, float pt, const float* x, float* sol, float* tmp, double* obj, int* flag, int64_t n, float* st0, float* st1,
+                 hipStream_t st);
+int me_tv_prox(const Problem& q, const float* x, float* extra, int64_t n_img, float* state0, float* state1, hipStream_t st, RtState* rt = nullptr);
+int tv_prior_rt(const Problem& q, float pt, lmc::StepArgs& A, RtState& rt, float* proxbuf, float* st0, float* st1, hipStream_t st);
+int tv_prior_rt_mode(const Problem& q, const lmc::StepArgs& A_probe, float pt);
+lmc::EnergyArgs energy_args(const Problem& q);
+int me_tv_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, float* extra, float* st0, float* st1,
+                 double* dbl /* 2*n_img */, hipStream_t st, RtState* rt);
+
+}  // namespace lmc::host
+
+struct lmc_sampler {
+  int kind = 0;   // 0 MYULA, 1 ULPDA, 2 MYMALA
+  int device = -1;   // the device the handle's buffers live on (current at creation); every call on the handle runs there
+  // ULPDA state (kind == 1)
+  float mu = 0, theta = 1;
+  int gfirst = 0, cg_niter = 0, warm = 1;
+  const float* z = nullptr;
+  float* xhat = nullptr; float* ydual = nullptr; float* uw = nullptr; float* rhs = nullptr;
+  float* uw2 = nullptr;       // ULPDA: the other home of the implicit-step solution (two Chebyshev iterations per launch deliver it there)
+  float* cr = nullptr; float* cp = nullptr; float* cq = nullptr; float* ctmp = nullptr; float* xi = nullptr;
+  float* htb = nullptr; double* scal = nullptr; float* zero_y = nullptr;
+  float* tvstate[2] = {nullptr, nullptr};   // dual-state ping-pong for chunked TV proxes (K > 12, ME-TV)
+  float* tvwarm[2] = {nullptr, nullptr};    // warm-started TV prox: projected dual (p, q) of the previous / this MYULA iteration, [C][2][H][W]
+  int wcur = 0;
+  float* extra = nullptr;                   // ME-TV inner prox
+  float* pxbuf = nullptr;                   // Haar-l1 prox / early-exit TV prox of the current state
+  float* rtmp = nullptr; double* robj = nullptr; int* rflag = nullptr;   // early-exit TV prox (tv_rtol > 0), pass-by-pass path: pass iterate, objectives, flags
+  lmc::host::RtState rt_tv, rt_me;          // early-exit TV prox on the device (tv_prox_rt): of the TV prior / of the ME-TV inner prox
+  // launch policy, fixed at creation (lmc_problem fields; their environment variables supply the defaults): see lmc_atomi.h
+  int pol_pair = 1;          // 0 never, 1 where it pays, 2 wherever covered: two MYULA iterations per launch (rows kernel)
+  int pol_blockpair = 1;     // 0 / 1: two or four iterations per launch on the block kernel
+  int pol_overlap = 0;       // 0 by size, 1 on, -1 off
+  int pol_bg_wgs = -1;       // workgroups of the background reduction, -1 by size
+  lmc::host::Problem prob;
+  int C = 0;
+  int64_t chain_offset = 0;
+  float tau = 0, gamma = 0, epsg = 1;
+  uint64_t seed = 0;
+  int noise_mode = 0;
+  int moments = 0, burn_in = 0, thin = 1;
+  int64_t iteration = 0;
+  uint64_t count = 0;
+  float* x[2] = {nullptr, nullptr};
+  float* xspare = nullptr;    // third state array of the two-iterations-per-launch MYULA path (allocated at its first use)
+  // kept iterates in between of pair launches whose reductions run on the side stream: arrays of their own, alternating by launch
+  float* xmid[2] = {nullptr, nullptr};
+  int cur = 0;
+  double* s1 = nullptr;
+  double* s2 = nullptr;
+  double* packed = nullptr;              // [2 H W + 1]: the send / receive buffer of lmc_allreduce_moments
+  lmc::StepArgs base{};
+  // MYMALA state (kind == 2): proposal mean of the current state, proposal, its mean, energies, decisions
+  float* mx = nullptr; float* xp = nullptr; float* mxp = nullptr;
+  double* mala_d = nullptr;              // [5C]: U(x), f(x'), g(x'), ||x'-m(x)||^2, ||x-m(x')||^2 ; then [C] log alpha
+  int* flag = nullptr;
+  unsigned long long* nacc = nullptr;
+  bool mala_fresh = false;               // mx / U match x[cur]
+  // moment reductions on a side stream, overlapping the next step kernel (HBM-bound reduction under a VALU-bound step kernel); which of them are
+  // still running is known only inside one lmc_sampler_step call (SideMoments), which joins them all before it returns
+  hipStream_t side = nullptr;
+  hipEvent_t side_ev[1 + lmc::host::kSideBatches] = {};   // [0]: "the launch is done" (caller's stream); [1 + i]: "batch i of reductions is done" (side stream)
+  std::vector<hipEvent_t> ev;   // pairs (begin, end) around each step-kernel launch of the last step() call
+  bool timing = false;
+  bool timed = false;
+  int last_launches = 0;
+  std::string kernel_name;
+};

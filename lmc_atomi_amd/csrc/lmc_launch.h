@@ -47,7 +47,7 @@ hipError_t launch_tv1d_sol(const float* x, const float* rr, float* out, int64_t 
 hipError_t launch_tv1d_iter(const float* x, const float* rr_in, float* p, float* rr_out, int64_t n, size_t N, float gam, float cstep, float beta, const int* flag,
                             hipStream_t st);
 hipError_t launch_tv1d_objective(const float* x, const float* sol, int64_t n, size_t N, float gam, const int* flag, double* obj, hipStream_t st);
-// the early exit without leaving the device (speculate / verify / re-run; lmc_ops.hip, lmc_capi.hip: tv_prox_rt)
+// the early exit without leaving the device (speculate / verify / re-run; lmc_ops.hip, lmc_tv_exit.hip: tv_prox_rt)
 hipError_t launch_tv_rt_begin(int64_t n, const int* pred, int* kc, int* start, double* obj, int stride, int niter, hipStream_t st);
 hipError_t launch_tv_rt_decide(int64_t n, int* kc, int* start, int* pred, double* obj, int stride, int niter, double rtol, int round,
                                unsigned long long* reruns, hipStream_t st);
@@ -107,19 +107,11 @@ hipError_t ulpda_finish_philox(float* x, float* xhat, const float* u, int64_t C,
                                uint32_t key1, uint32_t iteration, uint32_t chain_offset, hipStream_t st);
 hipError_t ulpda_finish(float* x, float* xhat, const float* u, const float* xi, int64_t C, int H, int W, float s, float theta,
                         hipStream_t st);
-// finish + dual update in one row-streaming pass (gfirst = false; xhat stays in registers)
-bool ulpda_finish_dual_supported(int H, int W);
-hipError_t ulpda_finish_dual(const float* x, float* xnew, const float* u, float* y, const float* xi, int64_t C, int H, int W, float s, float theta, float mu,
-                             float radius, int iso, int philox, uint32_t key0, uint32_t key1, uint32_t iteration, uint32_t chain_offset,
-                             hipStream_t st);
 hipError_t cg_dot(const float* p, const float* q, int64_t C, size_t img, double* pq, const int* done, hipStream_t st);
 hipError_t cg_init(const float* rhs, const float* q, float* r, float* p, int64_t C, size_t img, double* rs, double* b2, hipStream_t st);
 hipError_t cg_update(float* u, float* r, const float* p, const float* q, int64_t C, size_t img, const double* rs, const double* pq,
                      double* rs_new, const int* done, hipStream_t st);
 hipError_t cg_dir(float* p, const float* r, int64_t C, size_t img, double* rs, const double* rs_new, const int* done, hipStream_t st);
-bool ulpda_dual_rhs_supported(int H, int W);
-hipError_t ulpda_dual_rhs(const float* xhat, const float* y_in, float* y_out, const float* x, const float* z, const float* htb, float* rhs, int64_t C,
-                          int H, int W, float mu, float radius, int iso, float tau, float ts, hipStream_t st);
 hipError_t cheb_count(int64_t C, const double* stat, double inv_alpha2, double tol, double inv_log_inv_c, int kmax, int* count,
                       hipStream_t st);
 hipError_t cg_check(int64_t C, const double* rsv, const double* b2, double tol2, int* done, hipStream_t st);

@@ -682,7 +682,7 @@ hipError_t launch_hbm_copy_probe(const float* x, float* y, size_t n_floats, int 
   return hipGetLastError();
 }
 
-// ---- pyproximal.TV's early exit (lmc_problem.tv_rtol > 0): the pieces of the exact, pass-by-pass path (lmc_capi.hip: tv_prox_rtol) -------
+// ---- pyproximal.TV's early exit (lmc_problem.tv_rtol > 0): the pieces of the exact, pass-by-pass path (lmc_tv_exit.hip: tv_prox_rtol) -------
 // obj[c] += 1/2 ||x_c - sol_c||^2 + gam * TV_iso(sol_c) for the chains still iterating (flag[c] < 0): the primal objective upstream
 // evaluates at the top of every loop pass.  fp32 terms, fp64 sums.
 __global__ __launch_bounds__(256) void tv_objective_kernel(const float* __restrict__ x, const float* __restrict__ sol, int H, int W, float gam,
@@ -758,7 +758,7 @@ hipError_t launch_tv_rtol_select(const float* tmp, float* sol, const int* flag, 
 
 // ---- 1-D TV over the flattened image: the inner prox of the ANISOTROPIC ME-TV term of algs.L2_ncvx_tv (algs.py:170: pyproximal.TV((prod(dims),), 1., niter,
 // rtol)) ----  No model of the reference's driver uses it (prox_lmc_deconv.py:106-113 are the isotropic ones), so this is plain coverage: one pass over the
-// images per dual iteration, dual and projected dual ping-ponged through memory, the same pass-by-pass early exit as tv_prox_rtol (lmc_capi.hip: tv1d_prox).
+// images per dual iteration, dual and projected dual ping-ponged through memory, the same pass-by-pass early exit as tv_prox_rtol (lmc_tv_exit.hip: tv1d_prox).
 // One dual component r: sol = x - gam div(rr), div(r)[i] = r[i] - r[i-1] with the last entry of r taken as zero; r = rr - c (sol[i+1] - sol[i]) (0 at the
 // end), p' = r / max(1, |r|), rr' = p' + beta (p' - p).  Images with flag[c] >= 0 (left already) are skipped.
 __device__ __forceinline__ float tv1d_sol_at(const float* __restrict__ x, const float* __restrict__ rr, size_t i, size_t N, float gam) {
@@ -824,7 +824,7 @@ hipError_t launch_tv1d_objective(const float* x, const float* sol, int64_t n, si
   return hipGetLastError();
 }
 
-// ---- the same early exit without leaving the device (lmc_capi.hip: tv_prox_rt): speculate, verify, re-run -------------------------------------
+// ---- the same early exit without leaving the device (lmc_tv_exit.hip: tv_prox_rt): speculate, verify, re-run -------------------------------------
 // A chain's prox runs with a PREDICTED number of dual updates k (the pass it left in at the previous call: the objective is a sum over the
 // whole image and moves little from one MYULA iterate to the next), fused in the RT instantiations of the pipe kernel, which leave the primal
 // objective of every iterate they form in obj[c][0 .. k].  tv_rt_decide replays upstream's test on them, one thread per chain:

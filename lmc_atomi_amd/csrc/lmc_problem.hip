@@ -1,0 +1,282 @@
+// lmc_problem -> Problem (the argument checks of every entry point that takes a problem), the StepArgs of one update, the library defaults and
+// the step-kernel dispatch.
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "lmc_host.h"
+
+namespace lmc::host {
+
+int fill_taps(lmc::BlurTaps& T, const float* h, int kh, int kw, int oy, int ox) {
+  if (!h) return fail(LMC_E_INVALID, "blur kernel pointer is NULL");
+  if (kh < 1 || kw < 1 || kh > lmc::kMaxBlur || kw > lmc::kMaxBlur)
+    return fail(LMC_E_UNSUPPORTED, "blur kernel %dx%d outside 1..%d", kh, kw, lmc::kMaxBlur);
+  if (oy < 0 || oy >= kh || ox < 0 || ox >= kw) return fail(LMC_E_INVALID, "blur offset (%d,%d) outside kernel", oy, ox);
+  T.kh = kh; T.kw = kw; T.oy = oy; T.ox = ox;
+  std::memset(T.h, 0, sizeof T.h);
+  std::memcpy(T.h, h, sizeof(float) * kh * kw);
+  return LMC_OK;
+}
+
+// default momentum table: t_k = (1 + sqrt(4 t_{k-1}^2))/2 (pyproximal.TV / UNLocBoX), beta_k = (t_{k-1}-1)/t_k
+void default_betas(float* b, int n) {
+  double t = 1.0;
+  for (int k = 0; k < n; ++k) {
+    const double tn = (1.0 + std::sqrt(4.0 * t * t)) / 2.0;
+    b[k] = (float)((t - 1.0) / tn);
+    t = tn;
+  }
+}
+
+int load_problem(const lmc_problem* p, Problem& q) {
+  if (!p) return fail(LMC_E_INVALID, "lmc_problem is NULL");
+  if (p->struct_size != sizeof(lmc_problem))
+    return fail(LMC_E_INVALID, "lmc_problem.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(lmc_problem));
+  if (p->H < 1 || p->W < 1 || (int64_t)p->H * p->W > (int64_t)1 << 30) return fail(LMC_E_INVALID, "bad image size %dx%d", p->H, p->W);
+  q.H = p->H; q.W = p->W;
+  q.data_kind = p->data_kind;
+  q.sigma_f = p->sigma_f;
+  q.y = p->y_dev;
+  q.mask = p->mask_dev;
+  switch (p->data_kind) {
+    case LMC_DATA_NONE: break;
+    case LMC_DATA_IDENTITY:
+      if (!p->y_dev) return fail(LMC_E_INVALID, "data term needs y_dev");
+      break;
+    case LMC_DATA_MASK:
+      if (!p->y_dev || !p->mask_dev) return fail(LMC_E_INVALID, "mask data term needs y_dev and mask_dev");
+      break;
+    case LMC_DATA_BLUR: {
+      if (!p->y_dev) return fail(LMC_E_INVALID, "data term needs y_dev");
+      int rc = fill_taps(q.taps, p->h_host, p->kh, p->kw, p->oy, p->ox);
+      if (rc) return rc;
+      break;
+    }
+    default: return fail(LMC_E_INVALID, "unknown data_kind %d", p->data_kind);
+  }
+  q.prior_kind = p->prior_kind;
+  q.prior_sigma = p->prior_sigma;
+  switch (p->prior_kind) {
+    case LMC_PRIOR_NONE: case LMC_PRIOR_L2: case LMC_PRIOR_L1: case LMC_PRIOR_TV_ANISO: break;
+    case LMC_PRIOR_EPROX:
+      if (p->eprox_kind < 0 || p->eprox_kind > LMC_EPROX_LAPLACE_CONJ) return fail(LMC_E_INVALID, "unknown eprox_kind %d", p->eprox_kind);
+      if (p->eprox_scale_mask < 0 || p->eprox_scale_mask > 3) return fail(LMC_E_INVALID, "eprox_scale_mask must be 0..3");
+      if (!(p->eprox_p0 == p->eprox_p0) || !(p->eprox_p1 == p->eprox_p1)) return fail(LMC_E_INVALID, "eprox parameter is NaN");
+      q.eprox_kind = p->eprox_kind; q.eprox_mask = p->eprox_scale_mask; q.eprox_p0 = p->eprox_p0; q.eprox_p1 = p->eprox_p1;
+      break;
+    case LMC_PRIOR_HAAR_L1:
+      if ((p->H & 7) || (p->W & 7)) return fail(LMC_E_UNSUPPORTED, "the Haar-l1 prior needs H and W to be multiples of 8 (got %dx%d)", p->H, p->W);
+      break;
+    case LMC_PRIOR_TV_ISO:
+      if (p->tv_niter < 1 || p->tv_niter > lmc::kMaxTvIters)
+        return fail(LMC_E_UNSUPPORTED, "tv_niter %d outside 1..%d", p->tv_niter, lmc::kMaxTvIters);
+      if (!(p->tv_rtol >= 0.f) || p->tv_rtol >= 1.f) return fail(LMC_E_INVALID, "tv_rtol must be in [0, 1)");
+      q.tv_rtol = p->tv_rtol;
+      q.tv_niter = p->tv_niter - (p->tv_lagged_output ? 1 : 0);     // lagged: the iterate after tv_niter - 1 dual updates (0: prox = x)
+      q.tv_step = p->tv_step > 0.f ? p->tv_step : 0.125f;
+      if (p->tv_betas_host) std::memcpy(q.betas, p->tv_betas_host, sizeof(float) * p->tv_niter);
+      else default_betas(q.betas, p->tv_niter);
+      break;
+    default: return fail(LMC_E_INVALID, "unknown prior_kind %d", p->prior_kind);
+  }
+  if (p->prior_kind != LMC_PRIOR_NONE && p->prior_kind != LMC_PRIOR_EPROX && !(p->prior_sigma >= 0.f)) return fail(LMC_E_INVALID, "prior_sigma must be >= 0");
+  if (p->ncvx_kind != LMC_NCVX_NONE) {
+    if (p->ncvx_kind != LMC_NCVX_MC_TV && p->ncvx_kind != LMC_NCVX_ME_TV && p->ncvx_kind != LMC_NCVX_MC_TV_ANISO && p->ncvx_kind != LMC_NCVX_ME_TV_ANISO)
+      return fail(LMC_E_INVALID, "unknown ncvx_kind %d", p->ncvx_kind);
+    if (!(p->ncvx_gamma > 0.f)) return fail(LMC_E_INVALID, "ncvx_gamma must be > 0");
+    const bool me = p->ncvx_kind == LMC_NCVX_ME_TV || p->ncvx_kind == LMC_NCVX_ME_TV_ANISO;
+    if (me && (p->ncvx_niter < 1 || p->ncvx_niter > lmc::kMaxTvIters))
+      return fail(LMC_E_INVALID, "ncvx_niter %d outside 1..%d", p->ncvx_niter, lmc::kMaxTvIters);
+    q.ncvx_kind = p->ncvx_kind; q.ncvx_lambda = p->ncvx_lambda; q.ncvx_gamma = p->ncvx_gamma;
+    // anisotropic ME-TV: inside the library the ME-TV kind with the 1-D inner prox (every code path that adds the term's gradient serves both)
+    if (p->ncvx_kind == LMC_NCVX_ME_TV_ANISO) { q.ncvx_kind = LMC_NCVX_ME_TV; q.ncvx_aniso = 1; }
+    // anisotropic MC-TV: inside the library the same kind with a NEGATIVE gamma -- mc_tv_grad (lmc_device.h) and the energy kernels take
+    // the sign as "component-wise weights 1 / max(|d|, gamma)" instead of the pixel norm; every MC-TV code path serves both
+    if (p->ncvx_kind == LMC_NCVX_MC_TV_ANISO) { q.ncvx_kind = LMC_NCVX_MC_TV; q.ncvx_gamma = -p->ncvx_gamma; }
+    q.ncvx_niter = p->ncvx_niter - ((me && p->tv_lagged_output) ? 1 : 0);
+    if (me) {
+      if (!(p->ncvx_rtol >= 0.f) || p->ncvx_rtol >= 1.f) return fail(LMC_E_INVALID, "ncvx_rtol must be in [0, 1)");
+      q.ncvx_rtol = p->ncvx_rtol;
+    }
+  }
+  if (p->tv_exit_path != 0 && p->tv_exit_path != 1) return fail(LMC_E_INVALID, "tv_exit_path must be 0 (device path where covered) or 1 (pass by pass)");
+  q.tv_exit_path = p->tv_exit_path;
+  if (p->iterations_per_launch < 0 || p->iterations_per_launch > 2) return fail(LMC_E_INVALID, "iterations_per_launch must be 0 (auto), 1 or 2");
+  if (p->moments_overlap < -1 || p->moments_overlap > 1) return fail(LMC_E_INVALID, "moments_overlap must be 0 (auto), 1 (on) or -1 (off)");
+  if (p->moments_bg_workgroups < 0 || p->graph_replay < 0 || p->graph_replay > 1) return fail(LMC_E_INVALID, "bad moments_bg_workgroups / graph_replay");
+  q.iters_per_launch = p->iterations_per_launch; q.moments_overlap = p->moments_overlap;
+  q.moments_bg_wgs = p->moments_bg_workgroups;   // (graph_replay: validated, no effect)
+  {
+    const char* e = getenv("LMC_CHEB_PAIR");
+    const char* e2 = getenv("LMC_ITERS_PER_LAUNCH");
+    const int ipl = q.iters_per_launch ? q.iters_per_launch : (e2 ? atoi(e2) : 0);
+    q.cheb_pair = ipl == 1 ? 0 : (ipl == 2 ? 2 : (e ? atoi(e) : 1));
+  }
+  if (p->step_variant < 0 || p->step_variant > 8 || p->step_variant == 2)
+    return fail(LMC_E_INVALID, "step_variant %d: 0 (library default), 1 tile, 3 split, 4 point, 5 block, 6 rows, 7 pipe, 8 pipe2", p->step_variant);
+  q.variant = p->step_variant;
+  if (p->prox_scale) {
+    if (p->prior_kind != LMC_PRIOR_L2 && p->prior_kind != LMC_PRIOR_L1 && p->prior_kind != LMC_PRIOR_EPROX)
+      return fail(LMC_E_UNSUPPORTED, "prox_scale (array-valued epsg) is built for the closed-form priors (l2, l1, prox.py closed forms) only");
+    if (p->prox_scale_chain_stride < 0 || p->prox_scale_pixel_stride < 0) return fail(LMC_E_INVALID, "prox_scale strides must be >= 0");
+    q.prox_scale = p->prox_scale; q.prox_scale_cs = p->prox_scale_chain_stride; q.prox_scale_ps = p->prox_scale_pixel_stride;
+  }
+  q.tv_warm = (p->tv_warm != 0 && p->prior_kind == LMC_PRIOR_TV_ISO) ? 1 : 0;
+  if (!(p->implicit_tol == p->implicit_tol)) return fail(LMC_E_INVALID, "implicit_tol is NaN");
+  q.implicit_tol = p->implicit_tol;
+  return LMC_OK;
+}
+
+// StepArgs for: out = a*x - t*grad f + b*prox_{pt*g}(x) + s*xi
+int make_step_args(const Problem& q, float a, float t, float b, float pt, float s, lmc::StepArgs& A) {
+  std::memset(&A, 0, sizeof A);
+  A.H = q.H; A.W = q.W;
+  A.data_kind = (t == 0.f) ? LMC_DATA_NONE : q.data_kind;   // skip the stencil work if its weight is zero
+  A.sigma_f = q.sigma_f;
+  A.y = q.y; A.mask = q.mask;
+  A.blur = q.taps;
+  A.prior_kind = (b == 0.f) ? LMC_PRIOR_NONE : q.prior_kind;
+  if (A.prior_kind == LMC_PRIOR_TV_ISO && q.tv_niter == 0) A.prior_kind = LMC_PRIOR_NONE;   // lagged output of a 1-iteration prox: x itself
+  if (A.prior_kind == LMC_PRIOR_HAAR_L1) A.prior_p0 = pt * q.prior_sigma;  // soft threshold of the detail coefficients
+  if (A.prior_kind == LMC_PRIOR_L2) A.prior_p0 = 1.f / (1.f + pt * q.prior_sigma);
+  if (A.prior_kind == LMC_PRIOR_L1) A.prior_p0 = pt * q.prior_sigma;
+  if (A.prior_kind == LMC_PRIOR_EPROX) {     // prox.py closed forms: the parameters the mask names scale with the prox parameter
+    A.eprox_kind = q.eprox_kind;
+    A.prior_p0 = (q.eprox_mask & 1) ? pt * q.eprox_p0 : q.eprox_p0;
+    A.prior_p1 = (q.eprox_mask & 2) ? pt * q.eprox_p1 : q.eprox_p1;
+  }
+  if (A.prior_kind == LMC_PRIOR_TV_ISO) {
+    const float gam = pt * q.prior_sigma;
+    if (!(gam > 0.f)) return fail(LMC_E_INVALID, "TV prox parameter must be > 0 (got %g)", (double)gam);
+    A.tv.niter = q.tv_niter;
+    A.tv.gamma = gam;
+    A.tv.c = q.tv_step / gam;
+    std::memcpy(A.tv.betas, q.betas, sizeof(float) * q.tv_niter);
+  }
+  if (t != 0.f && q.ncvx_kind == LMC_NCVX_MC_TV) {
+    A.ncvx_kind = q.ncvx_kind; A.ncvx_lambda = q.ncvx_lambda; A.ncvx_gamma = q.ncvx_gamma; A.ncvx_inv_gamma = 1.f / q.ncvx_gamma;
+  }
+  // LMC_NCVX_ME_TV: the caller runs me_tv_prox first and sets A.extra / A.extra_coef
+  A.a = a; A.t = t; A.b = b; A.s = s;
+  A.noise_mode = LMC_NOISE_NONE;
+  return LMC_OK;
+}
+
+// Pointers that the configuration does not use are pointed at the input state (always valid for the
+// index ranges the kernels form) so that no kernel ever holds a null pointer it could dereference.
+void sanitize_pointers(lmc::StepArgs& A) {
+  if (!A.y) A.y = A.x_in;
+  if (!A.mask) A.mask = A.x_in;
+  if (!A.noise) A.noise = A.x_in;
+}
+
+// Library-wide DEFAULTS only (lmc_set_step_variant / lmc_set_cg_tolerance): every launch takes its variant and tolerance from the
+// lmc_problem it was configured from (step_variant / implicit_tol) and falls back to these when that field is 0.
+int g_variant = 0;  // 0 auto, 1 tile, (2: removed) 3 split, 4 point, 5 block, 6 rows, 7 pipe (one team), 8 pipe2 (two teams)
+float g_cg_tol = 1e-6f;   // relative residual at which the inner solver stops (0: always cg_niter iterations)
+int variant_of(const Problem& q) { return q.variant ? q.variant : g_variant; }
+float tol_of(const Problem& q) { return q.implicit_tol > 0.f ? q.implicit_tol : (q.implicit_tol < 0.f ? 0.f : g_cg_tol); }
+
+// Picks the step-kernel variant.  auto: the split streaming pipeline (two wave groups, 4 waves/SIMD) when
+// it covers the configuration (W <= 512, separable blur <= 7x7, supported K), else the LDS-tiled kernel.
+hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
+  int v = variant;
+  // no stencil in the data term and a prox local to 8 x 8 blocks (Haar-l1, l2, l1, none): the register-block kernel
+  if ((v == 0 || v == 5) && lmc::block_supported(A_in)) {
+    if (name) *name = "myula_step_block_kernel";
+    return lmc::launch_step_block(A_in, st);
+  }
+  if ((v == 0 || v == 5) && A_in.ncvx_kind == LMC_NCVX_MC_TV) {
+    // stencil-free data term + block-local prox + MC-TV term: the block kernel without the term, then one stencil
+    // pass that adds t * lambda * A^T(A x / max(|A x|, gamma)) to its output
+    lmc::StepArgs B = A_in;
+    B.ncvx_kind = LMC_NCVX_NONE;
+    if (lmc::block_supported(B)) {
+      if (name) *name = "myula_step_block_kernel";
+      hipError_t e = lmc::launch_step_block(B, st);
+      if (e != hipSuccess) return e;
+      return lmc::launch_mc_tv_add(A_in.x_in, A_in.x_out, A_in.C, A_in.H, A_in.W, A_in.t * A_in.ncvx_lambda, A_in.ncvx_gamma, st);
+    }
+  }
+  if (v == 5) return hipErrorInvalidConfiguration;
+  lmc::StepArgs A = A_in;
+  if (A.prior_kind == LMC_PRIOR_HAAR_L1) {   // other data terms: the block-wavelet prox first, consumed by the fused step kernel
+    if (!pxbuf) return hipErrorInvalidConfiguration;
+    hipError_t e = lmc::launch_haar_prox(A.x_in, pxbuf, A.C, A.H, A.W, A.prior_p0, st);
+    if (e != hipSuccess) return e;
+    A.prior_kind = LMC_PRIOR_NONE;
+    A.prox_ext = pxbuf;
+  }
+  // separable blur + closed-form prior (no TV pipeline): barrier-free row streaming, one wave per band of rows
+  if ((v == 0 || v == 6) && lmc::rows_supported(A)) {
+    if (name) *name = "myula_step_rows_kernel";
+    return lmc::launch_step_rows(A, st);
+  }
+  if (v == 6) return hipErrorInvalidConfiguration;
+  // TV K = 10 on a 264..512-wide image with a separable blur: the stage-parallel full-width pipeline (auto: its two-team layout where that
+  // covers the configuration, else one team; 7: one team; 8: the two-team layout or nothing)
+  if (v == 0 || v == 7 || v == 8) {
+    const int links = lmc::pipe_links(A);
+    if (links == 1 || (links > 1 && state0 && state1 && v != 8)) {
+      if (name) *name = "myula_step_pipe_kernel";
+      return lmc::launch_step_pipe(A, st, state0, state1, v == 7 ? 1 : v == 8 ? 2 : 0);
+    }
+  }
+  if (v == 7 || v == 8) return hipErrorInvalidConfiguration;
+  // auto: split pipeline when it covers the configuration (W <= 512); for wider images the tiled kernels:
+  // "point" for closed-form priors with a separable blur, else the general LDS-tiled kernel
+  // a closed-form elementwise prior (LMC_PRIOR_EPROX) that reaches this point (a non-log-concave term, or a blur the row kernel does not cover): the split and
+  // tiled kernels have no functor for it -- the point kernel evaluates it in place; where that does not cover the data term the prox is formed by one elementwise
+  // launch and consumed as a ready-made prox.  (Round 3's configuration-matrix test found these combinations running with prox = identity.)
+  if (A.prior_kind == LMC_PRIOR_EPROX) {
+    if ((v == 0 || v == 4) && lmc::point_supported(A)) v = 4;
+    else {
+      if (!pxbuf) return hipErrorInvalidConfiguration;
+      hipError_t e = lmc::launch_eprox(A.eprox_kind, A.x_in, pxbuf, (int64_t)A.C * A.H * A.W, A.prior_p0, A.prior_p1, st);
+      if (e != hipSuccess) return e;
+      A.prior_kind = LMC_PRIOR_NONE;
+      A.prox_ext = pxbuf;
+    }
+  }
+  if (v == 0) v = lmc::split_supported(A) ? 3 : (lmc::point_supported(A) ? 4 : 1);
+  if (v == 4) {
+    if (!lmc::point_supported(A)) return hipErrorInvalidConfiguration;
+    if (name) *name = "myula_step_point_kernel";
+    return lmc::launch_step_point(A, st);
+  }
+  if (v == 3) {
+    if (!lmc::split_supported(A)) return hipErrorInvalidConfiguration;
+    if (name) *name = "myula_step_split_kernel";
+    return lmc::launch_step_split(A, st);
+  }
+  if (name) *name = "myula_step_tile_kernel";
+  if (lmc::tile_needs_chunks(A)) {
+    if (!state0 || !state1) return hipErrorInvalidConfiguration;
+    return lmc::launch_step_tile_chunked(A, state0, state1, st);
+  }
+  return lmc::launch_step_tile(A, st);
+}
+
+}  // namespace lmc::host
+
+using namespace lmc::host;
+
+extern "C" {
+
+float lmc_set_cg_tolerance(float tol) {
+  const float prev = g_cg_tol;
+  if (tol >= 0.f) g_cg_tol = tol;
+  return prev;
+}
+
+int lmc_set_step_variant(int32_t variant) {
+  if (variant < 0 || variant > 8 || variant == 2)
+    return fail(LMC_E_INVALID, "variant must be 0 (auto), 1 (tile), 3 (split), 4 (point), 5 (block), 6 (rows), 7 (pipe) or 8 (pipe2); 2 (the one-group "
+                "streaming kernel of ABI 1) was removed");
+  const int prev = g_variant;
+  g_variant = variant;
+  return prev;
+}
+
+}  // extern "C"

@@ -1,0 +1,120 @@
+// Multi-GPU: the RCCL entry points and the all-reduce of the posterior moments.
+#include <dlfcn.h>
+#include <rccl/rccl.h>   // types and enums only: the library itself is dlopen'd (liblmc_atomi loads without RCCL)
+
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "lmc_host.h"
+
+using namespace lmc::host;
+
+// ---- multi-GPU: the one collective of the path -----------------------------------------------------------------
+// RCCL is reached through dlopen so that the library (and every single-GPU use) does not depend on it.  When the host process has
+// RCCL loaded already (PyTorch-ROCm ships its own librccl.so.1) that instance is the one bound, so a communicator created by the host
+// framework is valid here.
+namespace {
+struct RcclApi {
+  void* lib = nullptr;
+  ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
+  ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
+  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
+  ncclResult_t (*CommCount)(const ncclComm_t, int*) = nullptr;
+  ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
+  const char* (*GetErrorString)(ncclResult_t) = nullptr;
+  std::string why;
+};
+RcclApi* rccl_api() {
+  static RcclApi api = [] {
+    RcclApi a;
+    const char* env = getenv("LMC_RCCL_LIB");
+    const char* names[] = {env, "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+    for (const char* n : names) {
+      if (!n || !*n) continue;
+      a.lib = dlopen(n, RTLD_NOW | RTLD_NOLOAD);          // the instance the process already has, if any
+      if (!a.lib) a.lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
+      if (a.lib) break;
+    }
+    if (!a.lib) { const char* e = dlerror(); a.why = std::string("librccl not found (set LMC_RCCL_LIB): ") + (e ? e : ""); return a; }
+    auto sym = [&](const char* n) { void* p = dlsym(a.lib, n); if (!p && a.why.empty()) a.why = std::string("librccl lacks ") + n; return p; };
+    a.GetUniqueId = reinterpret_cast<decltype(a.GetUniqueId)>(sym("ncclGetUniqueId"));
+    a.CommInitRank = reinterpret_cast<decltype(a.CommInitRank)>(sym("ncclCommInitRank"));
+    a.CommDestroy = reinterpret_cast<decltype(a.CommDestroy)>(sym("ncclCommDestroy"));
+    a.CommCount = reinterpret_cast<decltype(a.CommCount)>(sym("ncclCommCount"));
+    a.AllReduce = reinterpret_cast<decltype(a.AllReduce)>(sym("ncclAllReduce"));
+    a.GetErrorString = reinterpret_cast<decltype(a.GetErrorString)>(sym("ncclGetErrorString"));
+    if (!a.why.empty()) { dlclose(a.lib); a.lib = nullptr; }
+    return a;
+  }();
+  return &api;
+}
+#define RCCL_TRY(api, expr)                                                                                       \
+  do {                                                                                                            \
+    ncclResult_t r_ = (expr);                                                                                     \
+    if (r_ != ncclSuccess) return fail(LMC_E_HIP, "%s failed: %s", #expr, (api)->GetErrorString(r_));            \
+  } while (0)
+}  // namespace
+
+extern "C" {
+
+int lmc_rccl_available(void) { return rccl_api()->lib ? 1 : 0; }
+
+int lmc_rccl_unique_id(void* id128_host) {
+  RcclApi* R = rccl_api();
+  if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
+  if (!id128_host) return fail(LMC_E_INVALID, "NULL argument");
+  static_assert(sizeof(ncclUniqueId) == LMC_RCCL_UNIQUE_ID_BYTES, "ncclUniqueId size");
+  ncclUniqueId id;
+  RCCL_TRY(R, R->GetUniqueId(&id));
+  std::memcpy(id128_host, &id, sizeof id);
+  return LMC_OK;
+}
+
+int lmc_rccl_comm_create(void** comm_out, int32_t world, int32_t rank, const void* id128_host) {
+  RcclApi* R = rccl_api();
+  if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
+  if (!comm_out || !id128_host) return fail(LMC_E_INVALID, "NULL argument");
+  if (world < 1 || rank < 0 || rank >= world) return fail(LMC_E_INVALID, "bad rank %d of %d", rank, world);
+  ncclUniqueId id;
+  std::memcpy(&id, id128_host, sizeof id);
+  ncclComm_t comm = nullptr;
+  RCCL_TRY(R, R->CommInitRank(&comm, world, id, rank));      // on the current device: one process per GPU
+  *comm_out = comm;
+  return LMC_OK;
+}
+
+int lmc_rccl_comm_destroy(void* comm) {
+  RcclApi* R = rccl_api();
+  if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
+  if (!comm) return LMC_OK;
+  RCCL_TRY(R, R->CommDestroy(static_cast<ncclComm_t>(comm)));
+  return LMC_OK;
+}
+
+int lmc_allreduce_moments(lmc_sampler* s, void* rccl_comm, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
+  hipStream_t st = S(stream);
+  const size_t n = (size_t)s->prob.H * s->prob.W;
+  if (!rccl_comm) return lmc_sampler_get_moments(s, sum_dev, sumsq_dev, count, stream);   // a job of one rank
+  RcclApi* R = rccl_api();
+  if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
+  if (!s->packed) HIP_TRY(hipMalloc(&s->packed, sizeof(double) * (2 * n + 1)));
+  // one packed buffer {sum x, sum x^2, count}: ONE ncclAllReduce(sum) over xGMI (4 MiB at 512 x 512), in place
+  HIP_TRY(hipMemcpyAsync(s->packed, s->s1, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->packed + n, s->s2, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  const double cnt = (double)s->count;                      // exact below 2^53 samples
+  HIP_TRY(hipMemcpyAsync(s->packed + 2 * n, &cnt, sizeof(double), hipMemcpyHostToDevice, st));
+  RCCL_TRY(R, R->AllReduce(s->packed, s->packed, 2 * n + 1, ncclFloat64, ncclSum, static_cast<ncclComm_t>(rccl_comm), st));
+  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, s->packed, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, s->packed + n, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  double total = 0.0;
+  HIP_TRY(hipMemcpyAsync(&total, s->packed + 2 * n, sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (count) *count = (uint64_t)(total + 0.5);
+  return LMC_OK;
+}
+
+}  // extern "C"

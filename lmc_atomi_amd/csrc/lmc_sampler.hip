@@ -1,0 +1,799 @@
+// The samplers behind lmc_sampler: create / destroy / state / step of MYULA, MYMALA and ULPDA, and the accessors of a handle.
+#include <cmath>
+#include <cstdlib>
+#include <new>
+
+#include "lmc_host.h"
+
+using namespace lmc::host;
+
+namespace {
+int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+
+// The checks of a sampler configuration that MYULA, MYMALA and ULPDA share, in the order the create calls make them: steps_ok / steps_msg are
+// the sampler's own check of its step sizes, which comes after the chain ids.
+template <class Cfg>
+int check_config(const Cfg& cfg, bool steps_ok, const char* steps_msg) {
+  if (cfg.n_chains < 1) return fail(LMC_E_INVALID, "n_chains must be >= 1");
+  if (cfg.chain_offset < 0 || cfg.chain_offset + cfg.n_chains > 0xFFFFFFFFLL)
+    return fail(LMC_E_INVALID, "global chain ids must fit 32 bits");
+  if (!steps_ok) return fail(LMC_E_INVALID, "%s", steps_msg);
+  if (cfg.noise_mode < LMC_NOISE_PHILOX || cfg.noise_mode > LMC_NOISE_NONE) return fail(LMC_E_INVALID, "bad noise_mode");
+  return LMC_OK;
+}
+
+// The posterior-moment accumulators s1, s2 ([H][W] doubles each, zeroed) of a sampler created with moments on.
+hipError_t alloc_moments(lmc_sampler* s) {
+  if (!s->moments) return hipSuccess;
+  const size_t mb = sizeof(double) * (size_t)s->prob.H * s->prob.W;
+  hipError_t e = hipMalloc(&s->s1, mb);
+  if (e == hipSuccess) e = hipMalloc(&s->s2, mb);
+  if (e == hipSuccess) e = hipMemset(s->s1, 0, mb);
+  if (e == hipSuccess) e = hipMemset(s->s2, 0, mb);
+  return e;
+}
+
+// A create call whose device allocation failed: the sampler goes, the status says why.
+int alloc_failed(lmc_sampler* s, hipError_t e) {
+  const int rc = fail(e == hipErrorOutOfMemory ? LMC_E_NOMEM : LMC_E_HIP, "sampler allocation failed: %s", hipGetErrorString(e));
+  lmc_sampler_destroy(s);
+  return rc;
+}
+}  // namespace
+
+extern "C" {
+
+// ---- sampler ---------------------------------------------------------------------------------
+
+int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
+  if (!cfg || !out) return fail(LMC_E_INVALID, "NULL argument");
+  *out = nullptr;
+  if (cfg->struct_size != sizeof(lmc_myula_config))
+    return fail(LMC_E_INVALID, "lmc_myula_config.struct_size %u != %zu (ABI mismatch)", cfg->struct_size, sizeof(lmc_myula_config));
+  int rc = check_config(*cfg, cfg->tau > 0.f && cfg->gamma > 0.f, "tau and gamma must be > 0");
+  if (rc) return rc;
+  if (cfg->moments && cfg->thin < 1) return fail(LMC_E_INVALID, "thin must be >= 1");
+  lmc_sampler* s = new (std::nothrow) lmc_sampler();
+  if (!s) return fail(LMC_E_NOMEM, "host allocation failed");
+  rc = load_problem(&cfg->problem, s->prob);
+  if (rc) { delete s; return rc; }
+  if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }
+  s->C = cfg->n_chains;
+  s->chain_offset = cfg->chain_offset;
+  s->tau = cfg->tau; s->gamma = cfg->gamma; s->epsg = cfg->epsg;
+  s->seed = cfg->seed;
+  s->noise_mode = cfg->noise_mode;
+  s->moments = cfg->moments; s->burn_in = cfg->burn_in; s->thin = cfg->thin < 1 ? 1 : cfg->thin;
+  // x <- (1 - tau/gamma) x - tau grad f(x) + (tau/gamma) prox_{epsg*gamma*g}(x) + sqrt(2 tau) xi   (algs.py:569)
+  rc = make_step_args(s->prob, 1.f - s->tau / s->gamma, s->tau, s->tau / s->gamma, s->epsg * s->gamma,
+                      std::sqrt(2.f * s->tau), s->base);
+  if (rc) { delete s; return rc; }
+  s->base.C = s->C;
+  s->base.noise_mode = s->noise_mode;
+  s->base.key0 = (uint32_t)(s->seed & 0xFFFFFFFFu);
+  s->base.key1 = (uint32_t)(s->seed >> 32);
+  s->base.chain_offset = (uint32_t)s->chain_offset;
+  const size_t nbytes = sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W;
+  hipError_t e = hipMalloc(&s->x[0], nbytes);
+  if (e == hipSuccess) e = hipMalloc(&s->x[1], nbytes);
+  if (e == hipSuccess) e = hipMemset(s->x[0], 0, nbytes);
+  if (e == hipSuccess && needs_tv_state(s->prob)) {
+    e = hipMalloc(&s->tvstate[0], 4 * nbytes);
+    if (e == hipSuccess) e = hipMalloc(&s->tvstate[1], 4 * nbytes);
+  }
+  if (e == hipSuccess && s->prob.ncvx_kind == LMC_NCVX_ME_TV) e = hipMalloc(&s->extra, nbytes);
+  if (e == hipSuccess && (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 || s->prob.prior_kind == LMC_PRIOR_EPROX || s->prob.prox_scale)) e = hipMalloc(&s->pxbuf, nbytes);
+  if (e == hipSuccess && s->prob.tv_rtol > 0.f && s->base.prior_kind == LMC_PRIOR_TV_ISO) {
+    if (s->prob.tv_warm) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "tv_rtol > 0 and tv_warm exclude each other"); }
+    const int mode = tv_prior_rt_mode(s->prob, s->base, s->epsg * s->gamma);     // 1: inside the fused launch, 0: prox alone, 2: pass by pass
+    if (mode != 2) e = s->rt_tv.need((size_t)s->C, s->prob.tv_niter);
+    if (e == hipSuccess && mode != 1 && !s->pxbuf) e = hipMalloc(&s->pxbuf, nbytes);
+    if (mode == 2) {
+      if (e == hipSuccess) e = hipMalloc(&s->rtmp, nbytes);
+      if (e == hipSuccess) e = hipMalloc(&s->robj, sizeof(double) * 2 * (size_t)s->C);
+      if (e == hipSuccess) e = hipMalloc(&s->rflag, sizeof(int) * ((size_t)s->C + 1));
+    }
+  }
+  if (e == hipSuccess && s->prob.ncvx_kind == LMC_NCVX_ME_TV && s->prob.ncvx_rtol > 0.f) e = s->rt_me.need((size_t)s->C, s->prob.ncvx_niter);
+  {   // launch policy: the lmc_problem fields, their environment variables where a field is 0 -- read here, once, never inside lmc_sampler_step
+    const Problem& q = s->prob;
+    const int ipl = q.iters_per_launch ? q.iters_per_launch : env_int("LMC_ITERS_PER_LAUNCH", 0);
+    s->pol_pair = ipl == 1 ? 0 : (ipl == 2 ? 2 : env_int("LMC_ROWS_PAIR", 1));
+    s->pol_blockpair = ipl == 1 ? 0 : (ipl == 2 ? 1 : (env_int("LMC_BLOCK_PAIR", 1) != 0));
+    s->pol_overlap = q.moments_overlap ? q.moments_overlap : (getenv("LMC_MOMENTS_OVERLAP") ? (env_int("LMC_MOMENTS_OVERLAP", 0) ? 1 : -1) : 0);
+    s->pol_bg_wgs = q.moments_bg_wgs > 0 ? q.moments_bg_wgs : env_int("LMC_MOMENTS_BG_WGS", -1);
+    if (q.prox_scale) { s->pol_pair = 0; s->pol_blockpair = 0; }   // array-valued epsg: the prox is its own launch before every step
+  }
+  if (e == hipSuccess && s->prob.tv_warm) {
+    lmc::StepArgs probe = s->base;
+    probe.x_in = s->x[0];
+    if (s->base.prior_kind != LMC_PRIOR_TV_ISO || !lmc::pipe_warm_supported(probe)) {
+      lmc_sampler_destroy(s);
+      return fail(LMC_E_UNSUPPORTED, "tv_warm: needs tv_niter in {1, 2, 3} (after tv_lagged_output) and the full-width pipeline kernel "
+                  "(W > 128, W %% 4 == 0 (%% 8 above 256), separable blur <= 7 taps / pointwise / no data term)");
+    }
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+      e = hipMalloc(&s->tvwarm[i], 2 * nbytes);
+      if (e == hipSuccess) e = hipMemset(s->tvwarm[i], 0, 2 * nbytes);
+    }
+  }
+  if (e == hipSuccess) e = alloc_moments(s);
+  if (e != hipSuccess) return alloc_failed(s, e);
+  s->kernel_name = "(no step launched yet)";
+  *out = s;
+  return LMC_OK;
+}
+
+void lmc_sampler_destroy(lmc_sampler* s) {
+  if (!s) return;
+  DeviceGuard dg(s->device);
+  for (float* b : {s->xmid[0], s->xmid[1], s->xspare, s->zero_y, s->xhat, s->ydual, s->uw, s->uw2, s->rhs, s->cr, s->cp, s->cq, s->ctmp, s->xi, s->htb, s->tvstate[0], s->tvstate[1], s->extra, s->pxbuf,
+                   s->mx, s->xp, s->mxp, s->tvwarm[0], s->tvwarm[1], s->rtmp})
+    if (b) (void)hipFree(b);
+  if (s->robj) (void)hipFree(s->robj);
+  if (s->rflag) (void)hipFree(s->rflag);
+  s->rt_tv.release();
+  s->rt_me.release();
+  if (s->mala_d) (void)hipFree(s->mala_d);
+  if (s->flag) (void)hipFree(s->flag);
+  if (s->nacc) (void)hipFree(s->nacc);
+  if (s->scal) (void)hipFree(s->scal);
+  if (s->x[0]) (void)hipFree(s->x[0]);
+  if (s->x[1]) (void)hipFree(s->x[1]);
+  if (s->s1) (void)hipFree(s->s1);
+  if (s->s2) (void)hipFree(s->s2);
+  if (s->packed) (void)hipFree(s->packed);
+  for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
+  if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }
+  for (hipEvent_t e : s->side_ev) if (e) (void)hipEventDestroy(e);
+  delete s;
+}
+
+int lmc_sampler_set_state(lmc_sampler* s, const float* x_dev, void* stream) {
+  if (!s || !x_dev) return fail(LMC_E_INVALID, "NULL argument");
+  DeviceGuard dg(s->device);
+  const size_t nbytes = sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W;
+  HIP_TRY(hipMemcpyAsync(s->x[s->cur], x_dev, nbytes, hipMemcpyDeviceToDevice, S(stream)));
+  if (s->kind == 1) HIP_TRY(hipMemcpyAsync(s->xhat, x_dev, nbytes, hipMemcpyDeviceToDevice, S(stream)));   // xhat = x (algs.py:426)
+  if (s->tvwarm[s->wcur]) HIP_TRY(hipMemsetAsync(s->tvwarm[s->wcur], 0, 2 * nbytes, S(stream)));           // a new start: zero dual
+  s->mala_fresh = false;
+  return LMC_OK;
+}
+
+int lmc_sampler_get_state(lmc_sampler* s, float* x_dev, void* stream) {
+  if (!s || !x_dev) return fail(LMC_E_INVALID, "NULL argument");
+  DeviceGuard dg(s->device);
+  const size_t nbytes = sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W;
+  HIP_TRY(hipMemcpyAsync(x_dev, s->x[s->cur], nbytes, hipMemcpyDeviceToDevice, S(stream)));
+  return LMC_OK;
+}
+
+static int ulpda_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, hipStream_t st);
+static int mymala_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, hipStream_t st);
+
+// f(x_c), g(x_c) of `x` ([C][H][W]) with the sampler's problem and scratch buffers
+static int sampler_energies_at(lmc_sampler* s, const float* x, double* f_out_dev, double* g_out_dev, hipStream_t st) {
+  HIP_TRY(lmc::launch_energies(x, s->C, energy_args(s->prob), f_out_dev, g_out_dev, st));
+  if (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 && g_out_dev)
+    HIP_TRY(lmc::launch_haar_value(x, s->C, s->prob.H, s->prob.W, s->prob.prior_sigma, g_out_dev, st));
+  if (s->prob.ncvx_kind == LMC_NCVX_ME_TV && f_out_dev) {
+    Scratch& sc = scratch_here();
+    HIP_TRY(sc.need_dbl(3 * (size_t)s->C + 2));
+    int rc = me_tv_energy(s->prob, x, s->C, f_out_dev, s->extra, s->tvstate[0], s->tvstate[1], sc.dbl, st, &s->rt_me);
+    if (rc) return rc;
+  }
+  return LMC_OK;
+}
+
+// an iterate the posterior-moment accumulators keep: after burn-in, every thin-th
+static bool kept(const lmc_sampler* s, int64_t it) { return s->moments && it >= s->burn_in && (it - s->burn_in) % s->thin == 0; }
+
+// ME-TV: the inner prox of the Moreau-envelope term at A.x_in, which the fused step then takes as its extra gradient term
+static int me_tv_extra(lmc_sampler* s, lmc::StepArgs& A, hipStream_t st) {
+  if (s->prob.ncvx_kind != LMC_NCVX_ME_TV) return LMC_OK;
+  int rc = me_tv_prox(s->prob, A.x_in, s->extra, s->C, s->tvstate[0], s->tvstate[1], st, &s->rt_me);
+  if (rc) return rc;
+  A.extra = s->extra;
+  A.extra_coef = -s->prob.ncvx_lambda / s->prob.ncvx_gamma;
+  return LMC_OK;
+}
+
+// out = base update of `x_in` with the sampler's coefficients; noise_scale 0 gives the proposal mean m(x_in)
+static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool with_noise, const float* noise, uint32_t iteration,
+                          hipStream_t st, const char** kname, double* f_out = nullptr, double* g_out = nullptr, bool* fused = nullptr) {
+  lmc::StepArgs A = s->base;
+  if (fused) *fused = false;
+  if (f_out && g_out && (variant_of(s->prob) == 0 || variant_of(s->prob) == 7) && s->prob.ncvx_kind == LMC_NCVX_NONE && s->prob.prior_kind == LMC_PRIOR_TV_ISO) {
+    lmc::StepArgs probe = A;
+    probe.x_in = x_in;
+    if (lmc::pipe_supported(probe)) {   // the pipe kernel returns f(x_in), g(x_in) as by-products
+      HIP_TRY(hipMemsetAsync(f_out, 0, sizeof(double) * s->C, st));
+      HIP_TRY(hipMemsetAsync(g_out, 0, sizeof(double) * s->C, st));
+      A.f_out = f_out; A.g_out = g_out; A.g_scale = s->prob.prior_sigma;
+      if (fused) *fused = true;
+    }
+  }
+  A.x_in = x_in;
+  A.x_out = x_out;
+  A.iteration = iteration;
+  A.noise = noise;
+  if (!with_noise) { A.s = 0.f; A.noise_mode = LMC_NOISE_NONE; A.noise = nullptr; }
+  sanitize_pointers(A);
+  int rc = me_tv_extra(s, A, st);   // inner prox of the Moreau-envelope term, then the fused step
+  if (rc) return rc;
+  hipError_t e = launch_step(A, variant_of(s->prob), st, kname, s->tvstate[0], s->tvstate[1], s->pxbuf);
+  if (e == hipErrorInvalidConfiguration) return fail(LMC_E_UNSUPPORTED, "no step-kernel variant covers this configuration");
+  HIP_TRY(e);
+  return LMC_OK;
+}
+
+// ---- MYULA steps ----------------------------------------------------------------------------------------------------------------
+// Posterior-moment reductions of one lmc_sampler_step call.  A kept iterate is reduced in line on the caller's stream, or on the sampler's
+// side stream under the launches that follow.  The side stream runs its batches in the order they were enqueued, so the pending batches form
+// a queue and waiting for one waits for every earlier one.  Three rules order them against the launches:
+//  - a launch that writes an array first waits for every pending batch that reads it, whatever that launch keeps;
+//  - an in-line reduction first waits for every pending batch (the accumulators are shared);
+//  - the call joins every pending batch before it returns: nothing is in flight between calls.
+struct SideMoments {
+  lmc_sampler* s;
+  hipStream_t st;             // the caller's stream
+  bool overlap;               // reductions may go to the side stream in this call
+  int bg_wgs;                 // workgroups of a side-stream reduction
+  const float* reads[kSideBatches][2] = {};   // by slot: the arrays the batch in that slot reads; its end event is s->side_ev[1 + slot]
+  int head = 0, n = 0;                        // pending batches: slots head .. head + n - 1 (mod kSideBatches), oldest first
+
+  hipError_t wait_through(int i) {            // the caller's stream waits for pending batch i (0 = the oldest), hence for batches 0 .. i
+    const int slot = (head + i) % kSideBatches;
+    head = (slot + 1) % kSideBatches;
+    n -= i + 1;
+    return hipStreamWaitEvent(st, s->side_ev[1 + slot], 0);
+  }
+  hipError_t before_write(const float* a, const float* b = nullptr) {   // the launch about to be enqueued writes a and b (b may be NULL)
+    for (int i = n - 1; i >= 0; --i)
+      for (const float* r : reads[(head + i) % kSideBatches])
+        if (r && (r == a || r == b)) return wait_through(i);
+    return hipSuccess;
+  }
+  hipError_t join() { return n ? wait_through(n - 1) : hipSuccess; }
+  // the kept iterates a and b (either may be NULL) that the launch just enqueued wrote: into the accumulators, beside later launches or in line
+  int keep(const float* a, const float* b, bool beside) {
+    if (!a && !b) return LMC_OK;
+    if (beside) {
+      if (n == kSideBatches) HIP_TRY(wait_through(0));
+      const int slot = (head + n) % kSideBatches;
+      HIP_TRY(hipEventRecord(s->side_ev[0], st));
+      HIP_TRY(hipStreamWaitEvent(s->side, s->side_ev[0], 0));
+      for (const float* x : {a, b})
+        if (x) HIP_TRY(lmc::launch_moments_bg(x, s->C, s->prob.H, s->prob.W, s->s1, s->s2, bg_wgs, s->side));
+      HIP_TRY(hipEventRecord(s->side_ev[1 + slot], s->side));
+      reads[slot][0] = a;
+      reads[slot][1] = b;
+      ++n;
+    } else {
+      HIP_TRY(join());
+      for (const float* x : {a, b})
+        if (x) HIP_TRY(lmc::launch_moments(x, s->C, s->prob.H, s->prob.W, s->s1, s->s2, st));
+    }
+    s->count += (uint64_t)s->C * ((a ? 1 : 0) + (b ? 1 : 0));
+    return LMC_OK;
+  }
+};
+
+// The array of its own for a kept iterate in between whose reduction runs under the next launch (alternating by launch).
+static hipError_t xmid_array(lmc_sampler* s, float** out) {
+  float*& xm = s->xmid[s->last_launches & 1];
+  const hipError_t e = xm ? hipSuccess : hipMalloc(&xm, sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W);
+  *out = xm;
+  return e;
+}
+
+// The launch helpers below return the iterations they ran (0: they do not cover the next ones) or a negative lmc_status.
+
+// Two MYULA iterations per launch (lmc_step_rows_pair.hip) where that kernel covers the configuration and the launch is large enough for its
+// long bands: x_{k+2} goes to a third array (neighbouring bands re-read x_k), x_{k+1} is stored only when the moment accumulators keep it.
+// lmc_problem.iterations_per_launch / LMC_ROWS_PAIR: 0 = never, 2 = wherever covered (tests), default = where it pays (n_chains * H >= 2^17).
+static int myula_rows_pair(lmc_sampler* s, SideMoments& m, int left) {
+  if (!s->pol_pair || left < 2 || s->tvwarm[0] || s->rtmp || s->prob.ncvx_kind != LMC_NCVX_NONE ||
+      (variant_of(s->prob) != 0 && variant_of(s->prob) != 6) || (s->pol_pair != 2 && (long long)s->C * s->prob.H < (1 << 17)))
+    return 0;
+  lmc::StepArgs A = s->base;
+  A.x_in = s->x[s->cur];
+  A.iteration = (uint32_t)s->iteration;
+  A.noise = nullptr;
+  sanitize_pointers(A);
+  if (!lmc::rows_pair_supported(A)) return 0;
+  if (!s->xspare) HIP_TRY(hipMalloc(&s->xspare, sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W));
+  const bool keep_mid = kept(s, s->iteration), keep_out = kept(s, s->iteration + 1);
+  float* mid = keep_mid ? s->x[s->cur ^ 1] : nullptr;
+  if (keep_mid && m.overlap) HIP_TRY(xmid_array(s, &mid));
+  HIP_TRY(m.before_write(s->xspare, mid));
+  A.x_out = s->xspare;
+  if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches], m.st));
+  HIP_TRY(lmc::launch_step_rows_pair(A, mid, m.st));
+  if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches + 1], m.st));
+  s->kernel_name = "myula_step_rows_pair_kernel";
+  int rc = m.keep(mid, keep_out ? s->xspare : nullptr, m.overlap);
+  if (rc) return rc;
+  std::swap(s->x[s->cur], s->xspare);        // x[cur] = x_{k+2}; the array that held x_k is the spare now
+  s->iteration += 2;
+  ++s->last_launches;
+  return 2;
+}
+
+// Two iterations per launch on the register-block kernel (Haar prior, stencil-free data term: BASELINE config 5): the update never leaves a
+// thread's 8 x 8 block, so the second iteration runs on the block while it is on chip; x_{k+1} is written (in place, over x_k) only when the
+// moment accumulators keep it.  LMC_BLOCK_PAIR=0 turns it off.  Same arithmetic, same noise: bit-identical to two launches.
+static int myula_block_pair(lmc_sampler* s, SideMoments& m, int left) {
+  if (!s->pol_blockpair || left < 2 || s->tvwarm[0] || s->rtmp || s->prob.ncvx_kind != LMC_NCVX_NONE ||
+      (variant_of(s->prob) != 0 && variant_of(s->prob) != 5))
+    return 0;
+  lmc::StepArgs A = s->base;
+  A.x_in = s->x[s->cur];
+  A.x_out = s->x[s->cur ^ 1];
+  A.iteration = (uint32_t)s->iteration;
+  A.noise = nullptr;
+  sanitize_pointers(A);
+  if (!lmc::block_pair_supported(A)) return 0;
+  // four iterations on chip when none of the three iterates in between is kept (moments off, burn-in, thinning by >= 4)
+  const bool four = left >= 4 && !kept(s, s->iteration) && !kept(s, s->iteration + 1) && !kept(s, s->iteration + 2);
+  const int nf = four ? 4 : 2;
+  const bool keep_mid = !four && kept(s, s->iteration), keep_out = kept(s, s->iteration + nf - 1);
+  A.fused_iters = nf;
+  A.x_mid = keep_mid ? s->x[s->cur] : nullptr;              // in place over x_k (the update is block-local) ...
+  if (keep_mid && m.overlap) HIP_TRY(xmid_array(s, &A.x_mid));   // ... unless its reduction runs under the next launch, which writes x_{k+3} there
+  HIP_TRY(m.before_write(A.x_out, A.x_mid));
+  if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches], m.st));
+  HIP_TRY(lmc::launch_step_block(A, m.st));
+  if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches + 1], m.st));
+  s->kernel_name = four ? "myula_step_block_kernel(4 iterations)" : "myula_step_block_kernel(2 iterations)";
+  int rc = m.keep(A.x_mid, keep_out ? A.x_out : nullptr, m.overlap);
+  if (rc) return rc;
+  s->cur ^= 1;
+  s->iteration += nf;
+  ++s->last_launches;
+  return nf;
+}
+
+// One iteration per launch: every configuration, and the only path for injected noise, the ME-TV term, the warm-started TV prox, the early
+// exits of the TV prox and array-valued epsg.  `last`: the call's last iteration, whose reduction runs in line.
+static int myula_single(lmc_sampler* s, SideMoments& m, const float* noise, bool last) {
+  hipStream_t st = m.st;
+  lmc::StepArgs A = s->base;
+  A.x_in = s->x[s->cur];
+  A.x_out = s->x[s->cur ^ 1];
+  A.iteration = (uint32_t)s->iteration;
+  A.noise = noise;
+  sanitize_pointers(A);
+  int rc = me_tv_extra(s, A, st);   // inner prox of the Moreau-envelope term, then the fused step
+  if (rc) return rc;
+  HIP_TRY(m.before_write(A.x_out));
+  if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches], st));
+  const char* kname = nullptr;
+  hipError_t e;
+  bool stepped = false;
+  if (s->rt_tv.kc && A.prior_kind == LMC_PRIOR_TV_ISO) {   // early exit of the TV prox decided on the device: inside the fused launch, or the prox alone first
+    rc = tv_prior_rt(s->prob, s->epsg * s->gamma, A, s->rt_tv, s->pxbuf, s->tvstate[0], s->tvstate[1], st);
+    if (rc < 0) return rc;
+    if (rc == 2) return fail(LMC_E_STATE, "the device-side early exit no longer covers this sampler");
+    if (rc == 1) { stepped = true; kname = "myula_step_pipe_kernel(per-chain exit)"; }
+  }
+  if (s->rtmp && A.prior_kind == LMC_PRIOR_TV_ISO) {   // early-exit TV prox first (exact pass-by-pass path), consumed as a ready-made prox
+    rc = tv_prox_rtol(s->prob, s->epsg * s->gamma, A.x_in, s->pxbuf, s->rtmp, s->robj, s->rflag, s->C, s->tvstate[0], s->tvstate[1], st);
+    if (rc) return rc;
+    A.prior_kind = LMC_PRIOR_NONE;
+    A.prox_ext = s->pxbuf;
+  }
+  if (s->prob.prox_scale && A.prior_kind != LMC_PRIOR_NONE) {   // array-valued epsg: prox_{epsg[c,i] gamma g} first, consumed as a ready-made prox
+    const Problem& q = s->prob;
+    HIP_TRY(lmc::launch_prior_prox_scaled(q.prior_kind, q.eprox_kind, A.x_in, s->pxbuf, s->C, (int64_t)q.H * q.W, q.prox_scale, q.prox_scale_cs, q.prox_scale_ps,
+                                          s->epsg * s->gamma, q.prior_sigma, q.eprox_p0, q.eprox_p1, q.eprox_mask, st));
+    A.prior_kind = LMC_PRIOR_NONE;
+    A.prox_ext = s->pxbuf;
+  }
+  if (stepped) {
+    e = hipSuccess;
+  } else if (s->tvwarm[0]) {     // warm-started TV prox: the dual of the previous iteration in, this iteration's out
+    A.tv_in = s->tvwarm[s->wcur];
+    A.tv_out = s->tvwarm[s->wcur ^ 1];
+    e = lmc::launch_step_pipe_warm(A, st);
+    kname = "myula_step_pipe_kernel(warm)";
+    s->wcur ^= 1;
+  } else {
+    e = launch_step(A, variant_of(s->prob), st, &kname, s->tvstate[0], s->tvstate[1], s->pxbuf);
+  }
+  if (e == hipErrorInvalidConfiguration) return fail(LMC_E_UNSUPPORTED, "no step-kernel variant covers this configuration");
+  HIP_TRY(e);
+  if (kname) s->kernel_name = kname;
+  if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches + 1], st));
+  s->cur ^= 1;
+  if (kept(s, s->iteration)) {
+    // beside the next launch unless the step kernel is a single launch of an HBM-heavy closed-form-prior kernel at full size: the two then share the memory
+    // system and the reduction outlasts the kernel whatever its workgroup count (blur + l2, 512 x 512 x 1024: in line 0.714 ms per iteration, beside it 0.73-0.83)
+    const bool beside = m.overlap && !last &&
+                        (s->pol_overlap > 0 || s->base.prior_kind == LMC_PRIOR_TV_ISO || (long long)s->C * s->prob.H * s->prob.W <= (1LL << 25));
+    rc = m.keep(s->x[s->cur], nullptr, beside);
+    if (rc) return rc;
+  }
+  ++s->iteration;
+  ++s->last_launches;
+  return 1;
+}
+
+static int myula_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, hipStream_t st) {
+  const size_t per_iter = (size_t)s->C * s->prob.H * s->prob.W;
+  s->timed = false;
+  s->last_launches = 0;
+  if (n_iters == 0) return LMC_OK;
+  if (s->timing) {  // one event pair per step-kernel launch: moment reductions stay outside the brackets
+    while ((int)s->ev.size() < 2 * n_iters) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreate(&e));
+      s->ev.push_back(e);
+    }
+  }
+  // Moment reductions on the side stream under the following launches (lmc_problem.moments_overlap / LMC_MOMENTS_OVERLAP): on at every size --
+  // what bench.py's `value` measures -- and off while the launches are being event-timed (lmc_sampler_enable_timing: the roofline leg wants the
+  // step kernel alone).  BASELINE config 2 (256 x 256 x 128): the 15 us reduction is 40 % of a serial iteration, 40.2 -> 35.9 us per iteration
+  // with 128 background workgroups.  Headline size: the reduction under the step kernel costs that kernel 6 % (1.76 -> 1.89 ms per launch) and
+  // saves its own 0.22 ms -- 1.976 -> 1.90-1.92 ms per iteration with 256 workgroups (16: 3.19, 64: 2.07, 128: 1.92, 256: 1.90, 512: 1.94,
+  // 1024: 1.98 ms; too few and the reduction outlasts the step kernel).  (lmc_problem.moments_bg_workgroups / LMC_MOMENTS_BG_WGS: fixed at creation)
+  const bool overlap = !s->timing && s->pol_overlap >= 0 && s->moments && n_iters > 1;
+  const int bg_wgs = s->pol_bg_wgs >= 0 ? s->pol_bg_wgs : ((long long)per_iter <= (1LL << 25) ? 128 : 256);   // 0: the full-speed kernel
+  if (overlap && !s->side) {
+    int prio_least = 0, prio_greatest = 0;     // lowest priority: the step kernel's workgroups go first
+    HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    HIP_TRY(hipStreamCreateWithPriority(&s->side, hipStreamNonBlocking, prio_least));
+    for (hipEvent_t& e : s->side_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  SideMoments m{s, st, overlap, bg_wgs};
+  for (int k = 0; k < n_iters;) {
+    int done = 0;
+    if (!noise_dev) done = myula_rows_pair(s, m, n_iters - k);        // the pair launches draw Philox noise
+    if (!noise_dev && !done) done = myula_block_pair(s, m, n_iters - k);
+    if (!done) done = myula_single(s, m, noise_dev ? noise_dev + (size_t)k * per_iter : nullptr, k + 1 == n_iters);
+    if (done < 0) {
+      (void)m.join();
+      return done;
+    }
+    k += done;
+  }
+  HIP_TRY(m.join());   // everything this call enqueued is ordered before whatever the caller enqueues next
+  s->timed = s->timing;
+  return LMC_OK;
+}
+
+int lmc_sampler_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (n_iters < 0) return fail(LMC_E_INVALID, "n_iters < 0");
+  if (s->noise_mode == LMC_NOISE_INJECTED && !noise_dev && n_iters > 0)
+    return fail(LMC_E_INVALID, "noise_mode is INJECTED but noise_dev is NULL");
+  if (s->noise_mode != LMC_NOISE_INJECTED && noise_dev)
+    return fail(LMC_E_INVALID, "noise_dev given but noise_mode is not INJECTED");
+  if (s->iteration + n_iters > 0xFFFFFFFFLL) return fail(LMC_E_STATE, "iteration counter would exceed 32 bits");
+  if (s->kind == 2) return mymala_step(s, n_iters, noise_dev, S(stream));
+  if (s->kind == 1) return ulpda_step(s, n_iters, noise_dev, S(stream));
+  return myula_step(s, n_iters, noise_dev, S(stream));
+}
+
+// ---- MYMALA: Metropolis-adjusted MYULA at image scale (generalises prox_lmc.py:134-158) -------------------------------
+int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out) {
+  int rc = lmc_myula_create(cfg, out);
+  if (rc) return rc;
+  lmc_sampler* s = *out;
+  *out = nullptr;
+  if (s->tvwarm[0]) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA needs a proposal mean that is a function of x alone: tv_warm is not allowed"); }
+  if (s->rtmp || s->rt_tv.kc) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA with tv_rtol > 0 is not built (use the fixed-count prox, tv_rtol = 0)"); }
+  if (s->prob.prox_scale) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA takes a scalar epsg (the reference's array-valued epsg is MYULA's, algs.py:509)"); }
+  s->kind = 2;
+  const size_t nbytes = sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W;
+  hipError_t e = hipMalloc(&s->mx, nbytes);
+  if (e == hipSuccess) e = hipMalloc(&s->xp, nbytes);
+  if (e == hipSuccess) e = hipMalloc(&s->mxp, nbytes);
+  if (e == hipSuccess) e = hipMalloc(&s->mala_d, sizeof(double) * 6 * (size_t)s->C);
+  if (e == hipSuccess) e = hipMalloc(&s->flag, sizeof(int) * (size_t)s->C);
+  if (e == hipSuccess) e = hipMalloc(&s->nacc, sizeof(unsigned long long) * (size_t)s->C);
+  if (e == hipSuccess) e = hipMemset(s->nacc, 0, sizeof(unsigned long long) * (size_t)s->C);
+  if (e == hipSuccess) e = hipMemset(s->mala_d, 0, sizeof(double) * 6 * (size_t)s->C);
+  if (e != hipSuccess) return alloc_failed(s, e);
+  *out = s;
+  return LMC_OK;
+}
+
+static int mymala_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, hipStream_t st) {
+  const size_t img = (size_t)s->prob.H * s->prob.W, per_iter = (size_t)s->C * img;
+  const int C = s->C;
+  double *U = s->mala_d, *fp = U + C, *gp = U + 2 * C, *d1 = U + 3 * C, *d2 = U + 4 * C, *la = U + 5 * C;
+  float* x = s->x[s->cur];
+  s->timed = false;
+  s->last_launches = 0;
+  const char* kname = nullptr;
+  if (!s->mala_fresh && n_iters > 0) {   // m(x) and U(x) = f(x) + g(x) of the current state (after create / set_state)
+    bool fused = false;
+    int rc = sampler_update(s, x, s->mx, false, nullptr, (uint32_t)s->iteration, st, &kname, fp, gp, &fused);
+    if (rc) return rc;
+    if (!fused) rc = sampler_energies_at(s, x, fp, gp, st);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d1, 0, sizeof(double) * C, st));
+    HIP_TRY(lmc::launch_axpy_env(fp, gp, d1, C, -s->epsg, 1.f, st));    // fp += epsg * gp  (f -= (-epsg) * (g + d1/2) with d1 = 0): U = f + epsg g, the
+                                                                        // potential MYULA's drift is built from (algs.py:569, 582)
+    HIP_TRY(hipMemcpyAsync(U, fp, sizeof(double) * C, hipMemcpyDeviceToDevice, st));
+    s->mala_fresh = true;
+  }
+  for (int k = 0; k < n_iters; ++k) {
+    const float* xi = noise_dev ? noise_dev + (size_t)k * per_iter : s->xi;
+    if (s->noise_mode == LMC_NOISE_PHILOX) {   // x' = m(x) + s xi with the Philox field drawn inside the proposal kernel, and ||x' - m(x)||^2
+      HIP_TRY(lmc::mala_propose_philox(s->mx, s->xp, C, s->prob.H, s->prob.W, s->base.s, s->base.key0, s->base.key1, (uint32_t)s->iteration,
+                                       s->base.chain_offset, d1, st));
+    } else if (s->noise_mode == LMC_NOISE_NONE) {   // deterministic proposal x' = m(x): d1 = 0
+      HIP_TRY(hipMemcpyAsync(s->xp, s->mx, sizeof(float) * per_iter, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemsetAsync(d1, 0, sizeof(double) * C, st));
+    } else {
+      HIP_TRY(lmc::mala_propose(s->mx, xi, s->xp, C, img, s->base.s, d1, st));          // x' and ||x' - m(x)||^2
+    }
+    bool fused = false;
+    int rc = sampler_update(s, s->xp, s->mxp, false, nullptr, (uint32_t)s->iteration, st, &kname, fp, gp, &fused);   // m(x') [+ f, g]
+    if (rc) return rc;
+    if (!fused) rc = sampler_energies_at(s, s->xp, fp, gp, st);                           // f(x'), g(x')
+    if (rc) return rc;
+    HIP_TRY(lmc::launch_sqdiff(x, s->mxp, C, img, d2, st));                               // ||x - m(x')||^2
+    HIP_TRY(lmc::mala_accept(C, U, fp, gp, s->epsg, d1, d2, s->tau, s->base.key0, s->base.key1, (uint32_t)s->iteration, s->base.chain_offset,
+                             s->flag, s->nacc, la, st));
+    // accepted chains: x <- x', m(x) <- m(x').  (The other direction -- keep the proposal buffers and give the rejected chains their old
+    // state back -- was measured: 3.0 instead of 3.7 ms at 98 % acceptance, but 3.7 instead of 3.0 ms at 48 %; the choice would have to
+    // follow the acceptance rate, which the host does not see without a synchronisation.)
+    HIP_TRY(lmc::mala_select(s->flag, x, s->mx, s->xp, s->mxp, C, img, 1, st));
+    if (kept(s, s->iteration)) {
+      HIP_TRY(lmc::launch_moments(x, C, s->prob.H, s->prob.W, s->s1, s->s2, st));
+      s->count += (uint64_t)C;
+    }
+    ++s->iteration;
+  }
+  if (kname) s->kernel_name = kname;
+  return LMC_OK;
+}
+
+int lmc_sampler_get_acceptance(lmc_sampler* s, uint64_t* accepted_dev, double* last_log_alpha_dev, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (s->kind != 2) return fail(LMC_E_STATE, "not a MYMALA sampler");
+  if (accepted_dev) HIP_TRY(hipMemcpyAsync(accepted_dev, s->nacc, sizeof(uint64_t) * (size_t)s->C, hipMemcpyDeviceToDevice, S(stream)));
+  if (last_log_alpha_dev)
+    HIP_TRY(hipMemcpyAsync(last_log_alpha_dev, s->mala_d + 5 * (size_t)s->C, sizeof(double) * (size_t)s->C, hipMemcpyDeviceToDevice, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_sampler_enable_timing(lmc_sampler* s, int32_t on) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  s->timing = on != 0;
+  s->timed = false;
+  return LMC_OK;
+}
+
+// ---- ULPDA ---------------------------------------------------------------------------------------
+
+static int ulpda_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, hipStream_t st) {
+  const int H = s->prob.H, W = s->prob.W;
+  const int64_t C = s->C;
+  const size_t per_iter = (size_t)C * H * W;
+  const int iso = s->prob.prior_kind == LMC_PRIOR_TV_ISO;
+  s->timed = false;
+  s->last_launches = 0;
+  bool used_pairs = false;
+  for (int k = 0; k < n_iters; ++k) {
+    float* x = s->x[s->cur];
+    const float ts = s->tau * s->prob.sigma_f;
+    // pre-step of L2_ncvx_tv.prox: with a blur the right-hand side also takes tau sigma H^T b; the pointwise solves add their tau sigma m b themselves
+    const float* htb_nc = s->prob.data_kind == LMC_DATA_BLUR ? s->htb : s->prob.y;
+    const float ts_nc = s->prob.data_kind == LMC_DATA_BLUR ? ts : 0.f;
+    if (s->gfirst)   // y <- proxdual(y + mu A xhat)   (algs.py:436)
+      HIP_TRY(lmc::ulpda_dual_update(s->xhat, s->ydual, C, H, W, s->mu, s->prob.prior_sigma, iso, st));
+    // v = x - tau (A^T y + z) [+ tau sigma H^T b]      (algs.py:437-440 / 443-446)
+    if (s->prob.ncvx_kind == LMC_NCVX_MC_TV) {   // L2_ncvx_tv.prox pre-step (algs.py:213-217), then + tau sigma H^T b (:225)
+      HIP_TRY(lmc::ulpda_rhs(x, s->ydual, s->z, nullptr, s->ctmp, C, H, W, s->tau, ts, st));
+      HIP_TRY(lmc::ulpda_ncvx_rhs(s->ctmp, htb_nc, s->rhs, C, H, W, s->tau * s->prob.ncvx_lambda, s->prob.ncvx_gamma, ts_nc, st));
+    } else if (s->prob.ncvx_kind == LMC_NCVX_ME_TV) {   // x += tau*lamda/gamma (x - prox_{gamma TV}(x))  (algs.py:221-223)
+      HIP_TRY(lmc::ulpda_rhs(x, s->ydual, s->z, nullptr, s->ctmp, C, H, W, s->tau, ts, st));
+      int rc = me_tv_prox(s->prob, s->ctmp, s->extra, C, s->tvstate[0], s->tvstate[1], st, &s->rt_me);
+      if (rc) return rc;
+      HIP_TRY(lmc::ulpda_me_rhs(s->ctmp, s->extra, htb_nc, s->rhs, C, H, W, s->tau * s->prob.ncvx_lambda / s->prob.ncvx_gamma, ts_nc, st));
+    } else {
+      HIP_TRY(lmc::ulpda_rhs(x, s->ydual, s->z, s->prob.data_kind == LMC_DATA_BLUR ? s->htb : nullptr, s->rhs, C, H, W, s->tau, ts, st));
+    }
+    const float* u = s->rhs;
+    if (s->prob.data_kind == LMC_DATA_BLUR) {
+      if (!s->warm) HIP_TRY(hipMemsetAsync(s->uw, 0, sizeof(float) * per_iter, st));
+      float* where = s->uw;
+      { int rc = cg_solve_fused(s->prob, ts, s->uw, s->rhs, s->cr, s->cp, s->cq, s->scal, C, s->cg_niter, s->zero_y, st, s->uw2, &where); if (rc) return rc; }
+      if (where != s->uw) { s->uw2 = s->uw; s->uw = where; used_pairs = true; }       // the pair launches deliver the solution in the other array
+      u = s->uw;
+    } else if (s->prob.data_kind != LMC_DATA_NONE) {
+      HIP_TRY(lmc::ulpda_pointwise_prox(s->rhs, s->uw, s->prob.y, s->prob.mask, C, H, W, ts, s->prob.data_kind, st));
+      u = s->uw;
+    }
+    // x <- u + sqrt(2 tau) xi ; xhat <- x + theta (x - x_old)     (algs.py:440-441 / 446-447)
+    if (s->noise_mode == LMC_NOISE_PHILOX && (W & 3) == 0) {     // the Philox field is drawn inside the pass
+      HIP_TRY(lmc::ulpda_finish_philox(x, s->xhat, u, C, H, W, std::sqrt(2.f * s->tau), s->theta, s->base.key0, s->base.key1,
+                                       (uint32_t)s->iteration, s->base.chain_offset, st));
+    } else {
+      const float* xi = nullptr;
+      if (s->noise_mode == LMC_NOISE_INJECTED) xi = noise_dev + (size_t)k * per_iter;
+      else if (s->noise_mode == LMC_NOISE_PHILOX) {
+        HIP_TRY(lmc::launch_noise(s->xi, (int)C, H, W, s->base.key0, s->base.key1, (uint32_t)s->iteration, s->base.chain_offset, st));
+        xi = s->xi;
+      }
+      HIP_TRY(lmc::ulpda_finish(x, s->xhat, u, xi, C, H, W, std::sqrt(2.f * s->tau), s->theta, st));
+    }
+    if (!s->gfirst)  // (algs.py:448)
+      HIP_TRY(lmc::ulpda_dual_update(s->xhat, s->ydual, C, H, W, s->mu, s->prob.prior_sigma, iso, st));
+    if (kept(s, s->iteration)) {
+      HIP_TRY(lmc::launch_moments(x, s->C, H, W, s->s1, s->s2, st));
+      s->count += (uint64_t)s->C;
+    }
+    ++s->iteration;
+  }
+  s->kernel_name = used_pairs ? "ulpda (multi-kernel, chebyshev pairs)" : "ulpda (multi-kernel)";
+  return LMC_OK;
+}
+
+int lmc_ulpda_create(const lmc_ulpda_config* cfg, lmc_sampler** out) {
+  if (!cfg || !out) return fail(LMC_E_INVALID, "NULL argument");
+  *out = nullptr;
+  if (cfg->struct_size != sizeof(lmc_ulpda_config))
+    return fail(LMC_E_INVALID, "lmc_ulpda_config.struct_size %u != %zu (ABI mismatch)", cfg->struct_size, sizeof(lmc_ulpda_config));
+  int rc = check_config(*cfg, cfg->tau > 0.f && cfg->mu > 0.f, "tau and mu must be > 0");
+  if (rc) return rc;
+  if (cfg->problem.prior_kind != LMC_PRIOR_TV_ISO && cfg->problem.prior_kind != LMC_PRIOR_TV_ANISO)
+    return fail(LMC_E_UNSUPPORTED, "ULPDA needs g o A with g = L21 (LMC_PRIOR_TV_ISO) or L1 (LMC_PRIOR_TV_ANISO)");
+  if (!(cfg->problem.prior_sigma > 0.f)) return fail(LMC_E_INVALID, "prior_sigma (dual ball radius) must be > 0");
+  if (cfg->problem.data_kind == LMC_DATA_BLUR && cfg->cg_niter < 1) return fail(LMC_E_INVALID, "cg_niter must be >= 1");
+  if (cfg->problem.ncvx_kind != LMC_NCVX_NONE && cfg->problem.data_kind == LMC_DATA_NONE)
+    return fail(LMC_E_UNSUPPORTED, "the non-convex term belongs to a data term (blur, identity or mask)");
+  lmc_sampler* s = new (std::nothrow) lmc_sampler();
+  if (!s) return fail(LMC_E_NOMEM, "host allocation failed");
+  lmc_problem pr = cfg->problem;
+  if (pr.prior_kind == LMC_PRIOR_TV_ISO && pr.tv_niter < 1) pr.tv_niter = 1;   // unused by ULPDA; keeps the loader happy
+  rc = load_problem(&pr, s->prob);
+  if (rc) { delete s; return rc; }
+  if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }
+  s->kind = 1;
+  s->C = cfg->n_chains;
+  s->chain_offset = cfg->chain_offset;
+  s->tau = cfg->tau; s->mu = cfg->mu; s->theta = cfg->theta;
+  s->gfirst = cfg->gfirst != 0; s->cg_niter = cfg->cg_niter; s->warm = cfg->warm != 0;
+  s->z = cfg->z_dev;
+  s->seed = cfg->seed;
+  s->noise_mode = cfg->noise_mode;
+  s->moments = cfg->moments; s->burn_in = cfg->burn_in; s->thin = cfg->thin < 1 ? 1 : cfg->thin;
+  s->base.key0 = (uint32_t)(s->seed & 0xFFFFFFFFu);
+  s->base.key1 = (uint32_t)(s->seed >> 32);
+  s->base.chain_offset = (uint32_t)s->chain_offset;
+  const size_t n = (size_t)s->C * s->prob.H * s->prob.W, img = (size_t)s->prob.H * s->prob.W;
+  hipError_t e = hipSuccess;
+  auto alloc = [&](float** p, size_t count) { if (e == hipSuccess) e = hipMalloc(p, sizeof(float) * count); if (e == hipSuccess) e = hipMemset(*p, 0, sizeof(float) * count); };
+  alloc(&s->x[0], n); alloc(&s->xhat, n); alloc(&s->ydual, 2 * n); alloc(&s->uw, n); alloc(&s->rhs, n);
+  if (s->noise_mode == LMC_NOISE_PHILOX) alloc(&s->xi, n);
+  if (s->prob.data_kind == LMC_DATA_BLUR) {
+    alloc(&s->cr, n); alloc(&s->cp, n); alloc(&s->cq, n); alloc(&s->ctmp, n); alloc(&s->htb, img); alloc(&s->zero_y, img);
+    if (lmc::cheb_pair_supported(s->prob.H, s->prob.W, s->prob.taps)) alloc(&s->uw2, n);
+    if (e == hipSuccess) e = hipMalloc(&s->scal, sizeof(double) * (4 * (size_t)s->C + 1));
+    if (e == hipSuccess) e = lmc::launch_blur(s->prob.y, s->htb, 1, s->prob.H, s->prob.W, s->prob.taps, 1, nullptr);   // H^T b
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  if (s->prob.ncvx_kind != LMC_NCVX_NONE && !s->ctmp) alloc(&s->ctmp, n);      // pointwise data terms: the pre-step of L2_ncvx_tv.prox needs its own array
+  if (s->prob.ncvx_kind == LMC_NCVX_ME_TV) {
+    alloc(&s->extra, n);
+    if (needs_tv_state(s->prob)) { alloc(&s->tvstate[0], 4 * n); alloc(&s->tvstate[1], 4 * n); }
+    if (e == hipSuccess && s->prob.ncvx_rtol > 0.f) e = s->rt_me.need((size_t)s->C, s->prob.ncvx_niter);     // early exit of the inner prox, decided on the device
+  }
+  if (e == hipSuccess) e = alloc_moments(s);
+  if (e != hipSuccess) return alloc_failed(s, e);
+  s->kernel_name = "(no step launched yet)";
+  *out = s;
+  return LMC_OK;
+}
+
+int lmc_sampler_set_dual(lmc_sampler* s, const float* y_dev, void* stream) {
+  if (!s || !y_dev) return fail(LMC_E_INVALID, "NULL argument");
+  DeviceGuard dg(s->device);
+  if (s->kind != 1) return fail(LMC_E_STATE, "not a ULPDA sampler");
+  HIP_TRY(hipMemcpyAsync(s->ydual, y_dev, sizeof(float) * 2 * (size_t)s->C * s->prob.H * s->prob.W, hipMemcpyDeviceToDevice, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_sampler_get_dual(lmc_sampler* s, float* y_dev, void* stream) {
+  if (!s || !y_dev) return fail(LMC_E_INVALID, "NULL argument");
+  DeviceGuard dg(s->device);
+  if (s->kind != 1) return fail(LMC_E_STATE, "not a ULPDA sampler");
+  HIP_TRY(hipMemcpyAsync(y_dev, s->ydual, sizeof(float) * 2 * (size_t)s->C * s->prob.H * s->prob.W, hipMemcpyDeviceToDevice, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_sampler_set_steps(lmc_sampler* s, float tau, float mu) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  if (s->kind != 1) return fail(LMC_E_STATE, "not a ULPDA sampler");
+  if (!(tau > 0.f) || !(mu > 0.f)) return fail(LMC_E_INVALID, "tau and mu must be > 0");
+  s->tau = tau; s->mu = mu;
+  return LMC_OK;
+}
+
+int64_t lmc_sampler_iteration(const lmc_sampler* s) { return s ? s->iteration : -1; }
+
+int lmc_sampler_set_iteration(lmc_sampler* s, int64_t it) {
+  if (!s || it < 0 || it > 0xFFFFFFFFLL) return fail(LMC_E_INVALID, "bad iteration");
+  s->iteration = it;
+  return LMC_OK;
+}
+
+int lmc_sampler_get_moments(lmc_sampler* s, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
+  const size_t mb = sizeof(double) * (size_t)s->prob.H * s->prob.W;
+  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, s->s1, mb, hipMemcpyDeviceToDevice, S(stream)));
+  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, s->s2, mb, hipMemcpyDeviceToDevice, S(stream)));
+  HIP_TRY(hipStreamSynchronize(S(stream)));
+  if (count) *count = s->count;
+  return LMC_OK;
+}
+
+int lmc_sampler_reset_moments(lmc_sampler* s, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
+  const size_t mb = sizeof(double) * (size_t)s->prob.H * s->prob.W;
+  HIP_TRY(hipMemsetAsync(s->s1, 0, mb, S(stream)));
+  HIP_TRY(hipMemsetAsync(s->s2, 0, mb, S(stream)));
+  s->count = 0;
+  return LMC_OK;
+}
+
+int lmc_sampler_energies(lmc_sampler* s, double* f_out_dev, double* g_out_dev, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  return sampler_energies_at(s, s->x[s->cur], f_out_dev, g_out_dev, S(stream));
+}
+
+int lmc_sampler_noise(lmc_sampler* s, int64_t iteration, float* out_dev, void* stream) {
+  if (!s || !out_dev) return fail(LMC_E_INVALID, "NULL argument");
+  DeviceGuard dg(s->device);
+  if (iteration < 0 || iteration > 0xFFFFFFFFLL) return fail(LMC_E_INVALID, "bad iteration");
+  HIP_TRY(lmc::launch_noise(out_dev, s->C, s->prob.H, s->prob.W, s->base.key0, s->base.key1, (uint32_t)iteration,
+                            s->base.chain_offset, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_sampler_last_step_timing(lmc_sampler* s, float* total_ms, int32_t* n_launches) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (!s->timed || s->last_launches < 1)
+    return fail(LMC_E_STATE, "no timed lmc_sampler_step call to report (lmc_sampler_enable_timing first)");
+  HIP_TRY(hipEventSynchronize(s->ev[2 * s->last_launches - 1]));
+  float ms = 0.f;
+  for (int k = 0; k < s->last_launches; ++k) {
+    float d = 0.f;
+    HIP_TRY(hipEventElapsedTime(&d, s->ev[2 * k], s->ev[2 * k + 1]));
+    ms += d;
+  }
+  if (total_ms) *total_ms = ms;
+  if (n_launches) *n_launches = s->last_launches;
+  return LMC_OK;
+}
+
+const char* lmc_sampler_kernel_name(const lmc_sampler* s) { return s ? s->kernel_name.c_str() : ""; }
+
+int lmc_sampler_tv_exit_stats(lmc_sampler* s, int32_t which, int32_t* passes_dev, uint64_t* reruns_host, void* stream) {
+  if (!s || (which != 0 && which != 1)) return fail(LMC_E_INVALID, "bad arguments");
+  DeviceGuard dg(s->device);
+  RtState& rt = which == 0 ? s->rt_tv : s->rt_me;
+  if (!rt.kc) return fail(LMC_E_STATE, "this sampler does not run the device-side early exit for that prox (tv_rtol / ncvx_rtol = 0, or the pass-by-pass path)");
+  hipStream_t st = S(stream);
+  if (passes_dev) HIP_TRY(hipMemcpyAsync(passes_dev, rt.pred, sizeof(int) * (size_t)s->C, hipMemcpyDeviceToDevice, st));
+  unsigned long long r[4] = {0, 0, 0, 0};
+  if (reruns_host) HIP_TRY(hipMemcpyAsync(r, rt.reruns, sizeof r, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (reruns_host) for (int i = 0; i < 4; ++i) reruns_host[i] = r[i];
+  return LMC_OK;
+}
+
+}  // extern "C"

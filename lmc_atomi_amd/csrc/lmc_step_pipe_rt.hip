@@ -3,7 +3,7 @@
 // The K = 10 pipeline serves every iteration cap up to 10 in one launch (stages past a chain's count pass the dual through) and up to 60 as a chain of
 // links that hand the dual state over in HBM (the inner prox of the ME-TV term, niter_l2 = 50): a chain leaves in the link that holds its last update,
 // the links before it only advance its dual state, the links after it return at once.  The host side that predicts, verifies and re-runs is
-// lmc_capi.hip: tv_prox_rt.  A translation unit of its own so that the instantiations compile in parallel with the others.
+// lmc_tv_exit.hip: tv_prox_rt.  A translation unit of its own so that the instantiations compile in parallel with the others.
 #include "lmc_step_pipe_kernel.h"
 
 namespace lmc {

@@ -92,7 +92,7 @@ hipError_t launch_step_rows(StepArgs a, hipStream_t st) {
   const long long waves = (long long)a.C * nbands * nstrips;
   if (waves > (1ll << 31) - 8) return hipErrorInvalidConfiguration;
   const int nblk = (int)((waves + 3) / 4);
-  if (a.dot_out) {        // CG operator apply with the p.Ap reduction fused (lmc_capi.hip: cg_solve_fused)
+  if (a.dot_out) {        // CG operator apply with the p.Ap reduction fused (lmc_solve.hip: cg_solve_fused)
     if (!al) {
       if (KT == 5) hipLaunchKernelGGL((myula_step_rows_kernel<8, 5, true, -1, -1, false>), dim3(nblk), dim3(256), 0, st, a, band, nbands);
       else hipLaunchKernelGGL((myula_step_rows_kernel<8, 7, true, -1, -1, false>), dim3(nblk), dim3(256), 0, st, a, band, nbands);
@@ -106,20 +106,16 @@ hipError_t launch_step_rows(StepArgs a, hipStream_t st) {
     return hipGetLastError();
   }
   // uniform boxes (all the reference's blurs): the sliding-window form.  Taps constant on one window [lo, hi] -- the same for rows and columns --
-  // and zero elsewhere; LMC_ROWS_UNI=0 keeps the general form (A/B runs).
-  static const bool uni_on = [] { const char* e = getenv("LMC_ROWS_UNI"); return !e || atoi(e) != 0; }();
-  int lo = -1, hi = -1;
-  if (uni_on) {
-    auto window = [&](const float* t, int& l, int& h) {
-      l = -1; h = -1;
-      for (int i = 0; i < KT; ++i) if (t[i] != 0.f) { if (l < 0) l = i; h = i; }
-      if (l < 0) return false;
-      for (int i = l; i <= h; ++i) if (std::fabs(t[i] - t[l]) > 1e-6f * std::fabs(t[l])) return false;
-      return true;
-    };
-    int l2, h2;
-    if (!(window(uc, lo, hi) && window(vc, l2, h2) && l2 == lo && h2 == hi)) lo = hi = -1;
-  }
+  // and zero elsewhere; other taps take the general form.
+  auto window = [&](const float* t, int& l, int& h) {
+    l = -1; h = -1;
+    for (int i = 0; i < KT; ++i) if (t[i] != 0.f) { if (l < 0) l = i; h = i; }
+    if (l < 0) return false;
+    for (int i = l; i <= h; ++i) if (std::fabs(t[i] - t[l]) > 1e-6f * std::fabs(t[l])) return false;
+    return true;
+  };
+  int lo = -1, hi = -1, l2, h2;
+  if (!(window(uc, lo, hi) && window(vc, l2, h2) && l2 == lo && h2 == hi)) lo = hi = -1;
   {   // uniform boxes and the closed-form elementwise priors: instantiated in lmc_step_rows_uni.hip
     bool handled = false;
     const hipError_t e = launch_step_rows_uni(a, KT, lo, hi, al, nblk, band, nbands, st, &handled);

@@ -100,7 +100,7 @@ __device__ __forceinline__ void rows_body(const StepArgs& P, const int band_rows
   constexpr bool UNI = ULO >= 0;
   static_assert(!UNI || (UHI >= ULO && UHI < KT && !DOT), "uniform-box window");
   if constexpr (DOT) {
-    if (P.skip_flag && *P.skip_flag) return;            // CG operator apply after convergence (lmc_capi.hip: cg_solve_fused)
+    if (P.skip_flag && *P.skip_flag) return;            // CG operator apply after convergence (lmc_solve.hip: cg_solve_fused)
   }
   if (P.run_count && *P.run_count <= P.run_index) return;   // Chebyshev iteration the solve does not need (uniform, one scalar load)
   const int lane = threadIdx.x & 63;

@@ -5,7 +5,7 @@ namespace lmc {
 
 hipError_t launch_step_rows_uni(const StepArgs& a, int KT, int lo, int hi, bool al, int nblk, int band, int nbands, hipStream_t st, bool* handled) {
   *handled = true;
-#define LMC_ROWS_UNI_LAUNCH(PX, KTT, LO, HI, ...)                                                                              \
+#define ROWS_UNI_LAUNCH(PX, KTT, LO, HI, ...)                                                                                  \
   if (KT == KTT && lo == LO && hi == HI) {                                                                                   \
     hipLaunchKernelGGL((myula_step_rows_kernel<PX, KTT, false, LO, HI, ##__VA_ARGS__>), dim3(nblk), dim3(256), 0, st, a, band, nbands); \
     return hipGetLastError();                                                                                                \
@@ -23,13 +23,13 @@ hipError_t launch_step_rows_uni(const StepArgs& a, int KT, int lo, int hi, bool 
     return hipGetLastError();
   }
   if (!al) {
-    LMC_ROWS_UNI_LAUNCH(8, 5, 0, 4, false) LMC_ROWS_UNI_LAUNCH(8, 7, 0, 6, false) LMC_ROWS_UNI_LAUNCH(8, 7, 0, 5, false)
+    ROWS_UNI_LAUNCH(8, 5, 0, 4, false) ROWS_UNI_LAUNCH(8, 7, 0, 6, false) ROWS_UNI_LAUNCH(8, 7, 0, 5, false)
   } else if (a.W <= 256) {
-    LMC_ROWS_UNI_LAUNCH(4, 5, 0, 4) LMC_ROWS_UNI_LAUNCH(4, 7, 0, 6) LMC_ROWS_UNI_LAUNCH(4, 7, 0, 5)
+    ROWS_UNI_LAUNCH(4, 5, 0, 4) ROWS_UNI_LAUNCH(4, 7, 0, 6) ROWS_UNI_LAUNCH(4, 7, 0, 5)
   } else {
-    LMC_ROWS_UNI_LAUNCH(8, 5, 0, 4) LMC_ROWS_UNI_LAUNCH(8, 7, 0, 6) LMC_ROWS_UNI_LAUNCH(8, 7, 0, 5)
+    ROWS_UNI_LAUNCH(8, 5, 0, 4) ROWS_UNI_LAUNCH(8, 7, 0, 6) ROWS_UNI_LAUNCH(8, 7, 0, 5)
   }
-#undef LMC_ROWS_UNI_LAUNCH
+#undef ROWS_UNI_LAUNCH
   *handled = false;
   return hipSuccess;
 }

@@ -334,86 +334,6 @@ __global__ __launch_bounds__(256) void ulpda_rhs4_kernel(const float* __restrict
   *reinterpret_cast<float4*>(rhs + (size_t)blockIdx.y * img + p) = make_float4(o[0], o[1], o[2], o[3]);
 }
 
-// Dual update of iteration k FUSED with the right-hand side of iteration k + 1 (gfirst = false: algs.py:448 followed by :443-445 of the next pass):
-//   y' = proj(y + mu grad(xhat))      rhs = x - tau (A^T y' + z) + ts H^T b
-// A^T y' at a pixel needs y' at the pixel, at the pixel above (row component) and at the pixel to the left (column component): those two dual
-// updates are recomputed here (their inputs are cache hits: the neighbouring threads stream the same lines), y goes from y_in to y_out (other
-// threads still read y_in at their neighbours: not in place).  28 instead of 20 + 16 B per pixel.  Same formulas in the same order as
-// ulpda_dual4_kernel and ulpda_rhs4_kernel: bit-identical to running the two.
-__device__ __forceinline__ void dual_proj(float& a, float& b, float radius, int iso) {
-  if (iso) {
-    const float sc = 1.f / fmaxf(1.f, sqrtf(fmaf(a, a, b * b)) / radius);
-    a *= sc; b *= sc;
-  } else {
-    a = fminf(fmaxf(a, -radius), radius);
-    b = fminf(fmaxf(b, -radius), radius);
-  }
-}
-__global__ __launch_bounds__(256) void ulpda_dual_rhs4_kernel(const float* __restrict__ xhat, const float* __restrict__ y_in, float* __restrict__ y_out,
-                                                              const float* __restrict__ x, const float* __restrict__ z, const float* __restrict__ htb,
-                                                              float* __restrict__ rhs, int H, int W, float mu, float radius, int iso, float tau, float ts) {
-  const unsigned img = (unsigned)H * (unsigned)W;
-  const unsigned p = (blockIdx.x * blockDim.x + threadIdx.x) * 4u;
-  if (p >= img) return;
-  const unsigned r = p / (unsigned)W, col = p - r * (unsigned)W;
-  const float* xc = xhat + (size_t)blockIdx.y * img;
-  const float* yr = y_in + (size_t)blockIdx.y * 2 * img;
-  const float* yc = yr + img;
-  float* yro = y_out + (size_t)blockIdx.y * 2 * img;
-  float* yco = yro + img;
-  const bool down = r + 1 < (unsigned)H, up = r > 0, left = col > 0, right = col + 4 < (unsigned)W;
-  // own pixels (as ulpda_dual4_kernel)
-  const float4 v = *reinterpret_cast<const float4*>(xc + p);
-  const float4 vd = down ? *reinterpret_cast<const float4*>(xc + p + W) : v;
-  const float vr = right ? xc[p + 4] : v.w;
-  const float4 a4 = *reinterpret_cast<const float4*>(yr + p);
-  const float4 b4 = *reinterpret_cast<const float4*>(yc + p);
-  float a[4] = {fmaf(mu, vd.x - v.x, a4.x), fmaf(mu, vd.y - v.y, a4.y), fmaf(mu, vd.z - v.z, a4.z), fmaf(mu, vd.w - v.w, a4.w)};
-  float b[4] = {fmaf(mu, v.y - v.x, b4.x), fmaf(mu, v.z - v.y, b4.y), fmaf(mu, v.w - v.z, b4.z), fmaf(mu, vr - v.w, b4.w)};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) dual_proj(a[k], b[k], radius, iso);
-  *reinterpret_cast<float4*>(yro + p) = make_float4(a[0], a[1], a[2], a[3]);
-  *reinterpret_cast<float4*>(yco + p) = make_float4(b[0], b[1], b[2], b[3]);
-  // the row above: its row component (its "down" neighbour is this row, so it is never a last row)
-  float ua[4] = {0.f, 0.f, 0.f, 0.f};
-  if (up) {
-    const float4 vu = *reinterpret_cast<const float4*>(xc + p - W);
-    const float vur = right ? xc[p - W + 4] : vu.w;
-    const float4 ua4 = *reinterpret_cast<const float4*>(yr + p - W);
-    const float4 ub4 = *reinterpret_cast<const float4*>(yc + p - W);
-    float ub[4] = {fmaf(mu, vu.y - vu.x, ub4.x), fmaf(mu, vu.z - vu.y, ub4.y), fmaf(mu, vu.w - vu.z, ub4.z), fmaf(mu, vur - vu.w, ub4.w)};
-    ua[0] = fmaf(mu, v.x - vu.x, ua4.x); ua[1] = fmaf(mu, v.y - vu.y, ua4.y); ua[2] = fmaf(mu, v.z - vu.z, ua4.z); ua[3] = fmaf(mu, v.w - vu.w, ua4.w);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dual_proj(ua[k], ub[k], radius, iso);
-  }
-  // the pixel to the left: its column component (its "right" neighbour is this thread's first pixel, so it is never a last column)
-  float lb = 0.f;
-  if (left) {
-    const float vl = xc[p - 1];
-    const float vld = down ? xc[p - 1 + W] : vl;
-    float la = fmaf(mu, vld - vl, yr[p - 1]);
-    lb = fmaf(mu, v.x - vl, yc[p - 1]);
-    dual_proj(la, lb, radius, iso);
-  }
-  // right-hand side (as ulpda_rhs4_kernel): A^T y = -div y, terms in the same order: -yr[p] + yr[p-W] - yc[p] + yc[p-1]; the row component of the
-  // last row and the column component of the last column count as zero
-  const float ra[4] = {down ? a[0] : 0.f, down ? a[1] : 0.f, down ? a[2] : 0.f, down ? a[3] : 0.f};
-  const float ca[4] = {b[0], b[1], b[2], right ? b[3] : 0.f};
-  float aty[4] = {((0.f - ra[0]) + ua[0] - ca[0]) + lb, ((0.f - ra[1]) + ua[1] - ca[1]) + ca[0], ((0.f - ra[2]) + ua[2] - ca[2]) + ca[1],
-                  ((0.f - ra[3]) + ua[3] - ca[3]) + ca[2]};
-  if (z) {
-    const float4 zz = *reinterpret_cast<const float4*>(z + p);
-    aty[0] += zz.x; aty[1] += zz.y; aty[2] += zz.z; aty[3] += zz.w;
-  }
-  const float4 xv = *reinterpret_cast<const float4*>(x + (size_t)blockIdx.y * img + p);
-  float o[4] = {fmaf(-tau, aty[0], xv.x), fmaf(-tau, aty[1], xv.y), fmaf(-tau, aty[2], xv.z), fmaf(-tau, aty[3], xv.w)};
-  if (htb) {
-    const float4 hb = *reinterpret_cast<const float4*>(htb + p);
-    o[0] = fmaf(ts, hb.x, o[0]); o[1] = fmaf(ts, hb.y, o[1]); o[2] = fmaf(ts, hb.z, o[2]); o[3] = fmaf(ts, hb.w, o[3]);
-  }
-  *reinterpret_cast<float4*>(rhs + (size_t)blockIdx.y * img + p) = make_float4(o[0], o[1], o[2], o[3]);
-}
-
 __global__ __launch_bounds__(256) void ulpda_finish4_kernel(float4* __restrict__ x, float4* __restrict__ xhat, const float4* __restrict__ u,
                                                             const float4* __restrict__ xi, size_t total4, float s, float theta) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
@@ -475,178 +395,6 @@ hipError_t ulpda_finish_philox(float* x, float* xhat, const float* u, int64_t C,
   return hipGetLastError();
 }
 
-// ---- fused finish + dual update (gfirst = false, algs.py:446-448):  x <- u + s xi ; xhat = x + theta (x - x_old) ;
-//      y <- prox_{mu g*}(y + mu A xhat)   in ONE row-streaming pass.  xhat is consumed in registers and never stored: with gfirst = false
-// nothing else reads it.  One wavefront owns the full width of a band of rows of one chain (lane = PXL consecutive pixels, W <= 64 PXL,
-// W % 4 == 0), so the right-hand neighbour of the forward difference is in the same lane or one wave-shift DPP move away, and the row
-// below is the next row the wave computes -- a band looks one row ahead (recomputed by the next band: its Philox quad included).
-// HBM bytes per pixel: x_old 4 + u 4 + y 8 read, x 4 + y 8 written = 28 (the two separate passes: 16 + 20 = 36).  x_new goes to a second
-// state buffer (ping-pong).
-template <int PXL>
-__global__ __launch_bounds__(256) void ulpda_finish_dual_kernel(const float* __restrict__ x, float* __restrict__ xnew, const float* __restrict__ u, float* __restrict__ y,
-                                                                const float* __restrict__ xi, int H, int W, int C, int band_rows, int nbands,
-                                                                float s, float theta, float mu, float radius, int iso, int philox,
-                                                                uint32_t key0, uint32_t key1, uint32_t iteration, uint32_t chain_offset) {
-  const int lane = threadIdx.x & 63;
-  const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (gw >= C * nbands) return;
-  const int chain = gw / nbands, band = gw - chain * nbands;
-  const int r0 = band * band_rows, r1 = min(r0 + band_rows, H);      // band_rows % 4 == 0: bands start on Philox quad rows
-  const int c0 = lane * PXL;
-  const size_t img = (size_t)H * W;
-  const float* __restrict__ xc = x + (size_t)chain * img;       // x_old: read-only here (the look-ahead row of a band is the first row
-  float* __restrict__ xo_ = xnew + (size_t)chain * img;         // of the next one, which writes its x_new concurrently: separate buffers)
-  const float* __restrict__ uc = u + (size_t)chain * img;
-  const float* __restrict__ nc = xi ? xi + (size_t)chain * img : nullptr;
-  float* __restrict__ yr = y + (size_t)chain * 2 * img;
-  float* __restrict__ yc = yr + img;
-  constexpr int NG = PXL / 4;
-  bool gok[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) gok[g] = c0 + 4 * g < W;
-  float nz[PXL][4];                    // normals of the current quad row-group: [pixel][row in quad]
-  float xh_prev[PXL], xh_cur[PXL];
-#pragma unroll
-  for (int k = 0; k < PXL; ++k) { xh_prev[k] = 0.f; xh_cur[k] = 0.f; nz[k][0] = nz[k][1] = nz[k][2] = nz[k][3] = 0.f; }
-  const int i_end = r1 < H ? r1 : H - 1;              // last row whose xhat is formed: the look-ahead row r1, or the last image row
-  // software pipeline: the loads of row i + 1 (x_old, u, injected noise, and the dual rows of row i) are issued before the arithmetic of
-  // row i; vector-memory operations complete in order, so they stay in flight behind nothing but the stores of row i - 1
-  float4 xo4[2][NG], uu4[2][NG], nn4[2][NG], ya4[2][NG], yb4[2][NG];
-  auto fetch = [&](const int slot, const int row) __attribute__((always_inline)) {
-    const size_t go = (size_t)min(row, H - 1) * W;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const int cc = gok[g] ? c0 + 4 * g : 0;             // lanes past the row read its start (valid memory), their results are never stored
-      xo4[slot][g] = *reinterpret_cast<const float4*>(xc + go + cc);
-      uu4[slot][g] = *reinterpret_cast<const float4*>(uc + go + cc);
-      if (nc) nn4[slot][g] = *reinterpret_cast<const float4*>(nc + go + cc);
-      if (row > r0) {                                      // dual rows of row - 1
-        ya4[slot][g] = *reinterpret_cast<const float4*>(yr + go - W + cc);
-        yb4[slot][g] = *reinterpret_cast<const float4*>(yc + go - W + cc);
-      }
-    }
-  };
-#pragma unroll
-  for (int sl = 0; sl < 2; ++sl)
-#pragma unroll
-    for (int g = 0; g < NG; ++g) nn4[sl][g] = ya4[sl][g] = yb4[sl][g] = make_float4(0.f, 0.f, 0.f, 0.f);
-  fetch(0, r0);
-  auto row_step = [&](auto ss, const int i) __attribute__((always_inline)) {
-    constexpr int SL = decltype(ss)::value;
-    if (i < i_end) fetch(SL ^ 1, i + 1);
-    if (philox && (i & 3) == 0) {
-#pragma unroll
-      for (int k = 0; k < PXL; ++k)
-        if (gok[k >> 2]) quad_normals(key0, key1, iteration, chain_offset + (uint32_t)chain, (uint32_t)(i >> 2) * (uint32_t)W + (uint32_t)(c0 + k), nz[k]);
-    }
-    const size_t go = (size_t)i * W;
-    // x_new and xhat of row i
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const float xo[4] = {xo4[SL][g].x, xo4[SL][g].y, xo4[SL][g].z, xo4[SL][g].w};
-      const float uu[4] = {uu4[SL][g].x, uu4[SL][g].y, uu4[SL][g].z, uu4[SL][g].w};
-      const float nn[4] = {nn4[SL][g].x, nn4[SL][g].y, nn4[SL][g].z, nn4[SL][g].w};
-      float xn[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float nv = philox ? nz[4 * g + q][i & 3] : nn[q];
-        xn[q] = (philox || nc) ? fmaf(s, nv, uu[q]) : uu[q];
-        xh_cur[4 * g + q] = fmaf(theta, xn[q] - xo[q], xn[q]);
-      }
-      if (gok[g] && i < r1) *reinterpret_cast<float4*>(xo_ + go + c0 + 4 * g) = make_float4(xn[0], xn[1], xn[2], xn[3]);
-    }
-    // dual update of row j = i - 1 (its vertical difference needs row i)
-    if (i > r0) {
-      const float right_edge = dpp_right0(xh_prev[0]);          // first pixel of the lane to the right (0 past the wave)
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const float av[4] = {ya4[SL][g].x, ya4[SL][g].y, ya4[SL][g].z, ya4[SL][g].w}, bv[4] = {yb4[SL][g].x, yb4[SL][g].y, yb4[SL][g].z, yb4[SL][g].w};
-        float ao[4], bo[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int k = 4 * g + q;
-          const float here = xh_prev[k];
-          const float rgt = k == PXL - 1 ? right_edge : xh_prev[k + 1];
-          const float dx = xh_cur[k] - here;
-          const float dy = (c0 + k + 1 < W) ? rgt - here : 0.f;
-          float a = fmaf(mu, dx, av[q]), b = fmaf(mu, dy, bv[q]);
-          if (iso) {
-            const float sc = 1.f / fmaxf(1.f, sqrtf(fmaf(a, a, b * b)) / radius);
-            a *= sc; b *= sc;
-          } else {
-            a = fminf(fmaxf(a, -radius), radius);
-            b = fminf(fmaxf(b, -radius), radius);
-          }
-          ao[q] = a; bo[q] = b;
-        }
-        if (gok[g]) {
-          *reinterpret_cast<float4*>(yr + go - W + c0 + 4 * g) = make_float4(ao[0], ao[1], ao[2], ao[3]);
-          *reinterpret_cast<float4*>(yc + go - W + c0 + 4 * g) = make_float4(bo[0], bo[1], bo[2], bo[3]);
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < PXL; ++k) xh_prev[k] = xh_cur[k];
-  };
-  for (int i = r0; i <= i_end; i += 2) {
-    row_step(std::integral_constant<int, 0>{}, i);
-    if (i + 1 <= i_end) row_step(std::integral_constant<int, 1>{}, i + 1);
-  }
-  if (r1 == H) {      // last image row (this band owns it): no row below, dx = 0
-    const size_t go = (size_t)(H - 1) * W;
-    const float right_edge = dpp_right0(xh_prev[0]);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      if (!gok[g]) continue;
-      const float4 a4 = *reinterpret_cast<const float4*>(yr + go + c0 + 4 * g);
-      const float4 b4 = *reinterpret_cast<const float4*>(yc + go + c0 + 4 * g);
-      const float av[4] = {a4.x, a4.y, a4.z, a4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
-      float ao[4], bo[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int k = 4 * g + q;
-        const float here = xh_prev[k];
-        const float rgt = k == PXL - 1 ? right_edge : xh_prev[k + 1];
-        const float dy = (c0 + k + 1 < W) ? rgt - here : 0.f;
-        float a = av[q], b = fmaf(mu, dy, bv[q]);
-        if (iso) {
-          const float sc = 1.f / fmaxf(1.f, sqrtf(fmaf(a, a, b * b)) / radius);
-          a *= sc; b *= sc;
-        } else {
-          a = fminf(fmaxf(a, -radius), radius);
-          b = fminf(fmaxf(b, -radius), radius);
-        }
-        ao[q] = a; bo[q] = b;
-      }
-      *reinterpret_cast<float4*>(yr + go + c0 + 4 * g) = make_float4(ao[0], ao[1], ao[2], ao[3]);
-      *reinterpret_cast<float4*>(yc + go + c0 + 4 * g) = make_float4(bo[0], bo[1], bo[2], bo[3]);
-    }
-  }
-}
-
-bool ulpda_finish_dual_supported(int H, int W) { return (W & 3) == 0 && W >= 4 && W <= 512 && H >= 1; }
-
-// xi: injected noise [C][H][W] or NULL; philox != 0 draws the field in place (xi must then be NULL)
-hipError_t ulpda_finish_dual(const float* x, float* xnew, const float* u, float* y, const float* xi, int64_t C, int H, int W, float s, float theta, float mu,
-                             float radius, int iso, int philox, uint32_t key0, uint32_t key1, uint32_t iteration, uint32_t chain_offset,
-                             hipStream_t st) {
-  if (!ulpda_finish_dual_supported(H, W) || C > (1 << 24) || x == xnew) return hipErrorInvalidConfiguration;
-  const int want = (int)((4096 + C - 1) / C);                       // bands per chain for ~4 waves per SIMD
-  int band = (H + want - 1) / want;
-  if (band < 16) band = 16;
-  band = (band + 3) & ~3;
-  const int nbands = (H + band - 1) / band;
-  const long long waves = (long long)C * nbands;
-  const int nblk = (int)((waves + 3) / 4);
-  if (W <= 256)
-    hipLaunchKernelGGL(ulpda_finish_dual_kernel<4>, dim3(nblk), dim3(256), 0, st, x, xnew, u, y, xi, H, W, (int)C, band, nbands, s, theta, mu, radius,
-                       iso, philox, key0, key1, iteration, chain_offset);
-  else
-    hipLaunchKernelGGL(ulpda_finish_dual_kernel<8>, dim3(nblk), dim3(256), 0, st, x, xnew, u, y, xi, H, W, (int)C, band, nbands, s, theta, mu, radius,
-                       iso, philox, key0, key1, iteration, chain_offset);
-  return hipGetLastError();
-}
-
 static inline bool vec4_ok(int H, int W) { return (W & 3) == 0 && (size_t)H * W < (1ull << 31); }
 
 hipError_t ulpda_dual_update(const float* xhat, float* y, int64_t C, int H, int W, float mu, float radius, int iso,
@@ -661,20 +409,6 @@ hipError_t ulpda_dual_update(const float* xhat, float* y, int64_t C, int H, int 
     return hipGetLastError();
   }
   hipLaunchKernelGGL(ulpda_dual_kernel, dim3(grid1d((size_t)H * W * C, 256)), dim3(256), 0, st, xhat, y, H, W, C, mu, radius, iso);
-  return hipGetLastError();
-}
-
-bool ulpda_dual_rhs_supported(int H, int W) { return vec4_ok(H, W); }
-hipError_t ulpda_dual_rhs(const float* xhat, const float* y_in, float* y_out, const float* x, const float* z, const float* htb, float* rhs, int64_t C,
-                          int H, int W, float mu, float radius, int iso, float tau, float ts, hipStream_t st) {
-  if (!vec4_ok(H, W) || y_in == y_out) return hipErrorInvalidConfiguration;
-  const size_t img = (size_t)H * W;
-  const unsigned gx = (unsigned)((img / 4 + 255) / 256);
-  for (int64_t c0 = 0; c0 < C; c0 += 65535) {
-    const unsigned nc = (unsigned)((C - c0) < 65535 ? (C - c0) : 65535);
-    hipLaunchKernelGGL(ulpda_dual_rhs4_kernel, dim3(gx, nc), dim3(256), 0, st, xhat + c0 * img, y_in + c0 * 2 * img, y_out + c0 * 2 * img, x + c0 * img, z,
-                       htb, rhs + c0 * img, H, W, mu, radius, iso, tau, ts);
-  }
   return hipGetLastError();
 }
 

@@ -289,27 +289,3 @@ def test_ulpda_two_chebyshev_iterations_per_launch(la, shape, C, band, monkeypat
         rowerr = np.abs(got[c] - xs[-1].reshape(shape)).max(axis=1)
         assert rowerr.max() < 0.05, (int(rowerr.argmax()), float(rowerr.max()))       # nothing special at band seams
     smp.close()
-
-
-@pytest.mark.parametrize("shape,C,prior", [((40, 64), 3, "l21"), ((37, 36), 2, "l1"), ((150, 512), 2, "l21"), ((24, 8), 1, "l21")])
-def test_ulpda_dual_update_fused_with_the_next_right_hand_side(la, shape, C, prior, monkeypatch):
-    """gfirst = False: the dual update of iteration k and the right-hand side of iteration k + 1 in one pass (28 instead of 36 B per pixel; the
-    dual projections of the upper and left neighbours are recomputed): bit-identical to the two passes, state and dual, inside one call of
-    several iterations and across calls (where the two passes run)."""
-    rng = np.random.default_rng(shape[1] + 1)
-    img = np.zeros(shape); img[shape[0] // 5:shape[0] // 2, shape[1] // 6:2 * shape[1] // 3] = 150.0
-    h = np.ones((5, 5)) / 25
-    y = O.blur(img, h, (2, 2)) + rng.normal(0, 0.75, shape)
-    outs = {}
-    for mode in ("0", "1"):
-        monkeypatch.setenv("LMC_ULPDA_DUAL_RHS", mode)
-        l2 = la.L2(Op=la.Convolve2D(shape, h), b=y.ravel(), sigma=1 / 0.5625, niter=50, warm=True)
-        pg = la.L21(sigma=0.3) if prior == "l21" else la.L1(sigma=0.3)
-        smp = la.ULPDASampler(l2, pg, la.Gradient(shape), shape, n_chains=C, tau=0.95 * 0.5625, mu=1.0, theta=1.0, gfirst=False, seed=3, chain_offset=1)
-        smp.step(4)
-        smp.set_steps(0.8 * 0.5625, 0.9)            # between calls: the right-hand side is formed again with the new steps
-        smp.step(3)
-        outs[mode] = (smp.get_state().cpu().numpy(), smp.get_dual().cpu().numpy())
-        smp.close()
-    np.testing.assert_array_equal(outs["1"][0], outs["0"][0])
-    np.testing.assert_array_equal(outs["1"][1], outs["0"][1])
