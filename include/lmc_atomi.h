@@ -123,12 +123,13 @@ typedef struct lmc_problem {
    * call at prox_lmc_deconv.py:122 does not override): at the top of loop pass j >= 1 the iterate x - gamma div(r_j) is returned when
    * |obj_j - obj_{j-1}| / obj_j < rtol.  0 (default): off -- every image runs tv_niter dual iterations in one fused launch.  > 0: every image
    * (chain) leaves in the pass the reference's loop leaves it in.  Two implementations, chosen by tv_exit_path:
-   *  - on the device, without synchronisation (ABI 3; the default where the full-width pipeline covers the problem: 128 < W <= 512,
-   *    W % 4 == 0 up to 256 columns and W % 8 == 0 above, tv_niter <= 60): the fused launch runs every chain with a PREDICTED pass count
+   *  - on the device, without synchronisation (ABI 3; the default where the full-width pipeline covers the problem: every width
+   *    128 < W <= 16384, rows of any alignment, tv_niter <= 60; images wider than 512 columns run as column strips whose workgroups
+   *    add their shares of a chain's objectives): the fused launch runs every chain with a PREDICTED pass count
    *    (the pass it left in at the previous call), the stages past it hand the dual through, and the primal objectives of all the iterates
    *    formed are by-products; a one-thread-per-chain kernel replays the exit test on them and the chains whose prediction was wrong
    *    run again (at most three more rounds settle every chain; the launches of settled chains return at once).
-   *  - pass by pass (ABI 2; everything else): one launch per loop pass for the iterate, one for its objective; the host reads the number
+   *  - pass by pass (ABI 2; everything else -- W <= 128, tv_niter > 60 -- and tv_exit_path = 1): one launch per loop pass for the iterate, one for its objective; the host reads the number
    *    of images still iterating after every pass, so this path SYNCHRONISES the stream.
    * Not with tv_warm or MYMALA. */
   float tv_rtol;
@@ -148,7 +149,7 @@ typedef struct lmc_problem {
   /* The same early exit for the inner prox of the ME-TV term: algs.L2_ncvx_tv builds it as TV(dims, 1., niter, rtol) with the class's own
    * default rtol = 1e-4 (algs.py:130,169), used by value, gradient and prox of models M3 / M6 / M9 (prox_lmc_deconv.py:111-113).
    * 0: fixed ncvx_niter updates.  > 0: the device path above over the chained launches (ncvx_niter <= 60, same widths); elsewhere
-   * LMC_E_UNSUPPORTED. */
+   * (W <= 128, ncvx_niter > 60, tv_exit_path = 1) the pass-by-pass path above, which synchronises the stream after every pass. */
   float ncvx_rtol;
   int32_t tv_exit_path;           /* tv_rtol > 0: 0 = the device path where it covers the problem, 1 = always pass by pass (synchronises) */
   /* Launch policy of samplers created from this problem (0 = the library decides).  Each field has an environment variable that supplies the

@@ -140,14 +140,34 @@ __device__ __forceinline__ v2f pipe_ncr(const PipeCr<NP>& c, int i) {
 // what the stage computes anyway -- x - sol = gam T with T = div(rr, ss) on row a, and the forward differences of sol on row b (masked like the dual
 // step: none across the last row / column).  sq += sum T^2 (row a), tv += sum |grad sol| (row b), fp32 per row; the caller folds rows into fp64.
 struct StageObj { v2f sq, tv; };
-template <int NP>
-struct ObjMask { float md; v2f mlast; };     // 1 / 0: the row below exists; the column to the right of the lane's last pair exists
+// PERPIX (rows whose last column can be any pixel of a lane, and column strips): per-pixel 1 / 0 weights instead of mlast -- mx: the column belongs to
+// the sums of this workgroup (its strip's interior, inside the image); my: the same, and a column to its right exists in the IMAGE (a strip's edge is
+// no image edge: the neighbour in the halo is a value of the same iterate).  Set once per wave, before the tick loop: they do not depend on the row.
+template <int NP, bool PERPIX = false>
+struct ObjMask {
+  float md; v2f mlast;                        // 1 / 0: the row below exists; the column to the right of the lane's last pair exists
+  v2f mx[PERPIX ? NP : 1], my[PERPIX ? NP : 1];
+};
+// the objective terms of one pixel pair: T^2 -> sq, |grad sol| -> tv
+template <int NP, bool LASTLANE>
+__device__ __forceinline__ v2f obj_sq(const ObjMask<NP, !LASTLANE>* om, int i, v2f T) {
+  if constexpr (LASTLANE) return T;
+  else return T * om->mx[i];
+}
+template <int NP, bool LASTLANE>
+__device__ __forceinline__ v2f obj_tv(const ObjMask<NP, !LASTLANE>* om, int i, v2f dxv, v2f dyv) {
+  v2f dxm, dym;
+  if constexpr (LASTLANE) { dxm = dxv * pk_set(om->md); dym = i == NP - 1 ? dyv * om->mlast : dyv; }
+  else { dxm = dxv * pk_set(om->md) * om->mx[i]; dym = dyv * om->my[i]; }
+  const v2f n = pk_fma(dxm, dxm, dym * dym);
+  return v2f{__builtin_amdgcn_sqrtf(n.x), __builtin_amdgcn_sqrtf(n.y)};
+}
 
 // SEAML / SEAMR (two-team layout): lane 0's left neighbour of s1 / lane 63's right neighbour of solb is the other team's, `ssl_edge` / `solr_edge`.
 template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAML = false, bool SEAMR = false>
 __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[NP], const v2f (&s1)[NP], const DualRow<NP>& in0,
                                            v2f (&solb)[NP], float gam, float cdown, const PipeCr<NP>& cr, float beta,
-                                           DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP>* om = nullptr,
+                                           DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP, !LASTLANE>* om = nullptr,
                                            float ssl_edge = 0.f, float solr_edge = 0.f) {
   v2f sol[NP];
   const float ssl0 = SEAML ? wave_from_left(s1[NP - 1].y, ssl_edge) : dpp_left0(s1[NP - 1].y);
@@ -157,7 +177,7 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
     const v2f ssl = v2f{i == 0 ? ssl0 : s1[i - 1].y, s1[i].x};
     const v2f T = (r1[i] - in0.rr[i]) + (s1[i] - ssl);
     sol[i] = pk_fma(ngam, T, xa[i]);
-    if constexpr (OBJ) ob->sq = i == 0 ? T * T : pk_fma(T, T, ob->sq);
+    if constexpr (OBJ) { const v2f Tm = obj_sq<NP, LASTLANE>(om, i, T); ob->sq = i == 0 ? Tm * Tm : pk_fma(Tm, Tm, ob->sq); }
   }
   const float solr_last = SEAMR ? wave_from_right(solb[0].x, solr_edge) : dpp_right0(solb[0].x);
 #pragma unroll
@@ -166,10 +186,7 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
     const v2f ncr = pipe_ncr<NP, LASTLANE>(cr, i);
     const v2f dxv = sol[i] - solb[i], dyv = solr - solb[i];
     if constexpr (OBJ) {
-      static_assert(!OBJ || LASTLANE, "objective by-products: rows whose last column is a lane's last pixel");
-      const v2f dxm = dxv * pk_set(om->md), dym = i == NP - 1 ? dyv * om->mlast : dyv;
-      const v2f n = pk_fma(dxm, dxm, dym * dym);
-      const v2f nr = v2f{__builtin_amdgcn_sqrtf(n.x), __builtin_amdgcn_sqrtf(n.y)};
+      const v2f nr = obj_tv<NP, LASTLANE>(om, i, dxv, dyv);
       ob->tv = i == 0 ? nr : ob->tv + nr;
     }
     const v2f r = pk_fma(ncd, dxv, in0.rr[i]);
@@ -192,7 +209,7 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
 // iterate vanish.  Bit-identical to pipe_stage() fed with zeros (x - 0 = x, fma(c, d, 0) = c*d), at ~60 % of its instructions.
 template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAMR = false>
 __device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb)[NP], float cdown, const PipeCr<NP>& cr, float beta,
-                                                 DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP>* om = nullptr,
+                                                 DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP, !LASTLANE>* om = nullptr,
                                                  float solr_edge = 0.f) {
   const float solr_last = SEAMR ? wave_from_right(solb[0].x, solr_edge) : dpp_right0(solb[0].x);
   const v2f ncd = pk_set(-cdown), vb = pk_set(beta);
@@ -203,9 +220,7 @@ __device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb
     const v2f ncr = pipe_ncr<NP, LASTLANE>(cr, i);
     const v2f dxv = xa[i] - solb[i], dyv = solr - solb[i];
     if constexpr (OBJ) {
-      const v2f dxm = dxv * pk_set(om->md), dym = i == NP - 1 ? dyv * om->mlast : dyv;
-      const v2f n = pk_fma(dxm, dxm, dym * dym);
-      const v2f nr = v2f{__builtin_amdgcn_sqrtf(n.x), __builtin_amdgcn_sqrtf(n.y)};
+      const v2f nr = obj_tv<NP, LASTLANE>(om, i, dxv, dyv);
       ob->tv = i == 0 ? nr : ob->tv + nr;
     }
     const v2f r = ncd * dxv;
@@ -295,6 +310,8 @@ __host__ __device__ constexpr int pipe_halo(int K, int KT, int PXL) {
 // them pass (rr, ss) through unchanged -- a delay line with the live stages' timing, so the combine wave forms x - gamma div(rr^kc, ss^kc) -- and every
 // iterate formed leaves its primal objective behind.  In a chained launch the link a chain leaves in does its combine; the links before it only
 // advance the dual state, the ones after it return at once.
+// RT with AL = false: any width the fixed-count kernel covers.  A chain is then gridDim.y workgroups (column strips) that read the same live count, so they
+// run, return and combine together; each adds to the chain's objective slots only what lies in the columns it writes (ObjMask: per-pixel weights).
 // (Round 3, measured and removed again -- git history, commit 49bc3f1 and the three builds after it: the posterior moments of the INPUT state reduced inside this
 // kernel, workgroup b summing the 256-pixel slices b, b + C, ... over all chains, two 1 KB reads per tick.  As a ninth wave: three waves on one SIMD cap the kernel
 // at 168 VGPRs, 128-184 spilled.  In the combine wave: its conditional stores make the compiler wait for every load in flight each tick, 4.05 ms per iteration.  In the
@@ -319,7 +336,10 @@ __host__ __device__ constexpr int pipe_halo(int K, int KT, int PXL) {
 template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS>
 __device__ __forceinline__ void pipe_body(const StepArgs& A) {
   static_assert(!WARM || CHAIN, "the warm dual uses the state hand-over of the chained launches");
-  static_assert(!RT || (AL && !WARM && (K & 1) == 0), "per-chain exit: aligned rows, cold start, even K");
+  static_assert(!RT || (!WARM && (K & 1) == 0), "per-chain exit: cold start, even K");
+  // RT with AL = false: any width, column strips included.  The objective of an iterate reads it one column beyond the strip's interior, which needs
+  // the dual one column further out than the update itself does (K + 1)
+  static_assert(!RT || AL || pipe_halo(K, KT, PXL) >= K + 2, "per-chain exit on column strips: the halo holds the objective's extra column");
   static_assert(TEAMS == 1 || (TEAMS == 2 && K == 10 && PXL == 4 && KT == 5 && AL && !CHAIN && !WARM && !RT),
                 "two teams: one fixed-count launch, 5 taps, aligned rows, 4 pixels per lane");
   using G = PipeGeom<K>;
@@ -684,9 +704,18 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     constexpr int NP = PXL / 2;
     const bool live1 = !RT || g1 <= kc, live2 = !RT || (!spread && g2 <= kc);      // wave-uniform; live stages are a prefix
     const bool fullpass2 = spread && wave < kc;          // a later wave still runs a live stage: slot k2 hands all four fields on, not (rr, ss) only
-    ObjMask<NP> om;
+    ObjMask<NP, !AL> om;
     om.md = 0.f;
     om.mlast = v2f{1.f, (c0 + PXL - 1 == W - 1) ? 0.f : 1.f};
+    if constexpr (RT && !AL) {
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        const int ca = c0 + 2 * i, cb = ca + 1;
+        const bool ina = ca >= st_lo && ca < st_hi, inb_ = cb >= st_lo && cb < st_hi;      // st_hi <= W
+        om.mx[i] = v2f{ina ? 1.f : 0.f, inb_ ? 1.f : 0.f};
+        om.my[i] = v2f{ina && ca < W - 1 ? 1.f : 0.f, inb_ && cb < W - 1 ? 1.f : 0.f};
+      }
+    }
     double osq1 = 0.0, otv1 = 0.0, osq2 = 0.0, otv2 = 0.0;            // RT: objective sums of the iterates stages k1 / k2 form (fp64 over rows)
     DualRow<NP> inb[2], o1[2];
     v2f sol1[NP], sol2[NP];
@@ -893,6 +922,17 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     float pprev[RT ? PXL : 1];
 #pragma unroll
     for (int k = 0; k < (RT ? PXL : 1); ++k) pprev[k] = 0.f;
+    // AL = false: per-pixel weights of the sums, as in the stages (ObjMask): the strip's interior; no horizontal difference across the last image column
+    constexpr bool PM = RT && !AL;
+    float cmx[PM ? PXL : 1], cmy[PM ? PXL : 1];
+    if constexpr (PM) {
+#pragma unroll
+      for (int j = 0; j < PXL; ++j) {
+        const bool in = c0 + j >= st_lo && c0 + j < st_hi;
+        cmx[j] = in ? 1.f : 0.f;
+        cmy[j] = in && c0 + j + 1 < W ? 1.f : 0.f;
+      }
+    }
     // rows of the ME-TV term's prox image (A.extra), requested three ticks ahead of their use (slot tick & 3): a load issued at
     // its point of use would expose an HBM access per tick
     float exq[4][PXL];
@@ -935,7 +975,8 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         const float ssl = j == 0 ? ssl0 : css[j - 1];
         const float dv = (crr[P][j] - crr[P ^ 1][j]) + (css[j] - ssl);
         prox[j] = fmaf(-gam, dv, xo[j]);
-        if constexpr (RT) dvs = fmaf(dv, dv, dvs);
+        if constexpr (PM) { const float dm = dv * cmx[j]; dvs = fmaf(dm, dm, dvs); }
+        else if constexpr (RT) dvs = fmaf(dv, dv, dvs);
       }
       if constexpr (RT) {
         if (want_obj && o >= 0 && o < H) {
@@ -945,9 +986,15 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
             float tvs = 0.f;
 #pragma unroll
             for (int j = 0; j < PXL; ++j) {
-              const float dx = prox[j] - pprev[j];
-              const float dy = (c0 + j + 1 < W) ? (j == PXL - 1 ? pr_last : pprev[j + 1]) - pprev[j] : 0.f;
-              tvs += __builtin_amdgcn_sqrtf(fmaf(dx, dx, dy * dy));
+              if constexpr (PM) {
+                const float dx = (prox[j] - pprev[j]) * cmx[j];
+                const float dy = ((j == PXL - 1 ? pr_last : pprev[j + 1]) - pprev[j]) * cmy[j];
+                tvs += __builtin_amdgcn_sqrtf(fmaf(dx, dx, dy * dy));
+              } else {
+                const float dx = prox[j] - pprev[j];
+                const float dy = (c0 + j + 1 < W) ? (j == PXL - 1 ? pr_last : pprev[j + 1]) - pprev[j] : 0.f;
+                tvs += __builtin_amdgcn_sqrtf(fmaf(dx, dx, dy * dy));
+              }
             }
             otv += (double)tvs;
           }
@@ -1042,7 +1089,10 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         const float pr_last = dpp_right0(pprev[0]);
         float tvs = 0.f;
 #pragma unroll
-        for (int j = 0; j < PXL; ++j) tvs += (c0 + j + 1 < W) ? fabsf((j == PXL - 1 ? pr_last : pprev[j + 1]) - pprev[j]) : 0.f;
+        for (int j = 0; j < PXL; ++j) {
+          if constexpr (PM) tvs += fabsf((j == PXL - 1 ? pr_last : pprev[j + 1]) - pprev[j]) * cmy[j];
+          else tvs += (c0 + j + 1 < W) ? fabsf((j == PXL - 1 ? pr_last : pprev[j + 1]) - pprev[j]) : 0.f;
+        }
         otv += (double)tvs;
         const double dg = (double)gam;
         const double tot = wave_sum(0.5 * dg * dg * osq + dg * otv);

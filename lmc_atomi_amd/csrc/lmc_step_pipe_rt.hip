@@ -13,29 +13,39 @@ bool pipe_rt_supported(const StepArgs& a) {
   const int n = a.tv.niter;
   if (n < 1 || n > 60 || n > kMaxTvIters) return false;
   if (a.tv_in || a.tv_out || a.tv_state_only || a.tv_warm) return false;
-  if (!pipe_geometry_ok(a)) return false;
-  // one strip (objective sums would count the recomputed halos of column strips twice), the last image column a lane's last pixel
-  if (a.W > 512 || (a.W & (a.W > 256 ? 7 : 3))) return false;
+  // every width the fixed-count K = 10 kernel covers (the launches here are K = 10 pipelines whatever the cap: ask for that geometry)
+  StepArgs g = a;
+  g.tv.niter = 10;
+  if (!pipe_geometry_ok(g)) return false;
   if (a.f_out || a.g_out) return false;
   // chained links: the pure prox only (every link may be the one some chain leaves in, so none could skip a data term)
   if (n > 10 && (a.data_kind != LMC_DATA_NONE || a.noise_mode != LMC_NOISE_NONE || a.ncvx_kind != LMC_NCVX_NONE || a.extra)) return false;
   return true;
 }
 
-template <bool CHAIN>
-static hipError_t pipe_dispatch_rt(const StepArgs& a, int KT, hipStream_t st) {
+// AL as in pipe_dispatch_k (the last image column is a lane's last pixel, rows are 16-byte aligned) -- and one strip: the AL = true kernels sum the
+// objectives over whole rows.  Everything else -- unaligned rows, column strips of any alignment -- runs the AL = false kernels, whose objective sums
+// carry per-pixel weights (the strip's interior, the last image column).
+template <bool CHAIN, bool AL>
+static hipError_t pipe_dispatch_rt_al(const StepArgs& a, int KT, hipStream_t st) {
   if (a.W > 256) {
     if constexpr (!CHAIN) {
-      if (KT == 5) return pipe_launch_one<8, 5, false, 10, false, true, true>(a, st);
-      if (KT == 7) return pipe_launch_one<8, 7, false, 10, false, true, true>(a, st);
+      if (KT == 5) return pipe_launch_one<8, 5, false, 10, false, AL, true>(a, st);
+      if (KT == 7) return pipe_launch_one<8, 7, false, 10, false, AL, true>(a, st);
     }
-    return pipe_launch_one<8, 0, CHAIN, 10, false, true, true>(a, st);
+    return pipe_launch_one<8, 0, CHAIN, 10, false, AL, true>(a, st);
   }
   if constexpr (!CHAIN) {
-    if (KT == 5) return pipe_launch_one<4, 5, false, 10, false, true, true>(a, st);
-    if (KT == 7) return pipe_launch_one<4, 7, false, 10, false, true, true>(a, st);
+    if (KT == 5) return pipe_launch_one<4, 5, false, 10, false, AL, true>(a, st);
+    if (KT == 7) return pipe_launch_one<4, 7, false, 10, false, AL, true>(a, st);
   }
-  return pipe_launch_one<4, 0, CHAIN, 10, false, true, true>(a, st);
+  return pipe_launch_one<4, 0, CHAIN, 10, false, AL, true>(a, st);
+}
+template <bool CHAIN>
+static hipError_t pipe_dispatch_rt(const StepArgs& a, int KT, hipStream_t st) {
+  const bool lastlane = (a.W & (a.W > 256 ? 7 : 3)) == 0;
+  if (lastlane && a.W <= 512) return pipe_dispatch_rt_al<CHAIN, true>(a, KT, st);
+  return pipe_dispatch_rt_al<CHAIN, false>(a, KT, st);
 }
 
 hipError_t launch_step_pipe_rt(StepArgs a, hipStream_t st, float* state0, float* state1) {

@@ -96,7 +96,7 @@ int me_tv_prox(const Problem& q, const float* x, float* extra, int64_t n_img, fl
   }
   if (q.ncvx_rtol > 0.f) {     // the class's own rtol (algs.py:130,169): per-chain early exit
     if (rt && q.tv_exit_path == 0 && lmc::pipe_rt_supported(A)) return tv_prox_rt(A, *rt, q.ncvx_rtol, state0, state1, st);     // on the device
-    // elsewhere (narrow / wide / unaligned images): pass by pass, as the TV prior's prox (synchronises the stream)
+    // elsewhere (images up to 128 columns wide, more than 60 passes, tv_exit_path = 1): pass by pass, as the TV prior's prox (synchronises the stream)
     Problem qt;
     qt.H = q.H; qt.W = q.W;
     qt.prior_kind = LMC_PRIOR_TV_ISO; qt.prior_sigma = 1.f; qt.tv_niter = q.ncvx_niter; qt.tv_step = 0.125f; qt.tv_rtol = q.ncvx_rtol;

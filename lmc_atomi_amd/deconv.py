@@ -35,8 +35,8 @@ def prox_lmc_deconv(gamma_mc=15., gamma_me=15., sigma=0.75, tau=0.3, N=1000, nit
     """Posterior means of the nine models M1..M9 (prox_lmc_deconv.py:447-703) by ULPDA or MYULA on the GPU.
 
     ``rtol``: the early exit of the TV proxes AS THE REFERENCE IS CONFIGURED -- ``pyproximal.TV(dims, sigma, niter=niter_tv)`` leaves upstream's default
-    ``rtol = 1e-4`` in force (:122) and ``algs.L2_ncvx_tv`` has it as its own default (algs.py:130,169).  Decided on the device, chain by chain (DESIGN
-    3.0r); ``rtol=0``: every prox runs all its passes.  (MYMALA: the TV prior keeps the fixed count -- its Metropolis test needs one proposal map.)
+    ``rtol = 1e-4`` in force (:122) and ``algs.L2_ncvx_tv`` has it as its own default (algs.py:130,169).  Decided on the device, chain by chain, on every image wider
+    than 128 columns (narrower ones: pass by pass, with a host read per pass); ``rtol=0``: every prox runs all its passes.  (MYMALA: the TV prior keeps the fixed count -- its Metropolis test needs one proposal map.)
 
     ``n_chains=None`` runs the reference's single chain (every iterate kept on the host, mean over iterates,
     ``:474``); ``n_chains=C`` runs C chains per model and averages over chains and kept iterations.

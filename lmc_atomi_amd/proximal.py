@@ -19,6 +19,27 @@ from . import _capi, _dev
 from .operators import Convolve2D, Diagonal, Identity, LinearOperator
 
 
+_warned_pass_by_pass = False
+
+
+def _exit_lands_on_passes(W, tv_rtol, ncvx_rtol, exit_path):
+    """Whether a problem with an early exit (``TV(rtol > 0)`` / isotropic ``L2_ncvx_tv(rtol > 0)``) that did not ask for the pass-by-pass path
+    gets it all the same: images up to 128 columns wide, which the full-width pipeline (and with it the exit decided on the device) does not cover."""
+    return exit_path == 0 and W <= 128 and (tv_rtol > 0.0 or ncvx_rtol > 0.0)
+
+
+def _warn_pass_by_pass(W):
+    """Once per process: the pass-by-pass early exit synchronises the stream after every pass."""
+    global _warned_pass_by_pass
+    if _warned_pass_by_pass:
+        return
+    _warned_pass_by_pass = True
+    warnings.warn(f"rtol > 0 on an image {W} columns wide: the early exit of the TV prox is decided pass by pass (one launch per pass for the iterate, one "
+                  "for its objective, and a host read that synchronises the stream after every pass); it is decided on the device, without "
+                  "synchronisation, on images wider than 128 columns.  exit_path='passes' asks for this path explicitly (no warning).",
+                  RuntimeWarning, stacklevel=3)
+
+
 def fgp_betas(niter, momentum="unlocbox"):
     """Momentum table beta_k = (t_{k-1}-1)/t_k of the TV dual iteration.  'unlocbox' is the
     sequence pyproximal.TV inherits from UNLocBoX [upstream]; 'fista' the textbook one."""
@@ -107,6 +128,9 @@ class _Problem:
         # ABI 3: early exit of the ME-TV inner prox, which of the two exit paths, launch policy (0 = the library decides)
         p.ncvx_rtol = float(data.get("ncvx_rtol", 0.0) or 0.0)
         p.tv_exit_path = int(prior.get("tv_exit_path", 0) or opt.get("tv_exit_path", 0) or 0)
+        if _exit_lands_on_passes(p.W, p.tv_rtol if p.prior_kind == _capi.PRIOR_TV_ISO else 0.0,
+                                 p.ncvx_rtol if p.ncvx_kind == _capi.NCVX_ME_TV else 0.0, p.tv_exit_path):
+            _warn_pass_by_pass(p.W)
         p.iterations_per_launch = int(opt.get("iterations_per_launch", 0) or 0)
         p.moments_overlap = int(opt.get("moments_overlap", 0) or 0)
         p.moments_bg_workgroups = int(opt.get("moments_bg_workgroups", 0) or 0)
@@ -309,10 +333,12 @@ class TV(ProxOperator):
       reference's call does not override).  Default here: 0 = off, every image runs ``niter`` dual iterations in ONE fused launch (against
       the reference as configured the trajectory differs by 1.5e-4 rel-L2 and the posterior mean by 8e-5).
       ``rtol > 0`` reproduces the reference's configured behaviour -- every image leaves in the pass upstream's loop leaves it in:
-      decided on the device without synchronisation where the full-width pipeline covers the image (128 < W <= 512; every chain runs
-      with the pass count it left in at the previous call, the launch leaves the primal objectives of its iterates behind, chains whose
-      prediction was wrong run again), pass by pass elsewhere (``exit_path='passes'`` forces that path: one launch per loop pass plus
-      one for its objective and a host read after every pass).
+      decided on the device without synchronisation where the full-width pipeline covers the image (every width above 128 columns, rows
+      of any alignment, ``niter <= 60``: every chain runs with the pass count it left in at the previous call, the launch leaves the primal
+      objectives of its iterates behind, chains whose prediction was wrong run again; images wider than 512 columns run as column strips
+      that add their shares of every objective), pass by pass elsewhere -- one launch per loop pass plus one for its objective and a host
+      read after every pass; landing there without having asked for it (``W <= 128``) raises a ``RuntimeWarning`` once per process, and
+      ``exit_path='passes'`` forces that path silently.
     * ``lagged_output``: whether upstream's truncated iterate after ``niter`` loop passes reflects ``niter`` or ``niter - 1`` dual
       updates depends on the loop bound of the un-pinned upstream version; ``False`` (default) = ``niter`` updates,
       ``True`` = ``niter - 1`` (one pipeline stage fewer).
