@@ -57,7 +57,14 @@ typedef enum lmc_prior_kind {
   LMC_PRIOR_L1 = 2,     /* g = sigma ||x||_1        : soft threshold t*sigma  (prox.py:18) */
   LMC_PRIOR_TV_ISO = 3, /* g = sigma TV_iso(x)      : tv_niter FGP dual iterations (pyproximal.TV, prox_lmc_deconv.py:122);
                          *  in ULPDA: g o A with g = sigma*L21 (prox_lmc_deconv.py:116), dual prox = l2-ball projection */
-  LMC_PRIOR_TV_ANISO = 4, /* ULPDA / energies only: g o A with g = sigma*L1 (prox_lmc_deconv.py:119), dual prox = clip */
+  LMC_PRIOR_TV_ANISO = 4, /* g = sigma (||d_r x||_1 + ||d_c x||_1), the anisotropic TV (build-specified: pyproximal.TV has no such form).
+                           *  MYULA, MYMALA, lmc_fused_eval: prox by tv_niter FGP dual iterations with the dual clipped to [-1, 1] per component
+                           *  (tv_step, tv_betas_host, tv_lagged_output as for LMC_PRIOR_TV_ISO); tv_niter in 1..LMC_MAX_TV_ITERS, else
+                           *  LMC_E_INVALID; tv_rtol > 0, tv_warm and prox_scale: LMC_E_UNSUPPORTED (no early exit, no warm dual for it).  Kernels:
+                           *  the full-width pipeline for tv_niter in {10, 20, ... 60} on images wider than 128 columns (any alignment; column
+                           *  strips above 512), the LDS-tiled kernel elsewhere.  lmc_energies: g as above.
+                           *  In ULPDA: g o A with g = sigma*L1 (prox_lmc_deconv.py:119), dual prox = clip; tv_niter may stay 0 there and
+                           *  for lmc_energies. */
   LMC_PRIOR_HAAR_L1 = 5, /* g = sigma * || detail coefficients of the 3-level orthonormal Haar transform of x ||_1 (BASELINE
                           * config 5; no counterpart in the reference): prox = W^T soft(W x, t*sigma); H, W multiples of 8 */
   LMC_PRIOR_EPROX = 6    /* (ABI 3) a separable prior whose prox is one of the closed forms of prox.py (lmc_eprox_kind below; prox.py:18-85, used
@@ -398,7 +405,9 @@ float lmc_set_cg_tolerance(float tol);
  * warm-dual 1, 2, 3 -- need W % 4 == 0 up to 256 columns and W % 8 == 0 above), in its one-team layout (8 waves of up to 8 pixels per lane),
  * 8 = the same pipeline in its two-team layout (16 waves of 4 pixels per lane, each team on half the width; one launch of 10 dual iterations,
  * 5 x 5 blur, 264 <= W <= 512 with W % 8 == 0, no energy by-products or non-convex term; other configurations: LMC_E_UNSUPPORTED; bit-identical
- * to 7).  Auto picks the two-team layout where it covers the configuration (the headline one) and the one-team layout elsewhere.  The value 8
+ * to 7).  Auto picks the two-team layout where it covers the configuration (the headline one) and the one-team layout elsewhere.
+ * LMC_PRIOR_TV_ANISO has forms of 1, 7 (tv_niter in {10, 20, ... 60}, W > 128) and 8 (the configurations named above) only, auto picks among
+ * them; every other value returns LMC_E_UNSUPPORTED from the call that would launch it.  The value 8
  * is accepted since this ABI revision (additive).  Returns the previous setting (>= 0) or a negative lmc_status.  All variants compute the same update; the
  * switch exists for A/B tests and profiles. */
 int lmc_set_step_variant(int32_t variant);

@@ -131,6 +131,8 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
   if (!x_dev || !out_dev || x_dev == out_dev) return fail(LMC_E_INVALID, "bad pointers (in-place not allowed)");
   if (n_img < 1 || n_img > (1 << 24)) return fail(LMC_E_INVALID, "bad n_img %lld", (long long)n_img);
   if (q.prox_scale) return fail(LMC_E_UNSUPPORTED, "prox_scale (array-valued epsg) belongs to the MYULA sampler");
+  rc = check_prox_prior(q, b);
+  if (rc) return rc;
   lmc::StepArgs A;
   rc = make_step_args(q, a, t, b, pt, 0.f, A);
   if (rc) return rc;

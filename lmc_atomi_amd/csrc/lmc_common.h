@@ -44,8 +44,11 @@ struct StepArgs {
   const float* noise;        // [C][H][W] of this iteration (injected)
   uint32_t key0, key1;       // Philox key = seed
   uint32_t iteration;        // Philox counter word 1
-  uint64_t unused;           // holds the argument layout of every step kernel (dropping the slot moves the fields behind it, and with them the
-                             // register allocation and spills of some 180 kernels)
+  // host side only (no kernel reads it; the anisotropic kernels are instantiations of their own): prior_kind == LMC_PRIOR_TV_ISO with the box
+  // projection of the dual, p = clip(r, -1, 1) per component, instead of the pixel-norm ball -- the prox of sigma (|d_r x|_1 + |d_c x|_1)
+  alignas(8) uint32_t tv_aniso;
+  uint32_t unused;           // the two hold the argument layout of every step kernel (an 8-byte slot: dropping it moves the fields behind it, and with
+                             // them the register allocation and spills of some 180 kernels)
   uint32_t chain_offset;     // global id of chain 0 (counter word 2 = chain_offset + c)
   const float* x_in;
   float* x_out;

@@ -42,6 +42,8 @@ struct Problem {
   int ncvx_niter = 0;
   int ncvx_aniso = 0;       // ME-TV: the 1-D TV of the flattened image (LMC_NCVX_ME_TV_ANISO)
   int tv_warm = 0;
+  int tv_warm_asked = 0;    // lmc_problem.tv_warm as given (tv_warm: where the prior has a warm dual)
+  int tv_niter_asked = 0;   // lmc_problem.tv_niter as given (tv_niter: after tv_lagged_output)
   float tv_rtol = 0.f;      // > 0: pyproximal.TV's per-image early exit (device path tv_prox_rt, or the pass-by-pass path tv_prox_rtol)
   float ncvx_rtol = 0.f;    // > 0: the same for the inner prox of the ME-TV term (device path only)
   int tv_exit_path = 0;     // 1: always pass by pass
@@ -139,6 +141,7 @@ constexpr int kSideBatches = 4;
 int fill_taps(lmc::BlurTaps& T, const float* h, int kh, int kw, int oy, int ox);
 void default_betas(float* b, int n);
 int load_problem(const lmc_problem* p, Problem& q);
+int check_prox_prior(const Problem& q, float b);
 int make_step_args(const Problem& q, float a, float t, float b, float pt, float s, lmc::StepArgs& A);
 void sanitize_pointers(lmc::StepArgs& A);
 int variant_of(const Problem& q);

@@ -58,7 +58,7 @@ int load_problem(const lmc_problem* p, Problem& q) {
   q.prior_kind = p->prior_kind;
   q.prior_sigma = p->prior_sigma;
   switch (p->prior_kind) {
-    case LMC_PRIOR_NONE: case LMC_PRIOR_L2: case LMC_PRIOR_L1: case LMC_PRIOR_TV_ANISO: break;
+    case LMC_PRIOR_NONE: case LMC_PRIOR_L2: case LMC_PRIOR_L1: break;
     case LMC_PRIOR_EPROX:
       if (p->eprox_kind < 0 || p->eprox_kind > LMC_EPROX_LAPLACE_CONJ) return fail(LMC_E_INVALID, "unknown eprox_kind %d", p->eprox_kind);
       if (p->eprox_scale_mask < 0 || p->eprox_scale_mask > 3) return fail(LMC_E_INVALID, "eprox_scale_mask must be 0..3");
@@ -68,11 +68,16 @@ int load_problem(const lmc_problem* p, Problem& q) {
     case LMC_PRIOR_HAAR_L1:
       if ((p->H & 7) || (p->W & 7)) return fail(LMC_E_UNSUPPORTED, "the Haar-l1 prior needs H and W to be multiples of 8 (got %dx%d)", p->H, p->W);
       break;
+    case LMC_PRIOR_TV_ANISO:
+      // tv_niter = 0: the callers that never form the prox (ULPDA, lmc_energies); the entry points that do refuse it (check_prox_prior)
+      if (p->tv_niter == 0) break;
+      [[fallthrough]];
     case LMC_PRIOR_TV_ISO:
       if (p->tv_niter < 1 || p->tv_niter > lmc::kMaxTvIters)
         return fail(LMC_E_UNSUPPORTED, "tv_niter %d outside 1..%d", p->tv_niter, lmc::kMaxTvIters);
       if (!(p->tv_rtol >= 0.f) || p->tv_rtol >= 1.f) return fail(LMC_E_INVALID, "tv_rtol must be in [0, 1)");
       q.tv_rtol = p->tv_rtol;
+      q.tv_niter_asked = p->tv_niter;
       q.tv_niter = p->tv_niter - (p->tv_lagged_output ? 1 : 0);     // lagged: the iterate after tv_niter - 1 dual updates (0: prox = x)
       q.tv_step = p->tv_step > 0.f ? p->tv_step : 0.125f;
       if (p->tv_betas_host) std::memcpy(q.betas, p->tv_betas_host, sizeof(float) * p->tv_niter);
@@ -123,8 +128,20 @@ int load_problem(const lmc_problem* p, Problem& q) {
     q.prox_scale = p->prox_scale; q.prox_scale_cs = p->prox_scale_chain_stride; q.prox_scale_ps = p->prox_scale_pixel_stride;
   }
   q.tv_warm = (p->tv_warm != 0 && p->prior_kind == LMC_PRIOR_TV_ISO) ? 1 : 0;
+  q.tv_warm_asked = p->tv_warm != 0;
   if (!(p->implicit_tol == p->implicit_tol)) return fail(LMC_E_INVALID, "implicit_tol is NaN");
   q.implicit_tol = p->implicit_tol;
+  return LMC_OK;
+}
+
+// What the entry points that form prox_g (MYULA, MYMALA, lmc_fused_eval) ask of the anisotropic TV prior beyond load_problem: an iteration
+// count, and none of the options that are built for the isotropic prior only.
+int check_prox_prior(const Problem& q, float b) {
+  if (q.prior_kind != LMC_PRIOR_TV_ANISO) return LMC_OK;
+  if (q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "tv_rtol > 0 (early exit of the prox) is not built for LMC_PRIOR_TV_ANISO: use the fixed-count prox, tv_rtol = 0");
+  if (q.tv_warm_asked) return fail(LMC_E_UNSUPPORTED, "tv_warm (warm-started dual) is not built for LMC_PRIOR_TV_ANISO");
+  if (b != 0.f && q.tv_niter_asked < 1)
+    return fail(LMC_E_INVALID, "LMC_PRIOR_TV_ANISO: the prox needs tv_niter in 1..%d (got 0)", lmc::kMaxTvIters);
   return LMC_OK;
 }
 
@@ -137,7 +154,10 @@ int make_step_args(const Problem& q, float a, float t, float b, float pt, float 
   A.y = q.y; A.mask = q.mask;
   A.blur = q.taps;
   A.prior_kind = (b == 0.f) ? LMC_PRIOR_NONE : q.prior_kind;
-  if (A.prior_kind == LMC_PRIOR_TV_ISO && q.tv_niter == 0) A.prior_kind = LMC_PRIOR_NONE;   // lagged output of a 1-iteration prox: x itself
+  // the anisotropic TV prior: inside the library the TV kind plus a flag (every dispatch test on LMC_PRIOR_TV_ISO serves both; the kernels that
+  // have no anisotropic form say "not covered" when the flag is set).  Problem::prior_kind stays as given (ULPDA, the energies).
+  if (A.prior_kind == LMC_PRIOR_TV_ANISO) { A.prior_kind = LMC_PRIOR_TV_ISO; A.tv_aniso = 1; }
+  if (A.prior_kind == LMC_PRIOR_TV_ISO && q.tv_niter == 0) { A.prior_kind = LMC_PRIOR_NONE; A.tv_aniso = 0; }   // lagged output of a 1-iteration prox: x itself
   if (A.prior_kind == LMC_PRIOR_HAAR_L1) A.prior_p0 = pt * q.prior_sigma;  // soft threshold of the detail coefficients
   if (A.prior_kind == LMC_PRIOR_L2) A.prior_p0 = 1.f / (1.f + pt * q.prior_sigma);
   if (A.prior_kind == LMC_PRIOR_L1) A.prior_p0 = pt * q.prior_sigma;
@@ -219,7 +239,7 @@ hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, c
   if (v == 0 || v == 7 || v == 8) {
     const int links = lmc::pipe_links(A);
     if (links == 1 || (links > 1 && state0 && state1 && v != 8)) {
-      if (name) *name = "myula_step_pipe_kernel";
+      if (name) *name = A.tv_aniso ? "myula_step_pipe_aniso_kernel" : "myula_step_pipe_kernel";
       return lmc::launch_step_pipe(A, st, state0, state1, v == 7 ? 1 : v == 8 ? 2 : 0);
     }
   }

@@ -57,6 +57,8 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   if (!s) return fail(LMC_E_NOMEM, "host allocation failed");
   rc = load_problem(&cfg->problem, s->prob);
   if (rc) { delete s; return rc; }
+  rc = check_prox_prior(s->prob, cfg->tau / cfg->gamma);
+  if (rc) { delete s; return rc; }
   if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }
   s->C = cfg->n_chains;
   s->chain_offset = cfg->chain_offset;

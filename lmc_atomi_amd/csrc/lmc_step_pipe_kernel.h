@@ -92,6 +92,8 @@ __device__ __forceinline__ void prow_store(float* row, int lane, const float (&v
 typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ v2f pk_set(float a) { return v2f{a, a}; }
+// projection onto [-1, 1] per component (the dual ball of the anisotropic TV prior)
+__device__ __forceinline__ v2f pipe_clamp1(v2f a) { return v2f{__builtin_amdgcn_fmed3f(a.x, -1.f, 1.f), __builtin_amdgcn_fmed3f(a.y, -1.f, 1.f)}; }
 
 template <int NP>   // NP = PXL / 2 pairs
 __device__ __forceinline__ void pairs_load(v2f (&v)[NP], const float* row, int lane) {
@@ -164,7 +166,9 @@ __device__ __forceinline__ v2f obj_tv(const ObjMask<NP, !LASTLANE>* om, int i, v
 }
 
 // SEAML / SEAMR (two-team layout): lane 0's left neighbour of s1 / lane 63's right neighbour of solb is the other team's, `ssl_edge` / `solr_edge`.
-template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAML = false, bool SEAMR = false>
+// ANISO: the anisotropic prior sigma (|d_r x|_1 + |d_c x|_1): the dual is projected onto the l-infinity unit ball, one clamp per component
+// (v_med3_f32), instead of the pixel-norm ball; everything else in the stage is shared.
+template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAML = false, bool SEAMR = false, bool ANISO = false>
 __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[NP], const v2f (&s1)[NP], const DualRow<NP>& in0,
                                            v2f (&solb)[NP], float gam, float cdown, const PipeCr<NP>& cr, float beta,
                                            DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP, !LASTLANE>* om = nullptr,
@@ -191,11 +195,17 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
     }
     const v2f r = pk_fma(ncd, dxv, in0.rr[i]);
     const v2f s = pk_fma(ncr, dyv, in0.ss[i]);
-    const v2f n2 = pk_fma(r, r, s * s);
-    // min(1, rsq(n2)) == rsq(max(n2, 1)) bit for bit (rsq is monotone, rsq(1) = 1); written as a [0,1] clamp it folds into the
-    // output modifier of v_rsq_f32 and the v_max disappears
-    const v2f inv = v2f{__builtin_amdgcn_fmed3f(__builtin_amdgcn_rsqf(n2.x), 0.f, 1.f), __builtin_amdgcn_fmed3f(__builtin_amdgcn_rsqf(n2.y), 0.f, 1.f)};
-    const v2f pn = r * inv, qn = s * inv;
+    v2f pn, qn;
+    if constexpr (ANISO) {
+      pn = pipe_clamp1(r);
+      qn = pipe_clamp1(s);
+    } else {
+      const v2f n2 = pk_fma(r, r, s * s);
+      // min(1, rsq(n2)) == rsq(max(n2, 1)) bit for bit (rsq is monotone, rsq(1) = 1); written as a [0,1] clamp it folds into the
+      // output modifier of v_rsq_f32 and the v_max disappears
+      const v2f inv = v2f{__builtin_amdgcn_fmed3f(__builtin_amdgcn_rsqf(n2.x), 0.f, 1.f), __builtin_amdgcn_fmed3f(__builtin_amdgcn_rsqf(n2.y), 0.f, 1.f)};
+      pn = r * inv; qn = s * inv;
+    }
     out.rr[i] = pk_fma(vb, pn - in0.p[i], pn);
     out.ss[i] = pk_fma(vb, qn - in0.q[i], qn);
     out.p[i] = pn;
@@ -207,7 +217,7 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
 
 // Stage 1 of a launch that starts from the zero dual state: (rr, ss, p, q)^0 = 0, so sol^1 = x and the differences with the previous
 // iterate vanish.  Bit-identical to pipe_stage() fed with zeros (x - 0 = x, fma(c, d, 0) = c*d), at ~60 % of its instructions.
-template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAMR = false>
+template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAMR = false, bool ANISO = false>
 __device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb)[NP], float cdown, const PipeCr<NP>& cr, float beta,
                                                  DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP, !LASTLANE>* om = nullptr,
                                                  float solr_edge = 0.f) {
@@ -225,9 +235,15 @@ __device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb
     }
     const v2f r = ncd * dxv;
     const v2f s = ncr * dyv;
-    const v2f n2 = pk_fma(r, r, s * s);
-    const v2f inv = v2f{__builtin_amdgcn_fmed3f(__builtin_amdgcn_rsqf(n2.x), 0.f, 1.f), __builtin_amdgcn_fmed3f(__builtin_amdgcn_rsqf(n2.y), 0.f, 1.f)};
-    const v2f pn = r * inv, qn = s * inv;
+    v2f pn, qn;
+    if constexpr (ANISO) {
+      pn = pipe_clamp1(r);
+      qn = pipe_clamp1(s);
+    } else {
+      const v2f n2 = pk_fma(r, r, s * s);
+      const v2f inv = v2f{__builtin_amdgcn_fmed3f(__builtin_amdgcn_rsqf(n2.x), 0.f, 1.f), __builtin_amdgcn_fmed3f(__builtin_amdgcn_rsqf(n2.y), 0.f, 1.f)};
+      pn = r * inv; qn = s * inv;
+    }
     out.rr[i] = pk_fma(vb, pn, pn);
     out.ss[i] = pk_fma(vb, qn, qn);
     out.p[i] = pn;
@@ -333,9 +349,15 @@ __host__ __device__ constexpr int pipe_halo(int K, int KT, int PXL) {
 // two-stage T waves beside L + C of one team, or beside N + T1 of one team, on each SIMD
 #define LMC_PIPE2_ROLES 0x5D3BC4A291E6F780ull
 #endif
-template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS>
+// ANISO (myula_step_pipe_aniso_kernel, lmc_step_pipe_aniso.hip): the stages project the dual onto the box (pipe_stage); fixed count, cold start.
+template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS, bool ANISO = false>
 __device__ __forceinline__ void pipe_body(const StepArgs& A) {
   static_assert(!WARM || CHAIN, "the warm dual uses the state hand-over of the chained launches");
+  static_assert(!ANISO || (!WARM && !RT), "anisotropic prior: the early exit's objective and the warm dual are not built");
+  // Anisotropic prior, the link of a chain that carries the blur (the last one) at 8 pixels per lane: the N wave, not L, hands the dual state of the
+  // previous link to stage 1.  With the state rows' prefetch registers beside the blur windows the L wave needs more than 256 VGPRs (the isotropic
+  // twins of these four kernels spill 20 to 90 of them); the N wave has them to spare and issues no other global access.
+  constexpr bool kStateInN = ANISO && CHAIN && KT > 0 && PXL == 8;
   static_assert(!RT || (!WARM && (K & 1) == 0), "per-chain exit: cold start, even K");
   // RT with AL = false: any width, column strips included.  The objective of an iterate reads it one column beyond the strip's interior, which needs
   // the dual one column further out than the update itself does (K + 1)
@@ -514,7 +536,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     constexpr int kSPF = 2;
     float spre[CHAIN ? kSPF : 1][CHAIN ? nsf : 1][CHAIN ? PXL : 1];
     const float* const sin = CHAIN && A.tv_in ? A.tv_in + (size_t)chain * nsf * img : nullptr;
-    if constexpr (CHAIN) {
+    if constexpr (CHAIN && !kStateInN) {
 #pragma unroll
       for (int u = 0; u < kSPF; ++u) {
         const int rs = u - E - 1;
@@ -545,7 +567,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         prow_store<PXL>(ring_row(t), lane, xv);
         gload_raw<PXL>(xpre[U], xin + (size_t)min(t + kXPF, H - 1) * W, cl, W, al);
       }
-      if constexpr (CHAIN) {   // dual state row t - E - 1 of the previous link -> stage 1's hand-off slot P (read next tick)
+      if constexpr (CHAIN && !kStateInN) {   // dual state row t - E - 1 of the previous link -> stage 1's hand-off slot P (read next tick)
         float* hb = lds + L::o_hand0 + P * 4 * RP;
         constexpr int SP = U & (kSPF - 1);
         const int rh = t - E - 1;                                  // the row fetched kSPF ticks ago
@@ -792,7 +814,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         if (live2) {
           StageObj ob;
           om.md = cdown != 0.f ? 1.f : 0.f;
-          pipe_stage<NP, AL, RT, SL, SRt>(xk[P], o1[P ^ 1].rr, o1[P ^ 1].ss, o1[P], sol2, gam, cdown, crc, beta2, out, &ob, &om, edge.y, edge.y);
+          pipe_stage<NP, AL, RT, SL, SRt, ANISO>(xk[P], o1[P ^ 1].rr, o1[P ^ 1].ss, o1[P], sol2, gam, cdown, crc, beta2, out, &ob, &om, edge.y, edge.y);
           if constexpr (RT) { osq2 += (double)(ob.sq.x + ob.sq.y); otv2 += (double)(ob.tv.x + ob.tv.y); }
         } else {                 // pass-through: the state of row a2 - 1 as stage k1 left it
 #pragma unroll
@@ -825,8 +847,8 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           const float cdown = ((unsigned)(a1 - 1) >= (unsigned)(H - 1)) ? 0.f : cstep;
           StageObj ob;
           om.md = cdown != 0.f ? 1.f : 0.f;
-          if constexpr (FIRST) pipe_stage_first<NP, AL, RT, SRt>(xk[P], sol1, cdown, crc, beta1, o1[P], &ob, &om, edge.x);
-          else pipe_stage<NP, AL, RT, SL, SRt>(xk[P], inb[P].rr, inb[P].ss, inb[P ^ 1], sol1, gam, cdown, crc, beta1, o1[P], &ob, &om, edge.x, edge.x);
+          if constexpr (FIRST) pipe_stage_first<NP, AL, RT, SRt, ANISO>(xk[P], sol1, cdown, crc, beta1, o1[P], &ob, &om, edge.x);
+          else pipe_stage<NP, AL, RT, SL, SRt, ANISO>(xk[P], inb[P].rr, inb[P].ss, inb[P ^ 1], sol1, gam, cdown, crc, beta1, o1[P], &ob, &om, edge.x, edge.x);
           if constexpr (RT) { osq1 += (double)(ob.sq.x + ob.sq.y); otv1 += (double)(ob.tv.x + ob.tv.y); }
         } else {                 // pass-through: the state of row a1 - 1, read one tick ago
 #pragma unroll
@@ -878,10 +900,41 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     // (spread evenly over the ticks: a burst every 4th tick would stall every wave at the barrier).
     float* const slab = slab_base + lane;              // normal (row q of the quad, pixel k) at slab[(q*PXL + k)*64]
     const uint32_t iter = A.iteration;
+    // kStateInN: the state hand-over of the L wave, here (four fields per pixel, rows fetched kSPF = 2 ticks ahead; row t - E - 1 is published at tick t)
+    constexpr int nsf = 4, kSPF = 2;
+    float spre[kStateInN ? kSPF : 1][kStateInN ? nsf : 1][kStateInN ? PXL : 1];
+    const float* const sin = kStateInN && A.tv_in ? A.tv_in + (size_t)chain * nsf * img : nullptr;
+    if constexpr (kStateInN) {
+#pragma unroll
+      for (int u = 0; u < kSPF; ++u) {
+        const int rs = u - E - 1;
+#pragma unroll
+        for (int f = 0; f < nsf; ++f)      // raw: masked where the row is handed over
+          gload_raw<PXL>(spre[u][f], sin ? sin + (size_t)f * img + (size_t)min(max(rs, 0), H - 1) * W : xin, c0, W, al);
+      }
+    }
     auto tick = [&](auto uu, const int t) __attribute__((always_inline)) {
       constexpr int U = decltype(uu)::value;
       constexpr int NI = ((U - D) % 4 + 4) % 4;        // == o & 3  (t = 4m + U)
       const int o = t - D;
+      if constexpr (kStateInN) {   // dual state row t - E - 1 of the previous link -> stage 1's hand-off slot P (read next tick)
+        constexpr int P = U & 1, SP = U & (kSPF - 1);
+        float* hb = lds + L::o_hand0 + P * 4 * RP;
+        const int rh = t - E - 1;                                  // the row fetched kSPF ticks ago
+        const bool rowok_h = sin && rh >= 0 && rh < H;
+#pragma unroll
+        for (int f = 0; f < nsf; ++f) {
+          gfix_raw<PXL, AL>(spre[SP][f], c0, W);
+          float sv[PXL];
+#pragma unroll
+          for (int k = 0; k < PXL; ++k) sv[k] = (rowok_h && c0 + (AL ? (k & ~3) : k) < W) ? spre[SP][f][k] : 0.f;
+          prow_store<PXL>(hb + f * RP, lane, sv);
+        }
+        const int rs = t + kSPF - E - 1;
+#pragma unroll
+        for (int f = 0; f < nsf; ++f)
+          gload_raw<PXL>(spre[SP][f], sin ? sin + (size_t)f * img + (size_t)min(max(rs, 0), H - 1) * W : xin, c0, W, al);
+      }
       if (A.noise_mode == LMC_NOISE_PHILOX && !state_only) {
         const int qn = ((o - NI) >> 2) + 1;             // quad row-group being prepared (o - NI is a multiple of 4)
         if (qn >= 0 && 4 * qn < H) {
@@ -1209,5 +1262,9 @@ int pipe_taps(StepArgs& a);
 // lmc_step_pipe_chain.hip: the CHAIN instantiations (dual state in / out through HBM): links of a chained launch (K = 9, 10) and the
 // warm-started prox (a.tv_warm: K = 1, 2, 3)
 hipError_t pipe_dispatch_chain(const StepArgs& a, int K, int KT, hipStream_t st);
+
+// lmc_step_pipe_aniso.hip: the anisotropic-prior instantiations (myula_step_pipe_aniso_kernel: K = 10, one launch or a link of a chain; the
+// two-team layout, teams = 2, covers what pipe_teams_covered names)
+hipError_t pipe_dispatch_aniso(const StepArgs& a, int KT, bool chain, int teams, hipStream_t st);
 
 }  // namespace lmc

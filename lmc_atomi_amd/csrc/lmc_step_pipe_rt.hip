@@ -9,7 +9,7 @@
 namespace lmc {
 
 bool pipe_rt_supported(const StepArgs& a) {
-  if (a.prior_kind != LMC_PRIOR_TV_ISO) return false;
+  if (a.prior_kind != LMC_PRIOR_TV_ISO || a.tv_aniso) return false;     // (the objective of the anisotropic prior is not built)
   const int n = a.tv.niter;
   if (n < 1 || n > 60 || n > kMaxTvIters) return false;
   if (a.tv_in || a.tv_out || a.tv_state_only || a.tv_warm) return false;

@@ -534,7 +534,7 @@ static int split_k(const StepArgs& a) { return a.prior_kind == LMC_PRIOR_TV_ISO 
 
 bool split_supported(const StepArgs& a) {
   const int NW = split_nw(a.W);
-  if (NW == 0 || a.H < 1) return false;
+  if (NW == 0 || a.H < 1 || a.tv_aniso) return false;      // (no anisotropic form of this kernel)
   bool fits = false;
   switch (split_k(a)) {
 #ifndef LMC_ONLY_K10

@@ -15,8 +15,10 @@ constexpr int kStepThreads = 1024;
 // LDS image: (PH + 2) rows of PW floats; row -1 and row PH are pad rows so that the +-1 neighbour
 // reads of tile-border pixels stay inside the allocation (their values never reach the interior:
 // information moves one pixel per dual iteration and the halo is >= niter).
-template <int NP, bool TV>
+// ANISO (with TV): the anisotropic TV prior -- the dual is projected onto the l-infinity unit ball (a clamp per component).
+template <int NP, bool TV, bool ANISO = false>
 __global__ __launch_bounds__(kStepThreads) void myula_step_tile_kernel(const StepArgs P) {
+  static_assert(TV || !ANISO, "the anisotropic projection belongs to the TV prox");
   extern __shared__ float lds[];
   const int tid = threadIdx.x;
   const int logical = xcd_logical_block(blockIdx.x, gridDim.x);
@@ -149,8 +151,14 @@ __global__ __launch_bounds__(kStepThreads) void myula_step_tile_kernel(const Ste
           const float dy = (flags[m] & 4) ? S[p + 1] - solv[m] : 0.f;
           const float r = fmaf(-cstep, dx, rrv[m]);
           const float s = fmaf(-cstep, dy, ssv[m]);
-          const float inv = rsqrtf(fmaxf(fmaf(r, r, s * s), 1.f));
-          const float pn = r * inv, qn = s * inv;
+          float pn, qn;
+          if constexpr (ANISO) {
+            pn = __builtin_amdgcn_fmed3f(r, -1.f, 1.f);
+            qn = __builtin_amdgcn_fmed3f(s, -1.f, 1.f);
+          } else {
+            const float inv = rsqrtf(fmaxf(fmaf(r, r, s * s), 1.f));
+            pn = r * inv; qn = s * inv;
+          }
           rrv[m] = fmaf(beta, pn - pv[m], pn);
           ssv[m] = fmaf(beta, qn - qv[m], qn);
           pv[m] = pn;
@@ -250,9 +258,9 @@ static bool plan_tiles(int H, int W, int halo, bool tv, size_t lds_limit, TilePl
   return false;
 }
 
-template <int NP, bool TV>
+template <int NP, bool TV, bool ANISO>
 static hipError_t launch_np(const StepArgs& a, size_t lds, hipStream_t st) {
-  auto k = myula_step_tile_kernel<NP, TV>;
+  auto k = myula_step_tile_kernel<NP, TV, ANISO>;
   static thread_local size_t configured = 0;
   if (lds > configured) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
@@ -265,17 +273,17 @@ static hipError_t launch_np(const StepArgs& a, size_t lds, hipStream_t st) {
   return hipGetLastError();
 }
 
-template <bool TV>
+template <bool TV, bool ANISO = false>
 static hipError_t launch_tv(const StepArgs& a, int NP, size_t lds, hipStream_t st) {
   switch (NP) {
-    case 1: return launch_np<1, TV>(a, lds, st);
-    case 2: return launch_np<2, TV>(a, lds, st);
-    case 3: return launch_np<3, TV>(a, lds, st);
-    case 4: return launch_np<4, TV>(a, lds, st);
-    case 5: return launch_np<5, TV>(a, lds, st);
-    case 6: return launch_np<6, TV>(a, lds, st);
-    case 7: return launch_np<7, TV>(a, lds, st);
-    case 8: return launch_np<8, TV>(a, lds, st);
+    case 1: return launch_np<1, TV, ANISO>(a, lds, st);
+    case 2: return launch_np<2, TV, ANISO>(a, lds, st);
+    case 3: return launch_np<3, TV, ANISO>(a, lds, st);
+    case 4: return launch_np<4, TV, ANISO>(a, lds, st);
+    case 5: return launch_np<5, TV, ANISO>(a, lds, st);
+    case 6: return launch_np<6, TV, ANISO>(a, lds, st);
+    case 7: return launch_np<7, TV, ANISO>(a, lds, st);
+    case 8: return launch_np<8, TV, ANISO>(a, lds, st);
   }
   return hipErrorInvalidValue;
 }
@@ -297,6 +305,7 @@ hipError_t launch_step_tile(StepArgs a, hipStream_t st) {
   a.TH = tp.TH; a.TW = tp.TW; a.HL = tp.HL; a.PH = tp.PH; a.PW = tp.PW;
   a.tiles_x = (a.W + tp.TW - 1) / tp.TW;
   a.tiles_y = (a.H + tp.TH - 1) / tp.TH;
+  if (tv && a.tv_aniso) return launch_tv<true, true>(a, tp.NP, tp.lds_bytes, st);
   return tv ? launch_tv<true>(a, tp.NP, tp.lds_bytes, st) : launch_tv<false>(a, tp.NP, tp.lds_bytes, st);
 }
 

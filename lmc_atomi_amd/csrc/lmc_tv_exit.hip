@@ -7,7 +7,7 @@
 namespace lmc::host {
 
 bool needs_tv_state(const Problem& q) {
-  return (q.prior_kind == LMC_PRIOR_TV_ISO && (q.tv_niter > 12 || (q.tv_rtol > 0.f && q.tv_niter > 10))) ||
+  return ((q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO) && (q.tv_niter > 12 || (q.tv_rtol > 0.f && q.tv_niter > 10))) ||
          (q.ncvx_kind == LMC_NCVX_ME_TV && (q.ncvx_aniso || q.ncvx_niter > 12 || (q.ncvx_rtol > 0.f && q.ncvx_niter > 10)));
 }
 

@@ -105,7 +105,8 @@ class _Problem:
             p.h_host = _dev.fptr(h)
         p.prior_kind = prior["prior_kind"]
         p.prior_sigma = float(prior.get("prior_sigma", 0.0))
-        if p.prior_kind == _capi.PRIOR_TV_ISO:
+        # (ULPDA's anisotropic descriptor carries no prox: tv_niter stays 0)
+        if p.prior_kind == _capi.PRIOR_TV_ISO or (p.prior_kind == _capi.PRIOR_TV_ANISO and prior.get("tv_niter") is not None):
             p.tv_niter = int(prior["tv_niter"])
             p.tv_step = float(prior.get("tv_step", 0.125))
             b = np.ascontiguousarray(prior["tv_betas"], dtype=np.float32)
@@ -327,6 +328,10 @@ class TV(ProxOperator):
     (prox_lmc_deconv.py:122).  ``prox`` runs ``niter`` fast-gradient-projection dual iterations fully
     on chip.
 
+    ``isotropic=False`` (build extension; pyproximal's ``TV`` has no anisotropic form): ``sigma * (||d_r x||_1 + ||d_c x||_1)``, the same
+    dual iteration with the dual clipped to [-1, 1] per component instead of projected onto the pixel-norm ball.  Fixed count only:
+    ``rtol > 0`` and ``warm=True`` raise ``NotImplementedError``.
+
     Deviations from upstream, both named in DESIGN section 4:
 
     * ``rtol``: pyproximal's per-image early exit on the relative change of the primal objective (its default 1e-4, which the
@@ -345,8 +350,14 @@ class TV(ProxOperator):
     * ``warm`` (build extension, MYULA samplers only): carry the projected dual from one MYULA iteration to the next, ``niter``
       in {1, 2, 3} updates per MYULA iteration ("K in {1,3} warm-dual")."""
 
-    def __init__(self, dims, sigma=1.0, niter=10, rtol=0.0, step=0.125, momentum="unlocbox", lagged_output=False, warm=False, exit_path="auto"):
+    def __init__(self, dims, sigma=1.0, niter=10, rtol=0.0, step=0.125, momentum="unlocbox", lagged_output=False, warm=False, exit_path="auto",
+                 isotropic=True):
         super().__init__(None, False)
+        self.isotropic = bool(isotropic)
+        if not self.isotropic and float(rtol) > 0.0:
+            raise NotImplementedError("TV(isotropic=False) has no early exit: rtol must be 0 (every image runs niter dual iterations)")
+        if not self.isotropic and warm:
+            raise NotImplementedError("TV(isotropic=False) has no warm-started dual: warm must be False")
         self.dims = (int(dims[0]), int(dims[1]))
         self.sigma = float(sigma)
         self.niter = int(niter)
@@ -359,7 +370,7 @@ class TV(ProxOperator):
         self._prob = None
 
     def prior_descriptor(self):
-        return {"prior_kind": _capi.PRIOR_TV_ISO, "prior_sigma": self.sigma, "tv_niter": self.niter,
+        return {"prior_kind": _capi.PRIOR_TV_ISO if self.isotropic else _capi.PRIOR_TV_ANISO, "prior_sigma": self.sigma, "tv_niter": self.niter,
                 "tv_step": self.step, "tv_betas": fgp_betas(self.niter, self.momentum),
                 "tv_lagged_output": self.lagged_output, "tv_warm": self.warm, "tv_rtol": self.rtol, "tv_exit_path": self.exit_path}
 
