@@ -807,20 +807,28 @@ static dim3 tv1d_grid(int64_t n, size_t N) {
   if (gx > 256) gx = 256;
   return dim3((unsigned)gx, (unsigned)n);
 }
+// images on gridDim.y in chunks of 65535, like launch_blur: every per-image pointer advances by the chunk start
 hipError_t launch_tv1d_sol(const float* x, const float* rr, float* out, int64_t n, size_t N, float gam, const int* flag, hipStream_t st) {
-  if (n > 65535) return hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL(tv1d_sol_kernel, tv1d_grid(n, N), dim3(256), 0, st, x, rr, out, N, gam, flag);
+  for (int64_t c0 = 0; c0 < n; c0 += 65535) {
+    const int64_t nc = (n - c0) < 65535 ? (n - c0) : 65535;
+    hipLaunchKernelGGL(tv1d_sol_kernel, tv1d_grid(nc, N), dim3(256), 0, st, x + c0 * N, rr + c0 * N, out + c0 * N, N, gam, flag ? flag + c0 : nullptr);
+  }
   return hipGetLastError();
 }
 hipError_t launch_tv1d_iter(const float* x, const float* rr_in, float* p, float* rr_out, int64_t n, size_t N, float gam, float cstep, float beta, const int* flag,
                             hipStream_t st) {
-  if (n > 65535) return hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL(tv1d_iter_kernel, tv1d_grid(n, N), dim3(256), 0, st, x, rr_in, p, rr_out, N, gam, cstep, beta, flag);
+  for (int64_t c0 = 0; c0 < n; c0 += 65535) {
+    const int64_t nc = (n - c0) < 65535 ? (n - c0) : 65535;
+    hipLaunchKernelGGL(tv1d_iter_kernel, tv1d_grid(nc, N), dim3(256), 0, st, x + c0 * N, rr_in + c0 * N, p + c0 * N, rr_out + c0 * N, N, gam, cstep, beta,
+                       flag ? flag + c0 : nullptr);
+  }
   return hipGetLastError();
 }
 hipError_t launch_tv1d_objective(const float* x, const float* sol, int64_t n, size_t N, float gam, const int* flag, double* obj, hipStream_t st) {
-  if (n > 65535) return hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL(tv1d_objective_kernel, tv1d_grid(n, N), dim3(256), 0, st, x, sol, N, gam, flag, obj);
+  for (int64_t c0 = 0; c0 < n; c0 += 65535) {
+    const int64_t nc = (n - c0) < 65535 ? (n - c0) : 65535;
+    hipLaunchKernelGGL(tv1d_objective_kernel, tv1d_grid(nc, N), dim3(256), 0, st, x + c0 * N, sol + c0 * N, N, gam, flag ? flag + c0 : nullptr, obj + c0);
+  }
   return hipGetLastError();
 }
 
