@@ -13,9 +13,7 @@
 
 namespace lmc {
 
-#ifndef LMC_BLK_OCC
-#define LMC_BLK_OCC 2   // workgroups (4 waves each) per CU the register budget is sized for: 232 VGPRs, no scratch
-#endif
+constexpr int kBlkOcc = 2;   // workgroups (4 waves each) per CU the register budget is sized for: 232 VGPRs, no scratch
 
 __device__ __forceinline__ float soft_thr_b(float v, float thr) { return copysignf(fmaxf(fabsf(v) - thr, 0.f), v); }
 
@@ -23,7 +21,7 @@ __device__ __forceinline__ float soft_thr_b(float v, float thr) { return copysig
 // of three 10-pixel rows (block columns -1 .. 8) around the output row -- the interior from the LDS copy, the halo from the
 // neighbouring blocks in memory (cache hits: those lines are being streamed by the neighbouring threads).
 template <int DATA, int PRIOR, bool MC = false, int NF = 1>
-__global__ __launch_bounds__(256, LMC_BLK_OCC) void myula_step_block_kernel(const StepArgs P) {
+__global__ __launch_bounds__(256, kBlkOcc) void myula_step_block_kernel(const StepArgs P) {
   static_assert(NF == 1 || ((NF == 2 || NF == 4) && PRIOR == LMC_PRIOR_HAAR_L1 && !MC), "fused iterations: Haar prior without the MC-TV term");
   const int H = P.H, W = P.W;
   const int nbx = W >> 3;

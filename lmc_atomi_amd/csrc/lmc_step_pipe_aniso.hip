@@ -18,62 +18,28 @@ __global__ __launch_bounds__(128 * ((K + 1) / 2 + 3), 4) void myula_step_pipe2_a
   pipe_body<K, 4, KT, false, false, true, false, 2, true>(A);
 }
 
-// the dynamic-LDS attribute belongs to the function's code object on each device: set once per device
-static hipError_t pipe_aniso_lds_attr(const void* kern, size_t lb, bool (&attr_set)[64]) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
-  return hipSuccess;
-}
-
 template <int PXL, int KT, bool CHAIN, bool AL>
 static hipError_t pipe_aniso_launch_one(const StepArgs& a, hipStream_t st) {
   constexpr int K = 10;
-  auto kern = myula_step_pipe_aniso_kernel<K, PXL, KT, CHAIN, AL>;
-  constexpr size_t lb = pipe_lds_bytes<K, PXL, KT, CHAIN>();
-  static bool attr_set[64] = {};
-  hipError_t e = pipe_aniso_lds_attr(reinterpret_cast<const void*>(kern), lb, attr_set);
-  if (e != hipSuccess) return e;
-  const int BWk = 64 * PXL, U = BWk - 2 * pipe_halo(K, KT, PXL);
-  const int nstrips = a.W <= BWk ? 1 : (a.W + U - 1) / U;       // wider than one wave: column strips with recomputed halos
-  hipLaunchKernelGGL(kern, dim3(a.C, nstrips), dim3(64 * ((K + 1) / 2 + 3)), lb, st, a);
-  return hipGetLastError();
+  return pipe_launch<myula_step_pipe_aniso_kernel<K, PXL, KT, CHAIN, AL>>(pipe_lds_bytes<K, PXL, KT, CHAIN>(), dim3(a.C, pipe_nstrips<K, PXL, KT>(a.W)),
+                                                                          dim3(pipe_block(K, 1)), a, st);
 }
 
 static hipError_t pipe_aniso_launch_teams(const StepArgs& a, hipStream_t st) {
   constexpr int K = 10;
-  auto kern = myula_step_pipe2_aniso_kernel<K, 5>;
-  constexpr size_t lb = sizeof(float) * (size_t)PipeLds<K, 4, false, 2>::total;
-  static_assert(lb <= 160 * 1024, "LDS of one workgroup");
-  static bool attr_set[64] = {};
-  hipError_t e = pipe_aniso_lds_attr(reinterpret_cast<const void*>(kern), lb, attr_set);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(a.C), dim3(128 * ((K + 1) / 2 + 3)), lb, st, a);
-  return hipGetLastError();
+  return pipe_launch<myula_step_pipe2_aniso_kernel<K, 5>>(pipe_teams_lds_bytes<K>(), dim3(a.C), dim3(pipe_block(K, 2)), a, st);
 }
 
 template <bool CHAIN, bool AL>
 static hipError_t pipe_aniso_dispatch(const StepArgs& a, int KT, hipStream_t st) {
-  if (a.W > 256) {
-    if (KT == 5) return pipe_aniso_launch_one<8, 5, CHAIN, AL>(a, st);
-    if (KT == 7) return pipe_aniso_launch_one<8, 7, CHAIN, AL>(a, st);
-    return pipe_aniso_launch_one<8, 0, CHAIN, AL>(a, st);
-  }
-  if (KT == 5) return pipe_aniso_launch_one<4, 5, CHAIN, AL>(a, st);
-  if (KT == 7) return pipe_aniso_launch_one<4, 7, CHAIN, AL>(a, st);
-  return pipe_aniso_launch_one<4, 0, CHAIN, AL>(a, st);
+  return pipe_select(a.W, KT, [&](auto pxl, auto kt) { return pipe_aniso_launch_one<decltype(pxl)::value, decltype(kt)::value, CHAIN, AL>(a, st); });
 }
 
 hipError_t pipe_dispatch_aniso(const StepArgs& a, int KT, bool chain, int teams, hipStream_t st) {
   if (a.tv.niter != 10 || a.tv_warm || a.rt_kc || !(KT == 0 || KT == 5 || KT == 7)) return hipErrorInvalidConfiguration;
   if (teams == 2) return chain ? hipErrorInvalidConfiguration : pipe_aniso_launch_teams(a, st);
   // AL: the last image column is the last pixel of a lane and rows are 16-byte aligned (as pipe_dispatch_k)
-  const bool lastlane = (a.W & (a.W > 256 ? 7 : 3)) == 0;
+  const bool lastlane = pipe_lastlane(a.W);
   if (chain) return lastlane ? pipe_aniso_dispatch<true, true>(a, KT, st) : pipe_aniso_dispatch<true, false>(a, KT, st);
   return lastlane ? pipe_aniso_dispatch<false, true>(a, KT, st) : pipe_aniso_dispatch<false, false>(a, KT, st);
 }

@@ -17,30 +17,10 @@
 
 namespace lmc {
 
-#ifndef LMC_RT_SPREAD
-#define LMC_RT_SPREAD 1
-#endif
-#ifndef LMC_RT_CHAIN_MAP
-#define LMC_RT_CHAIN_MAP 1
-#endif
-#ifndef LMC_RT_MAP_SPREAD
-#define LMC_RT_MAP_SPREAD 3
-#endif
-#ifndef LMC_WARM_MIN_WAVES
-#define LMC_WARM_MIN_WAVES 1
-#endif
 // Timing experiments of round 2 that were measured and removed again (git history): stage k1's hand-off reads before stage
 // k2's arithmetic (1.876 ms), the same with stage k2's stores interleaved with its arithmetic behind scheduling barriers (1.799 ms), and the
 // two-team layout -- 16 waves of 4 pixels per lane, the teams' roles on complementary SIMDs, the column seam through LDS; exact -- at commit
 // 4183175 (1.811 ms).  Base: 1.749 ms.
-#ifdef LMC_EXP_NOBARRIER   // timing experiment: waves free-run (results are wrong); a compiler-only fence keeps every LDS store alive (without it the stores of
-                           // a tick that the same wave overwrites two ticks later are dead, and the arithmetic behind them with them)
-#define PIPE_TICK_SYNC() asm volatile("" ::: "memory")
-#elif defined(LMC_EXP_SLEEP_MASK)   // timing experiment: the waves in the mask start every tick LMC_EXP_SLEEP_N x 64 cycles late (phase shift)
-#define PIPE_TICK_SYNC() do { __syncthreads(); if ((LMC_EXP_SLEEP_MASK >> wave) & 1) __builtin_amdgcn_s_sleep(LMC_EXP_SLEEP_N); } while (0)
-#else
-#define PIPE_TICK_SYNC() __syncthreads()
-#endif
 
 template <int K>
 struct PipeGeom {
@@ -315,6 +295,47 @@ __host__ __device__ constexpr int pipe_halo(int K, int KT, int PXL) {
   return (need + PXL - 1) / PXL * PXL;
 }
 
+// Which role a hardware wave plays.  Roles: 0 = L, 1 .. NT = T, NT + 1 = C, NT + 2 = N (file header).  Hardware waves w and w + 4 share a SIMD (two teams:
+// w, w + 4, w + 8, w + 12), so the map decides which roles compete for one SIMD's issue slots.  Role of hardware wave w = nibble w of the case's code.
+// All 105 pairings of the eight roles were timed in round 3 (512 x 512 x 1024, 16 launches each, the role map taken from an environment variable; the search
+// script and its build switch were removed, they are at commit b3bb1ec: scripts/round3/perm_search.py).  Results are exact under any pairing.
+//   case                                      code          pairing (one SIMD each)                measured
+//   K != 10                                   plain         L + T4 | T1 + T5 | T2 + C | T3 + N     not searched
+//   K = 10, one launch, 5 taps / no blur      0x76325410u   L + T2 | T1 + T3 | T4 + C | T5 + N     1.736 ms against 1.775 plain, 2.07 worst (L + C or L + N, two TV waves together)
+//   K = 10, one launch, 7 taps                0x75264310u   L + C  | T1 + T2 | T3 + T5 | T4 + N    1.838 against 1.875
+//   K = 10, one launch, MC-TV term (in C)     0x76354210u   L + T5 | T1 + T3 | T2 + C  | T4 + N    1.962 against 1.983
+//   K = 10, link of a fixed-count chain       0x67325410u   L + T2 | T1 + T3 | T4 + N | T5 + C     ME-TV, 50 passes: 13.27 against 13.95 ms per iteration
+//   RT, kc = 5: one live stage per wave       0x76543210u   plain                                  \  live TV waves beside L, N, C or a pass-through wave, never beside
+//   RT, kc = 4: one live stage per wave       0x67514320u   L + T1 | T2 + T5 | T3 + N | T4 + C      > each other.  bench.py's data (chains settle at 4 passes, 3 with the 7-tap
+//   RT, kc <= 3: one live stage per wave      0x64753210u   L + T5 | T1 + N  | T2 + T4 | T3 + C    /  models): 1.504 / 1.511 ms per iteration against 1.591 / 1.566 plain
+//   RT, kc > 5, link of a chained prox        0x67254310u   L + T5 | T1 + T2 | T3 + N | T4 + C     ME-TV as configured: 15.95 against 16.73 ms
+//   RT, kc > 5, one launch                    0x74563210u   L + C  | T1 + T5 | T2 + T4 | T3 + N    DESIGN 3.0r (no figure of its own)
+//   two teams (16 waves; kPipe2Roles, nibble = team << 3 | role, decoded in pipe_body): two two-stage T waves beside L + C of one team, or beside
+//                                                           N + T1 of one team, on each SIMD; the one candidate measured
+// RT (per-chain exit): the kc live stages are a prefix; up to NT of them run one per wave (t_role: spread), the other T waves only pass the dual on, and the best
+// pairing for one live count is among the worst for another -- so the map follows kc.
+// The compiler's output follows the form of these expressions, not only their values: the last one-team row is a swap of hardware waves 4 and 6 because its
+// nibble code changes the instruction streams of the twelve one-launch RT kernels, and the two-team nibble is split where it is used because returning it
+// from here changes the two two-team kernels (scripts/kernel_resources.py --code-hash shows which kernels an edit moves).
+constexpr unsigned long long kPipe2Roles = 0x5D3BC4A291E6F780ull;
+template <int K, int KT, bool CHAIN, bool RT>
+__device__ __forceinline__ int pipe_role(int hw_wave, int kc, int ncvx_kind) {
+  constexpr int NT = PipeGeom<K>::NT;
+  if constexpr (K != 10) {
+    return hw_wave;
+  } else if constexpr (!RT) {
+    const unsigned code = CHAIN ? 0x67325410u : ncvx_kind == LMC_NCVX_MC_TV ? 0x76354210u : (KT == 7 ? 0x75264310u : 0x76325410u);
+    return (code >> (4 * hw_wave)) & 15;
+  } else {
+    if (kc <= NT) {
+      const unsigned code = kc >= 5 ? 0x76543210u : kc == 4 ? 0x67514320u : 0x64753210u;
+      return (code >> (4 * hw_wave)) & 15;
+    }
+    if (CHAIN) return (0x67254310u >> (4 * hw_wave)) & 15;
+    return hw_wave == 4 ? 6 : hw_wave == 6 ? 4 : hw_wave;
+  }
+}
+
 // KT = 0: no data term (pure prox, or t = 0).  CHAIN: the launch is one link of a chain of launches that together run more than K
 // dual iterations: stage 1 starts from the dual state A.tv_in of the previous link ([C][4][H][W]: rr, ss, p, q; NULL = zeros), the last
 // stage's state goes to A.tv_out (NULL = not stored), and with A.tv_state_only the combine / store of x_out is skipped.
@@ -344,11 +365,6 @@ __host__ __device__ constexpr int pipe_halo(int K, int KT, int PXL) {
 //   SR [2][4]           residual edge columns of the blur wave: left team lane 63's last HW (0, 1), right team lane 0's first HW (2, 3)
 // A T wave reads one 8-byte record per tick; the blur wave forms the residual row one tick before its adjoint (the row's seam columns
 // travel through SR).  Every pixel runs the arithmetic of the one-team kernel on the same operands: the results are bit-identical.
-#ifndef LMC_PIPE2_ROLES
-// role of hardware wave w = nibble w: team << 3 | role (0 L, 1..NT T, NT + 1 C, NT + 2 N).  Waves w, w + 4, w + 8, w + 12 share a SIMD: two
-// two-stage T waves beside L + C of one team, or beside N + T1 of one team, on each SIMD
-#define LMC_PIPE2_ROLES 0x5D3BC4A291E6F780ull
-#endif
 // ANISO (myula_step_pipe_aniso_kernel, lmc_step_pipe_aniso.hip): the stages project the dual onto the box (pipe_stage); fixed count, cold start.
 template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS, bool ANISO = false>
 __device__ __forceinline__ void pipe_body(const StepArgs& A) {
@@ -373,7 +389,6 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
   extern __shared__ float lds_all[];
   const int lane = threadIdx.x & 63;
   const int hw_wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int team = 0;
   const int chain = blockIdx.x;
   const int H = A.H, W = A.W;
   // per-chain exit: live stages of this launch, and whether this link only advances the dual state of this chain (it leaves in a later link)
@@ -386,45 +401,15 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     kc = min(kc_g - A.rt_base, K);
     state_only = CHAIN && kc_g > A.rt_base + K;
   }
-  // `wave` = the ROLE index used below (0 = L, 1 .. NT = T, NT + 1 = C, NT + 2 = N).  Hardware waves w and w + 4 share a SIMD: L + T4 | T1 + T5 |
-  // T2 + C | T3 + N.  In an RT launch the live stages are a prefix: a typical chain runs 3 to 5 of the 10 (waves T1, T2, half of T3), each with the
-  // objective sums on top, the other T waves only pass the dual on, and the combine wave forms the objective of the iterate it returns.  A chain
-  // with few live stages therefore pairs every heavy wave with a pass-through one: L + N | T1 + T4 | T2 + T3 | C + T5 (measured: DESIGN 3.0r).
-  // Which roles share a SIMD was searched exhaustively in round 3 (scripts/round3/perm_search.py: all 105 pairings, 512 x 512 x 1024; the role of hardware
-  // wave w is nibble w of the code): fixed K = 10: L + T2 | T1 + T3 | T4 + C | T5 + N 1.736 ms against 1.775 for the plain order and 2.07 for the worst
-  // (L + C or L + N with two TV waves together); per-chain exit with one live stage per wave: by live count, below.
-  int wave = hw_wave;
+  // `wave` = the ROLE index used below, not the hardware wave (table above pipe_role); two teams: and the team
+  int team = 0, wave;
   if constexpr (TEAMS == 2) {
-    const unsigned nib = (unsigned)(LMC_PIPE2_ROLES >> (4 * hw_wave)) & 15u;
+    const unsigned nib = (unsigned)(kPipe2Roles >> (4 * hw_wave)) & 15u;
     team = nib >> 3;
     wave = nib & 7;
-  } else if constexpr (K == 10 && !RT && !CHAIN) {   // 7 taps: L + C | T1 + T2 | T3 + T5 | T4 + N (1.838 vs 1.875); with the MC-TV term in the combine wave: L + T5 | T1 + T3 | T2 + C | T4 + N (1.962 vs 1.983)
-    const unsigned code = A.ncvx_kind == LMC_NCVX_MC_TV ? 0x76354210u : (KT == 7 ? 0x75264310u : 0x76325410u);
-    wave = (code >> (4 * hw_wave)) & 15;
+  } else {
+    wave = pipe_role<K, KT, CHAIN, RT>(hw_wave, kc, A.ncvx_kind);
   }
-  if constexpr (K == 10 && !RT && CHAIN) wave = (0x67325410u >> (4 * hw_wave)) & 15;      // links of a fixed-count chain: L + T2 | T1 + T3 | T4 + N | T5 + C (ME-TV, 50 passes: 13.27 vs 13.95 ms)
-  if constexpr (RT && K == 10) {
-#ifndef LMC_RT_MAP
-#define LMC_RT_MAP 0
-#endif
-    if (LMC_RT_SPREAD && LMC_RT_MAP_SPREAD >= 3 && kc <= NT) {
-      // one live stage per wave (t_role: spread)
-      // live TV waves beside L, N, C or a pass-through wave, never beside each other (searched on bench.py's data, where the chains settle at 4 passes -- 3 with
-      // the 7-tap models: 1.504 / 1.511 ms per iteration against 1.591 / 1.566 for the plain order; the best pairing for one live count is among the worst for another)
-      const unsigned code = kc >= 5 ? 0x76543210u : kc == 4 ? 0x67514320u      // kc = 4: L + T1 | T2 + T5 | T3 + N | T4 + C
-                                                              : 0x64753210u;     // kc <= 3: L + T5 | T1 + N | T2 + T4 | T3 + C
-      wave = (code >> (4 * hw_wave)) & 15;
-    } else if (kc <= 4) {
-      if (LMC_RT_MAP == 0) wave = hw_wave == 3 ? 6 : hw_wave == 4 ? 7 : hw_wave == 5 ? 4 : hw_wave == 6 ? 3 : hw_wave == 7 ? 5 : hw_wave;
-      else if (LMC_RT_MAP == 1) wave = hw_wave == 4 ? 6 : hw_wave == 6 ? 4 : hw_wave;                                              // L + C | T1 + T5 | T2 + T4 | T3 + N
-      else wave = hw_wave == 3 ? 6 : hw_wave == 4 ? 5 : hw_wave == 5 ? 4 : hw_wave == 6 ? 3 : hw_wave;                              // L + T5 | T1 + T4 | T2 + T3 | C + N
-    }
-    else if (CHAIN && LMC_RT_CHAIN_MAP) wave = ((LMC_RT_CHAIN_MAP == 2 ? 0x76345210u : 0x67254310u) >> (4 * hw_wave)) & 15;       // all stages live, a link of a chained prox: L + T5 | T1 + T2 | T3 + N | T4 + C (ME-TV as configured: 15.95 vs 16.73 ms)
-    else wave = hw_wave == 4 ? 6 : hw_wave == 6 ? 4 : hw_wave;        // more live stages: L + C | T1 + T5 | T2 + T4 | T3 + N
-  }
-#ifdef LMC_EXP_PERM   // timing experiment (scripts/round3/perm_search.py): role of hardware wave w = nibble w of A.PH (the tile kernel's field, unused here)
-  if (TEAMS == 1 && A.PH && (LMC_EXP_PERM == 1 || CHAIN)) wave = (A.PH >> (4 * hw_wave)) & 15;      // LMC_EXP_PERM=2: the chained links only
-#endif
   // column strip of this workgroup (blockIdx.y; one strip = the whole row when W <= 64 PXL): c0 is a GLOBAL column, LDS rows are indexed by lane
   constexpr int HALO = pipe_halo(K, KT, PXL);
   const int strip = blockIdx.y;
@@ -459,22 +444,14 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
   float* const xring = lds + L::o_x;
   auto ring_row = [&](int row) -> float* { return xring + ((unsigned)(row + RB) % (unsigned)RB) * RP; };   // row >= -RB
 
-#ifdef LMC_EXP_SKIP   // timing experiment (with LMC_EXP_NOBARRIER): the waves in the bitmask leave at once (results are wrong)
-  if ((LMC_EXP_SKIP >> wave) & 1) return;
-#endif
   // Issue arbitration on the shared SIMDs: the short, latency-bound waves everybody waits for at the barrier (L publishes the
   // ring row, C frees the hand-off slot) go first, the TV waves next, the Philox wave -- pure arithmetic, a quad row-group ahead
   // of its consumer -- last.  Measured: 2.04 -> 1.98 ms; the other way round (TV waves first) 2.37 ms.
-#ifndef LMC_PRIO_L
-#define LMC_PRIO_L 3
-#define LMC_PRIO_C 3
-#define LMC_PRIO_T 1
-#define LMC_PRIO_N 0
-#endif
-  if (wave == 0) __builtin_amdgcn_s_setprio(LMC_PRIO_L);
-  else if (wave == NT + 1) __builtin_amdgcn_s_setprio(LMC_PRIO_C);
-  else if (wave <= NT) __builtin_amdgcn_s_setprio(LMC_PRIO_T);
-  else __builtin_amdgcn_s_setprio(LMC_PRIO_N);
+  constexpr int kPrioL = 3, kPrioC = 3, kPrioT = 1, kPrioN = 0;
+  if (wave == 0) __builtin_amdgcn_s_setprio(kPrioL);
+  else if (wave == NT + 1) __builtin_amdgcn_s_setprio(kPrioC);
+  else if (wave <= NT) __builtin_amdgcn_s_setprio(kPrioT);
+  else __builtin_amdgcn_s_setprio(kPrioN);
   // the roles, once per team (two teams: the seam code of each team is static)
   auto roles = [&](auto team_tag) __attribute__((always_inline)) {
   constexpr int TM = decltype(team_tag)::value;
@@ -690,7 +667,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           prow_store<PXL>(lds + L::o_g + P * RP, lane, gout);      // row t + 1 - D, read by C next tick
         }
       }
-      PIPE_TICK_SYNC();
+      __syncthreads();
     };
     for (int t = 0; t < T_end; t += 4) static_for<0, 4>([&](auto uu) { tick(uu, t + decltype(uu)::value); });
     if (TEAMS == 1 && A.f_out) {
@@ -708,7 +685,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     // RT, at most NT live stages (the chain the reference configures settles at 4): ONE live stage per wave -- slot k1 of wave j runs stage j, slot k2 only
     // hands its state on -- instead of two stages each in the first waves and none in the rest: a wave's tick is then half as long, and what the others wait for at
     // the barrier is no longer the two-stage waves' chain of hand-off reads, two stages and stores.  Same arithmetic on the same data: bit-identical.
-    const bool spread = RT && LMC_RT_SPREAD && kc <= NT;
+    const bool spread = RT && kc <= NT;
     const int g1 = spread ? wave : k1, g2 = k2;          // the STAGES the slots run (momentum coefficient, objective slot)
     const float gam = A.tv.gamma, cstep = A.tv.c;
     const float beta1 = A.tv.betas[g1 - 1], beta2 = SINGLE ? 0.f : A.tv.betas[g2 - 1];
@@ -761,19 +738,11 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         pairs_store<NP>(hb + RP, lane, out.ss);
       } else if (!CHAIN || wave < NT) {
         float* hb = hout + P * 4 * RP;
-#ifdef LMC_EXP_NO_HSTORE     // timing experiment: the hand-off stores never execute (results are wrong), the arithmetic stays alive
-        if (A.tv.niter == 12345)
-#endif
-        {
         pairs_store<NP>(hb, lane, out.rr);
         pairs_store<NP>(hb + RP, lane, out.ss);
-#ifdef LMC_EXP_HALF_HSTORE   // timing experiment: half the hand-off stores
-        if (A.tv.niter == 12345)
-#endif
         if (wave < NT) {     // the combine wave reads rr, ss only: the last TV wave (which shares its SIMD with T1) skips half of its hand-off stores
-        pairs_store<NP>(hb + 2 * RP, lane, out.p);
-        pairs_store<NP>(hb + 3 * RP, lane, out.q);
-        }
+          pairs_store<NP>(hb + 2 * RP, lane, out.p);
+          pairs_store<NP>(hb + 3 * RP, lane, out.q);
         }
       } else {
         float* hb = hout + P * 2 * RP;                   // last boundary of a chained launch: rr, ss for the final primal step ...
@@ -863,7 +832,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           so[1] = TM == 0 ? ss2_edge : sol2[0].x;
         }
       }
-      PIPE_TICK_SYNC();
+      __syncthreads();
     };
     for (int t = 0; t < T_end; t += 4) static_for<0, 4>([&](auto uu) { tick(uu, t + decltype(uu)::value); });
     if constexpr (RT) {          // objectives of the iterates this wave's live stages formed: sol^{g-1} in stage g = rt_base + k
@@ -949,7 +918,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           }
         }
       }
-      PIPE_TICK_SYNC();
+      __syncthreads();
     };
     for (int t = 0; t < T_end; t += 4) static_for<0, 4>([&](auto uu) { tick(uu, t + decltype(uu)::value); });
   } else {
@@ -1005,7 +974,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       constexpr int U = decltype(uu)::value, P = U & 1;
       constexpr int NI = ((U - D) % 4 + 4) % 4;        // == o & 3  (t = 4m + U)
       const int o = t - D;
-      if (state_only) { PIPE_TICK_SYNC(); return; }     // this link only advances the dual state (of this chain)
+      if (state_only) { __syncthreads(); return; }     // this link only advances the dual state (of this chain)
       if (XT && VM && A.extra) {
         const int r3 = o + 3;
         gload_raw<PXL>(exq[(U + 3) & 3], A.extra + (size_t)chain * img + (size_t)min(max(r3, 0), H - 1) * W, cl, W, al);
@@ -1130,7 +1099,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           }
         }
       }
-      PIPE_TICK_SYNC();
+      __syncthreads();
     };
     for (int t = 0; t < T_end; t += 4) static_for<0, 4>([&](auto uu) { tick(uu, t + decltype(uu)::value); });
     if (XT && A.g_out) {
@@ -1166,7 +1135,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
 }
 
 template <int K, int PXL, int KT, bool CHAIN = false, bool WARM = false, bool AL = true, bool RT = false>
-__global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? (WARM ? LMC_WARM_MIN_WAVES : 1) : 2) void myula_step_pipe_kernel(const StepArgs A) {
+__global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), (PXL == 8 || CHAIN) ? 1 : 2) void myula_step_pipe_kernel(const StepArgs A) {
   pipe_body<K, PXL, KT, CHAIN, WARM, AL, RT, 1>(A);
 }
 
@@ -1179,80 +1148,72 @@ __global__ __launch_bounds__(128 * ((K + 1) / 2 + 3), 4) void myula_step_pipe2_k
 
 template <int K, int PXL, int KT, bool CHAIN = false>
 static constexpr size_t pipe_lds_bytes() { return sizeof(float) * (size_t)PipeLds<K, PXL, CHAIN>::total; }
+template <int K>
+static constexpr size_t pipe_teams_lds_bytes() { return sizeof(float) * (size_t)PipeLds<K, 4, false, 2>::total; }
+static_assert(pipe_teams_lds_bytes<10>() <= 160 * 1024, "LDS of one workgroup");
 
-template <int PXL, int KT, bool CHAIN, int K = 10, bool WARM = false, bool AL = true, bool RT = false>
-static hipError_t pipe_launch_one(const StepArgs& a, hipStream_t st) {
-  auto kern = myula_step_pipe_kernel<K, PXL, KT, CHAIN, WARM, AL, RT>;
-  constexpr size_t lb = pipe_lds_bytes<K, PXL, KT, CHAIN>();
-  static bool attr_set[64] = {};        // per device: the attribute belongs to the function's code object on that device
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
-  const int BWk = 64 * PXL, U = BWk - 2 * pipe_halo(K, KT, PXL);
-  const int nstrips = a.W <= BWk ? 1 : (a.W + U - 1) / U;       // wider than one wave: column strips with recomputed halos
-#ifdef LMC_EXP_PERM
-  StepArgs b = a;
-  if (const char* e = getenv("LMC_EXP_PERM")) b.PH = (int)strtoul(e, nullptr, 16);
-  hipLaunchKernelGGL(kern, dim3(a.C, nstrips), dim3(64 * ((K + 1) / 2 + 3)), lb, st, b);
-  return hipGetLastError();
-#endif
-  hipLaunchKernelGGL(kern, dim3(a.C, nstrips), dim3(64 * ((K + 1) / 2 + 3)), lb, st, a);
-  return hipGetLastError();
-}
-
-// the two-team kernel (one launch, K = 10, 5 taps, 264 <= W <= 512, W % 8 == 0: pipe_teams_covered)
-template <int K, int KT>
-static hipError_t pipe_launch_teams(const StepArgs& a, hipStream_t st) {
-  auto kern = myula_step_pipe2_kernel<K, KT>;
-  constexpr size_t lb = sizeof(float) * (size_t)PipeLds<K, 4, false, 2>::total;
-  static_assert(lb <= 160 * 1024, "LDS of one workgroup");
+// The one launcher of every pipe kernel, one and two teams, either prior.  The dynamic-LDS limit belongs to the function's code object on
+// each device and is set once per device; Kern is a template argument so that every kernel has a memo of its own.
+template <auto Kern>
+static hipError_t pipe_launch(size_t lds_bytes, dim3 grid, dim3 block, const StepArgs& a, hipStream_t st) {
   static bool attr_set[64] = {};
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
   if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
     if (dev >= 0 && dev < 64) attr_set[dev] = true;
   }
-  hipLaunchKernelGGL(kern, dim3(a.C), dim3(128 * ((K + 1) / 2 + 3)), lb, st, a);
+  hipLaunchKernelGGL(Kern, grid, block, lds_bytes, st, a);
   return hipGetLastError();
 }
 
-// one launch with K dual iterations: blur taps 5 / 7 / none (KT), 8 pixels per lane above 256 columns, else 4
-// rows not 16-byte aligned (W % 4 != 0): the pixel-by-pixel instantiations, K = 10 only (see pipe_links)
-template <int K, bool CHAIN>
-static hipError_t pipe_dispatch_unaligned(const StepArgs& a, int KT, hipStream_t st) {
-  if (a.W > 256) {
-    if (KT == 5) return pipe_launch_one<8, 5, CHAIN, K, false, false>(a, st);
-    if (KT == 7) return pipe_launch_one<8, 7, CHAIN, K, false, false>(a, st);
-    return pipe_launch_one<8, 0, CHAIN, K, false, false>(a, st);
-  }
-  if (KT == 5) return pipe_launch_one<4, 5, CHAIN, K, false, false>(a, st);
-  if (KT == 7) return pipe_launch_one<4, 7, CHAIN, K, false, false>(a, st);
-  return pipe_launch_one<4, 0, CHAIN, K, false, false>(a, st);
+// column strips of a one-team launch (wider than one wave: strips with recomputed halos, pipe_halo)
+template <int K, int PXL, int KT>
+static int pipe_nstrips(int W) {
+  constexpr int BWk = 64 * PXL, U = BWk - 2 * pipe_halo(K, KT, PXL);
+  return W <= BWk ? 1 : (W + U - 1) / U;
+}
+constexpr int pipe_block(int K, int teams) { return 64 * teams * ((K + 1) / 2 + 3); }
+
+// the last image column is the last pixel of a lane, rows are 16-byte aligned (the AL = true kernels)
+static bool pipe_lastlane(int W) { return (W & (W > 256 ? 7 : 3)) == 0; }
+
+// Pixels per lane and blur taps of a launch as compile-time values: 8 pixels per lane above 256 columns, else 4; taps 5 / 7 / none.
+// f(std::integral_constant<int, PXL>, std::integral_constant<int, KT>) launches the kernel of its family.
+template <class F>
+static hipError_t pipe_select(int W, int KT, F&& f) {
+  auto taps = [&](auto pxl) {
+    if (KT == 5) return f(pxl, std::integral_constant<int, 5>{});
+    if (KT == 7) return f(pxl, std::integral_constant<int, 7>{});
+    return f(pxl, std::integral_constant<int, 0>{});
+  };
+  return W > 256 ? taps(std::integral_constant<int, 8>{}) : taps(std::integral_constant<int, 4>{});
 }
 
+template <int PXL, int KT, bool CHAIN, int K = 10, bool WARM = false, bool AL = true, bool RT = false>
+static hipError_t pipe_launch_one(const StepArgs& a, hipStream_t st) {
+  return pipe_launch<myula_step_pipe_kernel<K, PXL, KT, CHAIN, WARM, AL, RT>>(pipe_lds_bytes<K, PXL, KT, CHAIN>(), dim3(a.C, pipe_nstrips<K, PXL, KT>(a.W)),
+                                                                              dim3(pipe_block(K, 1)), a, st);
+}
+
+// the two-team kernel (one launch, K = 10, 5 taps, 264 <= W <= 512, W % 8 == 0: pipe_teams_covered)
+template <int K, int KT>
+static hipError_t pipe_launch_teams(const StepArgs& a, hipStream_t st) {
+  return pipe_launch<myula_step_pipe2_kernel<K, KT>>(pipe_teams_lds_bytes<K>(), dim3(a.C), dim3(pipe_block(K, 2)), a, st);
+}
+
+// one launch with K dual iterations.  Widths that are not a multiple of the pixels per lane (rows not 16-byte aligned: W % 4 != 0): the
+// pixel-by-pixel instantiations, K = 10 without the warm dual only (see pipe_links)
 template <int K, bool CHAIN, bool WARM = false>
 static hipError_t pipe_dispatch_k(const StepArgs& a, int KT, hipStream_t st) {
-  const bool lastlane = (a.W & (a.W > 256 ? 7 : 3)) == 0;       // the last image column is the last pixel of a lane, rows are 16-byte aligned
-  if constexpr (K == 10 && !WARM) {
-    if (!lastlane) return pipe_dispatch_unaligned<K, CHAIN>(a, KT, st);
-  }
-  if (!lastlane) return hipErrorInvalidConfiguration;
-  if (a.W > 256) {
-    if (KT == 5) return pipe_launch_one<8, 5, CHAIN, K, WARM>(a, st);
-    if (KT == 7) return pipe_launch_one<8, 7, CHAIN, K, WARM>(a, st);
-    return pipe_launch_one<8, 0, CHAIN, K, WARM>(a, st);
-  }
-  if (KT == 5) return pipe_launch_one<4, 5, CHAIN, K, WARM>(a, st);
-  if (KT == 7) return pipe_launch_one<4, 7, CHAIN, K, WARM>(a, st);
-  return pipe_launch_one<4, 0, CHAIN, K, WARM>(a, st);
+  return pipe_select(a.W, KT, [&](auto pxl, auto kt) {
+    constexpr int PXL = decltype(pxl)::value, KTc = decltype(kt)::value;
+    if (pipe_lastlane(a.W)) return pipe_launch_one<PXL, KTc, CHAIN, K, WARM>(a, st);
+    if constexpr (K == 10 && !WARM) return pipe_launch_one<PXL, KTc, CHAIN, K, false, false>(a, st);
+    else return hipErrorInvalidConfiguration;
+  });
 }
 
 // lmc_step_pipe.hip: geometry / data term the pipe kernels cover, and the centred taps (returns KT)

@@ -26,25 +26,18 @@ bool pipe_rt_supported(const StepArgs& a) {
 // AL as in pipe_dispatch_k (the last image column is a lane's last pixel, rows are 16-byte aligned) -- and one strip: the AL = true kernels sum the
 // objectives over whole rows.  Everything else -- unaligned rows, column strips of any alignment -- runs the AL = false kernels, whose objective sums
 // carry per-pixel weights (the strip's interior, the last image column).
+// The links of a chained prox carry no data term: they are built for KT = 0 only.
 template <bool CHAIN, bool AL>
 static hipError_t pipe_dispatch_rt_al(const StepArgs& a, int KT, hipStream_t st) {
-  if (a.W > 256) {
-    if constexpr (!CHAIN) {
-      if (KT == 5) return pipe_launch_one<8, 5, false, 10, false, AL, true>(a, st);
-      if (KT == 7) return pipe_launch_one<8, 7, false, 10, false, AL, true>(a, st);
-    }
-    return pipe_launch_one<8, 0, CHAIN, 10, false, AL, true>(a, st);
-  }
-  if constexpr (!CHAIN) {
-    if (KT == 5) return pipe_launch_one<4, 5, false, 10, false, AL, true>(a, st);
-    if (KT == 7) return pipe_launch_one<4, 7, false, 10, false, AL, true>(a, st);
-  }
-  return pipe_launch_one<4, 0, CHAIN, 10, false, AL, true>(a, st);
+  return pipe_select(a.W, KT, [&](auto pxl, auto kt) {
+    constexpr int PXL = decltype(pxl)::value, KTc = decltype(kt)::value;
+    if constexpr (CHAIN && KTc != 0) return hipErrorInvalidConfiguration;
+    else return pipe_launch_one<PXL, KTc, CHAIN, 10, false, AL, true>(a, st);
+  });
 }
 template <bool CHAIN>
 static hipError_t pipe_dispatch_rt(const StepArgs& a, int KT, hipStream_t st) {
-  const bool lastlane = (a.W & (a.W > 256 ? 7 : 3)) == 0;
-  if (lastlane && a.W <= 512) return pipe_dispatch_rt_al<CHAIN, true>(a, KT, st);
+  if (pipe_lastlane(a.W) && a.W <= 512) return pipe_dispatch_rt_al<CHAIN, true>(a, KT, st);
   return pipe_dispatch_rt_al<CHAIN, false>(a, KT, st);
 }
 

@@ -11,10 +11,7 @@
 
 namespace lmc {
 
-#ifndef LMC_PT_TW
-#define LMC_PT_TW 64
-#endif
-constexpr int kPtTW = LMC_PT_TW, kPtTH = 32, kPtThreads = 4 * LMC_PT_TW;   // thread -> one column x 8 rows in the combine
+constexpr int kPtTW = 64, kPtTH = 32, kPtThreads = 4 * kPtTW;   // thread -> one column x 8 rows in the combine
 
 template <int KT>   // taps zero-padded to KT (5 or 7); KT == 0: no blur (pointwise / no data term)
 __global__ __launch_bounds__(kPtThreads) void myula_step_point_kernel(const StepArgs P) {

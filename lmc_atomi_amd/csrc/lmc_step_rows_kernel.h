@@ -18,19 +18,6 @@
 
 namespace lmc {
 
-#ifndef LMC_ROWS_PF
-#define LMC_ROWS_PF 4
-#endif
-#ifndef LMC_ROWS_PF4
-#define LMC_ROWS_PF4 4
-#endif
-#ifndef LMC_ROWS_PF7
-#define LMC_ROWS_PF7 2
-#endif
-#ifndef LMC_ROWS_YD7
-#define LMC_ROWS_YD7 0
-#endif
-
 template <int PXL, int KT>
 struct RowsGeom {
   static constexpr int HW = (KT - 1) / 2;         // taps are centred: window c-HW .. c+HW
@@ -39,9 +26,9 @@ struct RowsGeom {
   // fenced by tests/test_kernel_resources.py): 4 at 5 taps (8 or 4 pixels per lane).  At 7 taps and 8 pixels per lane three rings of 7-8 rows x 8 pixels leave little: x rows 2 steps ahead
   // and the observation row requested in the step that uses it (measured at 512 x 512 x 1024, 7 x 7 box + l2 prior: 0.600 ms per launch; x 1 ahead /
   // y 1 ahead 0.629; x 1 / y 0: 0.665; round 2's 2 / 1 with 23 spilled VGPRs: 0.647), 1 ahead for the 6 x 6 box (window 0..5), which still spilled at 2
-  static constexpr int PFW = (PXL == 8 && KT == 7) ? LMC_ROWS_PF7 : (PXL == 4 ? LMC_ROWS_PF4 : LMC_ROWS_PF);
+  static constexpr int PFW = (PXL == 8 && KT == 7) ? 2 : 4;                 // x rows requested this many steps ahead (where LAG leaves room: PF)
   static constexpr int PF = 8 - LAG < PFW ? 8 - LAG : PFW;
-  static constexpr int YD = (PXL == 8 && KT == 7) ? LMC_ROWS_YD7 : 1;        // observation rows requested this many steps ahead
+  static constexpr int YD = (PXL == 8 && KT == 7) ? 0 : 1;        // observation rows requested this many steps ahead
 };
 
 // Row load with zero fill (predicated: here the value must stay untouched until its use several steps later -- a select applied at
@@ -389,15 +376,12 @@ __device__ __forceinline__ void rows_body(const StepArgs& P, const int band_rows
   }
 }
 
-#ifndef LMC_ROWS_X3_OFF7
-#define LMC_ROWS_X3_OFF7 0
-#endif
 template <int PXL, int KT, bool DOT = false, int ULO = -1, int UHI = -1, bool AL = true, bool EP = false>
 __global__ __launch_bounds__(256, (PXL == 8 || KT == 7) ? 2 : 3) void myula_step_rows_kernel(const StepArgs P, const int band_rows, const int nbands) {
   __shared__ float nz_lds[PXL == 8 ? 4 * PXL * 4 * 64 : 1];
   const int m = (P.noise_mode == LMC_NOISE_INJECTED ? 1 : 0) | (P.prox_ext ? 2 : 0) | (P.extra ? 4 : 0);      // uniform over the grid
   if (m == 0) rows_body<PXL, KT, DOT, ULO, UHI, AL, EP, 0>(P, band_rows, nbands, nz_lds);
-  else if (!EP && !(LMC_ROWS_X3_OFF7 && PXL == 8 && KT == 7) && m == 3) rows_body<PXL, KT, DOT, ULO, UHI, AL, EP, EP ? -1 : 3>(P, band_rows, nbands, nz_lds);
+  else if (!EP && m == 3) rows_body<PXL, KT, DOT, ULO, UHI, AL, EP, EP ? -1 : 3>(P, band_rows, nbands, nz_lds);
   else rows_body<PXL, KT, DOT, ULO, UHI, AL, EP, -1>(P, band_rows, nbands, nz_lds);
 }
 

@@ -16,15 +16,6 @@
 
 namespace lmc {
 
-#ifdef LMC_EXP_NOLDS   // timing experiment: no LDS traffic at all (results are wrong)
-__device__ __forceinline__ float exp_keep(float v) { asm volatile("" : "+v"(v)); return v; }
-#define LR(ptr_expr, alt) exp_keep(alt)
-#define LW(lhs, val) do { float v_ = (val); asm volatile("" ::"v"(v_)); } while (0)
-#else
-#define LR(ptr_expr, alt) (ptr_expr)
-#define LW(lhs, val) (lhs) = (val)
-#endif
-
 template <int K>
 struct SplitGeom {
   static constexpr int D = (2 * K + 2 > 10) ? 2 * K + 2 : 10;  // output row lag: o = t - D
@@ -56,11 +47,7 @@ template <int V0, int V1>
 __device__ __forceinline__ void load_ghost(const float* blk, float (&g)[16]) {
   static_for<V0, V1 + 1>([&](auto vv) {
     constexpr int v = decltype(vv)::value;
-#ifdef LMC_EXP_NOLDS
-    const float4 q = {1.f, 2.f, 3.f, 4.f};
-#else
     const float4 q = *reinterpret_cast<const float4*>(blk + 4 * v);
-#endif
     g[4 * v + 0] = q.x; g[4 * v + 1] = q.y; g[4 * v + 2] = q.z; g[4 * v + 3] = q.w;
   });
 }
@@ -108,8 +95,8 @@ __device__ __forceinline__ void split_tick_a(const StepArgs& A, const int t, con
     float xv = S.xpre[U];
     if (EDGE) xv = (t < H) ? xv : 0.f;
     xv = incol ? xv : 0.f;
-    LW(xb[0], xv);
-    LW(xb[G::RB * BWP], xv);
+    xb[0] = xv;
+    xb[G::RB * BWP] = xv;
     int tn = t + 4;
     if (EDGE) tn = tn < H ? tn : H - 1;
     S.xpre[U] = LD(c.xin, (size_t)tn * W + c.colc, (size_t)H * W, 1);
@@ -124,26 +111,18 @@ __device__ __forceinline__ void split_tick_a(const StepArgs& A, const int t, con
     if constexpr (KA > 1) load_ghost<(15 - (KA - 1)) / 4, 3>(c.lds + L::o_gss + (P ^ 1) * L::GB + c.wave * 64 + (c.lane & 48) + 48, gssv);
 #pragma unroll
     for (int k = KA; k >= 1; --k) {
-      const float xa = LR(xb[(G::RB - (G::E + 2 * k)) * BWP], S.xpre[0] + (float)k);
+      const float xa = xb[(G::RB - (G::E + 2 * k)) * BWP];
       float sol;
       if (k == 1) {
         sol = xa;
       } else {
         const float ssc = S.ss[k - 1][P ^ 1];
-#ifdef LMC_EXP_NOGHOST
-        const float ssl = NB_LEFT(c, ssc, 0.f);
-#else
         const float ssl = NB_LEFT(c, ssc, gssv[15 - (k - 1)]);
-#endif
         sol = fmaf(-gam, (S.rr[k - 1][P ^ 1] - S.rr[k - 1][P]) + (ssc - ssl), xa);
       }
       S.sol[k][P] = sol;
       const float solb = S.sol[k][P ^ 1];
-#ifdef LMC_EXP_NOGHOST
-      const float solr = NB_RIGHT(c, solb, 0.f);
-#else
       const float solr = NB_RIGHT(c, solb, gsolv[k]);
-#endif
       float cdown = cstep;
       if (EDGE) {
         const int b = t - G::E - 2 * k - 1;
@@ -158,25 +137,20 @@ __device__ __forceinline__ void split_tick_a(const StepArgs& A, const int t, con
       const float sn = fmaf(beta, qn - S.q[k - 1][P], qn);
       if (k == KA) {  // hand the stage over to group B
         float* hb = c.lds + L::o_hand + P * 4 * BWP + kPad + c.col;
-        LW(hb[0], rn); LW(hb[BWP], sn); LW(hb[2 * BWP], pn); LW(hb[3 * BWP], qn);
+        hb[0] = rn; hb[BWP] = sn; hb[2 * BWP] = pn; hb[3 * BWP] = qn;
       } else {
         S.rr[k][P] = rn; S.ss[k][P] = sn; S.p[k][P] = pn; S.q[k][P] = qn;
       }
-#ifdef LMC_SPLIT_SCHED
-      if ((k % LMC_SPLIT_SCHED) == 0) __builtin_amdgcn_sched_barrier(0);
-#endif
     }
-#ifndef LMC_EXP_NOGHOST
     {   // one store per direction: the row-edge values of every stage gathered into lanes by DPP, all lanes store
       float gs = 0.f, gq = 0.f;
       static_for<1, KA + 1>([&](auto kk) { constexpr int k = decltype(kk)::value; gs = gather_first<k>(gs, S.sol[k][P]); });
-      LW(c.lds[L::o_gsol + P * L::GB + c.wave * 64 + c.lane], gs);
+      c.lds[L::o_gsol + P * L::GB + c.wave * 64 + c.lane] = gs;
       if constexpr (KA > 1) {
         static_for<1, KA>([&](auto kk) { constexpr int k = decltype(kk)::value; gq = gather_last<k>(gq, S.ss[k][P]); });
-        LW(c.lds[L::o_gss + P * L::GB + (c.wave + 1) * 64 + c.lane], gq);
+        c.lds[L::o_gss + P * L::GB + (c.wave + 1) * 64 + c.lane] = gq;
       }
     }
-#endif
   }
 
   // blur gradient pipeline, one row ahead of the output: g[o+1] -> garr[P] (group B reads it next tick)
@@ -188,7 +162,7 @@ __device__ __forceinline__ void split_tick_a(const StepArgs& A, const int t, con
     {
       const float* xr = xb + (G::RB - (G::D - 1 - KT)) * BWP + ox;   // x row o1 + KT
 #pragma unroll
-      for (int b = 0; b < KT; ++b) hxn = fmaf(uv[kMaxBlur + b], LR(xr[-b], S.xpre[1] + (float)b), hxn);
+      for (int b = 0; b < KT; ++b) hxn = fmaf(uv[kMaxBlur + b], xr[-b], hxn);
     }
     const int i = o1 + KT - oy;   // residual row
     {
@@ -201,7 +175,7 @@ __device__ __forceinline__ void split_tick_a(const StepArgs& A, const int t, con
       float rv = acc - S.ypre[U];
       if (EDGE) rv = ((i >= 0) & (i < H)) ? rv : 0.f;
       rv = incol ? rv : 0.f;
-      LW(c.lds[L::o_rrow + P * BWP + kPad + c.col], rv);
+      c.lds[L::o_rrow + P * BWP + kPad + c.col] = rv;
       int in2 = i + 4;
       if (EDGE) in2 = in2 < 0 ? 0 : (in2 < H ? in2 : H - 1);
       S.ypre[U] = LD(A.y, (size_t)in2 * W + c.colc, (size_t)H * W, 2);
@@ -210,7 +184,7 @@ __device__ __forceinline__ void split_tick_a(const StepArgs& A, const int t, con
     {
       const float* rp = c.lds + L::o_rrow + (P ^ 1) * BWP + kPad + c.col - ox;
 #pragma unroll
-      for (int b = 0; b < KT; ++b) hrn = fmaf(uv[kMaxBlur + b], LR(rp[b], S.ypre[1] + (float)b), hrn);
+      for (int b = 0; b < KT; ++b) hrn = fmaf(uv[kMaxBlur + b], rp[b], hrn);
     }
     {
       float acc = uv[KT - 1] * hrn;
@@ -219,12 +193,10 @@ __device__ __forceinline__ void split_tick_a(const StepArgs& A, const int t, con
 #pragma unroll
       for (int a = KT - 2; a >= 1; --a) S.hrw[a] = S.hrw[a - 1];
       S.hrw[0] = hrn;
-      LW(c.lds[L::o_garr + P * BWP + kPad + c.col], A.sigma_f * acc);
+      c.lds[L::o_garr + P * BWP + kPad + c.col] = A.sigma_f * acc;
     }
   }
-#ifndef LMC_EXP_NOBARRIER
   __syncthreads();
-#endif
 }
 
 // ---- group B tick --------------------------------------------------------------------------------------
@@ -243,11 +215,11 @@ __device__ __forceinline__ void split_tick_b(const StepArgs& A, const int t, con
   if constexpr (K > 0) {
     // stage KA's outputs of the previous tick, and the left neighbour of its ss
     const float* hb = c.lds + L::o_hand + (P ^ 1) * 4 * BWP + kPad + c.col;
-    S.hrr[P ^ 1] = LR(hb[0], S.hrr[P] + 1.f);
-    S.hss[P ^ 1] = LR(hb[BWP], S.hss[P] + 1.f);
-    S.hp[P ^ 1] = LR(hb[2 * BWP], S.hp[P] + 1.f);
-    S.hq[P ^ 1] = LR(hb[3 * BWP], S.hq[P] + 1.f);
-    const float hssl = LR(hb[BWP - 1], S.hss[P] + 2.f);
+    S.hrr[P ^ 1] = hb[0];
+    S.hss[P ^ 1] = hb[BWP];
+    S.hp[P ^ 1] = hb[2 * BWP];
+    S.hq[P ^ 1] = hb[3 * BWP];
+    const float hssl = hb[BWP - 1];
     const float gam = A.tv.gamma, cstep = A.tv.c;
     float gsolv[16], gssv[16];
     if constexpr (K > KA) {
@@ -256,17 +228,13 @@ __device__ __forceinline__ void split_tick_b(const StepArgs& A, const int t, con
     }
 #pragma unroll
     for (int k = K + 1; k > KA; --k) {
-      const float xa = LR(xb[(G::RB - (G::E + 2 * k)) * BWP], S.nz[0] + (float)k);
+      const float xa = xb[(G::RB - (G::E + 2 * k)) * BWP];
       float rr1, rr2, ssc, ssl;   // rr^{k-1} on rows a, a-1 ; ss^{k-1} on row a and its left neighbour
       if (k - 1 == KA) {
         rr1 = S.hrr[P ^ 1]; rr2 = S.hrr[P]; ssc = S.hss[P ^ 1]; ssl = hssl;
       } else {
         rr1 = S.rr[k - 1][P ^ 1]; rr2 = S.rr[k - 1][P]; ssc = S.ss[k - 1][P ^ 1];
-#ifdef LMC_EXP_NOGHOST
-        ssl = NB_LEFT(c, ssc, 0.f);
-#else
         ssl = NB_LEFT(c, ssc, gssv[15 - (k - 1)]);
-#endif
       }
       const float sol = fmaf(-gam, (rr1 - rr2) + (ssc - ssl), xa);
       S.sol[k][P] = sol;
@@ -274,11 +242,7 @@ __device__ __forceinline__ void split_tick_b(const StepArgs& A, const int t, con
         prox_o = sol;
       } else {
         const float solb = S.sol[k][P ^ 1];
-#ifdef LMC_EXP_NOGHOST
-        const float solr = NB_RIGHT(c, solb, 0.f);
-#else
         const float solr = NB_RIGHT(c, solb, gsolv[k]);
-#endif
         float cdown = cstep;
         if (EDGE) {
           const int b = t - G::E - 2 * k - 1;
@@ -297,19 +261,14 @@ __device__ __forceinline__ void split_tick_b(const StepArgs& A, const int t, con
         S.p[k][P] = pn;
         S.q[k][P] = qn;
       }
-#ifdef LMC_SPLIT_SCHED
-      if ((k % LMC_SPLIT_SCHED) == 0) __builtin_amdgcn_sched_barrier(0);
-#endif
     }
-#ifndef LMC_EXP_NOGHOST
     if constexpr (K > KA) {
       float gs = 0.f, gq = 0.f;
       static_for<KA + 1, K + 1>([&](auto kk) { constexpr int k = decltype(kk)::value; gs = gather_first<k>(gs, S.sol[k][P]); });
-      LW(c.lds[L::o_gsol + (2 + P) * L::GB + c.wave * 64 + c.lane], gs);
+      c.lds[L::o_gsol + (2 + P) * L::GB + c.wave * 64 + c.lane] = gs;
       static_for<KA + 1, K + 1>([&](auto kk) { constexpr int k = decltype(kk)::value; gq = gather_last<k>(gq, S.ss[k][P]); });
-      LW(c.lds[L::o_gss + (2 + P) * L::GB + (c.wave + 1) * 64 + c.lane], gq);
+      c.lds[L::o_gss + (2 + P) * L::GB + (c.wave + 1) * 64 + c.lane] = gq;
     }
-#endif
   }
 
   constexpr int NI = ((U - G::D) % 4 + 4) % 4;  // == o & 3
@@ -322,10 +281,10 @@ __device__ __forceinline__ void split_tick_b(const StepArgs& A, const int t, con
 
   if ((!EDGE || (o >= 0 && o < H)) && incol) {
     const size_t gi = (size_t)o * W + c.col;
-    const float x = LR(xb[(G::RB - G::D) * BWP], S.nz[1] + 3.f);
+    const float x = xb[(G::RB - G::D) * BWP];
     float g = 0.f;
     if constexpr (KT > 0) {
-      g = LR(c.lds[L::o_garr + (P ^ 1) * BWP + kPad + c.col], S.nz[2] + 1.f);
+      g = c.lds[L::o_garr + (P ^ 1) * BWP + kPad + c.col];
     } else if (A.data_kind == LMC_DATA_IDENTITY) {
       g = A.sigma_f * (x - S.ypre[U]);
     } else if (A.data_kind == LMC_DATA_MASK) {
@@ -362,9 +321,7 @@ __device__ __forceinline__ void split_tick_b(const StepArgs& A, const int t, con
     S.ypre[U] = LD(A.y, (size_t)on * W + c.colc, (size_t)H * W, 3);
     if (A.data_kind == LMC_DATA_MASK) S.mpre[U] = LD(A.mask, (size_t)on * W + c.colc, (size_t)H * W, 4);
   }
-#ifndef LMC_EXP_NOBARRIER
   __syncthreads();
-#endif
 }
 
 template <int K, int NW, int KT>
@@ -392,16 +349,7 @@ __global__ __launch_bounds__(128 * NW) void myula_step_split_kernel(const StepAr
 
   const int T = H + G::D;
   constexpr int t_lo = (G::D + 3) & ~3;
-#ifdef LMC_NO_STEADY
-  constexpr bool kSteady = false;
-#else
-  constexpr bool kSteady = true;
-#endif
-#ifdef LMC_SPLIT_ONLY_B
-  if (false) {
-#else
   if (is_a) {
-#endif
     StateA<K, KT> S;
 #pragma unroll
     for (int k = 0; k <= G::KA; ++k)
@@ -434,16 +382,12 @@ __global__ __launch_bounds__(128 * NW) void myula_step_split_kernel(const StepAr
     split_tick_a<K, NW, KT, 3, EDGE_>(A, t0 + 3, tm, c, S); tm = (tm + 1 == RB) ? 0 : tm + 1;
     // three loops in sequence: fill (general ticks), steady (predicate-free ticks), drain (general ticks)
     int t0 = 0;
-    const int t_hi = kSteady ? ((H - 5 - 3) & ~3) : 0;   // last group start with t0 + 3 + 4 < H (prefetch distance 4)
-    for (; t0 < T && (t0 < t_lo || !kSteady || t0 > t_hi); t0 += 4) { LMC_A_GROUP(true) }
-    if (kSteady) for (; t0 <= t_hi; t0 += 4) { LMC_A_GROUP(false) }
+    const int t_hi = (H - 5 - 3) & ~3;   // last group start with t0 + 3 + 4 < H (prefetch distance 4)
+    for (; t0 < T && (t0 < t_lo || t0 > t_hi); t0 += 4) { LMC_A_GROUP(true) }
+    for (; t0 <= t_hi; t0 += 4) { LMC_A_GROUP(false) }
     for (; t0 < T; t0 += 4) { LMC_A_GROUP(true) }
 #undef LMC_A_GROUP
-#ifdef LMC_SPLIT_ONLY_A
-  } else if (false) {
-#else
   } else {
-#endif
     StateB<K> S;
     S.hrr[0] = S.hrr[1] = S.hss[0] = S.hss[1] = S.hp[0] = S.hp[1] = S.hq[0] = S.hq[1] = 0.f;
 #pragma unroll
@@ -475,9 +419,9 @@ __global__ __launch_bounds__(128 * NW) void myula_step_split_kernel(const StepAr
     split_tick_b<K, NW, KT, 2, EDGE_>(A, t0 + 2, tm, c, S); tm = (tm + 1 == RB) ? 0 : tm + 1;               \
     split_tick_b<K, NW, KT, 3, EDGE_>(A, t0 + 3, tm, c, S); tm = (tm + 1 == RB) ? 0 : tm + 1;
     int t0 = 0;
-    const int t_hi = kSteady ? ((H - 5 - 3) & ~3) : 0;
-    for (; t0 < T && (t0 < t_lo || !kSteady || t0 > t_hi); t0 += 4) { LMC_B_GROUP(true) }
-    if (kSteady) for (; t0 <= t_hi; t0 += 4) { LMC_B_GROUP(false) }
+    const int t_hi = (H - 5 - 3) & ~3;
+    for (; t0 < T && (t0 < t_lo || t0 > t_hi); t0 += 4) { LMC_B_GROUP(true) }
+    for (; t0 <= t_hi; t0 += 4) { LMC_B_GROUP(false) }
     for (; t0 < T; t0 += 4) { LMC_B_GROUP(true) }
 #undef LMC_B_GROUP
   }
@@ -537,7 +481,6 @@ bool split_supported(const StepArgs& a) {
   if (NW == 0 || a.H < 1 || a.tv_aniso) return false;      // (no anisotropic form of this kernel)
   bool fits = false;
   switch (split_k(a)) {
-#ifndef LMC_ONLY_K10
     case 0: fits = split_fits<0>(NW); break;
     case 1: fits = split_fits<1>(NW); break;
     case 2: fits = split_fits<2>(NW); break;
@@ -548,7 +491,6 @@ bool split_supported(const StepArgs& a) {
     case 8: fits = split_fits<8>(NW); break;
     case 9: fits = split_fits<9>(NW); break;      // the lagged reading of niter = 10
     case 12: fits = split_fits<12>(NW); break;
-#endif
     case 10: fits = split_fits<10>(NW); break;
     default: return false;
   }
@@ -570,7 +512,6 @@ hipError_t launch_step_split(StepArgs a, hipStream_t st) {
     KT = (a.blur.kh > a.blur.kw ? a.blur.kh : a.blur.kw) <= 5 ? 5 : 7;
   }
   switch (split_k(a)) {
-#ifndef LMC_ONLY_K10
     case 0: return launch_split_kt<0>(a, KT, st);
     case 1: return launch_split_kt<1>(a, KT, st);
     case 2: return launch_split_kt<2>(a, KT, st);
@@ -581,7 +522,6 @@ hipError_t launch_step_split(StepArgs a, hipStream_t st) {
     case 8: return launch_split_kt<8>(a, KT, st);
     case 9: return launch_split_kt<9>(a, KT, st);
     case 12: return launch_split_kt<12>(a, KT, st);
-#endif
     case 10: return launch_split_kt<10>(a, KT, st);
   }
   return hipErrorInvalidConfiguration;

@@ -67,10 +67,15 @@ def test_kernels_of_the_reference_models_use_no_scratch(resources):
 
 def test_role_pairing_codes_are_permutations():
     """The pipe kernel assigns its eight roles to hardware waves by 8-nibble codes (nibble w = role of hardware wave w; waves w and w + 4 share a
-    SIMD): every code in the kernel source must name each role exactly once -- a repeated role would leave another one without a wave."""
+    SIMD): every code in the kernel source -- in pipe_role and in the table above it -- must name each role exactly once: a repeated role would leave
+    another one without a wave.  The two-team kernel's 16-nibble code (nibble = team << 3 | role) must name every (team, role) once."""
     import re
     src = open(os.path.join(ROOT, "lmc_atomi_amd", "csrc", "lmc_step_pipe_kernel.h")).read()
-    codes = re.findall(r"0x([0-9a-fA-F]{8})u", src)
-    assert len(codes) >= 5
+    codes = re.findall(r"0x([0-9a-fA-F]{8})u\b", src)
+    assert len(set(codes)) >= 9, sorted(set(codes))
     for c in codes:
         assert sorted(int(ch, 16) for ch in c) == list(range(8)), c
+    teams = re.findall(r"0x([0-9a-fA-F]{16})ull\b", src)
+    assert len(teams) >= 1
+    for c in teams:
+        assert sorted(int(ch, 16) for ch in c) == list(range(16)), c
