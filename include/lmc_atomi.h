@@ -317,6 +317,16 @@ int lmc_sampler_set_iteration(lmc_sampler* s, int64_t it);
 /* sum_dev, sumsq_dev: [H][W] double (device).  count = samples accumulated (chains*kept its). */
 int lmc_sampler_get_moments(lmc_sampler* s, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream);
 int lmc_sampler_reset_moments(lmc_sampler* s, void* stream);
+/* Multi-scale moments: for every enabled scale s, over the same kept samples x as the pixel moments (the same count), with
+ * b(x) = the sum of x over the block [i s, min((i+1) s, H)) x [j s, min((j+1) s, W)) (edge blocks are partial), the library keeps
+ * sum b and sum b^2 in float64, b itself formed in float64.  The accumulators are block SUMS: the mean and the variance of a block
+ * mean follow with the block's own pixel count.  One fused reduction reads a kept iterate once for the pixels and all scales;
+ * with no scale enabled the library launches exactly what it launches without this call.
+ * scales: n_scales distinct values out of {2,4,8,16}; n_scales = 0 turns them off.  Needs cfg.moments != 0 (else LMC_E_STATE) and
+ * count == 0, i.e. right after create or lmc_sampler_reset_moments (else LMC_E_STATE).  Anything else in scales: LMC_E_INVALID. */
+int lmc_sampler_set_moment_scales(lmc_sampler* s, int32_t n_scales, const int32_t* scales);
+/* sum_dev, sumsq_dev: [ceil(H/scale)][ceil(W/scale)] double (device, either nullable).  A scale that is not enabled: LMC_E_INVALID. */
+int lmc_sampler_get_block_moments(lmc_sampler* s, int32_t scale, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream);
 /* per-chain energies f(x_c), g(x_c) of the current state (device double [n_chains]) */
 int lmc_sampler_energies(lmc_sampler* s, double* f_out_dev, double* g_out_dev, void* stream);
 /* the noise field xi[n_chains][H][W] the sampler draws at `iteration` (parity rung R3) */
@@ -356,6 +366,8 @@ int lmc_rccl_unique_id(void* id128_host);
 int lmc_rccl_comm_create(void** comm_out, int32_t world, int32_t rank, const void* id128_host);
 int lmc_rccl_comm_destroy(void* comm);
 int lmc_allreduce_moments(lmc_sampler* s, void* rccl_comm, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream);
+/* as lmc_allreduce_moments, for ONE scale; rccl_comm NULL = a job of one rank (plain copy).  Packs through the same code as the pixel collective. */
+int lmc_allreduce_block_moments(lmc_sampler* s, void* rccl_comm, int32_t scale, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream);
 
 /* ---- ULPDA sampler (replaces algs.UnadjustedLangevinPrimalDual, algs.py:295-474) --------------------
  *   x    <- prox_{tau f}(x - tau (A^T y + z)) + sqrt(2 tau) xi      (algs.py:440/446)

@@ -41,6 +41,45 @@ def _data_descriptor(proxf):
     return fn()
 
 
+MOMENT_SCALES = (2, 4, 8, 16)
+
+
+def _check_moment_scales(moment_scales, moments):
+    """The tuple of block sizes a sampler is asked to keep second moments for (``None`` / empty = none); raises before any device call."""
+    scales = tuple(int(v) for v in (moment_scales or ()))
+    if scales and not moments:
+        raise ValueError("moment_scales needs moments=True: the block moments are accumulated over the kept samples of the pixel moments")
+    if len(set(scales)) != len(scales) or any(v not in MOMENT_SCALES for v in scales):
+        raise ValueError(f"moment_scales must be distinct values out of {MOMENT_SCALES}, got {scales}")
+    return scales
+
+
+def block_mean_var(S1, S2, count, scale, dims):
+    """Mean and variance of the block MEAN at one scale from the block-sum accumulators of :meth:`MYULASampler.block_moments`
+    (torch tensors or numpy arrays ``[ceil(H/scale), ceil(W/scale)]``).  Every block is divided by its own pixel count, so the partial
+    blocks at the bottom and right edges of an image whose sides are no multiple of ``scale`` need no special rule."""
+    H, W = int(dims[0]), int(dims[1])
+    s = int(scale)
+    rows = np.minimum(s, H - s * np.arange(-(-H // s)))
+    cols = np.minimum(s, W - s * np.arange(-(-W // s)))
+    npix = np.outer(rows, cols).astype(np.float64)
+    if isinstance(S1, torch.Tensor):
+        npix = torch.as_tensor(npix, dtype=S1.dtype, device=S1.device)
+    mean = S1 / (count * npix)
+    var = S2 / (count * npix * npix) - mean * mean
+    return mean, var
+
+
+def _scale_summaries(smp):
+    """``({scale: mean}, {scale: std})`` of the block means of every scale the sampler keeps."""
+    means, stds = {}, {}
+    for sc in smp.moment_scales:
+        S1, S2, cnt = smp.block_moments(sc)
+        m, v = block_mean_var(S1, S2, max(cnt, 1), sc, smp.dims)
+        means[sc], stds[sc] = m, v.clamp_min(0).sqrt()
+    return means, stds
+
+
 class MYULASampler:
     """Many-chain MYULA on one GPU: owns an ``lmc_sampler`` handle.
 
@@ -50,10 +89,13 @@ class MYULASampler:
     """
 
     def __init__(self, proxf, proxg, dims, n_chains=1, tau=None, gamma=0.1, epsg=1.0, seed=0,
-                 chain_offset=0, noise="philox", moments=False, burn_in=0, thin=1, device=None, variant=None, tv_warm=None, policy=None):
+                 chain_offset=0, noise="philox", moments=False, burn_in=0, thin=1, device=None, variant=None, tv_warm=None, policy=None,
+                 moment_scales=None):
         """``variant``: step-kernel variant of THIS sampler ('auto' | 'tile' | 'split' | 'point' | 'block' | 'rows' | 'pipe' | 'pipe2'; None = the
         library default, :func:`set_step_variant`).  ``tv_warm``: carry the TV dual between iterations (see :class:`TV`; None = as
-        ``proxg.warm`` says).  Every call on the sampler runs on ``device`` whatever the current device is."""
+        ``proxg.warm`` says).  ``moment_scales``: block sizes out of (2, 4, 8, 16) whose block sums get second moments of their own over the kept samples
+        (:meth:`block_moments`; needs ``moments=True``).  Every call on the sampler runs on ``device`` whatever the current device is."""
+        scales = _check_moment_scales(moment_scales, moments)
         if tau is None:
             raise NotImplementedError("tau=None (backtracking) is not implemented by the reference loop either")
         self.dims = (int(dims[0]), int(dims[1]))
@@ -87,8 +129,16 @@ class MYULASampler:
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             _capi.check(getattr(_dev.lib(), self._create_fn)(C.byref(cfg), C.byref(self._h)))
+        self._set_moment_scales(scales)
 
     _create_fn = "lmc_myula_create"
+    moment_scales = ()
+
+    def _set_moment_scales(self, scales):
+        if scales:
+            with torch.cuda.device(self.device):
+                _capi.check(_dev.lib().lmc_sampler_set_moment_scales(self._h, len(scales), (C.c_int32 * len(scales))(*scales)))
+        self.moment_scales = tuple(scales)
 
     def _epsg_array(self, epsg):
         """Device copy + (chain, pixel) strides of an array-valued ``epsg``.  The reference hands ``epsg * gamma`` to ``proxg.prox`` (algs.py:569), whose
@@ -211,6 +261,31 @@ class MYULASampler:
     def reset_moments(self):
         _capi.check(_dev.lib().lmc_sampler_reset_moments(self._h, _dev.stream_ptr(self.device)))
 
+    def _block_shape(self, scale):
+        s = int(scale)
+        return (-(-self.dims[0] // s), -(-self.dims[1] // s))
+
+    def block_moments(self, scale):
+        """(S1, S2, count) of one enabled scale: the sums of b and of b^2 over chains and kept iterations, b = the SUM of a sample over
+        a ``scale`` x ``scale`` block (``[ceil(H/scale), ceil(W/scale)]`` f64; edge blocks are partial).  :func:`block_mean_var` turns
+        them into the mean and the variance of the block mean."""
+        S1 = torch.empty(self._block_shape(scale), dtype=torch.float64, device=self.device)
+        S2 = torch.empty_like(S1)
+        cnt = C.c_uint64()
+        _capi.check(_dev.lib().lmc_sampler_get_block_moments(self._h, int(scale), _dev.ptr(S1), _dev.ptr(S2), C.byref(cnt),
+                                                             _dev.stream_ptr(self.device)))
+        return S1, S2, int(cnt.value)
+
+    def allreduce_block_moments(self, rccl_comm, scale):
+        """Job-wide :meth:`block_moments` of one scale: ONE ``ncclAllReduce`` through the C ABI (``lmc_allreduce_block_moments``)."""
+        S1 = torch.empty(self._block_shape(scale), dtype=torch.float64, device=self.device)
+        S2 = torch.empty_like(S1)
+        cnt = C.c_uint64()
+        comm = rccl_comm if isinstance(rccl_comm, C.c_void_p) else C.c_void_p(int(rccl_comm or 0))
+        _capi.check(_dev.lib().lmc_allreduce_block_moments(self._h, comm, int(scale), _dev.ptr(S1), _dev.ptr(S2), C.byref(cnt),
+                                                           _dev.stream_ptr(self.device)))
+        return S1, S2, int(cnt.value)
+
     def allreduce_moments(self, rccl_comm):
         """Job-wide (sum, sumsq, count): ONE ``ncclAllReduce`` (RCCL over xGMI) of the packed accumulators through the C ABI
         (``lmc_allreduce_moments``).  ``rccl_comm``: an ``ncclComm_t`` as an integer / ``c_void_p`` (``None`` or 0 = a job of one rank)."""
@@ -229,9 +304,11 @@ class ULPDASampler(MYULASampler):
     gradient.  The implicit data step runs ``proxf.niter`` warm-started CG iterations per chain on the GPU."""
 
     def __init__(self, proxf, proxg, A, dims, n_chains=1, tau=None, mu=None, theta=1.0, gfirst=True, z=None, seed=0,
-                 chain_offset=0, noise="philox", moments=False, burn_in=0, thin=1, device=None, variant=None, implicit_tol=None):
+                 chain_offset=0, noise="philox", moments=False, burn_in=0, thin=1, device=None, variant=None, implicit_tol=None,
+                 moment_scales=None):
         from .operators import Gradient
         from .proximal import L1, L21
+        scales = _check_moment_scales(moment_scales, moments)
         if not isinstance(A, Gradient):
             raise NotImplementedError("ULPDA on the GPU supports A = Gradient (the reference's operator, prox_lmc_deconv.py:98)")
         if isinstance(proxg, L21):
@@ -272,6 +349,7 @@ class ULPDASampler(MYULASampler):
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             _capi.check(_dev.lib().lmc_ulpda_create(C.byref(cfg), C.byref(self._h)))
+        self._set_moment_scales(scales)
 
     def set_steps(self, tau, mu):
         _capi.check(_dev.lib().lmc_sampler_set_steps(self._h, float(tau), float(mu)))
@@ -294,13 +372,14 @@ class ULPDASampler(MYULASampler):
 
 def UnadjustedLangevinPrimalDual(proxf, proxg, A, x0, tau, mu, y0=None, z=None, theta=1., niter=10, seed=0, gfirst=True,
                                  callback=None, callbacky=False, returny=False, show=False, *, n_chains=None, dims=None,
-                                 rng="philox", chain_offset=0, burn_in=0, thin=1, device=None, diagnostics=None):
+                                 rng="philox", chain_offset=0, burn_in=0, thin=1, device=None, diagnostics=None, moment_scales=None):
     r"""Unadjusted Langevin Primal-Dual algorithm (ULPDA) -- drop-in for algs.py:295-474.
 
     Reference form (``n_chains is None``): one chain, returns ``np.ndarray (niter, n)`` (and the duals ``(niter, 2n)`` with
     ``returny``), ``callback(x)`` / ``callback(x, y)`` every iteration, ``tau`` / ``mu`` scalars or per-iteration arrays
     (algs.py:402-408).  ``rng='pcg64'`` injects the reference's noise stream.  Many-chain form: :class:`MYULAResult`
-    (``diagnostics=(ph, pw)`` or ``True``: split R-hat / ESS across chains as in :func:`MoreauYosidaUnadjustedLangevin`).
+    (``diagnostics=(ph, pw)`` or ``True``: split R-hat / ESS across chains as in :func:`MoreauYosidaUnadjustedLangevin`;
+    ``moment_scales``: as there).
     """
     if dims is None:
         dims = getattr(A, "dims", None) or getattr(proxf, "dims", None)
@@ -313,11 +392,13 @@ def UnadjustedLangevinPrimalDual(proxf, proxg, A, x0, tau, mu, y0=None, z=None, 
         raise ValueError("rng must be 'philox' or 'pcg64'")
     if rng == "pcg64" and C_ != 1:
         raise ValueError("rng='pcg64' reproduces the reference's single chain; use n_chains=None")
+    if moment_scales and not many:
+        raise ValueError("moment_scales belongs to the many-chain form (n_chains=C): the reference form keeps every iterate instead")
     taus = np.full(niter, tau, dtype=np.float64) if np.isscalar(tau) else np.asarray(tau, dtype=np.float64)
     mus = np.full(niter, mu, dtype=np.float64) if np.isscalar(mu) else np.asarray(mu, dtype=np.float64)
     smp = ULPDASampler(proxf, proxg, A, dims, n_chains=C_, tau=taus[0], mu=mus[0], theta=theta, gfirst=gfirst, z=z,
                        seed=seed, chain_offset=chain_offset, noise="injected" if rng == "pcg64" else "philox",
-                       moments=many, burn_in=burn_in, thin=thin, device=device)
+                       moments=many, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales)
     try:
         smp.set_state(x0)
         if y0 is not None:
@@ -371,9 +452,10 @@ def UnadjustedLangevinPrimalDual(proxf, proxg, A, x0, tau, mu, y0=None, z=None, 
         state = smp.get_state()
         torch.cuda.current_stream().synchronize()
         mean, var = mean_var_from_moments(s1, s2, max(cnt, 1))
+        scale_mean, scale_std = _scale_summaries(smp)
         diag = tracer.summary() if tracer is not None and len(tracer) else None
         return MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, diagnostics=diag,
-                           trace=tracer.trace() if diag is not None else None)
+                           trace=tracer.trace() if diag is not None else None, scale_mean=scale_mean, scale_std=scale_std)
     finally:
         smp.close()
 
@@ -388,15 +470,17 @@ def mean_var_from_moments(s1, s2, count):
 class MYULAResult:
     """Return value of the many-chain form of :func:`MoreauYosidaUnadjustedLangevin`."""
 
-    def __init__(self, state, mean, var, count, energy_f, energy_g, elapsed, diagnostics=None, trace=None):
+    def __init__(self, state, mean, var, count, energy_f, energy_g, elapsed, diagnostics=None, trace=None, scale_mean=None, scale_std=None):
         self.state, self.mean, self.var, self.count = state, mean, var, count
+        # moment_scales: posterior mean and standard deviation of the image averaged over s x s blocks, {s: tensor [ceil(H/s), ceil(W/s)]}; empty when not asked
+        self.scale_mean, self.scale_std = dict(scale_mean or {}), dict(scale_std or {})
         self.energy_f, self.energy_g, self.elapsed = energy_f, energy_g, elapsed
         self.diagnostics, self.trace = diagnostics, trace      # split R-hat / ESS across chains (diagnostics.py), [T, C, Q] trace
 
 
 def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1., niter=10, seed=0,
                                    callback=None, show=False, *, n_chains=None, dims=None, rng="philox",
-                                   chain_offset=0, burn_in=0, thin=1, device=None, diagnostics=None):
+                                   chain_offset=0, burn_in=0, thin=1, device=None, diagnostics=None, moment_scales=None):
     r"""Moreau--Yosida Unadjusted Langevin algorithm (MYULA) -- drop-in for algs.py:477-587.
 
     .. math::
@@ -413,7 +497,9 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
     no iterates, returns a :class:`MYULAResult` (final states, posterior mean / variance over
     chains and kept iterations, per-chain energies).  ``diagnostics=(ph, pw)`` (or ``True`` = (8, 8)) additionally records,
     at every kept iteration, a ph x pw grid of block means and the energies of every chain and returns split R-hat and
-    effective sample size across chains in ``result.diagnostics`` (:mod:`lmc_atomi_amd.diagnostics`).
+    effective sample size across chains in ``result.diagnostics`` (:mod:`lmc_atomi_amd.diagnostics`).  ``moment_scales=(2, 4, 8, 16)`` (any
+    subset) additionally returns the posterior mean and standard deviation of the image averaged over s x s blocks -- uncertainty at
+    several scales -- in ``result.scale_mean[s]`` / ``result.scale_std[s]``.
     """
     if dims is None:
         dims = getattr(proxf, "dims", None) or getattr(proxg, "dims", None)
@@ -426,9 +512,11 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
         raise ValueError("rng must be 'philox' or 'pcg64'")
     if rng == "pcg64" and C_ != 1:
         raise ValueError("rng='pcg64' reproduces the reference's single chain; use n_chains=None")
+    if moment_scales and not many:
+        raise ValueError("moment_scales belongs to the many-chain form (n_chains=C): the reference form keeps every iterate instead")
     smp = MYULASampler(proxf, proxg, dims, n_chains=C_, tau=tau, gamma=gamma, epsg=epsg, seed=seed,
                        chain_offset=chain_offset, noise="injected" if rng == "pcg64" else "philox",
-                       moments=many, burn_in=burn_in, thin=thin, device=device)
+                       moments=many, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales)
     try:
         smp.set_state(x0)
         tstart = time.time()
@@ -490,9 +578,10 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
         state = smp.get_state()
         torch.cuda.current_stream().synchronize()
         mean, var = mean_var_from_moments(s1, s2, max(cnt, 1))
+        scale_mean, scale_std = _scale_summaries(smp)
         diag = tracer.summary() if tracer is not None and len(tracer) else None
         return MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, diagnostics=diag,
-                           trace=tracer.trace() if diag is not None else None)
+                           trace=tracer.trace() if diag is not None else None, scale_mean=scale_mean, scale_std=scale_std)
     finally:
         smp.close()
 
@@ -517,16 +606,16 @@ class MYMALASampler(MYULASampler):
 
 
 def MoreauYosidaMetropolisAdjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1., niter=10, seed=0, callback=None, *,
-                                           n_chains=1, dims=None, chain_offset=0, burn_in=0, thin=1, device=None):
+                                           n_chains=1, dims=None, chain_offset=0, burn_in=0, thin=1, device=None, moment_scales=None):
     """MYMALA at image scale for ``n_chains`` chains (the accept / reject of prox_lmc.py:134-158 around the MYULA move of
     algs.py:569): returns a :class:`MYULAResult` with two extra attributes, ``accepted`` (per-chain counts) and
-    ``acceptance_rate``.  ``callback(state)`` after every iteration if given."""
+    ``acceptance_rate``.  ``callback(state)`` after every iteration if given.  ``moment_scales``: as in :func:`MoreauYosidaUnadjustedLangevin`."""
     if dims is None:
         dims = getattr(proxf, "dims", None) or getattr(proxg, "dims", None)
     if dims is None:
         raise ValueError("image shape unknown: pass dims=(ny, nx)")
     smp = MYMALASampler(proxf, proxg, dims, n_chains=int(n_chains), tau=tau, gamma=gamma, epsg=epsg, seed=seed,
-                        chain_offset=chain_offset, moments=True, burn_in=burn_in, thin=thin, device=device)
+                        chain_offset=chain_offset, moments=True, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales)
     try:
         smp.set_state(x0)
         tstart = time.time()
@@ -542,7 +631,8 @@ def MoreauYosidaMetropolisAdjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1,
         acc, _ = smp.acceptance()
         torch.cuda.current_stream().synchronize()
         mean, var = mean_var_from_moments(s1, s2, max(cnt, 1))
-        res = MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart)
+        scale_mean, scale_std = _scale_summaries(smp)
+        res = MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, scale_mean=scale_mean, scale_std=scale_std)
         res.accepted = acc
         res.acceptance_rate = acc.double() / max(niter, 1)
         return res

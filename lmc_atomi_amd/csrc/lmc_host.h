@@ -205,7 +205,18 @@ struct lmc_sampler {
   int cur = 0;
   double* s1 = nullptr;
   double* s2 = nullptr;
-  double* packed = nullptr;              // [2 H W + 1]: the send / receive buffer of lmc_allreduce_moments
+  double* packed = nullptr;              // [2 H W + 1]: the send / receive buffer of lmc_allreduce_moments and lmc_allreduce_block_moments
+  // multi-scale moments (lmc_sampler_set_moment_scales): one packed buffer of the sum b^2 arrays of the enabled scales; scales.s2[i] points into it
+  double* bs2 = nullptr;
+  size_t bs2_count = 0;                  // doubles in bs2
+  lmc::BlockScales scales{};
+  // the kept iterate x into the accumulators: the fused multi-scale reduction when scales are enabled, else exactly the launches of before
+  hipError_t reduce(const float* x, hipStream_t st) {
+    return bs2 ? lmc::launch_moments_ms(x, C, prob.H, prob.W, s1, s2, scales, st) : lmc::launch_moments(x, C, prob.H, prob.W, s1, s2, st);
+  }
+  hipError_t reduce_bg(const float* x, int n_wg, hipStream_t st) {
+    return bs2 ? lmc::launch_moments_ms_bg(x, C, prob.H, prob.W, s1, s2, scales, n_wg, st) : lmc::launch_moments_bg(x, C, prob.H, prob.W, s1, s2, n_wg, st);
+  }
   lmc::StepArgs base{};
   // MYMALA state (kind == 2): proposal mean of the current state, proposal, its mean, energies, decisions
   float* mx = nullptr; float* xp = nullptr; float* mxp = nullptr;

@@ -36,6 +36,13 @@ hipError_t launch_haar_value(const float* x, int64_t n_img, int H, int W, float 
 hipError_t launch_mc_tv_add(const float* x, float* out, int64_t n_img, int H, int W, float coef, float gamma, hipStream_t st);
 hipError_t launch_moments(const float* x, int C, int H, int W, double* s1, double* s2, hipStream_t st);
 hipError_t launch_moments_bg(const float* x, int C, int H, int W, double* s1, double* s2, int n_wg, hipStream_t st);
+// multi-scale moments (lmc_moments_ms.hip): the pixel accumulators and sum b^2 of the block sums b of every enabled scale, in one pass
+struct BlockScales {
+  double* s2[4];          // by scale 2, 4, 8, 16: [ceil(H / s)][ceil(W / s)] doubles, NULL = that scale is off
+};
+hipError_t launch_moments_ms(const float* x, int C, int H, int W, double* s1, double* s2, const BlockScales& B, hipStream_t st);
+hipError_t launch_moments_ms_bg(const float* x, int C, int H, int W, double* s1, double* s2, const BlockScales& B, int n_wg, hipStream_t st);
+hipError_t launch_block_sums(const double* src, int H, int W, int scale, double* out, hipStream_t st);
 hipError_t launch_energies(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, double* g_out,
                            hipStream_t st);
 // pieces of the exact early-exit path of the TV prox (lmc_problem.tv_rtol > 0)

@@ -1,4 +1,4 @@
-// Multi-GPU: the RCCL entry points and the all-reduce of the posterior moments.
+// Multi-GPU: the RCCL entry points and the all-reduces of the posterior moments (pixels, and the blocks of one scale).
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types and enums only: the library itself is dlopen'd (liblmc_atomi loads without RCCL)
 
@@ -92,19 +92,9 @@ int lmc_rccl_comm_destroy(void* comm) {
   return LMC_OK;
 }
 
-int lmc_allreduce_moments(lmc_sampler* s, void* rccl_comm, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream) {
-  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
-  DeviceGuard dg(s->device);
-  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
-  hipStream_t st = S(stream);
-  const size_t n = (size_t)s->prob.H * s->prob.W;
-  if (!rccl_comm) return lmc_sampler_get_moments(s, sum_dev, sumsq_dev, count, stream);   // a job of one rank
-  RcclApi* R = rccl_api();
-  if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
-  if (!s->packed) HIP_TRY(hipMalloc(&s->packed, sizeof(double) * (2 * n + 1)));
-  // one packed buffer {sum x, sum x^2, count}: ONE ncclAllReduce(sum) over xGMI (4 MiB at 512 x 512), in place
-  HIP_TRY(hipMemcpyAsync(s->packed, s->s1, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s->packed + n, s->s2, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+// The collective of the moments: s->packed holds {sum [n], sumsq [n]} of this rank; the count joins them, ONE ncclAllReduce(sum) over xGMI
+// (4 MiB at 512 x 512) in place, and the three come back out.
+static int allreduce_packed(lmc_sampler* s, RcclApi* R, void* rccl_comm, size_t n, double* sum_dev, double* sumsq_dev, uint64_t* count, hipStream_t st) {
   const double cnt = (double)s->count;                      // exact below 2^53 samples
   HIP_TRY(hipMemcpyAsync(s->packed + 2 * n, &cnt, sizeof(double), hipMemcpyHostToDevice, st));
   RCCL_TRY(R, R->AllReduce(s->packed, s->packed, 2 * n + 1, ncclFloat64, ncclSum, static_cast<ncclComm_t>(rccl_comm), st));
@@ -115,6 +105,35 @@ int lmc_allreduce_moments(lmc_sampler* s, void* rccl_comm, double* sum_dev, doub
   HIP_TRY(hipStreamSynchronize(st));
   if (count) *count = (uint64_t)(total + 0.5);
   return LMC_OK;
+}
+
+int lmc_allreduce_moments(lmc_sampler* s, void* rccl_comm, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
+  hipStream_t st = S(stream);
+  const size_t n = (size_t)s->prob.H * s->prob.W;
+  if (!rccl_comm) return lmc_sampler_get_moments(s, sum_dev, sumsq_dev, count, stream);   // a job of one rank
+  RcclApi* R = rccl_api();
+  if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
+  if (!s->packed) HIP_TRY(hipMalloc(&s->packed, sizeof(double) * (2 * n + 1)));
+  HIP_TRY(hipMemcpyAsync(s->packed, s->s1, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->packed + n, s->s2, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  return allreduce_packed(s, R, rccl_comm, n, sum_dev, sumsq_dev, count, st);
+}
+
+int lmc_allreduce_block_moments(lmc_sampler* s, void* rccl_comm, int32_t scale, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (!rccl_comm) return lmc_sampler_get_block_moments(s, scale, sum_dev, sumsq_dev, count, stream);   // a job of one rank
+  hipStream_t st = S(stream);
+  RcclApi* R = rccl_api();
+  if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
+  if (!s->packed) HIP_TRY(hipMalloc(&s->packed, sizeof(double) * (2 * (size_t)s->prob.H * s->prob.W + 1)));   // the blocks of a scale are fewer than the pixels
+  const size_t n = (size_t)((s->prob.H + scale - 1) / (scale > 0 ? scale : 1)) * ((s->prob.W + scale - 1) / (scale > 0 ? scale : 1));
+  int rc = lmc_sampler_get_block_moments(s, scale, s->packed, s->packed + n, nullptr, stream);   // refuses a scale that is not enabled
+  if (rc) return rc;
+  return allreduce_packed(s, R, rccl_comm, n, sum_dev, sumsq_dev, count, st);
 }
 
 }  // extern "C"

@@ -145,6 +145,7 @@ void lmc_sampler_destroy(lmc_sampler* s) {
   if (s->s1) (void)hipFree(s->s1);
   if (s->s2) (void)hipFree(s->s2);
   if (s->packed) (void)hipFree(s->packed);
+  if (s->bs2) (void)hipFree(s->bs2);
   for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
   if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }
   for (hipEvent_t e : s->side_ev) if (e) (void)hipEventDestroy(e);
@@ -266,7 +267,7 @@ struct SideMoments {
       HIP_TRY(hipEventRecord(s->side_ev[0], st));
       HIP_TRY(hipStreamWaitEvent(s->side, s->side_ev[0], 0));
       for (const float* x : {a, b})
-        if (x) HIP_TRY(lmc::launch_moments_bg(x, s->C, s->prob.H, s->prob.W, s->s1, s->s2, bg_wgs, s->side));
+        if (x) HIP_TRY(s->reduce_bg(x, bg_wgs, s->side));
       HIP_TRY(hipEventRecord(s->side_ev[1 + slot], s->side));
       reads[slot][0] = a;
       reads[slot][1] = b;
@@ -274,7 +275,7 @@ struct SideMoments {
     } else {
       HIP_TRY(join());
       for (const float* x : {a, b})
-        if (x) HIP_TRY(lmc::launch_moments(x, s->C, s->prob.H, s->prob.W, s->s1, s->s2, st));
+        if (x) HIP_TRY(s->reduce(x, st));
     }
     s->count += (uint64_t)s->C * ((a ? 1 : 0) + (b ? 1 : 0));
     return LMC_OK;
@@ -546,7 +547,7 @@ static int mymala_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, 
     // follow the acceptance rate, which the host does not see without a synchronisation.)
     HIP_TRY(lmc::mala_select(s->flag, x, s->mx, s->xp, s->mxp, C, img, 1, st));
     if (kept(s, s->iteration)) {
-      HIP_TRY(lmc::launch_moments(x, C, s->prob.H, s->prob.W, s->s1, s->s2, st));
+      HIP_TRY(s->reduce(x, st));
       s->count += (uint64_t)C;
     }
     ++s->iteration;
@@ -629,7 +630,7 @@ static int ulpda_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, h
     if (!s->gfirst)  // (algs.py:448)
       HIP_TRY(lmc::ulpda_dual_update(s->xhat, s->ydual, C, H, W, s->mu, s->prob.prior_sigma, iso, st));
     if (kept(s, s->iteration)) {
-      HIP_TRY(lmc::launch_moments(x, s->C, H, W, s->s1, s->s2, st));
+      HIP_TRY(s->reduce(x, st));
       s->count += (uint64_t)s->C;
     }
     ++s->iteration;
@@ -746,7 +747,60 @@ int lmc_sampler_reset_moments(lmc_sampler* s, void* stream) {
   const size_t mb = sizeof(double) * (size_t)s->prob.H * s->prob.W;
   HIP_TRY(hipMemsetAsync(s->s1, 0, mb, S(stream)));
   HIP_TRY(hipMemsetAsync(s->s2, 0, mb, S(stream)));
+  if (s->bs2) HIP_TRY(hipMemsetAsync(s->bs2, 0, sizeof(double) * s->bs2_count, S(stream)));
   s->count = 0;
+  return LMC_OK;
+}
+
+// ---- multi-scale moments: sum b and sum b^2 of the block sums b of every kept sample, for scales out of {2, 4, 8, 16} ----
+static int scale_index(int32_t scale) { return scale == 2 ? 0 : scale == 4 ? 1 : scale == 8 ? 2 : scale == 16 ? 3 : -1; }
+
+int lmc_sampler_set_moment_scales(lmc_sampler* s, int32_t n_scales, const int32_t* scales) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (n_scales < 0 || n_scales > 4 || (n_scales > 0 && !scales)) return fail(LMC_E_INVALID, "n_scales must be 0 .. 4 (distinct scales out of 2, 4, 8, 16)");
+  size_t off[4] = {0, 0, 0, 0}, total = 0;
+  bool on[4] = {false, false, false, false};
+  for (int i = 0; i < n_scales; ++i) {
+    const int k = scale_index(scales[i]);
+    if (k < 0) return fail(LMC_E_INVALID, "moment scale %d: the scales are 2, 4, 8 and 16", scales[i]);
+    if (on[k]) return fail(LMC_E_INVALID, "moment scale %d given twice", scales[i]);
+    on[k] = true;
+  }
+  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
+  if (s->count != 0) return fail(LMC_E_STATE, "the moment scales change only while the accumulators are empty (after create or lmc_sampler_reset_moments)");
+  for (int k = 0; k < 4; ++k) {
+    const size_t sc = (size_t)2 << k;
+    off[k] = total;
+    if (on[k]) total += ((s->prob.H + sc - 1) / sc) * ((s->prob.W + sc - 1) / sc);
+  }
+  if (s->bs2) HIP_TRY(hipFree(s->bs2));
+  s->bs2 = nullptr;
+  s->bs2_count = 0;
+  s->scales = lmc::BlockScales{};
+  if (!total) return LMC_OK;
+  hipError_t e = hipMalloc(&s->bs2, sizeof(double) * total);
+  if (e == hipSuccess) e = hipMemset(s->bs2, 0, sizeof(double) * total);
+  if (e != hipSuccess) {
+    if (s->bs2) (void)hipFree(s->bs2);
+    s->bs2 = nullptr;
+    return fail(e == hipErrorOutOfMemory ? LMC_E_NOMEM : LMC_E_HIP, "block-moment allocation failed: %s", hipGetErrorString(e));
+  }
+  s->bs2_count = total;
+  for (int k = 0; k < 4; ++k) s->scales.s2[k] = on[k] ? s->bs2 + off[k] : nullptr;
+  return LMC_OK;
+}
+
+int lmc_sampler_get_block_moments(lmc_sampler* s, int32_t scale, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  const int k = scale_index(scale);
+  if (k < 0 || !s->scales.s2[k]) return fail(LMC_E_INVALID, "moment scale %d is not enabled (lmc_sampler_set_moment_scales)", scale);
+  const size_t nb = (size_t)((s->prob.H + scale - 1) / scale) * ((s->prob.W + scale - 1) / scale);
+  if (sum_dev) HIP_TRY(lmc::launch_block_sums(s->s1, s->prob.H, s->prob.W, scale, sum_dev, S(stream)));
+  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, s->scales.s2[k], sizeof(double) * nb, hipMemcpyDeviceToDevice, S(stream)));
+  HIP_TRY(hipStreamSynchronize(S(stream)));
+  if (count) *count = s->count;
   return LMC_OK;
 }
 

@@ -31,7 +31,8 @@ def synthetic_image(ny=512, nx=512, seed=1234):
 
 
 def prox_lmc_deconv(gamma_mc=15., gamma_me=15., sigma=0.75, tau=0.3, N=1000, niter_l2=50, niter_tv=10, image=None,
-                    alg='ULPDA', seed=0, n_chains=None, burn_in=0, thin=1, models=None, verbose=True, diagnostics=None, rtol=1e-4):
+                    alg='ULPDA', seed=0, n_chains=None, burn_in=0, thin=1, models=None, verbose=True, diagnostics=None, rtol=1e-4,
+                    moment_scales=None):
     """Posterior means of the nine models M1..M9 (prox_lmc_deconv.py:447-703) by ULPDA or MYULA on the GPU.
 
     ``rtol``: the early exit of the TV proxes AS THE REFERENCE IS CONFIGURED -- ``pyproximal.TV(dims, sigma, niter=niter_tv)`` leaves upstream's default
@@ -40,6 +41,8 @@ def prox_lmc_deconv(gamma_mc=15., gamma_me=15., sigma=0.75, tau=0.3, N=1000, nit
 
     ``n_chains=None`` runs the reference's single chain (every iterate kept on the host, mean over iterates,
     ``:474``); ``n_chains=C`` runs C chains per model and averages over chains and kept iterations.
+    ``moment_scales`` (with ``n_chains``): block sizes out of (2, 4, 8, 16); every model then also carries ``scale_mean`` / ``scale_std``,
+    ``{s: array}`` of the posterior mean and standard deviation of the image averaged over s x s blocks.
     Returns ``{"M1": {"mean", "snr", "psnr", "mse", "seconds"}, ...}``.
     """
     img = synthetic_image() if image is None else np.asarray(image, dtype=np.float64)
@@ -72,20 +75,21 @@ def prox_lmc_deconv(gamma_mc=15., gamma_me=15., sigma=0.75, tau=0.3, N=1000, nit
         if models is not None and name not in models:
             continue
         f = data_term(k, kind)
+        ms = {"moment_scales": moment_scales} if moment_scales else {}
         t0 = time.time()
         if alg == 'ULPDA':                                          # :455-464
             res = UnadjustedLangevinPrimalDual(f, L21(ndim=2, sigma=tau), Gop, tau=tau0, mu=mu0, theta=1., x0=x0, gfirst=False,
-                                               niter=N, seed=seed, n_chains=n_chains, burn_in=burn_in, thin=thin,
+                                               niter=N, seed=seed, n_chains=n_chains, burn_in=burn_in, thin=thin, **ms,
                                                **({"diagnostics": diagnostics} if (diagnostics and n_chains) else {}))
         elif alg == 'MYULA':                                        # :465-473
             res = MoreauYosidaUnadjustedLangevin(f, TV(dims=(ny, nx), sigma=tau, niter=niter_tv, rtol=rtol), tau=tau_myula,
                                                  gamma=gamma_myula, x0=x0, niter=N, seed=seed, n_chains=n_chains,
-                                                 burn_in=burn_in, thin=thin,
+                                                 burn_in=burn_in, thin=thin, **ms,
                                                  **({"diagnostics": diagnostics} if (diagnostics and n_chains) else {}))
         elif alg == 'MYMALA':                                       # Metropolis-adjusted MYULA (generalises prox_lmc.py:134-158)
             res = MoreauYosidaMetropolisAdjustedLangevin(f, TV(dims=(ny, nx), sigma=tau, niter=niter_tv), tau=tau_myula,
                                                          gamma=gamma_myula, x0=x0, niter=N, seed=seed, n_chains=n_chains or 1,
-                                                         burn_in=burn_in, thin=thin)
+                                                         burn_in=burn_in, thin=thin, **ms)
         else:
             raise ValueError("alg must be 'ULPDA', 'MYULA' or 'MYMALA'")
         mean = res.mean(axis=0) if isinstance(res, np.ndarray) else res.mean.cpu().numpy().ravel()      # :474
@@ -94,6 +98,9 @@ def prox_lmc_deconv(gamma_mc=15., gamma_me=15., sigma=0.75, tau=0.3, N=1000, nit
                      "psnr": float(peak_signal_noise_ratio(img, mean, dims=(ny, nx))),
                      "mse": float(mean_squared_error(img, mean, dims=(ny, nx))),
                      "seconds": time.time() - t0}
+        if moment_scales:
+            out[name]["scale_mean"] = {sc: v.cpu().numpy() for sc, v in res.scale_mean.items()}
+            out[name]["scale_std"] = {sc: v.cpu().numpy() for sc, v in res.scale_std.items()}
         diag = getattr(res, "diagnostics", None)
         if diag is not None:                                        # split R-hat / ESS across chains (diagnostics.py)
             out[name].update(rhat_max=diag["rhat_max"], ess_min=diag["ess_min"], rhat=diag["rhat"].cpu().numpy(),

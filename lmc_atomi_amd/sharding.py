@@ -92,6 +92,18 @@ def allreduce_sampler_moments(smp, group=None):
     return allreduce_moments(s1, s2, cnt, group)
 
 
+def allreduce_sampler_block_moments(smp, scale, group=None):
+    """Job-wide (S1, S2, count) of one scale of a sampler's block-moment accumulators (:meth:`MYULASampler.block_moments`), by the same
+    routes as :func:`allreduce_sampler_moments`: ``lmc_allreduce_block_moments`` under "nccl", the packed host all-reduce under "gloo"."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return smp.block_moments(scale)
+    if dist.get_backend(group) == "nccl":
+        return smp.allreduce_block_moments(rccl_comm(group, smp.device), scale)
+    S1, S2, cnt = smp.block_moments(scale)
+    return allreduce_moments(S1, S2, cnt, group)
+
+
 def allgather_chains(t: torch.Tensor, dim: int = 1, group=None):
     """Concatenate per-rank tensors along their chain dimension in rank order (= global chain order under
     :func:`chain_shard`); ranks may own different numbers of chains.  Used for the diagnostics trace ``[T, C_rank, Q]``
@@ -119,10 +131,11 @@ def posterior_mean_var(s1, s2, count):
 
 
 def sharded_myula(proxf, proxg, dims, n_chains_total, x0, tau, gamma, epsg=1.0, niter=10, seed=0,
-                  burn_in=0, thin=1, group=None, device=None):
+                  burn_in=0, thin=1, group=None, device=None, moment_scales=None):
     """Run ``n_chains_total`` MYULA chains split over the ranks of the default process group (or run
     them all here when torch.distributed is not initialised) and return the job-wide posterior
-    (mean, var, count) plus this rank's final states."""
+    (mean, var, count) plus this rank's final states.  With ``moment_scales`` (block sizes out of 2, 4, 8, 16) a fifth value
+    follows: ``{scale: (mean, std)}`` of the image averaged over scale x scale blocks, job-wide as well."""
     import torch.distributed as dist
     from .algs import MYULASampler
     world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
@@ -131,13 +144,19 @@ def sharded_myula(proxf, proxg, dims, n_chains_total, x0, tau, gamma, epsg=1.0, 
         raise ValueError(f"{n_chains_total} chains cannot be sharded over {world} ranks (every rank needs at least one)")
     offset, count = chain_shard(n_chains_total, world, rank)
     smp = MYULASampler(proxf, proxg, dims, n_chains=count, tau=tau, gamma=gamma, epsg=epsg, seed=seed,
-                       chain_offset=offset, moments=True, burn_in=burn_in, thin=thin, device=device)
+                       chain_offset=offset, moments=True, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales)
+    scales = {}
     try:
         smp.set_state(x0)
         smp.step(niter)
         s1, s2, cnt = allreduce_sampler_moments(smp, group)
+        for sc in smp.moment_scales:
+            from .algs import block_mean_var
+            S1, S2, n = allreduce_sampler_block_moments(smp, sc, group)
+            m, v = block_mean_var(S1, S2, max(n, 1), sc, smp.dims)
+            scales[sc] = (m, v.clamp_min(0).sqrt())
         state = smp.get_state()
     finally:
         smp.close()
     mean, var = posterior_mean_var(s1, s2, cnt)
-    return mean, var, cnt, state
+    return (mean, var, cnt, state, scales) if moment_scales else (mean, var, cnt, state)
