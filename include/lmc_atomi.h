@@ -246,7 +246,9 @@ int lmc_chain_probes(const float* x_dev, float* out_dev, int64_t n_img, int32_t 
 int lmc_dual_project(const float* y_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W,
                      float radius, int32_t isotropic, void* stream);
 
-/* Closed-form elementwise proxes of prox.py (the functional plugin surface), n elements. */
+/* Closed-form elementwise proxes of prox.py (the functional plugin surface), n elements.  Each is accurate to a few fp32 eps of its RESULT for
+ * parameters 1e-5 .. 1e2 (DESIGN.md "Closed-form proxes: accuracy").  gamma, tau, omega (gamma family, uniform) and kappa are weights or bounds:
+ * 0 is allowed (a weight of 0 gives the identity), a negative or NaN one is LMC_E_INVALID. */
 typedef enum lmc_eprox_kind {
   LMC_EPROX_LAPLACE = 0,            /* prox.py:18  params: gamma                */
   LMC_EPROX_UNCENTERED_LAPLACE = 1, /* prox.py:22  params: gamma, mu            */

@@ -23,6 +23,23 @@ MAX_TV_ITERS = 64
 (EPROX_LAPLACE, EPROX_UNCENTERED_LAPLACE, EPROX_GAUSSIAN, EPROX_GEN_GAUSSIAN_4_3, EPROX_GEN_GAUSSIAN_3_2,
  EPROX_GEN_GAUSSIAN_3, EPROX_GEN_GAUSSIAN_4, EPROX_HUBER, EPROX_SMOOTHED_LAPLACE, EPROX_EXP, EPROX_GAMMA,
  EPROX_CHI, EPROX_UNIFORM, EPROX_TRIANGULAR, EPROX_LAPLACE_CONJ) = range(15)
+# lmc_eprox_kind -> (name, parameter names in the order of prox.py, indices of the parameters that are weights, scales or bounds).  Those must be >= 0,
+# and 0 is the prox of the zero function.  The library refuses a negative one with LMC_E_INVALID from the same table (eprox_params_ok in
+# csrc/lmc_host.h; tests/test_gpu_eprox_accuracy.py holds the two against each other, parameter by parameter); the Python surface says which one first.
+EPROX_PARAMS = {EPROX_LAPLACE: ("laplace", ("gamma",), (0,)), EPROX_UNCENTERED_LAPLACE: ("uncentered_laplace", ("gamma", "mu"), (0,)),
+                EPROX_GAUSSIAN: ("gaussian", ("gamma",), (0,)), EPROX_GEN_GAUSSIAN_4_3: ("gen_gaussian_4_3", ("gamma",), (0,)),
+                EPROX_GEN_GAUSSIAN_3_2: ("gen_gaussian_3_2", ("gamma",), (0,)), EPROX_GEN_GAUSSIAN_3: ("gen_gaussian_3", ("gamma",), (0,)),
+                EPROX_GEN_GAUSSIAN_4: ("gen_gaussian_4", ("gamma",), (0,)), EPROX_HUBER: ("huber", ("gamma", "tau"), (0, 1)),
+                EPROX_SMOOTHED_LAPLACE: ("smoothed_laplace", ("gamma",), (0,)), EPROX_EXP: ("exp", ("gamma",), (0,)),
+                EPROX_GAMMA: ("gamma", ("omega", "kappa"), (0, 1)), EPROX_CHI: ("chi", ("kappa",), (0,)), EPROX_UNIFORM: ("uniform", ("omega",), (0,)),
+                EPROX_TRIANGULAR: ("triangular", ("omega1", "omega2"), ()), EPROX_LAPLACE_CONJ: ("laplace_conj", ("gamma",), ())}
+
+
+def check_eprox_params(kind, params):
+    name, names, nonneg = EPROX_PARAMS[kind]
+    for i in nonneg:
+        if not float(params[i]) >= 0:
+            raise ValueError(f"prox_{name}: {names[i]} is a weight and must be >= 0 (got {params[i]!r})")
 
 
 class LMCError(RuntimeError):

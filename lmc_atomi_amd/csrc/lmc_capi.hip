@@ -282,6 +282,7 @@ int lmc_prox_elementwise(int32_t kind, const float* x_dev, float* out_dev, int64
   if (n_params != need[kind] || !params_host)
     return fail(LMC_E_INVALID, "elementwise prox %d takes %d parameter(s), got %d", kind, need[kind], n_params);
   const float p0 = params_host[0], p1 = n_params > 1 ? params_host[1] : 0.f;
+  if (!eprox_params_ok(kind, p0, p1)) return fail(LMC_E_INVALID, "elementwise prox %d: negative (or NaN) weight %g, %g", kind, (double)p0, (double)p1);
   HIP_TRY(lmc::launch_eprox(kind, x_dev, out_dev, n, p0, p1, S(stream)));
   return LMC_OK;
 }

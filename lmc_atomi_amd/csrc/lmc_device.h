@@ -239,48 +239,66 @@ __device__ __forceinline__ float gather_last(float acc, float v) {
 // fused step kernels ----------------------------------------------------------------------------------------------------------------------
 struct EproxParams { float p0, p1; };
 
-__device__ __forceinline__ float sgn(float x) { return (x > 0.f) - (x < 0.f); }
 __device__ __forceinline__ float soft(float x, float t) { return copysignf(fmaxf(fabsf(x) - t, 0.f), x); }
 
+// Every form is written so that no sum takes terms of opposite sign of like size (the textbook forms of prox.py cancel for prox parameters
+// t = epsg gamma lambda << 1 and >> 1): conjugate roots for the quadratics, (a - b)(a^2 + a b + b^2) = a^3 - b^3 with a b known in closed form for
+// Cardano's cube roots.  Accurate to K eps of the RESULT for parameters 1e-5 .. 1e2 (DESIGN "Closed-form proxes: accuracy"; the same expressions in
+// numpy float32: tests/_eprox_ref.py model32), a weight of 0 is the identity bit for bit, and the sign of x (of -0 too) is carried by copysignf.
 __device__ __forceinline__ float eprox(int kind, float x, EproxParams q) {
-  const float g = q.p0;
+  // The parameters are uniform, so everything derived from them alone (sqrtf(27 g), 4g/9, Huber's split constant, ...) is loop-invariant for the
+  // caller's pixel loop, and the compiler hoists those values of all fifteen forms into VGPRs held for the whole kernel: the row kernels spill
+  // for it.  The empty asm makes them per-call values: a few more VALU operations per pixel in the one form that runs (hence constants folded
+  // into one factor and no division that only serves a parameter).  Scratch and step times with and without it: DESIGN 3.3 "Closed-form proxes:
+  // accuracy".
+  asm volatile("" : "+v"(q.p0), "+v"(q.p1));
+  const float g = q.p0, ax = fabsf(x);
   switch (kind) {
-    case LMC_EPROX_LAPLACE: return sgn(x) * fmaxf(fabsf(x) - g, 0.f);
-    case LMC_EPROX_UNCENTERED_LAPLACE: { const float d = x - q.p1; return q.p1 + sgn(d) * fmaxf(fabsf(d) - g, 0.f); }
+    case LMC_EPROX_LAPLACE: return soft(x, g);
+    // not mu + soft(x - mu, g): that rounds at the size of x - mu.  -((-x) - g) is x + g that keeps the sign of -0 at g = 0
+    case LMC_EPROX_UNCENTERED_LAPLACE: return x < q.p1 - g ? -((-x) - g) : (x > q.p1 + g ? x - g : q.p1);
     case LMC_EPROX_GAUSSIAN: return x / (2.f * g + 1.f);
-    case LMC_EPROX_GEN_GAUSSIAN_4_3: {
-      const float xi = sqrtf(x * x + 256.f * g * g * g / 729.f);
-      return x + 4.f * g / (3.f * cbrtf(2.f)) * (cbrtf(xi - x) - cbrtf(xi + x));
+    case LMC_EPROX_GEN_GAUSSIAN_4_3: {   // r = |p|^(1/3): r^3 + (4g/3) r = |x|, r = a - b with a^3 - b^3 = |x|, a b = 4g/9
+      const float xi = sqrtf(x * x + g * g * g * (256.f / 729.f)), a = cbrtf((xi + ax) * 0.5f), g49 = g * (4.f / 9.f);
+      const float b = a > 0.f ? g49 / a : 0.f, den = a * a + b * b + g49;
+      const float r = den > 0.f ? ax / den : 0.f, w = g * (4.f / 3.f) * r;
+      return copysignf(w < 0.5f * ax ? ax - w : r * r * r, x);      // |p| = |x| - (4g/3) r where that keeps half of |x| (exact at g = 0), else r^3
     }
-    case LMC_EPROX_GEN_GAUSSIAN_3_2:
-      return x + 9.f * g * g * sgn(x) * (1.f - sqrtf(1.f + 16.f * fabsf(x) / (9.f * g * g))) / 8.f;
-    case LMC_EPROX_GEN_GAUSSIAN_3: return sgn(x) * (sqrtf(1.f + 12.f * g * fabsf(x)) - 1.f) / (6.f * g);
-    case LMC_EPROX_GEN_GAUSSIAN_4: {
-      const float xi = sqrtf(x * x + 1.f / (27.f * g));
-      return cbrtf((xi + x) / (8.f * g)) - cbrtf((xi - x) / (8.f * g));
+    case LMC_EPROX_GEN_GAUSSIAN_3_2: {   // r = |p|^(1/2): r^2 + (3g/2) r = |x|
+      const float den = 3.f * g + sqrtf(9.f * g * g + 16.f * ax);
+      const float r = den > 0.f ? 4.f * ax / den : 0.f, w = 1.5f * g * r;
+      return copysignf(w < 0.5f * ax ? ax - w : r * r, x);
+    }
+    case LMC_EPROX_GEN_GAUSSIAN_3: return copysignf(2.f * ax / (sqrtf(1.f + 12.f * g * ax) + 1.f), x);
+    case LMC_EPROX_GEN_GAUSSIAN_4: {     // p = a - b, a b = 1/(12g), a^3 - b^3 = x/(4g); scaled by sqrt(27g): m = 12 g a^2, 1/m = 12 g b^2
+      const float s = sqrtf(27.f * g) * ax, e = sqrtf(s * s + 1.f) + s, m = cbrtf(e * e);
+      return x * (3.f / (1.f + m + 1.f / m));
     }
     case LMC_EPROX_HUBER: {
-      const float t = q.p1;
-      return fabsf(x) <= g * (2.f * t + 1.f) / sqrtf(2.f * t) ? x / (2.f * t + 1.f) : x - g * sqrtf(2.f * t) * sgn(x);
+      const float t2 = 2.f * q.p1, s = sqrtf(t2);
+      if (ax * s <= g * (t2 + 1.f)) return x / (t2 + 1.f);
+      // |x| - g sqrt(2t) keeps 1/(2t+1) of |x| just above the kink: sqrt(2t) = s + s_lo to twice the precision, and |x| - g s in ONE rounding (an
+      // explicit fmaf: a rounded product g s with its own correction term would be contracted into this fma by the compiler, and corrected twice).
+      // s_lo is of relative size eps: the approximate reciprocal does for it.
+      const float s_lo = fmaf(-s, s, t2) * (0.5f * __builtin_amdgcn_rcpf(s));
+      return copysignf(fmaf(-g, s, ax) - g * s_lo, x);
     }
     case LMC_EPROX_SMOOTHED_LAPLACE: {
-      const float ax = fabsf(x), u = g * ax - g * g - 1.f;
-      return sgn(x) * (u + sqrtf(u * u + 4.f * g * ax)) / (2.f * g);
+      const float u = g * (ax - g) - 1.f, r = sqrtf(u * u + 4.f * g * ax);
+      return copysignf((u < 0.f ? 2.f * ax : u + r) / (u < 0.f ? r - u : 2.f * g), x);      // one division for both roots' forms
     }
     case LMC_EPROX_EXP: return x >= g ? x - g : 0.f;
-    case LMC_EPROX_GAMMA: { const float d = x - q.p0; return (d + sqrtf(d * d + 4.f * q.p1)) * 0.5f; }
-    case LMC_EPROX_CHI: return (x + sqrtf(x * x + 8.f * q.p0)) * 0.25f;
-    case LMC_EPROX_UNIFORM: return fminf(fmaxf(x, -q.p0), q.p0);
+    case LMC_EPROX_GAMMA: { const float d = x - q.p0, r = sqrtf(d * d + 4.f * q.p1); return d < 0.f ? 2.f * q.p1 / (r - d) : (d + r) * 0.5f; }
+    case LMC_EPROX_CHI: { const float r = sqrtf(x * x + 8.f * g); return x < 0.f ? 2.f * g / (r - x) : (x + r) * 0.25f; }
+    case LMC_EPROX_UNIFORM: return fminf(fmaxf(x, -g), g);
     case LMC_EPROX_TRIANGULAR: {
       const float o1 = q.p0, o2 = q.p1;
-      if (x < 1.f / o1) return (x + o1 + sqrtf((x - o1) * (x - o1) + 4.f)) * 0.5f;
-      if (x > 1.f / o2) return (x + o2 + sqrtf((x - o2) * (x - o2) + 4.f)) * 0.5f;
+      // below 1/o1 < 0 both roots of p^2 - (x + o1) p + (x o1 - 1) are negative: the one nearer to zero through the product of the roots
+      if (x < 1.f / o1) return 2.f * fmaf(x, o1, -1.f) / ((x + o1) - sqrtf((x - o1) * (x - o1) + 4.f));
+      if (x > 1.f / o2) return ((x + o2) + sqrtf((x - o2) * (x - o2) + 4.f)) * 0.5f;
       return 0.f;
     }
-    case LMC_EPROX_LAPLACE_CONJ: {  // x - g * prox_laplace(x/g, 1/g)
-      const float z = x / g;
-      return x - g * (sgn(z) * fmaxf(fabsf(z) - 1.f / g, 0.f));
-    }
+    case LMC_EPROX_LAPLACE_CONJ: return fminf(fmaxf(x, -1.f), 1.f);   // x - g prox_laplace(x/g, 1/g) = x - soft(x, 1) for every g
   }
   return x;
 }

@@ -24,6 +24,13 @@ int fail(int code, const char* fmt, ...);
 
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Closed-form proxes: the parameters that are weights, scales or bounds must be >= 0 (a negative one has no prox, and the closed forms take square roots of
+// it); 0 is allowed (the prox of the zero function is the identity).  NaN fails too.  Bit i of the table = parameter i is such a parameter.
+inline bool eprox_params_ok(int kind, float p0, float p1) {
+  static const unsigned char nonneg[] = {1, 1, 1, 1, 1, 1, 1, 3, 1, 1, 3, 1, 1, 0, 0};
+  return (!(nonneg[kind] & 1) || p0 >= 0.f) && (!(nonneg[kind] & 2) || p1 >= 0.f);
+}
+
 // Validated, self-contained copy of an lmc_problem.
 struct Problem {
   int H = 0, W = 0;

@@ -63,6 +63,8 @@ int load_problem(const lmc_problem* p, Problem& q) {
       if (p->eprox_kind < 0 || p->eprox_kind > LMC_EPROX_LAPLACE_CONJ) return fail(LMC_E_INVALID, "unknown eprox_kind %d", p->eprox_kind);
       if (p->eprox_scale_mask < 0 || p->eprox_scale_mask > 3) return fail(LMC_E_INVALID, "eprox_scale_mask must be 0..3");
       if (!(p->eprox_p0 == p->eprox_p0) || !(p->eprox_p1 == p->eprox_p1)) return fail(LMC_E_INVALID, "eprox parameter is NaN");
+      if (!eprox_params_ok(p->eprox_kind, p->eprox_p0, p->eprox_p1))
+        return fail(LMC_E_INVALID, "eprox_kind %d: negative weight %g, %g", p->eprox_kind, (double)p->eprox_p0, (double)p->eprox_p1);
       q.eprox_kind = p->eprox_kind; q.eprox_mask = p->eprox_scale_mask; q.eprox_p0 = p->eprox_p0; q.eprox_p1 = p->eprox_p1;
       break;
     case LMC_PRIOR_HAAR_L1:

@@ -15,6 +15,7 @@ from . import _capi, _dev
 
 
 def _run(kind, x, *params):
+    _capi.check_eprox_params(kind, params)            # a negative weight: ValueError
     xt = _dev.to_dev(x)
     out = torch.empty_like(xt)
     par = np.asarray(params, dtype=np.float32)

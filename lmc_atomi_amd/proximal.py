@@ -416,6 +416,7 @@ class ElementwiseProx(ProxOperator):
         self.scaled = tuple(int(i) for i in scaled)
         if any(i < 0 or i >= n for i in self.scaled):
             raise ValueError("scaled: indices of the parameters that are multiplied by tau")
+        _capi.check_eprox_params(self.code, self.params)      # weights >= 0; 0 is the identity
 
     def _scaled_params(self, tau):
         return [v * float(tau) if i in self.scaled else v for i, v in enumerate(self.params)]
@@ -431,6 +432,7 @@ class ElementwiseProx(ProxOperator):
     def prox(self, x, tau):
         xt = _dev.to_dev(x)
         out = torch.empty_like(xt)
+        _capi.check_eprox_params(self.code, self._scaled_params(tau))
         par = np.asarray(self._scaled_params(tau), dtype=np.float32)
         _dev.run(xt, "lmc_prox_elementwise", self.code, _dev.ptr(xt), _dev.ptr(out), xt.numel(), _dev.fptr(par), par.size)
         return _dev.like_input(out, x)
