@@ -241,6 +241,11 @@ int lmc_haar_l1_prox(const float* x_dev, float* out_dev, int64_t n_img, int32_t 
  * (integer division).  1 <= ph <= H, 1 <= pw <= W, W <= 8192.  out_dev: n_img*ph*pw floats. */
 int lmc_chain_probes(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t ph, int32_t pw, void* stream);
 
+/* Stateless, operator level: ADDS the pixel histogram of x[C][H][W] into counts_dev [(n_bins+2)*H*W] uint64 (rows as documented at
+ * lmc_sampler_set_histogram; 1 <= n_bins <= 62; lo_dev, scale_dev: [H*W] floats). */
+int lmc_pixel_histogram(const float* x_dev, int64_t C, int32_t H, int32_t W, int32_t n_bins,
+                        const float* lo_dev, const float* scale_dev, uint64_t* counts_dev, void* stream);
+
 /* Per-pixel projection of the stacked field y[2][H][W] onto the l2 ball (isotropic != 0) or the
  * box (isotropic == 0) of radius `radius`: L21.proxdual / L1.proxdual (algs.py:436,448). */
 int lmc_dual_project(const float* y_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W,
@@ -329,6 +334,18 @@ int lmc_sampler_reset_moments(lmc_sampler* s, void* stream);
 int lmc_sampler_set_moment_scales(lmc_sampler* s, int32_t n_scales, const int32_t* scales);
 /* sum_dev, sumsq_dev: [ceil(H/scale)][ceil(W/scale)] double (device, either nullable).  A scale that is not enabled: LMC_E_INVALID. */
 int lmc_sampler_get_block_moments(lmc_sampler* s, int32_t scale, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream);
+/* Pixel histograms: over the same kept samples as the pixel moments (the same count) the library keeps, per pixel p, n_bins + 2
+ * unsigned 64-bit counters.  A sample v (fp32) is classified in fp32 by t = (v - lo[p]) * scale[p] -- one subtraction, then one
+ * multiplication; scale is bins per unit, n_bins / (hi - lo) -- into row 0 (t < 0), row 1 + floor(t) (0 <= t < n_bins) or row
+ * n_bins + 1 (everything else: t >= n_bins, +inf, NaN), so the rows of a pixel always sum to count.  Integer atomics: the counts do
+ * not depend on launch shapes or orders.  The histogram is a launch of its own after the moment reduction of the same iterate; a
+ * sampler without one launches exactly what it launches without this call.
+ * n_bins = 0 turns it off.  Copies lo / scale ([H*W] floats, device) into the handle.  Needs cfg.moments != 0 and count == 0
+ * (else LMC_E_STATE); n_bins outside 0 .. 62 or a NULL array with n_bins > 0: LMC_E_INVALID.  lmc_sampler_reset_moments zeroes
+ * the counts too. */
+int lmc_sampler_set_histogram(lmc_sampler* s, int32_t n_bins, const float* lo_dev, const float* scale_dev);
+/* counts_dev: [(n_bins+2)*H*W] uint64 (device, nullable).  A handle without a histogram: LMC_E_INVALID. */
+int lmc_sampler_get_histogram(lmc_sampler* s, uint64_t* counts_dev, uint64_t* count, void* stream);
 /* per-chain energies f(x_c), g(x_c) of the current state (device double [n_chains]) */
 int lmc_sampler_energies(lmc_sampler* s, double* f_out_dev, double* g_out_dev, void* stream);
 /* the noise field xi[n_chains][H][W] the sampler draws at `iteration` (parity rung R3) */
@@ -370,6 +387,8 @@ int lmc_rccl_comm_destroy(void* comm);
 int lmc_allreduce_moments(lmc_sampler* s, void* rccl_comm, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream);
 /* as lmc_allreduce_moments, for ONE scale; rccl_comm NULL = a job of one rank (plain copy).  Packs through the same code as the pixel collective. */
 int lmc_allreduce_block_moments(lmc_sampler* s, void* rccl_comm, int32_t scale, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream);
+/* one ncclAllReduce(ncclUint64, sum) of counts + count; rccl_comm NULL = a job of one rank (plain copy).  A handle without a histogram: LMC_E_INVALID. */
+int lmc_allreduce_histogram(lmc_sampler* s, void* rccl_comm, uint64_t* counts_dev, uint64_t* count, void* stream);
 
 /* ---- ULPDA sampler (replaces algs.UnadjustedLangevinPrimalDual, algs.py:295-474) --------------------
  *   x    <- prox_{tau f}(x - tau (A^T y + z)) + sqrt(2 tau) xi      (algs.py:440/446)

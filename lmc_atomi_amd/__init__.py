@@ -8,13 +8,13 @@ from .operators import Convolve2D, Diagonal, Gradient, Identity, LinearOperator
 from .proximal import (L1, L2, L21, TV, L2_ncvx_tv, WaveletL1, ProxOperator, fgp_betas, ElementwiseProx, Laplace, UncenteredLaplace, Gaussian,
                        GenGaussian, Huber, SmoothedLaplace)
 from .algs import (MYULAResult, MYULASampler, MYMALASampler, MoreauYosidaUnadjustedLangevin, MoreauYosidaMetropolisAdjustedLangevin, ULPDASampler,
-                   UnadjustedLangevinPrimalDual, block_mean_var, mean_var_from_moments,
+                   UnadjustedLangevinPrimalDual, block_mean_var, hist_exceedance, hist_quantiles, mean_var_from_moments, pixel_histogram,
                    set_step_variant, set_cg_tolerance)
 
 from . import diagnostics, metrics
 from .diagnostics import ChainTrace, chain_probes, ess, split_rhat
 from .metrics import MetricsCallback, mean_squared_error, peak_signal_noise_ratio, signal_noise_ratio
-from .sharding import (allgather_chains, allreduce_moments, allreduce_sampler_block_moments, allreduce_sampler_moments, chain_shard, posterior_mean_var, rccl_comm,
+from .sharding import (allgather_chains, allreduce_moments, allreduce_sampler_block_moments, allreduce_sampler_histogram, allreduce_sampler_moments, chain_shard, posterior_mean_var, rccl_comm,
                        sharded_myula)
 
 __all__ = [
@@ -25,5 +25,6 @@ __all__ = [
     "L1", "L2", "L21", "TV", "L2_ncvx_tv", "WaveletL1", "ProxOperator", "fgp_betas",
     "MYULASampler", "MYMALASampler", "MoreauYosidaMetropolisAdjustedLangevin", "MYULAResult", "MoreauYosidaUnadjustedLangevin", "ULPDASampler", "UnadjustedLangevinPrimalDual", "mean_var_from_moments", "set_step_variant", "set_cg_tolerance",
     "block_mean_var", "allreduce_sampler_block_moments",
+    "pixel_histogram", "hist_quantiles", "hist_exceedance", "allreduce_sampler_histogram",
 ]
 __version__ = "0.2.0"

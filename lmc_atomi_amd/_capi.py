@@ -151,6 +151,8 @@ _SIGNATURES = {
     "lmc_sampler_reset_moments": (C.c_int, [_P, _P]),
     "lmc_sampler_set_moment_scales": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32)]),
     "lmc_sampler_get_block_moments": (C.c_int, [_P, C.c_int32, _P, _P, C.POINTER(C.c_uint64), _P]),
+    "lmc_sampler_set_histogram": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "lmc_sampler_get_histogram": (C.c_int, [_P, _P, C.POINTER(C.c_uint64), _P]),
     "lmc_sampler_energies": (C.c_int, [_P, _P, _P, _P]),
     "lmc_sampler_noise": (C.c_int, [_P, C.c_int64, _P, _P]),
     "lmc_sampler_enable_timing": (C.c_int, [_P, C.c_int32]),
@@ -168,6 +170,8 @@ _SIGNATURES = {
     "lmc_rccl_comm_destroy": (C.c_int, [_P]),
     "lmc_allreduce_moments": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_uint64), _P]),
     "lmc_allreduce_block_moments": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.POINTER(C.c_uint64), _P]),
+    "lmc_allreduce_histogram": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64), _P]),
+    "lmc_pixel_histogram": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
 }
 RCCL_UNIQUE_ID_BYTES = 128
 VARIANTS = ["auto", "tile", "(removed)", "split", "point", "block", "rows", "pipe", "pipe2"]

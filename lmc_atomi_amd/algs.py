@@ -70,6 +70,135 @@ def block_mean_var(S1, S2, count, scale, dims):
     return mean, var
 
 
+HIST_MAX_BINS = 62
+
+
+def _host_array(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _hist_arrays(bins, lo, hi, dims):
+    """``(B, lo, scale)`` of a histogram of ``B`` bins over ``[lo, hi)`` per pixel: fp32 ``[H, W]`` numpy arrays, ``scale`` = bins per unit
+    formed once as ``float32(B) / (float32(hi) - float32(lo))``.  Raises ``ValueError`` for what no histogram can be made of."""
+    B = int(bins)
+    if not 1 <= B <= HIST_MAX_BINS:
+        raise ValueError(f"hist_bins must be 1 .. {HIST_MAX_BINS}, got {B}")
+    shape = (int(dims[0]), int(dims[1]))
+    try:
+        lo32 = np.ascontiguousarray(np.broadcast_to(_host_array(lo).astype(np.float32), shape))
+        hi32 = np.ascontiguousarray(np.broadcast_to(_host_array(hi).astype(np.float32), shape))
+    except ValueError:
+        raise ValueError(f"hist_range: lo and hi must be scalars or arrays of the image shape {shape}") from None
+    if not (np.isfinite(lo32).all() and np.isfinite(hi32).all()):
+        raise ValueError("hist_range: lo and hi must be finite at every pixel")
+    if (hi32 <= lo32).any():
+        raise ValueError("hist_range: hi must be above lo at every pixel (in fp32)")
+    scale = np.float32(B) / (hi32 - lo32)
+    if not np.isfinite(scale).all():
+        raise ValueError("hist_range: hi - lo is too small for fp32 at some pixel")
+    return B, lo32, scale.astype(np.float32)
+
+
+def _check_histogram(hist_bins, hist_range, moments, dims):
+    """``None`` or ``(B, lo, scale)`` of the histogram a sampler is asked to keep; raises before any device call."""
+    if hist_bins is None and hist_range is None:
+        return None
+    if hist_bins is None or hist_range is None:
+        raise ValueError("hist_bins and hist_range go together: the bins of a pixel histogram need their range (lo, hi)")
+    if not moments:
+        raise ValueError("hist_bins needs moments=True: the histogram is accumulated over the kept samples of the pixel moments")
+    if not isinstance(hist_range, (tuple, list)) or len(hist_range) != 2:
+        raise ValueError("hist_range must be (lo, hi), each a scalar or an [H, W] array")
+    return _hist_arrays(hist_bins, hist_range[0], hist_range[1], dims)
+
+
+def _hist_host(counts, lo, scale):
+    c = _host_array(counts).astype(np.int64)
+    if c.ndim != 3 or c.shape[0] < 3:
+        raise ValueError("counts must be [B + 2, H, W]")
+    lo64 = np.broadcast_to(_host_array(lo).astype(np.float64), c.shape[1:])
+    sc64 = np.broadcast_to(_host_array(scale).astype(np.float64), c.shape[1:])
+    return c, lo64, sc64
+
+
+def hist_quantiles(counts, lo, scale, q):
+    """Pixel-wise quantiles ``[len(q), H, W]`` (float64) from the counters ``[B + 2, H, W]`` of a pixel histogram (:meth:`MYULASampler.histogram`,
+    :func:`pixel_histogram`) with its ``lo`` and ``scale`` (bins per unit).  Per pixel, with ``n`` the sum of the rows, ``r = q n``, ``cum`` the
+    running sum over the rows and ``j`` the first row with ``cum_j >= r``: ``lo + (j - 1 + (r - cum_{j-1}) / counts_j) / scale``, i.e. linear inside
+    the bin that holds the quantile.  ``j = 0`` gives ``-inf`` and ``j = B + 1`` gives ``+inf``: a quantile outside the chosen range is reported as
+    infinite, not clamped -- the sign to widen the range.  By the same rule ``q = 0`` is ``-inf`` everywhere (row 0 already has ``cum_0 >= 0``): ask for a
+    small positive ``q`` instead.  A pixel without samples gives NaN.  torch in, torch out (on the device of ``counts``);
+    the arithmetic is on the host."""
+    c, lo64, sc64 = _hist_host(counts, lo, scale)
+    B = c.shape[0] - 2
+    qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if qs.ndim != 1 or ((qs < 0) | (qs > 1)).any():
+        raise ValueError("q must be probabilities in [0, 1]")
+    cum = np.cumsum(c, axis=0)
+    n = cum[-1]
+    out = np.empty((len(qs),) + c.shape[1:], dtype=np.float64)
+    for i, qq in enumerate(qs):
+        r = qq * n.astype(np.float64)
+        j = (cum < r[None]).sum(axis=0)                               # the first row with cum_j >= r
+        jm = np.clip(j, 1, B)
+        below = np.take_along_axis(cum, (jm - 1)[None], axis=0)[0]
+        inbin = np.take_along_axis(c, jm[None], axis=0)[0]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            v = lo64 + (jm - 1 + (r - below) / inbin) / sc64
+        v = np.where(j == 0, -np.inf, np.where(j == B + 1, np.inf, v))
+        out[i] = np.where(n == 0, np.nan, v)
+    return torch.from_numpy(out).to(counts.device) if isinstance(counts, torch.Tensor) else out
+
+
+def hist_exceedance(counts, lo, scale, t):
+    """Pixel-wise exceedance probability from the counters of a pixel histogram: the fraction of the samples in the rows from the first row
+    whose lower edge ``lo + (j - 1) / scale`` is at or above ``t`` (a scalar or ``[H, W]``) upwards, the row above the range included.  The
+    resolution is the bin width ``1 / scale``: it is P(x >= edge) for the first bin edge at or above ``t`` -- exact for ``t`` on an edge, and
+    otherwise below P(x >= t) by at most the mass of the bin ``t`` lies in; for ``t`` below ``lo`` (``-inf`` included) the edge is ``lo`` itself, and
+    ``t = +inf`` gives 0.  A NaN in ``t`` raises ``ValueError``.  ``[H, W]`` float64; torch in, torch out."""
+    c, lo64, sc64 = _hist_host(counts, lo, scale)
+    B = c.shape[0] - 2
+    t64 = np.broadcast_to(_host_array(t).astype(np.float64), c.shape[1:])
+    if np.isnan(t64).any():
+        raise ValueError("hist_exceedance: t must not be NaN")
+    first = np.clip(1 + np.ceil((t64 - lo64) * sc64), 1, B + 2).astype(np.int64)
+    rows = np.arange(B + 2)[:, None, None]
+    n = c.sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = np.where(rows >= first[None], c, 0).sum(axis=0) / n.astype(np.float64)
+    return torch.from_numpy(out).to(counts.device) if isinstance(counts, torch.Tensor) else out
+
+
+def pixel_histogram(x, bins, lo, hi, out=None):
+    """Pixel-wise histogram of the images ``x`` (``[C, H, W]``): counters ``[bins + 2, H, W]`` (``torch.int64`` on the device) over ``bins`` equal
+    bins of ``[lo, hi)`` (scalars or ``[H, W]`` arrays), row 0 below the range and row ``bins + 1`` at or above it (NaN included).  Stateless
+    (``lmc_pixel_histogram``); with ``out`` it ADDS into that tensor and returns it."""
+    xt = _dev.to_dev(x)
+    if xt.dim() != 3:
+        raise ValueError("x must be [C, H, W]")
+    Cn, H, W = (int(v) for v in xt.shape)
+    B, lo32, sc32 = _hist_arrays(bins, lo, hi, (H, W))
+    if out is None:
+        out = torch.zeros((B + 2, H, W), dtype=torch.int64, device=xt.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.int64 and tuple(out.shape) == (B + 2, H, W) and out.is_contiguous()
+              and out.device == xt.device):
+        raise ValueError(f"out must be a contiguous torch.int64 tensor {(B + 2, H, W)} on {xt.device}")
+    lo_d, sc_d = _dev.to_dev(lo32, xt.device), _dev.to_dev(sc32, xt.device)
+    _dev.run(xt, "lmc_pixel_histogram", _dev.ptr(xt), Cn, H, W, B, _dev.ptr(lo_d), _dev.ptr(sc_d), _dev.ptr(out))
+    torch.cuda.current_stream(xt.device).synchronize()          # lo_d / sc_d live until the launch is done
+    return out
+
+
+def _hist_summaries(smp, quantiles):
+    """``(counts, lo, scale, {q: tensor [H, W]})`` of a sampler's histogram; Nones and an empty dict without one."""
+    if smp.hist_bins is None:
+        return None, None, None, {}
+    counts, _ = smp.histogram()
+    qs = tuple(float(v) for v in (quantiles or ()))
+    vals = hist_quantiles(counts, smp.hist_lo, smp.hist_scale, qs) if qs else ()
+    return counts, smp.hist_lo, smp.hist_scale, {qv: vals[i] for i, qv in enumerate(qs)}
+
+
 def _scale_summaries(smp):
     """``({scale: mean}, {scale: std})`` of the block means of every scale the sampler keeps."""
     means, stds = {}, {}
@@ -90,12 +219,16 @@ class MYULASampler:
 
     def __init__(self, proxf, proxg, dims, n_chains=1, tau=None, gamma=0.1, epsg=1.0, seed=0,
                  chain_offset=0, noise="philox", moments=False, burn_in=0, thin=1, device=None, variant=None, tv_warm=None, policy=None,
-                 moment_scales=None):
+                 moment_scales=None, hist_bins=None, hist_range=None):
         """``variant``: step-kernel variant of THIS sampler ('auto' | 'tile' | 'split' | 'point' | 'block' | 'rows' | 'pipe' | 'pipe2'; None = the
         library default, :func:`set_step_variant`).  ``tv_warm``: carry the TV dual between iterations (see :class:`TV`; None = as
         ``proxg.warm`` says).  ``moment_scales``: block sizes out of (2, 4, 8, 16) whose block sums get second moments of their own over the kept samples
-        (:meth:`block_moments`; needs ``moments=True``).  Every call on the sampler runs on ``device`` whatever the current device is."""
+        (:meth:`block_moments`; needs ``moments=True``).  ``hist_bins`` (1 .. 62) with ``hist_range=(lo, hi)``, each a scalar or an ``[H, W]`` array:
+        a histogram per pixel over the kept samples (:meth:`histogram`, :func:`hist_quantiles`; needs ``moments=True``) -- a short pilot run gives
+        ``mean`` and ``var``, and ``(mean - 5 sqrt(var), mean + 5 sqrt(var))`` is then a range whose 62 bins resolve 0.16 standard deviations.
+        Every call on the sampler runs on ``device`` whatever the current device is."""
         scales = _check_moment_scales(moment_scales, moments)
+        hist = _check_histogram(hist_bins, hist_range, moments, dims)
         if tau is None:
             raise NotImplementedError("tau=None (backtracking) is not implemented by the reference loop either")
         self.dims = (int(dims[0]), int(dims[1]))
@@ -130,9 +263,22 @@ class MYULASampler:
         with torch.cuda.device(self.device):
             _capi.check(getattr(_dev.lib(), self._create_fn)(C.byref(cfg), C.byref(self._h)))
         self._set_moment_scales(scales)
+        self._set_histogram(hist)
 
     _create_fn = "lmc_myula_create"
     moment_scales = ()
+    hist_bins = hist_lo = hist_scale = None
+
+    def _set_histogram(self, hist):
+        """``hist``: None or (B, lo, scale) as :func:`_check_histogram` returns them; the sampler keeps fp32 device copies of lo and scale."""
+        if hist is None:
+            return
+        B, lo32, sc32 = hist
+        lo_d, sc_d = _dev.to_dev(lo32, self.device), _dev.to_dev(sc32, self.device)
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()
+            _capi.check(_dev.lib().lmc_sampler_set_histogram(self._h, B, _dev.ptr(lo_d), _dev.ptr(sc_d)))
+        self.hist_bins, self.hist_lo, self.hist_scale = B, lo_d, sc_d
 
     def _set_moment_scales(self, scales):
         if scales:
@@ -286,6 +432,27 @@ class MYULASampler:
                                                            _dev.stream_ptr(self.device)))
         return S1, S2, int(cnt.value)
 
+    def histogram(self):
+        """(counts ``[hist_bins + 2, H, W]`` ``torch.int64``, count): the pixel histogram over chains and kept iterations.  Row 0 counts the
+        samples below ``lo``, row ``1 + k`` those of bin ``k``, the last row everything at or above ``hi`` (NaN included); the rows of a pixel
+        sum to ``count``."""
+        if self.hist_bins is None:
+            raise ValueError("the sampler keeps no histogram (hist_bins=, hist_range=)")
+        counts = torch.empty((self.hist_bins + 2,) + self.dims, dtype=torch.int64, device=self.device)
+        cnt = C.c_uint64()
+        _capi.check(_dev.lib().lmc_sampler_get_histogram(self._h, _dev.ptr(counts), C.byref(cnt), _dev.stream_ptr(self.device)))
+        return counts, int(cnt.value)
+
+    def allreduce_histogram(self, rccl_comm):
+        """Job-wide :meth:`histogram`: ONE ``ncclAllReduce`` of the integer counters through the C ABI (``lmc_allreduce_histogram``)."""
+        if self.hist_bins is None:
+            raise ValueError("the sampler keeps no histogram (hist_bins=, hist_range=)")
+        counts = torch.empty((self.hist_bins + 2,) + self.dims, dtype=torch.int64, device=self.device)
+        cnt = C.c_uint64()
+        comm = rccl_comm if isinstance(rccl_comm, C.c_void_p) else C.c_void_p(int(rccl_comm or 0))
+        _capi.check(_dev.lib().lmc_allreduce_histogram(self._h, comm, _dev.ptr(counts), C.byref(cnt), _dev.stream_ptr(self.device)))
+        return counts, int(cnt.value)
+
     def allreduce_moments(self, rccl_comm):
         """Job-wide (sum, sumsq, count): ONE ``ncclAllReduce`` (RCCL over xGMI) of the packed accumulators through the C ABI
         (``lmc_allreduce_moments``).  ``rccl_comm``: an ``ncclComm_t`` as an integer / ``c_void_p`` (``None`` or 0 = a job of one rank)."""
@@ -305,10 +472,11 @@ class ULPDASampler(MYULASampler):
 
     def __init__(self, proxf, proxg, A, dims, n_chains=1, tau=None, mu=None, theta=1.0, gfirst=True, z=None, seed=0,
                  chain_offset=0, noise="philox", moments=False, burn_in=0, thin=1, device=None, variant=None, implicit_tol=None,
-                 moment_scales=None):
+                 moment_scales=None, hist_bins=None, hist_range=None):
         from .operators import Gradient
         from .proximal import L1, L21
         scales = _check_moment_scales(moment_scales, moments)
+        hist = _check_histogram(hist_bins, hist_range, moments, dims)
         if not isinstance(A, Gradient):
             raise NotImplementedError("ULPDA on the GPU supports A = Gradient (the reference's operator, prox_lmc_deconv.py:98)")
         if isinstance(proxg, L21):
@@ -350,6 +518,7 @@ class ULPDASampler(MYULASampler):
         with torch.cuda.device(self.device):
             _capi.check(_dev.lib().lmc_ulpda_create(C.byref(cfg), C.byref(self._h)))
         self._set_moment_scales(scales)
+        self._set_histogram(hist)
 
     def set_steps(self, tau, mu):
         _capi.check(_dev.lib().lmc_sampler_set_steps(self._h, float(tau), float(mu)))
@@ -372,14 +541,15 @@ class ULPDASampler(MYULASampler):
 
 def UnadjustedLangevinPrimalDual(proxf, proxg, A, x0, tau, mu, y0=None, z=None, theta=1., niter=10, seed=0, gfirst=True,
                                  callback=None, callbacky=False, returny=False, show=False, *, n_chains=None, dims=None,
-                                 rng="philox", chain_offset=0, burn_in=0, thin=1, device=None, diagnostics=None, moment_scales=None):
+                                 rng="philox", chain_offset=0, burn_in=0, thin=1, device=None, diagnostics=None, moment_scales=None,
+                                 hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95)):
     r"""Unadjusted Langevin Primal-Dual algorithm (ULPDA) -- drop-in for algs.py:295-474.
 
     Reference form (``n_chains is None``): one chain, returns ``np.ndarray (niter, n)`` (and the duals ``(niter, 2n)`` with
     ``returny``), ``callback(x)`` / ``callback(x, y)`` every iteration, ``tau`` / ``mu`` scalars or per-iteration arrays
     (algs.py:402-408).  ``rng='pcg64'`` injects the reference's noise stream.  Many-chain form: :class:`MYULAResult`
     (``diagnostics=(ph, pw)`` or ``True``: split R-hat / ESS across chains as in :func:`MoreauYosidaUnadjustedLangevin`;
-    ``moment_scales``: as there).
+    ``moment_scales``, ``hist_bins`` / ``hist_range`` / ``quantiles``: as there).
     """
     if dims is None:
         dims = getattr(A, "dims", None) or getattr(proxf, "dims", None)
@@ -394,11 +564,14 @@ def UnadjustedLangevinPrimalDual(proxf, proxg, A, x0, tau, mu, y0=None, z=None, 
         raise ValueError("rng='pcg64' reproduces the reference's single chain; use n_chains=None")
     if moment_scales and not many:
         raise ValueError("moment_scales belongs to the many-chain form (n_chains=C): the reference form keeps every iterate instead")
+    if (hist_bins is not None or hist_range is not None) and not many:
+        raise ValueError("hist_bins / hist_range belong to the many-chain form (n_chains=C): the reference form keeps every iterate instead")
     taus = np.full(niter, tau, dtype=np.float64) if np.isscalar(tau) else np.asarray(tau, dtype=np.float64)
     mus = np.full(niter, mu, dtype=np.float64) if np.isscalar(mu) else np.asarray(mu, dtype=np.float64)
     smp = ULPDASampler(proxf, proxg, A, dims, n_chains=C_, tau=taus[0], mu=mus[0], theta=theta, gfirst=gfirst, z=z,
                        seed=seed, chain_offset=chain_offset, noise="injected" if rng == "pcg64" else "philox",
-                       moments=many, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales)
+                       moments=many, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
+                       hist_bins=hist_bins, hist_range=hist_range)
     try:
         smp.set_state(x0)
         if y0 is not None:
@@ -455,7 +628,8 @@ def UnadjustedLangevinPrimalDual(proxf, proxg, A, x0, tau, mu, y0=None, z=None, 
         scale_mean, scale_std = _scale_summaries(smp)
         diag = tracer.summary() if tracer is not None and len(tracer) else None
         return MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, diagnostics=diag,
-                           trace=tracer.trace() if diag is not None else None, scale_mean=scale_mean, scale_std=scale_std)
+                           trace=tracer.trace() if diag is not None else None, scale_mean=scale_mean, scale_std=scale_std,
+                           hist=_hist_summaries(smp, quantiles))
     finally:
         smp.close()
 
@@ -470,8 +644,11 @@ def mean_var_from_moments(s1, s2, count):
 class MYULAResult:
     """Return value of the many-chain form of :func:`MoreauYosidaUnadjustedLangevin`."""
 
-    def __init__(self, state, mean, var, count, energy_f, energy_g, elapsed, diagnostics=None, trace=None, scale_mean=None, scale_std=None):
+    def __init__(self, state, mean, var, count, energy_f, energy_g, elapsed, diagnostics=None, trace=None, scale_mean=None, scale_std=None, hist=None):
         self.state, self.mean, self.var, self.count = state, mean, var, count
+        # hist_bins / hist_range: the pixel histogram [B + 2, H, W] int64 with its lo and scale (None when not asked), and {q: tensor [H, W]} of
+        # the quantiles asked for (hist_quantiles; empty without a histogram)
+        self.hist, self.hist_lo, self.hist_scale, self.quantiles = hist if hist is not None else (None, None, None, {})
         # moment_scales: posterior mean and standard deviation of the image averaged over s x s blocks, {s: tensor [ceil(H/s), ceil(W/s)]}; empty when not asked
         self.scale_mean, self.scale_std = dict(scale_mean or {}), dict(scale_std or {})
         self.energy_f, self.energy_g, self.elapsed = energy_f, energy_g, elapsed
@@ -480,7 +657,8 @@ class MYULAResult:
 
 def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1., niter=10, seed=0,
                                    callback=None, show=False, *, n_chains=None, dims=None, rng="philox",
-                                   chain_offset=0, burn_in=0, thin=1, device=None, diagnostics=None, moment_scales=None):
+                                   chain_offset=0, burn_in=0, thin=1, device=None, diagnostics=None, moment_scales=None,
+                                   hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95)):
     r"""Moreau--Yosida Unadjusted Langevin algorithm (MYULA) -- drop-in for algs.py:477-587.
 
     .. math::
@@ -499,7 +677,11 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
     at every kept iteration, a ph x pw grid of block means and the energies of every chain and returns split R-hat and
     effective sample size across chains in ``result.diagnostics`` (:mod:`lmc_atomi_amd.diagnostics`).  ``moment_scales=(2, 4, 8, 16)`` (any
     subset) additionally returns the posterior mean and standard deviation of the image averaged over s x s blocks -- uncertainty at
-    several scales -- in ``result.scale_mean[s]`` / ``result.scale_std[s]``.
+    several scales -- in ``result.scale_mean[s]`` / ``result.scale_std[s]``.  ``hist_bins=B`` (1 .. 62) with ``hist_range=(lo, hi)`` (scalars or
+    ``[H, W]`` arrays, e.g. mean -+ 5 std of a pilot run) keeps a histogram per pixel over the kept samples: ``result.hist`` (counters
+    ``[B + 2, H, W]``), ``result.hist_lo`` / ``result.hist_scale``, and the pixel-wise quantile maps ``result.quantiles[q]`` for every ``q`` in
+    ``quantiles`` -- credible intervals that, unlike mean -+ 2 std, follow the skew of a TV posterior next to edges (:func:`hist_quantiles`,
+    :func:`hist_exceedance`).
     """
     if dims is None:
         dims = getattr(proxf, "dims", None) or getattr(proxg, "dims", None)
@@ -514,9 +696,12 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
         raise ValueError("rng='pcg64' reproduces the reference's single chain; use n_chains=None")
     if moment_scales and not many:
         raise ValueError("moment_scales belongs to the many-chain form (n_chains=C): the reference form keeps every iterate instead")
+    if (hist_bins is not None or hist_range is not None) and not many:
+        raise ValueError("hist_bins / hist_range belong to the many-chain form (n_chains=C): the reference form keeps every iterate instead")
     smp = MYULASampler(proxf, proxg, dims, n_chains=C_, tau=tau, gamma=gamma, epsg=epsg, seed=seed,
                        chain_offset=chain_offset, noise="injected" if rng == "pcg64" else "philox",
-                       moments=many, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales)
+                       moments=many, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
+                       hist_bins=hist_bins, hist_range=hist_range)
     try:
         smp.set_state(x0)
         tstart = time.time()
@@ -581,7 +766,8 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
         scale_mean, scale_std = _scale_summaries(smp)
         diag = tracer.summary() if tracer is not None and len(tracer) else None
         return MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, diagnostics=diag,
-                           trace=tracer.trace() if diag is not None else None, scale_mean=scale_mean, scale_std=scale_std)
+                           trace=tracer.trace() if diag is not None else None, scale_mean=scale_mean, scale_std=scale_std,
+                           hist=_hist_summaries(smp, quantiles))
     finally:
         smp.close()
 
@@ -606,16 +792,19 @@ class MYMALASampler(MYULASampler):
 
 
 def MoreauYosidaMetropolisAdjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1., niter=10, seed=0, callback=None, *,
-                                           n_chains=1, dims=None, chain_offset=0, burn_in=0, thin=1, device=None, moment_scales=None):
+                                           n_chains=1, dims=None, chain_offset=0, burn_in=0, thin=1, device=None, moment_scales=None,
+                                           hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95)):
     """MYMALA at image scale for ``n_chains`` chains (the accept / reject of prox_lmc.py:134-158 around the MYULA move of
     algs.py:569): returns a :class:`MYULAResult` with two extra attributes, ``accepted`` (per-chain counts) and
-    ``acceptance_rate``.  ``callback(state)`` after every iteration if given.  ``moment_scales``: as in :func:`MoreauYosidaUnadjustedLangevin`."""
+    ``acceptance_rate``.  ``callback(state)`` after every iteration if given.  ``moment_scales``, ``hist_bins`` / ``hist_range`` /
+    ``quantiles``: as in :func:`MoreauYosidaUnadjustedLangevin`."""
     if dims is None:
         dims = getattr(proxf, "dims", None) or getattr(proxg, "dims", None)
     if dims is None:
         raise ValueError("image shape unknown: pass dims=(ny, nx)")
     smp = MYMALASampler(proxf, proxg, dims, n_chains=int(n_chains), tau=tau, gamma=gamma, epsg=epsg, seed=seed,
-                        chain_offset=chain_offset, moments=True, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales)
+                        chain_offset=chain_offset, moments=True, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
+                        hist_bins=hist_bins, hist_range=hist_range)
     try:
         smp.set_state(x0)
         tstart = time.time()
@@ -632,7 +821,8 @@ def MoreauYosidaMetropolisAdjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1,
         torch.cuda.current_stream().synchronize()
         mean, var = mean_var_from_moments(s1, s2, max(cnt, 1))
         scale_mean, scale_std = _scale_summaries(smp)
-        res = MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, scale_mean=scale_mean, scale_std=scale_std)
+        res = MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, scale_mean=scale_mean, scale_std=scale_std,
+                          hist=_hist_summaries(smp, quantiles))
         res.accepted = acc
         res.acceptance_rate = acc.double() / max(niter, 1)
         return res

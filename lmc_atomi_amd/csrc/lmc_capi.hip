@@ -266,6 +266,14 @@ int lmc_chain_probes(const float* x_dev, float* out_dev, int64_t n_img, int32_t 
   return LMC_OK;
 }
 
+int lmc_pixel_histogram(const float* x_dev, int64_t C, int32_t H, int32_t W, int32_t n_bins, const float* lo_dev, const float* scale_dev,
+                        uint64_t* counts_dev, void* stream) {
+  if (!x_dev || !lo_dev || !scale_dev || !counts_dev || C < 1 || H < 1 || W < 1) return fail(LMC_E_INVALID, "bad arguments");
+  if (n_bins < 1 || n_bins > 62) return fail(LMC_E_INVALID, "n_bins must be 1 .. 62 (got %d)", n_bins);
+  HIP_TRY(lmc::launch_pixel_hist(x_dev, C, H, W, n_bins, lo_dev, scale_dev, reinterpret_cast<unsigned long long*>(counts_dev), S(stream)));
+  return LMC_OK;
+}
+
 int lmc_dual_project(const float* y_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, float radius,
                      int32_t isotropic, void* stream) {
   if (!y_dev || !out_dev) return fail(LMC_E_INVALID, "NULL pointer");

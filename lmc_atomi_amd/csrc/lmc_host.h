@@ -217,12 +217,21 @@ struct lmc_sampler {
   double* bs2 = nullptr;
   size_t bs2_count = 0;                  // doubles in bs2
   lmc::BlockScales scales{};
-  // the kept iterate x into the accumulators: the fused multi-scale reduction when scales are enabled, else exactly the launches of before
+  // pixel histograms (lmc_sampler_set_histogram): hist = counts [hist_bins + 2][H][W], NULL = off; hist_lo / hist_scale [H][W] are the handle's copies
+  int hist_bins = 0;
+  unsigned long long* hist = nullptr;
+  float* hist_lo = nullptr;
+  float* hist_scale = nullptr;
+  unsigned long long* hist_packed = nullptr;   // [(hist_bins + 2) H W + 1]: the send / receive buffer of lmc_allreduce_histogram
+  // the kept iterate x into the accumulators: the fused multi-scale reduction when scales are enabled, else exactly the launches of before;
+  // then, with a histogram, its launch (it has no paced twin: beside a step kernel it is the in-line form on the side stream)
   hipError_t reduce(const float* x, hipStream_t st) {
-    return bs2 ? lmc::launch_moments_ms(x, C, prob.H, prob.W, s1, s2, scales, st) : lmc::launch_moments(x, C, prob.H, prob.W, s1, s2, st);
+    const hipError_t e = bs2 ? lmc::launch_moments_ms(x, C, prob.H, prob.W, s1, s2, scales, st) : lmc::launch_moments(x, C, prob.H, prob.W, s1, s2, st);
+    return e != hipSuccess || !hist ? e : lmc::launch_pixel_hist(x, C, prob.H, prob.W, hist_bins, hist_lo, hist_scale, hist, st);
   }
   hipError_t reduce_bg(const float* x, int n_wg, hipStream_t st) {
-    return bs2 ? lmc::launch_moments_ms_bg(x, C, prob.H, prob.W, s1, s2, scales, n_wg, st) : lmc::launch_moments_bg(x, C, prob.H, prob.W, s1, s2, n_wg, st);
+    const hipError_t e = bs2 ? lmc::launch_moments_ms_bg(x, C, prob.H, prob.W, s1, s2, scales, n_wg, st) : lmc::launch_moments_bg(x, C, prob.H, prob.W, s1, s2, n_wg, st);
+    return e != hipSuccess || !hist ? e : lmc::launch_pixel_hist(x, C, prob.H, prob.W, hist_bins, hist_lo, hist_scale, hist, st);
   }
   lmc::StepArgs base{};
   // MYMALA state (kind == 2): proposal mean of the current state, proposal, its mean, energies, decisions

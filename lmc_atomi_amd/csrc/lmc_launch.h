@@ -43,6 +43,9 @@ struct BlockScales {
 hipError_t launch_moments_ms(const float* x, int C, int H, int W, double* s1, double* s2, const BlockScales& B, hipStream_t st);
 hipError_t launch_moments_ms_bg(const float* x, int C, int H, int W, double* s1, double* s2, const BlockScales& B, int n_wg, hipStream_t st);
 hipError_t launch_block_sums(const double* src, int H, int W, int scale, double* out, hipStream_t st);
+// pixel-wise histograms (lmc_pixel_hist.hip): counts[B + 2][H][W] += the rows of x[C][H][W] under t = (x - lo) * scale, 1 <= B <= 62
+hipError_t launch_pixel_hist(const float* x, int64_t C, int H, int W, int B, const float* lo, const float* scale, unsigned long long* counts,
+                             hipStream_t st);
 hipError_t launch_energies(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, double* g_out,
                            hipStream_t st);
 // pieces of the exact early-exit path of the TV prox (lmc_problem.tv_rtol > 0)

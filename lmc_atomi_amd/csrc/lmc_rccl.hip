@@ -136,4 +136,27 @@ int lmc_allreduce_block_moments(lmc_sampler* s, void* rccl_comm, int32_t scale, 
   return allreduce_packed(s, R, rccl_comm, n, sum_dev, sumsq_dev, count, st);
 }
 
+// The collective of the histogram: the counts of this rank and its count in one uint64 buffer, ONE ncclAllReduce(ncclUint64, sum).
+int lmc_allreduce_histogram(lmc_sampler* s, void* rccl_comm, uint64_t* counts_dev, uint64_t* count, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (!s->hist) return fail(LMC_E_INVALID, "the sampler has no histogram (lmc_sampler_set_histogram)");
+  if (!rccl_comm) return lmc_sampler_get_histogram(s, counts_dev, count, stream);   // a job of one rank
+  hipStream_t st = S(stream);
+  RcclApi* R = rccl_api();
+  if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
+  const size_t n = (size_t)(s->hist_bins + 2) * s->prob.H * s->prob.W;
+  if (!s->hist_packed) HIP_TRY(hipMalloc(&s->hist_packed, sizeof(unsigned long long) * (n + 1)));
+  const unsigned long long cnt = s->count;
+  HIP_TRY(hipMemcpyAsync(s->hist_packed, s->hist, sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->hist_packed + n, &cnt, sizeof cnt, hipMemcpyHostToDevice, st));
+  RCCL_TRY(R, R->AllReduce(s->hist_packed, s->hist_packed, n + 1, ncclUint64, ncclSum, static_cast<ncclComm_t>(rccl_comm), st));
+  if (counts_dev) HIP_TRY(hipMemcpyAsync(counts_dev, s->hist_packed, sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, st));
+  unsigned long long total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, s->hist_packed + n, sizeof total, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (count) *count = total;
+  return LMC_OK;
+}
+
 }  // extern "C"

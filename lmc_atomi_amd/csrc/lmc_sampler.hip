@@ -126,6 +126,16 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   return LMC_OK;
 }
 
+static void release_histogram(lmc_sampler* s) {
+  if (s->hist) (void)hipFree(s->hist);
+  if (s->hist_lo) (void)hipFree(s->hist_lo);
+  if (s->hist_scale) (void)hipFree(s->hist_scale);
+  if (s->hist_packed) (void)hipFree(s->hist_packed);
+  s->hist = s->hist_packed = nullptr;
+  s->hist_lo = s->hist_scale = nullptr;
+  s->hist_bins = 0;
+}
+
 void lmc_sampler_destroy(lmc_sampler* s) {
   if (!s) return;
   DeviceGuard dg(s->device);
@@ -146,6 +156,7 @@ void lmc_sampler_destroy(lmc_sampler* s) {
   if (s->s2) (void)hipFree(s->s2);
   if (s->packed) (void)hipFree(s->packed);
   if (s->bs2) (void)hipFree(s->bs2);
+  release_histogram(s);
   for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
   if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }
   for (hipEvent_t e : s->side_ev) if (e) (void)hipEventDestroy(e);
@@ -748,6 +759,7 @@ int lmc_sampler_reset_moments(lmc_sampler* s, void* stream) {
   HIP_TRY(hipMemsetAsync(s->s1, 0, mb, S(stream)));
   HIP_TRY(hipMemsetAsync(s->s2, 0, mb, S(stream)));
   if (s->bs2) HIP_TRY(hipMemsetAsync(s->bs2, 0, sizeof(double) * s->bs2_count, S(stream)));
+  if (s->hist) HIP_TRY(hipMemsetAsync(s->hist, 0, sizeof(unsigned long long) * (size_t)(s->hist_bins + 2) * s->prob.H * s->prob.W, S(stream)));
   s->count = 0;
   return LMC_OK;
 }
@@ -799,6 +811,44 @@ int lmc_sampler_get_block_moments(lmc_sampler* s, int32_t scale, double* sum_dev
   const size_t nb = (size_t)((s->prob.H + scale - 1) / scale) * ((s->prob.W + scale - 1) / scale);
   if (sum_dev) HIP_TRY(lmc::launch_block_sums(s->s1, s->prob.H, s->prob.W, scale, sum_dev, S(stream)));
   if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, s->scales.s2[k], sizeof(double) * nb, hipMemcpyDeviceToDevice, S(stream)));
+  HIP_TRY(hipStreamSynchronize(S(stream)));
+  if (count) *count = s->count;
+  return LMC_OK;
+}
+
+// ---- pixel histograms: counts [n_bins + 2][H][W] of the kept samples, rows by t = (x - lo) * scale (lmc_pixel_hist.hip) ----
+int lmc_sampler_set_histogram(lmc_sampler* s, int32_t n_bins, const float* lo_dev, const float* scale_dev) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (n_bins < 0 || n_bins > 62) return fail(LMC_E_INVALID, "n_bins must be 0 .. 62 (got %d)", n_bins);
+  if (n_bins > 0 && (!lo_dev || !scale_dev)) return fail(LMC_E_INVALID, "NULL lo / scale array with n_bins > 0");
+  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
+  if (s->count != 0) return fail(LMC_E_STATE, "the histogram changes only while the accumulators are empty (after create or lmc_sampler_reset_moments)");
+  HIP_TRY(hipDeviceSynchronize());     // nothing of an earlier histogram is in flight when its buffers go
+  release_histogram(s);
+  if (!n_bins) return LMC_OK;
+  const size_t img = (size_t)s->prob.H * s->prob.W, nc = (size_t)(n_bins + 2) * img;
+  hipError_t e = hipMalloc(&s->hist, sizeof(unsigned long long) * nc);
+  if (e == hipSuccess) e = hipMalloc(&s->hist_lo, sizeof(float) * img);
+  if (e == hipSuccess) e = hipMalloc(&s->hist_scale, sizeof(float) * img);
+  if (e == hipSuccess) e = hipMemset(s->hist, 0, sizeof(unsigned long long) * nc);
+  if (e == hipSuccess) e = hipMemcpy(s->hist_lo, lo_dev, sizeof(float) * img, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess) e = hipMemcpy(s->hist_scale, scale_dev, sizeof(float) * img, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    release_histogram(s);
+    return fail(e == hipErrorOutOfMemory ? LMC_E_NOMEM : LMC_E_HIP, "histogram allocation failed: %s", hipGetErrorString(e));
+  }
+  s->hist_bins = n_bins;
+  return LMC_OK;
+}
+
+int lmc_sampler_get_histogram(lmc_sampler* s, uint64_t* counts_dev, uint64_t* count, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (!s->hist) return fail(LMC_E_INVALID, "the sampler has no histogram (lmc_sampler_set_histogram)");
+  const size_t nb = sizeof(unsigned long long) * (size_t)(s->hist_bins + 2) * s->prob.H * s->prob.W;
+  if (counts_dev) HIP_TRY(hipMemcpyAsync(counts_dev, s->hist, nb, hipMemcpyDeviceToDevice, S(stream)));
   HIP_TRY(hipStreamSynchronize(S(stream)));
   if (count) *count = s->count;
   return LMC_OK;

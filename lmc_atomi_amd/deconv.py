@@ -32,7 +32,7 @@ def synthetic_image(ny=512, nx=512, seed=1234):
 
 def prox_lmc_deconv(gamma_mc=15., gamma_me=15., sigma=0.75, tau=0.3, N=1000, niter_l2=50, niter_tv=10, image=None,
                     alg='ULPDA', seed=0, n_chains=None, burn_in=0, thin=1, models=None, verbose=True, diagnostics=None, rtol=1e-4,
-                    moment_scales=None):
+                    moment_scales=None, hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95)):
     """Posterior means of the nine models M1..M9 (prox_lmc_deconv.py:447-703) by ULPDA or MYULA on the GPU.
 
     ``rtol``: the early exit of the TV proxes AS THE REFERENCE IS CONFIGURED -- ``pyproximal.TV(dims, sigma, niter=niter_tv)`` leaves upstream's default
@@ -43,6 +43,8 @@ def prox_lmc_deconv(gamma_mc=15., gamma_me=15., sigma=0.75, tau=0.3, N=1000, nit
     ``:474``); ``n_chains=C`` runs C chains per model and averages over chains and kept iterations.
     ``moment_scales`` (with ``n_chains``): block sizes out of (2, 4, 8, 16); every model then also carries ``scale_mean`` / ``scale_std``,
     ``{s: array}`` of the posterior mean and standard deviation of the image averaged over s x s blocks.
+    ``hist_bins`` / ``hist_range=(lo, hi)`` / ``quantiles`` (with ``n_chains``): a histogram per pixel over the kept samples; every model then also
+    carries ``hist`` (counters ``[hist_bins + 2, ny, nx]``) and ``quantiles`` (``{q: array}``, the pixel-wise quantile maps).
     Returns ``{"M1": {"mean", "snr", "psnr", "mse", "seconds"}, ...}``.
     """
     img = synthetic_image() if image is None else np.asarray(image, dtype=np.float64)
@@ -76,6 +78,8 @@ def prox_lmc_deconv(gamma_mc=15., gamma_me=15., sigma=0.75, tau=0.3, N=1000, nit
             continue
         f = data_term(k, kind)
         ms = {"moment_scales": moment_scales} if moment_scales else {}
+        if hist_bins is not None or hist_range is not None:
+            ms.update(hist_bins=hist_bins, hist_range=hist_range, quantiles=quantiles)
         t0 = time.time()
         if alg == 'ULPDA':                                          # :455-464
             res = UnadjustedLangevinPrimalDual(f, L21(ndim=2, sigma=tau), Gop, tau=tau0, mu=mu0, theta=1., x0=x0, gfirst=False,
@@ -101,6 +105,9 @@ def prox_lmc_deconv(gamma_mc=15., gamma_me=15., sigma=0.75, tau=0.3, N=1000, nit
         if moment_scales:
             out[name]["scale_mean"] = {sc: v.cpu().numpy() for sc, v in res.scale_mean.items()}
             out[name]["scale_std"] = {sc: v.cpu().numpy() for sc, v in res.scale_std.items()}
+        if getattr(res, "hist", None) is not None:
+            out[name]["hist"] = res.hist.cpu().numpy()
+            out[name]["quantiles"] = {q: v.cpu().numpy() for q, v in res.quantiles.items()}
         diag = getattr(res, "diagnostics", None)
         if diag is not None:                                        # split R-hat / ESS across chains (diagnostics.py)
             out[name].update(rhat_max=diag["rhat_max"], ess_min=diag["ess_min"], rhat=diag["rhat"].cpu().numpy(),

@@ -104,6 +104,31 @@ def allreduce_sampler_block_moments(smp, scale, group=None):
     return allreduce_moments(S1, S2, cnt, group)
 
 
+def allreduce_counts(counts, count, group=None):
+    """Sum integer counters (``torch.int64``, any shape) and a sample count over the ranks of ``group`` on the host: exact, whatever the backend
+    (the "gloo" route of :func:`allreduce_sampler_histogram`).  Returns (counts on the device they came from, count)."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return counts, int(count)
+    packed = torch.cat([counts.detach().reshape(-1).to(device="cpu", dtype=torch.int64), torch.tensor([int(count)], dtype=torch.int64)])
+    if dist.get_backend(group) == "nccl":
+        packed = packed.to(counts.device)
+    dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
+    return packed[:-1].reshape(counts.shape).to(counts.device), int(packed[-1])
+
+
+def allreduce_sampler_histogram(smp, group=None):
+    """Job-wide (counts, count) of a sampler's pixel histogram (:meth:`MYULASampler.histogram`), by the same routes as
+    :func:`allreduce_sampler_block_moments`: ``lmc_allreduce_histogram`` under "nccl", a host all-reduce of the int64 tensor under "gloo"."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return smp.histogram()
+    if dist.get_backend(group) == "nccl":
+        return smp.allreduce_histogram(rccl_comm(group, smp.device))
+    counts, cnt = smp.histogram()
+    return allreduce_counts(counts, cnt, group)
+
+
 def allgather_chains(t: torch.Tensor, dim: int = 1, group=None):
     """Concatenate per-rank tensors along their chain dimension in rank order (= global chain order under
     :func:`chain_shard`); ranks may own different numbers of chains.  Used for the diagnostics trace ``[T, C_rank, Q]``
@@ -130,12 +155,26 @@ def posterior_mean_var(s1, s2, count):
     return mean, s2 / count - mean * mean
 
 
+class ShardedResult(tuple):
+    """What :func:`sharded_myula` returns: the tuple it has always returned -- ``(mean, var, count, state)``, then the scales when ``moment_scales``
+    is given, then the histogram when ``hist_bins`` is given, so its length depends on the keywords -- with every part also under a name that does
+    not: ``.mean``, ``.var``, ``.count``, ``.state``, ``.scales`` (``{}`` when not asked for) and ``.hist`` (``None`` when not asked for)."""
+
+    def __new__(cls, items, mean, var, count, state, scales, hist):
+        self = super().__new__(cls, items)
+        self.mean, self.var, self.count, self.state, self.scales, self.hist = mean, var, count, state, scales, hist
+        return self
+
+
 def sharded_myula(proxf, proxg, dims, n_chains_total, x0, tau, gamma, epsg=1.0, niter=10, seed=0,
-                  burn_in=0, thin=1, group=None, device=None, moment_scales=None):
+                  burn_in=0, thin=1, group=None, device=None, moment_scales=None, hist_bins=None,
+                  hist_range=None):
     """Run ``n_chains_total`` MYULA chains split over the ranks of the default process group (or run
     them all here when torch.distributed is not initialised) and return the job-wide posterior
     (mean, var, count) plus this rank's final states.  With ``moment_scales`` (block sizes out of 2, 4, 8, 16) a fifth value
-    follows: ``{scale: (mean, std)}`` of the image averaged over scale x scale blocks, job-wide as well."""
+    follows: ``{scale: (mean, std)}`` of the image averaged over scale x scale blocks, job-wide as well.  With ``hist_bins`` / ``hist_range`` (as
+    :class:`MYULASampler` takes them) the job-wide counters of the pixel histogram ``[hist_bins + 2, H, W]`` follow as the last value.  The tuple is a :class:`ShardedResult`: index it
+    as before, or -- since its length depends on the keywords -- read ``.mean``, ``.var``, ``.count``, ``.state``, ``.scales`` and ``.hist``."""
     import torch.distributed as dist
     from .algs import MYULASampler
     world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
@@ -144,8 +183,10 @@ def sharded_myula(proxf, proxg, dims, n_chains_total, x0, tau, gamma, epsg=1.0, 
         raise ValueError(f"{n_chains_total} chains cannot be sharded over {world} ranks (every rank needs at least one)")
     offset, count = chain_shard(n_chains_total, world, rank)
     smp = MYULASampler(proxf, proxg, dims, n_chains=count, tau=tau, gamma=gamma, epsg=epsg, seed=seed,
-                       chain_offset=offset, moments=True, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales)
+                       chain_offset=offset, moments=True, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
+                       hist_bins=hist_bins, hist_range=hist_range)
     scales = {}
+    hist = None
     try:
         smp.set_state(x0)
         smp.step(niter)
@@ -155,8 +196,11 @@ def sharded_myula(proxf, proxg, dims, n_chains_total, x0, tau, gamma, epsg=1.0, 
             S1, S2, n = allreduce_sampler_block_moments(smp, sc, group)
             m, v = block_mean_var(S1, S2, max(n, 1), sc, smp.dims)
             scales[sc] = (m, v.clamp_min(0).sqrt())
+        if smp.hist_bins is not None:
+            hist, _ = allreduce_sampler_histogram(smp, group)
         state = smp.get_state()
     finally:
         smp.close()
     mean, var = posterior_mean_var(s1, s2, cnt)
-    return (mean, var, cnt, state, scales) if moment_scales else (mean, var, cnt, state)
+    out = (mean, var, cnt, state, scales) if moment_scales else (mean, var, cnt, state)
+    return ShardedResult(out + (hist,) if hist is not None else out, mean, var, cnt, state, scales, hist)
