@@ -450,7 +450,10 @@ static int myula_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, h
   // step kernel alone).  BASELINE config 2 (256 x 256 x 128): the 15 us reduction is 40 % of a serial iteration, 40.2 -> 35.9 us per iteration
   // with 128 background workgroups.  Headline size: the reduction under the step kernel costs that kernel 6 % (1.76 -> 1.89 ms per launch) and
   // saves its own 0.22 ms -- 1.976 -> 1.90-1.92 ms per iteration with 256 workgroups (16: 3.19, 64: 2.07, 128: 1.92, 256: 1.90, 512: 1.94,
-  // 1024: 1.98 ms; too few and the reduction outlasts the step kernel).  (lmc_problem.moments_bg_workgroups / LMC_MOMENTS_BG_WGS: fixed at creation)
+  // 1024: 1.98 ms; too few and the reduction outlasts the step kernel).  Re-measured under the two-team kernel (four 112-VGPR waves per SIMD, one 64-VGPR wave
+  // fits beside them): 128 / 192 / 256 / 384 / 512 workgroups of 256 threads: 1.725 / 1.729 / 1.709 / 1.710 / 1.771 ms per step; one-wave workgroups and a chain
+  // unroll of 2 or 8 instead of 4 are equal at equal wave counts, never better: 256 stays.
+  // (lmc_problem.moments_bg_workgroups / LMC_MOMENTS_BG_WGS: fixed at creation)
   const bool overlap = !s->timing && s->pol_overlap >= 0 && s->moments && n_iters > 1;
   const int bg_wgs = s->pol_bg_wgs >= 0 ? s->pol_bg_wgs : ((long long)per_iter <= (1LL << 25) ? 128 : 256);   // 0: the full-speed kernel
   if (overlap && !s->side) {

@@ -310,14 +310,21 @@ __host__ __device__ constexpr int pipe_halo(int K, int KT, int PXL) {
 //   RT, kc <= 3: one live stage per wave      0x64753210u   L + T5 | T1 + N  | T2 + T4 | T3 + C    /  models): 1.504 / 1.511 ms per iteration against 1.591 / 1.566 plain
 //   RT, kc > 5, link of a chained prox        0x67254310u   L + T5 | T1 + T2 | T3 + N | T4 + C     ME-TV as configured: 15.95 against 16.73 ms
 //   RT, kc > 5, one launch                    0x74563210u   L + C  | T1 + T5 | T2 + T4 | T3 + N    DESIGN 3.0r (no figure of its own)
-//   two teams (16 waves; kPipe2Roles, nibble = team << 3 | role, decoded in pipe_body): two two-stage T waves beside L + C of one team, or beside
-//                                                           N + T1 of one team, on each SIMD; the one candidate measured
+//   two teams (16 waves; kPipe2Roles, nibble = team << 3 | role, decoded in pipe_body; a = left team, b = right team; hardware waves w, w + 4, w + 8, w + 12
+//   share a SIMD, in that order):                           L.a T4.a C.a T5.b | T1.a T5.a T1.b C.b | T2.a N.a T3.b T4.b | T3.a L.b T2.b N.b
+//                                                           1.711 ms per step against 1.742 for round 4's map 0x5D3BC4A291E6F780 (L.a C.a T2.a T3.b | L.b C.b T2.b T3.a |
+//                                                           N.a T1.a T4.a T5.b | N.b T1.b T4.b T5.a), five alternating pairs.  Searched in round 5 with a build that read the
+//                                                           map at run time (4400 placements from 34 structured seeds by swaps between SIMDs, then 940 orders of the waves:
+//                                                           1.60 - 1.92 ms per launch); that build only ranks -- its kernel is another instruction stream -- so nine of its
+//                                                           best were rebuilt as constants and timed with bench.py: 1.707 - 1.739 ms per step.  The ORDER of the waves on a SIMD
+//                                                           counts as much as the placement (the same four sets in another order: 1.739), and the per-SIMD VALU sums still
+//                                                           predict nothing (this map: 298 / 281 / 367 / 354 slots per tick, round 4's: 301 / 352).  DESIGN section 7.
 // RT (per-chain exit): the kc live stages are a prefix; up to NT of them run one per wave (t_role: spread), the other T waves only pass the dual on, and the best
 // pairing for one live count is among the worst for another -- so the map follows kc.
 // The compiler's output follows the form of these expressions, not only their values: the last one-team row is a swap of hardware waves 4 and 6 because its
 // nibble code changes the instruction streams of the twelve one-launch RT kernels, and the two-team nibble is split where it is used because returning it
 // from here changes the two two-team kernels (scripts/kernel_resources.py --code-hash shows which kernels an edit moves).
-constexpr unsigned long long kPipe2Roles = 0x5D3BC4A291E6F780ull;
+constexpr unsigned long long kPipe2Roles = 0xFCEDAB9687543210ull;
 template <int K, int KT, bool CHAIN, bool RT>
 __device__ __forceinline__ int pipe_role(int hw_wave, int kc, int ncvx_kind) {
   constexpr int NT = PipeGeom<K>::NT;
