@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LMC_ATOMI_ABI_VERSION 3
+#define LMC_ATOMI_ABI_VERSION 4
 
 typedef enum lmc_status {
   LMC_OK = 0,
@@ -95,6 +95,7 @@ typedef enum lmc_noise_mode {
 
 #define LMC_MAX_BLUR 9       /* kernels up to 9x9 */
 #define LMC_MAX_TV_ITERS 64
+#define LMC_MAX_SKROCK_STAGES 64
 
 /* Geometry + potential U(x) = f(x) + eps*g(x).  Plain data; copied by the callee. */
 typedef struct lmc_problem {
@@ -306,6 +307,37 @@ int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out);
 /* accepted_dev [n_chains] uint64: accepted proposals so far; last_log_alpha_dev [n_chains] f64 (nullable): log acceptance
  * ratio of the latest iteration.  Device buffers. */
 int lmc_sampler_get_acceptance(lmc_sampler* s, uint64_t* accepted_dev, double* last_log_alpha_dev, void* stream);
+
+/* SK-ROCK -- the stochastic orthogonal Runge-Kutta-Chebyshev scheme for the Moreau-Yosida-smoothed posterior MYULA samples (Pereyra, Vargas
+ * Mieles, Zygalakis, SIAM J. Imaging Sci. 2020; Abdulle, Almuslimani, Vilmart 2018): s >= 2 evaluations of the MYULA drift per iteration, stable
+ * up to delta = l_s / L with l_s = (s - 1/2)^2 (2 - 4 eta / 3) - 3/2 and L = L_f + 1/gamma, where MYULA stops near 1 / L.  Build-specified (the
+ * reference has no such sampler); this text is its definition.
+ *   T_j: Chebyshev polynomials of the first kind, w0 = 1 + eta / s^2, w1 = T_s(w0) / T_s'(w0)
+ *   mu_1 = w1 / w0, nu_1 = s w1 / 2, kappa_1 = s w1 / w0
+ *   mu_j = 2 w1 T_{j-1}(w0) / T_j(w0), nu_j = 2 w0 T_{j-1}(w0) / T_j(w0), kappa_j = -T_{j-2}(w0) / T_j(w0) = 1 - nu_j      (j = 2 .. s)
+ *   drift(x) = -grad f(x) - (x - prox_{epsg gamma g}(x)) / gamma       (the drift of MYULA, algs.py:569), delta = cfg.tau, q = sqrt(2 delta)
+ * One iteration draws ONE field Z ~ N(0, I):
+ *   K_0 = X
+ *   K_1 = X + mu_1 delta drift(X + nu_1 q Z) + kappa_1 q Z
+ *   K_j = mu_j delta drift(K_{j-1}) + nu_j K_{j-1} + kappa_j K_{j-2}       (j = 2 .. s)
+ *   X+  = K_s
+ * For a linear drift -l x and z = -delta l this is X+ = R_s(z) X + q B_s(z) Z with R_s(z) = T_s(w0 + w1 z) / T_s(w0) and
+ * B_s(z) = U_{s-1}(w0 + w1 z) / U_{s-1}(w0) (1 + w1 z / 2), U the Chebyshev polynomials of the second kind.
+ *
+ * lmc_skrock_coefficients: host only (no device needed).  mu, nu, kappa: n_stages doubles each, entry j - 1 = stage j; *step_factor = l_s; all
+ * four nullable.  Formed in double by the three-term recurrences of T_j and T_j'.  n_stages outside 2 .. LMC_MAX_SKROCK_STAGES, or eta not finite
+ * and positive: LMC_E_INVALID. */
+int lmc_skrock_coefficients(int32_t n_stages, double eta, double* mu, double* nu, double* kappa, double* step_factor);
+/* The sampler: lmc_myula_config as for MYULA (tau = delta), every data term, prior and non-convex term of MYULA.  Every stage is one launch of
+ * the fused step kernel  a x - t grad f(x) + b prox(x) + s n  with  a = nu_j - mu_j delta / gamma, t = mu_j delta, b = mu_j delta / gamma,
+ * s = kappa_j  and K_{j-2} as the injected field n; stage 1 runs on Y = X + nu_1 q Z (one streaming launch before it) with a = 1 - mu_1 delta / gamma,
+ * s = (kappa_1 - nu_1) q and the same Z -- the definition up to the fp32 rounding of Y - nu_1 q Z.  One noise field per ITERATION: with
+ * LMC_NOISE_PHILOX the field lmc_sampler_noise(s, iteration) returns, with LMC_NOISE_INJECTED noise_dev[iteration of the call]; the iteration
+ * counter advances once per iteration.  The moment accumulators take K_s of the kept iterations (in line).  With timing enabled every stage
+ * launch has its event pair: n_launches = n_stages * n_iters.  lmc_sampler_get_acceptance: LMC_E_STATE.
+ * LMC_E_UNSUPPORTED for what runs outside the fused launch: tv_warm, tv_rtol > 0 on the prior, prox_scale (ncvx_rtol stays allowed).
+ * n_stages / eta: as lmc_skrock_coefficients (LMC_E_INVALID). */
+int lmc_skrock_create(const lmc_myula_config* cfg, int32_t n_stages, float eta, lmc_sampler** out);
 
 /* x_dev: [n_chains][H][W].  x0 of algs.py:559 (copied). */
 int lmc_sampler_set_state(lmc_sampler* s, const float* x_dev, void* stream);

@@ -9,7 +9,7 @@ from .proximal import (L1, L2, L21, TV, L2_ncvx_tv, WaveletL1, ProxOperator, fgp
                        GenGaussian, Huber, SmoothedLaplace)
 from .algs import (MYULAResult, MYULASampler, MYMALASampler, MoreauYosidaUnadjustedLangevin, MoreauYosidaMetropolisAdjustedLangevin, ULPDASampler,
                    UnadjustedLangevinPrimalDual, block_mean_var, hist_exceedance, hist_quantiles, mean_var_from_moments, pixel_histogram,
-                   set_step_variant, set_cg_tolerance)
+                   set_step_variant, set_cg_tolerance, SKROCKSampler, StabilisedLangevin, skrock_coefficients, skrock_step_bound)
 
 from . import diagnostics, metrics
 from .diagnostics import ChainTrace, chain_probes, ess, split_rhat
@@ -26,5 +26,6 @@ __all__ = [
     "MYULASampler", "MYMALASampler", "MoreauYosidaMetropolisAdjustedLangevin", "MYULAResult", "MoreauYosidaUnadjustedLangevin", "ULPDASampler", "UnadjustedLangevinPrimalDual", "mean_var_from_moments", "set_step_variant", "set_cg_tolerance",
     "block_mean_var", "allreduce_sampler_block_moments",
     "pixel_histogram", "hist_quantiles", "hist_exceedance", "allreduce_sampler_histogram",
+    "SKROCKSampler", "StabilisedLangevin", "skrock_coefficients", "skrock_step_bound",
 ]
 __version__ = "0.2.0"

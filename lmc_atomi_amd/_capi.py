@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "liblmc_atomi.so")
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 # enums (include/lmc_atomi.h)
 DATA_NONE, DATA_IDENTITY, DATA_BLUR, DATA_MASK = 0, 1, 2, 3
@@ -20,6 +20,7 @@ NOISE_PHILOX, NOISE_INJECTED, NOISE_NONE = 0, 1, 2
 NCVX_NONE, NCVX_MC_TV, NCVX_ME_TV, NCVX_MC_TV_ANISO, NCVX_ME_TV_ANISO = 0, 1, 2, 3, 4
 MAX_BLUR = 9
 MAX_TV_ITERS = 64
+MAX_SKROCK_STAGES = 64
 (EPROX_LAPLACE, EPROX_UNCENTERED_LAPLACE, EPROX_GAUSSIAN, EPROX_GEN_GAUSSIAN_4_3, EPROX_GEN_GAUSSIAN_3_2,
  EPROX_GEN_GAUSSIAN_3, EPROX_GEN_GAUSSIAN_4, EPROX_HUBER, EPROX_SMOOTHED_LAPLACE, EPROX_EXP, EPROX_GAMMA,
  EPROX_CHI, EPROX_UNIFORM, EPROX_TRIANGULAR, EPROX_LAPLACE_CONJ) = range(15)
@@ -121,6 +122,7 @@ class lmc_ulpda_config(C.Structure):
 
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
+_D = C.POINTER(C.c_double)
 _SIGNATURES = {
     "lmc_version": (C.c_int, []),
     "lmc_last_error": (C.c_char_p, []),
@@ -135,6 +137,8 @@ _SIGNATURES = {
     "lmc_energies": (C.c_int, [C.POINTER(lmc_problem), _P, C.c_int64, _P, _P, _P]),
     "lmc_mymala_create": (C.c_int, [C.POINTER(lmc_myula_config), C.POINTER(_P)]),
     "lmc_sampler_get_acceptance": (C.c_int, [_P, _P, _P, _P]),
+    "lmc_skrock_coefficients": (C.c_int, [C.c_int32, C.c_double, _D, _D, _D, _D]),
+    "lmc_skrock_create": (C.c_int, [C.POINTER(lmc_myula_config), C.c_int32, C.c_float, C.POINTER(_P)]),
     "lmc_set_cg_tolerance": (C.c_float, [C.c_float]),
     "lmc_chain_probes": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "lmc_haar_l1_prox": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),

@@ -261,11 +261,15 @@ class MYULASampler:
         self.moments_on = bool(moments)
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _capi.check(getattr(_dev.lib(), self._create_fn)(C.byref(cfg), C.byref(self._h)))
+            _capi.check(self._create(cfg))
         self._set_moment_scales(scales)
         self._set_histogram(hist)
 
     _create_fn = "lmc_myula_create"
+
+    def _create(self, cfg):
+        return getattr(_dev.lib(), self._create_fn)(C.byref(cfg), C.byref(self._h))
+
     moment_scales = ()
     hist_bins = hist_lo = hist_scale = None
 
@@ -825,6 +829,94 @@ def MoreauYosidaMetropolisAdjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1,
                           hist=_hist_summaries(smp, quantiles))
         res.accepted = acc
         res.acceptance_rate = acc.double() / max(niter, 1)
+        return res
+    finally:
+        smp.close()
+
+
+def skrock_coefficients(n_stages, eta=0.05):
+    """``(mu, nu, kappa)`` of SK-ROCK with ``n_stages`` stages and damping ``eta``: float64 arrays, entry ``j - 1`` = stage ``j``, as the library
+    forms them (``lmc_skrock_coefficients``; the definition is in include/lmc_atomi.h).  Needs no GPU.  ``n_stages`` outside 2 .. 64 or an ``eta``
+    that is not finite and positive raises ``ValueError``."""
+    mu, nu, kappa, _ = _skrock_coefficients(n_stages, eta)
+    return mu, nu, kappa
+
+
+def _skrock_coefficients(n_stages, eta):
+    s = int(n_stages)
+    n = min(max(s, 1), _capi.MAX_SKROCK_STAGES)
+    mu, nu, kappa = (np.zeros(n, dtype=np.float64) for _ in range(3))
+    ls = C.c_double()
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    rc = _dev.lib().lmc_skrock_coefficients(s, float(eta), dp(mu), dp(nu), dp(kappa), C.byref(ls))
+    if rc == -1:       # LMC_E_INVALID
+        raise ValueError(_dev.lib().lmc_last_error().decode("utf-8", "replace"))
+    _capi.check(rc)
+    return mu, nu, kappa, float(ls.value)
+
+
+def skrock_step_bound(L, n_stages, eta=0.05):
+    """Largest stable step of SK-ROCK for a drift with Lipschitz constant ``L`` (``L_f + 1 / gamma`` for the MYULA drift):
+    ``l_s / L`` with ``l_s = (s - 1/2)^2 (2 - 4 eta / 3) - 3/2``, where MYULA stops near ``1 / L``."""
+    return _skrock_coefficients(n_stages, eta)[3] / float(L)
+
+
+class SKROCKSampler(MYULASampler):
+    """SK-ROCK for many chains at image scale (Pereyra, Vargas Mieles, Zygalakis 2020): ``n_stages`` evaluations of the MYULA drift per iteration,
+    each one launch of the fused step kernel with Chebyshev coefficients, stable up to ``tau = skrock_step_bound(L, n_stages, eta)`` --
+    integrated time per gradient evaluation grows like ``n_stages``.  The other arguments are :class:`MYULASampler`'s; one noise field per
+    iteration (``step(n, noise=[n, C, H, W])`` with ``noise='injected'``), ``iteration`` counts iterations, not stages.  ``TV(rtol > 0)``,
+    a warm-started TV dual and array-valued ``epsg`` run outside the fused launch and raise ``NotImplementedError``."""
+
+    def __init__(self, proxf, proxg, dims, n_stages=10, eta=0.05, **kw):
+        prior = _prior_descriptor(proxg)
+        if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
+            raise NotImplementedError("SK-ROCK runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
+        if prior.get("tv_warm") or kw.get("tv_warm"):
+            raise NotImplementedError("SK-ROCK evaluates the drift at n_stages points per iteration: a warm-started TV dual (warm=True) is not built for it")
+        if np.asarray(kw.get("epsg", 1.0)).size > 1:
+            raise NotImplementedError("SK-ROCK takes a scalar epsg (array-valued epsg is MYULA's)")
+        _skrock_coefficients(n_stages, eta)          # ValueError for a stage count or damping the library refuses
+        self.n_stages, self.eta = int(n_stages), float(eta)
+        super().__init__(proxf, proxg, dims, **kw)
+
+    def _create(self, cfg):
+        return _dev.lib().lmc_skrock_create(C.byref(cfg), self.n_stages, self.eta, C.byref(self._h))
+
+
+def StabilisedLangevin(proxf, proxg, x0, tau, gamma=.1, epsg=1., niter=10, n_stages=10, eta=0.05, seed=0, callback=None, *,
+                       n_chains=1, dims=None, chain_offset=0, burn_in=0, thin=1, device=None, moment_scales=None,
+                       hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95)):
+    """SK-ROCK at image scale for ``n_chains`` chains (:class:`SKROCKSampler`): ``niter`` iterations of ``n_stages`` drift evaluations each at
+    step ``tau`` (up to :func:`skrock_step_bound`).  Returns a :class:`MYULAResult` with two extra attributes, ``n_stages`` and
+    ``gradient_evaluations = niter * n_stages``.  ``callback(state)`` after every iteration if given.  ``moment_scales``, ``hist_bins`` /
+    ``hist_range`` / ``quantiles``: as in :func:`MoreauYosidaUnadjustedLangevin`."""
+    if dims is None:
+        dims = getattr(proxf, "dims", None) or getattr(proxg, "dims", None)
+    if dims is None:
+        raise ValueError("image shape unknown: pass dims=(ny, nx)")
+    smp = SKROCKSampler(proxf, proxg, dims, n_stages=n_stages, eta=eta, n_chains=int(n_chains), tau=tau, gamma=gamma, epsg=epsg, seed=seed,
+                        chain_offset=chain_offset, moments=True, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
+                        hist_bins=hist_bins, hist_range=hist_range)
+    try:
+        smp.set_state(x0)
+        tstart = time.time()
+        if callback is None:
+            smp.step(niter)
+        else:
+            for _ in range(niter):
+                smp.step(1)
+                callback(smp.get_state())
+        s1, s2, cnt = smp.moments()
+        f, g = smp.energies()
+        state = smp.get_state()
+        torch.cuda.current_stream().synchronize()
+        mean, var = mean_var_from_moments(s1, s2, max(cnt, 1))
+        scale_mean, scale_std = _scale_summaries(smp)
+        res = MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, scale_mean=scale_mean, scale_std=scale_std,
+                          hist=_hist_summaries(smp, quantiles))
+        res.n_stages = smp.n_stages
+        res.gradient_evaluations = int(niter) * smp.n_stages
         return res
     finally:
         smp.close()

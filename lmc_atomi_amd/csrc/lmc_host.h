@@ -3,7 +3,7 @@
 //   lmc_problem.hip     lmc_problem -> Problem, StepArgs of an update, the step-kernel dispatch, the library defaults
 //   lmc_solve.hip       the implicit step (I + ts H^T H) u = rhs: Chebyshev, CG
 //   lmc_tv_exit.hip     the early exits of the TV prox, the ME-TV inner prox and envelope
-//   lmc_sampler.hip     the MYULA, MYMALA and ULPDA samplers
+//   lmc_sampler.hip     the MYULA, MYMALA, SK-ROCK and ULPDA samplers
 //   lmc_rccl.hip        the dlopen'd RCCL and the moment all-reduce
 #pragma once
 #include <string>
@@ -174,7 +174,7 @@ int me_tv_energy(const Problem& q, const float* x, int64_t n_img, double* f_out,
 }  // namespace lmc::host
 
 struct lmc_sampler {
-  int kind = 0;   // 0 MYULA, 1 ULPDA, 2 MYMALA
+  int kind = 0;   // 0 MYULA, 1 ULPDA, 2 MYMALA, 3 SK-ROCK
   int device = -1;   // the device the handle's buffers live on (current at creation); every call on the handle runs there
   // ULPDA state (kind == 1)
   float mu = 0, theta = 1;
@@ -240,6 +240,9 @@ struct lmc_sampler {
   int* flag = nullptr;
   unsigned long long* nacc = nullptr;
   bool mala_fresh = false;               // mx / U match x[cur]
+  // SK-ROCK state (kind == 3): stage count and the stage coefficients (entry j - 1 = stage j); the third state array of its rotation is xspare
+  int sk_stages = 0;
+  double sk_mu[LMC_MAX_SKROCK_STAGES] = {}, sk_nu[LMC_MAX_SKROCK_STAGES] = {}, sk_kappa[LMC_MAX_SKROCK_STAGES] = {};
   // moment reductions on a side stream, overlapping the next step kernel (HBM-bound reduction under a VALU-bound step kernel); which of them are
   // still running is known only inside one lmc_sampler_step call (SideMoments), which joins them all before it returns
   hipStream_t side = nullptr;

@@ -160,3 +160,11 @@ hipError_t mala_accept(int C, double* U, const double* fp, const double* gp, flo
 hipError_t mala_select(const int* flag, float* x, float* mx, const float* xp, const float* mxp, int64_t C, size_t img, int when,
                        hipStream_t st);
 }  // namespace lmc
+
+namespace lmc {
+// SK-ROCK stage 1 (lmc_skrock.hip): out = x + coef * Z, Z the Philox / Box-Muller field of `iteration` that the step kernels and launch_noise draw
+// (same device functions, same counter layout: bit for bit that field), or the caller's field xi.  x, out (and xi): [C][H][W] / n floats, distinct.
+hipError_t launch_skrock_perturb_philox(const float* x, float* out, int64_t C, int H, int W, float coef, uint32_t key0, uint32_t key1,
+                                        uint32_t iteration, uint32_t chain_offset, hipStream_t st);
+hipError_t launch_skrock_perturb(const float* x, const float* xi, float* out, size_t n, float coef, hipStream_t st);
+}  // namespace lmc

@@ -1,4 +1,4 @@
-// The samplers behind lmc_sampler: create / destroy / state / step of MYULA, MYMALA and ULPDA, and the accessors of a handle.
+// The samplers behind lmc_sampler: create / destroy / state / step of MYULA, MYMALA, SK-ROCK and ULPDA, and the accessors of a handle.
 #include <cmath>
 #include <cstdlib>
 #include <new>
@@ -184,6 +184,7 @@ int lmc_sampler_get_state(lmc_sampler* s, float* x_dev, void* stream) {
 
 static int ulpda_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, hipStream_t st);
 static int mymala_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, hipStream_t st);
+static int skrock_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, hipStream_t st);
 
 // f(x_c), g(x_c) of `x` ([C][H][W]) with the sampler's problem and scratch buffers
 static int sampler_energies_at(lmc_sampler* s, const float* x, double* f_out_dev, double* g_out_dev, hipStream_t st) {
@@ -212,9 +213,19 @@ static int me_tv_extra(lmc_sampler* s, lmc::StepArgs& A, hipStream_t st) {
   return LMC_OK;
 }
 
+// One launch with coefficients, noise mode and noise array of its own in place of the sampler's (an SK-ROCK stage); ev_begin / ev_end (nullable)
+// are recorded around the step launch.
+struct StepOverride {
+  float a, t, b, s;
+  int noise_mode;
+  const float* noise;
+  hipEvent_t ev_begin, ev_end;
+};
+
 // out = base update of `x_in` with the sampler's coefficients; noise_scale 0 gives the proposal mean m(x_in)
 static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool with_noise, const float* noise, uint32_t iteration,
-                          hipStream_t st, const char** kname, double* f_out = nullptr, double* g_out = nullptr, bool* fused = nullptr) {
+                          hipStream_t st, const char** kname, double* f_out = nullptr, double* g_out = nullptr, bool* fused = nullptr,
+                          const StepOverride* ov = nullptr) {
   lmc::StepArgs A = s->base;
   if (fused) *fused = false;
   if (f_out && g_out && (variant_of(s->prob) == 0 || variant_of(s->prob) == 7) && s->prob.ncvx_kind == LMC_NCVX_NONE && s->prob.prior_kind == LMC_PRIOR_TV_ISO) {
@@ -232,12 +243,15 @@ static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool 
   A.iteration = iteration;
   A.noise = noise;
   if (!with_noise) { A.s = 0.f; A.noise_mode = LMC_NOISE_NONE; A.noise = nullptr; }
+  if (ov) { A.a = ov->a; A.t = ov->t; A.b = ov->b; A.s = ov->s; A.noise_mode = ov->noise_mode; A.noise = ov->noise; }
   sanitize_pointers(A);
   int rc = me_tv_extra(s, A, st);   // inner prox of the Moreau-envelope term, then the fused step
   if (rc) return rc;
+  if (ov && ov->ev_begin) HIP_TRY(hipEventRecord(ov->ev_begin, st));
   hipError_t e = launch_step(A, variant_of(s->prob), st, kname, s->tvstate[0], s->tvstate[1], s->pxbuf);
   if (e == hipErrorInvalidConfiguration) return fail(LMC_E_UNSUPPORTED, "no step-kernel variant covers this configuration");
   HIP_TRY(e);
+  if (ov && ov->ev_end) HIP_TRY(hipEventRecord(ov->ev_end, st));
   return LMC_OK;
 }
 
@@ -488,6 +502,7 @@ int lmc_sampler_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, vo
   if (s->noise_mode != LMC_NOISE_INJECTED && noise_dev)
     return fail(LMC_E_INVALID, "noise_dev given but noise_mode is not INJECTED");
   if (s->iteration + n_iters > 0xFFFFFFFFLL) return fail(LMC_E_STATE, "iteration counter would exceed 32 bits");
+  if (s->kind == 3) return skrock_step(s, n_iters, noise_dev, S(stream));
   if (s->kind == 2) return mymala_step(s, n_iters, noise_dev, S(stream));
   if (s->kind == 1) return ulpda_step(s, n_iters, noise_dev, S(stream));
   return myula_step(s, n_iters, noise_dev, S(stream));
@@ -577,6 +592,136 @@ int lmc_sampler_get_acceptance(lmc_sampler* s, uint64_t* accepted_dev, double* l
   if (accepted_dev) HIP_TRY(hipMemcpyAsync(accepted_dev, s->nacc, sizeof(uint64_t) * (size_t)s->C, hipMemcpyDeviceToDevice, S(stream)));
   if (last_log_alpha_dev)
     HIP_TRY(hipMemcpyAsync(last_log_alpha_dev, s->mala_d + 5 * (size_t)s->C, sizeof(double) * (size_t)s->C, hipMemcpyDeviceToDevice, S(stream)));
+  return LMC_OK;
+}
+
+// ---- SK-ROCK: s stages of the MYULA drift per iteration, each one launch of the fused step kernel (definition: lmc_atomi.h) -----------------
+int lmc_skrock_coefficients(int32_t n_stages, double eta, double* mu, double* nu, double* kappa, double* step_factor) {
+  if (n_stages < 2 || n_stages > LMC_MAX_SKROCK_STAGES) return fail(LMC_E_INVALID, "n_stages must be 2 .. %d (got %d)", LMC_MAX_SKROCK_STAGES, n_stages);
+  if (!std::isfinite(eta) || !(eta > 0.0)) return fail(LMC_E_INVALID, "eta must be finite and > 0");
+  const int s = n_stages;
+  const double w0 = 1.0 + eta / ((double)s * s);
+  double T[LMC_MAX_SKROCK_STAGES + 1], dT[LMC_MAX_SKROCK_STAGES + 1];     // T_j(w0), T_j'(w0): T_j = 2 w0 T_{j-1} - T_{j-2}, differentiated for T_j'
+  T[0] = 1.0; T[1] = w0; dT[0] = 0.0; dT[1] = 1.0;
+  for (int j = 2; j <= s; ++j) {
+    T[j] = 2.0 * w0 * T[j - 1] - T[j - 2];
+    dT[j] = 2.0 * T[j - 1] + 2.0 * w0 * dT[j - 1] - dT[j - 2];
+  }
+  const double w1 = T[s] / dT[s];
+  for (int j = 1; j <= s; ++j) {
+    if (mu) mu[j - 1] = j == 1 ? w1 / w0 : 2.0 * w1 * T[j - 1] / T[j];
+    if (nu) nu[j - 1] = j == 1 ? s * w1 / 2.0 : 2.0 * w0 * T[j - 1] / T[j];
+    if (kappa) kappa[j - 1] = j == 1 ? s * w1 / w0 : -T[j - 2] / T[j];
+  }
+  if (step_factor) *step_factor = (s - 0.5) * (s - 0.5) * (2.0 - 4.0 * eta / 3.0) - 1.5;
+  return LMC_OK;
+}
+
+int lmc_skrock_create(const lmc_myula_config* cfg, int32_t n_stages, float eta, lmc_sampler** out) {
+  if (!out) return fail(LMC_E_INVALID, "NULL argument");
+  *out = nullptr;
+  double mu[LMC_MAX_SKROCK_STAGES], nu[LMC_MAX_SKROCK_STAGES], kappa[LMC_MAX_SKROCK_STAGES];
+  int rc = lmc_skrock_coefficients(n_stages, (double)eta, mu, nu, kappa, nullptr);
+  if (rc) return rc;
+  rc = lmc_myula_create(cfg, out);
+  if (rc) return rc;
+  lmc_sampler* s = *out;
+  *out = nullptr;
+  // every stage is a launch of the fused step kernel with coefficients of its own: what MYULA runs outside that launch has no stage form
+  if (s->tvwarm[0]) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "SK-ROCK evaluates the drift at s different points per iteration: tv_warm (a dual carried between evaluations) is not allowed"); }
+  if (s->rtmp || s->rt_tv.kc) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "SK-ROCK with tv_rtol > 0 is not built (use the fixed-count prox, tv_rtol = 0)"); }
+  if (s->prob.prox_scale) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "SK-ROCK takes a scalar epsg (array-valued epsg is MYULA's)"); }
+  s->kind = 3;
+  s->sk_stages = n_stages;
+  for (int j = 0; j < n_stages; ++j) { s->sk_mu[j] = mu[j]; s->sk_nu[j] = nu[j]; s->sk_kappa[j] = kappa[j]; }
+  const hipError_t e = hipMalloc(&s->xspare, sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W);   // the third array of the stage rotation
+  if (e != hipSuccess) return alloc_failed(s, e);
+  *out = s;
+  return LMC_OK;
+}
+
+// One iteration = n_stages launches of the step kernel over three rotating arrays (x_in = K_{j-1}, noise = K_{j-2}, x_out = K_j, always
+// distinct), after one streaming launch that forms the perturbed point of stage 1 in the array stage 1 does not write.
+static int skrock_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, hipStream_t st) {
+  const size_t per_iter = (size_t)s->C * s->prob.H * s->prob.W;
+  const int ns = s->sk_stages;
+  const double delta = s->tau, dg = delta / (double)s->gamma, q = std::sqrt(2.0 * delta);
+  s->timed = false;
+  s->last_launches = 0;
+  if (n_iters == 0) return LMC_OK;
+  if (s->timing) {   // one event pair per stage launch; the perturbation launch and the reductions stay outside
+    if ((long long)n_iters * ns > (1 << 24)) return fail(LMC_E_INVALID, "too many stage launches to time in one call");
+    while (s->ev.size() < (size_t)2 * n_iters * ns) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreate(&e));
+      s->ev.push_back(e);
+    }
+  }
+  const char* kname = nullptr;
+  for (int k = 0; k < n_iters; ++k) {
+    float* X = s->x[s->cur];            // K_0
+    float* Yb = s->x[s->cur ^ 1];       // the perturbed point, then K_2
+    float* K1 = s->xspare;
+    const uint32_t it = (uint32_t)s->iteration;
+    const float* Z = noise_dev ? noise_dev + (size_t)k * per_iter : nullptr;
+    const bool noisy = s->noise_mode != LMC_NOISE_NONE;
+    const float* in1 = X;
+    if (noisy) {   // Y = X + nu_1 q Z
+      const float coef = (float)(s->sk_nu[0] * q);
+      if (s->noise_mode == LMC_NOISE_PHILOX)
+        HIP_TRY(lmc::launch_skrock_perturb_philox(X, Yb, s->C, s->prob.H, s->prob.W, coef, s->base.key0, s->base.key1, it, s->base.chain_offset, st));
+      else
+        HIP_TRY(lmc::launch_skrock_perturb(X, Z, Yb, per_iter, coef, st));
+      in1 = Yb;
+    }
+    const float* prev2 = X;      // K_{j-2}
+    const float* prev1 = nullptr;   // K_{j-1}
+    float* free_buf = Yb;        // the array stage j writes, for j >= 2
+    for (int j = 1; j <= ns; ++j) {
+      const double mu = s->sk_mu[j - 1], nu = s->sk_nu[j - 1], kappa = s->sk_kappa[j - 1];
+      StepOverride ov{};
+      ov.t = (float)(mu * delta);
+      ov.b = (float)(mu * dg);
+      if (j == 1) {   // K_1 = Y - mu_1 delta/gamma (Y - prox(Y)) - mu_1 delta grad f(Y) + (kappa_1 - nu_1) q Z
+        ov.a = (float)(1.0 - mu * dg);
+        ov.s = noisy ? (float)((kappa - nu) * q) : 0.f;
+        ov.noise_mode = s->noise_mode;
+        ov.noise = Z;
+      } else {        // K_j = nu_j K_{j-1} + mu_j delta drift(K_{j-1}) + kappa_j K_{j-2}
+        ov.a = (float)(nu - mu * dg);
+        ov.s = (float)kappa;
+        ov.noise_mode = LMC_NOISE_INJECTED;
+        ov.noise = prev2;
+      }
+      if (s->timing) { ov.ev_begin = s->ev[2 * s->last_launches]; ov.ev_end = s->ev[2 * s->last_launches + 1]; }
+      const float* xin = j == 1 ? in1 : prev1;
+      float* xout = j == 1 ? K1 : free_buf;
+      int rc = sampler_update(s, xin, xout, true, nullptr, it, st, &kname, nullptr, nullptr, nullptr, &ov);
+      if (rc) return rc;
+      ++s->last_launches;
+      if (j >= 2) {      // the array that held K_{j-2} is free now
+        free_buf = const_cast<float*>(prev2);
+        prev2 = prev1;
+      }
+      prev1 = xout;
+    }
+    // K_s becomes the public state; the other two arrays are the spares of the next iteration
+    float* Ks = const_cast<float*>(prev1);
+    float* all[3] = {X, Yb, K1};
+    float* rest[2];
+    int nr = 0;
+    for (float* b : all) if (b != Ks) rest[nr++] = b;
+    s->x[s->cur] = Ks;
+    s->x[s->cur ^ 1] = rest[0];
+    s->xspare = rest[1];
+    if (kept(s, s->iteration)) {
+      HIP_TRY(s->reduce(Ks, st));
+      s->count += (uint64_t)s->C;
+    }
+    ++s->iteration;
+  }
+  if (kname) s->kernel_name = kname;
+  s->timed = s->timing;
   return LMC_OK;
 }
 
