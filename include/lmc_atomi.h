@@ -339,6 +339,59 @@ int lmc_skrock_coefficients(int32_t n_stages, double eta, double* mu, double* nu
  * n_stages / eta: as lmc_skrock_coefficients (LMC_E_INVALID). */
 int lmc_skrock_create(const lmc_myula_config* cfg, int32_t n_stages, float eta, lmc_sampler** out);
 
+/* ---- empirical-Bayes prior weight: SAPG (Vidal, De Bortoli, Pereyra, Durmus, SIAM J. Imaging Sci. 2020, Algorithm 1) ----------------------
+ * The weight theta = lmc_problem.prior_sigma of a prior theta g(x), g positively homogeneous of degree k, estimated by marginal maximum
+ * likelihood: one projected stochastic-gradient step on theta after every iters_per_update sampler iterations.  d/dtheta log Z(theta) =
+ * -d / (k theta), so the gradient needs only g of the current samples: gbar = the mean of g(x_c) (weight 1) over the C chains of the handle.
+ * Build-specified (the reference has no such estimator); this text is its definition.  With n the 0-based update index, d = dim_eff:
+ *   delta_n     = step_scale (n + 1)^(-step_exponent) / d
+ *   eta_{n+1}   = clamp(log(theta_n) + delta_n (d / k - theta_n gbar), log(theta_min), log(theta_max))
+ *   theta_{n+1} = exp(eta_{n+1});  a clamped step returns the bound itself, bit for bit
+ * (the log-parametrised form of the authors' code), all in double.
+ *
+ * lmc_prior_statistic: stat_dev[i] = g(x_i) with weight 1 (n_img doubles on the device): float64 sums of the fp32 per-pixel terms of
+ * lmc_energies, every image summed in a fixed order (two runs give equal bits), one streaming read of x and no data term.  Stateless; only
+ * struct_size, prior_kind, H and W of prob are read.  LMC_PRIOR_NONE / LMC_PRIOR_EPROX (no defined value): LMC_E_UNSUPPORTED. */
+int lmc_prior_statistic(const lmc_problem* prob, const float* x_dev, int64_t n_img, double* stat_dev, void* stream);
+
+/* The weight for every later launch of this handle: after the call the handle runs exactly what a sampler created with prior_sigma = sigma
+ * runs.  MYULA and SK-ROCK handles (tv_rtol > 0 included: the predicted pass counts correct themselves).  LMC_E_UNSUPPORTED: MYMALA (its
+ * cached Metropolis energy would go stale), ULPDA, tv_warm (the carried dual belongs to the old weight), prox_scale, and priors without a
+ * weight (LMC_PRIOR_NONE, LMC_PRIOR_EPROX).  sigma not finite or <= 0: LMC_E_INVALID. */
+int lmc_sampler_set_prior_sigma(lmc_sampler* s, float sigma);
+
+typedef struct lmc_sapg_config {
+  uint32_t struct_size;                  /* = sizeof(lmc_sapg_config) */
+  double theta0, theta_min, theta_max;   /* 0 < min <= theta0 <= max */
+  double dim_eff;                        /* 0 = the default of lmc_sapg_dimension */
+  double step_scale, step_exponent;      /* c0 > 0;  0.5 < p <= 1 */
+  int32_t warmup_iters;                  /* sampler iterations at theta0 before the first update, >= 0 */
+  int32_t n_updates;                     /* >= 1 */
+  int32_t iters_per_update;              /* >= 1 */
+  int32_t average_from;                  /* theta_bar = mean of theta_n, average_from < n <= n_updates;  0 <= average_from < n_updates */
+} lmc_sapg_config;
+
+/* Host only, no device needed.  lmc_sapg_dimension: the default d and the degree k of the prior of prob (struct_size, prior_kind, H, W are
+ * read): L1 (H W, 1), L2 (H W, 2), TV_ISO / TV_ANISO (H W - 1, 1: constants are in the null space of g), HAAR_L1 (H W - (H/8)(W/8), 1: the
+ * number of detail coefficients); LMC_PRIOR_NONE / LMC_PRIOR_EPROX: LMC_E_UNSUPPORTED.  Either output may be NULL.
+ * lmc_sapg_update: *theta_next = theta_{n+1} of the definition above for a prior of degree k = 1, from the same inline function the update
+ * kernel of lmc_sampler_sapg is compiled from (for degree k pass step_scale / k and k gbar: the same step).  cfg is checked as by
+ * lmc_sampler_sapg and cfg->dim_eff must be > 0 here; n < 0, theta not finite or <= 0, gbar not finite: LMC_E_INVALID. */
+int lmc_sapg_dimension(const lmc_problem* prob, double* dim_eff, double* degree);
+int lmc_sapg_update(const lmc_sapg_config* cfg, int64_t n, double theta, double gbar, double* theta_next);
+
+/* The loop on a MYULA or SK-ROCK handle: warmup_iters sampler iterations at theta0, then n_updates times { iters_per_update iterations, the
+ * statistic of the new state, the update kernel (one workgroup: the float64 mean of the statistic in a fixed order, the update above, the
+ * device traces, theta_{n+1} into a pinned host-mapped double), one host wait on an event recorded after that kernel, the new weight set as by
+ * lmc_sampler_set_prior_sigma }.  No stream synchronisation and no copy of the state.  The iteration counter advances as in lmc_sampler_step;
+ * the moment, block-moment and histogram accumulators take nothing during the call (samples at a moving theta do not belong in them; the
+ * count is unchanged).  On return the handle's weight is *theta_bar.
+ * theta_trace_host: n_updates + 1 doubles, [0] = theta0; gbar_trace_host: n_updates doubles, nullable; theta_bar nullable;
+ * noise_dev: [warmup_iters + n_updates * iters_per_update][C][H][W] with LMC_NOISE_INJECTED, else NULL.
+ * Refusals of lmc_sampler_set_prior_sigma (LMC_E_UNSUPPORTED), then a bad cfg (LMC_E_INVALID). */
+int lmc_sampler_sapg(lmc_sampler* s, const lmc_sapg_config* cfg, const float* noise_dev,
+                     double* theta_trace_host, double* gbar_trace_host, double* theta_bar, void* stream);
+
 /* x_dev: [n_chains][H][W].  x0 of algs.py:559 (copied). */
 int lmc_sampler_set_state(lmc_sampler* s, const float* x_dev, void* stream);
 int lmc_sampler_get_state(lmc_sampler* s, float* x_dev, void* stream);

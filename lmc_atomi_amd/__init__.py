@@ -9,7 +9,8 @@ from .proximal import (L1, L2, L21, TV, L2_ncvx_tv, WaveletL1, ProxOperator, fgp
                        GenGaussian, Huber, SmoothedLaplace)
 from .algs import (MYULAResult, MYULASampler, MYMALASampler, MoreauYosidaUnadjustedLangevin, MoreauYosidaMetropolisAdjustedLangevin, ULPDASampler,
                    UnadjustedLangevinPrimalDual, block_mean_var, hist_exceedance, hist_quantiles, mean_var_from_moments, pixel_histogram,
-                   set_step_variant, set_cg_tolerance, SKROCKSampler, StabilisedLangevin, skrock_coefficients, skrock_step_bound)
+                   set_step_variant, set_cg_tolerance, SKROCKSampler, StabilisedLangevin, skrock_coefficients, skrock_step_bound,
+                   SAPGResult, EstimatePriorWeight, prior_statistic, sapg_dimension, sapg_update)
 
 from . import diagnostics, metrics
 from .diagnostics import ChainTrace, chain_probes, ess, split_rhat
@@ -27,5 +28,6 @@ __all__ = [
     "block_mean_var", "allreduce_sampler_block_moments",
     "pixel_histogram", "hist_quantiles", "hist_exceedance", "allreduce_sampler_histogram",
     "SKROCKSampler", "StabilisedLangevin", "skrock_coefficients", "skrock_step_bound",
+    "SAPGResult", "EstimatePriorWeight", "prior_statistic", "sapg_dimension", "sapg_update",
 ]
 __version__ = "0.2.0"

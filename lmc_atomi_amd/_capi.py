@@ -120,6 +120,19 @@ class lmc_ulpda_config(C.Structure):
     ]
 
 
+class lmc_sapg_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("theta0", C.c_double), ("theta_min", C.c_double), ("theta_max", C.c_double),
+        ("dim_eff", C.c_double),
+        ("step_scale", C.c_double), ("step_exponent", C.c_double),
+        ("warmup_iters", C.c_int32),
+        ("n_updates", C.c_int32),
+        ("iters_per_update", C.c_int32),
+        ("average_from", C.c_int32),
+    ]
+
+
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 _D = C.POINTER(C.c_double)
@@ -139,6 +152,11 @@ _SIGNATURES = {
     "lmc_sampler_get_acceptance": (C.c_int, [_P, _P, _P, _P]),
     "lmc_skrock_coefficients": (C.c_int, [C.c_int32, C.c_double, _D, _D, _D, _D]),
     "lmc_skrock_create": (C.c_int, [C.POINTER(lmc_myula_config), C.c_int32, C.c_float, C.POINTER(_P)]),
+    "lmc_prior_statistic": (C.c_int, [C.POINTER(lmc_problem), _P, C.c_int64, _P, _P]),
+    "lmc_sampler_set_prior_sigma": (C.c_int, [_P, C.c_float]),
+    "lmc_sapg_dimension": (C.c_int, [C.POINTER(lmc_problem), _D, _D]),
+    "lmc_sapg_update": (C.c_int, [C.POINTER(lmc_sapg_config), C.c_int64, C.c_double, C.c_double, _D]),
+    "lmc_sampler_sapg": (C.c_int, [_P, C.POINTER(lmc_sapg_config), _P, _D, _D, _D, _P]),
     "lmc_set_cg_tolerance": (C.c_float, [C.c_float]),
     "lmc_chain_probes": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "lmc_haar_l1_prox": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),

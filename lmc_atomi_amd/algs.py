@@ -209,6 +209,124 @@ def _scale_summaries(smp):
     return means, stds
 
 
+class SAPGResult:
+    """Outcome of a SAPG estimation: ``theta`` (the averaged weight), ``theta_trace`` (``n_updates + 1`` float64, entry 0 = theta0),
+    ``stat_trace`` (``n_updates`` float64: the mean over the chains of the prior value with weight 1 at every update), ``dim_eff`` and
+    ``degree`` as used; ``state`` only from :func:`EstimatePriorWeight`."""
+
+    def __init__(self, theta, theta_trace, stat_trace, dim_eff, degree, state=None):
+        self.theta = theta
+        self.theta_trace = theta_trace
+        self.stat_trace = stat_trace
+        self.dim_eff = dim_eff
+        self.degree = degree
+        self.state = state
+
+
+def _check_sapg(rc):
+    """Status of a weight / SAPG call: LMC_E_INVALID -> ValueError, LMC_E_UNSUPPORTED -> NotImplementedError (the module's convention)."""
+    if rc in (-1, -2):
+        msg = _dev.lib().lmc_last_error().decode("utf-8", "replace")
+        raise (ValueError if rc == -1 else NotImplementedError)(msg)
+    _capi.check(rc)
+
+
+def _prior_weight(proxg):
+    w = _prior_descriptor(proxg).get("prior_sigma")
+    if w is None:
+        raise NotImplementedError(f"{type(proxg).__name__} has no weight to estimate")
+    return float(w)
+
+
+def _stat_problem(proxg, dims):
+    """The part of an ``lmc_problem`` the prior statistic and its dimension read: no device buffer."""
+    p = _capi.lmc_problem()
+    p.struct_size = C.sizeof(_capi.lmc_problem)
+    p.H, p.W = int(dims[0]), int(dims[1])
+    p.prior_kind = _prior_descriptor(proxg)["prior_kind"]
+    return p
+
+
+def sapg_dimension(proxg, dims=None):
+    """``(dim_eff, degree)`` the SAPG update uses by default for the prior ``proxg`` on ``dims`` images: l1 ``(H W, 1)``, l2 ``(H W, 2)``,
+    TV ``(H W - 1, 1)``, Haar-l1 ``(H W - (H/8)(W/8), 1)``.  Needs no GPU; a prior without a value raises ``NotImplementedError``."""
+    if dims is None:
+        dims = getattr(proxg, "dims", None)
+    if dims is None:
+        raise ValueError("image shape unknown: pass dims=(ny, nx)")
+    d, k = C.c_double(), C.c_double()
+    _check_sapg(_dev.lib().lmc_sapg_dimension(C.byref(_stat_problem(proxg, dims)), C.byref(d), C.byref(k)))
+    return d.value, k.value
+
+
+def _sapg_config(n_updates, theta_bounds, theta0, warmup=0, iters_per_update=1, step_scale=10., step_exponent=0.8, average_from=None, dim_eff=None):
+    """A checked ``lmc_sapg_config``; every argument error is a ``ValueError`` raised here, before any device call."""
+    try:
+        lo, hi = (float(v) for v in theta_bounds)
+    except (TypeError, ValueError):
+        raise ValueError("theta_bounds must be a pair (lo, hi)") from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo <= hi):
+        raise ValueError(f"theta_bounds must satisfy 0 < lo <= hi (got {theta_bounds!r})")
+    theta0 = float(theta0)
+    if not lo <= theta0 <= hi:
+        raise ValueError(f"theta0 = {theta0} lies outside theta_bounds = ({lo}, {hi})")
+    if not 0.5 < float(step_exponent) <= 1.0:
+        raise ValueError(f"step_exponent must be in (0.5, 1] (got {step_exponent})")
+    if not (np.isfinite(step_scale) and float(step_scale) > 0.0):
+        raise ValueError(f"step_scale must be > 0 (got {step_scale})")
+    n_updates, warmup, iters_per_update = int(n_updates), int(warmup), int(iters_per_update)
+    if n_updates < 1 or warmup < 0 or iters_per_update < 1:
+        raise ValueError("n_updates >= 1, warmup >= 0 and iters_per_update >= 1 are required")
+    average_from = n_updates // 2 if average_from is None else int(average_from)
+    if not 0 <= average_from < n_updates:
+        raise ValueError(f"average_from must be in 0 .. n_updates - 1 (got {average_from})")
+    dim_eff = 0.0 if dim_eff is None else float(dim_eff)
+    if not (np.isfinite(dim_eff) and dim_eff >= 0.0):
+        raise ValueError(f"dim_eff must be > 0, or None for the default (got {dim_eff})")
+    cfg = _capi.lmc_sapg_config()
+    cfg.struct_size = C.sizeof(_capi.lmc_sapg_config)
+    cfg.theta0, cfg.theta_min, cfg.theta_max = theta0, lo, hi
+    cfg.dim_eff = dim_eff
+    cfg.step_scale, cfg.step_exponent = float(step_scale), float(step_exponent)
+    cfg.warmup_iters, cfg.n_updates, cfg.iters_per_update, cfg.average_from = warmup, n_updates, iters_per_update, average_from
+    return cfg
+
+
+def sapg_update(theta, gbar, n, dim_eff, degree=1.0, theta_bounds=(1e-3, 1e2), step_scale=10., step_exponent=0.8):
+    """One SAPG update on the host (``lmc_sapg_update``, the function the device kernel is compiled from): ``theta_{n+1}`` from ``theta_n``, the
+    mean prior value ``gbar`` and the 0-based update index ``n``.  Needs no GPU.  The library's entry point is the degree-1 update; a prior of
+    degree k is the same step with ``step_scale / k`` and ``k gbar``."""
+    k = float(degree)
+    if not k > 0.0:
+        raise ValueError("degree must be > 0")
+    if not float(dim_eff) > 0.0:
+        raise ValueError("dim_eff must be > 0")
+    cfg = _sapg_config(1, theta_bounds, theta_bounds[0], step_scale=float(step_scale) / k, step_exponent=step_exponent, dim_eff=dim_eff)
+    out = C.c_double()
+    _check_sapg(_dev.lib().lmc_sapg_update(C.byref(cfg), int(n), float(theta), k * float(gbar), C.byref(out)))
+    return out.value
+
+
+def prior_statistic(proxg, x, dims=None):
+    """``g(x_i)`` with weight 1 for every image of ``x`` (float64 tensor in HBM, one entry per image): what the SAPG update averages over the
+    chains.  One streaming read, no data term; every image is summed in a fixed order."""
+    if dims is None:
+        dims = getattr(proxg, "dims", None)
+    if dims is None:
+        if not (hasattr(x, "shape") and len(x.shape) >= 2):
+            raise ValueError("image shape unknown: pass dims=(ny, nx)")
+        dims = tuple(x.shape[-2:])
+    p = _stat_problem(proxg, dims)
+    xt = _dev.to_dev(x)
+    n = p.H * p.W
+    if xt.numel() % n or xt.numel() == 0:
+        raise ValueError(f"operand of shape {tuple(xt.shape)} is not a batch of {tuple(dims)} images")
+    out = torch.empty(xt.numel() // n, dtype=torch.float64, device=xt.device)
+    with torch.cuda.device(xt.device):
+        _check_sapg(_dev.lib().lmc_prior_statistic(C.byref(p), _dev.ptr(xt), xt.numel() // n, _dev.ptr(out), _dev.stream_ptr()))
+    return out
+
+
 class MYULASampler:
     """Many-chain MYULA on one GPU: owns an ``lmc_sampler`` handle.
 
@@ -246,6 +364,7 @@ class MYULASampler:
             opts["prox_scale"] = self._epsg_array(epsg)
             epsg = 1.0
         self._problem = _Problem(self.dims, _data_descriptor(proxf), _prior_descriptor(proxg), self.device, options=opts)
+        self.prior_weight = float(self._problem.c.prior_sigma)      # follows set_prior_weight / estimate_prior_weight
         cfg = _capi.lmc_myula_config()
         cfg.struct_size = C.sizeof(_capi.lmc_myula_config)
         cfg.problem = self._problem.c
@@ -272,6 +391,7 @@ class MYULASampler:
 
     moment_scales = ()
     hist_bins = hist_lo = hist_scale = None
+    prior_weight = None
 
     def _set_histogram(self, hist):
         """``hist``: None or (B, lo, scale) as :func:`_check_histogram` returns them; the sampler keeps fp32 device copies of lo and scale."""
@@ -385,6 +505,42 @@ class MYULASampler:
         rr = (C.c_uint64 * 4)()
         _capi.check(_dev.lib().lmc_sampler_tv_exit_stats(self._h, {"prior": 0, "ncvx": 1}[which], _dev.ptr(passes), rr, _dev.stream_ptr(self.device)))
         return passes, [int(v) for v in rr]
+
+    # -- empirical-Bayes prior weight (SAPG; definition in include/lmc_atomi.h) -----------------
+    def set_prior_weight(self, theta):
+        """The weight of ``proxg`` (``lmc_problem.prior_sigma``) for every later launch of this sampler: afterwards it runs exactly what a sampler
+        created with that weight runs.  MYULA and SK-ROCK; MYMALA, ULPDA, a warm-started TV dual, array-valued ``epsg`` and priors without a
+        weight raise ``NotImplementedError``, a weight that is not finite and positive ``ValueError``."""
+        _check_sapg(_dev.lib().lmc_sampler_set_prior_sigma(self._h, float(theta)))
+        self.prior_weight = float(np.float32(theta))
+
+    def estimate_prior_weight(self, n_updates, theta_bounds, theta0=None, warmup=0, iters_per_update=1, step_scale=10., step_exponent=0.8,
+                              average_from=None, dim_eff=None, noise=None):
+        """SAPG estimate of the weight of ``proxg`` by marginal maximum likelihood (Vidal, De Bortoli, Pereyra, Durmus 2020, Algorithm 1), on
+        the device: ``warmup`` iterations at ``theta0`` (default: the weight of ``proxg``), then ``n_updates`` times { ``iters_per_update``
+        iterations, the mean over the chains of the prior value of the new state, one projected step on log theta with step
+        ``step_scale (n + 1)^(-step_exponent) / dim_eff`` }, theta kept inside ``theta_bounds = (lo, hi)``.  Returns a :class:`SAPGResult`
+        whose ``theta`` is the mean of the iterates after update ``average_from`` (default ``n_updates // 2``); the sampler's weight is that
+        mean afterwards.  The moment accumulators take nothing during the call; the iteration counter advances.  ``noise`` (only with
+        noise='injected'): ``[warmup + n_updates * iters_per_update, n_chains, H, W]``.  Argument errors raise ``ValueError``, what the
+        library has no path for ``NotImplementedError``."""
+        if theta0 is None:
+            theta0 = _prior_weight(self.proxg)
+        cfg = _sapg_config(n_updates, theta_bounds, theta0, warmup, iters_per_update, step_scale, step_exponent, average_from, dim_eff)
+        d, k = sapg_dimension(self.proxg, self.dims)
+        n_iters = cfg.warmup_iters + cfg.n_updates * cfg.iters_per_update
+        nt = None
+        if noise is not None:
+            nt = _dev.to_dev(noise, self.device)
+            if nt.numel() != n_iters * self.n_chains * self.dims[0] * self.dims[1]:
+                raise ValueError("noise must have shape [warmup + n_updates * iters_per_update, n_chains, H, W]")
+        trace = np.zeros(cfg.n_updates + 1, dtype=np.float64)
+        stat = np.zeros(cfg.n_updates, dtype=np.float64)
+        bar = C.c_double()
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        _check_sapg(_dev.lib().lmc_sampler_sapg(self._h, C.byref(cfg), _dev.ptr(nt), dp(trace), dp(stat), C.byref(bar), _dev.stream_ptr(self.device)))
+        self.prior_weight = float(np.float32(bar.value))
+        return SAPGResult(float(bar.value), trace, stat, float(cfg.dim_eff) if cfg.dim_eff > 0 else d, k)
 
     # -- diagnostics ---------------------------------------------------------------------
     def energies(self):
@@ -917,6 +1073,44 @@ def StabilisedLangevin(proxf, proxg, x0, tau, gamma=.1, epsg=1., niter=10, n_sta
                           hist=_hist_summaries(smp, quantiles))
         res.n_stages = smp.n_stages
         res.gradient_evaluations = int(niter) * smp.n_stages
+        return res
+    finally:
+        smp.close()
+
+
+def EstimatePriorWeight(proxf, proxg, x0, tau, gamma, n_updates, theta_bounds, theta0=None, warmup=0, iters_per_update=1, step_scale=10.,
+                        step_exponent=0.8, average_from=None, dim_eff=None, epsg=1., seed=0, *, n_chains=1, sampler="myula", n_stages=10, eta=0.05,
+                        dims=None, chain_offset=0, device=None):
+    """Empirical-Bayes weight of ``proxg`` in one call: a :class:`MYULASampler` (``sampler='myula'``) or :class:`SKROCKSampler`
+    (``'skrock'``, ``n_stages`` / ``eta``) of ``n_chains`` chains started at ``x0``, then :meth:`MYULASampler.estimate_prior_weight`.
+    Returns its :class:`SAPGResult` with the final ``state`` ``[n_chains, H, W]``.  The gradient estimate is the mean of the prior value over
+    the chains, so many chains help directly.  Argument errors (bounds, ``theta0`` outside them, exponent outside (0.5, 1]) raise ``ValueError``
+    and unsupported combinations ``NotImplementedError``, both before a sampler exists."""
+    if sampler not in ("myula", "skrock"):
+        raise NotImplementedError(f"sampler {sampler!r}: the weight is estimated with 'myula' or 'skrock' (MYMALA caches its Metropolis energy, "
+                                  "ULPDA has no setter)")
+    if dims is None:
+        dims = getattr(proxf, "dims", None) or getattr(proxg, "dims", None)
+    if dims is None:
+        raise ValueError("image shape unknown: pass dims=(ny, nx)")
+    prior = _prior_descriptor(proxg)
+    if theta0 is None:
+        theta0 = _prior_weight(proxg)
+    _sapg_config(n_updates, theta_bounds, theta0, warmup, iters_per_update, step_scale, step_exponent, average_from, dim_eff)
+    if prior["prior_kind"] in (_capi.PRIOR_NONE, _capi.PRIOR_EPROX):
+        raise NotImplementedError(f"{type(proxg).__name__} has no value g(x): its weight cannot be estimated")
+    if prior.get("tv_warm"):
+        raise NotImplementedError("a warm-started TV dual (warm=True) belongs to the weight it was formed with: the weight cannot move")
+    if np.asarray(epsg).size > 1:
+        raise NotImplementedError("array-valued epsg carries the weights itself: the scalar weight cannot be estimated")
+    kw = dict(n_chains=int(n_chains), tau=tau, gamma=gamma, epsg=epsg, seed=seed, chain_offset=chain_offset, device=device)
+    smp = SKROCKSampler(proxf, proxg, dims, n_stages=n_stages, eta=eta, **kw) if sampler == "skrock" else MYULASampler(proxf, proxg, dims, **kw)
+    try:
+        smp.set_state(x0)
+        res = smp.estimate_prior_weight(n_updates, theta_bounds, theta0=theta0, warmup=warmup, iters_per_update=iters_per_update,
+                                        step_scale=step_scale, step_exponent=step_exponent, average_from=average_from, dim_eff=dim_eff)
+        res.state = smp.get_state()
+        torch.cuda.current_stream(smp.device).synchronize()
         return res
     finally:
         smp.close()

@@ -243,6 +243,15 @@ struct lmc_sampler {
   // SK-ROCK state (kind == 3): stage count and the stage coefficients (entry j - 1 = stage j); the third state array of its rotation is xspare
   int sk_stages = 0;
   double sk_mu[LMC_MAX_SKROCK_STAGES] = {}, sk_nu[LMC_MAX_SKROCK_STAGES] = {}, sk_kappa[LMC_MAX_SKROCK_STAGES] = {};
+  // lmc_sampler_sapg (allocated at its first call): the per-chain statistic followed by its partial sums, the device traces of theta and gbar,
+  // the pinned host-mapped pair (theta_{n+1}, gbar) with its device address, the event recorded after the update kernel
+  bool suspend_moments = false;          // the accumulators take nothing while the estimation runs
+  double* sapg_stat = nullptr;
+  double* sapg_trace = nullptr;
+  size_t sapg_trace_n = 0;               // doubles in sapg_trace
+  double* sapg_host = nullptr;
+  double* sapg_host_dev = nullptr;
+  hipEvent_t sapg_ev = nullptr;
   // moment reductions on a side stream, overlapping the next step kernel (HBM-bound reduction under a VALU-bound step kernel); which of them are
   // still running is known only inside one lmc_sampler_step call (SideMoments), which joins them all before it returns
   hipStream_t side = nullptr;
@@ -253,3 +262,12 @@ struct lmc_sampler {
   int last_launches = 0;
   std::string kernel_name;
 };
+
+namespace lmc::host {
+// ---- lmc_sampler.hip ----
+// s->base of a MYULA / MYMALA / SK-ROCK handle from s->prob and the handle's steps, seed and chain ids: the one path of lmc_myula_create and
+// lmc_sampler_set_prior_sigma
+int rebuild_base(lmc_sampler* s);
+// what lmc_sampler_set_prior_sigma and lmc_sampler_sapg refuse (LMC_E_UNSUPPORTED), else LMC_OK
+int check_weight_settable(const lmc_sampler* s);
+}  // namespace lmc::host

@@ -162,6 +162,18 @@ hipError_t mala_select(const int* flag, float* x, float* mx, const float* xp, co
 }  // namespace lmc
 
 namespace lmc {
+// SAPG estimation of the prior weight (lmc_sapg.hip).  stat[i] = g(x_i) with weight 1 for LMC_PRIOR_L2 / L1 / TV_ISO / TV_ANISO / HAAR_L1 (other
+// kinds: hipErrorInvalidValue), every image summed in a fixed order.  An image is read by prior_stat_segments(n_img, H) workgroups; when that is
+// more than one, `part` holds n_img * segments doubles for their partial sums (else it may be NULL).
+struct SapgParams;
+int prior_stat_segments(int64_t n_img, int H);
+hipError_t launch_prior_stat(const float* x, int64_t n_img, int H, int W, int prior_kind, double* stat, double* part, hipStream_t st);
+// one workgroup: gbar = mean of stat[C] (fixed order), theta_trace[n + 1] = the update of `theta`, gbar_trace[n] = gbar, host2[0 .. 1] = both
+hipError_t launch_sapg_update(const double* stat, int C, const SapgParams& P, long long n, double theta, double* theta_trace, double* gbar_trace,
+                              double* host2, hipStream_t st);
+}  // namespace lmc
+
+namespace lmc {
 // SK-ROCK stage 1 (lmc_skrock.hip): out = x + coef * Z, Z the Philox / Box-Muller field of `iteration` that the step kernels and launch_noise draw
 // (same device functions, same counter layout: bit for bit that field), or the caller's field xi.  x, out (and xi): [C][H][W] / n floats, distinct.
 hipError_t launch_skrock_perturb_philox(const float* x, float* out, int64_t C, int H, int W, float coef, uint32_t key0, uint32_t key1,

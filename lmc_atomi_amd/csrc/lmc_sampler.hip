@@ -41,7 +41,46 @@ int alloc_failed(lmc_sampler* s, hipError_t e) {
 }
 }  // namespace
 
+namespace lmc::host {
+int rebuild_base(lmc_sampler* s) {
+  // x <- (1 - tau/gamma) x - tau grad f(x) + (tau/gamma) prox_{epsg*gamma*g}(x) + sqrt(2 tau) xi   (algs.py:569)
+  lmc::StepArgs A;
+  const int rc = make_step_args(s->prob, 1.f - s->tau / s->gamma, s->tau, s->tau / s->gamma, s->epsg * s->gamma,
+                                std::sqrt(2.f * s->tau), A);
+  if (rc) return rc;
+  s->base = A;
+  s->base.C = s->C;
+  s->base.noise_mode = s->noise_mode;
+  s->base.key0 = (uint32_t)(s->seed & 0xFFFFFFFFu);
+  s->base.key1 = (uint32_t)(s->seed >> 32);
+  s->base.chain_offset = (uint32_t)s->chain_offset;
+  return LMC_OK;
+}
+
+int check_weight_settable(const lmc_sampler* s) {
+  if (s->kind == 2) return fail(LMC_E_UNSUPPORTED, "MYMALA caches the Metropolis energy of its state at the weight it was created with: the weight cannot change");
+  if (s->kind == 1) return fail(LMC_E_UNSUPPORTED, "the prior weight of a ULPDA handle cannot change");
+  if (s->prob.tv_warm) return fail(LMC_E_UNSUPPORTED, "tv_warm carries a dual that belongs to the weight it was formed with: the weight cannot change");
+  if (s->prob.prox_scale) return fail(LMC_E_UNSUPPORTED, "prox_scale (array-valued epsg) carries the weights itself: the scalar weight cannot change");
+  if (s->prob.prior_kind == LMC_PRIOR_NONE || s->prob.prior_kind == LMC_PRIOR_EPROX)
+    return fail(LMC_E_UNSUPPORTED, "prior_kind %d has no weight prior_sigma", s->prob.prior_kind);
+  return LMC_OK;
+}
+}  // namespace lmc::host
+
 extern "C" {
+
+int lmc_sampler_set_prior_sigma(lmc_sampler* s, float sigma) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  int rc = check_weight_settable(s);
+  if (rc) return rc;
+  if (!std::isfinite(sigma) || !(sigma > 0.f)) return fail(LMC_E_INVALID, "prior_sigma must be finite and > 0 (got %g)", (double)sigma);
+  const float old = s->prob.prior_sigma;
+  s->prob.prior_sigma = sigma;
+  rc = rebuild_base(s);
+  if (rc) s->prob.prior_sigma = old;     // s->base is untouched by a failed rebuild
+  return rc;
+}
 
 // ---- sampler ---------------------------------------------------------------------------------
 
@@ -66,15 +105,8 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   s->seed = cfg->seed;
   s->noise_mode = cfg->noise_mode;
   s->moments = cfg->moments; s->burn_in = cfg->burn_in; s->thin = cfg->thin < 1 ? 1 : cfg->thin;
-  // x <- (1 - tau/gamma) x - tau grad f(x) + (tau/gamma) prox_{epsg*gamma*g}(x) + sqrt(2 tau) xi   (algs.py:569)
-  rc = make_step_args(s->prob, 1.f - s->tau / s->gamma, s->tau, s->tau / s->gamma, s->epsg * s->gamma,
-                      std::sqrt(2.f * s->tau), s->base);
+  rc = rebuild_base(s);
   if (rc) { delete s; return rc; }
-  s->base.C = s->C;
-  s->base.noise_mode = s->noise_mode;
-  s->base.key0 = (uint32_t)(s->seed & 0xFFFFFFFFu);
-  s->base.key1 = (uint32_t)(s->seed >> 32);
-  s->base.chain_offset = (uint32_t)s->chain_offset;
   const size_t nbytes = sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W;
   hipError_t e = hipMalloc(&s->x[0], nbytes);
   if (e == hipSuccess) e = hipMalloc(&s->x[1], nbytes);
@@ -156,6 +188,10 @@ void lmc_sampler_destroy(lmc_sampler* s) {
   if (s->s2) (void)hipFree(s->s2);
   if (s->packed) (void)hipFree(s->packed);
   if (s->bs2) (void)hipFree(s->bs2);
+  if (s->sapg_stat) (void)hipFree(s->sapg_stat);
+  if (s->sapg_trace) (void)hipFree(s->sapg_trace);
+  if (s->sapg_host) (void)hipHostFree(s->sapg_host);
+  if (s->sapg_ev) (void)hipEventDestroy(s->sapg_ev);
   release_histogram(s);
   for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
   if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }
@@ -200,8 +236,8 @@ static int sampler_energies_at(lmc_sampler* s, const float* x, double* f_out_dev
   return LMC_OK;
 }
 
-// an iterate the posterior-moment accumulators keep: after burn-in, every thin-th
-static bool kept(const lmc_sampler* s, int64_t it) { return s->moments && it >= s->burn_in && (it - s->burn_in) % s->thin == 0; }
+// an iterate the posterior-moment accumulators keep: after burn-in, every thin-th (none while lmc_sampler_sapg runs)
+static bool kept(const lmc_sampler* s, int64_t it) { return s->moments && !s->suspend_moments && it >= s->burn_in && (it - s->burn_in) % s->thin == 0; }
 
 // ME-TV: the inner prox of the Moreau-envelope term at A.x_in, which the fused step then takes as its extra gradient term
 static int me_tv_extra(lmc_sampler* s, lmc::StepArgs& A, hipStream_t st) {
@@ -468,7 +504,7 @@ static int myula_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, h
   // fits beside them): 128 / 192 / 256 / 384 / 512 workgroups of 256 threads: 1.725 / 1.729 / 1.709 / 1.710 / 1.771 ms per step; one-wave workgroups and a chain
   // unroll of 2 or 8 instead of 4 are equal at equal wave counts, never better: 256 stays.
   // (lmc_problem.moments_bg_workgroups / LMC_MOMENTS_BG_WGS: fixed at creation)
-  const bool overlap = !s->timing && s->pol_overlap >= 0 && s->moments && n_iters > 1;
+  const bool overlap = !s->timing && s->pol_overlap >= 0 && s->moments && !s->suspend_moments && n_iters > 1;
   const int bg_wgs = s->pol_bg_wgs >= 0 ? s->pol_bg_wgs : ((long long)per_iter <= (1LL << 25) ? 128 : 256);   // 0: the full-speed kernel
   if (overlap && !s->side) {
     int prio_least = 0, prio_greatest = 0;     // lowest priority: the step kernel's workgroups go first
