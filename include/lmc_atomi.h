@@ -96,6 +96,7 @@ typedef enum lmc_noise_mode {
 #define LMC_MAX_BLUR 9       /* kernels up to 9x9 */
 #define LMC_MAX_TV_ITERS 64
 #define LMC_MAX_SKROCK_STAGES 64
+#define LMC_MAX_CHAIN_GROUPS 64
 
 /* Geometry + potential U(x) = f(x) + eps*g(x).  Plain data; copied by the callee. */
 typedef struct lmc_problem {
@@ -247,6 +248,13 @@ int lmc_chain_probes(const float* x_dev, float* out_dev, int64_t n_img, int32_t 
 int lmc_pixel_histogram(const float* x_dev, int64_t C, int32_t H, int32_t W, int32_t n_bins,
                         const float* lo_dev, const float* scale_dev, uint64_t* counts_dev, void* stream);
 
+/* Stateless, operator level: ADDS the chain-group moments of x[C][H][W] into sum_dev and sumsq_dev ([n_groups*H*W] float64 each; groups and
+ * arithmetic as documented at lmc_sampler_set_chain_groups; 2 <= n_groups <= LMC_MAX_CHAIN_GROUPS, chain_offset >= 0).  One owner per (group,
+ * pixel) and launch, no atomics: the same call on the same arrays gives the same bits, and calls that share sum_dev / sumsq_dev must be ordered
+ * (one stream). */
+int lmc_group_moments(const float* x_dev, int64_t C, int64_t chain_offset, int32_t H, int32_t W, int32_t n_groups,
+                      double* sum_dev, double* sumsq_dev, void* stream);
+
 /* Per-pixel projection of the stacked field y[2][H][W] onto the l2 ball (isotropic != 0) or the
  * box (isotropic == 0) of radius `radius`: L21.proxdual / L1.proxdual (algs.py:436,448). */
 int lmc_dual_project(const float* y_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W,
@@ -384,7 +392,7 @@ int lmc_sapg_update(const lmc_sapg_config* cfg, int64_t n, double theta, double 
  * statistic of the new state, the update kernel (one workgroup: the float64 mean of the statistic in a fixed order, the update above, the
  * device traces, theta_{n+1} into a pinned host-mapped double), one host wait on an event recorded after that kernel, the new weight set as by
  * lmc_sampler_set_prior_sigma }.  No stream synchronisation and no copy of the state.  The iteration counter advances as in lmc_sampler_step;
- * the moment, block-moment and histogram accumulators take nothing during the call (samples at a moving theta do not belong in them; the
+ * the moment, block-moment, histogram and chain-group accumulators take nothing during the call (samples at a moving theta do not belong in them; the
  * count is unchanged).  On return the handle's weight is *theta_bar.
  * theta_trace_host: n_updates + 1 doubles, [0] = theta0; gbar_trace_host: n_updates doubles, nullable; theta_bar nullable;
  * noise_dev: [warmup_iters + n_updates * iters_per_update][C][H][W] with LMC_NOISE_INJECTED, else NULL.
@@ -431,6 +439,28 @@ int lmc_sampler_get_block_moments(lmc_sampler* s, int32_t scale, double* sum_dev
 int lmc_sampler_set_histogram(lmc_sampler* s, int32_t n_bins, const float* lo_dev, const float* scale_dev);
 /* counts_dev: [(n_bins+2)*H*W] uint64 (device, nullable).  A handle without a histogram: LMC_E_INVALID. */
 int lmc_sampler_get_histogram(lmc_sampler* s, uint64_t* counts_dev, uint64_t* count, void* stream);
+/* Chain-group moments: Monte-Carlo error of the pixel moments from the scatter of chain groups.  Chain c of the handle has global id
+ * chain_offset + c; its group is that id mod G, so every sharding of the chains over GPUs gives every rank all groups.  Over the same kept
+ * samples as the pixel moments the library keeps, in float64, A[g][p] = sum x and B[g][p] = sum x^2 per group g and pixel p ([G][H][W] each);
+ * the fp32 sample is widened first, so x^2 is exact in float64.  n[g] = (kept iterations) x (chains of the handle in group g), computed on the
+ * host; a group without a local chain has n = 0 and its accumulators stay zero.
+ * With N = sum n, m_g = A_g / n_g, v_g = B_g / n_g - m_g^2, m = sum A_g / N, v = sum B_g / N - m^2 (float64, per pixel), the summaries are
+ *   mcse_mean = sqrt(s / N),   s  = sum_g n_g (m_g - m)^2 / (G - 1)
+ *   mcse_var  = sqrt(sv / N),  sv = sum_g n_g (v_g - vbar)^2 / (G - 1),  vbar = sum n_g v_g / N
+ *   ess       = N v / s        (+inf where s = 0, not a clamp)
+ * For equal n_g this is the textbook standard error of G independent replicate means -- it includes the autocorrelation of the chains and needs
+ * neither lags nor a stored iterate; the weights keep it unbiased when the chain count is no multiple of G.  The relative precision of s is
+ * sqrt(2 / (G - 1)): about 25 % at G = 32 and 18 % at G = 64, which is why the cap is 64 and not 8.  The library keeps the accumulators; the
+ * summaries are host arithmetic on them (mcse_from_group_moments in the Python package).
+ * The pass is a launch of its own after the moment reduction (and the histogram) of the same iterate, one owner per (group, pixel) and no
+ * atomics: equal runs give equal bits.  A sampler without groups launches exactly what it launches without this call.  lmc_sampler_sapg
+ * suspends these accumulators with the others.
+ * n_groups = 0 turns them off; n_groups may exceed the handle's chain count (empty groups).  Needs cfg.moments != 0 and count == 0 (else
+ * LMC_E_STATE); n_groups outside {0, 2 .. LMC_MAX_CHAIN_GROUPS}: LMC_E_INVALID.  lmc_sampler_reset_moments zeroes the accumulators too. */
+int lmc_sampler_set_chain_groups(lmc_sampler* s, int32_t n_groups);
+/* sum_dev, sumsq_dev: [n_groups*H*W] double (device, nullable); counts_host: [n_groups] (host, nullable).  A handle without groups:
+ * LMC_E_INVALID. */
+int lmc_sampler_get_group_moments(lmc_sampler* s, double* sum_dev, double* sumsq_dev, uint64_t* counts_host, void* stream);
 /* per-chain energies f(x_c), g(x_c) of the current state (device double [n_chains]) */
 int lmc_sampler_energies(lmc_sampler* s, double* f_out_dev, double* g_out_dev, void* stream);
 /* the noise field xi[n_chains][H][W] the sampler draws at `iteration` (parity rung R3) */
@@ -474,6 +504,9 @@ int lmc_allreduce_moments(lmc_sampler* s, void* rccl_comm, double* sum_dev, doub
 int lmc_allreduce_block_moments(lmc_sampler* s, void* rccl_comm, int32_t scale, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream);
 /* one ncclAllReduce(ncclUint64, sum) of counts + count; rccl_comm NULL = a job of one rank (plain copy).  A handle without a histogram: LMC_E_INVALID. */
 int lmc_allreduce_histogram(lmc_sampler* s, void* rccl_comm, uint64_t* counts_dev, uint64_t* count, void* stream);
+/* one ncclAllReduce(ncclFloat64, sum) of the packed {A, B, n} (the counts travel as doubles, exact far below 2^53); rccl_comm NULL = a job of one
+ * rank (plain copy).  A handle without groups: LMC_E_INVALID. */
+int lmc_allreduce_group_moments(lmc_sampler* s, void* rccl_comm, double* sum_dev, double* sumsq_dev, uint64_t* counts_host, void* stream);
 
 /* ---- ULPDA sampler (replaces algs.UnadjustedLangevinPrimalDual, algs.py:295-474) --------------------
  *   x    <- prox_{tau f}(x - tau (A^T y + z)) + sqrt(2 tau) xi      (algs.py:440/446)

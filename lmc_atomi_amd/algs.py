@@ -199,6 +199,108 @@ def _hist_summaries(smp, quantiles):
     return counts, smp.hist_lo, smp.hist_scale, {qv: vals[i] for i, qv in enumerate(qs)}
 
 
+MAX_CHAIN_GROUPS = _capi.MAX_CHAIN_GROUPS
+
+
+def _check_chain_groups(chain_groups, moments, n_chains=None):
+    """``None`` or the number of chain groups a sampler is asked to keep moments for; raises before any device call.  ``n_chains``: the entry
+    points refuse more groups than chains (an empty group has no mean); a sampler accepts them, as the library does."""
+    if chain_groups is None:
+        return None
+    G = int(chain_groups)
+    if not 2 <= G <= MAX_CHAIN_GROUPS:
+        raise ValueError(f"chain_groups must be 2 .. {MAX_CHAIN_GROUPS}, got {G}")
+    if not moments:
+        raise ValueError("chain_groups needs moments=True: the group moments are accumulated over the kept samples of the pixel moments")
+    if n_chains is not None and G > int(n_chains):
+        raise ValueError(f"chain_groups = {G} exceeds n_chains = {int(n_chains)}: every group needs a chain")
+    return G
+
+
+def group_moments(x, n_groups, chain_offset=0, out=None):
+    """Chain-group moments of the images ``x`` (``[C, H, W]``): ``(S1, S2)``, float64 ``[n_groups, H, W]`` on the device, the sums of x and of
+    x^2 over the chains of every group -- chain ``c`` belongs to group ``(chain_offset + c) % n_groups``.  Stateless (``lmc_group_moments``);
+    with ``out=(S1, S2)`` it ADDS into those tensors and returns them.  No atomics: equal calls give equal bits."""
+    xt = _dev.to_dev(x)
+    if xt.dim() != 3:
+        raise ValueError("x must be [C, H, W]")
+    G = int(n_groups)
+    if not 2 <= G <= MAX_CHAIN_GROUPS:
+        raise ValueError(f"n_groups must be 2 .. {MAX_CHAIN_GROUPS}, got {G}")
+    if int(chain_offset) < 0:
+        raise ValueError("chain_offset must be >= 0")
+    Cn, H, W = (int(v) for v in xt.shape)
+    if out is None:
+        out = (torch.zeros((G, H, W), dtype=torch.float64, device=xt.device), torch.zeros((G, H, W), dtype=torch.float64, device=xt.device))
+    elif not (isinstance(out, (tuple, list)) and len(out) == 2 and all(
+            isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == (G, H, W) and t.is_contiguous() and t.device == xt.device
+            for t in out)):
+        raise ValueError(f"out must be two contiguous torch.float64 tensors {(G, H, W)} on {xt.device}")
+    if out[0].data_ptr() == out[1].data_ptr():
+        raise ValueError("out must be two DISTINCT tensors: the sums of x and of x^2 do not share an array")
+    _dev.run(xt, "lmc_group_moments", _dev.ptr(xt), Cn, int(chain_offset), H, W, G, _dev.ptr(out[0]), _dev.ptr(out[1]))
+    torch.cuda.current_stream(xt.device).synchronize()          # xt may be a temporary
+    return out[0], out[1]
+
+
+class GroupMCSE:
+    """What :func:`mcse_from_group_moments` returns, per pixel in float64: ``mean``, ``var`` (pooled over all groups), ``mcse_mean`` and
+    ``mcse_var`` (the Monte-Carlo standard errors of the two) and ``ess`` (the effective sample size of the mean)."""
+
+    def __init__(self, mean, var, mcse_mean, mcse_var, ess):
+        self.mean, self.var, self.mcse_mean, self.mcse_var, self.ess = mean, var, mcse_mean, mcse_var, ess
+
+
+def mcse_from_group_moments(S1, S2, counts):
+    """Pixel-wise Monte-Carlo error of the posterior mean and variance from chain-group moments (:meth:`MYULASampler.group_moments`,
+    :func:`group_moments`): ``S1``, ``S2`` ``[G, H, W]`` = the sums of x and x^2 per group, ``counts`` ``[G]`` = the samples per group.  With
+    ``N = sum n``, ``m_g = S1_g / n_g``, ``v_g = S2_g / n_g - m_g^2``, ``m = sum S1_g / N`` and ``v = sum S2_g / N - m^2``:
+
+    * ``mcse_mean = sqrt(s / N)``, ``s = sum_g n_g (m_g - m)^2 / (G - 1)``;
+    * ``mcse_var = sqrt(sv / N)``, ``sv = sum_g n_g (v_g - vbar)^2 / (G - 1)``, ``vbar = sum n_g v_g / N``;
+    * ``ess = N v / s``, ``+inf`` where ``s = 0`` (not a clamp).
+
+    For equal counts this is the textbook standard error of G independent replicate means: the scatter of the group means carries the
+    autocorrelation of the chains, with no lags and no stored iterate; the weights keep it unbiased when the chain count is no multiple of G.
+    The relative precision of ``s`` is ``sqrt(2 / (G - 1))`` -- about 25 % at G = 32 and 18 % at G = 64 (which is why the library allows up to 64
+    groups, not 8): read single pixels of these maps with that in mind, medians and smoothed maps are far tighter.  numpy in, numpy out; torch in,
+    torch out (on the device of ``S1``); float64, the arithmetic is on the host.  ``ValueError`` for fewer than 2 groups or a group without
+    samples."""
+    a, b = _host_array(S1).astype(np.float64), _host_array(S2).astype(np.float64)
+    n = _host_array(counts).astype(np.float64).reshape(-1)
+    if a.ndim < 1 or a.shape != b.shape or a.shape[0] != n.size:
+        raise ValueError("S1 and S2 must be [G, ...] of one shape and counts [G]")
+    G = n.size
+    if G < 2:
+        raise ValueError("the Monte-Carlo error needs at least 2 chain groups")
+    if (n <= 0).any():
+        raise ValueError("every chain group needs samples: a count of 0 has no group mean (fewer groups than chains avoid it)")
+    ng = n.reshape((G,) + (1,) * (a.ndim - 1))
+    N = n.sum()
+    mg = a / ng
+    vg = b / ng - mg * mg
+    mean = a.sum(axis=0) / N
+    var = b.sum(axis=0) / N - mean * mean
+    s = (ng * (mg - mean) ** 2).sum(axis=0) / (G - 1)
+    vbar = (ng * vg).sum(axis=0) / N
+    sv = (ng * (vg - vbar) ** 2).sum(axis=0) / (G - 1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ess = np.where(s == 0, np.inf, N * var / s)
+    parts = (mean, var, np.sqrt(s / N), np.sqrt(sv / N), ess)
+    if isinstance(S1, torch.Tensor):
+        parts = tuple(torch.from_numpy(np.ascontiguousarray(v)).to(S1.device) for v in parts)
+    return GroupMCSE(*parts)
+
+
+def _group_summaries(smp):
+    """``(mcse_mean, mcse_var, ess, counts)`` of a sampler's chain-group moments; None without them."""
+    if smp.chain_groups is None:
+        return None
+    S1, S2, counts = smp.group_moments()
+    r = mcse_from_group_moments(S1, S2, counts)
+    return r.mcse_mean, r.mcse_var, r.ess, counts
+
+
 def _scale_summaries(smp):
     """``({scale: mean}, {scale: std})`` of the block means of every scale the sampler keeps."""
     means, stds = {}, {}
@@ -337,16 +439,19 @@ class MYULASampler:
 
     def __init__(self, proxf, proxg, dims, n_chains=1, tau=None, gamma=0.1, epsg=1.0, seed=0,
                  chain_offset=0, noise="philox", moments=False, burn_in=0, thin=1, device=None, variant=None, tv_warm=None, policy=None,
-                 moment_scales=None, hist_bins=None, hist_range=None):
+                 moment_scales=None, hist_bins=None, hist_range=None, chain_groups=None):
         """``variant``: step-kernel variant of THIS sampler ('auto' | 'tile' | 'split' | 'point' | 'block' | 'rows' | 'pipe' | 'pipe2'; None = the
         library default, :func:`set_step_variant`).  ``tv_warm``: carry the TV dual between iterations (see :class:`TV`; None = as
         ``proxg.warm`` says).  ``moment_scales``: block sizes out of (2, 4, 8, 16) whose block sums get second moments of their own over the kept samples
         (:meth:`block_moments`; needs ``moments=True``).  ``hist_bins`` (1 .. 62) with ``hist_range=(lo, hi)``, each a scalar or an ``[H, W]`` array:
         a histogram per pixel over the kept samples (:meth:`histogram`, :func:`hist_quantiles`; needs ``moments=True``) -- a short pilot run gives
         ``mean`` and ``var``, and ``(mean - 5 sqrt(var), mean + 5 sqrt(var))`` is then a range whose 62 bins resolve 0.16 standard deviations.
+        ``chain_groups=G`` (2 .. 64): the sums of x and x^2 per pixel and chain group over the kept samples, the group of a chain being its global id
+        mod G (:meth:`group_moments`, :func:`mcse_from_group_moments`: Monte-Carlo error and ESS maps; needs ``moments=True``).
         Every call on the sampler runs on ``device`` whatever the current device is."""
         scales = _check_moment_scales(moment_scales, moments)
         hist = _check_histogram(hist_bins, hist_range, moments, dims)
+        groups = _check_chain_groups(chain_groups, moments)
         if tau is None:
             raise NotImplementedError("tau=None (backtracking) is not implemented by the reference loop either")
         self.dims = (int(dims[0]), int(dims[1]))
@@ -383,6 +488,7 @@ class MYULASampler:
             _capi.check(self._create(cfg))
         self._set_moment_scales(scales)
         self._set_histogram(hist)
+        self._set_chain_groups(groups)
 
     _create_fn = "lmc_myula_create"
 
@@ -391,7 +497,15 @@ class MYULASampler:
 
     moment_scales = ()
     hist_bins = hist_lo = hist_scale = None
+    chain_groups = None
     prior_weight = None
+
+    def _set_chain_groups(self, groups):
+        if groups is None:
+            return
+        with torch.cuda.device(self.device):
+            _capi.check(_dev.lib().lmc_sampler_set_chain_groups(self._h, int(groups)))
+        self.chain_groups = int(groups)
 
     def _set_histogram(self, hist):
         """``hist``: None or (B, lo, scale) as :func:`_check_histogram` returns them; the sampler keeps fp32 device copies of lo and scale."""
@@ -613,6 +727,26 @@ class MYULASampler:
         _capi.check(_dev.lib().lmc_allreduce_histogram(self._h, comm, _dev.ptr(counts), C.byref(cnt), _dev.stream_ptr(self.device)))
         return counts, int(cnt.value)
 
+    def _group_call(self, fn, *head):
+        if self.chain_groups is None:
+            raise ValueError("the sampler keeps no chain-group moments (chain_groups=)")
+        S1 = torch.empty((self.chain_groups,) + self.dims, dtype=torch.float64, device=self.device)
+        S2 = torch.empty_like(S1)
+        cnt = (C.c_uint64 * self.chain_groups)()
+        _capi.check(getattr(_dev.lib(), fn)(self._h, *head, _dev.ptr(S1), _dev.ptr(S2), cnt, _dev.stream_ptr(self.device)))
+        return S1, S2, torch.tensor([int(v) for v in cnt], dtype=torch.int64)
+
+    def group_moments(self):
+        """(S1, S2 ``[chain_groups, H, W]`` f64, counts ``[chain_groups]`` int64 CPU tensor): the sums of x and x^2 over the kept samples of every
+        chain group (global chain id mod ``chain_groups``) and the samples per group.  :func:`mcse_from_group_moments` turns them into the
+        Monte-Carlo error of the mean and the variance and the effective sample size, per pixel."""
+        return self._group_call("lmc_sampler_get_group_moments")
+
+    def allreduce_group_moments(self, rccl_comm):
+        """Job-wide :meth:`group_moments`: ONE ``ncclAllReduce`` of the packed sums and counts through the C ABI (``lmc_allreduce_group_moments``)."""
+        comm = rccl_comm if isinstance(rccl_comm, C.c_void_p) else C.c_void_p(int(rccl_comm or 0))
+        return self._group_call("lmc_allreduce_group_moments", comm)
+
     def allreduce_moments(self, rccl_comm):
         """Job-wide (sum, sumsq, count): ONE ``ncclAllReduce`` (RCCL over xGMI) of the packed accumulators through the C ABI
         (``lmc_allreduce_moments``).  ``rccl_comm``: an ``ncclComm_t`` as an integer / ``c_void_p`` (``None`` or 0 = a job of one rank)."""
@@ -632,11 +766,12 @@ class ULPDASampler(MYULASampler):
 
     def __init__(self, proxf, proxg, A, dims, n_chains=1, tau=None, mu=None, theta=1.0, gfirst=True, z=None, seed=0,
                  chain_offset=0, noise="philox", moments=False, burn_in=0, thin=1, device=None, variant=None, implicit_tol=None,
-                 moment_scales=None, hist_bins=None, hist_range=None):
+                 moment_scales=None, hist_bins=None, hist_range=None, chain_groups=None):
         from .operators import Gradient
         from .proximal import L1, L21
         scales = _check_moment_scales(moment_scales, moments)
         hist = _check_histogram(hist_bins, hist_range, moments, dims)
+        groups = _check_chain_groups(chain_groups, moments)
         if not isinstance(A, Gradient):
             raise NotImplementedError("ULPDA on the GPU supports A = Gradient (the reference's operator, prox_lmc_deconv.py:98)")
         if isinstance(proxg, L21):
@@ -679,6 +814,7 @@ class ULPDASampler(MYULASampler):
             _capi.check(_dev.lib().lmc_ulpda_create(C.byref(cfg), C.byref(self._h)))
         self._set_moment_scales(scales)
         self._set_histogram(hist)
+        self._set_chain_groups(groups)
 
     def set_steps(self, tau, mu):
         _capi.check(_dev.lib().lmc_sampler_set_steps(self._h, float(tau), float(mu)))
@@ -702,14 +838,14 @@ class ULPDASampler(MYULASampler):
 def UnadjustedLangevinPrimalDual(proxf, proxg, A, x0, tau, mu, y0=None, z=None, theta=1., niter=10, seed=0, gfirst=True,
                                  callback=None, callbacky=False, returny=False, show=False, *, n_chains=None, dims=None,
                                  rng="philox", chain_offset=0, burn_in=0, thin=1, device=None, diagnostics=None, moment_scales=None,
-                                 hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95)):
+                                 hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95), chain_groups=None):
     r"""Unadjusted Langevin Primal-Dual algorithm (ULPDA) -- drop-in for algs.py:295-474.
 
     Reference form (``n_chains is None``): one chain, returns ``np.ndarray (niter, n)`` (and the duals ``(niter, 2n)`` with
     ``returny``), ``callback(x)`` / ``callback(x, y)`` every iteration, ``tau`` / ``mu`` scalars or per-iteration arrays
     (algs.py:402-408).  ``rng='pcg64'`` injects the reference's noise stream.  Many-chain form: :class:`MYULAResult`
     (``diagnostics=(ph, pw)`` or ``True``: split R-hat / ESS across chains as in :func:`MoreauYosidaUnadjustedLangevin`;
-    ``moment_scales``, ``hist_bins`` / ``hist_range`` / ``quantiles``: as there).
+    ``moment_scales``, ``hist_bins`` / ``hist_range`` / ``quantiles``, ``chain_groups``: as there).
     """
     if dims is None:
         dims = getattr(A, "dims", None) or getattr(proxf, "dims", None)
@@ -726,12 +862,15 @@ def UnadjustedLangevinPrimalDual(proxf, proxg, A, x0, tau, mu, y0=None, z=None, 
         raise ValueError("moment_scales belongs to the many-chain form (n_chains=C): the reference form keeps every iterate instead")
     if (hist_bins is not None or hist_range is not None) and not many:
         raise ValueError("hist_bins / hist_range belong to the many-chain form (n_chains=C): the reference form keeps every iterate instead")
+    if chain_groups is not None and not many:
+        raise ValueError("chain_groups belongs to the many-chain form (n_chains=C): one chain has no groups to compare")
+    _check_chain_groups(chain_groups, True, C_)
     taus = np.full(niter, tau, dtype=np.float64) if np.isscalar(tau) else np.asarray(tau, dtype=np.float64)
     mus = np.full(niter, mu, dtype=np.float64) if np.isscalar(mu) else np.asarray(mu, dtype=np.float64)
     smp = ULPDASampler(proxf, proxg, A, dims, n_chains=C_, tau=taus[0], mu=mus[0], theta=theta, gfirst=gfirst, z=z,
                        seed=seed, chain_offset=chain_offset, noise="injected" if rng == "pcg64" else "philox",
                        moments=many, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
-                       hist_bins=hist_bins, hist_range=hist_range)
+                       hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups)
     try:
         smp.set_state(x0)
         if y0 is not None:
@@ -789,7 +928,7 @@ def UnadjustedLangevinPrimalDual(proxf, proxg, A, x0, tau, mu, y0=None, z=None, 
         diag = tracer.summary() if tracer is not None and len(tracer) else None
         return MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, diagnostics=diag,
                            trace=tracer.trace() if diag is not None else None, scale_mean=scale_mean, scale_std=scale_std,
-                           hist=_hist_summaries(smp, quantiles))
+                           hist=_hist_summaries(smp, quantiles), groups=_group_summaries(smp))
     finally:
         smp.close()
 
@@ -804,8 +943,11 @@ def mean_var_from_moments(s1, s2, count):
 class MYULAResult:
     """Return value of the many-chain form of :func:`MoreauYosidaUnadjustedLangevin`."""
 
-    def __init__(self, state, mean, var, count, energy_f, energy_g, elapsed, diagnostics=None, trace=None, scale_mean=None, scale_std=None, hist=None):
+    def __init__(self, state, mean, var, count, energy_f, energy_g, elapsed, diagnostics=None, trace=None, scale_mean=None, scale_std=None, hist=None, groups=None):
         self.state, self.mean, self.var, self.count = state, mean, var, count
+        # chain_groups: Monte-Carlo standard error of mean and var and the effective sample size, [H, W] float64 each (mcse_from_group_moments), and the
+        # samples per chain group [G] int64; None when not asked
+        self.mcse_mean, self.mcse_var, self.ess, self.group_counts = groups if groups is not None else (None, None, None, None)
         # hist_bins / hist_range: the pixel histogram [B + 2, H, W] int64 with its lo and scale (None when not asked), and {q: tensor [H, W]} of
         # the quantiles asked for (hist_quantiles; empty without a histogram)
         self.hist, self.hist_lo, self.hist_scale, self.quantiles = hist if hist is not None else (None, None, None, {})
@@ -818,7 +960,7 @@ class MYULAResult:
 def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1., niter=10, seed=0,
                                    callback=None, show=False, *, n_chains=None, dims=None, rng="philox",
                                    chain_offset=0, burn_in=0, thin=1, device=None, diagnostics=None, moment_scales=None,
-                                   hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95)):
+                                   hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95), chain_groups=None):
     r"""Moreau--Yosida Unadjusted Langevin algorithm (MYULA) -- drop-in for algs.py:477-587.
 
     .. math::
@@ -841,7 +983,10 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
     ``[H, W]`` arrays, e.g. mean -+ 5 std of a pilot run) keeps a histogram per pixel over the kept samples: ``result.hist`` (counters
     ``[B + 2, H, W]``), ``result.hist_lo`` / ``result.hist_scale``, and the pixel-wise quantile maps ``result.quantiles[q]`` for every ``q`` in
     ``quantiles`` -- credible intervals that, unlike mean -+ 2 std, follow the skew of a TV posterior next to edges (:func:`hist_quantiles`,
-    :func:`hist_exceedance`).
+    :func:`hist_exceedance`).  ``chain_groups=G`` (2 .. 64, at most ``n_chains``) splits the chains into G groups by global chain id mod G and returns the
+    pixel-wise Monte-Carlo standard errors ``result.mcse_mean`` and ``result.mcse_var`` of ``result.mean`` and ``result.var``, the effective sample size
+    ``result.ess`` and the samples per group ``result.group_counts`` (:func:`mcse_from_group_moments`: the scatter of the group means, which includes
+    the autocorrelation of the chains; one pixel of these maps is precise to sqrt(2 / (G - 1)), 25 % at G = 32).
     """
     if dims is None:
         dims = getattr(proxf, "dims", None) or getattr(proxg, "dims", None)
@@ -858,10 +1003,13 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
         raise ValueError("moment_scales belongs to the many-chain form (n_chains=C): the reference form keeps every iterate instead")
     if (hist_bins is not None or hist_range is not None) and not many:
         raise ValueError("hist_bins / hist_range belong to the many-chain form (n_chains=C): the reference form keeps every iterate instead")
+    if chain_groups is not None and not many:
+        raise ValueError("chain_groups belongs to the many-chain form (n_chains=C): one chain has no groups to compare")
+    _check_chain_groups(chain_groups, True, C_)
     smp = MYULASampler(proxf, proxg, dims, n_chains=C_, tau=tau, gamma=gamma, epsg=epsg, seed=seed,
                        chain_offset=chain_offset, noise="injected" if rng == "pcg64" else "philox",
                        moments=many, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
-                       hist_bins=hist_bins, hist_range=hist_range)
+                       hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups)
     try:
         smp.set_state(x0)
         tstart = time.time()
@@ -927,7 +1075,7 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
         diag = tracer.summary() if tracer is not None and len(tracer) else None
         return MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, diagnostics=diag,
                            trace=tracer.trace() if diag is not None else None, scale_mean=scale_mean, scale_std=scale_std,
-                           hist=_hist_summaries(smp, quantiles))
+                           hist=_hist_summaries(smp, quantiles), groups=_group_summaries(smp))
     finally:
         smp.close()
 
@@ -953,18 +1101,19 @@ class MYMALASampler(MYULASampler):
 
 def MoreauYosidaMetropolisAdjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1., niter=10, seed=0, callback=None, *,
                                            n_chains=1, dims=None, chain_offset=0, burn_in=0, thin=1, device=None, moment_scales=None,
-                                           hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95)):
+                                           hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95), chain_groups=None):
     """MYMALA at image scale for ``n_chains`` chains (the accept / reject of prox_lmc.py:134-158 around the MYULA move of
     algs.py:569): returns a :class:`MYULAResult` with two extra attributes, ``accepted`` (per-chain counts) and
     ``acceptance_rate``.  ``callback(state)`` after every iteration if given.  ``moment_scales``, ``hist_bins`` / ``hist_range`` /
-    ``quantiles``: as in :func:`MoreauYosidaUnadjustedLangevin`."""
+    ``quantiles``, ``chain_groups``: as in :func:`MoreauYosidaUnadjustedLangevin`."""
     if dims is None:
         dims = getattr(proxf, "dims", None) or getattr(proxg, "dims", None)
     if dims is None:
         raise ValueError("image shape unknown: pass dims=(ny, nx)")
+    _check_chain_groups(chain_groups, True, n_chains)
     smp = MYMALASampler(proxf, proxg, dims, n_chains=int(n_chains), tau=tau, gamma=gamma, epsg=epsg, seed=seed,
                         chain_offset=chain_offset, moments=True, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
-                        hist_bins=hist_bins, hist_range=hist_range)
+                        hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups)
     try:
         smp.set_state(x0)
         tstart = time.time()
@@ -982,7 +1131,7 @@ def MoreauYosidaMetropolisAdjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1,
         mean, var = mean_var_from_moments(s1, s2, max(cnt, 1))
         scale_mean, scale_std = _scale_summaries(smp)
         res = MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, scale_mean=scale_mean, scale_std=scale_std,
-                          hist=_hist_summaries(smp, quantiles))
+                          hist=_hist_summaries(smp, quantiles), groups=_group_summaries(smp))
         res.accepted = acc
         res.acceptance_rate = acc.double() / max(niter, 1)
         return res
@@ -1025,6 +1174,7 @@ class SKROCKSampler(MYULASampler):
     a warm-started TV dual and array-valued ``epsg`` run outside the fused launch and raise ``NotImplementedError``."""
 
     def __init__(self, proxf, proxg, dims, n_stages=10, eta=0.05, **kw):
+        _check_chain_groups(kw.get("chain_groups"), kw.get("moments", False))      # before anything touches the proxes
         prior = _prior_descriptor(proxg)
         if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
             raise NotImplementedError("SK-ROCK runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
@@ -1042,18 +1192,19 @@ class SKROCKSampler(MYULASampler):
 
 def StabilisedLangevin(proxf, proxg, x0, tau, gamma=.1, epsg=1., niter=10, n_stages=10, eta=0.05, seed=0, callback=None, *,
                        n_chains=1, dims=None, chain_offset=0, burn_in=0, thin=1, device=None, moment_scales=None,
-                       hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95)):
+                       hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95), chain_groups=None):
     """SK-ROCK at image scale for ``n_chains`` chains (:class:`SKROCKSampler`): ``niter`` iterations of ``n_stages`` drift evaluations each at
     step ``tau`` (up to :func:`skrock_step_bound`).  Returns a :class:`MYULAResult` with two extra attributes, ``n_stages`` and
     ``gradient_evaluations = niter * n_stages``.  ``callback(state)`` after every iteration if given.  ``moment_scales``, ``hist_bins`` /
-    ``hist_range`` / ``quantiles``: as in :func:`MoreauYosidaUnadjustedLangevin`."""
+    ``hist_range`` / ``quantiles``, ``chain_groups``: as in :func:`MoreauYosidaUnadjustedLangevin`."""
     if dims is None:
         dims = getattr(proxf, "dims", None) or getattr(proxg, "dims", None)
     if dims is None:
         raise ValueError("image shape unknown: pass dims=(ny, nx)")
+    _check_chain_groups(chain_groups, True, n_chains)
     smp = SKROCKSampler(proxf, proxg, dims, n_stages=n_stages, eta=eta, n_chains=int(n_chains), tau=tau, gamma=gamma, epsg=epsg, seed=seed,
                         chain_offset=chain_offset, moments=True, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
-                        hist_bins=hist_bins, hist_range=hist_range)
+                        hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups)
     try:
         smp.set_state(x0)
         tstart = time.time()
@@ -1070,7 +1221,7 @@ def StabilisedLangevin(proxf, proxg, x0, tau, gamma=.1, epsg=1., niter=10, n_sta
         mean, var = mean_var_from_moments(s1, s2, max(cnt, 1))
         scale_mean, scale_std = _scale_summaries(smp)
         res = MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, scale_mean=scale_mean, scale_std=scale_std,
-                          hist=_hist_summaries(smp, quantiles))
+                          hist=_hist_summaries(smp, quantiles), groups=_group_summaries(smp))
         res.n_stages = smp.n_stages
         res.gradient_evaluations = int(niter) * smp.n_stages
         return res

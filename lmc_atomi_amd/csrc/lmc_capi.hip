@@ -274,6 +274,14 @@ int lmc_pixel_histogram(const float* x_dev, int64_t C, int32_t H, int32_t W, int
   return LMC_OK;
 }
 
+int lmc_group_moments(const float* x_dev, int64_t C, int64_t chain_offset, int32_t H, int32_t W, int32_t n_groups, double* sum_dev, double* sumsq_dev,
+                      void* stream) {
+  if (!x_dev || !sum_dev || !sumsq_dev || C < 1 || chain_offset < 0 || H < 1 || W < 1) return fail(LMC_E_INVALID, "bad arguments");
+  if (n_groups < 2 || n_groups > LMC_MAX_CHAIN_GROUPS) return fail(LMC_E_INVALID, "n_groups must be 2 .. %d (got %d)", LMC_MAX_CHAIN_GROUPS, n_groups);
+  HIP_TRY(lmc::launch_group_moments(x_dev, C, chain_offset, H, W, n_groups, sum_dev, sumsq_dev, S(stream)));
+  return LMC_OK;
+}
+
 int lmc_dual_project(const float* y_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, float radius,
                      int32_t isotropic, void* stream) {
   if (!y_dev || !out_dev) return fail(LMC_E_INVALID, "NULL pointer");

@@ -223,15 +223,24 @@ struct lmc_sampler {
   float* hist_lo = nullptr;
   float* hist_scale = nullptr;
   unsigned long long* hist_packed = nullptr;   // [(hist_bins + 2) H W + 1]: the send / receive buffer of lmc_allreduce_histogram
+  // chain-group moments (lmc_sampler_set_chain_groups): grp = {A [n_groups][H][W], B [n_groups][H][W]} in one buffer, NULL = off
+  int n_groups = 0;
+  double* grp = nullptr;
+  double* grp_packed = nullptr;                // [2 n_groups H W + n_groups]: the send / receive buffer of lmc_allreduce_group_moments
+  // the launches that follow the moment reduction of a kept iterate: the histogram, then the chain-group moments (neither has a paced twin: beside
+  // a step kernel they are the in-line forms on the side stream)
+  hipError_t reduce_more(hipError_t e, const float* x, hipStream_t st) {
+    if (e == hipSuccess && hist) e = lmc::launch_pixel_hist(x, C, prob.H, prob.W, hist_bins, hist_lo, hist_scale, hist, st);
+    if (e == hipSuccess && grp) e = lmc::launch_group_moments(x, C, chain_offset, prob.H, prob.W, n_groups, grp, grp + (size_t)n_groups * prob.H * prob.W, st);
+    return e;
+  }
   // the kept iterate x into the accumulators: the fused multi-scale reduction when scales are enabled, else exactly the launches of before;
-  // then, with a histogram, its launch (it has no paced twin: beside a step kernel it is the in-line form on the side stream)
+  // then what reduce_more adds
   hipError_t reduce(const float* x, hipStream_t st) {
-    const hipError_t e = bs2 ? lmc::launch_moments_ms(x, C, prob.H, prob.W, s1, s2, scales, st) : lmc::launch_moments(x, C, prob.H, prob.W, s1, s2, st);
-    return e != hipSuccess || !hist ? e : lmc::launch_pixel_hist(x, C, prob.H, prob.W, hist_bins, hist_lo, hist_scale, hist, st);
+    return reduce_more(bs2 ? lmc::launch_moments_ms(x, C, prob.H, prob.W, s1, s2, scales, st) : lmc::launch_moments(x, C, prob.H, prob.W, s1, s2, st), x, st);
   }
   hipError_t reduce_bg(const float* x, int n_wg, hipStream_t st) {
-    const hipError_t e = bs2 ? lmc::launch_moments_ms_bg(x, C, prob.H, prob.W, s1, s2, scales, n_wg, st) : lmc::launch_moments_bg(x, C, prob.H, prob.W, s1, s2, n_wg, st);
-    return e != hipSuccess || !hist ? e : lmc::launch_pixel_hist(x, C, prob.H, prob.W, hist_bins, hist_lo, hist_scale, hist, st);
+    return reduce_more(bs2 ? lmc::launch_moments_ms_bg(x, C, prob.H, prob.W, s1, s2, scales, n_wg, st) : lmc::launch_moments_bg(x, C, prob.H, prob.W, s1, s2, n_wg, st), x, st);
   }
   lmc::StepArgs base{};
   // MYMALA state (kind == 2): proposal mean of the current state, proposal, its mean, energies, decisions
@@ -270,4 +279,6 @@ namespace lmc::host {
 int rebuild_base(lmc_sampler* s);
 // what lmc_sampler_set_prior_sigma and lmc_sampler_sapg refuse (LMC_E_UNSUPPORTED), else LMC_OK
 int check_weight_settable(const lmc_sampler* s);
+// n[g] of the chain-group moments: kept iterations x chains of the handle in group g, into counts[s->n_groups]
+void group_counts(const lmc_sampler* s, uint64_t* counts);
 }  // namespace lmc::host

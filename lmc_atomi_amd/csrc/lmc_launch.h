@@ -46,6 +46,9 @@ hipError_t launch_block_sums(const double* src, int H, int W, int scale, double*
 // pixel-wise histograms (lmc_pixel_hist.hip): counts[B + 2][H][W] += the rows of x[C][H][W] under t = (x - lo) * scale, 1 <= B <= 62
 hipError_t launch_pixel_hist(const float* x, int64_t C, int H, int W, int B, const float* lo, const float* scale, unsigned long long* counts,
                              hipStream_t st);
+// chain-group moments (lmc_group_moments.hip): A[G][H][W] += sum x, B[G][H][W] += sum x^2 over the chains of every group of x[C][H][W], the group of
+// chain c = (chain_offset + c) mod G; float64, one owner per (group, pixel) and launch, no atomics
+hipError_t launch_group_moments(const float* x, int64_t C, int64_t chain_offset, int H, int W, int G, double* A, double* B, hipStream_t st);
 hipError_t launch_energies(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, double* g_out,
                            hipStream_t st);
 // pieces of the exact early-exit path of the TV prox (lmc_problem.tv_rtol > 0)

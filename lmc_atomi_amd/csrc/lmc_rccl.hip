@@ -1,4 +1,4 @@
-// Multi-GPU: the RCCL entry points and the all-reduces of the posterior moments (pixels, and the blocks of one scale).
+// Multi-GPU: the RCCL entry points and the all-reduces of the posterior moments (pixels, the blocks of one scale, the chain groups) and of the histogram.
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types and enums only: the library itself is dlopen'd (liblmc_atomi loads without RCCL)
 
@@ -156,6 +156,35 @@ int lmc_allreduce_histogram(lmc_sampler* s, void* rccl_comm, uint64_t* counts_de
   HIP_TRY(hipMemcpyAsync(&total, s->hist_packed + n, sizeof total, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (count) *count = total;
+  return LMC_OK;
+}
+
+// The collective of the chain-group moments: {A [n], B [n], counts [G] as doubles (exact far below 2^53)} of this rank in one float64 buffer,
+// ONE ncclAllReduce(sum) in place, and the three come back out.
+int lmc_allreduce_group_moments(lmc_sampler* s, void* rccl_comm, double* sum_dev, double* sumsq_dev, uint64_t* counts_host, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (!s->grp) return fail(LMC_E_INVALID, "the sampler has no chain groups (lmc_sampler_set_chain_groups)");
+  if (!rccl_comm) return lmc_sampler_get_group_moments(s, sum_dev, sumsq_dev, counts_host, stream);   // a job of one rank
+  hipStream_t st = S(stream);
+  RcclApi* R = rccl_api();
+  if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
+  const size_t G = (size_t)s->n_groups, n = G * s->prob.H * s->prob.W;
+  if (!s->grp_packed) HIP_TRY(hipMalloc(&s->grp_packed, sizeof(double) * (2 * n + G)));
+  uint64_t cnt[LMC_MAX_CHAIN_GROUPS];
+  double cntd[LMC_MAX_CHAIN_GROUPS];
+  group_counts(s, cnt);
+  for (size_t g = 0; g < G; ++g) cntd[g] = (double)cnt[g];
+  HIP_TRY(hipMemcpyAsync(s->grp_packed, s->grp, sizeof(double) * 2 * n, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->grp_packed + 2 * n, cntd, sizeof(double) * G, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));                          // cntd is pageable host memory of this frame
+  RCCL_TRY(R, R->AllReduce(s->grp_packed, s->grp_packed, 2 * n + G, ncclFloat64, ncclSum, static_cast<ncclComm_t>(rccl_comm), st));
+  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, s->grp_packed, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, s->grp_packed + n, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(cntd, s->grp_packed + 2 * n, sizeof(double) * G, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (counts_host)
+    for (size_t g = 0; g < G; ++g) counts_host[g] = (uint64_t)(cntd[g] + 0.5);
   return LMC_OK;
 }
 

@@ -66,6 +66,15 @@ int check_weight_settable(const lmc_sampler* s) {
     return fail(LMC_E_UNSUPPORTED, "prior_kind %d has no weight prior_sigma", s->prob.prior_kind);
   return LMC_OK;
 }
+
+void group_counts(const lmc_sampler* s, uint64_t* counts) {
+  const uint64_t G = (uint64_t)s->n_groups, kept_its = s->count / (uint64_t)s->C;
+  const uint64_t first = (uint64_t)s->chain_offset % G;     // the group of local chain 0
+  for (uint64_t g = 0; g < G; ++g) {
+    const uint64_t c0 = (g + G - first) % G;                 // the first local chain of group g, then every G-th
+    counts[g] = kept_its * (c0 < (uint64_t)s->C ? ((uint64_t)s->C - c0 + G - 1) / G : 0);
+  }
+}
 }  // namespace lmc::host
 
 extern "C" {
@@ -168,6 +177,13 @@ static void release_histogram(lmc_sampler* s) {
   s->hist_bins = 0;
 }
 
+static void release_chain_groups(lmc_sampler* s) {
+  if (s->grp) (void)hipFree(s->grp);
+  if (s->grp_packed) (void)hipFree(s->grp_packed);
+  s->grp = s->grp_packed = nullptr;
+  s->n_groups = 0;
+}
+
 void lmc_sampler_destroy(lmc_sampler* s) {
   if (!s) return;
   DeviceGuard dg(s->device);
@@ -193,6 +209,7 @@ void lmc_sampler_destroy(lmc_sampler* s) {
   if (s->sapg_host) (void)hipHostFree(s->sapg_host);
   if (s->sapg_ev) (void)hipEventDestroy(s->sapg_ev);
   release_histogram(s);
+  release_chain_groups(s);
   for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
   if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }
   for (hipEvent_t e : s->side_ev) if (e) (void)hipEventDestroy(e);
@@ -944,6 +961,7 @@ int lmc_sampler_reset_moments(lmc_sampler* s, void* stream) {
   HIP_TRY(hipMemsetAsync(s->s2, 0, mb, S(stream)));
   if (s->bs2) HIP_TRY(hipMemsetAsync(s->bs2, 0, sizeof(double) * s->bs2_count, S(stream)));
   if (s->hist) HIP_TRY(hipMemsetAsync(s->hist, 0, sizeof(unsigned long long) * (size_t)(s->hist_bins + 2) * s->prob.H * s->prob.W, S(stream)));
+  if (s->grp) HIP_TRY(hipMemsetAsync(s->grp, 0, sizeof(double) * 2 * (size_t)s->n_groups * s->prob.H * s->prob.W, S(stream)));
   s->count = 0;
   return LMC_OK;
 }
@@ -1035,6 +1053,41 @@ int lmc_sampler_get_histogram(lmc_sampler* s, uint64_t* counts_dev, uint64_t* co
   if (counts_dev) HIP_TRY(hipMemcpyAsync(counts_dev, s->hist, nb, hipMemcpyDeviceToDevice, S(stream)));
   HIP_TRY(hipStreamSynchronize(S(stream)));
   if (count) *count = s->count;
+  return LMC_OK;
+}
+
+// ---- chain-group moments: A, B [n_groups][H][W] = sum x, sum x^2 of the kept samples by chain group (lmc_group_moments.hip) ----
+int lmc_sampler_set_chain_groups(lmc_sampler* s, int32_t n_groups) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (n_groups != 0 && (n_groups < 2 || n_groups > LMC_MAX_CHAIN_GROUPS))
+    return fail(LMC_E_INVALID, "n_groups must be 0 or 2 .. %d (got %d)", LMC_MAX_CHAIN_GROUPS, n_groups);
+  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
+  if (s->count != 0) return fail(LMC_E_STATE, "the chain groups change only while the accumulators are empty (after create or lmc_sampler_reset_moments)");
+  HIP_TRY(hipDeviceSynchronize());     // nothing of earlier groups is in flight when their buffers go
+  release_chain_groups(s);
+  if (!n_groups) return LMC_OK;
+  const size_t nd = 2 * (size_t)n_groups * s->prob.H * s->prob.W;
+  hipError_t e = hipMalloc(&s->grp, sizeof(double) * nd);
+  if (e == hipSuccess) e = hipMemset(s->grp, 0, sizeof(double) * nd);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    release_chain_groups(s);
+    return fail(e == hipErrorOutOfMemory ? LMC_E_NOMEM : LMC_E_HIP, "chain-group allocation failed: %s", hipGetErrorString(e));
+  }
+  s->n_groups = n_groups;
+  return LMC_OK;
+}
+
+int lmc_sampler_get_group_moments(lmc_sampler* s, double* sum_dev, double* sumsq_dev, uint64_t* counts_host, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (!s->grp) return fail(LMC_E_INVALID, "the sampler has no chain groups (lmc_sampler_set_chain_groups)");
+  const size_t n = (size_t)s->n_groups * s->prob.H * s->prob.W;
+  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, s->grp, sizeof(double) * n, hipMemcpyDeviceToDevice, S(stream)));
+  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, s->grp + n, sizeof(double) * n, hipMemcpyDeviceToDevice, S(stream)));
+  HIP_TRY(hipStreamSynchronize(S(stream)));
+  if (counts_host) group_counts(s, counts_host);
   return LMC_OK;
 }
 

@@ -129,6 +129,37 @@ def allreduce_sampler_histogram(smp, group=None):
     return allreduce_counts(counts, cnt, group)
 
 
+def allreduce_group_moments(S1, S2, counts, group=None):
+    """Sum chain-group moments (:meth:`MYULASampler.group_moments`: ``S1``, ``S2`` float64 ``[G, H, W]``, ``counts`` int64 ``[G]``) over the ranks of
+    ``group`` on the host route: the sums in one packed float64 buffer, the counts as integers (exact).  Every rank holds all groups -- the group of a
+    chain is its global id mod G -- so the job-wide arrays are plain sums.  The identity without a process group.  Returns (S1, S2) on the device
+    they came from and the counts as an int64 CPU tensor."""
+    import torch.distributed as dist
+    cnt = torch.as_tensor(counts, dtype=torch.int64).detach().reshape(-1).cpu()
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return S1, S2, cnt
+    n = S1.numel()
+    nccl = dist.get_backend(group) == "nccl"
+    dev = S1.device if nccl else torch.device("cpu")
+    packed = torch.cat([S1.detach().reshape(-1).to(dev, torch.float64), S2.detach().reshape(-1).to(dev, torch.float64)])
+    dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
+    cnt = cnt.to(dev)
+    dist.all_reduce(cnt, op=dist.ReduceOp.SUM, group=group)
+    packed = packed.to(S1.device)
+    return packed[:n].reshape(S1.shape), packed[n:].reshape(S2.shape), cnt.cpu()
+
+
+def allreduce_sampler_group_moments(smp, group=None):
+    """Job-wide (S1, S2, counts) of a sampler's chain-group moments (:meth:`MYULASampler.group_moments`), by the same routes as
+    :func:`allreduce_sampler_block_moments`: ``lmc_allreduce_group_moments`` under "nccl", the host route of :func:`allreduce_group_moments` under "gloo"."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return smp.group_moments()
+    if dist.get_backend(group) == "nccl":
+        return smp.allreduce_group_moments(rccl_comm(group, smp.device))
+    return allreduce_group_moments(*smp.group_moments(), group)
+
+
 def allgather_chains(t: torch.Tensor, dim: int = 1, group=None):
     """Concatenate per-rank tensors along their chain dimension in rank order (= global chain order under
     :func:`chain_shard`); ranks may own different numbers of chains.  Used for the diagnostics trace ``[T, C_rank, Q]``
@@ -158,25 +189,30 @@ def posterior_mean_var(s1, s2, count):
 class ShardedResult(tuple):
     """What :func:`sharded_myula` returns: the tuple it has always returned -- ``(mean, var, count, state)``, then the scales when ``moment_scales``
     is given, then the histogram when ``hist_bins`` is given, so its length depends on the keywords -- with every part also under a name that does
-    not: ``.mean``, ``.var``, ``.count``, ``.state``, ``.scales`` (``{}`` when not asked for) and ``.hist`` (``None`` when not asked for)."""
+    not: ``.mean``, ``.var``, ``.count``, ``.state``, ``.scales`` (``{}`` when not asked for) and ``.hist`` (``None`` when not asked for).  ``chain_groups`` adds nothing to the tuple: its job-wide
+    results are ``.mcse_mean``, ``.mcse_var``, ``.ess`` and ``.group_counts`` (``None`` when not asked for)."""
 
-    def __new__(cls, items, mean, var, count, state, scales, hist):
+    def __new__(cls, items, mean, var, count, state, scales, hist, groups=None):
         self = super().__new__(cls, items)
         self.mean, self.var, self.count, self.state, self.scales, self.hist = mean, var, count, state, scales, hist
+        self.mcse_mean, self.mcse_var, self.ess, self.group_counts = groups if groups is not None else (None, None, None, None)
         return self
 
 
 def sharded_myula(proxf, proxg, dims, n_chains_total, x0, tau, gamma, epsg=1.0, niter=10, seed=0,
                   burn_in=0, thin=1, group=None, device=None, moment_scales=None, hist_bins=None,
-                  hist_range=None):
+                  hist_range=None, chain_groups=None):
     """Run ``n_chains_total`` MYULA chains split over the ranks of the default process group (or run
     them all here when torch.distributed is not initialised) and return the job-wide posterior
     (mean, var, count) plus this rank's final states.  With ``moment_scales`` (block sizes out of 2, 4, 8, 16) a fifth value
     follows: ``{scale: (mean, std)}`` of the image averaged over scale x scale blocks, job-wide as well.  With ``hist_bins`` / ``hist_range`` (as
     :class:`MYULASampler` takes them) the job-wide counters of the pixel histogram ``[hist_bins + 2, H, W]`` follow as the last value.  The tuple is a :class:`ShardedResult`: index it
-    as before, or -- since its length depends on the keywords -- read ``.mean``, ``.var``, ``.count``, ``.state``, ``.scales`` and ``.hist``."""
+    as before, or -- since its length depends on the keywords -- read ``.mean``, ``.var``, ``.count``, ``.state``, ``.scales`` and ``.hist``.
+    ``chain_groups=G`` (as :class:`MYULASampler` takes it; at most ``n_chains_total``) keeps chain-group moments on every rank and returns the job-wide
+    Monte-Carlo error maps under ``.mcse_mean``, ``.mcse_var``, ``.ess`` and ``.group_counts`` (:func:`lmc_atomi_amd.mcse_from_group_moments`)."""
     import torch.distributed as dist
-    from .algs import MYULASampler
+    from .algs import MYULASampler, _check_chain_groups, mcse_from_group_moments
+    _check_chain_groups(chain_groups, True, n_chains_total)
     world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
     rank = dist.get_rank(group) if world > 1 else 0
     if int(n_chains_total) < world:      # every rank sees the same numbers: all of them raise, none is left waiting in the collective
@@ -184,9 +220,10 @@ def sharded_myula(proxf, proxg, dims, n_chains_total, x0, tau, gamma, epsg=1.0, 
     offset, count = chain_shard(n_chains_total, world, rank)
     smp = MYULASampler(proxf, proxg, dims, n_chains=count, tau=tau, gamma=gamma, epsg=epsg, seed=seed,
                        chain_offset=offset, moments=True, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
-                       hist_bins=hist_bins, hist_range=hist_range)
+                       hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups)
     scales = {}
     hist = None
+    groups = None
     try:
         smp.set_state(x0)
         smp.step(niter)
@@ -198,9 +235,13 @@ def sharded_myula(proxf, proxg, dims, n_chains_total, x0, tau, gamma, epsg=1.0, 
             scales[sc] = (m, v.clamp_min(0).sqrt())
         if smp.hist_bins is not None:
             hist, _ = allreduce_sampler_histogram(smp, group)
+        if smp.chain_groups is not None:
+            G1, G2, gn = allreduce_sampler_group_moments(smp, group)
+            r = mcse_from_group_moments(G1, G2, gn)
+            groups = (r.mcse_mean, r.mcse_var, r.ess, gn)
         state = smp.get_state()
     finally:
         smp.close()
     mean, var = posterior_mean_var(s1, s2, cnt)
     out = (mean, var, cnt, state, scales) if moment_scales else (mean, var, cnt, state)
-    return ShardedResult(out + (hist,) if hist is not None else out, mean, var, cnt, state, scales, hist)
+    return ShardedResult(out + (hist,) if hist is not None else out, mean, var, cnt, state, scales, hist, groups)

@@ -9,7 +9,10 @@ Per configuration:
   - the budget of an iteration: s x (MYULA launch) + the perturbation launch (8 B per chain-pixel) + s extra reads of K_{j-2} (4 B per chain-pixel
     each), the last two at the bandwidth lmc_hbm_copy_probe measures in this process, all times 1.05;
   - ESS per second of the ChainTrace probes (8 x 8 block means): MYULA at tau = 1 / L against SK-ROCK at 0.8 l_s / L, L = 1 / sigma^2 + 1 / gamma,
-    after the same number of gradient evaluations (--evals; the first fifth discarded), per second of stepping.
+    after the same number of gradient evaluations (--evals; the first fifth discarded), per second of stepping;
+  - beside them, min and median over the PIXELS of the effective sample size per second from chain-group moments (chain_groups = 32,
+    mcse_from_group_moments) of a second run of the same length: the probes are low frequencies, which the data pins down; the stiff directions
+    SK-ROCK is built for live in the pixels.
 One JSON line per configuration at the end.
 
     python scripts/bench_skrock.py [--size 512x512x1024] [--stages 5,10,15] [--steps 60] [--warmup 10] [--repeats 5] [--evals 3000]
@@ -70,6 +73,24 @@ def ess_per_second(torch, la, smp, x0, iters, every, burn):
             "ess_min_per_s": float(e.min() / spent), "ess_median_per_s": float(np.median(e) / spent)}
 
 
+def pixel_ess_per_second(torch, la, make, x0, iters, burn, groups=32):
+    """ESS per second of the pixels: a sampler with chain-group moments runs `iters` iterations in one call, the first `burn` not kept."""
+    smp = make(moments=True, burn_in=burn, chain_groups=groups)
+    try:
+        smp.set_state(x0)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        smp.step(iters)
+        torch.cuda.synchronize()
+        spent = time.perf_counter() - t0
+        e = la.mcse_from_group_moments(*smp.group_moments()).ess.cpu().numpy()
+    finally:
+        smp.close()
+    e = e[np.isfinite(e)]
+    return {"kept": iters - burn, "step_seconds": spent, "pixel_ess_min": float(e.min()), "pixel_ess_median": float(np.median(e)),
+            "pixel_ess_min_per_s": float(e.min() / spent), "pixel_ess_median_per_s": float(np.median(e) / spent)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="512x512x1024", help="HxWxchains")
@@ -128,6 +149,10 @@ def main():
             res["myula_ess"] = ess_per_second(torch, la, plain, y, args.evals, 10, args.evals // 5)
             print(f"    MYULA tau = 1/L = {tau_m:.4f}: {res['myula_ess']}", flush=True)
         plain.close()
+        if args.evals and C >= 32:
+            make = lambda **kw: la.MYULASampler(pf, pg, (H, W), n_chains=C, tau=tau_m, gamma=gamma, seed=1, **kw)
+            res["myula_pixel_ess"] = pixel_ess_per_second(torch, la, make, y, args.evals, args.evals // 5)
+            print(f"        {res['myula_pixel_ess']}", flush=True)
         for s in stages:
             delta = 0.8 * la.skrock_step_bound(L, s)
             smp = la.SKROCKSampler(pf, pg, (H, W), n_stages=s, n_chains=C, tau=delta, gamma=gamma, seed=1)
@@ -148,6 +173,10 @@ def main():
                 every = max(1, 10 // s)
                 r["ess"] = ess_per_second(torch, la, smp, y, (args.evals // s // every) * every, every, args.evals // s // 5)
                 print(f"        {r['ess']}", flush=True)
+                if C >= 32:
+                    make = lambda **kw: la.SKROCKSampler(pf, pg, (H, W), n_stages=s, n_chains=C, tau=delta, gamma=gamma, seed=1, **kw)
+                    r["pixel_ess"] = pixel_ess_per_second(torch, la, make, y, (args.evals // s // every) * every, args.evals // s // 5)
+                    print(f"        {r['pixel_ess']}", flush=True)
             res["skrock"][str(s)] = r
             smp.close()
         results.append(res)
