@@ -50,25 +50,39 @@ struct PipeLds {
   static constexpr int total = o_seam + (TEAMS == 2 ? 64 : 0);
 };
 
-// LDS rows are stored so that every 16-byte access of a wave is contiguous: pixel k of lane l at (k>>2)*256 + 4*l + (k&3).
+// LDS rows: a lane's PXL pixels are held as NP = PXL / 2 pixel pairs (i, i + NP) -- see "Packed fp32" below -- and a row stores them pair by pair:
+// slot s of a lane holds its pixel (s >> 1) + NP * (s & 1) (PXL = 4: pixels 0, 2, 1, 3; PXL = 8: 0, 4, 1, 5 | 2, 6, 3, 7), slot s of lane l at
+// (s >> 2) * 256 + 4 * l + (s & 3), so that every 16-byte access of a wave is contiguous and returns two whole pairs.  This holds for every row of
+// every pipe kernel (ring, hand-offs, gradient row, state hand-over); everything in HBM is in natural order.  prow_load / prow_store address a row by
+// PIXEL (the permutation is a renaming of registers), pairs_load / pairs_store by pair.
+template <int PXL>
+__host__ __device__ constexpr int pipe_slot(int k) { return k < PXL / 2 ? 2 * k : 2 * (k - PXL / 2) + 1; }      // pixel of a lane -> slot
+template <int PXL>
+__host__ __device__ constexpr int pipe_pixel(int s) { return (s >> 1) + (PXL / 2) * (s & 1); }                // slot -> pixel of a lane
+template <int PXL>
+__host__ __device__ constexpr int pipe_slot_offset(int k) { return (pipe_slot<PXL>(k) >> 2) * 256 + (pipe_slot<PXL>(k) & 3); }   // of lane 0, in floats
 template <int PXL>
 __device__ __forceinline__ void prow_load(float (&v)[PXL], const float* row, int lane) {
 #pragma unroll
   for (int g = 0; g < PXL / 4; ++g) {
     const float4 q = *reinterpret_cast<const float4*>(row + g * 256 + lane * 4);
-    v[4 * g] = q.x; v[4 * g + 1] = q.y; v[4 * g + 2] = q.z; v[4 * g + 3] = q.w;
+    v[pipe_pixel<PXL>(4 * g)] = q.x; v[pipe_pixel<PXL>(4 * g + 1)] = q.y; v[pipe_pixel<PXL>(4 * g + 2)] = q.z; v[pipe_pixel<PXL>(4 * g + 3)] = q.w;
   }
 }
 template <int PXL>
 __device__ __forceinline__ void prow_store(float* row, int lane, const float (&v)[PXL]) {
 #pragma unroll
   for (int g = 0; g < PXL / 4; ++g)
-    *reinterpret_cast<float4*>(row + g * 256 + lane * 4) = make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
+    *reinterpret_cast<float4*>(row + g * 256 + lane * 4) =
+        make_float4(v[pipe_pixel<PXL>(4 * g)], v[pipe_pixel<PXL>(4 * g + 1)], v[pipe_pixel<PXL>(4 * g + 2)], v[pipe_pixel<PXL>(4 * g + 3)]);
 }
 
 // Packed fp32: gfx950 issues one wave64 VALU instruction per 4 cycles per SIMD, and v_pk_fma/mul/add_f32 process two floats
-// per lane in that slot.  The TV stages therefore work on pixel PAIRS (2i, 2i+1) held in even-aligned register pairs; only
-// the two neighbour-shifted operands of a stage need a v_pk_mov to re-pair, max / rsq stay scalar.
+// per lane in that slot.  The waves therefore work on pixel PAIRS held in even-aligned register pairs, and pair i of a lane is its pixels
+// (i, i + NP): the left neighbours of pair i are then pair i - 1 as it stands, the right neighbours pair i + 1, and only the two pairs at the
+// ends of a lane are built -- {from_left(pair[NP-1].y), pair[NP-1].x} and {pair[0].y, from_right(pair[0].x)}, the wave shift a stage makes
+// anyway plus one move each, whatever PXL is.  (Pairs of ADJACENT pixels (2i, 2i + 1), the layout before, make every neighbour operand straddle
+// two register pairs: one VALU instruction in six of a TV wave was a move that re-paired them.)  max / rsq stay scalar.
 typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ v2f pk_set(float a) { return v2f{a, a}; }
@@ -91,6 +105,22 @@ __device__ __forceinline__ void pairs_store(float* row, int lane, const v2f (&v)
     *reinterpret_cast<float4*>(row + g * 256 + lane * 4) = make_float4(v[2 * g].x, v[2 * g].y, v[2 * g + 1].x, v[2 * g + 1].y);
 }
 
+// pixel k of a lane (natural order) in its pair array
+template <int NP>
+__device__ __forceinline__ float pair_px(const v2f (&v)[NP], int k) { return k < NP ? v[k].x : v[k - NP].y; }
+// The neighbour rows of pair i: the pair beside it, and at the ends of a lane the one pair that is built.  `from_left` = pixel NP-1's
+// value of the lane to the left (v[NP-1].y shifted), `from_right` = pixel 0's value of the lane to the right (v[0].x shifted).
+template <int NP>
+__device__ __forceinline__ v2f left_pair(const v2f (&v)[NP], float from_left, int i) {
+  if (i == 0) return v2f{from_left, v[NP - 1].x};
+  return v[i - 1];
+}
+template <int NP>
+__device__ __forceinline__ v2f right_pair(const v2f (&v)[NP], float from_right, int i) {
+  if (i == NP - 1) return v2f{v[0].y, from_right};
+  return v[i + 1];
+}
+
 template <int NP>
 struct DualRow { v2f rr[NP], ss[NP], p[NP], q[NP]; };
 
@@ -107,8 +137,8 @@ __device__ __forceinline__ float wave_from_right(float v, float edge) {   // lan
 // One FGP dual iteration on NP pixel pairs per lane.  r1, s1 = (rr, ss)^{k-1} on row a; in0 = (rr, ss, p, q)^{k-1} on row
 // b = a-1; solb = sol^k on row b (in) -> sol^k on row a (out); out = (rr, ss, p, q)^k on row b.
 // The horizontal step coefficient per pixel: -c, and 0 for the pixel in the last image column (no difference across it).  LASTLANE: the image
-// width is a multiple of the pixels per lane, so that pixel is the last one of a lane (cr_last, a per-lane scalar); otherwise it can be any
-// pixel of a lane and the coefficients are a per-lane register array (ncrv).
+// width is a multiple of the pixels per lane, so that pixel is the last one of a lane (cr_last, a per-lane scalar: the .y of the last pair); otherwise it can be any
+// pixel of a lane and the coefficients are a per-lane register array (ncrv; pair i = pixels (i, i + NP)).
 template <int NP>
 struct PipeCr { float cstep, cr_last; v2f ncrv[NP]; };
 template <int NP, bool LASTLANE>
@@ -158,7 +188,7 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
   const v2f ngam = pk_set(-gam), ncd = pk_set(-cdown), vb = pk_set(beta);
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
-    const v2f ssl = v2f{i == 0 ? ssl0 : s1[i - 1].y, s1[i].x};
+    const v2f ssl = left_pair(s1, ssl0, i);
     const v2f T = (r1[i] - in0.rr[i]) + (s1[i] - ssl);
     sol[i] = pk_fma(ngam, T, xa[i]);
     if constexpr (OBJ) { const v2f Tm = obj_sq<NP, LASTLANE>(om, i, T); ob->sq = i == 0 ? Tm * Tm : pk_fma(Tm, Tm, ob->sq); }
@@ -166,7 +196,7 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
   const float solr_last = SEAMR ? wave_from_right(solb[0].x, solr_edge) : dpp_right0(solb[0].x);
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
-    const v2f solr = v2f{solb[i].y, i == NP - 1 ? solr_last : solb[i + 1].x};
+    const v2f solr = right_pair(solb, solr_last, i);
     const v2f ncr = pipe_ncr<NP, LASTLANE>(cr, i);
     const v2f dxv = sol[i] - solb[i], dyv = solr - solb[i];
     if constexpr (OBJ) {
@@ -206,7 +236,7 @@ __device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb
   if constexpr (OBJ) ob->sq = pk_set(0.f);       // sol^0 = x
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
-    const v2f solr = v2f{solb[i].y, i == NP - 1 ? solr_last : solb[i + 1].x};
+    const v2f solr = right_pair(solb, solr_last, i);
     const v2f ncr = pipe_ncr<NP, LASTLANE>(cr, i);
     const v2f dxv = xa[i] - solb[i], dyv = solr - solb[i];
     if constexpr (OBJ) {
@@ -438,8 +468,8 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
   const float* __restrict__ xin = A.x_in + (size_t)chain * img;
   float* __restrict__ xout = A.x_out + (size_t)chain * img;
 
-  // ring rows < 0, hand-offs of tick -1, g (two teams: and the seam records)
-  for (int e = threadIdx.x; e < (TEAMS == 2 ? L::total : L::o_slab); e += blockDim.x) lds_all[e] = 0.f;
+  // ring rows < 0, hand-offs of tick -1, g, the normals' slab (read by C whatever the noise mode) and, two teams, the seam records
+  for (int e = threadIdx.x; e < L::total; e += blockDim.x) lds_all[e] = 0.f;
   __syncthreads();
   float* const lds = lds_all + team * BW;                   // this team's copy of every row (row pitch RP)
   float* const slab_base = lds_all + L::o_slab + team * L::SLAB;
@@ -471,14 +501,16 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     constexpr int NWIN = KT > 1 ? KT - 1 : 1;
     // x rows: fetched kXPF ticks ahead, slot (tick & 3) (8 ahead was measured: no gain, +50 VGPRs)
     constexpr int kXPF = 4;
-    float xpre[kXPF][PXL], hxw[NWIN][PXL], hrw[NWIN][PXL], ypre[4][PXL];   // y rows: fetched kYPF ticks ahead, slot (tick & 3)
+    constexpr int NP = PXL / 2;
+    float xpre[kXPF][PXL], ypre[4][PXL];
+    v2f hxw[NWIN][NP], hrw[NWIN][NP];   // y rows: fetched kYPF ticks ahead, slot (tick & 3)
     // 7 taps: the windows already take 96 registers; two teams: 112 VGPRs per wave, so that a wave of the side-stream moment reduction (64)
     // still fits beside the four of a workgroup on each SIMD (at 120 it waited for whole CUs: 2.08 against 1.80 ms per step)
     constexpr int kYPF = (KT == 7 || TEAMS == 2) ? 2 : 3;
 #pragma unroll
     for (int a = 0; a < NWIN; ++a)
 #pragma unroll
-      for (int k = 0; k < PXL; ++k) { hxw[a][k] = 0.f; hrw[a][k] = 0.f; }
+      for (int k = 0; k < NP; ++k) { hxw[a][k] = pk_set(0.f); hrw[a][k] = pk_set(0.f); }
 #pragma unroll
     for (int u = 0; u < kXPF; ++u) gload_raw<PXL>(xpre[u], xin + (size_t)min(u, H - 1) * W, cl, W, al);
     // Vector-memory loads return in order: waiting for a load also waits for every load issued before it.  So the loads a tick
@@ -530,9 +562,9 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       }
     }
     double facc = 0.0;        // sum of squared residuals (A.f_out)
-    float Rprev[TEAMS == 2 ? PXL : 1];      // two teams: last tick's residual row (LAGT)
+    v2f Rprev[TEAMS == 2 ? NP : 1];      // two teams: last tick's residual row (LAGT)
 #pragma unroll
-    for (int k = 0; k < (TEAMS == 2 ? PXL : 1); ++k) Rprev[k] = 0.f;
+    for (int k = 0; k < (TEAMS == 2 ? NP : 1); ++k) Rprev[k] = pk_set(0.f);
     auto tick = [&](auto uu, const int t) __attribute__((always_inline)) {
       constexpr int U = decltype(uu)::value, P = U & 1;
       if constexpr (KT > 0) {   // observation row of the residual row kYPF ticks from now
@@ -570,88 +602,98 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           gload_raw<PXL>(spre[SP][f], sin ? sin + (size_t)f * img + (size_t)min(max(rs, 0), H - 1) * W : xin, c0, W, al);
       }
       if constexpr (KT > 0) {
+      // The blur pipeline works on the lane's pixel pairs (j, j + NP) like the TV stages: a horizontal pass reads its in-lane operands as the pairs
+      // they are, and each of its 2 HW halo pairs is one wave shift plus one move; the vertical passes are elementwise on pairs.
       const int i = t + 1 - D + (KT - 1) + LAGT;       // blur input row (<= t-1: published in an earlier tick)
-      float hxn[PXL];
+      v2f hxn[NP];
       {
-        float xi[PXL], e[PXL + 2 * HW];
+        v2f xi[NP];
+        float e[PXL + 2 * HW];
         const float* const xr = ring_row(i);
-        prow_load<PXL>(xi, xr, lane);
-        // two teams: across the seam, the other team's copy of the same ring row (the left team's last HW columns end its row)
+        pairs_load<NP>(xi, xr, lane);
+        // two teams: across the seam, the other team's copy of the same ring row (the left team's last HW columns are lane 63's of its copy)
 #pragma unroll
-        for (int m = 0; m < HW; ++m) e[m] = (TEAMS == 2 && TM == 1) ? wave_from_left(xi[PXL - HW + m], xr[m - HW]) : dpp_left0(xi[PXL - HW + m]);
+        for (int m = 0; m < HW; ++m)
+          e[m] = (TEAMS == 2 && TM == 1) ? wave_from_left(pair_px<NP>(xi, PXL - HW + m), xr[63 * 4 + pipe_slot_offset<PXL>(PXL - HW + m) - BW])
+                                         : dpp_left0(pair_px<NP>(xi, PXL - HW + m));
 #pragma unroll
-        for (int k = 0; k < PXL; ++k) e[HW + k] = xi[k];
+        for (int k = 0; k < PXL; ++k) e[HW + k] = pair_px<NP>(xi, k);
 #pragma unroll
-        for (int m = 0; m < HW; ++m) e[HW + PXL + m] = (TEAMS == 2 && TM == 0) ? wave_from_right(xi[m], xr[BW + m]) : dpp_right0(xi[m]);
+        for (int m = 0; m < HW; ++m)
+          e[HW + PXL + m] = (TEAMS == 2 && TM == 0) ? wave_from_right(pair_px<NP>(xi, m), xr[BW + pipe_slot_offset<PXL>(m)]) : dpp_right0(pair_px<NP>(xi, m));
 #pragma unroll
-        for (int k = 0; k < PXL; ++k) {
-          float acc = uv[kMaxBlur] * e[k + 2 * HW];
+        for (int j = 0; j < NP; ++j) {
+          v2f acc = pk_set(uv[kMaxBlur]) * v2f{e[j + 2 * HW], e[j + 2 * HW + NP]};
 #pragma unroll
-          for (int b = 1; b < KT; ++b) acc = fmaf(uv[kMaxBlur + b], e[k + 2 * HW - b], acc);
-          hxn[k] = acc;
+          for (int b = 1; b < KT; ++b) acc = pk_fma(pk_set(uv[kMaxBlur + b]), v2f{e[j + 2 * HW - b], e[j + 2 * HW - b + NP]}, acc);
+          hxn[j] = acc;
         }
       }
       const int r = i - HW;                     // residual row: Hx[r] = sum_a u[a] hx[i - a]
-      float R[PXL];
+      v2f R[NP];
       {
         const bool rowok = r >= 0 && r < H;
         const float rmask = rowok ? 1.f : 0.f;
         gfix_raw<PXL, AL>(ypre[U & 3], c0, W);
 #pragma unroll
-        for (int k = 0; k < PXL; ++k) {
-          float acc = uv[0] * hxn[k];
+        for (int j = 0; j < NP; ++j) {
+          v2f acc = pk_set(uv[0]) * hxn[j];
 #pragma unroll
-          for (int a = 1; a < KT; ++a) acc = fmaf(uv[a], hxw[kRing4 ? ((U - a) & 3) : a - 1][k], acc);
+          for (int a = 1; a < KT; ++a) acc = pk_fma(pk_set(uv[a]), hxw[kRing4 ? ((U - a) & 3) : a - 1][j], acc);
           // masked by a factor, not a select: a select on (row, column) turns into one exec-masked block per pixel (8 per tick: the wave's longest
-          // stretch of unpacked arithmetic and half of its scalar instructions); every operand is finite (clamped rows, zeroed ring rows)
-          R[k] = (acc - ypre[U & 3][k]) * ((TEAMS == 2 ? cok : AL ? c0 < W : c0 + k < W) ? rmask : 0.f);
+          // stretch of unpacked arithmetic and half of its scalar instructions); every operand is finite (clamped rows, zeroed ring rows).
+          // The observation row arrives in natural order: its subtraction is unpacked (as many instructions as a re-pairing move and a packed one)
+          const v2f d = v2f{acc.x - ypre[U & 3][j], acc.y - ypre[U & 3][j + NP]};
+          R[j] = d * v2f{(TEAMS == 2 ? cok : AL ? c0 < W : c0 + j < W) ? rmask : 0.f, (TEAMS == 2 ? cok : AL ? c0 < W : c0 + j + NP < W) ? rmask : 0.f};
         }
-        if (TEAMS == 1 && A.f_out) {     // (the energy by-products are not built for two teams: pipe_teams_covered)
+        if (TEAMS == 1 && A.f_out) {     // (the energy by-products are not built for two teams: pipe_teams_covered); pixels in natural order
 #pragma unroll
-          for (int k = 0; k < PXL; ++k) facc = fma((double)R[k], (double)R[k], facc);
+          for (int k = 0; k < PXL; ++k) facc = fma((double)pair_px<NP>(R, k), (double)pair_px<NP>(R, k), facc);
         }
         if constexpr (!kRing4) {
 #pragma unroll
           for (int a = KT - 2; a >= 1; --a)
 #pragma unroll
-            for (int k = 0; k < PXL; ++k) hxw[a][k] = hxw[a - 1][k];
+            for (int j = 0; j < NP; ++j) hxw[a][j] = hxw[a - 1][j];
         }
 #pragma unroll
-        for (int k = 0; k < PXL; ++k) hxw[kRing4 ? (U & 3) : 0][k] = hxn[k];
+        for (int j = 0; j < NP; ++j) hxw[kRing4 ? (U & 3) : 0][j] = hxn[j];
       }
       if constexpr (TEAMS == 2) {   // publish this row's seam columns for the other team; the adjoint below runs on LAST tick's row
         if (TM == 0 ? lane == 63 : lane == 0) {
 #pragma unroll
-          for (int m = 0; m < HW; ++m) seam[SR + P * 4 + 2 * TM + m] = R[TM == 0 ? PXL - HW + m : m];
+          for (int m = 0; m < HW; ++m) seam[SR + P * 4 + 2 * TM + m] = pair_px<NP>(R, TM == 0 ? PXL - HW + m : m);
         }
 #pragma unroll
-        for (int k = 0; k < PXL; ++k) { const float tmp = R[k]; R[k] = Rprev[k]; Rprev[k] = tmp; }
+        for (int j = 0; j < NP; ++j) { const v2f tmp = R[j]; R[j] = Rprev[j]; Rprev[j] = tmp; }
       }
       {   // horizontal adjoint, then G[r - HW] = sum_a u[a] hR[r - 2HW + a]
-        float e[PXL + 2 * HW], gout[PXL];
+        float e[PXL + 2 * HW];
+        v2f gout[NP];
         const float* const sr = seam + SR + (P ^ 1) * 4;          // two teams: the other team's seam columns of the row
 #pragma unroll
-        for (int m = 0; m < HW; ++m) e[m] = (TEAMS == 2 && TM == 1) ? wave_from_left(R[PXL - HW + m], sr[m]) : dpp_left0(R[PXL - HW + m]);
+        for (int m = 0; m < HW; ++m)
+          e[m] = (TEAMS == 2 && TM == 1) ? wave_from_left(pair_px<NP>(R, PXL - HW + m), sr[m]) : dpp_left0(pair_px<NP>(R, PXL - HW + m));
 #pragma unroll
-        for (int k = 0; k < PXL; ++k) e[HW + k] = R[k];
+        for (int k = 0; k < PXL; ++k) e[HW + k] = pair_px<NP>(R, k);
 #pragma unroll
-        for (int m = 0; m < HW; ++m) e[HW + PXL + m] = (TEAMS == 2 && TM == 0) ? wave_from_right(R[m], sr[2 + m]) : dpp_right0(R[m]);
+        for (int m = 0; m < HW; ++m) e[HW + PXL + m] = (TEAMS == 2 && TM == 0) ? wave_from_right(pair_px<NP>(R, m), sr[2 + m]) : dpp_right0(pair_px<NP>(R, m));
 #pragma unroll
-        for (int k = 0; k < PXL; ++k) {
-          float hrn = uv[kMaxBlur] * e[k];
+        for (int j = 0; j < NP; ++j) {
+          v2f hrn = pk_set(uv[kMaxBlur]) * v2f{e[j], e[j + NP]};
 #pragma unroll
-          for (int b = 1; b < KT; ++b) hrn = fmaf(uv[kMaxBlur + b], e[k + b], hrn);
-          float acc = uv[KT - 1] * hrn;
+          for (int b = 1; b < KT; ++b) hrn = pk_fma(pk_set(uv[kMaxBlur + b]), v2f{e[j + b], e[j + b + NP]}, hrn);
+          v2f acc = pk_set(uv[KT - 1]) * hrn;
 #pragma unroll
-          for (int a = 0; a < KT - 1; ++a) acc = fmaf(uv[a], hrw[kRing4 ? ((U - (KT - 1 - a)) & 3) : KT - 2 - a][k], acc);
+          for (int a = 0; a < KT - 1; ++a) acc = pk_fma(pk_set(uv[a]), hrw[kRing4 ? ((U - (KT - 1 - a)) & 3) : KT - 2 - a][j], acc);
           if constexpr (!kRing4) {
 #pragma unroll
-            for (int a = KT - 2; a >= 1; --a) hrw[a][k] = hrw[a - 1][k];
+            for (int a = KT - 2; a >= 1; --a) hrw[a][j] = hrw[a - 1][j];
           }
-          hrw[kRing4 ? (U & 3) : 0][k] = hrn;
-          gout[k] = A.sigma_f * acc;
+          hrw[kRing4 ? (U & 3) : 0][j] = hrn;
+          gout[j] = pk_set(A.sigma_f) * acc;
         }
-        prow_store<PXL>(lds + L::o_g + P * RP, lane, gout);      // row t + 1 - D, read by C next tick
+        pairs_store<NP>(lds + L::o_g + P * RP, lane, gout);      // row t + 1 - D, read by C next tick
       }
       }   // KT > 0
       if constexpr (KT == 0) {
@@ -700,7 +742,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     crc.cstep = cstep;
     crc.cr_last = (c0 + PXL - 1 == W - 1 || (TEAMS == 2 && !cok)) ? 0.f : cstep;   // (two teams: ss stays 0 left of column 0)
 #pragma unroll
-    for (int i = 0; i < PXL / 2; ++i) crc.ncrv[i] = v2f{c0 + 2 * i == W - 1 ? 0.f : -cstep, c0 + 2 * i + 1 == W - 1 ? 0.f : -cstep};
+    for (int i = 0; i < PXL / 2; ++i) crc.ncrv[i] = v2f{c0 + i == W - 1 ? 0.f : -cstep, c0 + i + PXL / 2 == W - 1 ? 0.f : -cstep};
     float* const hout = lds + L::o_hand + (wave - 1) * 8 * RP;       // this wave's hand-off [2][4][BW] ([2][2][BW] for the last one if CHAIN)
     const bool from_state = CHAIN && wave == 1 && A.tv_in != nullptr;
     constexpr bool warm = WARM;
@@ -716,7 +758,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     if constexpr (RT && !AL) {
 #pragma unroll
       for (int i = 0; i < NP; ++i) {
-        const int ca = c0 + 2 * i, cb = ca + 1;
+        const int ca = c0 + i, cb = ca + NP;            // pair i = pixels (i, i + NP)
         const bool ina = ca >= st_lo && ca < st_hi, inb_ = cb >= st_lo && cb < st_hi;      // st_hi <= W
         om.mx[i] = v2f{ina ? 1.f : 0.f, inb_ ? 1.f : 0.f};
         om.my[i] = v2f{ina && ca < W - 1 ? 1.f : 0.f, inb_ && cb < W - 1 ? 1.f : 0.f};
@@ -761,13 +803,13 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
             float* d = sout + (size_t)brow * W;
             const int cg = c0 + 4 * g;
             if (warm) {
-              gstore4(d, cg, st_lo, st_hi, al, out.p[2 * g].x, out.p[2 * g].y, out.p[2 * g + 1].x, out.p[2 * g + 1].y);
-              gstore4(d + img, cg, st_lo, st_hi, al, out.q[2 * g].x, out.q[2 * g].y, out.q[2 * g + 1].x, out.q[2 * g + 1].y);
+              gstore4(d, cg, st_lo, st_hi, al, pair_px<NP>(out.p, 4 * g), pair_px<NP>(out.p, 4 * g + 1), pair_px<NP>(out.p, 4 * g + 2), pair_px<NP>(out.p, 4 * g + 3));
+              gstore4(d + img, cg, st_lo, st_hi, al, pair_px<NP>(out.q, 4 * g), pair_px<NP>(out.q, 4 * g + 1), pair_px<NP>(out.q, 4 * g + 2), pair_px<NP>(out.q, 4 * g + 3));
             } else {
-              gstore4(d, cg, st_lo, st_hi, al, out.rr[2 * g].x, out.rr[2 * g].y, out.rr[2 * g + 1].x, out.rr[2 * g + 1].y);
-              gstore4(d + img, cg, st_lo, st_hi, al, out.ss[2 * g].x, out.ss[2 * g].y, out.ss[2 * g + 1].x, out.ss[2 * g + 1].y);
-              gstore4(d + 2 * img, cg, st_lo, st_hi, al, out.p[2 * g].x, out.p[2 * g].y, out.p[2 * g + 1].x, out.p[2 * g + 1].y);
-              gstore4(d + 3 * img, cg, st_lo, st_hi, al, out.q[2 * g].x, out.q[2 * g].y, out.q[2 * g + 1].x, out.q[2 * g + 1].y);
+              gstore4(d, cg, st_lo, st_hi, al, pair_px<NP>(out.rr, 4 * g), pair_px<NP>(out.rr, 4 * g + 1), pair_px<NP>(out.rr, 4 * g + 2), pair_px<NP>(out.rr, 4 * g + 3));
+              gstore4(d + img, cg, st_lo, st_hi, al, pair_px<NP>(out.ss, 4 * g), pair_px<NP>(out.ss, 4 * g + 1), pair_px<NP>(out.ss, 4 * g + 2), pair_px<NP>(out.ss, 4 * g + 3));
+              gstore4(d + 2 * img, cg, st_lo, st_hi, al, pair_px<NP>(out.p, 4 * g), pair_px<NP>(out.p, 4 * g + 1), pair_px<NP>(out.p, 4 * g + 2), pair_px<NP>(out.p, 4 * g + 3));
+              gstore4(d + 3 * img, cg, st_lo, st_hi, al, pair_px<NP>(out.q, 4 * g), pair_px<NP>(out.q, 4 * g + 1), pair_px<NP>(out.q, 4 * g + 2), pair_px<NP>(out.q, 4 * g + 3));
             }
           }
         }
@@ -874,7 +916,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     // ---------------- N: Philox normals, one quad row-group ahead of C -------------------------------------
     // In the tick of row 4q + NI the normals of pixels NI*PXL/4 .. of quad q + 1 are drawn into the other half of the slab
     // (spread evenly over the ticks: a burst every 4th tick would stall every wave at the barrier).
-    float* const slab = slab_base + lane;              // normal (row q of the quad, pixel k) at slab[(q*PXL + k)*64]
+    float* const slab = slab_base + lane;              // normal (row q of the quad, pixel k) at slab[(q*PXL + pipe_slot(k))*64]
     const uint32_t iter = A.iteration;
     // kStateInN: the state hand-over of the L wave, here (four fields per pixel, rows fetched kSPF = 2 ticks ahead; row t - E - 1 is published at tick t)
     constexpr int nsf = 4, kSPF = 2;
@@ -921,7 +963,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
             float n4[4];
             quad_normals(A.key0, A.key1, iter, A.chain_offset + (uint32_t)chain, (uint32_t)qn * (uint32_t)W + (uint32_t)(c0 + k), n4);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) sl[(q * PXL + k) * 64] = n4[q];
+            for (int q = 0; q < 4; ++q) sl[(q * PXL + pipe_slot<PXL>(k)) * 64] = n4[q];
           }
         }
       }
@@ -939,11 +981,15 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     const float gam = A.tv.gamma;
     const float* const hin = lds + L::o_hand + (NT - 1) * 8 * RP;      // [2][4][BW], or [2][2][BW] in a chained launch
     constexpr int HSTR = CHAIN ? 2 * RP : 4 * RP;
-    float* const slab = slab_base + lane;              // normal (row q of the quad, pixel k) at slab[(q*PXL + k)*64]
+    float* const slab = slab_base + lane;              // normal (row q of the quad, pixel k) at slab[(q*PXL + pipe_slot(k))*64]
     double gacc = 0.0;        // sum |grad x_in| (A.g_out)
-    float crr[2][PXL], xprev[PXL];
+    constexpr int NP = PXL / 2;        // the lane's pixel pairs (j, j + NP), as in the TV stages
+    v2f crr[2][NP];
+    float xprev[PXL];
 #pragma unroll
-    for (int k = 0; k < PXL; ++k) crr[0][k] = crr[1][k] = xprev[k] = 0.f;
+    for (int k = 0; k < NP; ++k) crr[0][k] = crr[1][k] = pk_set(0.f);
+#pragma unroll
+    for (int k = 0; k < PXL; ++k) xprev[k] = 0.f;
     // RT: primal objective of the iterate this wave returns, sol^kc (the one the exit test of pass kc looks at; not needed when kc is the
     // last pass, whose iterate is returned untested): sum of squared divergences row by row, |grad sol| of row o - 1 once row o is known
     const bool want_obj = RT && !state_only && A.rt_base + kc < A.rt_total;
@@ -986,26 +1032,38 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         const int r3 = o + 3;
         gload_raw<PXL>(exq[(U + 3) & 3], A.extra + (size_t)chain * img + (size_t)min(max(r3, 0), H - 1) * W, cl, W, al);
       }
-      float css[PXL], xo[PXL], gv[PXL], prox[PXL];
-      prow_load<PXL>(crr[P], hin + (P ^ 1) * HSTR, lane);            // rr^K on row o (written last tick)
-      prow_load<PXL>(css, hin + (P ^ 1) * HSTR + RP, lane);
-      prow_load<PXL>(xo, ring_row(o), lane);
+      v2f css[NP], xop[NP], gvp[NP], proxp[NP];
+      pairs_load<NP>(crr[P], hin + (P ^ 1) * HSTR, lane);            // rr^K on row o (written last tick)
+      pairs_load<NP>(css, hin + (P ^ 1) * HSTR + RP, lane);
+      pairs_load<NP>(xop, ring_row(o), lane);
       if (KT > 0 || A.data_kind == LMC_DATA_IDENTITY || A.data_kind == LMC_DATA_MASK) {
-        prow_load<PXL>(gv, lds + L::o_g + (P ^ 1) * RP, lane);
+        pairs_load<NP>(gvp, lds + L::o_g + (P ^ 1) * RP, lane);
       } else {                                  // no data term: o_g is never written (stale LDS could hold NaN bit patterns)
 #pragma unroll
-        for (int j = 0; j < PXL; ++j) gv[j] = 0.f;
+        for (int j = 0; j < NP; ++j) gvp[j] = pk_set(0.f);
       }
       // two teams, right team: the left team's ss^K edge, published with its hand-off row (SA slot 2 NT)
-      const float ssl0 = (TEAMS == 2 && TM == 1) ? wave_from_left(css[PXL - 1], seam[SA + (P ^ 1) * 2 * (NT + 1) + 2 * NT]) : dpp_left0(css[PXL - 1]);
-      float dvs = 0.f;
+      const float ssl0 = (TEAMS == 2 && TM == 1) ? wave_from_left(css[NP - 1].y, seam[SA + (P ^ 1) * 2 * (NT + 1) + 2 * NT]) : dpp_left0(css[NP - 1].y);
+      const v2f ngam = pk_set(-gam);
+      v2f dvp[NP];
 #pragma unroll
-      for (int j = 0; j < PXL; ++j) {
-        const float ssl = j == 0 ? ssl0 : css[j - 1];
-        const float dv = (crr[P][j] - crr[P ^ 1][j]) + (css[j] - ssl);
-        prox[j] = fmaf(-gam, dv, xo[j]);
-        if constexpr (PM) { const float dm = dv * cmx[j]; dvs = fmaf(dm, dm, dvs); }
-        else if constexpr (RT) dvs = fmaf(dv, dv, dvs);
+      for (int j = 0; j < NP; ++j) {
+        const v2f ssl = left_pair(css, ssl0, j);
+        dvp[j] = (crr[P][j] - crr[P ^ 1][j]) + (css[j] - ssl);
+        proxp[j] = pk_fma(ngam, dvp[j], xop[j]);
+      }
+      // the by-products below (early exit's objective, MC-TV term, TV energy) name pixels in natural order: their sums keep their order
+      float xo[PXL], gv[PXL], prox[PXL];
+#pragma unroll
+      for (int j = 0; j < PXL; ++j) { xo[j] = pair_px<NP>(xop, j); gv[j] = pair_px<NP>(gvp, j); prox[j] = pair_px<NP>(proxp, j); }
+      float dvs = 0.f;
+      if constexpr (RT) {
+#pragma unroll
+        for (int j = 0; j < PXL; ++j) {
+          const float dv = pair_px<NP>(dvp, j);
+          if constexpr (PM) { const float dm = dv * cmx[j]; dvs = fmaf(dm, dm, dvs); }
+          else dvs = fmaf(dv, dv, dvs);
+        }
       }
       if constexpr (RT) {
         if (want_obj && o >= 0 && o < H) {
@@ -1076,34 +1134,46 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       if (o >= 0 && o < H) {
         const float* const slr = slab + ((o >> 2) & 1) * (4 * PXL * 64);
         const size_t go = (size_t)o * W;
+        // noise and prox-image rows arrive per pixel in natural order, the stores leave in natural order; in between the combine runs on the pairs.
+        // A group of four columns outside this workgroup's interior loads nothing and stores nothing; its lanes' arithmetic is discarded.
+        // The slab is read whatever the noise mode (zero-filled before the first tick, written by the N wave for Philox noise only), pair by pair:
+        // the slab holds a row's normals in slot order like every other LDS row, so a pair is two adjacent entries
+        float xi[PXL], ex[PXL];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) { xi[j] = slr[(NI * PXL + 2 * j) * 64]; xi[j + NP] = slr[(NI * PXL + 2 * j + 1) * 64]; }
+#pragma unroll
+        for (int k = 0; k < PXL; ++k) ex[k] = 0.f;
+        if constexpr (VM) {
+#pragma unroll
+          for (int g = 0; g < PXL / 4; ++g) {
+            if (c0 + 4 * g < st_hi && c0 + 4 * g + 3 >= st_lo) {      // the group touches this workgroup's interior
+              if (A.noise_mode == LMC_NOISE_INJECTED) {
+                const float* nrow = A.noise + (size_t)chain * img + go;
+                if (al) {
+                  const float4 v = *reinterpret_cast<const float4*>(nrow + c0 + 4 * g);
+                  xi[4 * g] = v.x; xi[4 * g + 1] = v.y; xi[4 * g + 2] = v.z; xi[4 * g + 3] = v.w;
+                } else load4_dword_aligned(xi[4 * g], xi[4 * g + 1], xi[4 * g + 2], xi[4 * g + 3], nrow, c0 + 4 * g, W);
+              }
+              if (XT && A.extra) {
+                ex[4 * g] = exq[U][4 * g]; ex[4 * g + 1] = exq[U][4 * g + 1]; ex[4 * g + 2] = exq[U][4 * g + 2]; ex[4 * g + 3] = exq[U][4 * g + 3];
+                if constexpr (!AL) unshift4_dword_aligned(ex[4 * g], ex[4 * g + 1], ex[4 * g + 2], ex[4 * g + 3], c0 + 4 * g, W);
+              }
+            }
+          }
+        }
+        v2f ovp[NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+          const v2f x = xop[j];
+          v2f gr = v2f{gv[j], gv[j + NP]};      // (gv: with the MC-TV term, if any)
+          if (XT && VM && A.extra) gr = pk_fma(pk_set(A.extra_coef), x - v2f{ex[j], ex[j + NP]}, gr);
+          const v2f in = pk_fma(pk_set(-A.t), gr, pk_fma(pk_set(A.b), proxp[j], pk_set(A.s) * v2f{xi[j], xi[j + NP]}));
+          ovp[j] = pk_fma(pk_set(A.a), x, in);
+        }
 #pragma unroll
         for (int g = 0; g < PXL / 4; ++g) {
-          if (c0 + 4 * g < st_hi && c0 + 4 * g + 3 >= st_lo) {      // the group touches this workgroup's interior
-            float xi[4] = {0.f, 0.f, 0.f, 0.f}, ex[4] = {0.f, 0.f, 0.f, 0.f};
-            if (A.noise_mode == LMC_NOISE_PHILOX) {
-#pragma unroll
-              for (int q = 0; q < 4; ++q) xi[q] = slr[(NI * PXL + 4 * g + q) * 64];
-            } else if (VM && A.noise_mode == LMC_NOISE_INJECTED) {
-              const float* nrow = A.noise + (size_t)chain * img + go;
-              if (al) {
-                const float4 v = *reinterpret_cast<const float4*>(nrow + c0 + 4 * g);
-                xi[0] = v.x; xi[1] = v.y; xi[2] = v.z; xi[3] = v.w;
-              } else load4_dword_aligned(xi[0], xi[1], xi[2], xi[3], nrow, c0 + 4 * g, W);
-            }
-            if (XT && VM && A.extra) {
-              ex[0] = exq[U][4 * g]; ex[1] = exq[U][4 * g + 1]; ex[2] = exq[U][4 * g + 2]; ex[3] = exq[U][4 * g + 3];
-              if constexpr (!AL) unshift4_dword_aligned(ex[0], ex[1], ex[2], ex[3], c0 + 4 * g, W);
-            }
-            float ov[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const float x = xo[4 * g + q];
-              float gr = gv[4 * g + q];
-              if (XT && VM && A.extra) gr = fmaf(A.extra_coef, x - ex[q], gr);
-              ov[q] = fmaf(A.a, x, fmaf(-A.t, gr, fmaf(A.b, prox[4 * g + q], A.s * xi[q])));
-            }
-            gstore4(xout + go, c0 + 4 * g, st_lo, st_hi, al, ov[0], ov[1], ov[2], ov[3]);
-          }
+          if (c0 + 4 * g < st_hi && c0 + 4 * g + 3 >= st_lo)
+            gstore4(xout + go, c0 + 4 * g, st_lo, st_hi, al, pair_px<NP>(ovp, 4 * g), pair_px<NP>(ovp, 4 * g + 1), pair_px<NP>(ovp, 4 * g + 2), pair_px<NP>(ovp, 4 * g + 3));
         }
       }
       __syncthreads();
