@@ -185,6 +185,23 @@ typedef struct lmc_problem {
   const float* prox_scale;
   int64_t prox_scale_chain_stride;
   int32_t prox_scale_pixel_stride;
+  /* Box constraint x in [box_lo, box_hi] (appended; LMC_ATOMI_ABI_VERSION stays 4, struct_size tells the layouts apart).  box_enable = 0 (default): none, the
+   * behaviour of before bit for bit.  1: the prior is g + the indicator of the box, and the prox is that of the sum:
+   *  - LMC_PRIOR_TV_ISO / TV_ANISO: Beck and Teboulle's constrained fast gradient projection -- the primal iterate of EVERY dual iteration and the returned one
+   *    are projected onto the box (not "clip afterwards": the two differ).  tv_niter >= 1 (0: LMC_E_INVALID).  Isotropic, tv_niter in {10, 20, ... 60} (after
+   *    tv_lagged_output), W > 128: the full-width pipeline (myula_step_pipe_box_kernel, two teams where lmc_set_step_variant's rule for 8 holds); everything
+   *    else, and the anisotropic prior at every width: the tiled kernel (myula_step_tile_box_kernel).
+   *  - LMC_PRIOR_NONE / L2 / L1 / EPROX (separable): the clamp of the prox of g, formed by one elementwise launch before the fused step (with prox_scale: the same
+   *    launch).  LMC_PRIOR_NONE: the indicator alone, prox = projection.
+   * Bounds: box_lo < box_hi, neither NaN (else LMC_E_INVALID); infinite ends are allowed ((0, +inf) is positivity).
+   * Honoured by lmc_myula_create / lmc_sampler_step and lmc_fused_eval (the prox, and the a, t, b combination with it).  LMC_E_UNSUPPORTED, with the reason
+   * in lmc_last_error: LMC_PRIOR_HAAR_L1 (not separable: clipping its prox is not the prox); tv_rtol > 0; tv_warm; lmc_mymala_create (the target would be +inf
+   * outside the box); lmc_ulpda_create; lmc_skrock_create; lmc_sampler_sapg / lmc_sampler_set_prior_sigma on a handle with a box (the d / k homogeneity argument
+   * does not hold on a bounded set); a forced step_variant without a box form.
+   * lmc_energies, lmc_sampler_energies and lmc_prior_statistic keep reporting sigma g(x) WITHOUT the indicator: MYULA iterates live in the Moreau-Yosida
+   * neighbourhood of the box, not in it. */
+  int32_t box_enable;
+  float box_lo, box_hi;
 } lmc_problem;
 
 /* ---- library ------------------------------------------------------------------------- */

@@ -86,6 +86,8 @@ class lmc_problem(C.Structure):
         ("graph_replay", C.c_int32),
         ("eprox_kind", C.c_int32), ("eprox_p0", C.c_float), ("eprox_p1", C.c_float), ("eprox_scale_mask", C.c_int32),
         ("prox_scale", C.c_void_p), ("prox_scale_chain_stride", C.c_int64), ("prox_scale_pixel_stride", C.c_int32),
+        # box constraint (appended; ABI stays 4)
+        ("box_enable", C.c_int32), ("box_lo", C.c_float), ("box_hi", C.c_float),
     ]
 
 

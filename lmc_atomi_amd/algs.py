@@ -32,6 +32,12 @@ def _prior_descriptor(proxg):
     return fn()
 
 
+def _refuse_box(prior, who, why):
+    """``NotImplementedError`` for a prior with ``bounds=`` where ``who`` has no box-constrained form (before any handle exists)."""
+    if prior.get("box") is not None:
+        raise NotImplementedError(f"{who} does not take a prior with bounds: {why}")
+
+
 def _data_descriptor(proxf):
     if proxf is None:
         return {"data_kind": _capi.DATA_NONE}
@@ -454,6 +460,10 @@ class MYULASampler:
         groups = _check_chain_groups(chain_groups, moments)
         if tau is None:
             raise NotImplementedError("tau=None (backtracking) is not implemented by the reference loop either")
+        if self._box_refusal is not None:
+            _refuse_box(_prior_descriptor(proxg), *self._box_refusal)
+        if tv_warm and _prior_descriptor(proxg).get("box") is not None:
+            raise NotImplementedError("a prior with bounds has no warm-started dual: tv_warm must be off")
         self.dims = (int(dims[0]), int(dims[1]))
         self.n_chains = int(n_chains)
         self.device = _dev.device(device)
@@ -491,6 +501,7 @@ class MYULASampler:
         self._set_chain_groups(groups)
 
     _create_fn = "lmc_myula_create"
+    _box_refusal = None          # (who, why) of a subclass that has no box-constrained form: raised before a handle exists
 
     def _create(self, cfg):
         return getattr(_dev.lib(), self._create_fn)(C.byref(cfg), C.byref(self._h))
@@ -774,6 +785,8 @@ class ULPDASampler(MYULASampler):
         groups = _check_chain_groups(chain_groups, moments)
         if not isinstance(A, Gradient):
             raise NotImplementedError("ULPDA on the GPU supports A = Gradient (the reference's operator, prox_lmc_deconv.py:98)")
+        if getattr(proxg, "bounds", None) is not None:
+            raise NotImplementedError("ULPDA does not take a prior with bounds: its prior enters through the dual ball of g o A, which has no box form; use MYULA")
         if isinstance(proxg, L21):
             prior = {"prior_kind": _capi.PRIOR_TV_ISO, "prior_sigma": proxg.sigma, "tv_niter": 1, "tv_betas": [0.0]}
         elif isinstance(proxg, L1):
@@ -1087,6 +1100,8 @@ class MYMALASampler(MYULASampler):
 
     _create_fn = "lmc_mymala_create"
 
+    _box_refusal = ("MYMALA", "its target would be +infinity outside the box, where MYULA's proposals land; use MYULA")
+
     def acceptance(self):
         """(accepted proposals per chain [C] int64 tensor, log acceptance ratio of the last iteration [C] float64 tensor)."""
         acc = torch.empty(self.n_chains, dtype=torch.int64, device=self.device)
@@ -1176,6 +1191,7 @@ class SKROCKSampler(MYULASampler):
     def __init__(self, proxf, proxg, dims, n_stages=10, eta=0.05, **kw):
         _check_chain_groups(kw.get("chain_groups"), kw.get("moments", False))      # before anything touches the proxes
         prior = _prior_descriptor(proxg)
+        _refuse_box(prior, "SK-ROCK", "its stability bound is derived for the unconstrained Moreau-Yosida envelope; use MYULA")
         if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
             raise NotImplementedError("SK-ROCK runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
         if prior.get("tv_warm") or kw.get("tv_warm"):
@@ -1245,6 +1261,7 @@ def EstimatePriorWeight(proxf, proxg, x0, tau, gamma, n_updates, theta_bounds, t
     if dims is None:
         raise ValueError("image shape unknown: pass dims=(ny, nx)")
     prior = _prior_descriptor(proxg)
+    _refuse_box(prior, "EstimatePriorWeight", "the d / k homogeneity argument of the estimator does not hold on a bounded set")
     if theta0 is None:
         theta0 = _prior_weight(proxg)
     _sapg_config(n_updates, theta_bounds, theta0, warmup, iters_per_update, step_scale, step_exponent, average_from, dim_eff)

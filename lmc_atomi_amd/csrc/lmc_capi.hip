@@ -149,7 +149,7 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
     A.extra = sc.extra;
     A.extra_coef = -q.ncvx_lambda / q.ncvx_gamma;
   }
-  if (A.prior_kind == LMC_PRIOR_HAAR_L1 || A.prior_kind == LMC_PRIOR_EPROX) HIP_TRY(sc.need_prox(npx));
+  if (A.prior_kind == LMC_PRIOR_HAAR_L1 || A.prior_kind == LMC_PRIOR_EPROX || (A.box && A.prior_kind != LMC_PRIOR_TV_ISO)) HIP_TRY(sc.need_prox(npx));
   if (A.prior_kind == LMC_PRIOR_TV_ISO && q.tv_rtol > 0.f && tv_prior_rt_mode(q, A, pt) != 2) {     // the early exit decided on the device
     HIP_TRY(sc.need_prox(npx));
     HIP_TRY(sc.rt_tv.need((size_t)n_img, q.tv_niter));
@@ -168,7 +168,9 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
     A.prox_ext = sc.prox;
   }
   hipError_t e = launch_step(A, variant_of(q), S(stream), nullptr, sc.state[0], sc.state[1], sc.prox);
-  if (e == hipErrorInvalidConfiguration) return fail(LMC_E_UNSUPPORTED, "no step-kernel variant covers this configuration");
+  if (e == hipErrorInvalidConfiguration)
+    return fail(LMC_E_UNSUPPORTED, A.box ? "step_variant %d has no box-constrained form of this prior (TV: auto, 1 tile, 7 / 8 pipe where the pipe covers the problem)"
+                                         : "no step-kernel variant covers this configuration", variant_of(q));
   HIP_TRY(e);
   return LMC_OK;
 }

@@ -1,6 +1,7 @@
 // Shared host/device declarations for liblmc_atomi (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "lmc_atomi.h"
 
@@ -47,8 +48,9 @@ struct StepArgs {
   // host side only (no kernel reads it; the anisotropic kernels are instantiations of their own): prior_kind == LMC_PRIOR_TV_ISO with the box
   // projection of the dual, p = clip(r, -1, 1) per component, instead of the pixel-norm ball -- the prox of sigma (|d_r x|_1 + |d_c x|_1)
   alignas(8) uint32_t tv_aniso;
-  uint32_t unused;           // the two hold the argument layout of every step kernel (an 8-byte slot: dropping it moves the fields behind it, and with
-                             // them the register allocation and spills of some 180 kernels)
+  uint32_t box;              // host side only, like tv_aniso (the box kernels are instantiations of their own): the prox is that of g + the indicator of
+                             // [box_lo, box_hi] (the fields of those names further down).  This slot and tv_aniso hold the argument layout of every step kernel (an 8-byte slot: dropping it
+                             // moves the fields behind it, and with them the register allocation and spills of some 180 kernels)
   uint32_t chain_offset;     // global id of chain 0 (counter word 2 = chain_offset + c)
   const float* x_in;
   float* x_out;
@@ -76,11 +78,17 @@ struct StepArgs {
   double* f_out;
   double* g_out;
   float g_scale;      // rows kernel only: the launch returns at once when *skip_flag != 0 (inner solver already converged)
+  // box constraint x in [box_lo, box_hi] (lmc_problem.box_enable, StepArgs::box; infinite ends allowed): read by the box kernels only (myula_step_pipe_box_kernel,
+  // myula_step_pipe_box2_kernel, myula_step_tile_box_kernel).  The two floats sit in the 4-byte holes that the alignment of the pointers behind g_scale and
+  // fused_iters leaves: no field moves and the argument keeps its size (appended at the end they grow it, and the compiler then lays out the argument
+  // loads of some 170 existing kernels differently -- scripts/kernel_resources.py --code-hash).  The asserts below hold the layout.
+  float box_lo;
   // prox computed by a preceding launch (Haar-l1 wavelet prior): px = prox_ext[c][i][j]; the kernel's own prior is NONE
   const float* prox_ext;
   // block kernel only (Haar prior, no MC-TV term): fused_iters = 2 runs TWO iterations on the thread's 8 x 8 block before it goes back to memory
   // (iterations `iteration` and `iteration + 1`; x_out <- x_{k+2}); x_mid (may be NULL, may be x_in itself: the update is block-local) <- x_{k+1}
   int fused_iters;
+  float box_hi;       // (see box_lo)
   float* x_mid;
   // pipe kernel, RT instantiations only: per-chain early exit of the TV prox (pyproximal.TV's rtol; lmc_problem.tv_rtol / ncvx_rtol).  A chain's
   // workgroup runs rt_kc[c] dual updates in all (counted over the links of a chained prox; this launch holds updates rt_base + 1 .. rt_base + K),
@@ -93,6 +101,12 @@ struct StepArgs {
   double* rt_obj;
   int rt_stride, rt_base, rt_total;
 };
+
+static_assert(sizeof(StepArgs) == 952, "the argument of every step kernel keeps its size");
+static_assert(offsetof(StepArgs, box_lo) == offsetof(StepArgs, g_scale) + 4 && offsetof(StepArgs, prox_ext) == offsetof(StepArgs, g_scale) + 8,
+              "box_lo fills the hole behind g_scale");
+static_assert(offsetof(StepArgs, box_hi) == offsetof(StepArgs, fused_iters) + 4 && offsetof(StepArgs, x_mid) == offsetof(StepArgs, fused_iters) + 8,
+              "box_hi fills the hole behind fused_iters");
 
 constexpr uint32_t kPhiloxStream = 0x4C4D4301u;  // counter word 3 (noise field)
 constexpr uint32_t kPhiloxAccept = 0x4C4D4302u;  // counter word 3 (Metropolis uniforms: ctr = (0, iteration, chain, this))

@@ -60,6 +60,8 @@ struct Problem {
   float eprox_p0 = 0.f, eprox_p1 = 0.f;
   const float* prox_scale = nullptr;   // array-valued epsg: per-chain / per-pixel multiplier of the prox parameter (closed-form priors of MYULA only)
   int64_t prox_scale_cs = 0, prox_scale_ps = 0;
+  int box = 0;              // lmc_problem.box_enable: x in [box_lo, box_hi], the prox is that of g + the indicator of the box
+  float box_lo = 0.f, box_hi = 0.f;
   int variant = 0;          // 0: the library default (g_variant)
   float implicit_tol = 0.f; // 0: the library default (g_cg_tol); < 0: disabled
 };
@@ -149,6 +151,7 @@ int fill_taps(lmc::BlurTaps& T, const float* h, int kh, int kw, int oy, int ox);
 void default_betas(float* b, int n);
 int load_problem(const lmc_problem* p, Problem& q);
 int check_prox_prior(const Problem& q, float b);
+int check_no_box(const Problem& q, const char* who, const char* why);
 int make_step_args(const Problem& q, float a, float t, float b, float pt, float s, lmc::StepArgs& A);
 void sanitize_pointers(lmc::StepArgs& A);
 int variant_of(const Problem& q);

@@ -30,6 +30,10 @@ hipError_t launch_dual_project(const float* y, float* out, int64_t n_img, int H,
 hipError_t launch_eprox(int kind, const float* x, float* out, int64_t n, float p0, float p1, hipStream_t st);
 hipError_t launch_prior_prox_scaled(int prior, int kind, const float* x, float* out, int64_t n_chains, int64_t img, const float* scale, int64_t cs, int64_t ps,
                                     float pt, float sigma, float p0, float p1, int mask, hipStream_t st);
+// clip(prox_{t g}(x), lo, hi) for the separable priors (none, l2, l1, EPROX), lmc_box.hip: scale == NULL -- p0 / p1 are the step's parameters (StepArgs::prior_p0 /
+// prior_p1); scale != NULL -- array-valued prox parameter, the arguments of launch_prior_prox_scaled
+hipError_t launch_box_prox(int prior, int kind, const float* x, float* out, int64_t n_chains, int64_t img, const float* scale, int64_t cs, int64_t ps,
+                           float pt, float sigma, float p0, float p1, int mask, float lo, float hi, hipStream_t st);
 hipError_t launch_haar_prox(const float* x, float* out, int64_t n_img, int H, int W, float thr, hipStream_t st);
 hipError_t launch_chain_probes(const float* x, float* out, int64_t n_img, int H, int W, int ph, int pw, hipStream_t st);
 hipError_t launch_haar_value(const float* x, int64_t n_img, int H, int W, float sigma, double* val, hipStream_t st);

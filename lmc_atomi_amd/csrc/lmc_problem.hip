@@ -6,6 +6,10 @@
 
 #include "lmc_host.h"
 
+namespace lmc {
+int pipe_taps(StepArgs& a);      // lmc_step_pipe.hip: centred taps of the pipe kernels, returns KT
+}
+
 namespace lmc::host {
 
 int fill_taps(lmc::BlurTaps& T, const float* h, int kh, int kw, int oy, int ox) {
@@ -57,6 +61,8 @@ int load_problem(const lmc_problem* p, Problem& q) {
   }
   q.prior_kind = p->prior_kind;
   q.prior_sigma = p->prior_sigma;
+  if (p->box_enable && (p->prior_kind == LMC_PRIOR_TV_ISO || p->prior_kind == LMC_PRIOR_TV_ANISO) && p->tv_niter == 0)
+    return fail(LMC_E_INVALID, "box with a TV prior: the projection runs inside the dual iterations, tv_niter must be >= 1");
   switch (p->prior_kind) {
     case LMC_PRIOR_NONE: case LMC_PRIOR_L2: case LMC_PRIOR_L1: break;
     case LMC_PRIOR_EPROX:
@@ -133,7 +139,24 @@ int load_problem(const lmc_problem* p, Problem& q) {
   q.tv_warm_asked = p->tv_warm != 0;
   if (!(p->implicit_tol == p->implicit_tol)) return fail(LMC_E_INVALID, "implicit_tol is NaN");
   q.implicit_tol = p->implicit_tol;
+  if (p->box_enable) {
+    if (p->box_enable != 1) return fail(LMC_E_INVALID, "box_enable must be 0 or 1 (got %d)", p->box_enable);
+    if (!(p->box_lo == p->box_lo) || !(p->box_hi == p->box_hi)) return fail(LMC_E_INVALID, "box: a bound is NaN");
+    if (!(p->box_lo < p->box_hi)) return fail(LMC_E_INVALID, "box: needs box_lo < box_hi (got [%g, %g])", (double)p->box_lo, (double)p->box_hi);
+    if (p->prior_kind == LMC_PRIOR_HAAR_L1)
+      return fail(LMC_E_UNSUPPORTED, "box with LMC_PRIOR_HAAR_L1: the prior is not separable in the pixels, so the clamp of its prox is not the prox of the sum");
+    const bool tv = p->prior_kind == LMC_PRIOR_TV_ISO || p->prior_kind == LMC_PRIOR_TV_ANISO;
+    if (tv && p->tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "box with tv_rtol > 0: the early exit's objective is that of the unconstrained prox; use the fixed count, tv_rtol = 0");
+    if (tv && p->tv_warm) return fail(LMC_E_UNSUPPORTED, "box with tv_warm: the warm-started dual has no box form");
+    q.box = 1; q.box_lo = p->box_lo; q.box_hi = p->box_hi;
+  }
   return LMC_OK;
+}
+
+// The entry points that have no box-constrained form refuse a problem that carries one.
+int check_no_box(const Problem& q, const char* who, const char* why) {
+  if (!q.box) return LMC_OK;
+  return fail(LMC_E_UNSUPPORTED, "%s does not take a box constraint (lmc_problem.box_enable): %s", who, why);
 }
 
 // What the entry points that form prox_g (MYULA, MYMALA, lmc_fused_eval) ask of the anisotropic TV prior beyond load_problem: an iteration
@@ -180,6 +203,8 @@ int make_step_args(const Problem& q, float a, float t, float b, float pt, float 
     A.ncvx_kind = q.ncvx_kind; A.ncvx_lambda = q.ncvx_lambda; A.ncvx_gamma = q.ncvx_gamma; A.ncvx_inv_gamma = 1.f / q.ncvx_gamma;
   }
   // LMC_NCVX_ME_TV: the caller runs me_tv_prox first and sets A.extra / A.extra_coef
+  // box constraint: part of the prox, so a launch without a prox term (b = 0) carries none; a lagged 1-iteration TV prox (x itself) becomes the projection
+  if (q.box && b != 0.f) { A.box = 1; A.box_lo = q.box_lo; A.box_hi = q.box_hi; }
   A.a = a; A.t = t; A.b = b; A.s = s;
   A.noise_mode = LMC_NOISE_NONE;
   return LMC_OK;
@@ -202,7 +227,48 @@ float tol_of(const Problem& q) { return q.implicit_tol > 0.f ? q.implicit_tol : 
 
 // Picks the step-kernel variant.  auto: the split streaming pipeline (two wave groups, 4 waves/SIMD) when
 // it covers the configuration (W <= 512, separable blur <= 7x7, supported K), else the LDS-tiled kernel.
+static hipError_t launch_step_nobox(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf);
+
+// The box-constrained forms.  Separable priors: one elementwise launch forms clip(prox) into pxbuf, then the step of the variant asked for consumes it.
+// TV priors: the pipe kernel's box instantiations (isotropic; auto, 7, 8) or the tile kernel's (either form; auto, 1); a forced variant without a box
+// form is not covered.
 hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
+  if (!A_in.box) return launch_step_nobox(A_in, variant, st, name, state0, state1, pxbuf);
+  lmc::StepArgs A = A_in;
+  if (A.prior_kind != LMC_PRIOR_TV_ISO) {
+    if (A.prior_kind == LMC_PRIOR_HAAR_L1 || !pxbuf) return hipErrorInvalidConfiguration;
+    if (!A.prox_ext) {     // (a ready-made prox is clamped already: array-valued epsg)
+      hipError_t e = lmc::launch_box_prox(A.prior_kind, A.eprox_kind, A.x_in, pxbuf, A.C, (int64_t)A.H * A.W, nullptr, 0, 0, 0.f, 0.f, A.prior_p0, A.prior_p1, 0,
+                                          A.box_lo, A.box_hi, st);
+      if (e != hipSuccess) return e;
+      A.prox_ext = pxbuf;
+    }
+    A.prior_kind = LMC_PRIOR_NONE;
+    A.box = 0;
+    return launch_step_nobox(A, variant, st, name, state0, state1, pxbuf);
+  }
+  const int v = variant;
+  if (v == 0 || v == 7 || v == 8) {
+    const int links = A.tv_aniso ? 0 : lmc::pipe_links(A);
+    if (links == 1 || (links > 1 && state0 && state1 && v != 8)) {
+      if (name) {       // the name of the kernel launch_step_pipe picks: two teams where covered unless one team is forced
+        lmc::StepArgs T = A;
+        const bool two = links == 1 && v != 7 && lmc::pipe_teams_covered(A, lmc::pipe_taps(T));
+        *name = two ? "myula_step_pipe_box2_kernel" : "myula_step_pipe_box_kernel";
+      }
+      return lmc::launch_step_pipe(A, st, state0, state1, v == 7 ? 1 : v == 8 ? 2 : 0);
+    }
+  }
+  if (v != 0 && v != 1) return hipErrorInvalidConfiguration;
+  if (name) *name = "myula_step_tile_box_kernel";
+  if (lmc::tile_needs_chunks(A)) {
+    if (!state0 || !state1) return hipErrorInvalidConfiguration;
+    return lmc::launch_step_tile_chunked(A, state0, state1, st);
+  }
+  return lmc::launch_step_tile(A, st);
+}
+
+static hipError_t launch_step_nobox(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
   int v = variant;
   // no stencil in the data term and a prox local to 8 x 8 blocks (Haar-l1, l2, l1, none): the register-block kernel
   if ((v == 0 || v == 5) && lmc::block_supported(A_in)) {

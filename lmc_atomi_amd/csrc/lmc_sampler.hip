@@ -62,6 +62,7 @@ int check_weight_settable(const lmc_sampler* s) {
   if (s->kind == 1) return fail(LMC_E_UNSUPPORTED, "the prior weight of a ULPDA handle cannot change");
   if (s->prob.tv_warm) return fail(LMC_E_UNSUPPORTED, "tv_warm carries a dual that belongs to the weight it was formed with: the weight cannot change");
   if (s->prob.prox_scale) return fail(LMC_E_UNSUPPORTED, "prox_scale (array-valued epsg) carries the weights itself: the scalar weight cannot change");
+  if (s->prob.box) return fail(LMC_E_UNSUPPORTED, "the handle carries a box constraint: the estimation of the weight rests on the homogeneity of g on the whole space (the d / k term), which does not hold on a bounded set");
   if (s->prob.prior_kind == LMC_PRIOR_NONE || s->prob.prior_kind == LMC_PRIOR_EPROX)
     return fail(LMC_E_UNSUPPORTED, "prior_kind %d has no weight prior_sigma", s->prob.prior_kind);
   return LMC_OK;
@@ -125,7 +126,8 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     if (e == hipSuccess) e = hipMalloc(&s->tvstate[1], 4 * nbytes);
   }
   if (e == hipSuccess && s->prob.ncvx_kind == LMC_NCVX_ME_TV) e = hipMalloc(&s->extra, nbytes);
-  if (e == hipSuccess && (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 || s->prob.prior_kind == LMC_PRIOR_EPROX || s->prob.prox_scale)) e = hipMalloc(&s->pxbuf, nbytes);
+  if (e == hipSuccess && (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 || s->prob.prior_kind == LMC_PRIOR_EPROX || s->prob.prox_scale ||
+                          (s->base.box && s->base.prior_kind != LMC_PRIOR_TV_ISO))) e = hipMalloc(&s->pxbuf, nbytes);
   if (e == hipSuccess && s->prob.tv_rtol > 0.f && s->base.prior_kind == LMC_PRIOR_TV_ISO) {
     if (s->prob.tv_warm) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "tv_rtol > 0 and tv_warm exclude each other"); }
     const int mode = tv_prior_rt_mode(s->prob, s->base, s->epsg * s->gamma);     // 1: inside the fused launch, 0: prox alone, 2: pass by pass
@@ -145,7 +147,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     s->pol_blockpair = ipl == 1 ? 0 : (ipl == 2 ? 1 : (env_int("LMC_BLOCK_PAIR", 1) != 0));
     s->pol_overlap = q.moments_overlap ? q.moments_overlap : (getenv("LMC_MOMENTS_OVERLAP") ? (env_int("LMC_MOMENTS_OVERLAP", 0) ? 1 : -1) : 0);
     s->pol_bg_wgs = q.moments_bg_wgs > 0 ? q.moments_bg_wgs : env_int("LMC_MOMENTS_BG_WGS", -1);
-    if (q.prox_scale) { s->pol_pair = 0; s->pol_blockpair = 0; }   // array-valued epsg: the prox is its own launch before every step
+    if (q.prox_scale || q.box) { s->pol_pair = 0; s->pol_blockpair = 0; }   // array-valued epsg, box constraint: the prox is its own launch before every step
   }
   if (e == hipSuccess && s->prob.tv_warm) {
     lmc::StepArgs probe = s->base;
@@ -466,8 +468,13 @@ static int myula_single(lmc_sampler* s, SideMoments& m, const float* noise, bool
   }
   if (s->prob.prox_scale && A.prior_kind != LMC_PRIOR_NONE) {   // array-valued epsg: prox_{epsg[c,i] gamma g} first, consumed as a ready-made prox
     const Problem& q = s->prob;
+    if (A.box)     // the same launch with the clamp
+      HIP_TRY(lmc::launch_box_prox(q.prior_kind, q.eprox_kind, A.x_in, s->pxbuf, s->C, (int64_t)q.H * q.W, q.prox_scale, q.prox_scale_cs, q.prox_scale_ps,
+                                   s->epsg * s->gamma, q.prior_sigma, q.eprox_p0, q.eprox_p1, q.eprox_mask, A.box_lo, A.box_hi, st));
+    else
     HIP_TRY(lmc::launch_prior_prox_scaled(q.prior_kind, q.eprox_kind, A.x_in, s->pxbuf, s->C, (int64_t)q.H * q.W, q.prox_scale, q.prox_scale_cs, q.prox_scale_ps,
                                           s->epsg * s->gamma, q.prior_sigma, q.eprox_p0, q.eprox_p1, q.eprox_mask, st));
+    A.box = 0;
     A.prior_kind = LMC_PRIOR_NONE;
     A.prox_ext = s->pxbuf;
   }
@@ -482,7 +489,9 @@ static int myula_single(lmc_sampler* s, SideMoments& m, const float* noise, bool
   } else {
     e = launch_step(A, variant_of(s->prob), st, &kname, s->tvstate[0], s->tvstate[1], s->pxbuf);
   }
-  if (e == hipErrorInvalidConfiguration) return fail(LMC_E_UNSUPPORTED, "no step-kernel variant covers this configuration");
+  if (e == hipErrorInvalidConfiguration)
+    return fail(LMC_E_UNSUPPORTED, s->base.box ? "step_variant %d has no box-constrained form of this prior (TV: auto, 1 tile, 7 / 8 pipe where the pipe covers the problem)"
+                                               : "no step-kernel variant covers this configuration", variant_of(s->prob));
   HIP_TRY(e);
   if (kname) s->kernel_name = kname;
   if (s->timing) HIP_TRY(hipEventRecord(s->ev[2 * s->last_launches + 1], st));
@@ -570,6 +579,7 @@ int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   if (s->tvwarm[0]) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA needs a proposal mean that is a function of x alone: tv_warm is not allowed"); }
   if (s->rtmp || s->rt_tv.kc) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA with tv_rtol > 0 is not built (use the fixed-count prox, tv_rtol = 0)"); }
   if (s->prob.prox_scale) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA takes a scalar epsg (the reference's array-valued epsg is MYULA's, algs.py:509)"); }
+  if (s->prob.box) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_box(q, "MYMALA", "its target would be +infinity outside the box, where MYULA's proposals land; use MYULA"); }
   s->kind = 2;
   const size_t nbytes = sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W;
   hipError_t e = hipMalloc(&s->mx, nbytes);
@@ -684,6 +694,7 @@ int lmc_skrock_create(const lmc_myula_config* cfg, int32_t n_stages, float eta, 
   if (s->tvwarm[0]) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "SK-ROCK evaluates the drift at s different points per iteration: tv_warm (a dual carried between evaluations) is not allowed"); }
   if (s->rtmp || s->rt_tv.kc) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "SK-ROCK with tv_rtol > 0 is not built (use the fixed-count prox, tv_rtol = 0)"); }
   if (s->prob.prox_scale) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "SK-ROCK takes a scalar epsg (array-valued epsg is MYULA's)"); }
+  if (s->prob.box) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_box(q, "SK-ROCK", "its stability bound is derived for the unconstrained Moreau-Yosida envelope; use MYULA"); }
   s->kind = 3;
   s->sk_stages = n_stages;
   for (int j = 0; j < n_stages; ++j) { s->sk_mu[j] = mu[j]; s->sk_nu[j] = nu[j]; s->sk_kappa[j] = kappa[j]; }
@@ -869,6 +880,7 @@ int lmc_ulpda_create(const lmc_ulpda_config* cfg, lmc_sampler** out) {
   lmc_problem pr = cfg->problem;
   if (pr.prior_kind == LMC_PRIOR_TV_ISO && pr.tv_niter < 1) pr.tv_niter = 1;   // unused by ULPDA; keeps the loader happy
   rc = load_problem(&pr, s->prob);
+  if (!rc) rc = check_no_box(s->prob, "ULPDA", "its prior enters through the dual ball of g o A, which has no box form; use MYULA");
   if (rc) { delete s; return rc; }
   if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }
   s->kind = 1;

@@ -39,6 +39,8 @@ int pipe_links(const StepArgs& a) {
   if (!single && (n < 19 || (n % 10 != 0 && n % 10 != 9))) return 0;
   // anisotropic prior (a.tv_aniso; lmc_step_pipe_aniso.hip): launches of 10 only -- 10, 20, ... 60 -- and no energy by-products (g_out is the isotropic value)
   if (a.tv_aniso && (n % 10 != 0 || a.f_out || a.g_out)) return 0;
+  // box constraint (a.box; lmc_step_pipe_box.hip): the same, isotropic prior only
+  if (a.box && (n % 10 != 0 || a.f_out || a.g_out || a.tv_aniso)) return 0;
   if (a.tv_in || a.tv_out || a.tv_state_only || a.tv_warm) return 0;
   if (!pipe_geometry_ok(a)) return 0;
   return single ? 1 : (n + 9) / 10;
@@ -50,7 +52,7 @@ bool pipe_supported(const StepArgs& a) { return pipe_links(a) == 1; }
 // a.tv_out ([C][2][H][W] each, never NULL), a.tv.niter in {1, 2, 3} dual iterations per MYULA iteration
 bool pipe_warm_supported(const StepArgs& a) {
   const int n = a.tv.niter;
-  if (!(n == 1 || n == 2 || n == 3) || a.tv_aniso) return false;
+  if (!(n == 1 || n == 2 || n == 3) || a.tv_aniso || a.box) return false;
   return pipe_geometry_ok(a);
 }
 
@@ -92,6 +94,10 @@ hipError_t launch_step_pipe(StepArgs a, hipStream_t st, float* state0, float* st
     if (two && teams != 1) return pipe_dispatch_aniso(a, KT, false, 2, st);     // (512 x 512 x 1024: 1.38 against 1.57 ms per launch, bit-identical)
     if (links == 1) return pipe_dispatch_aniso(a, KT, false, 1, st);
   }
+  if (a.box) {
+    if (two && teams != 1) return pipe_dispatch_box(a, KT, false, 2, st);
+    if (links == 1) return pipe_dispatch_box(a, KT, false, 1, st);
+  }
   if (two && teams != 1) return pipe_launch_teams<10, 5>(a, st);
   if (links == 1) {
     switch (a.tv.niter) {
@@ -112,7 +118,8 @@ hipError_t launch_step_pipe(StepArgs a, hipStream_t st, float* state0, float* st
     b.tv_out = j < links - 1 ? st_buf[j & 1] : nullptr;
     b.tv_state_only = j < links - 1;
     // the data term, the noise and the energies belong to the last link only; the earlier ones skip the blur pipeline
-    hipError_t e = a.tv_aniso ? pipe_dispatch_aniso(b, b.tv_state_only ? 0 : KT, true, 1, st) : pipe_dispatch_chain(b, kl, b.tv_state_only ? 0 : KT, st);
+    const int ktl = b.tv_state_only ? 0 : KT;
+    hipError_t e = a.tv_aniso ? pipe_dispatch_aniso(b, ktl, true, 1, st) : a.box ? pipe_dispatch_box(b, ktl, true, 1, st) : pipe_dispatch_chain(b, kl, ktl, st);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;

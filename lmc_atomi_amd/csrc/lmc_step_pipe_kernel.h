@@ -88,6 +88,8 @@ __device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_el
 __device__ __forceinline__ v2f pk_set(float a) { return v2f{a, a}; }
 // projection onto [-1, 1] per component (the dual ball of the anisotropic TV prior)
 __device__ __forceinline__ v2f pipe_clamp1(v2f a) { return v2f{__builtin_amdgcn_fmed3f(a.x, -1.f, 1.f), __builtin_amdgcn_fmed3f(a.y, -1.f, 1.f)}; }
+// projection of the primal iterate onto [lo, hi] (the box-constrained prior: one v_med3_f32 per pixel; infinite ends pass through)
+__device__ __forceinline__ v2f pipe_clamp_box(v2f a, float lo, float hi) { return v2f{__builtin_amdgcn_fmed3f(a.x, lo, hi), __builtin_amdgcn_fmed3f(a.y, lo, hi)}; }
 
 template <int NP>   // NP = PXL / 2 pairs
 __device__ __forceinline__ void pairs_load(v2f (&v)[NP], const float* row, int lane) {
@@ -178,11 +180,15 @@ __device__ __forceinline__ v2f obj_tv(const ObjMask<NP, !LASTLANE>* om, int i, v
 // SEAML / SEAMR (two-team layout): lane 0's left neighbour of s1 / lane 63's right neighbour of solb is the other team's, `ssl_edge` / `solr_edge`.
 // ANISO: the anisotropic prior sigma (|d_r x|_1 + |d_c x|_1): the dual is projected onto the l-infinity unit ball, one clamp per component
 // (v_med3_f32), instead of the pixel-norm ball; everything else in the stage is shared.
-template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAML = false, bool SEAMR = false, bool ANISO = false>
+// BOX: g = sigma TV + the indicator of [blo, bhi] (Beck and Teboulle's constrained FGP): the primal iterate the stage forms is projected onto the box
+// before it is differenced and before it is kept as solb.  Pixels outside the image (lanes past W, rows outside, vacant lanes of a wave shift) then
+// hold blo / bhi / 0 instead of 0; no difference that reaches an image pixel depends on them: vertical ones across the image's first / last row are cut
+// by cdown, the horizontal one across the last column by pipe_ncr, and the dual of column W - 1 (s = 0 there) shields the image from the columns to its right.
+template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAML = false, bool SEAMR = false, bool ANISO = false, bool BOX = false>
 __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[NP], const v2f (&s1)[NP], const DualRow<NP>& in0,
                                            v2f (&solb)[NP], float gam, float cdown, const PipeCr<NP>& cr, float beta,
                                            DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP, !LASTLANE>* om = nullptr,
-                                           float ssl_edge = 0.f, float solr_edge = 0.f) {
+                                           float ssl_edge = 0.f, float solr_edge = 0.f, float blo = 0.f, float bhi = 0.f) {
   v2f sol[NP];
   const float ssl0 = SEAML ? wave_from_left(s1[NP - 1].y, ssl_edge) : dpp_left0(s1[NP - 1].y);
   const v2f ngam = pk_set(-gam), ncd = pk_set(-cdown), vb = pk_set(beta);
@@ -191,6 +197,7 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
     const v2f ssl = left_pair(s1, ssl0, i);
     const v2f T = (r1[i] - in0.rr[i]) + (s1[i] - ssl);
     sol[i] = pk_fma(ngam, T, xa[i]);
+    if constexpr (BOX) sol[i] = pipe_clamp_box(sol[i], blo, bhi);
     if constexpr (OBJ) { const v2f Tm = obj_sq<NP, LASTLANE>(om, i, T); ob->sq = i == 0 ? Tm * Tm : pk_fma(Tm, Tm, ob->sq); }
   }
   const float solr_last = SEAMR ? wave_from_right(solb[0].x, solr_edge) : dpp_right0(solb[0].x);
@@ -227,18 +234,25 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
 
 // Stage 1 of a launch that starts from the zero dual state: (rr, ss, p, q)^0 = 0, so sol^1 = x and the differences with the previous
 // iterate vanish.  Bit-identical to pipe_stage() fed with zeros (x - 0 = x, fma(c, d, 0) = c*d), at ~60 % of its instructions.
-template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAMR = false, bool ANISO = false>
+// BOX: sol^0 = clip(x).
+template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAMR = false, bool ANISO = false, bool BOX = false>
 __device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb)[NP], float cdown, const PipeCr<NP>& cr, float beta,
                                                  DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP, !LASTLANE>* om = nullptr,
-                                                 float solr_edge = 0.f) {
+                                                 float solr_edge = 0.f, float blo = 0.f, float bhi = 0.f) {
   const float solr_last = SEAMR ? wave_from_right(solb[0].x, solr_edge) : dpp_right0(solb[0].x);
   const v2f ncd = pk_set(-cdown), vb = pk_set(beta);
   if constexpr (OBJ) ob->sq = pk_set(0.f);       // sol^0 = x
+  v2f xc[BOX ? NP : 1];
+  if constexpr (BOX) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) xc[i] = pipe_clamp_box(xa[i], blo, bhi);
+  }
+  auto x0 = [&](int i) __attribute__((always_inline)) -> v2f { if constexpr (BOX) return xc[i]; else return xa[i]; };
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const v2f solr = right_pair(solb, solr_last, i);
     const v2f ncr = pipe_ncr<NP, LASTLANE>(cr, i);
-    const v2f dxv = xa[i] - solb[i], dyv = solr - solb[i];
+    const v2f dxv = x0(i) - solb[i], dyv = solr - solb[i];
     if constexpr (OBJ) {
       const v2f nr = obj_tv<NP, LASTLANE>(om, i, dxv, dyv);
       ob->tv = i == 0 ? nr : ob->tv + nr;
@@ -260,7 +274,7 @@ __device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb
     out.q[i] = qn;
   }
 #pragma unroll
-  for (int i = 0; i < NP; ++i) solb[i] = xa[i];
+  for (int i = 0; i < NP; ++i) solb[i] = x0(i);
 }
 
 // Row load with zero fill.  The load itself is unconditional (masked-off lanes read the start of the row, always a valid address:
@@ -403,14 +417,17 @@ __device__ __forceinline__ int pipe_role(int hw_wave, int kc, int ncvx_kind) {
 // A T wave reads one 8-byte record per tick; the blur wave forms the residual row one tick before its adjoint (the row's seam columns
 // travel through SR).  Every pixel runs the arithmetic of the one-team kernel on the same operands: the results are bit-identical.
 // ANISO (myula_step_pipe_aniso_kernel, lmc_step_pipe_aniso.hip): the stages project the dual onto the box (pipe_stage); fixed count, cold start.
-template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS, bool ANISO = false>
+// BOX (myula_step_pipe_box_kernel, lmc_step_pipe_box.hip): the prior is sigma TV + the indicator of [A.box_lo, A.box_hi]: every stage and the combine
+// wave project the primal iterate they form onto the box (pipe_stage); fixed count, cold start.  Links with tv_state_only do not combine and clamp nothing there.
+template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS, bool ANISO = false, bool BOX = false>
 __device__ __forceinline__ void pipe_body(const StepArgs& A) {
   static_assert(!WARM || CHAIN, "the warm dual uses the state hand-over of the chained launches");
   static_assert(!ANISO || (!WARM && !RT), "anisotropic prior: the early exit's objective and the warm dual are not built");
-  // Anisotropic prior, the link of a chain that carries the blur (the last one) at 8 pixels per lane: the N wave, not L, hands the dual state of the
+  static_assert(!BOX || (!WARM && !RT), "box constraint: the early exit's objective and the warm dual are not built");
+  // Anisotropic prior or box constraint, the link of a chain that carries the blur (the last one) at 8 pixels per lane: the N wave, not L, hands the dual state of the
   // previous link to stage 1.  With the state rows' prefetch registers beside the blur windows the L wave needs more than 256 VGPRs (the isotropic
   // twins of these four kernels spill 20 to 90 of them); the N wave has them to spare and issues no other global access.
-  constexpr bool kStateInN = ANISO && CHAIN && KT > 0 && PXL == 8;
+  constexpr bool kStateInN = (ANISO || BOX) && CHAIN && KT > 0 && PXL == 8;
   static_assert(!RT || (!WARM && (K & 1) == 0), "per-chain exit: cold start, even K");
   // RT with AL = false: any width, column strips included.  The objective of an iterate reads it one column beyond the strip's interior, which needs
   // the dual one column further out than the update itself does (K + 1)
@@ -737,6 +754,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     const bool spread = RT && kc <= NT;
     const int g1 = spread ? wave : k1, g2 = k2;          // the STAGES the slots run (momentum coefficient, objective slot)
     const float gam = A.tv.gamma, cstep = A.tv.c;
+    const float blo = BOX ? A.box_lo : 0.f, bhi = BOX ? A.box_hi : 0.f;
     const float beta1 = A.tv.betas[g1 - 1], beta2 = SINGLE ? 0.f : A.tv.betas[g2 - 1];
     PipeCr<PXL / 2> crc;                                              // see PipeCr: AL kernels need W % PXL == 0 (host check), the others take any W
     crc.cstep = cstep;
@@ -832,7 +850,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         if (live2) {
           StageObj ob;
           om.md = cdown != 0.f ? 1.f : 0.f;
-          pipe_stage<NP, AL, RT, SL, SRt, ANISO>(xk[P], o1[P ^ 1].rr, o1[P ^ 1].ss, o1[P], sol2, gam, cdown, crc, beta2, out, &ob, &om, edge.y, edge.y);
+          pipe_stage<NP, AL, RT, SL, SRt, ANISO, BOX>(xk[P], o1[P ^ 1].rr, o1[P ^ 1].ss, o1[P], sol2, gam, cdown, crc, beta2, out, &ob, &om, edge.y, edge.y, blo, bhi);
           if constexpr (RT) { osq2 += (double)(ob.sq.x + ob.sq.y); otv2 += (double)(ob.tv.x + ob.tv.y); }
         } else {                 // pass-through: the state of row a2 - 1 as stage k1 left it
 #pragma unroll
@@ -865,8 +883,8 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           const float cdown = ((unsigned)(a1 - 1) >= (unsigned)(H - 1)) ? 0.f : cstep;
           StageObj ob;
           om.md = cdown != 0.f ? 1.f : 0.f;
-          if constexpr (FIRST) pipe_stage_first<NP, AL, RT, SRt, ANISO>(xk[P], sol1, cdown, crc, beta1, o1[P], &ob, &om, edge.x);
-          else pipe_stage<NP, AL, RT, SL, SRt, ANISO>(xk[P], inb[P].rr, inb[P].ss, inb[P ^ 1], sol1, gam, cdown, crc, beta1, o1[P], &ob, &om, edge.x, edge.x);
+          if constexpr (FIRST) pipe_stage_first<NP, AL, RT, SRt, ANISO, BOX>(xk[P], sol1, cdown, crc, beta1, o1[P], &ob, &om, edge.x, blo, bhi);
+          else pipe_stage<NP, AL, RT, SL, SRt, ANISO, BOX>(xk[P], inb[P].rr, inb[P].ss, inb[P ^ 1], sol1, gam, cdown, crc, beta1, o1[P], &ob, &om, edge.x, edge.x, blo, bhi);
           if constexpr (RT) { osq1 += (double)(ob.sq.x + ob.sq.y); otv1 += (double)(ob.tv.x + ob.tv.y); }
         } else {                 // pass-through: the state of row a1 - 1, read one tick ago
 #pragma unroll
@@ -1051,6 +1069,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         const v2f ssl = left_pair(css, ssl0, j);
         dvp[j] = (crr[P][j] - crr[P ^ 1][j]) + (css[j] - ssl);
         proxp[j] = pk_fma(ngam, dvp[j], xop[j]);
+        if constexpr (BOX) proxp[j] = pipe_clamp_box(proxp[j], A.box_lo, A.box_hi);
       }
       // the by-products below (early exit's objective, MC-TV term, TV energy) name pixels in natural order: their sums keep their order
       float xo[PXL], gv[PXL], prox[PXL];
@@ -1300,6 +1319,10 @@ int pipe_taps(StepArgs& a);
 // lmc_step_pipe_chain.hip: the CHAIN instantiations (dual state in / out through HBM): links of a chained launch (K = 9, 10) and the
 // warm-started prox (a.tv_warm: K = 1, 2, 3)
 hipError_t pipe_dispatch_chain(const StepArgs& a, int K, int KT, hipStream_t st);
+
+// lmc_step_pipe_box.hip: the box-constrained instantiations (myula_step_pipe_box_kernel / myula_step_pipe_box2_kernel: isotropic prior, K = 10, one launch or a link
+// of a chain; teams = 2 covers what pipe_teams_covered names)
+hipError_t pipe_dispatch_box(const StepArgs& a, int KT, bool chain, int teams, hipStream_t st);
 
 // lmc_step_pipe_aniso.hip: the anisotropic-prior instantiations (myula_step_pipe_aniso_kernel: K = 10, one launch or a link of a chain; the
 // two-team layout, teams = 2, covers what pipe_teams_covered names)

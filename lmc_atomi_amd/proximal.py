@@ -58,6 +58,40 @@ def fgp_betas(niter, momentum="unlocbox"):
     return np.asarray(out, dtype=np.float32)
 
 
+def check_bounds(bounds):
+    """``bounds=None`` or ``(lo, hi)`` with ``lo < hi``, neither NaN; infinite ends are allowed (``(0, inf)`` is positivity).  Returns None or the pair of
+    floats; anything else raises ``ValueError``."""
+    if bounds is None:
+        return None
+    try:
+        lo, hi = (float(v) for v in bounds)
+    except (TypeError, ValueError):
+        raise ValueError(f"bounds must be None or a pair (lo, hi) (got {bounds!r})") from None
+    if lo != lo or hi != hi or not lo < hi:
+        raise ValueError(f"bounds: need lo < hi, neither NaN (got ({lo}, {hi}))")
+    return lo, hi
+
+
+def _with_box(desc, bounds):
+    """The prior descriptor ``desc`` with the box constraint ``bounds`` (None: as it is)."""
+    if bounds is not None:
+        desc["box"] = bounds
+    return desc
+
+
+def _box_prox(op, x, tau):
+    """``clip(prox_{tau g}(x), lo, hi)`` of a separable prior with bounds -- the prox of g + the indicator of the box -- through ``lmc_fused_eval`` (one
+    elementwise launch forms it).  Arrays with two or more axes are batches of images on the last two; anything else is one row."""
+    shape = tuple(np.shape(x)) if not isinstance(x, torch.Tensor) else tuple(x.shape)
+    n = int(np.prod(shape)) if shape else 1
+    dims = (int(shape[-2]), int(shape[-1])) if len(shape) >= 2 else (1, n)
+    key = (dims, x.device if isinstance(x, torch.Tensor) and x.is_cuda else None)
+    cache = op.__dict__.setdefault("_box_problems", {})
+    if key not in cache:
+        cache[key] = _Problem(dims, prior=op.prior_descriptor(), dev=key[1])
+    return cache[key].eval(x, 0.0, 0.0, 1.0, float(tau))
+
+
 class ProxOperator:
     """Base class; subclassing hook mirrors ``super().__init__(Op, hasgrad)`` (algs.py:132)."""
 
@@ -144,6 +178,9 @@ class _Problem:
             sc, cs, ps = opt["prox_scale"]
             self._keep.append(sc)
             p.prox_scale, p.prox_scale_chain_stride, p.prox_scale_pixel_stride = _dev.ptr(sc), int(cs), int(ps)
+        if prior.get("box") is not None:          # x in [lo, hi]: the prox is that of g + the indicator of the box
+            p.box_enable = 1
+            p.box_lo, p.box_hi = check_bounds(prior["box"])
         self.c = p
 
     def eval(self, x, a, t, b, pt):
@@ -179,8 +216,11 @@ class L2(ProxOperator):
     provided by :mod:`lmc_atomi_amd.algs` for ULPDA; for ``Op is None`` it is closed form.
     """
 
-    def __init__(self, Op=None, b=None, sigma=1.0, niter=10, warm=True, dims=None):
+    def __init__(self, Op=None, b=None, sigma=1.0, niter=10, warm=True, dims=None, bounds=None):
         super().__init__(Op, True)
+        self.bounds = check_bounds(bounds)        # as the prior only: sigma/2 ||x||^2 + the indicator of [lo, hi]
+        if self.bounds is not None and (Op is not None or b is not None):
+            raise NotImplementedError("bounds belong to the prior: only L2(sigma=...) without Op / b takes them")
         self.b = b
         self.sigma = float(sigma)
         self.niter = niter
@@ -207,7 +247,7 @@ class L2(ProxOperator):
         """As the prior g = sigma/2 ||x||^2 (closed-form prox)."""
         if self.Op is not None or self.b is not None:
             raise NotImplementedError("only L2(sigma=...) without Op/b can act as the prior")
-        return {"prior_kind": _capi.PRIOR_L2, "prior_sigma": self.sigma}
+        return _with_box({"prior_kind": _capi.PRIOR_L2, "prior_sigma": self.sigma}, self.bounds)
 
     def _problem(self):
         if self._prob is None:
@@ -231,6 +271,8 @@ class L2(ProxOperator):
     def prox(self, x, tau):
         """``(I + tau*sigma*Op^T Op)^{-1}(x + tau*sigma*Op^T b)`` (pyproximal.L2.prox; in-repo twin algs.py:224-256).
         With a blur operator: ``niter`` warm-started CG iterations on the GPU (lmc_l2_prox)."""
+        if self.bounds is not None:
+            return _box_prox(self, x, tau)
         if self.Op is None and self.b is None:
             return x / (1.0 + tau * self.sigma)
         prob = self._problem()
@@ -256,13 +298,14 @@ class L2(ProxOperator):
 class L1(ProxOperator):
     """``sigma ||x||_1`` -- drop-in for ``pyproximal.L1(sigma=tau)`` (prox_lmc_deconv.py:119)."""
 
-    def __init__(self, sigma=1.0, dims=None):
+    def __init__(self, sigma=1.0, dims=None, bounds=None):
         super().__init__(None, False)
         self.sigma = float(sigma)
         self.dims = dims
+        self.bounds = check_bounds(bounds)        # sigma ||x||_1 + the indicator of [lo, hi]: prox = clip(soft threshold)
 
     def prior_descriptor(self):
-        return {"prior_kind": _capi.PRIOR_L1, "prior_sigma": self.sigma}
+        return _with_box({"prior_kind": _capi.PRIOR_L1, "prior_sigma": self.sigma}, self.bounds)
 
     def __call__(self, x):
         xt = _dev.to_dev(x).reshape(1, -1)
@@ -271,6 +314,8 @@ class L1(ProxOperator):
         return float(g[0])
 
     def prox(self, x, tau):
+        if self.bounds is not None:
+            return _box_prox(self, x, tau)
         xt = _dev.to_dev(x)
         out = torch.empty_like(xt)
         par = np.asarray([self.sigma * float(tau)], dtype=np.float32)
@@ -348,12 +393,23 @@ class TV(ProxOperator):
       updates depends on the loop bound of the un-pinned upstream version; ``False`` (default) = ``niter`` updates,
       ``True`` = ``niter - 1`` (one pipeline stage fewer).
     * ``warm`` (build extension, MYULA samplers only): carry the projected dual from one MYULA iteration to the next, ``niter``
-      in {1, 2, 3} updates per MYULA iteration ("K in {1,3} warm-dual")."""
+      in {1, 2, 3} updates per MYULA iteration ("K in {1,3} warm-dual").
+    * ``bounds=(lo, hi)`` (build extension; either form of the prior): ``g(x) = sigma TV(x) +`` the indicator of ``lo <= x <= hi``.  ``prox`` is Beck and
+      Teboulle's constrained fast gradient projection -- the primal iterate is projected onto the box inside every dual iteration, which converges to the
+      prox of the sum (clipping the unconstrained prox afterwards does not).  Infinite ends are allowed.  ``__call__`` keeps returning ``sigma TV(x)``.
+      Fixed count only: ``rtol > 0`` and ``warm=True`` raise ``NotImplementedError``."""
 
     def __init__(self, dims, sigma=1.0, niter=10, rtol=0.0, step=0.125, momentum="unlocbox", lagged_output=False, warm=False, exit_path="auto",
-                 isotropic=True):
+                 isotropic=True, bounds=None):
         super().__init__(None, False)
         self.isotropic = bool(isotropic)
+        self.bounds = check_bounds(bounds)
+        if self.bounds is not None and float(rtol) > 0.0:
+            raise NotImplementedError("TV(bounds=...) has no early exit: rtol must be 0 (every image runs niter dual iterations)")
+        if self.bounds is not None and warm:
+            raise NotImplementedError("TV(bounds=...) has no warm-started dual: warm must be False")
+        if self.bounds is not None and int(niter) < 1:
+            raise ValueError("TV(bounds=...): the projection runs inside the dual iterations, niter must be >= 1")
         if not self.isotropic and float(rtol) > 0.0:
             raise NotImplementedError("TV(isotropic=False) has no early exit: rtol must be 0 (every image runs niter dual iterations)")
         if not self.isotropic and warm:
@@ -370,9 +426,9 @@ class TV(ProxOperator):
         self._prob = None
 
     def prior_descriptor(self):
-        return {"prior_kind": _capi.PRIOR_TV_ISO if self.isotropic else _capi.PRIOR_TV_ANISO, "prior_sigma": self.sigma, "tv_niter": self.niter,
-                "tv_step": self.step, "tv_betas": fgp_betas(self.niter, self.momentum),
-                "tv_lagged_output": self.lagged_output, "tv_warm": self.warm, "tv_rtol": self.rtol, "tv_exit_path": self.exit_path}
+        return _with_box({"prior_kind": _capi.PRIOR_TV_ISO if self.isotropic else _capi.PRIOR_TV_ANISO, "prior_sigma": self.sigma, "tv_niter": self.niter,
+                          "tv_step": self.step, "tv_betas": fgp_betas(self.niter, self.momentum),
+                          "tv_lagged_output": self.lagged_output, "tv_warm": self.warm, "tv_rtol": self.rtol, "tv_exit_path": self.exit_path}, self.bounds)
 
     def _problem(self):
         if self._prob is None:
@@ -404,8 +460,9 @@ class ElementwiseProx(ProxOperator):
              "chi": (_capi.EPROX_CHI, 1), "uniform": (_capi.EPROX_UNIFORM, 1), "triangular": (_capi.EPROX_TRIANGULAR, 2),
              "laplace_conj": (_capi.EPROX_LAPLACE_CONJ, 1)}
 
-    def __init__(self, kind, *params, scaled=()):
+    def __init__(self, kind, *params, scaled=(), bounds=None):
         super().__init__(None, False)
+        self.bounds = check_bounds(bounds)        # g + the indicator of [lo, hi]: prox = clip(closed form)
         if kind not in self.KINDS:
             raise ValueError(f"unknown closed-form prox {kind!r}")
         self.kind = kind
@@ -423,13 +480,16 @@ class ElementwiseProx(ProxOperator):
 
     def prior_descriptor(self):
         p = self.params + (0.0,) * (2 - len(self.params))
-        return {"prior_kind": _capi.PRIOR_EPROX, "eprox_kind": self.code, "eprox_p0": p[0], "eprox_p1": p[1],
-                "eprox_scale_mask": sum(1 << i for i in self.scaled)}
+        return _with_box({"prior_kind": _capi.PRIOR_EPROX, "eprox_kind": self.code, "eprox_p0": p[0], "eprox_p1": p[1],
+                          "eprox_scale_mask": sum(1 << i for i in self.scaled)}, self.bounds)
 
     def __call__(self, x):
         return 0.0
 
     def prox(self, x, tau):
+        if self.bounds is not None:
+            _capi.check_eprox_params(self.code, self._scaled_params(tau))
+            return _box_prox(self, x, tau)
         xt = _dev.to_dev(x)
         out = torch.empty_like(xt)
         _capi.check_eprox_params(self.code, self._scaled_params(tau))
@@ -438,41 +498,62 @@ class ElementwiseProx(ProxOperator):
         return _dev.like_input(out, x)
 
 
-def Laplace(lam):
+def Laplace(lam, bounds=None):
     """``lam * ||x||_1`` through ``prox_laplace(x, tau * lam)`` (prox.py:18; prox_lmc.py:106)."""
-    return ElementwiseProx("laplace", lam, scaled=(0,))
+    return ElementwiseProx("laplace", lam, scaled=(0,), bounds=bounds)
 
 
-def UncenteredLaplace(lam, mu):
-    return ElementwiseProx("uncentered_laplace", lam, mu, scaled=(0,))       # prox.py:22
+def UncenteredLaplace(lam, mu, bounds=None):
+    return ElementwiseProx("uncentered_laplace", lam, mu, scaled=(0,), bounds=bounds)       # prox.py:22
 
 
-def Gaussian(lam):
-    return ElementwiseProx("gaussian", lam, scaled=(0,))                     # prox.py:26: x / (2 tau lam + 1)
+def Gaussian(lam, bounds=None):
+    return ElementwiseProx("gaussian", lam, scaled=(0,), bounds=bounds)                     # prox.py:26: x / (2 tau lam + 1)
 
 
-def GenGaussian(p, lam):
+def GenGaussian(p, lam, bounds=None):
     """``lam * |x|^p``, p in {4/3, 3/2, 3, 4} (prox.py:30-41)."""
     names = {4 / 3: "gen_gaussian_4_3", 3 / 2: "gen_gaussian_3_2", 3: "gen_gaussian_3", 4: "gen_gaussian_4"}
     if p not in names:
         raise ValueError("p must be one of 4/3, 3/2, 3, 4")
-    return ElementwiseProx(names[p], lam, scaled=(0,))
+    return ElementwiseProx(names[p], lam, scaled=(0,), bounds=bounds)
 
 
-def Huber(gamma, tau):
-    return ElementwiseProx("huber", gamma, tau, scaled=(1,))                 # prox.py:44: tau is the prox weight
+def Huber(gamma, tau, bounds=None):
+    return ElementwiseProx("huber", gamma, tau, scaled=(1,), bounds=bounds)                 # prox.py:44: tau is the prox weight
 
 
-def SmoothedLaplace(lam):
-    return ElementwiseProx("smoothed_laplace", lam, scaled=(0,))             # prox.py:52
+def SmoothedLaplace(lam, bounds=None):
+    return ElementwiseProx("smoothed_laplace", lam, scaled=(0,), bounds=bounds)             # prox.py:52
+
+
+class Box(ProxOperator):
+    """The indicator of ``lo <= x <= hi`` alone (build extension): ``prox`` is the projection onto the box, whatever ``tau``.  As ``proxg`` of the MYULA
+    samplers it is the constrained sampler of Durmus, Moulines and Pereyra with a flat prior: the Moreau-Yosida envelope of the indicator pulls the
+    iterates towards the box, it does not keep them inside.  ``__call__`` returns 0 (the value inside the box)."""
+
+    def __init__(self, lo, hi):
+        super().__init__(None, False)
+        self.bounds = check_bounds((lo, hi))
+
+    def prior_descriptor(self):
+        return _with_box({"prior_kind": _capi.PRIOR_NONE}, self.bounds)
+
+    def __call__(self, x):
+        return 0.0
+
+    def prox(self, x, tau):
+        return _box_prox(self, x, tau)
 
 
 class WaveletL1(ProxOperator):
     """``sigma * || detail coefficients of the 3-level orthonormal Haar transform of x ||_1`` -- the prior of BASELINE config 5
     (build-specified; the reference has no wavelet code).  ``prox`` = W^T soft(W x, tau*sigma) on independent 8 x 8 blocks."""
 
-    def __init__(self, dims, sigma=1.0, levels=3):
+    def __init__(self, dims, sigma=1.0, levels=3, bounds=None):
         super().__init__(None, False)
+        if bounds is not None:
+            raise NotImplementedError("WaveletL1 takes no bounds: the prior is not separable in the pixels, so clipping its prox is not the prox of the sum")
         if levels != 3:
             raise NotImplementedError("levels=3 (8 x 8 blocks) only")
         self.dims = (int(dims[0]), int(dims[1]))
