@@ -47,7 +47,31 @@ typedef enum lmc_data_kind {
   LMC_DATA_NONE = 0,     /* f = 0 */
   LMC_DATA_IDENTITY = 1, /* Op = I */
   LMC_DATA_BLUR = 2,     /* Op = zero-padded "same" convolution, pylops Convolve2D (prox_lmc_deconv.py:55-69) */
-  LMC_DATA_MASK = 3      /* Op = diag(mask), inpainting (BASELINE config 5) */
+  LMC_DATA_MASK = 3,     /* Op = diag(mask), inpainting (BASELINE config 5) */
+  /* Poisson likelihood, y_p ~ Poisson((Op x)_p + beta_p) (additive values; LMC_ATOMI_ABI_VERSION stays 4, the layout of lmc_problem is unchanged).
+   * Build-specified (the reference has no such term); this text is its definition.  Operator fields as for kinds 1 to 3; y_dev points to
+   * [2][H][W] floats: plane 0 the counts y >= 0 (they need not be integers), plane 1 the known background beta > 0 (a scalar background is a
+   * constant plane).  Preconditions, not checked on the device: y >= 0, beta > 0, both finite.  With u = (Op x)_p:
+   *   u >= 0:  phi(u) = (u + beta) - y + y log(y / (u + beta))   (0 log 0 = 0)        phi'(u) = 1 - y / (u + beta)
+   *   u <  0:  phi(u) = phi(0) + phi'(0) u + y u^2 / (2 beta^2)                       phi'(u) = 1 - y / beta + y u / beta^2
+   *   f(x) = sigma_f sum_p phi_p((Op x)_p),   grad f(x) = sigma_f Op^T phi'(Op x)
+   * the generalised Kullback-Leibler divergence (the Poisson negative log-likelihood up to a constant) for u >= 0 and its second-order Taylor
+   * extension at 0 below: f is convex and C^1 on the whole space (MYULA iterates live near the positive orthant, not in it) with
+   * L_f = sigma_f max_p(y_p / beta_p^2) ||Op||^2.  Both branches are one expression: t = 1 / (max(u, 0) + beta), phi'(u) = 1 - y t (1 - t min(u, 0)).
+   * sigma_f = 1 is the true likelihood.  Mask: u = m_p x_p, gradient sigma_f m_p phi'(m_p x_p).  A pixel with y_p = 0 has a linear phi, unbounded
+   * below as u -> -inf: use the model with box_enable and box_lo = 0.
+   * Honoured by lmc_myula_create and lmc_skrock_create with all of lmc_sampler_* (lmc_sampler_sapg included), lmc_fused_eval, lmc_energies and
+   * lmc_sampler_energies (f as above: phi in float64 from the fp32 u, summed in float64; every width).  Priors: NONE, L2, L1, EPROX, TV_ISO and
+   * TV_ANISO with any tv_niter and tv_lagged_output, box_enable with each as it is honoured for the Gaussian term (so: not by SK-ROCK and SAPG).
+   * Kernels: the full-width pipeline (myula_step_pipe_pois_kernel, myula_step_pipe_pois_box_kernel; one team) for the isotropic TV prior with exactly 10
+   * dual iterations after tv_lagged_output, W > 128, a separable blur of 5 or 7 taps or a pointwise data term; the LDS-tiled kernel
+   * (myula_step_tile_pois_kernel, myula_step_tile_pois_box_kernel) for everything else -- every prior, width and blur.  One iteration per launch
+   * (iterations_per_launch is ignored).  LMC_E_UNSUPPORTED, with the reason in lmc_last_error: lmc_mymala_create, lmc_ulpda_create, lmc_l2_prox (no
+   * closed implicit step), ncvx_kind != NONE, tv_rtol > 0, tv_warm, LMC_PRIOR_HAAR_L1, a forced step_variant other than 0, 1 and 7; 7 on a problem the
+   * pipeline does not cover (from lmc_myula_create / lmc_skrock_create, and from lmc_fused_eval). */
+  LMC_DATA_POISSON_IDENTITY = 4,
+  LMC_DATA_POISSON_BLUR = 5,
+  LMC_DATA_POISSON_MASK = 6
 } lmc_data_kind;
 
 /* prior g whose prox enters the MYULA update (algs.py:569) */

@@ -38,6 +38,26 @@ def _refuse_box(prior, who, why):
         raise NotImplementedError(f"{who} does not take a prior with bounds: {why}")
 
 
+def _refuse_poisson(data, prior, opts, who=None):
+    """``NotImplementedError`` for what the library refuses with a Poisson data term (``LMC_E_UNSUPPORTED`` in include/lmc_atomi.h), before a handle
+    exists.  ``who``: (name, why) of a sampler that has no Poisson form at all."""
+    if data.get("data_kind") not in _capi.POISSON_KINDS:
+        return
+    if who is not None:
+        raise NotImplementedError(f"{who[0]} does not take the Poisson data term: {who[1]}")
+    if prior.get("prior_kind") == _capi.PRIOR_HAAR_L1:
+        raise NotImplementedError("the Poisson data term with the Haar-l1 prior (WaveletL1) is not built")
+    if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
+        raise NotImplementedError("the Poisson data term runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
+    if prior.get("tv_warm") or opts.get("tv_warm"):
+        raise NotImplementedError("the Poisson data term has no warm-started TV dual: warm / tv_warm must be off")
+    v = opts.get("step_variant", 0) or 0
+    v = _capi.VARIANTS.index(v) if isinstance(v, str) else int(v)
+    if v not in (0, 1, 7):
+        raise NotImplementedError(f"step-kernel variant {_capi.VARIANTS[v]!r} has no form of the Poisson data term: 'auto', 'tile' or 'pipe' (where it covers "
+                                  "the problem)")
+
+
 def _data_descriptor(proxf):
     if proxf is None:
         return {"data_kind": _capi.DATA_NONE}
@@ -478,6 +498,7 @@ class MYULASampler:
         if np.asarray(epsg).size > 1:      # array-valued epsg (algs.py:509,539-542): the prox parameter epsg * gamma is an array that the prox broadcasts
             opts["prox_scale"] = self._epsg_array(epsg)
             epsg = 1.0
+        _refuse_poisson(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._poisson_refusal)
         self._problem = _Problem(self.dims, _data_descriptor(proxf), _prior_descriptor(proxg), self.device, options=opts)
         self.prior_weight = float(self._problem.c.prior_sigma)      # follows set_prior_weight / estimate_prior_weight
         cfg = _capi.lmc_myula_config()
@@ -495,13 +516,17 @@ class MYULASampler:
         self.moments_on = bool(moments)
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _capi.check(self._create(cfg))
+            rc = self._create(cfg)
+        if rc == -2 and self._problem.c.data_kind in _capi.POISSON_KINDS:      # (no handle exists: e.g. variant='pipe' on a problem the pipeline does not cover)
+            raise NotImplementedError(_dev.lib().lmc_last_error().decode())
+        _capi.check(rc)
         self._set_moment_scales(scales)
         self._set_histogram(hist)
         self._set_chain_groups(groups)
 
     _create_fn = "lmc_myula_create"
     _box_refusal = None          # (who, why) of a subclass that has no box-constrained form: raised before a handle exists
+    _poisson_refusal = None      # the same for the Poisson data term
 
     def _create(self, cfg):
         return getattr(_dev.lib(), self._create_fn)(C.byref(cfg), C.byref(self._h))
@@ -787,6 +812,7 @@ class ULPDASampler(MYULASampler):
             raise NotImplementedError("ULPDA on the GPU supports A = Gradient (the reference's operator, prox_lmc_deconv.py:98)")
         if getattr(proxg, "bounds", None) is not None:
             raise NotImplementedError("ULPDA does not take a prior with bounds: its prior enters through the dual ball of g o A, which has no box form; use MYULA")
+        _refuse_poisson(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA"))
         if isinstance(proxg, L21):
             prior = {"prior_kind": _capi.PRIOR_TV_ISO, "prior_sigma": proxg.sigma, "tv_niter": 1, "tv_betas": [0.0]}
         elif isinstance(proxg, L1):
@@ -1101,6 +1127,7 @@ class MYMALASampler(MYULASampler):
     _create_fn = "lmc_mymala_create"
 
     _box_refusal = ("MYMALA", "its target would be +infinity outside the box, where MYULA's proposals land; use MYULA")
+    _poisson_refusal = ("MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK")
 
     def acceptance(self):
         """(accepted proposals per chain [C] int64 tensor, log acceptance ratio of the last iteration [C] float64 tensor)."""

@@ -52,6 +52,9 @@ struct StepArgs {
                              // [box_lo, box_hi] (the fields of those names further down).  This slot and tv_aniso hold the argument layout of every step kernel (an 8-byte slot: dropping it
                              // moves the fields behind it, and with them the register allocation and spills of some 180 kernels)
   uint32_t chain_offset;     // global id of chain 0 (counter word 2 = chain_offset + c)
+  uint32_t pois;             // host side only, like tv_aniso and box (the Poisson kernels are instantiations of their own): the data term is the Poisson
+                             // likelihood of lmc_atomi.h -- data_kind stays the operator's kind (identity, blur, mask), y is [2][H][W]: the counts, then the
+                             // background beta at y + H W.  It sits in the 4-byte hole the alignment of x_in leaves: no field moves (the asserts below)
   const float* x_in;
   float* x_out;
   // resumable TV prox (tile kernel): dual state [C][4][H][W] = (rr, ss, p, q) carried between launches so that
@@ -105,6 +108,8 @@ struct StepArgs {
 static_assert(sizeof(StepArgs) == 952, "the argument of every step kernel keeps its size");
 static_assert(offsetof(StepArgs, box_lo) == offsetof(StepArgs, g_scale) + 4 && offsetof(StepArgs, prox_ext) == offsetof(StepArgs, g_scale) + 8,
               "box_lo fills the hole behind g_scale");
+static_assert(offsetof(StepArgs, pois) == offsetof(StepArgs, chain_offset) + 4 && offsetof(StepArgs, x_in) == offsetof(StepArgs, chain_offset) + 8,
+              "pois fills the hole behind chain_offset");
 static_assert(offsetof(StepArgs, box_hi) == offsetof(StepArgs, fused_iters) + 4 && offsetof(StepArgs, x_mid) == offsetof(StepArgs, fused_iters) + 8,
               "box_hi fills the hole behind fused_iters");
 

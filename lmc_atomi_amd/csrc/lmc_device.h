@@ -116,6 +116,24 @@ __device__ __forceinline__ double mc_tv_envelope(float dx, float dy, float gamma
   return hub(sqrtf(fmaf(dx, dx, dy * dy)));
 }
 
+// ---- Poisson data term (LMC_DATA_POISSON_*; definition: lmc_atomi.h) --------------------------------------------------
+// rho(u) = phi'(u) at u = (Op x)_p with counts y >= 0 and background beta > 0: 1 - y / (u + beta) for u >= 0, its first-order Taylor
+// extension 1 - y / beta + y u / beta^2 below 0 -- one branch-free expression.  IEEE division (not v_rcp_f32: 1 ulp of t is 1e-7 of a term
+// that cancels against 1 near y = u + beta).
+__device__ __forceinline__ float pois_rho(float u, float y, float beta) {
+  const float t = 1.f / (fmaxf(u, 0.f) + beta);
+  return fmaf(-y * t, fmaf(-t, fminf(u, 0.f), 1.f), 1.f);
+}
+// phi(u) in float64 from the fp32 operands (the energies): the generalised Kullback-Leibler divergence for u >= 0 (0 log 0 = 0), its
+// second-order Taylor extension at 0 below
+__device__ __forceinline__ double pois_phi(float u, float y, float beta) {
+  const double ud = (double)u, yd = (double)y, bd = (double)beta;
+  const double d = fmax(ud, 0.0) + bd;
+  const double kl = d - yd + (yd > 0.0 ? yd * log(yd / d) : 0.0);      // phi(max(u, 0))
+  if (ud >= 0.0) return kl;
+  return kl + (1.0 - yd / bd) * ud + yd * ud * ud / (2.0 * bd * bd);
+}
+
 // ---- shared by the streaming step kernels ---------------------------------------------------------
 constexpr int kPad = 8;  // zero columns on both sides of LDS rows (>= kMaxBlur - 1)
 #ifdef LMC_BOUNDS_CHECK   // debug build: out-of-range global accesses are recorded and skipped, never issued

@@ -40,10 +40,16 @@ int load_problem(const lmc_problem* p, Problem& q) {
   if (p->H < 1 || p->W < 1 || (int64_t)p->H * p->W > (int64_t)1 << 30) return fail(LMC_E_INVALID, "bad image size %dx%d", p->H, p->W);
   q.H = p->H; q.W = p->W;
   q.data_kind = p->data_kind;
+  // the Poisson likelihood: inside the library the operator's kind plus a flag (every test on LMC_DATA_BLUR / IDENTITY / MASK serves both; the entry
+  // points without a Poisson form refuse the flag: check_no_poisson, check_poisson)
+  if (p->data_kind >= LMC_DATA_POISSON_IDENTITY && p->data_kind <= LMC_DATA_POISSON_MASK) {
+    q.data_kind = p->data_kind - LMC_DATA_POISSON_IDENTITY + LMC_DATA_IDENTITY;
+    q.pois = 1;
+  }
   q.sigma_f = p->sigma_f;
   q.y = p->y_dev;
   q.mask = p->mask_dev;
-  switch (p->data_kind) {
+  switch (q.data_kind) {
     case LMC_DATA_NONE: break;
     case LMC_DATA_IDENTITY:
       if (!p->y_dev) return fail(LMC_E_INVALID, "data term needs y_dev");
@@ -159,6 +165,27 @@ int check_no_box(const Problem& q, const char* who, const char* why) {
   return fail(LMC_E_UNSUPPORTED, "%s does not take a box constraint (lmc_problem.box_enable): %s", who, why);
 }
 
+// The entry points that have no form of the Poisson likelihood refuse a problem that carries one.
+int check_no_poisson(const Problem& q, const char* who, const char* why) {
+  if (!q.pois) return LMC_OK;
+  return fail(LMC_E_UNSUPPORTED, "%s does not take the Poisson data term (LMC_DATA_POISSON_*): %s", who, why);
+}
+
+// What the entry points that do take it (MYULA, SK-ROCK, lmc_fused_eval) refuse with it: everything that is not the fused step of the tiled kernel or of
+// the full-width pipeline's Poisson instantiations.
+int check_poisson(const Problem& q) {
+  if (!q.pois) return LMC_OK;
+  if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the Poisson data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
+  const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
+  if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "the Poisson data term with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0");
+  if (q.tv_warm_asked) return fail(LMC_E_UNSUPPORTED, "the Poisson data term with tv_warm: the warm-started dual has no Poisson form");
+  if (q.prior_kind == LMC_PRIOR_HAAR_L1) return fail(LMC_E_UNSUPPORTED, "the Poisson data term with LMC_PRIOR_HAAR_L1 is not built");
+  const int v = variant_of(q);
+  if (v != 0 && v != 1 && v != 7)
+    return fail(LMC_E_UNSUPPORTED, "step_variant %d has no form of the Poisson data term: 0 (auto), 1 (tile) or 7 (pipe, where it covers the problem)", v);
+  return LMC_OK;
+}
+
 // What the entry points that form prox_g (MYULA, MYMALA, lmc_fused_eval) ask of the anisotropic TV prior beyond load_problem: an iteration
 // count, and none of the options that are built for the isotropic prior only.
 int check_prox_prior(const Problem& q, float b) {
@@ -175,6 +202,7 @@ int make_step_args(const Problem& q, float a, float t, float b, float pt, float 
   std::memset(&A, 0, sizeof A);
   A.H = q.H; A.W = q.W;
   A.data_kind = (t == 0.f) ? LMC_DATA_NONE : q.data_kind;   // skip the stencil work if its weight is zero
+  A.pois = (q.pois && A.data_kind != LMC_DATA_NONE) ? 1 : 0;
   A.sigma_f = q.sigma_f;
   A.y = q.y; A.mask = q.mask;
   A.blur = q.taps;
@@ -229,10 +257,44 @@ float tol_of(const Problem& q) { return q.implicit_tol > 0.f ? q.implicit_tol : 
 // it covers the configuration (W <= 512, separable blur <= 7x7, supported K), else the LDS-tiled kernel.
 static hipError_t launch_step_nobox(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf);
 
+// The Poisson data term.  The full-width pipeline's Poisson instantiations where they cover the problem (isotropic TV, exactly 10 dual iterations, W > 128,
+// separable blur or pointwise data term; auto and 7), the tiled kernel's everywhere else and for every other prior (auto and 1): TV (either form, box or
+// not) and none / l2 / l1 run inside that kernel; a closed-form prior of prox.py and the box of a separable prior are formed by the elementwise launch
+// before it and consumed as a ready-made prox.
+bool pois_pipe_covers(const lmc::StepArgs& A) { return A.pois && A.prior_kind == LMC_PRIOR_TV_ISO && lmc::pipe_links(A) == 1; }
+
+static hipError_t launch_step_pois(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
+  if (variant != 0 && variant != 1 && variant != 7) return hipErrorInvalidConfiguration;
+  if (variant != 1 && pois_pipe_covers(A_in)) {
+    if (name) *name = A_in.box ? "myula_step_pipe_pois_box_kernel" : "myula_step_pipe_pois_kernel";
+    return lmc::launch_step_pipe(A_in, st, nullptr, nullptr, 1);
+  }
+  if (variant == 7) return hipErrorInvalidConfiguration;
+  if (A_in.ncvx_kind != LMC_NCVX_NONE || A_in.extra || A_in.prior_kind == LMC_PRIOR_HAAR_L1) return hipErrorInvalidConfiguration;
+  lmc::StepArgs A = A_in;
+  const bool tv = A.prior_kind == LMC_PRIOR_TV_ISO;
+  if (!tv && !A.prox_ext && (A.box || A.prior_kind == LMC_PRIOR_EPROX)) {
+    if (!pxbuf) return hipErrorInvalidConfiguration;
+    hipError_t e = A.box ? lmc::launch_box_prox(A.prior_kind, A.eprox_kind, A.x_in, pxbuf, A.C, (int64_t)A.H * A.W, nullptr, 0, 0, 0.f, 0.f, A.prior_p0, A.prior_p1, 0,
+                                                A.box_lo, A.box_hi, st)
+                         : lmc::launch_eprox(A.eprox_kind, A.x_in, pxbuf, (int64_t)A.C * A.H * A.W, A.prior_p0, A.prior_p1, st);
+    if (e != hipSuccess) return e;
+    A.prox_ext = pxbuf;
+  }
+  if (!tv) { if (A.prox_ext) A.prior_kind = LMC_PRIOR_NONE; A.box = 0; }
+  if (name) *name = A.box ? "myula_step_tile_pois_box_kernel" : "myula_step_tile_pois_kernel";
+  if (lmc::tile_needs_chunks(A)) {
+    if (!state0 || !state1) return hipErrorInvalidConfiguration;
+    return lmc::launch_step_tile_chunked(A, state0, state1, st);
+  }
+  return lmc::launch_step_tile(A, st);
+}
+
 // The box-constrained forms.  Separable priors: one elementwise launch forms clip(prox) into pxbuf, then the step of the variant asked for consumes it.
 // TV priors: the pipe kernel's box instantiations (isotropic; auto, 7, 8) or the tile kernel's (either form; auto, 1); a forced variant without a box
 // form is not covered.
 hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
+  if (A_in.pois) return launch_step_pois(A_in, variant, st, name, state0, state1, pxbuf);
   if (!A_in.box) return launch_step_nobox(A_in, variant, st, name, state0, state1, pxbuf);
   lmc::StepArgs A = A_in;
   if (A.prior_kind != LMC_PRIOR_TV_ISO) {

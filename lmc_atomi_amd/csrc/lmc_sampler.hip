@@ -107,6 +107,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   rc = load_problem(&cfg->problem, s->prob);
   if (rc) { delete s; return rc; }
   rc = check_prox_prior(s->prob, cfg->tau / cfg->gamma);
+  if (!rc) rc = check_poisson(s->prob);
   if (rc) { delete s; return rc; }
   if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }
   s->C = cfg->n_chains;
@@ -117,6 +118,11 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   s->moments = cfg->moments; s->burn_in = cfg->burn_in; s->thin = cfg->thin < 1 ? 1 : cfg->thin;
   rc = rebuild_base(s);
   if (rc) { delete s; return rc; }
+  if (s->prob.pois && variant_of(s->prob) == 7 && !pois_pipe_covers(s->base)) {
+    delete s;
+    return fail(LMC_E_UNSUPPORTED, "step_variant 7 (pipe) does not cover this Poisson problem: isotropic TV with 10 dual iterations (after tv_lagged_output), "
+                "W > 128, separable blur of 5 or 7 taps or a pointwise data term; use 0 (auto) or 1 (tile)");
+  }
   const size_t nbytes = sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W;
   hipError_t e = hipMalloc(&s->x[0], nbytes);
   if (e == hipSuccess) e = hipMalloc(&s->x[1], nbytes);
@@ -148,6 +154,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     s->pol_overlap = q.moments_overlap ? q.moments_overlap : (getenv("LMC_MOMENTS_OVERLAP") ? (env_int("LMC_MOMENTS_OVERLAP", 0) ? 1 : -1) : 0);
     s->pol_bg_wgs = q.moments_bg_wgs > 0 ? q.moments_bg_wgs : env_int("LMC_MOMENTS_BG_WGS", -1);
     if (q.prox_scale || q.box) { s->pol_pair = 0; s->pol_blockpair = 0; }   // array-valued epsg, box constraint: the prox is its own launch before every step
+    if (q.pois) { s->pol_pair = 0; s->pol_blockpair = 0; }                  // Poisson data term: one iteration per launch (the pair kernels have no form of it)
   }
   if (e == hipSuccess && s->prob.tv_warm) {
     lmc::StepArgs probe = s->base;
@@ -244,6 +251,10 @@ static int skrock_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, 
 // f(x_c), g(x_c) of `x` ([C][H][W]) with the sampler's problem and scratch buffers
 static int sampler_energies_at(lmc_sampler* s, const float* x, double* f_out_dev, double* g_out_dev, hipStream_t st) {
   HIP_TRY(lmc::launch_energies(x, s->C, energy_args(s->prob), f_out_dev, g_out_dev, st));
+  {
+    const int rc = pois_energy(s->prob, x, s->C, f_out_dev, st);
+    if (rc) return rc;
+  }
   if (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 && g_out_dev)
     HIP_TRY(lmc::launch_haar_value(x, s->C, s->prob.H, s->prob.W, s->prob.prior_sigma, g_out_dev, st));
   if (s->prob.ncvx_kind == LMC_NCVX_ME_TV && f_out_dev) {
@@ -579,6 +590,7 @@ int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   if (s->tvwarm[0]) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA needs a proposal mean that is a function of x alone: tv_warm is not allowed"); }
   if (s->rtmp || s->rt_tv.kc) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA with tv_rtol > 0 is not built (use the fixed-count prox, tv_rtol = 0)"); }
   if (s->prob.prox_scale) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA takes a scalar epsg (the reference's array-valued epsg is MYULA's, algs.py:509)"); }
+  if (s->prob.pois) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_poisson(q, "MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK"); }
   if (s->prob.box) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_box(q, "MYMALA", "its target would be +infinity outside the box, where MYULA's proposals land; use MYULA"); }
   s->kind = 2;
   const size_t nbytes = sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W;
@@ -880,6 +892,7 @@ int lmc_ulpda_create(const lmc_ulpda_config* cfg, lmc_sampler** out) {
   lmc_problem pr = cfg->problem;
   if (pr.prior_kind == LMC_PRIOR_TV_ISO && pr.tv_niter < 1) pr.tv_niter = 1;   // unused by ULPDA; keeps the loader happy
   rc = load_problem(&pr, s->prob);
+  if (!rc) rc = check_no_poisson(s->prob, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA");
   if (!rc) rc = check_no_box(s->prob, "ULPDA", "its prior enters through the dual ball of g o A, which has no box form; use MYULA");
   if (rc) { delete s; return rc; }
   if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }

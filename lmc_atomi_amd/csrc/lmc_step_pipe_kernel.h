@@ -88,6 +88,15 @@ __device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_el
 __device__ __forceinline__ v2f pk_set(float a) { return v2f{a, a}; }
 // projection onto [-1, 1] per component (the dual ball of the anisotropic TV prior)
 __device__ __forceinline__ v2f pipe_clamp1(v2f a) { return v2f{__builtin_amdgcn_fmed3f(a.x, -1.f, 1.f), __builtin_amdgcn_fmed3f(a.y, -1.f, 1.f)}; }
+// Poisson data term, two pixels: rho(u) = 1 - y t (1 - t min(u, 0)), t = 1 / (max(u, 0) + beta) (pois_rho, lmc_device.h; lmc_atomi.h).  The reciprocal
+// is v_rcp_f32 with one Newton step (two packed fmas; half an ulp of t) instead of the IEEE division sequence: the L wave is the short wave every
+// other one waits for at the barrier.
+__device__ __forceinline__ v2f pois_rho2(v2f u, v2f y, v2f beta) {
+  const v2f den = v2f{fmaxf(u.x, 0.f), fmaxf(u.y, 0.f)} + beta, un = v2f{fminf(u.x, 0.f), fminf(u.y, 0.f)};
+  const v2f t0 = v2f{__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
+  const v2f t = pk_fma(t0, pk_fma(-den, t0, pk_set(1.f)), t0);
+  return pk_fma(-(y * t), pk_fma(-t, un, pk_set(1.f)), pk_set(1.f));
+}
 // projection of the primal iterate onto [lo, hi] (the box-constrained prior: one v_med3_f32 per pixel; infinite ends pass through)
 __device__ __forceinline__ v2f pipe_clamp_box(v2f a, float lo, float hi) { return v2f{__builtin_amdgcn_fmed3f(a.x, lo, hi), __builtin_amdgcn_fmed3f(a.y, lo, hi)}; }
 
@@ -419,8 +428,15 @@ __device__ __forceinline__ int pipe_role(int hw_wave, int kc, int ncvx_kind) {
 // ANISO (myula_step_pipe_aniso_kernel, lmc_step_pipe_aniso.hip): the stages project the dual onto the box (pipe_stage); fixed count, cold start.
 // BOX (myula_step_pipe_box_kernel, lmc_step_pipe_box.hip): the prior is sigma TV + the indicator of [A.box_lo, A.box_hi]: every stage and the combine
 // wave project the primal iterate they form onto the box (pipe_stage); fixed count, cold start.  Links with tv_state_only do not combine and clamp nothing there.
-template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS, bool ANISO = false, bool BOX = false>
+// POIS (myula_step_pipe_pois_kernel, myula_step_pipe_pois_box_kernel, lmc_step_pipe_pois.hip): the Poisson data term -- A.y is [2][H][W], counts then
+// background; where the L wave forms the residual d = H x - y (blur) or the pointwise gradient (identity, mask) it forms rho(H x) instead.  The
+// background row travels through a second prefetch ring (bpre) with the slots and the lead of ypre.  The residual stays masked by a 0 / 1 FACTOR: every
+// raw row load returns values of the row it reads (lanes and pixels past the row end read inside it, rows outside the image are clamped), so with the
+// documented precondition beta > 0 over the whole plane t = 1 / (max(u, 0) + beta) is finite in every lane and rho * 0 is 0, never NaN (a zero-FILLED
+// background would make it inf * 0).  One team, one launch, no energy by-products (pipe_links).
+template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS, bool ANISO = false, bool BOX = false, bool POIS = false>
 __device__ __forceinline__ void pipe_body(const StepArgs& A) {
+  static_assert(!POIS || (TEAMS == 1 && !CHAIN && !WARM && !RT && !ANISO && K == 10), "Poisson data term: one team, one launch of 10 dual iterations, isotropic prior");
   static_assert(!WARM || CHAIN, "the warm dual uses the state hand-over of the chained launches");
   static_assert(!ANISO || (!WARM && !RT), "anisotropic prior: the early exit's objective and the warm dual are not built");
   static_assert(!BOX || (!WARM && !RT), "box constraint: the early exit's objective and the warm dual are not built");
@@ -520,6 +536,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     constexpr int kXPF = 4;
     constexpr int NP = PXL / 2;
     float xpre[kXPF][PXL], ypre[4][PXL];
+    float bpre[POIS ? 4 : 1][POIS ? PXL : 1];      // POIS: the background rows, slot for slot beside ypre
     v2f hxw[NWIN][NP], hrw[NWIN][NP];   // y rows: fetched kYPF ticks ahead, slot (tick & 3)
     // 7 taps: the windows already take 96 registers; two teams: 112 VGPRs per wave, so that a wave of the side-stream moment reduction (64)
     // still fits beside the four of a workgroup on each SIMD (at 120 it waited for whole CUs: 2.08 against 1.80 ms per step)
@@ -538,6 +555,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       for (int u = 0; u < kYPF; ++u) {
         const int r = u + 1 - D + (KT - 1) - HW + LAGT;
         gload_raw<PXL>(ypre[u], A.y + (size_t)min(max(r, 0), H - 1) * W, cl, W, al);
+        if constexpr (POIS) gload_raw<PXL>(bpre[u], A.y + img + (size_t)min(max(r, 0), H - 1) * W, cl, W, al);
       }
     }
     // Without a blur: pointwise data terms (identity, diagonal mask).  Their gradient sigma_f m (m x - y) of row t + 1 - D -- the row the
@@ -551,11 +569,18 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       for (int u = 0; u < 4; ++u)
 #pragma unroll
         for (int k = 0; k < PXL; ++k) { ypre[u][k] = 0.f; mpre[u][k] = 0.f; }
+      if constexpr (POIS) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int k = 0; k < PXL; ++k) bpre[u][k] = 1.f;
+      }
       if (pw_id || pw_mask) {
 #pragma unroll
         for (int u = 0; u < kYPF; ++u) {
           const size_t ro = (size_t)min(max(u + 1 - D, 0), H - 1) * W;
           gload_raw<PXL>(ypre[u], A.y + ro, c0, W, al);
+          if constexpr (POIS) gload_raw<PXL>(bpre[u], A.y + img + ro, c0, W, al);
           if (pw_mask) gload_raw<PXL>(mpre[u], A.mask + ro, c0, W, al);
         }
       }
@@ -587,9 +612,11 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       if constexpr (KT > 0) {   // observation row of the residual row kYPF ticks from now
         const int r3 = t + kYPF + 1 - D + (KT - 1) - HW + LAGT;
         gload_raw<PXL>(ypre[(U + kYPF) & 3], A.y + (size_t)min(max(r3, 0), H - 1) * W, cl, W, al);
+        if constexpr (POIS) gload_raw<PXL>(bpre[(U + kYPF) & 3], A.y + img + (size_t)min(max(r3, 0), H - 1) * W, cl, W, al);
       } else if (pw_id || pw_mask) {
         const size_t ro = (size_t)min(max(t + kYPF + 1 - D, 0), H - 1) * W;
         gload_raw<PXL>(ypre[(U + kYPF) & 3], A.y + ro, c0, W, al);
+        if constexpr (POIS) gload_raw<PXL>(bpre[(U + kYPF) & 3], A.y + img + ro, c0, W, al);
         if (pw_mask) gload_raw<PXL>(mpre[(U + kYPF) & 3], A.mask + ro, c0, W, al);
       }
       {   // row t arrives: publish it in the ring (zeros below the image); fetch row t + 4
@@ -652,6 +679,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         const bool rowok = r >= 0 && r < H;
         const float rmask = rowok ? 1.f : 0.f;
         gfix_raw<PXL, AL>(ypre[U & 3], c0, W);
+        if constexpr (POIS) gfix_raw<PXL, AL>(bpre[U & 3], c0, W);
 #pragma unroll
         for (int j = 0; j < NP; ++j) {
           v2f acc = pk_set(uv[0]) * hxn[j];
@@ -660,7 +688,9 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           // masked by a factor, not a select: a select on (row, column) turns into one exec-masked block per pixel (8 per tick: the wave's longest
           // stretch of unpacked arithmetic and half of its scalar instructions); every operand is finite (clamped rows, zeroed ring rows).
           // The observation row arrives in natural order: its subtraction is unpacked (as many instructions as a re-pairing move and a packed one)
-          const v2f d = v2f{acc.x - ypre[U & 3][j], acc.y - ypre[U & 3][j + NP]};
+          v2f d;
+          if constexpr (POIS) d = pois_rho2(acc, v2f{ypre[U & 3][j], ypre[U & 3][j + NP]}, v2f{bpre[U & 3][j], bpre[U & 3][j + NP]});     // (finite in every lane: see POIS above)
+          else d = v2f{acc.x - ypre[U & 3][j], acc.y - ypre[U & 3][j + NP]};
           R[j] = d * v2f{(TEAMS == 2 ? cok : AL ? c0 < W : c0 + j < W) ? rmask : 0.f, (TEAMS == 2 ? cok : AL ? c0 < W : c0 + j + NP < W) ? rmask : 0.f};
         }
         if (TEAMS == 1 && A.f_out) {     // (the energy by-products are not built for two teams: pipe_teams_covered); pixels in natural order
@@ -721,12 +751,18 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           const bool rowok = i >= 0 && i < H;
           gfix_raw<PXL, AL>(ypre[U & 3], c0, W);
           if (pw_mask) gfix_raw<PXL, AL>(mpre[U & 3], c0, W);
+          if constexpr (POIS) gfix_raw<PXL, AL>(bpre[U & 3], c0, W);
 #pragma unroll
           for (int k = 0; k < PXL; ++k) {
             float g = 0.f;
             if (rowok && c0 + k < W) {
+              if constexpr (POIS) {
+                if (pw_id) g = A.sigma_f * pois_rho(xi[k], ypre[U & 3][k], bpre[U & 3][k]);
+                else g = A.sigma_f * mpre[U & 3][k] * pois_rho(mpre[U & 3][k] * xi[k], ypre[U & 3][k], bpre[U & 3][k]);
+              } else {
               if (pw_id) g = A.sigma_f * (xi[k] - ypre[U & 3][k]);
               else g = A.sigma_f * mpre[U & 3][k] * fmaf(mpre[U & 3][k], xi[k], -ypre[U & 3][k]);
+              }
             }
             gout[k] = g;
           }
@@ -1327,5 +1363,8 @@ hipError_t pipe_dispatch_box(const StepArgs& a, int KT, bool chain, int teams, h
 // lmc_step_pipe_aniso.hip: the anisotropic-prior instantiations (myula_step_pipe_aniso_kernel: K = 10, one launch or a link of a chain; the
 // two-team layout, teams = 2, covers what pipe_teams_covered names)
 hipError_t pipe_dispatch_aniso(const StepArgs& a, int KT, bool chain, int teams, hipStream_t st);
+
+// lmc_step_pipe_pois.hip: the Poisson data term (myula_step_pipe_pois_kernel / myula_step_pipe_pois_box_kernel: isotropic prior, K = 10, one launch, one team)
+hipError_t pipe_dispatch_pois(const StepArgs& a, int KT, hipStream_t st);
 
 }  // namespace lmc

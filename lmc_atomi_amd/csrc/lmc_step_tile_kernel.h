@@ -1,6 +1,6 @@
 // The body of the LDS-tiled step kernel (lmc_step_tile.hip), included once per kernel NAME: the including file defines
 //   LMC_TILE_KERNEL_HEAD   the template head and the kernel's name, up to its argument list
-//   LMC_TILE_KERNEL_FLAGS  constexpr definitions of whichever of TV, ANISO, BOX are no template parameters of that head
+//   LMC_TILE_KERNEL_FLAGS  constexpr definitions of whichever of TV, ANISO, BOX, POIS are no template parameters of that head
 // Textual inclusion, not a shared device function: the unconstrained kernels keep their instruction streams bit for bit that way (as a
 // function inlined into two kernels the same source compiles to other streams for all sixteen -- scripts/kernel_resources.py --code-hash), and the
 // box-constrained kernels get names of their own without a fourth template argument on myula_step_tile_kernel.
@@ -12,6 +12,8 @@
 // BOX (with TV; myula_step_tile_box_kernel): the prior is sigma TV + the indicator of [P.box_lo, P.box_hi] -- every primal iterate, the returned one
 // included, is projected onto the box (Beck and Teboulle's constrained FGP).  Pixels outside the image then hold the clamp of 0; the has-down / has-right
 // flags cut every difference with them, and their own dual stays 0 (no flag set), as before.
+// POIS (myula_step_tile_pois_kernel, myula_step_tile_pois_box_kernel): the Poisson data term -- P.y is [2][H][W], counts then background, and the
+// residual H x - y becomes rho(H x) = phi'(H x) (pois_rho, lmc_device.h) at the three places that form it.  P.data_kind stays the operator's kind.
 LMC_TILE_KERNEL_HEAD(const StepArgs P) {
   LMC_TILE_KERNEL_FLAGS
   static_assert(TV || !ANISO, "the anisotropic projection belongs to the TV prox");
@@ -84,7 +86,10 @@ LMC_TILE_KERNEL_HEAD(const StepArgs P) {
             for (int a = 0; a < kh; ++a)
               for (int b = 0; b < kw; ++b)
                 acc = fmaf(P.blur.h[a * kw + b], xs[(r - a + oy) * PW + (c - b + ox)], acc);
-            acc -= P.y[(size_t)(row0 + r) * W + (col0 + c)];
+            const size_t gi = (size_t)(row0 + r) * W + (col0 + c);
+            // (inside the guard: rho of a pixel outside the image is not 0 -- it is 1 for y = 0)
+            if constexpr (POIS) acc = pois_rho(acc, P.y[gi], P.y[img + gi]);
+            else acc -= P.y[gi];
           }
           S[p] = acc;  // residual, zero outside the image (zero-padded adjoint)
         }
@@ -205,10 +210,12 @@ LMC_TILE_KERNEL_HEAD(const StepArgs P) {
     const float x = xs[p];
     float g = gv[j];
     if (P.data_kind == LMC_DATA_IDENTITY) {
-      g = P.sigma_f * (x - P.y[gi]);
+      if constexpr (POIS) g = P.sigma_f * pois_rho(x, P.y[gi], P.y[img + gi]);
+      else g = P.sigma_f * (x - P.y[gi]);
     } else if (P.data_kind == LMC_DATA_MASK) {
       const float mk = P.mask[gi];
-      g = P.sigma_f * mk * fmaf(mk, x, -P.y[gi]);
+      if constexpr (POIS) g = P.sigma_f * mk * pois_rho(mk * x, P.y[gi], P.y[img + gi]);
+      else g = P.sigma_f * mk * fmaf(mk, x, -P.y[gi]);
     }
     if (P.ncvx_kind == LMC_NCVX_MC_TV) {   // - lambda * A^T(A x / max(|A x|, gamma))  (algs.py:273-277, 291)
       g -= P.ncvx_lambda * mc_tv_grad(xs[p - PW], xs[p - PW + 1], xs[p - 1], x, xs[p + 1], xs[p + PW - 1], xs[p + PW],

@@ -124,14 +124,15 @@ class _Problem:
         p.data_kind = data["data_kind"]
         p.sigma_f = float(data.get("sigma_f", 0.0))
         if data.get("y") is not None:
-            y = _dev.to_dev(data["y"], dev).reshape(self.dims)
+            # (a Poisson term: [2][H][W], the counts then the background)
+            y = _dev.to_dev(data["y"], dev).reshape(((2,) if p.data_kind in _capi.POISSON_KINDS else ()) + self.dims)
             self._keep.append(y)
             p.y_dev = y.data_ptr()
         if data.get("mask") is not None:
             m = _dev.to_dev(data["mask"], dev).reshape(self.dims)
             self._keep.append(m)
             p.mask_dev = m.data_ptr()
-        if p.data_kind == _capi.DATA_BLUR:
+        if p.data_kind in (_capi.DATA_BLUR, _capi.DATA_POISSON_BLUR):
             h = np.ascontiguousarray(data["h"], dtype=np.float32)
             self._keep.append(h)
             p.kh, p.kw = h.shape
@@ -293,6 +294,94 @@ class L2(ProxOperator):
         if self.warm:
             self._x0 = out.clone()
         return _dev.like_input(out.reshape(xt.shape), x)
+
+
+class Poisson(ProxOperator):
+    r"""Poisson likelihood of photon-limited imaging, ``b_p ~ Poisson((Op x)_p + background_p)`` (build extension; the reference has no such term --
+    ``LMC_DATA_POISSON_*`` in include/lmc_atomi.h is its definition): ``f(x) = sigma * sum_p phi_p((Op x)_p)`` with, for ``u >= 0``,
+    ``phi(u) = (u + beta) - y + y log(y / (u + beta))`` -- the generalised Kullback-Leibler divergence, the negative log-likelihood up to a constant --
+    and for ``u < 0`` its second-order Taylor extension at 0, ``phi(0) + phi'(0) u + y u^2 / (2 beta^2)``.  The extension makes ``f`` convex and C^1
+    everywhere with a Lipschitz gradient (:meth:`grad_lipschitz`), which MYULA needs: its iterates live near the positive orthant, not in it.
+
+    ``Op``: :class:`Convolve2D`, :class:`Diagonal` or :class:`Identity` (``dims``: the image shape where neither ``Op`` nor a 2-D ``b`` carries it);
+    ``b``: the counts (>= 0, finite; they need not be integers); ``background``: a
+    positive scalar or an ``[H, W]`` array (dark current, known sky); ``sigma = 1`` is the true likelihood.  A pixel with ``b_p = 0`` has a linear ``phi``,
+    unbounded below as ``u -> -inf``: USE THE MODEL WITH A POSITIVITY CONSTRAINT on the prior, e.g. ``TV(dims, ..., bounds=(0, inf))``.
+
+    As ``proxf`` of :class:`MYULASampler` / :func:`MoreauYosidaUnadjustedLangevin`, :class:`SKROCKSampler` / :func:`StabilisedLangevin` and
+    :func:`EstimatePriorWeight`, with the priors none / L2 / L1 / closed forms / TV (either form, any ``niter``, ``bounds``); the term enters the fused step
+    of the full-width pipeline (isotropic TV with 10 dual iterations, W > 128, separable blur or pointwise operator) and of the LDS-tiled kernel everywhere
+    else.  MYMALA, ULPDA, ``prox`` (no closed implicit step), ``TV(rtol > 0)``, ``TV(warm=True)``, :class:`WaveletL1` and a forced kernel variant other
+    than 'auto' / 'tile' / 'pipe' raise ``NotImplementedError``."""
+
+    def __init__(self, Op, b, background, sigma=1.0, dims=None):
+        super().__init__(Op, True)
+        if not isinstance(Op, (Convolve2D, Diagonal, Identity)):
+            raise NotImplementedError(f"no device functor for Poisson with Op of type {type(Op).__name__} (Convolve2D, Diagonal or Identity)")
+        y = _host(b).astype(np.float64)
+        # the image shape: `dims`, else the operator's, else that of an [H, W] array of counts or background
+        for cand in (dims, getattr(Op, "dims", None), y.shape if y.ndim == 2 else None, np.shape(background) if np.ndim(background) == 2 else None):
+            if cand is not None:
+                self.dims = (int(cand[0]), int(cand[1]))
+                break
+        else:
+            raise ValueError("Poisson: image shape unknown (Op carries none and b is flat): pass dims=(ny, nx)")
+        if y.size != self.dims[0] * self.dims[1]:
+            raise ValueError(f"Poisson: {y.size} counts for an image of shape {self.dims}")
+        y = y.reshape(self.dims)
+        if not np.all(np.isfinite(y)) or np.any(y < 0):
+            raise ValueError("Poisson: the counts b must be finite and >= 0")
+        beta = _host(background).astype(np.float64)
+        if beta.ndim != 0 and beta.size != y.size:
+            raise ValueError(f"Poisson: the background must be a scalar or an array of the image's shape {self.dims} (got {beta.shape})")
+        beta = np.full(self.dims, float(beta)) if beta.ndim == 0 else beta.reshape(self.dims)
+        if not np.all(np.isfinite(beta)) or np.any(beta <= 0):
+            raise ValueError("Poisson: the background must be finite and > 0 (a scalar or an [H, W] array)")
+        self.b, self.background = y, beta
+        self.sigma = float(sigma)
+        self._yb = np.ascontiguousarray(np.stack([y, beta]), dtype=np.float32)      # [2][H][W]: what y_dev points to
+        self._yb_dev = {}
+        self._prob = None
+
+    def _buffer(self):
+        """The [2][H][W] device buffer, built once (per device) and kept alive by this object; a problem on another device takes its own copy."""
+        key = _dev.device(None)
+        if key not in self._yb_dev:
+            self._yb_dev[key] = _dev.to_dev(self._yb, key)
+        return self._yb_dev[key]
+
+    def descriptor(self):
+        yb = self._buffer() if torch.cuda.is_available() else self._yb      # (without a device: the host array, for whoever only reads the description)
+        if isinstance(self.Op, Convolve2D):
+            return {"data_kind": _capi.DATA_POISSON_BLUR, "sigma_f": self.sigma, "y": yb, "h": self.Op.h, "offset": self.Op.offset}
+        if isinstance(self.Op, Diagonal):
+            return {"data_kind": _capi.DATA_POISSON_MASK, "sigma_f": self.sigma, "y": yb, "mask": self.Op.d}
+        return {"data_kind": _capi.DATA_POISSON_IDENTITY, "sigma_f": self.sigma, "y": yb}
+
+    def grad_lipschitz(self):
+        """``L_f = sigma * max(b / background^2) * ||Op||^2`` with ``||Op|| <= sum |h|`` for a convolution and the factor 1 for a mask (entries in [0, 1])
+        or the identity.  Host arithmetic, no GPU."""
+        op2 = float(np.abs(np.asarray(self.Op.h, dtype=np.float64)).sum()) ** 2 if isinstance(self.Op, Convolve2D) else 1.0
+        return self.sigma * float(np.max(self.b / self.background ** 2)) * op2
+
+    def _problem(self):
+        if self._prob is None:
+            self._prob = _Problem(self.dims, data=self.descriptor())
+        return self._prob
+
+    def __call__(self, x):
+        f, _ = self._problem().energies(x)
+        return float(f[0]) if f.numel() == 1 else (f if isinstance(x, torch.Tensor) else f.cpu().numpy())
+
+    def grad(self, x):
+        return self._problem().eval(x, 0.0, -1.0, 0.0, 0.0)
+
+    def prox(self, x, tau):
+        raise NotImplementedError("Poisson.prox: the implicit step of the Poisson likelihood has no closed form (lmc_l2_prox refuses it)")
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
 class L1(ProxOperator):
