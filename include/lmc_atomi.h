@@ -95,7 +95,9 @@ typedef enum lmc_prior_kind {
                           * inside the reference's samplers at prox_lmc.py:106,115): prox(x) = prox_X(x; p0, p1) pixel by pixel, evaluated inside
                           * the fused step kernel.  lmc_problem.eprox_kind / eprox_p0 / eprox_p1; eprox_scale_mask bit i set = parameter i is
                           * multiplied by the prox parameter (epsg * gamma in MYULA) -- e.g. prox_laplace(x, gamma * lam): p0 = lam, mask = 1.
-                          * MYULA / MYMALA steps and lmc_fused_eval; its value g(x) is not defined for every family: lmc_energies returns g = 0. */
+                          * MYULA steps and lmc_fused_eval; its value g(x) is not defined for every family: lmc_energies returns g = 0.
+                          * lmc_mymala_create returns LMC_E_UNSUPPORTED for it: without a value of g the Metropolis target exp(-f - epsg*g) is
+                          * undefined (lmc_prior_statistic and lmc_sampler_sapg refuse it for the same reason). */
 } lmc_prior_kind;
 
 typedef enum lmc_ncvx_kind {
@@ -351,7 +353,8 @@ void lmc_sampler_destroy(lmc_sampler* s);
  * min(1, pi(x') q(x|x') / (pi(x) q(x'|x))), pi = exp(-f - epsg*g), q(.|b) = N(m(b), 2 tau I) (:139-143,151-154); u ~ U(0,1) from
  * Philox (ctr = (0, iteration, global chain id, 0x4C4D4302), key = seed).  A rejected chain keeps its state, which is
  * counted again by the moment accumulators (the reference's toy version drops rejected iterations from its output list).
- * All lmc_sampler_* calls apply. */
+ * All lmc_sampler_* calls apply.  LMC_E_UNSUPPORTED, with the reason in lmc_last_error: tv_warm, tv_rtol > 0, prox_scale, a Poisson data
+ * term, a box constraint, and LMC_PRIOR_EPROX (a prior with a prox and no value: the target is undefined). */
 int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out);
 /* accepted_dev [n_chains] uint64: accepted proposals so far; last_log_alpha_dev [n_chains] f64 (nullable): log acceptance
  * ratio of the latest iteration.  Device buffers. */

@@ -38,6 +38,12 @@ def _refuse_box(prior, who, why):
         raise NotImplementedError(f"{who} does not take a prior with bounds: {why}")
 
 
+def _refuse_eprox(prior, who, why):
+    """``NotImplementedError`` for a closed-form prior (``LMC_PRIOR_EPROX``: a prox and no value) where ``who`` needs g(x) (before any handle exists)."""
+    if prior.get("prior_kind") == _capi.PRIOR_EPROX:
+        raise NotImplementedError(f"{who} does not take a closed-form prior (ElementwiseProx, Laplace, Huber, ...): {why}")
+
+
 def _refuse_poisson(data, prior, opts, who=None):
     """``NotImplementedError`` for what the library refuses with a Poisson data term (``LMC_E_UNSUPPORTED`` in include/lmc_atomi.h), before a handle
     exists.  ``who``: (name, why) of a sampler that has no Poisson form at all."""
@@ -482,6 +488,8 @@ class MYULASampler:
             raise NotImplementedError("tau=None (backtracking) is not implemented by the reference loop either")
         if self._box_refusal is not None:
             _refuse_box(_prior_descriptor(proxg), *self._box_refusal)
+        if self._eprox_refusal is not None:
+            _refuse_eprox(_prior_descriptor(proxg), *self._eprox_refusal)
         if tv_warm and _prior_descriptor(proxg).get("box") is not None:
             raise NotImplementedError("a prior with bounds has no warm-started dual: tv_warm must be off")
         self.dims = (int(dims[0]), int(dims[1]))
@@ -527,6 +535,7 @@ class MYULASampler:
     _create_fn = "lmc_myula_create"
     _box_refusal = None          # (who, why) of a subclass that has no box-constrained form: raised before a handle exists
     _poisson_refusal = None      # the same for the Poisson data term
+    _eprox_refusal = None        # the same for a closed-form prior (a prox without a value)
 
     def _create(self, cfg):
         return getattr(_dev.lib(), self._create_fn)(C.byref(cfg), C.byref(self._h))
@@ -1128,6 +1137,7 @@ class MYMALASampler(MYULASampler):
 
     _box_refusal = ("MYMALA", "its target would be +infinity outside the box, where MYULA's proposals land; use MYULA")
     _poisson_refusal = ("MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK")
+    _eprox_refusal = ("MYMALA", "the prior has a prox and no value g(x), so the Metropolis target exp(-f - epsg g) is undefined; use MYULA")
 
     def acceptance(self):
         """(accepted proposals per chain [C] int64 tensor, log acceptance ratio of the last iteration [C] float64 tensor)."""

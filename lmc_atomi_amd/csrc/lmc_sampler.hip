@@ -295,9 +295,13 @@ static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool 
   lmc::StepArgs A = s->base;
   if (fused) *fused = false;
   if (f_out && g_out && (variant_of(s->prob) == 0 || variant_of(s->prob) == 7) && s->prob.ncvx_kind == LMC_NCVX_NONE && s->prob.prior_kind == LMC_PRIOR_TV_ISO) {
+    // The pipe kernel returns f(x_in), g(x_in) as by-products where one launch WITH them covers the problem: the probe carries the outputs, since
+    // they narrow the coverage (no column strips, a blur only).  Elsewhere the launch below runs without them -- on whatever kernel covers the
+    // update alone, the strips and the pointwise data terms of the pipe kernel included -- and the caller forms the energies itself.
     lmc::StepArgs probe = A;
     probe.x_in = x_in;
-    if (lmc::pipe_supported(probe)) {   // the pipe kernel returns f(x_in), g(x_in) as by-products
+    probe.f_out = f_out; probe.g_out = g_out;
+    if (lmc::pipe_supported(probe)) {
       HIP_TRY(hipMemsetAsync(f_out, 0, sizeof(double) * s->C, st));
       HIP_TRY(hipMemsetAsync(g_out, 0, sizeof(double) * s->C, st));
       A.f_out = f_out; A.g_out = g_out; A.g_scale = s->prob.prior_sigma;
@@ -592,6 +596,7 @@ int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   if (s->prob.prox_scale) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA takes a scalar epsg (the reference's array-valued epsg is MYULA's, algs.py:509)"); }
   if (s->prob.pois) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_poisson(q, "MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK"); }
   if (s->prob.box) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_box(q, "MYMALA", "its target would be +infinity outside the box, where MYULA's proposals land; use MYULA"); }
+  if (s->prob.prior_kind == LMC_PRIOR_EPROX) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA does not take a closed-form prior (LMC_PRIOR_EPROX): the prior has a prox and no value g(x), so its Metropolis target exp(-f - epsg g) is undefined; use MYULA"); }
   s->kind = 2;
   const size_t nbytes = sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W;
   hipError_t e = hipMalloc(&s->mx, nbytes);

@@ -1,7 +1,7 @@
 """GPU parity of the anisotropic TV prior, g(x) = sigma (||d_r x||_1 + ||d_c x||_1), as `TV(..., isotropic=False)`: the prox alone, inside the
 fused MYULA step (pipe kernel `myula_step_pipe_aniso_kernel` and the tile fallback), in MYMALA, and the refusals of the C ABI.
 
-The reference of the prox is `tv_prox_aniso` below: the checker's `tv_prox_fgp` (oracle/lmc_oracle.py) with the projection of the dual onto the
+The reference of the prox is `tv_prox_aniso` (tests/_tv_aniso_ref.py): the checker's `tv_prox_fgp` (oracle/lmc_oracle.py) with the projection of the dual onto the
 l-infinity unit ball (`np.clip`) instead of the pixel-norm ball -- the set `L1.proxdual` projects onto.  Everything else (blur, gradients, momentum
 tables, the MC-TV term) is the checker's own.
 
@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import lmc_oracle as O
+from tests._tv_aniso_ref import tv_aniso_value, tv_prox_aniso
 
 pytestmark = pytest.mark.gpu
 
@@ -26,28 +27,6 @@ def rel(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
     return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
-
-
-def tv_prox_aniso(x, gamma, niter, step=0.125, momentum="unlocbox"):
-    """prox_{gamma TV_aniso}(x): `niter` FGP dual updates from the zero dual, then x - gamma div(rr, ss); images on the last two axes."""
-    x = np.asarray(x)
-    dt = x.dtype
-    gamma = dt.type(gamma)
-    c = dt.type(step) / gamma
-    betas = np.asarray(O.fgp_betas(niter, momentum), dtype=dt)
-    rr, ss, p, q = (np.zeros_like(x) for _ in range(4))
-    one = dt.type(1)
-    for k in range(niter):
-        dr, dc = O.grad2d(x - gamma * O.div2d(rr, ss))
-        pn, qn = np.clip(rr - c * dr, -one, one), np.clip(ss - c * dc, -one, one)
-        rr, ss = pn + betas[k] * (pn - p), qn + betas[k] * (qn - q)
-        p, q = pn, qn
-    return x - gamma * O.div2d(rr, ss)
-
-
-def tv_aniso_value(x):
-    dr, dc = O.grad2d(x)
-    return np.sum(np.abs(dr) + np.abs(dc), axis=(-2, -1))
 
 
 class AnisoTV:
