@@ -71,7 +71,29 @@ typedef enum lmc_data_kind {
    * pipeline does not cover (from lmc_myula_create / lmc_skrock_create, and from lmc_fused_eval). */
   LMC_DATA_POISSON_IDENTITY = 4,
   LMC_DATA_POISSON_BLUR = 5,
-  LMC_DATA_POISSON_MASK = 6
+  LMC_DATA_POISSON_MASK = 6,
+  /* Per-pixel weights on the Gaussian data term: masked, heteroscedastic deconvolution (additive values; LMC_ATOMI_ABI_VERSION stays 4, the layout of
+   * lmc_problem is unchanged: sizeof 200).  Build-specified (the reference has no such term); this text is its definition.  Operator fields as for kinds
+   * 1 and 2; y_dev points to [2][H][W] floats: plane 0 the observation y, plane 1 the weights w.  Preconditions, not checked on the device: w >= 0,
+   * w and y finite.  With u = (Op x)_p:
+   *   f(x) = sigma_f/2 sum_p w_p (u_p - y_p)^2
+   *   grad f(x) = sigma_f Op^T( w .* (Op x - y) )
+   *   L_f = sigma_f max_p w_p ||Op||^2     (||Op|| <= sum |h| for a blur, 1 for the identity)
+   * The weight multiplies the residual BEFORE the adjoint.  w == 1 is kinds 1 and 2.  A pixel with w_p = 0 is unobserved (dead, saturated or masked-out
+   * pixels under a blur; w_p = 1 / sigma_p^2 is a noise map; zero weights on a border give the unknown-boundary model).  There is no weighted mask kind:
+   * a binary mask m on a blur is w = m, and mask_dev must be NULL with these kinds (LMC_E_INVALID otherwise: a mask would be silently ignored).
+   * Honoured by lmc_myula_create, lmc_mymala_create and lmc_skrock_create with all of lmc_sampler_* (lmc_sampler_sapg included), lmc_fused_eval,
+   * lmc_energies and lmc_sampler_energies (u in fp32, w (u - y)^2 widened to and summed in float64; every width).  Priors: NONE, L2, L1, EPROX, TV_ISO
+   * and TV_ANISO with any tv_niter and tv_lagged_output, box_enable with each as it is honoured for the unweighted term.  Kernels: the full-width
+   * pipeline (myula_step_pipe_wl2_kernel, myula_step_pipe_wl2_box_kernel; one team) for the isotropic TV prior with exactly 10 dual iterations after
+   * tv_lagged_output, W > 128, a separable blur of 5 or 7 taps or the identity; the LDS-tiled kernel (myula_step_tile_wl2_kernel,
+   * myula_step_tile_wl2_box_kernel) for everything else -- every prior, width and blur.  One iteration per launch (iterations_per_launch is ignored).
+   * MYMALA takes f and g of its Metropolis target from the separate energy launch (the weighted pipe kernels form no by-products); its other refusals
+   * stand.  LMC_E_UNSUPPORTED, with the reason in lmc_last_error: lmc_ulpda_create, lmc_l2_prox (the implicit step (I + tau sigma_f Op^T W Op)^{-1} is
+   * not built), ncvx_kind != NONE, tv_rtol > 0, tv_warm, LMC_PRIOR_HAAR_L1, a forced step_variant other than 0, 1 and 7; 7 on a problem the pipeline
+   * does not cover (from the create functions, and from lmc_fused_eval). */
+  LMC_DATA_WL2_IDENTITY = 7,
+  LMC_DATA_WL2_BLUR = 8
 } lmc_data_kind;
 
 /* prior g whose prox enters the MYULA update (algs.py:569) */
@@ -216,7 +238,8 @@ typedef struct lmc_problem {
    *  - LMC_PRIOR_TV_ISO / TV_ANISO: Beck and Teboulle's constrained fast gradient projection -- the primal iterate of EVERY dual iteration and the returned one
    *    are projected onto the box (not "clip afterwards": the two differ).  tv_niter >= 1 (0: LMC_E_INVALID).  Isotropic, tv_niter in {10, 20, ... 60} (after
    *    tv_lagged_output), W > 128: the full-width pipeline (myula_step_pipe_box_kernel, two teams where lmc_set_step_variant's rule for 8 holds); everything
-   *    else, and the anisotropic prior at every width: the tiled kernel (myula_step_tile_box_kernel).
+   *    else, and the anisotropic prior at every width: the tiled kernel (myula_step_tile_box_kernel).  With a Poisson or a weighted Gaussian data term
+   *    (LMC_DATA_POISSON_*, LMC_DATA_WL2_*): the box instantiations named there (tv_niter 10 on the pipeline, the tiled kernel for the rest).
    *  - LMC_PRIOR_NONE / L2 / L1 / EPROX (separable): the clamp of the prox of g, formed by one elementwise launch before the fused step (with prox_scale: the same
    *    launch).  LMC_PRIOR_NONE: the indicator alone, prox = projection.
    * Bounds: box_lo < box_hi, neither NaN (else LMC_E_INVALID); infinite ends are allowed ((0, +inf) is positivity).
@@ -354,7 +377,8 @@ void lmc_sampler_destroy(lmc_sampler* s);
  * Philox (ctr = (0, iteration, global chain id, 0x4C4D4302), key = seed).  A rejected chain keeps its state, which is
  * counted again by the moment accumulators (the reference's toy version drops rejected iterations from its output list).
  * All lmc_sampler_* calls apply.  LMC_E_UNSUPPORTED, with the reason in lmc_last_error: tv_warm, tv_rtol > 0, prox_scale, a Poisson data
- * term, a box constraint, and LMC_PRIOR_EPROX (a prior with a prox and no value: the target is undefined). */
+ * term, a box constraint, and LMC_PRIOR_EPROX (a prior with a prox and no value: the target is undefined).  The weighted Gaussian data term
+ * (LMC_DATA_WL2_*) is taken: it is quadratic and smooth, and f and g of the target then come from the separate energy launch. */
 int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out);
 /* accepted_dev [n_chains] uint64: accepted proposals so far; last_log_alpha_dev [n_chains] f64 (nullable): log acceptance
  * ratio of the latest iteration.  Device buffers. */

@@ -17,6 +17,8 @@ ABI_VERSION = 4
 DATA_NONE, DATA_IDENTITY, DATA_BLUR, DATA_MASK = 0, 1, 2, 3
 DATA_POISSON_IDENTITY, DATA_POISSON_BLUR, DATA_POISSON_MASK = 4, 5, 6      # y_dev: [2][H][W], the counts then the background
 POISSON_KINDS = (DATA_POISSON_IDENTITY, DATA_POISSON_BLUR, DATA_POISSON_MASK)
+DATA_WL2_IDENTITY, DATA_WL2_BLUR = 7, 8      # y_dev: [2][H][W], the observation then the per-pixel weights
+WL2_KINDS = (DATA_WL2_IDENTITY, DATA_WL2_BLUR)
 PRIOR_NONE, PRIOR_L2, PRIOR_L1, PRIOR_TV_ISO, PRIOR_TV_ANISO, PRIOR_HAAR_L1, PRIOR_EPROX = 0, 1, 2, 3, 4, 5, 6
 NOISE_PHILOX, NOISE_INJECTED, NOISE_NONE = 0, 1, 2
 NCVX_NONE, NCVX_MC_TV, NCVX_ME_TV, NCVX_MC_TV_ANISO, NCVX_ME_TV_ANISO = 0, 1, 2, 3, 4

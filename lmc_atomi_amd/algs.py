@@ -64,6 +64,25 @@ def _refuse_poisson(data, prior, opts, who=None):
                                   "the problem)")
 
 
+def _refuse_wl2(data, prior, opts, who=None):
+    """The same for the weighted Gaussian data term (``L2(weights=...)``, ``LMC_DATA_WL2_*``)."""
+    if data.get("data_kind") not in _capi.WL2_KINDS:
+        return
+    if who is not None:
+        raise NotImplementedError(f"{who[0]} does not take the weighted Gaussian data term (L2 with weights): {who[1]}")
+    if prior.get("prior_kind") == _capi.PRIOR_HAAR_L1:
+        raise NotImplementedError("the weighted Gaussian data term with the Haar-l1 prior (WaveletL1) is not built")
+    if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
+        raise NotImplementedError("the weighted Gaussian data term runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
+    if prior.get("tv_warm") or opts.get("tv_warm"):
+        raise NotImplementedError("the weighted Gaussian data term has no warm-started TV dual: warm / tv_warm must be off")
+    v = opts.get("step_variant", 0) or 0
+    v = _capi.VARIANTS.index(v) if isinstance(v, str) else int(v)
+    if v not in (0, 1, 7):
+        raise NotImplementedError(f"step-kernel variant {_capi.VARIANTS[v]!r} has no form of the weighted Gaussian data term: 'auto', 'tile' or 'pipe' "
+                                  "(where it covers the problem)")
+
+
 def _data_descriptor(proxf):
     if proxf is None:
         return {"data_kind": _capi.DATA_NONE}
@@ -507,6 +526,7 @@ class MYULASampler:
             opts["prox_scale"] = self._epsg_array(epsg)
             epsg = 1.0
         _refuse_poisson(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._poisson_refusal)
+        _refuse_wl2(_data_descriptor(proxf), _prior_descriptor(proxg), opts)
         self._problem = _Problem(self.dims, _data_descriptor(proxf), _prior_descriptor(proxg), self.device, options=opts)
         self.prior_weight = float(self._problem.c.prior_sigma)      # follows set_prior_weight / estimate_prior_weight
         cfg = _capi.lmc_myula_config()
@@ -525,7 +545,7 @@ class MYULASampler:
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             rc = self._create(cfg)
-        if rc == -2 and self._problem.c.data_kind in _capi.POISSON_KINDS:      # (no handle exists: e.g. variant='pipe' on a problem the pipeline does not cover)
+        if rc == -2 and self._problem.c.data_kind in _capi.POISSON_KINDS + _capi.WL2_KINDS:      # (no handle exists: e.g. variant='pipe' on a problem the pipeline does not cover)
             raise NotImplementedError(_dev.lib().lmc_last_error().decode())
         _capi.check(rc)
         self._set_moment_scales(scales)
@@ -822,6 +842,7 @@ class ULPDASampler(MYULASampler):
         if getattr(proxg, "bounds", None) is not None:
             raise NotImplementedError("ULPDA does not take a prior with bounds: its prior enters through the dual ball of g o A, which has no box form; use MYULA")
         _refuse_poisson(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA"))
+        _refuse_wl2(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, (I + tau sigma Op^T W Op)^{-1}, which is not built; use MYULA"))
         if isinstance(proxg, L21):
             prior = {"prior_kind": _capi.PRIOR_TV_ISO, "prior_sigma": proxg.sigma, "tv_niter": 1, "tv_betas": [0.0]}
         elif isinstance(proxg, L1):

@@ -133,6 +133,7 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
   if (q.prox_scale) return fail(LMC_E_UNSUPPORTED, "prox_scale (array-valued epsg) belongs to the MYULA sampler");
   rc = check_prox_prior(q, b);
   if (!rc) rc = check_poisson(q);
+  if (!rc) rc = check_wl2(q);
   if (rc) return rc;
   lmc::StepArgs A;
   rc = make_step_args(q, a, t, b, pt, 0.f, A);
@@ -183,8 +184,10 @@ int lmc_energies(const lmc_problem* prob, const float* x_dev, int64_t n_img, dou
   if (rc) return rc;
   if (!x_dev || n_img < 1) return fail(LMC_E_INVALID, "bad arguments");
   if (q.pois && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the Poisson data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
+  if (q.wl2 && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
   HIP_TRY(lmc::launch_energies(x_dev, n_img, energy_args(q), f_out_dev, g_out_dev, S(stream)));
   rc = pois_energy(q, x_dev, n_img, f_out_dev, S(stream));
+  if (!rc) rc = wl2_energy(q, x_dev, n_img, f_out_dev, S(stream));
   if (rc) return rc;
   if (q.prior_kind == LMC_PRIOR_HAAR_L1 && g_out_dev) HIP_TRY(lmc::launch_haar_value(x_dev, n_img, q.H, q.W, q.prior_sigma, g_out_dev, S(stream)));
   if (q.ncvx_kind == LMC_NCVX_ME_TV && f_out_dev) {
@@ -207,6 +210,7 @@ int lmc_l2_prox(const lmc_problem* prob, const float* x_dev, float* out_dev, int
   int rc = load_problem(prob, q);
   if (rc) return rc;
   rc = check_no_poisson(q, "lmc_l2_prox", "its implicit step (I + tau grad f)^{-1} has no closed form");
+  if (!rc) rc = check_no_wl2(q, "lmc_l2_prox", "the implicit step (I + tau sigma_f Op^T W Op)^{-1} is not built");
   if (rc) return rc;
   if (!x_dev || !out_dev || x_dev == out_dev || n_img < 1) return fail(LMC_E_INVALID, "bad arguments (in-place not allowed)");
   if (!(tau > 0.f)) return fail(LMC_E_INVALID, "tau must be > 0");

@@ -67,6 +67,9 @@ struct StepArgs {
   // extra gradient term g += extra_coef * (x - extra[c][i][j])   (ME-TV: extra = prox_{gamma TV}(x), algs.py:282)
   const float* extra;
   float extra_coef;
+  uint32_t wl2;              // host side only, like pois (the weighted kernels are instantiations of their own): the Gaussian data term carries per-pixel
+                             // weights, sigma_f/2 sum_p w_p (u_p - y_p)^2 (LMC_DATA_WL2_*, lmc_atomi.h) -- data_kind stays the operator's kind (identity, blur),
+                             // y is [2][H][W]: the observation, then the weights w at y + H W.  It sits in the 4-byte hole behind extra_coef (the asserts below)
   // rows kernel only: dot_out[c] += sum_ij x_in[c][i][j] * x_out[c][i][j] (the p.Ap of a CG iteration, fused into the operator apply)
   double* dot_out;
   const int* skip_flag;
@@ -110,6 +113,8 @@ static_assert(offsetof(StepArgs, box_lo) == offsetof(StepArgs, g_scale) + 4 && o
               "box_lo fills the hole behind g_scale");
 static_assert(offsetof(StepArgs, pois) == offsetof(StepArgs, chain_offset) + 4 && offsetof(StepArgs, x_in) == offsetof(StepArgs, chain_offset) + 8,
               "pois fills the hole behind chain_offset");
+static_assert(offsetof(StepArgs, wl2) == offsetof(StepArgs, extra_coef) + 4 && offsetof(StepArgs, dot_out) == offsetof(StepArgs, extra_coef) + 8,
+              "wl2 fills the hole behind extra_coef");
 static_assert(offsetof(StepArgs, box_hi) == offsetof(StepArgs, fused_iters) + 4 && offsetof(StepArgs, x_mid) == offsetof(StepArgs, fused_iters) + 8,
               "box_hi fills the hole behind fused_iters");
 

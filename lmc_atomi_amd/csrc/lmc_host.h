@@ -35,6 +35,7 @@ inline bool eprox_params_ok(int kind, float p0, float p1) {
 struct Problem {
   int H = 0, W = 0;
   int data_kind = 0;        // the operator's kind, LMC_DATA_NONE .. LMC_DATA_MASK (a Poisson term: with pois = 1)
+  int wl2 = 0;              // LMC_DATA_WL2_*: per-pixel weights on the Gaussian term of that operator; y is [2][H][W], observation then weights
   int pois = 0;             // LMC_DATA_POISSON_*: the Poisson likelihood on that operator; y is [2][H][W], counts then background
   float sigma_f = 0.f;
   const float* y = nullptr;
@@ -155,6 +156,9 @@ int check_prox_prior(const Problem& q, float b);
 int check_no_box(const Problem& q, const char* who, const char* why);
 int check_no_poisson(const Problem& q, const char* who, const char* why);
 int check_poisson(const Problem& q);
+int check_no_wl2(const Problem& q, const char* who, const char* why);
+int check_wl2(const Problem& q);
+bool wl2_pipe_covers(const lmc::StepArgs& A);       // the full-width pipeline has a weighted form of this launch
 bool pois_pipe_covers(const lmc::StepArgs& A);      // the full-width pipeline has a Poisson form of this launch
 int make_step_args(const Problem& q, float a, float t, float b, float pt, float s, lmc::StepArgs& A);
 void sanitize_pointers(lmc::StepArgs& A);
@@ -176,6 +180,7 @@ int tv_prior_rt(const Problem& q, float pt, lmc::StepArgs& A, RtState& rt, float
 int tv_prior_rt_mode(const Problem& q, const lmc::StepArgs& A_probe, float pt);
 lmc::EnergyArgs energy_args(const Problem& q);
 int pois_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
+int wl2_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
 int me_tv_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, float* extra, float* st0, float* st1,
                  double* dbl /* 2*n_img */, hipStream_t st, RtState* rt);
 

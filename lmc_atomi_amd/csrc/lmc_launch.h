@@ -57,6 +57,9 @@ hipError_t launch_energies(const float* x, int64_t n_img, const EnergyArgs& E, d
                            hipStream_t st);
 // ADDS the Poisson data term's value to f_out (zeroed by launch_energies): E.data_kind = the operator's kind, E.y = [2][H][W] counts, background
 hipError_t launch_energy_pois(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, hipStream_t st);
+// ADDS the weighted Gaussian data term's value to f_out (zeroed by launch_energies): E.data_kind = the operator's kind (identity, blur), E.y = [2][H][W]
+// observation, weights
+hipError_t launch_energy_wl2(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, hipStream_t st);
 // pieces of the exact early-exit path of the TV prox (lmc_problem.tv_rtol > 0)
 hipError_t launch_tv_objective(const float* x, const float* sol, int64_t n, int H, int W, float gam, const int* flag, double* obj, hipStream_t st);
 hipError_t launch_tv_rtol_decide(int64_t n, double* prev, double* cur, int* flag, int pass, double rtol, int* n_active, hipStream_t st);

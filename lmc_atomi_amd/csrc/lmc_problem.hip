@@ -46,6 +46,13 @@ int load_problem(const lmc_problem* p, Problem& q) {
     q.data_kind = p->data_kind - LMC_DATA_POISSON_IDENTITY + LMC_DATA_IDENTITY;
     q.pois = 1;
   }
+  // per-pixel weights on the Gaussian term: the same arrangement (check_no_wl2, check_wl2)
+  if (p->data_kind == LMC_DATA_WL2_IDENTITY || p->data_kind == LMC_DATA_WL2_BLUR) {
+    // there is no weighted mask kind: a caller that hands over a mask with the weights would get it silently ignored -- say so instead (w = m is the mask)
+    if (p->mask_dev) return fail(LMC_E_INVALID, "data_kind %d (weighted Gaussian term) takes no mask_dev: there is no weighted mask kind, put the mask into the weights", p->data_kind);
+    q.data_kind = p->data_kind == LMC_DATA_WL2_BLUR ? LMC_DATA_BLUR : LMC_DATA_IDENTITY;
+    q.wl2 = 1;
+  }
   q.sigma_f = p->sigma_f;
   q.y = p->y_dev;
   q.mask = p->mask_dev;
@@ -186,6 +193,27 @@ int check_poisson(const Problem& q) {
   return LMC_OK;
 }
 
+// The entry points that have no form of the weighted Gaussian data term refuse a problem that carries one.
+int check_no_wl2(const Problem& q, const char* who, const char* why) {
+  if (!q.wl2) return LMC_OK;
+  return fail(LMC_E_UNSUPPORTED, "%s does not take the weighted Gaussian data term (LMC_DATA_WL2_*): %s", who, why);
+}
+
+// What the entry points that do take it (MYULA, MYMALA, SK-ROCK, lmc_fused_eval) refuse with it: everything that is not the fused step of the tiled
+// kernel or of the full-width pipeline's weighted instantiations.
+int check_wl2(const Problem& q) {
+  if (!q.wl2) return LMC_OK;
+  if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
+  const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
+  if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0");
+  if (q.tv_warm_asked) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term with tv_warm: the warm-started dual has no weighted form");
+  if (q.prior_kind == LMC_PRIOR_HAAR_L1) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term with LMC_PRIOR_HAAR_L1 is not built");
+  const int v = variant_of(q);
+  if (v != 0 && v != 1 && v != 7)
+    return fail(LMC_E_UNSUPPORTED, "step_variant %d has no form of the weighted Gaussian data term: 0 (auto), 1 (tile) or 7 (pipe, where it covers the problem)", v);
+  return LMC_OK;
+}
+
 // What the entry points that form prox_g (MYULA, MYMALA, lmc_fused_eval) ask of the anisotropic TV prior beyond load_problem: an iteration
 // count, and none of the options that are built for the isotropic prior only.
 int check_prox_prior(const Problem& q, float b) {
@@ -203,6 +231,7 @@ int make_step_args(const Problem& q, float a, float t, float b, float pt, float 
   A.H = q.H; A.W = q.W;
   A.data_kind = (t == 0.f) ? LMC_DATA_NONE : q.data_kind;   // skip the stencil work if its weight is zero
   A.pois = (q.pois && A.data_kind != LMC_DATA_NONE) ? 1 : 0;
+  A.wl2 = (q.wl2 && A.data_kind != LMC_DATA_NONE) ? 1 : 0;
   A.sigma_f = q.sigma_f;
   A.y = q.y; A.mask = q.mask;
   A.blur = q.taps;
@@ -263,10 +292,18 @@ static hipError_t launch_step_nobox(const lmc::StepArgs& A_in, int variant, hipS
 // before it and consumed as a ready-made prox.
 bool pois_pipe_covers(const lmc::StepArgs& A) { return A.pois && A.prior_kind == LMC_PRIOR_TV_ISO && lmc::pipe_links(A) == 1; }
 
-static hipError_t launch_step_pois(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
+// The weighted Gaussian data term (launch_step_wl2) takes the same route with kernels of its own: the pipe where pipe_links == 1 covers the problem, the
+// tile kernel for everything else.
+bool wl2_pipe_covers(const lmc::StepArgs& A) { return A.wl2 && A.prior_kind == LMC_PRIOR_TV_ISO && lmc::pipe_links(A) == 1; }
+
+// the four kernel names of a data term that has instantiations of its own: pipe, pipe + box, tile, tile + box
+struct TermNames { const char *pipe, *pipe_box, *tile, *tile_box; };
+
+static hipError_t launch_step_term(const lmc::StepArgs& A_in, int variant, bool pipe_covers, const TermNames& nm, hipStream_t st, const char** name, float* state0,
+                                   float* state1, float* pxbuf) {
   if (variant != 0 && variant != 1 && variant != 7) return hipErrorInvalidConfiguration;
-  if (variant != 1 && pois_pipe_covers(A_in)) {
-    if (name) *name = A_in.box ? "myula_step_pipe_pois_box_kernel" : "myula_step_pipe_pois_kernel";
+  if (variant != 1 && pipe_covers) {
+    if (name) *name = A_in.box ? nm.pipe_box : nm.pipe;
     return lmc::launch_step_pipe(A_in, st, nullptr, nullptr, 1);
   }
   if (variant == 7) return hipErrorInvalidConfiguration;
@@ -282,7 +319,7 @@ static hipError_t launch_step_pois(const lmc::StepArgs& A_in, int variant, hipSt
     A.prox_ext = pxbuf;
   }
   if (!tv) { if (A.prox_ext) A.prior_kind = LMC_PRIOR_NONE; A.box = 0; }
-  if (name) *name = A.box ? "myula_step_tile_pois_box_kernel" : "myula_step_tile_pois_kernel";
+  if (name) *name = A.box ? nm.tile_box : nm.tile;
   if (lmc::tile_needs_chunks(A)) {
     if (!state0 || !state1) return hipErrorInvalidConfiguration;
     return lmc::launch_step_tile_chunked(A, state0, state1, st);
@@ -290,11 +327,22 @@ static hipError_t launch_step_pois(const lmc::StepArgs& A_in, int variant, hipSt
   return lmc::launch_step_tile(A, st);
 }
 
+static hipError_t launch_step_pois(const lmc::StepArgs& A, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
+  static const TermNames nm = {"myula_step_pipe_pois_kernel", "myula_step_pipe_pois_box_kernel", "myula_step_tile_pois_kernel", "myula_step_tile_pois_box_kernel"};
+  return launch_step_term(A, variant, pois_pipe_covers(A), nm, st, name, state0, state1, pxbuf);
+}
+
+static hipError_t launch_step_wl2(const lmc::StepArgs& A, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
+  static const TermNames nm = {"myula_step_pipe_wl2_kernel", "myula_step_pipe_wl2_box_kernel", "myula_step_tile_wl2_kernel", "myula_step_tile_wl2_box_kernel"};
+  return launch_step_term(A, variant, wl2_pipe_covers(A), nm, st, name, state0, state1, pxbuf);
+}
+
 // The box-constrained forms.  Separable priors: one elementwise launch forms clip(prox) into pxbuf, then the step of the variant asked for consumes it.
 // TV priors: the pipe kernel's box instantiations (isotropic; auto, 7, 8) or the tile kernel's (either form; auto, 1); a forced variant without a box
 // form is not covered.
 hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
   if (A_in.pois) return launch_step_pois(A_in, variant, st, name, state0, state1, pxbuf);
+  if (A_in.wl2) return launch_step_wl2(A_in, variant, st, name, state0, state1, pxbuf);
   if (!A_in.box) return launch_step_nobox(A_in, variant, st, name, state0, state1, pxbuf);
   lmc::StepArgs A = A_in;
   if (A.prior_kind != LMC_PRIOR_TV_ISO) {

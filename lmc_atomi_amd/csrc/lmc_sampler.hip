@@ -108,6 +108,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   if (rc) { delete s; return rc; }
   rc = check_prox_prior(s->prob, cfg->tau / cfg->gamma);
   if (!rc) rc = check_poisson(s->prob);
+  if (!rc) rc = check_wl2(s->prob);
   if (rc) { delete s; return rc; }
   if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }
   s->C = cfg->n_chains;
@@ -122,6 +123,11 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     delete s;
     return fail(LMC_E_UNSUPPORTED, "step_variant 7 (pipe) does not cover this Poisson problem: isotropic TV with 10 dual iterations (after tv_lagged_output), "
                 "W > 128, separable blur of 5 or 7 taps or a pointwise data term; use 0 (auto) or 1 (tile)");
+  }
+  if (s->prob.wl2 && variant_of(s->prob) == 7 && !wl2_pipe_covers(s->base)) {
+    delete s;
+    return fail(LMC_E_UNSUPPORTED, "step_variant 7 (pipe) does not cover this weighted Gaussian problem: isotropic TV with 10 dual iterations (after "
+                "tv_lagged_output), W > 128, separable blur of 5 or 7 taps or the identity; use 0 (auto) or 1 (tile)");
   }
   const size_t nbytes = sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W;
   hipError_t e = hipMalloc(&s->x[0], nbytes);
@@ -154,6 +160,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     s->pol_overlap = q.moments_overlap ? q.moments_overlap : (getenv("LMC_MOMENTS_OVERLAP") ? (env_int("LMC_MOMENTS_OVERLAP", 0) ? 1 : -1) : 0);
     s->pol_bg_wgs = q.moments_bg_wgs > 0 ? q.moments_bg_wgs : env_int("LMC_MOMENTS_BG_WGS", -1);
     if (q.prox_scale || q.box) { s->pol_pair = 0; s->pol_blockpair = 0; }   // array-valued epsg, box constraint: the prox is its own launch before every step
+    if (q.wl2) { s->pol_pair = 0; s->pol_blockpair = 0; }                   // weighted Gaussian data term: the same
     if (q.pois) { s->pol_pair = 0; s->pol_blockpair = 0; }                  // Poisson data term: one iteration per launch (the pair kernels have no form of it)
   }
   if (e == hipSuccess && s->prob.tv_warm) {
@@ -252,7 +259,8 @@ static int skrock_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, 
 static int sampler_energies_at(lmc_sampler* s, const float* x, double* f_out_dev, double* g_out_dev, hipStream_t st) {
   HIP_TRY(lmc::launch_energies(x, s->C, energy_args(s->prob), f_out_dev, g_out_dev, st));
   {
-    const int rc = pois_energy(s->prob, x, s->C, f_out_dev, st);
+    int rc = pois_energy(s->prob, x, s->C, f_out_dev, st);
+    if (!rc) rc = wl2_energy(s->prob, x, s->C, f_out_dev, st);
     if (rc) return rc;
   }
   if (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 && g_out_dev)
@@ -294,7 +302,8 @@ static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool 
                           const StepOverride* ov = nullptr) {
   lmc::StepArgs A = s->base;
   if (fused) *fused = false;
-  if (f_out && g_out && (variant_of(s->prob) == 0 || variant_of(s->prob) == 7) && s->prob.ncvx_kind == LMC_NCVX_NONE && s->prob.prior_kind == LMC_PRIOR_TV_ISO) {
+  // (a weighted Gaussian data term: its pipe kernels form no by-products -- the caller takes f and g from sampler_energies_at, as for strips)
+  if (f_out && g_out && !s->prob.wl2 && (variant_of(s->prob) == 0 || variant_of(s->prob) == 7) && s->prob.ncvx_kind == LMC_NCVX_NONE && s->prob.prior_kind == LMC_PRIOR_TV_ISO) {
     // The pipe kernel returns f(x_in), g(x_in) as by-products where one launch WITH them covers the problem: the probe carries the outputs, since
     // they narrow the coverage (no column strips, a blur only).  Elsewhere the launch below runs without them -- on whatever kernel covers the
     // update alone, the strips and the pointwise data terms of the pipe kernel included -- and the caller forms the energies itself.
@@ -897,6 +906,7 @@ int lmc_ulpda_create(const lmc_ulpda_config* cfg, lmc_sampler** out) {
   lmc_problem pr = cfg->problem;
   if (pr.prior_kind == LMC_PRIOR_TV_ISO && pr.tv_niter < 1) pr.tv_niter = 1;   // unused by ULPDA; keeps the loader happy
   rc = load_problem(&pr, s->prob);
+  if (!rc) rc = check_no_wl2(s->prob, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f Op^T W Op)^{-1}, which is not built; use MYULA");
   if (!rc) rc = check_no_poisson(s->prob, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA");
   if (!rc) rc = check_no_box(s->prob, "ULPDA", "its prior enters through the dual ball of g o A, which has no box form; use MYULA");
   if (rc) { delete s; return rc; }

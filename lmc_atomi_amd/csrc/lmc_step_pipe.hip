@@ -43,6 +43,8 @@ int pipe_links(const StepArgs& a) {
   if (a.box && (n % 10 != 0 || a.f_out || a.g_out || a.tv_aniso)) return 0;
   // Poisson data term (a.pois; lmc_step_pipe_pois.hip): one launch of exactly 10, isotropic prior, no energy by-products
   if (a.pois && (n != 10 || a.f_out || a.g_out || a.tv_aniso || a.ncvx_kind != LMC_NCVX_NONE || a.extra)) return 0;
+  // weighted Gaussian data term (a.wl2; lmc_step_pipe_wl2.hip): the same coverage; identity or blur (there is no weighted mask kind)
+  if (a.wl2 && (n != 10 || a.f_out || a.g_out || a.tv_aniso || a.ncvx_kind != LMC_NCVX_NONE || a.extra || a.data_kind == LMC_DATA_MASK)) return 0;
   if (a.tv_in || a.tv_out || a.tv_state_only || a.tv_warm) return 0;
   if (!pipe_geometry_ok(a)) return 0;
   return single ? 1 : (n + 9) / 10;
@@ -54,7 +56,7 @@ bool pipe_supported(const StepArgs& a) { return pipe_links(a) == 1; }
 // a.tv_out ([C][2][H][W] each, never NULL), a.tv.niter in {1, 2, 3} dual iterations per MYULA iteration
 bool pipe_warm_supported(const StepArgs& a) {
   const int n = a.tv.niter;
-  if (!(n == 1 || n == 2 || n == 3) || a.tv_aniso || a.box || a.pois) return false;
+  if (!(n == 1 || n == 2 || n == 3) || a.tv_aniso || a.box || a.pois || a.wl2) return false;
   return pipe_geometry_ok(a);
 }
 
@@ -80,7 +82,7 @@ hipError_t launch_step_pipe_warm(StepArgs a, hipStream_t st) {
 // wide, W % 8 == 0, that returns the update alone: no energy by-products, no non-convex term (their seam columns are not exchanged).
 bool pipe_teams_covered(const StepArgs& a, int KT) {
   return a.tv.niter == 10 && KT == 5 && a.W >= 264 && a.W <= 512 && (a.W & 7) == 0 && !a.f_out && !a.g_out &&
-         a.ncvx_kind == LMC_NCVX_NONE && !a.extra && !a.pois;
+         a.ncvx_kind == LMC_NCVX_NONE && !a.extra && !a.pois && !a.wl2;
 }
 
 // state0 / state1: [C][4][H][W] ping-pong buffers for the dual state between links (needed when a.tv.niter > 10)
@@ -93,6 +95,7 @@ hipError_t launch_step_pipe(StepArgs a, hipStream_t st, float* state0, float* st
   const bool two = links == 1 && pipe_teams_covered(a, KT);
   if (teams == 2 && !two) return hipErrorInvalidConfiguration;
   if (a.pois) return links == 1 ? pipe_dispatch_pois(a, KT, st) : hipErrorInvalidConfiguration;
+  if (a.wl2) return links == 1 ? pipe_dispatch_wl2(a, KT, st) : hipErrorInvalidConfiguration;
   if (a.tv_aniso) {
     if (two && teams != 1) return pipe_dispatch_aniso(a, KT, false, 2, st);     // (512 x 512 x 1024: 1.38 against 1.57 ms per launch, bit-identical)
     if (links == 1) return pipe_dispatch_aniso(a, KT, false, 1, st);

@@ -434,8 +434,15 @@ __device__ __forceinline__ int pipe_role(int hw_wave, int kc, int ncvx_kind) {
 // raw row load returns values of the row it reads (lanes and pixels past the row end read inside it, rows outside the image are clamped), so with the
 // documented precondition beta > 0 over the whole plane t = 1 / (max(u, 0) + beta) is finite in every lane and rho * 0 is 0, never NaN (a zero-FILLED
 // background would make it inf * 0).  One team, one launch, no energy by-products (pipe_links).
-template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS, bool ANISO = false, bool BOX = false, bool POIS = false>
+// WL2 (myula_step_pipe_wl2_kernel, myula_step_pipe_wl2_box_kernel, lmc_step_pipe_wl2.hip): the weighted Gaussian data term -- A.y is [2][H][W], observation
+// then weights; the L wave forms d = (H x - y) w (blur: one packed multiply per pixel pair, BEFORE the adjoint) or the pointwise gradient
+// sigma_f w (x - y) (identity).  The weight row travels through bpre exactly as the background does.  The residual stays masked by the 0 / 1 factor:
+// gload_raw never zero-fills but returns values of the row it reads, and with the documented precondition (w finite over the whole plane) d is finite in
+// every lane, so d * 0 is 0, never NaN.  One team, one launch, no energy by-products (pipe_links).
+template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS, bool ANISO = false, bool BOX = false, bool POIS = false, bool WL2 = false>
 __device__ __forceinline__ void pipe_body(const StepArgs& A) {
+  static_assert(!WL2 || (TEAMS == 1 && !CHAIN && !WARM && !RT && !ANISO && K == 10 && !POIS),
+                "weighted Gaussian data term: one team, one launch of 10 dual iterations, isotropic prior, not with the Poisson term");
   static_assert(!POIS || (TEAMS == 1 && !CHAIN && !WARM && !RT && !ANISO && K == 10), "Poisson data term: one team, one launch of 10 dual iterations, isotropic prior");
   static_assert(!WARM || CHAIN, "the warm dual uses the state hand-over of the chained launches");
   static_assert(!ANISO || (!WARM && !RT), "anisotropic prior: the early exit's objective and the warm dual are not built");
@@ -536,7 +543,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     constexpr int kXPF = 4;
     constexpr int NP = PXL / 2;
     float xpre[kXPF][PXL], ypre[4][PXL];
-    float bpre[POIS ? 4 : 1][POIS ? PXL : 1];      // POIS: the background rows, slot for slot beside ypre
+    float bpre[POIS || WL2 ? 4 : 1][POIS || WL2 ? PXL : 1];      // POIS: the background rows, WL2: the weight rows, slot for slot beside ypre
     v2f hxw[NWIN][NP], hrw[NWIN][NP];   // y rows: fetched kYPF ticks ahead, slot (tick & 3)
     // 7 taps: the windows already take 96 registers; two teams: 112 VGPRs per wave, so that a wave of the side-stream moment reduction (64)
     // still fits beside the four of a workgroup on each SIMD (at 120 it waited for whole CUs: 2.08 against 1.80 ms per step)
@@ -555,7 +562,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       for (int u = 0; u < kYPF; ++u) {
         const int r = u + 1 - D + (KT - 1) - HW + LAGT;
         gload_raw<PXL>(ypre[u], A.y + (size_t)min(max(r, 0), H - 1) * W, cl, W, al);
-        if constexpr (POIS) gload_raw<PXL>(bpre[u], A.y + img + (size_t)min(max(r, 0), H - 1) * W, cl, W, al);
+        if constexpr (POIS || WL2) gload_raw<PXL>(bpre[u], A.y + img + (size_t)min(max(r, 0), H - 1) * W, cl, W, al);
       }
     }
     // Without a blur: pointwise data terms (identity, diagonal mask).  Their gradient sigma_f m (m x - y) of row t + 1 - D -- the row the
@@ -569,7 +576,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       for (int u = 0; u < 4; ++u)
 #pragma unroll
         for (int k = 0; k < PXL; ++k) { ypre[u][k] = 0.f; mpre[u][k] = 0.f; }
-      if constexpr (POIS) {
+      if constexpr (POIS || WL2) {
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -580,7 +587,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         for (int u = 0; u < kYPF; ++u) {
           const size_t ro = (size_t)min(max(u + 1 - D, 0), H - 1) * W;
           gload_raw<PXL>(ypre[u], A.y + ro, c0, W, al);
-          if constexpr (POIS) gload_raw<PXL>(bpre[u], A.y + img + ro, c0, W, al);
+          if constexpr (POIS || WL2) gload_raw<PXL>(bpre[u], A.y + img + ro, c0, W, al);
           if (pw_mask) gload_raw<PXL>(mpre[u], A.mask + ro, c0, W, al);
         }
       }
@@ -612,11 +619,11 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       if constexpr (KT > 0) {   // observation row of the residual row kYPF ticks from now
         const int r3 = t + kYPF + 1 - D + (KT - 1) - HW + LAGT;
         gload_raw<PXL>(ypre[(U + kYPF) & 3], A.y + (size_t)min(max(r3, 0), H - 1) * W, cl, W, al);
-        if constexpr (POIS) gload_raw<PXL>(bpre[(U + kYPF) & 3], A.y + img + (size_t)min(max(r3, 0), H - 1) * W, cl, W, al);
+        if constexpr (POIS || WL2) gload_raw<PXL>(bpre[(U + kYPF) & 3], A.y + img + (size_t)min(max(r3, 0), H - 1) * W, cl, W, al);
       } else if (pw_id || pw_mask) {
         const size_t ro = (size_t)min(max(t + kYPF + 1 - D, 0), H - 1) * W;
         gload_raw<PXL>(ypre[(U + kYPF) & 3], A.y + ro, c0, W, al);
-        if constexpr (POIS) gload_raw<PXL>(bpre[(U + kYPF) & 3], A.y + img + ro, c0, W, al);
+        if constexpr (POIS || WL2) gload_raw<PXL>(bpre[(U + kYPF) & 3], A.y + img + ro, c0, W, al);
         if (pw_mask) gload_raw<PXL>(mpre[(U + kYPF) & 3], A.mask + ro, c0, W, al);
       }
       {   // row t arrives: publish it in the ring (zeros below the image); fetch row t + 4
@@ -679,7 +686,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         const bool rowok = r >= 0 && r < H;
         const float rmask = rowok ? 1.f : 0.f;
         gfix_raw<PXL, AL>(ypre[U & 3], c0, W);
-        if constexpr (POIS) gfix_raw<PXL, AL>(bpre[U & 3], c0, W);
+        if constexpr (POIS || WL2) gfix_raw<PXL, AL>(bpre[U & 3], c0, W);
 #pragma unroll
         for (int j = 0; j < NP; ++j) {
           v2f acc = pk_set(uv[0]) * hxn[j];
@@ -691,6 +698,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           v2f d;
           if constexpr (POIS) d = pois_rho2(acc, v2f{ypre[U & 3][j], ypre[U & 3][j + NP]}, v2f{bpre[U & 3][j], bpre[U & 3][j + NP]});     // (finite in every lane: see POIS above)
           else d = v2f{acc.x - ypre[U & 3][j], acc.y - ypre[U & 3][j + NP]};
+          if constexpr (WL2) d = d * v2f{bpre[U & 3][j], bpre[U & 3][j + NP]};     // w (H x - y): the weight enters before the adjoint (finite in every lane: see WL2 above)
           R[j] = d * v2f{(TEAMS == 2 ? cok : AL ? c0 < W : c0 + j < W) ? rmask : 0.f, (TEAMS == 2 ? cok : AL ? c0 < W : c0 + j + NP < W) ? rmask : 0.f};
         }
         if (TEAMS == 1 && A.f_out) {     // (the energy by-products are not built for two teams: pipe_teams_covered); pixels in natural order
@@ -751,7 +759,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           const bool rowok = i >= 0 && i < H;
           gfix_raw<PXL, AL>(ypre[U & 3], c0, W);
           if (pw_mask) gfix_raw<PXL, AL>(mpre[U & 3], c0, W);
-          if constexpr (POIS) gfix_raw<PXL, AL>(bpre[U & 3], c0, W);
+          if constexpr (POIS || WL2) gfix_raw<PXL, AL>(bpre[U & 3], c0, W);
 #pragma unroll
           for (int k = 0; k < PXL; ++k) {
             float g = 0.f;
@@ -759,6 +767,8 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
               if constexpr (POIS) {
                 if (pw_id) g = A.sigma_f * pois_rho(xi[k], ypre[U & 3][k], bpre[U & 3][k]);
                 else g = A.sigma_f * mpre[U & 3][k] * pois_rho(mpre[U & 3][k] * xi[k], ypre[U & 3][k], bpre[U & 3][k]);
+              } else if constexpr (WL2) {
+                g = A.sigma_f * (bpre[U & 3][k] * (xi[k] - ypre[U & 3][k]));     // (identity: pipe_links keeps the mask kind away)
               } else {
               if (pw_id) g = A.sigma_f * (xi[k] - ypre[U & 3][k]);
               else g = A.sigma_f * mpre[U & 3][k] * fmaf(mpre[U & 3][k], xi[k], -ypre[U & 3][k]);
@@ -1366,5 +1376,8 @@ hipError_t pipe_dispatch_aniso(const StepArgs& a, int KT, bool chain, int teams,
 
 // lmc_step_pipe_pois.hip: the Poisson data term (myula_step_pipe_pois_kernel / myula_step_pipe_pois_box_kernel: isotropic prior, K = 10, one launch, one team)
 hipError_t pipe_dispatch_pois(const StepArgs& a, int KT, hipStream_t st);
+
+// lmc_step_pipe_wl2.hip: the weighted Gaussian data term (myula_step_pipe_wl2_kernel / myula_step_pipe_wl2_box_kernel: isotropic prior, K = 10, one launch, one team)
+hipError_t pipe_dispatch_wl2(const StepArgs& a, int KT, hipStream_t st);
 
 }  // namespace lmc

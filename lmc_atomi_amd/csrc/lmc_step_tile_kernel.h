@@ -1,6 +1,6 @@
 // The body of the LDS-tiled step kernel (lmc_step_tile.hip), included once per kernel NAME: the including file defines
 //   LMC_TILE_KERNEL_HEAD   the template head and the kernel's name, up to its argument list
-//   LMC_TILE_KERNEL_FLAGS  constexpr definitions of whichever of TV, ANISO, BOX, POIS are no template parameters of that head
+//   LMC_TILE_KERNEL_FLAGS  constexpr definitions of whichever of TV, ANISO, BOX, POIS, WL2 are no template parameters of that head
 // Textual inclusion, not a shared device function: the unconstrained kernels keep their instruction streams bit for bit that way (as a
 // function inlined into two kernels the same source compiles to other streams for all sixteen -- scripts/kernel_resources.py --code-hash), and the
 // box-constrained kernels get names of their own without a fourth template argument on myula_step_tile_kernel.
@@ -14,6 +14,8 @@
 // flags cut every difference with them, and their own dual stays 0 (no flag set), as before.
 // POIS (myula_step_tile_pois_kernel, myula_step_tile_pois_box_kernel): the Poisson data term -- P.y is [2][H][W], counts then background, and the
 // residual H x - y becomes rho(H x) = phi'(H x) (pois_rho, lmc_device.h) at the three places that form it.  P.data_kind stays the operator's kind.
+// WL2 (myula_step_tile_wl2_kernel, myula_step_tile_wl2_box_kernel): the weighted Gaussian data term -- P.y is [2][H][W], observation then weights, and
+// the residual H x - y becomes w (H x - y): the weight multiplies BEFORE the adjoint.  Identity and blur (there is no weighted mask kind).
 LMC_TILE_KERNEL_HEAD(const StepArgs P) {
   LMC_TILE_KERNEL_FLAGS
   static_assert(TV || !ANISO, "the anisotropic projection belongs to the TV prox");
@@ -89,6 +91,7 @@ LMC_TILE_KERNEL_HEAD(const StepArgs P) {
             const size_t gi = (size_t)(row0 + r) * W + (col0 + c);
             // (inside the guard: rho of a pixel outside the image is not 0 -- it is 1 for y = 0)
             if constexpr (POIS) acc = pois_rho(acc, P.y[gi], P.y[img + gi]);
+            else if constexpr (WL2) acc = P.y[img + gi] * (acc - P.y[gi]);
             else acc -= P.y[gi];
           }
           S[p] = acc;  // residual, zero outside the image (zero-padded adjoint)
@@ -211,6 +214,7 @@ LMC_TILE_KERNEL_HEAD(const StepArgs P) {
     float g = gv[j];
     if (P.data_kind == LMC_DATA_IDENTITY) {
       if constexpr (POIS) g = P.sigma_f * pois_rho(x, P.y[gi], P.y[img + gi]);
+      else if constexpr (WL2) g = P.sigma_f * (P.y[img + gi] * (x - P.y[gi]));
       else g = P.sigma_f * (x - P.y[gi]);
     } else if (P.data_kind == LMC_DATA_MASK) {
       const float mk = P.mask[gi];

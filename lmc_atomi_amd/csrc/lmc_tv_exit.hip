@@ -201,8 +201,8 @@ int tv_prior_rt_mode(const Problem& q, const lmc::StepArgs& A_probe, float pt) {
 
 lmc::EnergyArgs energy_args(const Problem& q) {
   lmc::EnergyArgs E;
-  // (a Poisson data term: none here -- f stays 0 and pois_energy adds its value)
-  E.H = q.H; E.W = q.W; E.data_kind = q.pois ? LMC_DATA_NONE : q.data_kind; E.sigma_f = q.sigma_f; E.y = q.y; E.mask = q.mask;
+  // (a Poisson or a weighted Gaussian data term: none here -- f stays 0 and pois_energy / wl2_energy adds its value)
+  E.H = q.H; E.W = q.W; E.data_kind = (q.pois || q.wl2) ? LMC_DATA_NONE : q.data_kind; E.sigma_f = q.sigma_f; E.y = q.y; E.mask = q.mask;
   E.blur = q.taps; E.prior_kind = q.prior_kind; E.prior_sigma = q.prior_sigma;
   E.ncvx_kind = q.ncvx_kind == LMC_NCVX_MC_TV ? LMC_NCVX_MC_TV : LMC_NCVX_NONE;   // ME-TV envelope: me_tv_energy
   E.ncvx_lambda = q.ncvx_lambda; E.ncvx_gamma = q.ncvx_gamma;
@@ -216,6 +216,16 @@ int pois_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, 
   E.data_kind = q.data_kind;
   E.ncvx_kind = LMC_NCVX_NONE;
   HIP_TRY(lmc::launch_energy_pois(x, n_img, E, f_out, st));
+  return LMC_OK;
+}
+
+// the same for the weighted Gaussian data term (LMC_DATA_WL2_*)
+int wl2_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st) {
+  if (!q.wl2 || !f_out) return LMC_OK;
+  lmc::EnergyArgs E = energy_args(q);
+  E.data_kind = q.data_kind;
+  E.ncvx_kind = LMC_NCVX_NONE;
+  HIP_TRY(lmc::launch_energy_wl2(x, n_img, E, f_out, st));
   return LMC_OK;
 }
 

@@ -124,15 +124,15 @@ class _Problem:
         p.data_kind = data["data_kind"]
         p.sigma_f = float(data.get("sigma_f", 0.0))
         if data.get("y") is not None:
-            # (a Poisson term: [2][H][W], the counts then the background)
-            y = _dev.to_dev(data["y"], dev).reshape(((2,) if p.data_kind in _capi.POISSON_KINDS else ()) + self.dims)
+            # (a Poisson term: [2][H][W], the counts then the background; a weighted Gaussian term: the observation then the weights)
+            y = _dev.to_dev(data["y"], dev).reshape(((2,) if p.data_kind in _capi.POISSON_KINDS + _capi.WL2_KINDS else ()) + self.dims)
             self._keep.append(y)
             p.y_dev = y.data_ptr()
         if data.get("mask") is not None:
             m = _dev.to_dev(data["mask"], dev).reshape(self.dims)
             self._keep.append(m)
             p.mask_dev = m.data_ptr()
-        if p.data_kind in (_capi.DATA_BLUR, _capi.DATA_POISSON_BLUR):
+        if p.data_kind in (_capi.DATA_BLUR, _capi.DATA_POISSON_BLUR, _capi.DATA_WL2_BLUR):
             h = np.ascontiguousarray(data["h"], dtype=np.float32)
             self._keep.append(h)
             p.kh, p.kw = h.shape
@@ -215,9 +215,16 @@ class L2(ProxOperator):
     ``grad`` runs the fused blur-residual-adjoint kernel; value via the energy kernel.
     The implicit step ``prox`` with an operator (row a8 of SURVEY section 8, used by ULPDA only) is
     provided by :mod:`lmc_atomi_amd.algs` for ULPDA; for ``Op is None`` it is closed form.
+
+    ``weights`` (build extension; ``LMC_DATA_WL2_*`` in include/lmc_atomi.h is its definition): an ``[H, W]`` or flat array ``w >= 0`` of the image's
+    size gives ``f(x) = sigma/2 sum_p w_p ((Op x)_p - b_p)^2`` with ``grad f = sigma Op^T(w * (Op x - b))`` -- a pixel with ``w_p = 0`` is unobserved
+    (dead or saturated pixels under a blur, a masked-out border), ``w_p = 1 / sigma_p^2`` is a noise map.  ``Op``: :class:`Convolve2D`,
+    :class:`Identity` or ``None``; a binary mask on a blur is ``weights = mask`` (``Diagonal`` with weights is refused).  As ``proxf`` of MYULA, MYMALA,
+    SK-ROCK and :func:`EstimatePriorWeight`; ``prox``, ULPDA, ``TV(rtol > 0)``, ``TV(warm=True)``, :class:`WaveletL1` and a forced kernel variant other
+    than 'auto' / 'tile' / 'pipe' raise ``NotImplementedError``.  ``weights=None`` is the unweighted term, unchanged.
     """
 
-    def __init__(self, Op=None, b=None, sigma=1.0, niter=10, warm=True, dims=None, bounds=None):
+    def __init__(self, Op=None, b=None, sigma=1.0, niter=10, warm=True, dims=None, bounds=None, weights=None):
         super().__init__(Op, True)
         self.bounds = check_bounds(bounds)        # as the prior only: sigma/2 ||x||^2 + the indicator of [lo, hi]
         if self.bounds is not None and (Op is not None or b is not None):
@@ -229,10 +236,65 @@ class L2(ProxOperator):
         self.dims = dims if dims is not None else getattr(Op, "dims", None)
         self._prob = None
         self._x0 = None          # warm-start vector of the implicit step (stateful, as the reference's L2)
+        self.weights = None
+        if weights is not None:
+            self._set_weights(weights)
+
+    def _set_weights(self, weights):
+        """Validates the per-pixel weights and builds the [2][H][W] host array (observation, weights) that ``y_dev`` points to."""
+        if isinstance(self.Op, Diagonal):
+            raise NotImplementedError("L2(weights=...) with Op = Diagonal: there is no weighted mask kind -- a binary mask m on a blur is weights = m")
+        if self.b is None:
+            raise NotImplementedError("L2(weights=...) without b: the weights belong to the data term; as a prior they have no meaning")
+        if self.Op is not None and not isinstance(self.Op, (Convolve2D, Identity)):
+            raise NotImplementedError(f"no device functor for L2(weights=...) with Op of type {type(self.Op).__name__} (Convolve2D or Identity)")
+        w = _host(weights).astype(np.float64)
+        y = _host(self.b).astype(np.float64)
+        if self.dims is None:      # the image shape: `dims`, else the operator's, else that of an [H, W] array of weights or observations
+            for cand in (w.shape if w.ndim == 2 else None, y.shape if y.ndim == 2 else None):
+                if cand is not None:
+                    self.dims = cand
+                    break
+            else:
+                raise ValueError("L2(weights=...): image shape unknown (Op carries none, b and weights are flat): pass dims=(ny, nx)")
+        self.dims = (int(self.dims[0]), int(self.dims[1]))
+        n = self.dims[0] * self.dims[1]
+        if w.size != n or w.ndim not in (1, 2) or (w.ndim == 2 and w.shape != self.dims):
+            raise ValueError(f"L2: weights of shape {w.shape} for an image of shape {self.dims} (an [H, W] or flat array of its size)")
+        if y.size != n:
+            raise ValueError(f"L2: {y.size} observations for an image of shape {self.dims}")
+        if not np.all(np.isfinite(w)):
+            raise ValueError("L2: the weights must be finite")
+        if np.any(w < 0):
+            raise ValueError("L2: the weights must be >= 0 (0 marks an unobserved pixel)")
+        if not np.all(np.isfinite(y)):
+            raise ValueError("L2: b must be finite where weights are given (mark a bad pixel with weight 0, not with NaN)")
+        self.weights = w.reshape(self.dims)
+        self._yw = np.ascontiguousarray(np.stack([y.reshape(self.dims), self.weights]), dtype=np.float32)      # [2][H][W]: what y_dev points to
+        self._yw_dev = {}
+
+    def _buffer(self):
+        """The [2][H][W] device buffer of the weighted term, built once (per device) and kept alive by this object."""
+        key = _dev.device(None)
+        if key not in self._yw_dev:
+            self._yw_dev[key] = _dev.to_dev(self._yw, key)
+        return self._yw_dev[key]
+
+    def grad_lipschitz(self):
+        """``L_f = sigma * max(w) * ||Op||^2`` with ``||Op|| <= sum |h|`` for a convolution and the factor 1 for a mask (entries in [0, 1]), the
+        identity or no operator; ``max(w) = 1`` without weights.  Host arithmetic, no GPU."""
+        op2 = float(np.abs(np.asarray(self.Op.h, dtype=np.float64)).sum()) ** 2 if isinstance(self.Op, Convolve2D) else 1.0
+        wmax = float(np.max(self.weights)) if self.weights is not None else 1.0
+        return self.sigma * wmax * op2
 
     # -- descriptors ---------------------------------------------------------------------
     def descriptor(self):
         """As the data term f of the sampler."""
+        if self.weights is not None:
+            yw = self._buffer() if torch.cuda.is_available() else self._yw      # (without a device: the host array, for whoever only reads the description)
+            if isinstance(self.Op, Convolve2D):
+                return {"data_kind": _capi.DATA_WL2_BLUR, "sigma_f": self.sigma, "y": yw, "h": self.Op.h, "offset": self.Op.offset}
+            return {"data_kind": _capi.DATA_WL2_IDENTITY, "sigma_f": self.sigma, "y": yw}
         if self.Op is None or isinstance(self.Op, Identity):
             if self.b is None:
                 raise NotImplementedError("L2 without b as a data term: use it as the prior instead")
@@ -274,6 +336,8 @@ class L2(ProxOperator):
         With a blur operator: ``niter`` warm-started CG iterations on the GPU (lmc_l2_prox)."""
         if self.bounds is not None:
             return _box_prox(self, x, tau)
+        if self.weights is not None:
+            raise NotImplementedError("L2.prox with weights: the implicit step (I + tau sigma Op^T W Op)^{-1} is not built (lmc_l2_prox refuses it)")
         if self.Op is None and self.b is None:
             return x / (1.0 + tau * self.sigma)
         prob = self._problem()
