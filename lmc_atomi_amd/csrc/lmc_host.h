@@ -6,12 +6,24 @@
 //   lmc_sampler.hip     the MYULA, MYMALA, SK-ROCK and ULPDA samplers
 //   lmc_rccl.hip        the dlopen'd RCCL and the moment all-reduce
 #pragma once
+#include <cmath>
 #include <string>
 #include <vector>
 
 #include "lmc_launch.h"
 
 namespace lmc::host {
+
+// Uniform boxes (all the reference's blurs): the KT centred taps t are one constant on one window [lo, hi] and zero elsewhere.  The step kernels that
+// have a shared-sum form for such taps (rows: lmc_step_rows.hip, pipe: lmc_step_pipe.hip) take it when rows and columns have the same window; other taps
+// take the general form.
+inline bool uniform_window(const float* t, int KT, int& lo, int& hi) {
+  lo = -1; hi = -1;
+  for (int i = 0; i < KT; ++i) if (t[i] != 0.f) { if (lo < 0) lo = i; hi = i; }
+  if (lo < 0) return false;
+  for (int i = lo; i <= hi; ++i) if (std::fabs(t[i] - t[lo]) > 1e-6f * std::fabs(t[lo])) return false;
+  return true;
+}
 
 // Records the message lmc_last_error returns and passes `code` on.
 int fail(int code, const char* fmt, ...);

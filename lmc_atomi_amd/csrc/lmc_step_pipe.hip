@@ -1,6 +1,7 @@
 // Host side of the "pipe" step kernel (lmc_step_pipe_kernel.h): coverage tests, dispatch, chained launches.  This translation unit
 // holds the instantiations WITHOUT dual-state hand-over (one launch = the whole TV prox from the zero dual state); the ones that
 // read / write the dual state in HBM (chained launches, warm-started prox) are in lmc_step_pipe_chain.hip.
+#include "lmc_host.h"
 #include "lmc_step_pipe_kernel.h"
 
 namespace lmc {
@@ -85,6 +86,16 @@ bool pipe_teams_covered(const StepArgs& a, int KT) {
          a.ncvx_kind == LMC_NCVX_NONE && !a.extra && !a.pois && !a.wl2;
 }
 
+// The uniform-box form of the blur wave (pipe_body, UNI; lmc_step_pipe_uni.hip) covers one launch of 10 dual iterations with a uniform 5 x 5 box -- the centred
+// taps (a.blur.h after pipe_taps) one constant on the whole window [0, 4], rows and columns -- on aligned rows in one strip, the update alone.  Every other
+// case, taps that are not uniform among them, keeps the general form.
+bool pipe_uni_covered(const StepArgs& a, int KT) {
+  if (!(a.tv.niter == 10 && KT == 5 && a.W <= 512 && pipe_lastlane(a.W))) return false;
+  if (a.tv_aniso || a.box || a.pois || a.wl2 || a.f_out || a.g_out || a.ncvx_kind != LMC_NCVX_NONE || a.extra || a.rt_kc || a.tv_warm) return false;
+  int lo, hi, l2, h2;
+  return host::uniform_window(a.blur.h, KT, lo, hi) && host::uniform_window(a.blur.h + kMaxBlur, KT, l2, h2) && lo == 0 && hi == 4 && l2 == 0 && h2 == 4;
+}
+
 // state0 / state1: [C][4][H][W] ping-pong buffers for the dual state between links (needed when a.tv.niter > 10)
 // teams: 0 = the library's choice (two teams where covered: 1.70 against 1.80 ms per step at 512 x 512 x 1024, bit-identical),
 // 1 = one team, 2 = two teams (hipErrorInvalidConfiguration where not covered)
@@ -104,6 +115,7 @@ hipError_t launch_step_pipe(StepArgs a, hipStream_t st, float* state0, float* st
     if (two && teams != 1) return pipe_dispatch_box(a, KT, false, 2, st);
     if (links == 1) return pipe_dispatch_box(a, KT, false, 1, st);
   }
+  if (links == 1 && pipe_uni_covered(a, KT)) return pipe_dispatch_uni(a, KT, two && teams != 1 ? 2 : 1, st);
   if (two && teams != 1) return pipe_launch_teams<10, 5>(a, st);
   if (links == 1) {
     switch (a.tv.niter) {

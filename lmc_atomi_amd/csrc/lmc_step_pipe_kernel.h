@@ -135,6 +135,23 @@ __device__ __forceinline__ v2f right_pair(const v2f (&v)[NP], float from_right, 
 template <int NP>
 struct DualRow { v2f rr[NP], ss[NP], p[NP], q[NP]; };
 
+// Horizontal pass of the uniform 5-tap box (pipe_body, UNI): the plain sum of the window, per pixel c
+//     a_c = x_c + x_{c+1},   S_c = (a_{c-2} + a_c) + x_{c+2}
+// -- a fixed tree that does not depend on how pixels are laid out over lanes, so every layout gives the same bits.  e = the lane's 2 NP pixels in natural
+// order with two halo pixels on either side (e[2 + k] = pixel k); the halo a's are formed from the shifted x values, never by shifting a.  On pairs:
+// E(m) = pixels (m, m + NP), m = -2 .. NP + 1; A(m) = E(m) + E(m + 1), m = -2 .. NP - 1; S(j) = (A(j - 2) + A(j)) + E(j + 2): 3 NP + 2 packed additions
+// for 2 NP pixels against 5 NP packed multiply-adds.
+template <int NP>
+__device__ __forceinline__ void uni_hsum(const float (&e)[2 * NP + 4], v2f (&out)[NP]) {
+  v2f E[NP + 4], A[NP + 2];
+#pragma unroll
+  for (int m = 0; m < NP + 4; ++m) E[m] = v2f{e[m], e[m + NP]};
+#pragma unroll
+  for (int m = 0; m < NP + 2; ++m) A[m] = E[m] + E[m + 1];
+#pragma unroll
+  for (int j = 0; j < NP; ++j) out[j] = (A[j] + A[j + 2]) + E[j + 4];
+}
+
 // Wave shifts whose vacant lane takes `edge` instead of 0 (DPP without bound_ctrl: the lane with no source keeps the old value).  The
 // two-team layout puts a team's seam column in lane 63 (left team) or lane 0 (right team), so the neighbour across the seam enters with
 // the same one instruction as the neighbour inside the wave.
@@ -439,8 +456,19 @@ __device__ __forceinline__ int pipe_role(int hw_wave, int kc, int ncvx_kind) {
 // sigma_f w (x - y) (identity).  The weight row travels through bpre exactly as the background does.  The residual stays masked by the 0 / 1 factor:
 // gload_raw never zero-fills but returns values of the row it reads, and with the documented precondition (w finite over the whole plane) d is finite in
 // every lane, so d * 0 is 0, never NaN.  One team, one launch, no energy by-products (pipe_links).
-template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS, bool ANISO = false, bool BOX = false, bool POIS = false, bool WL2 = false>
+// UNI (myula_step_pipe_uni_kernel, myula_step_pipe_uni2_kernel, lmc_step_pipe_uni.hip): the blur is a uniform 5 x 5 box (centred taps one constant on the whole
+// window in both directions; uniform_window, lmc_host.h), so the four 5-tap passes of the L wave are plain sums with shared partial sums -- horizontally
+// uni_hsum, vertically V_i = (h_i + p_{i-1}) + p_{i-3} with p_i = h_i + h_{i-1}, the p rows in a ring of four slots indexed by (tick & 3), the previous h row
+// kept by parity: no row is copied and nothing is subtracted, so nothing drifts down the image -- and the scale c_u c_v enters once, H x = c V and
+// gradient = (sigma_f c) V'.  Every sum is defined per pixel, so 4 and 8 pixels per lane, one and two teams give the same bits; against the general form the
+// states move at rounding level (another order of additions, one rounded constant for five taps).  One fixed-count launch of 10 dual iterations from the
+// zero dual state on aligned rows, one strip, update alone.  EVERYTHING ELSE KEEPS THE GENERAL FORM: RT, chained links, the warm dual, the anisotropic
+// prior, the box constraint, the Poisson and weighted data terms, 7 taps, non-uniform taps, unaligned widths, column strips, the energy by-products.
+template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS, bool ANISO = false, bool BOX = false, bool POIS = false, bool WL2 = false,
+          bool UNI = false>
 __device__ __forceinline__ void pipe_body(const StepArgs& A) {
+  static_assert(!UNI || (K == 10 && KT == 5 && AL && !CHAIN && !WARM && !RT && !ANISO && !BOX && !POIS && !WL2),
+                "uniform-box form: one fixed-count launch of 10 dual iterations, 5 taps, aligned rows, plain Gaussian data term, isotropic prior");
   static_assert(!WL2 || (TEAMS == 1 && !CHAIN && !WARM && !RT && !ANISO && K == 10 && !POIS),
                 "weighted Gaussian data term: one team, one launch of 10 dual iterations, isotropic prior, not with the Poisson term");
   static_assert(!POIS || (TEAMS == 1 && !CHAIN && !WARM && !RT && !ANISO && K == 10), "Poisson data term: one team, one launch of 10 dual iterations, isotropic prior");
@@ -545,6 +573,13 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     float xpre[kXPF][PXL], ypre[4][PXL];
     float bpre[POIS || WL2 ? 4 : 1][POIS || WL2 ? PXL : 1];      // POIS: the background rows, WL2: the weight rows, slot for slot beside ypre
     v2f hxw[NWIN][NP], hrw[NWIN][NP];   // y rows: fetched kYPF ticks ahead, slot (tick & 3)
+    // UNI: hxw / hrw hold the pair sums p_i = h_i + h_{i-1} of the horizontally summed rows (ring, slot (tick & 3)), hxp / hrp the previous h row by parity
+    v2f hxp[UNI ? 2 : 1][NP], hrp[UNI ? 2 : 1][NP];
+    const float cbox = UNI ? uv[0] * uv[kMaxBlur] : 0.f;       // c_u c_v
+#pragma unroll
+    for (int a = 0; a < (UNI ? 2 : 1); ++a)
+#pragma unroll
+      for (int k = 0; k < NP; ++k) { hxp[a][k] = pk_set(0.f); hrp[a][k] = pk_set(0.f); }
     // 7 taps: the windows already take 96 registers; two teams: 112 VGPRs per wave, so that a wave of the side-stream moment reduction (64)
     // still fits beside the four of a workgroup on each SIMD (at 120 it waited for whole CUs: 2.08 against 1.80 ms per step)
     constexpr int kYPF = (KT == 7 || TEAMS == 2) ? 2 : 3;
@@ -672,12 +707,16 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
 #pragma unroll
         for (int m = 0; m < HW; ++m)
           e[HW + PXL + m] = (TEAMS == 2 && TM == 0) ? wave_from_right(pair_px<NP>(xi, m), xr[BW + pipe_slot_offset<PXL>(m)]) : dpp_right0(pair_px<NP>(xi, m));
+        if constexpr (UNI) {
+          uni_hsum<NP>(e, hxn);
+        } else {
 #pragma unroll
         for (int j = 0; j < NP; ++j) {
           v2f acc = pk_set(uv[kMaxBlur]) * v2f{e[j + 2 * HW], e[j + 2 * HW + NP]};
 #pragma unroll
           for (int b = 1; b < KT; ++b) acc = pk_fma(pk_set(uv[kMaxBlur + b]), v2f{e[j + 2 * HW - b], e[j + 2 * HW - b + NP]}, acc);
           hxn[j] = acc;
+        }
         }
       }
       const int r = i - HW;                     // residual row: Hx[r] = sum_a u[a] hx[i - a]
@@ -689,14 +728,20 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         if constexpr (POIS || WL2) gfix_raw<PXL, AL>(bpre[U & 3], c0, W);
 #pragma unroll
         for (int j = 0; j < NP; ++j) {
-          v2f acc = pk_set(uv[0]) * hxn[j];
+          v2f acc;
+          if constexpr (UNI) {   // V_i = (h_i + p_{i-1}) + p_{i-3}: rows i - 4 .. i
+            acc = (hxn[j] + hxw[(U - 1) & 3][j]) + hxw[(U - 3) & 3][j];
+          } else {
+          acc = pk_set(uv[0]) * hxn[j];
 #pragma unroll
           for (int a = 1; a < KT; ++a) acc = pk_fma(pk_set(uv[a]), hxw[kRing4 ? ((U - a) & 3) : a - 1][j], acc);
+          }
           // masked by a factor, not a select: a select on (row, column) turns into one exec-masked block per pixel (8 per tick: the wave's longest
           // stretch of unpacked arithmetic and half of its scalar instructions); every operand is finite (clamped rows, zeroed ring rows).
           // The observation row arrives in natural order: its subtraction is unpacked (as many instructions as a re-pairing move and a packed one)
           v2f d;
           if constexpr (POIS) d = pois_rho2(acc, v2f{ypre[U & 3][j], ypre[U & 3][j + NP]}, v2f{bpre[U & 3][j], bpre[U & 3][j + NP]});     // (finite in every lane: see POIS above)
+          else if constexpr (UNI) d = v2f{__builtin_fmaf(cbox, acc.x, -ypre[U & 3][j]), __builtin_fmaf(cbox, acc.y, -ypre[U & 3][j + NP])};   // c V - y, one rounding
           else d = v2f{acc.x - ypre[U & 3][j], acc.y - ypre[U & 3][j + NP]};
           if constexpr (WL2) d = d * v2f{bpre[U & 3][j], bpre[U & 3][j + NP]};     // w (H x - y): the weight enters before the adjoint (finite in every lane: see WL2 above)
           R[j] = d * v2f{(TEAMS == 2 ? cok : AL ? c0 < W : c0 + j < W) ? rmask : 0.f, (TEAMS == 2 ? cok : AL ? c0 < W : c0 + j + NP < W) ? rmask : 0.f};
@@ -712,7 +757,10 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
             for (int j = 0; j < NP; ++j) hxw[a][j] = hxw[a - 1][j];
         }
 #pragma unroll
-        for (int j = 0; j < NP; ++j) hxw[kRing4 ? (U & 3) : 0][j] = hxn[j];
+        for (int j = 0; j < NP; ++j) {
+          if constexpr (UNI) { hxw[U & 3][j] = hxn[j] + hxp[P ^ 1][j]; hxp[P][j] = hxn[j]; }
+          else hxw[kRing4 ? (U & 3) : 0][j] = hxn[j];
+        }
       }
       if constexpr (TEAMS == 2) {   // publish this row's seam columns for the other team; the adjoint below runs on LAST tick's row
         if (TM == 0 ? lane == 63 : lane == 0) {
@@ -733,6 +781,17 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         for (int k = 0; k < PXL; ++k) e[HW + k] = pair_px<NP>(R, k);
 #pragma unroll
         for (int m = 0; m < HW; ++m) e[HW + PXL + m] = (TEAMS == 2 && TM == 0) ? wave_from_right(pair_px<NP>(R, m), sr[2 + m]) : dpp_right0(pair_px<NP>(R, m));
+        if constexpr (UNI) {
+          v2f hrn[NP];
+          uni_hsum<NP>(e, hrn);
+#pragma unroll
+          for (int j = 0; j < NP; ++j) {
+            const v2f acc = (hrn[j] + hrw[(U - 1) & 3][j]) + hrw[(U - 3) & 3][j];     // rows r - 4 .. r
+            hrw[U & 3][j] = hrn[j] + hrp[P ^ 1][j];
+            hrp[P][j] = hrn[j];
+            gout[j] = pk_set(A.sigma_f * cbox) * acc;
+          }
+        } else {
 #pragma unroll
         for (int j = 0; j < NP; ++j) {
           v2f hrn = pk_set(uv[kMaxBlur]) * v2f{e[j], e[j + NP]};
@@ -747,6 +806,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           }
           hrw[kRing4 ? (U & 3) : 0][j] = hrn;
           gout[j] = pk_set(A.sigma_f) * acc;
+        }
         }
         pairs_store<NP>(lds + L::o_g + P * RP, lane, gout);      // row t + 1 - D, read by C next tick
       }
@@ -1373,6 +1433,10 @@ hipError_t pipe_dispatch_box(const StepArgs& a, int KT, bool chain, int teams, h
 // lmc_step_pipe_aniso.hip: the anisotropic-prior instantiations (myula_step_pipe_aniso_kernel: K = 10, one launch or a link of a chain; the
 // two-team layout, teams = 2, covers what pipe_teams_covered names)
 hipError_t pipe_dispatch_aniso(const StepArgs& a, int KT, bool chain, int teams, hipStream_t st);
+
+// lmc_step_pipe_uni.hip: the uniform-box instantiations (myula_step_pipe_uni_kernel / myula_step_pipe_uni2_kernel: K = 10, one launch, 5 taps, aligned rows, one strip;
+// teams = 2 covers what pipe_teams_covered names)
+hipError_t pipe_dispatch_uni(const StepArgs& a, int KT, int teams, hipStream_t st);
 
 // lmc_step_pipe_pois.hip: the Poisson data term (myula_step_pipe_pois_kernel / myula_step_pipe_pois_box_kernel: isotropic prior, K = 10, one launch, one team)
 hipError_t pipe_dispatch_pois(const StepArgs& a, int KT, hipStream_t st);

@@ -10,6 +10,7 @@
 // Horizontal neighbours: 2*HW wave-shift DPP moves per pass for PXL pixels.  All ring slots are (row & 7) with the row loop
 // unrolled by 8, so every index is a compile-time constant and the rings live in VGPRs without rotation moves.
 // Bands start KT-1 rows early (recompute instead of exchange); HBM traffic = x read once (+ band overlap) + x' written once.
+#include "lmc_host.h"
 #include "lmc_step_rows_kernel.h"
 
 #include <cmath>
@@ -106,16 +107,9 @@ hipError_t launch_step_rows(StepArgs a, hipStream_t st) {
     return hipGetLastError();
   }
   // uniform boxes (all the reference's blurs): the sliding-window form.  Taps constant on one window [lo, hi] -- the same for rows and columns --
-  // and zero elsewhere; other taps take the general form.
-  auto window = [&](const float* t, int& l, int& h) {
-    l = -1; h = -1;
-    for (int i = 0; i < KT; ++i) if (t[i] != 0.f) { if (l < 0) l = i; h = i; }
-    if (l < 0) return false;
-    for (int i = l; i <= h; ++i) if (std::fabs(t[i] - t[l]) > 1e-6f * std::fabs(t[l])) return false;
-    return true;
-  };
+  // and zero elsewhere (uniform_window, lmc_host.h); other taps take the general form.
   int lo = -1, hi = -1, l2, h2;
-  if (!(window(uc, lo, hi) && window(vc, l2, h2) && l2 == lo && h2 == hi)) lo = hi = -1;
+  if (!(host::uniform_window(uc, KT, lo, hi) && host::uniform_window(vc, KT, l2, h2) && l2 == lo && h2 == hi)) lo = hi = -1;
   {   // uniform boxes and the closed-form elementwise priors: instantiated in lmc_step_rows_uni.hip
     bool handled = false;
     const hipError_t e = launch_step_rows_uni(a, KT, lo, hi, al, nblk, band, nbands, st, &handled);

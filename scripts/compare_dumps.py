@@ -23,6 +23,8 @@ CONFIGS = {
     "w264_me": ["--size", "264", "--ncvx", "me"],
     "w264_mc": ["--size", "264", "--ncvx", "mc"],
     "w256_pxl4": ["--size", "256"],
+    "w264_gauss": ["--size", "264", "--blur", "gaussian"],
+    "w512_gauss": ["--size", "512", "--blur", "gaussian"],
 }
 ENERGIES = ("energy_f.npy", "energy_g.npy")      # sums of atomic adds: last-bit differences between two runs of one build
 
