@@ -5,6 +5,9 @@ the conditions on the reference alone that make the GPU comparisons discriminate
     u >= 0:  phi(u) = (u + beta) - y + y log(y / (u + beta))      (0 log 0 = 0)       phi'(u) = 1 - y / (u + beta)
     u <  0:  phi(u) = phi(0) + phi'(0) u + y u^2 / (2 beta^2)                          phi'(u) = 1 - y / beta + y u / beta^2
     f(x) = sigma sum_p phi_p((Op x)_p),      grad f(x) = sigma Op^T phi'(Op x)
+
+Everything computes in float64 unless a `dtype` is handed in (`dtype=np.float32`: the same operations in the device's number format, whose distance from
+the float64 result is the rounding scale of tests/_pixel.py); the float64 results do not depend on the keyword being there.
 """
 import numpy as np
 from numpy.polynomial import chebyshev as cheb
@@ -21,21 +24,24 @@ def rel(a, b):
 # ------------------------------------------------------------------ the definition
 def _kl(d, y):
     """d - y + y log(y / d) with 0 log 0 = 0, d > 0"""
+    one, zero = d.dtype.type(1), d.dtype.type(0)
     with np.errstate(divide="ignore", invalid="ignore"):
-        ylog = np.where(y > 0, y * np.log(np.where(y > 0, y, 1.0) / d), 0.0)
+        ylog = np.where(y > 0, y * np.log(np.where(y > 0, y, one) / d), zero)
     return d - y + ylog
 
 
-def phi(u, y, beta):
-    u, y, beta = np.broadcast_arrays(np.asarray(u, dtype=np.float64), np.asarray(y, dtype=np.float64), np.asarray(beta, dtype=np.float64))
-    pos = _kl(np.maximum(u, 0.0) + beta, y)
-    neg = _kl(beta, y) + (1.0 - y / beta) * u + y * u * u / (2.0 * beta * beta)
+def phi(u, y, beta, dtype=np.float64):
+    u, y, beta = np.broadcast_arrays(np.asarray(u, dtype=dtype), np.asarray(y, dtype=dtype), np.asarray(beta, dtype=dtype))
+    one, two, zero = u.dtype.type(1), u.dtype.type(2), u.dtype.type(0)
+    pos = _kl(np.maximum(u, zero) + beta, y)
+    neg = _kl(beta, y) + (one - y / beta) * u + y * u * u / (two * beta * beta)
     return np.where(u >= 0, pos, neg)
 
 
-def dphi(u, y, beta):
-    u, y, beta = np.broadcast_arrays(np.asarray(u, dtype=np.float64), np.asarray(y, dtype=np.float64), np.asarray(beta, dtype=np.float64))
-    return np.where(u >= 0, 1.0 - y / (np.maximum(u, 0.0) + beta), 1.0 - y / beta + y * u / (beta * beta))
+def dphi(u, y, beta, dtype=np.float64):
+    u, y, beta = np.broadcast_arrays(np.asarray(u, dtype=dtype), np.asarray(y, dtype=dtype), np.asarray(beta, dtype=dtype))
+    one, zero = u.dtype.type(1), u.dtype.type(0)
+    return np.where(u >= 0, one - y / (np.maximum(u, zero) + beta), one - y / beta + y * u / (beta * beta))
 
 
 def dphi_unextended(u, y, beta):
@@ -52,12 +58,12 @@ class Op:
     def fwd(self, x):
         if self.kind == "blur":
             return O.blur(x, self.args[0], self.args[1])
-        return x * self.args[0] if self.kind == "mask" else x
+        return x * np.asarray(self.args[0], dtype=x.dtype) if self.kind == "mask" else x
 
     def adj(self, r):
         if self.kind == "blur":
             return O.blur_adjoint(r, self.args[0], self.args[1])
-        return r * self.args[0] if self.kind == "mask" else r
+        return r * np.asarray(self.args[0], dtype=r.dtype) if self.kind == "mask" else r
 
     def norm2_bound(self):
         return float(np.abs(self.args[0]).sum()) ** 2 if self.kind == "blur" else 1.0
@@ -66,21 +72,21 @@ class Op:
 class PoissonRef:
     """Checker-side data term: `.grad(x)` and `__call__(x)` on flat images (what `O.myula` hands over) or on arrays with the image on the last two axes."""
 
-    def __init__(self, op, y, beta, sigma=1.0):
-        self.op, self.sigma = op, float(sigma)
-        self.y = np.asarray(y, dtype=np.float64)
+    def __init__(self, op, y, beta, sigma=1.0, dtype=np.float64):
+        self.op, self.sigma, self.dtype = op, float(sigma), np.dtype(dtype)
+        self.y = np.asarray(y, dtype=self.dtype)
         self.dims = self.y.shape
-        self.beta = np.broadcast_to(np.asarray(beta, dtype=np.float64), self.dims).copy()
+        self.beta = np.broadcast_to(np.asarray(beta, dtype=self.dtype), self.dims).copy()
 
     def _img(self, x):
-        x = np.asarray(x, dtype=np.float64)
+        x = np.asarray(x, dtype=self.dtype)
         return x.reshape(self.dims) if x.ndim == 1 else x
 
     def u(self, x):
         return self.op.fwd(self._img(x))
 
     def grad(self, x):
-        g = self.sigma * self.op.adj(dphi(self.u(x), self.y, self.beta))
+        g = self.dtype.type(self.sigma) * self.op.adj(dphi(self.u(x), self.y, self.beta, dtype=self.dtype))
         return g.reshape(np.shape(x))
 
     def grad_with(self, x, rho):
@@ -88,7 +94,7 @@ class PoissonRef:
         return self.sigma * self.op.adj(rho(self.u(x), self.y, self.beta))
 
     def __call__(self, x):
-        v = self.sigma * phi(self.u(x), self.y, self.beta).sum(axis=(-2, -1))
+        v = self.sigma * phi(self.u(x), self.y, self.beta, dtype=self.dtype).sum(axis=(-2, -1))
         return float(v) if np.ndim(v) == 0 else v
 
     def grad_lipschitz(self):
@@ -96,20 +102,22 @@ class PoissonRef:
 
 
 # ------------------------------------------------------------------ priors of the checker (the prox of O.myula's proxg)
-def tv_prox_box(x, gamma, niter, lo=-np.inf, hi=np.inf, aniso=False, step=0.125):
+def tv_prox_box(x, gamma, niter, lo=-np.inf, hi=np.inf, aniso=False, step=0.125, dtype=np.float64):
     """prox of gamma TV (either form) + the indicator of [lo, hi]: the checker's fast gradient projection with the primal iterate clipped in every dual
     iteration and on return (Beck and Teboulle), as tests/test_gpu_tv_box.py restates it; an infinite box is the checker's `O.tv_prox_fgp`."""
-    x = np.asarray(x, dtype=np.float64)
-    c = step / gamma
-    betas = np.asarray(O.fgp_betas(niter, "unlocbox"), dtype=np.float64)
+    x = np.asarray(x, dtype=dtype)
+    dt = x.dtype.type
+    gamma, lo, hi, one = dt(gamma), dt(lo), dt(hi), dt(1)
+    c = dt(step) / gamma
+    betas = np.asarray(O.fgp_betas(niter, "unlocbox"), dtype=x.dtype)
     rr, ss, p, q = (np.zeros_like(x) for _ in range(4))
     for k in range(niter):
         dr, dc = O.grad2d(np.clip(x - gamma * O.div2d(rr, ss), lo, hi))
         r, s = rr - c * dr, ss - c * dc
         if aniso:
-            pn, qn = np.clip(r, -1.0, 1.0), np.clip(s, -1.0, 1.0)
+            pn, qn = np.clip(r, -one, one), np.clip(s, -one, one)
         else:
-            n = np.maximum(1.0, np.sqrt(r * r + s * s))
+            n = np.maximum(one, np.sqrt(r * r + s * s))
             pn, qn = r / n, s / n
         rr, ss = pn + betas[k] * (pn - p), qn + betas[k] * (qn - q)
         p, q = pn, qn
@@ -117,14 +125,14 @@ def tv_prox_box(x, gamma, niter, lo=-np.inf, hi=np.inf, aniso=False, step=0.125)
 
 
 class TVRef:
-    def __init__(self, dims, sigma, niter, bounds=None, aniso=False):
-        self.dims, self.sigma, self.niter, self.aniso = dims, sigma, niter, aniso
+    def __init__(self, dims, sigma, niter, bounds=None, aniso=False, dtype=np.float64):
+        self.dims, self.sigma, self.niter, self.aniso, self.dtype = dims, sigma, niter, aniso, np.dtype(dtype)
         self.lo, self.hi = bounds if bounds is not None else (-np.inf, np.inf)
 
     def prox(self, x, t):
         x = np.asarray(x)
         img = x.reshape(self.dims) if x.ndim == 1 else x
-        return tv_prox_box(img, self.sigma * t, self.niter, self.lo, self.hi, aniso=self.aniso).reshape(x.shape)
+        return tv_prox_box(img, self.sigma * t, self.niter, self.lo, self.hi, aniso=self.aniso, dtype=self.dtype).reshape(x.shape)
 
     def value(self, x):
         dr, dc = O.grad2d(np.asarray(x, dtype=np.float64))
@@ -134,17 +142,22 @@ class TVRef:
 class SeparableRef:
     """clip(closed-form prox)"""
 
-    def __init__(self, prox, bounds=None):
-        self._prox = prox
+    def __init__(self, prox, bounds=None, dtype=np.float64):
+        self._prox, self.dtype = prox, np.dtype(dtype)
         self.lo, self.hi = bounds if bounds is not None else (-np.inf, np.inf)
 
     def prox(self, x, t):
-        return np.clip(self._prox(np.asarray(x, dtype=np.float64), t), self.lo, self.hi)
+        return np.clip(self._prox(np.asarray(x, dtype=self.dtype), t), self.dtype.type(self.lo), self.dtype.type(self.hi))
 
 
-def myula_step(pf, pg, x, tau, gamma, xi):
-    """One MYULA step on arrays with the image on the last two axes (algs.py:569)."""
-    return (1 - tau / gamma) * x - tau * pf.grad(x) + tau / gamma * pg.prox(x, gamma) + np.sqrt(2 * tau) * xi
+def myula_step(pf, pg, x, tau, gamma, xi, dtype=None):
+    """One MYULA step on arrays with the image on the last two axes (algs.py:569).  `dtype=None`: as numpy promotes the operands (float64 from float64
+    terms); a dtype: state, noise and the four coefficients in it (the terms `pf` and `pg` are built with the same one)."""
+    if dtype is None:
+        return (1 - tau / gamma) * x - tau * pf.grad(x) + tau / gamma * pg.prox(x, gamma) + np.sqrt(2 * tau) * xi
+    dt = np.dtype(dtype).type
+    x, xi = np.asarray(x, dtype=dtype), np.asarray(xi, dtype=dtype)
+    return dt(1 - tau / gamma) * x - dt(tau) * pf.grad(x) + dt(tau / gamma) * pg.prox(x, gamma) + dt(np.sqrt(2 * tau)) * xi
 
 
 # ------------------------------------------------------------------ SK-ROCK, restated from the header text of lmc_skrock_create

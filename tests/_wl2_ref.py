@@ -22,21 +22,22 @@ ENERGY_RTOL = 5e-5
 class WL2Ref:
     """Checker-side data term: `.grad(x)` and `__call__(x)` on flat images (what `O.myula` hands over) or on arrays with the image on the last two axes."""
 
-    def __init__(self, op, y, w, sigma=1.0):
-        self.op, self.sigma = op, float(sigma)
-        self.y = np.asarray(y, dtype=np.float64)
+    def __init__(self, op, y, w, sigma=1.0, dtype=np.float64):
+        """`dtype`: the number format every method computes in (float64 by default; float32: the device's, for the rounding scale of tests/_pixel.py)."""
+        self.op, self.sigma, self.dtype = op, float(sigma), np.dtype(dtype)
+        self.y = np.asarray(y, dtype=self.dtype)
         self.dims = self.y.shape
-        self.w = np.broadcast_to(np.asarray(w, dtype=np.float64), self.dims).copy()
+        self.w = np.broadcast_to(np.asarray(w, dtype=self.dtype), self.dims).copy()
 
     def _img(self, x):
-        x = np.asarray(x, dtype=np.float64)
+        x = np.asarray(x, dtype=self.dtype)
         return x.reshape(self.dims) if x.ndim == 1 else x
 
     def residual(self, x):
         return self.op.fwd(self._img(x)) - self.y
 
     def grad(self, x):
-        return (self.sigma * self.op.adj(self.w * self.residual(x))).reshape(np.shape(x))
+        return (self.dtype.type(self.sigma) * self.op.adj(self.w * self.residual(x))).reshape(np.shape(x))
 
     def grad_unweighted(self, x):
         """sigma Op^T (Op x - y): what a kernel that ignores the weights computes."""
