@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "lmc_atomi.h"
+#include "lmc_tv_fold.h"
 
 namespace lmc {
 
@@ -23,6 +24,11 @@ struct TvIter {
   float c;       // dual step = tv_step / gamma
   float betas[kMaxTvIters];
 };
+// One launch of a pipe kernel runs at most kTvFoldMax stages and reads betas[0 .. niter) only, so the launcher (pipe_launch) keeps the folded momentum
+// table of lmc_tv_fold.h -- (1 + beta_k, c_k) for stage k at betas[kTvFoldAt + 2 (k - 1)] -- in the tail of the array of ITS copy of the argument:
+// no field is added and none moves (the argument's size and layout hold the code of some 180 kernels, below).
+constexpr int kTvFoldAt = kMaxTvIters - 2 * kTvFoldMax;
+static_assert(kTvFoldAt >= kTvFoldMax, "the folded table lies behind the coefficients a launch reads");
 
 // out = a*x - t*grad f(x) + b*prox(x) + s*xi
 struct StepArgs {

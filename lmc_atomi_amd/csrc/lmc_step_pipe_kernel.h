@@ -22,6 +22,10 @@ namespace lmc {
 // two-team layout -- 16 waves of 4 pixels per lane, the teams' roles on complementary SIMDs, the column seam through LDS; exact -- at commit
 // 4183175 (1.811 ms).  Base: 1.749 ms.
 
+// The kernels that run the stages with the momentum folded into the projection scale (pipe_stage, FOLD): one fixed-count launch from the zero dual state
+// with the isotropic projection
+__host__ __device__ constexpr bool pipe_fold(bool chain, bool warm, bool rt, bool aniso) { return !chain && !warm && !rt && !aniso; }
+
 template <int K>
 struct PipeGeom {
   static constexpr int D = (2 * K + 2 > 10) ? 2 * K + 2 : 10;   // output row lag: o = t - D
@@ -37,7 +41,7 @@ struct PipeLds {
   // team's copy of the row it works on at a fixed distance of BW floats -- a constant offset of the same address
   static constexpr int RP = TEAMS * BW;
   static constexpr int o_x = 0;                                        // [RB][RP]
-  static constexpr int o_hand = o_x + PipeGeom<K>::RB * RP;            // [NT][2][4][RP]: rr, ss, p, q of the wave's last stage
+  static constexpr int o_hand = o_x + PipeGeom<K>::RB * RP;            // [NT][2][4][RP]: rr, ss, p, q of the wave's last stage (pipe_fold kernels: rr, ss, u, v; DualRow)
   // chained launches (more than K dual iterations): the last boundary (T_NT -> C) carries rr, ss only, [2][2][BW], and the 8*BW
   // saved hold the dual state of the previous launch for stage 1, [2][4][BW] (LDS budget: 160 KB)
   static constexpr int o_hand_last = o_hand + (PipeGeom<K>::NT - 1) * 8 * RP;
@@ -132,6 +136,8 @@ __device__ __forceinline__ v2f right_pair(const v2f (&v)[NP], float from_right, 
   return v[i + 1];
 }
 
+// (rr, ss): the extrapolated dual; (p, q): the projected dual -- in the kernels with the folded momentum (pipe_stage, FOLD) scaled by the stage's
+// 1 + beta_k: u, v.  Nothing but the next stage's momentum reads p, q there.
 template <int NP>
 struct DualRow { v2f rr[NP], ss[NP], p[NP], q[NP]; };
 
@@ -210,14 +216,22 @@ __device__ __forceinline__ v2f obj_tv(const ObjMask<NP, !LASTLANE>* om, int i, v
 // before it is differenced and before it is kept as solb.  Pixels outside the image (lanes past W, rows outside, vacant lanes of a wave shift) then
 // hold blo / bhi / 0 instead of 0; no difference that reaches an image pixel depends on them: vertical ones across the image's first / last row are cut
 // by cdown, the horizontal one across the last column by pipe_ncr, and the dual of column W - 1 (s = 0 there) shields the image from the columns to its right.
-template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAML = false, bool SEAMR = false, bool ANISO = false, bool BOX = false>
+// FOLD (pipe_fold: one fixed-count launch from the zero dual state, isotropic projection): the momentum is folded into the projection scale.  The fields
+// p, q of a DualRow then hold u = (1 + beta_k) p_k, v = (1 + beta_k) q_k, the factor goes into the one `inv` both components share, and the
+// extrapolation p_k + beta_k (p_k - p_{k-1}) = u_k - c_k u_{k-1} (c_k = beta_k / (1 + beta_{k-1}); lmc_tv_fold.h) never forms p_{k-1}: per pixel pair
+//     invs = inv (1 + beta_k);  u = r invs;  v = s invs;  rr = fma(-c_k, u_old, u);  ss = fma(-c_k, v_old, v)
+// -- five packed instructions where pn = r inv, qn = s inv, rr = fma(beta, pn - p_old, pn), ss = fma(beta, qn - q_old, qn) are six, 15 per pair and
+// stage in all instead of 16.  The same number in exact arithmetic, another association of the same products in fp32.  `mom`, `cfold`: beta_k and
+// nothing, or 1 + beta_k and c_k.
+template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAML = false, bool SEAMR = false, bool ANISO = false, bool BOX = false, bool FOLD = false>
 __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[NP], const v2f (&s1)[NP], const DualRow<NP>& in0,
-                                           v2f (&solb)[NP], float gam, float cdown, const PipeCr<NP>& cr, float beta,
+                                           v2f (&solb)[NP], float gam, float cdown, const PipeCr<NP>& cr, float mom,
                                            DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP, !LASTLANE>* om = nullptr,
-                                           float ssl_edge = 0.f, float solr_edge = 0.f, float blo = 0.f, float bhi = 0.f) {
+                                           float ssl_edge = 0.f, float solr_edge = 0.f, float blo = 0.f, float bhi = 0.f, float cfold = 0.f) {
+  static_assert(!FOLD || (!ANISO && !OBJ), "the folded momentum needs the shared scale of the isotropic projection; the early exit keeps p, q");
   v2f sol[NP];
   const float ssl0 = SEAML ? wave_from_left(s1[NP - 1].y, ssl_edge) : dpp_left0(s1[NP - 1].y);
-  const v2f ngam = pk_set(-gam), ncd = pk_set(-cdown), vb = pk_set(beta);
+  const v2f ngam = pk_set(-gam), ncd = pk_set(-cdown), vb = pk_set(mom), nvc = pk_set(-cfold);
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const v2f ssl = left_pair(s1, ssl0, i);
@@ -247,10 +261,20 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
       // min(1, rsq(n2)) == rsq(max(n2, 1)) bit for bit (rsq is monotone, rsq(1) = 1); written as a [0,1] clamp it folds into the
       // output modifier of v_rsq_f32 and the v_max disappears
       const v2f inv = v2f{__builtin_amdgcn_fmed3f(__builtin_amdgcn_rsqf(n2.x), 0.f, 1.f), __builtin_amdgcn_fmed3f(__builtin_amdgcn_rsqf(n2.y), 0.f, 1.f)};
-      pn = r * inv; qn = s * inv;
+      if constexpr (FOLD) {
+        const v2f invs = inv * vb;           // ONE packed multiply for both components (vb = 1 + beta_k)
+        pn = r * invs; qn = s * invs;        // u, v
+      } else {
+        pn = r * inv; qn = s * inv;
+      }
     }
-    out.rr[i] = pk_fma(vb, pn - in0.p[i], pn);
-    out.ss[i] = pk_fma(vb, qn - in0.q[i], qn);
+    if constexpr (FOLD) {
+      out.rr[i] = pk_fma(nvc, in0.p[i], pn);
+      out.ss[i] = pk_fma(nvc, in0.q[i], qn);
+    } else {
+      out.rr[i] = pk_fma(vb, pn - in0.p[i], pn);
+      out.ss[i] = pk_fma(vb, qn - in0.q[i], qn);
+    }
     out.p[i] = pn;
     out.q[i] = qn;
   }
@@ -260,13 +284,14 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
 
 // Stage 1 of a launch that starts from the zero dual state: (rr, ss, p, q)^0 = 0, so sol^1 = x and the differences with the previous
 // iterate vanish.  Bit-identical to pipe_stage() fed with zeros (x - 0 = x, fma(c, d, 0) = c*d), at ~60 % of its instructions.
-// BOX: sol^0 = clip(x).
-template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAMR = false, bool ANISO = false, bool BOX = false>
-__device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb)[NP], float cdown, const PipeCr<NP>& cr, float beta,
+// BOX: sol^0 = clip(x).  FOLD (`mom` = 1 + beta_1): u_0 = 0, so rr = u and ss = v -- the two fma(beta, pn, pn) go, the one scaled `inv` comes.
+template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAMR = false, bool ANISO = false, bool BOX = false, bool FOLD = false>
+__device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb)[NP], float cdown, const PipeCr<NP>& cr, float mom,
                                                  DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP, !LASTLANE>* om = nullptr,
                                                  float solr_edge = 0.f, float blo = 0.f, float bhi = 0.f) {
   const float solr_last = SEAMR ? wave_from_right(solb[0].x, solr_edge) : dpp_right0(solb[0].x);
-  const v2f ncd = pk_set(-cdown), vb = pk_set(beta);
+  static_assert(!FOLD || (!ANISO && !OBJ), "as pipe_stage");
+  const v2f ncd = pk_set(-cdown), vb = pk_set(mom);
   if constexpr (OBJ) ob->sq = pk_set(0.f);       // sol^0 = x
   v2f xc[BOX ? NP : 1];
   if constexpr (BOX) {
@@ -292,10 +317,23 @@ __device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb
     } else {
       const v2f n2 = pk_fma(r, r, s * s);
       const v2f inv = v2f{__builtin_amdgcn_fmed3f(__builtin_amdgcn_rsqf(n2.x), 0.f, 1.f), __builtin_amdgcn_fmed3f(__builtin_amdgcn_rsqf(n2.y), 0.f, 1.f)};
-      pn = r * inv; qn = s * inv;
+      if constexpr (FOLD) {
+        // rr = u and ss = v are plain products here, and stage 2 of the same wave subtracts them in registers: left contractable, the compiler fuses
+        // product and difference in some instantiations and not in others, and the layouts no longer give the same bits
+#pragma clang fp contract(off)
+        const v2f invs = inv * vb;
+        pn = r * invs; qn = s * invs;
+      } else {
+        pn = r * inv; qn = s * inv;
+      }
     }
-    out.rr[i] = pk_fma(vb, pn, pn);
-    out.ss[i] = pk_fma(vb, qn, qn);
+    if constexpr (FOLD) {
+      out.rr[i] = pn;
+      out.ss[i] = qn;
+    } else {
+      out.rr[i] = pk_fma(vb, pn, pn);
+      out.ss[i] = pk_fma(vb, qn, qn);
+    }
     out.p[i] = pn;
     out.q[i] = qn;
   }
@@ -485,6 +523,11 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
   static_assert(!RT || AL || pipe_halo(K, KT, PXL) >= K + 2, "per-chain exit on column strips: the halo holds the objective's extra column");
   static_assert(TEAMS == 1 || (TEAMS == 2 && K == 10 && PXL == 4 && KT == 5 && AL && !CHAIN && !WARM && !RT),
                 "two teams: one fixed-count launch, 5 taps, aligned rows, 4 pixels per lane");
+  // Momentum folded into the projection scale (pipe_stage): wherever nothing but the next stage's momentum reads p, q -- not where they travel through HBM
+  // (links, the warm dual), not with the early exit (pass-through slots copy them, and a rounding-level move can flip an exit pass), not with the
+  // anisotropic clamp (no shared scale).  Those keep the code and the bits they had.
+  constexpr bool FOLD = pipe_fold(CHAIN, WARM, RT, ANISO);
+  static_assert(!FOLD || K <= kTvFoldMax, "the folded table holds one launch's stages");
   using G = PipeGeom<K>;
   using L = PipeLds<K, PXL, CHAIN, TEAMS>;
   constexpr int D = G::D, E = G::E, RB = G::RB, NT = G::NT, BW = L::BW, RP = L::RP, HW = KT > 0 ? (KT - 1) / 2 : 0;
@@ -861,7 +904,9 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     const int g1 = spread ? wave : k1, g2 = k2;          // the STAGES the slots run (momentum coefficient, objective slot)
     const float gam = A.tv.gamma, cstep = A.tv.c;
     const float blo = BOX ? A.box_lo : 0.f, bhi = BOX ? A.box_hi : 0.f;
-    const float beta1 = A.tv.betas[g1 - 1], beta2 = SINGLE ? 0.f : A.tv.betas[g2 - 1];
+    // FOLD: 1 + beta_g and c_g of the launcher's table (lmc_common.h: kTvFoldAt) in place of beta_g
+    const float beta1 = A.tv.betas[FOLD ? kTvFoldAt + 2 * (g1 - 1) : g1 - 1], beta2 = SINGLE ? 0.f : A.tv.betas[FOLD ? kTvFoldAt + 2 * (g2 - 1) : g2 - 1];
+    const float cf1 = FOLD ? A.tv.betas[kTvFoldAt + 2 * (g1 - 1) + 1] : 0.f, cf2 = FOLD && !SINGLE ? A.tv.betas[kTvFoldAt + 2 * (g2 - 1) + 1] : 0.f;
     PipeCr<PXL / 2> crc;                                              // see PipeCr: AL kernels need W % PXL == 0 (host check), the others take any W
     crc.cstep = cstep;
     crc.cr_last = (c0 + PXL - 1 == W - 1 || (TEAMS == 2 && !cok)) ? 0.f : cstep;   // (two teams: ss stays 0 left of column 0)
@@ -956,7 +1001,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         if (live2) {
           StageObj ob;
           om.md = cdown != 0.f ? 1.f : 0.f;
-          pipe_stage<NP, AL, RT, SL, SRt, ANISO, BOX>(xk[P], o1[P ^ 1].rr, o1[P ^ 1].ss, o1[P], sol2, gam, cdown, crc, beta2, out, &ob, &om, edge.y, edge.y, blo, bhi);
+          pipe_stage<NP, AL, RT, SL, SRt, ANISO, BOX, FOLD>(xk[P], o1[P ^ 1].rr, o1[P ^ 1].ss, o1[P], sol2, gam, cdown, crc, beta2, out, &ob, &om, edge.y, edge.y, blo, bhi, cf2);
           if constexpr (RT) { osq2 += (double)(ob.sq.x + ob.sq.y); otv2 += (double)(ob.tv.x + ob.tv.y); }
         } else {                 // pass-through: the state of row a2 - 1 as stage k1 left it
 #pragma unroll
@@ -989,8 +1034,8 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           const float cdown = ((unsigned)(a1 - 1) >= (unsigned)(H - 1)) ? 0.f : cstep;
           StageObj ob;
           om.md = cdown != 0.f ? 1.f : 0.f;
-          if constexpr (FIRST) pipe_stage_first<NP, AL, RT, SRt, ANISO, BOX>(xk[P], sol1, cdown, crc, beta1, o1[P], &ob, &om, edge.x, blo, bhi);
-          else pipe_stage<NP, AL, RT, SL, SRt, ANISO, BOX>(xk[P], inb[P].rr, inb[P].ss, inb[P ^ 1], sol1, gam, cdown, crc, beta1, o1[P], &ob, &om, edge.x, edge.x, blo, bhi);
+          if constexpr (FIRST) pipe_stage_first<NP, AL, RT, SRt, ANISO, BOX, FOLD>(xk[P], sol1, cdown, crc, beta1, o1[P], &ob, &om, edge.x, blo, bhi);
+          else pipe_stage<NP, AL, RT, SL, SRt, ANISO, BOX, FOLD>(xk[P], inb[P].rr, inb[P].ss, inb[P ^ 1], sol1, gam, cdown, crc, beta1, o1[P], &ob, &om, edge.x, edge.x, blo, bhi, cf1);
           if constexpr (RT) { osq1 += (double)(ob.sq.x + ob.sq.y); otv1 += (double)(ob.tv.x + ob.tv.y); }
         } else {                 // pass-through: the state of row a1 - 1, read one tick ago
 #pragma unroll
@@ -1356,8 +1401,12 @@ static_assert(pipe_teams_lds_bytes<10>() <= 160 * 1024, "LDS of one workgroup");
 
 // The one launcher of every pipe kernel, one and two teams, either prior.  The dynamic-LDS limit belongs to the function's code object on
 // each device and is set once per device; Kern is a template argument so that every kernel has a memo of its own.
+// The folded momentum table (lmc_common.h: kTvFoldAt) goes into this launch's copy of the argument, for every kernel: the ones without the fold never read it.
 template <auto Kern>
-static hipError_t pipe_launch(size_t lds_bytes, dim3 grid, dim3 block, const StepArgs& a, hipStream_t st) {
+static hipError_t pipe_launch(size_t lds_bytes, dim3 grid, dim3 block, const StepArgs& a0, hipStream_t st) {
+  StepArgs a = a0;
+  const bool fold_ok = tv_fold_table(a0.tv.betas, a0.tv.niter < kTvFoldMax ? a0.tv.niter : kTvFoldMax, a.tv.betas + kTvFoldAt);
+  if (!fold_ok && pipe_fold(a.tv_in || a.tv_out || a.tv_state_only, a.tv_warm != 0, a.rt_kc != nullptr, a.tv_aniso != 0)) return hipErrorInvalidConfiguration;
   static bool attr_set[64] = {};
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);

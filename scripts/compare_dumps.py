@@ -25,6 +25,7 @@ CONFIGS = {
     "w256_pxl4": ["--size", "256"],
     "w264_gauss": ["--size", "264", "--blur", "gaussian"],
     "w512_gauss": ["--size", "512", "--blur", "gaussian"],
+    "w264_tv20_chained": ["--size", "264", "--tv-iters", "20"],      # two links through the dual state in HBM
 }
 ENERGIES = ("energy_f.npy", "energy_g.npy")      # sums of atomic adds: last-bit differences between two runs of one build
 
