@@ -145,6 +145,7 @@ typedef enum lmc_noise_mode {
 #define LMC_MAX_TV_ITERS 64
 #define LMC_MAX_SKROCK_STAGES 64
 #define LMC_MAX_CHAIN_GROUPS 64
+#define LMC_MAX_COV_PROBES 32
 
 /* Geometry + potential U(x) = f(x) + eps*g(x).  Plain data; copied by the callee. */
 typedef struct lmc_problem {
@@ -320,6 +321,15 @@ int lmc_pixel_histogram(const float* x_dev, int64_t C, int32_t H, int32_t W, int
  * (one stream). */
 int lmc_group_moments(const float* x_dev, int64_t C, int64_t chain_offset, int32_t H, int32_t W, int32_t n_groups,
                       double* sum_dev, double* sumsq_dev, void* stream);
+
+/* Stateless, operator level: ADDS the covariance sketch of x[C][H][W] (definition and arithmetic at lmc_sampler_set_cov_sketch) into y_dev
+ * [k*H*W], s_dev [k] and q_dev [k*k] (float64 each).  probes_dev: [k*H*W] floats, 1 <= k <= LMC_MAX_COV_PROBES; center_dev: [H*W] floats or NULL
+ * (= 0).  workspace_dev: lmc_cov_sketch_workspace_bytes(C, H, W, k) bytes of device memory, 16-byte aligned, overwritten by every call (the
+ * function returns 0 for arguments the call would refuse).  One owner per output element and launch, no atomics: the same call on the same arrays
+ * gives the same bits, and calls that share y / s / q or the workspace must be ordered (one stream). */
+size_t lmc_cov_sketch_workspace_bytes(int64_t C, int32_t H, int32_t W, int32_t k);
+int lmc_cov_sketch(const float* x_dev, int64_t C, int32_t H, int32_t W, int32_t k, const float* probes_dev, const float* center_dev,
+                   double* y_dev, double* s_dev, double* q_dev, void* workspace_dev, void* stream);
 
 /* Per-pixel projection of the stacked field y[2][H][W] onto the l2 ball (isotropic != 0) or the
  * box (isotropic == 0) of radius `radius`: L21.proxdual / L1.proxdual (algs.py:436,448). */
@@ -529,6 +539,32 @@ int lmc_sampler_set_chain_groups(lmc_sampler* s, int32_t n_groups);
 /* sum_dev, sumsq_dev: [n_groups*H*W] double (device, nullable); counts_host: [n_groups] (host, nullable).  A handle without groups:
  * LMC_E_INVALID. */
 int lmc_sampler_get_group_moments(lmc_sampler* s, double* sum_dev, double* sumsq_dev, uint64_t* counts_host, void* stream);
+/* Covariance sketch: how pixels move together, without a stored iterate.  Given k probe images P[k][H][W] (fp32, 1 <= k <= LMC_MAX_COV_PROBES) and a
+ * centre m[H][W] (fp32, NULL = 0), every kept sample x_c (chain c) contributes
+ *   d_c[p]  = x_c[p] - m[p]                      (one fp32 subtraction)
+ *   t_c[j]  = sum_p P[j][p] d_c[p]               (the projection of the sample on probe j)
+ *   Y[j][p] += sum_c t_c[j] d_c[p]               [k][H][W] float64
+ *   s[j]    += sum_c t_c[j]                      [k]       float64
+ *   Q[j][l] += sum_c t_c[j] t_c[l]               [k][k]    float64
+ * over the same kept samples, and with the same count, as the pixel moments s1, s2.  With n = count, dbar = s1 / n - m and tbar = s / n (float64
+ * host arithmetic; cov_from_sketch in the Python package) the summaries are
+ *   cov_xt[j][p] = Y[j][p] / n - tbar[j] dbar[p]     = (Sigma P_j^T)[p], Sigma the N x N posterior sample covariance: every pixel against projection j
+ *   cov_tt       = Q / n - tbar tbar^T               = P Sigma P^T, k x k
+ * exactly.  Region indicators as probes give the covariance matrix of the region fluxes and the correlation map of every pixel with a region;
+ * Gaussian random probes give the one-pass Nystrom sketch Sigma ~ cov_xt^T cov_tt^+ cov_xt of the leading uncertainty modes (exact when
+ * rank Sigma <= k; it underestimates eigenvalues otherwise).  Without a centre cov_xt is a difference of terms of size mean^2 and loses digits:
+ * pass a pilot-run mean as centre.
+ * Arithmetic: t_c[j] is formed from fp32 products accumulated in fp32 (an ordered fmaf chain) over runs of at most 2048 pixels, the run sums are
+ * combined in float64 in ascending order.  In the Y update t is rounded to fp32, the products are accumulated in fp32 over runs of at most 1024
+ * chains, and the run sums are added to Y in float64 with a plain read-add-write.  s and Q are float64 sums of the float64 t.  No float atomics,
+ * one owner per output element and launch: equal runs give equal bits.  Tails are zero-filled operands.
+ * The passes are launches of their own after the moment reduction (the histogram, the chain-group moments) of the same iterate; a sampler without a
+ * sketch launches exactly what it launches without this call.  lmc_sampler_sapg suspends these accumulators with the others.
+ * The call copies probes and centre into the handle.  k = 0 turns the sketch off.  Needs cfg.moments != 0 and count == 0 (else LMC_E_STATE); k outside
+ * 0 .. LMC_MAX_COV_PROBES or NULL probes with k > 0: LMC_E_INVALID.  lmc_sampler_reset_moments zeroes Y, s and Q too. */
+int lmc_sampler_set_cov_sketch(lmc_sampler* s, int32_t k, const float* probes_dev, const float* center_dev);
+/* y_dev: [k*H*W], s_dev: [k], q_dev: [k*k] double (device, nullable); count: kept samples.  A handle without a sketch: LMC_E_INVALID. */
+int lmc_sampler_get_cov_sketch(lmc_sampler* s, double* y_dev, double* s_dev, double* q_dev, uint64_t* count, void* stream);
 /* per-chain energies f(x_c), g(x_c) of the current state (device double [n_chains]) */
 int lmc_sampler_energies(lmc_sampler* s, double* f_out_dev, double* g_out_dev, void* stream);
 /* the noise field xi[n_chains][H][W] the sampler draws at `iteration` (parity rung R3) */

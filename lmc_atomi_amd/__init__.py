@@ -10,12 +10,13 @@ from .proximal import (L1, L2, L21, TV, L2_ncvx_tv, WaveletL1, ProxOperator, fgp
 from .algs import (MYULAResult, MYULASampler, MYMALASampler, MoreauYosidaUnadjustedLangevin, MoreauYosidaMetropolisAdjustedLangevin, ULPDASampler,
                    UnadjustedLangevinPrimalDual, block_mean_var, hist_exceedance, hist_quantiles, mean_var_from_moments, pixel_histogram,
                    set_step_variant, set_cg_tolerance, SKROCKSampler, StabilisedLangevin, skrock_coefficients, skrock_step_bound,
-                   SAPGResult, EstimatePriorWeight, prior_statistic, sapg_dimension, sapg_update, GroupMCSE, group_moments, mcse_from_group_moments)
+                   SAPGResult, EstimatePriorWeight, prior_statistic, sapg_dimension, sapg_update, GroupMCSE, group_moments, mcse_from_group_moments,
+                   CovSketch, cov_sketch, cov_from_sketch, random_probes)
 
 from . import diagnostics, metrics
 from .diagnostics import ChainTrace, chain_probes, ess, split_rhat
 from .metrics import MetricsCallback, mean_squared_error, peak_signal_noise_ratio, signal_noise_ratio
-from .sharding import (allgather_chains, allreduce_group_moments, allreduce_moments, allreduce_sampler_group_moments, allreduce_sampler_block_moments, allreduce_sampler_histogram, allreduce_sampler_moments, chain_shard, posterior_mean_var, rccl_comm,
+from .sharding import (allgather_chains, allreduce_cov_sketch, allreduce_group_moments, allreduce_moments, allreduce_sampler_group_moments, allreduce_sampler_block_moments, allreduce_sampler_histogram, allreduce_sampler_moments, chain_shard, posterior_mean_var, rccl_comm,
                        sharded_myula)
 
 __all__ = [
@@ -29,6 +30,7 @@ __all__ = [
     "pixel_histogram", "hist_quantiles", "hist_exceedance", "allreduce_sampler_histogram",
     "SKROCKSampler", "StabilisedLangevin", "skrock_coefficients", "skrock_step_bound",
     "group_moments", "mcse_from_group_moments", "GroupMCSE", "allreduce_group_moments", "allreduce_sampler_group_moments",
+    "cov_sketch", "cov_from_sketch", "CovSketch", "random_probes", "allreduce_cov_sketch",
     "SAPGResult", "EstimatePriorWeight", "prior_statistic", "sapg_dimension", "sapg_update",
 ]
 __version__ = "0.2.0"

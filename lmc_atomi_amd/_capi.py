@@ -26,6 +26,7 @@ MAX_BLUR = 9
 MAX_TV_ITERS = 64
 MAX_SKROCK_STAGES = 64
 MAX_CHAIN_GROUPS = 64
+MAX_COV_PROBES = 32
 (EPROX_LAPLACE, EPROX_UNCENTERED_LAPLACE, EPROX_GAUSSIAN, EPROX_GEN_GAUSSIAN_4_3, EPROX_GEN_GAUSSIAN_3_2,
  EPROX_GEN_GAUSSIAN_3, EPROX_GEN_GAUSSIAN_4, EPROX_HUBER, EPROX_SMOOTHED_LAPLACE, EPROX_EXP, EPROX_GAMMA,
  EPROX_CHI, EPROX_UNIFORM, EPROX_TRIANGULAR, EPROX_LAPLACE_CONJ) = range(15)
@@ -205,6 +206,10 @@ _SIGNATURES = {
     "lmc_sampler_set_chain_groups": (C.c_int, [_P, C.c_int32]),
     "lmc_sampler_get_group_moments": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64), _P]),
     "lmc_allreduce_group_moments": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_uint64), _P]),
+    "lmc_cov_sketch_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "lmc_cov_sketch": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "lmc_sampler_set_cov_sketch": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "lmc_sampler_get_cov_sketch": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_uint64), _P]),
 }
 RCCL_UNIQUE_ID_BYTES = 128
 VARIANTS = ["auto", "tile", "(removed)", "split", "point", "block", "rows", "pipe", "pipe2"]

@@ -352,6 +352,139 @@ def _group_summaries(smp):
     return r.mcse_mean, r.mcse_var, r.ess, counts
 
 
+MAX_COV_PROBES = _capi.MAX_COV_PROBES
+
+
+def _check_cov_sketch(cov_probes, cov_center, moments, dims):
+    """``None`` or ``(k, probes fp32 [k, H*W], centre fp32 [H*W] or None)`` (host arrays) of the covariance sketch a sampler is asked to keep;
+    raises ``ValueError`` before any device call."""
+    if cov_probes is None:
+        if cov_center is not None:
+            raise ValueError("cov_center without cov_probes: the centre belongs to the covariance sketch")
+        return None
+    H, W = int(dims[0]), int(dims[1])
+    n = H * W
+    P = np.asarray(_host_array(cov_probes), dtype=np.float32)
+    if not ((P.ndim == 3 and P.shape[1:] == (H, W)) or (P.ndim == 2 and P.shape[1] == n)):
+        raise ValueError(f"cov_probes must be [k, {H}, {W}] or [k, {n}], got {tuple(P.shape)}")
+    k = int(P.shape[0])
+    if not 1 <= k <= MAX_COV_PROBES:
+        raise ValueError(f"cov_probes: the number of probes must be 1 .. {MAX_COV_PROBES}, got {k}")
+    P = np.ascontiguousarray(P.reshape(k, n))
+    if not np.isfinite(P).all():
+        raise ValueError("cov_probes must be finite")
+    m = None
+    if cov_center is not None:
+        m = np.asarray(_host_array(cov_center), dtype=np.float32)
+        if m.size != n or m.shape not in ((H, W), (n,)):
+            raise ValueError(f"cov_center must be [{H}, {W}] or [{n}], got {tuple(m.shape)}")
+        m = np.ascontiguousarray(m.reshape(n))
+        if not np.isfinite(m).all():
+            raise ValueError("cov_center must be finite")
+    if not moments:
+        raise ValueError("cov_probes needs moments=True: the covariance sketch is accumulated over the kept samples of the pixel moments")
+    return k, P, m
+
+
+def cov_sketch(x, probes, center=None, out=None):
+    """Covariance sketch of the images ``x`` (``[C, H, W]``) against the probe images ``probes`` (``[k, H, W]`` or ``[k, H*W]``, 1 <= k <= 32) about
+    ``center`` (``[H, W]`` or flat, ``None`` = 0): ``(Y, s, Q)``, float64 on the device, ``Y[k, H, W] = sum_c t_c d_c``, ``s[k] = sum_c t_c``,
+    ``Q[k, k] = sum_c t_c t_c^T`` with ``d_c = x_c - center`` (fp32) and ``t_c = probes . d_c``.  Stateless (``lmc_cov_sketch``); with
+    ``out=(Y, s, Q)`` it ADDS into those tensors and returns them.  No atomics: equal calls give equal bits.  :func:`cov_from_sketch` turns the
+    sums into covariances."""
+    if not (hasattr(x, "shape") and len(x.shape) == 3):
+        raise ValueError("x must be [C, H, W]")
+    Cn, H, W = (int(v) for v in x.shape)
+    k, P, m = _check_cov_sketch(probes, center, True, (H, W))
+    xt = _dev.to_dev(x)
+    P_d = _dev.to_dev(P, xt.device)
+    m_d = None if m is None else _dev.to_dev(m, xt.device)
+    shapes = ((k, H, W), (k,), (k, k))
+    if out is None:
+        out = tuple(torch.zeros(s, dtype=torch.float64, device=xt.device) for s in shapes)
+    elif not (isinstance(out, (tuple, list)) and len(out) == 3 and all(
+            isinstance(t, torch.Tensor) and t.dtype == torch.float64 and tuple(t.shape) == s and t.is_contiguous() and t.device == xt.device
+            for t, s in zip(out, shapes))):
+        raise ValueError(f"out must be three contiguous torch.float64 tensors {shapes} on {xt.device}")
+    nbytes = int(_dev.lib().lmc_cov_sketch_workspace_bytes(Cn, H, W, k))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=xt.device)
+    _dev.run(xt, "lmc_cov_sketch", _dev.ptr(xt), Cn, H, W, k, _dev.ptr(P_d), _dev.ptr(m_d), _dev.ptr(out[0]), _dev.ptr(out[1]), _dev.ptr(out[2]),
+             _dev.ptr(ws))
+    torch.cuda.current_stream(xt.device).synchronize()          # xt, the probes and the workspace may be temporaries
+    return out[0], out[1], out[2]
+
+
+class CovSketch:
+    """What :func:`cov_from_sketch` returns, float64 numpy arrays: ``cov_xt`` ``[k, H, W]`` (the covariance of every pixel with projection j, row j
+    of ``P Sigma``), ``cov_tt`` ``[k, k]`` (``P Sigma P^T``), ``t_mean`` ``[k]`` (the mean projections) and ``n`` (the samples)."""
+
+    def __init__(self, cov_xt, cov_tt, t_mean, n):
+        self.cov_xt, self.cov_tt, self.t_mean, self.n = cov_xt, cov_tt, t_mean, n
+
+    def corr(self, var):
+        """Correlation maps ``[k, H, W]``: ``cov_xt[j] / sqrt(var * cov_tt[j, j])`` with the pixel variance ``var`` (``[H, W]``).  NaN where a
+        variance (of the pixel or of the projection) is 0 or negative -- not a clamp."""
+        v = _host_array(var).astype(np.float64).reshape(self.cov_xt.shape[1:])
+        den = v[None] * np.diag(self.cov_tt).reshape((-1,) + (1,) * v.ndim)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(den > 0, self.cov_xt / np.sqrt(den), np.nan)
+
+    def modes(self, rank, rcond=1e-10):
+        """``(eigenvalues [rank], eigen-images [rank, H, W])`` of the Nystrom approximation ``Sigma ~ cov_xt^T cov_tt^+ cov_xt``, largest first.
+        ``cov_tt`` is symmetrised and decomposed (``eigh``), eigenvalues ``<= rcond * max`` are dropped, ``B = cov_xt^T V w^{-1/2}`` of the kept
+        pairs has ``Sigma ~ B B^T``; its singular values squared and left vectors are returned.  Exact when the rank of the sample covariance is at
+        most the number of probes (Gaussian probes, :func:`random_probes`); otherwise the eigenvalues are UNDERESTIMATED, as Nystrom
+        approximations of a positive semi-definite matrix always are -- read them as lower bounds.  ``ValueError`` if ``rank`` exceeds the number
+        of eigenvalues kept."""
+        k = self.cov_tt.shape[0]
+        w, V = np.linalg.eigh(0.5 * (self.cov_tt + self.cov_tt.T))
+        keep = w > float(rcond) * max(float(w.max()), 0.0)
+        r = int(rank)
+        if r < 1 or r > int(keep.sum()):
+            raise ValueError(f"rank = {r}: the sketch keeps {int(keep.sum())} of {k} directions (rcond = {rcond})")
+        B = self.cov_xt.reshape(k, -1).T @ (V[:, keep] / np.sqrt(w[keep]))
+        U, sv, _ = np.linalg.svd(B, full_matrices=False)
+        return sv[:r] ** 2, np.ascontiguousarray(U[:, :r].T).reshape((r,) + self.cov_xt.shape[1:])
+
+
+def cov_from_sketch(Y, s, Q, n, s1, center=None):
+    """Covariances from the sums of a covariance sketch (:meth:`MYULASampler.cov_sketch`, :func:`cov_sketch`) and the pixel sums ``s1`` of the same
+    ``n`` samples: with ``dbar = s1 / n - center`` and ``tbar = s / n``, a :class:`CovSketch` of ``cov_xt = Y / n - tbar dbar`` -- exactly
+    ``P Sigma``, ``Sigma`` the sample covariance (``np.cov(bias=True)``) of the samples as flat images -- and ``cov_tt = Q / n - tbar tbar^T``
+    -- exactly ``P Sigma P^T``.  ``center`` must be the one the sums were formed with.  float64 on the host.  Without a centre ``cov_xt`` is a
+    difference of terms of size mean^2 and loses digits: form the sums about a pilot-run mean."""
+    Yh, sh, Qh = (_host_array(v).astype(np.float64) for v in (Y, s, Q))
+    n = int(n)
+    if n < 1:
+        raise ValueError("the covariance sketch holds no samples")
+    if Yh.ndim < 2 or sh.shape != (Yh.shape[0],) or Qh.shape != (Yh.shape[0], Yh.shape[0]):
+        raise ValueError("Y must be [k, H, W] (or [k, H*W]), s [k] and Q [k, k]")
+    k = Yh.shape[0]
+    dbar = _host_array(s1).astype(np.float64).reshape(Yh.shape[1:]) / n
+    if center is not None:
+        dbar = dbar - _host_array(center).astype(np.float32).astype(np.float64).reshape(Yh.shape[1:])
+    tbar = sh / n
+    cov_xt = Yh / n - tbar.reshape((k,) + (1,) * (Yh.ndim - 1)) * dbar[None]
+    return CovSketch(cov_xt, Qh / n - np.outer(tbar, tbar), tbar, n)
+
+
+def random_probes(k, dims, seed=0):
+    """``k`` Gaussian random probe images ``[k, H, W]`` (fp32 numpy) from ``numpy.random.default_rng(seed)``: the probes of the Nystrom sketch
+    (:meth:`CovSketch.modes`).  Every rank of a sharded job must use the same ``seed``."""
+    k = int(k)
+    if not 1 <= k <= MAX_COV_PROBES:
+        raise ValueError(f"k must be 1 .. {MAX_COV_PROBES}, got {k}")
+    return default_rng(seed).standard_normal((k, int(dims[0]), int(dims[1]))).astype(np.float32)
+
+
+def _cov_summary(smp, s1):
+    """The :class:`CovSketch` of a sampler's covariance sketch and pixel sums ``s1``; None without one (or without samples)."""
+    if smp.cov_k is None:
+        return None
+    Y, s, Q, n = smp.cov_sketch()
+    return cov_from_sketch(Y, s, Q, n, s1, smp.cov_center) if n else None
+
+
 def _scale_summaries(smp):
     """``({scale: mean}, {scale: std})`` of the block means of every scale the sampler keeps."""
     means, stds = {}, {}
@@ -490,7 +623,7 @@ class MYULASampler:
 
     def __init__(self, proxf, proxg, dims, n_chains=1, tau=None, gamma=0.1, epsg=1.0, seed=0,
                  chain_offset=0, noise="philox", moments=False, burn_in=0, thin=1, device=None, variant=None, tv_warm=None, policy=None,
-                 moment_scales=None, hist_bins=None, hist_range=None, chain_groups=None):
+                 moment_scales=None, hist_bins=None, hist_range=None, chain_groups=None, cov_probes=None, cov_center=None):
         """``variant``: step-kernel variant of THIS sampler ('auto' | 'tile' | 'split' | 'point' | 'block' | 'rows' | 'pipe' | 'pipe2'; None = the
         library default, :func:`set_step_variant`).  ``tv_warm``: carry the TV dual between iterations (see :class:`TV`; None = as
         ``proxg.warm`` says).  ``moment_scales``: block sizes out of (2, 4, 8, 16) whose block sums get second moments of their own over the kept samples
@@ -499,10 +632,15 @@ class MYULASampler:
         ``mean`` and ``var``, and ``(mean - 5 sqrt(var), mean + 5 sqrt(var))`` is then a range whose 62 bins resolve 0.16 standard deviations.
         ``chain_groups=G`` (2 .. 64): the sums of x and x^2 per pixel and chain group over the kept samples, the group of a chain being its global id
         mod G (:meth:`group_moments`, :func:`mcse_from_group_moments`: Monte-Carlo error and ESS maps; needs ``moments=True``).
+        ``cov_probes`` (``[k, H, W]`` or ``[k, H*W]``, k <= 32) with ``cov_center`` (``[H, W]`` or flat, None = 0; best the mean of a pilot run): the
+        covariance sketch over the kept samples -- ``Y = sum t d``, ``s = sum t``, ``Q = sum t t^T`` with ``d = x - cov_center`` and ``t = cov_probes . d``
+        (:meth:`cov_sketch`, :func:`cov_from_sketch`: the covariance of every pixel with every projection, of region fluxes, Nystrom uncertainty modes;
+        needs ``moments=True``).
         Every call on the sampler runs on ``device`` whatever the current device is."""
         scales = _check_moment_scales(moment_scales, moments)
         hist = _check_histogram(hist_bins, hist_range, moments, dims)
         groups = _check_chain_groups(chain_groups, moments)
+        cov = _check_cov_sketch(cov_probes, cov_center, moments, dims)
         if tau is None:
             raise NotImplementedError("tau=None (backtracking) is not implemented by the reference loop either")
         if self._box_refusal is not None:
@@ -551,6 +689,7 @@ class MYULASampler:
         self._set_moment_scales(scales)
         self._set_histogram(hist)
         self._set_chain_groups(groups)
+        self._set_cov_sketch(cov)
 
     _create_fn = "lmc_myula_create"
     _box_refusal = None          # (who, why) of a subclass that has no box-constrained form: raised before a handle exists
@@ -563,7 +702,21 @@ class MYULASampler:
     moment_scales = ()
     hist_bins = hist_lo = hist_scale = None
     chain_groups = None
+    cov_k = cov_probes = cov_center = None
     prior_weight = None
+
+    def _set_cov_sketch(self, cov):
+        """``cov``: None or (k, probes, centre) as :func:`_check_cov_sketch` returns them; the library copies both, the sampler keeps fp32 device
+        copies for :func:`cov_from_sketch`."""
+        if cov is None:
+            return
+        k, P, m = cov
+        P_d = _dev.to_dev(P, self.device).reshape((k,) + self.dims)
+        m_d = None if m is None else _dev.to_dev(m, self.device).reshape(self.dims)
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()
+            _capi.check(_dev.lib().lmc_sampler_set_cov_sketch(self._h, k, _dev.ptr(P_d), _dev.ptr(m_d)))
+        self.cov_k, self.cov_probes, self.cov_center = k, P_d, m_d
 
     def _set_chain_groups(self, groups):
         if groups is None:
@@ -807,6 +960,20 @@ class MYULASampler:
         Monte-Carlo error of the mean and the variance and the effective sample size, per pixel."""
         return self._group_call("lmc_sampler_get_group_moments")
 
+    def cov_sketch(self):
+        """(Y ``[k, H, W]``, s ``[k]``, Q ``[k, k]`` f64, n): the sums of the covariance sketch over the kept samples (``cov_probes=``) and the number
+        of samples, which is the count of :meth:`moments`.  :func:`cov_from_sketch` turns them, with ``moments()[0]`` and ``cov_center``, into
+        covariances."""
+        if self.cov_k is None:
+            raise ValueError("the sampler keeps no covariance sketch (cov_probes=)")
+        k = self.cov_k
+        Y = torch.empty((k,) + self.dims, dtype=torch.float64, device=self.device)
+        sv = torch.empty(k, dtype=torch.float64, device=self.device)
+        Q = torch.empty((k, k), dtype=torch.float64, device=self.device)
+        cnt = C.c_uint64()
+        _capi.check(_dev.lib().lmc_sampler_get_cov_sketch(self._h, _dev.ptr(Y), _dev.ptr(sv), _dev.ptr(Q), C.byref(cnt), _dev.stream_ptr(self.device)))
+        return Y, sv, Q, int(cnt.value)
+
     def allreduce_group_moments(self, rccl_comm):
         """Job-wide :meth:`group_moments`: ONE ``ncclAllReduce`` of the packed sums and counts through the C ABI (``lmc_allreduce_group_moments``)."""
         comm = rccl_comm if isinstance(rccl_comm, C.c_void_p) else C.c_void_p(int(rccl_comm or 0))
@@ -831,12 +998,13 @@ class ULPDASampler(MYULASampler):
 
     def __init__(self, proxf, proxg, A, dims, n_chains=1, tau=None, mu=None, theta=1.0, gfirst=True, z=None, seed=0,
                  chain_offset=0, noise="philox", moments=False, burn_in=0, thin=1, device=None, variant=None, implicit_tol=None,
-                 moment_scales=None, hist_bins=None, hist_range=None, chain_groups=None):
+                 moment_scales=None, hist_bins=None, hist_range=None, chain_groups=None, cov_probes=None, cov_center=None):
         from .operators import Gradient
         from .proximal import L1, L21
         scales = _check_moment_scales(moment_scales, moments)
         hist = _check_histogram(hist_bins, hist_range, moments, dims)
         groups = _check_chain_groups(chain_groups, moments)
+        cov = _check_cov_sketch(cov_probes, cov_center, moments, dims)
         if not isinstance(A, Gradient):
             raise NotImplementedError("ULPDA on the GPU supports A = Gradient (the reference's operator, prox_lmc_deconv.py:98)")
         if getattr(proxg, "bounds", None) is not None:
@@ -884,6 +1052,7 @@ class ULPDASampler(MYULASampler):
         self._set_moment_scales(scales)
         self._set_histogram(hist)
         self._set_chain_groups(groups)
+        self._set_cov_sketch(cov)
 
     def set_steps(self, tau, mu):
         _capi.check(_dev.lib().lmc_sampler_set_steps(self._h, float(tau), float(mu)))
@@ -907,14 +1076,14 @@ class ULPDASampler(MYULASampler):
 def UnadjustedLangevinPrimalDual(proxf, proxg, A, x0, tau, mu, y0=None, z=None, theta=1., niter=10, seed=0, gfirst=True,
                                  callback=None, callbacky=False, returny=False, show=False, *, n_chains=None, dims=None,
                                  rng="philox", chain_offset=0, burn_in=0, thin=1, device=None, diagnostics=None, moment_scales=None,
-                                 hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95), chain_groups=None):
+                                 hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95), chain_groups=None, cov_probes=None, cov_center=None):
     r"""Unadjusted Langevin Primal-Dual algorithm (ULPDA) -- drop-in for algs.py:295-474.
 
     Reference form (``n_chains is None``): one chain, returns ``np.ndarray (niter, n)`` (and the duals ``(niter, 2n)`` with
     ``returny``), ``callback(x)`` / ``callback(x, y)`` every iteration, ``tau`` / ``mu`` scalars or per-iteration arrays
     (algs.py:402-408).  ``rng='pcg64'`` injects the reference's noise stream.  Many-chain form: :class:`MYULAResult`
     (``diagnostics=(ph, pw)`` or ``True``: split R-hat / ESS across chains as in :func:`MoreauYosidaUnadjustedLangevin`;
-    ``moment_scales``, ``hist_bins`` / ``hist_range`` / ``quantiles``, ``chain_groups``: as there).
+    ``moment_scales``, ``hist_bins`` / ``hist_range`` / ``quantiles``, ``chain_groups``, ``cov_probes`` / ``cov_center``: as there).
     """
     if dims is None:
         dims = getattr(A, "dims", None) or getattr(proxf, "dims", None)
@@ -934,12 +1103,15 @@ def UnadjustedLangevinPrimalDual(proxf, proxg, A, x0, tau, mu, y0=None, z=None, 
     if chain_groups is not None and not many:
         raise ValueError("chain_groups belongs to the many-chain form (n_chains=C): one chain has no groups to compare")
     _check_chain_groups(chain_groups, True, C_)
+    if (cov_probes is not None or cov_center is not None) and not many:
+        raise ValueError("cov_probes / cov_center belong to the many-chain form (n_chains=C): the reference form keeps every iterate instead")
+    _check_cov_sketch(cov_probes, cov_center, True, dims)
     taus = np.full(niter, tau, dtype=np.float64) if np.isscalar(tau) else np.asarray(tau, dtype=np.float64)
     mus = np.full(niter, mu, dtype=np.float64) if np.isscalar(mu) else np.asarray(mu, dtype=np.float64)
     smp = ULPDASampler(proxf, proxg, A, dims, n_chains=C_, tau=taus[0], mu=mus[0], theta=theta, gfirst=gfirst, z=z,
                        seed=seed, chain_offset=chain_offset, noise="injected" if rng == "pcg64" else "philox",
                        moments=many, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
-                       hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups)
+                       hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups, cov_probes=cov_probes, cov_center=cov_center)
     try:
         smp.set_state(x0)
         if y0 is not None:
@@ -997,7 +1169,7 @@ def UnadjustedLangevinPrimalDual(proxf, proxg, A, x0, tau, mu, y0=None, z=None, 
         diag = tracer.summary() if tracer is not None and len(tracer) else None
         return MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, diagnostics=diag,
                            trace=tracer.trace() if diag is not None else None, scale_mean=scale_mean, scale_std=scale_std,
-                           hist=_hist_summaries(smp, quantiles), groups=_group_summaries(smp))
+                           hist=_hist_summaries(smp, quantiles), groups=_group_summaries(smp), cov=_cov_summary(smp, s1))
     finally:
         smp.close()
 
@@ -1012,11 +1184,13 @@ def mean_var_from_moments(s1, s2, count):
 class MYULAResult:
     """Return value of the many-chain form of :func:`MoreauYosidaUnadjustedLangevin`."""
 
-    def __init__(self, state, mean, var, count, energy_f, energy_g, elapsed, diagnostics=None, trace=None, scale_mean=None, scale_std=None, hist=None, groups=None):
+    def __init__(self, state, mean, var, count, energy_f, energy_g, elapsed, diagnostics=None, trace=None, scale_mean=None, scale_std=None, hist=None, groups=None, cov=None):
         self.state, self.mean, self.var, self.count = state, mean, var, count
         # chain_groups: Monte-Carlo standard error of mean and var and the effective sample size, [H, W] float64 each (mcse_from_group_moments), and the
         # samples per chain group [G] int64; None when not asked
         self.mcse_mean, self.mcse_var, self.ess, self.group_counts = groups if groups is not None else (None, None, None, None)
+        # cov_probes: the covariances of the sketch (CovSketch: cov_xt, cov_tt, t_mean, n; cov_from_sketch); None when not asked
+        self.cov_sketch = cov
         # hist_bins / hist_range: the pixel histogram [B + 2, H, W] int64 with its lo and scale (None when not asked), and {q: tensor [H, W]} of
         # the quantiles asked for (hist_quantiles; empty without a histogram)
         self.hist, self.hist_lo, self.hist_scale, self.quantiles = hist if hist is not None else (None, None, None, {})
@@ -1029,7 +1203,7 @@ class MYULAResult:
 def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1., niter=10, seed=0,
                                    callback=None, show=False, *, n_chains=None, dims=None, rng="philox",
                                    chain_offset=0, burn_in=0, thin=1, device=None, diagnostics=None, moment_scales=None,
-                                   hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95), chain_groups=None):
+                                   hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95), chain_groups=None, cov_probes=None, cov_center=None):
     r"""Moreau--Yosida Unadjusted Langevin algorithm (MYULA) -- drop-in for algs.py:477-587.
 
     .. math::
@@ -1056,6 +1230,11 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
     pixel-wise Monte-Carlo standard errors ``result.mcse_mean`` and ``result.mcse_var`` of ``result.mean`` and ``result.var``, the effective sample size
     ``result.ess`` and the samples per group ``result.group_counts`` (:func:`mcse_from_group_moments`: the scatter of the group means, which includes
     the autocorrelation of the chains; one pixel of these maps is precise to sqrt(2 / (G - 1)), 25 % at G = 32).
+    ``cov_probes=P`` (``[k, H, W]``, k <= 32; region indicators, or :func:`random_probes`) with ``cov_center=m`` (``[H, W]``, best the mean of a pilot run;
+    None = 0, which costs digits) keeps the covariance sketch of the kept samples and returns ``result.cov_sketch``, a :class:`CovSketch`: ``cov_xt[j]`` the
+    covariance of every pixel with the projection on probe j, ``cov_tt`` the covariance matrix of the projections (of the region fluxes), ``.corr(result.var)``
+    the correlation maps and ``.modes(r)`` the leading eigenvalues and eigen-images of the Nystrom approximation of the posterior covariance (exact when its
+    rank is at most k, lower bounds otherwise).
     """
     if dims is None:
         dims = getattr(proxf, "dims", None) or getattr(proxg, "dims", None)
@@ -1075,10 +1254,13 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
     if chain_groups is not None and not many:
         raise ValueError("chain_groups belongs to the many-chain form (n_chains=C): one chain has no groups to compare")
     _check_chain_groups(chain_groups, True, C_)
+    if (cov_probes is not None or cov_center is not None) and not many:
+        raise ValueError("cov_probes / cov_center belong to the many-chain form (n_chains=C): the reference form keeps every iterate instead")
+    _check_cov_sketch(cov_probes, cov_center, True, dims)
     smp = MYULASampler(proxf, proxg, dims, n_chains=C_, tau=tau, gamma=gamma, epsg=epsg, seed=seed,
                        chain_offset=chain_offset, noise="injected" if rng == "pcg64" else "philox",
                        moments=many, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
-                       hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups)
+                       hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups, cov_probes=cov_probes, cov_center=cov_center)
     try:
         smp.set_state(x0)
         tstart = time.time()
@@ -1144,7 +1326,7 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
         diag = tracer.summary() if tracer is not None and len(tracer) else None
         return MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, diagnostics=diag,
                            trace=tracer.trace() if diag is not None else None, scale_mean=scale_mean, scale_std=scale_std,
-                           hist=_hist_summaries(smp, quantiles), groups=_group_summaries(smp))
+                           hist=_hist_summaries(smp, quantiles), groups=_group_summaries(smp), cov=_cov_summary(smp, s1))
     finally:
         smp.close()
 
@@ -1174,19 +1356,20 @@ class MYMALASampler(MYULASampler):
 
 def MoreauYosidaMetropolisAdjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1., niter=10, seed=0, callback=None, *,
                                            n_chains=1, dims=None, chain_offset=0, burn_in=0, thin=1, device=None, moment_scales=None,
-                                           hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95), chain_groups=None):
+                                           hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95), chain_groups=None, cov_probes=None, cov_center=None):
     """MYMALA at image scale for ``n_chains`` chains (the accept / reject of prox_lmc.py:134-158 around the MYULA move of
     algs.py:569): returns a :class:`MYULAResult` with two extra attributes, ``accepted`` (per-chain counts) and
     ``acceptance_rate``.  ``callback(state)`` after every iteration if given.  ``moment_scales``, ``hist_bins`` / ``hist_range`` /
-    ``quantiles``, ``chain_groups``: as in :func:`MoreauYosidaUnadjustedLangevin`."""
+    ``quantiles``, ``chain_groups``, ``cov_probes`` / ``cov_center``: as in :func:`MoreauYosidaUnadjustedLangevin`."""
     if dims is None:
         dims = getattr(proxf, "dims", None) or getattr(proxg, "dims", None)
     if dims is None:
         raise ValueError("image shape unknown: pass dims=(ny, nx)")
     _check_chain_groups(chain_groups, True, n_chains)
+    _check_cov_sketch(cov_probes, cov_center, True, dims)
     smp = MYMALASampler(proxf, proxg, dims, n_chains=int(n_chains), tau=tau, gamma=gamma, epsg=epsg, seed=seed,
                         chain_offset=chain_offset, moments=True, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
-                        hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups)
+                        hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups, cov_probes=cov_probes, cov_center=cov_center)
     try:
         smp.set_state(x0)
         tstart = time.time()
@@ -1204,7 +1387,7 @@ def MoreauYosidaMetropolisAdjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1,
         mean, var = mean_var_from_moments(s1, s2, max(cnt, 1))
         scale_mean, scale_std = _scale_summaries(smp)
         res = MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, scale_mean=scale_mean, scale_std=scale_std,
-                          hist=_hist_summaries(smp, quantiles), groups=_group_summaries(smp))
+                          hist=_hist_summaries(smp, quantiles), groups=_group_summaries(smp), cov=_cov_summary(smp, s1))
         res.accepted = acc
         res.acceptance_rate = acc.double() / max(niter, 1)
         return res
@@ -1248,6 +1431,7 @@ class SKROCKSampler(MYULASampler):
 
     def __init__(self, proxf, proxg, dims, n_stages=10, eta=0.05, **kw):
         _check_chain_groups(kw.get("chain_groups"), kw.get("moments", False))      # before anything touches the proxes
+        _check_cov_sketch(kw.get("cov_probes"), kw.get("cov_center"), kw.get("moments", False), dims)
         prior = _prior_descriptor(proxg)
         _refuse_box(prior, "SK-ROCK", "its stability bound is derived for the unconstrained Moreau-Yosida envelope; use MYULA")
         if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
@@ -1266,19 +1450,20 @@ class SKROCKSampler(MYULASampler):
 
 def StabilisedLangevin(proxf, proxg, x0, tau, gamma=.1, epsg=1., niter=10, n_stages=10, eta=0.05, seed=0, callback=None, *,
                        n_chains=1, dims=None, chain_offset=0, burn_in=0, thin=1, device=None, moment_scales=None,
-                       hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95), chain_groups=None):
+                       hist_bins=None, hist_range=None, quantiles=(0.05, 0.5, 0.95), chain_groups=None, cov_probes=None, cov_center=None):
     """SK-ROCK at image scale for ``n_chains`` chains (:class:`SKROCKSampler`): ``niter`` iterations of ``n_stages`` drift evaluations each at
     step ``tau`` (up to :func:`skrock_step_bound`).  Returns a :class:`MYULAResult` with two extra attributes, ``n_stages`` and
     ``gradient_evaluations = niter * n_stages``.  ``callback(state)`` after every iteration if given.  ``moment_scales``, ``hist_bins`` /
-    ``hist_range`` / ``quantiles``, ``chain_groups``: as in :func:`MoreauYosidaUnadjustedLangevin`."""
+    ``hist_range`` / ``quantiles``, ``chain_groups``, ``cov_probes`` / ``cov_center``: as in :func:`MoreauYosidaUnadjustedLangevin`."""
     if dims is None:
         dims = getattr(proxf, "dims", None) or getattr(proxg, "dims", None)
     if dims is None:
         raise ValueError("image shape unknown: pass dims=(ny, nx)")
     _check_chain_groups(chain_groups, True, n_chains)
+    _check_cov_sketch(cov_probes, cov_center, True, dims)
     smp = SKROCKSampler(proxf, proxg, dims, n_stages=n_stages, eta=eta, n_chains=int(n_chains), tau=tau, gamma=gamma, epsg=epsg, seed=seed,
                         chain_offset=chain_offset, moments=True, burn_in=burn_in, thin=thin, device=device, moment_scales=moment_scales,
-                        hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups)
+                        hist_bins=hist_bins, hist_range=hist_range, chain_groups=chain_groups, cov_probes=cov_probes, cov_center=cov_center)
     try:
         smp.set_state(x0)
         tstart = time.time()
@@ -1295,7 +1480,7 @@ def StabilisedLangevin(proxf, proxg, x0, tau, gamma=.1, epsg=1., niter=10, n_sta
         mean, var = mean_var_from_moments(s1, s2, max(cnt, 1))
         scale_mean, scale_std = _scale_summaries(smp)
         res = MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart, scale_mean=scale_mean, scale_std=scale_std,
-                          hist=_hist_summaries(smp, quantiles), groups=_group_summaries(smp))
+                          hist=_hist_summaries(smp, quantiles), groups=_group_summaries(smp), cov=_cov_summary(smp, s1))
         res.n_stages = smp.n_stages
         res.gradient_evaluations = int(niter) * smp.n_stages
         return res

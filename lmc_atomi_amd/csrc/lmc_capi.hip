@@ -294,6 +294,17 @@ int lmc_group_moments(const float* x_dev, int64_t C, int64_t chain_offset, int32
   return LMC_OK;
 }
 
+size_t lmc_cov_sketch_workspace_bytes(int64_t C, int32_t H, int32_t W, int32_t k) { return lmc::cov_sketch_workspace_bytes(C, H, W, k); }
+
+int lmc_cov_sketch(const float* x_dev, int64_t C, int32_t H, int32_t W, int32_t k, const float* probes_dev, const float* center_dev, double* y_dev,
+                   double* s_dev, double* q_dev, void* workspace_dev, void* stream) {
+  if (!x_dev || !probes_dev || !y_dev || !s_dev || !q_dev || !workspace_dev || C < 1 || H < 1 || W < 1) return fail(LMC_E_INVALID, "bad arguments");
+  if (k < 1 || k > LMC_MAX_COV_PROBES) return fail(LMC_E_INVALID, "k must be 1 .. %d (got %d)", LMC_MAX_COV_PROBES, k);
+  if (reinterpret_cast<uintptr_t>(workspace_dev) & 15) return fail(LMC_E_INVALID, "the workspace must be 16-byte aligned");
+  HIP_TRY(lmc::launch_cov_sketch(x_dev, C, H, W, k, probes_dev, center_dev, y_dev, s_dev, q_dev, workspace_dev, S(stream)));
+  return LMC_OK;
+}
+
 int lmc_dual_project(const float* y_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, float radius,
                      int32_t isotropic, void* stream) {
   if (!y_dev || !out_dev) return fail(LMC_E_INVALID, "NULL pointer");

@@ -252,11 +252,26 @@ struct lmc_sampler {
   int n_groups = 0;
   double* grp = nullptr;
   double* grp_packed = nullptr;                // [2 n_groups H W + n_groups]: the send / receive buffer of lmc_allreduce_group_moments
-  // the launches that follow the moment reduction of a kept iterate: the histogram, then the chain-group moments (neither has a paced twin: beside
-  // a step kernel they are the in-line forms on the side stream)
+  // covariance sketch (lmc_sampler_set_cov_sketch): cov = {Y [cov_k][H][W], s [cov_k], Q [cov_k][cov_k]} in one buffer, NULL = off; cov_probes
+  // [cov_k][H][W] and cov_center [H][W] (NULL = 0) are the handle's copies, cov_ws the workspace of lmc_cov_sketch.hip
+  int cov_k = 0;
+  double* cov = nullptr;
+  float* cov_probes = nullptr;
+  float* cov_center = nullptr;
+  void* cov_ws = nullptr;
+  // the launches that follow the moment reduction of a kept iterate: the histogram, the chain-group moments, then the covariance sketch (none has a
+  // paced twin: beside a step kernel they are the in-line forms on the side stream).
+  // ONE workspace (T and the slab partials of the sketch) per handle is enough: a handle never has reduce_more in flight on two streams at once.
+  // The side stream runs its batches in order, both iterates of a pair launch (x_mid and the result) go to the same stream one after the other,
+  // and an in-line reduction on the caller's stream first joins every pending side batch (SideMoments::keep) -- the rule the shared accumulators
+  // s1 / s2 already impose.
   hipError_t reduce_more(hipError_t e, const float* x, hipStream_t st) {
     if (e == hipSuccess && hist) e = lmc::launch_pixel_hist(x, C, prob.H, prob.W, hist_bins, hist_lo, hist_scale, hist, st);
     if (e == hipSuccess && grp) e = lmc::launch_group_moments(x, C, chain_offset, prob.H, prob.W, n_groups, grp, grp + (size_t)n_groups * prob.H * prob.W, st);
+    if (e == hipSuccess && cov) {
+      const size_t ny = (size_t)cov_k * prob.H * prob.W;
+      e = lmc::launch_cov_sketch(x, C, prob.H, prob.W, cov_k, cov_probes, cov_center, cov, cov + ny, cov + ny + cov_k, cov_ws, st);
+    }
     return e;
   }
   // the kept iterate x into the accumulators: the fused multi-scale reduction when scales are enabled, else exactly the launches of before;

@@ -53,6 +53,12 @@ hipError_t launch_pixel_hist(const float* x, int64_t C, int H, int W, int B, con
 // chain-group moments (lmc_group_moments.hip): A[G][H][W] += sum x, B[G][H][W] += sum x^2 over the chains of every group of x[C][H][W], the group of
 // chain c = (chain_offset + c) mod G; float64, one owner per (group, pixel) and launch, no atomics
 hipError_t launch_group_moments(const float* x, int64_t C, int64_t chain_offset, int H, int W, int G, double* A, double* B, hipStream_t st);
+// covariance sketch (lmc_cov_sketch.hip): with d_c = x_c - m and t_c[j] = <P_j, d_c>, Y[k][H][W] += sum_c t_c[j] d_c, s[k] += sum_c t_c[j],
+// Q[k][k] += sum_c t_c[j] t_c[l]; float64 accumulators, fp32-input MFMA passes, one owner per element and launch, no atomics.  m may be NULL (0);
+// ws: cov_sketch_workspace_bytes(C, H, W, k) bytes, 16-byte aligned (0 bytes = bad arguments)
+size_t cov_sketch_workspace_bytes(int64_t C, int H, int W, int k);
+hipError_t launch_cov_sketch(const float* x, int64_t C, int H, int W, int k, const float* P, const float* m, double* Y, double* s, double* Q, void* ws,
+                             hipStream_t st);
 hipError_t launch_energies(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, double* g_out,
                            hipStream_t st);
 // ADDS the Poisson data term's value to f_out (zeroed by launch_energies): E.data_kind = the operator's kind, E.y = [2][H][W] counts, background

@@ -200,6 +200,17 @@ static void release_chain_groups(lmc_sampler* s) {
   s->n_groups = 0;
 }
 
+static void release_cov_sketch(lmc_sampler* s) {
+  if (s->cov) (void)hipFree(s->cov);
+  if (s->cov_probes) (void)hipFree(s->cov_probes);
+  if (s->cov_center) (void)hipFree(s->cov_center);
+  if (s->cov_ws) (void)hipFree(s->cov_ws);
+  s->cov = nullptr;
+  s->cov_probes = s->cov_center = nullptr;
+  s->cov_ws = nullptr;
+  s->cov_k = 0;
+}
+
 void lmc_sampler_destroy(lmc_sampler* s) {
   if (!s) return;
   DeviceGuard dg(s->device);
@@ -226,6 +237,7 @@ void lmc_sampler_destroy(lmc_sampler* s) {
   if (s->sapg_ev) (void)hipEventDestroy(s->sapg_ev);
   release_histogram(s);
   release_chain_groups(s);
+  release_cov_sketch(s);
   for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
   if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }
   for (hipEvent_t e : s->side_ev) if (e) (void)hipEventDestroy(e);
@@ -1002,6 +1014,7 @@ int lmc_sampler_reset_moments(lmc_sampler* s, void* stream) {
   if (s->bs2) HIP_TRY(hipMemsetAsync(s->bs2, 0, sizeof(double) * s->bs2_count, S(stream)));
   if (s->hist) HIP_TRY(hipMemsetAsync(s->hist, 0, sizeof(unsigned long long) * (size_t)(s->hist_bins + 2) * s->prob.H * s->prob.W, S(stream)));
   if (s->grp) HIP_TRY(hipMemsetAsync(s->grp, 0, sizeof(double) * 2 * (size_t)s->n_groups * s->prob.H * s->prob.W, S(stream)));
+  if (s->cov) HIP_TRY(hipMemsetAsync(s->cov, 0, sizeof(double) * ((size_t)s->cov_k * s->prob.H * s->prob.W + s->cov_k + (size_t)s->cov_k * s->cov_k), S(stream)));
   s->count = 0;
   return LMC_OK;
 }
@@ -1128,6 +1141,47 @@ int lmc_sampler_get_group_moments(lmc_sampler* s, double* sum_dev, double* sumsq
   if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, s->grp + n, sizeof(double) * n, hipMemcpyDeviceToDevice, S(stream)));
   HIP_TRY(hipStreamSynchronize(S(stream)));
   if (counts_host) group_counts(s, counts_host);
+  return LMC_OK;
+}
+
+// ---- covariance sketch: Y [k][H][W], s [k], Q [k][k] of the kept samples against k probe images (lmc_cov_sketch.hip) ----
+int lmc_sampler_set_cov_sketch(lmc_sampler* s, int32_t k, const float* probes_dev, const float* center_dev) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (k < 0 || k > LMC_MAX_COV_PROBES) return fail(LMC_E_INVALID, "k must be 0 .. %d (got %d)", LMC_MAX_COV_PROBES, k);
+  if (k > 0 && !probes_dev) return fail(LMC_E_INVALID, "NULL probe array with k > 0");
+  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
+  if (s->count != 0) return fail(LMC_E_STATE, "the covariance sketch changes only while the accumulators are empty (after create or lmc_sampler_reset_moments)");
+  HIP_TRY(hipDeviceSynchronize());     // nothing of an earlier sketch is in flight when its buffers go
+  release_cov_sketch(s);
+  if (!k) return LMC_OK;
+  const size_t img = (size_t)s->prob.H * s->prob.W, nd = (size_t)k * img + k + (size_t)k * k;
+  hipError_t e = hipMalloc(&s->cov, sizeof(double) * nd);
+  if (e == hipSuccess) e = hipMalloc(&s->cov_probes, sizeof(float) * k * img);
+  if (e == hipSuccess && center_dev) e = hipMalloc(&s->cov_center, sizeof(float) * img);
+  if (e == hipSuccess) e = hipMalloc(&s->cov_ws, lmc::cov_sketch_workspace_bytes(s->C, s->prob.H, s->prob.W, k));
+  if (e == hipSuccess) e = hipMemset(s->cov, 0, sizeof(double) * nd);
+  if (e == hipSuccess) e = hipMemcpy(s->cov_probes, probes_dev, sizeof(float) * k * img, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess && center_dev) e = hipMemcpy(s->cov_center, center_dev, sizeof(float) * img, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    release_cov_sketch(s);
+    return fail(e == hipErrorOutOfMemory ? LMC_E_NOMEM : LMC_E_HIP, "covariance-sketch allocation failed: %s", hipGetErrorString(e));
+  }
+  s->cov_k = k;
+  return LMC_OK;
+}
+
+int lmc_sampler_get_cov_sketch(lmc_sampler* s, double* y_dev, double* s_dev, double* q_dev, uint64_t* count, void* stream) {
+  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
+  DeviceGuard dg(s->device);
+  if (!s->cov) return fail(LMC_E_INVALID, "the sampler has no covariance sketch (lmc_sampler_set_cov_sketch)");
+  const size_t k = (size_t)s->cov_k, ny = k * s->prob.H * s->prob.W;
+  if (y_dev) HIP_TRY(hipMemcpyAsync(y_dev, s->cov, sizeof(double) * ny, hipMemcpyDeviceToDevice, S(stream)));
+  if (s_dev) HIP_TRY(hipMemcpyAsync(s_dev, s->cov + ny, sizeof(double) * k, hipMemcpyDeviceToDevice, S(stream)));
+  if (q_dev) HIP_TRY(hipMemcpyAsync(q_dev, s->cov + ny + k, sizeof(double) * k * k, hipMemcpyDeviceToDevice, S(stream)));
+  HIP_TRY(hipStreamSynchronize(S(stream)));
+  if (count) *count = s->count;
   return LMC_OK;
 }
 

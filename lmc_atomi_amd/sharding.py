@@ -160,6 +160,26 @@ def allreduce_sampler_group_moments(smp, group=None):
     return allreduce_group_moments(*smp.group_moments(), group)
 
 
+def allreduce_cov_sketch(Y, s, Q, n, group=None):
+    """Sum the sums of a covariance sketch (:meth:`MYULASampler.cov_sketch`: ``Y`` ``[k, H, W]``, ``s`` ``[k]``, ``Q`` ``[k, k]`` float64, ``n`` the
+    samples) over the ranks of ``group``: the three arrays in one packed float64 buffer, the count as an integer (exact).  The sums of chains on
+    different ranks add up to the sums of all chains ONLY IF probes and centre are equal on every rank -- same arrays, same
+    :func:`lmc_atomi_amd.random_probes` seed; nothing here can check that.  The identity without a process group.  Returns (Y, s, Q) on the device
+    they came from and the job-wide count; :func:`lmc_atomi_amd.cov_from_sketch` wants the job-wide ``s1`` (:func:`allreduce_moments`) with them."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return Y, s, Q, int(n)
+    nccl = dist.get_backend(group) == "nccl"
+    dev = Y.device if nccl else torch.device("cpu")
+    packed = torch.cat([t.detach().reshape(-1).to(dev, torch.float64) for t in (Y, s, Q)])
+    dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
+    cnt = torch.tensor([int(n)], dtype=torch.int64, device=dev)
+    dist.all_reduce(cnt, op=dist.ReduceOp.SUM, group=group)
+    packed = packed.to(Y.device)
+    ny, ns = Y.numel(), s.numel()
+    return packed[:ny].reshape(Y.shape), packed[ny:ny + ns].reshape(s.shape), packed[ny + ns:].reshape(Q.shape), int(cnt.item())
+
+
 def allgather_chains(t: torch.Tensor, dim: int = 1, group=None):
     """Concatenate per-rank tensors along their chain dimension in rank order (= global chain order under
     :func:`chain_shard`); ranks may own different numbers of chains.  Used for the diagnostics trace ``[T, C_rank, Q]``
