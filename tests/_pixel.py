@@ -312,15 +312,23 @@ class Stepper:
         else:
             raise ValueError(c.prior)
 
-    def step(self, x, xi):
+    def _step(self, x, tau, xi):
         c, m = self.c, self.m
         x, xi = np.asarray(x, dtype=self.dtype), np.asarray(xi, dtype=self.dtype)
         if self.standard:
-            out = O.myula_step(x, self.y, self.h, m.offset, m.sigma_f, m.tau, m.gamma, self.prior, xi, mask=self.mask)
+            out = O.myula_step(x, self.y, self.h, m.offset, m.sigma_f, tau, m.gamma, self.prior, xi, mask=self.mask)
         else:
-            out = P.myula_step(self.pf, self.pg, x, m.tau, m.gamma, xi, dtype=self.dtype)
+            out = P.myula_step(self.pf, self.pg, x, tau, m.gamma, xi, dtype=self.dtype)
         assert out.dtype == self.dtype, (case_id(c), out.dtype)
         return out
+
+    def step(self, x, xi):
+        return self._step(x, self.m.tau, xi)
+
+    def advance(self, x, t):
+        """v + t drift(v), drift(v) = -grad f(v) - (v - prox(v)) / gamma: the checker's step with tau = t and xi = 0 (what the stages of SK-ROCK are made
+        of; tests/_skrock_pixel.py)."""
+        return self._step(x, t, 0.0)
 
     def prox(self, x, t):
         return O.tv_prox_fgp(np.asarray(x, dtype=self.dtype), weight(self.c) * t, self.c.K)
