@@ -3,13 +3,15 @@
 //   lmc_problem.hip     lmc_problem -> Problem, StepArgs of an update, the step-kernel dispatch, the library defaults
 //   lmc_solve.hip       the implicit step (I + ts H^T H) u = rhs: Chebyshev, CG
 //   lmc_tv_exit.hip     the early exits of the TV prox, the ME-TV inner prox and envelope
-//   lmc_sampler.hip     the MYULA, MYMALA, SK-ROCK and ULPDA samplers
-//   lmc_rccl.hip        the dlopen'd RCCL and the moment all-reduce
+//   lmc_sampler.hip     the MYULA, MYMALA, SK-ROCK and ULPDA samplers: create / destroy, state, the step loops
+//   lmc_accum.hip       the accumulators over the kept samples (lmc_accum.h): their reductions and their set / get / reset entry points
+//   lmc_rccl.hip        the dlopen'd RCCL and the all-reduces of the accumulators
 #pragma once
 #include <cmath>
 #include <string>
 #include <vector>
 
+#include "lmc_accum.h"
 #include "lmc_launch.h"
 
 namespace lmc::host {
@@ -229,59 +231,12 @@ struct lmc_sampler {
   int noise_mode = 0;
   int moments = 0, burn_in = 0, thin = 1;
   int64_t iteration = 0;
-  uint64_t count = 0;
   float* x[2] = {nullptr, nullptr};
   float* xspare = nullptr;    // third state array of the two-iterations-per-launch MYULA path (allocated at its first use)
   // kept iterates in between of pair launches whose reductions run on the side stream: arrays of their own, alternating by launch
   float* xmid[2] = {nullptr, nullptr};
   int cur = 0;
-  double* s1 = nullptr;
-  double* s2 = nullptr;
-  double* packed = nullptr;              // [2 H W + 1]: the send / receive buffer of lmc_allreduce_moments and lmc_allreduce_block_moments
-  // multi-scale moments (lmc_sampler_set_moment_scales): one packed buffer of the sum b^2 arrays of the enabled scales; scales.s2[i] points into it
-  double* bs2 = nullptr;
-  size_t bs2_count = 0;                  // doubles in bs2
-  lmc::BlockScales scales{};
-  // pixel histograms (lmc_sampler_set_histogram): hist = counts [hist_bins + 2][H][W], NULL = off; hist_lo / hist_scale [H][W] are the handle's copies
-  int hist_bins = 0;
-  unsigned long long* hist = nullptr;
-  float* hist_lo = nullptr;
-  float* hist_scale = nullptr;
-  unsigned long long* hist_packed = nullptr;   // [(hist_bins + 2) H W + 1]: the send / receive buffer of lmc_allreduce_histogram
-  // chain-group moments (lmc_sampler_set_chain_groups): grp = {A [n_groups][H][W], B [n_groups][H][W]} in one buffer, NULL = off
-  int n_groups = 0;
-  double* grp = nullptr;
-  double* grp_packed = nullptr;                // [2 n_groups H W + n_groups]: the send / receive buffer of lmc_allreduce_group_moments
-  // covariance sketch (lmc_sampler_set_cov_sketch): cov = {Y [cov_k][H][W], s [cov_k], Q [cov_k][cov_k]} in one buffer, NULL = off; cov_probes
-  // [cov_k][H][W] and cov_center [H][W] (NULL = 0) are the handle's copies, cov_ws the workspace of lmc_cov_sketch.hip
-  int cov_k = 0;
-  double* cov = nullptr;
-  float* cov_probes = nullptr;
-  float* cov_center = nullptr;
-  void* cov_ws = nullptr;
-  // the launches that follow the moment reduction of a kept iterate: the histogram, the chain-group moments, then the covariance sketch (none has a
-  // paced twin: beside a step kernel they are the in-line forms on the side stream).
-  // ONE workspace (T and the slab partials of the sketch) per handle is enough: a handle never has reduce_more in flight on two streams at once.
-  // The side stream runs its batches in order, both iterates of a pair launch (x_mid and the result) go to the same stream one after the other,
-  // and an in-line reduction on the caller's stream first joins every pending side batch (SideMoments::keep) -- the rule the shared accumulators
-  // s1 / s2 already impose.
-  hipError_t reduce_more(hipError_t e, const float* x, hipStream_t st) {
-    if (e == hipSuccess && hist) e = lmc::launch_pixel_hist(x, C, prob.H, prob.W, hist_bins, hist_lo, hist_scale, hist, st);
-    if (e == hipSuccess && grp) e = lmc::launch_group_moments(x, C, chain_offset, prob.H, prob.W, n_groups, grp, grp + (size_t)n_groups * prob.H * prob.W, st);
-    if (e == hipSuccess && cov) {
-      const size_t ny = (size_t)cov_k * prob.H * prob.W;
-      e = lmc::launch_cov_sketch(x, C, prob.H, prob.W, cov_k, cov_probes, cov_center, cov, cov + ny, cov + ny + cov_k, cov_ws, st);
-    }
-    return e;
-  }
-  // the kept iterate x into the accumulators: the fused multi-scale reduction when scales are enabled, else exactly the launches of before;
-  // then what reduce_more adds
-  hipError_t reduce(const float* x, hipStream_t st) {
-    return reduce_more(bs2 ? lmc::launch_moments_ms(x, C, prob.H, prob.W, s1, s2, scales, st) : lmc::launch_moments(x, C, prob.H, prob.W, s1, s2, st), x, st);
-  }
-  hipError_t reduce_bg(const float* x, int n_wg, hipStream_t st) {
-    return reduce_more(bs2 ? lmc::launch_moments_ms_bg(x, C, prob.H, prob.W, s1, s2, scales, n_wg, st) : lmc::launch_moments_bg(x, C, prob.H, prob.W, s1, s2, n_wg, st), x, st);
-  }
+  lmc::host::Accumulators acc;          // what the kept iterates are reduced into (lmc_accum.h)
   lmc::StepArgs base{};
   // MYMALA state (kind == 2): proposal mean of the current state, proposal, its mean, energies, decisions
   float* mx = nullptr; float* xp = nullptr; float* mxp = nullptr;
@@ -319,6 +274,4 @@ namespace lmc::host {
 int rebuild_base(lmc_sampler* s);
 // what lmc_sampler_set_prior_sigma and lmc_sampler_sapg refuse (LMC_E_UNSUPPORTED), else LMC_OK
 int check_weight_settable(const lmc_sampler* s);
-// n[g] of the chain-group moments: kept iterations x chains of the handle in group g, into counts[s->n_groups]
-void group_counts(const lmc_sampler* s, uint64_t* counts);
 }  // namespace lmc::host

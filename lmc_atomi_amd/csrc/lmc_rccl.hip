@@ -92,16 +92,16 @@ int lmc_rccl_comm_destroy(void* comm) {
   return LMC_OK;
 }
 
-// The collective of the moments: s->packed holds {sum [n], sumsq [n]} of this rank; the count joins them, ONE ncclAllReduce(sum) over xGMI
+// The collective of the moments: s->acc.packed holds {sum [n], sumsq [n]} of this rank; the count joins them, ONE ncclAllReduce(sum) over xGMI
 // (4 MiB at 512 x 512) in place, and the three come back out.
-static int allreduce_packed(lmc_sampler* s, RcclApi* R, void* rccl_comm, size_t n, double* sum_dev, double* sumsq_dev, uint64_t* count, hipStream_t st) {
-  const double cnt = (double)s->count;                      // exact below 2^53 samples
-  HIP_TRY(hipMemcpyAsync(s->packed + 2 * n, &cnt, sizeof(double), hipMemcpyHostToDevice, st));
-  RCCL_TRY(R, R->AllReduce(s->packed, s->packed, 2 * n + 1, ncclFloat64, ncclSum, static_cast<ncclComm_t>(rccl_comm), st));
-  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, s->packed, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, s->packed + n, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+static int allreduce_packed(Accumulators& a, RcclApi* R, void* rccl_comm, size_t n, double* sum_dev, double* sumsq_dev, uint64_t* count, hipStream_t st) {
+  const double cnt = (double)a.count;                      // exact below 2^53 samples
+  HIP_TRY(hipMemcpyAsync(a.packed + 2 * n, &cnt, sizeof(double), hipMemcpyHostToDevice, st));
+  RCCL_TRY(R, R->AllReduce(a.packed, a.packed, 2 * n + 1, ncclFloat64, ncclSum, static_cast<ncclComm_t>(rccl_comm), st));
+  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, a.packed, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, a.packed + n, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
   double total = 0.0;
-  HIP_TRY(hipMemcpyAsync(&total, s->packed + 2 * n, sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&total, a.packed + 2 * n, sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (count) *count = (uint64_t)(total + 0.5);
   return LMC_OK;
@@ -112,14 +112,15 @@ int lmc_allreduce_moments(lmc_sampler* s, void* rccl_comm, double* sum_dev, doub
   DeviceGuard dg(s->device);
   if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
   hipStream_t st = S(stream);
-  const size_t n = (size_t)s->prob.H * s->prob.W;
+  Accumulators& a = s->acc;
+  const size_t n = a.pixels();
   if (!rccl_comm) return lmc_sampler_get_moments(s, sum_dev, sumsq_dev, count, stream);   // a job of one rank
   RcclApi* R = rccl_api();
   if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
-  if (!s->packed) HIP_TRY(hipMalloc(&s->packed, sizeof(double) * (2 * n + 1)));
-  HIP_TRY(hipMemcpyAsync(s->packed, s->s1, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s->packed + n, s->s2, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-  return allreduce_packed(s, R, rccl_comm, n, sum_dev, sumsq_dev, count, st);
+  HIP_TRY(a.need_packed());
+  HIP_TRY(hipMemcpyAsync(a.packed, a.s1, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(a.packed + n, a.s2, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  return allreduce_packed(a, R, rccl_comm, n, sum_dev, sumsq_dev, count, st);
 }
 
 int lmc_allreduce_block_moments(lmc_sampler* s, void* rccl_comm, int32_t scale, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream) {
@@ -129,31 +130,34 @@ int lmc_allreduce_block_moments(lmc_sampler* s, void* rccl_comm, int32_t scale, 
   hipStream_t st = S(stream);
   RcclApi* R = rccl_api();
   if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
-  if (!s->packed) HIP_TRY(hipMalloc(&s->packed, sizeof(double) * (2 * (size_t)s->prob.H * s->prob.W + 1)));   // the blocks of a scale are fewer than the pixels
-  const size_t n = (size_t)((s->prob.H + scale - 1) / (scale > 0 ? scale : 1)) * ((s->prob.W + scale - 1) / (scale > 0 ? scale : 1));
-  int rc = lmc_sampler_get_block_moments(s, scale, s->packed, s->packed + n, nullptr, stream);   // refuses a scale that is not enabled
+  Accumulators& a = s->acc;
+  HIP_TRY(a.need_packed());                                                                 // the blocks of a scale are fewer than the pixels
+  const int k = BlockMoments::index(scale);
+  const size_t n = k < 0 ? 0 : BlockMoments::blocks(a.H, a.W, k);
+  int rc = lmc_sampler_get_block_moments(s, scale, a.packed, a.packed + n, nullptr, stream);   // refuses a scale that is not enabled
   if (rc) return rc;
-  return allreduce_packed(s, R, rccl_comm, n, sum_dev, sumsq_dev, count, st);
+  return allreduce_packed(a, R, rccl_comm, n, sum_dev, sumsq_dev, count, st);
 }
 
 // The collective of the histogram: the counts of this rank and its count in one uint64 buffer, ONE ncclAllReduce(ncclUint64, sum).
 int lmc_allreduce_histogram(lmc_sampler* s, void* rccl_comm, uint64_t* counts_dev, uint64_t* count, void* stream) {
   if (!s) return fail(LMC_E_INVALID, "NULL sampler");
   DeviceGuard dg(s->device);
-  if (!s->hist) return fail(LMC_E_INVALID, "the sampler has no histogram (lmc_sampler_set_histogram)");
+  Histogram& h = s->acc.hist;
+  if (!h.counts) return fail(LMC_E_INVALID, "the sampler has no histogram (lmc_sampler_set_histogram)");
   if (!rccl_comm) return lmc_sampler_get_histogram(s, counts_dev, count, stream);   // a job of one rank
   hipStream_t st = S(stream);
   RcclApi* R = rccl_api();
   if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
-  const size_t n = (size_t)(s->hist_bins + 2) * s->prob.H * s->prob.W;
-  if (!s->hist_packed) HIP_TRY(hipMalloc(&s->hist_packed, sizeof(unsigned long long) * (n + 1)));
-  const unsigned long long cnt = s->count;
-  HIP_TRY(hipMemcpyAsync(s->hist_packed, s->hist, sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s->hist_packed + n, &cnt, sizeof cnt, hipMemcpyHostToDevice, st));
-  RCCL_TRY(R, R->AllReduce(s->hist_packed, s->hist_packed, n + 1, ncclUint64, ncclSum, static_cast<ncclComm_t>(rccl_comm), st));
-  if (counts_dev) HIP_TRY(hipMemcpyAsync(counts_dev, s->hist_packed, sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, st));
+  const size_t n = h.elems(s->acc.H, s->acc.W);
+  if (!h.packed) HIP_TRY(hipMalloc(&h.packed, sizeof(unsigned long long) * (n + 1)));
+  const unsigned long long cnt = s->acc.count;
+  HIP_TRY(hipMemcpyAsync(h.packed, h.counts, sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h.packed + n, &cnt, sizeof cnt, hipMemcpyHostToDevice, st));
+  RCCL_TRY(R, R->AllReduce(h.packed, h.packed, n + 1, ncclUint64, ncclSum, static_cast<ncclComm_t>(rccl_comm), st));
+  if (counts_dev) HIP_TRY(hipMemcpyAsync(counts_dev, h.packed, sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, st));
   unsigned long long total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, s->hist_packed + n, sizeof total, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&total, h.packed + n, sizeof total, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (count) *count = total;
   return LMC_OK;
@@ -164,24 +168,25 @@ int lmc_allreduce_histogram(lmc_sampler* s, void* rccl_comm, uint64_t* counts_de
 int lmc_allreduce_group_moments(lmc_sampler* s, void* rccl_comm, double* sum_dev, double* sumsq_dev, uint64_t* counts_host, void* stream) {
   if (!s) return fail(LMC_E_INVALID, "NULL sampler");
   DeviceGuard dg(s->device);
-  if (!s->grp) return fail(LMC_E_INVALID, "the sampler has no chain groups (lmc_sampler_set_chain_groups)");
+  ChainGroups& g = s->acc.groups;
+  if (!g.sums) return fail(LMC_E_INVALID, "the sampler has no chain groups (lmc_sampler_set_chain_groups)");
   if (!rccl_comm) return lmc_sampler_get_group_moments(s, sum_dev, sumsq_dev, counts_host, stream);   // a job of one rank
   hipStream_t st = S(stream);
   RcclApi* R = rccl_api();
   if (!R->lib) return fail(LMC_E_UNSUPPORTED, "%s", R->why.c_str());
-  const size_t G = (size_t)s->n_groups, n = G * s->prob.H * s->prob.W;
-  if (!s->grp_packed) HIP_TRY(hipMalloc(&s->grp_packed, sizeof(double) * (2 * n + G)));
+  const size_t G = (size_t)g.n, n = g.elems(s->acc.H, s->acc.W) / 2;
+  if (!g.packed) HIP_TRY(hipMalloc(&g.packed, sizeof(double) * (2 * n + G)));
   uint64_t cnt[LMC_MAX_CHAIN_GROUPS];
   double cntd[LMC_MAX_CHAIN_GROUPS];
-  group_counts(s, cnt);
+  s->acc.group_counts(cnt);
   for (size_t g = 0; g < G; ++g) cntd[g] = (double)cnt[g];
-  HIP_TRY(hipMemcpyAsync(s->grp_packed, s->grp, sizeof(double) * 2 * n, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s->grp_packed + 2 * n, cntd, sizeof(double) * G, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(g.packed, g.sums, sizeof(double) * 2 * n, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(g.packed + 2 * n, cntd, sizeof(double) * G, hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));                          // cntd is pageable host memory of this frame
-  RCCL_TRY(R, R->AllReduce(s->grp_packed, s->grp_packed, 2 * n + G, ncclFloat64, ncclSum, static_cast<ncclComm_t>(rccl_comm), st));
-  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, s->grp_packed, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, s->grp_packed + n, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(cntd, s->grp_packed + 2 * n, sizeof(double) * G, hipMemcpyDeviceToHost, st));
+  RCCL_TRY(R, R->AllReduce(g.packed, g.packed, 2 * n + G, ncclFloat64, ncclSum, static_cast<ncclComm_t>(rccl_comm), st));
+  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, g.packed, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, g.packed + n, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(cntd, g.packed + 2 * n, sizeof(double) * G, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (counts_host)
     for (size_t g = 0; g < G; ++g) counts_host[g] = (uint64_t)(cntd[g] + 0.5);

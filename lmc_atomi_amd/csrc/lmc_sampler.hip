@@ -1,4 +1,5 @@
-// The samplers behind lmc_sampler: create / destroy / state / step of MYULA, MYMALA, SK-ROCK and ULPDA, and the accessors of a handle.
+// The samplers behind lmc_sampler: create / destroy / state / step of MYULA, MYMALA, SK-ROCK and ULPDA, and the accessors of a handle (those of its
+// accumulators: lmc_accum.hip).
 #include <cmath>
 #include <cstdlib>
 #include <new>
@@ -22,15 +23,9 @@ int check_config(const Cfg& cfg, bool steps_ok, const char* steps_msg) {
   return LMC_OK;
 }
 
-// The posterior-moment accumulators s1, s2 ([H][W] doubles each, zeroed) of a sampler created with moments on.
+// The posterior-moment accumulators of a sampler created with moments on.
 hipError_t alloc_moments(lmc_sampler* s) {
-  if (!s->moments) return hipSuccess;
-  const size_t mb = sizeof(double) * (size_t)s->prob.H * s->prob.W;
-  hipError_t e = hipMalloc(&s->s1, mb);
-  if (e == hipSuccess) e = hipMalloc(&s->s2, mb);
-  if (e == hipSuccess) e = hipMemset(s->s1, 0, mb);
-  if (e == hipSuccess) e = hipMemset(s->s2, 0, mb);
-  return e;
+  return s->moments ? s->acc.alloc(s->C, s->chain_offset, s->prob.H, s->prob.W) : hipSuccess;
 }
 
 // A create call whose device allocation failed: the sampler goes, the status says why.
@@ -68,14 +63,6 @@ int check_weight_settable(const lmc_sampler* s) {
   return LMC_OK;
 }
 
-void group_counts(const lmc_sampler* s, uint64_t* counts) {
-  const uint64_t G = (uint64_t)s->n_groups, kept_its = s->count / (uint64_t)s->C;
-  const uint64_t first = (uint64_t)s->chain_offset % G;     // the group of local chain 0
-  for (uint64_t g = 0; g < G; ++g) {
-    const uint64_t c0 = (g + G - first) % G;                 // the first local chain of group g, then every G-th
-    counts[g] = kept_its * (c0 < (uint64_t)s->C ? ((uint64_t)s->C - c0 + G - 1) / G : 0);
-  }
-}
 }  // namespace lmc::host
 
 extern "C" {
@@ -183,34 +170,6 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   return LMC_OK;
 }
 
-static void release_histogram(lmc_sampler* s) {
-  if (s->hist) (void)hipFree(s->hist);
-  if (s->hist_lo) (void)hipFree(s->hist_lo);
-  if (s->hist_scale) (void)hipFree(s->hist_scale);
-  if (s->hist_packed) (void)hipFree(s->hist_packed);
-  s->hist = s->hist_packed = nullptr;
-  s->hist_lo = s->hist_scale = nullptr;
-  s->hist_bins = 0;
-}
-
-static void release_chain_groups(lmc_sampler* s) {
-  if (s->grp) (void)hipFree(s->grp);
-  if (s->grp_packed) (void)hipFree(s->grp_packed);
-  s->grp = s->grp_packed = nullptr;
-  s->n_groups = 0;
-}
-
-static void release_cov_sketch(lmc_sampler* s) {
-  if (s->cov) (void)hipFree(s->cov);
-  if (s->cov_probes) (void)hipFree(s->cov_probes);
-  if (s->cov_center) (void)hipFree(s->cov_center);
-  if (s->cov_ws) (void)hipFree(s->cov_ws);
-  s->cov = nullptr;
-  s->cov_probes = s->cov_center = nullptr;
-  s->cov_ws = nullptr;
-  s->cov_k = 0;
-}
-
 void lmc_sampler_destroy(lmc_sampler* s) {
   if (!s) return;
   DeviceGuard dg(s->device);
@@ -227,17 +186,11 @@ void lmc_sampler_destroy(lmc_sampler* s) {
   if (s->scal) (void)hipFree(s->scal);
   if (s->x[0]) (void)hipFree(s->x[0]);
   if (s->x[1]) (void)hipFree(s->x[1]);
-  if (s->s1) (void)hipFree(s->s1);
-  if (s->s2) (void)hipFree(s->s2);
-  if (s->packed) (void)hipFree(s->packed);
-  if (s->bs2) (void)hipFree(s->bs2);
+  s->acc.release();
   if (s->sapg_stat) (void)hipFree(s->sapg_stat);
   if (s->sapg_trace) (void)hipFree(s->sapg_trace);
   if (s->sapg_host) (void)hipHostFree(s->sapg_host);
   if (s->sapg_ev) (void)hipEventDestroy(s->sapg_ev);
-  release_histogram(s);
-  release_chain_groups(s);
-  release_cov_sketch(s);
   for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
   if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }
   for (hipEvent_t e : s->side_ev) if (e) (void)hipEventDestroy(e);
@@ -383,7 +336,7 @@ struct SideMoments {
       HIP_TRY(hipEventRecord(s->side_ev[0], st));
       HIP_TRY(hipStreamWaitEvent(s->side, s->side_ev[0], 0));
       for (const float* x : {a, b})
-        if (x) HIP_TRY(s->reduce_bg(x, bg_wgs, s->side));
+        if (x) HIP_TRY(s->acc.reduce_bg(x, bg_wgs, s->side));
       HIP_TRY(hipEventRecord(s->side_ev[1 + slot], s->side));
       reads[slot][0] = a;
       reads[slot][1] = b;
@@ -391,9 +344,9 @@ struct SideMoments {
     } else {
       HIP_TRY(join());
       for (const float* x : {a, b})
-        if (x) HIP_TRY(s->reduce(x, st));
+        if (x) HIP_TRY(s->acc.reduce(x, st));
     }
-    s->count += (uint64_t)s->C * ((a ? 1 : 0) + (b ? 1 : 0));
+    s->acc.count += (uint64_t)s->C * ((a ? 1 : 0) + (b ? 1 : 0));
     return LMC_OK;
   }
 };
@@ -677,8 +630,8 @@ static int mymala_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, 
     // follow the acceptance rate, which the host does not see without a synchronisation.)
     HIP_TRY(lmc::mala_select(s->flag, x, s->mx, s->xp, s->mxp, C, img, 1, st));
     if (kept(s, s->iteration)) {
-      HIP_TRY(s->reduce(x, st));
-      s->count += (uint64_t)C;
+      HIP_TRY(s->acc.reduce(x, st));
+      s->acc.count += (uint64_t)C;
     }
     ++s->iteration;
   }
@@ -817,8 +770,8 @@ static int skrock_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, 
     s->x[s->cur ^ 1] = rest[0];
     s->xspare = rest[1];
     if (kept(s, s->iteration)) {
-      HIP_TRY(s->reduce(Ks, st));
-      s->count += (uint64_t)s->C;
+      HIP_TRY(s->acc.reduce(Ks, st));
+      s->acc.count += (uint64_t)s->C;
     }
     ++s->iteration;
   }
@@ -891,8 +844,8 @@ static int ulpda_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, h
     if (!s->gfirst)  // (algs.py:448)
       HIP_TRY(lmc::ulpda_dual_update(s->xhat, s->ydual, C, H, W, s->mu, s->prob.prior_sigma, iso, st));
     if (kept(s, s->iteration)) {
-      HIP_TRY(s->reduce(x, st));
-      s->count += (uint64_t)s->C;
+      HIP_TRY(s->acc.reduce(x, st));
+      s->acc.count += (uint64_t)s->C;
     }
     ++s->iteration;
   }
@@ -989,199 +942,6 @@ int64_t lmc_sampler_iteration(const lmc_sampler* s) { return s ? s->iteration : 
 int lmc_sampler_set_iteration(lmc_sampler* s, int64_t it) {
   if (!s || it < 0 || it > 0xFFFFFFFFLL) return fail(LMC_E_INVALID, "bad iteration");
   s->iteration = it;
-  return LMC_OK;
-}
-
-int lmc_sampler_get_moments(lmc_sampler* s, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream) {
-  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
-  DeviceGuard dg(s->device);
-  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
-  const size_t mb = sizeof(double) * (size_t)s->prob.H * s->prob.W;
-  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, s->s1, mb, hipMemcpyDeviceToDevice, S(stream)));
-  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, s->s2, mb, hipMemcpyDeviceToDevice, S(stream)));
-  HIP_TRY(hipStreamSynchronize(S(stream)));
-  if (count) *count = s->count;
-  return LMC_OK;
-}
-
-int lmc_sampler_reset_moments(lmc_sampler* s, void* stream) {
-  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
-  DeviceGuard dg(s->device);
-  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
-  const size_t mb = sizeof(double) * (size_t)s->prob.H * s->prob.W;
-  HIP_TRY(hipMemsetAsync(s->s1, 0, mb, S(stream)));
-  HIP_TRY(hipMemsetAsync(s->s2, 0, mb, S(stream)));
-  if (s->bs2) HIP_TRY(hipMemsetAsync(s->bs2, 0, sizeof(double) * s->bs2_count, S(stream)));
-  if (s->hist) HIP_TRY(hipMemsetAsync(s->hist, 0, sizeof(unsigned long long) * (size_t)(s->hist_bins + 2) * s->prob.H * s->prob.W, S(stream)));
-  if (s->grp) HIP_TRY(hipMemsetAsync(s->grp, 0, sizeof(double) * 2 * (size_t)s->n_groups * s->prob.H * s->prob.W, S(stream)));
-  if (s->cov) HIP_TRY(hipMemsetAsync(s->cov, 0, sizeof(double) * ((size_t)s->cov_k * s->prob.H * s->prob.W + s->cov_k + (size_t)s->cov_k * s->cov_k), S(stream)));
-  s->count = 0;
-  return LMC_OK;
-}
-
-// ---- multi-scale moments: sum b and sum b^2 of the block sums b of every kept sample, for scales out of {2, 4, 8, 16} ----
-static int scale_index(int32_t scale) { return scale == 2 ? 0 : scale == 4 ? 1 : scale == 8 ? 2 : scale == 16 ? 3 : -1; }
-
-int lmc_sampler_set_moment_scales(lmc_sampler* s, int32_t n_scales, const int32_t* scales) {
-  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
-  DeviceGuard dg(s->device);
-  if (n_scales < 0 || n_scales > 4 || (n_scales > 0 && !scales)) return fail(LMC_E_INVALID, "n_scales must be 0 .. 4 (distinct scales out of 2, 4, 8, 16)");
-  size_t off[4] = {0, 0, 0, 0}, total = 0;
-  bool on[4] = {false, false, false, false};
-  for (int i = 0; i < n_scales; ++i) {
-    const int k = scale_index(scales[i]);
-    if (k < 0) return fail(LMC_E_INVALID, "moment scale %d: the scales are 2, 4, 8 and 16", scales[i]);
-    if (on[k]) return fail(LMC_E_INVALID, "moment scale %d given twice", scales[i]);
-    on[k] = true;
-  }
-  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
-  if (s->count != 0) return fail(LMC_E_STATE, "the moment scales change only while the accumulators are empty (after create or lmc_sampler_reset_moments)");
-  for (int k = 0; k < 4; ++k) {
-    const size_t sc = (size_t)2 << k;
-    off[k] = total;
-    if (on[k]) total += ((s->prob.H + sc - 1) / sc) * ((s->prob.W + sc - 1) / sc);
-  }
-  if (s->bs2) HIP_TRY(hipFree(s->bs2));
-  s->bs2 = nullptr;
-  s->bs2_count = 0;
-  s->scales = lmc::BlockScales{};
-  if (!total) return LMC_OK;
-  hipError_t e = hipMalloc(&s->bs2, sizeof(double) * total);
-  if (e == hipSuccess) e = hipMemset(s->bs2, 0, sizeof(double) * total);
-  if (e != hipSuccess) {
-    if (s->bs2) (void)hipFree(s->bs2);
-    s->bs2 = nullptr;
-    return fail(e == hipErrorOutOfMemory ? LMC_E_NOMEM : LMC_E_HIP, "block-moment allocation failed: %s", hipGetErrorString(e));
-  }
-  s->bs2_count = total;
-  for (int k = 0; k < 4; ++k) s->scales.s2[k] = on[k] ? s->bs2 + off[k] : nullptr;
-  return LMC_OK;
-}
-
-int lmc_sampler_get_block_moments(lmc_sampler* s, int32_t scale, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream) {
-  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
-  DeviceGuard dg(s->device);
-  const int k = scale_index(scale);
-  if (k < 0 || !s->scales.s2[k]) return fail(LMC_E_INVALID, "moment scale %d is not enabled (lmc_sampler_set_moment_scales)", scale);
-  const size_t nb = (size_t)((s->prob.H + scale - 1) / scale) * ((s->prob.W + scale - 1) / scale);
-  if (sum_dev) HIP_TRY(lmc::launch_block_sums(s->s1, s->prob.H, s->prob.W, scale, sum_dev, S(stream)));
-  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, s->scales.s2[k], sizeof(double) * nb, hipMemcpyDeviceToDevice, S(stream)));
-  HIP_TRY(hipStreamSynchronize(S(stream)));
-  if (count) *count = s->count;
-  return LMC_OK;
-}
-
-// ---- pixel histograms: counts [n_bins + 2][H][W] of the kept samples, rows by t = (x - lo) * scale (lmc_pixel_hist.hip) ----
-int lmc_sampler_set_histogram(lmc_sampler* s, int32_t n_bins, const float* lo_dev, const float* scale_dev) {
-  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
-  DeviceGuard dg(s->device);
-  if (n_bins < 0 || n_bins > 62) return fail(LMC_E_INVALID, "n_bins must be 0 .. 62 (got %d)", n_bins);
-  if (n_bins > 0 && (!lo_dev || !scale_dev)) return fail(LMC_E_INVALID, "NULL lo / scale array with n_bins > 0");
-  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
-  if (s->count != 0) return fail(LMC_E_STATE, "the histogram changes only while the accumulators are empty (after create or lmc_sampler_reset_moments)");
-  HIP_TRY(hipDeviceSynchronize());     // nothing of an earlier histogram is in flight when its buffers go
-  release_histogram(s);
-  if (!n_bins) return LMC_OK;
-  const size_t img = (size_t)s->prob.H * s->prob.W, nc = (size_t)(n_bins + 2) * img;
-  hipError_t e = hipMalloc(&s->hist, sizeof(unsigned long long) * nc);
-  if (e == hipSuccess) e = hipMalloc(&s->hist_lo, sizeof(float) * img);
-  if (e == hipSuccess) e = hipMalloc(&s->hist_scale, sizeof(float) * img);
-  if (e == hipSuccess) e = hipMemset(s->hist, 0, sizeof(unsigned long long) * nc);
-  if (e == hipSuccess) e = hipMemcpy(s->hist_lo, lo_dev, sizeof(float) * img, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess) e = hipMemcpy(s->hist_scale, scale_dev, sizeof(float) * img, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    release_histogram(s);
-    return fail(e == hipErrorOutOfMemory ? LMC_E_NOMEM : LMC_E_HIP, "histogram allocation failed: %s", hipGetErrorString(e));
-  }
-  s->hist_bins = n_bins;
-  return LMC_OK;
-}
-
-int lmc_sampler_get_histogram(lmc_sampler* s, uint64_t* counts_dev, uint64_t* count, void* stream) {
-  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
-  DeviceGuard dg(s->device);
-  if (!s->hist) return fail(LMC_E_INVALID, "the sampler has no histogram (lmc_sampler_set_histogram)");
-  const size_t nb = sizeof(unsigned long long) * (size_t)(s->hist_bins + 2) * s->prob.H * s->prob.W;
-  if (counts_dev) HIP_TRY(hipMemcpyAsync(counts_dev, s->hist, nb, hipMemcpyDeviceToDevice, S(stream)));
-  HIP_TRY(hipStreamSynchronize(S(stream)));
-  if (count) *count = s->count;
-  return LMC_OK;
-}
-
-// ---- chain-group moments: A, B [n_groups][H][W] = sum x, sum x^2 of the kept samples by chain group (lmc_group_moments.hip) ----
-int lmc_sampler_set_chain_groups(lmc_sampler* s, int32_t n_groups) {
-  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
-  DeviceGuard dg(s->device);
-  if (n_groups != 0 && (n_groups < 2 || n_groups > LMC_MAX_CHAIN_GROUPS))
-    return fail(LMC_E_INVALID, "n_groups must be 0 or 2 .. %d (got %d)", LMC_MAX_CHAIN_GROUPS, n_groups);
-  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
-  if (s->count != 0) return fail(LMC_E_STATE, "the chain groups change only while the accumulators are empty (after create or lmc_sampler_reset_moments)");
-  HIP_TRY(hipDeviceSynchronize());     // nothing of earlier groups is in flight when their buffers go
-  release_chain_groups(s);
-  if (!n_groups) return LMC_OK;
-  const size_t nd = 2 * (size_t)n_groups * s->prob.H * s->prob.W;
-  hipError_t e = hipMalloc(&s->grp, sizeof(double) * nd);
-  if (e == hipSuccess) e = hipMemset(s->grp, 0, sizeof(double) * nd);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    release_chain_groups(s);
-    return fail(e == hipErrorOutOfMemory ? LMC_E_NOMEM : LMC_E_HIP, "chain-group allocation failed: %s", hipGetErrorString(e));
-  }
-  s->n_groups = n_groups;
-  return LMC_OK;
-}
-
-int lmc_sampler_get_group_moments(lmc_sampler* s, double* sum_dev, double* sumsq_dev, uint64_t* counts_host, void* stream) {
-  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
-  DeviceGuard dg(s->device);
-  if (!s->grp) return fail(LMC_E_INVALID, "the sampler has no chain groups (lmc_sampler_set_chain_groups)");
-  const size_t n = (size_t)s->n_groups * s->prob.H * s->prob.W;
-  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, s->grp, sizeof(double) * n, hipMemcpyDeviceToDevice, S(stream)));
-  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, s->grp + n, sizeof(double) * n, hipMemcpyDeviceToDevice, S(stream)));
-  HIP_TRY(hipStreamSynchronize(S(stream)));
-  if (counts_host) group_counts(s, counts_host);
-  return LMC_OK;
-}
-
-// ---- covariance sketch: Y [k][H][W], s [k], Q [k][k] of the kept samples against k probe images (lmc_cov_sketch.hip) ----
-int lmc_sampler_set_cov_sketch(lmc_sampler* s, int32_t k, const float* probes_dev, const float* center_dev) {
-  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
-  DeviceGuard dg(s->device);
-  if (k < 0 || k > LMC_MAX_COV_PROBES) return fail(LMC_E_INVALID, "k must be 0 .. %d (got %d)", LMC_MAX_COV_PROBES, k);
-  if (k > 0 && !probes_dev) return fail(LMC_E_INVALID, "NULL probe array with k > 0");
-  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
-  if (s->count != 0) return fail(LMC_E_STATE, "the covariance sketch changes only while the accumulators are empty (after create or lmc_sampler_reset_moments)");
-  HIP_TRY(hipDeviceSynchronize());     // nothing of an earlier sketch is in flight when its buffers go
-  release_cov_sketch(s);
-  if (!k) return LMC_OK;
-  const size_t img = (size_t)s->prob.H * s->prob.W, nd = (size_t)k * img + k + (size_t)k * k;
-  hipError_t e = hipMalloc(&s->cov, sizeof(double) * nd);
-  if (e == hipSuccess) e = hipMalloc(&s->cov_probes, sizeof(float) * k * img);
-  if (e == hipSuccess && center_dev) e = hipMalloc(&s->cov_center, sizeof(float) * img);
-  if (e == hipSuccess) e = hipMalloc(&s->cov_ws, lmc::cov_sketch_workspace_bytes(s->C, s->prob.H, s->prob.W, k));
-  if (e == hipSuccess) e = hipMemset(s->cov, 0, sizeof(double) * nd);
-  if (e == hipSuccess) e = hipMemcpy(s->cov_probes, probes_dev, sizeof(float) * k * img, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess && center_dev) e = hipMemcpy(s->cov_center, center_dev, sizeof(float) * img, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    release_cov_sketch(s);
-    return fail(e == hipErrorOutOfMemory ? LMC_E_NOMEM : LMC_E_HIP, "covariance-sketch allocation failed: %s", hipGetErrorString(e));
-  }
-  s->cov_k = k;
-  return LMC_OK;
-}
-
-int lmc_sampler_get_cov_sketch(lmc_sampler* s, double* y_dev, double* s_dev, double* q_dev, uint64_t* count, void* stream) {
-  if (!s) return fail(LMC_E_INVALID, "NULL sampler");
-  DeviceGuard dg(s->device);
-  if (!s->cov) return fail(LMC_E_INVALID, "the sampler has no covariance sketch (lmc_sampler_set_cov_sketch)");
-  const size_t k = (size_t)s->cov_k, ny = k * s->prob.H * s->prob.W;
-  if (y_dev) HIP_TRY(hipMemcpyAsync(y_dev, s->cov, sizeof(double) * ny, hipMemcpyDeviceToDevice, S(stream)));
-  if (s_dev) HIP_TRY(hipMemcpyAsync(s_dev, s->cov + ny, sizeof(double) * k, hipMemcpyDeviceToDevice, S(stream)));
-  if (q_dev) HIP_TRY(hipMemcpyAsync(q_dev, s->cov + ny + k, sizeof(double) * k * k, hipMemcpyDeviceToDevice, S(stream)));
-  HIP_TRY(hipStreamSynchronize(S(stream)));
-  if (count) *count = s->count;
   return LMC_OK;
 }
 

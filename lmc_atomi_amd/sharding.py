@@ -11,6 +11,8 @@ from __future__ import annotations
 
 import torch
 
+from .summaries import _check_chain_groups, block_mean_var, mcse_from_group_moments, mean_var_from_moments
+
 
 def chain_shard(n_total: int, world: int, rank: int):
     """(offset, count) of the contiguous block of global chain ids owned by ``rank``."""
@@ -79,29 +81,28 @@ def rccl_comm(group=None, device=None):
     return _own_comms[key]
 
 
+def _route(group, local, nccl, host):
+    """The three routes of a sampler's job-wide accumulators: ``local()`` without a process group or with one rank, ``nccl()`` -- the C-ABI
+    collective on the RCCL communicator of the group (:func:`rccl_comm`) -- under backend "nccl", else ``host(*local())``, the host all-reduce of what the sampler holds."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return local()
+    if dist.get_backend(group) == "nccl":
+        return nccl()
+    return host(*local(), group)
+
+
 def allreduce_sampler_moments(smp, group=None):
     """Job-wide (sum, sumsq, count) of a sampler's posterior-moment accumulators.  Backend "nccl": ONE ``ncclAllReduce`` issued by
     the library itself (``lmc_allreduce_moments``, C ABI) on the RCCL communicator of the group -- no torch op in between;
     "gloo" (CPU tests, several ranks rehearsed on one GPU): the packed host all-reduce of :func:`allreduce_moments`."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-        return smp.moments()
-    if dist.get_backend(group) == "nccl":
-        return smp.allreduce_moments(rccl_comm(group, smp.device))
-    s1, s2, cnt = smp.moments()
-    return allreduce_moments(s1, s2, cnt, group)
+    return _route(group, smp.moments, lambda: smp.allreduce_moments(rccl_comm(group, smp.device)), allreduce_moments)
 
 
 def allreduce_sampler_block_moments(smp, scale, group=None):
     """Job-wide (S1, S2, count) of one scale of a sampler's block-moment accumulators (:meth:`MYULASampler.block_moments`), by the same
     routes as :func:`allreduce_sampler_moments`: ``lmc_allreduce_block_moments`` under "nccl", the packed host all-reduce under "gloo"."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-        return smp.block_moments(scale)
-    if dist.get_backend(group) == "nccl":
-        return smp.allreduce_block_moments(rccl_comm(group, smp.device), scale)
-    S1, S2, cnt = smp.block_moments(scale)
-    return allreduce_moments(S1, S2, cnt, group)
+    return _route(group, lambda: smp.block_moments(scale), lambda: smp.allreduce_block_moments(rccl_comm(group, smp.device), scale), allreduce_moments)
 
 
 def allreduce_counts(counts, count, group=None):
@@ -120,13 +121,7 @@ def allreduce_counts(counts, count, group=None):
 def allreduce_sampler_histogram(smp, group=None):
     """Job-wide (counts, count) of a sampler's pixel histogram (:meth:`MYULASampler.histogram`), by the same routes as
     :func:`allreduce_sampler_block_moments`: ``lmc_allreduce_histogram`` under "nccl", a host all-reduce of the int64 tensor under "gloo"."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-        return smp.histogram()
-    if dist.get_backend(group) == "nccl":
-        return smp.allreduce_histogram(rccl_comm(group, smp.device))
-    counts, cnt = smp.histogram()
-    return allreduce_counts(counts, cnt, group)
+    return _route(group, smp.histogram, lambda: smp.allreduce_histogram(rccl_comm(group, smp.device)), allreduce_counts)
 
 
 def allreduce_group_moments(S1, S2, counts, group=None):
@@ -152,12 +147,7 @@ def allreduce_group_moments(S1, S2, counts, group=None):
 def allreduce_sampler_group_moments(smp, group=None):
     """Job-wide (S1, S2, counts) of a sampler's chain-group moments (:meth:`MYULASampler.group_moments`), by the same routes as
     :func:`allreduce_sampler_block_moments`: ``lmc_allreduce_group_moments`` under "nccl", the host route of :func:`allreduce_group_moments` under "gloo"."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-        return smp.group_moments()
-    if dist.get_backend(group) == "nccl":
-        return smp.allreduce_group_moments(rccl_comm(group, smp.device))
-    return allreduce_group_moments(*smp.group_moments(), group)
+    return _route(group, smp.group_moments, lambda: smp.allreduce_group_moments(rccl_comm(group, smp.device)), allreduce_group_moments)
 
 
 def allreduce_cov_sketch(Y, s, Q, n, group=None):
@@ -201,9 +191,7 @@ def allgather_chains(t: torch.Tensor, dim: int = 1, group=None):
     return torch.cat([p[:c] for p, c in zip(parts, counts)], dim=0).movedim(0, dim)
 
 
-def posterior_mean_var(s1, s2, count):
-    mean = s1 / count
-    return mean, s2 / count - mean * mean
+posterior_mean_var = mean_var_from_moments
 
 
 class ShardedResult(tuple):
@@ -231,7 +219,7 @@ def sharded_myula(proxf, proxg, dims, n_chains_total, x0, tau, gamma, epsg=1.0, 
     ``chain_groups=G`` (as :class:`MYULASampler` takes it; at most ``n_chains_total``) keeps chain-group moments on every rank and returns the job-wide
     Monte-Carlo error maps under ``.mcse_mean``, ``.mcse_var``, ``.ess`` and ``.group_counts`` (:func:`lmc_atomi_amd.mcse_from_group_moments`)."""
     import torch.distributed as dist
-    from .algs import MYULASampler, _check_chain_groups, mcse_from_group_moments
+    from .algs import MYULASampler
     _check_chain_groups(chain_groups, True, n_chains_total)
     world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
     rank = dist.get_rank(group) if world > 1 else 0
@@ -249,7 +237,6 @@ def sharded_myula(proxf, proxg, dims, n_chains_total, x0, tau, gamma, epsg=1.0, 
         smp.step(niter)
         s1, s2, cnt = allreduce_sampler_moments(smp, group)
         for sc in smp.moment_scales:
-            from .algs import block_mean_var
             S1, S2, n = allreduce_sampler_block_moments(smp, sc, group)
             m, v = block_mean_var(S1, S2, max(n, 1), sc, smp.dims)
             scales[sc] = (m, v.clamp_min(0).sqrt())
