@@ -25,6 +25,14 @@ namespace lmc {
 // The kernels that run the stages with the momentum folded into the projection scale (pipe_stage, FOLD): one fixed-count launch from the zero dual state
 // with the isotropic projection
 __host__ __device__ constexpr bool pipe_fold(bool chain, bool warm, bool rt, bool aniso) { return !chain && !warm && !rt && !aniso; }
+// The kernels that fold the wave shifts of a stage into the differences that use them (sub_left_pair, right_pair_sub) and select the row-edge
+// coefficient in scalar registers (pipe_cdown): the folded-momentum kernels, but for the two-iteration launches without a blur (K = 2, KT = 0, aligned
+// rows, 4 and 8 pixels per lane), which would take 6 / 12 more VGPRs -- a block of 8 more -- and for the 7-tap kernels, which ran 1.5 % slower with the
+// folded shifts (512 x 512, 1024 chains: 1.748 against 1.723 ms per step; their L wave is the long one).  That one measurement is of the one-team kernel at
+// 8 pixels per lane; the 7-tap kernels at 4 pixels per lane are kept out with it UNMEASURED (the 5-tap layout at 4 pixels per lane gained the most,
+// 3.7 %, so they may well gain too: a lead, not a finding).  Those keep the built pairs and the parent's instruction streams
+// (tests/golden/pipe_shift_gated_code_hashes.txt).
+__host__ __device__ constexpr bool pipe_shift(bool fold, int k, int kt) { return fold && !(k == 2 && kt == 0) && kt != 7; }
 
 template <int K>
 struct PipeGeom {
@@ -168,6 +176,38 @@ __device__ __forceinline__ float wave_from_right(float v, float edge) {   // lan
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
 }
 
+// The difference with the one BUILT neighbour pair of a lane (left_pair(v, ., 0) / right_pair(v, ., NP - 1)), the wave shift folded into the
+// subtraction that uses it (pipe_shift kernels).  Building the pair costs a DPP move for the shift and a plain move to put the other pixel beside it (a
+// second one at the team seam, where the shift lands in the register the seam record was read into) before the one packed subtraction; formed half by
+// half the shift is the DPP operand of its own subtraction (v_subrev_f32_dpp / v_sub_f32_dpp; the compiler places the wait states a DPP read needs) and the
+// other half is one plain subtraction: two instructions and no move.  At the seam (SEAM: the vacant lane keeps `edge`) the DPP move into the record's
+// register stays, then two plain subtractions.  Each half is kept from being re-packed by an empty asm: without it the SLP vectoriser rebuilds the
+// pair.  The same IEEE subtraction on the same operands per pixel: the bits do not change.
+__device__ __forceinline__ v2f pk_halves(float hx, float hy) {
+  asm("" : "+v"(hx));
+  asm("" : "+v"(hy));
+  return v2f{hx, hy};
+}
+template <int NP, bool SEAM>      // a - left_pair(v, from_left(v[NP-1].y), 0)
+__device__ __forceinline__ v2f sub_left_pair(v2f a, const v2f (&v)[NP], float edge) {
+  const float vy = v[NP - 1].y, ax = a.x, ay = a.y, vx = v[NP - 1].x;
+  const float sh = SEAM ? wave_from_left(vy, edge) : dpp_left0(vy);
+  return pk_halves(ax - sh, ay - vx);
+}
+template <int NP, bool SEAM>      // right_pair(v, from_right(v[0].x), NP - 1) - b
+__device__ __forceinline__ v2f right_pair_sub(const v2f (&v)[NP], float edge, v2f b) {
+  const float vx = v[0].x, vy = v[0].y, bx = b.x, by = b.y;
+  const float sh = SEAM ? wave_from_right(vx, edge) : dpp_right0(vx);
+  return pk_halves(vy - bx, sh - by);
+}
+// The row-edge coefficient of a stage, cstep or 0 by row: wave-uniform, so in the pipe_shift kernels it is selected on the bit pattern in scalar registers (a float
+// select goes through v_cndmask_b32 and a move per stage) and the packed multiply-add reads the scalar.
+__device__ __forceinline__ float pipe_cdown(int a, int H, float cstep) {
+  int b = ((unsigned)(a - 1) >= (unsigned)(H - 1)) ? (int)0x80000000 : __builtin_bit_cast(int, -cstep);     // the stages read -cdown
+  asm("" : "+s"(b));
+  return -__builtin_bit_cast(float, b);
+}
+
 // One FGP dual iteration on NP pixel pairs per lane.  r1, s1 = (rr, ss)^{k-1} on row a; in0 = (rr, ss, p, q)^{k-1} on row
 // b = a-1; solb = sol^k on row b (in) -> sol^k on row a (out); out = (rr, ss, p, q)^k on row b.
 // The horizontal step coefficient per pixel: -c, and 0 for the pixel in the last image column (no difference across it).  LASTLANE: the image
@@ -223,29 +263,37 @@ __device__ __forceinline__ v2f obj_tv(const ObjMask<NP, !LASTLANE>* om, int i, v
 // -- five packed instructions where pn = r inv, qn = s inv, rr = fma(beta, pn - p_old, pn), ss = fma(beta, qn - q_old, qn) are six, 15 per pair and
 // stage in all instead of 16.  The same number in exact arithmetic, another association of the same products in fp32.  `mom`, `cfold`: beta_k and
 // nothing, or 1 + beta_k and c_k.
-template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAML = false, bool SEAMR = false, bool ANISO = false, bool BOX = false, bool FOLD = false>
+// SHIFT (pipe_shift kernels): the two differences with a built pair take their wave shift as an operand (sub_left_pair, right_pair_sub).  How it is
+// written: `SHIFT && i == 0 ? sub_left_pair(...) : s1[i] - ssl` with SHIFT and i compile-time constants after unrolling, so exactly one arm exists per
+// pair.  With SHIFT on, ssl0 / solr_last are a dummy 0 and the built pair of left_pair(., 0) / right_pair(., NP - 1) is formed but never read: dead code
+// that the compiler removes (no DPP move and no v_mov in the ISA).  With SHIFT off every statement is the one the kernels had before, in the same
+// order: the unfolded kernels' instruction streams are pinned by hash (tests/test_pipe_fold_resources.py) and depend on that order, which an
+// `if constexpr` block around the built-pair path changed when it was tried.  The same form in pipe_stage_first and in the combine wave.
+template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAML = false, bool SEAMR = false, bool ANISO = false, bool BOX = false, bool FOLD = false,
+          bool SHIFT = false>
 __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[NP], const v2f (&s1)[NP], const DualRow<NP>& in0,
                                            v2f (&solb)[NP], float gam, float cdown, const PipeCr<NP>& cr, float mom,
                                            DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP, !LASTLANE>* om = nullptr,
                                            float ssl_edge = 0.f, float solr_edge = 0.f, float blo = 0.f, float bhi = 0.f, float cfold = 0.f) {
   static_assert(!FOLD || (!ANISO && !OBJ), "the folded momentum needs the shared scale of the isotropic projection; the early exit keeps p, q");
+  static_assert(!SHIFT || FOLD, "the folded shifts go where the folded momentum goes");
   v2f sol[NP];
-  const float ssl0 = SEAML ? wave_from_left(s1[NP - 1].y, ssl_edge) : dpp_left0(s1[NP - 1].y);
+  const float ssl0 = SHIFT ? 0.f : SEAML ? wave_from_left(s1[NP - 1].y, ssl_edge) : dpp_left0(s1[NP - 1].y);
   const v2f ngam = pk_set(-gam), ncd = pk_set(-cdown), vb = pk_set(mom), nvc = pk_set(-cfold);
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const v2f ssl = left_pair(s1, ssl0, i);
-    const v2f T = (r1[i] - in0.rr[i]) + (s1[i] - ssl);
+    const v2f T = (r1[i] - in0.rr[i]) + (SHIFT && i == 0 ? sub_left_pair<NP, SEAML>(s1[i], s1, ssl_edge) : s1[i] - ssl);
     sol[i] = pk_fma(ngam, T, xa[i]);
     if constexpr (BOX) sol[i] = pipe_clamp_box(sol[i], blo, bhi);
     if constexpr (OBJ) { const v2f Tm = obj_sq<NP, LASTLANE>(om, i, T); ob->sq = i == 0 ? Tm * Tm : pk_fma(Tm, Tm, ob->sq); }
   }
-  const float solr_last = SEAMR ? wave_from_right(solb[0].x, solr_edge) : dpp_right0(solb[0].x);
+  const float solr_last = SHIFT ? 0.f : SEAMR ? wave_from_right(solb[0].x, solr_edge) : dpp_right0(solb[0].x);
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const v2f solr = right_pair(solb, solr_last, i);
     const v2f ncr = pipe_ncr<NP, LASTLANE>(cr, i);
-    const v2f dxv = sol[i] - solb[i], dyv = solr - solb[i];
+    const v2f dxv = sol[i] - solb[i], dyv = SHIFT && i == NP - 1 ? right_pair_sub<NP, SEAMR>(solb, solr_edge, solb[i]) : solr - solb[i];
     if constexpr (OBJ) {
       const v2f nr = obj_tv<NP, LASTLANE>(om, i, dxv, dyv);
       ob->tv = i == 0 ? nr : ob->tv + nr;
@@ -285,12 +333,13 @@ __device__ __forceinline__ void pipe_stage(const v2f (&xa)[NP], const v2f (&r1)[
 // Stage 1 of a launch that starts from the zero dual state: (rr, ss, p, q)^0 = 0, so sol^1 = x and the differences with the previous
 // iterate vanish.  Bit-identical to pipe_stage() fed with zeros (x - 0 = x, fma(c, d, 0) = c*d), at ~60 % of its instructions.
 // BOX: sol^0 = clip(x).  FOLD (`mom` = 1 + beta_1): u_0 = 0, so rr = u and ss = v -- the two fma(beta, pn, pn) go, the one scaled `inv` comes.
-template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAMR = false, bool ANISO = false, bool BOX = false, bool FOLD = false>
+template <int NP, bool LASTLANE = true, bool OBJ = false, bool SEAMR = false, bool ANISO = false, bool BOX = false, bool FOLD = false, bool SHIFT = false>
 __device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb)[NP], float cdown, const PipeCr<NP>& cr, float mom,
                                                  DualRow<NP>& out, StageObj* ob = nullptr, const ObjMask<NP, !LASTLANE>* om = nullptr,
                                                  float solr_edge = 0.f, float blo = 0.f, float bhi = 0.f) {
-  const float solr_last = SEAMR ? wave_from_right(solb[0].x, solr_edge) : dpp_right0(solb[0].x);
+  const float solr_last = SHIFT ? 0.f : SEAMR ? wave_from_right(solb[0].x, solr_edge) : dpp_right0(solb[0].x);
   static_assert(!FOLD || (!ANISO && !OBJ), "as pipe_stage");
+  static_assert(!SHIFT || FOLD, "as pipe_stage");
   const v2f ncd = pk_set(-cdown), vb = pk_set(mom);
   if constexpr (OBJ) ob->sq = pk_set(0.f);       // sol^0 = x
   v2f xc[BOX ? NP : 1];
@@ -303,7 +352,7 @@ __device__ __forceinline__ void pipe_stage_first(const v2f (&xa)[NP], v2f (&solb
   for (int i = 0; i < NP; ++i) {
     const v2f solr = right_pair(solb, solr_last, i);
     const v2f ncr = pipe_ncr<NP, LASTLANE>(cr, i);
-    const v2f dxv = x0(i) - solb[i], dyv = solr - solb[i];
+    const v2f dxv = x0(i) - solb[i], dyv = SHIFT && i == NP - 1 ? right_pair_sub<NP, SEAMR>(solb, solr_edge, solb[i]) : solr - solb[i];
     if constexpr (OBJ) {
       const v2f nr = obj_tv<NP, LASTLANE>(om, i, dxv, dyv);
       ob->tv = i == 0 ? nr : ob->tv + nr;
@@ -528,6 +577,8 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
   // anisotropic clamp (no shared scale).  Those keep the code and the bits they had.
   constexpr bool FOLD = pipe_fold(CHAIN, WARM, RT, ANISO);
   static_assert(!FOLD || K <= kTvFoldMax, "the folded table holds one launch's stages");
+  // Wave shifts folded into the differences that use them, the row-edge coefficient in scalar registers (sub_left_pair, right_pair_sub, pipe_cdown)
+  constexpr bool SHIFT = pipe_shift(FOLD, K, KT);
   using G = PipeGeom<K>;
   using L = PipeLds<K, PXL, CHAIN, TEAMS>;
   constexpr int D = G::D, E = G::E, RB = G::RB, NT = G::NT, BW = L::BW, RP = L::RP, HW = KT > 0 ? (KT - 1) / 2 : 0;
@@ -996,12 +1047,12 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       if constexpr (TEAMS == 2) edge = *reinterpret_cast<const float2*>(seam_in + (P ^ 1) * (TM == 1 ? 2 * (NT + 1) : 2 * NT));
       float ss2_edge = 0.f;
       if constexpr (!SINGLE) {   // stage k2 on row a2: inputs are this wave's stage k1, one tick (row a2) and two ticks (row a2-1) old
-        const float cdown = ((unsigned)(a2 - 1) >= (unsigned)(H - 1)) ? 0.f : cstep;
+        const float cdown = SHIFT ? pipe_cdown(a2, H, cstep) : ((unsigned)(a2 - 1) >= (unsigned)(H - 1)) ? 0.f : cstep;
         DualRow<NP> out;
         if (live2) {
           StageObj ob;
           om.md = cdown != 0.f ? 1.f : 0.f;
-          pipe_stage<NP, AL, RT, SL, SRt, ANISO, BOX, FOLD>(xk[P], o1[P ^ 1].rr, o1[P ^ 1].ss, o1[P], sol2, gam, cdown, crc, beta2, out, &ob, &om, edge.y, edge.y, blo, bhi, cf2);
+          pipe_stage<NP, AL, RT, SL, SRt, ANISO, BOX, FOLD, SHIFT>(xk[P], o1[P ^ 1].rr, o1[P ^ 1].ss, o1[P], sol2, gam, cdown, crc, beta2, out, &ob, &om, edge.y, edge.y, blo, bhi, cf2);
           if constexpr (RT) { osq2 += (double)(ob.sq.x + ob.sq.y); otv2 += (double)(ob.tv.x + ob.tv.y); }
         } else {                 // pass-through: the state of row a2 - 1 as stage k1 left it
 #pragma unroll
@@ -1031,11 +1082,11 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         }
         if (live1) {
           pairs_load<NP>(xk[P], ring_row(a1), lane);      // read two ticks ago as row a1 = this tick's a2: consumed above
-          const float cdown = ((unsigned)(a1 - 1) >= (unsigned)(H - 1)) ? 0.f : cstep;
+          const float cdown = SHIFT ? pipe_cdown(a1, H, cstep) : ((unsigned)(a1 - 1) >= (unsigned)(H - 1)) ? 0.f : cstep;
           StageObj ob;
           om.md = cdown != 0.f ? 1.f : 0.f;
-          if constexpr (FIRST) pipe_stage_first<NP, AL, RT, SRt, ANISO, BOX, FOLD>(xk[P], sol1, cdown, crc, beta1, o1[P], &ob, &om, edge.x, blo, bhi);
-          else pipe_stage<NP, AL, RT, SL, SRt, ANISO, BOX, FOLD>(xk[P], inb[P].rr, inb[P].ss, inb[P ^ 1], sol1, gam, cdown, crc, beta1, o1[P], &ob, &om, edge.x, edge.x, blo, bhi, cf1);
+          if constexpr (FIRST) pipe_stage_first<NP, AL, RT, SRt, ANISO, BOX, FOLD, SHIFT>(xk[P], sol1, cdown, crc, beta1, o1[P], &ob, &om, edge.x, blo, bhi);
+          else pipe_stage<NP, AL, RT, SL, SRt, ANISO, BOX, FOLD, SHIFT>(xk[P], inb[P].rr, inb[P].ss, inb[P ^ 1], sol1, gam, cdown, crc, beta1, o1[P], &ob, &om, edge.x, edge.x, blo, bhi, cf1);
           if constexpr (RT) { osq1 += (double)(ob.sq.x + ob.sq.y); otv1 += (double)(ob.tv.x + ob.tv.y); }
         } else {                 // pass-through: the state of row a1 - 1, read one tick ago
 #pragma unroll
@@ -1212,13 +1263,13 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         for (int j = 0; j < NP; ++j) gvp[j] = pk_set(0.f);
       }
       // two teams, right team: the left team's ss^K edge, published with its hand-off row (SA slot 2 NT)
-      const float ssl0 = (TEAMS == 2 && TM == 1) ? wave_from_left(css[NP - 1].y, seam[SA + (P ^ 1) * 2 * (NT + 1) + 2 * NT]) : dpp_left0(css[NP - 1].y);
+      const float ssl0 = SHIFT ? 0.f : (TEAMS == 2 && TM == 1) ? wave_from_left(css[NP - 1].y, seam[SA + (P ^ 1) * 2 * (NT + 1) + 2 * NT]) : dpp_left0(css[NP - 1].y);
       const v2f ngam = pk_set(-gam);
       v2f dvp[NP];
 #pragma unroll
       for (int j = 0; j < NP; ++j) {
         const v2f ssl = left_pair(css, ssl0, j);
-        dvp[j] = (crr[P][j] - crr[P ^ 1][j]) + (css[j] - ssl);
+        dvp[j] = (crr[P][j] - crr[P ^ 1][j]) + (SHIFT && j == 0 ? sub_left_pair<NP, TEAMS == 2 && TM == 1>(css[j], css, (TEAMS == 2 && TM == 1) ? seam[SA + (P ^ 1) * 2 * (NT + 1) + 2 * NT] : 0.f) : css[j] - ssl);
         proxp[j] = pk_fma(ngam, dvp[j], xop[j]);
         if constexpr (BOX) proxp[j] = pipe_clamp_box(proxp[j], A.box_lo, A.box_hi);
       }
