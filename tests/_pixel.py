@@ -20,7 +20,8 @@ one step and not drift, and a first-step edge error cannot hide in it.  "fused" 
 TV dual carried from one iteration to the next; `set_state` would zero it) cannot restart in between: both replays run the same iterations from x0 and
 the float32 replay carries its own drift, as the kernel does.  "prox": `TV.prox` alone, one evaluation.
 
-The early exit of the TV prox (rtol > 0) is left out: its pass count is a discontinuous function of the state and is pinned by the pass-count tests."""
+The early exit of the TV prox (rtol > 0) is left out: its pass count is a discontinuous function of the state and is pinned by the pass-count tests.
+The non-convex terms of L2_ncvx_tv (`ncvx_kind != NONE`) have cases of their own, on this file's problem recipe, bound and `check`: tests/_ncvx_pixel.py."""
 import functools
 from collections import namedtuple
 

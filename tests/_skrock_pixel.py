@@ -53,7 +53,8 @@ Parts (`CASES`).
   F  the strided part of the perturbation grid (`F_CASES`), more than 8192 x 256 units, by the closed form of a linear drift: grad f = l x,
      prox = x / (1 + gamma sp), so X' = R_s x0 + q B_s Z per pixel costs nothing and the float32 replays are the stage recursion on flat arrays.
 
-Out of scope: the non-convex terms (MC-TV, ME-TV) -- `O.L2NcvxTV` computes in float64 only and so has no float32 replay; `tv_rtol`, `tv_warm` and
+Out of scope: SK-ROCK with a non-convex term (MC-TV, ME-TV) -- tests/_ncvx_pixel.py holds the terms per pixel in the MYULA step kernels, which are the stage
+launches, and in ULPDA; the stage recurrence with the term stays with the rel-L2 tests (tests/test_gpu_skrock.py); `tv_rtol`, `tv_warm` and
 array-valued `epsg`, which SK-ROCK refuses (tests/test_gpu_skrock.py::test_c_abi_refusals)."""
 import functools
 import math

@@ -55,8 +55,8 @@ Paths (`expected_path`), from the dispatch of `cg_solve_fused` / `chebyshev_solv
 Seams: bands of 16 rows (two chains: 4096 / C bands wanted, at least 16 rows each) and column strips of 496 past 512 columns for the row kernel; bands
 of LMC_PAIR_BAND=32 rows with a recomputed halo of 8 for the pairs; 64 columns (and 64 rows) for the split and tile kernels.
 
-Out of scope: the L2_ncvx_tv pre-steps of ULPDA (ulpda_ncvx_rhs_kernel, ulpda_me_rhs_kernel) -- the checker's class computes in float64 only, they need
-a float32 replay of their own first; truncated solves at the default tolerance 1e-6 (the answer depends on the solver by design; rel-L2 tests); the
+The L2_ncvx_tv pre-steps of ULPDA (ulpda_ncvx_rhs_kernel, ulpda_me_rhs_kernel) are in tests/_ncvx_pixel.py, which restates the term in the dtype of its input and
+uses this file's solves, truncation condition and floors.  Out of scope: truncated solves at the default tolerance 1e-6 (the answer depends on the solver by design; rel-L2 tests); the
 chunking past 65535 chains (tests/test_gpu_many_images.py)."""
 import functools
 import math
