@@ -93,7 +93,27 @@ typedef enum lmc_data_kind {
    * not built), ncvx_kind != NONE, tv_rtol > 0, tv_warm, LMC_PRIOR_HAAR_L1, a forced step_variant other than 0, 1 and 7; 7 on a problem the pipeline
    * does not cover (from the create functions, and from lmc_fused_eval). */
   LMC_DATA_WL2_IDENTITY = 7,
-  LMC_DATA_WL2_BLUR = 8
+  LMC_DATA_WL2_BLUR = 8,
+  /* Large point-spread functions (appended; LMC_ATOMI_ABI_VERSION stays 4): Op = the zero-padded "same" convolution of LMC_DATA_BLUR with a kernel of
+   * 1 <= psf_kh, psf_kw <= LMC_MAX_PSF taps and any origin inside it, given by the psf_* fields of lmc_problem and the taps at h_host (kh = kw = oy =
+   * ox = 0 with these kinds, LMC_E_INVALID otherwise: the geometry of the small blur is not that of the PSF).  9: the Gaussian term of kind 2; 10: the Poisson term of kinds 4 .. 6 (y_dev = [2][H][W], counts then background);
+   * 11: the weighted Gaussian term of kinds 7, 8 (y_dev = [2][H][W], observation then weights; mask_dev must be NULL).  An operator of its own, NOT a
+   * larger LMC_DATA_BLUR: the update out = a x - t grad f(x) + b prox(x) + s xi runs as three launches on the caller's stream --
+   *   1. r = rho(H x) into a residual buffer (rho(u) = u - y, w (u - y), or the Poisson term's phi'(u)),
+   *   2. the step kernel of the same problem WITHOUT a data term: out = a x + b prox(x) + s xi -- every prior, the box, the Philox field and every
+   *      forced step_variant as they are for LMC_DATA_NONE (the variant selects the kernel of this launch),
+   *   3. out -= t sigma_f H^T r;  a launch without prox and noise (b == 0 and s == 0, e.g. the gradient alone) skips 2 and writes
+   *      out = a x - t sigma_f H^T r in 3.
+   * Kernels: psf_conv_kernel (lmc_psf.hip), one workgroup per 32 x 64 output tile and image, the tile and its halo staged in LDS, the taps read from a
+   * device buffer; a kernel that is an outer product (lmc_psf_separable) runs as two 1-D passes inside the tile unless psf_separable forbids it.
+   * Honoured by lmc_myula_create, lmc_skrock_create with all of lmc_sampler_* (lmc_sampler_sapg included), lmc_fused_eval, lmc_energies and
+   * lmc_sampler_energies (u in fp32, the terms widened to and summed in float64 by partial sums in a fixed order: equal from run to run).  A sampler
+   * handle uploads the taps once and owns the residual buffer; the stateless calls upload in stream order and take the buffer from their scratch.
+   * LMC_E_UNSUPPORTED, with the reason in lmc_last_error: lmc_mymala_create, lmc_ulpda_create, lmc_l2_prox (no implicit step, no pinned Metropolis path
+   * for it), ncvx_kind != NONE, tv_rtol > 0, tv_warm.  iterations_per_launch is ignored. */
+  LMC_DATA_PSF = 9,
+  LMC_DATA_POISSON_PSF = 10,
+  LMC_DATA_WL2_PSF = 11
 } lmc_data_kind;
 
 /* prior g whose prox enters the MYULA update (algs.py:569) */
@@ -142,6 +162,7 @@ typedef enum lmc_noise_mode {
 } lmc_noise_mode;
 
 #define LMC_MAX_BLUR 9       /* kernels up to 9x9 */
+#define LMC_MAX_PSF 33       /* LMC_DATA_PSF / lmc_psf_apply: kernels up to 33x33 (a Gaussian of sigma = 5 px at +-3 sigma; an even kernel of 32) */
 #define LMC_MAX_TV_ITERS 64
 #define LMC_MAX_SKROCK_STAGES 64
 #define LMC_MAX_CHAIN_GROUPS 64
@@ -154,10 +175,15 @@ typedef struct lmc_problem {
   /* data term */
   int32_t data_kind;        /* lmc_data_kind */
   float sigma_f;            /* multiplies the L2 term: 1/sigma^2 at prox_lmc_deconv.py:101 */
+  /* Large PSF: read with LMC_DATA_PSF / POISSON_PSF / WL2_PSF only.  The kernel's size, 1 .. LMC_MAX_PSF each, and its origin (pylops `offset`) inside it;
+   * the psf_kh * psf_kw taps, row-major, are at h_host (copied by the callee).  Bad geometry: LMC_E_INVALID.  The four bytes fill the alignment hole in
+   * front of y_dev and psf_separable (below) the one in front of prox_scale: no field moves and sizeof(lmc_problem) stays 200, so LMC_ATOMI_ABI_VERSION
+   * stays 4 and a caller built against the earlier header is unaffected (it never sets these kinds). */
+  uint8_t psf_kh, psf_kw, psf_oy, psf_ox;
   const float* y_dev;       /* [H][W] observation (borrowed; must outlive every use) */
   const float* mask_dev;    /* [H][W], LMC_DATA_MASK only */
-  int32_t kh, kw, oy, ox;   /* LMC_DATA_BLUR: kernel size and origin (pylops `offset`) */
-  const float* h_host;      /* kh*kw taps, row-major, host memory */
+  int32_t kh, kw, oy, ox;   /* LMC_DATA_BLUR: kernel size and origin (pylops `offset`); 0 with the large-PSF kinds */
+  const float* h_host;      /* kh*kw taps, row-major, host memory (large-PSF kinds: psf_kh*psf_kw taps) */
   /* prior */
   int32_t prior_kind;       /* lmc_prior_kind */
   float prior_sigma;        /* multiplicative coefficient of g (tau_reg = 0.3 at prox_lmc_deconv.py:116-122) */
@@ -231,6 +257,9 @@ typedef struct lmc_problem {
    * the prox parameter of chain c, pixel i is  epsg * gamma * prox_scale[c * prox_scale_chain_stride + i * prox_scale_pixel_stride]
    * (strides in elements: (0, 1) per pixel, (1, 0) per chain, (H*W, 1) both).  MYULA with LMC_PRIOR_L2 / L1 / EPROX only (the prox is evaluated by
    * one launch before the fused step, which consumes it); LMC_E_UNSUPPORTED for the other priors and samplers.  Must outlive the sampler. */
+  /* Large PSF (see psf_kh): 0 = two 1-D passes where lmc_psf_separable accepts the kernel, 1 = require them (LMC_E_INVALID for a kernel that fails the
+   * criterion), 2 = the general 2-D form always. */
+  int32_t psf_separable;
   const float* prox_scale;
   int64_t prox_scale_chain_stride;
   int32_t prox_scale_pixel_stride;
@@ -269,6 +298,16 @@ int lmc_hbm_copy_probe(size_t bytes, int32_t reps, float* gbs_out, void* stream)
  * Replaces Convolve2D.matvec / .rmatvec (prox_lmc_deconv.py:58; algs.py:284). */
 int lmc_blur(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W,
              const float* h_host, int32_t kh, int32_t kw, int32_t oy, int32_t ox, int32_t adjoint, void* stream);
+
+/* The same operator for kernels up to LMC_MAX_PSF x LMC_MAX_PSF (the operator of LMC_DATA_PSF): out = H x (adjoint == 0) or H^T x for n_img images,
+ * any n_img.  separable: 0 auto, 1 require (LMC_E_INVALID where lmc_psf_separable rejects the kernel), 2 the general form.  Not in place. */
+int lmc_psf_apply(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W,
+                  const float* h_host, int32_t kh, int32_t kw, int32_t oy, int32_t ox, int32_t adjoint, int32_t separable, void* stream);
+/* Host only, no device needed.  1 when h (kh x kw, row-major) is an outer product u v^T to a fraction of float32 rounding, 0 when not, LMC_E_INVALID
+ * for bad arguments.  With the pivot (pa, pb) of largest magnitude, u_a = h[a][pb] / h[pa][pb] and v_b = h[pa][b] formed in double must satisfy
+ * |u_a v_b - h_ab| <= 2^-22 |h_ab| for every tap (so a zero tap is reproduced as zero).  u_out (kh floats) and v_out (kw floats) may be NULL; they are
+ * written when the answer is 1. */
+int lmc_psf_separable(const float* h_host, int32_t kh, int32_t kw, float* u_out, float* v_out);
 
 /* out[2][H][W] = forward-difference gradient of x (zero in last row/col); pylops.Gradient.matvec
  * (prox_lmc_deconv.py:98; algs.py:436,448). */

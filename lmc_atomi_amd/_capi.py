@@ -18,11 +18,15 @@ DATA_NONE, DATA_IDENTITY, DATA_BLUR, DATA_MASK = 0, 1, 2, 3
 DATA_POISSON_IDENTITY, DATA_POISSON_BLUR, DATA_POISSON_MASK = 4, 5, 6      # y_dev: [2][H][W], the counts then the background
 POISSON_KINDS = (DATA_POISSON_IDENTITY, DATA_POISSON_BLUR, DATA_POISSON_MASK)
 DATA_WL2_IDENTITY, DATA_WL2_BLUR = 7, 8      # y_dev: [2][H][W], the observation then the per-pixel weights
+DATA_PSF, DATA_POISSON_PSF, DATA_WL2_PSF = 9, 10, 11      # the large PSF (psf_* fields): Gaussian, Poisson, weighted Gaussian term
+PSF_KINDS = (DATA_PSF, DATA_POISSON_PSF, DATA_WL2_PSF)
 WL2_KINDS = (DATA_WL2_IDENTITY, DATA_WL2_BLUR)
+TWO_PLANE_KINDS = POISSON_KINDS + WL2_KINDS + (DATA_POISSON_PSF, DATA_WL2_PSF)      # y_dev is [2][H][W]
 PRIOR_NONE, PRIOR_L2, PRIOR_L1, PRIOR_TV_ISO, PRIOR_TV_ANISO, PRIOR_HAAR_L1, PRIOR_EPROX = 0, 1, 2, 3, 4, 5, 6
 NOISE_PHILOX, NOISE_INJECTED, NOISE_NONE = 0, 1, 2
 NCVX_NONE, NCVX_MC_TV, NCVX_ME_TV, NCVX_MC_TV_ANISO, NCVX_ME_TV_ANISO = 0, 1, 2, 3, 4
 MAX_BLUR = 9
+MAX_PSF = 33
 MAX_TV_ITERS = 64
 MAX_SKROCK_STAGES = 64
 MAX_CHAIN_GROUPS = 64
@@ -63,6 +67,8 @@ class lmc_problem(C.Structure):
         ("H", C.c_int32), ("W", C.c_int32),
         ("data_kind", C.c_int32),
         ("sigma_f", C.c_float),
+        # large PSF (data kinds 9 .. 11): size and origin of the kernel at h_host; the four bytes fill the alignment hole in front of y_dev
+        ("psf_kh", C.c_uint8), ("psf_kw", C.c_uint8), ("psf_oy", C.c_uint8), ("psf_ox", C.c_uint8),
         ("y_dev", C.c_void_p),
         ("mask_dev", C.c_void_p),
         ("kh", C.c_int32), ("kw", C.c_int32), ("oy", C.c_int32), ("ox", C.c_int32),
@@ -90,6 +96,7 @@ class lmc_problem(C.Structure):
         ("moments_bg_workgroups", C.c_int32),
         ("graph_replay", C.c_int32),
         ("eprox_kind", C.c_int32), ("eprox_p0", C.c_float), ("eprox_p1", C.c_float), ("eprox_scale_mask", C.c_int32),
+        ("psf_separable", C.c_int32),      # large PSF: 0 auto, 1 require, 2 forbid the two-pass form (fills the hole in front of prox_scale)
         ("prox_scale", C.c_void_p), ("prox_scale_chain_stride", C.c_int64), ("prox_scale_pixel_stride", C.c_int32),
         # box constraint (appended; ABI stays 4)
         ("box_enable", C.c_int32), ("box_lo", C.c_float), ("box_hi", C.c_float),
@@ -150,6 +157,8 @@ _SIGNATURES = {
     "lmc_device_info": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "lmc_hbm_copy_probe": (C.c_int, [C.c_size_t, C.c_int32, C.POINTER(C.c_float), _P]),
     "lmc_blur": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "lmc_psf_apply": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "lmc_psf_separable": (C.c_int, [_F, C.c_int32, C.c_int32, _F, _F]),
     "lmc_gradient": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "lmc_gradient_adjoint": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "lmc_fused_eval": (C.c_int, [C.POINTER(lmc_problem), _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P]),

@@ -88,6 +88,20 @@ def _refuse_wl2(data, prior, opts, who=None):
                                   "(where it covers the problem)")
 
 
+def _refuse_psf(data, prior, opts, who=None):
+    """The same for a large PSF (``Op = PSF(...)``, ``LMC_DATA_PSF`` / ``POISSON_PSF`` / ``WL2_PSF``)."""
+    if data.get("data_kind") not in _capi.PSF_KINDS:
+        return
+    if who is not None:
+        raise NotImplementedError(f"{who[0]} does not take a large PSF (Op = PSF(...)): {who[1]}")
+    if data.get("ncvx_kind", _capi.NCVX_NONE) != _capi.NCVX_NONE:
+        raise NotImplementedError("a large PSF has no non-convex form")
+    if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
+        raise NotImplementedError("a large PSF runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
+    if prior.get("tv_warm") or opts.get("tv_warm"):
+        raise NotImplementedError("a large PSF has no warm-started TV dual: warm / tv_warm must be off")
+
+
 def _data_descriptor(proxf):
     if proxf is None:
         return {"data_kind": _capi.DATA_NONE}
@@ -296,6 +310,7 @@ class MYULASampler:
             epsg = 1.0
         _refuse_poisson(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._poisson_refusal)
         _refuse_wl2(_data_descriptor(proxf), _prior_descriptor(proxg), opts)
+        _refuse_psf(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._psf_refusal)
         self._problem = _Problem(self.dims, _data_descriptor(proxf), _prior_descriptor(proxg), self.device, options=opts)
         self.prior_weight = float(self._problem.c.prior_sigma)      # follows set_prior_weight / estimate_prior_weight
         cfg = _capi.lmc_myula_config()
@@ -314,7 +329,7 @@ class MYULASampler:
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             rc = self._create(cfg)
-        if rc == -2 and self._problem.c.data_kind in _capi.POISSON_KINDS + _capi.WL2_KINDS:      # (no handle exists: e.g. variant='pipe' on a problem the pipeline does not cover)
+        if rc == -2 and self._problem.c.data_kind in _capi.POISSON_KINDS + _capi.WL2_KINDS + _capi.PSF_KINDS:      # (no handle exists: e.g. variant='pipe' on a problem the pipeline does not cover)
             raise NotImplementedError(_dev.lib().lmc_last_error().decode())
         _capi.check(rc)
         self._attach_accumulators(acc)
@@ -322,6 +337,7 @@ class MYULASampler:
     _create_fn = "lmc_myula_create"
     _box_refusal = None          # (who, why) of a subclass that has no box-constrained form: raised before a handle exists
     _poisson_refusal = None      # the same for the Poisson data term
+    _psf_refusal = None          # the same for a large PSF
     _eprox_refusal = None        # the same for a closed-form prior (a prox without a value)
 
     def _create(self, cfg):
@@ -606,6 +622,7 @@ class ULPDASampler(MYULASampler):
             raise NotImplementedError("ULPDA does not take a prior with bounds: its prior enters through the dual ball of g o A, which has no box form; use MYULA")
         _refuse_poisson(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA"))
         _refuse_wl2(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, (I + tau sigma Op^T W Op)^{-1}, which is not built; use MYULA"))
+        _refuse_psf(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which is not built for a large PSF; use MYULA"))
         if isinstance(proxg, L21):
             prior = {"prior_kind": _capi.PRIOR_TV_ISO, "prior_sigma": proxg.sigma, "tv_niter": 1, "tv_betas": [0.0]}
         elif isinstance(proxg, L1):
@@ -904,6 +921,7 @@ class MYMALASampler(MYULASampler):
 
     _box_refusal = ("MYMALA", "its target would be +infinity outside the box, where MYULA's proposals land; use MYULA")
     _poisson_refusal = ("MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK")
+    _psf_refusal = ("MYMALA", "its Metropolis ratio is pinned for the fused step, which the three-launch PSF step is not; use MYULA or SK-ROCK")
     _eprox_refusal = ("MYMALA", "the prior has a prox and no value g(x), so the Metropolis target exp(-f - epsg g) is undefined; use MYULA")
 
     def acceptance(self):

@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <string>
 
 #include "lmc_host.h"
@@ -24,6 +25,30 @@ int scratch_me_tv(Scratch& sc, const Problem& q, const float* x, int64_t n_img, 
   if (q.ncvx_rtol > 0.f) HIP_TRY(sc.rt_me.need((size_t)n_img, q.ncvx_niter));
   if (f_out) return me_tv_energy(q, x, n_img, f_out, sc.extra, sc.state[0], sc.state[1], sc.dbl, st, &sc.rt_me);
   return me_tv_prox(q, x, sc.extra, n_img, sc.state[0], sc.state[1], st, &sc.rt_me);
+}
+
+// The large PSF of a stateless call: q.psf gets the device table and the residual buffer of the scratch sc.  The table is uploaded in stream order from
+// a pinned copy, and only when it differs from the one the scratch holds.
+int scratch_psf(Scratch& sc, lmc::PsfOp& P, size_t n_resid, hipStream_t st) {
+  if (!P.on) return LMC_OK;
+  if (!sc.psf_tab) {
+    HIP_TRY(hipMalloc(&sc.psf_tab, sizeof P.tab));
+    HIP_TRY(hipHostMalloc(&sc.psf_host, sizeof P.tab));
+    HIP_TRY(hipEventCreateWithFlags(&sc.psf_ev, hipEventDisableTiming));
+    sc.psf_valid = false;
+  }
+  if (!sc.psf_valid || std::memcmp(sc.psf_host, P.tab, sizeof P.tab) != 0) {
+    if (sc.psf_valid) HIP_TRY(hipEventSynchronize(sc.psf_ev));      // the previous upload has read the pinned copy
+    sc.psf_valid = false;
+    std::memcpy(sc.psf_host, P.tab, sizeof P.tab);
+    HIP_TRY(hipMemcpyAsync(sc.psf_tab, sc.psf_host, sizeof P.tab, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(sc.psf_ev, st));
+    sc.psf_valid = true;
+  }
+  if (n_resid) HIP_TRY(sc.need_resid(n_resid));
+  P.tab_dev = sc.psf_tab;
+  P.resid = sc.resid;
+  return LMC_OK;
 }
 
 }  // namespace
@@ -109,6 +134,30 @@ int lmc_blur(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32
   return LMC_OK;
 }
 
+int lmc_psf_separable(const float* h_host, int32_t kh, int32_t kw, float* u_out, float* v_out) {
+  if (!h_host) return fail(LMC_E_INVALID, "PSF pointer is NULL");
+  if (kh < 1 || kw < 1 || kh > lmc::kPsfMax || kw > lmc::kPsfMax) return fail(LMC_E_INVALID, "PSF %dx%d outside 1..%d", kh, kw, lmc::kPsfMax);
+  return lmc::psf_separable(h_host, kh, kw, u_out, v_out);
+}
+
+int lmc_psf_apply(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, const float* h_host, int32_t kh, int32_t kw, int32_t oy,
+                  int32_t ox, int32_t adjoint, int32_t separable, void* stream) {
+  if (!x_dev || !out_dev) return fail(LMC_E_INVALID, "NULL image pointer");
+  if (x_dev == out_dev) return fail(LMC_E_INVALID, "lmc_psf_apply cannot run in place");
+  if (n_img < 1 || H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30) return fail(LMC_E_INVALID, "bad shape n_img=%lld H=%d W=%d", (long long)n_img, H, W);
+  if (!h_host) return fail(LMC_E_INVALID, "PSF pointer is NULL");
+  if (kh < 1 || kw < 1 || kh > lmc::kPsfMax || kw > lmc::kPsfMax) return fail(LMC_E_INVALID, "PSF %dx%d outside 1..%d", kh, kw, lmc::kPsfMax);
+  if (oy < 0 || oy >= kh || ox < 0 || ox >= kw) return fail(LMC_E_INVALID, "PSF offset (%d,%d) outside the kernel", oy, ox);
+  if (separable < 0 || separable > 2) return fail(LMC_E_INVALID, "separable must be 0 (auto), 1 (require) or 2 (forbid)");
+  lmc::PsfOp P;
+  if (!lmc::psf_prepare(P, h_host, kh, kw, oy, ox, separable))
+    return fail(LMC_E_INVALID, "separable = 1 on a kernel that is no outer product to 2^-22 of every tap (lmc_psf_separable)");
+  int rc = scratch_psf(scratch_here(), P, 0, S(stream));
+  if (rc) return rc;
+  HIP_TRY(lmc::launch_psf(P, adjoint != 0, lmc::kPsfRaw, x_dev, out_dev, nullptr, nullptr, n_img, H, W, 0.f, 0.f, S(stream)));
+  return LMC_OK;
+}
+
 int lmc_gradient(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, void* stream) {
   if (!x_dev || !out_dev || x_dev == out_dev) return fail(LMC_E_INVALID, "bad pointers");
   if (n_img < 1 || H < 1 || W < 1) return fail(LMC_E_INVALID, "bad shape");
@@ -134,6 +183,7 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
   rc = check_prox_prior(q, b);
   if (!rc) rc = check_poisson(q);
   if (!rc) rc = check_wl2(q);
+  if (!rc) rc = check_psf(q);
   if (rc) return rc;
   lmc::StepArgs A;
   rc = make_step_args(q, a, t, b, pt, 0.f, A);
@@ -145,6 +195,7 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
   const size_t npx = (size_t)n_img * q.H * q.W;
   Scratch& sc = scratch_here();
   if (needs_tv_state(q)) HIP_TRY(sc.need_state(4 * npx));
+  if (t != 0.f) { rc = scratch_psf(sc, q.psf, npx, S(stream)); if (rc) return rc; }
   if (t != 0.f && q.ncvx_kind == LMC_NCVX_ME_TV) {
     rc = scratch_me_tv(sc, q, x_dev, n_img, nullptr, S(stream));
     if (rc) return rc;
@@ -169,7 +220,7 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
     A.prior_kind = LMC_PRIOR_NONE;
     A.prox_ext = sc.prox;
   }
-  hipError_t e = launch_step(A, variant_of(q), S(stream), nullptr, sc.state[0], sc.state[1], sc.prox);
+  hipError_t e = launch_step(A, variant_of(q), S(stream), nullptr, sc.state[0], sc.state[1], sc.prox, q.psf.on ? &q.psf : nullptr);
   if (e == hipErrorInvalidConfiguration)
     return fail(LMC_E_UNSUPPORTED, A.box ? "step_variant %d has no box-constrained form of this prior (TV: auto, 1 tile, 7 / 8 pipe where the pipe covers the problem)"
                                          : "no step-kernel variant covers this configuration", variant_of(q));
@@ -185,9 +236,12 @@ int lmc_energies(const lmc_problem* prob, const float* x_dev, int64_t n_img, dou
   if (!x_dev || n_img < 1) return fail(LMC_E_INVALID, "bad arguments");
   if (q.pois && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the Poisson data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
   if (q.wl2 && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
+  if (q.psf.on && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "a large PSF has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
+  if (f_out_dev) { rc = scratch_psf(scratch_here(), q.psf, 0, S(stream)); if (rc) return rc; }
   HIP_TRY(lmc::launch_energies(x_dev, n_img, energy_args(q), f_out_dev, g_out_dev, S(stream)));
   rc = pois_energy(q, x_dev, n_img, f_out_dev, S(stream));
   if (!rc) rc = wl2_energy(q, x_dev, n_img, f_out_dev, S(stream));
+  if (!rc) rc = psf_energy(q, x_dev, n_img, f_out_dev, S(stream));
   if (rc) return rc;
   if (q.prior_kind == LMC_PRIOR_HAAR_L1 && g_out_dev) HIP_TRY(lmc::launch_haar_value(x_dev, n_img, q.H, q.W, q.prior_sigma, g_out_dev, S(stream)));
   if (q.ncvx_kind == LMC_NCVX_ME_TV && f_out_dev) {
@@ -211,6 +265,7 @@ int lmc_l2_prox(const lmc_problem* prob, const float* x_dev, float* out_dev, int
   if (rc) return rc;
   rc = check_no_poisson(q, "lmc_l2_prox", "its implicit step (I + tau grad f)^{-1} has no closed form");
   if (!rc) rc = check_no_wl2(q, "lmc_l2_prox", "the implicit step (I + tau sigma_f Op^T W Op)^{-1} is not built");
+  if (!rc) rc = check_no_psf(q, "lmc_l2_prox", "the implicit step (I + tau sigma_f H^T H)^{-1} is not built for it");
   if (rc) return rc;
   if (!x_dev || !out_dev || x_dev == out_dev || n_img < 1) return fail(LMC_E_INVALID, "bad arguments (in-place not allowed)");
   if (!(tau > 0.f)) return fail(LMC_E_INVALID, "tau must be > 0");

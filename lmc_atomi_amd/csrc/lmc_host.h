@@ -55,6 +55,7 @@ struct Problem {
   const float* y = nullptr;
   const float* mask = nullptr;
   lmc::BlurTaps taps{};
+  lmc::PsfOp psf;           // LMC_DATA_PSF / POISSON_PSF / WL2_PSF: data_kind = LMC_DATA_PSF (with pois / wl2), the operator and its device table
   int prior_kind = 0;
   float prior_sigma = 0.f;
   int tv_niter = 0;
@@ -123,6 +124,14 @@ struct Scratch {
   float* prox = nullptr;                  // Haar-l1 prox / early-exit TV prox, [n][H][W]
   float* rtmp = nullptr;                  // early-exit TV prox: the iterate of the current pass, [n][H][W]
   double* dbl = nullptr;                  // 2*n doubles
+  float* resid = nullptr;                 // large PSF: the residual rho(H x) of a step, [n][H][W]
+  // large PSF: the device tap table of the stateless calls, the pinned host copy it was uploaded from (compared with the next call's table: equal
+  // taps are not uploaded again) and the event behind the last upload (the host copy is not rewritten before that upload has run)
+  float* psf_tab = nullptr;
+  float* psf_host = nullptr;
+  hipEvent_t psf_ev = nullptr;
+  bool psf_valid = false;
+  size_t n_resid = 0;
   RtState rt_tv, rt_me;                   // device-side early exit of the TV prior's prox / of the ME-TV inner prox
   size_t n_state[2] = {0, 0}, n_extra = 0, n_prox = 0, n_rtmp = 0, n_dbl = 0;   // elements allocated
   // p holds at least n elements afterwards; what it held is not kept when it grows
@@ -143,6 +152,7 @@ struct Scratch {
   hipError_t need_prox(size_t n) { return grow(prox, n_prox, n); }
   hipError_t need_rtmp(size_t n) { return grow(rtmp, n_rtmp, n); }
   hipError_t need_dbl(size_t n) { return grow(dbl, n_dbl, n); }
+  hipError_t need_resid(size_t n) { return grow(resid, n_resid, n); }
 };
 // The scratch of the current device: a process may drive several GPUs (one sampler handle each); the stateless entry points run on the current device.
 Scratch& scratch_here();
@@ -172,14 +182,17 @@ int check_no_poisson(const Problem& q, const char* who, const char* why);
 int check_poisson(const Problem& q);
 int check_no_wl2(const Problem& q, const char* who, const char* why);
 int check_wl2(const Problem& q);
+int check_no_psf(const Problem& q, const char* who, const char* why);
+int check_psf(const Problem& q);
 bool wl2_pipe_covers(const lmc::StepArgs& A);       // the full-width pipeline has a weighted form of this launch
 bool pois_pipe_covers(const lmc::StepArgs& A);      // the full-width pipeline has a Poisson form of this launch
 int make_step_args(const Problem& q, float a, float t, float b, float pt, float s, lmc::StepArgs& A);
 void sanitize_pointers(lmc::StepArgs& A);
 int variant_of(const Problem& q);
 float tol_of(const Problem& q);
+// psf: the operator of a launch whose data_kind is LMC_DATA_PSF (with its device table and residual buffer); such a launch without it is not covered
 hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0 = nullptr,
-                       float* state1 = nullptr, float* pxbuf = nullptr);
+                       float* state1 = nullptr, float* pxbuf = nullptr, const lmc::PsfOp* psf = nullptr);
 
 // ---- lmc_solve.hip ----
 int cg_solve_fused(const Problem& q, float ts, float* u, const float* rhs, float* r, float* p, float* qq, double* scal,
@@ -195,6 +208,7 @@ int tv_prior_rt_mode(const Problem& q, const lmc::StepArgs& A_probe, float pt);
 lmc::EnergyArgs energy_args(const Problem& q);
 int pois_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
 int wl2_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
+int psf_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
 int me_tv_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, float* extra, float* st0, float* st1,
                  double* dbl /* 2*n_img */, hipStream_t st, RtState* rt);
 
@@ -216,6 +230,7 @@ struct lmc_sampler {
   int wcur = 0;
   float* extra = nullptr;                   // ME-TV inner prox
   float* pxbuf = nullptr;                   // Haar-l1 prox / early-exit TV prox of the current state
+  float* psf_tab = nullptr; float* psf_resid = nullptr;   // large PSF: the device tap table (uploaded at creation) and the residual buffer, [C][H][W]
   float* rtmp = nullptr; double* robj = nullptr; int* rflag = nullptr;   // early-exit TV prox (tv_rtol > 0), pass-by-pass path: pass iterate, objectives, flags
   lmc::host::RtState rt_tv, rt_me;          // early-exit TV prox on the device (tv_prox_rt): of the TV prior / of the ME-TV inner prox
   // launch policy, fixed at creation (lmc_problem fields; their environment variables supply the defaults): see lmc_atomi.h

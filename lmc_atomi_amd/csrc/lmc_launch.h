@@ -192,6 +192,48 @@ hipError_t launch_sapg_update(const double* stat, int C, const SapgParams& P, lo
 }  // namespace lmc
 
 namespace lmc {
+// Large point-spread functions (lmc_psf.hip, lmc_psf_kernel.h): the operator of LMC_DATA_PSF and lmc_psf_apply, kernels up to kPsfMax x kPsfMax.
+constexpr int kPsfMax = LMC_MAX_PSF;
+constexpr int kPsfKP = 40;                                   // tap rows of the device table: kPsfMax padded to whole blocks of 8
+constexpr int kPsfTabFloats = 2 * kPsfMax * kPsfKP;          // the table of one direction (general form, or the two factors in its head); H then H^T
+// what a launch does with u = H x or H^T x
+enum PsfEpi {
+  kPsfRaw = 0,      // out = u
+  kPsfRhoL2,        // out = u - y
+  kPsfRhoWl2,       // out = w (u - y),            y = [2][H][W]: observation, weights
+  kPsfRhoPois,      // out = pois_rho(u, y, beta), y = [2][H][W]: counts, background
+  kPsfSub,          // out -= coef u
+  kPsfOverwrite,    // out = a xin - coef u
+  kPsfEnL2,         // part[image][tile] = sum 1/2 (u - y)^2        (no store of u)
+  kPsfEnWl2,        // part[image][tile] = sum 1/2 w (u - y)^2
+  kPsfEnPois        // part[image][tile] = sum pois_phi(u, y, beta)
+};
+// Host description of a validated PSF and the device table made from it.  tab (host) / tab_dev: [2][kPsfMax * kPsfKP] floats, direction 0 = H (taps
+// flipped, origin mirrored), 1 = H^T, each in the correlation form of the kernel: general g[b * kPsfKP + a], separable gu[kPsfKP] then gv[kPsfKP].
+struct PsfOp {
+  int on = 0;                 // the problem's operator is a PSF
+  int kh = 0, kw = 0, oy = 0, ox = 0;
+  int separable = 0;          // the two-pass form
+  float tab[kPsfTabFloats] = {};
+  const float* tab_dev = nullptr;      // set by whoever owns the device copy (a sampler handle, the stateless scratch)
+  float* resid = nullptr;              // [C][H][W] residual buffer of the step, same owner
+};
+// 1 / 0: h is an outer product by the criterion of lmc_psf_separable (u, v may be NULL)
+int psf_separable(const float* h, int kh, int kw, float* u, float* v);
+// fills kh .. separable and tab from validated geometry; mode: lmc_problem.psf_separable (0 auto, 1 require, 2 forbid).  false: mode 1 on a kernel that
+// fails the criterion
+bool psf_prepare(PsfOp& P, const float* h, int kh, int kw, int oy, int ox, int mode);
+// epi: PsfEpi of lmc_psf_kernel.h, store forms only.  out = epilogue(H x or H^T x); xin: kPsfOverwrite; y: the rho forms
+hipError_t launch_psf(const PsfOp& P, int adjoint, int epi, const float* x, float* out, const float* xin, const float* y, int64_t n_img, int H, int W,
+                      float a, float coef, hipStream_t st);
+// doubles `part` must hold for launch_psf_energy
+size_t psf_energy_partials(int64_t n_img, int H, int W);
+// f_out[c] += the data term's value at x_c (term: 0 Gaussian, 1 weighted, 2 Poisson), float64 by partial sums in a fixed order
+hipError_t launch_psf_energy(const PsfOp& P, int term, const float* x, const float* y, int64_t n_img, int H, int W, float sigma_f, double* part,
+                             double* f_out, hipStream_t st);
+}  // namespace lmc
+
+namespace lmc {
 // SK-ROCK stage 1 (lmc_skrock.hip): out = x + coef * Z, Z the Philox / Box-Muller field of `iteration` that the step kernels and launch_noise draw
 // (same device functions, same counter layout: bit for bit that field), or the caller's field xi.  x, out (and xi): [C][H][W] / n floats, distinct.
 hipError_t launch_skrock_perturb_philox(const float* x, float* out, int64_t C, int H, int W, float coef, uint32_t key0, uint32_t key1,

@@ -53,6 +53,15 @@ int load_problem(const lmc_problem* p, Problem& q) {
     q.data_kind = p->data_kind == LMC_DATA_WL2_BLUR ? LMC_DATA_BLUR : LMC_DATA_IDENTITY;
     q.wl2 = 1;
   }
+  // a large PSF: one operator kind of its own plus the same two flags (check_psf, check_no_psf) -- NOT LMC_DATA_BLUR, whose taps stay empty: a path
+  // that was not taught about the PSF meets an unknown data kind, not a blur without taps
+  if (p->data_kind >= LMC_DATA_PSF && p->data_kind <= LMC_DATA_WL2_PSF) {
+    if (p->kh || p->kw || p->oy || p->ox) return fail(LMC_E_INVALID, "data_kind %d (large PSF) takes its geometry in the psf_* fields: kh = kw = oy = ox = 0", p->data_kind);
+    if (p->data_kind == LMC_DATA_WL2_PSF && p->mask_dev) return fail(LMC_E_INVALID, "data_kind %d (weighted Gaussian term) takes no mask_dev: put the mask into the weights", p->data_kind);
+    q.data_kind = LMC_DATA_PSF;
+    q.pois = p->data_kind == LMC_DATA_POISSON_PSF;
+    q.wl2 = p->data_kind == LMC_DATA_WL2_PSF;
+  }
   q.sigma_f = p->sigma_f;
   q.y = p->y_dev;
   q.mask = p->mask_dev;
@@ -68,6 +77,18 @@ int load_problem(const lmc_problem* p, Problem& q) {
       if (!p->y_dev) return fail(LMC_E_INVALID, "data term needs y_dev");
       int rc = fill_taps(q.taps, p->h_host, p->kh, p->kw, p->oy, p->ox);
       if (rc) return rc;
+      break;
+    }
+    case LMC_DATA_PSF: {
+      if (!p->y_dev) return fail(LMC_E_INVALID, "data term needs y_dev");
+      if (!p->h_host) return fail(LMC_E_INVALID, "PSF pointer (h_host) is NULL");
+      if (p->psf_kh < 1 || p->psf_kw < 1 || p->psf_kh > lmc::kPsfMax || p->psf_kw > lmc::kPsfMax)
+        return fail(LMC_E_INVALID, "PSF %dx%d outside 1..%d", p->psf_kh, p->psf_kw, lmc::kPsfMax);
+      if (p->psf_oy >= p->psf_kh || p->psf_ox >= p->psf_kw)
+        return fail(LMC_E_INVALID, "PSF offset (%d,%d) outside the kernel", p->psf_oy, p->psf_ox);
+      if (p->psf_separable < 0 || p->psf_separable > 2) return fail(LMC_E_INVALID, "psf_separable must be 0 (auto), 1 (require) or 2 (forbid)");
+      if (!lmc::psf_prepare(q.psf, p->h_host, p->psf_kh, p->psf_kw, p->psf_oy, p->psf_ox, p->psf_separable))
+        return fail(LMC_E_INVALID, "psf_separable = 1 on a kernel that is no outer product to 2^-22 of every tap (lmc_psf_separable)");
       break;
     }
     default: return fail(LMC_E_INVALID, "unknown data_kind %d", p->data_kind);
@@ -181,7 +202,7 @@ int check_no_poisson(const Problem& q, const char* who, const char* why) {
 // What the entry points that do take it (MYULA, SK-ROCK, lmc_fused_eval) refuse with it: everything that is not the fused step of the tiled kernel or of
 // the full-width pipeline's Poisson instantiations.
 int check_poisson(const Problem& q) {
-  if (!q.pois) return LMC_OK;
+  if (!q.pois || q.psf.on) return LMC_OK;     // (a large PSF: check_psf -- its prior launch is that of a problem without a data term)
   if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the Poisson data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
   const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
   if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "the Poisson data term with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0");
@@ -202,7 +223,7 @@ int check_no_wl2(const Problem& q, const char* who, const char* why) {
 // What the entry points that do take it (MYULA, MYMALA, SK-ROCK, lmc_fused_eval) refuse with it: everything that is not the fused step of the tiled
 // kernel or of the full-width pipeline's weighted instantiations.
 int check_wl2(const Problem& q) {
-  if (!q.wl2) return LMC_OK;
+  if (!q.wl2 || q.psf.on) return LMC_OK;      // (a large PSF: check_psf)
   if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
   const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
   if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0");
@@ -211,6 +232,22 @@ int check_wl2(const Problem& q) {
   const int v = variant_of(q);
   if (v != 0 && v != 1 && v != 7)
     return fail(LMC_E_UNSUPPORTED, "step_variant %d has no form of the weighted Gaussian data term: 0 (auto), 1 (tile) or 7 (pipe, where it covers the problem)", v);
+  return LMC_OK;
+}
+
+// The entry points that have no form of the large PSF refuse a problem that carries one.
+int check_no_psf(const Problem& q, const char* who, const char* why) {
+  if (!q.psf.on) return LMC_OK;
+  return fail(LMC_E_UNSUPPORTED, "%s does not take a large PSF (LMC_DATA_PSF, LMC_DATA_POISSON_PSF, LMC_DATA_WL2_PSF): %s", who, why);
+}
+
+// What the entry points that do take it (MYULA, SK-ROCK, lmc_fused_eval) refuse with it: what does not split into residual, prior launch and adjoint.
+int check_psf(const Problem& q) {
+  if (!q.psf.on) return LMC_OK;
+  if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "a large PSF has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
+  const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
+  if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "a large PSF with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0");
+  if (q.tv_warm_asked) return fail(LMC_E_UNSUPPORTED, "a large PSF with tv_warm: the warm-started dual is not built for it");
   return LMC_OK;
 }
 
@@ -340,7 +377,31 @@ static hipError_t launch_step_wl2(const lmc::StepArgs& A, int variant, hipStream
 // The box-constrained forms.  Separable priors: one elementwise launch forms clip(prox) into pxbuf, then the step of the variant asked for consumes it.
 // TV priors: the pipe kernel's box instantiations (isotropic; auto, 7, 8) or the tile kernel's (either form; auto, 1); a forced variant without a box
 // form is not covered.
-hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
+// A large PSF: the update as three launches.  The residual r = rho(H x) into psf->resid; the step of the same arguments without a data term
+// (t = 0: every prior, the box, the noise and the forced variant as they are there); x_out -= t sigma_f H^T r.  Without prox and noise the second
+// launch has nothing to do and the third writes a x - t sigma_f H^T r.
+static hipError_t launch_step_psf(const lmc::StepArgs& A, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf,
+                                  const lmc::PsfOp* psf) {
+  if (!psf || !psf->on || !psf->tab_dev || !psf->resid) return hipErrorInvalidConfiguration;
+  if (A.ncvx_kind != LMC_NCVX_NONE || A.extra || A.tv_in || A.tv_out || A.f_out || A.g_out || A.rt_kc) return hipErrorInvalidConfiguration;
+  const int rho = A.pois ? lmc::kPsfRhoPois : A.wl2 ? lmc::kPsfRhoWl2 : lmc::kPsfRhoL2;
+  hipError_t e = lmc::launch_psf(*psf, 0, rho, A.x_in, psf->resid, nullptr, A.y, A.C, A.H, A.W, 0.f, 0.f, st);
+  if (e != hipSuccess) return e;
+  const float coef = A.t * A.sigma_f;
+  if (A.b == 0.f && A.s == 0.f) {
+    if (name) *name = "psf_conv_kernel";
+    return lmc::launch_psf(*psf, 1, lmc::kPsfOverwrite, psf->resid, A.x_out, A.x_in, nullptr, A.C, A.H, A.W, A.a, coef, st);
+  }
+  lmc::StepArgs B = A;
+  B.data_kind = LMC_DATA_NONE; B.t = 0.f; B.pois = 0; B.wl2 = 0;
+  e = launch_step(B, variant, st, name, state0, state1, pxbuf);
+  if (e != hipSuccess) return e;
+  return lmc::launch_psf(*psf, 1, lmc::kPsfSub, psf->resid, A.x_out, nullptr, nullptr, A.C, A.H, A.W, 0.f, coef, st);
+}
+
+hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf,
+                       const lmc::PsfOp* psf) {
+  if (A_in.data_kind == LMC_DATA_PSF) return launch_step_psf(A_in, variant, st, name, state0, state1, pxbuf, psf);
   if (A_in.pois) return launch_step_pois(A_in, variant, st, name, state0, state1, pxbuf);
   if (A_in.wl2) return launch_step_wl2(A_in, variant, st, name, state0, state1, pxbuf);
   if (!A_in.box) return launch_step_nobox(A_in, variant, st, name, state0, state1, pxbuf);

@@ -96,6 +96,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   rc = check_prox_prior(s->prob, cfg->tau / cfg->gamma);
   if (!rc) rc = check_poisson(s->prob);
   if (!rc) rc = check_wl2(s->prob);
+  if (!rc) rc = check_psf(s->prob);
   if (rc) { delete s; return rc; }
   if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }
   s->C = cfg->n_chains;
@@ -125,6 +126,13 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     if (e == hipSuccess) e = hipMalloc(&s->tvstate[1], 4 * nbytes);
   }
   if (e == hipSuccess && s->prob.ncvx_kind == LMC_NCVX_ME_TV) e = hipMalloc(&s->extra, nbytes);
+  if (e == hipSuccess && s->prob.psf.on) {     // large PSF: the handle uploads the tap table once and owns the residual buffer
+    e = hipMalloc(&s->psf_tab, sizeof s->prob.psf.tab);
+    if (e == hipSuccess) e = hipMemcpy(s->psf_tab, s->prob.psf.tab, sizeof s->prob.psf.tab, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&s->psf_resid, nbytes);
+    s->prob.psf.tab_dev = s->psf_tab;
+    s->prob.psf.resid = s->psf_resid;
+  }
   if (e == hipSuccess && (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 || s->prob.prior_kind == LMC_PRIOR_EPROX || s->prob.prox_scale ||
                           (s->base.box && s->base.prior_kind != LMC_PRIOR_TV_ISO))) e = hipMalloc(&s->pxbuf, nbytes);
   if (e == hipSuccess && s->prob.tv_rtol > 0.f && s->base.prior_kind == LMC_PRIOR_TV_ISO) {
@@ -149,6 +157,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     if (q.prox_scale || q.box) { s->pol_pair = 0; s->pol_blockpair = 0; }   // array-valued epsg, box constraint: the prox is its own launch before every step
     if (q.wl2) { s->pol_pair = 0; s->pol_blockpair = 0; }                   // weighted Gaussian data term: the same
     if (q.pois) { s->pol_pair = 0; s->pol_blockpair = 0; }                  // Poisson data term: one iteration per launch (the pair kernels have no form of it)
+    if (q.psf.on) { s->pol_pair = 0; s->pol_blockpair = 0; }                // large PSF: three launches per iteration
   }
   if (e == hipSuccess && s->prob.tv_warm) {
     lmc::StepArgs probe = s->base;
@@ -174,7 +183,7 @@ void lmc_sampler_destroy(lmc_sampler* s) {
   if (!s) return;
   DeviceGuard dg(s->device);
   for (float* b : {s->xmid[0], s->xmid[1], s->xspare, s->zero_y, s->xhat, s->ydual, s->uw, s->uw2, s->rhs, s->cr, s->cp, s->cq, s->ctmp, s->xi, s->htb, s->tvstate[0], s->tvstate[1], s->extra, s->pxbuf,
-                   s->mx, s->xp, s->mxp, s->tvwarm[0], s->tvwarm[1], s->rtmp})
+                   s->psf_tab, s->psf_resid, s->mx, s->xp, s->mxp, s->tvwarm[0], s->tvwarm[1], s->rtmp})
     if (b) (void)hipFree(b);
   if (s->robj) (void)hipFree(s->robj);
   if (s->rflag) (void)hipFree(s->rflag);
@@ -226,6 +235,7 @@ static int sampler_energies_at(lmc_sampler* s, const float* x, double* f_out_dev
   {
     int rc = pois_energy(s->prob, x, s->C, f_out_dev, st);
     if (!rc) rc = wl2_energy(s->prob, x, s->C, f_out_dev, st);
+    if (!rc) rc = psf_energy(s->prob, x, s->C, f_out_dev, st);
     if (rc) return rc;
   }
   if (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 && g_out_dev)
@@ -292,7 +302,7 @@ static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool 
   int rc = me_tv_extra(s, A, st);   // inner prox of the Moreau-envelope term, then the fused step
   if (rc) return rc;
   if (ov && ov->ev_begin) HIP_TRY(hipEventRecord(ov->ev_begin, st));
-  hipError_t e = launch_step(A, variant_of(s->prob), st, kname, s->tvstate[0], s->tvstate[1], s->pxbuf);
+  hipError_t e = launch_step(A, variant_of(s->prob), st, kname, s->tvstate[0], s->tvstate[1], s->pxbuf, s->prob.psf.on ? &s->prob.psf : nullptr);
   if (e == hipErrorInvalidConfiguration) return fail(LMC_E_UNSUPPORTED, "no step-kernel variant covers this configuration");
   HIP_TRY(e);
   if (ov && ov->ev_end) HIP_TRY(hipEventRecord(ov->ev_end, st));
@@ -476,7 +486,7 @@ static int myula_single(lmc_sampler* s, SideMoments& m, const float* noise, bool
     kname = "myula_step_pipe_kernel(warm)";
     s->wcur ^= 1;
   } else {
-    e = launch_step(A, variant_of(s->prob), st, &kname, s->tvstate[0], s->tvstate[1], s->pxbuf);
+    e = launch_step(A, variant_of(s->prob), st, &kname, s->tvstate[0], s->tvstate[1], s->pxbuf, s->prob.psf.on ? &s->prob.psf : nullptr);
   }
   if (e == hipErrorInvalidConfiguration)
     return fail(LMC_E_UNSUPPORTED, s->base.box ? "step_variant %d has no box-constrained form of this prior (TV: auto, 1 tile, 7 / 8 pipe where the pipe covers the problem)"
@@ -568,6 +578,7 @@ int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   if (s->tvwarm[0]) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA needs a proposal mean that is a function of x alone: tv_warm is not allowed"); }
   if (s->rtmp || s->rt_tv.kc) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA with tv_rtol > 0 is not built (use the fixed-count prox, tv_rtol = 0)"); }
   if (s->prob.prox_scale) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA takes a scalar epsg (the reference's array-valued epsg is MYULA's, algs.py:509)"); }
+  if (s->prob.psf.on) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_psf(q, "MYMALA", "its Metropolis ratio is pinned for the fused step and its energy by-products, which the three-launch PSF step does not form; use MYULA or SK-ROCK"); }
   if (s->prob.pois) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_poisson(q, "MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK"); }
   if (s->prob.box) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_box(q, "MYMALA", "its target would be +infinity outside the box, where MYULA's proposals land; use MYULA"); }
   if (s->prob.prior_kind == LMC_PRIOR_EPROX) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA does not take a closed-form prior (LMC_PRIOR_EPROX): the prior has a prox and no value g(x), so its Metropolis target exp(-f - epsg g) is undefined; use MYULA"); }
@@ -873,6 +884,7 @@ int lmc_ulpda_create(const lmc_ulpda_config* cfg, lmc_sampler** out) {
   rc = load_problem(&pr, s->prob);
   if (!rc) rc = check_no_wl2(s->prob, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f Op^T W Op)^{-1}, which is not built; use MYULA");
   if (!rc) rc = check_no_poisson(s->prob, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA");
+  if (!rc) rc = check_no_psf(s->prob, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f H^T H)^{-1}, which is not built for a large PSF; use MYULA");
   if (!rc) rc = check_no_box(s->prob, "ULPDA", "its prior enters through the dual ball of g o A, which has no box form; use MYULA");
   if (rc) { delete s; return rc; }
   if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }

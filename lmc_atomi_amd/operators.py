@@ -104,6 +104,73 @@ class Convolve2D(LinearOperator):
         return self._apply(y, True)
 
 
+class PSF(LinearOperator):
+    """The same zero-padded "same" convolution with origin ``offset`` for a realistic point-spread function: ``h`` of 1 .. 33 taps in each direction
+    (a Gaussian of sigma = 5 px at +-3 sigma, a motion blur, an Airy pattern), any origin inside it (default: the centre tap).  ``matvec`` = H x,
+    ``rmatvec`` = H^T x (lmc_psf_apply).  ``separable``: None -- two 1-D passes where ``h`` is an outer product to a fraction of float32 rounding
+    (``lmc_psf_separable``: :attr:`factors`), the general 2-D form elsewhere; True -- require the two-pass form (``ValueError`` where ``h`` is no outer
+    product); False -- always the general form.  As ``Op`` of :class:`L2` (with or without ``weights``) and :class:`Poisson` in MYULA, SK-ROCK and
+    :func:`EstimatePriorWeight`; MYMALA, ULPDA, ``L2.prox``, the non-convex terms, ``TV(rtol > 0)`` and ``TV(warm=True)`` raise ``NotImplementedError``.
+    :class:`Convolve2D` (up to 9 x 9, inside the fused step kernels) is unchanged."""
+
+    def __init__(self, dims, h, offset=None, separable=None):
+        self.dims = (int(dims[0]), int(dims[1]))
+        n = self.dims[0] * self.dims[1]
+        super().__init__((n, n))
+        h64 = np.asarray(h, dtype=np.float64)
+        if h64.ndim != 2:
+            raise ValueError("h must be 2-D")
+        kh, kw = h64.shape
+        if not (1 <= kh <= _capi.MAX_PSF and 1 <= kw <= _capi.MAX_PSF):
+            raise ValueError(f"PSF of {kh}x{kw} taps: 1 .. {_capi.MAX_PSF} in each direction are supported")
+        if not np.all(np.isfinite(h64)):
+            raise ValueError("the taps of the PSF must be finite")
+        self.h = np.ascontiguousarray(h64, dtype=np.float32)
+        self.offset = (kh // 2, kw // 2) if offset is None else (int(offset[0]), int(offset[1]))
+        if not (0 <= self.offset[0] < kh and 0 <= self.offset[1] < kw):
+            raise ValueError(f"offset {self.offset} outside the {kh}x{kw} kernel")
+        if separable not in (None, True, False):
+            raise ValueError("separable must be None (auto), True (require) or False (forbid)")
+        self.separable = separable
+        self._factors = None
+        if separable is not False:      # the library's own test (host only: no device needed)
+            u, v = np.zeros(kh, dtype=np.float32), np.zeros(kw, dtype=np.float32)
+            rc = _capi.load().lmc_psf_separable(_dev.fptr(self.h), kh, kw, _dev.fptr(u), _dev.fptr(v))
+            if rc < 0:
+                _capi.check(rc)
+            if rc == 1:
+                self._factors = (u, v)
+            elif separable:
+                raise ValueError("separable=True, but h is no outer product u v^T to 2^-22 of every tap (lmc_psf_separable)")
+
+    @property
+    def factors(self):
+        """``(u, v)`` with ``h = u v^T`` where the two-pass form runs, else ``None``."""
+        return self._factors
+
+    def _mode(self):
+        return 2 if self.separable is False else (1 if self.separable else 0)
+
+    def descriptor(self):
+        """The operator's part of a data-term descriptor (``lmc_problem.psf_*``)."""
+        return {"h": self.h, "offset": self.offset, "psf_separable": self._mode()}
+
+    def _apply(self, x, adjoint):
+        import torch
+        t, n_img, _ = self._batch(x, self.shape[1])
+        out = torch.empty_like(t)
+        kh, kw = self.h.shape
+        _dev.run(t, "lmc_psf_apply", _dev.ptr(t), _dev.ptr(out), n_img, self.dims[0], self.dims[1],
+                 _dev.fptr(self.h), kh, kw, self.offset[0], self.offset[1], 1 if adjoint else 0, self._mode())
+        return _dev.like_input(out.reshape(tuple(np.shape(x))), x)
+
+    def matvec(self, x):
+        return self._apply(x, False)
+
+    def rmatvec(self, y):
+        return self._apply(y, True)
+
+
 class Gradient(LinearOperator):
     """Stacked forward differences ``[d_row x; d_col x]`` (zero in the last row / column) --
     drop-in for ``pylops.Gradient(dims, sampling=1, edge=False, kind='forward')``

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _capi, _dev
-from .operators import Convolve2D, Diagonal, Identity, LinearOperator
+from .operators import PSF, Convolve2D, Diagonal, Identity, LinearOperator
 
 
 _warned_pass_by_pass = False
@@ -125,7 +125,7 @@ class _Problem:
         p.sigma_f = float(data.get("sigma_f", 0.0))
         if data.get("y") is not None:
             # (a Poisson term: [2][H][W], the counts then the background; a weighted Gaussian term: the observation then the weights)
-            y = _dev.to_dev(data["y"], dev).reshape(((2,) if p.data_kind in _capi.POISSON_KINDS + _capi.WL2_KINDS else ()) + self.dims)
+            y = _dev.to_dev(data["y"], dev).reshape(((2,) if p.data_kind in _capi.TWO_PLANE_KINDS else ()) + self.dims)
             self._keep.append(y)
             p.y_dev = y.data_ptr()
         if data.get("mask") is not None:
@@ -138,6 +138,13 @@ class _Problem:
             p.kh, p.kw = h.shape
             p.oy, p.ox = data["offset"]
             p.h_host = _dev.fptr(h)
+        if p.data_kind in _capi.PSF_KINDS:      # the large PSF: its geometry in fields of its own (kh = kw = oy = ox = 0), the taps at h_host
+            h = np.ascontiguousarray(data["h"], dtype=np.float32)
+            self._keep.append(h)
+            p.psf_kh, p.psf_kw = h.shape
+            p.psf_oy, p.psf_ox = data["offset"]
+            p.h_host = _dev.fptr(h)
+            p.psf_separable = int(data.get("psf_separable", 0))
         p.prior_kind = prior["prior_kind"]
         p.prior_sigma = float(prior.get("prior_sigma", 0.0))
         # (ULPDA's anisotropic descriptor carries no prox: tv_niter stays 0)
@@ -246,8 +253,8 @@ class L2(ProxOperator):
             raise NotImplementedError("L2(weights=...) with Op = Diagonal: there is no weighted mask kind -- a binary mask m on a blur is weights = m")
         if self.b is None:
             raise NotImplementedError("L2(weights=...) without b: the weights belong to the data term; as a prior they have no meaning")
-        if self.Op is not None and not isinstance(self.Op, (Convolve2D, Identity)):
-            raise NotImplementedError(f"no device functor for L2(weights=...) with Op of type {type(self.Op).__name__} (Convolve2D or Identity)")
+        if self.Op is not None and not isinstance(self.Op, (Convolve2D, PSF, Identity)):
+            raise NotImplementedError(f"no device functor for L2(weights=...) with Op of type {type(self.Op).__name__} (Convolve2D, PSF or Identity)")
         w = _host(weights).astype(np.float64)
         y = _host(self.b).astype(np.float64)
         if self.dims is None:      # the image shape: `dims`, else the operator's, else that of an [H, W] array of weights or observations
@@ -283,7 +290,7 @@ class L2(ProxOperator):
     def grad_lipschitz(self):
         """``L_f = sigma * max(w) * ||Op||^2`` with ``||Op|| <= sum |h|`` for a convolution and the factor 1 for a mask (entries in [0, 1]), the
         identity or no operator; ``max(w) = 1`` without weights.  Host arithmetic, no GPU."""
-        op2 = float(np.abs(np.asarray(self.Op.h, dtype=np.float64)).sum()) ** 2 if isinstance(self.Op, Convolve2D) else 1.0
+        op2 = float(np.abs(np.asarray(self.Op.h, dtype=np.float64)).sum()) ** 2 if isinstance(self.Op, (Convolve2D, PSF)) else 1.0
         wmax = float(np.max(self.weights)) if self.weights is not None else 1.0
         return self.sigma * wmax * op2
 
@@ -292,6 +299,8 @@ class L2(ProxOperator):
         """As the data term f of the sampler."""
         if self.weights is not None:
             yw = self._buffer() if torch.cuda.is_available() else self._yw      # (without a device: the host array, for whoever only reads the description)
+            if isinstance(self.Op, PSF):
+                return {"data_kind": _capi.DATA_WL2_PSF, "sigma_f": self.sigma, "y": yw, **self.Op.descriptor()}
             if isinstance(self.Op, Convolve2D):
                 return {"data_kind": _capi.DATA_WL2_BLUR, "sigma_f": self.sigma, "y": yw, "h": self.Op.h, "offset": self.Op.offset}
             return {"data_kind": _capi.DATA_WL2_IDENTITY, "sigma_f": self.sigma, "y": yw}
@@ -299,6 +308,8 @@ class L2(ProxOperator):
             if self.b is None:
                 raise NotImplementedError("L2 without b as a data term: use it as the prior instead")
             return {"data_kind": _capi.DATA_IDENTITY, "sigma_f": self.sigma, "y": self.b}
+        if isinstance(self.Op, PSF):
+            return {"data_kind": _capi.DATA_PSF, "sigma_f": self.sigma, "y": self.b, **self.Op.descriptor()}
         if isinstance(self.Op, Convolve2D):
             return {"data_kind": _capi.DATA_BLUR, "sigma_f": self.sigma, "y": self.b, "h": self.Op.h,
                     "offset": self.Op.offset}
@@ -336,6 +347,8 @@ class L2(ProxOperator):
         With a blur operator: ``niter`` warm-started CG iterations on the GPU (lmc_l2_prox)."""
         if self.bounds is not None:
             return _box_prox(self, x, tau)
+        if isinstance(self.Op, PSF):
+            raise NotImplementedError("L2.prox with a large PSF: the implicit step (I + tau sigma Op^T Op)^{-1} is not built for it (lmc_l2_prox refuses it)")
         if self.weights is not None:
             raise NotImplementedError("L2.prox with weights: the implicit step (I + tau sigma Op^T W Op)^{-1} is not built (lmc_l2_prox refuses it)")
         if self.Op is None and self.b is None:
@@ -380,8 +393,8 @@ class Poisson(ProxOperator):
 
     def __init__(self, Op, b, background, sigma=1.0, dims=None):
         super().__init__(Op, True)
-        if not isinstance(Op, (Convolve2D, Diagonal, Identity)):
-            raise NotImplementedError(f"no device functor for Poisson with Op of type {type(Op).__name__} (Convolve2D, Diagonal or Identity)")
+        if not isinstance(Op, (Convolve2D, PSF, Diagonal, Identity)):
+            raise NotImplementedError(f"no device functor for Poisson with Op of type {type(Op).__name__} (Convolve2D, PSF, Diagonal or Identity)")
         y = _host(b).astype(np.float64)
         # the image shape: `dims`, else the operator's, else that of an [H, W] array of counts or background
         for cand in (dims, getattr(Op, "dims", None), y.shape if y.ndim == 2 else None, np.shape(background) if np.ndim(background) == 2 else None):
@@ -416,6 +429,8 @@ class Poisson(ProxOperator):
 
     def descriptor(self):
         yb = self._buffer() if torch.cuda.is_available() else self._yb      # (without a device: the host array, for whoever only reads the description)
+        if isinstance(self.Op, PSF):
+            return {"data_kind": _capi.DATA_POISSON_PSF, "sigma_f": self.sigma, "y": yb, **self.Op.descriptor()}
         if isinstance(self.Op, Convolve2D):
             return {"data_kind": _capi.DATA_POISSON_BLUR, "sigma_f": self.sigma, "y": yb, "h": self.Op.h, "offset": self.Op.offset}
         if isinstance(self.Op, Diagonal):
@@ -425,7 +440,7 @@ class Poisson(ProxOperator):
     def grad_lipschitz(self):
         """``L_f = sigma * max(b / background^2) * ||Op||^2`` with ``||Op|| <= sum |h|`` for a convolution and the factor 1 for a mask (entries in [0, 1])
         or the identity.  Host arithmetic, no GPU."""
-        op2 = float(np.abs(np.asarray(self.Op.h, dtype=np.float64)).sum()) ** 2 if isinstance(self.Op, Convolve2D) else 1.0
+        op2 = float(np.abs(np.asarray(self.Op.h, dtype=np.float64)).sum()) ** 2 if isinstance(self.Op, (Convolve2D, PSF)) else 1.0
         return self.sigma * float(np.max(self.b / self.background ** 2)) * op2
 
     def _problem(self):
