@@ -133,13 +133,33 @@ typedef enum lmc_prior_kind {
                            *  for lmc_energies. */
   LMC_PRIOR_HAAR_L1 = 5, /* g = sigma * || detail coefficients of the 3-level orthonormal Haar transform of x ||_1 (BASELINE
                           * config 5; no counterpart in the reference): prox = W^T soft(W x, t*sigma); H, W multiples of 8 */
-  LMC_PRIOR_EPROX = 6    /* (ABI 3) a separable prior whose prox is one of the closed forms of prox.py (lmc_eprox_kind below; prox.py:18-85, used
+  LMC_PRIOR_EPROX = 6,   /* (ABI 3) a separable prior whose prox is one of the closed forms of prox.py (lmc_eprox_kind below; prox.py:18-85, used
                           * inside the reference's samplers at prox_lmc.py:106,115): prox(x) = prox_X(x; p0, p1) pixel by pixel, evaluated inside
                           * the fused step kernel.  lmc_problem.eprox_kind / eprox_p0 / eprox_p1; eprox_scale_mask bit i set = parameter i is
                           * multiplied by the prox parameter (epsg * gamma in MYULA) -- e.g. prox_laplace(x, gamma * lam): p0 = lam, mask = 1.
                           * MYULA steps and lmc_fused_eval; its value g(x) is not defined for every family: lmc_energies returns g = 0.
                           * lmc_mymala_create returns LMC_E_UNSUPPORTED for it: without a value of g the Metropolis target exp(-f - epsg*g) is
                           * undefined (lmc_prior_statistic and lmc_sampler_sapg refuse it for the same reason). */
+  /* Daubechies wavelet-l1 prior (appended; LMC_ATOMI_ABI_VERSION stays 4 and sizeof(lmc_problem) 200).  Build-specified; this text is its definition.
+   * p in 1 .. 4 vanishing moments, L in 1 .. LMC_MAX_WAVELET_LEVELS levels.  The kind reads its two parameters from fields that are otherwise unread
+   * for it (the struct has no hole left):  tv_niter = L (levels),  eprox_kind = p;  prior_sigma = sigma.
+   *   scaling filter h[0 .. 2p-1]: the extremal-phase (minimum-phase) Daubechies filter -- P(y) = sum_{k<p} C(p-1+k, k) y^k with y = (2 - z - 1/z)/4, of
+   *   every root pair {z, 1/z} the root inside the unit circle, times (1 + z)^p, normalised to sum h = sqrt 2 (db2 = 0.48296291, 0.83651630,
+   *   0.22414387, -0.12940952; lmc_wavelet_filter returns the compiled-in taps);  wavelet filter g[k] = (-1)^k h[2p-1-k].
+   *   one level on a periodic signal a of even length n >= 2p:  lo[m] = sum_k h[k] a[(2m+k) mod n],  hi[m] = sum_k g[k] a[(2m+k) mod n],  m < n/2.
+   *   2-D: one level along the rows, then along the columns (subbands LL, and the three details), deeper levels on LL; W over L levels is orthonormal.
+   *   g(x) = sigma * sum |all detail coefficients of all levels| (the last LL is not penalised);  prox_{t g}(x) = W^T S(W x), S the soft threshold
+   *   t sigma on the details -- exact, no inner iteration.  p = 1, L = 3 is the value and prox of LMC_PRIOR_HAAR_L1 (other kernels, other rounding).
+   * Preconditions (LMC_E_INVALID otherwise): H and W multiples of 2^L, min(H, W) >> (L - 1) >= 2p (every level wraps at most once).
+   * Kernels (lmc_wavelet.hip): one launch per level and direction, wav_fwd_kernel / wav_inv_kernel, the tile and its halo in LDS, the threshold fused
+   * into the stores of the forward levels; the prox goes to a buffer the fused step kernel then consumes as a ready-made prox (the route of
+   * LMC_PRIOR_HAAR_L1: the step kernel is that of the same problem with LMC_PRIOR_NONE), so every data term, the Poisson and weighted Gaussian terms
+   * and the large PSF included, takes it.  Workspace: 1.25 state-sized buffers (the thresholded pyramid, the LL ping-pong), owned by the sampler handle
+   * or taken from the scratch of the stateless calls.  The value is formed by partial sums in a fixed order: equal from run to run.
+   * Honoured by lmc_myula_create, lmc_mymala_create, lmc_skrock_create, lmc_fused_eval, lmc_energies, lmc_sampler_energies, lmc_prior_statistic,
+   * lmc_sapg_dimension (d = H W - (H >> L)(W >> L), k = 1), lmc_sampler_sapg, lmc_sampler_set_prior_sigma.  LMC_E_UNSUPPORTED, with the reason in
+   * lmc_last_error: box_enable (not separable, as LMC_PRIOR_HAAR_L1), prox_scale, lmc_ulpda_create.  iterations_per_launch is ignored. */
+  LMC_PRIOR_WAVELET_L1 = 7
 } lmc_prior_kind;
 
 typedef enum lmc_ncvx_kind {
@@ -167,6 +187,7 @@ typedef enum lmc_noise_mode {
 #define LMC_MAX_SKROCK_STAGES 64
 #define LMC_MAX_CHAIN_GROUPS 64
 #define LMC_MAX_COV_PROBES 32
+#define LMC_MAX_WAVELET_LEVELS 8   /* LMC_PRIOR_WAVELET_L1: levels of the transform */
 
 /* Geometry + potential U(x) = f(x) + eps*g(x).  Plain data; copied by the callee. */
 typedef struct lmc_problem {
@@ -187,7 +208,7 @@ typedef struct lmc_problem {
   /* prior */
   int32_t prior_kind;       /* lmc_prior_kind */
   float prior_sigma;        /* multiplicative coefficient of g (tau_reg = 0.3 at prox_lmc_deconv.py:116-122) */
-  int32_t tv_niter;         /* LMC_PRIOR_TV_ISO: number of dual iterations (niter_tv = 10) */
+  int32_t tv_niter;         /* LMC_PRIOR_TV_ISO: number of dual iterations (niter_tv = 10); LMC_PRIOR_WAVELET_L1: the levels of the transform */
   float tv_step;            /* dual step is tv_step / (prox parameter); 0 -> 1/8 */
   const float* tv_betas_host; /* tv_niter momentum coefficients, host; NULL -> UNLocBoX/pyproximal sequence */
   /* non-log-concave data term of algs.L2_ncvx_tv (algs.py:22-291): f(x) = sigma_f/2||Hx-y||^2 - ncvx_lambda * env_gamma(TV)(x).
@@ -249,7 +270,7 @@ typedef struct lmc_problem {
   int32_t moments_bg_workgroups;
   int32_t graph_replay;
   /* LMC_PRIOR_EPROX */
-  int32_t eprox_kind;             /* lmc_eprox_kind */
+  int32_t eprox_kind;             /* lmc_eprox_kind; LMC_PRIOR_WAVELET_L1: p, the vanishing moments of the filter (1 .. 4) */
   float eprox_p0, eprox_p1;
   int32_t eprox_scale_mask;
   /* Array-valued epsg (algs.py:509,539-542: "float or np.ndarray"; the prox parameter at algs.py:569 is then the array epsg * gamma, which the
@@ -274,7 +295,7 @@ typedef struct lmc_problem {
    *    launch).  LMC_PRIOR_NONE: the indicator alone, prox = projection.
    * Bounds: box_lo < box_hi, neither NaN (else LMC_E_INVALID); infinite ends are allowed ((0, +inf) is positivity).
    * Honoured by lmc_myula_create / lmc_sampler_step and lmc_fused_eval (the prox, and the a, t, b combination with it).  LMC_E_UNSUPPORTED, with the reason
-   * in lmc_last_error: LMC_PRIOR_HAAR_L1 (not separable: clipping its prox is not the prox); tv_rtol > 0; tv_warm; lmc_mymala_create (the target would be +inf
+   * in lmc_last_error: LMC_PRIOR_HAAR_L1 and LMC_PRIOR_WAVELET_L1 (not separable: clipping their prox is not the prox); tv_rtol > 0; tv_warm; lmc_mymala_create (the target would be +inf
    * outside the box); lmc_ulpda_create; lmc_skrock_create; lmc_sampler_sapg / lmc_sampler_set_prior_sigma on a handle with a box (the d / k homogeneity argument
    * does not hold on a bounded set); a forced step_variant without a box form.
    * lmc_energies, lmc_sampler_energies and lmc_prior_statistic keep reporting sigma g(x) WITHOUT the indicator: MYULA iterates live in the Moreau-Yosida
@@ -342,6 +363,18 @@ int lmc_energies(const lmc_problem* prob, const float* x_dev, int64_t n_img,
 
 /* out = prox_{thr * ||W_detail . ||_1}(x): 3-level orthonormal Haar, soft threshold of the detail coefficients.  H, W % 8 == 0. */
 int lmc_haar_l1_prox(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, float thr, void* stream);
+
+/* The transform of LMC_PRIOR_WAVELET_L1 (its text above is the definition; p in 1 .. 4, levels in 1 .. LMC_MAX_WAVELET_LEVELS, the shape
+ * preconditions there: LMC_E_INVALID otherwise).
+ * lmc_wavelet_filter: host only, no device needed.  The compiled-in scaling taps h[0 .. 2p-1] in float64 into h_out (8 doubles are enough), their
+ * number into *len_out (nullable).
+ * lmc_wavelet_apply: out = W x (inverse == 0) or W^T x (inverse != 0) for n_img images, not in place.  Coefficients are in Mallat layout: the
+ * approximation at the top-left, (H >> levels) x (W >> levels); the details of level j in the three other quadrants of the (H >> (j-1)) x (W >> (j-1))
+ * corner -- rows-hi (filtered g along the rows) to the right, columns-hi below, both in the lower right.
+ * lmc_wavelet_l1_prox: out = W^T S(W x), S the soft threshold thr >= 0 on every detail coefficient; not in place. */
+int lmc_wavelet_filter(int32_t p, double* h_out, int32_t* len_out);
+int lmc_wavelet_apply(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t p, int32_t levels, int32_t inverse, void* stream);
+int lmc_wavelet_l1_prox(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t p, int32_t levels, float thr, void* stream);
 
 /* Chain probes for convergence diagnostics across chains (split R-hat / effective sample size; SURVEY 8(f).3 -- absent in the
  * reference, whose only diagnostics are the per-iterate scalars of prox_lmc_deconv.py:128-133): every image is reduced to a
@@ -476,7 +509,7 @@ int lmc_skrock_create(const lmc_myula_config* cfg, int32_t n_stages, float eta, 
  *
  * lmc_prior_statistic: stat_dev[i] = g(x_i) with weight 1 (n_img doubles on the device): float64 sums of the fp32 per-pixel terms of
  * lmc_energies, every image summed in a fixed order (two runs give equal bits), one streaming read of x and no data term.  Stateless; only
- * struct_size, prior_kind, H and W of prob are read.  LMC_PRIOR_NONE / LMC_PRIOR_EPROX (no defined value): LMC_E_UNSUPPORTED. */
+ * struct_size, prior_kind, H and W of prob are read (LMC_PRIOR_WAVELET_L1: tv_niter and eprox_kind too, its levels and p).  LMC_PRIOR_NONE / LMC_PRIOR_EPROX (no defined value): LMC_E_UNSUPPORTED. */
 int lmc_prior_statistic(const lmc_problem* prob, const float* x_dev, int64_t n_img, double* stat_dev, void* stream);
 
 /* The weight for every later launch of this handle: after the call the handle runs exactly what a sampler created with prior_sigma = sigma
@@ -498,7 +531,7 @@ typedef struct lmc_sapg_config {
 
 /* Host only, no device needed.  lmc_sapg_dimension: the default d and the degree k of the prior of prob (struct_size, prior_kind, H, W are
  * read): L1 (H W, 1), L2 (H W, 2), TV_ISO / TV_ANISO (H W - 1, 1: constants are in the null space of g), HAAR_L1 (H W - (H/8)(W/8), 1: the
- * number of detail coefficients); LMC_PRIOR_NONE / LMC_PRIOR_EPROX: LMC_E_UNSUPPORTED.  Either output may be NULL.
+ * number of detail coefficients), WAVELET_L1 (H W - (H >> L)(W >> L), 1: tv_niter = L and eprox_kind = p are read too); LMC_PRIOR_NONE / LMC_PRIOR_EPROX: LMC_E_UNSUPPORTED.  Either output may be NULL.
  * lmc_sapg_update: *theta_next = theta_{n+1} of the definition above for a prior of degree k = 1, from the same inline function the update
  * kernel of lmc_sampler_sapg is compiled from (for degree k pass step_scale / k and k gbar: the same step).  cfg is checked as by
  * lmc_sampler_sapg and cfg->dim_eff must be > 0 here; n < 0, theta not finite or <= 0, gbar not finite: LMC_E_INVALID. */

@@ -23,6 +23,7 @@ PSF_KINDS = (DATA_PSF, DATA_POISSON_PSF, DATA_WL2_PSF)
 WL2_KINDS = (DATA_WL2_IDENTITY, DATA_WL2_BLUR)
 TWO_PLANE_KINDS = POISSON_KINDS + WL2_KINDS + (DATA_POISSON_PSF, DATA_WL2_PSF)      # y_dev is [2][H][W]
 PRIOR_NONE, PRIOR_L2, PRIOR_L1, PRIOR_TV_ISO, PRIOR_TV_ANISO, PRIOR_HAAR_L1, PRIOR_EPROX = 0, 1, 2, 3, 4, 5, 6
+PRIOR_WAVELET_L1 = 7      # Daubechies wavelet-l1: lmc_problem.tv_niter = levels, eprox_kind = p (the struct has no hole left)
 NOISE_PHILOX, NOISE_INJECTED, NOISE_NONE = 0, 1, 2
 NCVX_NONE, NCVX_MC_TV, NCVX_ME_TV, NCVX_MC_TV_ANISO, NCVX_ME_TV_ANISO = 0, 1, 2, 3, 4
 MAX_BLUR = 9
@@ -31,6 +32,8 @@ MAX_TV_ITERS = 64
 MAX_SKROCK_STAGES = 64
 MAX_CHAIN_GROUPS = 64
 MAX_COV_PROBES = 32
+MAX_WAVELET_LEVELS = 8
+WAVELETS = {"haar": 1, "db1": 1, "db2": 2, "db3": 3, "db4": 4}      # name -> p, the vanishing moments of the filter
 (EPROX_LAPLACE, EPROX_UNCENTERED_LAPLACE, EPROX_GAUSSIAN, EPROX_GEN_GAUSSIAN_4_3, EPROX_GEN_GAUSSIAN_3_2,
  EPROX_GEN_GAUSSIAN_3, EPROX_GEN_GAUSSIAN_4, EPROX_HUBER, EPROX_SMOOTHED_LAPLACE, EPROX_EXP, EPROX_GAMMA,
  EPROX_CHI, EPROX_UNIFORM, EPROX_TRIANGULAR, EPROX_LAPLACE_CONJ) = range(15)
@@ -177,6 +180,9 @@ _SIGNATURES = {
     "lmc_set_cg_tolerance": (C.c_float, [C.c_float]),
     "lmc_chain_probes": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "lmc_haar_l1_prox": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),
+    "lmc_wavelet_filter": (C.c_int, [C.c_int32, _D, C.POINTER(C.c_int32)]),
+    "lmc_wavelet_apply": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "lmc_wavelet_l1_prox": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
     "lmc_dual_project": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),
     "lmc_prox_elementwise": (C.c_int, [C.c_int32, _P, _P, C.c_int64, _F, C.c_int32, _P]),
     "lmc_myula_create": (C.c_int, [C.POINTER(lmc_myula_config), C.POINTER(_P)]),
@@ -256,6 +262,21 @@ def load(path: str | None = None):
 def check(rc: int):
     if rc != 0:
         raise LMCError(rc, load().lmc_last_error().decode("utf-8", "replace"))
+
+
+def check_wavelet(dims, wavelet, levels):
+    """``(p, levels)`` of a wavelet name on ``dims`` images; ``ValueError`` for what the library refuses with LMC_E_INVALID (include/lmc_atomi.h)."""
+    if wavelet not in WAVELETS:
+        raise ValueError(f"wavelet must be one of {sorted(WAVELETS)} (got {wavelet!r})")
+    p, levels = WAVELETS[wavelet], int(levels)
+    if not 1 <= levels <= MAX_WAVELET_LEVELS:
+        raise ValueError(f"levels must be in 1 .. {MAX_WAVELET_LEVELS} (got {levels})")
+    H, W = int(dims[0]), int(dims[1])
+    if H % (1 << levels) or W % (1 << levels):
+        raise ValueError(f"image sides must be multiples of 2^levels = {1 << levels} (got {H} x {W})")
+    if (min(H, W) >> (levels - 1)) < 2 * p:
+        raise ValueError(f"{levels} levels of {wavelet} need min(H, W) >> (levels - 1) >= {2 * p} (got {H} x {W}): the coarsest level must hold the filter")
+    return p, levels
 
 
 def exported_symbols():

@@ -177,13 +177,16 @@ def _stat_problem(proxg, dims):
     p = _capi.lmc_problem()
     p.struct_size = C.sizeof(_capi.lmc_problem)
     p.H, p.W = int(dims[0]), int(dims[1])
-    p.prior_kind = _prior_descriptor(proxg)["prior_kind"]
+    d = _prior_descriptor(proxg)
+    p.prior_kind = d["prior_kind"]
+    if p.prior_kind == _capi.PRIOR_WAVELET_L1:      # the kind's two parameters: levels and p
+        p.tv_niter, p.eprox_kind = int(d["wavelet_levels"]), int(d["wavelet_p"])
     return p
 
 
 def sapg_dimension(proxg, dims=None):
     """``(dim_eff, degree)`` the SAPG update uses by default for the prior ``proxg`` on ``dims`` images: l1 ``(H W, 1)``, l2 ``(H W, 2)``,
-    TV ``(H W - 1, 1)``, Haar-l1 ``(H W - (H/8)(W/8), 1)``.  Needs no GPU; a prior without a value raises ``NotImplementedError``."""
+    TV ``(H W - 1, 1)``, Haar-l1 ``(H W - (H/8)(W/8), 1)``, wavelet-l1 over L levels ``(H W - (H >> L)(W >> L), 1)``.  Needs no GPU; a prior without a value raises ``NotImplementedError``."""
     if dims is None:
         dims = getattr(proxg, "dims", None)
     if dims is None:
@@ -292,6 +295,8 @@ class MYULASampler:
             _refuse_box(_prior_descriptor(proxg), *self._box_refusal)
         if self._eprox_refusal is not None:
             _refuse_eprox(_prior_descriptor(proxg), *self._eprox_refusal)
+        if np.asarray(epsg).size > 1 and _prior_descriptor(proxg).get("prior_kind") == _capi.PRIOR_WAVELET_L1:
+            raise NotImplementedError("array-valued epsg is built for the closed-form priors only: the wavelet-l1 prior takes a scalar epsg")
         if tv_warm and _prior_descriptor(proxg).get("box") is not None:
             raise NotImplementedError("a prior with bounds has no warm-started dual: tv_warm must be off")
         self.dims = (int(dims[0]), int(dims[1]))

@@ -202,7 +202,12 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
     A.extra = sc.extra;
     A.extra_coef = -q.ncvx_lambda / q.ncvx_gamma;
   }
-  if (A.prior_kind == LMC_PRIOR_HAAR_L1 || A.prior_kind == LMC_PRIOR_EPROX || (A.box && A.prior_kind != LMC_PRIOR_TV_ISO)) HIP_TRY(sc.need_prox(npx));
+  if (A.prior_kind == LMC_PRIOR_HAAR_L1 || A.prior_kind == LMC_PRIOR_WAVELET_L1 || A.prior_kind == LMC_PRIOR_EPROX || (A.box && A.prior_kind != LMC_PRIOR_TV_ISO))
+    HIP_TRY(sc.need_prox(npx));
+  if (A.prior_kind == LMC_PRIOR_WAVELET_L1) {
+    HIP_TRY(sc.need_wav(lmc::wavelet_ws_floats(n_img, q.H, q.W), 0));
+    q.wav.ws = sc.wav;
+  }
   if (A.prior_kind == LMC_PRIOR_TV_ISO && q.tv_rtol > 0.f && tv_prior_rt_mode(q, A, pt) != 2) {     // the early exit decided on the device
     HIP_TRY(sc.need_prox(npx));
     HIP_TRY(sc.rt_tv.need((size_t)n_img, q.tv_niter));
@@ -220,7 +225,7 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
     A.prior_kind = LMC_PRIOR_NONE;
     A.prox_ext = sc.prox;
   }
-  hipError_t e = launch_step(A, variant_of(q), S(stream), nullptr, sc.state[0], sc.state[1], sc.prox, q.psf.on ? &q.psf : nullptr);
+  hipError_t e = launch_step(A, variant_of(q), S(stream), nullptr, sc.state[0], sc.state[1], sc.prox, q.psf.on ? &q.psf : nullptr, &q.wav);
   if (e == hipErrorInvalidConfiguration)
     return fail(LMC_E_UNSUPPORTED, A.box ? "step_variant %d has no box-constrained form of this prior (TV: auto, 1 tile, 7 / 8 pipe where the pipe covers the problem)"
                                          : "no step-kernel variant covers this configuration", variant_of(q));
@@ -244,6 +249,13 @@ int lmc_energies(const lmc_problem* prob, const float* x_dev, int64_t n_img, dou
   if (!rc) rc = psf_energy(q, x_dev, n_img, f_out_dev, S(stream));
   if (rc) return rc;
   if (q.prior_kind == LMC_PRIOR_HAAR_L1 && g_out_dev) HIP_TRY(lmc::launch_haar_value(x_dev, n_img, q.H, q.W, q.prior_sigma, g_out_dev, S(stream)));
+  if (q.wav.on && g_out_dev) {
+    Scratch& sc = scratch_here();
+    HIP_TRY(sc.need_wav(lmc::wavelet_ws_floats(n_img, q.H, q.W), (size_t)n_img * lmc::wavelet_partials(q.H, q.W, q.wav.levels)));
+    q.wav.ws = sc.wav; q.wav.part = sc.wav_part;
+    rc = wavelet_energy(q, x_dev, n_img, g_out_dev, S(stream));
+    if (rc) return rc;
+  }
   if (q.ncvx_kind == LMC_NCVX_ME_TV && f_out_dev) {
     Scratch& sc = scratch_here();
     HIP_TRY(sc.need_dbl(3 * (size_t)n_img + 2));     // (the pass-by-pass fallback of the inner prox shares the buffer: sized for it up front)
@@ -322,6 +334,43 @@ int lmc_haar_l1_prox(const float* x_dev, float* out_dev, int64_t n_img, int32_t 
   if ((H & 7) || (W & 7)) return fail(LMC_E_UNSUPPORTED, "H and W must be multiples of 8 (got %dx%d)", H, W);
   if (!(thr >= 0.f)) return fail(LMC_E_INVALID, "threshold must be >= 0");
   HIP_TRY(lmc::launch_haar_prox(x_dev, out_dev, n_img, H, W, thr, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_wavelet_filter(int32_t p, double* h_out, int32_t* len_out) {
+  if (!h_out) return fail(LMC_E_INVALID, "h_out is NULL");
+  const int n = lmc::wavelet_filter(p, h_out);
+  if (!n) return fail(LMC_E_INVALID, "p must be 1..%d (got %d)", lmc::kWaveletMaxP, p);
+  if (len_out) *len_out = n;
+  return LMC_OK;
+}
+
+// the argument checks the two stateless wavelet calls share
+static int check_wavelet_call(const float* x_dev, const float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t p, int32_t levels) {
+  if (!x_dev || !out_dev || x_dev == out_dev) return fail(LMC_E_INVALID, "bad pointers (in-place not allowed)");
+  if (n_img < 1 || H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30) return fail(LMC_E_INVALID, "bad shape n_img=%lld H=%d W=%d", (long long)n_img, H, W);
+  if (!lmc::wavelet_shape_ok(H, W, p, levels))
+    return fail(LMC_E_INVALID, "a %dx%d image does not take %d levels of db%d: p in 1..%d, levels in 1..%d, H and W multiples of 2^levels, "
+                "min(H, W) >> (levels - 1) >= 2p", H, W, levels, p, lmc::kWaveletMaxP, LMC_MAX_WAVELET_LEVELS);
+  return LMC_OK;
+}
+
+int lmc_wavelet_apply(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t p, int32_t levels, int32_t inverse, void* stream) {
+  int rc = check_wavelet_call(x_dev, out_dev, n_img, H, W, p, levels);
+  if (rc) return rc;
+  Scratch& sc = scratch_here();
+  HIP_TRY(sc.need_wav(lmc::wavelet_ws_floats(n_img, H, W), 0));
+  HIP_TRY(lmc::launch_wavelet_apply(x_dev, out_dev, n_img, H, W, p, levels, inverse != 0, sc.wav, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_wavelet_l1_prox(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t p, int32_t levels, float thr, void* stream) {
+  int rc = check_wavelet_call(x_dev, out_dev, n_img, H, W, p, levels);
+  if (rc) return rc;
+  if (!(thr >= 0.f)) return fail(LMC_E_INVALID, "threshold must be >= 0");
+  Scratch& sc = scratch_here();
+  HIP_TRY(sc.need_wav(lmc::wavelet_ws_floats(n_img, H, W), 0));
+  HIP_TRY(lmc::launch_wavelet_prox(x_dev, out_dev, n_img, H, W, p, levels, thr, sc.wav, S(stream)));
   return LMC_OK;
 }
 

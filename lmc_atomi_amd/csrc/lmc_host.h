@@ -58,6 +58,7 @@ struct Problem {
   lmc::PsfOp psf;           // LMC_DATA_PSF / POISSON_PSF / WL2_PSF: data_kind = LMC_DATA_PSF (with pois / wl2), the operator and its device table
   int prior_kind = 0;
   float prior_sigma = 0.f;
+  lmc::WaveletOp wav;       // LMC_PRIOR_WAVELET_L1: p, levels and the workspace of whoever owns it
   int tv_niter = 0;
   float tv_step = 0.125f;
   float betas[lmc::kMaxTvIters] = {};
@@ -125,13 +126,15 @@ struct Scratch {
   float* rtmp = nullptr;                  // early-exit TV prox: the iterate of the current pass, [n][H][W]
   double* dbl = nullptr;                  // 2*n doubles
   float* resid = nullptr;                 // large PSF: the residual rho(H x) of a step, [n][H][W]
+  float* wav = nullptr;                   // wavelet prior: the thresholded pyramid and the LL ping-pong
+  double* wav_part = nullptr;             // wavelet prior: the partial sums of its value
   // large PSF: the device tap table of the stateless calls, the pinned host copy it was uploaded from (compared with the next call's table: equal
   // taps are not uploaded again) and the event behind the last upload (the host copy is not rewritten before that upload has run)
   float* psf_tab = nullptr;
   float* psf_host = nullptr;
   hipEvent_t psf_ev = nullptr;
   bool psf_valid = false;
-  size_t n_resid = 0;
+  size_t n_resid = 0, n_wav = 0, n_wav_part = 0;
   RtState rt_tv, rt_me;                   // device-side early exit of the TV prior's prox / of the ME-TV inner prox
   size_t n_state[2] = {0, 0}, n_extra = 0, n_prox = 0, n_rtmp = 0, n_dbl = 0;   // elements allocated
   // p holds at least n elements afterwards; what it held is not kept when it grows
@@ -153,6 +156,16 @@ struct Scratch {
   hipError_t need_rtmp(size_t n) { return grow(rtmp, n_rtmp, n); }
   hipError_t need_dbl(size_t n) { return grow(dbl, n_dbl, n); }
   hipError_t need_resid(size_t n) { return grow(resid, n_resid, n); }
+  hipError_t need_wav(size_t n, size_t n_part) {
+    hipError_t e = grow(wav, n_wav, n);
+    return e == hipSuccess && n_part ? grow(wav_part, n_wav_part, n_part) : e;
+  }
+  // frees the wavelet workspace (the largest buffer a stateless call takes: 1.25 states); the next call that needs it allocates again
+  void release() {
+    if (wav) (void)hipFree(wav);
+    if (wav_part) (void)hipFree(wav_part);
+    wav = nullptr; wav_part = nullptr; n_wav = 0; n_wav_part = 0;
+  }
 };
 // The scratch of the current device: a process may drive several GPUs (one sampler handle each); the stateless entry points run on the current device.
 Scratch& scratch_here();
@@ -191,8 +204,9 @@ void sanitize_pointers(lmc::StepArgs& A);
 int variant_of(const Problem& q);
 float tol_of(const Problem& q);
 // psf: the operator of a launch whose data_kind is LMC_DATA_PSF (with its device table and residual buffer); such a launch without it is not covered
+// wav: the transform of a launch whose prior_kind is LMC_PRIOR_WAVELET_L1 (with its workspace); such a launch without it, or without pxbuf, is not covered
 hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0 = nullptr,
-                       float* state1 = nullptr, float* pxbuf = nullptr, const lmc::PsfOp* psf = nullptr);
+                       float* state1 = nullptr, float* pxbuf = nullptr, const lmc::PsfOp* psf = nullptr, const lmc::WaveletOp* wav = nullptr);
 
 // ---- lmc_solve.hip ----
 int cg_solve_fused(const Problem& q, float ts, float* u, const float* rhs, float* r, float* p, float* qq, double* scal,
@@ -209,6 +223,8 @@ lmc::EnergyArgs energy_args(const Problem& q);
 int pois_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
 int wl2_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
 int psf_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
+// after launch_energies: g_out = the value of the wavelet prior (nothing for the other priors); q.wav carries the workspace
+int wavelet_energy(const Problem& q, const float* x, int64_t n_img, double* g_out, hipStream_t st);
 int me_tv_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, float* extra, float* st0, float* st1,
                  double* dbl /* 2*n_img */, hipStream_t st, RtState* rt);
 
@@ -230,6 +246,7 @@ struct lmc_sampler {
   int wcur = 0;
   float* extra = nullptr;                   // ME-TV inner prox
   float* pxbuf = nullptr;                   // Haar-l1 prox / early-exit TV prox of the current state
+  float* wav_ws = nullptr; double* wav_part = nullptr;    // wavelet prior: the pyramid and the LL ping-pong (1.25 states), the partial sums of its value
   float* psf_tab = nullptr; float* psf_resid = nullptr;   // large PSF: the device tap table (uploaded at creation) and the residual buffer, [C][H][W]
   float* rtmp = nullptr; double* robj = nullptr; int* rflag = nullptr;   // early-exit TV prox (tv_rtol > 0), pass-by-pass path: pass iterate, objectives, flags
   lmc::host::RtState rt_tv, rt_me;          // early-exit TV prox on the device (tv_prox_rt): of the TV prior / of the ME-TV inner prox

@@ -240,3 +240,28 @@ hipError_t launch_skrock_perturb_philox(const float* x, float* out, int64_t C, i
                                         uint32_t iteration, uint32_t chain_offset, hipStream_t st);
 hipError_t launch_skrock_perturb(const float* x, const float* xi, float* out, size_t n, float coef, hipStream_t st);
 }  // namespace lmc
+
+namespace lmc {
+// Daubechies wavelet-l1 prior (lmc_wavelet.hip): the periodic multi-level transform of db1 .. db4, its prox and its value.
+constexpr int kWaveletMaxP = 4;
+// The prior of a validated problem and the device workspace of whoever owns it (a sampler handle, the stateless scratch): ws holds
+// wavelet_ws_floats(n, H, W) floats (the thresholded pyramid and the LL ping-pong: 1.25 states), part n * wavelet_partials(H, W, levels) doubles.
+struct WaveletOp {
+  int on = 0;
+  int p = 0, levels = 0;
+  float* ws = nullptr;
+  double* part = nullptr;
+};
+bool wavelet_shape_ok(int H, int W, int p, int levels);       // the preconditions of include/lmc_atomi.h
+int wavelet_filter(int p, double* h);                         // taps in float64 into h[2p], returns 2p (0: bad p)
+size_t wavelet_ll_floats(int64_t n_img, int H, int W);        // the approximations of level 1
+size_t wavelet_ws_floats(int64_t n_img, int H, int W);
+int wavelet_partials(int H, int W, int levels);
+// out = W^T soft(W x, thr); x != out; ws: wavelet_ws_floats
+hipError_t launch_wavelet_prox(const float* x, float* out, int64_t n_img, int H, int W, int p, int levels, float thr, float* ws, hipStream_t st);
+// val[i] = sigma * sum |details of x_i|; ws: 5/4 wavelet_ll_floats (+ 1), part: n_img * wavelet_partials doubles
+hipError_t launch_wavelet_value(const float* x, int64_t n_img, int H, int W, int p, int levels, float sigma, float* ws, double* part, double* val,
+                                hipStream_t st);
+// out = W x or W^T x (Mallat layout); x != out; ws as for the value
+hipError_t launch_wavelet_apply(const float* x, float* out, int64_t n_img, int H, int W, int p, int levels, int inverse_dir, float* ws, hipStream_t st);
+}  // namespace lmc

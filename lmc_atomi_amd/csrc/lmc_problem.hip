@@ -110,6 +110,16 @@ int load_problem(const lmc_problem* p, Problem& q) {
     case LMC_PRIOR_HAAR_L1:
       if ((p->H & 7) || (p->W & 7)) return fail(LMC_E_UNSUPPORTED, "the Haar-l1 prior needs H and W to be multiples of 8 (got %dx%d)", p->H, p->W);
       break;
+    case LMC_PRIOR_WAVELET_L1:      // tv_niter = levels, eprox_kind = p (include/lmc_atomi.h)
+      if (p->eprox_kind < 1 || p->eprox_kind > lmc::kWaveletMaxP)
+        return fail(LMC_E_INVALID, "LMC_PRIOR_WAVELET_L1: eprox_kind holds p, the vanishing moments of the filter, 1..%d (got %d)", lmc::kWaveletMaxP, p->eprox_kind);
+      if (p->tv_niter < 1 || p->tv_niter > LMC_MAX_WAVELET_LEVELS)
+        return fail(LMC_E_INVALID, "LMC_PRIOR_WAVELET_L1: tv_niter holds the levels of the transform, 1..%d (got %d)", LMC_MAX_WAVELET_LEVELS, p->tv_niter);
+      if (!lmc::wavelet_shape_ok(p->H, p->W, p->eprox_kind, p->tv_niter))
+        return fail(LMC_E_INVALID, "LMC_PRIOR_WAVELET_L1: a %dx%d image does not take %d levels of db%d: H and W must be multiples of 2^levels and "
+                    "min(H, W) >> (levels - 1) >= 2p", p->H, p->W, p->tv_niter, p->eprox_kind);
+      q.wav.on = 1; q.wav.p = p->eprox_kind; q.wav.levels = p->tv_niter;
+      break;
     case LMC_PRIOR_TV_ANISO:
       // tv_niter = 0: the callers that never form the prox (ULPDA, lmc_energies); the entry points that do refuse it (check_prox_prior)
       if (p->tv_niter == 0) break;
@@ -179,6 +189,8 @@ int load_problem(const lmc_problem* p, Problem& q) {
     if (!(p->box_lo < p->box_hi)) return fail(LMC_E_INVALID, "box: needs box_lo < box_hi (got [%g, %g])", (double)p->box_lo, (double)p->box_hi);
     if (p->prior_kind == LMC_PRIOR_HAAR_L1)
       return fail(LMC_E_UNSUPPORTED, "box with LMC_PRIOR_HAAR_L1: the prior is not separable in the pixels, so the clamp of its prox is not the prox of the sum");
+    if (p->prior_kind == LMC_PRIOR_WAVELET_L1)
+      return fail(LMC_E_UNSUPPORTED, "box with LMC_PRIOR_WAVELET_L1: the prior is not separable in the pixels, so the clamp of its prox is not the prox of the sum");
     const bool tv = p->prior_kind == LMC_PRIOR_TV_ISO || p->prior_kind == LMC_PRIOR_TV_ANISO;
     if (tv && p->tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "box with tv_rtol > 0: the early exit's objective is that of the unconstrained prox; use the fixed count, tv_rtol = 0");
     if (tv && p->tv_warm) return fail(LMC_E_UNSUPPORTED, "box with tv_warm: the warm-started dual has no box form");
@@ -277,7 +289,7 @@ int make_step_args(const Problem& q, float a, float t, float b, float pt, float 
   // have no anisotropic form say "not covered" when the flag is set).  Problem::prior_kind stays as given (ULPDA, the energies).
   if (A.prior_kind == LMC_PRIOR_TV_ANISO) { A.prior_kind = LMC_PRIOR_TV_ISO; A.tv_aniso = 1; }
   if (A.prior_kind == LMC_PRIOR_TV_ISO && q.tv_niter == 0) { A.prior_kind = LMC_PRIOR_NONE; A.tv_aniso = 0; }   // lagged output of a 1-iteration prox: x itself
-  if (A.prior_kind == LMC_PRIOR_HAAR_L1) A.prior_p0 = pt * q.prior_sigma;  // soft threshold of the detail coefficients
+  if (A.prior_kind == LMC_PRIOR_HAAR_L1 || A.prior_kind == LMC_PRIOR_WAVELET_L1) A.prior_p0 = pt * q.prior_sigma;  // soft threshold of the detail coefficients
   if (A.prior_kind == LMC_PRIOR_L2) A.prior_p0 = 1.f / (1.f + pt * q.prior_sigma);
   if (A.prior_kind == LMC_PRIOR_L1) A.prior_p0 = pt * q.prior_sigma;
   if (A.prior_kind == LMC_PRIOR_EPROX) {     // prox.py closed forms: the parameters the mask names scale with the prox parameter
@@ -394,13 +406,24 @@ static hipError_t launch_step_psf(const lmc::StepArgs& A, int variant, hipStream
   }
   lmc::StepArgs B = A;
   B.data_kind = LMC_DATA_NONE; B.t = 0.f; B.pois = 0; B.wl2 = 0;
-  e = launch_step(B, variant, st, name, state0, state1, pxbuf);
+  e = launch_step(B, variant, st, name, state0, state1, pxbuf);      // (a wavelet prior: launch_step has formed its prox already, B carries it)
   if (e != hipSuccess) return e;
   return lmc::launch_psf(*psf, 1, lmc::kPsfSub, psf->resid, A.x_out, nullptr, nullptr, A.C, A.H, A.W, 0.f, coef, st);
 }
 
 hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf,
-                       const lmc::PsfOp* psf) {
+                       const lmc::PsfOp* psf, const lmc::WaveletOp* wav) {
+  if (A_in.prior_kind == LMC_PRIOR_WAVELET_L1) {
+    // the route of LMC_PRIOR_HAAR_L1 in launch_step_nobox, taken before the data terms part ways: the prox into pxbuf, then the step of the same
+    // problem without a prior, which consumes it as a ready-made prox -- on whatever kernel that problem gets
+    if (!pxbuf || !wav || !wav->on || !wav->ws) return hipErrorInvalidConfiguration;
+    hipError_t e = lmc::launch_wavelet_prox(A_in.x_in, pxbuf, A_in.C, A_in.H, A_in.W, wav->p, wav->levels, A_in.prior_p0, wav->ws, st);
+    if (e != hipSuccess) return e;
+    lmc::StepArgs A = A_in;
+    A.prior_kind = LMC_PRIOR_NONE;
+    A.prox_ext = pxbuf;
+    return launch_step(A, variant, st, name, state0, state1, pxbuf, psf, nullptr);
+  }
   if (A_in.data_kind == LMC_DATA_PSF) return launch_step_psf(A_in, variant, st, name, state0, state1, pxbuf, psf);
   if (A_in.pois) return launch_step_pois(A_in, variant, st, name, state0, state1, pxbuf);
   if (A_in.wl2) return launch_step_wl2(A_in, variant, st, name, state0, state1, pxbuf);

@@ -133,7 +133,13 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     s->prob.psf.tab_dev = s->psf_tab;
     s->prob.psf.resid = s->psf_resid;
   }
-  if (e == hipSuccess && (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 || s->prob.prior_kind == LMC_PRIOR_EPROX || s->prob.prox_scale ||
+  if (e == hipSuccess && s->prob.wav.on) {     // wavelet prior: the handle owns the pyramid, the LL ping-pong and the partial sums of the value
+    e = hipMalloc(&s->wav_ws, sizeof(float) * lmc::wavelet_ws_floats(s->C, s->prob.H, s->prob.W));
+    if (e == hipSuccess) e = hipMalloc(&s->wav_part, sizeof(double) * (size_t)s->C * lmc::wavelet_partials(s->prob.H, s->prob.W, s->prob.wav.levels));
+    s->prob.wav.ws = s->wav_ws;
+    s->prob.wav.part = s->wav_part;
+  }
+  if (e == hipSuccess && (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 || s->prob.prior_kind == LMC_PRIOR_WAVELET_L1 || s->prob.prior_kind == LMC_PRIOR_EPROX || s->prob.prox_scale ||
                           (s->base.box && s->base.prior_kind != LMC_PRIOR_TV_ISO))) e = hipMalloc(&s->pxbuf, nbytes);
   if (e == hipSuccess && s->prob.tv_rtol > 0.f && s->base.prior_kind == LMC_PRIOR_TV_ISO) {
     if (s->prob.tv_warm) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "tv_rtol > 0 and tv_warm exclude each other"); }
@@ -158,6 +164,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     if (q.wl2) { s->pol_pair = 0; s->pol_blockpair = 0; }                   // weighted Gaussian data term: the same
     if (q.pois) { s->pol_pair = 0; s->pol_blockpair = 0; }                  // Poisson data term: one iteration per launch (the pair kernels have no form of it)
     if (q.psf.on) { s->pol_pair = 0; s->pol_blockpair = 0; }                // large PSF: three launches per iteration
+    if (q.wav.on) { s->pol_pair = 0; s->pol_blockpair = 0; }                // wavelet prior: the prox is launches of its own before every step
   }
   if (e == hipSuccess && s->prob.tv_warm) {
     lmc::StepArgs probe = s->base;
@@ -182,10 +189,11 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
 void lmc_sampler_destroy(lmc_sampler* s) {
   if (!s) return;
   DeviceGuard dg(s->device);
-  for (float* b : {s->xmid[0], s->xmid[1], s->xspare, s->zero_y, s->xhat, s->ydual, s->uw, s->uw2, s->rhs, s->cr, s->cp, s->cq, s->ctmp, s->xi, s->htb, s->tvstate[0], s->tvstate[1], s->extra, s->pxbuf,
+  for (float* b : {s->xmid[0], s->xmid[1], s->xspare, s->zero_y, s->xhat, s->ydual, s->uw, s->uw2, s->rhs, s->cr, s->cp, s->cq, s->ctmp, s->xi, s->htb, s->tvstate[0], s->tvstate[1], s->extra, s->pxbuf, s->wav_ws,
                    s->psf_tab, s->psf_resid, s->mx, s->xp, s->mxp, s->tvwarm[0], s->tvwarm[1], s->rtmp})
     if (b) (void)hipFree(b);
   if (s->robj) (void)hipFree(s->robj);
+  if (s->wav_part) (void)hipFree(s->wav_part);
   if (s->rflag) (void)hipFree(s->rflag);
   s->rt_tv.release();
   s->rt_me.release();
@@ -240,6 +248,10 @@ static int sampler_energies_at(lmc_sampler* s, const float* x, double* f_out_dev
   }
   if (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 && g_out_dev)
     HIP_TRY(lmc::launch_haar_value(x, s->C, s->prob.H, s->prob.W, s->prob.prior_sigma, g_out_dev, st));
+  {
+    const int rc = wavelet_energy(s->prob, x, s->C, g_out_dev, st);
+    if (rc) return rc;
+  }
   if (s->prob.ncvx_kind == LMC_NCVX_ME_TV && f_out_dev) {
     Scratch& sc = scratch_here();
     HIP_TRY(sc.need_dbl(3 * (size_t)s->C + 2));
@@ -302,7 +314,7 @@ static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool 
   int rc = me_tv_extra(s, A, st);   // inner prox of the Moreau-envelope term, then the fused step
   if (rc) return rc;
   if (ov && ov->ev_begin) HIP_TRY(hipEventRecord(ov->ev_begin, st));
-  hipError_t e = launch_step(A, variant_of(s->prob), st, kname, s->tvstate[0], s->tvstate[1], s->pxbuf, s->prob.psf.on ? &s->prob.psf : nullptr);
+  hipError_t e = launch_step(A, variant_of(s->prob), st, kname, s->tvstate[0], s->tvstate[1], s->pxbuf, s->prob.psf.on ? &s->prob.psf : nullptr, &s->prob.wav);
   if (e == hipErrorInvalidConfiguration) return fail(LMC_E_UNSUPPORTED, "no step-kernel variant covers this configuration");
   HIP_TRY(e);
   if (ov && ov->ev_end) HIP_TRY(hipEventRecord(ov->ev_end, st));
@@ -486,7 +498,7 @@ static int myula_single(lmc_sampler* s, SideMoments& m, const float* noise, bool
     kname = "myula_step_pipe_kernel(warm)";
     s->wcur ^= 1;
   } else {
-    e = launch_step(A, variant_of(s->prob), st, &kname, s->tvstate[0], s->tvstate[1], s->pxbuf, s->prob.psf.on ? &s->prob.psf : nullptr);
+    e = launch_step(A, variant_of(s->prob), st, &kname, s->tvstate[0], s->tvstate[1], s->pxbuf, s->prob.psf.on ? &s->prob.psf : nullptr, &s->prob.wav);
   }
   if (e == hipErrorInvalidConfiguration)
     return fail(LMC_E_UNSUPPORTED, s->base.box ? "step_variant %d has no box-constrained form of this prior (TV: auto, 1 tile, 7 / 8 pipe where the pipe covers the problem)"

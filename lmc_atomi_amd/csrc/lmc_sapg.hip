@@ -211,13 +211,14 @@ using namespace lmc::host;
 
 namespace {
 // d and k of the table in include/lmc_atomi.h; false: the prior has no statistic
-bool sapg_dimension(int prior_kind, int H, int W, double* d, double* k) {
+bool sapg_dimension(int prior_kind, int H, int W, int levels, double* d, double* k) {
   const double n = (double)H * (double)W;
   switch (prior_kind) {
     case LMC_PRIOR_L1: *d = n; *k = 1.0; return true;
     case LMC_PRIOR_L2: *d = n; *k = 2.0; return true;
     case LMC_PRIOR_TV_ISO: case LMC_PRIOR_TV_ANISO: *d = n - 1.0; *k = 1.0; return true;
     case LMC_PRIOR_HAAR_L1: *d = n - (double)(H / 8) * (double)(W / 8); *k = 1.0; return true;
+    case LMC_PRIOR_WAVELET_L1: *d = n - (double)(H >> levels) * (double)(W >> levels); *k = 1.0; return true;
     default: return false;
   }
 }
@@ -228,11 +229,13 @@ int check_stat_problem(const lmc_problem* p) {
   if (p->struct_size != sizeof(lmc_problem))
     return fail(LMC_E_INVALID, "lmc_problem.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(lmc_problem));
   if (p->H < 1 || p->W < 1 || (int64_t)p->H * p->W > (int64_t)1 << 30) return fail(LMC_E_INVALID, "bad image size %dx%d", p->H, p->W);
-  if (p->prior_kind < LMC_PRIOR_NONE || p->prior_kind > LMC_PRIOR_EPROX) return fail(LMC_E_INVALID, "unknown prior_kind %d", p->prior_kind);
+  if (p->prior_kind < LMC_PRIOR_NONE || p->prior_kind > LMC_PRIOR_WAVELET_L1) return fail(LMC_E_INVALID, "unknown prior_kind %d", p->prior_kind);
   if (p->prior_kind == LMC_PRIOR_NONE || p->prior_kind == LMC_PRIOR_EPROX)
     return fail(LMC_E_UNSUPPORTED, "prior_kind %d has no value g(x): no statistic", p->prior_kind);
   if (p->prior_kind == LMC_PRIOR_HAAR_L1 && ((p->H & 7) || (p->W & 7)))
     return fail(LMC_E_UNSUPPORTED, "the Haar-l1 prior needs H and W to be multiples of 8 (got %dx%d)", p->H, p->W);
+  if (p->prior_kind == LMC_PRIOR_WAVELET_L1 && !lmc::wavelet_shape_ok(p->H, p->W, p->eprox_kind, p->tv_niter))
+    return fail(LMC_E_INVALID, "LMC_PRIOR_WAVELET_L1: a %dx%d image does not take %d levels (tv_niter) of db%d (eprox_kind)", p->H, p->W, p->tv_niter, p->eprox_kind);
   return LMC_OK;
 }
 
@@ -294,7 +297,11 @@ int sapg_loop(lmc_sampler* s, const lmc_sapg_config& c, const lmc::SapgParams& P
   for (int n = 0; n < c.n_updates; ++n) {
     rc = lmc_sampler_step(s, c.iters_per_update, noise ? noise + (size_t)n * c.iters_per_update * per_iter : nullptr, st);
     if (rc) return rc;
-    HIP_TRY(lmc::launch_prior_stat(s->x[s->cur], s->C, s->prob.H, s->prob.W, s->prob.prior_kind, s->sapg_stat, part, st));
+    if (s->prob.wav.on)      // the wavelet prior: its value with weight 1, from the handle's workspace
+      HIP_TRY(lmc::launch_wavelet_value(s->x[s->cur], s->C, s->prob.H, s->prob.W, s->prob.wav.p, s->prob.wav.levels, 1.f, s->prob.wav.ws, s->prob.wav.part,
+                                        s->sapg_stat, st));
+    else
+      HIP_TRY(lmc::launch_prior_stat(s->x[s->cur], s->C, s->prob.H, s->prob.W, s->prob.prior_kind, s->sapg_stat, part, st));
     HIP_TRY(lmc::launch_sapg_update(s->sapg_stat, s->C, P, n, theta, theta_trace, gbar_trace, s->sapg_host_dev, st));
     HIP_TRY(hipEventRecord(s->sapg_ev, st));
     HIP_TRY(hipEventSynchronize(s->sapg_ev));                // the one host wait of an update
@@ -323,6 +330,12 @@ int lmc_prior_statistic(const lmc_problem* prob, const float* x_dev, int64_t n_i
   int rc = check_stat_problem(prob);
   if (rc) return rc;
   if (!x_dev || !stat_dev || n_img < 1) return fail(LMC_E_INVALID, "bad arguments");
+  if (prob->prior_kind == LMC_PRIOR_WAVELET_L1) {
+    Scratch& sc = scratch_here();
+    HIP_TRY(sc.need_wav(lmc::wavelet_ws_floats(n_img, prob->H, prob->W), (size_t)n_img * lmc::wavelet_partials(prob->H, prob->W, prob->tv_niter)));
+    HIP_TRY(lmc::launch_wavelet_value(x_dev, n_img, prob->H, prob->W, prob->eprox_kind, prob->tv_niter, 1.f, sc.wav, sc.wav_part, stat_dev, S(stream)));
+    return LMC_OK;
+  }
   double* part = nullptr;
   const int nseg = lmc::prior_stat_segments(n_img, prob->H);
   if (nseg > 1) {
@@ -338,7 +351,7 @@ int lmc_sapg_dimension(const lmc_problem* prob, double* dim_eff, double* degree)
   int rc = check_stat_problem(prob);
   if (rc) return rc;
   double d = 0.0, k = 1.0;
-  sapg_dimension(prob->prior_kind, prob->H, prob->W, &d, &k);
+  sapg_dimension(prob->prior_kind, prob->H, prob->W, prob->tv_niter, &d, &k);
   if (dim_eff) *dim_eff = d;
   if (degree) *degree = k;
   return LMC_OK;
@@ -369,7 +382,7 @@ int lmc_sampler_sapg(lmc_sampler* s, const lmc_sapg_config* cfg, const float* no
   if (s->noise_mode != LMC_NOISE_INJECTED && noise_dev) return fail(LMC_E_INVALID, "noise_dev given but noise_mode is not INJECTED");
   if (s->iteration + iters > 0xFFFFFFFFLL) return fail(LMC_E_STATE, "iteration counter would exceed 32 bits");
   double d = 0.0, k = 1.0;
-  if (!sapg_dimension(s->prob.prior_kind, s->prob.H, s->prob.W, &d, &k)) return fail(LMC_E_UNSUPPORTED, "the prior has no statistic");
+  if (!sapg_dimension(s->prob.prior_kind, s->prob.H, s->prob.W, s->prob.wav.levels, &d, &k)) return fail(LMC_E_UNSUPPORTED, "the prior has no statistic");
   if (cfg->dim_eff > 0.0) d = cfg->dim_eff;
   if (!(d > 0.0)) return fail(LMC_E_INVALID, "the effective dimension of a %dx%d image under this prior is 0", s->prob.H, s->prob.W);
   DeviceGuard dg(s->device);

@@ -229,6 +229,13 @@ int wl2_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, h
   return LMC_OK;
 }
 
+// g_out = the value of the wavelet prior (LMC_PRIOR_WAVELET_L1; launch_energies leaves 0 there), from the workspace q.wav carries
+int wavelet_energy(const Problem& q, const float* x, int64_t n_img, double* g_out, hipStream_t st) {
+  if (!q.wav.on || !g_out) return LMC_OK;
+  HIP_TRY(lmc::launch_wavelet_value(x, n_img, q.H, q.W, q.wav.p, q.wav.levels, q.prior_sigma, q.wav.ws, q.wav.part, g_out, st));
+  return LMC_OK;
+}
+
 // the same for a large PSF (LMC_DATA_PSF with its pois / wl2 flags): deterministic partial sums, from the scratch of the current device
 int psf_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st) {
   if (!q.psf.on || !f_out) return LMC_OK;

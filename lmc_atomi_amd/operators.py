@@ -203,6 +203,33 @@ class Gradient(LinearOperator):
         return _dev.like_input(out.reshape(lead + (self.shape[1],)), y)
 
 
+class Wavelet2D(LinearOperator):
+    """The orthonormal periodic wavelet transform of :class:`~lmc_atomi_amd.proximal.WaveletL1` as an operator (``lmc_wavelet_apply``), to look at
+    coefficients: ``wavelet`` in 'haar' / 'db1' .. 'db4', ``levels`` in 1 .. 8, the shape rules of ``LMC_PRIOR_WAVELET_L1`` (include/lmc_atomi.h).
+    ``matvec`` = W x in Mallat layout -- the approximation at the top-left, the details of level j in the other three quadrants of the
+    ``(H >> (j-1), W >> (j-1))`` corner; ``rmatvec`` / ``.H`` = W^T = W^-1."""
+
+    def __init__(self, dims, wavelet="db2", levels=3):
+        self.dims = (int(dims[0]), int(dims[1]))
+        self.wavelet = wavelet
+        self.p, self.levels = _capi.check_wavelet(self.dims, wavelet, levels)
+        n = self.dims[0] * self.dims[1]
+        super().__init__((n, n))
+
+    def _apply(self, x, inverse):
+        import torch
+        t, n_img, lead = self._batch(x, self.shape[1])
+        out = torch.empty_like(t)
+        _dev.run(t, "lmc_wavelet_apply", _dev.ptr(t), _dev.ptr(out), n_img, self.dims[0], self.dims[1], self.p, self.levels, inverse)
+        return _dev.like_input(out.reshape(lead + (self.shape[0],)), x)
+
+    def matvec(self, x):
+        return self._apply(x, 0)
+
+    def rmatvec(self, y):
+        return self._apply(y, 1)
+
+
 class Identity(LinearOperator):
     """``pylops.Identity(n)`` (prox_lmc_deconv.py:125)."""
 

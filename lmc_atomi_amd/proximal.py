@@ -178,6 +178,8 @@ class _Problem:
         p.moments_overlap = int(opt.get("moments_overlap", 0) or 0)
         p.moments_bg_workgroups = int(opt.get("moments_bg_workgroups", 0) or 0)
         p.graph_replay = 1 if opt.get("graph_replay") else 0
+        if p.prior_kind == _capi.PRIOR_WAVELET_L1:      # its two parameters ride in fields the kind does not otherwise read
+            p.tv_niter, p.eprox_kind = int(prior["wavelet_levels"]), int(prior["wavelet_p"])
         if p.prior_kind == _capi.PRIOR_EPROX:
             p.eprox_kind = int(prior["eprox_kind"])
             p.eprox_p0, p.eprox_p1 = float(prior["eprox_p0"]), float(prior["eprox_p1"])
@@ -227,7 +229,7 @@ class L2(ProxOperator):
     size gives ``f(x) = sigma/2 sum_p w_p ((Op x)_p - b_p)^2`` with ``grad f = sigma Op^T(w * (Op x - b))`` -- a pixel with ``w_p = 0`` is unobserved
     (dead or saturated pixels under a blur, a masked-out border), ``w_p = 1 / sigma_p^2`` is a noise map.  ``Op``: :class:`Convolve2D`,
     :class:`Identity` or ``None``; a binary mask on a blur is ``weights = mask`` (``Diagonal`` with weights is refused).  As ``proxf`` of MYULA, MYMALA,
-    SK-ROCK and :func:`EstimatePriorWeight`; ``prox``, ULPDA, ``TV(rtol > 0)``, ``TV(warm=True)``, :class:`WaveletL1` and a forced kernel variant other
+    SK-ROCK and :func:`EstimatePriorWeight`; ``prox``, ULPDA, ``TV(rtol > 0)``, ``TV(warm=True)``, the block-Haar :class:`WaveletL1` and a forced kernel variant other
     than 'auto' / 'tile' / 'pipe' raise ``NotImplementedError``.  ``weights=None`` is the unweighted term, unchanged.
     """
 
@@ -388,7 +390,7 @@ class Poisson(ProxOperator):
     As ``proxf`` of :class:`MYULASampler` / :func:`MoreauYosidaUnadjustedLangevin`, :class:`SKROCKSampler` / :func:`StabilisedLangevin` and
     :func:`EstimatePriorWeight`, with the priors none / L2 / L1 / closed forms / TV (either form, any ``niter``, ``bounds``); the term enters the fused step
     of the full-width pipeline (isotropic TV with 10 dual iterations, W > 128, separable blur or pointwise operator) and of the LDS-tiled kernel everywhere
-    else.  MYMALA, ULPDA, ``prox`` (no closed implicit step), ``TV(rtol > 0)``, ``TV(warm=True)``, :class:`WaveletL1` and a forced kernel variant other
+    else.  MYMALA, ULPDA, ``prox`` (no closed implicit step), ``TV(rtol > 0)``, ``TV(warm=True)``, the block-Haar :class:`WaveletL1` and a forced kernel variant other
     than 'auto' / 'tile' / 'pipe' raise ``NotImplementedError``."""
 
     def __init__(self, Op, b, background, sigma=1.0, dims=None):
@@ -715,24 +717,31 @@ class Box(ProxOperator):
 
 
 class WaveletL1(ProxOperator):
-    """``sigma * || detail coefficients of the 3-level orthonormal Haar transform of x ||_1`` -- the prior of BASELINE config 5
-    (build-specified; the reference has no wavelet code).  ``prox`` = W^T soft(W x, tau*sigma) on independent 8 x 8 blocks."""
+    """``sigma * || detail coefficients of an orthonormal wavelet transform of x ||_1`` (build-specified; the reference has no wavelet code);
+    ``prox`` = W^T soft(W x, tau*sigma), exact.
 
-    def __init__(self, dims, sigma=1.0, levels=3, bounds=None):
+    ``wavelet='haar'`` with ``levels=3`` (the default) is the prior of BASELINE config 5, ``LMC_PRIOR_HAAR_L1``: the 3-level Haar transform on
+    independent 8 x 8 blocks, with the kernels it has always had.  ``'haar'`` with another level count and ``'db1'`` .. ``'db4'`` with any are
+    ``LMC_PRIOR_WAVELET_L1`` (include/lmc_atomi.h is its definition): the periodic transform of the Daubechies extremal-phase filter with p vanishing
+    moments over ``levels`` levels (1 .. 8); the sides must be multiples of ``2^levels`` and the coarsest level must hold the filter,
+    ``min(H, W) >> (levels - 1) >= 2p``.  ``'db1'`` is the Haar filter through the general transform.  As ``proxg`` of MYULA, MYMALA, SK-ROCK and
+    :func:`EstimatePriorWeight`, with every data term; ``bounds``, ULPDA and array-valued ``epsg`` raise ``NotImplementedError``."""
+
+    def __init__(self, dims, sigma=1.0, levels=3, bounds=None, wavelet="haar"):
         super().__init__(None, False)
         if bounds is not None:
             raise NotImplementedError("WaveletL1 takes no bounds: the prior is not separable in the pixels, so clipping its prox is not the prox of the sum")
-        if levels != 3:
-            raise NotImplementedError("levels=3 (8 x 8 blocks) only")
         self.dims = (int(dims[0]), int(dims[1]))
-        if self.dims[0] % 8 or self.dims[1] % 8:
-            raise ValueError("image sides must be multiples of 8")
+        self.wavelet = wavelet
+        self.p, self.levels = _capi.check_wavelet(self.dims, wavelet, levels)
+        self.block_haar = wavelet == "haar" and self.levels == 3
         self.sigma = float(sigma)
-        self.levels = levels
         self._prob = None
 
     def prior_descriptor(self):
-        return {"prior_kind": _capi.PRIOR_HAAR_L1, "prior_sigma": self.sigma}
+        if self.block_haar:
+            return {"prior_kind": _capi.PRIOR_HAAR_L1, "prior_sigma": self.sigma}
+        return {"prior_kind": _capi.PRIOR_WAVELET_L1, "prior_sigma": self.sigma, "wavelet_p": self.p, "wavelet_levels": self.levels}
 
     def __call__(self, x):
         if self._prob is None:
@@ -744,8 +753,12 @@ class WaveletL1(ProxOperator):
         xt = _dev.to_dev(x)
         out = torch.empty_like(xt)
         n = self.dims[0] * self.dims[1]
-        _dev.run(xt, "lmc_haar_l1_prox", _dev.ptr(xt), _dev.ptr(out), xt.numel() // n, self.dims[0], self.dims[1],
-                                                self.sigma * float(tau))
+        if self.block_haar:
+            _dev.run(xt, "lmc_haar_l1_prox", _dev.ptr(xt), _dev.ptr(out), xt.numel() // n, self.dims[0], self.dims[1],
+                                                    self.sigma * float(tau))
+        else:
+            _dev.run(xt, "lmc_wavelet_l1_prox", _dev.ptr(xt), _dev.ptr(out), xt.numel() // n, self.dims[0], self.dims[1], self.p, self.levels,
+                                                       self.sigma * float(tau))
         return _dev.like_input(out, x)
 
 
