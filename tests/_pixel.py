@@ -18,7 +18,9 @@ For one case (kernel family, shape, data term, prior, blur taps, K, noise):
 Modes.  "restart" (injected noise, 2 iterations): after the first iteration both sides restart from `ref64` rounded to float32, so the second measures
 one step and not drift, and a first-step edge error cannot hide in it.  "fused" (Philox noise; two or four iterations inside one launch) and "warm" (the
 TV dual carried from one iteration to the next; `set_state` would zero it) cannot restart in between: both replays run the same iterations from x0 and
-the float32 replay carries its own drift, as the kernel does.  "prox": `TV.prox` alone, one evaluation.
+the float32 replay carries its own drift, as the kernel does.  "prox": `TV.prox` alone, one evaluation.  "philox" and "philox_warm" (`PHILOX_CASES`,
+below): "restart" and "warm" with the noise the kernel draws itself; their bound gains q NOISE_TOL for the device's deviates (`philox_bound_of`), and
+tests/test_philox_pixel_reference.py checks them on the CPU and plants the faults of a draw that the bound has to reject.
 
 The early exit of the TV prox (rtol > 0) is left out: its pass count is a discontinuous function of the state and is pinned by the pass-count tests.
 The non-convex terms of L2_ncvx_tv (`ncvx_kind != NONE`) have cases of their own, on this file's problem recipe, bound and `check`: tests/_ncvx_pixel.py."""
@@ -61,8 +63,9 @@ BLURS = {   # name -> (taps, origin)
 
 # family, shape, term ('l2' | 'pois' | 'wl2'), data (a BLURS key | 'identity' | 'mask' | 'none'), prior ('tv' | 'aniso' | 'l1' | 'l2' | 'none' | 'haar' |
 # 'eprox'), K (dual iterations the prox runs), lagged (TV(niter=K + 1, lagged_output=True)), box (None | (lo, hi)), variant, kernel (the exact
-# `kernel_name`; None: the variant must refuse), mode ('restart' | 'fused' | 'warm' | 'prox'), iters, seam rows, seam columns, tag
-Case = namedtuple("Case", "family shape term data prior K lagged box variant kernel mode iters seam_rows seam_cols tag")
+# `kernel_name`; None: the variant must refuse), mode ('restart' | 'fused' | 'warm' | 'prox' | 'philox' | 'philox_warm'), iters, seam rows, seam columns,
+# tag, it0 (the iteration counter the run starts at: the Philox modes and "fused")
+Case = namedtuple("Case", "family shape term data prior K lagged box variant kernel mode iters seam_rows seam_cols tag it0", defaults=(0,))
 
 
 def case_id(c):
@@ -206,6 +209,123 @@ LAYOUT_PAIRS = [(a, b) for a in CASES for b in CASES if a.family == "pipe" and b
                 == b._replace(family="", variant="", kernel="", seam_cols=())]
 
 
+# ------------------------------------------------------------------ the Philox cases: the noise the step kernel draws itself
+# Every case above but the six fused launches injects its noise, so the counter arithmetic of a kernel's own draw -- (quad, iteration, global chain,
+# stream), the quad q = (i >> 2) W + j -- is held per pixel nowhere else.  A Philox case is an injected-noise case with the noise source changed and
+# nothing else: same family, shape, terms, kernel.  Mode "philox" is "restart" with the noise of iteration `it` taken from the field
+# O.philox_normals(SEED_P, it0 + it, CHAIN_OFFSET + arange(N_CHAINS), H, W); "philox_warm" is "warm" with that field.  The device side sets the counter
+# (`smp.iteration = it0 + it`) before every single-iteration launch.  Left out: the rtol > 0 instantiations -- their pass count is discontinuous, and their
+# Philox code is the same template code.
+SEED_P = 0x9E3779B185EBCA87            # both 32-bit halves non-zero and distinct: key0 and key1 swapped or one of them dropped shows
+NOISE_TOL = 2e-5                       # the project's stated error of a device deviate (lmc_device.h, rung R3); not fitted here
+IT_TOP, IT_TOP_FUSED = 0xFFFFFFFD, 0xFFFFFFFB      # the library allows iteration + n <= 0xFFFFFFFF: two single launches, one launch of four
+PHILOX_MODES = ("philox", "philox_warm")
+
+
+def _seams(variant, shape):
+    H, W = shape
+    rows = {"tile": 64, "point": 32, "rows": 16, "block": 8}.get(variant)
+    if variant in ("tile", "split", "point", "block"):
+        cols = _mult(8 if variant == "block" else 64, W)
+    elif variant == "rows":
+        cols = _mult(496, W) if W > 512 else ()
+    else:
+        cols = _mult(512, W) if W > 512 else ((W // 2,) if variant == "pipe2" else ())
+    return (_mult(rows, H) if rows else ()), cols
+
+
+def _build_philox_cases():
+    by_key = {}
+    for c in CASES:
+        by_key.setdefault((c.family, c.tag), []).append(c)
+    out = []
+
+    def twin(family, shape, tag, it0=0, mode="philox", suffix="", name=None):
+        """The injected-noise case (family, tag) at `shape` -- the one of CASES where it has that shape, else its recipe at the new shape -- with the
+        noise source changed."""
+        base = next((c for c in by_key[(family, tag)] if c.shape == shape), by_key[(family, tag)][0])
+        assert base.mode in ("restart", "warm", "fused"), case_id(base)
+        rows, cols = _seams(base.variant if base.variant != "auto" else "pipe", shape)
+        out.append(base._replace(shape=shape, seam_rows=rows, seam_cols=cols, mode=mode, tag=f"{name or tag}-philox{suffix}", it0=it0))
+
+    for s in [(3, 5), (17, 67), (66, 67), (65, 130)]:
+        twin("tile", s, "tv10-A")
+    for tag in ("tv20-A", "tv10box-A", "l1-A"):                # tv20: chunks of 8 + 8 + 4 dual iterations, the noise added once
+        twin("tile", (66, 67), tag)
+    twin("tile", (17, 67), "aniso10-A")
+    for s in [(5, 64), (5, 65), (5, 129), (6, 257), (1, 300)]:
+        twin("split", s, "tv10-A")
+    twin("split", (5, 65), "tv5-B")
+    twin("point", (33, 65), "l1-B")
+    twin("point", (34, 130), "l2-A")
+    twin("point", (33, 65), "eprox-B")
+    for s in [(9, 4), (17, 67), (9, 512), (9, 513), (9, 516)]:     # (one iteration per launch: policy iterations_per_launch = 1)
+        twin("rows", s, "l1-A")
+    twin("rows", (17, 67), "none-B")
+    twin("rows", (9, 512), "eprox-A")
+    for s in [(8, 8), (16, 72)]:
+        for p in ("haar", "l1"):
+            for d in ("identity", "mask"):
+                twin("block", s, f"{p}-{d}")
+    # pipe.  Quad boundaries: H on either side of 4, 8, 12 at PXL = 8 (W = 264) and PXL = 4 (W = 136); three row-groups (H = 9, 13) exercise both halves
+    # of the double-buffered slab and a partial last quad.  The recipe of the K = 10, blur A launch is that of "tv10-A-unaligned".
+    for W in (264, 136):
+        for H in (1, 2, 3, 4, 5, 7, 8, 9, 13):
+            twin("pipe", (H, W), "tv10-A-unaligned", name="tv10-A")
+    for s in [(6, 129), (6, 132), (6, 133), (6, 257), (6, 260), (6, 261)]:
+        twin("pipe", s, "tv10-A-unaligned", name="tv10-A")
+    for s in [(6, 513), (6, 1024), (6, 1026), (5, 1544)]:
+        twin("pipe", s, "tv10-A-strips", name="tv10-A")
+    for tag in ("tv10-B", "tv10-D", "tv2-A", "tv6-A", "tv8-A", "tv9lagged-A", "tv20-A-chained", "tv29-A-chained", "tv60-A-chained", "tv10box-A", "tv20box-A"):
+        twin("pipe", (6, 264), tag)
+    twin("pipe", (6, 132), "tv30-A-chained")
+    for d in ("identity", "mask", "none"):
+        twin("pipe", (6, 136), f"tv10-{d}")
+    for s in [(6, 264), (6, 520)]:
+        twin("pipe", s, "aniso10-A")
+    for tag in ("tv10-B", "aniso10-A", "tv10box-A"):
+        twin("pipe2", (6, 264), tag)
+    for term in ("pois", "wl2"):
+        for s in [(6, 264), (6, 136)]:
+            twin(term, s, "pipe-tv10-A")
+        twin(term, (6, 264), "pipe-tv10box-A")
+        twin(term, (17, 67), "tile-tv10-A")
+    for K in (1, 2, 3):        # the warm dual cannot restart: the field as the noise of three carried iterations
+        twin("pipe", (6, 264), f"tv{K}-A-warm", mode="philox_warm")
+    # the counter's top: iterations 0xFFFFFFFD and 0xFFFFFFFE in single launches, 0xFFFFFFFB .. 0xFFFFFFFE inside the launches of two and four
+    twin("tile", (17, 67), "tv10-A", it0=IT_TOP, suffix="-top")
+    twin("split", (5, 65), "tv10-A", it0=IT_TOP, suffix="-top")
+    twin("rows", (17, 67), "l1-A", it0=IT_TOP, suffix="-top")
+    twin("block", (16, 72), "haar-mask", it0=IT_TOP, suffix="-top")
+    twin("pipe", (6, 264), "tv10-B", it0=IT_TOP, suffix="-top")
+    for c in CASES:
+        if c.mode == "fused":
+            out.append(c._replace(tag=c.tag + "-top", it0=IT_TOP_FUSED))
+    return out
+
+
+PHILOX_CASES = _build_philox_cases()
+PHILOX_IDS = [case_id(c) for c in PHILOX_CASES]
+assert len(set(PHILOX_IDS + IDS)) == len(PHILOX_IDS) + len(IDS), "case ids must be unique"
+PHILOX_LAYOUT_PAIRS = [(a, b) for a in PHILOX_CASES for b in PHILOX_CASES if a.family == "pipe" and b.family == "pipe2" and a.it0 == b.it0
+                       and a._replace(family="", variant="", kernel="", seam_cols=()) == b._replace(family="", variant="", kernel="", seam_cols=())]
+
+
+def seed_of(c):
+    return SEED_P if c.mode in PHILOX_MODES else SEED
+
+
+def philox_field(c, it):
+    """The noise of iteration `it` of a Philox case, as the "fused" mode computes it."""
+    return O.philox_normals(seed_of(c), c.it0 + it, np.arange(CHAIN_OFFSET, CHAIN_OFFSET + N_CHAINS), *c.shape)
+
+
+def noise_gain(c):
+    """q, the coefficient of xi in the case's step: sqrt(2 tau) in the step's float32 (tests/test_philox_pixel_reference.py checks it against the
+    checker: step(x, 1) - step(x, 0))."""
+    return float(np.sqrt(np.float32(2.0 * problem(c).tau)))
+
+
 # ------------------------------------------------------------------ the problem of a case: float32 numbers, made once
 def f32(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float32))
@@ -248,8 +368,8 @@ def problem(c):
         y = f32(op.fwd(img) + rng.normal(0, SIGMA, shape) * (mask if mask is not None else 1.0))
         x0 = f32(img[None] + rng.normal(0, 10, (N_CHAINS,) + shape))
         gamma, sigma_f, tau = GAMMA, 1 / SIGMA ** 2, TAU
-    if c.mode == "fused":
-        noise = np.stack([O.philox_normals(SEED, i, np.arange(CHAIN_OFFSET, CHAIN_OFFSET + N_CHAINS), *shape) for i in range(c.iters)])
+    if c.mode == "fused" or c.mode in PHILOX_MODES:
+        noise = np.stack([philox_field(c, i) for i in range(c.iters)])
         assert noise.dtype == np.float32
     else:
         noise = f32(rng.standard_normal((c.iters, N_CHAINS) + shape))
@@ -291,7 +411,7 @@ class Stepper:
         self.h, self.mask, self.y = cast(m.h), cast(m.mask), cast(m.y)
         if self.standard:       # the checker's own step, as the rel-L2 tests call it
             self.prior = {"kind": c.prior, "sigma": weight(c), "niter": c.K, "t": m.gamma}
-            if c.mode == "warm":
+            if c.mode in ("warm", "philox_warm"):
                 self.prior["warm"] = True
             return
         op = P.Op("blur", self.h, m.offset) if m.h is not None else (P.Op("mask", self.mask) if m.mask is not None else P.Op("identity"))
@@ -335,6 +455,16 @@ class Stepper:
         return O.tv_prox_fgp(np.asarray(x, dtype=self.dtype), weight(self.c) * t, self.c.K)
 
 
+def replay32(c, noise):
+    """The launch-form float32 replay of case `c` with `noise` ([iters, chains, H, W]) in place of its own: the float32 state after every iteration, from
+    the starts of `reference(c)` ("restart", "philox") or carried from x0.  What a kernel with a fault in its draw would hold."""
+    s32, out, x = Stepper(c, np.float32), [], problem(c).x0
+    for it, st in enumerate(reference(c)):
+        x = s32.step(st.start if st.start is not None else x, f32(noise[it]))
+        out.append(x)
+    return out
+
+
 def ulp32(v):
     return float(np.spacing(np.float32(abs(v))))
 
@@ -348,7 +478,20 @@ PROX_T = 2.5       # the prox parameter of the "prox" mode: TV.prox(x, PROX_T), 
 
 # start: the float32 state both sides start the comparison's iteration(s) from (None: they carry their own); compare: whether the device state is compared
 # after this iteration
+# after this iteration
 Stage = namedtuple("Stage", "start ref64 ref32 e32 bound compare")
+# a stage of the Philox modes; noise_term: the part of `bound` that is not rounding, q NOISE_TOL per carried iteration
+PStage = namedtuple("PStage", Stage._fields + ("noise_term",))
+
+
+def philox_bound_of(c, ref64, ref32, carried=1):
+    """The bound of a Philox stage: max(3 e32, 2 ulp32) + carried q NOISE_TOL.  The second term is there because the reference's field is exact
+    arithmetic (float64 log / sqrt / sin / cos, rounded once) and the device's is hardware log2 / sqrt / sin / cos, which lmc_device.h states to within
+    NOISE_TOL per deviate; the deviate enters the state as q xi.  `carried`: the iterations since both sides last started from the same state (the warm
+    dual cannot restart) -- the step without its noise does not expand a difference (tau is below the stability limit), so the terms add."""
+    e32, rounding = bound_of(ref64, ref32)
+    term = carried * noise_gain(c) * NOISE_TOL
+    return e32, rounding + term, term
 
 
 @functools.lru_cache(maxsize=None)
@@ -360,12 +503,22 @@ def reference(c):
     if c.mode == "prox":
         r64, r32 = s64.prox(m.x0, PROX_T), s32.prox(m.x0, PROX_T)
         stages.append(Stage(m.x0, r64, r32, *bound_of(r64, r32), True))
-    elif c.mode == "restart":
+    elif c.mode in ("restart", "philox"):
         start = m.x0
         for it in range(c.iters):
             r64, r32 = s64.step(start, m.noise[it]), s32.step(start, m.noise[it])
-            stages.append(Stage(start, r64, r32, *bound_of(r64, r32), True))
+            if c.mode == "philox":
+                e32, bound, term = philox_bound_of(c, r64, r32)
+                stages.append(PStage(start, r64, r32, e32, bound, True, term))
+            else:
+                stages.append(Stage(start, r64, r32, *bound_of(r64, r32), True))
             start = f32(r64)
+    elif c.mode == "philox_warm":
+        x64, x32 = m.x0.astype(np.float64), m.x0
+        for it in range(c.iters):
+            x64, x32 = s64.step(x64, m.noise[it]), s32.step(x32, m.noise[it])
+            e32, bound, term = philox_bound_of(c, x64, x32, carried=it + 1)
+            stages.append(PStage(m.x0 if it == 0 else None, x64, x32, e32, bound, True, term))
     else:       # fused, warm: no restart in between
         x64, x32 = m.x0.astype(np.float64), m.x0
         for it in range(c.iters):

@@ -174,6 +174,8 @@ def _build_cases():
     rows_pair = lambda shape, tag: _find("rows_pair", shape, tag)._replace(family="rows", kernel="myula_step_rows_kernel")
     d = [pipe._replace(shape=(8, 264)), pipe, _find("split", (5, 65), "tv10-A"), _find("pipe", (1, 256), "tv10-none"), _find("rows", (9, 4), "l1-A"),
          _find("block", (16, 72), "haar-identity"), rows_pair((16, 264), "l2-A-2it"), rows_pair((40, 132), "l1-A-2it")]
+    # the pipe shapes the perturbation's draw had not seen: 4 pixels per lane, rows that are not 16-byte aligned, two column strips
+    d += [_find("pipe", (6, 132), "tv8-A"), _find("pipe", (6, 261), "tv10-A-unaligned"), _find("pipe", (6, 1026), "tv10-A-strips")]
     for c in d:
         out += [SCase("D", _philox(c), s, "philox", "carried", 2) for s in (5, 2)]
     return out

@@ -122,6 +122,7 @@ A_SHAPES4 = [(9, 12), (17, 64), (1, 8), (8, 4)]          # W % 4 == 0: the 4-pix
 A_SHAPES1 = [(17, 67), (5, 7), (1, 5), (3, 1)]           # the scalar kernels
 A_FULL = [(17, 64), (17, 67)]                            # every combination of the axes; the other shapes take six each, every value of every axis
 A_PHILOX = [(16, 64), (17, 64), (3, 12), (16, 67), (17, 67), (3, 7)]      # heights 16, 17 (a last quad of one row) and 3
+A_PHILOX += [(5, 65), (6, 66), (7, 69)]       # the draw is four columns per thread: H % 4 = 1, 2, 3 with W % 4 = 1, 2, 1 (W % 4 = 3: above)
 
 
 def case_id(c):

@@ -235,13 +235,13 @@ def test_forced_tile_variant_on_the_odd_image(la, data, prior):
 
 # ---- Philox mode on an image whose rows do not fill the proposal kernel's quads -------------------------------------------------------------
 
-def test_philox_proposals_on_a_partial_row_quad(la):
+def test_philox_proposals_on_a_partial_row_quad(la, shape=R.ODD):
     """noise='philox' at 17 x 67: the proposal kernel draws quads of 4 rows, the last quad has one.  The reference runs on ``O.philox_normals``,
     which the device's normals match to 2e-5 (hardware log2 / sqrt / sin / cos: tests/test_gpu_parity.py).  That difference dxi enters log alpha
     through ||x' - m(x)||^2 / (4 tau) = sum xi^2 / 2, by at most 2e-5 sum |xi| per chain and iteration, and through x' = m(x) + sqrt(2 tau) xi,
     by 2.1e-5 per pixel -- the size of the fp32 rounding of x' itself (ulp(150) = 1.5e-5), which the bound allows for once already.  Hence
     tol = 2 bound + 2e-5 sum |xi|.  One wrong normal (an error of order 1) moves sum xi dxi by order 1, fifty times this."""
-    case = R.Case(R.ODD, "blur5", "tv10")
+    case = R.Case(shape, "blur5", "tv10")
     m = R.reference(case).model
     H, W = m.shape
     chains = R.CHAIN_OFFSET + np.arange(R.N_CHAINS)
@@ -274,6 +274,13 @@ def test_philox_proposals_on_a_partial_row_quad(la):
     assert (err[agree] < tol[agree]).all(), (err, tol)
     assert (accs[-1][safe] == acc_ref[safe]).all(), (accs[-1], acc_ref, safe)
     assert rel(got[safe], x_ref[safe]) < STATE_TOL
+
+
+@pytest.mark.parametrize("shape", [(5, 7), (9, 130)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_philox_proposals_on_other_partial_quads(la, shape):
+    """The same at 5 x 7 (two row-groups, the last of one row, fewer columns than a wave) and at 9 x 130 (three row-groups, columns past two waves):
+    the proposal kernel's quad index is (i >> 2) W + j, and 17 x 67 alone leaves the other widths and a last group behind two full ones unchecked."""
+    test_philox_proposals_on_a_partial_row_quad(la, shape)
 
 
 # ---- the stateless energies at the edges of the separable energy kernel's 32 x 64 tile ---------------------------------------------------

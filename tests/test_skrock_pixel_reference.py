@@ -49,7 +49,9 @@ def test_the_lists_have_every_part_family_and_form():
     assert {sc.s for sc in parts["B"]} == {2, 3, 4, 10, 15} and {sc.s % 3 for sc in parts["B"]} == {0, 1, 2}
     assert [(sc.base.family, sc.base.shape, sc.noise, sc.s) for sc in parts["C"]] == [("pipe", (6, 264), "none", 3), ("rows", (17, 67), "none", 3),
                                                                                      ("block", (8, 8), "none", 3)]
-    assert {sc.base.shape for sc in parts["D"]} == {(8, 264), (6, 264), (5, 65), (1, 256), (9, 4), (16, 72), (16, 264), (40, 132)}
+    assert {sc.base.shape for sc in parts["D"]} == {(8, 264), (6, 264), (5, 65), (1, 256), (9, 4), (16, 72), (16, 264), (40, 132),
+                                                    (6, 132), (6, 261), (6, 1026)}      # (the last three: 4 pixels per lane, unaligned rows, two strips)
+    assert all(sc.base.kernel == "myula_step_pipe_kernel" for sc in parts["D"] if sc.base.shape in ((6, 132), (6, 261), (6, 1026)))
     assert all(sc.noise == "philox" and sc.mode == "carried" and sc.s in (5, 2) for sc in parts["D"])
     for sc in parts["D"]:
         if sc.base.shape in ((16, 264), (40, 132)):

@@ -21,7 +21,9 @@ def test_the_matrix_covers_the_axes_the_shapes_and_the_paths():
     for shape in U.A_FULL:
         assert len({c[2:7] for c in rs if c.shape == shape}) == 48
     ph = [c for c in U.A_CASES if c.mode == "philox"]
-    assert {c.shape[0] for c in ph} == {16, 17, 3} and {c.shape[1] % 4 == 0 for c in ph} == {True, False}
+    assert {c.shape[0] for c in ph} == {16, 17, 3, 5, 6, 7} and {c.shape[1] % 4 == 0 for c in ph} == {True, False}
+    # the draw is four columns per thread and four rows per quad: every remainder of both
+    assert {c.shape[0] % 4 for c in ph} == {0, 1, 2, 3} and {c.shape[1] % 4 for c in ph} == {0, 1, 2, 3}
     assert {c.family for c in U.B_CASES} == {"cheb", "cheb-uni", "cheb-pairs", "cg-rows", "cg-general"}
     for fam in ("cheb", "cheb-uni", "cheb-pairs"):
         assert any(c.family == fam and c.mode == "warm" for c in U.B_CASES), fam
