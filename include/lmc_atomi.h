@@ -113,7 +113,33 @@ typedef enum lmc_data_kind {
    * for it), ncvx_kind != NONE, tv_rtol > 0, tv_warm.  iterations_per_launch is ignored. */
   LMC_DATA_PSF = 9,
   LMC_DATA_POISSON_PSF = 10,
-  LMC_DATA_WL2_PSF = 11
+  LMC_DATA_WL2_PSF = 11,
+  /* Fourier-domain data term: k-space masks and periodic blurs (appended; LMC_ATOMI_ABI_VERSION stays 4 and sizeof(lmc_problem) 200).  Build-specified;
+   * this text is its definition.  F: the unitary 2-D DFT of an H x W real image in numpy's unshifted fft2(norm="ortho") index order; G and b: complex
+   * H x W arrays, the gain and the data per frequency.
+   *   f(x) = sigma_f / 2 sum_k |G_k (F x)_k - b_k|^2 over the full plane,  grad f(x) = sigma_f Re F^H(conj(G) (G F x - b)),  L_f = sigma_f max_k A_k.
+   * x is real, so F x is Hermitian and only the Hermitian part of the residual survives the real part.  With -k = ((-i) mod H, (-j) mod W),
+   *   A_k = (|G_k|^2 + |G_-k|^2) / 2 (real),  B_k = (conj(G_k) b_k + G_-k conj(b_-k)) / 2,
+   *   grad f = sigma_f irfft2(A rfft2(x) - B) exactly, on the half plane of Wh = W / 2 + 1 columns alone,
+   *   prox_{tau f}(v) = irfft2((rfft2(v) + tau sigma_f B) / (1 + tau sigma_f A)),
+   *   f = sigma_f / 2 times the half-plane sum of |G_k xh_k - b_k|^2 + |conj(G_-k) xh_k - conj(b_-k)|^2, the second term zeroed in the self-conjugate
+   *   columns j = 0 and j = W / 2 (where -k is itself visited): formed from the residuals in fp32, widened to float64 and summed by partial sums in a
+   *   fixed order -- never the expanded form A |xh|^2 - 2 Re(.), which cancels.
+   * It covers k-space sampling (MRI, gridded radio visibilities: G = mask or sqrt(weights), optionally times a transfer function) and the periodic
+   * convolution with a kernel of any support up to the image (G = the unnormalised DFT of the kernel wrapped about its origin, b = F(observation)).
+   * The struct has no hole left, so the kind reads only fields that are otherwise unread for it: y_dev -> device floats [11][H][Wh], planes 0 .. 2 =
+   * A, Re B, Im B, planes 3 .. 10 = Re / Im of G_k, b_k, conj(G_-k), conj(b_-k), the last two pairs zeroed in the self-conjugate columns
+   * (lmc_spectral_tables builds them on the host).  mask_dev, h_host, kh, kw, oy, ox and the psf_* bytes must be NULL / 0 (LMC_E_INVALID otherwise).
+   * H and W: powers of two, 8 .. 1024 (LMC_E_UNSUPPORTED otherwise; mixed radix is not built).
+   * The update out = a x - t grad f(x) + b prox(x) + s xi runs as LMC_DATA_PSF's does: the spectrum of the residual into a handle-owned buffer
+   * (fft_rows_fwd_kernel, fft_cols_spectral_kernel), the step of the same problem without a data term, out -= t sigma_f irfft (fft_rows_inv_kernel);
+   * without prox and noise the last launch writes a x - t sigma_f irfft and the middle one is skipped.  Kernels: lmc_fft.hip -- a Stockham autosort in
+   * LDS, radix 4 with one radix-2 stage for an odd log2, twiddles from a table computed in float64 and rounded once.
+   * Honoured by lmc_myula_create, lmc_skrock_create with all of lmc_sampler_* (lmc_sampler_sapg included), lmc_fused_eval, lmc_energies,
+   * lmc_sampler_energies and lmc_l2_prox (the closed form above: niter, warm and the workspace are ignored).  Every prior and box LMC_DATA_NONE takes.
+   * A sampler handle owns the spectrum buffer and the twiddle table; the stateless calls take theirs from scratch.  LMC_E_UNSUPPORTED, with the reason
+   * in lmc_last_error: lmc_mymala_create, lmc_ulpda_create, ncvx_kind != NONE, tv_rtol > 0, tv_warm.  iterations_per_launch is ignored. */
+  LMC_DATA_SPECTRAL = 12
 } lmc_data_kind;
 
 /* prior g whose prox enters the MYULA update (algs.py:569) */
@@ -329,6 +355,17 @@ int lmc_psf_apply(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, 
  * |u_a v_b - h_ab| <= 2^-22 |h_ab| for every tap (so a zero tap is reproduced as zero).  u_out (kh floats) and v_out (kw floats) may be NULL; they are
  * written when the answer is 1. */
 int lmc_psf_separable(const float* h_host, int32_t kh, int32_t kw, float* u_out, float* v_out);
+
+/* The transforms of LMC_DATA_SPECTRAL, norm = "ortho", on the half plane: H and W powers of two in 8 .. 1024 (LMC_E_UNSUPPORTED otherwise), any n_img.
+ * lmc_rfft2: x_dev real [n][H][W] -> out_dev complex [n][H][W / 2 + 1] (interleaved floats), numpy.fft.rfft2(x, norm="ortho").
+ * lmc_irfft2: x_dev complex [n][H][W / 2 + 1] -> out_dev real [n][H][W], numpy.fft.irfft2(c, s=(H, W), norm="ortho"); x_dev is not modified.
+ * lmc_spectral_filter: out = irfft2(M rfft2(x)) with the complex multiplier m_dev = [2][H][W / 2 + 1] (Re M, then Im M).  Not in place. */
+int lmc_rfft2(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, void* stream);
+int lmc_irfft2(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, void* stream);
+int lmc_spectral_filter(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, const float* m_dev, void* stream);
+/* Host only, no device needed.  The [11][H][W / 2 + 1] float planes of LMC_DATA_SPECTRAL (what y_dev points to, once uploaded) from G and b, each
+ * [H][W] complex as interleaved float64, full plane; the fold runs in float64 and every entry is rounded once. */
+int lmc_spectral_tables(const double* G_host, const double* b_host, int32_t H, int32_t W, float* out_host);
 
 /* out[2][H][W] = forward-difference gradient of x (zero in last row/col); pylops.Gradient.matvec
  * (prox_lmc_deconv.py:98; algs.py:436,448). */

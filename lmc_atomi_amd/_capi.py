@@ -21,6 +21,9 @@ DATA_WL2_IDENTITY, DATA_WL2_BLUR = 7, 8      # y_dev: [2][H][W], the observation
 DATA_PSF, DATA_POISSON_PSF, DATA_WL2_PSF = 9, 10, 11      # the large PSF (psf_* fields): Gaussian, Poisson, weighted Gaussian term
 PSF_KINDS = (DATA_PSF, DATA_POISSON_PSF, DATA_WL2_PSF)
 WL2_KINDS = (DATA_WL2_IDENTITY, DATA_WL2_BLUR)
+DATA_SPECTRAL = 12      # the Fourier-domain data term: y_dev is [11][H][W / 2 + 1], the planes of lmc_spectral_tables
+SPECTRAL_PLANES = 11
+FFT_MIN, FFT_MAX = 8, 1024      # sides of the transforms: powers of two in this range
 TWO_PLANE_KINDS = POISSON_KINDS + WL2_KINDS + (DATA_POISSON_PSF, DATA_WL2_PSF)      # y_dev is [2][H][W]
 PRIOR_NONE, PRIOR_L2, PRIOR_L1, PRIOR_TV_ISO, PRIOR_TV_ANISO, PRIOR_HAAR_L1, PRIOR_EPROX = 0, 1, 2, 3, 4, 5, 6
 PRIOR_WAVELET_L1 = 7      # Daubechies wavelet-l1: lmc_problem.tv_niter = levels, eprox_kind = p (the struct has no hole left)
@@ -162,6 +165,10 @@ _SIGNATURES = {
     "lmc_blur": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "lmc_psf_apply": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "lmc_psf_separable": (C.c_int, [_F, C.c_int32, C.c_int32, _F, _F]),
+    "lmc_rfft2": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "lmc_irfft2": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "lmc_spectral_filter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
+    "lmc_spectral_tables": (C.c_int, [_D, _D, C.c_int32, C.c_int32, _F]),
     "lmc_gradient": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "lmc_gradient_adjoint": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "lmc_fused_eval": (C.c_int, [C.POINTER(lmc_problem), _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
@@ -277,6 +284,18 @@ def check_wavelet(dims, wavelet, levels):
     if (min(H, W) >> (levels - 1)) < 2 * p:
         raise ValueError(f"{levels} levels of {wavelet} need min(H, W) >> (levels - 1) >= {2 * p} (got {H} x {W}): the coarsest level must hold the filter")
     return p, levels
+
+
+def check_fft_dims(dims):
+    """``(H, W)`` as ints; ``ValueError`` unless both are powers of two in ``FFT_MIN .. FFT_MAX`` (the sides the LDS transforms are built for)."""
+    try:
+        H, W = int(dims[0]), int(dims[1])
+    except (TypeError, ValueError, IndexError):
+        raise ValueError(f"dims must be a pair (H, W) (got {dims!r})") from None
+    for n in (H, W):
+        if not (FFT_MIN <= n <= FFT_MAX) or n & (n - 1):
+            raise ValueError(f"the transforms take sides that are powers of two in {FFT_MIN} .. {FFT_MAX} (got {H} x {W})")
+    return H, W
 
 
 def exported_symbols():

@@ -102,6 +102,18 @@ def _refuse_psf(data, prior, opts, who=None):
         raise NotImplementedError("a large PSF has no warm-started TV dual: warm / tv_warm must be off")
 
 
+def _refuse_spectral(data, prior, opts, who=None):
+    """The same for the Fourier-domain data term (``Op = FourierSampling(...)`` / ``PeriodicConvolve2D(...)``, ``LMC_DATA_SPECTRAL``)."""
+    if data.get("data_kind") != _capi.DATA_SPECTRAL:
+        return
+    if who is not None:
+        raise NotImplementedError(f"{who[0]} does not take the Fourier-domain data term (Op = FourierSampling / PeriodicConvolve2D): {who[1]}")
+    if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
+        raise NotImplementedError("the Fourier-domain data term runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
+    if prior.get("tv_warm") or opts.get("tv_warm"):
+        raise NotImplementedError("the Fourier-domain data term has no warm-started TV dual: warm / tv_warm must be off")
+
+
 def _data_descriptor(proxf):
     if proxf is None:
         return {"data_kind": _capi.DATA_NONE}
@@ -316,6 +328,7 @@ class MYULASampler:
         _refuse_poisson(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._poisson_refusal)
         _refuse_wl2(_data_descriptor(proxf), _prior_descriptor(proxg), opts)
         _refuse_psf(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._psf_refusal)
+        _refuse_spectral(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._spectral_refusal)
         self._problem = _Problem(self.dims, _data_descriptor(proxf), _prior_descriptor(proxg), self.device, options=opts)
         self.prior_weight = float(self._problem.c.prior_sigma)      # follows set_prior_weight / estimate_prior_weight
         cfg = _capi.lmc_myula_config()
@@ -334,7 +347,7 @@ class MYULASampler:
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             rc = self._create(cfg)
-        if rc == -2 and self._problem.c.data_kind in _capi.POISSON_KINDS + _capi.WL2_KINDS + _capi.PSF_KINDS:      # (no handle exists: e.g. variant='pipe' on a problem the pipeline does not cover)
+        if rc == -2 and self._problem.c.data_kind in _capi.POISSON_KINDS + _capi.WL2_KINDS + _capi.PSF_KINDS + (_capi.DATA_SPECTRAL,):      # (no handle exists: e.g. variant='pipe' on a problem the pipeline does not cover)
             raise NotImplementedError(_dev.lib().lmc_last_error().decode())
         _capi.check(rc)
         self._attach_accumulators(acc)
@@ -343,6 +356,7 @@ class MYULASampler:
     _box_refusal = None          # (who, why) of a subclass that has no box-constrained form: raised before a handle exists
     _poisson_refusal = None      # the same for the Poisson data term
     _psf_refusal = None          # the same for a large PSF
+    _spectral_refusal = None     # the same for the Fourier-domain data term
     _eprox_refusal = None        # the same for a closed-form prior (a prox without a value)
 
     def _create(self, cfg):
@@ -627,6 +641,7 @@ class ULPDASampler(MYULASampler):
             raise NotImplementedError("ULPDA does not take a prior with bounds: its prior enters through the dual ball of g o A, which has no box form; use MYULA")
         _refuse_poisson(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA"))
         _refuse_wl2(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, (I + tau sigma Op^T W Op)^{-1}, which is not built; use MYULA"))
+        _refuse_spectral(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal-dual loop is not wired to the closed-form implicit step of this term; use MYULA"))
         _refuse_psf(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which is not built for a large PSF; use MYULA"))
         if isinstance(proxg, L21):
             prior = {"prior_kind": _capi.PRIOR_TV_ISO, "prior_sigma": proxg.sigma, "tv_niter": 1, "tv_betas": [0.0]}
@@ -927,6 +942,7 @@ class MYMALASampler(MYULASampler):
     _box_refusal = ("MYMALA", "its target would be +infinity outside the box, where MYULA's proposals land; use MYULA")
     _poisson_refusal = ("MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK")
     _psf_refusal = ("MYMALA", "its Metropolis ratio is pinned for the fused step, which the three-launch PSF step is not; use MYULA or SK-ROCK")
+    _spectral_refusal = ("MYMALA", "its Metropolis ratio is pinned for the fused step, which the three-launch spectral step is not; use MYULA or SK-ROCK")
     _eprox_refusal = ("MYMALA", "the prior has a prox and no value g(x), so the Metropolis target exp(-f - epsg g) is undefined; use MYULA")
 
     def acceptance(self):

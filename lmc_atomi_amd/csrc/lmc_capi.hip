@@ -51,6 +51,33 @@ int scratch_psf(Scratch& sc, lmc::PsfOp& P, size_t n_resid, hipStream_t st) {
   return LMC_OK;
 }
 
+// The spectral data term of a stateless call: F gets the twiddle table (uploaded once per device, synchronously: it never changes) and the spectrum
+// buffer / value partials of the scratch sc.
+int scratch_fft(Scratch& sc, lmc::FftOp& F, size_t n_spec, size_t n_part) {
+  if (!sc.fft_tw) {
+    float tw[2 * lmc::kFftTw];
+    lmc::fft_twiddles(tw);
+    float* d = nullptr;
+    HIP_TRY(hipMalloc(&d, sizeof tw));
+    hipError_t e = hipMemcpy(d, tw, sizeof tw, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); HIP_TRY(e); }
+    sc.fft_tw = d;
+  }
+  HIP_TRY(sc.need_fft(n_spec, n_part));
+  F.tw = reinterpret_cast<const float2*>(sc.fft_tw);
+  F.spec = reinterpret_cast<float2*>(sc.fft_spec);
+  F.part = sc.fft_part;
+  return LMC_OK;
+}
+
+// the argument checks the stateless transform calls share
+int check_fft_call(const void* x_dev, const void* out_dev, int64_t n_img, int32_t H, int32_t W) {
+  if (!x_dev || !out_dev || x_dev == out_dev) return fail(LMC_E_INVALID, "bad pointers (in-place not allowed)");
+  if (n_img < 1 || H < 1 || W < 1) return fail(LMC_E_INVALID, "bad shape n_img=%lld H=%d W=%d", (long long)n_img, H, W);
+  if (!lmc::fft_shape_ok(H, W)) return fail(LMC_E_UNSUPPORTED, "H and W must be powers of two in %d .. %d (got %dx%d)", lmc::kFftMin, lmc::kFftMax, H, W);
+  return LMC_OK;
+}
+
 }  // namespace
 
 int fail(int code, const char* fmt, ...) {
@@ -158,6 +185,52 @@ int lmc_psf_apply(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, 
   return LMC_OK;
 }
 
+int lmc_rfft2(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, void* stream) {
+  int rc = check_fft_call(x_dev, out_dev, n_img, H, W);
+  if (rc) return rc;
+  lmc::FftOp F;
+  rc = scratch_fft(scratch_here(), F, 0, 0);
+  if (rc) return rc;
+  float2* spec = reinterpret_cast<float2*>(out_dev);
+  HIP_TRY(lmc::launch_fft_rows_fwd(x_dev, spec, F.tw, n_img, H, W, S(stream)));
+  HIP_TRY(lmc::launch_fft_cols(lmc::kFftColFwd, spec, nullptr, F.tw, n_img, H, W, 0.f, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_irfft2(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, void* stream) {
+  int rc = check_fft_call(x_dev, out_dev, n_img, H, W);
+  if (rc) return rc;
+  lmc::FftOp F;
+  const size_t nf = lmc::fft_spec_floats(n_img, H, W);
+  rc = scratch_fft(scratch_here(), F, nf, 0);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(F.spec, x_dev, sizeof(float) * nf, hipMemcpyDeviceToDevice, S(stream)));      // the column pass runs in place: on a copy
+  HIP_TRY(lmc::launch_fft_cols(lmc::kFftColInv, F.spec, nullptr, F.tw, n_img, H, W, 0.f, S(stream)));
+  HIP_TRY(lmc::launch_fft_rows_inv(lmc::kFftStore, F.spec, out_dev, nullptr, F.tw, n_img, H, W, 0.f, 0.f, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_spectral_filter(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, const float* m_dev, void* stream) {
+  int rc = check_fft_call(x_dev, out_dev, n_img, H, W);
+  if (rc) return rc;
+  if (!m_dev) return fail(LMC_E_INVALID, "the multiplier m_dev is NULL");
+  lmc::FftOp F;
+  rc = scratch_fft(scratch_here(), F, lmc::fft_spec_floats(n_img, H, W), 0);
+  if (rc) return rc;
+  HIP_TRY(lmc::launch_fft_rows_fwd(x_dev, F.spec, F.tw, n_img, H, W, S(stream)));
+  HIP_TRY(lmc::launch_fft_cols(lmc::kFftMul, F.spec, m_dev, F.tw, n_img, H, W, 0.f, S(stream)));
+  HIP_TRY(lmc::launch_fft_rows_inv(lmc::kFftStore, F.spec, out_dev, nullptr, F.tw, n_img, H, W, 0.f, 0.f, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_spectral_tables(const double* G_host, const double* b_host, int32_t H, int32_t W, float* out_host) {
+  if (!G_host || !b_host || !out_host) return fail(LMC_E_INVALID, "NULL pointer");
+  if (H < 1 || W < 1) return fail(LMC_E_INVALID, "bad shape H=%d W=%d", H, W);
+  if (!lmc::fft_shape_ok(H, W)) return fail(LMC_E_UNSUPPORTED, "H and W must be powers of two in %d .. %d (got %dx%d)", lmc::kFftMin, lmc::kFftMax, H, W);
+  lmc::fft_tables(G_host, b_host, H, W, out_host);
+  return LMC_OK;
+}
+
 int lmc_gradient(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, void* stream) {
   if (!x_dev || !out_dev || x_dev == out_dev) return fail(LMC_E_INVALID, "bad pointers");
   if (n_img < 1 || H < 1 || W < 1) return fail(LMC_E_INVALID, "bad shape");
@@ -184,6 +257,7 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
   if (!rc) rc = check_poisson(q);
   if (!rc) rc = check_wl2(q);
   if (!rc) rc = check_psf(q);
+  if (!rc) rc = check_spectral(q);
   if (rc) return rc;
   lmc::StepArgs A;
   rc = make_step_args(q, a, t, b, pt, 0.f, A);
@@ -196,6 +270,7 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
   Scratch& sc = scratch_here();
   if (needs_tv_state(q)) HIP_TRY(sc.need_state(4 * npx));
   if (t != 0.f) { rc = scratch_psf(sc, q.psf, npx, S(stream)); if (rc) return rc; }
+  if (t != 0.f && q.fft.on) { rc = scratch_fft(sc, q.fft, lmc::fft_spec_floats(n_img, q.H, q.W), 0); if (rc) return rc; }
   if (t != 0.f && q.ncvx_kind == LMC_NCVX_ME_TV) {
     rc = scratch_me_tv(sc, q, x_dev, n_img, nullptr, S(stream));
     if (rc) return rc;
@@ -225,7 +300,7 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
     A.prior_kind = LMC_PRIOR_NONE;
     A.prox_ext = sc.prox;
   }
-  hipError_t e = launch_step(A, variant_of(q), S(stream), nullptr, sc.state[0], sc.state[1], sc.prox, q.psf.on ? &q.psf : nullptr, &q.wav);
+  hipError_t e = launch_step(A, variant_of(q), S(stream), nullptr, sc.state[0], sc.state[1], sc.prox, q.psf.on ? &q.psf : nullptr, &q.wav, q.fft.on ? &q.fft : nullptr);
   if (e == hipErrorInvalidConfiguration)
     return fail(LMC_E_UNSUPPORTED, A.box ? "step_variant %d has no box-constrained form of this prior (TV: auto, 1 tile, 7 / 8 pipe where the pipe covers the problem)"
                                          : "no step-kernel variant covers this configuration", variant_of(q));
@@ -242,11 +317,17 @@ int lmc_energies(const lmc_problem* prob, const float* x_dev, int64_t n_img, dou
   if (q.pois && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the Poisson data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
   if (q.wl2 && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
   if (q.psf.on && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "a large PSF has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
+  if (q.fft.on && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the spectral data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
   if (f_out_dev) { rc = scratch_psf(scratch_here(), q.psf, 0, S(stream)); if (rc) return rc; }
+  if (f_out_dev && q.fft.on) {
+    rc = scratch_fft(scratch_here(), q.fft, lmc::fft_spec_floats(n_img, q.H, q.W), lmc::fft_value_partials(n_img, q.H, q.W));
+    if (rc) return rc;
+  }
   HIP_TRY(lmc::launch_energies(x_dev, n_img, energy_args(q), f_out_dev, g_out_dev, S(stream)));
   rc = pois_energy(q, x_dev, n_img, f_out_dev, S(stream));
   if (!rc) rc = wl2_energy(q, x_dev, n_img, f_out_dev, S(stream));
   if (!rc) rc = psf_energy(q, x_dev, n_img, f_out_dev, S(stream));
+  if (!rc) rc = spectral_energy(q, x_dev, n_img, f_out_dev, S(stream));
   if (rc) return rc;
   if (q.prior_kind == LMC_PRIOR_HAAR_L1 && g_out_dev) HIP_TRY(lmc::launch_haar_value(x_dev, n_img, q.H, q.W, q.prior_sigma, g_out_dev, S(stream)));
   if (q.wav.on && g_out_dev) {
@@ -285,6 +366,15 @@ int lmc_l2_prox(const lmc_problem* prob, const float* x_dev, float* out_dev, int
   const float ts = tau * q.sigma_f;
   const size_t n = (size_t)n_img * q.H * q.W;
   Scratch& sc = scratch_here();
+  if (q.fft.on) {      // the spectral data term: the implicit step in closed form, (vh + ts B) / (1 + ts A) between the two column transforms
+    if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the spectral data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
+    rc = scratch_fft(sc, q.fft, lmc::fft_spec_floats(n_img, q.H, q.W), 0);
+    if (rc) return rc;
+    HIP_TRY(lmc::launch_fft_rows_fwd(x_dev, q.fft.spec, q.fft.tw, n_img, q.H, q.W, st));
+    HIP_TRY(lmc::launch_fft_cols(lmc::kFftProx, q.fft.spec, q.fft.tab, q.fft.tw, n_img, q.H, q.W, ts, st));
+    HIP_TRY(lmc::launch_fft_rows_inv(lmc::kFftStore, q.fft.spec, out_dev, nullptr, q.fft.tw, n_img, q.H, q.W, 0.f, 0.f, st));
+    return LMC_OK;
+  }
   if (q.data_kind != LMC_DATA_BLUR) {
     const float* xin = x_dev;
     if (q.ncvx_kind != LMC_NCVX_NONE && q.data_kind != LMC_DATA_NONE) {

@@ -56,6 +56,7 @@ struct Problem {
   const float* mask = nullptr;
   lmc::BlurTaps taps{};
   lmc::PsfOp psf;           // LMC_DATA_PSF / POISSON_PSF / WL2_PSF: data_kind = LMC_DATA_PSF (with pois / wl2), the operator and its device table
+  lmc::FftOp fft;           // LMC_DATA_SPECTRAL: the planes at y_dev and the device buffers of whoever owns them
   int prior_kind = 0;
   float prior_sigma = 0.f;
   lmc::WaveletOp wav;       // LMC_PRIOR_WAVELET_L1: p, levels and the workspace of whoever owns it
@@ -134,6 +135,11 @@ struct Scratch {
   float* psf_host = nullptr;
   hipEvent_t psf_ev = nullptr;
   bool psf_valid = false;
+  // spectral data term: the twiddle table (uploaded once), the spectrum buffer [n][H][Wh] complex, the partial sums of the value
+  float* fft_tw = nullptr;
+  float* fft_spec = nullptr;
+  double* fft_part = nullptr;
+  size_t n_fft_spec = 0, n_fft_part = 0;
   size_t n_resid = 0, n_wav = 0, n_wav_part = 0;
   RtState rt_tv, rt_me;                   // device-side early exit of the TV prior's prox / of the ME-TV inner prox
   size_t n_state[2] = {0, 0}, n_extra = 0, n_prox = 0, n_rtmp = 0, n_dbl = 0;   // elements allocated
@@ -156,6 +162,10 @@ struct Scratch {
   hipError_t need_rtmp(size_t n) { return grow(rtmp, n_rtmp, n); }
   hipError_t need_dbl(size_t n) { return grow(dbl, n_dbl, n); }
   hipError_t need_resid(size_t n) { return grow(resid, n_resid, n); }
+  hipError_t need_fft(size_t n_spec, size_t n_part) {
+    hipError_t e = grow(fft_spec, n_fft_spec, n_spec);
+    return e == hipSuccess && n_part ? grow(fft_part, n_fft_part, n_part) : e;
+  }
   hipError_t need_wav(size_t n, size_t n_part) {
     hipError_t e = grow(wav, n_wav, n);
     return e == hipSuccess && n_part ? grow(wav_part, n_wav_part, n_part) : e;
@@ -197,6 +207,8 @@ int check_no_wl2(const Problem& q, const char* who, const char* why);
 int check_wl2(const Problem& q);
 int check_no_psf(const Problem& q, const char* who, const char* why);
 int check_psf(const Problem& q);
+int check_no_spectral(const Problem& q, const char* who, const char* why);
+int check_spectral(const Problem& q);
 bool wl2_pipe_covers(const lmc::StepArgs& A);       // the full-width pipeline has a weighted form of this launch
 bool pois_pipe_covers(const lmc::StepArgs& A);      // the full-width pipeline has a Poisson form of this launch
 int make_step_args(const Problem& q, float a, float t, float b, float pt, float s, lmc::StepArgs& A);
@@ -204,9 +216,11 @@ void sanitize_pointers(lmc::StepArgs& A);
 int variant_of(const Problem& q);
 float tol_of(const Problem& q);
 // psf: the operator of a launch whose data_kind is LMC_DATA_PSF (with its device table and residual buffer); such a launch without it is not covered
+// fft: the same for LMC_DATA_SPECTRAL (with its twiddle table and spectrum buffer)
 // wav: the transform of a launch whose prior_kind is LMC_PRIOR_WAVELET_L1 (with its workspace); such a launch without it, or without pxbuf, is not covered
 hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0 = nullptr,
-                       float* state1 = nullptr, float* pxbuf = nullptr, const lmc::PsfOp* psf = nullptr, const lmc::WaveletOp* wav = nullptr);
+                       float* state1 = nullptr, float* pxbuf = nullptr, const lmc::PsfOp* psf = nullptr, const lmc::WaveletOp* wav = nullptr,
+                       const lmc::FftOp* fft = nullptr);
 
 // ---- lmc_solve.hip ----
 int cg_solve_fused(const Problem& q, float ts, float* u, const float* rhs, float* r, float* p, float* qq, double* scal,
@@ -223,6 +237,7 @@ lmc::EnergyArgs energy_args(const Problem& q);
 int pois_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
 int wl2_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
 int psf_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
+int spectral_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);     // q.fft carries the buffers
 // after launch_energies: g_out = the value of the wavelet prior (nothing for the other priors); q.wav carries the workspace
 int wavelet_energy(const Problem& q, const float* x, int64_t n_img, double* g_out, hipStream_t st);
 int me_tv_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, float* extra, float* st0, float* st1,
@@ -248,6 +263,7 @@ struct lmc_sampler {
   float* pxbuf = nullptr;                   // Haar-l1 prox / early-exit TV prox of the current state
   float* wav_ws = nullptr; double* wav_part = nullptr;    // wavelet prior: the pyramid and the LL ping-pong (1.25 states), the partial sums of its value
   float* psf_tab = nullptr; float* psf_resid = nullptr;   // large PSF: the device tap table (uploaded at creation) and the residual buffer, [C][H][W]
+  float* fft_tw = nullptr; float* fft_spec = nullptr; double* fft_part = nullptr;   // spectral data term: twiddle table, spectrum buffer [C][H][Wh] complex, value partials
   float* rtmp = nullptr; double* robj = nullptr; int* rflag = nullptr;   // early-exit TV prox (tv_rtol > 0), pass-by-pass path: pass iterate, objectives, flags
   lmc::host::RtState rt_tv, rt_me;          // early-exit TV prox on the device (tv_prox_rt): of the TV prior / of the ME-TV inner prox
   // launch policy, fixed at creation (lmc_problem fields; their environment variables supply the defaults): see lmc_atomi.h

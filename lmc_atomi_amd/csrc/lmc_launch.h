@@ -265,3 +265,51 @@ hipError_t launch_wavelet_value(const float* x, int64_t n_img, int H, int W, int
 // out = W x or W^T x (Mallat layout); x != out; ws as for the value
 hipError_t launch_wavelet_apply(const float* x, float* out, int64_t n_img, int H, int W, int p, int levels, int inverse_dir, float* ws, hipStream_t st);
 }  // namespace lmc
+
+namespace lmc {
+// The spectral data term (lmc_fft.hip, lmc_fft_kernel.h): the batched 2-D real FFT in LDS of LMC_DATA_SPECTRAL, lmc_rfft2 / lmc_irfft2 and
+// lmc_spectral_filter; power-of-two sides kFftMin .. kFftMax, the half plane of W / 2 + 1 columns, norm = "ortho".
+constexpr int kFftMin = 8, kFftMax = 1024;
+constexpr int kFftTw = kFftMax;           // entries of the twiddle table: exp(-2 pi i m / kFftTw)
+constexpr int kFftThreads = 512;          // eight waves share the two LDS buffers of a workgroup: two workgroups per CU, four waves per SIMD
+constexpr int kFftElems = 4096;           // complex values of one of a workgroup's two LDS buffers: kFftElems / N lines of length N
+constexpr int kFftPlanes = 11;            // planes [H][Wh] of the descriptor at lmc_problem.y_dev
+// what fft_rows_inv_kernel does with the real part v of the inverted row
+enum FftEpi {
+  kFftStore = 0,    // out = v
+  kFftSub,          // out -= coef v
+  kFftOverwrite     // out = a x - coef v
+};
+// what fft_cols_spectral_kernel does between (or in place of) its two column transforms
+enum FftMode {
+  kFftColFwd = 0,   // forward only
+  kFftColInv,       // inverse only
+  kFftGrad,         // A xh - B
+  kFftProx,         // (vh + ts B) / (1 + ts A)
+  kFftMul,          // M xh
+  kFftValue         // part[image][strip] = sum |G xh - b|^2 + |conj(G_-k) xh - conj(b_-k)|^2
+};
+// The operator of a validated problem and the device buffers of whoever owns them (a sampler handle, the stateless scratch): tw the twiddle table
+// (fft_twiddles), spec [n][H][W / 2 + 1] complex, part fft_value_partials doubles.
+struct FftOp {
+  int on = 0;
+  const float* tab = nullptr;       // lmc_problem.y_dev: [kFftPlanes][H][Wh]
+  const float2* tw = nullptr;
+  float2* spec = nullptr;
+  double* part = nullptr;
+};
+bool fft_shape_ok(int H, int W);
+void fft_twiddles(float* tw_host /* [2 * kFftTw] */);     // float64 sine and cosine, rounded once
+size_t fft_spec_floats(int64_t n_img, int H, int W);
+size_t fft_value_partials(int64_t n_img, int H, int W);
+// host: the descriptor planes from G and b ([H][W] complex, interleaved float64), folded in float64
+void fft_tables(const double* G, const double* b, int H, int W, float* out);
+hipError_t launch_fft_rows_fwd(const float* x, float2* spec, const float2* tw, int64_t n_img, int H, int W, hipStream_t st);
+// mode: FftMode but kFftValue; tab: the planes the functor reads
+hipError_t launch_fft_cols(int mode, float2* spec, const float* tab, const float2* tw, int64_t n_img, int H, int W, float ts, hipStream_t st);
+// epi: FftEpi; xin: kFftOverwrite
+hipError_t launch_fft_rows_inv(int epi, const float2* spec, float* out, const float* xin, const float2* tw, int64_t n_img, int H, int W, float a, float coef,
+                               hipStream_t st);
+// f_out[c] += sigma_f / 2 * the half-plane sum at x_c, float64 by partial sums in a fixed order
+hipError_t launch_fft_value(const FftOp& F, const float* x, int64_t n_img, int H, int W, float sigma_f, double* f_out, hipStream_t st);
+}  // namespace lmc

@@ -91,6 +91,14 @@ int load_problem(const lmc_problem* p, Problem& q) {
         return fail(LMC_E_INVALID, "psf_separable = 1 on a kernel that is no outer product to 2^-22 of every tap (lmc_psf_separable)");
       break;
     }
+    case LMC_DATA_SPECTRAL:
+      if (!p->y_dev) return fail(LMC_E_INVALID, "LMC_DATA_SPECTRAL needs y_dev: the [11][H][W / 2 + 1] planes of lmc_spectral_tables");
+      if (p->mask_dev || p->h_host || p->kh || p->kw || p->oy || p->ox || p->psf_kh || p->psf_kw || p->psf_oy || p->psf_ox)
+        return fail(LMC_E_INVALID, "LMC_DATA_SPECTRAL reads y_dev alone: mask_dev, h_host, kh, kw, oy, ox and the psf_* fields must be NULL / 0");
+      if (!lmc::fft_shape_ok(p->H, p->W))
+        return fail(LMC_E_UNSUPPORTED, "LMC_DATA_SPECTRAL: H and W must be powers of two in %d .. %d (got %dx%d)", lmc::kFftMin, lmc::kFftMax, p->H, p->W);
+      q.fft.on = 1; q.fft.tab = p->y_dev;
+      break;
     default: return fail(LMC_E_INVALID, "unknown data_kind %d", p->data_kind);
   }
   q.prior_kind = p->prior_kind;
@@ -263,6 +271,22 @@ int check_psf(const Problem& q) {
   return LMC_OK;
 }
 
+// The entry points that have no form of the spectral data term refuse a problem that carries one.
+int check_no_spectral(const Problem& q, const char* who, const char* why) {
+  if (!q.fft.on) return LMC_OK;
+  return fail(LMC_E_UNSUPPORTED, "%s does not take the spectral data term (LMC_DATA_SPECTRAL): %s", who, why);
+}
+
+// What the entry points that do take it refuse with it: what does not split into spectrum, prior launch and inverse transform.
+int check_spectral(const Problem& q) {
+  if (!q.fft.on) return LMC_OK;
+  if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the spectral data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
+  const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
+  if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "the spectral data term with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0");
+  if (q.tv_warm_asked) return fail(LMC_E_UNSUPPORTED, "the spectral data term with tv_warm: the warm-started dual is not built for it");
+  return LMC_OK;
+}
+
 // What the entry points that form prox_g (MYULA, MYMALA, lmc_fused_eval) ask of the anisotropic TV prior beyond load_problem: an iteration
 // count, and none of the options that are built for the isotropic prior only.
 int check_prox_prior(const Problem& q, float b) {
@@ -411,8 +435,31 @@ static hipError_t launch_step_psf(const lmc::StepArgs& A, int variant, hipStream
   return lmc::launch_psf(*psf, 1, lmc::kPsfSub, psf->resid, A.x_out, nullptr, nullptr, A.C, A.H, A.W, 0.f, coef, st);
 }
 
+// The spectral data term: the same three steps.  The spectrum A xh - B of the gradient into fft->spec (row transform, then the column kernel with its
+// functor between the two column transforms); the step of the same arguments without a data term; x_out -= t sigma_f irfft (row inverse).  Without prox
+// and noise the last launch writes a x - t sigma_f irfft.
+static hipError_t launch_step_fft(const lmc::StepArgs& A, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf,
+                                  const lmc::FftOp* fft) {
+  if (!fft || !fft->on || !fft->tab || !fft->tw || !fft->spec) return hipErrorInvalidConfiguration;
+  if (A.ncvx_kind != LMC_NCVX_NONE || A.extra || A.tv_in || A.tv_out || A.f_out || A.g_out || A.rt_kc) return hipErrorInvalidConfiguration;
+  hipError_t e = lmc::launch_fft_rows_fwd(A.x_in, fft->spec, fft->tw, A.C, A.H, A.W, st);
+  if (e != hipSuccess) return e;
+  e = lmc::launch_fft_cols(lmc::kFftGrad, fft->spec, fft->tab, fft->tw, A.C, A.H, A.W, 0.f, st);
+  if (e != hipSuccess) return e;
+  const float coef = A.t * A.sigma_f;
+  if (A.b == 0.f && A.s == 0.f) {
+    if (name) *name = "fft_rows_inv_kernel";
+    return lmc::launch_fft_rows_inv(lmc::kFftOverwrite, fft->spec, A.x_out, A.x_in, fft->tw, A.C, A.H, A.W, A.a, coef, st);
+  }
+  lmc::StepArgs B = A;
+  B.data_kind = LMC_DATA_NONE; B.t = 0.f;
+  e = launch_step(B, variant, st, name, state0, state1, pxbuf);      // (a wavelet prior: launch_step has formed its prox already, B carries it)
+  if (e != hipSuccess) return e;
+  return lmc::launch_fft_rows_inv(lmc::kFftSub, fft->spec, A.x_out, nullptr, fft->tw, A.C, A.H, A.W, 0.f, coef, st);
+}
+
 hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf,
-                       const lmc::PsfOp* psf, const lmc::WaveletOp* wav) {
+                       const lmc::PsfOp* psf, const lmc::WaveletOp* wav, const lmc::FftOp* fft) {
   if (A_in.prior_kind == LMC_PRIOR_WAVELET_L1) {
     // the route of LMC_PRIOR_HAAR_L1 in launch_step_nobox, taken before the data terms part ways: the prox into pxbuf, then the step of the same
     // problem without a prior, which consumes it as a ready-made prox -- on whatever kernel that problem gets
@@ -422,9 +469,10 @@ hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, c
     lmc::StepArgs A = A_in;
     A.prior_kind = LMC_PRIOR_NONE;
     A.prox_ext = pxbuf;
-    return launch_step(A, variant, st, name, state0, state1, pxbuf, psf, nullptr);
+    return launch_step(A, variant, st, name, state0, state1, pxbuf, psf, nullptr, fft);
   }
   if (A_in.data_kind == LMC_DATA_PSF) return launch_step_psf(A_in, variant, st, name, state0, state1, pxbuf, psf);
+  if (A_in.data_kind == LMC_DATA_SPECTRAL) return launch_step_fft(A_in, variant, st, name, state0, state1, pxbuf, fft);
   if (A_in.pois) return launch_step_pois(A_in, variant, st, name, state0, state1, pxbuf);
   if (A_in.wl2) return launch_step_wl2(A_in, variant, st, name, state0, state1, pxbuf);
   if (!A_in.box) return launch_step_nobox(A_in, variant, st, name, state0, state1, pxbuf);

@@ -97,6 +97,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   if (!rc) rc = check_poisson(s->prob);
   if (!rc) rc = check_wl2(s->prob);
   if (!rc) rc = check_psf(s->prob);
+  if (!rc) rc = check_spectral(s->prob);
   if (rc) { delete s; return rc; }
   if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }
   s->C = cfg->n_chains;
@@ -133,6 +134,17 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     s->prob.psf.tab_dev = s->psf_tab;
     s->prob.psf.resid = s->psf_resid;
   }
+  if (e == hipSuccess && s->prob.fft.on) {     // spectral data term: the handle uploads the twiddle table once and owns the spectrum buffer and the value partials
+    float tw[2 * lmc::kFftTw];
+    lmc::fft_twiddles(tw);
+    e = hipMalloc(&s->fft_tw, sizeof tw);
+    if (e == hipSuccess) e = hipMemcpy(s->fft_tw, tw, sizeof tw, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&s->fft_spec, sizeof(float) * lmc::fft_spec_floats(s->C, s->prob.H, s->prob.W));
+    if (e == hipSuccess) e = hipMalloc(&s->fft_part, sizeof(double) * lmc::fft_value_partials(s->C, s->prob.H, s->prob.W));
+    s->prob.fft.tw = reinterpret_cast<const float2*>(s->fft_tw);
+    s->prob.fft.spec = reinterpret_cast<float2*>(s->fft_spec);
+    s->prob.fft.part = s->fft_part;
+  }
   if (e == hipSuccess && s->prob.wav.on) {     // wavelet prior: the handle owns the pyramid, the LL ping-pong and the partial sums of the value
     e = hipMalloc(&s->wav_ws, sizeof(float) * lmc::wavelet_ws_floats(s->C, s->prob.H, s->prob.W));
     if (e == hipSuccess) e = hipMalloc(&s->wav_part, sizeof(double) * (size_t)s->C * lmc::wavelet_partials(s->prob.H, s->prob.W, s->prob.wav.levels));
@@ -164,6 +176,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     if (q.wl2) { s->pol_pair = 0; s->pol_blockpair = 0; }                   // weighted Gaussian data term: the same
     if (q.pois) { s->pol_pair = 0; s->pol_blockpair = 0; }                  // Poisson data term: one iteration per launch (the pair kernels have no form of it)
     if (q.psf.on) { s->pol_pair = 0; s->pol_blockpair = 0; }                // large PSF: three launches per iteration
+    if (q.fft.on) { s->pol_pair = 0; s->pol_blockpair = 0; }                // spectral data term: the same
     if (q.wav.on) { s->pol_pair = 0; s->pol_blockpair = 0; }                // wavelet prior: the prox is launches of its own before every step
   }
   if (e == hipSuccess && s->prob.tv_warm) {
@@ -190,10 +203,11 @@ void lmc_sampler_destroy(lmc_sampler* s) {
   if (!s) return;
   DeviceGuard dg(s->device);
   for (float* b : {s->xmid[0], s->xmid[1], s->xspare, s->zero_y, s->xhat, s->ydual, s->uw, s->uw2, s->rhs, s->cr, s->cp, s->cq, s->ctmp, s->xi, s->htb, s->tvstate[0], s->tvstate[1], s->extra, s->pxbuf, s->wav_ws,
-                   s->psf_tab, s->psf_resid, s->mx, s->xp, s->mxp, s->tvwarm[0], s->tvwarm[1], s->rtmp})
+                   s->psf_tab, s->psf_resid, s->fft_tw, s->fft_spec, s->mx, s->xp, s->mxp, s->tvwarm[0], s->tvwarm[1], s->rtmp})
     if (b) (void)hipFree(b);
   if (s->robj) (void)hipFree(s->robj);
   if (s->wav_part) (void)hipFree(s->wav_part);
+  if (s->fft_part) (void)hipFree(s->fft_part);
   if (s->rflag) (void)hipFree(s->rflag);
   s->rt_tv.release();
   s->rt_me.release();
@@ -244,6 +258,7 @@ static int sampler_energies_at(lmc_sampler* s, const float* x, double* f_out_dev
     int rc = pois_energy(s->prob, x, s->C, f_out_dev, st);
     if (!rc) rc = wl2_energy(s->prob, x, s->C, f_out_dev, st);
     if (!rc) rc = psf_energy(s->prob, x, s->C, f_out_dev, st);
+    if (!rc) rc = spectral_energy(s->prob, x, s->C, f_out_dev, st);
     if (rc) return rc;
   }
   if (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 && g_out_dev)
@@ -314,7 +329,7 @@ static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool 
   int rc = me_tv_extra(s, A, st);   // inner prox of the Moreau-envelope term, then the fused step
   if (rc) return rc;
   if (ov && ov->ev_begin) HIP_TRY(hipEventRecord(ov->ev_begin, st));
-  hipError_t e = launch_step(A, variant_of(s->prob), st, kname, s->tvstate[0], s->tvstate[1], s->pxbuf, s->prob.psf.on ? &s->prob.psf : nullptr, &s->prob.wav);
+  hipError_t e = launch_step(A, variant_of(s->prob), st, kname, s->tvstate[0], s->tvstate[1], s->pxbuf, s->prob.psf.on ? &s->prob.psf : nullptr, &s->prob.wav, s->prob.fft.on ? &s->prob.fft : nullptr);
   if (e == hipErrorInvalidConfiguration) return fail(LMC_E_UNSUPPORTED, "no step-kernel variant covers this configuration");
   HIP_TRY(e);
   if (ov && ov->ev_end) HIP_TRY(hipEventRecord(ov->ev_end, st));
@@ -498,7 +513,7 @@ static int myula_single(lmc_sampler* s, SideMoments& m, const float* noise, bool
     kname = "myula_step_pipe_kernel(warm)";
     s->wcur ^= 1;
   } else {
-    e = launch_step(A, variant_of(s->prob), st, &kname, s->tvstate[0], s->tvstate[1], s->pxbuf, s->prob.psf.on ? &s->prob.psf : nullptr, &s->prob.wav);
+    e = launch_step(A, variant_of(s->prob), st, &kname, s->tvstate[0], s->tvstate[1], s->pxbuf, s->prob.psf.on ? &s->prob.psf : nullptr, &s->prob.wav, s->prob.fft.on ? &s->prob.fft : nullptr);
   }
   if (e == hipErrorInvalidConfiguration)
     return fail(LMC_E_UNSUPPORTED, s->base.box ? "step_variant %d has no box-constrained form of this prior (TV: auto, 1 tile, 7 / 8 pipe where the pipe covers the problem)"
@@ -583,6 +598,11 @@ int lmc_sampler_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, vo
 
 // ---- MYMALA: Metropolis-adjusted MYULA at image scale (generalises prox_lmc.py:134-158) -------------------------------
 int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out) {
+  if (cfg && out && cfg->struct_size == sizeof(lmc_myula_config) && cfg->problem.data_kind == LMC_DATA_SPECTRAL) {      // (before any buffer exists)
+    *out = nullptr;
+    return fail(LMC_E_UNSUPPORTED, "MYMALA does not take the spectral data term (LMC_DATA_SPECTRAL): its Metropolis ratio is pinned for the fused step and its "
+                "energy by-products, which the three-launch spectral step does not form; use MYULA or SK-ROCK");
+  }
   int rc = lmc_myula_create(cfg, out);
   if (rc) return rc;
   lmc_sampler* s = *out;
@@ -897,6 +917,7 @@ int lmc_ulpda_create(const lmc_ulpda_config* cfg, lmc_sampler** out) {
   if (!rc) rc = check_no_wl2(s->prob, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f Op^T W Op)^{-1}, which is not built; use MYULA");
   if (!rc) rc = check_no_poisson(s->prob, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA");
   if (!rc) rc = check_no_psf(s->prob, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f H^T H)^{-1}, which is not built for a large PSF; use MYULA");
+  if (!rc) rc = check_no_spectral(s->prob, "ULPDA", "its primal step through lmc_l2_prox's closed form is not wired into the primal-dual loop; use MYULA");
   if (!rc) rc = check_no_box(s->prob, "ULPDA", "its prior enters through the dual ball of g o A, which has no box form; use MYULA");
   if (rc) { delete s; return rc; }
   if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }

@@ -202,7 +202,7 @@ int tv_prior_rt_mode(const Problem& q, const lmc::StepArgs& A_probe, float pt) {
 lmc::EnergyArgs energy_args(const Problem& q) {
   lmc::EnergyArgs E;
   // (a Poisson or a weighted Gaussian data term: none here -- f stays 0 and pois_energy / wl2_energy adds its value)
-  E.H = q.H; E.W = q.W; E.data_kind = (q.pois || q.wl2 || q.psf.on) ? LMC_DATA_NONE : q.data_kind; E.sigma_f = q.sigma_f; E.y = q.y; E.mask = q.mask;
+  E.H = q.H; E.W = q.W; E.data_kind = (q.pois || q.wl2 || q.psf.on || q.fft.on) ? LMC_DATA_NONE : q.data_kind; E.sigma_f = q.sigma_f; E.y = q.y; E.mask = q.mask;
   E.blur = q.taps; E.prior_kind = q.prior_kind; E.prior_sigma = q.prior_sigma;
   E.ncvx_kind = q.ncvx_kind == LMC_NCVX_MC_TV ? LMC_NCVX_MC_TV : LMC_NCVX_NONE;   // ME-TV envelope: me_tv_energy
   E.ncvx_lambda = q.ncvx_lambda; E.ncvx_gamma = q.ncvx_gamma;
@@ -242,6 +242,13 @@ int psf_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, h
   Scratch& sc = scratch_here();
   HIP_TRY(sc.need_dbl(lmc::psf_energy_partials(n_img, q.H, q.W)));
   HIP_TRY(lmc::launch_psf_energy(q.psf, q.pois ? 2 : q.wl2 ? 1 : 0, x, q.y, n_img, q.H, q.W, q.sigma_f, sc.dbl, f_out, st));
+  return LMC_OK;
+}
+
+// the same for the spectral data term (LMC_DATA_SPECTRAL): row transform, column transform and residuals, the fixed-order sum
+int spectral_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st) {
+  if (!q.fft.on || !f_out) return LMC_OK;
+  HIP_TRY(lmc::launch_fft_value(q.fft, x, n_img, q.H, q.W, q.sigma_f, f_out, st));
   return LMC_OK;
 }
 

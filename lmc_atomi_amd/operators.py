@@ -249,3 +249,171 @@ class Diagonal(LinearOperator):
         self.d = np.ascontiguousarray(np.asarray(d, dtype=np.float32)).ravel()
         self.dims = None if dims is None else (int(dims[0]), int(dims[1]))
         super().__init__((self.d.size, self.d.size))
+
+
+def rfft2(x):
+    """``numpy.fft.rfft2(x, norm="ortho")`` of real images on the last two axes (``lmc_rfft2``: the LDS transforms of the spectral data term): sides that
+    are powers of two in 8 .. 1024, complex64 on the half plane ``[..., H, W // 2 + 1]``.  numpy in, numpy out; a torch tensor in HBM stays there."""
+    import torch
+    if np.ndim(x) < 2:
+        raise ValueError("rfft2 takes images on the last two axes")
+    H, W = _capi.check_fft_dims(tuple(x.shape)[-2:])
+    t = _dev.to_dev(x)
+    n_img = t.numel() // (H * W)
+    out = torch.empty(tuple(t.shape[:-1]) + (W // 2 + 1, 2), dtype=torch.float32, device=t.device)
+    _dev.run(t, "lmc_rfft2", _dev.ptr(t), _dev.ptr(out), n_img, H, W)
+    c = torch.view_as_complex(out)
+    return c if isinstance(x, torch.Tensor) else c.cpu().numpy()
+
+
+def irfft2(c, dims):
+    """``numpy.fft.irfft2(c, s=dims, norm="ortho")`` of half-plane spectra ``[..., H, W // 2 + 1]`` (``lmc_irfft2``), float32 images ``[..., H, W]``."""
+    import torch
+    H, W = _capi.check_fft_dims(dims)
+    if np.ndim(c) < 2 or tuple(c.shape)[-2:] != (H, W // 2 + 1):
+        raise ValueError(f"irfft2: a spectrum of shape {tuple(np.shape(c))} is not the half plane [..., {H}, {W // 2 + 1}] of {H} x {W} images")
+    if isinstance(c, torch.Tensor):
+        if not c.is_complex():
+            raise ValueError("irfft2 takes a complex spectrum")
+        t = torch.view_as_real(c.to(device=_dev.device(c.device if c.is_cuda else None), dtype=torch.complex64).contiguous())
+    else:
+        a = np.ascontiguousarray(np.asarray(c), dtype=np.complex64)
+        t = torch.from_numpy(a.view(np.float32).reshape(a.shape + (2,))).to(_dev.device(None))
+    n_img = t.numel() // (2 * H * (W // 2 + 1))
+    out = torch.empty(tuple(t.shape[:-3]) + (H, W), dtype=torch.float32, device=t.device)
+    _dev.run(t, "lmc_irfft2", _dev.ptr(t), _dev.ptr(out), n_img, H, W)
+    return out if isinstance(c, torch.Tensor) else out.cpu().numpy()
+
+
+def _minus_k(a):
+    """``a`` at ``-k = ((-i) mod H, (-j) mod W)``."""
+    return np.roll(np.flip(a, (0, 1)), (1, 1), (0, 1))
+
+
+def spectral_tables(G, b):
+    """The ``[11, H, W // 2 + 1]`` float32 planes of ``LMC_DATA_SPECTRAL`` from the full-plane complex gain ``G`` and data ``b`` (``lmc_spectral_tables``:
+    host only, folded in float64)."""
+    G = np.ascontiguousarray(G, dtype=np.complex128)
+    b = np.ascontiguousarray(b, dtype=np.complex128)
+    H, W = _capi.check_fft_dims(G.shape)
+    out = np.empty((_capi.SPECTRAL_PLANES, H, W // 2 + 1), dtype=np.float32)
+    dptr = lambda a: a.view(np.float64).ctypes.data_as(_capi.C.POINTER(_capi.C.c_double))      # noqa: E731
+    _capi.check(_capi.load().lmc_spectral_tables(dptr(G), dptr(b), H, W, _dev.fptr(out)))
+    return out
+
+
+class FourierSampling:
+    """Observation in Fourier space (build extension; ``LMC_DATA_SPECTRAL`` in include/lmc_atomi.h is its definition): ``y = G * F x + noise`` with F the
+    unitary 2-D DFT in numpy's unshifted ``fft2(norm="ortho")`` order and ``G = mask * transfer`` per frequency -- subsampled k-space MRI, gridded
+    radio-interferometric visibilities.  ``mask``: real, >= 0, finite, full plane ``[H, W]`` (it need not be Hermitian-symmetric); ``transfer``: an
+    optional complex ``[H, W]`` array.  Sides: powers of two in 8 .. 1024.  Use as ``L2(Op=FourierSampling(dims, mask), b=y_complex, sigma=...)``, with
+    ``weights=w`` per frequency for ``G sqrt(w)`` and ``b sqrt(w)``: ``grad``, ``__call__``, the closed-form ``prox`` and ``grad_lipschitz``; as
+    ``proxf`` of MYULA, SK-ROCK and :func:`EstimatePriorWeight` with every prior and ``bounds=`` a problem without a data term takes.  MYMALA, ULPDA,
+    :class:`Poisson`, the non-convex terms, ``TV(rtol > 0)`` and ``TV(warm=True)`` raise ``NotImplementedError``."""
+
+    def __init__(self, dims, mask, transfer=None):
+        self.dims = _capi.check_fft_dims(dims)
+        m = np.asarray(mask)
+        if np.iscomplexobj(m) or m.shape != self.dims:
+            raise ValueError(f"FourierSampling: mask must be a real array of the full plane {self.dims} (got shape {m.shape}, dtype {m.dtype})")
+        m = m.astype(np.float64)
+        if not np.all(np.isfinite(m)) or np.any(m < 0):
+            raise ValueError("FourierSampling: the mask must be finite and >= 0")
+        self.mask = m
+        self.transfer = None
+        if transfer is not None:
+            t = np.asarray(transfer, dtype=np.complex128)
+            if t.shape != self.dims:
+                raise ValueError(f"FourierSampling: transfer of shape {t.shape} for the full plane {self.dims}")
+            if not np.all(np.isfinite(t)):
+                raise ValueError("FourierSampling: the transfer function must be finite")
+            self.transfer = t
+        n = self.dims[0] * self.dims[1]
+        self.shape = (n, n)
+
+    def gain(self):
+        """G, complex128 ``[H, W]``."""
+        return self.mask.astype(np.complex128) if self.transfer is None else self.mask * self.transfer
+
+    def data(self, b):
+        """``b`` as the complex full-plane data; a real ``b`` is refused (k-space measurements are complex)."""
+        a = b.detach().cpu().numpy() if hasattr(b, "detach") else np.asarray(b)
+        if not np.iscomplexobj(a):
+            raise ValueError("L2 with FourierSampling: b must be complex, the measurements on the full plane [H, W]")
+        if a.size != self.dims[0] * self.dims[1]:
+            raise ValueError(f"L2 with FourierSampling: {a.size} measurements for the full plane {self.dims}")
+        a = a.astype(np.complex128).reshape(self.dims)
+        if not np.all(np.isfinite(a)):
+            raise ValueError("L2 with FourierSampling: b must be finite (drop a frequency with mask 0, not with NaN)")
+        return a
+
+
+class PeriodicConvolve2D(LinearOperator):
+    """Periodic (wrap-around) convolution with a kernel ``h`` of any support up to the image and origin ``offset`` (default: the centre tap):
+    ``(H x)[i, j] = sum_ab h[a, b] x[(i - a + oy) mod H, (j - b + ox) mod W]`` -- :class:`Convolve2D` with the borders joined.  In Fourier space the blur
+    is a diagonal multiply whatever its support: ``matvec``, ``rmatvec`` and ``.H`` run ``lmc_spectral_filter`` with the unnormalised DFT of the kernel
+    wrapped about its origin (``rmatvec``: its conjugate).  Sides: powers of two in 8 .. 1024.  As ``Op`` of ``L2(Op, b_real, sigma)`` it makes the
+    descriptor of :class:`FourierSampling` with ``G`` that DFT and ``b = F(observation)``."""
+
+    def __init__(self, dims, h, offset=None):
+        self.dims = _capi.check_fft_dims(dims)
+        n = self.dims[0] * self.dims[1]
+        super().__init__((n, n))
+        h64 = np.asarray(h, dtype=np.float64)
+        if h64.ndim != 2:
+            raise ValueError("h must be 2-D")
+        kh, kw = h64.shape
+        if kh < 1 or kw < 1 or kh > self.dims[0] or kw > self.dims[1]:
+            raise ValueError(f"a {kh}x{kw} kernel does not fit the {self.dims[0]} x {self.dims[1]} image")
+        if not np.all(np.isfinite(h64)):
+            raise ValueError("the taps of the kernel must be finite")
+        self.h = h64
+        self.offset = (kh // 2, kw // 2) if offset is None else (int(offset[0]), int(offset[1]))
+        if not (0 <= self.offset[0] < kh and 0 <= self.offset[1] < kw):
+            raise ValueError(f"offset {self.offset} outside the {kh}x{kw} kernel")
+        self._mult = {}
+
+    def gain(self):
+        """G: the unnormalised DFT of the kernel wrapped about its origin, complex128 ``[H, W]``."""
+        H, W = self.dims
+        k = np.zeros(self.dims)
+        kh, kw = self.h.shape
+        ii = (np.arange(kh) - self.offset[0]) % H
+        jj = (np.arange(kw) - self.offset[1]) % W
+        np.add.at(k, (ii[:, None], jj[None, :]), self.h)
+        return np.fft.fft2(k)
+
+    def data(self, b):
+        """F(observation) of a real observation ``b`` of the image's size."""
+        a = b.detach().cpu().numpy() if hasattr(b, "detach") else np.asarray(b)
+        if np.iscomplexobj(a):
+            raise ValueError("L2 with PeriodicConvolve2D: b is the real observation (its transform is taken here)")
+        if a.size != self.dims[0] * self.dims[1]:
+            raise ValueError(f"L2 with PeriodicConvolve2D: {a.size} observations for an image of shape {self.dims}")
+        a = a.astype(np.float64).reshape(self.dims)
+        if not np.all(np.isfinite(a)):
+            raise ValueError("L2 with PeriodicConvolve2D: b must be finite")
+        return np.fft.fft2(a, norm="ortho")
+
+    def _multiplier(self, adjoint, dev):
+        key = (bool(adjoint), dev)
+        if key not in self._mult:
+            G = self.gain()[:, : self.dims[1] // 2 + 1]
+            if adjoint:
+                G = np.conj(G)
+            self._mult[key] = _dev.to_dev(np.stack([G.real, G.imag]), dev)
+        return self._mult[key]
+
+    def _apply(self, x, adjoint):
+        import torch
+        t, n_img, _ = self._batch(x, self.shape[1])
+        out = torch.empty_like(t)
+        m = self._multiplier(adjoint, t.device)
+        _dev.run(t, "lmc_spectral_filter", _dev.ptr(t), _dev.ptr(out), n_img, self.dims[0], self.dims[1], _dev.ptr(m))
+        return _dev.like_input(out.reshape(tuple(np.shape(x))), x)
+
+    def matvec(self, x):
+        return self._apply(x, False)
+
+    def rmatvec(self, y):
+        return self._apply(y, True)

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _capi, _dev
-from .operators import PSF, Convolve2D, Diagonal, Identity, LinearOperator
+from .operators import PSF, Convolve2D, Diagonal, FourierSampling, Identity, LinearOperator, PeriodicConvolve2D, _minus_k, spectral_tables
 
 
 _warned_pass_by_pass = False
@@ -125,7 +125,10 @@ class _Problem:
         p.sigma_f = float(data.get("sigma_f", 0.0))
         if data.get("y") is not None:
             # (a Poisson term: [2][H][W], the counts then the background; a weighted Gaussian term: the observation then the weights)
-            y = _dev.to_dev(data["y"], dev).reshape(((2,) if p.data_kind in _capi.TWO_PLANE_KINDS else ()) + self.dims)
+            if p.data_kind == _capi.DATA_SPECTRAL:      # the spectral term: the [11][H][W / 2 + 1] planes of lmc_spectral_tables
+                y = _dev.to_dev(data["y"], dev).reshape(_capi.SPECTRAL_PLANES, self.dims[0], self.dims[1] // 2 + 1)
+            else:
+                y = _dev.to_dev(data["y"], dev).reshape(((2,) if p.data_kind in _capi.TWO_PLANE_KINDS else ()) + self.dims)
             self._keep.append(y)
             p.y_dev = y.data_ptr()
         if data.get("mask") is not None:
@@ -246,8 +249,36 @@ class L2(ProxOperator):
         self._prob = None
         self._x0 = None          # warm-start vector of the implicit step (stateful, as the reference's L2)
         self.weights = None
-        if weights is not None:
+        self._spectral = None
+        if isinstance(Op, (FourierSampling, PeriodicConvolve2D)):
+            self._set_spectral(weights)
+        elif weights is not None:
             self._set_weights(weights)
+
+    def _set_spectral(self, weights):
+        """The Fourier-domain data term (``LMC_DATA_SPECTRAL``): G and b of the operator, ``weights`` per frequency as G sqrt(w) and b sqrt(w), folded once on
+        the host into the planes ``y_dev`` points to."""
+        if self.b is None:
+            raise ValueError(f"L2 with {type(self.Op).__name__} needs b: the measurements")
+        self.dims = self.Op.dims
+        G, b = self.Op.gain(), self.Op.data(self.b)
+        if weights is not None:
+            w = _host(weights).astype(np.float64)
+            if w.size != G.size or w.ndim not in (1, 2) or (w.ndim == 2 and w.shape != self.dims):
+                raise ValueError(f"L2: weights of shape {w.shape} for the full plane {self.dims} (one weight per frequency)")
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError("L2: the weights must be finite and >= 0")
+            rw = np.sqrt(w.reshape(self.dims))
+            G, b = G * rw, b * rw
+        self._spectral = {"G": G, "b": b, "tab": spectral_tables(G, b), "dev": {}}
+        self._amax = float(np.max(0.5 * (np.abs(G) ** 2 + np.abs(_minus_k(G)) ** 2)))
+
+    def _spectral_buffer(self):
+        """The planes on the current device, uploaded once (per device) and kept alive by this object."""
+        key = _dev.device(None)
+        if key not in self._spectral["dev"]:
+            self._spectral["dev"][key] = _dev.to_dev(self._spectral["tab"], key)
+        return self._spectral["dev"][key]
 
     def _set_weights(self, weights):
         """Validates the per-pixel weights and builds the [2][H][W] host array (observation, weights) that ``y_dev`` points to."""
@@ -292,6 +323,8 @@ class L2(ProxOperator):
     def grad_lipschitz(self):
         """``L_f = sigma * max(w) * ||Op||^2`` with ``||Op|| <= sum |h|`` for a convolution and the factor 1 for a mask (entries in [0, 1]), the
         identity or no operator; ``max(w) = 1`` without weights.  Host arithmetic, no GPU."""
+        if self._spectral is not None:      # sigma max_k A_k, A the folded |G|^2
+            return self.sigma * self._amax
         op2 = float(np.abs(np.asarray(self.Op.h, dtype=np.float64)).sum()) ** 2 if isinstance(self.Op, (Convolve2D, PSF)) else 1.0
         wmax = float(np.max(self.weights)) if self.weights is not None else 1.0
         return self.sigma * wmax * op2
@@ -299,6 +332,9 @@ class L2(ProxOperator):
     # -- descriptors ---------------------------------------------------------------------
     def descriptor(self):
         """As the data term f of the sampler."""
+        if self._spectral is not None:
+            tab = self._spectral_buffer() if torch.cuda.is_available() else self._spectral["tab"]
+            return {"data_kind": _capi.DATA_SPECTRAL, "sigma_f": self.sigma, "y": tab}
         if self.weights is not None:
             yw = self._buffer() if torch.cuda.is_available() else self._yw      # (without a device: the host array, for whoever only reads the description)
             if isinstance(self.Op, PSF):
@@ -349,6 +385,13 @@ class L2(ProxOperator):
         With a blur operator: ``niter`` warm-started CG iterations on the GPU (lmc_l2_prox)."""
         if self.bounds is not None:
             return _box_prox(self, x, tau)
+        if self._spectral is not None:      # closed form between the two column transforms (lmc_l2_prox ignores niter, warm and the workspace)
+            prob = self._problem()
+            xt = _dev.to_dev(x, prob.device)
+            out = torch.empty_like(xt)
+            with torch.cuda.device(prob.device):
+                _dev.run(xt, "lmc_l2_prox", C.byref(prob.c), _dev.ptr(xt), _dev.ptr(out), xt.numel() // (self.dims[0] * self.dims[1]), float(tau), 0, 0, None)
+            return _dev.like_input(out, x)
         if isinstance(self.Op, PSF):
             raise NotImplementedError("L2.prox with a large PSF: the implicit step (I + tau sigma Op^T Op)^{-1} is not built for it (lmc_l2_prox refuses it)")
         if self.weights is not None:
