@@ -3,7 +3,6 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <cstring>
 #include <string>
 
 #include "lmc_host.h"
@@ -14,61 +13,7 @@ namespace {
 thread_local std::string g_err;
 
 constexpr int kMaxDevices = 64;
-Scratch g_scratch_dev[kMaxDevices];
-
-// The ME-TV term of a stateless call on n_img images, in the scratch sc (extra, the dual state where the inner prox needs it, the device-side
-// early exit): sc.extra <- the inner prox at x; with f_out also f_out -= the envelope (me_tv_energy; the caller sizes sc.dbl for it).
-int scratch_me_tv(Scratch& sc, const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st) {
-  const size_t npx = (size_t)n_img * q.H * q.W;
-  HIP_TRY(sc.need_extra(npx));
-  if (needs_tv_state(q)) HIP_TRY(sc.need_state(4 * npx));
-  if (q.ncvx_rtol > 0.f) HIP_TRY(sc.rt_me.need((size_t)n_img, q.ncvx_niter));
-  if (f_out) return me_tv_energy(q, x, n_img, f_out, sc.extra, sc.state[0], sc.state[1], sc.dbl, st, &sc.rt_me);
-  return me_tv_prox(q, x, sc.extra, n_img, sc.state[0], sc.state[1], st, &sc.rt_me);
-}
-
-// The large PSF of a stateless call: q.psf gets the device table and the residual buffer of the scratch sc.  The table is uploaded in stream order from
-// a pinned copy, and only when it differs from the one the scratch holds.
-int scratch_psf(Scratch& sc, lmc::PsfOp& P, size_t n_resid, hipStream_t st) {
-  if (!P.on) return LMC_OK;
-  if (!sc.psf_tab) {
-    HIP_TRY(hipMalloc(&sc.psf_tab, sizeof P.tab));
-    HIP_TRY(hipHostMalloc(&sc.psf_host, sizeof P.tab));
-    HIP_TRY(hipEventCreateWithFlags(&sc.psf_ev, hipEventDisableTiming));
-    sc.psf_valid = false;
-  }
-  if (!sc.psf_valid || std::memcmp(sc.psf_host, P.tab, sizeof P.tab) != 0) {
-    if (sc.psf_valid) HIP_TRY(hipEventSynchronize(sc.psf_ev));      // the previous upload has read the pinned copy
-    sc.psf_valid = false;
-    std::memcpy(sc.psf_host, P.tab, sizeof P.tab);
-    HIP_TRY(hipMemcpyAsync(sc.psf_tab, sc.psf_host, sizeof P.tab, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(sc.psf_ev, st));
-    sc.psf_valid = true;
-  }
-  if (n_resid) HIP_TRY(sc.need_resid(n_resid));
-  P.tab_dev = sc.psf_tab;
-  P.resid = sc.resid;
-  return LMC_OK;
-}
-
-// The spectral data term of a stateless call: F gets the twiddle table (uploaded once per device, synchronously: it never changes) and the spectrum
-// buffer / value partials of the scratch sc.
-int scratch_fft(Scratch& sc, lmc::FftOp& F, size_t n_spec, size_t n_part) {
-  if (!sc.fft_tw) {
-    float tw[2 * lmc::kFftTw];
-    lmc::fft_twiddles(tw);
-    float* d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof tw));
-    hipError_t e = hipMemcpy(d, tw, sizeof tw, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); HIP_TRY(e); }
-    sc.fft_tw = d;
-  }
-  HIP_TRY(sc.need_fft(n_spec, n_part));
-  F.tw = reinterpret_cast<const float2*>(sc.fft_tw);
-  F.spec = reinterpret_cast<float2*>(sc.fft_spec);
-  F.part = sc.fft_part;
-  return LMC_OK;
-}
+Workspace g_scratch_dev[kMaxDevices];     // grown on demand and never freed
 
 // the argument checks the stateless transform calls share
 int check_fft_call(const void* x_dev, const void* out_dev, int64_t n_img, int32_t H, int32_t W) {
@@ -90,7 +35,7 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-Scratch& scratch_here() {
+Workspace& scratch_here() {
   int dev = 0;
   (void)hipGetDevice(&dev);
   return g_scratch_dev[(dev >= 0 && dev < kMaxDevices) ? dev : 0];
@@ -179,8 +124,7 @@ int lmc_psf_apply(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, 
   lmc::PsfOp P;
   if (!lmc::psf_prepare(P, h_host, kh, kw, oy, ox, separable))
     return fail(LMC_E_INVALID, "separable = 1 on a kernel that is no outer product to 2^-22 of every tap (lmc_psf_separable)");
-  int rc = scratch_psf(scratch_here(), P, 0, S(stream));
-  if (rc) return rc;
+  HIP_TRY(scratch_here().bind_psf(P, 0, S(stream)));
   HIP_TRY(lmc::launch_psf(P, adjoint != 0, lmc::kPsfRaw, x_dev, out_dev, nullptr, nullptr, n_img, H, W, 0.f, 0.f, S(stream)));
   return LMC_OK;
 }
@@ -189,8 +133,7 @@ int lmc_rfft2(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int3
   int rc = check_fft_call(x_dev, out_dev, n_img, H, W);
   if (rc) return rc;
   lmc::FftOp F;
-  rc = scratch_fft(scratch_here(), F, 0, 0);
-  if (rc) return rc;
+  HIP_TRY(scratch_here().bind_fft(F, 0, 0));
   float2* spec = reinterpret_cast<float2*>(out_dev);
   HIP_TRY(lmc::launch_fft_rows_fwd(x_dev, spec, F.tw, n_img, H, W, S(stream)));
   HIP_TRY(lmc::launch_fft_cols(lmc::kFftColFwd, spec, nullptr, F.tw, n_img, H, W, 0.f, S(stream)));
@@ -202,8 +145,7 @@ int lmc_irfft2(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int
   if (rc) return rc;
   lmc::FftOp F;
   const size_t nf = lmc::fft_spec_floats(n_img, H, W);
-  rc = scratch_fft(scratch_here(), F, nf, 0);
-  if (rc) return rc;
+  HIP_TRY(scratch_here().bind_fft(F, nf, 0));
   HIP_TRY(hipMemcpyAsync(F.spec, x_dev, sizeof(float) * nf, hipMemcpyDeviceToDevice, S(stream)));      // the column pass runs in place: on a copy
   HIP_TRY(lmc::launch_fft_cols(lmc::kFftColInv, F.spec, nullptr, F.tw, n_img, H, W, 0.f, S(stream)));
   HIP_TRY(lmc::launch_fft_rows_inv(lmc::kFftStore, F.spec, out_dev, nullptr, F.tw, n_img, H, W, 0.f, 0.f, S(stream)));
@@ -215,8 +157,7 @@ int lmc_spectral_filter(const float* x_dev, float* out_dev, int64_t n_img, int32
   if (rc) return rc;
   if (!m_dev) return fail(LMC_E_INVALID, "the multiplier m_dev is NULL");
   lmc::FftOp F;
-  rc = scratch_fft(scratch_here(), F, lmc::fft_spec_floats(n_img, H, W), 0);
-  if (rc) return rc;
+  HIP_TRY(scratch_here().bind_fft(F, lmc::fft_spec_floats(n_img, H, W), 0));
   HIP_TRY(lmc::launch_fft_rows_fwd(x_dev, F.spec, F.tw, n_img, H, W, S(stream)));
   HIP_TRY(lmc::launch_fft_cols(lmc::kFftMul, F.spec, m_dev, F.tw, n_img, H, W, 0.f, S(stream)));
   HIP_TRY(lmc::launch_fft_rows_inv(lmc::kFftStore, F.spec, out_dev, nullptr, F.tw, n_img, H, W, 0.f, 0.f, S(stream)));
@@ -253,11 +194,7 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
   if (!x_dev || !out_dev || x_dev == out_dev) return fail(LMC_E_INVALID, "bad pointers (in-place not allowed)");
   if (n_img < 1 || n_img > (1 << 24)) return fail(LMC_E_INVALID, "bad n_img %lld", (long long)n_img);
   if (q.prox_scale) return fail(LMC_E_UNSUPPORTED, "prox_scale (array-valued epsg) belongs to the MYULA sampler");
-  rc = check_prox_prior(q, b);
-  if (!rc) rc = check_poisson(q);
-  if (!rc) rc = check_wl2(q);
-  if (!rc) rc = check_psf(q);
-  if (!rc) rc = check_spectral(q);
+  rc = check_step_problem(q, b);
   if (rc) return rc;
   lmc::StepArgs A;
   rc = make_step_args(q, a, t, b, pt, 0.f, A);
@@ -266,41 +203,26 @@ int lmc_fused_eval(const lmc_problem* prob, const float* x_dev, float* out_dev, 
   A.x_in = x_dev;
   A.x_out = out_dev;
   sanitize_pointers(A);
-  const size_t npx = (size_t)n_img * q.H * q.W;
-  Scratch& sc = scratch_here();
-  if (needs_tv_state(q)) HIP_TRY(sc.need_state(4 * npx));
-  if (t != 0.f) { rc = scratch_psf(sc, q.psf, npx, S(stream)); if (rc) return rc; }
-  if (t != 0.f && q.fft.on) { rc = scratch_fft(sc, q.fft, lmc::fft_spec_floats(n_img, q.H, q.W), 0); if (rc) return rc; }
+  Workspace& sc = scratch_here();
+  HIP_TRY(prepare(sc, q, A, n_img, pt, kForStep, S(stream)));
   if (t != 0.f && q.ncvx_kind == LMC_NCVX_ME_TV) {
-    rc = scratch_me_tv(sc, q, x_dev, n_img, nullptr, S(stream));
+    rc = me_tv_prox(q, x_dev, n_img, sc, S(stream));
     if (rc) return rc;
-    A.extra = sc.extra;
+    A.extra = sc.extra.p;
     A.extra_coef = -q.ncvx_lambda / q.ncvx_gamma;
   }
-  if (A.prior_kind == LMC_PRIOR_HAAR_L1 || A.prior_kind == LMC_PRIOR_WAVELET_L1 || A.prior_kind == LMC_PRIOR_EPROX || (A.box && A.prior_kind != LMC_PRIOR_TV_ISO))
-    HIP_TRY(sc.need_prox(npx));
-  if (A.prior_kind == LMC_PRIOR_WAVELET_L1) {
-    HIP_TRY(sc.need_wav(lmc::wavelet_ws_floats(n_img, q.H, q.W), 0));
-    q.wav.ws = sc.wav;
-  }
-  if (A.prior_kind == LMC_PRIOR_TV_ISO && q.tv_rtol > 0.f && tv_prior_rt_mode(q, A, pt) != 2) {     // the early exit decided on the device
-    HIP_TRY(sc.need_prox(npx));
-    HIP_TRY(sc.rt_tv.need((size_t)n_img, q.tv_niter));
-    if (needs_tv_state(q)) HIP_TRY(sc.need_state(4 * npx));
-    rc = tv_prior_rt(q, pt, A, sc.rt_tv, sc.prox, sc.state[0], sc.state[1], S(stream));
+  if (sc.tv_exit == 0 || sc.tv_exit == 1) {     // the early exit decided on the device
+    rc = tv_prior_rt(q, pt, A, sc, S(stream));
     if (rc < 0) return rc;
     if (rc == 1) return LMC_OK;
     if (rc == 2) return fail(LMC_E_UNSUPPORTED, "early exit of the TV prox: no path covers this configuration");
-  } else if (A.prior_kind == LMC_PRIOR_TV_ISO && q.tv_rtol > 0.f) {     // the early-exit prox first, then the fused update with it as a ready-made prox
-    HIP_TRY(sc.need_prox(npx));
-    HIP_TRY(sc.need_rtmp(npx));
-    HIP_TRY(sc.need_dbl(3 * (size_t)n_img + 2));
-    rc = tv_prox_rtol(q, pt, x_dev, sc.prox, sc.rtmp, sc.dbl, reinterpret_cast<int*>(sc.dbl + 2 * n_img), n_img, sc.state[0], sc.state[1], S(stream));
+  } else if (sc.tv_exit == 2) {     // the early-exit prox first, then the fused update with it as a ready-made prox
+    rc = tv_prox_rtol(q, pt, x_dev, sc.prox.p, n_img, sc, S(stream));
     if (rc) return rc;
     A.prior_kind = LMC_PRIOR_NONE;
-    A.prox_ext = sc.prox;
+    A.prox_ext = sc.prox.p;
   }
-  hipError_t e = launch_step(A, variant_of(q), S(stream), nullptr, sc.state[0], sc.state[1], sc.prox, q.psf.on ? &q.psf : nullptr, &q.wav, q.fft.on ? &q.fft : nullptr);
+  hipError_t e = launch_step(A, q, sc, S(stream), nullptr);
   if (e == hipErrorInvalidConfiguration)
     return fail(LMC_E_UNSUPPORTED, A.box ? "step_variant %d has no box-constrained form of this prior (TV: auto, 1 tile, 7 / 8 pipe where the pipe covers the problem)"
                                          : "no step-kernel variant covers this configuration", variant_of(q));
@@ -314,36 +236,11 @@ int lmc_energies(const lmc_problem* prob, const float* x_dev, int64_t n_img, dou
   int rc = load_problem(prob, q);
   if (rc) return rc;
   if (!x_dev || n_img < 1) return fail(LMC_E_INVALID, "bad arguments");
-  if (q.pois && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the Poisson data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
-  if (q.wl2 && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
-  if (q.psf.on && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "a large PSF has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
-  if (q.fft.on && q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the spectral data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
-  if (f_out_dev) { rc = scratch_psf(scratch_here(), q.psf, 0, S(stream)); if (rc) return rc; }
-  if (f_out_dev && q.fft.on) {
-    rc = scratch_fft(scratch_here(), q.fft, lmc::fft_spec_floats(n_img, q.H, q.W), lmc::fft_value_partials(n_img, q.H, q.W));
-    if (rc) return rc;
-  }
-  HIP_TRY(lmc::launch_energies(x_dev, n_img, energy_args(q), f_out_dev, g_out_dev, S(stream)));
-  rc = pois_energy(q, x_dev, n_img, f_out_dev, S(stream));
-  if (!rc) rc = wl2_energy(q, x_dev, n_img, f_out_dev, S(stream));
-  if (!rc) rc = psf_energy(q, x_dev, n_img, f_out_dev, S(stream));
-  if (!rc) rc = spectral_energy(q, x_dev, n_img, f_out_dev, S(stream));
+  rc = check_convex_terms(q);
   if (rc) return rc;
-  if (q.prior_kind == LMC_PRIOR_HAAR_L1 && g_out_dev) HIP_TRY(lmc::launch_haar_value(x_dev, n_img, q.H, q.W, q.prior_sigma, g_out_dev, S(stream)));
-  if (q.wav.on && g_out_dev) {
-    Scratch& sc = scratch_here();
-    HIP_TRY(sc.need_wav(lmc::wavelet_ws_floats(n_img, q.H, q.W), (size_t)n_img * lmc::wavelet_partials(q.H, q.W, q.wav.levels)));
-    q.wav.ws = sc.wav; q.wav.part = sc.wav_part;
-    rc = wavelet_energy(q, x_dev, n_img, g_out_dev, S(stream));
-    if (rc) return rc;
-  }
-  if (q.ncvx_kind == LMC_NCVX_ME_TV && f_out_dev) {
-    Scratch& sc = scratch_here();
-    HIP_TRY(sc.need_dbl(3 * (size_t)n_img + 2));     // (the pass-by-pass fallback of the inner prox shares the buffer: sized for it up front)
-    rc = scratch_me_tv(sc, q, x_dev, n_img, f_out_dev, S(stream));
-    if (rc) return rc;
-  }
-  return LMC_OK;
+  Workspace& sc = scratch_here();
+  HIP_TRY(prepare(sc, q, lmc::StepArgs{}, n_img, 0.f, (f_out_dev ? kForEnergyF : 0) | (g_out_dev ? kForEnergyG : 0), S(stream)));
+  return problem_energies(q, x_dev, n_img, f_out_dev, g_out_dev, sc, S(stream));
 }
 
 size_t lmc_l2_prox_workspace_bytes(int64_t n_img, int32_t H, int32_t W) {
@@ -365,30 +262,34 @@ int lmc_l2_prox(const lmc_problem* prob, const float* x_dev, float* out_dev, int
   hipStream_t st = S(stream);
   const float ts = tau * q.sigma_f;
   const size_t n = (size_t)n_img * q.H * q.W;
-  Scratch& sc = scratch_here();
+  Workspace& sc = scratch_here();
   if (q.fft.on) {      // the spectral data term: the implicit step in closed form, (vh + ts B) / (1 + ts A) between the two column transforms
     if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the spectral data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
-    rc = scratch_fft(sc, q.fft, lmc::fft_spec_floats(n_img, q.H, q.W), 0);
-    if (rc) return rc;
+    HIP_TRY(sc.bind_fft(q.fft, lmc::fft_spec_floats(n_img, q.H, q.W), 0));
     HIP_TRY(lmc::launch_fft_rows_fwd(x_dev, q.fft.spec, q.fft.tw, n_img, q.H, q.W, st));
     HIP_TRY(lmc::launch_fft_cols(lmc::kFftProx, q.fft.spec, q.fft.tab, q.fft.tw, n_img, q.H, q.W, ts, st));
     HIP_TRY(lmc::launch_fft_rows_inv(lmc::kFftStore, q.fft.spec, out_dev, nullptr, q.fft.tw, n_img, q.H, q.W, 0.f, 0.f, st));
     return LMC_OK;
+  }
+  if (q.ncvx_kind == LMC_NCVX_ME_TV && q.data_kind != LMC_DATA_NONE) {     // the inner prox of the ME-TV term: the buffers of a step that carries the term
+    lmc::StepArgs probe{};
+    probe.t = tau;
+    HIP_TRY(prepare(sc, q, probe, n_img, 0.f, kForStep, st));
   }
   if (q.data_kind != LMC_DATA_BLUR) {
     const float* xin = x_dev;
     if (q.ncvx_kind != LMC_NCVX_NONE && q.data_kind != LMC_DATA_NONE) {
       // L2_ncvx_tv.prox with a pointwise data term: the pre-step of algs.py:213-223 first (x + tau lambda A^T(Ax / max(|Ax|, gamma)), or
       // x + tau lambda / gamma (x - prox_{gamma TV}(x))), then the closed-form solve.  (Round 3's matrix test found this path applying the solve to x itself.)
-      HIP_TRY(sc.need_prox(n));
+      HIP_TRY(sc.prox.need(n));
       if (q.ncvx_kind == LMC_NCVX_MC_TV) {
-        HIP_TRY(lmc::ulpda_ncvx_rhs(x_dev, q.y, sc.prox, n_img, q.H, q.W, tau * q.ncvx_lambda, q.ncvx_gamma, 0.f, st));     // ts = 0: the H^T b slot adds nothing
+        HIP_TRY(lmc::ulpda_ncvx_rhs(x_dev, q.y, sc.prox.p, n_img, q.H, q.W, tau * q.ncvx_lambda, q.ncvx_gamma, 0.f, st));     // ts = 0: the H^T b slot adds nothing
       } else {
-        rc = scratch_me_tv(sc, q, x_dev, n_img, nullptr, st);
+        rc = me_tv_prox(q, x_dev, n_img, sc, st);
         if (rc) return rc;
-        HIP_TRY(lmc::ulpda_me_rhs(x_dev, sc.extra, q.y, sc.prox, n_img, q.H, q.W, tau * q.ncvx_lambda / q.ncvx_gamma, 0.f, st));
+        HIP_TRY(lmc::ulpda_me_rhs(x_dev, sc.extra.p, q.y, sc.prox.p, n_img, q.H, q.W, tau * q.ncvx_lambda / q.ncvx_gamma, 0.f, st));
       }
-      xin = sc.prox;
+      xin = sc.prox.p;
     }
     HIP_TRY(lmc::ulpda_pointwise_prox(xin, out_dev, q.y, q.mask, n_img, q.H, q.W, ts, q.data_kind, st));
     return LMC_OK;
@@ -405,9 +306,9 @@ int lmc_l2_prox(const lmc_problem* prob, const float* x_dev, float* out_dev, int
   if (q.ncvx_kind == LMC_NCVX_MC_TV) {
     HIP_TRY(lmc::ulpda_ncvx_rhs(x_dev, tmp, rhs, n_img, q.H, q.W, tau * q.ncvx_lambda, q.ncvx_gamma, ts, st));
   } else if (q.ncvx_kind == LMC_NCVX_ME_TV) {
-    rc = scratch_me_tv(sc, q, x_dev, n_img, nullptr, st);
+    rc = me_tv_prox(q, x_dev, n_img, sc, st);
     if (rc) return rc;
-    HIP_TRY(lmc::ulpda_me_rhs(x_dev, sc.extra, tmp, rhs, n_img, q.H, q.W, tau * q.ncvx_lambda / q.ncvx_gamma, ts, st));
+    HIP_TRY(lmc::ulpda_me_rhs(x_dev, sc.extra.p, tmp, rhs, n_img, q.H, q.W, tau * q.ncvx_lambda / q.ncvx_gamma, ts, st));
   } else {
     HIP_TRY(hipMemsetAsync(r, 0, sizeof(float) * 2 * n, st));
     HIP_TRY(lmc::ulpda_rhs(x_dev, r, nullptr, tmp, rhs, n_img, q.H, q.W, 0.f, ts, st));
@@ -448,9 +349,9 @@ static int check_wavelet_call(const float* x_dev, const float* out_dev, int64_t 
 int lmc_wavelet_apply(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t p, int32_t levels, int32_t inverse, void* stream) {
   int rc = check_wavelet_call(x_dev, out_dev, n_img, H, W, p, levels);
   if (rc) return rc;
-  Scratch& sc = scratch_here();
-  HIP_TRY(sc.need_wav(lmc::wavelet_ws_floats(n_img, H, W), 0));
-  HIP_TRY(lmc::launch_wavelet_apply(x_dev, out_dev, n_img, H, W, p, levels, inverse != 0, sc.wav, S(stream)));
+  Workspace& sc = scratch_here();
+  HIP_TRY(sc.wav.need(lmc::wavelet_ws_floats(n_img, H, W)));
+  HIP_TRY(lmc::launch_wavelet_apply(x_dev, out_dev, n_img, H, W, p, levels, inverse != 0, sc.wav.p, S(stream)));
   return LMC_OK;
 }
 
@@ -458,9 +359,9 @@ int lmc_wavelet_l1_prox(const float* x_dev, float* out_dev, int64_t n_img, int32
   int rc = check_wavelet_call(x_dev, out_dev, n_img, H, W, p, levels);
   if (rc) return rc;
   if (!(thr >= 0.f)) return fail(LMC_E_INVALID, "threshold must be >= 0");
-  Scratch& sc = scratch_here();
-  HIP_TRY(sc.need_wav(lmc::wavelet_ws_floats(n_img, H, W), 0));
-  HIP_TRY(lmc::launch_wavelet_prox(x_dev, out_dev, n_img, H, W, p, levels, thr, sc.wav, S(stream)));
+  Workspace& sc = scratch_here();
+  HIP_TRY(sc.wav.need(lmc::wavelet_ws_floats(n_img, H, W)));
+  HIP_TRY(lmc::launch_wavelet_prox(x_dev, out_dev, n_img, H, W, p, levels, thr, sc.wav.p, S(stream)));
   return LMC_OK;
 }
 

@@ -1,14 +1,19 @@
 // Internals of the C-ABI host code, shared by its translation units (not installed):
-//   lmc_capi.hip        the stateless extern "C" entry points, the last error, the stateless scratch
-//   lmc_problem.hip     lmc_problem -> Problem, StepArgs of an update, the step-kernel dispatch, the library defaults
+//   lmc_capi.hip        the stateless extern "C" entry points, the last error, the per-device workspaces of the stateless calls
+//   lmc_problem.hip     lmc_problem -> Problem and its checks, StepArgs of an update, prepare() (which work buffers a problem needs, and the binding
+//                       of its operators to them), the step-kernel dispatch, the library defaults
 //   lmc_solve.hip       the implicit step (I + ts H^T H) u = rhs: Chebyshev, CG
-//   lmc_tv_exit.hip     the early exits of the TV prox, the ME-TV inner prox and envelope
+//   lmc_tv_exit.hip     the early exits of the TV prox, the ME-TV inner prox and envelope, the energies of a problem
 //   lmc_sampler.hip     the MYULA, MYMALA, SK-ROCK and ULPDA samplers: create / destroy, state, the step loops
+//   lmc_sapg.hip        the SAPG estimation of the prior weight: its kernels, its stateless calls and lmc_sampler_sapg
 //   lmc_accum.hip       the accumulators over the kept samples (lmc_accum.h): their reductions and their set / get / reset entry points
 //   lmc_rccl.hip        the dlopen'd RCCL and the all-reduces of the accumulators
+// Ownership: this header has the three owners of device memory -- Workspace (problem-dependent work buffers, sized and bound by prepare()), Owned (the
+// per-sampler arrays of a handle) and Accumulators (lmc_accum.h).
 #pragma once
 #include <cmath>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "lmc_accum.h"
@@ -118,67 +123,117 @@ struct RtState {
   }
 };
 
-// Device scratch for the stateless entry points (grown on demand and never freed: it lives for the life of the process; calls are
-// serialised by the caller, see lmc_atomi.h).  Samplers own their buffers instead.
-struct Scratch {
-  float* state[2] = {nullptr, nullptr};   // TV dual state ping-pong, [n][4][H][W] each
-  float* extra = nullptr;                 // ME-TV inner prox, [n][H][W]
-  float* prox = nullptr;                  // Haar-l1 prox / early-exit TV prox, [n][H][W]
-  float* rtmp = nullptr;                  // early-exit TV prox: the iterate of the current pass, [n][H][W]
-  double* dbl = nullptr;                  // 2*n doubles
-  float* resid = nullptr;                 // large PSF: the residual rho(H x) of a step, [n][H][W]
-  float* wav = nullptr;                   // wavelet prior: the thresholded pyramid and the LL ping-pong
-  double* wav_part = nullptr;             // wavelet prior: the partial sums of its value
-  // large PSF: the device tap table of the stateless calls, the pinned host copy it was uploaded from (compared with the next call's table: equal
-  // taps are not uploaded again) and the event behind the last upload (the host copy is not rewritten before that upload has run)
+// A device array that grows on demand: it holds at least n elements after need(n); what it held is not kept when it grows.
+template <class T>
+struct Buf {
+  T* p = nullptr;
+  size_t n = 0;
+  hipError_t need(size_t want) {
+    if (want <= n) return hipSuccess;
+    release();
+    const hipError_t e = hipMalloc(&p, sizeof(T) * want);
+    if (e == hipSuccess) n = want;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr; n = 0;
+  }
+};
+
+// The one owner of the work buffers a problem needs beyond its state arrays.  There is one per device for the stateless entry points (scratch_here: it
+// lives for the life of the process; those calls are serialised by the caller, see lmc_atomi.h) and one inside every sampler handle, which never touches
+// the other.  prepare() is the one place that decides which buffers a problem needs, grows them and points the problem's operators at them.
+struct Workspace {
+  Buf<float> state[2];                    // TV dual state ping-pong, [n][4][H][W] each
+  Buf<float> extra;                       // ME-TV inner prox, [n][H][W]
+  Buf<float> prox;                        // a prox formed ahead of the step (Haar-l1, wavelet, closed forms, box, early-exit TV prox), [n][H][W]
+  Buf<float> rtmp;                        // pass-by-pass early exit: the iterate of the current pass, [n][H][W]
+  // small float64 scratch.  The pass-by-pass early exits lay it out as 2n objectives then n + 1 ints (exit_obj / exit_flag); the ME-TV envelope takes
+  // the first 2n doubles, the PSF energy its partial sums, lmc_prior_statistic its segments
+  Buf<double> dbl;
+  Buf<float> resid;                       // large PSF: the residual rho(H x) of a step, [n][H][W]
+  Buf<float> wav;                         // wavelet prior: the thresholded pyramid and the LL ping-pong (1.25 states)
+  Buf<double> wav_part;                   // wavelet prior: the partial sums of its value
+  // large PSF: the device tap table, the pinned host copy it was uploaded from (compared with the next table: equal taps are not uploaded again)
+  // and the event behind the last upload (the host copy is not rewritten before that upload has run)
   float* psf_tab = nullptr;
   float* psf_host = nullptr;
   hipEvent_t psf_ev = nullptr;
   bool psf_valid = false;
   // spectral data term: the twiddle table (uploaded once), the spectrum buffer [n][H][Wh] complex, the partial sums of the value
   float* fft_tw = nullptr;
-  float* fft_spec = nullptr;
-  double* fft_part = nullptr;
-  size_t n_fft_spec = 0, n_fft_part = 0;
-  size_t n_resid = 0, n_wav = 0, n_wav_part = 0;
+  Buf<float> fft_spec;
+  Buf<double> fft_part;
   RtState rt_tv, rt_me;                   // device-side early exit of the TV prior's prox / of the ME-TV inner prox
-  size_t n_state[2] = {0, 0}, n_extra = 0, n_prox = 0, n_rtmp = 0, n_dbl = 0;   // elements allocated
-  // p holds at least n elements afterwards; what it held is not kept when it grows
-  template <class T>
-  static hipError_t grow(T*& p, size_t& have, size_t n) {
-    if (n <= have) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr; have = 0;
-    hipError_t e = hipMalloc(&p, sizeof(T) * n);
-    if (e == hipSuccess) have = n;
-    return e;
-  }
-  hipError_t need_state(size_t n) {
-    hipError_t e = grow(state[0], n_state[0], n);
-    return e == hipSuccess ? grow(state[1], n_state[1], n) : e;
-  }
-  hipError_t need_extra(size_t n) { return grow(extra, n_extra, n); }
-  hipError_t need_prox(size_t n) { return grow(prox, n_prox, n); }
-  hipError_t need_rtmp(size_t n) { return grow(rtmp, n_rtmp, n); }
-  hipError_t need_dbl(size_t n) { return grow(dbl, n_dbl, n); }
-  hipError_t need_resid(size_t n) { return grow(resid, n_resid, n); }
-  hipError_t need_fft(size_t n_spec, size_t n_part) {
-    hipError_t e = grow(fft_spec, n_fft_spec, n_spec);
-    return e == hipSuccess && n_part ? grow(fft_part, n_fft_part, n_part) : e;
-  }
-  hipError_t need_wav(size_t n, size_t n_part) {
-    hipError_t e = grow(wav, n_wav, n);
-    return e == hipSuccess && n_part ? grow(wav_part, n_wav_part, n_part) : e;
-  }
-  // frees the wavelet workspace (the largest buffer a stateless call takes: 1.25 states); the next call that needs it allocates again
+  int tv_exit = -1;                       // the TV prior's early exit as the last prepare() found it: -1 none, else tv_prior_rt_mode (1 fused, 0 prox alone, 2 pass by pass)
+
+  static size_t exit_doubles(size_t n) { return 3 * n + 2; }
+  double* exit_obj() const { return dbl.p; }
+  int* exit_flag(int64_t n) const { return reinterpret_cast<int*>(dbl.p + 2 * n); }
+  // P gets the device table and, with n_resid > 0, the residual buffer.  The table is uploaded in stream order from the pinned copy, and only when it
+  // differs from the one held.
+  hipError_t bind_psf(lmc::PsfOp& P, size_t n_resid, hipStream_t st);
+  // F gets the twiddle table (uploaded once, synchronously: it never changes), the spectrum buffer and the value partials
+  hipError_t bind_fft(lmc::FftOp& F, size_t n_spec, size_t n_part);
+  // frees the wavelet buffers (the largest a stateless call takes: 1.25 states); the next call that needs them allocates again
+  void release_wavelet() { wav.release(); wav_part.release(); }
   void release() {
-    if (wav) (void)hipFree(wav);
-    if (wav_part) (void)hipFree(wav_part);
-    wav = nullptr; wav_part = nullptr; n_wav = 0; n_wav_part = 0;
+    for (Buf<float>* b : {&state[0], &state[1], &extra, &prox, &rtmp, &resid, &wav, &fft_spec}) b->release();
+    for (Buf<double>* b : {&dbl, &wav_part, &fft_part}) b->release();
+    if (psf_tab) (void)hipFree(psf_tab);
+    if (psf_host) (void)hipHostFree(psf_host);
+    if (psf_ev) (void)hipEventDestroy(psf_ev);
+    if (fft_tw) (void)hipFree(fft_tw);
+    psf_tab = psf_host = fft_tw = nullptr; psf_ev = nullptr; psf_valid = false;
+    rt_tv.release();
+    rt_me.release();
+    tv_exit = -1;
   }
 };
-// The scratch of the current device: a process may drive several GPUs (one sampler handle each); the stateless entry points run on the current device.
-Scratch& scratch_here();
+// The workspace of the current device: a process may drive several GPUs (one sampler handle each); the stateless entry points run on the current device.
+// Only the stateless extern "C" entry points call it.
+Workspace& scratch_here();
+
+// What a sampler handle owns beyond its workspace and accumulators: the per-sampler device arrays, pinned host memory and events.  The handle's fields
+// point at them and may rotate; the list frees the original allocations.
+struct Owned {
+  enum Kind { kDevice, kPinned, kEvent };
+  std::vector<std::pair<Kind, void*>> items;
+  template <class T>
+  hipError_t alloc(T** p, size_t count, bool zero) {
+    *p = nullptr;
+    hipError_t e = hipMalloc(p, sizeof(T) * count);
+    if (e != hipSuccess) return e;
+    items.emplace_back(kDevice, *p);
+    return zero ? hipMemset(*p, 0, sizeof(T) * count) : hipSuccess;
+  }
+  template <class T>
+  hipError_t pinned(T** p, size_t count, unsigned flags) {
+    *p = nullptr;
+    const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(p), sizeof(T) * count, flags);
+    if (e == hipSuccess) items.emplace_back(kPinned, *p);
+    return e;
+  }
+  hipError_t event(hipEvent_t* ev, unsigned flags) {
+    const hipError_t e = hipEventCreateWithFlags(ev, flags);
+    if (e == hipSuccess) items.emplace_back(kEvent, *ev);
+    return e;
+  }
+  static void free_item(const std::pair<Kind, void*>& it) {
+    if (it.first == kDevice) (void)hipFree(it.second);
+    else if (it.first == kPinned) (void)hipHostFree(it.second);
+    else (void)hipEventDestroy(static_cast<hipEvent_t>(it.second));
+  }
+  void drop(void* p) {      // one of them early: an array that a larger one replaces
+    for (size_t i = 0; i < items.size(); ++i)
+      if (items[i].second == p) { free_item(items[i]); items.erase(items.begin() + i); return; }
+  }
+  void release() {
+    for (const auto& it : items) free_item(it);
+    items.clear();
+  }
+};
 
 // Makes `dev` the current device for the duration of a call on a handle that lives there, and restores the caller's device.
 struct DeviceGuard {
@@ -199,28 +254,34 @@ constexpr int kSideBatches = 4;
 int fill_taps(lmc::BlurTaps& T, const float* h, int kh, int kw, int oy, int ox);
 void default_betas(float* b, int n);
 int load_problem(const lmc_problem* p, Problem& q);
-int check_prox_prior(const Problem& q, float b);
 int check_no_box(const Problem& q, const char* who, const char* why);
 int check_no_poisson(const Problem& q, const char* who, const char* why);
-int check_poisson(const Problem& q);
 int check_no_wl2(const Problem& q, const char* who, const char* why);
-int check_wl2(const Problem& q);
 int check_no_psf(const Problem& q, const char* who, const char* why);
-int check_psf(const Problem& q);
 int check_no_spectral(const Problem& q, const char* who, const char* why);
-int check_spectral(const Problem& q);
+// what the entry points that form the update a x - t grad f + b prox_g (MYULA, MYMALA, SK-ROCK, lmc_fused_eval) refuse: of the anisotropic TV prior
+// and of each data term with kernels of its own
+int check_step_problem(const Problem& q, float b);
+// the first refusal of each of those data terms alone (a non-convex term), for the callers that form no update (lmc_energies)
+int check_convex_terms(const Problem& q);
 bool wl2_pipe_covers(const lmc::StepArgs& A);       // the full-width pipeline has a weighted form of this launch
 bool pois_pipe_covers(const lmc::StepArgs& A);      // the full-width pipeline has a Poisson form of this launch
 int make_step_args(const Problem& q, float a, float t, float b, float pt, float s, lmc::StepArgs& A);
 void sanitize_pointers(lmc::StepArgs& A);
 int variant_of(const Problem& q);
 float tol_of(const Problem& q);
-// psf: the operator of a launch whose data_kind is LMC_DATA_PSF (with its device table and residual buffer); such a launch without it is not covered
-// fft: the same for LMC_DATA_SPECTRAL (with its twiddle table and spectrum buffer)
-// wav: the transform of a launch whose prior_kind is LMC_PRIOR_WAVELET_L1 (with its workspace); such a launch without it, or without pxbuf, is not covered
-hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0 = nullptr,
-                       float* state1 = nullptr, float* pxbuf = nullptr, const lmc::PsfOp* psf = nullptr, const lmc::WaveletOp* wav = nullptr,
-                       const lmc::FftOp* fft = nullptr);
+// Grows ws to what the problem q needs on n_img images and points q.psf, q.fft and q.wav at it (nothing else does: a grown buffer never leaves a
+// stale pointer behind).  what: kForStep -- the update `probe` describes (its data term, prior, box and t; pt: its prox parameter) with the proxes that
+// run ahead of it; kForEnergyF / kForEnergyG -- f / g of problem_energies.  The stateless calls prepare at every call (no-op once large enough), a
+// handle at its creation and never inside lmc_sampler_step.  st: the stream of a PSF table upload.
+enum { kForStep = 1, kForEnergyF = 2, kForEnergyG = 4, kForEnergies = kForEnergyF | kForEnergyG };
+hipError_t prepare(Workspace& ws, Problem& q, const lmc::StepArgs& probe, int64_t n_img, float pt, int what, hipStream_t st);
+// The update A of problem q on the step kernel of `variant`: the dual state and the prox buffer come from ws, the PSF / spectral / wavelet operators
+// from q (bound to ws by prepare; a launch that needs one that is not bound is not covered).
+hipError_t launch_step(const lmc::StepArgs& A, int variant, const Problem& q, Workspace& ws, hipStream_t st, const char** name);
+inline hipError_t launch_step(const lmc::StepArgs& A, const Problem& q, Workspace& ws, hipStream_t st, const char** name) {
+  return launch_step(A, variant_of(q), q, ws, st, name);
+}
 
 // ---- lmc_solve.hip ----
 int cg_solve_fused(const Problem& q, float ts, float* u, const float* rhs, float* r, float* p, float* qq, double* scal,
@@ -228,20 +289,16 @@ int cg_solve_fused(const Problem& q, float ts, float* u, const float* rhs, float
 
 // ---- lmc_tv_exit.hip ----
 bool needs_tv_state(const Problem& q);
-int tv_prox_rtol(const Problem& q, float pt, const float* x, float* sol, float* tmp, double* obj, int* flag, int64_t n, float* st0, float* st1,
-                 hipStream_t st);
-int me_tv_prox(const Problem& q, const float* x, float* extra, int64_t n_img, float* state0, float* state1, hipStream_t st, RtState* rt = nullptr);
-int tv_prior_rt(const Problem& q, float pt, lmc::StepArgs& A, RtState& rt, float* proxbuf, float* st0, float* st1, hipStream_t st);
+// (all of these work in the buffers of ws that prepare() sized for the problem)
+// sol <- prox_{pt g}(x) pass by pass; in ws: rtmp, the exit scalars of dbl, the dual state
+int tv_prox_rtol(const Problem& q, float pt, const float* x, float* sol, int64_t n, Workspace& ws, hipStream_t st);
+// ws.extra <- the inner prox of the ME-TV term at x
+int me_tv_prox(const Problem& q, const float* x, int64_t n_img, Workspace& ws, hipStream_t st);
+bool me_tv_exit_on_device(const Problem& q, int64_t n_img);     // its early exit (ncvx_rtol > 0) runs on the device, not pass by pass
+int tv_prior_rt(const Problem& q, float pt, lmc::StepArgs& A, Workspace& ws, hipStream_t st);
 int tv_prior_rt_mode(const Problem& q, const lmc::StepArgs& A_probe, float pt);
-lmc::EnergyArgs energy_args(const Problem& q);
-int pois_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
-int wl2_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
-int psf_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);
-int spectral_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, hipStream_t st);     // q.fft carries the buffers
-// after launch_energies: g_out = the value of the wavelet prior (nothing for the other priors); q.wav carries the workspace
-int wavelet_energy(const Problem& q, const float* x, int64_t n_img, double* g_out, hipStream_t st);
-int me_tv_energy(const Problem& q, const float* x, int64_t n_img, double* f_out, float* extra, float* st0, float* st1,
-                 double* dbl /* 2*n_img */, hipStream_t st, RtState* rt);
+// f_out[c] = f(x_c), g_out[c] = g(x_c) of the n_img images at x (either may be NULL): every data term, prior and non-convex term of q
+int problem_energies(const Problem& q, const float* x, int64_t n_img, double* f_out, double* g_out, Workspace& ws, hipStream_t st);
 
 }  // namespace lmc::host
 
@@ -256,16 +313,10 @@ struct lmc_sampler {
   float* uw2 = nullptr;       // ULPDA: the other home of the implicit-step solution (two Chebyshev iterations per launch deliver it there)
   float* cr = nullptr; float* cp = nullptr; float* cq = nullptr; float* ctmp = nullptr; float* xi = nullptr;
   float* htb = nullptr; double* scal = nullptr; float* zero_y = nullptr;
-  float* tvstate[2] = {nullptr, nullptr};   // dual-state ping-pong for chunked TV proxes (K > 12, ME-TV)
   float* tvwarm[2] = {nullptr, nullptr};    // warm-started TV prox: projected dual (p, q) of the previous / this MYULA iteration, [C][2][H][W]
   int wcur = 0;
-  float* extra = nullptr;                   // ME-TV inner prox
-  float* pxbuf = nullptr;                   // Haar-l1 prox / early-exit TV prox of the current state
-  float* wav_ws = nullptr; double* wav_part = nullptr;    // wavelet prior: the pyramid and the LL ping-pong (1.25 states), the partial sums of its value
-  float* psf_tab = nullptr; float* psf_resid = nullptr;   // large PSF: the device tap table (uploaded at creation) and the residual buffer, [C][H][W]
-  float* fft_tw = nullptr; float* fft_spec = nullptr; double* fft_part = nullptr;   // spectral data term: twiddle table, spectrum buffer [C][H][Wh] complex, value partials
-  float* rtmp = nullptr; double* robj = nullptr; int* rflag = nullptr;   // early-exit TV prox (tv_rtol > 0), pass-by-pass path: pass iterate, objectives, flags
-  lmc::host::RtState rt_tv, rt_me;          // early-exit TV prox on the device (tv_prox_rt): of the TV prior / of the ME-TV inner prox
+  lmc::host::Workspace ws;                  // the work buffers of prob on C images (prepare() at creation; prob's operators point into it)
+  lmc::host::Owned own;                     // every other device array, pinned array and event of the handle: the fields below point at its items
   // launch policy, fixed at creation (lmc_problem fields; their environment variables supply the defaults): see lmc_atomi.h
   int pol_pair = 1;          // 0 never, 1 where it pays, 2 wherever covered: two MYULA iterations per launch (rows kernel)
   int pol_blockpair = 1;     // 0 / 1: two or four iterations per launch on the block kernel

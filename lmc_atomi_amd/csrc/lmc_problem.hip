@@ -1,5 +1,6 @@
-// lmc_problem -> Problem (the argument checks of every entry point that takes a problem), the StepArgs of one update, the library defaults and
-// the step-kernel dispatch.
+// lmc_problem -> Problem (the argument checks of every entry point that takes a problem), the StepArgs of one update, prepare() (the work buffers
+// a problem needs and the binding of its operators to them), the library defaults and the step-kernel dispatch.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -41,19 +42,19 @@ int load_problem(const lmc_problem* p, Problem& q) {
   q.H = p->H; q.W = p->W;
   q.data_kind = p->data_kind;
   // the Poisson likelihood: inside the library the operator's kind plus a flag (every test on LMC_DATA_BLUR / IDENTITY / MASK serves both; the entry
-  // points without a Poisson form refuse the flag: check_no_poisson, check_poisson)
+  // points without a Poisson form refuse the flag: check_no_poisson, check_step_problem)
   if (p->data_kind >= LMC_DATA_POISSON_IDENTITY && p->data_kind <= LMC_DATA_POISSON_MASK) {
     q.data_kind = p->data_kind - LMC_DATA_POISSON_IDENTITY + LMC_DATA_IDENTITY;
     q.pois = 1;
   }
-  // per-pixel weights on the Gaussian term: the same arrangement (check_no_wl2, check_wl2)
+  // per-pixel weights on the Gaussian term: the same arrangement (check_no_wl2, check_step_problem)
   if (p->data_kind == LMC_DATA_WL2_IDENTITY || p->data_kind == LMC_DATA_WL2_BLUR) {
     // there is no weighted mask kind: a caller that hands over a mask with the weights would get it silently ignored -- say so instead (w = m is the mask)
     if (p->mask_dev) return fail(LMC_E_INVALID, "data_kind %d (weighted Gaussian term) takes no mask_dev: there is no weighted mask kind, put the mask into the weights", p->data_kind);
     q.data_kind = p->data_kind == LMC_DATA_WL2_BLUR ? LMC_DATA_BLUR : LMC_DATA_IDENTITY;
     q.wl2 = 1;
   }
-  // a large PSF: one operator kind of its own plus the same two flags (check_psf, check_no_psf) -- NOT LMC_DATA_BLUR, whose taps stay empty: a path
+  // a large PSF: one operator kind of its own plus the same two flags (check_step_problem, check_no_psf) -- NOT LMC_DATA_BLUR, whose taps stay empty: a path
   // that was not taught about the PSF meets an unknown data kind, not a blur without taps
   if (p->data_kind >= LMC_DATA_PSF && p->data_kind <= LMC_DATA_WL2_PSF) {
     if (p->kh || p->kw || p->oy || p->ox) return fail(LMC_E_INVALID, "data_kind %d (large PSF) takes its geometry in the psf_* fields: kh = kw = oy = ox = 0", p->data_kind);
@@ -129,7 +130,7 @@ int load_problem(const lmc_problem* p, Problem& q) {
       q.wav.on = 1; q.wav.p = p->eprox_kind; q.wav.levels = p->tv_niter;
       break;
     case LMC_PRIOR_TV_ANISO:
-      // tv_niter = 0: the callers that never form the prox (ULPDA, lmc_energies); the entry points that do refuse it (check_prox_prior)
+      // tv_niter = 0: the callers that never form the prox (ULPDA, lmc_energies); the entry points that do refuse it (check_step_problem)
       if (p->tv_niter == 0) break;
       [[fallthrough]];
     case LMC_PRIOR_TV_ISO:
@@ -219,40 +220,10 @@ int check_no_poisson(const Problem& q, const char* who, const char* why) {
   return fail(LMC_E_UNSUPPORTED, "%s does not take the Poisson data term (LMC_DATA_POISSON_*): %s", who, why);
 }
 
-// What the entry points that do take it (MYULA, SK-ROCK, lmc_fused_eval) refuse with it: everything that is not the fused step of the tiled kernel or of
-// the full-width pipeline's Poisson instantiations.
-int check_poisson(const Problem& q) {
-  if (!q.pois || q.psf.on) return LMC_OK;     // (a large PSF: check_psf -- its prior launch is that of a problem without a data term)
-  if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the Poisson data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
-  const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
-  if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "the Poisson data term with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0");
-  if (q.tv_warm_asked) return fail(LMC_E_UNSUPPORTED, "the Poisson data term with tv_warm: the warm-started dual has no Poisson form");
-  if (q.prior_kind == LMC_PRIOR_HAAR_L1) return fail(LMC_E_UNSUPPORTED, "the Poisson data term with LMC_PRIOR_HAAR_L1 is not built");
-  const int v = variant_of(q);
-  if (v != 0 && v != 1 && v != 7)
-    return fail(LMC_E_UNSUPPORTED, "step_variant %d has no form of the Poisson data term: 0 (auto), 1 (tile) or 7 (pipe, where it covers the problem)", v);
-  return LMC_OK;
-}
-
 // The entry points that have no form of the weighted Gaussian data term refuse a problem that carries one.
 int check_no_wl2(const Problem& q, const char* who, const char* why) {
   if (!q.wl2) return LMC_OK;
   return fail(LMC_E_UNSUPPORTED, "%s does not take the weighted Gaussian data term (LMC_DATA_WL2_*): %s", who, why);
-}
-
-// What the entry points that do take it (MYULA, MYMALA, SK-ROCK, lmc_fused_eval) refuse with it: everything that is not the fused step of the tiled
-// kernel or of the full-width pipeline's weighted instantiations.
-int check_wl2(const Problem& q) {
-  if (!q.wl2 || q.psf.on) return LMC_OK;      // (a large PSF: check_psf)
-  if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
-  const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
-  if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0");
-  if (q.tv_warm_asked) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term with tv_warm: the warm-started dual has no weighted form");
-  if (q.prior_kind == LMC_PRIOR_HAAR_L1) return fail(LMC_E_UNSUPPORTED, "the weighted Gaussian data term with LMC_PRIOR_HAAR_L1 is not built");
-  const int v = variant_of(q);
-  if (v != 0 && v != 1 && v != 7)
-    return fail(LMC_E_UNSUPPORTED, "step_variant %d has no form of the weighted Gaussian data term: 0 (auto), 1 (tile) or 7 (pipe, where it covers the problem)", v);
-  return LMC_OK;
 }
 
 // The entry points that have no form of the large PSF refuse a problem that carries one.
@@ -261,40 +232,57 @@ int check_no_psf(const Problem& q, const char* who, const char* why) {
   return fail(LMC_E_UNSUPPORTED, "%s does not take a large PSF (LMC_DATA_PSF, LMC_DATA_POISSON_PSF, LMC_DATA_WL2_PSF): %s", who, why);
 }
 
-// What the entry points that do take it (MYULA, SK-ROCK, lmc_fused_eval) refuse with it: what does not split into residual, prior launch and adjoint.
-int check_psf(const Problem& q) {
-  if (!q.psf.on) return LMC_OK;
-  if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "a large PSF has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
-  const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
-  if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "a large PSF with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0");
-  if (q.tv_warm_asked) return fail(LMC_E_UNSUPPORTED, "a large PSF with tv_warm: the warm-started dual is not built for it");
-  return LMC_OK;
-}
-
 // The entry points that have no form of the spectral data term refuse a problem that carries one.
 int check_no_spectral(const Problem& q, const char* who, const char* why) {
   if (!q.fft.on) return LMC_OK;
   return fail(LMC_E_UNSUPPORTED, "%s does not take the spectral data term (LMC_DATA_SPECTRAL): %s", who, why);
 }
 
-// What the entry points that do take it refuse with it: what does not split into spectrum, prior launch and inverse transform.
-int check_spectral(const Problem& q) {
-  if (!q.fft.on) return LMC_OK;
-  if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "the spectral data term has no non-convex form: ncvx_kind must be LMC_NCVX_NONE");
-  const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
-  if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "the spectral data term with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0");
-  if (q.tv_warm_asked) return fail(LMC_E_UNSUPPORTED, "the spectral data term with tv_warm: the warm-started dual is not built for it");
+// The data terms with step kernels of their own, in the order their refusals are made: its name in the messages, what the warm-started dual lacks
+// for it, and whether its step is a fused kernel of the term (the tiled kernel's and the full-width pipeline's instantiations: no Haar prior, variants
+// 0, 1, 7) or splits into the term's launches around the step of a problem without a data term (every prior and variant of that problem).
+struct DataTermRules { const char *name, *warm; bool own_kernels; };
+constexpr DataTermRules kDataTerms[4] = {{"the Poisson data term", "has no Poisson form", true},
+                                         {"the weighted Gaussian data term", "has no weighted form", true},
+                                         {"a large PSF", "is not built for it", false},
+                                         {"the spectral data term", "is not built for it", false}};
+#define LMC_DATA_TERMS_OF(q) {(q).pois != 0, (q).wl2 != 0, (q).psf.on != 0, (q).fft.on != 0}
+
+static int check_convex_term(const Problem& q, const DataTermRules& r) {
+  if (q.ncvx_kind == LMC_NCVX_NONE) return LMC_OK;
+  return fail(LMC_E_UNSUPPORTED, "%s has no non-convex form: ncvx_kind must be LMC_NCVX_NONE", r.name);
+}
+
+int check_convex_terms(const Problem& q) {
+  const bool has[4] = LMC_DATA_TERMS_OF(q);
+  for (int i = 0; i < 4; ++i)
+    if (has[i]) { const int rc = check_convex_term(q, kDataTerms[i]); if (rc) return rc; }
   return LMC_OK;
 }
 
-// What the entry points that form prox_g (MYULA, MYMALA, lmc_fused_eval) ask of the anisotropic TV prior beyond load_problem: an iteration
-// count, and none of the options that are built for the isotropic prior only.
-int check_prox_prior(const Problem& q, float b) {
-  if (q.prior_kind != LMC_PRIOR_TV_ANISO) return LMC_OK;
-  if (q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "tv_rtol > 0 (early exit of the prox) is not built for LMC_PRIOR_TV_ANISO: use the fixed-count prox, tv_rtol = 0");
-  if (q.tv_warm_asked) return fail(LMC_E_UNSUPPORTED, "tv_warm (warm-started dual) is not built for LMC_PRIOR_TV_ANISO");
-  if (b != 0.f && q.tv_niter_asked < 1)
-    return fail(LMC_E_INVALID, "LMC_PRIOR_TV_ANISO: the prox needs tv_niter in 1..%d (got 0)", lmc::kMaxTvIters);
+int check_step_problem(const Problem& q, float b) {
+  // the anisotropic TV prior beyond load_problem: an iteration count, and none of the options that are built for the isotropic prior only
+  if (q.prior_kind == LMC_PRIOR_TV_ANISO) {
+    if (q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "tv_rtol > 0 (early exit of the prox) is not built for LMC_PRIOR_TV_ANISO: use the fixed-count prox, tv_rtol = 0");
+    if (q.tv_warm_asked) return fail(LMC_E_UNSUPPORTED, "tv_warm (warm-started dual) is not built for LMC_PRIOR_TV_ANISO");
+    if (b != 0.f && q.tv_niter_asked < 1)
+      return fail(LMC_E_INVALID, "LMC_PRIOR_TV_ANISO: the prox needs tv_niter in 1..%d (got 0)", lmc::kMaxTvIters);
+  }
+  const bool has[4] = LMC_DATA_TERMS_OF(q);
+  const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
+  for (int i = 0; i < 4; ++i) {
+    const DataTermRules& r = kDataTerms[i];
+    if (!has[i] || (r.own_kernels && q.psf.on)) continue;     // (Poisson / weighted on a large PSF: the PSF's rules -- its step launch has no data term)
+    const int rc = check_convex_term(q, r);
+    if (rc) return rc;
+    if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "%s with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0", r.name);
+    if (q.tv_warm_asked) return fail(LMC_E_UNSUPPORTED, "%s with tv_warm: the warm-started dual %s", r.name, r.warm);
+    if (!r.own_kernels) continue;
+    if (q.prior_kind == LMC_PRIOR_HAAR_L1) return fail(LMC_E_UNSUPPORTED, "%s with LMC_PRIOR_HAAR_L1 is not built", r.name);
+    const int v = variant_of(q);
+    if (v != 0 && v != 1 && v != 7)
+      return fail(LMC_E_UNSUPPORTED, "step_variant %d has no form of %s: 0 (auto), 1 (tile) or 7 (pipe, where it covers the problem)", v, r.name);
+  }
   return LMC_OK;
 }
 
@@ -348,6 +336,91 @@ void sanitize_pointers(lmc::StepArgs& A) {
   if (!A.noise) A.noise = A.x_in;
 }
 
+hipError_t Workspace::bind_psf(lmc::PsfOp& P, size_t n_resid, hipStream_t st) {
+  hipError_t e = hipSuccess;
+  if (!psf_tab) e = hipMalloc(&psf_tab, sizeof P.tab);
+  if (e == hipSuccess && !psf_host) e = hipHostMalloc(&psf_host, sizeof P.tab);
+  if (e == hipSuccess && !psf_ev) e = hipEventCreateWithFlags(&psf_ev, hipEventDisableTiming);
+  if (e != hipSuccess) return e;
+  if (!psf_valid || std::memcmp(psf_host, P.tab, sizeof P.tab) != 0) {
+    if (psf_valid) e = hipEventSynchronize(psf_ev);      // the previous upload has read the pinned copy
+    psf_valid = false;
+    if (e != hipSuccess) return e;
+    std::memcpy(psf_host, P.tab, sizeof P.tab);
+    e = hipMemcpyAsync(psf_tab, psf_host, sizeof P.tab, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipEventRecord(psf_ev, st);
+    if (e != hipSuccess) return e;
+    psf_valid = true;
+  }
+  e = resid.need(n_resid);
+  P.tab_dev = psf_tab;
+  P.resid = resid.p;
+  return e;
+}
+
+hipError_t Workspace::bind_fft(lmc::FftOp& F, size_t n_spec, size_t n_part) {
+  if (!fft_tw) {
+    float tw[2 * lmc::kFftTw];
+    lmc::fft_twiddles(tw);
+    float* d = nullptr;
+    hipError_t e = hipMalloc(&d, sizeof tw);
+    if (e != hipSuccess) return e;
+    e = hipMemcpy(d, tw, sizeof tw, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); return e; }
+    fft_tw = d;
+  }
+  hipError_t e = fft_spec.need(n_spec);
+  if (e == hipSuccess) e = fft_part.need(n_part);
+  F.tw = reinterpret_cast<const float2*>(fft_tw);
+  F.spec = reinterpret_cast<float2*>(fft_spec.p);
+  F.part = fft_part.p;
+  return e;
+}
+
+hipError_t prepare(Workspace& ws, Problem& q, const lmc::StepArgs& probe, int64_t n_img, float pt, int what, hipStream_t st) {
+  const size_t n = (size_t)n_img, npx = n * q.H * q.W;
+  const bool step = what & kForStep, want_f = what & kForEnergyF, want_g = what & kForEnergyG;
+  const bool tv = step && probe.prior_kind == LMC_PRIOR_TV_ISO;                       // a TV prox runs (either form; not the lagged output of one pass)
+  const bool me = q.ncvx_kind == LMC_NCVX_ME_TV && ((step && probe.t != 0.f) || want_f);    // the inner prox of the ME-TV term runs
+  size_t n_prox = 0, n_rtmp = 0, n_dbl = 0;
+  hipError_t e = hipSuccess;
+  auto need = [&e](auto& buf, size_t count) { if (e == hipSuccess) e = buf.need(count); };
+  if (needs_tv_state(q) && (tv || me)) { need(ws.state[0], 4 * npx); need(ws.state[1], 4 * npx); }
+  if (me) {
+    need(ws.extra, npx);
+    if (e == hipSuccess && q.ncvx_rtol > 0.f) e = ws.rt_me.need(n, q.ncvx_niter);
+    n_dbl = Workspace::exit_doubles(n);      // the envelope's two sums; the exit scalars of the 1-D prox and of the pass-by-pass exit
+    if (q.ncvx_rtol > 0.f && !q.ncvx_aniso && !me_tv_exit_on_device(q, n_img)) n_rtmp = npx;
+  }
+  // a prox that is a launch of its own ahead of the step: the transforms, the closed forms (scalar or array-valued epsg), the box of a separable prior
+  if (step && (probe.prior_kind == LMC_PRIOR_HAAR_L1 || probe.prior_kind == LMC_PRIOR_WAVELET_L1 || probe.prior_kind == LMC_PRIOR_EPROX || q.prox_scale ||
+               (probe.box && probe.prior_kind != LMC_PRIOR_TV_ISO)))
+    n_prox = npx;
+  ws.tv_exit = -1;
+  if (tv && q.tv_rtol > 0.f) {     // the early exit of the TV prior's prox: 1 inside the fused launch, 0 the prox alone first, 2 pass by pass
+    ws.tv_exit = tv_prior_rt_mode(q, probe, pt);
+    if (e == hipSuccess && ws.tv_exit != 2) e = ws.rt_tv.need(n, q.tv_niter);
+    if (ws.tv_exit != 1) n_prox = npx;
+    if (ws.tv_exit == 2) { n_rtmp = npx; n_dbl = Workspace::exit_doubles(n); }
+  }
+  if (q.psf.on && ((step && probe.data_kind == LMC_DATA_PSF) || want_f)) {
+    if (e == hipSuccess) e = ws.bind_psf(q.psf, step && probe.data_kind == LMC_DATA_PSF ? npx : 0, st);
+    if (want_f) n_dbl = std::max(n_dbl, lmc::psf_energy_partials(n_img, q.H, q.W));
+  }
+  if (e == hipSuccess && q.fft.on && ((step && probe.data_kind == LMC_DATA_SPECTRAL) || want_f))
+    e = ws.bind_fft(q.fft, lmc::fft_spec_floats(n_img, q.H, q.W), want_f ? lmc::fft_value_partials(n_img, q.H, q.W) : 0);
+  if (q.wav.on && ((step && probe.prior_kind == LMC_PRIOR_WAVELET_L1) || want_g)) {
+    need(ws.wav, lmc::wavelet_ws_floats(n_img, q.H, q.W));
+    if (want_g) need(ws.wav_part, n * lmc::wavelet_partials(q.H, q.W, q.wav.levels));
+    q.wav.ws = ws.wav.p;
+    q.wav.part = ws.wav_part.p;
+  }
+  need(ws.prox, n_prox);
+  need(ws.rtmp, n_rtmp);
+  need(ws.dbl, n_dbl);
+  return e;
+}
+
 // Library-wide DEFAULTS only (lmc_set_step_variant / lmc_set_cg_tolerance): every launch takes its variant and tolerance from the
 // lmc_problem it was configured from (step_variant / implicit_tol) and falls back to these when that field is 0.
 int g_variant = 0;  // 0 auto, 1 tile, (2: removed) 3 split, 4 point, 5 block, 6 rows, 7 pipe (one team), 8 pipe2 (two teams)
@@ -357,7 +430,7 @@ float tol_of(const Problem& q) { return q.implicit_tol > 0.f ? q.implicit_tol : 
 
 // Picks the step-kernel variant.  auto: the split streaming pipeline (two wave groups, 4 waves/SIMD) when
 // it covers the configuration (W <= 512, separable blur <= 7x7, supported K), else the LDS-tiled kernel.
-static hipError_t launch_step_nobox(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf);
+static hipError_t launch_step_nobox(const lmc::StepArgs& A_in, int variant, Workspace& ws, hipStream_t st, const char** name);
 
 // The Poisson data term.  The full-width pipeline's Poisson instantiations where they cover the problem (isotropic TV, exactly 10 dual iterations, W > 128,
 // separable blur or pointwise data term; auto and 7), the tiled kernel's everywhere else and for every other prior (auto and 1): TV (either form, box or
@@ -365,15 +438,15 @@ static hipError_t launch_step_nobox(const lmc::StepArgs& A_in, int variant, hipS
 // before it and consumed as a ready-made prox.
 bool pois_pipe_covers(const lmc::StepArgs& A) { return A.pois && A.prior_kind == LMC_PRIOR_TV_ISO && lmc::pipe_links(A) == 1; }
 
-// The weighted Gaussian data term (launch_step_wl2) takes the same route with kernels of its own: the pipe where pipe_links == 1 covers the problem, the
+// The weighted Gaussian data term (kWl2Names) takes the same route with kernels of its own: the pipe where pipe_links == 1 covers the problem, the
 // tile kernel for everything else.
 bool wl2_pipe_covers(const lmc::StepArgs& A) { return A.wl2 && A.prior_kind == LMC_PRIOR_TV_ISO && lmc::pipe_links(A) == 1; }
 
 // the four kernel names of a data term that has instantiations of its own: pipe, pipe + box, tile, tile + box
 struct TermNames { const char *pipe, *pipe_box, *tile, *tile_box; };
 
-static hipError_t launch_step_term(const lmc::StepArgs& A_in, int variant, bool pipe_covers, const TermNames& nm, hipStream_t st, const char** name, float* state0,
-                                   float* state1, float* pxbuf) {
+static hipError_t launch_step_term(const lmc::StepArgs& A_in, int variant, bool pipe_covers, const TermNames& nm, Workspace& ws, hipStream_t st, const char** name) {
+  float *const state0 = ws.state[0].p, *const state1 = ws.state[1].p, *const pxbuf = ws.prox.p;
   if (variant != 0 && variant != 1 && variant != 7) return hipErrorInvalidConfiguration;
   if (variant != 1 && pipe_covers) {
     if (name) *name = A_in.box ? nm.pipe_box : nm.pipe;
@@ -400,82 +473,79 @@ static hipError_t launch_step_term(const lmc::StepArgs& A_in, int variant, bool 
   return lmc::launch_step_tile(A, st);
 }
 
-static hipError_t launch_step_pois(const lmc::StepArgs& A, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
-  static const TermNames nm = {"myula_step_pipe_pois_kernel", "myula_step_pipe_pois_box_kernel", "myula_step_tile_pois_kernel", "myula_step_tile_pois_box_kernel"};
-  return launch_step_term(A, variant, pois_pipe_covers(A), nm, st, name, state0, state1, pxbuf);
-}
-
-static hipError_t launch_step_wl2(const lmc::StepArgs& A, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
-  static const TermNames nm = {"myula_step_pipe_wl2_kernel", "myula_step_pipe_wl2_box_kernel", "myula_step_tile_wl2_kernel", "myula_step_tile_wl2_box_kernel"};
-  return launch_step_term(A, variant, wl2_pipe_covers(A), nm, st, name, state0, state1, pxbuf);
-}
+constexpr TermNames kPoisNames = {"myula_step_pipe_pois_kernel", "myula_step_pipe_pois_box_kernel", "myula_step_tile_pois_kernel", "myula_step_tile_pois_box_kernel"};
+constexpr TermNames kWl2Names = {"myula_step_pipe_wl2_kernel", "myula_step_pipe_wl2_box_kernel", "myula_step_tile_wl2_kernel", "myula_step_tile_wl2_box_kernel"};
 
 // The box-constrained forms.  Separable priors: one elementwise launch forms clip(prox) into pxbuf, then the step of the variant asked for consumes it.
 // TV priors: the pipe kernel's box instantiations (isotropic; auto, 7, 8) or the tile kernel's (either form; auto, 1); a forced variant without a box
 // form is not covered.
-// A large PSF: the update as three launches.  The residual r = rho(H x) into psf->resid; the step of the same arguments without a data term
-// (t = 0: every prior, the box, the noise and the forced variant as they are there); x_out -= t sigma_f H^T r.  Without prox and noise the second
-// launch has nothing to do and the third writes a x - t sigma_f H^T r.
-static hipError_t launch_step_psf(const lmc::StepArgs& A, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf,
-                                  const lmc::PsfOp* psf) {
-  if (!psf || !psf->on || !psf->tab_dev || !psf->resid) return hipErrorInvalidConfiguration;
+// A data term that is launches of its own (a large PSF, the spectral term): the update as three steps.  residual(): the term's residual r at x_in into
+// the operator's buffer; the step of the same arguments without a data term (t = 0: every prior, the box, the noise and the forced variant as they are
+// there); adjoint(false, 0, c): x_out -= c Op^T r.  Without prox and noise the second step has nothing to do and adjoint(true, a, c) writes
+// a x - c Op^T r under the kernel name `alone`.
+template <class Residual, class Adjoint>
+static hipError_t launch_step_around(const lmc::StepArgs& A, int variant, const Problem& q, Workspace& ws, hipStream_t st, const char** name, const char* alone,
+                                     Residual residual, Adjoint adjoint) {
   if (A.ncvx_kind != LMC_NCVX_NONE || A.extra || A.tv_in || A.tv_out || A.f_out || A.g_out || A.rt_kc) return hipErrorInvalidConfiguration;
-  const int rho = A.pois ? lmc::kPsfRhoPois : A.wl2 ? lmc::kPsfRhoWl2 : lmc::kPsfRhoL2;
-  hipError_t e = lmc::launch_psf(*psf, 0, rho, A.x_in, psf->resid, nullptr, A.y, A.C, A.H, A.W, 0.f, 0.f, st);
+  hipError_t e = residual();
   if (e != hipSuccess) return e;
   const float coef = A.t * A.sigma_f;
   if (A.b == 0.f && A.s == 0.f) {
-    if (name) *name = "psf_conv_kernel";
-    return lmc::launch_psf(*psf, 1, lmc::kPsfOverwrite, psf->resid, A.x_out, A.x_in, nullptr, A.C, A.H, A.W, A.a, coef, st);
+    if (name) *name = alone;
+    return adjoint(true, A.a, coef);
   }
   lmc::StepArgs B = A;
   B.data_kind = LMC_DATA_NONE; B.t = 0.f; B.pois = 0; B.wl2 = 0;
-  e = launch_step(B, variant, st, name, state0, state1, pxbuf);      // (a wavelet prior: launch_step has formed its prox already, B carries it)
+  e = launch_step(B, variant, q, ws, st, name);      // (a wavelet prior: launch_step has formed its prox already, B carries it)
   if (e != hipSuccess) return e;
-  return lmc::launch_psf(*psf, 1, lmc::kPsfSub, psf->resid, A.x_out, nullptr, nullptr, A.C, A.H, A.W, 0.f, coef, st);
+  return adjoint(false, 0.f, coef);
 }
 
-// The spectral data term: the same three steps.  The spectrum A xh - B of the gradient into fft->spec (row transform, then the column kernel with its
-// functor between the two column transforms); the step of the same arguments without a data term; x_out -= t sigma_f irfft (row inverse).  Without prox
-// and noise the last launch writes a x - t sigma_f irfft.
-static hipError_t launch_step_fft(const lmc::StepArgs& A, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf,
-                                  const lmc::FftOp* fft) {
-  if (!fft || !fft->on || !fft->tab || !fft->tw || !fft->spec) return hipErrorInvalidConfiguration;
-  if (A.ncvx_kind != LMC_NCVX_NONE || A.extra || A.tv_in || A.tv_out || A.f_out || A.g_out || A.rt_kc) return hipErrorInvalidConfiguration;
-  hipError_t e = lmc::launch_fft_rows_fwd(A.x_in, fft->spec, fft->tw, A.C, A.H, A.W, st);
-  if (e != hipSuccess) return e;
-  e = lmc::launch_fft_cols(lmc::kFftGrad, fft->spec, fft->tab, fft->tw, A.C, A.H, A.W, 0.f, st);
-  if (e != hipSuccess) return e;
-  const float coef = A.t * A.sigma_f;
-  if (A.b == 0.f && A.s == 0.f) {
-    if (name) *name = "fft_rows_inv_kernel";
-    return lmc::launch_fft_rows_inv(lmc::kFftOverwrite, fft->spec, A.x_out, A.x_in, fft->tw, A.C, A.H, A.W, A.a, coef, st);
-  }
-  lmc::StepArgs B = A;
-  B.data_kind = LMC_DATA_NONE; B.t = 0.f;
-  e = launch_step(B, variant, st, name, state0, state1, pxbuf);      // (a wavelet prior: launch_step has formed its prox already, B carries it)
-  if (e != hipSuccess) return e;
-  return lmc::launch_fft_rows_inv(lmc::kFftSub, fft->spec, A.x_out, nullptr, fft->tw, A.C, A.H, A.W, 0.f, coef, st);
+// A large PSF: r = rho(H x) into psf.resid, then H^T r.
+static hipError_t launch_step_psf(const lmc::StepArgs& A, int variant, const Problem& q, Workspace& ws, hipStream_t st, const char** name) {
+  const lmc::PsfOp& P = q.psf;
+  if (!P.on || !P.tab_dev || !P.resid) return hipErrorInvalidConfiguration;
+  const int rho = A.pois ? lmc::kPsfRhoPois : A.wl2 ? lmc::kPsfRhoWl2 : lmc::kPsfRhoL2;
+  return launch_step_around(A, variant, q, ws, st, name, "psf_conv_kernel",
+      [&] { return lmc::launch_psf(P, 0, rho, A.x_in, P.resid, nullptr, A.y, A.C, A.H, A.W, 0.f, 0.f, st); },
+      [&](bool alone, float a, float coef) {
+        return lmc::launch_psf(P, 1, alone ? lmc::kPsfOverwrite : lmc::kPsfSub, P.resid, A.x_out, alone ? A.x_in : nullptr, nullptr, A.C, A.H, A.W, a, coef, st);
+      });
 }
 
-hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf,
-                       const lmc::PsfOp* psf, const lmc::WaveletOp* wav, const lmc::FftOp* fft) {
+// The spectral data term: the spectrum A xh - B of the gradient into fft.spec (row transform, then the column kernel with its functor between the two
+// column transforms), then the row inverse.
+static hipError_t launch_step_fft(const lmc::StepArgs& A, int variant, const Problem& q, Workspace& ws, hipStream_t st, const char** name) {
+  const lmc::FftOp& F = q.fft;
+  if (!F.on || !F.tab || !F.tw || !F.spec) return hipErrorInvalidConfiguration;
+  return launch_step_around(A, variant, q, ws, st, name, "fft_rows_inv_kernel",
+      [&] {
+        const hipError_t e = lmc::launch_fft_rows_fwd(A.x_in, F.spec, F.tw, A.C, A.H, A.W, st);
+        return e != hipSuccess ? e : lmc::launch_fft_cols(lmc::kFftGrad, F.spec, F.tab, F.tw, A.C, A.H, A.W, 0.f, st);
+      },
+      [&](bool alone, float a, float coef) {
+        return lmc::launch_fft_rows_inv(alone ? lmc::kFftOverwrite : lmc::kFftSub, F.spec, A.x_out, alone ? A.x_in : nullptr, F.tw, A.C, A.H, A.W, a, coef, st);
+      });
+}
+
+hipError_t launch_step(const lmc::StepArgs& A_in, int variant, const Problem& q, Workspace& ws, hipStream_t st, const char** name) {
+  float *const state0 = ws.state[0].p, *const state1 = ws.state[1].p, *const pxbuf = ws.prox.p;
   if (A_in.prior_kind == LMC_PRIOR_WAVELET_L1) {
     // the route of LMC_PRIOR_HAAR_L1 in launch_step_nobox, taken before the data terms part ways: the prox into pxbuf, then the step of the same
     // problem without a prior, which consumes it as a ready-made prox -- on whatever kernel that problem gets
-    if (!pxbuf || !wav || !wav->on || !wav->ws) return hipErrorInvalidConfiguration;
-    hipError_t e = lmc::launch_wavelet_prox(A_in.x_in, pxbuf, A_in.C, A_in.H, A_in.W, wav->p, wav->levels, A_in.prior_p0, wav->ws, st);
+    if (!pxbuf || !q.wav.on || !q.wav.ws) return hipErrorInvalidConfiguration;
+    hipError_t e = lmc::launch_wavelet_prox(A_in.x_in, pxbuf, A_in.C, A_in.H, A_in.W, q.wav.p, q.wav.levels, A_in.prior_p0, q.wav.ws, st);
     if (e != hipSuccess) return e;
     lmc::StepArgs A = A_in;
     A.prior_kind = LMC_PRIOR_NONE;
     A.prox_ext = pxbuf;
-    return launch_step(A, variant, st, name, state0, state1, pxbuf, psf, nullptr, fft);
+    return launch_step(A, variant, q, ws, st, name);
   }
-  if (A_in.data_kind == LMC_DATA_PSF) return launch_step_psf(A_in, variant, st, name, state0, state1, pxbuf, psf);
-  if (A_in.data_kind == LMC_DATA_SPECTRAL) return launch_step_fft(A_in, variant, st, name, state0, state1, pxbuf, fft);
-  if (A_in.pois) return launch_step_pois(A_in, variant, st, name, state0, state1, pxbuf);
-  if (A_in.wl2) return launch_step_wl2(A_in, variant, st, name, state0, state1, pxbuf);
-  if (!A_in.box) return launch_step_nobox(A_in, variant, st, name, state0, state1, pxbuf);
+  if (A_in.data_kind == LMC_DATA_PSF) return launch_step_psf(A_in, variant, q, ws, st, name);
+  if (A_in.data_kind == LMC_DATA_SPECTRAL) return launch_step_fft(A_in, variant, q, ws, st, name);
+  if (A_in.pois) return launch_step_term(A_in, variant, pois_pipe_covers(A_in), kPoisNames, ws, st, name);
+  if (A_in.wl2) return launch_step_term(A_in, variant, wl2_pipe_covers(A_in), kWl2Names, ws, st, name);
+  if (!A_in.box) return launch_step_nobox(A_in, variant, ws, st, name);
   lmc::StepArgs A = A_in;
   if (A.prior_kind != LMC_PRIOR_TV_ISO) {
     if (A.prior_kind == LMC_PRIOR_HAAR_L1 || !pxbuf) return hipErrorInvalidConfiguration;
@@ -487,7 +557,7 @@ hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, c
     }
     A.prior_kind = LMC_PRIOR_NONE;
     A.box = 0;
-    return launch_step_nobox(A, variant, st, name, state0, state1, pxbuf);
+    return launch_step_nobox(A, variant, ws, st, name);
   }
   const int v = variant;
   if (v == 0 || v == 7 || v == 8) {
@@ -510,7 +580,8 @@ hipError_t launch_step(const lmc::StepArgs& A_in, int variant, hipStream_t st, c
   return lmc::launch_step_tile(A, st);
 }
 
-static hipError_t launch_step_nobox(const lmc::StepArgs& A_in, int variant, hipStream_t st, const char** name, float* state0, float* state1, float* pxbuf) {
+static hipError_t launch_step_nobox(const lmc::StepArgs& A_in, int variant, Workspace& ws, hipStream_t st, const char** name) {
+  float *const state0 = ws.state[0].p, *const state1 = ws.state[1].p, *const pxbuf = ws.prox.p;
   int v = variant;
   // no stencil in the data term and a prox local to 8 x 8 blocks (Haar-l1, l2, l1, none): the register-block kernel
   if ((v == 0 || v == 5) && lmc::block_supported(A_in)) {

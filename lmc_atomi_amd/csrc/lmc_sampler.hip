@@ -93,11 +93,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   if (!s) return fail(LMC_E_NOMEM, "host allocation failed");
   rc = load_problem(&cfg->problem, s->prob);
   if (rc) { delete s; return rc; }
-  rc = check_prox_prior(s->prob, cfg->tau / cfg->gamma);
-  if (!rc) rc = check_poisson(s->prob);
-  if (!rc) rc = check_wl2(s->prob);
-  if (!rc) rc = check_psf(s->prob);
-  if (!rc) rc = check_spectral(s->prob);
+  rc = check_step_problem(s->prob, cfg->tau / cfg->gamma);
   if (rc) { delete s; return rc; }
   if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }
   s->C = cfg->n_chains;
@@ -118,53 +114,14 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     return fail(LMC_E_UNSUPPORTED, "step_variant 7 (pipe) does not cover this weighted Gaussian problem: isotropic TV with 10 dual iterations (after "
                 "tv_lagged_output), W > 128, separable blur of 5 or 7 taps or the identity; use 0 (auto) or 1 (tile)");
   }
-  const size_t nbytes = sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W;
-  hipError_t e = hipMalloc(&s->x[0], nbytes);
-  if (e == hipSuccess) e = hipMalloc(&s->x[1], nbytes);
-  if (e == hipSuccess) e = hipMemset(s->x[0], 0, nbytes);
-  if (e == hipSuccess && needs_tv_state(s->prob)) {
-    e = hipMalloc(&s->tvstate[0], 4 * nbytes);
-    if (e == hipSuccess) e = hipMalloc(&s->tvstate[1], 4 * nbytes);
-  }
-  if (e == hipSuccess && s->prob.ncvx_kind == LMC_NCVX_ME_TV) e = hipMalloc(&s->extra, nbytes);
-  if (e == hipSuccess && s->prob.psf.on) {     // large PSF: the handle uploads the tap table once and owns the residual buffer
-    e = hipMalloc(&s->psf_tab, sizeof s->prob.psf.tab);
-    if (e == hipSuccess) e = hipMemcpy(s->psf_tab, s->prob.psf.tab, sizeof s->prob.psf.tab, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&s->psf_resid, nbytes);
-    s->prob.psf.tab_dev = s->psf_tab;
-    s->prob.psf.resid = s->psf_resid;
-  }
-  if (e == hipSuccess && s->prob.fft.on) {     // spectral data term: the handle uploads the twiddle table once and owns the spectrum buffer and the value partials
-    float tw[2 * lmc::kFftTw];
-    lmc::fft_twiddles(tw);
-    e = hipMalloc(&s->fft_tw, sizeof tw);
-    if (e == hipSuccess) e = hipMemcpy(s->fft_tw, tw, sizeof tw, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&s->fft_spec, sizeof(float) * lmc::fft_spec_floats(s->C, s->prob.H, s->prob.W));
-    if (e == hipSuccess) e = hipMalloc(&s->fft_part, sizeof(double) * lmc::fft_value_partials(s->C, s->prob.H, s->prob.W));
-    s->prob.fft.tw = reinterpret_cast<const float2*>(s->fft_tw);
-    s->prob.fft.spec = reinterpret_cast<float2*>(s->fft_spec);
-    s->prob.fft.part = s->fft_part;
-  }
-  if (e == hipSuccess && s->prob.wav.on) {     // wavelet prior: the handle owns the pyramid, the LL ping-pong and the partial sums of the value
-    e = hipMalloc(&s->wav_ws, sizeof(float) * lmc::wavelet_ws_floats(s->C, s->prob.H, s->prob.W));
-    if (e == hipSuccess) e = hipMalloc(&s->wav_part, sizeof(double) * (size_t)s->C * lmc::wavelet_partials(s->prob.H, s->prob.W, s->prob.wav.levels));
-    s->prob.wav.ws = s->wav_ws;
-    s->prob.wav.part = s->wav_part;
-  }
-  if (e == hipSuccess && (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 || s->prob.prior_kind == LMC_PRIOR_WAVELET_L1 || s->prob.prior_kind == LMC_PRIOR_EPROX || s->prob.prox_scale ||
-                          (s->base.box && s->base.prior_kind != LMC_PRIOR_TV_ISO))) e = hipMalloc(&s->pxbuf, nbytes);
-  if (e == hipSuccess && s->prob.tv_rtol > 0.f && s->base.prior_kind == LMC_PRIOR_TV_ISO) {
-    if (s->prob.tv_warm) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "tv_rtol > 0 and tv_warm exclude each other"); }
-    const int mode = tv_prior_rt_mode(s->prob, s->base, s->epsg * s->gamma);     // 1: inside the fused launch, 0: prox alone, 2: pass by pass
-    if (mode != 2) e = s->rt_tv.need((size_t)s->C, s->prob.tv_niter);
-    if (e == hipSuccess && mode != 1 && !s->pxbuf) e = hipMalloc(&s->pxbuf, nbytes);
-    if (mode == 2) {
-      if (e == hipSuccess) e = hipMalloc(&s->rtmp, nbytes);
-      if (e == hipSuccess) e = hipMalloc(&s->robj, sizeof(double) * 2 * (size_t)s->C);
-      if (e == hipSuccess) e = hipMalloc(&s->rflag, sizeof(int) * ((size_t)s->C + 1));
-    }
-  }
-  if (e == hipSuccess && s->prob.ncvx_kind == LMC_NCVX_ME_TV && s->prob.ncvx_rtol > 0.f) e = s->rt_me.need((size_t)s->C, s->prob.ncvx_niter);
+  if (s->prob.tv_rtol > 0.f && s->base.prior_kind == LMC_PRIOR_TV_ISO && s->prob.tv_warm) { delete s; return fail(LMC_E_UNSUPPORTED, "tv_rtol > 0 and tv_warm exclude each other"); }
+  const size_t n = (size_t)s->C * s->prob.H * s->prob.W;
+  hipError_t e = s->own.alloc(&s->x[0], n, true);
+  if (e == hipSuccess) e = s->own.alloc(&s->x[1], n, false);
+  // every work buffer of the step and of the energies, here and never inside lmc_sampler_step; the PSF table is on the device when this call returns
+  // (the caller's step stream need not order against the null stream)
+  if (e == hipSuccess) e = prepare(s->ws, s->prob, s->base, s->C, s->epsg * s->gamma, kForStep | kForEnergies, nullptr);
+  if (e == hipSuccess && s->ws.psf_ev) e = hipEventSynchronize(s->ws.psf_ev);
   {   // launch policy: the lmc_problem fields, their environment variables where a field is 0 -- read here, once, never inside lmc_sampler_step
     const Problem& q = s->prob;
     const int ipl = q.iters_per_launch ? q.iters_per_launch : env_int("LMC_ITERS_PER_LAUNCH", 0);
@@ -172,12 +129,11 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     s->pol_blockpair = ipl == 1 ? 0 : (ipl == 2 ? 1 : (env_int("LMC_BLOCK_PAIR", 1) != 0));
     s->pol_overlap = q.moments_overlap ? q.moments_overlap : (getenv("LMC_MOMENTS_OVERLAP") ? (env_int("LMC_MOMENTS_OVERLAP", 0) ? 1 : -1) : 0);
     s->pol_bg_wgs = q.moments_bg_wgs > 0 ? q.moments_bg_wgs : env_int("LMC_MOMENTS_BG_WGS", -1);
-    if (q.prox_scale || q.box) { s->pol_pair = 0; s->pol_blockpair = 0; }   // array-valued epsg, box constraint: the prox is its own launch before every step
-    if (q.wl2) { s->pol_pair = 0; s->pol_blockpair = 0; }                   // weighted Gaussian data term: the same
-    if (q.pois) { s->pol_pair = 0; s->pol_blockpair = 0; }                  // Poisson data term: one iteration per launch (the pair kernels have no form of it)
-    if (q.psf.on) { s->pol_pair = 0; s->pol_blockpair = 0; }                // large PSF: three launches per iteration
-    if (q.fft.on) { s->pol_pair = 0; s->pol_blockpair = 0; }                // spectral data term: the same
-    if (q.wav.on) { s->pol_pair = 0; s->pol_blockpair = 0; }                // wavelet prior: the prox is launches of its own before every step
+    // One iteration per launch (the pair kernels have no form of it) wherever an iteration is more than the one fused launch:
+    //   prox_scale, box, wav.on   the prox is a launch of its own before every step (array-valued epsg, the clamp, the wavelet transforms)
+    //   wl2, pois                 the weighted Gaussian and the Poisson data terms have kernels of their own, none of them a pair kernel
+    //   psf.on, fft.on            the large PSF and the spectral data term are three launches per iteration
+    if (q.prox_scale || q.box || q.wav.on || q.wl2 || q.pois || q.psf.on || q.fft.on) { s->pol_pair = 0; s->pol_blockpair = 0; }
   }
   if (e == hipSuccess && s->prob.tv_warm) {
     lmc::StepArgs probe = s->base;
@@ -187,10 +143,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
       return fail(LMC_E_UNSUPPORTED, "tv_warm: needs tv_niter in {1, 2, 3} (after tv_lagged_output) and the full-width pipeline kernel "
                   "(W > 128, W %% 4 == 0 (%% 8 above 256), separable blur <= 7 taps / pointwise / no data term)");
     }
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-      e = hipMalloc(&s->tvwarm[i], 2 * nbytes);
-      if (e == hipSuccess) e = hipMemset(s->tvwarm[i], 0, 2 * nbytes);
-    }
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = s->own.alloc(&s->tvwarm[i], 2 * n, true);
   }
   if (e == hipSuccess) e = alloc_moments(s);
   if (e != hipSuccess) return alloc_failed(s, e);
@@ -202,29 +155,10 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
 void lmc_sampler_destroy(lmc_sampler* s) {
   if (!s) return;
   DeviceGuard dg(s->device);
-  for (float* b : {s->xmid[0], s->xmid[1], s->xspare, s->zero_y, s->xhat, s->ydual, s->uw, s->uw2, s->rhs, s->cr, s->cp, s->cq, s->ctmp, s->xi, s->htb, s->tvstate[0], s->tvstate[1], s->extra, s->pxbuf, s->wav_ws,
-                   s->psf_tab, s->psf_resid, s->fft_tw, s->fft_spec, s->mx, s->xp, s->mxp, s->tvwarm[0], s->tvwarm[1], s->rtmp})
-    if (b) (void)hipFree(b);
-  if (s->robj) (void)hipFree(s->robj);
-  if (s->wav_part) (void)hipFree(s->wav_part);
-  if (s->fft_part) (void)hipFree(s->fft_part);
-  if (s->rflag) (void)hipFree(s->rflag);
-  s->rt_tv.release();
-  s->rt_me.release();
-  if (s->mala_d) (void)hipFree(s->mala_d);
-  if (s->flag) (void)hipFree(s->flag);
-  if (s->nacc) (void)hipFree(s->nacc);
-  if (s->scal) (void)hipFree(s->scal);
-  if (s->x[0]) (void)hipFree(s->x[0]);
-  if (s->x[1]) (void)hipFree(s->x[1]);
-  s->acc.release();
-  if (s->sapg_stat) (void)hipFree(s->sapg_stat);
-  if (s->sapg_trace) (void)hipFree(s->sapg_trace);
-  if (s->sapg_host) (void)hipHostFree(s->sapg_host);
-  if (s->sapg_ev) (void)hipEventDestroy(s->sapg_ev);
-  for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
   if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }
-  for (hipEvent_t e : s->side_ev) if (e) (void)hipEventDestroy(e);
+  s->own.release();
+  s->ws.release();
+  s->acc.release();
   delete s;
 }
 
@@ -251,29 +185,9 @@ static int ulpda_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, h
 static int mymala_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, hipStream_t st);
 static int skrock_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, hipStream_t st);
 
-// f(x_c), g(x_c) of `x` ([C][H][W]) with the sampler's problem and scratch buffers
+// f(x_c), g(x_c) of `x` ([C][H][W]) with the sampler's problem, in the sampler's workspace
 static int sampler_energies_at(lmc_sampler* s, const float* x, double* f_out_dev, double* g_out_dev, hipStream_t st) {
-  HIP_TRY(lmc::launch_energies(x, s->C, energy_args(s->prob), f_out_dev, g_out_dev, st));
-  {
-    int rc = pois_energy(s->prob, x, s->C, f_out_dev, st);
-    if (!rc) rc = wl2_energy(s->prob, x, s->C, f_out_dev, st);
-    if (!rc) rc = psf_energy(s->prob, x, s->C, f_out_dev, st);
-    if (!rc) rc = spectral_energy(s->prob, x, s->C, f_out_dev, st);
-    if (rc) return rc;
-  }
-  if (s->prob.prior_kind == LMC_PRIOR_HAAR_L1 && g_out_dev)
-    HIP_TRY(lmc::launch_haar_value(x, s->C, s->prob.H, s->prob.W, s->prob.prior_sigma, g_out_dev, st));
-  {
-    const int rc = wavelet_energy(s->prob, x, s->C, g_out_dev, st);
-    if (rc) return rc;
-  }
-  if (s->prob.ncvx_kind == LMC_NCVX_ME_TV && f_out_dev) {
-    Scratch& sc = scratch_here();
-    HIP_TRY(sc.need_dbl(3 * (size_t)s->C + 2));
-    int rc = me_tv_energy(s->prob, x, s->C, f_out_dev, s->extra, s->tvstate[0], s->tvstate[1], sc.dbl, st, &s->rt_me);
-    if (rc) return rc;
-  }
-  return LMC_OK;
+  return problem_energies(s->prob, x, s->C, f_out_dev, g_out_dev, s->ws, st);
 }
 
 // an iterate the posterior-moment accumulators keep: after burn-in, every thin-th (none while lmc_sampler_sapg runs)
@@ -282,9 +196,9 @@ static bool kept(const lmc_sampler* s, int64_t it) { return s->moments && !s->su
 // ME-TV: the inner prox of the Moreau-envelope term at A.x_in, which the fused step then takes as its extra gradient term
 static int me_tv_extra(lmc_sampler* s, lmc::StepArgs& A, hipStream_t st) {
   if (s->prob.ncvx_kind != LMC_NCVX_ME_TV) return LMC_OK;
-  int rc = me_tv_prox(s->prob, A.x_in, s->extra, s->C, s->tvstate[0], s->tvstate[1], st, &s->rt_me);
+  int rc = me_tv_prox(s->prob, A.x_in, s->C, s->ws, st);
   if (rc) return rc;
-  A.extra = s->extra;
+  A.extra = s->ws.extra.p;
   A.extra_coef = -s->prob.ncvx_lambda / s->prob.ncvx_gamma;
   return LMC_OK;
 }
@@ -329,7 +243,7 @@ static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool 
   int rc = me_tv_extra(s, A, st);   // inner prox of the Moreau-envelope term, then the fused step
   if (rc) return rc;
   if (ov && ov->ev_begin) HIP_TRY(hipEventRecord(ov->ev_begin, st));
-  hipError_t e = launch_step(A, variant_of(s->prob), st, kname, s->tvstate[0], s->tvstate[1], s->pxbuf, s->prob.psf.on ? &s->prob.psf : nullptr, &s->prob.wav, s->prob.fft.on ? &s->prob.fft : nullptr);
+  hipError_t e = launch_step(A, s->prob, s->ws, st, kname);
   if (e == hipErrorInvalidConfiguration) return fail(LMC_E_UNSUPPORTED, "no step-kernel variant covers this configuration");
   HIP_TRY(e);
   if (ov && ov->ev_end) HIP_TRY(hipEventRecord(ov->ev_end, st));
@@ -391,7 +305,7 @@ struct SideMoments {
 // The array of its own for a kept iterate in between whose reduction runs under the next launch (alternating by launch).
 static hipError_t xmid_array(lmc_sampler* s, float** out) {
   float*& xm = s->xmid[s->last_launches & 1];
-  const hipError_t e = xm ? hipSuccess : hipMalloc(&xm, sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W);
+  const hipError_t e = xm ? hipSuccess : s->own.alloc(&xm, (size_t)s->C * s->prob.H * s->prob.W, false);
   *out = xm;
   return e;
 }
@@ -402,7 +316,7 @@ static hipError_t xmid_array(lmc_sampler* s, float** out) {
 // long bands: x_{k+2} goes to a third array (neighbouring bands re-read x_k), x_{k+1} is stored only when the moment accumulators keep it.
 // lmc_problem.iterations_per_launch / LMC_ROWS_PAIR: 0 = never, 2 = wherever covered (tests), default = where it pays (n_chains * H >= 2^17).
 static int myula_rows_pair(lmc_sampler* s, SideMoments& m, int left) {
-  if (!s->pol_pair || left < 2 || s->tvwarm[0] || s->rtmp || s->prob.ncvx_kind != LMC_NCVX_NONE ||
+  if (!s->pol_pair || left < 2 || s->tvwarm[0] || s->ws.tv_exit == 2 || s->prob.ncvx_kind != LMC_NCVX_NONE ||
       (variant_of(s->prob) != 0 && variant_of(s->prob) != 6) || (s->pol_pair != 2 && (long long)s->C * s->prob.H < (1 << 17)))
     return 0;
   lmc::StepArgs A = s->base;
@@ -411,7 +325,7 @@ static int myula_rows_pair(lmc_sampler* s, SideMoments& m, int left) {
   A.noise = nullptr;
   sanitize_pointers(A);
   if (!lmc::rows_pair_supported(A)) return 0;
-  if (!s->xspare) HIP_TRY(hipMalloc(&s->xspare, sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W));
+  if (!s->xspare) HIP_TRY(s->own.alloc(&s->xspare, (size_t)s->C * s->prob.H * s->prob.W, false));
   const bool keep_mid = kept(s, s->iteration), keep_out = kept(s, s->iteration + 1);
   float* mid = keep_mid ? s->x[s->cur ^ 1] : nullptr;
   if (keep_mid && m.overlap) HIP_TRY(xmid_array(s, &mid));
@@ -433,7 +347,7 @@ static int myula_rows_pair(lmc_sampler* s, SideMoments& m, int left) {
 // thread's 8 x 8 block, so the second iteration runs on the block while it is on chip; x_{k+1} is written (in place, over x_k) only when the
 // moment accumulators keep it.  LMC_BLOCK_PAIR=0 turns it off.  Same arithmetic, same noise: bit-identical to two launches.
 static int myula_block_pair(lmc_sampler* s, SideMoments& m, int left) {
-  if (!s->pol_blockpair || left < 2 || s->tvwarm[0] || s->rtmp || s->prob.ncvx_kind != LMC_NCVX_NONE ||
+  if (!s->pol_blockpair || left < 2 || s->tvwarm[0] || s->ws.tv_exit == 2 || s->prob.ncvx_kind != LMC_NCVX_NONE ||
       (variant_of(s->prob) != 0 && variant_of(s->prob) != 5))
     return 0;
   lmc::StepArgs A = s->base;
@@ -480,29 +394,29 @@ static int myula_single(lmc_sampler* s, SideMoments& m, const float* noise, bool
   const char* kname = nullptr;
   hipError_t e;
   bool stepped = false;
-  if (s->rt_tv.kc && A.prior_kind == LMC_PRIOR_TV_ISO) {   // early exit of the TV prox decided on the device: inside the fused launch, or the prox alone first
-    rc = tv_prior_rt(s->prob, s->epsg * s->gamma, A, s->rt_tv, s->pxbuf, s->tvstate[0], s->tvstate[1], st);
+  if (s->ws.tv_exit == 0 || s->ws.tv_exit == 1) {   // early exit of the TV prox decided on the device: inside the fused launch, or the prox alone first
+    rc = tv_prior_rt(s->prob, s->epsg * s->gamma, A, s->ws, st);
     if (rc < 0) return rc;
     if (rc == 2) return fail(LMC_E_STATE, "the device-side early exit no longer covers this sampler");
     if (rc == 1) { stepped = true; kname = "myula_step_pipe_kernel(per-chain exit)"; }
   }
-  if (s->rtmp && A.prior_kind == LMC_PRIOR_TV_ISO) {   // early-exit TV prox first (exact pass-by-pass path), consumed as a ready-made prox
-    rc = tv_prox_rtol(s->prob, s->epsg * s->gamma, A.x_in, s->pxbuf, s->rtmp, s->robj, s->rflag, s->C, s->tvstate[0], s->tvstate[1], st);
+  if (s->ws.tv_exit == 2) {   // early-exit TV prox first (exact pass-by-pass path), consumed as a ready-made prox
+    rc = tv_prox_rtol(s->prob, s->epsg * s->gamma, A.x_in, s->ws.prox.p, s->C, s->ws, st);
     if (rc) return rc;
     A.prior_kind = LMC_PRIOR_NONE;
-    A.prox_ext = s->pxbuf;
+    A.prox_ext = s->ws.prox.p;
   }
   if (s->prob.prox_scale && A.prior_kind != LMC_PRIOR_NONE) {   // array-valued epsg: prox_{epsg[c,i] gamma g} first, consumed as a ready-made prox
     const Problem& q = s->prob;
     if (A.box)     // the same launch with the clamp
-      HIP_TRY(lmc::launch_box_prox(q.prior_kind, q.eprox_kind, A.x_in, s->pxbuf, s->C, (int64_t)q.H * q.W, q.prox_scale, q.prox_scale_cs, q.prox_scale_ps,
+      HIP_TRY(lmc::launch_box_prox(q.prior_kind, q.eprox_kind, A.x_in, s->ws.prox.p, s->C, (int64_t)q.H * q.W, q.prox_scale, q.prox_scale_cs, q.prox_scale_ps,
                                    s->epsg * s->gamma, q.prior_sigma, q.eprox_p0, q.eprox_p1, q.eprox_mask, A.box_lo, A.box_hi, st));
     else
-    HIP_TRY(lmc::launch_prior_prox_scaled(q.prior_kind, q.eprox_kind, A.x_in, s->pxbuf, s->C, (int64_t)q.H * q.W, q.prox_scale, q.prox_scale_cs, q.prox_scale_ps,
+    HIP_TRY(lmc::launch_prior_prox_scaled(q.prior_kind, q.eprox_kind, A.x_in, s->ws.prox.p, s->C, (int64_t)q.H * q.W, q.prox_scale, q.prox_scale_cs, q.prox_scale_ps,
                                           s->epsg * s->gamma, q.prior_sigma, q.eprox_p0, q.eprox_p1, q.eprox_mask, st));
     A.box = 0;
     A.prior_kind = LMC_PRIOR_NONE;
-    A.prox_ext = s->pxbuf;
+    A.prox_ext = s->ws.prox.p;
   }
   if (stepped) {
     e = hipSuccess;
@@ -513,7 +427,7 @@ static int myula_single(lmc_sampler* s, SideMoments& m, const float* noise, bool
     kname = "myula_step_pipe_kernel(warm)";
     s->wcur ^= 1;
   } else {
-    e = launch_step(A, variant_of(s->prob), st, &kname, s->tvstate[0], s->tvstate[1], s->pxbuf, s->prob.psf.on ? &s->prob.psf : nullptr, &s->prob.wav, s->prob.fft.on ? &s->prob.fft : nullptr);
+    e = launch_step(A, s->prob, s->ws, st, &kname);
   }
   if (e == hipErrorInvalidConfiguration)
     return fail(LMC_E_UNSUPPORTED, s->base.box ? "step_variant %d has no box-constrained form of this prior (TV: auto, 1 tile, 7 / 8 pipe where the pipe covers the problem)"
@@ -543,7 +457,7 @@ static int myula_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, h
   if (s->timing) {  // one event pair per step-kernel launch: moment reductions stay outside the brackets
     while ((int)s->ev.size() < 2 * n_iters) {
       hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
+      HIP_TRY(s->own.event(&e, hipEventDefault));
       s->ev.push_back(e);
     }
   }
@@ -562,7 +476,7 @@ static int myula_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, h
     int prio_least = 0, prio_greatest = 0;     // lowest priority: the step kernel's workgroups go first
     HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
     HIP_TRY(hipStreamCreateWithPriority(&s->side, hipStreamNonBlocking, prio_least));
-    for (hipEvent_t& e : s->side_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (hipEvent_t& e : s->side_ev) HIP_TRY(s->own.event(&e, hipEventDisableTiming));
   }
   SideMoments m{s, st, overlap, bg_wgs};
   for (int k = 0; k < n_iters;) {
@@ -608,22 +522,20 @@ int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   lmc_sampler* s = *out;
   *out = nullptr;
   if (s->tvwarm[0]) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA needs a proposal mean that is a function of x alone: tv_warm is not allowed"); }
-  if (s->rtmp || s->rt_tv.kc) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA with tv_rtol > 0 is not built (use the fixed-count prox, tv_rtol = 0)"); }
+  if (s->ws.tv_exit >= 0) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA with tv_rtol > 0 is not built (use the fixed-count prox, tv_rtol = 0)"); }
   if (s->prob.prox_scale) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA takes a scalar epsg (the reference's array-valued epsg is MYULA's, algs.py:509)"); }
   if (s->prob.psf.on) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_psf(q, "MYMALA", "its Metropolis ratio is pinned for the fused step and its energy by-products, which the three-launch PSF step does not form; use MYULA or SK-ROCK"); }
   if (s->prob.pois) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_poisson(q, "MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK"); }
   if (s->prob.box) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_box(q, "MYMALA", "its target would be +infinity outside the box, where MYULA's proposals land; use MYULA"); }
   if (s->prob.prior_kind == LMC_PRIOR_EPROX) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA does not take a closed-form prior (LMC_PRIOR_EPROX): the prior has a prox and no value g(x), so its Metropolis target exp(-f - epsg g) is undefined; use MYULA"); }
   s->kind = 2;
-  const size_t nbytes = sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W;
-  hipError_t e = hipMalloc(&s->mx, nbytes);
-  if (e == hipSuccess) e = hipMalloc(&s->xp, nbytes);
-  if (e == hipSuccess) e = hipMalloc(&s->mxp, nbytes);
-  if (e == hipSuccess) e = hipMalloc(&s->mala_d, sizeof(double) * 6 * (size_t)s->C);
-  if (e == hipSuccess) e = hipMalloc(&s->flag, sizeof(int) * (size_t)s->C);
-  if (e == hipSuccess) e = hipMalloc(&s->nacc, sizeof(unsigned long long) * (size_t)s->C);
-  if (e == hipSuccess) e = hipMemset(s->nacc, 0, sizeof(unsigned long long) * (size_t)s->C);
-  if (e == hipSuccess) e = hipMemset(s->mala_d, 0, sizeof(double) * 6 * (size_t)s->C);
+  const size_t n = (size_t)s->C * s->prob.H * s->prob.W;
+  hipError_t e = s->own.alloc(&s->mx, n, false);
+  if (e == hipSuccess) e = s->own.alloc(&s->xp, n, false);
+  if (e == hipSuccess) e = s->own.alloc(&s->mxp, n, false);
+  if (e == hipSuccess) e = s->own.alloc(&s->mala_d, 6 * (size_t)s->C, true);
+  if (e == hipSuccess) e = s->own.alloc(&s->flag, (size_t)s->C, false);
+  if (e == hipSuccess) e = s->own.alloc(&s->nacc, (size_t)s->C, true);
   if (e != hipSuccess) return alloc_failed(s, e);
   *out = s;
   return LMC_OK;
@@ -726,13 +638,13 @@ int lmc_skrock_create(const lmc_myula_config* cfg, int32_t n_stages, float eta, 
   *out = nullptr;
   // every stage is a launch of the fused step kernel with coefficients of its own: what MYULA runs outside that launch has no stage form
   if (s->tvwarm[0]) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "SK-ROCK evaluates the drift at s different points per iteration: tv_warm (a dual carried between evaluations) is not allowed"); }
-  if (s->rtmp || s->rt_tv.kc) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "SK-ROCK with tv_rtol > 0 is not built (use the fixed-count prox, tv_rtol = 0)"); }
+  if (s->ws.tv_exit >= 0) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "SK-ROCK with tv_rtol > 0 is not built (use the fixed-count prox, tv_rtol = 0)"); }
   if (s->prob.prox_scale) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "SK-ROCK takes a scalar epsg (array-valued epsg is MYULA's)"); }
   if (s->prob.box) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_box(q, "SK-ROCK", "its stability bound is derived for the unconstrained Moreau-Yosida envelope; use MYULA"); }
   s->kind = 3;
   s->sk_stages = n_stages;
   for (int j = 0; j < n_stages; ++j) { s->sk_mu[j] = mu[j]; s->sk_nu[j] = nu[j]; s->sk_kappa[j] = kappa[j]; }
-  const hipError_t e = hipMalloc(&s->xspare, sizeof(float) * (size_t)s->C * s->prob.H * s->prob.W);   // the third array of the stage rotation
+  const hipError_t e = s->own.alloc(&s->xspare, (size_t)s->C * s->prob.H * s->prob.W, false);   // the third array of the stage rotation
   if (e != hipSuccess) return alloc_failed(s, e);
   *out = s;
   return LMC_OK;
@@ -751,7 +663,7 @@ static int skrock_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, 
     if ((long long)n_iters * ns > (1 << 24)) return fail(LMC_E_INVALID, "too many stage launches to time in one call");
     while (s->ev.size() < (size_t)2 * n_iters * ns) {
       hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
+      HIP_TRY(s->own.event(&e, hipEventDefault));
       s->ev.push_back(e);
     }
   }
@@ -854,9 +766,9 @@ static int ulpda_step(lmc_sampler* s, int32_t n_iters, const float* noise_dev, h
       HIP_TRY(lmc::ulpda_ncvx_rhs(s->ctmp, htb_nc, s->rhs, C, H, W, s->tau * s->prob.ncvx_lambda, s->prob.ncvx_gamma, ts_nc, st));
     } else if (s->prob.ncvx_kind == LMC_NCVX_ME_TV) {   // x += tau*lamda/gamma (x - prox_{gamma TV}(x))  (algs.py:221-223)
       HIP_TRY(lmc::ulpda_rhs(x, s->ydual, s->z, nullptr, s->ctmp, C, H, W, s->tau, ts, st));
-      int rc = me_tv_prox(s->prob, s->ctmp, s->extra, C, s->tvstate[0], s->tvstate[1], st, &s->rt_me);
+      int rc = me_tv_prox(s->prob, s->ctmp, C, s->ws, st);
       if (rc) return rc;
-      HIP_TRY(lmc::ulpda_me_rhs(s->ctmp, s->extra, htb_nc, s->rhs, C, H, W, s->tau * s->prob.ncvx_lambda / s->prob.ncvx_gamma, ts_nc, st));
+      HIP_TRY(lmc::ulpda_me_rhs(s->ctmp, s->ws.extra.p, htb_nc, s->rhs, C, H, W, s->tau * s->prob.ncvx_lambda / s->prob.ncvx_gamma, ts_nc, st));
     } else {
       HIP_TRY(lmc::ulpda_rhs(x, s->ydual, s->z, s->prob.data_kind == LMC_DATA_BLUR ? s->htb : nullptr, s->rhs, C, H, W, s->tau, ts, st));
     }
@@ -935,21 +847,21 @@ int lmc_ulpda_create(const lmc_ulpda_config* cfg, lmc_sampler** out) {
   s->base.chain_offset = (uint32_t)s->chain_offset;
   const size_t n = (size_t)s->C * s->prob.H * s->prob.W, img = (size_t)s->prob.H * s->prob.W;
   hipError_t e = hipSuccess;
-  auto alloc = [&](float** p, size_t count) { if (e == hipSuccess) e = hipMalloc(p, sizeof(float) * count); if (e == hipSuccess) e = hipMemset(*p, 0, sizeof(float) * count); };
+  auto alloc = [&](float** p, size_t count) { if (e == hipSuccess) e = s->own.alloc(p, count, true); };
   alloc(&s->x[0], n); alloc(&s->xhat, n); alloc(&s->ydual, 2 * n); alloc(&s->uw, n); alloc(&s->rhs, n);
   if (s->noise_mode == LMC_NOISE_PHILOX) alloc(&s->xi, n);
   if (s->prob.data_kind == LMC_DATA_BLUR) {
     alloc(&s->cr, n); alloc(&s->cp, n); alloc(&s->cq, n); alloc(&s->ctmp, n); alloc(&s->htb, img); alloc(&s->zero_y, img);
     if (lmc::cheb_pair_supported(s->prob.H, s->prob.W, s->prob.taps)) alloc(&s->uw2, n);
-    if (e == hipSuccess) e = hipMalloc(&s->scal, sizeof(double) * (4 * (size_t)s->C + 1));
+    if (e == hipSuccess) e = s->own.alloc(&s->scal, 4 * (size_t)s->C + 1, false);
     if (e == hipSuccess) e = lmc::launch_blur(s->prob.y, s->htb, 1, s->prob.H, s->prob.W, s->prob.taps, 1, nullptr);   // H^T b
     if (e == hipSuccess) e = hipDeviceSynchronize();
   }
   if (s->prob.ncvx_kind != LMC_NCVX_NONE && !s->ctmp) alloc(&s->ctmp, n);      // pointwise data terms: the pre-step of L2_ncvx_tv.prox needs its own array
-  if (s->prob.ncvx_kind == LMC_NCVX_ME_TV) {
-    alloc(&s->extra, n);
-    if (needs_tv_state(s->prob)) { alloc(&s->tvstate[0], 4 * n); alloc(&s->tvstate[1], 4 * n); }
-    if (e == hipSuccess && s->prob.ncvx_rtol > 0.f) e = s->rt_me.need((size_t)s->C, s->prob.ncvx_niter);     // early exit of the inner prox, decided on the device
+  if (e == hipSuccess) {     // the inner prox of the ME-TV term (the pre-step adds it with weight tau) and the energies
+    lmc::StepArgs probe{};
+    probe.t = s->tau;
+    e = prepare(s->ws, s->prob, probe, s->C, 0.f, kForStep | kForEnergies, nullptr);
   }
   if (e == hipSuccess) e = alloc_moments(s);
   if (e != hipSuccess) return alloc_failed(s, e);
@@ -1027,7 +939,7 @@ const char* lmc_sampler_kernel_name(const lmc_sampler* s) { return s ? s->kernel
 int lmc_sampler_tv_exit_stats(lmc_sampler* s, int32_t which, int32_t* passes_dev, uint64_t* reruns_host, void* stream) {
   if (!s || (which != 0 && which != 1)) return fail(LMC_E_INVALID, "bad arguments");
   DeviceGuard dg(s->device);
-  RtState& rt = which == 0 ? s->rt_tv : s->rt_me;
+  RtState& rt = which == 0 ? s->ws.rt_tv : s->ws.rt_me;
   if (!rt.kc) return fail(LMC_E_STATE, "this sampler does not run the device-side early exit for that prox (tv_rtol / ncvx_rtol = 0, or the pass-by-pass path)");
   hipStream_t st = S(stream);
   if (passes_dev) HIP_TRY(hipMemcpyAsync(passes_dev, rt.pred, sizeof(int) * (size_t)s->C, hipMemcpyDeviceToDevice, st));

@@ -263,20 +263,19 @@ lmc::SapgParams sapg_params(const lmc_sapg_config& c, double d, double k) {
 // the buffers of lmc_sampler_sapg in the handle: statistic + partial sums, device traces, the mapped pair, the event
 int sapg_buffers(lmc_sampler* s, int n_updates) {
   const size_t C = (size_t)s->C;
-  if (!s->sapg_stat) HIP_TRY(hipMalloc(&s->sapg_stat, sizeof(double) * C * (1 + (size_t)lmc::prior_stat_segments(s->C, s->prob.H))));
+  if (!s->sapg_stat) HIP_TRY(s->own.alloc(&s->sapg_stat, C * (1 + (size_t)lmc::prior_stat_segments(s->C, s->prob.H)), false));
   const size_t need = 2 * (size_t)n_updates + 1;
   if (s->sapg_trace_n < need) {
-    if (s->sapg_trace) HIP_TRY(hipFree(s->sapg_trace));
-    s->sapg_trace = nullptr;
+    s->own.drop(s->sapg_trace);
     s->sapg_trace_n = 0;
-    HIP_TRY(hipMalloc(&s->sapg_trace, sizeof(double) * need));
+    HIP_TRY(s->own.alloc(&s->sapg_trace, need, false));
     s->sapg_trace_n = need;
   }
   if (!s->sapg_host) {
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->sapg_host), 2 * sizeof(double), hipHostMallocMapped));
+    HIP_TRY(s->own.pinned(&s->sapg_host, 2, hipHostMallocMapped));
     HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->sapg_host_dev), s->sapg_host, 0));
   }
-  if (!s->sapg_ev) HIP_TRY(hipEventCreateWithFlags(&s->sapg_ev, hipEventDisableTiming));
+  if (!s->sapg_ev) HIP_TRY(s->own.event(&s->sapg_ev, hipEventDisableTiming));
   return LMC_OK;
 }
 
@@ -331,17 +330,18 @@ int lmc_prior_statistic(const lmc_problem* prob, const float* x_dev, int64_t n_i
   if (rc) return rc;
   if (!x_dev || !stat_dev || n_img < 1) return fail(LMC_E_INVALID, "bad arguments");
   if (prob->prior_kind == LMC_PRIOR_WAVELET_L1) {
-    Scratch& sc = scratch_here();
-    HIP_TRY(sc.need_wav(lmc::wavelet_ws_floats(n_img, prob->H, prob->W), (size_t)n_img * lmc::wavelet_partials(prob->H, prob->W, prob->tv_niter)));
-    HIP_TRY(lmc::launch_wavelet_value(x_dev, n_img, prob->H, prob->W, prob->eprox_kind, prob->tv_niter, 1.f, sc.wav, sc.wav_part, stat_dev, S(stream)));
+    Workspace& sc = scratch_here();
+    HIP_TRY(sc.wav.need(lmc::wavelet_ws_floats(n_img, prob->H, prob->W)));
+    HIP_TRY(sc.wav_part.need((size_t)n_img * lmc::wavelet_partials(prob->H, prob->W, prob->tv_niter)));
+    HIP_TRY(lmc::launch_wavelet_value(x_dev, n_img, prob->H, prob->W, prob->eprox_kind, prob->tv_niter, 1.f, sc.wav.p, sc.wav_part.p, stat_dev, S(stream)));
     return LMC_OK;
   }
   double* part = nullptr;
   const int nseg = lmc::prior_stat_segments(n_img, prob->H);
   if (nseg > 1) {
-    Scratch& sc = scratch_here();
-    HIP_TRY(sc.need_dbl((size_t)n_img * nseg));
-    part = sc.dbl;
+    Workspace& sc = scratch_here();
+    HIP_TRY(sc.dbl.need((size_t)n_img * nseg));
+    part = sc.dbl.p;
   }
   HIP_TRY(lmc::launch_prior_stat(x_dev, n_img, prob->H, prob->W, prob->prior_kind, stat_dev, part, S(stream)));
   return LMC_OK;

@@ -184,7 +184,8 @@ int cg_solve_fused(const Problem& q, float ts, float* u, const float* rhs, float
   A.a = 1.f; A.t = -ts / q.sigma_f; A.b = 0.f; A.s = 0.f;
   A.noise_mode = LMC_NOISE_NONE;
   const char* kname = nullptr;
-  auto apply = [&](const float* in, float* out) -> hipError_t { A.x_in = in; A.x_out = out; return launch_step(A, variant_of(q), st, &kname); };
+  Workspace none;      // (a blur without a prior: the launch takes no work buffer)
+  auto apply = [&](const float* in, float* out) -> hipError_t { A.x_in = in; A.x_out = out; return launch_step(A, q, none, st, &kname); };
   HIP_TRY(hipMemsetAsync(scal, 0, sizeof(double) * (4 * C + 1), st));
   HIP_TRY(apply(u, qq));
   A.dot_out = pq;            // the row-streaming kernel accumulates p.Ap while it writes Ap (one pass less per iteration)
