@@ -139,7 +139,32 @@ typedef enum lmc_data_kind {
    * lmc_sampler_energies and lmc_l2_prox (the closed form above: niter, warm and the workspace are ignored).  Every prior and box LMC_DATA_NONE takes.
    * A sampler handle owns the spectrum buffer and the twiddle table; the stateless calls take theirs from scratch.  LMC_E_UNSUPPORTED, with the reason
    * in lmc_last_error: lmc_mymala_create, lmc_ulpda_create, ncvx_kind != NONE, tv_rtol > 0, tv_warm.  iterations_per_launch is ignored. */
-  LMC_DATA_SPECTRAL = 12
+  LMC_DATA_SPECTRAL = 12,
+  /* Huber data term: robust deconvolution with outliers at unknown positions -- impulse noise, cosmic rays, hot or saturated pixels (appended;
+   * LMC_ATOMI_ABI_VERSION stays 4 and sizeof(lmc_problem) 200).  Build-specified (the reference has no such term); this text is its definition.
+   * Operator fields as for kinds 1 (13), 2 (14) and 9 (15); y_dev points to [2][H][W] floats: plane 0 the observation y, plane 1 the thresholds
+   * delta in [0, +inf].  Preconditions, not checked on the device: delta >= 0 and not NaN, y finite.  With u = (Op x)_p and r = u - y_p:
+   *   h_delta(r) = r^2 / 2 for |r| <= delta,  delta (|r| - delta / 2) otherwise           psi_delta(r) = h_delta'(r) = clamp(r, -delta, delta)
+   *   f(x) = sigma_f sum_p h_delta_p(r_p)
+   *   grad f(x) = sigma_f Op^T psi_delta(Op x - y)
+   *   L_f = sigma_f ||Op||^2     (psi is 1-Lipschitz: the bound of the plain term; ||Op|| <= sum |h| for a blur, 1 for the identity)
+   * The clamp acts on the residual BEFORE the adjoint.  delta_p = +inf is the plain Gaussian term of kinds 1, 2 and 9 at that pixel; delta_p = 0 is an
+   * unobserved pixel, so a binary mask on a blur is delta = 0 there: there is no Huber mask kind, and mask_dev must be NULL with these kinds
+   * (LMC_E_INVALID otherwise: a mask would be silently ignored).  f is convex and C^1, so the Metropolis target of MYMALA is defined.
+   * Honoured by lmc_myula_create and lmc_skrock_create with all of lmc_sampler_* (lmc_sampler_sapg included), lmc_fused_eval, lmc_energies and
+   * lmc_sampler_energies -- all three kinds (r in fp32, its branch value widened to and summed in float64; every width) -- and by lmc_mymala_create for
+   * kinds 13 and 14, with f and g of the target from the separate energy launch (the Huber pipe kernels form no by-products); kind 15 is refused there
+   * like every large PSF.  Priors and box_enable exactly as for the weighted Gaussian term (kinds 7, 8; kind 11 for 15).  Kernels, kinds 13 and 14: the
+   * full-width pipeline (myula_step_pipe_hub_kernel, myula_step_pipe_hub_box_kernel; one team) for the isotropic TV prior with exactly 10 dual
+   * iterations after tv_lagged_output, W > 128, a separable blur of 5 or 7 taps or the identity; the LDS-tiled kernel (myula_step_tile_hub_kernel,
+   * myula_step_tile_hub_box_kernel) for everything else -- every prior, width and blur.  Kind 15: the three launches of LMC_DATA_PSF with
+   * r = psi_delta(H x - y) in the first.  One iteration per launch (iterations_per_launch is ignored).  LMC_E_UNSUPPORTED, with the reason in
+   * lmc_last_error: lmc_ulpda_create, lmc_l2_prox (no implicit step of the Huber loss under an operator is built), ncvx_kind != NONE, tv_rtol > 0,
+   * tv_warm, and for kinds 13 and 14 LMC_PRIOR_HAAR_L1, a forced step_variant other than 0, 1 and 7; 7 on a problem the pipeline does not cover (from the
+   * create functions, and from lmc_fused_eval).  Not built: Student-t / Cauchy losses, a weighted Huber term, chained and two-team pipe forms. */
+  LMC_DATA_HUBER_IDENTITY = 13,
+  LMC_DATA_HUBER_BLUR = 14,
+  LMC_DATA_HUBER_PSF = 15
 } lmc_data_kind;
 
 /* prior g whose prox enters the MYULA update (algs.py:569) */
@@ -222,7 +247,7 @@ typedef struct lmc_problem {
   /* data term */
   int32_t data_kind;        /* lmc_data_kind */
   float sigma_f;            /* multiplies the L2 term: 1/sigma^2 at prox_lmc_deconv.py:101 */
-  /* Large PSF: read with LMC_DATA_PSF / POISSON_PSF / WL2_PSF only.  The kernel's size, 1 .. LMC_MAX_PSF each, and its origin (pylops `offset`) inside it;
+  /* Large PSF: read with LMC_DATA_PSF / POISSON_PSF / WL2_PSF / HUBER_PSF only.  The kernel's size, 1 .. LMC_MAX_PSF each, and its origin (pylops `offset`) inside it;
    * the psf_kh * psf_kw taps, row-major, are at h_host (copied by the callee).  Bad geometry: LMC_E_INVALID.  The four bytes fill the alignment hole in
    * front of y_dev and psf_separable (below) the one in front of prox_scale: no field moves and sizeof(lmc_problem) stays 200, so LMC_ATOMI_ABI_VERSION
    * stays 4 and a caller built against the earlier header is unaffected (it never sets these kinds). */
@@ -497,7 +522,8 @@ void lmc_sampler_destroy(lmc_sampler* s);
  * counted again by the moment accumulators (the reference's toy version drops rejected iterations from its output list).
  * All lmc_sampler_* calls apply.  LMC_E_UNSUPPORTED, with the reason in lmc_last_error: tv_warm, tv_rtol > 0, prox_scale, a Poisson data
  * term, a box constraint, and LMC_PRIOR_EPROX (a prior with a prox and no value: the target is undefined).  The weighted Gaussian data term
- * (LMC_DATA_WL2_*) is taken: it is quadratic and smooth, and f and g of the target then come from the separate energy launch. */
+ * (LMC_DATA_WL2_*) is taken: it is quadratic and smooth, and f and g of the target then come from the separate energy launch.  So is the Huber data
+ * term on the small operators (LMC_DATA_HUBER_IDENTITY, LMC_DATA_HUBER_BLUR: convex and C^1), in the same way. */
 int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out);
 /* accepted_dev [n_chains] uint64: accepted proposals so far; last_log_alpha_dev [n_chains] f64 (nullable): log acceptance
  * ratio of the latest iteration.  Device buffers. */

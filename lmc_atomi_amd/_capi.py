@@ -19,12 +19,14 @@ DATA_POISSON_IDENTITY, DATA_POISSON_BLUR, DATA_POISSON_MASK = 4, 5, 6      # y_d
 POISSON_KINDS = (DATA_POISSON_IDENTITY, DATA_POISSON_BLUR, DATA_POISSON_MASK)
 DATA_WL2_IDENTITY, DATA_WL2_BLUR = 7, 8      # y_dev: [2][H][W], the observation then the per-pixel weights
 DATA_PSF, DATA_POISSON_PSF, DATA_WL2_PSF = 9, 10, 11      # the large PSF (psf_* fields): Gaussian, Poisson, weighted Gaussian term
-PSF_KINDS = (DATA_PSF, DATA_POISSON_PSF, DATA_WL2_PSF)
+DATA_HUBER_IDENTITY, DATA_HUBER_BLUR, DATA_HUBER_PSF = 13, 14, 15      # the Huber data term; y_dev: [2][H][W], the observation then the thresholds delta
+HUBER_KINDS = (DATA_HUBER_IDENTITY, DATA_HUBER_BLUR, DATA_HUBER_PSF)
+PSF_KINDS = (DATA_PSF, DATA_POISSON_PSF, DATA_WL2_PSF, DATA_HUBER_PSF)
 WL2_KINDS = (DATA_WL2_IDENTITY, DATA_WL2_BLUR)
 DATA_SPECTRAL = 12      # the Fourier-domain data term: y_dev is [11][H][W / 2 + 1], the planes of lmc_spectral_tables
 SPECTRAL_PLANES = 11
 FFT_MIN, FFT_MAX = 8, 1024      # sides of the transforms: powers of two in this range
-TWO_PLANE_KINDS = POISSON_KINDS + WL2_KINDS + (DATA_POISSON_PSF, DATA_WL2_PSF)      # y_dev is [2][H][W]
+TWO_PLANE_KINDS = POISSON_KINDS + WL2_KINDS + (DATA_POISSON_PSF, DATA_WL2_PSF) + HUBER_KINDS      # y_dev is [2][H][W]
 PRIOR_NONE, PRIOR_L2, PRIOR_L1, PRIOR_TV_ISO, PRIOR_TV_ANISO, PRIOR_HAAR_L1, PRIOR_EPROX = 0, 1, 2, 3, 4, 5, 6
 PRIOR_WAVELET_L1 = 7      # Daubechies wavelet-l1: lmc_problem.tv_niter = levels, eprox_kind = p (the struct has no hole left)
 NOISE_PHILOX, NOISE_INJECTED, NOISE_NONE = 0, 1, 2

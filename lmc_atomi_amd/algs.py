@@ -88,8 +88,29 @@ def _refuse_wl2(data, prior, opts, who=None):
                                   "(where it covers the problem)")
 
 
+def _refuse_hub(data, prior, opts, who=None):
+    """The same for the Huber data term (``HuberLoss``, ``LMC_DATA_HUBER_*``); on a large PSF the rest of the list is :func:`_refuse_psf`'s."""
+    if data.get("data_kind") not in _capi.HUBER_KINDS:
+        return
+    if who is not None:
+        raise NotImplementedError(f"{who[0]} does not take the Huber data term (HuberLoss): {who[1]}")
+    if data.get("data_kind") == _capi.DATA_HUBER_PSF:
+        return
+    if prior.get("prior_kind") == _capi.PRIOR_HAAR_L1:
+        raise NotImplementedError("the Huber data term with the Haar-l1 prior (WaveletL1) is not built")
+    if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
+        raise NotImplementedError("the Huber data term runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
+    if prior.get("tv_warm") or opts.get("tv_warm"):
+        raise NotImplementedError("the Huber data term has no warm-started TV dual: warm / tv_warm must be off")
+    v = opts.get("step_variant", 0) or 0
+    v = _capi.VARIANTS.index(v) if isinstance(v, str) else int(v)
+    if v not in (0, 1, 7):
+        raise NotImplementedError(f"step-kernel variant {_capi.VARIANTS[v]!r} has no form of the Huber data term: 'auto', 'tile' or 'pipe' "
+                                  "(where it covers the problem)")
+
+
 def _refuse_psf(data, prior, opts, who=None):
-    """The same for a large PSF (``Op = PSF(...)``, ``LMC_DATA_PSF`` / ``POISSON_PSF`` / ``WL2_PSF``)."""
+    """The same for a large PSF (``Op = PSF(...)``, ``LMC_DATA_PSF`` / ``POISSON_PSF`` / ``WL2_PSF`` / ``HUBER_PSF``)."""
     if data.get("data_kind") not in _capi.PSF_KINDS:
         return
     if who is not None:
@@ -327,6 +348,7 @@ class MYULASampler:
             epsg = 1.0
         _refuse_poisson(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._poisson_refusal)
         _refuse_wl2(_data_descriptor(proxf), _prior_descriptor(proxg), opts)
+        _refuse_hub(_data_descriptor(proxf), _prior_descriptor(proxg), opts)
         _refuse_psf(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._psf_refusal)
         _refuse_spectral(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._spectral_refusal)
         self._problem = _Problem(self.dims, _data_descriptor(proxf), _prior_descriptor(proxg), self.device, options=opts)
@@ -347,7 +369,7 @@ class MYULASampler:
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             rc = self._create(cfg)
-        if rc == -2 and self._problem.c.data_kind in _capi.POISSON_KINDS + _capi.WL2_KINDS + _capi.PSF_KINDS + (_capi.DATA_SPECTRAL,):      # (no handle exists: e.g. variant='pipe' on a problem the pipeline does not cover)
+        if rc == -2 and self._problem.c.data_kind in _capi.POISSON_KINDS + _capi.WL2_KINDS + _capi.HUBER_KINDS + _capi.PSF_KINDS + (_capi.DATA_SPECTRAL,):      # (no handle exists: e.g. variant='pipe' on a problem the pipeline does not cover)
             raise NotImplementedError(_dev.lib().lmc_last_error().decode())
         _capi.check(rc)
         self._attach_accumulators(acc)
@@ -641,6 +663,7 @@ class ULPDASampler(MYULASampler):
             raise NotImplementedError("ULPDA does not take a prior with bounds: its prior enters through the dual ball of g o A, which has no box form; use MYULA")
         _refuse_poisson(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA"))
         _refuse_wl2(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, (I + tau sigma Op^T W Op)^{-1}, which is not built; use MYULA"))
+        _refuse_hub(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which is not built for the Huber loss under an operator; use MYULA"))
         _refuse_spectral(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal-dual loop is not wired to the closed-form implicit step of this term; use MYULA"))
         _refuse_psf(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which is not built for a large PSF; use MYULA"))
         if isinstance(proxg, L21):

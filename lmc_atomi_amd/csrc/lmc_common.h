@@ -83,6 +83,9 @@ struct StepArgs {
   // chebyshev_solve): dot_out[2c] += sum (x_out - x_in)^2, dot_out[2c+1] += sum prox_ext^2.  run_count / run_index: the launch returns at
   // once when *run_count <= run_index (the iterations a warm-started solve turned out not to need).
   int dot_mode;
+  uint32_t hub;              // host side only, like wl2 (the Huber kernels are instantiations of their own): the data term is the Huber loss of the residual,
+                             // sigma_f sum_p h_delta_p(u_p - y_p) (LMC_DATA_HUBER_*, lmc_atomi.h) -- data_kind stays the operator's kind (identity, blur),
+                             // y is [2][H][W]: the observation, then the thresholds delta at y + H W.  It sits in the 4-byte hole behind dot_mode (the asserts below)
   const int* run_count;
   int run_index;
   // pipe kernel only: energies of x_in as by-products of the update (MYMALA): f_out[c] += sigma_f/2 ||H x - y||^2 (the residual rows
@@ -121,6 +124,8 @@ static_assert(offsetof(StepArgs, pois) == offsetof(StepArgs, chain_offset) + 4 &
               "pois fills the hole behind chain_offset");
 static_assert(offsetof(StepArgs, wl2) == offsetof(StepArgs, extra_coef) + 4 && offsetof(StepArgs, dot_out) == offsetof(StepArgs, extra_coef) + 8,
               "wl2 fills the hole behind extra_coef");
+static_assert(offsetof(StepArgs, hub) == offsetof(StepArgs, dot_mode) + 4 && offsetof(StepArgs, run_count) == offsetof(StepArgs, dot_mode) + 8,
+              "hub fills the hole behind dot_mode");
 static_assert(offsetof(StepArgs, box_hi) == offsetof(StepArgs, fused_iters) + 4 && offsetof(StepArgs, x_mid) == offsetof(StepArgs, fused_iters) + 8,
               "box_hi fills the hole behind fused_iters");
 

@@ -137,6 +137,17 @@ __device__ __forceinline__ double pois_phi(float u, float y, float beta) {
   return kl + (1.0 - yd / bd) * ud + yd * ud * ud / (2.0 * bd * bd);
 }
 
+// ---- Huber data term (LMC_DATA_HUBER_*; definition: lmc_atomi.h) ------------------------------------------------------
+// psi_delta(r) = clamp(r, -delta, delta) at the residual r = (Op x)_p - y_p with the threshold delta in [0, +inf]: one v_med3_f32.  Exact in fp32
+// (it returns one of its operands); delta = +inf passes r through, delta = 0 gives 0; finite whenever r is.
+__device__ __forceinline__ float hub_psi(float r, float delta) { return __builtin_amdgcn_fmed3f(r, -delta, delta); }
+// h_delta(r) in float64 from the fp32 operands (the energies): r^2 / 2 for |r| <= delta, delta (|r| - delta / 2) beyond.  delta = +inf takes the
+// quadratic branch (no inf * 0 is formed), delta = 0 the linear one, which gives 0.
+__device__ __forceinline__ double hub_h(float r, float delta) {
+  const double a = fabs((double)r), d = (double)delta;
+  return a <= d ? 0.5 * a * a : d * (a - 0.5 * d);
+}
+
 // ---- shared by the streaming step kernels ---------------------------------------------------------
 constexpr int kPad = 8;  // zero columns on both sides of LDS rows (>= kMaxBlur - 1)
 #ifdef LMC_BOUNDS_CHECK   // debug build: out-of-range global accesses are recorded and skipped, never issued

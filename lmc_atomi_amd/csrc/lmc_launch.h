@@ -66,6 +66,9 @@ hipError_t launch_energy_pois(const float* x, int64_t n_img, const EnergyArgs& E
 // ADDS the weighted Gaussian data term's value to f_out (zeroed by launch_energies): E.data_kind = the operator's kind (identity, blur), E.y = [2][H][W]
 // observation, weights
 hipError_t launch_energy_wl2(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, hipStream_t st);
+// ADDS the Huber data term's value to f_out (zeroed by launch_energies): E.data_kind = the operator's kind (identity, blur), E.y = [2][H][W]
+// observation, thresholds
+hipError_t launch_energy_hub(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, hipStream_t st);
 // pieces of the exact early-exit path of the TV prox (lmc_problem.tv_rtol > 0)
 hipError_t launch_tv_objective(const float* x, const float* sol, int64_t n, int H, int W, float gam, const int* flag, double* obj, hipStream_t st);
 hipError_t launch_tv_rtol_decide(int64_t n, double* prev, double* cur, int* flag, int pass, double rtol, int* n_active, hipStream_t st);
@@ -206,7 +209,10 @@ enum PsfEpi {
   kPsfOverwrite,    // out = a xin - coef u
   kPsfEnL2,         // part[image][tile] = sum 1/2 (u - y)^2        (no store of u)
   kPsfEnWl2,        // part[image][tile] = sum 1/2 w (u - y)^2
-  kPsfEnPois        // part[image][tile] = sum pois_phi(u, y, beta)
+  kPsfEnPois,       // part[image][tile] = sum pois_phi(u, y, beta)
+  // (appended: the values above are template arguments of kernels that keep their names)
+  kPsfRhoHub,       // out = clamp(u - y, -delta, delta),  y = [2][H][W]: observation, thresholds (the Huber term)
+  kPsfEnHub         // part[image][tile] = sum hub_h(u - y, delta)
 };
 // Host description of a validated PSF and the device table made from it.  tab (host) / tab_dev: [2][kPsfMax * kPsfKP] floats, direction 0 = H (taps
 // flipped, origin mirrored), 1 = H^T, each in the correlation form of the kernel: general g[b * kPsfKP + a], separable gu[kPsfKP] then gv[kPsfKP].
@@ -223,12 +229,12 @@ int psf_separable(const float* h, int kh, int kw, float* u, float* v);
 // fills kh .. separable and tab from validated geometry; mode: lmc_problem.psf_separable (0 auto, 1 require, 2 forbid).  false: mode 1 on a kernel that
 // fails the criterion
 bool psf_prepare(PsfOp& P, const float* h, int kh, int kw, int oy, int ox, int mode);
-// epi: PsfEpi of lmc_psf_kernel.h, store forms only.  out = epilogue(H x or H^T x); xin: kPsfOverwrite; y: the rho forms
+// epi: PsfEpi, store forms only (kPsfRaw .. kPsfOverwrite, kPsfRhoHub).  out = epilogue(H x or H^T x); xin: kPsfOverwrite; y: the rho forms
 hipError_t launch_psf(const PsfOp& P, int adjoint, int epi, const float* x, float* out, const float* xin, const float* y, int64_t n_img, int H, int W,
                       float a, float coef, hipStream_t st);
 // doubles `part` must hold for launch_psf_energy
 size_t psf_energy_partials(int64_t n_img, int H, int W);
-// f_out[c] += the data term's value at x_c (term: 0 Gaussian, 1 weighted, 2 Poisson), float64 by partial sums in a fixed order
+// f_out[c] += the data term's value at x_c (term: 0 Gaussian, 1 weighted, 2 Poisson, 3 Huber), float64 by partial sums in a fixed order
 hipError_t launch_psf_energy(const PsfOp& P, int term, const float* x, const float* y, int64_t n_img, int H, int W, float sigma_f, double* part,
                              double* f_out, hipStream_t st);
 }  // namespace lmc

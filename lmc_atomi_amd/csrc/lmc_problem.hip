@@ -54,9 +54,16 @@ int load_problem(const lmc_problem* p, Problem& q) {
     q.data_kind = p->data_kind == LMC_DATA_WL2_BLUR ? LMC_DATA_BLUR : LMC_DATA_IDENTITY;
     q.wl2 = 1;
   }
-  // a large PSF: one operator kind of its own plus the same two flags (check_step_problem, check_no_psf) -- NOT LMC_DATA_BLUR, whose taps stay empty: a path
+  // the Huber loss of the residual: the same arrangement again (check_no_hub, check_step_problem); 13, 14: the small operators, 15: the large PSF below
+  if (p->data_kind >= LMC_DATA_HUBER_IDENTITY && p->data_kind <= LMC_DATA_HUBER_PSF) {
+    // there is no Huber mask kind either: delta = 0 is the unobserved pixel
+    if (p->mask_dev) return fail(LMC_E_INVALID, "data_kind %d (Huber data term) takes no mask_dev: there is no Huber mask kind, put the mask into the thresholds (delta = 0)", p->data_kind);
+    if (p->data_kind != LMC_DATA_HUBER_PSF) q.data_kind = p->data_kind == LMC_DATA_HUBER_BLUR ? LMC_DATA_BLUR : LMC_DATA_IDENTITY;
+    q.hub = 1;
+  }
+  // a large PSF: one operator kind of its own plus the same flags (check_step_problem, check_no_psf) -- NOT LMC_DATA_BLUR, whose taps stay empty: a path
   // that was not taught about the PSF meets an unknown data kind, not a blur without taps
-  if (p->data_kind >= LMC_DATA_PSF && p->data_kind <= LMC_DATA_WL2_PSF) {
+  if ((p->data_kind >= LMC_DATA_PSF && p->data_kind <= LMC_DATA_WL2_PSF) || p->data_kind == LMC_DATA_HUBER_PSF) {
     if (p->kh || p->kw || p->oy || p->ox) return fail(LMC_E_INVALID, "data_kind %d (large PSF) takes its geometry in the psf_* fields: kh = kw = oy = ox = 0", p->data_kind);
     if (p->data_kind == LMC_DATA_WL2_PSF && p->mask_dev) return fail(LMC_E_INVALID, "data_kind %d (weighted Gaussian term) takes no mask_dev: put the mask into the weights", p->data_kind);
     q.data_kind = LMC_DATA_PSF;
@@ -226,10 +233,16 @@ int check_no_wl2(const Problem& q, const char* who, const char* why) {
   return fail(LMC_E_UNSUPPORTED, "%s does not take the weighted Gaussian data term (LMC_DATA_WL2_*): %s", who, why);
 }
 
+// The entry points that have no form of the Huber data term refuse a problem that carries one.
+int check_no_hub(const Problem& q, const char* who, const char* why) {
+  if (!q.hub) return LMC_OK;
+  return fail(LMC_E_UNSUPPORTED, "%s does not take the Huber data term (LMC_DATA_HUBER_*): %s", who, why);
+}
+
 // The entry points that have no form of the large PSF refuse a problem that carries one.
 int check_no_psf(const Problem& q, const char* who, const char* why) {
   if (!q.psf.on) return LMC_OK;
-  return fail(LMC_E_UNSUPPORTED, "%s does not take a large PSF (LMC_DATA_PSF, LMC_DATA_POISSON_PSF, LMC_DATA_WL2_PSF): %s", who, why);
+  return fail(LMC_E_UNSUPPORTED, "%s does not take a large PSF (LMC_DATA_PSF, LMC_DATA_POISSON_PSF, LMC_DATA_WL2_PSF, LMC_DATA_HUBER_PSF): %s", who, why);
 }
 
 // The entry points that have no form of the spectral data term refuse a problem that carries one.
@@ -242,11 +255,13 @@ int check_no_spectral(const Problem& q, const char* who, const char* why) {
 // for it, and whether its step is a fused kernel of the term (the tiled kernel's and the full-width pipeline's instantiations: no Haar prior, variants
 // 0, 1, 7) or splits into the term's launches around the step of a problem without a data term (every prior and variant of that problem).
 struct DataTermRules { const char *name, *warm; bool own_kernels; };
-constexpr DataTermRules kDataTerms[4] = {{"the Poisson data term", "has no Poisson form", true},
+constexpr int kNDataTerms = 5;
+constexpr DataTermRules kDataTerms[kNDataTerms] = {{"the Poisson data term", "has no Poisson form", true},
                                          {"the weighted Gaussian data term", "has no weighted form", true},
+                                         {"the Huber data term", "has no Huber form", true},
                                          {"a large PSF", "is not built for it", false},
                                          {"the spectral data term", "is not built for it", false}};
-#define LMC_DATA_TERMS_OF(q) {(q).pois != 0, (q).wl2 != 0, (q).psf.on != 0, (q).fft.on != 0}
+#define LMC_DATA_TERMS_OF(q) {(q).pois != 0, (q).wl2 != 0, (q).hub != 0, (q).psf.on != 0, (q).fft.on != 0}
 
 static int check_convex_term(const Problem& q, const DataTermRules& r) {
   if (q.ncvx_kind == LMC_NCVX_NONE) return LMC_OK;
@@ -254,8 +269,8 @@ static int check_convex_term(const Problem& q, const DataTermRules& r) {
 }
 
 int check_convex_terms(const Problem& q) {
-  const bool has[4] = LMC_DATA_TERMS_OF(q);
-  for (int i = 0; i < 4; ++i)
+  const bool has[kNDataTerms] = LMC_DATA_TERMS_OF(q);
+  for (int i = 0; i < kNDataTerms; ++i)
     if (has[i]) { const int rc = check_convex_term(q, kDataTerms[i]); if (rc) return rc; }
   return LMC_OK;
 }
@@ -268,11 +283,11 @@ int check_step_problem(const Problem& q, float b) {
     if (b != 0.f && q.tv_niter_asked < 1)
       return fail(LMC_E_INVALID, "LMC_PRIOR_TV_ANISO: the prox needs tv_niter in 1..%d (got 0)", lmc::kMaxTvIters);
   }
-  const bool has[4] = LMC_DATA_TERMS_OF(q);
+  const bool has[kNDataTerms] = LMC_DATA_TERMS_OF(q);
   const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < kNDataTerms; ++i) {
     const DataTermRules& r = kDataTerms[i];
-    if (!has[i] || (r.own_kernels && q.psf.on)) continue;     // (Poisson / weighted on a large PSF: the PSF's rules -- its step launch has no data term)
+    if (!has[i] || (r.own_kernels && q.psf.on)) continue;     // (Poisson / weighted / Huber on a large PSF: the PSF's rules -- its step launch has no data term)
     const int rc = check_convex_term(q, r);
     if (rc) return rc;
     if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "%s with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0", r.name);
@@ -293,6 +308,7 @@ int make_step_args(const Problem& q, float a, float t, float b, float pt, float 
   A.data_kind = (t == 0.f) ? LMC_DATA_NONE : q.data_kind;   // skip the stencil work if its weight is zero
   A.pois = (q.pois && A.data_kind != LMC_DATA_NONE) ? 1 : 0;
   A.wl2 = (q.wl2 && A.data_kind != LMC_DATA_NONE) ? 1 : 0;
+  A.hub = (q.hub && A.data_kind != LMC_DATA_NONE) ? 1 : 0;
   A.sigma_f = q.sigma_f;
   A.y = q.y; A.mask = q.mask;
   A.blur = q.taps;
@@ -442,6 +458,9 @@ bool pois_pipe_covers(const lmc::StepArgs& A) { return A.pois && A.prior_kind ==
 // tile kernel for everything else.
 bool wl2_pipe_covers(const lmc::StepArgs& A) { return A.wl2 && A.prior_kind == LMC_PRIOR_TV_ISO && lmc::pipe_links(A) == 1; }
 
+// The Huber data term (kHubNames): the same route again.
+bool hub_pipe_covers(const lmc::StepArgs& A) { return A.hub && A.prior_kind == LMC_PRIOR_TV_ISO && lmc::pipe_links(A) == 1; }
+
 // the four kernel names of a data term that has instantiations of its own: pipe, pipe + box, tile, tile + box
 struct TermNames { const char *pipe, *pipe_box, *tile, *tile_box; };
 
@@ -475,6 +494,7 @@ static hipError_t launch_step_term(const lmc::StepArgs& A_in, int variant, bool 
 
 constexpr TermNames kPoisNames = {"myula_step_pipe_pois_kernel", "myula_step_pipe_pois_box_kernel", "myula_step_tile_pois_kernel", "myula_step_tile_pois_box_kernel"};
 constexpr TermNames kWl2Names = {"myula_step_pipe_wl2_kernel", "myula_step_pipe_wl2_box_kernel", "myula_step_tile_wl2_kernel", "myula_step_tile_wl2_box_kernel"};
+constexpr TermNames kHubNames = {"myula_step_pipe_hub_kernel", "myula_step_pipe_hub_box_kernel", "myula_step_tile_hub_kernel", "myula_step_tile_hub_box_kernel"};
 
 // The box-constrained forms.  Separable priors: one elementwise launch forms clip(prox) into pxbuf, then the step of the variant asked for consumes it.
 // TV priors: the pipe kernel's box instantiations (isotropic; auto, 7, 8) or the tile kernel's (either form; auto, 1); a forced variant without a box
@@ -495,7 +515,7 @@ static hipError_t launch_step_around(const lmc::StepArgs& A, int variant, const 
     return adjoint(true, A.a, coef);
   }
   lmc::StepArgs B = A;
-  B.data_kind = LMC_DATA_NONE; B.t = 0.f; B.pois = 0; B.wl2 = 0;
+  B.data_kind = LMC_DATA_NONE; B.t = 0.f; B.pois = 0; B.wl2 = 0; B.hub = 0;
   e = launch_step(B, variant, q, ws, st, name);      // (a wavelet prior: launch_step has formed its prox already, B carries it)
   if (e != hipSuccess) return e;
   return adjoint(false, 0.f, coef);
@@ -505,7 +525,7 @@ static hipError_t launch_step_around(const lmc::StepArgs& A, int variant, const 
 static hipError_t launch_step_psf(const lmc::StepArgs& A, int variant, const Problem& q, Workspace& ws, hipStream_t st, const char** name) {
   const lmc::PsfOp& P = q.psf;
   if (!P.on || !P.tab_dev || !P.resid) return hipErrorInvalidConfiguration;
-  const int rho = A.pois ? lmc::kPsfRhoPois : A.wl2 ? lmc::kPsfRhoWl2 : lmc::kPsfRhoL2;
+  const int rho = A.pois ? lmc::kPsfRhoPois : A.wl2 ? lmc::kPsfRhoWl2 : A.hub ? lmc::kPsfRhoHub : lmc::kPsfRhoL2;
   return launch_step_around(A, variant, q, ws, st, name, "psf_conv_kernel",
       [&] { return lmc::launch_psf(P, 0, rho, A.x_in, P.resid, nullptr, A.y, A.C, A.H, A.W, 0.f, 0.f, st); },
       [&](bool alone, float a, float coef) {
@@ -545,6 +565,7 @@ hipError_t launch_step(const lmc::StepArgs& A_in, int variant, const Problem& q,
   if (A_in.data_kind == LMC_DATA_SPECTRAL) return launch_step_fft(A_in, variant, q, ws, st, name);
   if (A_in.pois) return launch_step_term(A_in, variant, pois_pipe_covers(A_in), kPoisNames, ws, st, name);
   if (A_in.wl2) return launch_step_term(A_in, variant, wl2_pipe_covers(A_in), kWl2Names, ws, st, name);
+  if (A_in.hub) return launch_step_term(A_in, variant, hub_pipe_covers(A_in), kHubNames, ws, st, name);
   if (!A_in.box) return launch_step_nobox(A_in, variant, ws, st, name);
   lmc::StepArgs A = A_in;
   if (A.prior_kind != LMC_PRIOR_TV_ISO) {

@@ -72,6 +72,12 @@ void psf_launch_one(bool sep, unsigned blocks, const PsfArgs& A, hipStream_t st)
   else hipLaunchKernelGGL((psf_conv_kernel<EPI, false>), dim3(blocks), dim3(256), 0, st, A);
 }
 
+template <int EPI>      // the Huber epilogues: psf_hub_kernel
+void psf_launch_hub(bool sep, unsigned blocks, const PsfArgs& A, hipStream_t st) {
+  if (sep) hipLaunchKernelGGL((psf_hub_kernel<EPI, true>), dim3(blocks), dim3(256), 0, st, A);
+  else hipLaunchKernelGGL((psf_hub_kernel<EPI, false>), dim3(blocks), dim3(256), 0, st, A);
+}
+
 hipError_t psf_launch_all(const PsfOp& P, int epi, PsfArgs A, int64_t n_img, hipStream_t st) {
   if (!P.on || !P.tab_dev || P.kh < 1 || P.kw < 1 || P.kh > kPsfMax || P.kw > kPsfMax) return hipErrorInvalidValue;
   const size_t img = (size_t)A.H * A.W;
@@ -96,6 +102,8 @@ hipError_t psf_launch_all(const PsfOp& P, int epi, PsfArgs A, int64_t n_img, hip
       case kPsfEnL2: psf_launch_one<kPsfEnL2>(sep, blocks, B, st); break;
       case kPsfEnWl2: psf_launch_one<kPsfEnWl2>(sep, blocks, B, st); break;
       case kPsfEnPois: psf_launch_one<kPsfEnPois>(sep, blocks, B, st); break;
+      case kPsfRhoHub: psf_launch_hub<kPsfRhoHub>(sep, blocks, B, st); break;
+      case kPsfEnHub: psf_launch_hub<kPsfEnHub>(sep, blocks, B, st); break;
       default: return hipErrorInvalidValue;
     }
   }
@@ -106,8 +114,9 @@ hipError_t psf_launch_all(const PsfOp& P, int epi, PsfArgs A, int64_t n_img, hip
 
 hipError_t launch_psf(const PsfOp& P, int adjoint, int epi, const float* x, float* out, const float* xin, const float* y, int64_t n_img, int H, int W,
                       float a, float coef, hipStream_t st) {
-  if (epi < kPsfRaw || epi > kPsfOverwrite || !x || !out || n_img < 1) return hipErrorInvalidValue;
-  if ((epi == kPsfOverwrite && !xin) || (epi >= kPsfRhoL2 && epi <= kPsfRhoPois && !y)) return hipErrorInvalidValue;
+  const bool rho = (epi >= kPsfRhoL2 && epi <= kPsfRhoPois) || epi == kPsfRhoHub;
+  if (epi < kPsfRaw || (epi > kPsfOverwrite && !rho) || !x || !out || n_img < 1) return hipErrorInvalidValue;
+  if ((epi == kPsfOverwrite && !xin) || (rho && !y)) return hipErrorInvalidValue;
   PsfArgs A = psf_args(P, adjoint, H, W);
   A.x = x; A.out = out; A.xin = xin; A.y = y; A.a = a; A.coef = coef;
   return psf_launch_all(P, epi, A, n_img, st);
@@ -119,10 +128,10 @@ size_t psf_energy_partials(int64_t n_img, int H, int W) {
 
 hipError_t launch_psf_energy(const PsfOp& P, int term, const float* x, const float* y, int64_t n_img, int H, int W, float sigma_f, double* part,
                              double* f_out, hipStream_t st) {
-  if (term < 0 || term > 2 || !x || !y || !part || !f_out || n_img < 1) return hipErrorInvalidValue;
+  if (term < 0 || term > 3 || !x || !y || !part || !f_out || n_img < 1) return hipErrorInvalidValue;
   PsfArgs A = psf_args(P, 0, H, W);
   A.x = x; A.y = y; A.part = part;
-  hipError_t e = psf_launch_all(P, term == 0 ? kPsfEnL2 : term == 1 ? kPsfEnWl2 : kPsfEnPois, A, n_img, st);
+  hipError_t e = psf_launch_all(P, term == 0 ? kPsfEnL2 : term == 1 ? kPsfEnWl2 : term == 2 ? kPsfEnPois : kPsfEnHub, A, n_img, st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(psf_energy_finish_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, st, part, n_img, A.tiles_x * A.tiles_y,
                      (double)sigma_f, f_out);

@@ -114,6 +114,11 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     return fail(LMC_E_UNSUPPORTED, "step_variant 7 (pipe) does not cover this weighted Gaussian problem: isotropic TV with 10 dual iterations (after "
                 "tv_lagged_output), W > 128, separable blur of 5 or 7 taps or the identity; use 0 (auto) or 1 (tile)");
   }
+  if (s->prob.hub && !s->prob.psf.on && variant_of(s->prob) == 7 && !hub_pipe_covers(s->base)) {
+    delete s;
+    return fail(LMC_E_UNSUPPORTED, "step_variant 7 (pipe) does not cover this Huber problem: isotropic TV with 10 dual iterations (after "
+                "tv_lagged_output), W > 128, separable blur of 5 or 7 taps or the identity; use 0 (auto) or 1 (tile)");
+  }
   if (s->prob.tv_rtol > 0.f && s->base.prior_kind == LMC_PRIOR_TV_ISO && s->prob.tv_warm) { delete s; return fail(LMC_E_UNSUPPORTED, "tv_rtol > 0 and tv_warm exclude each other"); }
   const size_t n = (size_t)s->C * s->prob.H * s->prob.W;
   hipError_t e = s->own.alloc(&s->x[0], n, true);
@@ -131,9 +136,9 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     s->pol_bg_wgs = q.moments_bg_wgs > 0 ? q.moments_bg_wgs : env_int("LMC_MOMENTS_BG_WGS", -1);
     // One iteration per launch (the pair kernels have no form of it) wherever an iteration is more than the one fused launch:
     //   prox_scale, box, wav.on   the prox is a launch of its own before every step (array-valued epsg, the clamp, the wavelet transforms)
-    //   wl2, pois                 the weighted Gaussian and the Poisson data terms have kernels of their own, none of them a pair kernel
+    //   wl2, hub, pois            the weighted Gaussian, the Huber and the Poisson data terms have kernels of their own, none of them a pair kernel
     //   psf.on, fft.on            the large PSF and the spectral data term are three launches per iteration
-    if (q.prox_scale || q.box || q.wav.on || q.wl2 || q.pois || q.psf.on || q.fft.on) { s->pol_pair = 0; s->pol_blockpair = 0; }
+    if (q.prox_scale || q.box || q.wav.on || q.wl2 || q.hub || q.pois || q.psf.on || q.fft.on) { s->pol_pair = 0; s->pol_blockpair = 0; }
   }
   if (e == hipSuccess && s->prob.tv_warm) {
     lmc::StepArgs probe = s->base;
@@ -218,8 +223,8 @@ static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool 
                           const StepOverride* ov = nullptr) {
   lmc::StepArgs A = s->base;
   if (fused) *fused = false;
-  // (a weighted Gaussian data term: its pipe kernels form no by-products -- the caller takes f and g from sampler_energies_at, as for strips)
-  if (f_out && g_out && !s->prob.wl2 && (variant_of(s->prob) == 0 || variant_of(s->prob) == 7) && s->prob.ncvx_kind == LMC_NCVX_NONE && s->prob.prior_kind == LMC_PRIOR_TV_ISO) {
+  // (a weighted Gaussian or a Huber data term: its pipe kernels form no by-products -- the caller takes f and g from sampler_energies_at, as for strips)
+  if (f_out && g_out && !s->prob.wl2 && !s->prob.hub && (variant_of(s->prob) == 0 || variant_of(s->prob) == 7) && s->prob.ncvx_kind == LMC_NCVX_NONE && s->prob.prior_kind == LMC_PRIOR_TV_ISO) {
     // The pipe kernel returns f(x_in), g(x_in) as by-products where one launch WITH them covers the problem: the probe carries the outputs, since
     // they narrow the coverage (no column strips, a blur only).  Elsewhere the launch below runs without them -- on whatever kernel covers the
     // update alone, the strips and the pointwise data terms of the pipe kernel included -- and the caller forms the energies itself.
@@ -826,6 +831,7 @@ int lmc_ulpda_create(const lmc_ulpda_config* cfg, lmc_sampler** out) {
   lmc_problem pr = cfg->problem;
   if (pr.prior_kind == LMC_PRIOR_TV_ISO && pr.tv_niter < 1) pr.tv_niter = 1;   // unused by ULPDA; keeps the loader happy
   rc = load_problem(&pr, s->prob);
+  if (!rc) rc = check_no_hub(s->prob, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Huber loss under an operator; use MYULA");
   if (!rc) rc = check_no_wl2(s->prob, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f Op^T W Op)^{-1}, which is not built; use MYULA");
   if (!rc) rc = check_no_poisson(s->prob, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA");
   if (!rc) rc = check_no_psf(s->prob, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f H^T H)^{-1}, which is not built for a large PSF; use MYULA");

@@ -14,35 +14,46 @@ constexpr int kStepThreads = 1024;
 
 // The sixteen kernels of before (their names and instruction streams are as they were) ...
 #define LMC_TILE_KERNEL_HEAD template <int NP, bool TV, bool ANISO = false> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool BOX = false, POIS = false, WL2 = false;
+#define LMC_TILE_KERNEL_FLAGS constexpr bool BOX = false, POIS = false, WL2 = false, HUB = false;
 #include "lmc_step_tile_kernel.h"
 #undef LMC_TILE_KERNEL_HEAD
 #undef LMC_TILE_KERNEL_FLAGS
 // ... and the box-constrained TV prior, either form, under a name of its own
 #define LMC_TILE_KERNEL_HEAD template <int NP, bool ANISO> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_box_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool TV = true, BOX = true, POIS = false, WL2 = false;
+#define LMC_TILE_KERNEL_FLAGS constexpr bool TV = true, BOX = true, POIS = false, WL2 = false, HUB = false;
 #include "lmc_step_tile_kernel.h"
 #undef LMC_TILE_KERNEL_HEAD
 #undef LMC_TILE_KERNEL_FLAGS
 // ... and the Poisson data term (StepArgs::pois), with every prior of the first and the box of the second
 #define LMC_TILE_KERNEL_HEAD template <int NP, bool TV, bool ANISO = false> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_pois_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool BOX = false, POIS = true, WL2 = false;
+#define LMC_TILE_KERNEL_FLAGS constexpr bool BOX = false, POIS = true, WL2 = false, HUB = false;
 #include "lmc_step_tile_kernel.h"
 #undef LMC_TILE_KERNEL_HEAD
 #undef LMC_TILE_KERNEL_FLAGS
 #define LMC_TILE_KERNEL_HEAD template <int NP, bool ANISO> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_pois_box_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool TV = true, BOX = true, POIS = true, WL2 = false;
+#define LMC_TILE_KERNEL_FLAGS constexpr bool TV = true, BOX = true, POIS = true, WL2 = false, HUB = false;
 #include "lmc_step_tile_kernel.h"
 #undef LMC_TILE_KERNEL_HEAD
 #undef LMC_TILE_KERNEL_FLAGS
 // ... and the weighted Gaussian data term (StepArgs::wl2), likewise
 #define LMC_TILE_KERNEL_HEAD template <int NP, bool TV, bool ANISO = false> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_wl2_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool BOX = false, POIS = false, WL2 = true;
+#define LMC_TILE_KERNEL_FLAGS constexpr bool BOX = false, POIS = false, WL2 = true, HUB = false;
 #include "lmc_step_tile_kernel.h"
 #undef LMC_TILE_KERNEL_HEAD
 #undef LMC_TILE_KERNEL_FLAGS
 #define LMC_TILE_KERNEL_HEAD template <int NP, bool ANISO> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_wl2_box_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool TV = true, BOX = true, POIS = false, WL2 = true;
+#define LMC_TILE_KERNEL_FLAGS constexpr bool TV = true, BOX = true, POIS = false, WL2 = true, HUB = false;
+#include "lmc_step_tile_kernel.h"
+#undef LMC_TILE_KERNEL_HEAD
+#undef LMC_TILE_KERNEL_FLAGS
+// ... and the Huber data term (StepArgs::hub), likewise
+#define LMC_TILE_KERNEL_HEAD template <int NP, bool TV, bool ANISO = false> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_hub_kernel
+#define LMC_TILE_KERNEL_FLAGS constexpr bool BOX = false, POIS = false, WL2 = false, HUB = true;
+#include "lmc_step_tile_kernel.h"
+#undef LMC_TILE_KERNEL_HEAD
+#undef LMC_TILE_KERNEL_FLAGS
+#define LMC_TILE_KERNEL_HEAD template <int NP, bool ANISO> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_hub_box_kernel
+#define LMC_TILE_KERNEL_FLAGS constexpr bool TV = true, BOX = true, POIS = false, WL2 = false, HUB = true;
 #include "lmc_step_tile_kernel.h"
 #undef LMC_TILE_KERNEL_HEAD
 #undef LMC_TILE_KERNEL_FLAGS
@@ -87,6 +98,12 @@ static hipError_t launch_kernel(const StepArgs& a, size_t lds, hipStream_t st) {
 
 template <int NP, bool TV, bool ANISO>
 static hipError_t launch_np(const StepArgs& a, size_t lds, hipStream_t st) {
+  if (a.hub) {
+    if constexpr (TV) {
+      if (a.box) return launch_kernel<myula_step_tile_hub_box_kernel<NP, ANISO>>(a, lds, st);
+    }
+    return launch_kernel<myula_step_tile_hub_kernel<NP, TV, ANISO>>(a, lds, st);
+  }
   if (a.wl2) {
     if constexpr (TV) {
       if (a.box) return launch_kernel<myula_step_tile_wl2_box_kernel<NP, ANISO>>(a, lds, st);
@@ -165,7 +182,7 @@ hipError_t launch_step_tile_chunked(const StepArgs& a, float* state0, float* sta
     b.tv_in = ch > 0 ? state[(ch - 1) & 1] : nullptr;
     b.tv_out = last ? nullptr : state[ch & 1];
     b.tv_state_only = last ? 0 : 1;
-    if (!last) { b.data_kind = LMC_DATA_NONE; b.pois = 0; b.wl2 = 0; b.ncvx_kind = LMC_NCVX_NONE; b.extra = nullptr; }
+    if (!last) { b.data_kind = LMC_DATA_NONE; b.pois = 0; b.wl2 = 0; b.hub = 0; b.ncvx_kind = LMC_NCVX_NONE; b.extra = nullptr; }
     hipError_t e = launch_step_tile(b, st);
     if (e != hipSuccess) return e;
   }

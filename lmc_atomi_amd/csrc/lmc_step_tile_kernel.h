@@ -1,6 +1,6 @@
 // The body of the LDS-tiled step kernel (lmc_step_tile.hip), included once per kernel NAME: the including file defines
 //   LMC_TILE_KERNEL_HEAD   the template head and the kernel's name, up to its argument list
-//   LMC_TILE_KERNEL_FLAGS  constexpr definitions of whichever of TV, ANISO, BOX, POIS, WL2 are no template parameters of that head
+//   LMC_TILE_KERNEL_FLAGS  constexpr definitions of whichever of TV, ANISO, BOX, POIS, WL2, HUB are no template parameters of that head
 // Textual inclusion, not a shared device function: the unconstrained kernels keep their instruction streams bit for bit that way (as a
 // function inlined into two kernels the same source compiles to other streams for all sixteen -- scripts/kernel_resources.py --code-hash), and the
 // box-constrained kernels get names of their own without a fourth template argument on myula_step_tile_kernel.
@@ -16,6 +16,8 @@
 // residual H x - y becomes rho(H x) = phi'(H x) (pois_rho, lmc_device.h) at the three places that form it.  P.data_kind stays the operator's kind.
 // WL2 (myula_step_tile_wl2_kernel, myula_step_tile_wl2_box_kernel): the weighted Gaussian data term -- P.y is [2][H][W], observation then weights, and
 // the residual H x - y becomes w (H x - y): the weight multiplies BEFORE the adjoint.  Identity and blur (there is no weighted mask kind).
+// HUB (myula_step_tile_hub_kernel, myula_step_tile_hub_box_kernel): the Huber data term -- P.y is [2][H][W], observation then thresholds delta, and the
+// residual H x - y becomes clamp(H x - y, -delta, delta) (hub_psi, lmc_device.h): the clamp acts BEFORE the adjoint.  Identity and blur (no mask kind).
 LMC_TILE_KERNEL_HEAD(const StepArgs P) {
   LMC_TILE_KERNEL_FLAGS
   static_assert(TV || !ANISO, "the anisotropic projection belongs to the TV prox");
@@ -92,6 +94,7 @@ LMC_TILE_KERNEL_HEAD(const StepArgs P) {
             // (inside the guard: rho of a pixel outside the image is not 0 -- it is 1 for y = 0)
             if constexpr (POIS) acc = pois_rho(acc, P.y[gi], P.y[img + gi]);
             else if constexpr (WL2) acc = P.y[img + gi] * (acc - P.y[gi]);
+            else if constexpr (HUB) acc = hub_psi(acc - P.y[gi], P.y[img + gi]);
             else acc -= P.y[gi];
           }
           S[p] = acc;  // residual, zero outside the image (zero-padded adjoint)
@@ -215,6 +218,7 @@ LMC_TILE_KERNEL_HEAD(const StepArgs P) {
     if (P.data_kind == LMC_DATA_IDENTITY) {
       if constexpr (POIS) g = P.sigma_f * pois_rho(x, P.y[gi], P.y[img + gi]);
       else if constexpr (WL2) g = P.sigma_f * (P.y[img + gi] * (x - P.y[gi]));
+      else if constexpr (HUB) g = P.sigma_f * hub_psi(x - P.y[gi], P.y[img + gi]);
       else g = P.sigma_f * (x - P.y[gi]);
     } else if (P.data_kind == LMC_DATA_MASK) {
       const float mk = P.mask[gi];

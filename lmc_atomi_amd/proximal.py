@@ -124,7 +124,7 @@ class _Problem:
         p.data_kind = data["data_kind"]
         p.sigma_f = float(data.get("sigma_f", 0.0))
         if data.get("y") is not None:
-            # (a Poisson term: [2][H][W], the counts then the background; a weighted Gaussian term: the observation then the weights)
+            # (a Poisson term: [2][H][W], the counts then the background; a weighted Gaussian term: the observation then the weights; a Huber term: the observation then the thresholds)
             if p.data_kind == _capi.DATA_SPECTRAL:      # the spectral term: the [11][H][W / 2 + 1] planes of lmc_spectral_tables
                 y = _dev.to_dev(data["y"], dev).reshape(_capi.SPECTRAL_PLANES, self.dims[0], self.dims[1] // 2 + 1)
             else:
@@ -135,7 +135,7 @@ class _Problem:
             m = _dev.to_dev(data["mask"], dev).reshape(self.dims)
             self._keep.append(m)
             p.mask_dev = m.data_ptr()
-        if p.data_kind in (_capi.DATA_BLUR, _capi.DATA_POISSON_BLUR, _capi.DATA_WL2_BLUR):
+        if p.data_kind in (_capi.DATA_BLUR, _capi.DATA_POISSON_BLUR, _capi.DATA_WL2_BLUR, _capi.DATA_HUBER_BLUR):
             h = np.ascontiguousarray(data["h"], dtype=np.float32)
             self._keep.append(h)
             p.kh, p.kw = h.shape
@@ -502,6 +502,92 @@ class Poisson(ProxOperator):
 
     def prox(self, x, tau):
         raise NotImplementedError("Poisson.prox: the implicit step of the Poisson likelihood has no closed form (lmc_l2_prox refuses it)")
+
+
+class HuberLoss(ProxOperator):
+    r"""Huber loss of the residual: robust deconvolution with outliers at unknown positions -- impulse noise, cosmic rays, hot or saturated pixels (build
+    extension; the reference has no such term -- ``LMC_DATA_HUBER_*`` in include/lmc_atomi.h is its definition).  With ``r = (Op x)_p - b_p``:
+    ``f(x) = sigma * sum_p h_delta_p(r_p)``, ``h_delta(r) = r^2 / 2`` for ``|r| <= delta`` and ``delta (|r| - delta / 2)`` beyond, so
+    ``grad f = sigma Op^T clamp(Op x - b, -delta, delta)``: the clamp acts on the residual before the adjoint.  (The name ``Huber`` is the prior factory.)
+
+    ``Op``: :class:`Convolve2D`, :class:`Identity` or :class:`PSF` (``dims``: the image shape where neither ``Op`` nor a 2-D ``b`` or ``delta`` carries it);
+    ``b``: the observation (finite); ``delta``: a scalar or an ``[H, W]`` / flat array of thresholds in ``[0, +inf]`` -- ``+inf`` is the plain Gaussian
+    term at that pixel, ``0`` an unobserved pixel, so a binary mask on a blur is ``delta = 0`` there (``Diagonal`` is refused).  f is convex and C^1 with
+    ``L_f = sigma ||Op||^2``.
+
+    As ``proxf`` of :class:`MYULASampler` / :func:`MoreauYosidaUnadjustedLangevin`, :class:`MYMALASampler` (not with ``PSF``), :class:`SKROCKSampler` /
+    :func:`StabilisedLangevin` and :func:`EstimatePriorWeight`, with the priors and ``bounds`` of ``L2(weights=...)``.  ``prox``, ULPDA, ``Diagonal``,
+    the Fourier-domain operators, ``TV(rtol > 0)``, ``TV(warm=True)``, the block-Haar :class:`WaveletL1` and a forced kernel variant other than 'auto' /
+    'tile' / 'pipe' raise ``NotImplementedError``."""
+
+    def __init__(self, Op, b, delta, sigma=1.0, dims=None):
+        super().__init__(Op, True)
+        if isinstance(Op, Diagonal):
+            raise NotImplementedError("HuberLoss with Op = Diagonal: there is no Huber mask kind -- a binary mask on a blur is delta = 0 at the masked pixels")
+        if isinstance(Op, (FourierSampling, PeriodicConvolve2D)):
+            raise NotImplementedError(f"HuberLoss with Op of type {type(Op).__name__}: the Huber loss of a Fourier-domain residual is not built")
+        if not isinstance(Op, (Convolve2D, PSF, Identity)):
+            raise NotImplementedError(f"no device functor for HuberLoss with Op of type {type(Op).__name__} (Convolve2D, PSF or Identity)")
+        y = _host(b).astype(np.float64)
+        d = _host(delta).astype(np.float64)
+        # the image shape: `dims`, else the operator's, else that of an [H, W] array of observations or thresholds
+        for cand in (dims, getattr(Op, "dims", None), y.shape if y.ndim == 2 else None, d.shape if d.ndim == 2 else None):
+            if cand is not None:
+                self.dims = (int(cand[0]), int(cand[1]))
+                break
+        else:
+            raise ValueError("HuberLoss: image shape unknown (Op carries none, b and delta are flat): pass dims=(ny, nx)")
+        n = self.dims[0] * self.dims[1]
+        if y.size != n:
+            raise ValueError(f"HuberLoss: {y.size} observations for an image of shape {self.dims}")
+        if not np.all(np.isfinite(y)):
+            raise ValueError("HuberLoss: b must be finite (mark a bad pixel with delta = 0, not with NaN)")
+        if d.ndim != 0 and (d.size != n or d.ndim not in (1, 2) or (d.ndim == 2 and d.shape != self.dims)):
+            raise ValueError(f"HuberLoss: delta of shape {d.shape} for an image of shape {self.dims} (a scalar, or an [H, W] or flat array of its size)")
+        if np.any(np.isnan(d)) or np.any(d < 0):
+            raise ValueError("HuberLoss: delta must be >= 0 and not NaN (0 marks an unobserved pixel, +inf the plain quadratic term)")
+        self.b = y.reshape(self.dims)
+        self.delta = np.full(self.dims, float(d)) if d.ndim == 0 else d.reshape(self.dims)
+        self.sigma = float(sigma)
+        self._yd = np.ascontiguousarray(np.stack([self.b, self.delta]), dtype=np.float32)      # [2][H][W]: what y_dev points to
+        self._yd_dev = {}
+        self._prob = None
+
+    def _buffer(self):
+        """The [2][H][W] device buffer, built once (per device) and kept alive by this object; a problem on another device takes its own copy."""
+        key = _dev.device(None)
+        if key not in self._yd_dev:
+            self._yd_dev[key] = _dev.to_dev(self._yd, key)
+        return self._yd_dev[key]
+
+    def descriptor(self):
+        yd = self._buffer() if torch.cuda.is_available() else self._yd      # (without a device: the host array, for whoever only reads the description)
+        if isinstance(self.Op, PSF):
+            return {"data_kind": _capi.DATA_HUBER_PSF, "sigma_f": self.sigma, "y": yd, **self.Op.descriptor()}
+        if isinstance(self.Op, Convolve2D):
+            return {"data_kind": _capi.DATA_HUBER_BLUR, "sigma_f": self.sigma, "y": yd, "h": self.Op.h, "offset": self.Op.offset}
+        return {"data_kind": _capi.DATA_HUBER_IDENTITY, "sigma_f": self.sigma, "y": yd}
+
+    def grad_lipschitz(self):
+        """``L_f = sigma * ||Op||^2`` (the clamp is 1-Lipschitz: the bound of the plain term) with ``||Op|| <= sum |h|`` for a convolution and 1 for the
+        identity.  Host arithmetic, no GPU."""
+        op2 = float(np.abs(np.asarray(self.Op.h, dtype=np.float64)).sum()) ** 2 if isinstance(self.Op, (Convolve2D, PSF)) else 1.0
+        return self.sigma * op2
+
+    def _problem(self):
+        if self._prob is None:
+            self._prob = _Problem(self.dims, data=self.descriptor())
+        return self._prob
+
+    def __call__(self, x):
+        f, _ = self._problem().energies(x)
+        return float(f[0]) if f.numel() == 1 else (f if isinstance(x, torch.Tensor) else f.cpu().numpy())
+
+    def grad(self, x):
+        return self._problem().eval(x, 0.0, -1.0, 0.0, 0.0)
+
+    def prox(self, x, tau):
+        raise NotImplementedError("HuberLoss.prox: the implicit step of the Huber loss under an operator is not built (lmc_l2_prox refuses it)")
 
 
 def _host(a):
