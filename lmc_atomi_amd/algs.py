@@ -49,64 +49,36 @@ def _refuse_eprox(prior, who, why):
         raise NotImplementedError(f"{who} does not take a closed-form prior (ElementwiseProx, Laplace, Huber, ...): {why}")
 
 
-def _refuse_poisson(data, prior, opts, who=None):
-    """``NotImplementedError`` for what the library refuses with a Poisson data term (``LMC_E_UNSUPPORTED`` in include/lmc_atomi.h), before a handle
-    exists.  ``who``: (name, why) of a sampler that has no Poisson form at all."""
-    if data.get("data_kind") not in _capi.POISSON_KINDS:
-        return
-    if who is not None:
-        raise NotImplementedError(f"{who[0]} does not take the Poisson data term: {who[1]}")
-    if prior.get("prior_kind") == _capi.PRIOR_HAAR_L1:
-        raise NotImplementedError("the Poisson data term with the Haar-l1 prior (WaveletL1) is not built")
-    if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
-        raise NotImplementedError("the Poisson data term runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
-    if prior.get("tv_warm") or opts.get("tv_warm"):
-        raise NotImplementedError("the Poisson data term has no warm-started TV dual: warm / tv_warm must be off")
-    v = opts.get("step_variant", 0) or 0
-    v = _capi.VARIANTS.index(v) if isinstance(v, str) else int(v)
-    if v not in (0, 1, 7):
-        raise NotImplementedError(f"step-kernel variant {_capi.VARIANTS[v]!r} has no form of the Poisson data term: 'auto', 'tile' or 'pipe' (where it covers "
-                                  "the problem)")
+# The data terms with step kernels of their own: (kinds, name in messages, what the user wrote -- appended where a sampler refuses the term outright --, the
+# kind on a large PSF whose remaining refusals are _refuse_psf's, or None).  The kinds are disjoint: at most one row speaks.
+_TERMS = {
+    "poisson": (_capi.POISSON_KINDS, "the Poisson data term", "", None),
+    "wl2": (_capi.WL2_KINDS, "the weighted Gaussian data term", " (L2 with weights)", None),
+    "huber": (_capi.HUBER_KINDS, "the Huber data term", " (HuberLoss)", _capi.DATA_HUBER_PSF),
+}
 
 
-def _refuse_wl2(data, prior, opts, who=None):
-    """The same for the weighted Gaussian data term (``L2(weights=...)``, ``LMC_DATA_WL2_*``)."""
-    if data.get("data_kind") not in _capi.WL2_KINDS:
-        return
-    if who is not None:
-        raise NotImplementedError(f"{who[0]} does not take the weighted Gaussian data term (L2 with weights): {who[1]}")
-    if prior.get("prior_kind") == _capi.PRIOR_HAAR_L1:
-        raise NotImplementedError("the weighted Gaussian data term with the Haar-l1 prior (WaveletL1) is not built")
-    if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
-        raise NotImplementedError("the weighted Gaussian data term runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
-    if prior.get("tv_warm") or opts.get("tv_warm"):
-        raise NotImplementedError("the weighted Gaussian data term has no warm-started TV dual: warm / tv_warm must be off")
-    v = opts.get("step_variant", 0) or 0
-    v = _capi.VARIANTS.index(v) if isinstance(v, str) else int(v)
-    if v not in (0, 1, 7):
-        raise NotImplementedError(f"step-kernel variant {_capi.VARIANTS[v]!r} has no form of the weighted Gaussian data term: 'auto', 'tile' or 'pipe' "
-                                  "(where it covers the problem)")
-
-
-def _refuse_hub(data, prior, opts, who=None):
-    """The same for the Huber data term (``HuberLoss``, ``LMC_DATA_HUBER_*``); on a large PSF the rest of the list is :func:`_refuse_psf`'s."""
-    if data.get("data_kind") not in _capi.HUBER_KINDS:
-        return
-    if who is not None:
-        raise NotImplementedError(f"{who[0]} does not take the Huber data term (HuberLoss): {who[1]}")
-    if data.get("data_kind") == _capi.DATA_HUBER_PSF:
-        return
-    if prior.get("prior_kind") == _capi.PRIOR_HAAR_L1:
-        raise NotImplementedError("the Huber data term with the Haar-l1 prior (WaveletL1) is not built")
-    if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
-        raise NotImplementedError("the Huber data term runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
-    if prior.get("tv_warm") or opts.get("tv_warm"):
-        raise NotImplementedError("the Huber data term has no warm-started TV dual: warm / tv_warm must be off")
-    v = opts.get("step_variant", 0) or 0
-    v = _capi.VARIANTS.index(v) if isinstance(v, str) else int(v)
-    if v not in (0, 1, 7):
-        raise NotImplementedError(f"step-kernel variant {_capi.VARIANTS[v]!r} has no form of the Huber data term: 'auto', 'tile' or 'pipe' "
-                                  "(where it covers the problem)")
+def _refuse_term(data, prior, opts, who=None):
+    """``NotImplementedError`` for what the library refuses with a Poisson, weighted Gaussian (``L2(weights=...)``) or Huber (``HuberLoss``) data term
+    (``LMC_E_UNSUPPORTED`` in include/lmc_atomi.h), before a handle exists.  ``who``: term -> (name, why) of a sampler that has no form of that term at all."""
+    kind = data.get("data_kind")
+    for term, (kinds, name, label, psf_kind) in _TERMS.items():
+        if kind not in kinds:
+            continue
+        if who and term in who:
+            raise NotImplementedError(f"{who[term][0]} does not take {name}{label}: {who[term][1]}")
+        if kind == psf_kind:
+            return
+        if prior.get("prior_kind") == _capi.PRIOR_HAAR_L1:
+            raise NotImplementedError(f"{name} with the Haar-l1 prior (WaveletL1) is not built")
+        if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
+            raise NotImplementedError(f"{name} runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
+        if prior.get("tv_warm") or opts.get("tv_warm"):
+            raise NotImplementedError(f"{name} has no warm-started TV dual: warm / tv_warm must be off")
+        v = opts.get("step_variant", 0) or 0
+        v = _capi.VARIANTS.index(v) if isinstance(v, str) else int(v)
+        if v not in (0, 1, 7):
+            raise NotImplementedError(f"step-kernel variant {_capi.VARIANTS[v]!r} has no form of {name}: 'auto', 'tile' or 'pipe' (where it covers the problem)")
 
 
 def _refuse_psf(data, prior, opts, who=None):
@@ -346,9 +318,7 @@ class MYULASampler:
         if np.asarray(epsg).size > 1:      # array-valued epsg (algs.py:509,539-542): the prox parameter epsg * gamma is an array that the prox broadcasts
             opts["prox_scale"] = self._epsg_array(epsg)
             epsg = 1.0
-        _refuse_poisson(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._poisson_refusal)
-        _refuse_wl2(_data_descriptor(proxf), _prior_descriptor(proxg), opts)
-        _refuse_hub(_data_descriptor(proxf), _prior_descriptor(proxg), opts)
+        _refuse_term(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._term_refusal)
         _refuse_psf(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._psf_refusal)
         _refuse_spectral(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._spectral_refusal)
         self._problem = _Problem(self.dims, _data_descriptor(proxf), _prior_descriptor(proxg), self.device, options=opts)
@@ -376,7 +346,7 @@ class MYULASampler:
 
     _create_fn = "lmc_myula_create"
     _box_refusal = None          # (who, why) of a subclass that has no box-constrained form: raised before a handle exists
-    _poisson_refusal = None      # the same for the Poisson data term
+    _term_refusal = None         # the same for the data terms of _TERMS: term -> (who, why)
     _psf_refusal = None          # the same for a large PSF
     _spectral_refusal = None     # the same for the Fourier-domain data term
     _eprox_refusal = None        # the same for a closed-form prior (a prox without a value)
@@ -661,9 +631,10 @@ class ULPDASampler(MYULASampler):
             raise NotImplementedError("ULPDA on the GPU supports A = Gradient (the reference's operator, prox_lmc_deconv.py:98)")
         if getattr(proxg, "bounds", None) is not None:
             raise NotImplementedError("ULPDA does not take a prior with bounds: its prior enters through the dual ball of g o A, which has no box form; use MYULA")
-        _refuse_poisson(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA"))
-        _refuse_wl2(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, (I + tau sigma Op^T W Op)^{-1}, which is not built; use MYULA"))
-        _refuse_hub(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which is not built for the Huber loss under an operator; use MYULA"))
+        _refuse_term(_data_descriptor(proxf), {}, {}, {
+            "poisson": ("ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA"),
+            "wl2": ("ULPDA", "its primal step is the implicit step of f, (I + tau sigma Op^T W Op)^{-1}, which is not built; use MYULA"),
+            "huber": ("ULPDA", "its primal step is the implicit step of f, which is not built for the Huber loss under an operator; use MYULA")})
         _refuse_spectral(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal-dual loop is not wired to the closed-form implicit step of this term; use MYULA"))
         _refuse_psf(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which is not built for a large PSF; use MYULA"))
         if isinstance(proxg, L21):
@@ -963,7 +934,7 @@ class MYMALASampler(MYULASampler):
     _create_fn = "lmc_mymala_create"
 
     _box_refusal = ("MYMALA", "its target would be +infinity outside the box, where MYULA's proposals land; use MYULA")
-    _poisson_refusal = ("MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK")
+    _term_refusal = {"poisson": ("MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK")}
     _psf_refusal = ("MYMALA", "its Metropolis ratio is pinned for the fused step, which the three-launch PSF step is not; use MYULA or SK-ROCK")
     _spectral_refusal = ("MYMALA", "its Metropolis ratio is pinned for the fused step, which the three-launch spectral step is not; use MYULA or SK-ROCK")
     _eprox_refusal = ("MYMALA", "the prior has a prox and no value g(x), so the Metropolis target exp(-f - epsg g) is undefined; use MYULA")

@@ -253,9 +253,9 @@ int lmc_l2_prox(const lmc_problem* prob, const float* x_dev, float* out_dev, int
   Problem q;
   int rc = load_problem(prob, q);
   if (rc) return rc;
-  rc = check_no_poisson(q, "lmc_l2_prox", "its implicit step (I + tau grad f)^{-1} has no closed form");
-  if (!rc) rc = check_no_hub(q, "lmc_l2_prox", "the implicit step of the Huber loss under an operator is not built");
-  if (!rc) rc = check_no_wl2(q, "lmc_l2_prox", "the implicit step (I + tau sigma_f Op^T W Op)^{-1} is not built");
+  rc = check_no_term(q, lmc::kTermPois, "lmc_l2_prox", "its implicit step (I + tau grad f)^{-1} has no closed form");
+  if (!rc) rc = check_no_term(q, lmc::kTermHub, "lmc_l2_prox", "the implicit step of the Huber loss under an operator is not built");
+  if (!rc) rc = check_no_term(q, lmc::kTermWl2, "lmc_l2_prox", "the implicit step (I + tau sigma_f Op^T W Op)^{-1} is not built");
   if (!rc) rc = check_no_psf(q, "lmc_l2_prox", "the implicit step (I + tau sigma_f H^T H)^{-1} is not built for it");
   if (rc) return rc;
   if (!x_dev || !out_dev || x_dev == out_dev || n_img < 1) return fail(LMC_E_INVALID, "bad arguments (in-place not allowed)");

@@ -30,6 +30,15 @@ struct TvIter {
 constexpr int kTvFoldAt = kMaxTvIters - 2 * kTvFoldMax;
 static_assert(kTvFoldAt >= kTvFoldMax, "the folded table lies behind the coefficients a launch reads");
 
+// The data term of a step: f(x) = sigma_f sum_p phi_p((A x)_p) over the operator A that data_kind names.  kTermL2 is the plain Gaussian term,
+// phi = (u - y)^2 / 2; the others read a second plane behind y ([2][H][W]) and have kernels of their own name (pipe, tile, energy):
+//   kTermPois  the Poisson likelihood (LMC_DATA_POISSON_*, lmc_atomi.h): y = the counts, then the background beta; A = identity, blur or mask
+//   kTermWl2   per-pixel weights, phi = w (u - y)^2 / 2 (LMC_DATA_WL2_*): y = the observation, then the weights w; A = identity or blur
+//   kTermHub   the Huber loss, phi = h_delta(u - y) (LMC_DATA_HUBER_*): y = the observation, then the thresholds delta; A = identity or blur
+// Host code selects by it (the term table of lmc_host.h); device code takes it as a template argument.
+enum DataTerm : uint32_t { kTermL2 = 0, kTermPois, kTermWl2, kTermHub };
+constexpr int kNumTerms = 4;
+
 // out = a*x - t*grad f(x) + b*prox(x) + s*xi
 struct StepArgs {
   int H, W, C;
@@ -58,9 +67,8 @@ struct StepArgs {
                              // [box_lo, box_hi] (the fields of those names further down).  This slot and tv_aniso hold the argument layout of every step kernel (an 8-byte slot: dropping it
                              // moves the fields behind it, and with them the register allocation and spills of some 180 kernels)
   uint32_t chain_offset;     // global id of chain 0 (counter word 2 = chain_offset + c)
-  uint32_t pois;             // host side only, like tv_aniso and box (the Poisson kernels are instantiations of their own): the data term is the Poisson
-                             // likelihood of lmc_atomi.h -- data_kind stays the operator's kind (identity, blur, mask), y is [2][H][W]: the counts, then the
-                             // background beta at y + H W.  It sits in the 4-byte hole the alignment of x_in leaves: no field moves (the asserts below)
+  uint32_t term;             // DataTerm.  Host side only, like tv_aniso and box (the kernels of a term are instantiations of their own); data_kind stays the
+                             // operator's kind.  It sits in the 4-byte hole the alignment of x_in leaves: no field moves (the asserts below)
   const float* x_in;
   float* x_out;
   // resumable TV prox (tile kernel): dual state [C][4][H][W] = (rr, ss, p, q) carried between launches so that
@@ -73,9 +81,7 @@ struct StepArgs {
   // extra gradient term g += extra_coef * (x - extra[c][i][j])   (ME-TV: extra = prox_{gamma TV}(x), algs.py:282)
   const float* extra;
   float extra_coef;
-  uint32_t wl2;              // host side only, like pois (the weighted kernels are instantiations of their own): the Gaussian data term carries per-pixel
-                             // weights, sigma_f/2 sum_p w_p (u_p - y_p)^2 (LMC_DATA_WL2_*, lmc_atomi.h) -- data_kind stays the operator's kind (identity, blur),
-                             // y is [2][H][W]: the observation, then the weights w at y + H W.  It sits in the 4-byte hole behind extra_coef (the asserts below)
+  uint32_t reserved0;        // the 4-byte hole behind extra_coef (the asserts below): no kernel reads it
   // rows kernel only: dot_out[c] += sum_ij x_in[c][i][j] * x_out[c][i][j] (the p.Ap of a CG iteration, fused into the operator apply)
   double* dot_out;
   const int* skip_flag;
@@ -83,9 +89,7 @@ struct StepArgs {
   // chebyshev_solve): dot_out[2c] += sum (x_out - x_in)^2, dot_out[2c+1] += sum prox_ext^2.  run_count / run_index: the launch returns at
   // once when *run_count <= run_index (the iterations a warm-started solve turned out not to need).
   int dot_mode;
-  uint32_t hub;              // host side only, like wl2 (the Huber kernels are instantiations of their own): the data term is the Huber loss of the residual,
-                             // sigma_f sum_p h_delta_p(u_p - y_p) (LMC_DATA_HUBER_*, lmc_atomi.h) -- data_kind stays the operator's kind (identity, blur),
-                             // y is [2][H][W]: the observation, then the thresholds delta at y + H W.  It sits in the 4-byte hole behind dot_mode (the asserts below)
+  uint32_t reserved1;        // the 4-byte hole behind dot_mode (the asserts below): no kernel reads it
   const int* run_count;
   int run_index;
   // pipe kernel only: energies of x_in as by-products of the update (MYMALA): f_out[c] += sigma_f/2 ||H x - y||^2 (the residual rows
@@ -120,12 +124,12 @@ struct StepArgs {
 static_assert(sizeof(StepArgs) == 952, "the argument of every step kernel keeps its size");
 static_assert(offsetof(StepArgs, box_lo) == offsetof(StepArgs, g_scale) + 4 && offsetof(StepArgs, prox_ext) == offsetof(StepArgs, g_scale) + 8,
               "box_lo fills the hole behind g_scale");
-static_assert(offsetof(StepArgs, pois) == offsetof(StepArgs, chain_offset) + 4 && offsetof(StepArgs, x_in) == offsetof(StepArgs, chain_offset) + 8,
-              "pois fills the hole behind chain_offset");
-static_assert(offsetof(StepArgs, wl2) == offsetof(StepArgs, extra_coef) + 4 && offsetof(StepArgs, dot_out) == offsetof(StepArgs, extra_coef) + 8,
-              "wl2 fills the hole behind extra_coef");
-static_assert(offsetof(StepArgs, hub) == offsetof(StepArgs, dot_mode) + 4 && offsetof(StepArgs, run_count) == offsetof(StepArgs, dot_mode) + 8,
-              "hub fills the hole behind dot_mode");
+static_assert(offsetof(StepArgs, term) == offsetof(StepArgs, chain_offset) + 4 && offsetof(StepArgs, x_in) == offsetof(StepArgs, chain_offset) + 8,
+              "term fills the hole behind chain_offset");
+static_assert(offsetof(StepArgs, reserved0) == offsetof(StepArgs, extra_coef) + 4 && offsetof(StepArgs, dot_out) == offsetof(StepArgs, extra_coef) + 8,
+              "reserved0 fills the hole behind extra_coef");
+static_assert(offsetof(StepArgs, reserved1) == offsetof(StepArgs, dot_mode) + 4 && offsetof(StepArgs, run_count) == offsetof(StepArgs, dot_mode) + 8,
+              "reserved1 fills the hole behind dot_mode");
 static_assert(offsetof(StepArgs, box_hi) == offsetof(StepArgs, fused_iters) + 4 && offsetof(StepArgs, x_mid) == offsetof(StepArgs, fused_iters) + 8,
               "box_hi fills the hole behind fused_iters");
 

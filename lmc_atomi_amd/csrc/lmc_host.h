@@ -53,15 +53,14 @@ inline bool eprox_params_ok(int kind, float p0, float p1) {
 // Validated, self-contained copy of an lmc_problem.
 struct Problem {
   int H = 0, W = 0;
-  int data_kind = 0;        // the operator's kind, LMC_DATA_NONE .. LMC_DATA_MASK (a Poisson term: with pois = 1)
-  int wl2 = 0;              // LMC_DATA_WL2_*: per-pixel weights on the Gaussian term of that operator; y is [2][H][W], observation then weights
-  int hub = 0;              // LMC_DATA_HUBER_*: the Huber loss of that operator's residual; y is [2][H][W], observation then thresholds delta
-  int pois = 0;             // LMC_DATA_POISSON_*: the Poisson likelihood on that operator; y is [2][H][W], counts then background
+  int data_kind = 0;        // the operator's kind, LMC_DATA_NONE .. LMC_DATA_MASK, LMC_DATA_PSF, LMC_DATA_SPECTRAL
+  lmc::DataTerm term = lmc::kTermL2;     // the data term on that operator (lmc_common.h): Poisson, weighted Gaussian or Huber from LMC_DATA_POISSON_* / _WL2_* / _HUBER_*, and y is
+                                         // [2][H][W] then (counts and background, observation and weights, observation and thresholds)
   float sigma_f = 0.f;
   const float* y = nullptr;
   const float* mask = nullptr;
   lmc::BlurTaps taps{};
-  lmc::PsfOp psf;           // LMC_DATA_PSF / POISSON_PSF / WL2_PSF / HUBER_PSF: data_kind = LMC_DATA_PSF (with pois / wl2 / hub), the operator and its device table
+  lmc::PsfOp psf;           // LMC_DATA_PSF / POISSON_PSF / WL2_PSF / HUBER_PSF: data_kind = LMC_DATA_PSF (with the term), the operator and its device table
   lmc::FftOp fft;           // LMC_DATA_SPECTRAL: the planes at y_dev and the device buffers of whoever owns them
   int prior_kind = 0;
   float prior_sigma = 0.f;
@@ -256,9 +255,17 @@ int fill_taps(lmc::BlurTaps& T, const float* h, int kh, int kw, int oy, int ox);
 void default_betas(float* b, int n);
 int load_problem(const lmc_problem* p, Problem& q);
 int check_no_box(const Problem& q, const char* who, const char* why);
-int check_no_poisson(const Problem& q, const char* who, const char* why);
-int check_no_wl2(const Problem& q, const char* who, const char* why);
-int check_no_hub(const Problem& q, const char* who, const char* why);
+// One row per DataTerm, indexed by it (the row of kTermL2 is empty: the plain Gaussian term has no kernels of its own and nothing refuses it)
+struct TermInfo {
+  const char* name;         // in messages: "the Poisson data term"
+  const char* label;        // its kinds in lmc_atomi.h: "LMC_DATA_POISSON_*"
+  const char* warm;         // what the warm-started dual lacks for it
+  const char *pipe, *pipe_box, *tile, *tile_box;     // the kernel names launch_step reports
+  const char *v7_name, *v7_ops;                      // the refusal of step_variant 7: "this <v7_name> problem", "... 5 or 7 taps or <v7_ops>"
+};
+extern const TermInfo kTerms[lmc::kNumTerms];
+// The entry points that have no form of the data term `term` refuse a problem that carries it.
+int check_no_term(const Problem& q, lmc::DataTerm term, const char* who, const char* why);
 int check_no_psf(const Problem& q, const char* who, const char* why);
 int check_no_spectral(const Problem& q, const char* who, const char* why);
 // what the entry points that form the update a x - t grad f + b prox_g (MYULA, MYMALA, SK-ROCK, lmc_fused_eval) refuse: of the anisotropic TV prior
@@ -266,9 +273,7 @@ int check_no_spectral(const Problem& q, const char* who, const char* why);
 int check_step_problem(const Problem& q, float b);
 // the first refusal of each of those data terms alone (a non-convex term), for the callers that form no update (lmc_energies)
 int check_convex_terms(const Problem& q);
-bool wl2_pipe_covers(const lmc::StepArgs& A);       // the full-width pipeline has a weighted form of this launch
-bool hub_pipe_covers(const lmc::StepArgs& A);       // the full-width pipeline has a Huber form of this launch
-bool pois_pipe_covers(const lmc::StepArgs& A);      // the full-width pipeline has a Poisson form of this launch
+bool term_pipe_covers(const lmc::StepArgs& A);      // the full-width pipeline has a form of this launch's data term (Poisson, weighted, Huber)
 int make_step_args(const Problem& q, float a, float t, float b, float pt, float s, lmc::StepArgs& A);
 void sanitize_pointers(lmc::StepArgs& A);
 int variant_of(const Problem& q);

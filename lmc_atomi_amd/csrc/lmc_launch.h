@@ -61,14 +61,9 @@ hipError_t launch_cov_sketch(const float* x, int64_t C, int H, int W, int k, con
                              hipStream_t st);
 hipError_t launch_energies(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, double* g_out,
                            hipStream_t st);
-// ADDS the Poisson data term's value to f_out (zeroed by launch_energies): E.data_kind = the operator's kind, E.y = [2][H][W] counts, background
-hipError_t launch_energy_pois(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, hipStream_t st);
-// ADDS the weighted Gaussian data term's value to f_out (zeroed by launch_energies): E.data_kind = the operator's kind (identity, blur), E.y = [2][H][W]
-// observation, weights
-hipError_t launch_energy_wl2(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, hipStream_t st);
-// ADDS the Huber data term's value to f_out (zeroed by launch_energies): E.data_kind = the operator's kind (identity, blur), E.y = [2][H][W]
-// observation, thresholds
-hipError_t launch_energy_hub(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, hipStream_t st);
+// ADDS the value of the data term `term` (DataTerm: kTermPois, kTermWl2, kTermHub) to f_out (zeroed by launch_energies): E.data_kind = the operator's kind
+// (identity, blur; for Poisson the mask too), E.y = [2][H][W]: counts and background, observation and weights, observation and thresholds
+hipError_t launch_energy_term(int term, const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, hipStream_t st);
 // pieces of the exact early-exit path of the TV prox (lmc_problem.tv_rtol > 0)
 hipError_t launch_tv_objective(const float* x, const float* sol, int64_t n, int H, int W, float gam, const int* flag, double* obj, hipStream_t st);
 hipError_t launch_tv_rtol_decide(int64_t n, double* prev, double* cur, int* flag, int pass, double rtol, int* n_active, hipStream_t st);
@@ -214,6 +209,9 @@ enum PsfEpi {
   kPsfRhoHub,       // out = clamp(u - y, -delta, delta),  y = [2][H][W]: observation, thresholds (the Huber term)
   kPsfEnHub         // part[image][tile] = sum hub_h(u - y, delta)
 };
+// the residual and the energy epilogue of a data term, indexed by DataTerm (lmc_common.h)
+struct PsfTermEpi { PsfEpi rho, energy; };
+constexpr PsfTermEpi kPsfTermEpi[kNumTerms] = {{kPsfRhoL2, kPsfEnL2}, {kPsfRhoPois, kPsfEnPois}, {kPsfRhoWl2, kPsfEnWl2}, {kPsfRhoHub, kPsfEnHub}};
 // Host description of a validated PSF and the device table made from it.  tab (host) / tab_dev: [2][kPsfMax * kPsfKP] floats, direction 0 = H (taps
 // flipped, origin mirrored), 1 = H^T, each in the correlation form of the kernel: general g[b * kPsfKP + a], separable gu[kPsfKP] then gv[kPsfKP].
 struct PsfOp {
@@ -234,7 +232,7 @@ hipError_t launch_psf(const PsfOp& P, int adjoint, int epi, const float* x, floa
                       float a, float coef, hipStream_t st);
 // doubles `part` must hold for launch_psf_energy
 size_t psf_energy_partials(int64_t n_img, int H, int W);
-// f_out[c] += the data term's value at x_c (term: 0 Gaussian, 1 weighted, 2 Poisson, 3 Huber), float64 by partial sums in a fixed order
+// f_out[c] += the data term's value at x_c (term: DataTerm), float64 by partial sums in a fixed order
 hipError_t launch_psf_energy(const PsfOp& P, int term, const float* x, const float* y, int64_t n_img, int H, int W, float sigma_f, double* part,
                              double* f_out, hipStream_t st);
 }  // namespace lmc

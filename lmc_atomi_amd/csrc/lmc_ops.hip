@@ -455,123 +455,33 @@ hipError_t launch_energies(const float* x, int64_t n_img, const EnergyArgs& E, d
   return hipGetLastError();
 }
 
-// The Poisson data term's value (LMC_DATA_POISSON_*; lmc_atomi.h): f_out[i] += sigma_f sum_p phi_p((Op x_i)_p), u = Op x in fp32 with the operator's
-// arithmetic of energy_kernel, phi in float64 (pois_phi), a plain reduction at every width.  E.data_kind is the operator's kind, E.y the counts and
-// E.y + H W the background.
-__global__ __launch_bounds__(256) void energy_pois_kernel(const float* __restrict__ x, EnergyArgs E, double* __restrict__ f_out) {
-  __shared__ double scratch[4];
-  const int H = E.H, W = E.W;
-  const size_t img = (size_t)H * W;
-  const float* xi = x + (size_t)blockIdx.y * img;
-  double fa = 0.0;
-  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < img; p += (size_t)gridDim.x * blockDim.x) {
-    const int r = (int)(p / W), c = (int)(p - (size_t)r * W);
-    float u = xi[p];
-    if (E.data_kind == LMC_DATA_BLUR) {
-      float acc = 0.f;
-      for (int a = 0; a < E.blur.kh; ++a)
-        for (int b = 0; b < E.blur.kw; ++b) {
-          const int rr = r - a + E.blur.oy, cc = c - b + E.blur.ox;
-          if (rr >= 0 && rr < H && cc >= 0 && cc < W) acc = fmaf(E.blur.h[a * E.blur.kw + b], xi[(size_t)rr * W + cc], acc);
-        }
-      u = acc;
-    } else if (E.data_kind == LMC_DATA_MASK) {
-      u = E.mask[p] * u;
-    }
-    fa += pois_phi(u, E.y[p], E.y[img + p]);
-  }
-  const double ft = block_sum(fa, scratch);
-  if (threadIdx.x == 0) unsafeAtomicAdd(&f_out[blockIdx.y], (double)E.sigma_f * ft);
-}
+// The values of the data terms with a second plane of y: one kernel per term (DataTerm), names as before
+#define LMC_ENERGY_TERM kTermPois
+#define LMC_ENERGY_TERM_KERNEL energy_pois_kernel
+#include "lmc_energy_term_kernel.h"
+#undef LMC_ENERGY_TERM
+#undef LMC_ENERGY_TERM_KERNEL
+#define LMC_ENERGY_TERM kTermWl2
+#define LMC_ENERGY_TERM_KERNEL energy_wl2_kernel
+#include "lmc_energy_term_kernel.h"
+#undef LMC_ENERGY_TERM
+#undef LMC_ENERGY_TERM_KERNEL
+#define LMC_ENERGY_TERM kTermHub
+#define LMC_ENERGY_TERM_KERNEL energy_hub_kernel
+#include "lmc_energy_term_kernel.h"
+#undef LMC_ENERGY_TERM
+#undef LMC_ENERGY_TERM_KERNEL
 
-hipError_t launch_energy_pois(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, hipStream_t st) {
+hipError_t launch_energy_term(int term, const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, hipStream_t st) {
+  auto* const kern = term == kTermPois ? energy_pois_kernel : term == kTermWl2 ? energy_wl2_kernel : term == kTermHub ? energy_hub_kernel : nullptr;
+  if (!kern) return hipErrorInvalidValue;
   const size_t img = (size_t)E.H * E.W;
   int gx = (int)((img + 255) / 256);
   if (gx > 64) gx = 64;
   const int64_t ymax = 65535;
   for (int64_t z0 = 0; z0 < n_img; z0 += ymax) {
     const int nz = (int)((n_img - z0) < ymax ? (n_img - z0) : ymax);
-    hipLaunchKernelGGL(energy_pois_kernel, dim3(gx, nz), dim3(256), 0, st, x + z0 * img, E, f_out + z0);
-  }
-  return hipGetLastError();
-}
-
-// The weighted Gaussian data term's value (LMC_DATA_WL2_*; lmc_atomi.h): f_out[i] += sigma_f/2 sum_p w_p ((Op x_i)_p - y_p)^2, u = Op x in fp32 with the
-// operator's arithmetic of energy_kernel, w (u - y)^2 widened to and summed in float64, a plain reduction at every width.  E.data_kind is the
-// operator's kind (identity or blur), E.y the observation and E.y + H W the weights.
-__global__ __launch_bounds__(256) void energy_wl2_kernel(const float* __restrict__ x, EnergyArgs E, double* __restrict__ f_out) {
-  __shared__ double scratch[4];
-  const int H = E.H, W = E.W;
-  const size_t img = (size_t)H * W;
-  const float* xi = x + (size_t)blockIdx.y * img;
-  double fa = 0.0;
-  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < img; p += (size_t)gridDim.x * blockDim.x) {
-    const int r = (int)(p / W), c = (int)(p - (size_t)r * W);
-    float u = xi[p];
-    if (E.data_kind == LMC_DATA_BLUR) {
-      float acc = 0.f;
-      for (int a = 0; a < E.blur.kh; ++a)
-        for (int b = 0; b < E.blur.kw; ++b) {
-          const int rr = r - a + E.blur.oy, cc = c - b + E.blur.ox;
-          if (rr >= 0 && rr < H && cc >= 0 && cc < W) acc = fmaf(E.blur.h[a * E.blur.kw + b], xi[(size_t)rr * W + cc], acc);
-        }
-      u = acc;
-    }
-    const double d = (double)u - (double)E.y[p];
-    fa += (double)E.y[img + p] * d * d;
-  }
-  const double ft = block_sum(fa, scratch);
-  if (threadIdx.x == 0) unsafeAtomicAdd(&f_out[blockIdx.y], 0.5 * (double)E.sigma_f * ft);
-}
-
-hipError_t launch_energy_wl2(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, hipStream_t st) {
-  const size_t img = (size_t)E.H * E.W;
-  int gx = (int)((img + 255) / 256);
-  if (gx > 64) gx = 64;
-  const int64_t ymax = 65535;
-  for (int64_t z0 = 0; z0 < n_img; z0 += ymax) {
-    const int nz = (int)((n_img - z0) < ymax ? (n_img - z0) : ymax);
-    hipLaunchKernelGGL(energy_wl2_kernel, dim3(gx, nz), dim3(256), 0, st, x + z0 * img, E, f_out + z0);
-  }
-  return hipGetLastError();
-}
-
-// The Huber data term's value (LMC_DATA_HUBER_*; lmc_atomi.h): f_out[i] += sigma_f sum_p h_delta_p((Op x_i)_p - y_p), u = Op x in fp32 with the operator's
-// arithmetic of energy_kernel, the residual r = u - y in fp32 (the operand the step kernels clamp), its branch value (hub_h, lmc_device.h) widened to and
-// summed in float64 in the order of energy_wl2_kernel.  E.data_kind is the operator's kind (identity or blur), E.y the observation and E.y + H W the
-// thresholds: delta = 0 takes the linear branch, which gives 0; delta = +inf the quadratic one, so no inf * 0 is formed.
-__global__ __launch_bounds__(256) void energy_hub_kernel(const float* __restrict__ x, EnergyArgs E, double* __restrict__ f_out) {
-  __shared__ double scratch[4];
-  const int H = E.H, W = E.W;
-  const size_t img = (size_t)H * W;
-  const float* xi = x + (size_t)blockIdx.y * img;
-  double fa = 0.0;
-  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < img; p += (size_t)gridDim.x * blockDim.x) {
-    const int r = (int)(p / W), c = (int)(p - (size_t)r * W);
-    float u = xi[p];
-    if (E.data_kind == LMC_DATA_BLUR) {
-      float acc = 0.f;
-      for (int a = 0; a < E.blur.kh; ++a)
-        for (int b = 0; b < E.blur.kw; ++b) {
-          const int rr = r - a + E.blur.oy, cc = c - b + E.blur.ox;
-          if (rr >= 0 && rr < H && cc >= 0 && cc < W) acc = fmaf(E.blur.h[a * E.blur.kw + b], xi[(size_t)rr * W + cc], acc);
-        }
-      u = acc;
-    }
-    fa += hub_h(u - E.y[p], E.y[img + p]);
-  }
-  const double ft = block_sum(fa, scratch);
-  if (threadIdx.x == 0) unsafeAtomicAdd(&f_out[blockIdx.y], (double)E.sigma_f * ft);
-}
-
-hipError_t launch_energy_hub(const float* x, int64_t n_img, const EnergyArgs& E, double* f_out, hipStream_t st) {
-  const size_t img = (size_t)E.H * E.W;
-  int gx = (int)((img + 255) / 256);
-  if (gx > 64) gx = 64;
-  const int64_t ymax = 65535;
-  for (int64_t z0 = 0; z0 < n_img; z0 += ymax) {
-    const int nz = (int)((n_img - z0) < ymax ? (n_img - z0) : ymax);
-    hipLaunchKernelGGL(energy_hub_kernel, dim3(gx, nz), dim3(256), 0, st, x + z0 * img, E, f_out + z0);
+    hipLaunchKernelGGL(kern, dim3(gx, nz), dim3(256), 0, st, x + z0 * img, E, f_out + z0);
   }
   return hipGetLastError();
 }

@@ -41,34 +41,31 @@ int load_problem(const lmc_problem* p, Problem& q) {
   if (p->H < 1 || p->W < 1 || (int64_t)p->H * p->W > (int64_t)1 << 30) return fail(LMC_E_INVALID, "bad image size %dx%d", p->H, p->W);
   q.H = p->H; q.W = p->W;
   q.data_kind = p->data_kind;
-  // the Poisson likelihood: inside the library the operator's kind plus a flag (every test on LMC_DATA_BLUR / IDENTITY / MASK serves both; the entry
-  // points without a Poisson form refuse the flag: check_no_poisson, check_step_problem)
-  if (p->data_kind >= LMC_DATA_POISSON_IDENTITY && p->data_kind <= LMC_DATA_POISSON_MASK) {
-    q.data_kind = p->data_kind - LMC_DATA_POISSON_IDENTITY + LMC_DATA_IDENTITY;
-    q.pois = 1;
-  }
-  // per-pixel weights on the Gaussian term: the same arrangement (check_no_wl2, check_step_problem)
-  if (p->data_kind == LMC_DATA_WL2_IDENTITY || p->data_kind == LMC_DATA_WL2_BLUR) {
-    // there is no weighted mask kind: a caller that hands over a mask with the weights would get it silently ignored -- say so instead (w = m is the mask)
-    if (p->mask_dev) return fail(LMC_E_INVALID, "data_kind %d (weighted Gaussian term) takes no mask_dev: there is no weighted mask kind, put the mask into the weights", p->data_kind);
-    q.data_kind = p->data_kind == LMC_DATA_WL2_BLUR ? LMC_DATA_BLUR : LMC_DATA_IDENTITY;
-    q.wl2 = 1;
-  }
-  // the Huber loss of the residual: the same arrangement again (check_no_hub, check_step_problem); 13, 14: the small operators, 15: the large PSF below
-  if (p->data_kind >= LMC_DATA_HUBER_IDENTITY && p->data_kind <= LMC_DATA_HUBER_PSF) {
-    // there is no Huber mask kind either: delta = 0 is the unobserved pixel
-    if (p->mask_dev) return fail(LMC_E_INVALID, "data_kind %d (Huber data term) takes no mask_dev: there is no Huber mask kind, put the mask into the thresholds (delta = 0)", p->data_kind);
-    if (p->data_kind != LMC_DATA_HUBER_PSF) q.data_kind = p->data_kind == LMC_DATA_HUBER_BLUR ? LMC_DATA_BLUR : LMC_DATA_IDENTITY;
-    q.hub = 1;
-  }
-  // a large PSF: one operator kind of its own plus the same flags (check_step_problem, check_no_psf) -- NOT LMC_DATA_BLUR, whose taps stay empty: a path
-  // that was not taught about the PSF meets an unknown data kind, not a blur without taps
-  if ((p->data_kind >= LMC_DATA_PSF && p->data_kind <= LMC_DATA_WL2_PSF) || p->data_kind == LMC_DATA_HUBER_PSF) {
-    if (p->kh || p->kw || p->oy || p->ox) return fail(LMC_E_INVALID, "data_kind %d (large PSF) takes its geometry in the psf_* fields: kh = kw = oy = ox = 0", p->data_kind);
-    if (p->data_kind == LMC_DATA_WL2_PSF && p->mask_dev) return fail(LMC_E_INVALID, "data_kind %d (weighted Gaussian term) takes no mask_dev: put the mask into the weights", p->data_kind);
-    q.data_kind = LMC_DATA_PSF;
-    q.pois = p->data_kind == LMC_DATA_POISSON_PSF;
-    q.wl2 = p->data_kind == LMC_DATA_WL2_PSF;
+  // Inside the library a public kind is the operator's kind plus the data term (every test on LMC_DATA_BLUR / IDENTITY / MASK / PSF serves every term; the
+  // entry points without a form of a term refuse it: check_no_term, check_step_problem).  A large PSF is one operator kind of its own -- NOT LMC_DATA_BLUR,
+  // whose taps stay empty: a path that was not taught about the PSF meets an unknown data kind, not a blur without taps.
+  // no_mask: the term has no mask kind, and a caller that hands over a mask with the second plane would get it silently ignored -- say so instead
+  struct KindMap { int op; lmc::DataTerm term; const char* no_mask; };
+  static const char* const kWl2Mask = "(weighted Gaussian term) takes no mask_dev: there is no weighted mask kind, put the mask into the weights";
+  static const char* const kHubMask = "(Huber data term) takes no mask_dev: there is no Huber mask kind, put the mask into the thresholds (delta = 0)";
+  static const KindMap kKinds[LMC_DATA_HUBER_PSF + 1] = {
+      {LMC_DATA_NONE, lmc::kTermL2, nullptr},      {LMC_DATA_IDENTITY, lmc::kTermL2, nullptr},  {LMC_DATA_BLUR, lmc::kTermL2, nullptr},   {LMC_DATA_MASK, lmc::kTermL2, nullptr},
+      {LMC_DATA_IDENTITY, lmc::kTermPois, nullptr}, {LMC_DATA_BLUR, lmc::kTermPois, nullptr},    {LMC_DATA_MASK, lmc::kTermPois, nullptr},
+      {LMC_DATA_IDENTITY, lmc::kTermWl2, kWl2Mask}, {LMC_DATA_BLUR, lmc::kTermWl2, kWl2Mask},
+      {LMC_DATA_PSF, lmc::kTermL2, nullptr},        {LMC_DATA_PSF, lmc::kTermPois, nullptr},
+      {LMC_DATA_PSF, lmc::kTermWl2, "(weighted Gaussian term) takes no mask_dev: put the mask into the weights"},
+      {LMC_DATA_SPECTRAL, lmc::kTermL2, nullptr},
+      {LMC_DATA_IDENTITY, lmc::kTermHub, kHubMask}, {LMC_DATA_BLUR, lmc::kTermHub, kHubMask},    {LMC_DATA_PSF, lmc::kTermHub, kHubMask}};
+  if (p->data_kind >= 0 && p->data_kind <= LMC_DATA_HUBER_PSF) {     // (any other kind: "unknown data_kind" below)
+    const KindMap& k = kKinds[p->data_kind];
+    const bool bad_mask = k.no_mask && p->mask_dev;
+    const bool bad_geometry = k.op == LMC_DATA_PSF && (p->kh || p->kw || p->oy || p->ox);
+    // (with both wrong the Huber PSF kind names the mask, the weighted PSF kind the geometry)
+    if (bad_geometry && !(bad_mask && k.term == lmc::kTermHub))
+      return fail(LMC_E_INVALID, "data_kind %d (large PSF) takes its geometry in the psf_* fields: kh = kw = oy = ox = 0", p->data_kind);
+    if (bad_mask) return fail(LMC_E_INVALID, "data_kind %d %s", p->data_kind, k.no_mask);
+    q.data_kind = k.op;
+    q.term = k.term;
   }
   q.sigma_f = p->sigma_f;
   q.y = p->y_dev;
@@ -221,22 +218,19 @@ int check_no_box(const Problem& q, const char* who, const char* why) {
   return fail(LMC_E_UNSUPPORTED, "%s does not take a box constraint (lmc_problem.box_enable): %s", who, why);
 }
 
-// The entry points that have no form of the Poisson likelihood refuse a problem that carries one.
-int check_no_poisson(const Problem& q, const char* who, const char* why) {
-  if (!q.pois) return LMC_OK;
-  return fail(LMC_E_UNSUPPORTED, "%s does not take the Poisson data term (LMC_DATA_POISSON_*): %s", who, why);
-}
+// One row per DataTerm (lmc_host.h)
+const TermInfo kTerms[lmc::kNumTerms] = {
+    {},
+    {"the Poisson data term", "LMC_DATA_POISSON_*", "has no Poisson form", "myula_step_pipe_pois_kernel", "myula_step_pipe_pois_box_kernel", "myula_step_tile_pois_kernel",
+     "myula_step_tile_pois_box_kernel", "Poisson", "a pointwise data term"},
+    {"the weighted Gaussian data term", "LMC_DATA_WL2_*", "has no weighted form", "myula_step_pipe_wl2_kernel", "myula_step_pipe_wl2_box_kernel", "myula_step_tile_wl2_kernel",
+     "myula_step_tile_wl2_box_kernel", "weighted Gaussian", "the identity"},
+    {"the Huber data term", "LMC_DATA_HUBER_*", "has no Huber form", "myula_step_pipe_hub_kernel", "myula_step_pipe_hub_box_kernel", "myula_step_tile_hub_kernel",
+     "myula_step_tile_hub_box_kernel", "Huber", "the identity"}};
 
-// The entry points that have no form of the weighted Gaussian data term refuse a problem that carries one.
-int check_no_wl2(const Problem& q, const char* who, const char* why) {
-  if (!q.wl2) return LMC_OK;
-  return fail(LMC_E_UNSUPPORTED, "%s does not take the weighted Gaussian data term (LMC_DATA_WL2_*): %s", who, why);
-}
-
-// The entry points that have no form of the Huber data term refuse a problem that carries one.
-int check_no_hub(const Problem& q, const char* who, const char* why) {
-  if (!q.hub) return LMC_OK;
-  return fail(LMC_E_UNSUPPORTED, "%s does not take the Huber data term (LMC_DATA_HUBER_*): %s", who, why);
+int check_no_term(const Problem& q, lmc::DataTerm term, const char* who, const char* why) {
+  if (q.term != term || term == lmc::kTermL2) return LMC_OK;
+  return fail(LMC_E_UNSUPPORTED, "%s does not take %s (%s): %s", who, kTerms[term].name, kTerms[term].label, why);
 }
 
 // The entry points that have no form of the large PSF refuse a problem that carries one.
@@ -254,14 +248,16 @@ int check_no_spectral(const Problem& q, const char* who, const char* why) {
 // The data terms with step kernels of their own, in the order their refusals are made: its name in the messages, what the warm-started dual lacks
 // for it, and whether its step is a fused kernel of the term (the tiled kernel's and the full-width pipeline's instantiations: no Haar prior, variants
 // 0, 1, 7) or splits into the term's launches around the step of a problem without a data term (every prior and variant of that problem).
+// The rows of kTerms, then the large PSF and the spectral term.
 struct DataTermRules { const char *name, *warm; bool own_kernels; };
-constexpr int kNDataTerms = 5;
-constexpr DataTermRules kDataTerms[kNDataTerms] = {{"the Poisson data term", "has no Poisson form", true},
-                                         {"the weighted Gaussian data term", "has no weighted form", true},
-                                         {"the Huber data term", "has no Huber form", true},
-                                         {"a large PSF", "is not built for it", false},
-                                         {"the spectral data term", "is not built for it", false}};
-#define LMC_DATA_TERMS_OF(q) {(q).pois != 0, (q).wl2 != 0, (q).hub != 0, (q).psf.on != 0, (q).fft.on != 0}
+constexpr int kNDataTerms = 3;
+static int data_terms_of(const Problem& q, DataTermRules (&r)[kNDataTerms]) {
+  int n = 0;
+  if (q.term != lmc::kTermL2) r[n++] = {kTerms[q.term].name, kTerms[q.term].warm, true};
+  if (q.psf.on) r[n++] = {"a large PSF", "is not built for it", false};
+  if (q.fft.on) r[n++] = {"the spectral data term", "is not built for it", false};
+  return n;
+}
 
 static int check_convex_term(const Problem& q, const DataTermRules& r) {
   if (q.ncvx_kind == LMC_NCVX_NONE) return LMC_OK;
@@ -269,9 +265,9 @@ static int check_convex_term(const Problem& q, const DataTermRules& r) {
 }
 
 int check_convex_terms(const Problem& q) {
-  const bool has[kNDataTerms] = LMC_DATA_TERMS_OF(q);
-  for (int i = 0; i < kNDataTerms; ++i)
-    if (has[i]) { const int rc = check_convex_term(q, kDataTerms[i]); if (rc) return rc; }
+  DataTermRules terms[kNDataTerms];
+  const int n = data_terms_of(q, terms);
+  for (int i = 0; i < n; ++i) { const int rc = check_convex_term(q, terms[i]); if (rc) return rc; }
   return LMC_OK;
 }
 
@@ -283,11 +279,12 @@ int check_step_problem(const Problem& q, float b) {
     if (b != 0.f && q.tv_niter_asked < 1)
       return fail(LMC_E_INVALID, "LMC_PRIOR_TV_ANISO: the prox needs tv_niter in 1..%d (got 0)", lmc::kMaxTvIters);
   }
-  const bool has[kNDataTerms] = LMC_DATA_TERMS_OF(q);
+  DataTermRules terms[kNDataTerms];
+  const int n = data_terms_of(q, terms);
   const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
-  for (int i = 0; i < kNDataTerms; ++i) {
-    const DataTermRules& r = kDataTerms[i];
-    if (!has[i] || (r.own_kernels && q.psf.on)) continue;     // (Poisson / weighted / Huber on a large PSF: the PSF's rules -- its step launch has no data term)
+  for (int i = 0; i < n; ++i) {
+    const DataTermRules& r = terms[i];
+    if (r.own_kernels && q.psf.on) continue;     // (Poisson / weighted / Huber on a large PSF: the PSF's rules -- its step launch has no data term)
     const int rc = check_convex_term(q, r);
     if (rc) return rc;
     if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "%s with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0", r.name);
@@ -306,9 +303,7 @@ int make_step_args(const Problem& q, float a, float t, float b, float pt, float 
   std::memset(&A, 0, sizeof A);
   A.H = q.H; A.W = q.W;
   A.data_kind = (t == 0.f) ? LMC_DATA_NONE : q.data_kind;   // skip the stencil work if its weight is zero
-  A.pois = (q.pois && A.data_kind != LMC_DATA_NONE) ? 1 : 0;
-  A.wl2 = (q.wl2 && A.data_kind != LMC_DATA_NONE) ? 1 : 0;
-  A.hub = (q.hub && A.data_kind != LMC_DATA_NONE) ? 1 : 0;
+  A.term = A.data_kind != LMC_DATA_NONE ? q.term : lmc::kTermL2;
   A.sigma_f = q.sigma_f;
   A.y = q.y; A.mask = q.mask;
   A.blur = q.taps;
@@ -448,26 +443,17 @@ float tol_of(const Problem& q) { return q.implicit_tol > 0.f ? q.implicit_tol : 
 // it covers the configuration (W <= 512, separable blur <= 7x7, supported K), else the LDS-tiled kernel.
 static hipError_t launch_step_nobox(const lmc::StepArgs& A_in, int variant, Workspace& ws, hipStream_t st, const char** name);
 
-// The Poisson data term.  The full-width pipeline's Poisson instantiations where they cover the problem (isotropic TV, exactly 10 dual iterations, W > 128,
-// separable blur or pointwise data term; auto and 7), the tiled kernel's everywhere else and for every other prior (auto and 1): TV (either form, box or
-// not) and none / l2 / l1 run inside that kernel; a closed-form prior of prox.py and the box of a separable prior are formed by the elementwise launch
-// before it and consumed as a ready-made prox.
-bool pois_pipe_covers(const lmc::StepArgs& A) { return A.pois && A.prior_kind == LMC_PRIOR_TV_ISO && lmc::pipe_links(A) == 1; }
+// The Poisson, weighted Gaussian and Huber data terms (kTerms).  The full-width pipeline's instantiations of the term where they cover the problem (isotropic
+// TV, exactly 10 dual iterations, W > 128, separable blur or pointwise data term; auto and 7), the tiled kernel's everywhere else and for every other prior
+// (auto and 1): TV (either form, box or not) and none / l2 / l1 run inside that kernel; a closed-form prior of prox.py and the box of a separable prior are
+// formed by the elementwise launch before it and consumed as a ready-made prox.
+bool term_pipe_covers(const lmc::StepArgs& A) { return A.term != lmc::kTermL2 && A.prior_kind == LMC_PRIOR_TV_ISO && lmc::pipe_links(A) == 1; }
 
-// The weighted Gaussian data term (kWl2Names) takes the same route with kernels of its own: the pipe where pipe_links == 1 covers the problem, the
-// tile kernel for everything else.
-bool wl2_pipe_covers(const lmc::StepArgs& A) { return A.wl2 && A.prior_kind == LMC_PRIOR_TV_ISO && lmc::pipe_links(A) == 1; }
-
-// The Huber data term (kHubNames): the same route again.
-bool hub_pipe_covers(const lmc::StepArgs& A) { return A.hub && A.prior_kind == LMC_PRIOR_TV_ISO && lmc::pipe_links(A) == 1; }
-
-// the four kernel names of a data term that has instantiations of its own: pipe, pipe + box, tile, tile + box
-struct TermNames { const char *pipe, *pipe_box, *tile, *tile_box; };
-
-static hipError_t launch_step_term(const lmc::StepArgs& A_in, int variant, bool pipe_covers, const TermNames& nm, Workspace& ws, hipStream_t st, const char** name) {
+static hipError_t launch_step_term(const lmc::StepArgs& A_in, int variant, Workspace& ws, hipStream_t st, const char** name) {
+  const TermInfo& nm = kTerms[A_in.term];
   float *const state0 = ws.state[0].p, *const state1 = ws.state[1].p, *const pxbuf = ws.prox.p;
   if (variant != 0 && variant != 1 && variant != 7) return hipErrorInvalidConfiguration;
-  if (variant != 1 && pipe_covers) {
+  if (variant != 1 && term_pipe_covers(A_in)) {
     if (name) *name = A_in.box ? nm.pipe_box : nm.pipe;
     return lmc::launch_step_pipe(A_in, st, nullptr, nullptr, 1);
   }
@@ -492,10 +478,6 @@ static hipError_t launch_step_term(const lmc::StepArgs& A_in, int variant, bool 
   return lmc::launch_step_tile(A, st);
 }
 
-constexpr TermNames kPoisNames = {"myula_step_pipe_pois_kernel", "myula_step_pipe_pois_box_kernel", "myula_step_tile_pois_kernel", "myula_step_tile_pois_box_kernel"};
-constexpr TermNames kWl2Names = {"myula_step_pipe_wl2_kernel", "myula_step_pipe_wl2_box_kernel", "myula_step_tile_wl2_kernel", "myula_step_tile_wl2_box_kernel"};
-constexpr TermNames kHubNames = {"myula_step_pipe_hub_kernel", "myula_step_pipe_hub_box_kernel", "myula_step_tile_hub_kernel", "myula_step_tile_hub_box_kernel"};
-
 // The box-constrained forms.  Separable priors: one elementwise launch forms clip(prox) into pxbuf, then the step of the variant asked for consumes it.
 // TV priors: the pipe kernel's box instantiations (isotropic; auto, 7, 8) or the tile kernel's (either form; auto, 1); a forced variant without a box
 // form is not covered.
@@ -515,7 +497,7 @@ static hipError_t launch_step_around(const lmc::StepArgs& A, int variant, const 
     return adjoint(true, A.a, coef);
   }
   lmc::StepArgs B = A;
-  B.data_kind = LMC_DATA_NONE; B.t = 0.f; B.pois = 0; B.wl2 = 0; B.hub = 0;
+  B.data_kind = LMC_DATA_NONE; B.t = 0.f; B.term = lmc::kTermL2;
   e = launch_step(B, variant, q, ws, st, name);      // (a wavelet prior: launch_step has formed its prox already, B carries it)
   if (e != hipSuccess) return e;
   return adjoint(false, 0.f, coef);
@@ -525,7 +507,7 @@ static hipError_t launch_step_around(const lmc::StepArgs& A, int variant, const 
 static hipError_t launch_step_psf(const lmc::StepArgs& A, int variant, const Problem& q, Workspace& ws, hipStream_t st, const char** name) {
   const lmc::PsfOp& P = q.psf;
   if (!P.on || !P.tab_dev || !P.resid) return hipErrorInvalidConfiguration;
-  const int rho = A.pois ? lmc::kPsfRhoPois : A.wl2 ? lmc::kPsfRhoWl2 : A.hub ? lmc::kPsfRhoHub : lmc::kPsfRhoL2;
+  const int rho = lmc::kPsfTermEpi[A.term].rho;
   return launch_step_around(A, variant, q, ws, st, name, "psf_conv_kernel",
       [&] { return lmc::launch_psf(P, 0, rho, A.x_in, P.resid, nullptr, A.y, A.C, A.H, A.W, 0.f, 0.f, st); },
       [&](bool alone, float a, float coef) {
@@ -563,9 +545,7 @@ hipError_t launch_step(const lmc::StepArgs& A_in, int variant, const Problem& q,
   }
   if (A_in.data_kind == LMC_DATA_PSF) return launch_step_psf(A_in, variant, q, ws, st, name);
   if (A_in.data_kind == LMC_DATA_SPECTRAL) return launch_step_fft(A_in, variant, q, ws, st, name);
-  if (A_in.pois) return launch_step_term(A_in, variant, pois_pipe_covers(A_in), kPoisNames, ws, st, name);
-  if (A_in.wl2) return launch_step_term(A_in, variant, wl2_pipe_covers(A_in), kWl2Names, ws, st, name);
-  if (A_in.hub) return launch_step_term(A_in, variant, hub_pipe_covers(A_in), kHubNames, ws, st, name);
+  if (A_in.term != lmc::kTermL2) return launch_step_term(A_in, variant, ws, st, name);
   if (!A_in.box) return launch_step_nobox(A_in, variant, ws, st, name);
   lmc::StepArgs A = A_in;
   if (A.prior_kind != LMC_PRIOR_TV_ISO) {

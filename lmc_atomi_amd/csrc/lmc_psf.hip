@@ -128,10 +128,10 @@ size_t psf_energy_partials(int64_t n_img, int H, int W) {
 
 hipError_t launch_psf_energy(const PsfOp& P, int term, const float* x, const float* y, int64_t n_img, int H, int W, float sigma_f, double* part,
                              double* f_out, hipStream_t st) {
-  if (term < 0 || term > 3 || !x || !y || !part || !f_out || n_img < 1) return hipErrorInvalidValue;
+  if (term < 0 || term >= kNumTerms || !x || !y || !part || !f_out || n_img < 1) return hipErrorInvalidValue;
   PsfArgs A = psf_args(P, 0, H, W);
   A.x = x; A.y = y; A.part = part;
-  hipError_t e = psf_launch_all(P, term == 0 ? kPsfEnL2 : term == 1 ? kPsfEnWl2 : term == 2 ? kPsfEnPois : kPsfEnHub, A, n_img, st);
+  hipError_t e = psf_launch_all(P, kPsfTermEpi[term].energy, A, n_img, st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(psf_energy_finish_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, st, part, n_img, A.tiles_x * A.tiles_y,
                      (double)sigma_f, f_out);

@@ -104,20 +104,12 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   s->moments = cfg->moments; s->burn_in = cfg->burn_in; s->thin = cfg->thin < 1 ? 1 : cfg->thin;
   rc = rebuild_base(s);
   if (rc) { delete s; return rc; }
-  if (s->prob.pois && variant_of(s->prob) == 7 && !pois_pipe_covers(s->base)) {
+  // (a Huber term on a large PSF is left to the PSF's own rules here; the Poisson and weighted ones on a PSF are refused by this text)
+  if (s->prob.term != lmc::kTermL2 && !(s->prob.term == lmc::kTermHub && s->prob.psf.on) && variant_of(s->prob) == 7 && !term_pipe_covers(s->base)) {
+    const TermInfo& t = kTerms[s->prob.term];
     delete s;
-    return fail(LMC_E_UNSUPPORTED, "step_variant 7 (pipe) does not cover this Poisson problem: isotropic TV with 10 dual iterations (after tv_lagged_output), "
-                "W > 128, separable blur of 5 or 7 taps or a pointwise data term; use 0 (auto) or 1 (tile)");
-  }
-  if (s->prob.wl2 && variant_of(s->prob) == 7 && !wl2_pipe_covers(s->base)) {
-    delete s;
-    return fail(LMC_E_UNSUPPORTED, "step_variant 7 (pipe) does not cover this weighted Gaussian problem: isotropic TV with 10 dual iterations (after "
-                "tv_lagged_output), W > 128, separable blur of 5 or 7 taps or the identity; use 0 (auto) or 1 (tile)");
-  }
-  if (s->prob.hub && !s->prob.psf.on && variant_of(s->prob) == 7 && !hub_pipe_covers(s->base)) {
-    delete s;
-    return fail(LMC_E_UNSUPPORTED, "step_variant 7 (pipe) does not cover this Huber problem: isotropic TV with 10 dual iterations (after "
-                "tv_lagged_output), W > 128, separable blur of 5 or 7 taps or the identity; use 0 (auto) or 1 (tile)");
+    return fail(LMC_E_UNSUPPORTED, "step_variant 7 (pipe) does not cover this %s problem: isotropic TV with 10 dual iterations (after tv_lagged_output), "
+                "W > 128, separable blur of 5 or 7 taps or %s; use 0 (auto) or 1 (tile)", t.v7_name, t.v7_ops);
   }
   if (s->prob.tv_rtol > 0.f && s->base.prior_kind == LMC_PRIOR_TV_ISO && s->prob.tv_warm) { delete s; return fail(LMC_E_UNSUPPORTED, "tv_rtol > 0 and tv_warm exclude each other"); }
   const size_t n = (size_t)s->C * s->prob.H * s->prob.W;
@@ -136,9 +128,9 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     s->pol_bg_wgs = q.moments_bg_wgs > 0 ? q.moments_bg_wgs : env_int("LMC_MOMENTS_BG_WGS", -1);
     // One iteration per launch (the pair kernels have no form of it) wherever an iteration is more than the one fused launch:
     //   prox_scale, box, wav.on   the prox is a launch of its own before every step (array-valued epsg, the clamp, the wavelet transforms)
-    //   wl2, hub, pois            the weighted Gaussian, the Huber and the Poisson data terms have kernels of their own, none of them a pair kernel
+    //   term                      the weighted Gaussian, the Huber and the Poisson data terms have kernels of their own, none of them a pair kernel
     //   psf.on, fft.on            the large PSF and the spectral data term are three launches per iteration
-    if (q.prox_scale || q.box || q.wav.on || q.wl2 || q.hub || q.pois || q.psf.on || q.fft.on) { s->pol_pair = 0; s->pol_blockpair = 0; }
+    if (q.prox_scale || q.box || q.wav.on || q.term != lmc::kTermL2 || q.psf.on || q.fft.on) { s->pol_pair = 0; s->pol_blockpair = 0; }
   }
   if (e == hipSuccess && s->prob.tv_warm) {
     lmc::StepArgs probe = s->base;
@@ -224,7 +216,7 @@ static int sampler_update(lmc_sampler* s, const float* x_in, float* x_out, bool 
   lmc::StepArgs A = s->base;
   if (fused) *fused = false;
   // (a weighted Gaussian or a Huber data term: its pipe kernels form no by-products -- the caller takes f and g from sampler_energies_at, as for strips)
-  if (f_out && g_out && !s->prob.wl2 && !s->prob.hub && (variant_of(s->prob) == 0 || variant_of(s->prob) == 7) && s->prob.ncvx_kind == LMC_NCVX_NONE && s->prob.prior_kind == LMC_PRIOR_TV_ISO) {
+  if (f_out && g_out && s->prob.term != lmc::kTermWl2 && s->prob.term != lmc::kTermHub && (variant_of(s->prob) == 0 || variant_of(s->prob) == 7) && s->prob.ncvx_kind == LMC_NCVX_NONE && s->prob.prior_kind == LMC_PRIOR_TV_ISO) {
     // The pipe kernel returns f(x_in), g(x_in) as by-products where one launch WITH them covers the problem: the probe carries the outputs, since
     // they narrow the coverage (no column strips, a blur only).  Elsewhere the launch below runs without them -- on whatever kernel covers the
     // update alone, the strips and the pointwise data terms of the pipe kernel included -- and the caller forms the energies itself.
@@ -530,7 +522,7 @@ int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   if (s->ws.tv_exit >= 0) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA with tv_rtol > 0 is not built (use the fixed-count prox, tv_rtol = 0)"); }
   if (s->prob.prox_scale) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA takes a scalar epsg (the reference's array-valued epsg is MYULA's, algs.py:509)"); }
   if (s->prob.psf.on) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_psf(q, "MYMALA", "its Metropolis ratio is pinned for the fused step and its energy by-products, which the three-launch PSF step does not form; use MYULA or SK-ROCK"); }
-  if (s->prob.pois) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_poisson(q, "MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK"); }
+  if (s->prob.term == lmc::kTermPois) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_term(q, lmc::kTermPois, "MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK"); }
   if (s->prob.box) { const lmc::host::Problem q = s->prob; lmc_sampler_destroy(s); return check_no_box(q, "MYMALA", "its target would be +infinity outside the box, where MYULA's proposals land; use MYULA"); }
   if (s->prob.prior_kind == LMC_PRIOR_EPROX) { lmc_sampler_destroy(s); return fail(LMC_E_UNSUPPORTED, "MYMALA does not take a closed-form prior (LMC_PRIOR_EPROX): the prior has a prox and no value g(x), so its Metropolis target exp(-f - epsg g) is undefined; use MYULA"); }
   s->kind = 2;
@@ -831,9 +823,9 @@ int lmc_ulpda_create(const lmc_ulpda_config* cfg, lmc_sampler** out) {
   lmc_problem pr = cfg->problem;
   if (pr.prior_kind == LMC_PRIOR_TV_ISO && pr.tv_niter < 1) pr.tv_niter = 1;   // unused by ULPDA; keeps the loader happy
   rc = load_problem(&pr, s->prob);
-  if (!rc) rc = check_no_hub(s->prob, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Huber loss under an operator; use MYULA");
-  if (!rc) rc = check_no_wl2(s->prob, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f Op^T W Op)^{-1}, which is not built; use MYULA");
-  if (!rc) rc = check_no_poisson(s->prob, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA");
+  if (!rc) rc = check_no_term(s->prob, lmc::kTermHub, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Huber loss under an operator; use MYULA");
+  if (!rc) rc = check_no_term(s->prob, lmc::kTermWl2, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f Op^T W Op)^{-1}, which is not built; use MYULA");
+  if (!rc) rc = check_no_term(s->prob, lmc::kTermPois, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA");
   if (!rc) rc = check_no_psf(s->prob, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f H^T H)^{-1}, which is not built for a large PSF; use MYULA");
   if (!rc) rc = check_no_spectral(s->prob, "ULPDA", "its primal step through lmc_l2_prox's closed form is not wired into the primal-dual loop; use MYULA");
   if (!rc) rc = check_no_box(s->prob, "ULPDA", "its prior enters through the dual ball of g o A, which has no box form; use MYULA");

@@ -42,12 +42,10 @@ int pipe_links(const StepArgs& a) {
   if (a.tv_aniso && (n % 10 != 0 || a.f_out || a.g_out)) return 0;
   // box constraint (a.box; lmc_step_pipe_box.hip): the same, isotropic prior only
   if (a.box && (n % 10 != 0 || a.f_out || a.g_out || a.tv_aniso)) return 0;
-  // Poisson data term (a.pois; lmc_step_pipe_pois.hip): one launch of exactly 10, isotropic prior, no energy by-products
-  if (a.pois && (n != 10 || a.f_out || a.g_out || a.tv_aniso || a.ncvx_kind != LMC_NCVX_NONE || a.extra)) return 0;
-  // weighted Gaussian data term (a.wl2; lmc_step_pipe_wl2.hip): the same coverage; identity or blur (there is no weighted mask kind)
-  if (a.wl2 && (n != 10 || a.f_out || a.g_out || a.tv_aniso || a.ncvx_kind != LMC_NCVX_NONE || a.extra || a.data_kind == LMC_DATA_MASK)) return 0;
-  // Huber data term (a.hub; lmc_step_pipe_hub.hip): the same coverage again (there is no Huber mask kind)
-  if (a.hub && (n != 10 || a.f_out || a.g_out || a.tv_aniso || a.ncvx_kind != LMC_NCVX_NONE || a.extra || a.data_kind == LMC_DATA_MASK)) return 0;
+  // Poisson, weighted and Huber data terms (a.term; lmc_step_pipe_term.hip): one launch of exactly 10, isotropic prior, no energy by-products; identity or
+  // blur, and for Poisson the mask (there is no weighted and no Huber mask kind)
+  if (a.term != kTermL2 && (n != 10 || a.f_out || a.g_out || a.tv_aniso || a.ncvx_kind != LMC_NCVX_NONE || a.extra ||
+                            (a.term != kTermPois && a.data_kind == LMC_DATA_MASK))) return 0;
   if (a.tv_in || a.tv_out || a.tv_state_only || a.tv_warm) return 0;
   if (!pipe_geometry_ok(a)) return 0;
   return single ? 1 : (n + 9) / 10;
@@ -59,7 +57,7 @@ bool pipe_supported(const StepArgs& a) { return pipe_links(a) == 1; }
 // a.tv_out ([C][2][H][W] each, never NULL), a.tv.niter in {1, 2, 3} dual iterations per MYULA iteration
 bool pipe_warm_supported(const StepArgs& a) {
   const int n = a.tv.niter;
-  if (!(n == 1 || n == 2 || n == 3) || a.tv_aniso || a.box || a.pois || a.wl2 || a.hub) return false;
+  if (!(n == 1 || n == 2 || n == 3) || a.tv_aniso || a.box || a.term != kTermL2) return false;
   return pipe_geometry_ok(a);
 }
 
@@ -85,7 +83,7 @@ hipError_t launch_step_pipe_warm(StepArgs a, hipStream_t st) {
 // wide, W % 8 == 0, that returns the update alone: no energy by-products, no non-convex term (their seam columns are not exchanged).
 bool pipe_teams_covered(const StepArgs& a, int KT) {
   return a.tv.niter == 10 && KT == 5 && a.W >= 264 && a.W <= 512 && (a.W & 7) == 0 && !a.f_out && !a.g_out &&
-         a.ncvx_kind == LMC_NCVX_NONE && !a.extra && !a.pois && !a.wl2 && !a.hub;
+         a.ncvx_kind == LMC_NCVX_NONE && !a.extra && a.term == kTermL2;
 }
 
 // The uniform-box form of the blur wave (pipe_body, UNI; lmc_step_pipe_uni.hip) covers one launch of 10 dual iterations with a uniform 5 x 5 box -- the centred
@@ -93,7 +91,7 @@ bool pipe_teams_covered(const StepArgs& a, int KT) {
 // case, taps that are not uniform among them, keeps the general form.
 bool pipe_uni_covered(const StepArgs& a, int KT) {
   if (!(a.tv.niter == 10 && KT == 5 && a.W <= 512 && pipe_lastlane(a.W))) return false;
-  if (a.tv_aniso || a.box || a.pois || a.wl2 || a.hub || a.f_out || a.g_out || a.ncvx_kind != LMC_NCVX_NONE || a.extra || a.rt_kc || a.tv_warm) return false;
+  if (a.tv_aniso || a.box || a.term != kTermL2 || a.f_out || a.g_out || a.ncvx_kind != LMC_NCVX_NONE || a.extra || a.rt_kc || a.tv_warm) return false;
   int lo, hi, l2, h2;
   return host::uniform_window(a.blur.h, KT, lo, hi) && host::uniform_window(a.blur.h + kMaxBlur, KT, l2, h2) && lo == 0 && hi == 4 && l2 == 0 && h2 == 4;
 }
@@ -107,9 +105,7 @@ hipError_t launch_step_pipe(StepArgs a, hipStream_t st, float* state0, float* st
   const int KT = pipe_taps(a);
   const bool two = links == 1 && pipe_teams_covered(a, KT);
   if (teams == 2 && !two) return hipErrorInvalidConfiguration;
-  if (a.pois) return links == 1 ? pipe_dispatch_pois(a, KT, st) : hipErrorInvalidConfiguration;
-  if (a.wl2) return links == 1 ? pipe_dispatch_wl2(a, KT, st) : hipErrorInvalidConfiguration;
-  if (a.hub) return links == 1 ? pipe_dispatch_hub(a, KT, st) : hipErrorInvalidConfiguration;
+  if (a.term != kTermL2) return links == 1 ? pipe_dispatch_term(a, KT, st) : hipErrorInvalidConfiguration;
   if (a.tv_aniso) {
     if (two && teams != 1) return pipe_dispatch_aniso(a, KT, false, 2, st);     // (512 x 512 x 1024: 1.38 against 1.57 ms per launch, bit-identical)
     if (links == 1) return pipe_dispatch_aniso(a, KT, false, 1, st);

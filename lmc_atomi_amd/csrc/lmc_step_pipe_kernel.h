@@ -532,18 +532,19 @@ __device__ __forceinline__ int pipe_role(int hw_wave, int kc, int ncvx_kind) {
 // ANISO (myula_step_pipe_aniso_kernel, lmc_step_pipe_aniso.hip): the stages project the dual onto the box (pipe_stage); fixed count, cold start.
 // BOX (myula_step_pipe_box_kernel, lmc_step_pipe_box.hip): the prior is sigma TV + the indicator of [A.box_lo, A.box_hi]: every stage and the combine
 // wave project the primal iterate they form onto the box (pipe_stage); fixed count, cold start.  Links with tv_state_only do not combine and clamp nothing there.
-// POIS (myula_step_pipe_pois_kernel, myula_step_pipe_pois_box_kernel, lmc_step_pipe_pois.hip): the Poisson data term -- A.y is [2][H][W], counts then
+// TERM (DataTerm, lmc_common.h; the instantiations are in lmc_step_pipe_term.hip; below, POIS, WL2 and HUB stand for TERM == kTermPois, kTermWl2, kTermHub):
+// POIS (myula_step_pipe_pois_kernel, myula_step_pipe_pois_box_kernel): the Poisson data term -- A.y is [2][H][W], counts then
 // background; where the L wave forms the residual d = H x - y (blur) or the pointwise gradient (identity, mask) it forms rho(H x) instead.  The
 // background row travels through a second prefetch ring (bpre) with the slots and the lead of ypre.  The residual stays masked by a 0 / 1 FACTOR: every
 // raw row load returns values of the row it reads (lanes and pixels past the row end read inside it, rows outside the image are clamped), so with the
 // documented precondition beta > 0 over the whole plane t = 1 / (max(u, 0) + beta) is finite in every lane and rho * 0 is 0, never NaN (a zero-FILLED
 // background would make it inf * 0).  One team, one launch, no energy by-products (pipe_links).
-// WL2 (myula_step_pipe_wl2_kernel, myula_step_pipe_wl2_box_kernel, lmc_step_pipe_wl2.hip): the weighted Gaussian data term -- A.y is [2][H][W], observation
+// WL2 (myula_step_pipe_wl2_kernel, myula_step_pipe_wl2_box_kernel): the weighted Gaussian data term -- A.y is [2][H][W], observation
 // then weights; the L wave forms d = (H x - y) w (blur: one packed multiply per pixel pair, BEFORE the adjoint) or the pointwise gradient
 // sigma_f w (x - y) (identity).  The weight row travels through bpre exactly as the background does.  The residual stays masked by the 0 / 1 factor:
 // gload_raw never zero-fills but returns values of the row it reads, and with the documented precondition (w finite over the whole plane) d is finite in
 // every lane, so d * 0 is 0, never NaN.  One team, one launch, no energy by-products (pipe_links).
-// HUB (myula_step_pipe_hub_kernel, myula_step_pipe_hub_box_kernel, lmc_step_pipe_hub.hip): the Huber data term -- A.y is [2][H][W], observation then
+// HUB (myula_step_pipe_hub_kernel, myula_step_pipe_hub_box_kernel): the Huber data term -- A.y is [2][H][W], observation then
 // thresholds delta in [0, +inf]; the L wave forms d = clamp(H x - y, -delta, delta) (blur: one v_med3_f32 per pixel where WL2 multiplies, BEFORE the
 // adjoint) or the pointwise gradient sigma_f clamp(x - y, -delta, delta) (identity).  The delta row travels through bpre exactly as the weights do.
 // The 0 / 1 factor argument of WL2 carries over: the clamp returns one of H x - y, -delta and delta, and it returns +-delta only where that lies
@@ -557,16 +558,14 @@ __device__ __forceinline__ int pipe_role(int hw_wave, int kc, int ncvx_kind) {
 // states move at rounding level (another order of additions, one rounded constant for five taps).  One fixed-count launch of 10 dual iterations from the
 // zero dual state on aligned rows, one strip, update alone.  EVERYTHING ELSE KEEPS THE GENERAL FORM: RT, chained links, the warm dual, the anisotropic
 // prior, the box constraint, the Poisson and weighted data terms, 7 taps, non-uniform taps, unaligned widths, column strips, the energy by-products.
-template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS, bool ANISO = false, bool BOX = false, bool POIS = false, bool WL2 = false,
-          bool UNI = false, bool HUB = false>
+template <int K, int PXL, int KT, bool CHAIN, bool WARM, bool AL, bool RT, int TEAMS, bool ANISO = false, bool BOX = false, int TERM = kTermL2, bool UNI = false>
 __device__ __forceinline__ void pipe_body(const StepArgs& A) {
-  static_assert(!UNI || (K == 10 && KT == 5 && AL && !CHAIN && !WARM && !RT && !ANISO && !BOX && !POIS && !WL2),
+  static_assert(TERM >= kTermL2 && TERM <= kTermHub, "TERM is a DataTerm");
+  constexpr bool kPlane2 = TERM != kTermL2;     // the term reads a second plane of A.y (background, weights, thresholds): the bpre ring beside ypre
+  static_assert(!UNI || (K == 10 && KT == 5 && AL && !CHAIN && !WARM && !RT && !ANISO && !BOX && !kPlane2),
                 "uniform-box form: one fixed-count launch of 10 dual iterations, 5 taps, aligned rows, plain Gaussian data term, isotropic prior");
-  static_assert(!HUB || (TEAMS == 1 && !CHAIN && !WARM && !RT && !ANISO && K == 10 && !POIS && !WL2 && !UNI),
-                "Huber data term: one team, one launch of 10 dual iterations, isotropic prior, not with the Poisson or the weighted term, general blur form");
-  static_assert(!WL2 || (TEAMS == 1 && !CHAIN && !WARM && !RT && !ANISO && K == 10 && !POIS),
-                "weighted Gaussian data term: one team, one launch of 10 dual iterations, isotropic prior, not with the Poisson term");
-  static_assert(!POIS || (TEAMS == 1 && !CHAIN && !WARM && !RT && !ANISO && K == 10), "Poisson data term: one team, one launch of 10 dual iterations, isotropic prior");
+  static_assert(!kPlane2 || (TEAMS == 1 && !CHAIN && !WARM && !RT && !ANISO && K == 10),
+                "Poisson, weighted and Huber data terms: one team, one launch of 10 dual iterations, isotropic prior, general blur form");
   static_assert(!WARM || CHAIN, "the warm dual uses the state hand-over of the chained launches");
   static_assert(!ANISO || (!WARM && !RT), "anisotropic prior: the early exit's objective and the warm dual are not built");
   static_assert(!BOX || (!WARM && !RT), "box constraint: the early exit's objective and the warm dual are not built");
@@ -673,7 +672,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
     constexpr int kXPF = 4;
     constexpr int NP = PXL / 2;
     float xpre[kXPF][PXL], ypre[4][PXL];
-    float bpre[POIS || WL2 || HUB ? 4 : 1][POIS || WL2 || HUB ? PXL : 1];      // POIS: the background rows, WL2: the weight rows, slot for slot beside ypre
+    float bpre[kPlane2 ? 4 : 1][kPlane2 ? PXL : 1];      // POIS: the background rows, WL2: the weight rows, slot for slot beside ypre
     v2f hxw[NWIN][NP], hrw[NWIN][NP];   // y rows: fetched kYPF ticks ahead, slot (tick & 3)
     // UNI: hxw / hrw hold the pair sums p_i = h_i + h_{i-1} of the horizontally summed rows (ring, slot (tick & 3)), hxp / hrp the previous h row by parity
     v2f hxp[UNI ? 2 : 1][NP], hrp[UNI ? 2 : 1][NP];
@@ -699,7 +698,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       for (int u = 0; u < kYPF; ++u) {
         const int r = u + 1 - D + (KT - 1) - HW + LAGT;
         gload_raw<PXL>(ypre[u], A.y + (size_t)min(max(r, 0), H - 1) * W, cl, W, al);
-        if constexpr (POIS || WL2 || HUB) gload_raw<PXL>(bpre[u], A.y + img + (size_t)min(max(r, 0), H - 1) * W, cl, W, al);
+        if constexpr (kPlane2) gload_raw<PXL>(bpre[u], A.y + img + (size_t)min(max(r, 0), H - 1) * W, cl, W, al);
       }
     }
     // Without a blur: pointwise data terms (identity, diagonal mask).  Their gradient sigma_f m (m x - y) of row t + 1 - D -- the row the
@@ -713,7 +712,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       for (int u = 0; u < 4; ++u)
 #pragma unroll
         for (int k = 0; k < PXL; ++k) { ypre[u][k] = 0.f; mpre[u][k] = 0.f; }
-      if constexpr (POIS || WL2 || HUB) {
+      if constexpr (kPlane2) {
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -724,7 +723,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         for (int u = 0; u < kYPF; ++u) {
           const size_t ro = (size_t)min(max(u + 1 - D, 0), H - 1) * W;
           gload_raw<PXL>(ypre[u], A.y + ro, c0, W, al);
-          if constexpr (POIS || WL2 || HUB) gload_raw<PXL>(bpre[u], A.y + img + ro, c0, W, al);
+          if constexpr (kPlane2) gload_raw<PXL>(bpre[u], A.y + img + ro, c0, W, al);
           if (pw_mask) gload_raw<PXL>(mpre[u], A.mask + ro, c0, W, al);
         }
       }
@@ -756,11 +755,11 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
       if constexpr (KT > 0) {   // observation row of the residual row kYPF ticks from now
         const int r3 = t + kYPF + 1 - D + (KT - 1) - HW + LAGT;
         gload_raw<PXL>(ypre[(U + kYPF) & 3], A.y + (size_t)min(max(r3, 0), H - 1) * W, cl, W, al);
-        if constexpr (POIS || WL2 || HUB) gload_raw<PXL>(bpre[(U + kYPF) & 3], A.y + img + (size_t)min(max(r3, 0), H - 1) * W, cl, W, al);
+        if constexpr (kPlane2) gload_raw<PXL>(bpre[(U + kYPF) & 3], A.y + img + (size_t)min(max(r3, 0), H - 1) * W, cl, W, al);
       } else if (pw_id || pw_mask) {
         const size_t ro = (size_t)min(max(t + kYPF + 1 - D, 0), H - 1) * W;
         gload_raw<PXL>(ypre[(U + kYPF) & 3], A.y + ro, c0, W, al);
-        if constexpr (POIS || WL2 || HUB) gload_raw<PXL>(bpre[(U + kYPF) & 3], A.y + img + ro, c0, W, al);
+        if constexpr (kPlane2) gload_raw<PXL>(bpre[(U + kYPF) & 3], A.y + img + ro, c0, W, al);
         if (pw_mask) gload_raw<PXL>(mpre[(U + kYPF) & 3], A.mask + ro, c0, W, al);
       }
       {   // row t arrives: publish it in the ring (zeros below the image); fetch row t + 4
@@ -827,7 +826,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
         const bool rowok = r >= 0 && r < H;
         const float rmask = rowok ? 1.f : 0.f;
         gfix_raw<PXL, AL>(ypre[U & 3], c0, W);
-        if constexpr (POIS || WL2 || HUB) gfix_raw<PXL, AL>(bpre[U & 3], c0, W);
+        if constexpr (kPlane2) gfix_raw<PXL, AL>(bpre[U & 3], c0, W);
 #pragma unroll
         for (int j = 0; j < NP; ++j) {
           v2f acc;
@@ -842,11 +841,11 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           // stretch of unpacked arithmetic and half of its scalar instructions); every operand is finite (clamped rows, zeroed ring rows).
           // The observation row arrives in natural order: its subtraction is unpacked (as many instructions as a re-pairing move and a packed one)
           v2f d;
-          if constexpr (POIS) d = pois_rho2(acc, v2f{ypre[U & 3][j], ypre[U & 3][j + NP]}, v2f{bpre[U & 3][j], bpre[U & 3][j + NP]});     // (finite in every lane: see POIS above)
+          if constexpr (TERM == kTermPois) d = pois_rho2(acc, v2f{ypre[U & 3][j], ypre[U & 3][j + NP]}, v2f{bpre[U & 3][j], bpre[U & 3][j + NP]});     // (finite in every lane: see POIS above)
           else if constexpr (UNI) d = v2f{__builtin_fmaf(cbox, acc.x, -ypre[U & 3][j]), __builtin_fmaf(cbox, acc.y, -ypre[U & 3][j + NP])};   // c V - y, one rounding
           else d = v2f{acc.x - ypre[U & 3][j], acc.y - ypre[U & 3][j + NP]};
-          if constexpr (WL2) d = d * v2f{bpre[U & 3][j], bpre[U & 3][j + NP]};     // w (H x - y): the weight enters before the adjoint (finite in every lane: see WL2 above)
-          if constexpr (HUB) d = v2f{hub_psi(d.x, bpre[U & 3][j]), hub_psi(d.y, bpre[U & 3][j + NP])};     // clamp(H x - y, -delta, delta), before the adjoint (finite in every lane: see HUB above)
+          if constexpr (TERM == kTermWl2) d = d * v2f{bpre[U & 3][j], bpre[U & 3][j + NP]};     // w (H x - y): the weight enters before the adjoint (finite in every lane: see WL2 above)
+          if constexpr (TERM == kTermHub) d = v2f{hub_psi(d.x, bpre[U & 3][j]), hub_psi(d.y, bpre[U & 3][j + NP])};     // clamp(H x - y, -delta, delta), before the adjoint (finite in every lane: see HUB above)
           R[j] = d * v2f{(TEAMS == 2 ? cok : AL ? c0 < W : c0 + j < W) ? rmask : 0.f, (TEAMS == 2 ? cok : AL ? c0 < W : c0 + j + NP < W) ? rmask : 0.f};
         }
         if (TEAMS == 1 && A.f_out) {     // (the energy by-products are not built for two teams: pipe_teams_covered); pixels in natural order
@@ -922,17 +921,17 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
           const bool rowok = i >= 0 && i < H;
           gfix_raw<PXL, AL>(ypre[U & 3], c0, W);
           if (pw_mask) gfix_raw<PXL, AL>(mpre[U & 3], c0, W);
-          if constexpr (POIS || WL2 || HUB) gfix_raw<PXL, AL>(bpre[U & 3], c0, W);
+          if constexpr (kPlane2) gfix_raw<PXL, AL>(bpre[U & 3], c0, W);
 #pragma unroll
           for (int k = 0; k < PXL; ++k) {
             float g = 0.f;
             if (rowok && c0 + k < W) {
-              if constexpr (POIS) {
+              if constexpr (TERM == kTermPois) {
                 if (pw_id) g = A.sigma_f * pois_rho(xi[k], ypre[U & 3][k], bpre[U & 3][k]);
                 else g = A.sigma_f * mpre[U & 3][k] * pois_rho(mpre[U & 3][k] * xi[k], ypre[U & 3][k], bpre[U & 3][k]);
-              } else if constexpr (WL2) {
+              } else if constexpr (TERM == kTermWl2) {
                 g = A.sigma_f * (bpre[U & 3][k] * (xi[k] - ypre[U & 3][k]));     // (identity: pipe_links keeps the mask kind away)
-              } else if constexpr (HUB) {
+              } else if constexpr (TERM == kTermHub) {
                 g = A.sigma_f * hub_psi(xi[k] - ypre[U & 3][k], bpre[U & 3][k]);     // (identity, likewise)
               } else {
               if (pw_id) g = A.sigma_f * (xi[k] - ypre[U & 3][k]);
@@ -1549,13 +1548,8 @@ hipError_t pipe_dispatch_aniso(const StepArgs& a, int KT, bool chain, int teams,
 // teams = 2 covers what pipe_teams_covered names)
 hipError_t pipe_dispatch_uni(const StepArgs& a, int KT, int teams, hipStream_t st);
 
-// lmc_step_pipe_pois.hip: the Poisson data term (myula_step_pipe_pois_kernel / myula_step_pipe_pois_box_kernel: isotropic prior, K = 10, one launch, one team)
-hipError_t pipe_dispatch_pois(const StepArgs& a, int KT, hipStream_t st);
-
-// lmc_step_pipe_wl2.hip: the weighted Gaussian data term (myula_step_pipe_wl2_kernel / myula_step_pipe_wl2_box_kernel: isotropic prior, K = 10, one launch, one team)
-hipError_t pipe_dispatch_wl2(const StepArgs& a, int KT, hipStream_t st);
-
-// lmc_step_pipe_hub.hip: the Huber data term (myula_step_pipe_hub_kernel / myula_step_pipe_hub_box_kernel: isotropic prior, K = 10, one launch, one team)
-hipError_t pipe_dispatch_hub(const StepArgs& a, int KT, hipStream_t st);
+// lmc_step_pipe_term.hip: the Poisson, weighted and Huber data terms, by a.term (myula_step_pipe_{pois,wl2,hub}_kernel and their _box_kernel: isotropic prior,
+// K = 10, one launch, one team)
+hipError_t pipe_dispatch_term(const StepArgs& a, int KT, hipStream_t st);
 
 }  // namespace lmc

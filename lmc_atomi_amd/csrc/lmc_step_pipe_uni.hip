@@ -10,12 +10,12 @@ namespace lmc {
 
 template <int K, int PXL, int KT>
 __global__ __launch_bounds__(64 * ((K + 1) / 2 + 3), PXL == 8 ? 1 : 2) void myula_step_pipe_uni_kernel(const StepArgs A) {
-  pipe_body<K, PXL, KT, false, false, true, false, 1, false, false, false, false, true>(A);
+  pipe_body<K, PXL, KT, false, false, true, false, 1, false, false, kTermL2, true>(A);
 }
 
 template <int K, int KT>
 __global__ __launch_bounds__(128 * ((K + 1) / 2 + 3), 4) void myula_step_pipe_uni2_kernel(const StepArgs A) {
-  pipe_body<K, 4, KT, false, false, true, false, 2, false, false, false, false, true>(A);
+  pipe_body<K, 4, KT, false, false, true, false, 2, false, false, kTermL2, true>(A);
 }
 
 template <int PXL>
@@ -26,7 +26,7 @@ static hipError_t pipe_uni_launch_one(const StepArgs& a, hipStream_t st) {
 
 // a.blur.h holds the centred taps (pipe_taps); the caller has checked the coverage (pipe_uni_covered, lmc_step_pipe.hip)
 hipError_t pipe_dispatch_uni(const StepArgs& a, int KT, int teams, hipStream_t st) {
-  if (a.tv.niter != 10 || KT != 5 || !pipe_lastlane(a.W) || a.W > 512 || a.tv_warm || a.tv_aniso || a.box || a.pois || a.wl2 || a.hub || a.rt_kc) return hipErrorInvalidConfiguration;
+  if (a.tv.niter != 10 || KT != 5 || !pipe_lastlane(a.W) || a.W > 512 || a.tv_warm || a.tv_aniso || a.box || a.term != kTermL2 || a.rt_kc) return hipErrorInvalidConfiguration;
   if (teams == 2) return pipe_launch<myula_step_pipe_uni2_kernel<10, 5>>(pipe_teams_lds_bytes<10>(), dim3(a.C), dim3(pipe_block(10, 2)), a, st);
   return a.W > 256 ? pipe_uni_launch_one<8>(a, st) : pipe_uni_launch_one<4>(a, st);
 }

@@ -12,51 +12,28 @@ namespace lmc {
 
 constexpr int kStepThreads = 1024;
 
-// The sixteen kernels of before (their names and instruction streams are as they were) ...
-#define LMC_TILE_KERNEL_HEAD template <int NP, bool TV, bool ANISO = false> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool BOX = false, POIS = false, WL2 = false, HUB = false;
+// One inclusion per data term gives its two kernels, LMC_TILE_NAME(_kernel)<NP, TV, ANISO> (every prior) and LMC_TILE_NAME(_box_kernel)<NP, ANISO> (the
+// box-constrained TV prior, either form): names and instruction streams as they were when each was a block of its own
+#define LMC_TILE_TERM kTermL2
+#define LMC_TILE_NAME(sfx) myula_step_tile##sfx
 #include "lmc_step_tile_kernel.h"
-#undef LMC_TILE_KERNEL_HEAD
-#undef LMC_TILE_KERNEL_FLAGS
-// ... and the box-constrained TV prior, either form, under a name of its own
-#define LMC_TILE_KERNEL_HEAD template <int NP, bool ANISO> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_box_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool TV = true, BOX = true, POIS = false, WL2 = false, HUB = false;
+#undef LMC_TILE_TERM
+#undef LMC_TILE_NAME
+#define LMC_TILE_TERM kTermPois
+#define LMC_TILE_NAME(sfx) myula_step_tile_pois##sfx
 #include "lmc_step_tile_kernel.h"
-#undef LMC_TILE_KERNEL_HEAD
-#undef LMC_TILE_KERNEL_FLAGS
-// ... and the Poisson data term (StepArgs::pois), with every prior of the first and the box of the second
-#define LMC_TILE_KERNEL_HEAD template <int NP, bool TV, bool ANISO = false> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_pois_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool BOX = false, POIS = true, WL2 = false, HUB = false;
+#undef LMC_TILE_TERM
+#undef LMC_TILE_NAME
+#define LMC_TILE_TERM kTermWl2
+#define LMC_TILE_NAME(sfx) myula_step_tile_wl2##sfx
 #include "lmc_step_tile_kernel.h"
-#undef LMC_TILE_KERNEL_HEAD
-#undef LMC_TILE_KERNEL_FLAGS
-#define LMC_TILE_KERNEL_HEAD template <int NP, bool ANISO> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_pois_box_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool TV = true, BOX = true, POIS = true, WL2 = false, HUB = false;
+#undef LMC_TILE_TERM
+#undef LMC_TILE_NAME
+#define LMC_TILE_TERM kTermHub
+#define LMC_TILE_NAME(sfx) myula_step_tile_hub##sfx
 #include "lmc_step_tile_kernel.h"
-#undef LMC_TILE_KERNEL_HEAD
-#undef LMC_TILE_KERNEL_FLAGS
-// ... and the weighted Gaussian data term (StepArgs::wl2), likewise
-#define LMC_TILE_KERNEL_HEAD template <int NP, bool TV, bool ANISO = false> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_wl2_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool BOX = false, POIS = false, WL2 = true, HUB = false;
-#include "lmc_step_tile_kernel.h"
-#undef LMC_TILE_KERNEL_HEAD
-#undef LMC_TILE_KERNEL_FLAGS
-#define LMC_TILE_KERNEL_HEAD template <int NP, bool ANISO> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_wl2_box_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool TV = true, BOX = true, POIS = false, WL2 = true, HUB = false;
-#include "lmc_step_tile_kernel.h"
-#undef LMC_TILE_KERNEL_HEAD
-#undef LMC_TILE_KERNEL_FLAGS
-// ... and the Huber data term (StepArgs::hub), likewise
-#define LMC_TILE_KERNEL_HEAD template <int NP, bool TV, bool ANISO = false> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_hub_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool BOX = false, POIS = false, WL2 = false, HUB = true;
-#include "lmc_step_tile_kernel.h"
-#undef LMC_TILE_KERNEL_HEAD
-#undef LMC_TILE_KERNEL_FLAGS
-#define LMC_TILE_KERNEL_HEAD template <int NP, bool ANISO> __global__ __launch_bounds__(kStepThreads) void myula_step_tile_hub_box_kernel
-#define LMC_TILE_KERNEL_FLAGS constexpr bool TV = true, BOX = true, POIS = false, WL2 = false, HUB = true;
-#include "lmc_step_tile_kernel.h"
-#undef LMC_TILE_KERNEL_HEAD
-#undef LMC_TILE_KERNEL_FLAGS
+#undef LMC_TILE_TERM
+#undef LMC_TILE_NAME
 
 // ---- host-side launcher --------------------------------------------------------------------
 
@@ -96,30 +73,33 @@ static hipError_t launch_kernel(const StepArgs& a, size_t lds, hipStream_t st) {
   return hipGetLastError();
 }
 
+// the kernel of a term: the box-constrained one where the prior is TV and the box is on
+template <int TERM, int NP, bool TV, bool ANISO, bool BOX>
+static constexpr auto tile_kernel() {
+#define LMC_TILE_PICK(name) if constexpr (BOX) return name##_box_kernel<NP, ANISO>; else return name##_kernel<NP, TV, ANISO>;
+  if constexpr (TERM == kTermPois) { LMC_TILE_PICK(myula_step_tile_pois) }
+  else if constexpr (TERM == kTermWl2) { LMC_TILE_PICK(myula_step_tile_wl2) }
+  else if constexpr (TERM == kTermHub) { LMC_TILE_PICK(myula_step_tile_hub) }
+  else { LMC_TILE_PICK(myula_step_tile) }
+#undef LMC_TILE_PICK
+}
+
+template <int TERM, int NP, bool TV, bool ANISO>
+static hipError_t launch_term(const StepArgs& a, size_t lds, hipStream_t st) {
+  if constexpr (TV) {
+    if (a.box) return launch_kernel<tile_kernel<TERM, NP, TV, ANISO, true>()>(a, lds, st);
+  }
+  return launch_kernel<tile_kernel<TERM, NP, TV, ANISO, false>()>(a, lds, st);
+}
+
 template <int NP, bool TV, bool ANISO>
 static hipError_t launch_np(const StepArgs& a, size_t lds, hipStream_t st) {
-  if (a.hub) {
-    if constexpr (TV) {
-      if (a.box) return launch_kernel<myula_step_tile_hub_box_kernel<NP, ANISO>>(a, lds, st);
-    }
-    return launch_kernel<myula_step_tile_hub_kernel<NP, TV, ANISO>>(a, lds, st);
+  switch (a.term) {
+    case kTermPois: return launch_term<kTermPois, NP, TV, ANISO>(a, lds, st);
+    case kTermWl2: return launch_term<kTermWl2, NP, TV, ANISO>(a, lds, st);
+    case kTermHub: return launch_term<kTermHub, NP, TV, ANISO>(a, lds, st);
+    default: return launch_term<kTermL2, NP, TV, ANISO>(a, lds, st);
   }
-  if (a.wl2) {
-    if constexpr (TV) {
-      if (a.box) return launch_kernel<myula_step_tile_wl2_box_kernel<NP, ANISO>>(a, lds, st);
-    }
-    return launch_kernel<myula_step_tile_wl2_kernel<NP, TV, ANISO>>(a, lds, st);
-  }
-  if (a.pois) {
-    if constexpr (TV) {
-      if (a.box) return launch_kernel<myula_step_tile_pois_box_kernel<NP, ANISO>>(a, lds, st);
-    }
-    return launch_kernel<myula_step_tile_pois_kernel<NP, TV, ANISO>>(a, lds, st);
-  }
-  if constexpr (TV) {
-    if (a.box) return launch_kernel<myula_step_tile_box_kernel<NP, ANISO>>(a, lds, st);
-  }
-  return launch_kernel<myula_step_tile_kernel<NP, TV, ANISO>>(a, lds, st);
 }
 
 template <bool TV, bool ANISO = false>
@@ -182,7 +162,7 @@ hipError_t launch_step_tile_chunked(const StepArgs& a, float* state0, float* sta
     b.tv_in = ch > 0 ? state[(ch - 1) & 1] : nullptr;
     b.tv_out = last ? nullptr : state[ch & 1];
     b.tv_state_only = last ? 0 : 1;
-    if (!last) { b.data_kind = LMC_DATA_NONE; b.pois = 0; b.wl2 = 0; b.hub = 0; b.ncvx_kind = LMC_NCVX_NONE; b.extra = nullptr; }
+    if (!last) { b.data_kind = LMC_DATA_NONE; b.term = kTermL2; b.ncvx_kind = LMC_NCVX_NONE; b.extra = nullptr; }
     hipError_t e = launch_step_tile(b, st);
     if (e != hipSuccess) return e;
   }

@@ -1,6 +1,6 @@
-// The body of the LDS-tiled step kernel (lmc_step_tile.hip), included once per kernel NAME: the including file defines
-//   LMC_TILE_KERNEL_HEAD   the template head and the kernel's name, up to its argument list
-//   LMC_TILE_KERNEL_FLAGS  constexpr definitions of whichever of TV, ANISO, BOX, POIS, WL2, HUB are no template parameters of that head
+// The body of the LDS-tiled step kernel (lmc_step_tile.hip), included once per data term: the including file defines
+//   LMC_TILE_TERM        the DataTerm of the two kernels
+//   LMC_TILE_NAME(sfx)   their names: LMC_TILE_NAME(_kernel)<NP, TV, ANISO> and, by the second pass at the end of this file, LMC_TILE_NAME(_box_kernel)<NP, ANISO>
 // Textual inclusion, not a shared device function: the unconstrained kernels keep their instruction streams bit for bit that way (as a
 // function inlined into two kernels the same source compiles to other streams for all sixteen -- scripts/kernel_resources.py --code-hash), and the
 // box-constrained kernels get names of their own without a fourth template argument on myula_step_tile_kernel.
@@ -12,14 +12,20 @@
 // BOX (with TV; myula_step_tile_box_kernel): the prior is sigma TV + the indicator of [P.box_lo, P.box_hi] -- every primal iterate, the returned one
 // included, is projected onto the box (Beck and Teboulle's constrained FGP).  Pixels outside the image then hold the clamp of 0; the has-down / has-right
 // flags cut every difference with them, and their own dual stays 0 (no flag set), as before.
-// POIS (myula_step_tile_pois_kernel, myula_step_tile_pois_box_kernel): the Poisson data term -- P.y is [2][H][W], counts then background, and the
+// TERM == kTermPois (myula_step_tile_pois_kernel, myula_step_tile_pois_box_kernel): the Poisson data term -- P.y is [2][H][W], counts then background, and the
 // residual H x - y becomes rho(H x) = phi'(H x) (pois_rho, lmc_device.h) at the three places that form it.  P.data_kind stays the operator's kind.
-// WL2 (myula_step_tile_wl2_kernel, myula_step_tile_wl2_box_kernel): the weighted Gaussian data term -- P.y is [2][H][W], observation then weights, and
+// TERM == kTermWl2 (myula_step_tile_wl2_kernel, myula_step_tile_wl2_box_kernel): the weighted Gaussian data term -- P.y is [2][H][W], observation then weights, and
 // the residual H x - y becomes w (H x - y): the weight multiplies BEFORE the adjoint.  Identity and blur (there is no weighted mask kind).
-// HUB (myula_step_tile_hub_kernel, myula_step_tile_hub_box_kernel): the Huber data term -- P.y is [2][H][W], observation then thresholds delta, and the
+// TERM == kTermHub (myula_step_tile_hub_kernel, myula_step_tile_hub_box_kernel): the Huber data term -- P.y is [2][H][W], observation then thresholds delta, and the
 // residual H x - y becomes clamp(H x - y, -delta, delta) (hub_psi, lmc_device.h): the clamp acts BEFORE the adjoint.  Identity and blur (no mask kind).
-LMC_TILE_KERNEL_HEAD(const StepArgs P) {
-  LMC_TILE_KERNEL_FLAGS
+#ifndef LMC_TILE_BOX_PASS
+template <int NP, bool TV, bool ANISO = false> __global__ __launch_bounds__(kStepThreads) void LMC_TILE_NAME(_kernel)(const StepArgs P) {
+  constexpr bool BOX = false;
+#else
+template <int NP, bool ANISO> __global__ __launch_bounds__(kStepThreads) void LMC_TILE_NAME(_box_kernel)(const StepArgs P) {
+  constexpr bool TV = true, BOX = true;
+#endif
+  constexpr int TERM = LMC_TILE_TERM;
   static_assert(TV || !ANISO, "the anisotropic projection belongs to the TV prox");
   static_assert(TV || !BOX, "the box is part of the TV prox here (separable priors: box_prior_prox_kernel)");
   extern __shared__ float lds[];
@@ -92,9 +98,9 @@ LMC_TILE_KERNEL_HEAD(const StepArgs P) {
                 acc = fmaf(P.blur.h[a * kw + b], xs[(r - a + oy) * PW + (c - b + ox)], acc);
             const size_t gi = (size_t)(row0 + r) * W + (col0 + c);
             // (inside the guard: rho of a pixel outside the image is not 0 -- it is 1 for y = 0)
-            if constexpr (POIS) acc = pois_rho(acc, P.y[gi], P.y[img + gi]);
-            else if constexpr (WL2) acc = P.y[img + gi] * (acc - P.y[gi]);
-            else if constexpr (HUB) acc = hub_psi(acc - P.y[gi], P.y[img + gi]);
+            if constexpr (TERM == kTermPois) acc = pois_rho(acc, P.y[gi], P.y[img + gi]);
+            else if constexpr (TERM == kTermWl2) acc = P.y[img + gi] * (acc - P.y[gi]);
+            else if constexpr (TERM == kTermHub) acc = hub_psi(acc - P.y[gi], P.y[img + gi]);
             else acc -= P.y[gi];
           }
           S[p] = acc;  // residual, zero outside the image (zero-padded adjoint)
@@ -216,13 +222,13 @@ LMC_TILE_KERNEL_HEAD(const StepArgs P) {
     const float x = xs[p];
     float g = gv[j];
     if (P.data_kind == LMC_DATA_IDENTITY) {
-      if constexpr (POIS) g = P.sigma_f * pois_rho(x, P.y[gi], P.y[img + gi]);
-      else if constexpr (WL2) g = P.sigma_f * (P.y[img + gi] * (x - P.y[gi]));
-      else if constexpr (HUB) g = P.sigma_f * hub_psi(x - P.y[gi], P.y[img + gi]);
+      if constexpr (TERM == kTermPois) g = P.sigma_f * pois_rho(x, P.y[gi], P.y[img + gi]);
+      else if constexpr (TERM == kTermWl2) g = P.sigma_f * (P.y[img + gi] * (x - P.y[gi]));
+      else if constexpr (TERM == kTermHub) g = P.sigma_f * hub_psi(x - P.y[gi], P.y[img + gi]);
       else g = P.sigma_f * (x - P.y[gi]);
     } else if (P.data_kind == LMC_DATA_MASK) {
       const float mk = P.mask[gi];
-      if constexpr (POIS) g = P.sigma_f * mk * pois_rho(mk * x, P.y[gi], P.y[img + gi]);
+      if constexpr (TERM == kTermPois) g = P.sigma_f * mk * pois_rho(mk * x, P.y[gi], P.y[img + gi]);
       else g = P.sigma_f * mk * fmaf(mk, x, -P.y[gi]);
     }
     if (P.ncvx_kind == LMC_NCVX_MC_TV) {   // - lambda * A^T(A x / max(|A x|, gamma))  (algs.py:273-277, 291)
@@ -246,3 +252,8 @@ LMC_TILE_KERNEL_HEAD(const StepArgs P) {
     xout[gi] = fmaf(P.a, x, fmaf(-P.t, g, fmaf(P.b, px, P.s * nz)));
   }
 }
+#ifndef LMC_TILE_BOX_PASS
+#define LMC_TILE_BOX_PASS
+#include "lmc_step_tile_kernel.h"
+#undef LMC_TILE_BOX_PASS
+#endif

@@ -81,14 +81,14 @@ def test_not_implemented_errors(la):
 
 
 def test_refusals_keep_to_the_block_haar_kind(la):
-    """`_refuse_poisson` / `_refuse_wl2` go on refusing LMC_PRIOR_HAAR_L1 and let the new kind through."""
+    """`_refuse_term` goes on refusing LMC_PRIOR_HAAR_L1 and lets the new kind through."""
     from lmc_atomi_amd import _capi, algs
     haar = la.WaveletL1((16, 24)).prior_descriptor()
     db2 = la.WaveletL1((16, 24), wavelet="db2", levels=2).prior_descriptor()
-    for fn, kind in ((algs._refuse_poisson, _capi.DATA_POISSON_IDENTITY), (algs._refuse_wl2, _capi.DATA_WL2_IDENTITY)):
+    for kind in (_capi.DATA_POISSON_IDENTITY, _capi.DATA_WL2_IDENTITY, _capi.DATA_HUBER_IDENTITY):
         with pytest.raises(NotImplementedError):
-            fn({"data_kind": kind}, haar, {})
-        fn({"data_kind": kind}, db2, {})
+            algs._refuse_term({"data_kind": kind}, haar, {})
+        algs._refuse_term({"data_kind": kind}, db2, {})
 
 
 def header_values():
