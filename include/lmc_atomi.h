@@ -164,7 +164,47 @@ typedef enum lmc_data_kind {
    * create functions, and from lmc_fused_eval).  Not built: Student-t / Cauchy losses, a weighted Huber term, chained and two-team pipe forms. */
   LMC_DATA_HUBER_IDENTITY = 13,
   LMC_DATA_HUBER_BLUR = 14,
-  LMC_DATA_HUBER_PSF = 15
+  LMC_DATA_HUBER_PSF = 15,
+  /* Tomography: the parallel-beam Radon operator and its data terms (appended; LMC_ATOMI_ABI_VERSION stays 4 and sizeof(lmc_problem) 200).
+   * Build-specified (the reference has no projection operator); this text is its definition.
+   * Geometry.  Image x[i][j], H x W, row i, column j; pixel centres at X_j = j - (W - 1) / 2 and Y_i = i - (H - 1) / 2.  Angles theta_a, a < n_angles,
+   * in radians: the float32 values ARE the angles (the caller rounds once; the tables below are formed from those values widened to double).  The
+   * detector has n_det bins at unit spacing.
+   * Tables and detector coordinate.  Two tables, computed on the host in float64 and rounded once to float32 (lmc_radon_tables returns them):
+   *   ax[a][j] = X_j cos theta_a            by[a][i] = Y_i sin theta_a + (n_det - 1) / 2
+   * The detector coordinate of pixel (i, j) at angle a is t = ax[a][j] + by[a][i]: ONE float32 addition, so a checker reproduces t bit for bit.
+   * Weight and operator.  w(t, d) = max(0, 1 - |t - d|): the pixel-driven projector with linear interpolation on the detector, evaluated in fp32 as
+   * written by one device function that both directions call.
+   *   forward  (A x)[a][d]   = sum_{i, j} w(t_{a,i,j}, d) x[i][j]
+   *   adjoint  (A^T r)[i][j] = sum_a sum_{d in {floor(t), floor(t) + 1}, 0 <= d < n_det} w(t, d) r[a][d]
+   * Bins outside the detector are dropped in both directions: a detector narrower than the image is a valid, truncated operator.  Sinograms are
+   * [n_img][n_angles][n_det] floats.  Results are deterministic: both directions gather, in a fixed summation order, without atomics.
+   * Limits: 1 <= n_angles <= LMC_MAX_RADON_ANGLES, 1 <= n_det <= LMC_MAX_RADON_DET (LMC_E_INVALID otherwise); H, W up to LMC_MAX_RADON_SIDE each
+   * (LMC_E_UNSUPPORTED beyond: the forward kernel's fp32 estimate of the pixels that reach a bin is proved to that size).
+   * Data terms, with u = A x in the sinogram domain; the formulas of kinds 4 .. 8 and 13 .. 15 carry over word for word with Op = A:
+   *   16  Gaussian            f = sigma_f / 2 sum (u - y)^2            y_dev = [n_angles][n_det]
+   *   17  Poisson             kinds 4 .. 6                             y_dev = [2][n_angles][n_det]: counts, background
+   *   18  weighted Gaussian   kinds 7, 8                               y_dev = [2][n_angles][n_det]: observation, weights
+   *   19  Huber               kinds 13 .. 15                           y_dev = [2][n_angles][n_det]: observation, thresholds
+   * The struct has no hole left, so the kinds read fields that are otherwise unread for them: kh = n_angles, kw = n_det, h_host = the n_angles angles
+   * (host floats, copied by the callee).  oy, ox, the psf_* bytes, psf_separable and mask_dev must be 0 / NULL (LMC_E_INVALID otherwise); a non-finite
+   * angle is LMC_E_INVALID.
+   * Lipschitz bound.  A is non-negative, so ||A||^2 <= max(A 1) max(A^T 1), and max(A^T 1) <= n_angles; L_f is the term's own factor (1, max(y /
+   * beta^2), max(w), 1) times sigma_f times that product.
+   * The update out = a x - t grad f(x) + b prox(x) + s xi runs as LMC_DATA_PSF's does: r = rho(A x) into a handle-owned sinogram buffer
+   * (radon_fwd_kernel), the step of the same problem without a data term -- every prior, the box, the Philox field and every forced step_variant as
+   * they are for LMC_DATA_NONE --, out -= t sigma_f A^T r (radon_adj_kernel); without prox and noise the last launch writes a x - t sigma_f A^T r
+   * and the middle one is skipped.  Kernels: lmc_radon.hip -- forward: a workgroup owns 256 bins and 8 angles, the image passes through LDS band by band
+   * and a lane evaluates w on the four pixels of each row (or column, by the angle) that can reach its bin; adjoint: a lane owns a pixel and walks the
+   * angles.  Honoured by lmc_myula_create, lmc_skrock_create with all of lmc_sampler_* (lmc_sampler_sapg included), lmc_fused_eval, lmc_energies and
+   * lmc_sampler_energies (u in fp32, the terms widened to and summed in float64 by partial sums in a fixed order).  A sampler handle owns the tables
+   * and the residual buffer; the stateless calls take theirs from scratch.  LMC_E_UNSUPPORTED, with the reason in lmc_last_error: lmc_mymala_create,
+   * lmc_ulpda_create, lmc_l2_prox, ncvx_kind != NONE, tv_rtol > 0, tv_warm.  iterations_per_launch is ignored.  Not built: fan and cone beams, a
+   * detector spacing other than 1 and detector offsets, ray-driven or distance-driven footprints, filtered back-projection, a fused form. */
+  LMC_DATA_RADON = 16,
+  LMC_DATA_POISSON_RADON = 17,
+  LMC_DATA_WL2_RADON = 18,
+  LMC_DATA_HUBER_RADON = 19
 } lmc_data_kind;
 
 /* prior g whose prox enters the MYULA update (algs.py:569) */
@@ -239,6 +279,9 @@ typedef enum lmc_noise_mode {
 #define LMC_MAX_CHAIN_GROUPS 64
 #define LMC_MAX_COV_PROBES 32
 #define LMC_MAX_WAVELET_LEVELS 8   /* LMC_PRIOR_WAVELET_L1: levels of the transform */
+#define LMC_MAX_RADON_ANGLES 1024  /* LMC_DATA_RADON .. LMC_DATA_HUBER_RADON / lmc_radon_apply: projection angles */
+#define LMC_MAX_RADON_DET 4096     /* ... detector bins */
+#define LMC_MAX_RADON_SIDE 1048576 /* ... image rows, image columns */
 
 /* Geometry + potential U(x) = f(x) + eps*g(x).  Plain data; copied by the callee. */
 typedef struct lmc_problem {
@@ -254,8 +297,8 @@ typedef struct lmc_problem {
   uint8_t psf_kh, psf_kw, psf_oy, psf_ox;
   const float* y_dev;       /* [H][W] observation (borrowed; must outlive every use) */
   const float* mask_dev;    /* [H][W], LMC_DATA_MASK only */
-  int32_t kh, kw, oy, ox;   /* LMC_DATA_BLUR: kernel size and origin (pylops `offset`); 0 with the large-PSF kinds */
-  const float* h_host;      /* kh*kw taps, row-major, host memory (large-PSF kinds: psf_kh*psf_kw taps) */
+  int32_t kh, kw, oy, ox;   /* LMC_DATA_BLUR: kernel size and origin (pylops `offset`); 0 with the large-PSF kinds; the Radon kinds: kh = n_angles, kw = n_det, oy = ox = 0 */
+  const float* h_host;      /* kh*kw taps, row-major, host memory (large-PSF kinds: psf_kh*psf_kw taps; the Radon kinds: the n_angles angles in radians) */
   /* prior */
   int32_t prior_kind;       /* lmc_prior_kind */
   float prior_sigma;        /* multiplicative coefficient of g (tau_reg = 0.3 at prox_lmc_deconv.py:116-122) */
@@ -391,6 +434,15 @@ int lmc_spectral_filter(const float* x_dev, float* out_dev, int64_t n_img, int32
 /* Host only, no device needed.  The [11][H][W / 2 + 1] float planes of LMC_DATA_SPECTRAL (what y_dev points to, once uploaded) from G and b, each
  * [H][W] complex as interleaved float64, full plane; the fold runs in float64 and every entry is rounded once. */
 int lmc_spectral_tables(const double* G_host, const double* b_host, int32_t H, int32_t W, float* out_host);
+
+/* The Radon operator of LMC_DATA_RADON (its text above is the definition): adjoint == 0 -- x_dev images [n][H][W] -> out_dev sinograms
+ * [n][n_angles][n_det]; adjoint != 0 -- x_dev sinograms -> out_dev images.  angles_host: n_angles floats in radians, 1 .. LMC_MAX_RADON_ANGLES, finite;
+ * n_det in 1 .. LMC_MAX_RADON_DET; any n_img.  Not in place. */
+int lmc_radon_apply(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, const float* angles_host, int32_t n_angles, int32_t n_det,
+                    int32_t adjoint, void* stream);
+/* Host only, no device needed.  The two tables of that definition as the kernels read them: ax_out [n_angles][W], by_out [n_angles][H] (either may be
+ * NULL), float64 products rounded once. */
+int lmc_radon_tables(const float* angles_host, int32_t n_angles, int32_t n_det, int32_t H, int32_t W, float* ax_out, float* by_out);
 
 /* out[2][H][W] = forward-difference gradient of x (zero in last row/col); pylops.Gradient.matvec
  * (prox_lmc_deconv.py:98; algs.py:436,448). */

@@ -26,6 +26,11 @@ WL2_KINDS = (DATA_WL2_IDENTITY, DATA_WL2_BLUR)
 DATA_SPECTRAL = 12      # the Fourier-domain data term: y_dev is [11][H][W / 2 + 1], the planes of lmc_spectral_tables
 SPECTRAL_PLANES = 11
 FFT_MIN, FFT_MAX = 8, 1024      # sides of the transforms: powers of two in this range
+# the parallel-beam Radon operator (kh = n_angles, kw = n_det, h_host = the angles): Gaussian, Poisson, weighted Gaussian, Huber term; y_dev is
+# sinogram-shaped, [n_angles][n_det], or [2][n_angles][n_det] for the last three
+DATA_RADON, DATA_POISSON_RADON, DATA_WL2_RADON, DATA_HUBER_RADON = 16, 17, 18, 19
+RADON_KINDS = (DATA_RADON, DATA_POISSON_RADON, DATA_WL2_RADON, DATA_HUBER_RADON)
+MAX_RADON_ANGLES, MAX_RADON_DET, MAX_RADON_SIDE = 1024, 4096, 1 << 20
 TWO_PLANE_KINDS = POISSON_KINDS + WL2_KINDS + (DATA_POISSON_PSF, DATA_WL2_PSF) + HUBER_KINDS      # y_dev is [2][H][W]
 PRIOR_NONE, PRIOR_L2, PRIOR_L1, PRIOR_TV_ISO, PRIOR_TV_ANISO, PRIOR_HAAR_L1, PRIOR_EPROX = 0, 1, 2, 3, 4, 5, 6
 PRIOR_WAVELET_L1 = 7      # Daubechies wavelet-l1: lmc_problem.tv_niter = levels, eprox_kind = p (the struct has no hole left)
@@ -171,6 +176,8 @@ _SIGNATURES = {
     "lmc_irfft2": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "lmc_spectral_filter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     "lmc_spectral_tables": (C.c_int, [_D, _D, C.c_int32, C.c_int32, _F]),
+    "lmc_radon_apply": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "lmc_radon_tables": (C.c_int, [_F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F]),
     "lmc_gradient": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "lmc_gradient_adjoint": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "lmc_fused_eval": (C.c_int, [C.POINTER(lmc_problem), _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P]),

@@ -107,6 +107,20 @@ def _refuse_spectral(data, prior, opts, who=None):
         raise NotImplementedError("the Fourier-domain data term has no warm-started TV dual: warm / tv_warm must be off")
 
 
+def _refuse_radon(data, prior, opts, who=None):
+    """The same for the Radon operator (``Op = Radon(...)``, ``LMC_DATA_RADON`` / ``POISSON_RADON`` / ``WL2_RADON`` / ``HUBER_RADON``)."""
+    if data.get("data_kind") not in _capi.RADON_KINDS:
+        return
+    if who is not None:
+        raise NotImplementedError(f"{who[0]} does not take the Radon operator (Op = Radon(...)): {who[1]}")
+    if data.get("ncvx_kind", _capi.NCVX_NONE) != _capi.NCVX_NONE:
+        raise NotImplementedError("the Radon operator has no non-convex form")
+    if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
+        raise NotImplementedError("the Radon operator runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
+    if prior.get("tv_warm") or opts.get("tv_warm"):
+        raise NotImplementedError("the Radon operator has no warm-started TV dual: warm / tv_warm must be off")
+
+
 def _data_descriptor(proxf):
     if proxf is None:
         return {"data_kind": _capi.DATA_NONE}
@@ -321,6 +335,7 @@ class MYULASampler:
         _refuse_term(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._term_refusal)
         _refuse_psf(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._psf_refusal)
         _refuse_spectral(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._spectral_refusal)
+        _refuse_radon(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._radon_refusal)
         self._problem = _Problem(self.dims, _data_descriptor(proxf), _prior_descriptor(proxg), self.device, options=opts)
         self.prior_weight = float(self._problem.c.prior_sigma)      # follows set_prior_weight / estimate_prior_weight
         cfg = _capi.lmc_myula_config()
@@ -339,7 +354,7 @@ class MYULASampler:
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             rc = self._create(cfg)
-        if rc == -2 and self._problem.c.data_kind in _capi.POISSON_KINDS + _capi.WL2_KINDS + _capi.HUBER_KINDS + _capi.PSF_KINDS + (_capi.DATA_SPECTRAL,):      # (no handle exists: e.g. variant='pipe' on a problem the pipeline does not cover)
+        if rc == -2 and self._problem.c.data_kind in _capi.POISSON_KINDS + _capi.WL2_KINDS + _capi.HUBER_KINDS + _capi.PSF_KINDS + (_capi.DATA_SPECTRAL,) + _capi.RADON_KINDS:      # (no handle exists: e.g. variant='pipe' on a problem the pipeline does not cover)
             raise NotImplementedError(_dev.lib().lmc_last_error().decode())
         _capi.check(rc)
         self._attach_accumulators(acc)
@@ -349,6 +364,7 @@ class MYULASampler:
     _term_refusal = None         # the same for the data terms of _TERMS: term -> (who, why)
     _psf_refusal = None          # the same for a large PSF
     _spectral_refusal = None     # the same for the Fourier-domain data term
+    _radon_refusal = None        # the same for the Radon operator
     _eprox_refusal = None        # the same for a closed-form prior (a prox without a value)
 
     def _create(self, cfg):
@@ -631,6 +647,7 @@ class ULPDASampler(MYULASampler):
             raise NotImplementedError("ULPDA on the GPU supports A = Gradient (the reference's operator, prox_lmc_deconv.py:98)")
         if getattr(proxg, "bounds", None) is not None:
             raise NotImplementedError("ULPDA does not take a prior with bounds: its prior enters through the dual ball of g o A, which has no box form; use MYULA")
+        _refuse_radon(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which is not built for the Radon operator; use MYULA"))
         _refuse_term(_data_descriptor(proxf), {}, {}, {
             "poisson": ("ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA"),
             "wl2": ("ULPDA", "its primal step is the implicit step of f, (I + tau sigma Op^T W Op)^{-1}, which is not built; use MYULA"),
@@ -937,6 +954,7 @@ class MYMALASampler(MYULASampler):
     _term_refusal = {"poisson": ("MYMALA", "its Metropolis ratio needs the energy by-products of the step, which the Poisson kernels do not form; use MYULA or SK-ROCK")}
     _psf_refusal = ("MYMALA", "its Metropolis ratio is pinned for the fused step, which the three-launch PSF step is not; use MYULA or SK-ROCK")
     _spectral_refusal = ("MYMALA", "its Metropolis ratio is pinned for the fused step, which the three-launch spectral step is not; use MYULA or SK-ROCK")
+    _radon_refusal = ("MYMALA", "its Metropolis ratio is pinned for the fused step, which the three-launch Radon step is not; use MYULA or SK-ROCK")
     _eprox_refusal = ("MYMALA", "the prior has a prox and no value g(x), so the Metropolis target exp(-f - epsg g) is undefined; use MYULA")
 
     def acceptance(self):

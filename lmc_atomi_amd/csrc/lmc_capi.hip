@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <string>
 
 #include "lmc_host.h"
@@ -172,6 +173,44 @@ int lmc_spectral_tables(const double* G_host, const double* b_host, int32_t H, i
   return LMC_OK;
 }
 
+// the argument checks the two Radon calls share; R: the validated operator
+static int check_radon_call(const float* angles_host, int32_t n_angles, int32_t n_det, int32_t H, int32_t W, lmc::RadonOp& R) {
+  if (H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30) return fail(LMC_E_INVALID, "bad image size %dx%d", H, W);
+  if (!angles_host) return fail(LMC_E_INVALID, "angles pointer is NULL");
+  if (n_angles < 1 || n_angles > lmc::kRadonMaxAngles) return fail(LMC_E_INVALID, "n_angles %d outside 1..%d", n_angles, lmc::kRadonMaxAngles);
+  if (n_det < 1 || n_det > lmc::kRadonMaxDet) return fail(LMC_E_INVALID, "n_det %d outside 1..%d", n_det, lmc::kRadonMaxDet);
+  for (int a = 0; a < n_angles; ++a)
+    if (!std::isfinite(angles_host[a])) return fail(LMC_E_INVALID, "angle %d is not finite", a);
+  if (H > lmc::kRadonMaxSide || W > lmc::kRadonMaxSide) return fail(LMC_E_UNSUPPORTED, "Radon operator: image sides up to %d (got %dx%d)", lmc::kRadonMaxSide, H, W);
+  lmc::radon_prepare(R, angles_host, n_angles, n_det);
+  return LMC_OK;
+}
+
+int lmc_radon_apply(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, const float* angles_host, int32_t n_angles, int32_t n_det,
+                    int32_t adjoint, void* stream) {
+  if (!x_dev || !out_dev) return fail(LMC_E_INVALID, "NULL image pointer");
+  if (x_dev == out_dev) return fail(LMC_E_INVALID, "lmc_radon_apply cannot run in place");
+  if (n_img < 1) return fail(LMC_E_INVALID, "bad n_img %lld", (long long)n_img);
+  lmc::RadonOp R;
+  int rc = check_radon_call(angles_host, n_angles, n_det, H, W, R);
+  if (rc) return rc;
+  HIP_TRY(scratch_here().bind_radon(R, H, W, 0, S(stream)));
+  if (adjoint) HIP_TRY(lmc::launch_radon_adjoint(R, lmc::kRadonRaw, x_dev, out_dev, nullptr, n_img, H, W, 0.f, 0.f, S(stream)));
+  else HIP_TRY(lmc::launch_radon_forward(R, lmc::kRadonRaw, x_dev, out_dev, nullptr, n_img, H, W, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_radon_tables(const float* angles_host, int32_t n_angles, int32_t n_det, int32_t H, int32_t W, float* ax_out, float* by_out) {
+  lmc::RadonOp R;
+  int rc = check_radon_call(angles_host, n_angles, n_det, H, W, R);
+  if (rc) return rc;
+  std::vector<float> tab(lmc::radon_table_floats(n_angles, H, W));
+  lmc::radon_tables(R, H, W, tab.data());
+  if (ax_out) std::memcpy(ax_out, tab.data(), sizeof(float) * (size_t)n_angles * W);
+  if (by_out) std::memcpy(by_out, tab.data() + (size_t)n_angles * W, sizeof(float) * (size_t)n_angles * H);
+  return LMC_OK;
+}
+
 int lmc_gradient(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, void* stream) {
   if (!x_dev || !out_dev || x_dev == out_dev) return fail(LMC_E_INVALID, "bad pointers");
   if (n_img < 1 || H < 1 || W < 1) return fail(LMC_E_INVALID, "bad shape");
@@ -253,7 +292,8 @@ int lmc_l2_prox(const lmc_problem* prob, const float* x_dev, float* out_dev, int
   Problem q;
   int rc = load_problem(prob, q);
   if (rc) return rc;
-  rc = check_no_term(q, lmc::kTermPois, "lmc_l2_prox", "its implicit step (I + tau grad f)^{-1} has no closed form");
+  rc = check_no_radon(q, "lmc_l2_prox", "the implicit step (I + tau sigma_f A^T A)^{-1} is not built for it");
+  if (!rc) rc = check_no_term(q, lmc::kTermPois, "lmc_l2_prox", "its implicit step (I + tau grad f)^{-1} has no closed form");
   if (!rc) rc = check_no_term(q, lmc::kTermHub, "lmc_l2_prox", "the implicit step of the Huber loss under an operator is not built");
   if (!rc) rc = check_no_term(q, lmc::kTermWl2, "lmc_l2_prox", "the implicit step (I + tau sigma_f Op^T W Op)^{-1} is not built");
   if (!rc) rc = check_no_psf(q, "lmc_l2_prox", "the implicit step (I + tau sigma_f H^T H)^{-1} is not built for it");

@@ -53,7 +53,7 @@ inline bool eprox_params_ok(int kind, float p0, float p1) {
 // Validated, self-contained copy of an lmc_problem.
 struct Problem {
   int H = 0, W = 0;
-  int data_kind = 0;        // the operator's kind, LMC_DATA_NONE .. LMC_DATA_MASK, LMC_DATA_PSF, LMC_DATA_SPECTRAL
+  int data_kind = 0;        // the operator's kind, LMC_DATA_NONE .. LMC_DATA_MASK, LMC_DATA_PSF, LMC_DATA_SPECTRAL, LMC_DATA_RADON
   lmc::DataTerm term = lmc::kTermL2;     // the data term on that operator (lmc_common.h): Poisson, weighted Gaussian or Huber from LMC_DATA_POISSON_* / _WL2_* / _HUBER_*, and y is
                                          // [2][H][W] then (counts and background, observation and weights, observation and thresholds)
   float sigma_f = 0.f;
@@ -62,6 +62,7 @@ struct Problem {
   lmc::BlurTaps taps{};
   lmc::PsfOp psf;           // LMC_DATA_PSF / POISSON_PSF / WL2_PSF / HUBER_PSF: data_kind = LMC_DATA_PSF (with the term), the operator and its device table
   lmc::FftOp fft;           // LMC_DATA_SPECTRAL: the planes at y_dev and the device buffers of whoever owns them
+  lmc::RadonOp radon;       // LMC_DATA_RADON / POISSON_RADON / WL2_RADON / HUBER_RADON: data_kind = LMC_DATA_RADON (with the term), y = the sinogram-shaped planes
   int prior_kind = 0;
   float prior_sigma = 0.f;
   lmc::WaveletOp wav;       // LMC_PRIOR_WAVELET_L1: p, levels and the workspace of whoever owns it
@@ -152,7 +153,7 @@ struct Workspace {
   // small float64 scratch.  The pass-by-pass early exits lay it out as 2n objectives then n + 1 ints (exit_obj / exit_flag); the ME-TV envelope takes
   // the first 2n doubles, the PSF energy its partial sums, lmc_prior_statistic its segments
   Buf<double> dbl;
-  Buf<float> resid;                       // large PSF: the residual rho(H x) of a step, [n][H][W]
+  Buf<float> resid;                       // large PSF: the residual rho(H x) of a step, [n][H][W]; Radon operator: rho(A x), [n][n_angles][n_det]
   Buf<float> wav;                         // wavelet prior: the thresholded pyramid and the LL ping-pong (1.25 states)
   Buf<double> wav_part;                   // wavelet prior: the partial sums of its value
   // large PSF: the device tap table, the pinned host copy it was uploaded from (compared with the next table: equal taps are not uploaded again)
@@ -165,6 +166,13 @@ struct Workspace {
   float* fft_tw = nullptr;
   Buf<float> fft_spec;
   Buf<double> fft_part;
+  // Radon operator: the device table (radon_table_floats), the pinned host copy it is uploaded from, the event behind the last upload and what the
+  // table was made for (H, W, n_det, then the angles' bits): an equal key is not computed or uploaded again
+  float* radon_tab = nullptr;
+  float* radon_host = nullptr;
+  size_t radon_cap = 0;                   // floats both hold
+  hipEvent_t radon_ev = nullptr;
+  std::vector<int32_t> radon_key;
   RtState rt_tv, rt_me;                   // device-side early exit of the TV prior's prox / of the ME-TV inner prox
   int tv_exit = -1;                       // the TV prior's early exit as the last prepare() found it: -1 none, else tv_prior_rt_mode (1 fused, 0 prox alone, 2 pass by pass)
 
@@ -176,6 +184,9 @@ struct Workspace {
   hipError_t bind_psf(lmc::PsfOp& P, size_t n_resid, hipStream_t st);
   // F gets the twiddle table (uploaded once, synchronously: it never changes), the spectrum buffer and the value partials
   hipError_t bind_fft(lmc::FftOp& F, size_t n_spec, size_t n_part);
+  // R gets the device table of its angles on H x W images and, with n_resid > 0, the residual buffer.  The table is computed on the host and uploaded
+  // in stream order from the pinned copy, and only when its key differs from the one held.
+  hipError_t bind_radon(lmc::RadonOp& R, int H, int W, size_t n_resid, hipStream_t st);
   // frees the wavelet buffers (the largest a stateless call takes: 1.25 states); the next call that needs them allocates again
   void release_wavelet() { wav.release(); wav_part.release(); }
   void release() {
@@ -186,6 +197,10 @@ struct Workspace {
     if (psf_ev) (void)hipEventDestroy(psf_ev);
     if (fft_tw) (void)hipFree(fft_tw);
     psf_tab = psf_host = fft_tw = nullptr; psf_ev = nullptr; psf_valid = false;
+    if (radon_tab) (void)hipFree(radon_tab);
+    if (radon_host) (void)hipHostFree(radon_host);
+    if (radon_ev) (void)hipEventDestroy(radon_ev);
+    radon_tab = radon_host = nullptr; radon_ev = nullptr; radon_cap = 0; radon_key.clear();
     rt_tv.release();
     rt_me.release();
     tv_exit = -1;
@@ -268,6 +283,7 @@ extern const TermInfo kTerms[lmc::kNumTerms];
 int check_no_term(const Problem& q, lmc::DataTerm term, const char* who, const char* why);
 int check_no_psf(const Problem& q, const char* who, const char* why);
 int check_no_spectral(const Problem& q, const char* who, const char* why);
+int check_no_radon(const Problem& q, const char* who, const char* why);
 // what the entry points that form the update a x - t grad f + b prox_g (MYULA, MYMALA, SK-ROCK, lmc_fused_eval) refuse: of the anisotropic TV prior
 // and of each data term with kernels of its own
 int check_step_problem(const Problem& q, float b);
@@ -278,13 +294,13 @@ int make_step_args(const Problem& q, float a, float t, float b, float pt, float 
 void sanitize_pointers(lmc::StepArgs& A);
 int variant_of(const Problem& q);
 float tol_of(const Problem& q);
-// Grows ws to what the problem q needs on n_img images and points q.psf, q.fft and q.wav at it (nothing else does: a grown buffer never leaves a
+// Grows ws to what the problem q needs on n_img images and points q.psf, q.fft, q.radon and q.wav at it (nothing else does: a grown buffer never leaves a
 // stale pointer behind).  what: kForStep -- the update `probe` describes (its data term, prior, box and t; pt: its prox parameter) with the proxes that
 // run ahead of it; kForEnergyF / kForEnergyG -- f / g of problem_energies.  The stateless calls prepare at every call (no-op once large enough), a
 // handle at its creation and never inside lmc_sampler_step.  st: the stream of a PSF table upload.
 enum { kForStep = 1, kForEnergyF = 2, kForEnergyG = 4, kForEnergies = kForEnergyF | kForEnergyG };
 hipError_t prepare(Workspace& ws, Problem& q, const lmc::StepArgs& probe, int64_t n_img, float pt, int what, hipStream_t st);
-// The update A of problem q on the step kernel of `variant`: the dual state and the prox buffer come from ws, the PSF / spectral / wavelet operators
+// The update A of problem q on the step kernel of `variant`: the dual state and the prox buffer come from ws, the PSF / spectral / Radon / wavelet operators
 // from q (bound to ws by prepare; a launch that needs one that is not bound is not covered).
 hipError_t launch_step(const lmc::StepArgs& A, int variant, const Problem& q, Workspace& ws, hipStream_t st, const char** name);
 inline hipError_t launch_step(const lmc::StepArgs& A, const Problem& q, Workspace& ws, hipStream_t st, const char** name) {

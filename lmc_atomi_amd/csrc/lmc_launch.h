@@ -317,3 +317,54 @@ hipError_t launch_fft_rows_inv(int epi, const float2* spec, float* out, const fl
 // f_out[c] += sigma_f / 2 * the half-plane sum at x_c, float64 by partial sums in a fixed order
 hipError_t launch_fft_value(const FftOp& F, const float* x, int64_t n_img, int H, int W, float sigma_f, double* f_out, hipStream_t st);
 }  // namespace lmc
+
+namespace lmc {
+// The parallel-beam Radon operator (lmc_radon.hip, lmc_radon_kernel.h): the operator of LMC_DATA_RADON .. LMC_DATA_HUBER_RADON and lmc_radon_apply;
+// lmc_atomi.h holds its definition.  Sinograms are [n_img][n_angles][n_det] floats.
+constexpr int kRadonMaxAngles = LMC_MAX_RADON_ANGLES;
+constexpr int kRadonMaxDet = LMC_MAX_RADON_DET;
+constexpr int kRadonMaxSide = 1 << 20;        // sides up to here: the forward kernel's column estimate stays within its margin (lmc_radon_kernel.h)
+// what a launch does with u = A x (forward: a sinogram) or A^T r (adjoint: an image)
+enum RadonEpi {
+  kRadonRaw = 0,      // out = u
+  kRadonRhoL2,        // out = u - y                                    (forward; y = [n_angles][n_det])
+  kRadonRhoPois,      // out = pois_rho(u, y, beta)                     (forward; y = [2][n_angles][n_det]: counts, background)
+  kRadonRhoWl2,       // out = w (u - y)                                (forward; observation, weights)
+  kRadonRhoHub,       // out = clamp(u - y, -delta, delta)              (forward; observation, thresholds)
+  kRadonEnL2,         // part[image][block] = sum 1/2 (u - y)^2         (forward; no store of u)
+  kRadonEnPois,       // part[image][block] = sum pois_phi(u, y, beta)
+  kRadonEnWl2,        // part[image][block] = sum 1/2 w (u - y)^2
+  kRadonEnHub,        // part[image][block] = sum hub_h(u - y, delta)
+  kRadonSub,          // out -= coef u                                  (adjoint)
+  kRadonOverwrite     // out = a xin - coef u                           (adjoint)
+};
+// the residual and the energy epilogue of a data term, indexed by DataTerm (lmc_common.h)
+struct RadonTermEpi { RadonEpi rho, energy; };
+constexpr RadonTermEpi kRadonTermEpi[kNumTerms] = {{kRadonRhoL2, kRadonEnL2}, {kRadonRhoPois, kRadonEnPois}, {kRadonRhoWl2, kRadonEnWl2}, {kRadonRhoHub, kRadonEnHub}};
+// Host description of a validated operator and the device buffers of whoever owns them (a sampler handle, the stateless scratch).  The forward kernel
+// walks image rows for an angle with |cos| >= |sin| and image columns for the others; order lists the angles of the first kind, then the rest.
+struct RadonOp {
+  int on = 0;                 // the problem's operator is the Radon operator
+  int n_angles = 0, n_det = 0;
+  int n_row = 0;              // angles with |cos| >= |sin|: order[0 .. n_row)
+  float angles[kRadonMaxAngles] = {};
+  int order[kRadonMaxAngles] = {};
+  const float* tab_dev = nullptr;      // radon_table_floats: ax[n_angles][W], by[n_angles][H], the reciprocal slopes [n_angles], order [n_angles] (ints)
+  float* resid = nullptr;              // [n][n_angles][n_det] residual buffer of the step
+};
+// fills n_angles .. order from validated arguments (finite angles, 1 <= n_angles <= kRadonMaxAngles, 1 <= n_det <= kRadonMaxDet)
+void radon_prepare(RadonOp& R, const float* angles, int n_angles, int n_det);
+size_t radon_table_floats(int n_angles, int H, int W);
+// host: the device table of R on H x W images (float64 products, rounded once)
+void radon_tables(const RadonOp& R, int H, int W, float* out);
+// epi: kRadonRaw or a rho form; out = epilogue(A x), [n_img][n_angles][n_det]
+hipError_t launch_radon_forward(const RadonOp& R, int epi, const float* x, float* out, const float* y, int64_t n_img, int H, int W, hipStream_t st);
+// epi: kRadonRaw, kRadonSub, kRadonOverwrite; out = epilogue(A^T r), [n_img][H][W]; xin: kRadonOverwrite
+hipError_t launch_radon_adjoint(const RadonOp& R, int epi, const float* r, float* out, const float* xin, int64_t n_img, int H, int W, float a, float coef,
+                                hipStream_t st);
+// doubles `part` must hold for launch_radon_energy
+size_t radon_energy_partials(const RadonOp& R, int64_t n_img);
+// f_out[c] += sigma_f * the data term's value at x_c (term: DataTerm), float64 by partial sums in a fixed order
+hipError_t launch_radon_energy(const RadonOp& R, int term, const float* x, const float* y, int64_t n_img, int H, int W, float sigma_f, double* part,
+                               double* f_out, hipStream_t st);
+}  // namespace lmc

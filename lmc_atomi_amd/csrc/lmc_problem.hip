@@ -48,15 +48,17 @@ int load_problem(const lmc_problem* p, Problem& q) {
   struct KindMap { int op; lmc::DataTerm term; const char* no_mask; };
   static const char* const kWl2Mask = "(weighted Gaussian term) takes no mask_dev: there is no weighted mask kind, put the mask into the weights";
   static const char* const kHubMask = "(Huber data term) takes no mask_dev: there is no Huber mask kind, put the mask into the thresholds (delta = 0)";
-  static const KindMap kKinds[LMC_DATA_HUBER_PSF + 1] = {
+  static const KindMap kKinds[LMC_DATA_HUBER_RADON + 1] = {
       {LMC_DATA_NONE, lmc::kTermL2, nullptr},      {LMC_DATA_IDENTITY, lmc::kTermL2, nullptr},  {LMC_DATA_BLUR, lmc::kTermL2, nullptr},   {LMC_DATA_MASK, lmc::kTermL2, nullptr},
       {LMC_DATA_IDENTITY, lmc::kTermPois, nullptr}, {LMC_DATA_BLUR, lmc::kTermPois, nullptr},    {LMC_DATA_MASK, lmc::kTermPois, nullptr},
       {LMC_DATA_IDENTITY, lmc::kTermWl2, kWl2Mask}, {LMC_DATA_BLUR, lmc::kTermWl2, kWl2Mask},
       {LMC_DATA_PSF, lmc::kTermL2, nullptr},        {LMC_DATA_PSF, lmc::kTermPois, nullptr},
       {LMC_DATA_PSF, lmc::kTermWl2, "(weighted Gaussian term) takes no mask_dev: put the mask into the weights"},
       {LMC_DATA_SPECTRAL, lmc::kTermL2, nullptr},
-      {LMC_DATA_IDENTITY, lmc::kTermHub, kHubMask}, {LMC_DATA_BLUR, lmc::kTermHub, kHubMask},    {LMC_DATA_PSF, lmc::kTermHub, kHubMask}};
-  if (p->data_kind >= 0 && p->data_kind <= LMC_DATA_HUBER_PSF) {     // (any other kind: "unknown data_kind" below)
+      {LMC_DATA_IDENTITY, lmc::kTermHub, kHubMask}, {LMC_DATA_BLUR, lmc::kTermHub, kHubMask},    {LMC_DATA_PSF, lmc::kTermHub, kHubMask},
+      // (the Radon kinds take no mask for any term: the operator's case below says so)
+      {LMC_DATA_RADON, lmc::kTermL2, nullptr},      {LMC_DATA_RADON, lmc::kTermPois, nullptr},   {LMC_DATA_RADON, lmc::kTermWl2, nullptr}, {LMC_DATA_RADON, lmc::kTermHub, nullptr}};
+  if (p->data_kind >= 0 && p->data_kind <= LMC_DATA_HUBER_RADON) {     // (any other kind: "unknown data_kind" below)
     const KindMap& k = kKinds[p->data_kind];
     const bool bad_mask = k.no_mask && p->mask_dev;
     const bool bad_geometry = k.op == LMC_DATA_PSF && (p->kh || p->kw || p->oy || p->ox);
@@ -104,6 +106,21 @@ int load_problem(const lmc_problem* p, Problem& q) {
         return fail(LMC_E_UNSUPPORTED, "LMC_DATA_SPECTRAL: H and W must be powers of two in %d .. %d (got %dx%d)", lmc::kFftMin, lmc::kFftMax, p->H, p->W);
       q.fft.on = 1; q.fft.tab = p->y_dev;
       break;
+    case LMC_DATA_RADON: {      // kh = n_angles, kw = n_det, h_host = the angles (include/lmc_atomi.h)
+      if (!p->y_dev) return fail(LMC_E_INVALID, "data_kind %d (Radon operator) needs y_dev: the sinogram-shaped data", p->data_kind);
+      if (p->mask_dev || p->oy || p->ox || p->psf_kh || p->psf_kw || p->psf_oy || p->psf_ox || p->psf_separable)
+        return fail(LMC_E_INVALID, "data_kind %d (Radon operator) reads kh = n_angles, kw = n_det and h_host = the angles: mask_dev, oy, ox and the psf_* fields must be NULL / 0",
+                    p->data_kind);
+      if (!p->h_host) return fail(LMC_E_INVALID, "data_kind %d (Radon operator): h_host (the angles) is NULL", p->data_kind);
+      if (p->kh < 1 || p->kh > lmc::kRadonMaxAngles) return fail(LMC_E_INVALID, "Radon operator: n_angles (kh) %d outside 1..%d", p->kh, lmc::kRadonMaxAngles);
+      if (p->kw < 1 || p->kw > lmc::kRadonMaxDet) return fail(LMC_E_INVALID, "Radon operator: n_det (kw) %d outside 1..%d", p->kw, lmc::kRadonMaxDet);
+      for (int a = 0; a < p->kh; ++a)
+        if (!std::isfinite(p->h_host[a])) return fail(LMC_E_INVALID, "Radon operator: angle %d is not finite", a);
+      if (p->H > lmc::kRadonMaxSide || p->W > lmc::kRadonMaxSide)
+        return fail(LMC_E_UNSUPPORTED, "Radon operator: image sides up to %d (got %dx%d)", lmc::kRadonMaxSide, p->H, p->W);
+      lmc::radon_prepare(q.radon, p->h_host, p->kh, p->kw);
+      break;
+    }
     default: return fail(LMC_E_INVALID, "unknown data_kind %d", p->data_kind);
   }
   q.prior_kind = p->prior_kind;
@@ -245,17 +262,24 @@ int check_no_spectral(const Problem& q, const char* who, const char* why) {
   return fail(LMC_E_UNSUPPORTED, "%s does not take the spectral data term (LMC_DATA_SPECTRAL): %s", who, why);
 }
 
+// The entry points that have no form of the Radon operator refuse a problem that carries one.
+int check_no_radon(const Problem& q, const char* who, const char* why) {
+  if (!q.radon.on) return LMC_OK;
+  return fail(LMC_E_UNSUPPORTED, "%s does not take the Radon operator (LMC_DATA_RADON, LMC_DATA_POISSON_RADON, LMC_DATA_WL2_RADON, LMC_DATA_HUBER_RADON): %s", who, why);
+}
+
 // The data terms with step kernels of their own, in the order their refusals are made: its name in the messages, what the warm-started dual lacks
 // for it, and whether its step is a fused kernel of the term (the tiled kernel's and the full-width pipeline's instantiations: no Haar prior, variants
 // 0, 1, 7) or splits into the term's launches around the step of a problem without a data term (every prior and variant of that problem).
-// The rows of kTerms, then the large PSF and the spectral term.
+// The rows of kTerms, then the large PSF, the spectral term and the Radon operator.
 struct DataTermRules { const char *name, *warm; bool own_kernels; };
-constexpr int kNDataTerms = 3;
+constexpr int kNDataTerms = 4;
 static int data_terms_of(const Problem& q, DataTermRules (&r)[kNDataTerms]) {
   int n = 0;
   if (q.term != lmc::kTermL2) r[n++] = {kTerms[q.term].name, kTerms[q.term].warm, true};
   if (q.psf.on) r[n++] = {"a large PSF", "is not built for it", false};
   if (q.fft.on) r[n++] = {"the spectral data term", "is not built for it", false};
+  if (q.radon.on) r[n++] = {"the Radon operator", "is not built for it", false};
   return n;
 }
 
@@ -284,7 +308,7 @@ int check_step_problem(const Problem& q, float b) {
   const bool tv = q.prior_kind == LMC_PRIOR_TV_ISO || q.prior_kind == LMC_PRIOR_TV_ANISO;
   for (int i = 0; i < n; ++i) {
     const DataTermRules& r = terms[i];
-    if (r.own_kernels && q.psf.on) continue;     // (Poisson / weighted / Huber on a large PSF: the PSF's rules -- its step launch has no data term)
+    if (r.own_kernels && (q.psf.on || q.radon.on)) continue;     // (Poisson / weighted / Huber on a large PSF or the Radon operator: the operator's rules -- its step launch has no data term)
     const int rc = check_convex_term(q, r);
     if (rc) return rc;
     if (tv && q.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "%s with tv_rtol > 0: the early exit of the TV prox is not built for it; use the fixed count, tv_rtol = 0", r.name);
@@ -388,6 +412,40 @@ hipError_t Workspace::bind_fft(lmc::FftOp& F, size_t n_spec, size_t n_part) {
   return e;
 }
 
+hipError_t Workspace::bind_radon(lmc::RadonOp& R, int H, int W, size_t n_resid, hipStream_t st) {
+  const int na = R.n_angles;
+  std::vector<int32_t> key(3 + (size_t)na);
+  key[0] = H; key[1] = W; key[2] = R.n_det;
+  std::memcpy(key.data() + 3, R.angles, sizeof(float) * na);
+  hipError_t e = hipSuccess;
+  if (!radon_ev) e = hipEventCreateWithFlags(&radon_ev, hipEventDisableTiming);
+  if (e != hipSuccess) return e;
+  if (key != radon_key) {
+    const size_t nt = lmc::radon_table_floats(na, H, W);
+    if (!radon_key.empty()) e = hipEventSynchronize(radon_ev);      // the previous upload has read the pinned copy
+    radon_key.clear();
+    if (e != hipSuccess) return e;
+    if (nt > radon_cap) {
+      if (radon_tab) (void)hipFree(radon_tab);
+      if (radon_host) (void)hipHostFree(radon_host);
+      radon_tab = radon_host = nullptr; radon_cap = 0;
+      e = hipMalloc(&radon_tab, sizeof(float) * nt);
+      if (e == hipSuccess) e = hipHostMalloc(&radon_host, sizeof(float) * nt);
+      if (e != hipSuccess) return e;
+      radon_cap = nt;
+    }
+    lmc::radon_tables(R, H, W, radon_host);
+    e = hipMemcpyAsync(radon_tab, radon_host, sizeof(float) * nt, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipEventRecord(radon_ev, st);
+    if (e != hipSuccess) return e;
+    radon_key = std::move(key);
+  }
+  e = resid.need(n_resid);
+  R.tab_dev = radon_tab;
+  R.resid = resid.p;
+  return e;
+}
+
 hipError_t prepare(Workspace& ws, Problem& q, const lmc::StepArgs& probe, int64_t n_img, float pt, int what, hipStream_t st) {
   const size_t n = (size_t)n_img, npx = n * q.H * q.W;
   const bool step = what & kForStep, want_f = what & kForEnergyF, want_g = what & kForEnergyG;
@@ -420,6 +478,11 @@ hipError_t prepare(Workspace& ws, Problem& q, const lmc::StepArgs& probe, int64_
   }
   if (e == hipSuccess && q.fft.on && ((step && probe.data_kind == LMC_DATA_SPECTRAL) || want_f))
     e = ws.bind_fft(q.fft, lmc::fft_spec_floats(n_img, q.H, q.W), want_f ? lmc::fft_value_partials(n_img, q.H, q.W) : 0);
+  if (q.radon.on && ((step && probe.data_kind == LMC_DATA_RADON) || want_f)) {
+    const size_t n_resid = step && probe.data_kind == LMC_DATA_RADON ? n * q.radon.n_angles * q.radon.n_det : 0;
+    if (e == hipSuccess) e = ws.bind_radon(q.radon, q.H, q.W, n_resid, st);
+    if (want_f) n_dbl = std::max(n_dbl, lmc::radon_energy_partials(q.radon, n_img));
+  }
   if (q.wav.on && ((step && probe.prior_kind == LMC_PRIOR_WAVELET_L1) || want_g)) {
     need(ws.wav, lmc::wavelet_ws_floats(n_img, q.H, q.W));
     if (want_g) need(ws.wav_part, n * lmc::wavelet_partials(q.H, q.W, q.wav.levels));
@@ -530,6 +593,18 @@ static hipError_t launch_step_fft(const lmc::StepArgs& A, int variant, const Pro
       });
 }
 
+// The Radon operator: r = rho(A x) into radon.resid (a sinogram per chain), then A^T r.
+static hipError_t launch_step_radon(const lmc::StepArgs& A, int variant, const Problem& q, Workspace& ws, hipStream_t st, const char** name) {
+  const lmc::RadonOp& R = q.radon;
+  if (!R.on || !R.tab_dev || !R.resid) return hipErrorInvalidConfiguration;
+  const int rho = lmc::kRadonTermEpi[A.term].rho;
+  return launch_step_around(A, variant, q, ws, st, name, "radon_adj_kernel",
+      [&] { return lmc::launch_radon_forward(R, rho, A.x_in, R.resid, A.y, A.C, A.H, A.W, st); },
+      [&](bool alone, float a, float coef) {
+        return lmc::launch_radon_adjoint(R, alone ? lmc::kRadonOverwrite : lmc::kRadonSub, R.resid, A.x_out, alone ? A.x_in : nullptr, A.C, A.H, A.W, a, coef, st);
+      });
+}
+
 hipError_t launch_step(const lmc::StepArgs& A_in, int variant, const Problem& q, Workspace& ws, hipStream_t st, const char** name) {
   float *const state0 = ws.state[0].p, *const state1 = ws.state[1].p, *const pxbuf = ws.prox.p;
   if (A_in.prior_kind == LMC_PRIOR_WAVELET_L1) {
@@ -545,6 +620,7 @@ hipError_t launch_step(const lmc::StepArgs& A_in, int variant, const Problem& q,
   }
   if (A_in.data_kind == LMC_DATA_PSF) return launch_step_psf(A_in, variant, q, ws, st, name);
   if (A_in.data_kind == LMC_DATA_SPECTRAL) return launch_step_fft(A_in, variant, q, ws, st, name);
+  if (A_in.data_kind == LMC_DATA_RADON) return launch_step_radon(A_in, variant, q, ws, st, name);
   if (A_in.term != lmc::kTermL2) return launch_step_term(A_in, variant, ws, st, name);
   if (!A_in.box) return launch_step_nobox(A_in, variant, ws, st, name);
   lmc::StepArgs A = A_in;

@@ -105,7 +105,8 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   rc = rebuild_base(s);
   if (rc) { delete s; return rc; }
   // (a Huber term on a large PSF is left to the PSF's own rules here; the Poisson and weighted ones on a PSF are refused by this text)
-  if (s->prob.term != lmc::kTermL2 && !(s->prob.term == lmc::kTermHub && s->prob.psf.on) && variant_of(s->prob) == 7 && !term_pipe_covers(s->base)) {
+  // (any term on the Radon operator: the operator's rules -- the forced variant selects the kernel of the middle launch, as for LMC_DATA_NONE)
+  if (s->prob.term != lmc::kTermL2 && !(s->prob.term == lmc::kTermHub && s->prob.psf.on) && !s->prob.radon.on && variant_of(s->prob) == 7 && !term_pipe_covers(s->base)) {
     const TermInfo& t = kTerms[s->prob.term];
     delete s;
     return fail(LMC_E_UNSUPPORTED, "step_variant 7 (pipe) does not cover this %s problem: isotropic TV with 10 dual iterations (after tv_lagged_output), "
@@ -119,6 +120,7 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
   // (the caller's step stream need not order against the null stream)
   if (e == hipSuccess) e = prepare(s->ws, s->prob, s->base, s->C, s->epsg * s->gamma, kForStep | kForEnergies, nullptr);
   if (e == hipSuccess && s->ws.psf_ev) e = hipEventSynchronize(s->ws.psf_ev);
+  if (e == hipSuccess && s->ws.radon_ev) e = hipEventSynchronize(s->ws.radon_ev);      // (the Radon tables, likewise)
   {   // launch policy: the lmc_problem fields, their environment variables where a field is 0 -- read here, once, never inside lmc_sampler_step
     const Problem& q = s->prob;
     const int ipl = q.iters_per_launch ? q.iters_per_launch : env_int("LMC_ITERS_PER_LAUNCH", 0);
@@ -129,8 +131,8 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     // One iteration per launch (the pair kernels have no form of it) wherever an iteration is more than the one fused launch:
     //   prox_scale, box, wav.on   the prox is a launch of its own before every step (array-valued epsg, the clamp, the wavelet transforms)
     //   term                      the weighted Gaussian, the Huber and the Poisson data terms have kernels of their own, none of them a pair kernel
-    //   psf.on, fft.on            the large PSF and the spectral data term are three launches per iteration
-    if (q.prox_scale || q.box || q.wav.on || q.term != lmc::kTermL2 || q.psf.on || q.fft.on) { s->pol_pair = 0; s->pol_blockpair = 0; }
+    //   psf.on, fft.on, radon.on  the large PSF, the spectral data term and the Radon operator are three launches per iteration
+    if (q.prox_scale || q.box || q.wav.on || q.term != lmc::kTermL2 || q.psf.on || q.fft.on || q.radon.on) { s->pol_pair = 0; s->pol_blockpair = 0; }
   }
   if (e == hipSuccess && s->prob.tv_warm) {
     lmc::StepArgs probe = s->base;
@@ -514,6 +516,11 @@ int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     return fail(LMC_E_UNSUPPORTED, "MYMALA does not take the spectral data term (LMC_DATA_SPECTRAL): its Metropolis ratio is pinned for the fused step and its "
                 "energy by-products, which the three-launch spectral step does not form; use MYULA or SK-ROCK");
   }
+  if (cfg && out && cfg->struct_size == sizeof(lmc_myula_config) && cfg->problem.data_kind >= LMC_DATA_RADON && cfg->problem.data_kind <= LMC_DATA_HUBER_RADON) {
+    *out = nullptr;
+    return fail(LMC_E_UNSUPPORTED, "MYMALA does not take the Radon operator (LMC_DATA_RADON, LMC_DATA_POISSON_RADON, LMC_DATA_WL2_RADON, LMC_DATA_HUBER_RADON): its "
+                "Metropolis ratio is pinned for the fused step and its energy by-products, which the three-launch Radon step does not form; use MYULA or SK-ROCK");
+  }
   int rc = lmc_myula_create(cfg, out);
   if (rc) return rc;
   lmc_sampler* s = *out;
@@ -823,6 +830,7 @@ int lmc_ulpda_create(const lmc_ulpda_config* cfg, lmc_sampler** out) {
   lmc_problem pr = cfg->problem;
   if (pr.prior_kind == LMC_PRIOR_TV_ISO && pr.tv_niter < 1) pr.tv_niter = 1;   // unused by ULPDA; keeps the loader happy
   rc = load_problem(&pr, s->prob);
+  if (!rc) rc = check_no_radon(s->prob, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f A^T A)^{-1}, which is not built for the Radon operator; use MYULA");
   if (!rc) rc = check_no_term(s->prob, lmc::kTermHub, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Huber loss under an operator; use MYULA");
   if (!rc) rc = check_no_term(s->prob, lmc::kTermWl2, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f Op^T W Op)^{-1}, which is not built; use MYULA");
   if (!rc) rc = check_no_term(s->prob, lmc::kTermPois, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA");

@@ -171,6 +171,98 @@ class PSF(LinearOperator):
         return self._apply(y, True)
 
 
+class Radon(LinearOperator):
+    """Parallel-beam Radon operator for transmission CT and emission tomography (PET / SPECT) -- build extension; ``LMC_DATA_RADON`` in
+    include/lmc_atomi.h is its definition: the pixel-driven projector with linear interpolation on a detector of ``n_det`` unit bins, pixel ``(i, j)``
+    at ``t = X_j cos(theta) + Y_i sin(theta) + (n_det - 1) / 2`` giving ``max(0, 1 - |t - d|)`` of its value to bin ``d``.  ``angles``: 1 .. 1024
+    finite angles in radians (rounded to float32 once: those values are the angles); ``n_det``: 1 .. 4096, default ``ceil(hypot(H, W)) + 2`` -- every
+    pixel then keeps its full weight at every angle; a detector narrower than the image truncates.  ``matvec``: images ``[..., H*W]`` or
+    ``[..., H, W]`` -> sinograms ``[..., n_angles*n_det]``; ``rmatvec`` / ``.H``: the exact adjoint (``lmc_radon_apply``).  As ``Op`` of :class:`L2`
+    (with or without ``weights``), :class:`Poisson` and :class:`HuberLoss` (``b``, ``weights``, ``background``, ``delta`` of the sinogram's size) in
+    MYULA, SK-ROCK and :func:`EstimatePriorWeight` with every prior and ``bounds=`` a problem without a data term takes; MYMALA, ULPDA, the terms'
+    ``prox``, the non-convex terms, ``TV(rtol > 0)`` and ``TV(warm=True)`` raise ``NotImplementedError``."""
+
+    def __init__(self, dims, angles, n_det=None):
+        try:
+            self.dims = (int(dims[0]), int(dims[1]))
+        except (TypeError, ValueError, IndexError):
+            raise ValueError(f"dims must be a pair (H, W) (got {dims!r})") from None
+        H, W = self.dims
+        if H < 1 or W < 1 or max(H, W) > _capi.MAX_RADON_SIDE:
+            raise ValueError(f"Radon: image sides must be in 1 .. {_capi.MAX_RADON_SIDE} (got {H} x {W})")
+        a = np.atleast_1d(np.asarray(angles, dtype=np.float64))
+        if a.ndim != 1 or not 1 <= a.size <= _capi.MAX_RADON_ANGLES:
+            raise ValueError(f"Radon: angles must be a 1-D array of 1 .. {_capi.MAX_RADON_ANGLES} angles (got shape {np.shape(angles)})")
+        with np.errstate(over="ignore"):
+            a32 = np.ascontiguousarray(a, dtype=np.float32)
+        if not np.all(np.isfinite(a)) or not np.all(np.isfinite(a32)):
+            raise ValueError("Radon: the angles must be finite (as float32)")
+        self.angles = a32
+        n_det = int(np.ceil(np.hypot(H, W))) + 2 if n_det is None else int(n_det)
+        if not 1 <= n_det <= _capi.MAX_RADON_DET:
+            raise ValueError(f"Radon: n_det must be in 1 .. {_capi.MAX_RADON_DET} (got {n_det})")
+        self.n_det = n_det
+        self.n_angles = int(self.angles.size)
+        self.sino_shape = (self.n_angles, self.n_det)
+        super().__init__((self.n_angles * self.n_det, H * W))
+        self._bound = None
+
+    def descriptor(self):
+        """The operator's part of a data-term descriptor (``lmc_problem``: kh = n_angles, kw = n_det, h_host = the angles)."""
+        return {"angles": self.angles, "n_det": self.n_det}
+
+    def tables(self):
+        """``(ax, by)``, float32 ``[n_angles, W]`` and ``[n_angles, H]``, as the kernels read them (``lmc_radon_tables``: host only)."""
+        H, W = self.dims
+        ax = np.empty((self.n_angles, W), dtype=np.float32)
+        by = np.empty((self.n_angles, H), dtype=np.float32)
+        _capi.check(_capi.load().lmc_radon_tables(_dev.fptr(self.angles), self.n_angles, self.n_det, H, W, _dev.fptr(ax), _dev.fptr(by)))
+        return ax, by
+
+    def norm_bound(self):
+        """``max(A 1) * max(A^T 1) >= ||A||^2`` (A has no negative entry), from the tables in float64 on the host; cached."""
+        if self._bound is None:
+            ax, by = self.tables()
+            stride = self.n_det + 1                                # bin n_det of every angle takes what falls off the detector
+            rows = np.zeros(self.n_angles * stride)
+            cols = np.zeros(self.dims)
+            base = (np.arange(self.n_angles) * stride)[:, None]
+            for i in range(self.dims[0]):
+                t = (ax + by[:, i:i + 1]).astype(np.float64)      # (the float32 sum IS t)
+                f = np.floor(t)
+                w1 = t - f
+                for d, w in ((f, 1.0 - w1), (f + 1.0, w1)):
+                    ok = (d >= 0) & (d < self.n_det)
+                    w = np.where(ok, w, 0.0)
+                    rows += np.bincount((base + np.where(ok, d, self.n_det).astype(np.int64)).ravel(), weights=w.ravel(), minlength=rows.size)
+                    cols[i] += w.sum(0)
+            self._bound = float(rows.reshape(self.n_angles, stride)[:, :-1].max() * cols.max())
+        return self._bound
+
+    def _apply(self, x, adjoint):
+        import torch
+        n_in, n_out = (self.shape[0], self.shape[1]) if adjoint else (self.shape[1], self.shape[0])
+        t = _dev.to_dev(x)
+        if t.shape[-1] == n_in:
+            lead = tuple(t.shape[:-1])
+        elif t.ndim >= 2 and tuple(t.shape[-2:]) == (self.sino_shape if adjoint else self.dims):
+            lead = tuple(t.shape[:-2])
+        else:
+            raise ValueError(f"operand of shape {tuple(t.shape)} does not match operator input size {n_in}")
+        t = t.reshape(-1, n_in)
+        n_img = int(t.shape[0])
+        out = torch.empty((n_img, n_out), dtype=torch.float32, device=t.device)
+        _dev.run(t, "lmc_radon_apply", _dev.ptr(t), _dev.ptr(out), n_img, self.dims[0], self.dims[1], _dev.fptr(self.angles), self.n_angles, self.n_det,
+                 1 if adjoint else 0)
+        return _dev.like_input(out.reshape(lead + (n_out,)), x)
+
+    def matvec(self, x):
+        return self._apply(x, False)
+
+    def rmatvec(self, y):
+        return self._apply(y, True)
+
+
 class Gradient(LinearOperator):
     """Stacked forward differences ``[d_row x; d_col x]`` (zero in the last row / column) --
     drop-in for ``pylops.Gradient(dims, sampling=1, edge=False, kind='forward')``

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _capi, _dev
-from .operators import PSF, Convolve2D, Diagonal, FourierSampling, Identity, LinearOperator, PeriodicConvolve2D, _minus_k, spectral_tables
+from .operators import PSF, Convolve2D, Diagonal, FourierSampling, Identity, LinearOperator, PeriodicConvolve2D, Radon, _minus_k, spectral_tables
 
 
 _warned_pass_by_pass = False
@@ -127,6 +127,8 @@ class _Problem:
             # (a Poisson term: [2][H][W], the counts then the background; a weighted Gaussian term: the observation then the weights; a Huber term: the observation then the thresholds)
             if p.data_kind == _capi.DATA_SPECTRAL:      # the spectral term: the [11][H][W / 2 + 1] planes of lmc_spectral_tables
                 y = _dev.to_dev(data["y"], dev).reshape(_capi.SPECTRAL_PLANES, self.dims[0], self.dims[1] // 2 + 1)
+            elif p.data_kind in _capi.RADON_KINDS:      # the Radon operator: sinogram-shaped planes, one (Gaussian) or two (the other terms)
+                y = _dev.to_dev(data["y"], dev).reshape(((2,) if p.data_kind != _capi.DATA_RADON else ()) + (len(data["angles"]), int(data["n_det"])))
             else:
                 y = _dev.to_dev(data["y"], dev).reshape(((2,) if p.data_kind in _capi.TWO_PLANE_KINDS else ()) + self.dims)
             self._keep.append(y)
@@ -148,6 +150,11 @@ class _Problem:
             p.psf_oy, p.psf_ox = data["offset"]
             p.h_host = _dev.fptr(h)
             p.psf_separable = int(data.get("psf_separable", 0))
+        if p.data_kind in _capi.RADON_KINDS:      # the Radon operator rides in fields it does not otherwise read: kh = n_angles, kw = n_det, h_host = the angles
+            ang = np.ascontiguousarray(data["angles"], dtype=np.float32)
+            self._keep.append(ang)
+            p.kh, p.kw = ang.size, int(data["n_det"])
+            p.h_host = _dev.fptr(ang)
         p.prior_kind = prior["prior_kind"]
         p.prior_sigma = float(prior.get("prior_sigma", 0.0))
         # (ULPDA's anisotropic descriptor carries no prox: tv_niter stays 0)
@@ -252,8 +259,27 @@ class L2(ProxOperator):
         self._spectral = None
         if isinstance(Op, (FourierSampling, PeriodicConvolve2D)):
             self._set_spectral(weights)
+        elif isinstance(Op, Radon):
+            self._set_radon(weights)
         elif weights is not None:
             self._set_weights(weights)
+
+    def _set_radon(self, weights):
+        """The Gaussian terms on the Radon operator (``LMC_DATA_RADON`` / ``LMC_DATA_WL2_RADON``): ``b`` and ``weights`` live on the sinogram."""
+        if self.b is None:
+            raise ValueError("L2 with Radon needs b: the sinogram")
+        self.dims = self.Op.dims
+        y = _sino_plane(self.Op, self.b, "L2", "b")
+        if not np.all(np.isfinite(y)):
+            raise ValueError("L2 with Radon: b must be finite (mark a bad bin with weight 0, not with NaN)")
+        self._sino = np.ascontiguousarray(y, dtype=np.float32)
+        if weights is not None:
+            w = _sino_plane(self.Op, weights, "L2", "weights")
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError("L2: the weights must be finite and >= 0 (0 marks an unobserved bin)")
+            self.weights = w
+            self._yw = np.ascontiguousarray(np.stack([y, w]), dtype=np.float32)      # [2][n_angles][n_det]: what y_dev points to
+            self._yw_dev = {}
 
     def _set_spectral(self, weights):
         """The Fourier-domain data term (``LMC_DATA_SPECTRAL``): G and b of the operator, ``weights`` per frequency as G sqrt(w) and b sqrt(w), folded once on
@@ -325,6 +351,8 @@ class L2(ProxOperator):
         identity or no operator; ``max(w) = 1`` without weights.  Host arithmetic, no GPU."""
         if self._spectral is not None:      # sigma max_k A_k, A the folded |G|^2
             return self.sigma * self._amax
+        if isinstance(self.Op, Radon):      # ||A||^2 <= max(A 1) max(A^T 1)
+            return self.sigma * (float(np.max(self.weights)) if self.weights is not None else 1.0) * self.Op.norm_bound()
         op2 = float(np.abs(np.asarray(self.Op.h, dtype=np.float64)).sum()) ** 2 if isinstance(self.Op, (Convolve2D, PSF)) else 1.0
         wmax = float(np.max(self.weights)) if self.weights is not None else 1.0
         return self.sigma * wmax * op2
@@ -335,6 +363,11 @@ class L2(ProxOperator):
         if self._spectral is not None:
             tab = self._spectral_buffer() if torch.cuda.is_available() else self._spectral["tab"]
             return {"data_kind": _capi.DATA_SPECTRAL, "sigma_f": self.sigma, "y": tab}
+        if isinstance(self.Op, Radon):
+            if self.weights is not None:
+                yw = self._buffer() if torch.cuda.is_available() else self._yw
+                return {"data_kind": _capi.DATA_WL2_RADON, "sigma_f": self.sigma, "y": yw, **self.Op.descriptor()}
+            return {"data_kind": _capi.DATA_RADON, "sigma_f": self.sigma, "y": self._sino, **self.Op.descriptor()}
         if self.weights is not None:
             yw = self._buffer() if torch.cuda.is_available() else self._yw      # (without a device: the host array, for whoever only reads the description)
             if isinstance(self.Op, PSF):
@@ -394,6 +427,8 @@ class L2(ProxOperator):
             return _dev.like_input(out, x)
         if isinstance(self.Op, PSF):
             raise NotImplementedError("L2.prox with a large PSF: the implicit step (I + tau sigma Op^T Op)^{-1} is not built for it (lmc_l2_prox refuses it)")
+        if isinstance(self.Op, Radon):
+            raise NotImplementedError("L2.prox with Radon: the implicit step (I + tau sigma A^T A)^{-1} is not built for it (lmc_l2_prox refuses it)")
         if self.weights is not None:
             raise NotImplementedError("L2.prox with weights: the implicit step (I + tau sigma Op^T W Op)^{-1} is not built (lmc_l2_prox refuses it)")
         if self.Op is None and self.b is None:
@@ -438,8 +473,22 @@ class Poisson(ProxOperator):
 
     def __init__(self, Op, b, background, sigma=1.0, dims=None):
         super().__init__(Op, True)
+        if isinstance(Op, Radon):      # emission tomography: counts and background live on the sinogram (LMC_DATA_POISSON_RADON)
+            self.dims = Op.dims
+            y = _sino_plane(Op, b, "Poisson", "b")
+            if not np.all(np.isfinite(y)) or np.any(y < 0):
+                raise ValueError("Poisson: the counts b must be finite and >= 0")
+            beta = _sino_plane(Op, background, "Poisson", "background", scalar=True)
+            if not np.all(np.isfinite(beta)) or np.any(beta <= 0):
+                raise ValueError("Poisson: the background must be finite and > 0 (a scalar or an array of the sinogram's shape)")
+            self.b, self.background = y, beta
+            self.sigma = float(sigma)
+            self._yb = np.ascontiguousarray(np.stack([y, beta]), dtype=np.float32)      # [2][n_angles][n_det]: what y_dev points to
+            self._yb_dev = {}
+            self._prob = None
+            return
         if not isinstance(Op, (Convolve2D, PSF, Diagonal, Identity)):
-            raise NotImplementedError(f"no device functor for Poisson with Op of type {type(Op).__name__} (Convolve2D, PSF, Diagonal or Identity)")
+            raise NotImplementedError(f"no device functor for Poisson with Op of type {type(Op).__name__} (Convolve2D, PSF, Diagonal, Identity or Radon)")
         y = _host(b).astype(np.float64)
         # the image shape: `dims`, else the operator's, else that of an [H, W] array of counts or background
         for cand in (dims, getattr(Op, "dims", None), y.shape if y.ndim == 2 else None, np.shape(background) if np.ndim(background) == 2 else None):
@@ -474,6 +523,8 @@ class Poisson(ProxOperator):
 
     def descriptor(self):
         yb = self._buffer() if torch.cuda.is_available() else self._yb      # (without a device: the host array, for whoever only reads the description)
+        if isinstance(self.Op, Radon):
+            return {"data_kind": _capi.DATA_POISSON_RADON, "sigma_f": self.sigma, "y": yb, **self.Op.descriptor()}
         if isinstance(self.Op, PSF):
             return {"data_kind": _capi.DATA_POISSON_PSF, "sigma_f": self.sigma, "y": yb, **self.Op.descriptor()}
         if isinstance(self.Op, Convolve2D):
@@ -485,6 +536,8 @@ class Poisson(ProxOperator):
     def grad_lipschitz(self):
         """``L_f = sigma * max(b / background^2) * ||Op||^2`` with ``||Op|| <= sum |h|`` for a convolution and the factor 1 for a mask (entries in [0, 1])
         or the identity.  Host arithmetic, no GPU."""
+        if isinstance(self.Op, Radon):      # ||A||^2 <= max(A 1) max(A^T 1)
+            return self.sigma * float(np.max(self.b / self.background ** 2)) * self.Op.norm_bound()
         op2 = float(np.abs(np.asarray(self.Op.h, dtype=np.float64)).sum()) ** 2 if isinstance(self.Op, (Convolve2D, PSF)) else 1.0
         return self.sigma * float(np.max(self.b / self.background ** 2)) * op2
 
@@ -526,8 +579,22 @@ class HuberLoss(ProxOperator):
             raise NotImplementedError("HuberLoss with Op = Diagonal: there is no Huber mask kind -- a binary mask on a blur is delta = 0 at the masked pixels")
         if isinstance(Op, (FourierSampling, PeriodicConvolve2D)):
             raise NotImplementedError(f"HuberLoss with Op of type {type(Op).__name__}: the Huber loss of a Fourier-domain residual is not built")
+        if isinstance(Op, Radon):      # robust tomography: observation and thresholds live on the sinogram (LMC_DATA_HUBER_RADON)
+            self.dims = Op.dims
+            y = _sino_plane(Op, b, "HuberLoss", "b")
+            if not np.all(np.isfinite(y)):
+                raise ValueError("HuberLoss: b must be finite (mark a bad bin with delta = 0, not with NaN)")
+            d = _sino_plane(Op, delta, "HuberLoss", "delta", scalar=True)
+            if np.any(np.isnan(d)) or np.any(d < 0):
+                raise ValueError("HuberLoss: delta must be >= 0 and not NaN (0 marks an unobserved bin, +inf the plain quadratic term)")
+            self.b, self.delta = y, d
+            self.sigma = float(sigma)
+            self._yd = np.ascontiguousarray(np.stack([y, d]), dtype=np.float32)      # [2][n_angles][n_det]: what y_dev points to
+            self._yd_dev = {}
+            self._prob = None
+            return
         if not isinstance(Op, (Convolve2D, PSF, Identity)):
-            raise NotImplementedError(f"no device functor for HuberLoss with Op of type {type(Op).__name__} (Convolve2D, PSF or Identity)")
+            raise NotImplementedError(f"no device functor for HuberLoss with Op of type {type(Op).__name__} (Convolve2D, PSF, Identity or Radon)")
         y = _host(b).astype(np.float64)
         d = _host(delta).astype(np.float64)
         # the image shape: `dims`, else the operator's, else that of an [H, W] array of observations or thresholds
@@ -562,6 +629,8 @@ class HuberLoss(ProxOperator):
 
     def descriptor(self):
         yd = self._buffer() if torch.cuda.is_available() else self._yd      # (without a device: the host array, for whoever only reads the description)
+        if isinstance(self.Op, Radon):
+            return {"data_kind": _capi.DATA_HUBER_RADON, "sigma_f": self.sigma, "y": yd, **self.Op.descriptor()}
         if isinstance(self.Op, PSF):
             return {"data_kind": _capi.DATA_HUBER_PSF, "sigma_f": self.sigma, "y": yd, **self.Op.descriptor()}
         if isinstance(self.Op, Convolve2D):
@@ -571,6 +640,8 @@ class HuberLoss(ProxOperator):
     def grad_lipschitz(self):
         """``L_f = sigma * ||Op||^2`` (the clamp is 1-Lipschitz: the bound of the plain term) with ``||Op|| <= sum |h|`` for a convolution and 1 for the
         identity.  Host arithmetic, no GPU."""
+        if isinstance(self.Op, Radon):      # ||A||^2 <= max(A 1) max(A^T 1)
+            return self.sigma * self.Op.norm_bound()
         op2 = float(np.abs(np.asarray(self.Op.h, dtype=np.float64)).sum()) ** 2 if isinstance(self.Op, (Convolve2D, PSF)) else 1.0
         return self.sigma * op2
 
@@ -592,6 +663,17 @@ class HuberLoss(ProxOperator):
 
 def _host(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _sino_plane(op, a, who, what, scalar=False):
+    """``a`` as a float64 ``[n_angles, n_det]`` plane of the sinogram of the Radon operator ``op`` (``scalar``: a scalar fills it); ``ValueError`` for
+    any other size."""
+    v = _host(a).astype(np.float64)
+    if scalar and v.ndim == 0:
+        return np.full(op.sino_shape, float(v))
+    if v.size != op.sino_shape[0] * op.sino_shape[1] or (v.ndim >= 2 and v.shape != op.sino_shape):
+        raise ValueError(f"{who} with Radon: {what} of shape {v.shape} for a sinogram of shape {op.sino_shape} ([n_angles, n_det] or flat)")
+    return v.reshape(op.sino_shape)
 
 
 class L1(ProxOperator):
