@@ -96,6 +96,7 @@ __device__ __forceinline__ void prow_store(float* row, int lane, const float (&v
 // anyway plus one move each, whatever PXL is.  (Pairs of ADJACENT pixels (2i, 2i + 1), the layout before, make every neighbour operand straddle
 // two register pairs: one VALU instruction in six of a TV wave was a move that re-paired them.)  max / rsq stay scalar.
 typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));      // what the non-temporal builtins take (float4 is a class)
 __device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ v2f pk_set(float a) { return v2f{a, a}; }
 // projection onto [-1, 1] per component (the dual ball of the anisotropic TV prior)
@@ -416,13 +417,19 @@ __device__ __forceinline__ void gload_row(float (&dst)[PXL], const float* __rest
 
 // The same without the select: for values that are masked where they are USED (a select at load time makes the wave wait for
 // the prefetch at once).  Lanes / pixels past the row read its start.
-template <int PXL>
+// STREAM (aligned rows only): a row that is read once -- the load carries the non-temporal policy (`nt` in the ISA).
+template <int PXL, bool STREAM = false>
 __device__ __forceinline__ void gload_raw(float (&dst)[PXL], const float* __restrict__ row, int c0, int W, bool al = true) {
   if (al) {
 #pragma unroll
     for (int g = 0; g < PXL / 4; ++g) {
-      const float4 v = *reinterpret_cast<const float4*>(row + (c0 + 4 * g < W ? c0 + 4 * g : 0));
-      dst[4 * g] = v.x; dst[4 * g + 1] = v.y; dst[4 * g + 2] = v.z; dst[4 * g + 3] = v.w;
+      if constexpr (STREAM) {
+        const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(row + (c0 + 4 * g < W ? c0 + 4 * g : 0)));
+        dst[4 * g] = v.x; dst[4 * g + 1] = v.y; dst[4 * g + 2] = v.z; dst[4 * g + 3] = v.w;
+      } else {
+        const float4 v = *reinterpret_cast<const float4*>(row + (c0 + 4 * g < W ? c0 + 4 * g : 0));
+        dst[4 * g] = v.x; dst[4 * g + 1] = v.y; dst[4 * g + 2] = v.z; dst[4 * g + 3] = v.w;
+      }
     }
   } else {
 #pragma unroll
@@ -436,9 +443,17 @@ __device__ __forceinline__ void gfix_raw(float (&r)[PXL], int c0, int W) {
 }
 
 // Four pixels of a row to global memory: columns c .. c + 3, of which those in [lo, hi) are written (the interior of a column strip, and < W).
+// STREAM (aligned rows only): a non-temporal store, for rows nobody reads back before the next launch.  Written as four scalar stores that the SLP
+// vectoriser joins into one global_store_dwordx4 nt: a vector built by hand re-pairs the combine wave's arithmetic and costs it 7 v_mov_b32 per tick.
+template <bool STREAM = false>
 __device__ __forceinline__ void gstore4(float* __restrict__ row, int c, int lo, int hi, bool al, float v0, float v1, float v2, float v3) {
   if (al) {        // W, lo, hi multiples of 4: the group is inside or outside as a whole
-    if (c >= lo && c < hi) *reinterpret_cast<float4*>(row + c) = make_float4(v0, v1, v2, v3);
+    if (c >= lo && c < hi) {
+      if constexpr (STREAM) {
+        float* const p = static_cast<float*>(__builtin_assume_aligned(row + c, 16));
+        __builtin_nontemporal_store(v0, p); __builtin_nontemporal_store(v1, p + 1); __builtin_nontemporal_store(v2, p + 2); __builtin_nontemporal_store(v3, p + 3);
+      } else *reinterpret_cast<float4*>(row + c) = make_float4(v0, v1, v2, v3);
+    }
   } else store4_dword_aligned(row, c, lo, hi, v0, v1, v2, v3);
 }
 
@@ -636,6 +651,11 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
   const size_t img = (size_t)H * W;
   const float* __restrict__ xin = A.x_in + (size_t)chain * img;
   float* __restrict__ xout = A.x_out + (size_t)chain * img;
+  // Two teams: the state is a use-once stream through L2 -- every row of x_in is read once and every row of x_out written once per launch, while
+  // the observation rows are re-read by every chain of the XCD.  The L wave's x prefetch and the C wave's stores carry the non-temporal policy, the
+  // y loads keep the default one (round 10: -2 % per step, and as much with the kernel alone).  The anisotropic two-team
+  // kernel and the one-team kernels keep their instruction streams (tests/test_stream_policy_resources.py).
+  constexpr bool kStream = TEAMS == 2 && !ANISO;
 
   // ring rows < 0, hand-offs of tick -1, g, the normals' slab (read by C whatever the noise mode) and, two teams, the seam records
   for (int e = threadIdx.x; e < L::total; e += blockDim.x) lds_all[e] = 0.f;
@@ -653,6 +673,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
   // Issue arbitration on the shared SIMDs: the short, latency-bound waves everybody waits for at the barrier (L publishes the
   // ring row, C frees the hand-off slot) go first, the TV waves next, the Philox wave -- pure arithmetic, a quad row-group ahead
   // of its consumer -- last.  Measured: 2.04 -> 1.98 ms; the other way round (TV waves first) 2.37 ms.
+  // (Two teams with every role above the side-stream moment reduction's waves, 3 / 3 / 2 / 1: measured in round 10, no gain, not kept)
   constexpr int kPrioL = 3, kPrioC = 3, kPrioT = 1, kPrioN = 0;
   if (wave == 0) __builtin_amdgcn_s_setprio(kPrioL);
   else if (wave == NT + 1) __builtin_amdgcn_s_setprio(kPrioC);
@@ -689,7 +710,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
 #pragma unroll
       for (int k = 0; k < NP; ++k) { hxw[a][k] = pk_set(0.f); hrw[a][k] = pk_set(0.f); }
 #pragma unroll
-    for (int u = 0; u < kXPF; ++u) gload_raw<PXL>(xpre[u], xin + (size_t)min(u, H - 1) * W, cl, W, al);
+    for (int u = 0; u < kXPF; ++u) gload_raw<PXL, kStream>(xpre[u], xin + (size_t)min(u, H - 1) * W, cl, W, al);
     // Vector-memory loads return in order: waiting for a load also waits for every load issued before it.  So the loads a tick
     // consumes must be the OLDEST in flight: y rows are requested three ticks ahead and, inside a tick, before the x row that is only
     // needed four ticks later (with y one tick ahead and issued after x, every tick waited for a fresh HBM access: ~2000 cycles).
@@ -768,7 +789,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
 #pragma unroll
         for (int k = 0; k < PXL; ++k) xv[k] = (t < H && col_in(k)) ? xpre[U][k] : 0.f;
         prow_store<PXL>(ring_row(t), lane, xv);
-        gload_raw<PXL>(xpre[U], xin + (size_t)min(t + kXPF, H - 1) * W, cl, W, al);
+        gload_raw<PXL, kStream>(xpre[U], xin + (size_t)min(t + kXPF, H - 1) * W, cl, W, al);
       }
       if constexpr (CHAIN && !kStateInN) {   // dual state row t - E - 1 of the previous link -> stage 1's hand-off slot P (read next tick)
         float* hb = lds + L::o_hand0 + P * 4 * RP;
@@ -1404,7 +1425,7 @@ __device__ __forceinline__ void pipe_body(const StepArgs& A) {
 #pragma unroll
         for (int g = 0; g < PXL / 4; ++g) {
           if (c0 + 4 * g < st_hi && c0 + 4 * g + 3 >= st_lo)
-            gstore4(xout + go, c0 + 4 * g, st_lo, st_hi, al, pair_px<NP>(ovp, 4 * g), pair_px<NP>(ovp, 4 * g + 1), pair_px<NP>(ovp, 4 * g + 2), pair_px<NP>(ovp, 4 * g + 3));
+            gstore4<kStream>(xout + go, c0 + 4 * g, st_lo, st_hi, al, pair_px<NP>(ovp, 4 * g), pair_px<NP>(ovp, 4 * g + 1), pair_px<NP>(ovp, 4 * g + 2), pair_px<NP>(ovp, 4 * g + 3));
         }
       }
       __syncthreads();
