@@ -250,7 +250,32 @@ typedef enum lmc_prior_kind {
    * Honoured by lmc_myula_create, lmc_mymala_create, lmc_skrock_create, lmc_fused_eval, lmc_energies, lmc_sampler_energies, lmc_prior_statistic,
    * lmc_sapg_dimension (d = H W - (H >> L)(W >> L), k = 1), lmc_sampler_sapg, lmc_sampler_set_prior_sigma.  LMC_E_UNSUPPORTED, with the reason in
    * lmc_last_error: box_enable (not separable, as LMC_PRIOR_HAAR_L1), prox_scale, lmc_ulpda_create.  iterations_per_launch is ignored. */
-  LMC_PRIOR_WAVELET_L1 = 7
+  LMC_PRIOR_WAVELET_L1 = 7,
+  /* Vectorial total variation of a multi-channel image (appended; LMC_ATOMI_ABI_VERSION stays 4 and sizeof(lmc_problem) 200).  Build-specified (the
+   * reference has single-plane images only); this text is its definition.  On x[ch][H][W], ch = 0 .. n_channels - 1, 1 <= n_channels <= LMC_MAX_CHANNELS:
+   *   g(x) = sigma * VTV(x),   VTV(x) = sum_pixels sqrt( sum_ch (d_r x_ch)^2 + (d_c x_ch)^2 )
+   * -- ONE gradient norm per pixel over all channels (Blomgren-Chan / Bresson-Chan, the "Frobenius" form), with the forward differences of lmc_gradient
+   * (zero in the last row / column) and their negative adjoint div.  The channels share their edges; they couple in the dual projection and nowhere else.
+   * prox_{t g}(x) is niter fast-gradient-projection dual iterations from the zero dual with gamma = t sigma -- the loop of LMC_PRIOR_TV_ISO with the
+   * projection weight shared by the channels of a pixel:
+   *   (rr, ss) = (p, q) = 0                                          per channel
+   *   repeat niter times (k = 0 ...):
+   *     sol_ch = clip(x_ch - gamma div(rr_ch, ss_ch))                clip only with a box; else the identity
+   *     (r, s)_ch = (rr, ss)_ch - (step / gamma) grad(sol_ch)
+   *     w = max(1, sqrt(sum_ch r_ch^2 + s_ch^2))                     ONE w per pixel
+   *     (p', q')_ch = (r, s)_ch / w
+   *     (rr, ss)_ch = (p', q')_ch + beta_k ((p', q')_ch - (p, q)_ch);   (p, q) = (p', q')
+   *   return clip(x_ch - gamma div(rr_ch, ss_ch))
+   * step defaults to 1/8 (||grad||^2 <= 8 holds per channel and the operator is block-diagonal over the channels); beta_k: the table of LMC_PRIOR_TV_ISO.
+   * With a box the primal iterate of EVERY dual iteration and the returned one are clipped (Beck and Teboulle's constrained FGP, as the box TV kernels do it;
+   * clipping afterwards gives a different point).  n_channels = 1 is LMC_PRIOR_TV_ISO.  1 <= niter <= LMC_MAX_TV_ITERS.
+   * Layout: channel-major -- image (ch, n) is at x + ch * channel_stride + n * H * W; a batch of n_img multi-channel images has channel_stride = n_img * H * W.
+   * Kernels (lmc_vtv.hip): vtv_prox_kernel -- a workgroup owns a patch (tile + halo) of one multi-channel image, a lane all channels of its pixels, so w is
+   * lane-local; up to 10 dual iterations are ONE launch, more are chained launches that carry the dual state through work buffers exactly.  vtv_value_kernel:
+   * float64 partial sums in a fixed order.  No atomics: equal runs give equal bits.
+   * Valid in lmc_mch_* and lmc_vtv_* only; every other entry point that takes an lmc_problem: LMC_E_UNSUPPORTED with the reason in lmc_last_error
+   * (lmc_prior_statistic and lmc_sapg_dimension, which read the kinds with a single-plane value alone, keep their range check: LMC_E_INVALID). */
+  LMC_PRIOR_VTV = 8
 } lmc_prior_kind;
 
 typedef enum lmc_ncvx_kind {
@@ -282,6 +307,7 @@ typedef enum lmc_noise_mode {
 #define LMC_MAX_RADON_ANGLES 1024  /* LMC_DATA_RADON .. LMC_DATA_HUBER_RADON / lmc_radon_apply: projection angles */
 #define LMC_MAX_RADON_DET 4096     /* ... detector bins */
 #define LMC_MAX_RADON_SIDE 1048576 /* ... image rows, image columns */
+#define LMC_MAX_CHANNELS 4         /* LMC_PRIOR_VTV: channels of a multi-channel image */
 
 /* Geometry + potential U(x) = f(x) + eps*g(x).  Plain data; copied by the callee. */
 typedef struct lmc_problem {
@@ -489,6 +515,21 @@ int lmc_haar_l1_prox(const float* x_dev, float* out_dev, int64_t n_img, int32_t 
 int lmc_wavelet_filter(int32_t p, double* h_out, int32_t* len_out);
 int lmc_wavelet_apply(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t p, int32_t levels, int32_t inverse, void* stream);
 int lmc_wavelet_l1_prox(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t p, int32_t levels, float thr, void* stream);
+
+/* The prox and the value of LMC_PRIOR_VTV (its text above is the definition) on n_img multi-channel images in channel-major layout.
+ * lmc_vtv_prox: out = prox_{t_sigma VTV}(x), niter dual iterations (1 .. LMC_MAX_TV_ITERS) of step `step` (0 -> 1/8) with the momentum table betas_host
+ * (niter floats; NULL: the default table); box_enable != 0: the constrained form on [box_lo, box_hi] (box_lo < box_hi, neither NaN, infinite ends allowed;
+ * else LMC_E_INVALID).  out has the layout of x; not in place.  t_sigma = 0 is the identity (out = x, box or not); negative or NaN: LMC_E_INVALID.
+ * n_channels outside 1 .. LMC_MAX_CHANNELS, or a channel_stride below n_img * H * W with more than one channel: LMC_E_INVALID.  Work buffers (the dual
+ * state of a chained prox, the partial sums of the value) come from the workspace of the stateless calls.
+ * lmc_vtv_value: out_dev[n] = VTV(x_n), unweighted, n_img doubles on the device.
+ * lmc_vtv_plan: host only, no device needed.  The launch plan of a prox of niter iterations on n_channels channels: the tile a workgroup owns (its patch is
+ * the tile plus a halo of iters_per_launch pixels, one more on a chained prox), the dual iterations of one launch and the launches; niter <= 10 is one
+ * launch at every channel count.  H and W >= 1 are checked and do not change the plan.  Every output may be NULL. */
+int lmc_vtv_prox(const float* x_dev, float* out_dev, int64_t n_img, int32_t n_channels, int64_t channel_stride, int32_t H, int32_t W, float t_sigma,
+                 int32_t niter, float step, const float* betas_host, int32_t box_enable, float box_lo, float box_hi, void* stream);
+int lmc_vtv_value(const float* x_dev, double* out_dev, int64_t n_img, int32_t n_channels, int64_t channel_stride, int32_t H, int32_t W, void* stream);
+int lmc_vtv_plan(int32_t H, int32_t W, int32_t n_channels, int32_t niter, int32_t* tile_h, int32_t* tile_w, int32_t* iters_per_launch, int32_t* n_launches);
 
 /* Chain probes for convergence diagnostics across chains (split R-hat / effective sample size; SURVEY 8(f).3 -- absent in the
  * reference, whose only diagnostics are the per-iterate scalars of prox_lmc_deconv.py:128-133): every image is reduced to a
@@ -770,6 +811,49 @@ const char* lmc_sampler_kernel_name(const lmc_sampler* s);
  * reruns_host[4] (host, nullable) = chains whose run had to be repeated after round 1 / 2 / 3 / 4, summed over all calls since creation
  * (round 4's count stays 0 by construction).  Synchronises `stream`.  LMC_E_STATE when the sampler does not use the device path. */
 int lmc_sampler_tv_exit_stats(lmc_sampler* s, int32_t which, int32_t* passes_dev, uint64_t* reruns_host, void* stream);
+
+/* ---- multi-channel MYULA sampler: colour, Bayer mosaics, dual-energy pairs under the vectorial TV prior --------------------------------
+ * A handle type of its own (lmc_mch.hip), not an lmc_sampler: that type's pair launches, early exits, warm duals and side-stream moments stay as they
+ * are.  The posterior is exp(-sum_ch f_ch(x_ch) - epsg sigma VTV(x)); one iteration is MYULA's (lmc_myula_create) on all channels at once, in two stages:
+ *   prox   lmc_vtv_prox at the parameter epsg gamma sigma over all chains and channels, into a buffer of the handle;
+ *   step   per channel ONE launch of the fused step kernel of the same problem without a prior, which consumes that channel's block of the buffer as a
+ *          ready-made prox: x_ch <- (1 - tau / gamma) x_ch - tau grad f_ch(x_ch) + (tau / gamma) prox_ch + sqrt(2 tau) xi_ch.
+ * problem: prior_kind must be LMC_PRIOR_VTV; prior_sigma, tv_niter, tv_step, tv_betas_host and box_* are read as for LMC_PRIOR_TV_ISO; data_kind is
+ * LMC_DATA_NONE, IDENTITY, BLUR or MASK; y_dev is [n_channels][H][W]; mask_dev is [H][W] (mask_channel_stride = 0: one mask for all channels) or
+ * [n_channels][H][W] (mask_channel_stride = H * W: one per channel, a Bayer mosaic); sigma_f and the taps are shared by the channels.
+ * State and injected noise are [n_channels][n_chains][H][W] ([n_iters] in front for the noise): channel-major, each channel's chains contiguous.
+ * Noise: channel ch draws the Philox field of the seed (seed + (ch << 32)) mod 2^64 -- key1 = (uint32)(seed >> 32) + ch -- so channel 0 is the field of
+ * a grey sampler of the same seed, and any sharding of the chains (chain_offset) reproduces the same trajectories.
+ * Moments: [n_channels][H][W] doubles for the sum and the sum of squares (the reductions of lmc_sampler_get_moments, one accumulator per channel) and one
+ * count = kept iterates x chains.  Energies: f[c] = sum_ch f_ch(x_ch,c) (the energy launches of lmc_sampler_energies per channel, added in float64),
+ * g[c] = sigma VTV(x_c) (without the indicator of a box, as everywhere).
+ * LMC_E_UNSUPPORTED, with the reason in lmc_last_error: every other data_kind, ncvx_kind != LMC_NCVX_NONE, tv_rtol > 0, tv_warm, prox_scale,
+ * tv_lagged_output.  LMC_E_INVALID: n_channels outside 1 .. LMC_MAX_CHANNELS, tv_niter outside 1 .. LMC_MAX_TV_ITERS, bad bounds, a
+ * mask_channel_stride other than 0 or H * W, a prior_kind other than LMC_PRIOR_VTV.  Calls on one handle must be serialised by the caller. */
+typedef struct lmc_mch lmc_mch; /* opaque */
+
+typedef struct lmc_mch_config {
+  uint32_t struct_size;     /* = sizeof(lmc_mch_config) */
+  lmc_problem problem;
+  int32_t n_channels;
+  int64_t mask_channel_stride;          /* 0: one mask for all channels; H*W: one per channel (a Bayer mosaic) */
+  int32_t n_chains; int64_t chain_offset; float tau, gamma, epsg; uint64_t seed; int32_t noise_mode;
+  int32_t moments, burn_in, thin;
+} lmc_mch_config;
+
+int lmc_mch_create(const lmc_mch_config* cfg, lmc_mch** out);
+void lmc_mch_destroy(lmc_mch* s);
+int lmc_mch_set_state(lmc_mch* s, const float* x_dev, void* stream);
+int lmc_mch_get_state(lmc_mch* s, float* x_dev, void* stream);
+int lmc_mch_step(lmc_mch* s, int32_t n_iters, const float* noise_dev, void* stream);
+int64_t lmc_mch_iteration(const lmc_mch* s);
+int lmc_mch_set_iteration(lmc_mch* s, int64_t it);
+int lmc_mch_get_moments(lmc_mch* s, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream);
+int lmc_mch_reset_moments(lmc_mch* s, void* stream);
+int lmc_mch_energies(lmc_mch* s, double* f_out_dev, double* g_out_dev, void* stream);
+int lmc_mch_noise(lmc_mch* s, int64_t iteration, float* out_dev, void* stream);
+/* the kernels of the latest iteration: the prox kernel and the step kernel of the last channel */
+const char* lmc_mch_kernel_name(const lmc_mch* s);
 
 /* ---- multi-GPU: the one collective of the path ----------------------------------------------
  * Chains are sharded over GPUs by global chain id (chain_offset), one process per GPU, no data-path collective.  The only

@@ -34,6 +34,8 @@ MAX_RADON_ANGLES, MAX_RADON_DET, MAX_RADON_SIDE = 1024, 4096, 1 << 20
 TWO_PLANE_KINDS = POISSON_KINDS + WL2_KINDS + (DATA_POISSON_PSF, DATA_WL2_PSF) + HUBER_KINDS      # y_dev is [2][H][W]
 PRIOR_NONE, PRIOR_L2, PRIOR_L1, PRIOR_TV_ISO, PRIOR_TV_ANISO, PRIOR_HAAR_L1, PRIOR_EPROX = 0, 1, 2, 3, 4, 5, 6
 PRIOR_WAVELET_L1 = 7      # Daubechies wavelet-l1: lmc_problem.tv_niter = levels, eprox_kind = p (the struct has no hole left)
+PRIOR_VTV = 8             # vectorial TV of a multi-channel image: lmc_mch_* and lmc_vtv_* only, every other entry point refuses it
+MAX_CHANNELS = 4
 NOISE_PHILOX, NOISE_INJECTED, NOISE_NONE = 0, 1, 2
 NCVX_NONE, NCVX_MC_TV, NCVX_ME_TV, NCVX_MC_TV_ANISO, NCVX_ME_TV_ANISO = 0, 1, 2, 3, 4
 MAX_BLUR = 9
@@ -131,6 +133,21 @@ class lmc_myula_config(C.Structure):
     ]
 
 
+class lmc_mch_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("problem", lmc_problem),
+        ("n_channels", C.c_int32),
+        ("mask_channel_stride", C.c_int64),
+        ("n_chains", C.c_int32),
+        ("chain_offset", C.c_int64),
+        ("tau", C.c_float), ("gamma", C.c_float), ("epsg", C.c_float),
+        ("seed", C.c_uint64),
+        ("noise_mode", C.c_int32),
+        ("moments", C.c_int32), ("burn_in", C.c_int32), ("thin", C.c_int32),
+    ]
+
+
 class lmc_ulpda_config(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -199,6 +216,21 @@ _SIGNATURES = {
     "lmc_wavelet_filter": (C.c_int, [C.c_int32, _D, C.POINTER(C.c_int32)]),
     "lmc_wavelet_apply": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "lmc_wavelet_l1_prox": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
+    "lmc_vtv_prox": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float, _F, C.c_int32, C.c_float, C.c_float, _P]),
+    "lmc_vtv_value": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "lmc_vtv_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 4),
+    "lmc_mch_create": (C.c_int, [C.POINTER(lmc_mch_config), C.POINTER(_P)]),
+    "lmc_mch_destroy": (None, [_P]),
+    "lmc_mch_set_state": (C.c_int, [_P, _P, _P]),
+    "lmc_mch_get_state": (C.c_int, [_P, _P, _P]),
+    "lmc_mch_step": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "lmc_mch_iteration": (C.c_int64, [_P]),
+    "lmc_mch_set_iteration": (C.c_int, [_P, C.c_int64]),
+    "lmc_mch_get_moments": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64), _P]),
+    "lmc_mch_reset_moments": (C.c_int, [_P, _P]),
+    "lmc_mch_energies": (C.c_int, [_P, _P, _P, _P]),
+    "lmc_mch_noise": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "lmc_mch_kernel_name": (C.c_char_p, [_P]),
     "lmc_dual_project": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),
     "lmc_prox_elementwise": (C.c_int, [C.c_int32, _P, _P, C.c_int64, _F, C.c_int32, _P]),
     "lmc_myula_create": (C.c_int, [C.POINTER(lmc_myula_config), C.POINTER(_P)]),
@@ -305,6 +337,13 @@ def check_fft_dims(dims):
         if not (FFT_MIN <= n <= FFT_MAX) or n & (n - 1):
             raise ValueError(f"the transforms take sides that are powers of two in {FFT_MIN} .. {FFT_MAX} (got {H} x {W})")
     return H, W
+
+
+def vtv_plan(dims, n_channels, niter):
+    """``(tile_h, tile_w, iters_per_launch, n_launches)`` of the vectorial-TV prox kernel (lmc_vtv_plan; host only, no device needed)."""
+    out = [C.c_int32() for _ in range(4)]
+    check(load().lmc_vtv_plan(int(dims[0]), int(dims[1]), int(n_channels), int(niter), *[C.byref(o) for o in out]))
+    return tuple(o.value for o in out)
 
 
 def exported_symbols():

@@ -18,7 +18,8 @@ import torch
 from numpy.random import default_rng
 
 from . import _capi, _dev
-from .proximal import _Problem
+from .proximal import L2, VectorialTV, _Problem
+from .operators import Convolve2D, Diagonal, Identity
 from .summaries import (ACCUMULATOR_KEYWORDS, HIST_MAX_BINS, MAX_CHAIN_GROUPS, MAX_COV_PROBES, MOMENT_SCALES, CovSketch, GroupMCSE,  # noqa: F401
                         _check_accumulators, _check_chain_groups, _check_cov_sketch, _check_histogram, _check_moment_scales, _cov_summary,
                         _group_summaries, _hist_arrays, _hist_host, _hist_summaries, _host_array, _scale_summaries, block_mean_var,
@@ -119,6 +120,14 @@ def _refuse_radon(data, prior, opts, who=None):
         raise NotImplementedError("the Radon operator runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
     if prior.get("tv_warm") or opts.get("tv_warm"):
         raise NotImplementedError("the Radon operator has no warm-started TV dual: warm / tv_warm must be off")
+
+
+def _refuse_vtv(proxg, who):
+    """``NotImplementedError`` for the vectorial TV prior where ``who`` samples single-plane images (before any handle exists)."""
+    if isinstance(proxg, VectorialTV):
+        raise NotImplementedError(f"{who} does not take VectorialTV: the multi-channel prior is built for MultichannelMYULASampler (and "
+                                  "MoreauYosidaUnadjustedLangevin, which routes to it) only -- MYMALA, SK-ROCK, ULPDA and the estimation of the prior "
+                                  "weight are not built for it")
 
 
 def _data_descriptor(proxf):
@@ -308,6 +317,7 @@ class MYULASampler:
         needs ``moments=True``).
         Every call on the sampler runs on ``device`` whatever the current device is."""
         acc = _check_accumulators(locals(), moments, dims)      # before anything touches the proxes
+        _refuse_vtv(proxg, type(self).__name__)
         if tau is None:
             raise NotImplementedError("tau=None (backtracking) is not implemented by the reference loop either")
         if self._box_refusal is not None:
@@ -872,6 +882,17 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
     the correlation maps and ``.modes(r)`` the leading eigenvalues and eigen-images of the Nystrom approximation of the posterior covariance (exact when its
     rank is at most k, lower bounds otherwise).
     """
+    if isinstance(proxg, VectorialTV):
+        # multi-channel images: the sampler of its own, many-chain form only (n_chains=None: one chain); x0 [nch, H, W] or [nch, C, H, W]
+        asked = {"moment_scales": moment_scales, "hist_bins": hist_bins, "hist_range": hist_range, "chain_groups": chain_groups, "cov_probes": cov_probes,
+                 "cov_center": cov_center, "callback": callback, "diagnostics": diagnostics or None,
+                 "quantiles": None if quantiles is None or tuple(quantiles) == (0.05, 0.5, 0.95) else quantiles,
+                 "show": show or None, "rng='pcg64'": None if rng == "philox" else rng}
+        for name, value in asked.items():
+            if value is not None:
+                raise NotImplementedError(f"{name} is not built for multi-channel images (VectorialTV): the multi-channel sampler keeps the pixel moments "
+                                          "and the energies only")
+        return _multichannel_myula(proxf, proxg, x0, tau, gamma, epsg, niter, seed, n_chains, dims, chain_offset, burn_in, thin, device)
     dims = _dims_of(dims, proxf, proxg)
     many = n_chains is not None
     C_ = int(n_chains) if many else 1
@@ -941,6 +962,210 @@ def MoreauYosidaUnadjustedLangevin(proxf, proxg, x0, tau=None, gamma=.1, epsg=1.
                 print('%6g  %12.5e  %10.3e  %10.3e  %10.3e' % (done, x00, float(f.mean()), float(g.mean()),
                                                               float((f + (epsg if np.asarray(epsg).size == 1 else float(np.sum(epsg))) * g).mean())))
         return _result(smp, quantiles, tstart, tracer)
+
+
+def _multichannel_data(proxf, n_channels, dims):
+    """The per-channel data terms of a multi-channel sampler as one description: ``(data descriptor of channel 0 without y and mask, y [nch, H, W] or None,
+    masks [nch, H, W] or None)``.  Host checks only, before any device call: a sequence of ``n_channels`` :class:`L2` terms with the same operator kind
+    (``Convolve2D``, ``Diagonal``, ``Identity`` or none), the same taps and offset and the same ``sigma``; ``None`` = no data term."""
+    if proxf is None:
+        return {"data_kind": _capi.DATA_NONE}, None, None
+    try:
+        terms = list(proxf)
+    except TypeError:
+        raise ValueError(f"proxf must be a sequence of {n_channels} L2 terms, one per channel (got {type(proxf).__name__})") from None
+    if len(terms) != n_channels:
+        raise ValueError(f"proxf holds {len(terms)} terms for {n_channels} channels: one L2 term per channel")
+    n = int(dims[0]) * int(dims[1])
+    for t in terms:
+        if not isinstance(t, L2):
+            raise NotImplementedError(f"the multi-channel sampler is built for L2 data terms per channel; {type(t).__name__} (Poisson, Huber, ...) is not built")
+        if t.weights is not None or getattr(t, "_spectral", None) is not None:
+            raise ValueError("the multi-channel sampler takes unweighted L2 terms: per-pixel weights are not built per channel")
+        if t.Op is not None and not isinstance(t.Op, (Convolve2D, Diagonal, Identity)):
+            raise NotImplementedError(f"the multi-channel sampler is built for Op = Convolve2D, Diagonal, Identity or None; {type(t.Op).__name__} is not built per channel")
+        if t.b is None:
+            raise ValueError("every channel's L2 term needs its observation b")
+        if np.size(t.b) != n:
+            raise ValueError(f"a channel's b has {np.size(t.b)} entries for an image of shape {tuple(dims)}")
+    kind = lambda t: Identity if t.Op is None else type(t.Op)
+    if any(kind(t) is not kind(terms[0]) for t in terms):
+        raise ValueError("the channels' L2 terms must have the same operator kind (Convolve2D, Diagonal, Identity or none)")
+    if any(float(t.sigma) != float(terms[0].sigma) for t in terms):
+        raise ValueError("the channels' L2 terms must have the same sigma: sigma_f is shared by the channels")
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    y = np.stack([host(t.b).astype(np.float32).reshape(dims) for t in terms])
+    data, masks = {"sigma_f": float(terms[0].sigma)}, None
+    op = terms[0].Op
+    if isinstance(op, Convolve2D):
+        for t in terms[1:]:
+            if np.shape(t.Op.h) != np.shape(op.h) or not np.array_equal(np.asarray(t.Op.h), np.asarray(op.h)) or tuple(t.Op.offset) != tuple(op.offset):
+                raise ValueError("the channels' blurs must have the same taps and offset: the blur is shared by the channels")
+        data.update(data_kind=_capi.DATA_BLUR, h=op.h, offset=op.offset)
+    elif isinstance(op, Diagonal):
+        for t in terms:
+            if np.size(t.Op.d) != n:
+                raise ValueError(f"a channel's mask has {np.size(t.Op.d)} entries for an image of shape {tuple(dims)}")
+        masks = np.stack([host(t.Op.d).astype(np.float32).reshape(dims) for t in terms])
+        data["data_kind"] = _capi.DATA_MASK
+    else:
+        data["data_kind"] = _capi.DATA_IDENTITY
+    return data, y, masks
+
+
+class MultichannelMYULASampler:
+    """Many-chain MYULA on multi-channel images under the vectorial TV prior: owns an ``lmc_mch`` handle (include/lmc_atomi.h).
+
+    ``proxf``: a sequence of ``n_channels`` :class:`L2` terms, one per channel -- each channel has its own ``b`` and, with ``Op = Diagonal``, its own mask (a
+    Bayer mosaic); the operator kind (``Convolve2D``, ``Diagonal``, ``Identity`` or none), the taps and offset and ``sigma`` are shared (a mismatch, or
+    weights: ``ValueError``; any other term: ``NotImplementedError``).  ``proxg``: a :class:`VectorialTV` of that many channels.
+    State in HBM: ``[n_channels, n_chains, H, W]`` fp32, channel-major.  Channel ``ch`` draws the Philox field of the seed ``(seed + (ch << 32)) mod 2^64``:
+    channel 0 is the field of :class:`MYULASampler` with the same seed, and any sharding of the chains reproduces the same trajectories.
+    One iteration: the coupled prox over all chains and channels, then per channel the fused step kernel with that prox as a ready-made one."""
+
+    def __init__(self, proxf, proxg, dims, n_chains=1, tau=None, gamma=0.1, epsg=1.0, seed=0, chain_offset=0, noise="philox", moments=False,
+                 burn_in=0, thin=1, device=None, variant=None):
+        if not isinstance(proxg, VectorialTV):
+            raise NotImplementedError(f"MultichannelMYULASampler is built for proxg = VectorialTV (got {type(proxg).__name__}); single-plane priors run in MYULASampler")
+        if tau is None:
+            raise NotImplementedError("tau=None (backtracking) is not implemented by the reference loop either")
+        if np.asarray(epsg).size > 1:
+            raise NotImplementedError("array-valued epsg is built for the closed-form priors only: VectorialTV takes a scalar epsg")
+        self.dims = (int(dims[0]), int(dims[1]))
+        if self.dims != proxg.dims:
+            raise ValueError(f"dims {self.dims} differ from the prior's {proxg.dims}")
+        self.n_channels = proxg.n_channels
+        data, y, masks = _multichannel_data(proxf, self.n_channels, self.dims)
+        if noise not in ("philox", "injected", "none"):
+            raise ValueError("noise must be 'philox', 'injected' or 'none'")
+        self.n_chains = int(n_chains)
+        self.device = _dev.device(device)
+        self.proxf, self.proxg = proxf, proxg
+        self._problem = _Problem(self.dims, data, proxg.prior_descriptor(), self.device, options={"step_variant": variant or 0, "multichannel": True})
+        cfg = _capi.lmc_mch_config()
+        cfg.struct_size = C.sizeof(_capi.lmc_mch_config)
+        cfg.problem = self._problem.c
+        self._y = self._masks = None
+        if y is not None:
+            self._y = _dev.to_dev(y, self.device)
+            cfg.problem.y_dev = self._y.data_ptr()
+        shared = masks is not None and all(np.array_equal(masks[0], m) for m in masks[1:])
+        if masks is not None:
+            self._masks = _dev.to_dev(masks[0] if shared else masks, self.device)
+            cfg.problem.mask_dev = self._masks.data_ptr()
+            cfg.mask_channel_stride = 0 if shared else self.dims[0] * self.dims[1]
+        cfg.n_channels = self.n_channels
+        cfg.n_chains = self.n_chains
+        cfg.chain_offset = int(chain_offset)
+        cfg.tau, cfg.gamma, cfg.epsg = float(tau), float(gamma), float(epsg)
+        cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        cfg.noise_mode = {"philox": _capi.NOISE_PHILOX, "injected": _capi.NOISE_INJECTED, "none": _capi.NOISE_NONE}[noise]
+        cfg.moments = 1 if moments else 0
+        cfg.burn_in = int(burn_in)
+        cfg.thin = int(thin)
+        self.noise_mode = noise
+        self.moments_on = bool(moments)
+        self._h = C.c_void_p()
+        torch.cuda.current_stream(self.device).synchronize()      # y and the masks are on the device before the handle reads them
+        with torch.cuda.device(self.device):
+            _capi.check(_dev.lib().lmc_mch_create(C.byref(cfg), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _dev.lib().lmc_mch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def shape(self):
+        return (self.n_channels, self.n_chains) + self.dims
+
+    def set_state(self, x):
+        """``x``: ``[n_channels, H, W]`` (broadcast to every chain) or ``[n_channels, n_chains, H, W]``."""
+        xt = _dev.to_dev(x, self.device)
+        n = self.dims[0] * self.dims[1]
+        if xt.numel() == self.n_channels * n:
+            xt = xt.reshape(self.n_channels, 1, *self.dims).expand(self.shape).contiguous()
+        if xt.numel() != self.n_channels * self.n_chains * n:
+            raise ValueError(f"state of shape {tuple(xt.shape)} does not match {self.shape}")
+        _capi.check(_dev.lib().lmc_mch_set_state(self._h, _dev.ptr(xt), _dev.stream_ptr(self.device)))
+        torch.cuda.current_stream(self.device).synchronize()  # xt may be a temporary
+
+    def get_state(self, out=None):
+        if out is None:
+            out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        _capi.check(_dev.lib().lmc_mch_get_state(self._h, _dev.ptr(out), _dev.stream_ptr(self.device)))
+        return out
+
+    @property
+    def iteration(self):
+        return int(_dev.lib().lmc_mch_iteration(self._h))
+
+    @iteration.setter
+    def iteration(self, it):
+        _capi.check(_dev.lib().lmc_mch_set_iteration(self._h, int(it)))
+
+    def step(self, n_iters=1, noise=None):
+        """Run ``n_iters`` iterations on every chain and channel.  ``noise`` (only with noise='injected'): ``[n_iters, n_channels, n_chains, H, W]``."""
+        nt = None
+        if noise is not None:
+            nt = _dev.to_dev(noise, self.device)
+            if nt.numel() != n_iters * int(np.prod(self.shape)):
+                raise ValueError("noise must have shape [n_iters, n_channels, n_chains, H, W]")
+        _capi.check(_dev.lib().lmc_mch_step(self._h, int(n_iters), _dev.ptr(nt), _dev.stream_ptr(self.device)))
+        if nt is not None:
+            torch.cuda.current_stream(self.device).synchronize()
+
+    @property
+    def kernel_name(self):
+        return _dev.lib().lmc_mch_kernel_name(self._h).decode()
+
+    def energies(self):
+        """Per-chain ``f(x_c) = sum_ch f_ch`` and ``g(x_c) = sigma VTV(x_c)`` (float64 tensors in HBM)."""
+        f = torch.empty(self.n_chains, dtype=torch.float64, device=self.device)
+        g = torch.empty(self.n_chains, dtype=torch.float64, device=self.device)
+        _capi.check(_dev.lib().lmc_mch_energies(self._h, _dev.ptr(f), _dev.ptr(g), _dev.stream_ptr(self.device)))
+        return f, g
+
+    def noise_field(self, iteration):
+        out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        _capi.check(_dev.lib().lmc_mch_noise(self._h, int(iteration), _dev.ptr(out), _dev.stream_ptr(self.device)))
+        return out
+
+    def moments(self):
+        """(sum [nch, H, W] f64, sumsq [nch, H, W] f64, count) over chains and kept iterations."""
+        a = torch.empty((self.n_channels,) + self.dims, dtype=torch.float64, device=self.device)
+        b = torch.empty_like(a)
+        cnt = C.c_uint64()
+        _capi.check(_dev.lib().lmc_mch_get_moments(self._h, _dev.ptr(a), _dev.ptr(b), C.byref(cnt), _dev.stream_ptr(self.device)))
+        return a, b, int(cnt.value)
+
+    def reset_moments(self):
+        _capi.check(_dev.lib().lmc_mch_reset_moments(self._h, _dev.stream_ptr(self.device)))
+
+
+def _multichannel_myula(proxf, proxg, x0, tau, gamma, epsg, niter, seed, n_chains, dims, chain_offset, burn_in, thin, device):
+    """The many-chain form of :func:`MoreauYosidaUnadjustedLangevin` under a :class:`VectorialTV` prior: ``mean`` / ``var`` ``[nch, H, W]``, ``state``
+    ``[nch, C, H, W]``."""
+    smp = MultichannelMYULASampler(proxf, proxg, dims if dims is not None else proxg.dims, n_chains=1 if n_chains is None else int(n_chains), tau=tau,
+                                   gamma=gamma, epsg=epsg, seed=seed, chain_offset=chain_offset, moments=True, burn_in=burn_in, thin=thin, device=device)
+    with smp:
+        smp.set_state(x0)
+        tstart = time.time()
+        smp.step(niter)
+        s1, s2, cnt = smp.moments()
+        f, g = smp.energies()
+        state = smp.get_state()
+        torch.cuda.current_stream(smp.device).synchronize()
+        mean, var = mean_var_from_moments(s1, s2, max(cnt, 1))
+        return MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart)
 
 
 class MYMALASampler(MYULASampler):
@@ -1068,6 +1293,7 @@ def EstimatePriorWeight(proxf, proxg, x0, tau, gamma, n_updates, theta_bounds, t
     if sampler not in ("myula", "skrock"):
         raise NotImplementedError(f"sampler {sampler!r}: the weight is estimated with 'myula' or 'skrock' (MYMALA caches its Metropolis energy, "
                                   "ULPDA has no setter)")
+    _refuse_vtv(proxg, "EstimatePriorWeight")
     dims = _dims_of(dims, proxf, proxg)
     prior = _prior_descriptor(proxg)
     _refuse_box(prior, "EstimatePriorWeight", "the d / k homogeneity argument of the estimator does not hold on a bounded set")

@@ -406,6 +406,69 @@ int lmc_wavelet_l1_prox(const float* x_dev, float* out_dev, int64_t n_img, int32
   return LMC_OK;
 }
 
+// the argument checks the two stateless vectorial-TV calls share
+static int check_vtv_call(const void* x_dev, const void* out_dev, int64_t n_img, int32_t n_channels, int64_t channel_stride, int32_t H, int32_t W) {
+  if (!x_dev || !out_dev || x_dev == out_dev) return fail(LMC_E_INVALID, "bad pointers (in-place not allowed)");
+  if (n_img < 1 || n_img > (1 << 24) || H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30)
+    return fail(LMC_E_INVALID, "bad shape n_img=%lld H=%d W=%d", (long long)n_img, H, W);
+  if (n_channels < 1 || n_channels > LMC_MAX_CHANNELS) return fail(LMC_E_INVALID, "n_channels %d outside 1..%d", n_channels, LMC_MAX_CHANNELS);
+  if (n_channels > 1 && channel_stride < n_img * (int64_t)H * W)
+    return fail(LMC_E_INVALID, "channel_stride %lld is below n_img * H * W = %lld: the channels would overlap", (long long)channel_stride, (long long)(n_img * (int64_t)H * W));
+  return LMC_OK;
+}
+
+int lmc_vtv_prox(const float* x_dev, float* out_dev, int64_t n_img, int32_t n_channels, int64_t channel_stride, int32_t H, int32_t W, float t_sigma,
+                 int32_t niter, float step, const float* betas_host, int32_t box_enable, float box_lo, float box_hi, void* stream) {
+  int rc = check_vtv_call(x_dev, out_dev, n_img, n_channels, channel_stride, H, W);
+  if (rc) return rc;
+  if (niter < 1 || niter > lmc::kMaxTvIters) return fail(LMC_E_INVALID, "niter %d outside 1..%d", niter, lmc::kMaxTvIters);
+  if (!(t_sigma >= 0.f)) return fail(LMC_E_INVALID, "t_sigma must be >= 0 (got %g)", (double)t_sigma);
+  if (!(step >= 0.f)) return fail(LMC_E_INVALID, "step must be >= 0 (0: the default 1/8)");
+  if (box_enable) {
+    if (box_enable != 1) return fail(LMC_E_INVALID, "box_enable must be 0 or 1 (got %d)", box_enable);
+    if (!(box_lo == box_lo) || !(box_hi == box_hi)) return fail(LMC_E_INVALID, "box: a bound is NaN");
+    if (!(box_lo < box_hi)) return fail(LMC_E_INVALID, "box: needs box_lo < box_hi (got [%g, %g])", (double)box_lo, (double)box_hi);
+  }
+  const size_t plane = sizeof(float) * (size_t)n_img * H * W;
+  if (t_sigma == 0.f) {      // the prox of the zero function
+    for (int ch = 0; ch < n_channels; ++ch)
+      HIP_TRY(hipMemcpyAsync(out_dev + (size_t)ch * channel_stride, x_dev + (size_t)ch * channel_stride, plane, hipMemcpyDeviceToDevice, S(stream)));
+    return LMC_OK;
+  }
+  float betas[lmc::kMaxTvIters];
+  if (betas_host) std::memcpy(betas, betas_host, sizeof(float) * niter);
+  else default_betas(betas, niter);
+  Workspace& sc = scratch_here();
+  const size_t ns = lmc::vtv_state_floats(n_img, n_channels, H, W, niter);
+  HIP_TRY(sc.state[0].need(ns));
+  HIP_TRY(sc.state[1].need(ns));
+  HIP_TRY(lmc::launch_vtv_prox(x_dev, out_dev, n_img, n_channels, channel_stride, H, W, t_sigma, step > 0.f ? step : 0.125f, betas, niter, box_enable, box_lo,
+                               box_hi, sc.state[0].p, sc.state[1].p, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_vtv_value(const float* x_dev, double* out_dev, int64_t n_img, int32_t n_channels, int64_t channel_stride, int32_t H, int32_t W, void* stream) {
+  int rc = check_vtv_call(x_dev, out_dev, n_img, n_channels, channel_stride, H, W);
+  if (rc) return rc;
+  Workspace& sc = scratch_here();
+  HIP_TRY(sc.vtv_part.need(lmc::vtv_value_partials(n_img, H, W)));
+  HIP_TRY(lmc::launch_vtv_value(x_dev, n_img, n_channels, channel_stride, H, W, 1.0, sc.vtv_part.p, out_dev, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_vtv_plan(int32_t H, int32_t W, int32_t n_channels, int32_t niter, int32_t* tile_h, int32_t* tile_w, int32_t* iters_per_launch, int32_t* n_launches) {
+  if (H < 1 || W < 1) return fail(LMC_E_INVALID, "bad image size %dx%d", H, W);
+  if (n_channels < 1 || n_channels > LMC_MAX_CHANNELS) return fail(LMC_E_INVALID, "n_channels %d outside 1..%d", n_channels, LMC_MAX_CHANNELS);
+  if (niter < 1 || niter > lmc::kMaxTvIters) return fail(LMC_E_INVALID, "niter %d outside 1..%d", niter, lmc::kMaxTvIters);
+  lmc::VtvPlan pl;
+  if (!lmc::vtv_plan(n_channels, niter, pl)) return fail(LMC_E_INVALID, "no plan");
+  if (tile_h) *tile_h = pl.TH;
+  if (tile_w) *tile_w = pl.TW;
+  if (iters_per_launch) *iters_per_launch = pl.iters;
+  if (n_launches) *n_launches = pl.n_launches;
+  return LMC_OK;
+}
+
 int lmc_chain_probes(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t ph, int32_t pw, void* stream) {
   if (!x_dev || !out_dev || n_img < 1 || H < 1 || W < 1) return fail(LMC_E_INVALID, "bad arguments");
   if (ph < 1 || pw < 1 || ph > H || pw > W) return fail(LMC_E_INVALID, "probe grid %dx%d does not fit a %dx%d image", ph, pw, H, W);

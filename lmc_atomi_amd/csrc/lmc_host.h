@@ -5,6 +5,7 @@
 //   lmc_solve.hip       the implicit step (I + ts H^T H) u = rhs: Chebyshev, CG
 //   lmc_tv_exit.hip     the early exits of the TV prox, the ME-TV inner prox and envelope, the energies of a problem
 //   lmc_sampler.hip     the MYULA, MYMALA, SK-ROCK and ULPDA samplers: create / destroy, state, the step loops
+//   lmc_mch.hip         the multi-channel MYULA sampler under the vectorial TV prior (lmc_mch_*): a handle type of its own
 //   lmc_sapg.hip        the SAPG estimation of the prior weight: its kernels, its stateless calls and lmc_sampler_sapg
 //   lmc_accum.hip       the accumulators over the kept samples (lmc_accum.h): their reductions and their set / get / reset entry points
 //   lmc_rccl.hip        the dlopen'd RCCL and the all-reduces of the accumulators
@@ -156,6 +157,7 @@ struct Workspace {
   Buf<float> resid;                       // large PSF: the residual rho(H x) of a step, [n][H][W]; Radon operator: rho(A x), [n][n_angles][n_det]
   Buf<float> wav;                         // wavelet prior: the thresholded pyramid and the LL ping-pong (1.25 states)
   Buf<double> wav_part;                   // wavelet prior: the partial sums of its value
+  Buf<double> vtv_part;                   // vectorial TV: the partial sums of its value (its chained prox carries the dual through state[])
   // large PSF: the device tap table, the pinned host copy it was uploaded from (compared with the next table: equal taps are not uploaded again)
   // and the event behind the last upload (the host copy is not rewritten before that upload has run)
   float* psf_tab = nullptr;
@@ -191,7 +193,7 @@ struct Workspace {
   void release_wavelet() { wav.release(); wav_part.release(); }
   void release() {
     for (Buf<float>* b : {&state[0], &state[1], &extra, &prox, &rtmp, &resid, &wav, &fft_spec}) b->release();
-    for (Buf<double>* b : {&dbl, &wav_part, &fft_part}) b->release();
+    for (Buf<double>* b : {&dbl, &wav_part, &vtv_part, &fft_part}) b->release();
     if (psf_tab) (void)hipFree(psf_tab);
     if (psf_host) (void)hipHostFree(psf_host);
     if (psf_ev) (void)hipEventDestroy(psf_ev);

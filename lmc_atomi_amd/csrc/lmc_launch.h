@@ -271,6 +271,29 @@ hipError_t launch_wavelet_apply(const float* x, float* out, int64_t n_img, int H
 }  // namespace lmc
 
 namespace lmc {
+// Vectorial TV (lmc_vtv.hip): the prox and the value of LMC_PRIOR_VTV on channel-major multi-channel images, image (ch, n) at x + ch * cs + n * H * W.
+constexpr int kVtvMaxChannels = LMC_MAX_CHANNELS;
+// The launch plan of a prox of niter dual iterations on nch channels: a workgroup owns a PH x PW patch = a TH x TW tile plus a halo of HL pixels, which
+// covers the `iters` dual iterations of one launch; n_launches launches are chained through the dual state.  Host only.
+struct VtvPlan {
+  int PH, PW, HL, TH, TW;
+  int iters, n_launches;
+  size_t lds_bytes;           // dynamic LDS of one workgroup
+};
+bool vtv_plan(int nch, int niter, VtvPlan& out);       // false: nch outside 1 .. kVtvMaxChannels or niter outside 1 .. kMaxTvIters
+// floats each of the two state buffers of a chained prox holds ([n_img][nch][4][H][W]); 0 when one launch covers niter
+size_t vtv_state_floats(int64_t n_img, int nch, int H, int W, int niter);
+// out = prox of gamma * VTV at x (gamma = t sigma > 0), niter dual iterations of step `step` / gamma with the momentum table betas[niter] (host); box != 0:
+// the constrained form on [box_lo, box_hi].  x != out, both with channel stride cs.  state0 / state1: vtv_state_floats each (may be NULL when that is 0).
+hipError_t launch_vtv_prox(const float* x, float* out, int64_t n_img, int nch, int64_t cs, int H, int W, float gamma, float step, const float* betas, int niter,
+                           int box, float box_lo, float box_hi, float* state0, float* state1, hipStream_t st);
+// doubles `part` must hold for launch_vtv_value
+size_t vtv_value_partials(int64_t n_img, int H, int W);
+// val[n] = scale * VTV(x_n), float64 by partial sums in a fixed order
+hipError_t launch_vtv_value(const float* x, int64_t n_img, int nch, int64_t cs, int H, int W, double scale, double* part, double* val, hipStream_t st);
+}  // namespace lmc
+
+namespace lmc {
 // The spectral data term (lmc_fft.hip, lmc_fft_kernel.h): the batched 2-D real FFT in LDS of LMC_DATA_SPECTRAL, lmc_rfft2 / lmc_irfft2 and
 // lmc_spectral_filter; power-of-two sides kFftMin .. kFftMax, the half plane of W / 2 + 1 columns, norm = "ortho".
 constexpr int kFftMin = 8, kFftMax = 1024;

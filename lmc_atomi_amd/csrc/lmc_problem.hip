@@ -165,6 +165,9 @@ int load_problem(const lmc_problem* p, Problem& q) {
       if (p->tv_betas_host) std::memcpy(q.betas, p->tv_betas_host, sizeof(float) * p->tv_niter);
       else default_betas(q.betas, p->tv_niter);
       break;
+    case LMC_PRIOR_VTV:
+      return fail(LMC_E_UNSUPPORTED, "LMC_PRIOR_VTV (vectorial TV) acts on a multi-channel image: it is built for lmc_mch_create, lmc_vtv_prox and lmc_vtv_value only; "
+                  "this entry point takes single-plane images");
     default: return fail(LMC_E_INVALID, "unknown prior_kind %d", p->prior_kind);
   }
   if (p->prior_kind != LMC_PRIOR_NONE && p->prior_kind != LMC_PRIOR_EPROX && !(p->prior_sigma >= 0.f)) return fail(LMC_E_INVALID, "prior_sigma must be >= 0");

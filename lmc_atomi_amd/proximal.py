@@ -112,6 +112,10 @@ class _Problem:
     every buffer it points to alive."""
 
     def __init__(self, dims, data=None, prior=None, dev=None, options=None):
+        if (prior or {}).get("prior_kind") == _capi.PRIOR_VTV and not (options or {}).get("multichannel"):
+            raise NotImplementedError("VectorialTV acts on multi-channel images: it is built for MultichannelMYULASampler / MoreauYosidaUnadjustedLangevin and "
+                                      "for its own prox and value only; MYMALA, SK-ROCK, ULPDA, the estimation of the prior weight and the single-plane "
+                                      "MYULASampler are not built for it")
         self.dims = (int(dims[0]), int(dims[1]))
         self.device = _dev.device(dev)
         dev = self.device
@@ -158,7 +162,7 @@ class _Problem:
         p.prior_kind = prior["prior_kind"]
         p.prior_sigma = float(prior.get("prior_sigma", 0.0))
         # (ULPDA's anisotropic descriptor carries no prox: tv_niter stays 0)
-        if p.prior_kind == _capi.PRIOR_TV_ISO or (p.prior_kind == _capi.PRIOR_TV_ANISO and prior.get("tv_niter") is not None):
+        if p.prior_kind in (_capi.PRIOR_TV_ISO, _capi.PRIOR_VTV) or (p.prior_kind == _capi.PRIOR_TV_ANISO and prior.get("tv_niter") is not None):
             p.tv_niter = int(prior["tv_niter"])
             p.tv_step = float(prior.get("tv_step", 0.125))
             b = np.ascontiguousarray(prior["tv_betas"], dtype=np.float32)
@@ -970,6 +974,73 @@ class WaveletL1(ProxOperator):
         else:
             _dev.run(xt, "lmc_wavelet_l1_prox", _dev.ptr(xt), _dev.ptr(out), xt.numel() // n, self.dims[0], self.dims[1], self.p, self.levels,
                                                        self.sigma * float(tau))
+        return _dev.like_input(out, x)
+
+
+class VectorialTV(ProxOperator):
+    """``sigma * VTV(x)`` on a multi-channel image ``x[ch, H, W]``: ``VTV(x) = sum_pixels sqrt(sum_ch (d_r x_ch)^2 + (d_c x_ch)^2)``, ONE gradient norm per
+    pixel over all channels (Blomgren-Chan / Bresson-Chan; build-specified, ``LMC_PRIOR_VTV`` in include/lmc_atomi.h is its definition).  The channels of an
+    RGB photograph, a Bayer mosaic, a dual-energy CT pair share their edges; this prior says so, and running the channels as unrelated grey problems
+    under :class:`TV` samples another posterior.  ``prox`` is ``niter`` (1 .. 64) fast-gradient-projection dual iterations from the zero dual with the
+    projection weight shared by the channels of a pixel; ``n_channels=1`` is :class:`TV`.  ``bounds=(lo, hi)``: the constrained form, as ``TV(bounds=...)``.
+
+    ``prox(x, tau)`` and ``__call__(x)`` take ``[nch, H, W]``, a batch ``[nch, n, H, W]`` (channel-major: each channel's images contiguous) or a flat array of
+    one of those sizes; ``prox`` returns the shape it was given, ``__call__`` one value per multi-channel image.  As ``proxg`` of
+    :class:`MultichannelMYULASampler` and of :func:`MoreauYosidaUnadjustedLangevin` (which routes to it); every other sampler raises
+    ``NotImplementedError``."""
+
+    def __init__(self, dims, n_channels, sigma=1.0, niter=10, step=0.125, momentum="unlocbox", bounds=None):
+        super().__init__(None, False)
+        self.dims = (int(dims[0]), int(dims[1]))
+        if self.dims[0] < 1 or self.dims[1] < 1:
+            raise ValueError(f"dims must be a pair of positive sizes (got {dims!r})")
+        self.n_channels = int(n_channels)
+        if not 1 <= self.n_channels <= _capi.MAX_CHANNELS:
+            raise ValueError(f"n_channels must be in 1 .. {_capi.MAX_CHANNELS} (got {n_channels})")
+        self.niter = int(niter)
+        if not 1 <= self.niter <= _capi.MAX_TV_ITERS:
+            raise ValueError(f"niter must be in 1 .. {_capi.MAX_TV_ITERS} (got {niter})")
+        self.bounds = check_bounds(bounds)
+        self.sigma = float(sigma)
+        if not self.sigma >= 0.0:
+            raise ValueError(f"sigma must be >= 0 (got {sigma})")
+        self.step = float(step)
+        if not self.step > 0.0:
+            raise ValueError(f"step must be > 0 (got {step})")
+        self.momentum = momentum
+        self._betas = fgp_betas(self.niter, momentum)
+
+    def prior_descriptor(self):
+        return _with_box({"prior_kind": _capi.PRIOR_VTV, "prior_sigma": self.sigma, "tv_niter": self.niter, "tv_step": self.step, "tv_betas": self._betas,
+                          "n_channels": self.n_channels}, self.bounds)
+
+    def _batch(self, x):
+        """The number of multi-channel images in ``x``; ``ValueError`` for a shape that is none of ``[nch, H, W]``, ``[nch, n, H, W]`` or flat of those sizes."""
+        shape = tuple(x.shape) if isinstance(x, torch.Tensor) else tuple(np.shape(x))
+        one = self.n_channels * self.dims[0] * self.dims[1]
+        size = int(np.prod(shape)) if shape else 1
+        ok = (len(shape) == 1 and size and size % one == 0) or shape == (self.n_channels,) + self.dims or \
+             (len(shape) == 4 and shape[0] == self.n_channels and shape[1] >= 1 and shape[2:] == self.dims)
+        if not ok:
+            raise ValueError(f"operand of shape {shape} is neither [{self.n_channels}, {self.dims[0]}, {self.dims[1]}], nor a batch [{self.n_channels}, n, "
+                             f"{self.dims[0]}, {self.dims[1]}], nor flat of one of those sizes")
+        return size // one
+
+    def __call__(self, x):
+        n = self._batch(x)
+        xt = _dev.to_dev(x)
+        g = torch.empty(n, dtype=torch.float64, device=xt.device)
+        _dev.run(xt, "lmc_vtv_value", _dev.ptr(xt), _dev.ptr(g), n, self.n_channels, n * self.dims[0] * self.dims[1], self.dims[0], self.dims[1])
+        g = g * self.sigma
+        return float(g[0]) if n == 1 else (g if isinstance(x, torch.Tensor) else g.cpu().numpy())
+
+    def prox(self, x, tau):
+        n = self._batch(x)
+        xt = _dev.to_dev(x)
+        out = torch.empty_like(xt)
+        lo, hi = self.bounds if self.bounds is not None else (0.0, 0.0)
+        _dev.run(xt, "lmc_vtv_prox", _dev.ptr(xt), _dev.ptr(out), n, self.n_channels, n * self.dims[0] * self.dims[1], self.dims[0], self.dims[1],
+                 self.sigma * float(tau), self.niter, self.step, _dev.fptr(self._betas), 1 if self.bounds is not None else 0, lo, hi)
         return _dev.like_input(out, x)
 
 
