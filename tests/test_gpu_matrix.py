@@ -2,7 +2,9 @@
 7 taps, identity, mask), priors (TV fixed count and with upstream's early exit, l2, l1, Haar-l1, a closed form of prox.py) and the non-log-concave terms
 of L2_ncvx_tv (MC-TV, ME-TV with its rtol) -- each run for three MYULA iterations on three chains with injected noise against the CPU checker's
 class-based loop.  The single-feature suites test each kernel in depth; this one looks for holes BETWEEN features (round 3 found one by running the driver
-end to end: the ULPDA sampler without the early-exit state of the ME-TV prox)."""
+end to end: the ULPDA sampler without the early-exit state of the ME-TV prox).
+The data kinds, priors and samplers added since (Poisson, weighted, Huber, large PSF, spectral, Radon; anisotropic TV, wavelets, the box; SK-ROCK) are crossed
+per pixel by the lattice: tests/_lattice.py, tests/test_gpu_lattice.py."""
 import itertools
 
 import numpy as np
