@@ -275,7 +275,43 @@ typedef enum lmc_prior_kind {
    * float64 partial sums in a fixed order.  No atomics: equal runs give equal bits.
    * Valid in lmc_mch_* and lmc_vtv_* only; every other entry point that takes an lmc_problem: LMC_E_UNSUPPORTED with the reason in lmc_last_error
    * (lmc_prior_statistic and lmc_sapg_dimension, which read the kinds with a single-plane value alone, keep their range check: LMC_E_INVALID). */
-  LMC_PRIOR_VTV = 8
+  LMC_PRIOR_VTV = 8,
+  /* Total generalised variation of order two (Bredies, Kunisch and Pock 2010; appended; LMC_ATOMI_ABI_VERSION stays 4 and sizeof(lmc_problem) 200).
+   * Build-specified (the reference has first-order TV only); this text is its definition.
+   * Operators.  grad: the forward differences of lmc_gradient, zero in the last row / column; div: their negative adjoint.  For a field w = (w1, w2):
+   *   E w = (e11, e22, e12) with (e11, a) = grad w1, (b, e22) = grad w2, e12 = (a + b) / 2 -- the symmetrised derivative;
+   *   |e|_F = sqrt(e11^2 + e22^2 + 2 e12^2), the Frobenius norm of the symmetric 2 x 2 matrix;
+   *   div2 q = (div(q11, q12), div(q12, q22)), so that <E w, q>_F = -<w, div2 q>.
+   * The prior:
+   *   g(x) = sigma * min_w ( sum_pixels |grad x - w|_2 + alpha0 * sum_pixels |E w|_F )
+   * An affine ramp costs nothing (w = grad x, E w = 0) where TV charges its full variation: no staircase in the samples.
+   * The prox at parameter t: lam1 = t sigma, lam0 = alpha0 lam1.  prox_{t g}(v) is niter Chambolle-Pock iterations on the saddle-point problem
+   * min_{u, w} max_{|p| <= lam1, |q|_F <= lam0} 1/2 |u - v|^2 + <grad u - w, p> + <E w, q>, from u = ub = v and w = wb = p = q = 0, with ONE step s
+   * for both sides:
+   *   p  <- P_lam1( p + s (grad ub - wb) )           P_lam(z) = z / max(1, |z| / lam) per pixel; for q the norm is |.|_F above
+   *   q  <- P_lam0( q + s E wb )
+   *   u' = clip( (u + s div p + s v) / (1 + s) )     clip only with a box: the exact prox of 1/2 |. - v|^2 + the indicator (clipping after the loop
+   *                                                  gives a different point)
+   *   w' = w + s (p + div2 q)
+   *   ub = 2 u' - u,  wb = 2 w' - w,  (u, w) = (u', w')
+   *   return u
+   * s defaults to 1 / sqrt(12): ||K||^2 < 12 for K = [[grad, -I], [0, E]] (power iteration on 64 x 64 gives 11.34); a step with 12 s^2 > 1 (beyond
+   * float32 rounding of the default) is LMC_E_INVALID.  The count is fixed and the result is the TRUNCATED iterate, as LMC_PRIOR_TV_ISO's is: the
+   * iteration converges sublinearly (on a 32 x 48 two-facet affine image with noise of sd 10 at lam1 = 5 the distance to the converged prox relative to
+   * |prox - v| is 0.14, 0.085, 0.048, 0.032, 0.021 after 10, 20, 40, 80, 160 iterations).
+   * Fields, read from slots the kind does not otherwise use (the struct has no hole left):  prior_sigma = sigma;  tv_niter = niter, 1 .. LMC_MAX_TGV_ITERS;
+   * eprox_p0 = alpha0, finite and > 0;  tv_step = s, 0 selects the default;  box_* as for LMC_PRIOR_TV_ISO.  Anything else: LMC_E_INVALID.
+   * Kernel (lmc_tgv.hip): tgv_prox_kernel -- a workgroup owns a 64 x 64 patch (tile + halo) of one image, a lane v, u, w, p, q of its four pixels in
+   * registers; the fields neighbours read (ub, wb at +1; p, q at -1) live in LDS, eight planes.  lmc_tgv_launch_iters() iterations are ONE launch (its halo);
+   * more are chained launches that carry (u, ub, w, wb, p, q), 11 planes, through two work buffers exactly.  Two barriers per iteration, no atomics:
+   * equal runs give equal bits.  The prox goes to a buffer that the step kernel of the same problem WITHOUT a prior consumes as a ready-made prox (the
+   * route of LMC_PRIOR_WAVELET_L1), so every data term -- blur, mask, Poisson, weighted, Huber, large PSF, spectral, Radon -- and the box take it.
+   * Honoured by lmc_myula_create, lmc_skrock_create (not with a box, as every prior) and lmc_fused_eval.  lmc_energies and lmc_sampler_energies report
+   * g = 0 (the LMC_PRIOR_EPROX precedent): the value is a minimisation over w and is not built.  LMC_E_UNSUPPORTED, with the reason in lmc_last_error:
+   * lmc_mymala_create, lmc_ulpda_create, lmc_mch_create, lmc_sampler_sapg, lmc_sampler_set_prior_sigma, lmc_prior_statistic, lmc_sapg_dimension (all
+   * need the value or a dual form); prox_scale, tv_rtol > 0, tv_warm, tv_lagged_output.  iterations_per_launch is ignored.  Not built: the value, a dual
+   * carried across sampler iterations, a prox fused into the step kernel, TGV of higher order, vectorial TGV. */
+  LMC_PRIOR_TGV = 9
 } lmc_prior_kind;
 
 typedef enum lmc_ncvx_kind {
@@ -308,6 +344,7 @@ typedef enum lmc_noise_mode {
 #define LMC_MAX_RADON_DET 4096     /* ... detector bins */
 #define LMC_MAX_RADON_SIDE 1048576 /* ... image rows, image columns */
 #define LMC_MAX_CHANNELS 4         /* LMC_PRIOR_VTV: channels of a multi-channel image */
+#define LMC_MAX_TGV_ITERS 256      /* LMC_PRIOR_TGV: primal-dual iterations of the prox */
 
 /* Geometry + potential U(x) = f(x) + eps*g(x).  Plain data; copied by the callee. */
 typedef struct lmc_problem {
@@ -530,6 +567,17 @@ int lmc_vtv_prox(const float* x_dev, float* out_dev, int64_t n_img, int32_t n_ch
                  int32_t niter, float step, const float* betas_host, int32_t box_enable, float box_lo, float box_hi, void* stream);
 int lmc_vtv_value(const float* x_dev, double* out_dev, int64_t n_img, int32_t n_channels, int64_t channel_stride, int32_t H, int32_t W, void* stream);
 int lmc_vtv_plan(int32_t H, int32_t W, int32_t n_channels, int32_t niter, int32_t* tile_h, int32_t* tile_w, int32_t* iters_per_launch, int32_t* n_launches);
+
+/* The prox of LMC_PRIOR_TGV (its text above is the definition) on n_img single-plane images [n][H][W].
+ * lmc_tgv_prox: out = prox_{t g}(x) with t_sigma = t sigma, niter iterations (1 .. LMC_MAX_TGV_ITERS) of step `step` (0 -> 1 / sqrt(12); 12 step^2 > 1:
+ * LMC_E_INVALID); alpha0 finite and > 0; w_out_dev: NULL, or [n][2][H][W] floats that receive the auxiliary field w (row component first); box_enable
+ * != 0: the constrained form on [box_lo, box_hi] (box_lo < box_hi, neither NaN, infinite ends allowed; else LMC_E_INVALID).  Not in place.  t_sigma = 0
+ * is the prox of the indicator alone (out = x, or its clamp; w = 0); negative or NaN: LMC_E_INVALID.  The two 11-plane state buffers of a chained
+ * prox (niter > lmc_tgv_launch_iters()) come from the workspace of the stateless calls.
+ * lmc_tgv_launch_iters: host only.  The iterations one launch of tgv_prox_kernel holds; a prox of more is ceil(niter / that) chained launches. */
+int lmc_tgv_prox(const float* x_dev, float* out_dev, float* w_out_dev, int64_t n_img, int32_t H, int32_t W, float t_sigma, float alpha0, int32_t niter,
+                 float step, int32_t box_enable, float box_lo, float box_hi, void* stream);
+int lmc_tgv_launch_iters(void);
 
 /* Chain probes for convergence diagnostics across chains (split R-hat / effective sample size; SURVEY 8(f).3 -- absent in the
  * reference, whose only diagnostics are the per-iterate scalars of prox_lmc_deconv.py:128-133): every image is reduced to a

@@ -6,7 +6,7 @@ from . import _capi
 from ._capi import LMCError
 from .operators import PSF, Convolve2D, Diagonal, FourierSampling, Gradient, Identity, LinearOperator, PeriodicConvolve2D, Radon, Wavelet2D, irfft2, rfft2
 from .proximal import (L1, L2, L21, TV, L2_ncvx_tv, WaveletL1, ProxOperator, fgp_betas, ElementwiseProx, Laplace, UncenteredLaplace, Gaussian,
-                       GenGaussian, Huber, SmoothedLaplace, Box, Poisson, HuberLoss, VectorialTV)
+                       GenGaussian, Huber, SmoothedLaplace, Box, Poisson, HuberLoss, VectorialTV, TGV)
 from .algs import (MYULAResult, MYULASampler, MYMALASampler, MoreauYosidaUnadjustedLangevin, MoreauYosidaMetropolisAdjustedLangevin, ULPDASampler,
                    UnadjustedLangevinPrimalDual, block_mean_var, hist_exceedance, hist_quantiles, mean_var_from_moments, pixel_histogram,
                    set_step_variant, set_cg_tolerance, SKROCKSampler, StabilisedLangevin, skrock_coefficients, skrock_step_bound,
@@ -32,6 +32,6 @@ __all__ = [
     "group_moments", "mcse_from_group_moments", "GroupMCSE", "allreduce_group_moments", "allreduce_sampler_group_moments",
     "cov_sketch", "cov_from_sketch", "CovSketch", "random_probes", "allreduce_cov_sketch",
     "SAPGResult", "EstimatePriorWeight", "prior_statistic", "sapg_dimension", "sapg_update",
-    "VectorialTV", "MultichannelMYULASampler",
+    "VectorialTV", "MultichannelMYULASampler", "TGV",
 ]
 __version__ = "0.2.0"

@@ -36,6 +36,8 @@ PRIOR_NONE, PRIOR_L2, PRIOR_L1, PRIOR_TV_ISO, PRIOR_TV_ANISO, PRIOR_HAAR_L1, PRI
 PRIOR_WAVELET_L1 = 7      # Daubechies wavelet-l1: lmc_problem.tv_niter = levels, eprox_kind = p (the struct has no hole left)
 PRIOR_VTV = 8             # vectorial TV of a multi-channel image: lmc_mch_* and lmc_vtv_* only, every other entry point refuses it
 MAX_CHANNELS = 4
+PRIOR_TGV = 9             # second-order TGV: lmc_problem.tv_niter = iterations of the prox, eprox_p0 = alpha0, tv_step = the primal-dual step (0: 1 / sqrt(12))
+MAX_TGV_ITERS = 256
 NOISE_PHILOX, NOISE_INJECTED, NOISE_NONE = 0, 1, 2
 NCVX_NONE, NCVX_MC_TV, NCVX_ME_TV, NCVX_MC_TV_ANISO, NCVX_ME_TV_ANISO = 0, 1, 2, 3, 4
 MAX_BLUR = 9
@@ -219,6 +221,8 @@ _SIGNATURES = {
     "lmc_vtv_prox": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float, _F, C.c_int32, C.c_float, C.c_float, _P]),
     "lmc_vtv_value": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P]),
     "lmc_vtv_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 4),
+    "lmc_tgv_prox": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_float, _P]),
+    "lmc_tgv_launch_iters": (C.c_int, []),
     "lmc_mch_create": (C.c_int, [C.POINTER(lmc_mch_config), C.POINTER(_P)]),
     "lmc_mch_destroy": (None, [_P]),
     "lmc_mch_set_state": (C.c_int, [_P, _P, _P]),
@@ -344,6 +348,11 @@ def vtv_plan(dims, n_channels, niter):
     out = [C.c_int32() for _ in range(4)]
     check(load().lmc_vtv_plan(int(dims[0]), int(dims[1]), int(n_channels), int(niter), *[C.byref(o) for o in out]))
     return tuple(o.value for o in out)
+
+
+def tgv_launch_iters():
+    """The iterations one launch of the TGV prox kernel holds (lmc_tgv_launch_iters; host only): a prox of more runs as chained launches."""
+    return int(load().lmc_tgv_launch_iters())
 
 
 def exported_symbols():

@@ -130,6 +130,12 @@ def _refuse_vtv(proxg, who):
                                   "weight are not built for it")
 
 
+def _refuse_tgv(prior, who, why):
+    """``NotImplementedError`` for the TGV prior (``LMC_PRIOR_TGV``: a prox and no value) where ``who`` needs g(x) or a scalar-free prox (before any handle exists)."""
+    if prior.get("prior_kind") == _capi.PRIOR_TGV:
+        raise NotImplementedError(f"{who} does not take the TGV prior: {why}")
+
+
 def _data_descriptor(proxf):
     if proxf is None:
         return {"data_kind": _capi.DATA_NONE}
@@ -324,8 +330,12 @@ class MYULASampler:
             _refuse_box(_prior_descriptor(proxg), *self._box_refusal)
         if self._eprox_refusal is not None:
             _refuse_eprox(_prior_descriptor(proxg), *self._eprox_refusal)
+            _refuse_tgv(_prior_descriptor(proxg), self._eprox_refusal[0], "its value g(x) is a minimisation over the auxiliary field and is not built, so the "
+                        "Metropolis target exp(-f - epsg g) cannot be evaluated; use MYULA or SK-ROCK")
         if np.asarray(epsg).size > 1 and _prior_descriptor(proxg).get("prior_kind") == _capi.PRIOR_WAVELET_L1:
             raise NotImplementedError("array-valued epsg is built for the closed-form priors only: the wavelet-l1 prior takes a scalar epsg")
+        if np.asarray(epsg).size > 1:
+            _refuse_tgv(_prior_descriptor(proxg), "array-valued epsg", "it is built for the closed-form priors only; TGV takes a scalar epsg")
         if tv_warm and _prior_descriptor(proxg).get("box") is not None:
             raise NotImplementedError("a prior with bounds has no warm-started dual: tv_warm must be off")
         self.dims = (int(dims[0]), int(dims[1]))
@@ -1296,6 +1306,7 @@ def EstimatePriorWeight(proxf, proxg, x0, tau, gamma, n_updates, theta_bounds, t
     _refuse_vtv(proxg, "EstimatePriorWeight")
     dims = _dims_of(dims, proxf, proxg)
     prior = _prior_descriptor(proxg)
+    _refuse_tgv(prior, "EstimatePriorWeight", "its value g(x), the statistic of the estimator, is a minimisation over the auxiliary field and is not built")
     _refuse_box(prior, "EstimatePriorWeight", "the d / k homogeneity argument of the estimator does not hold on a bounded set")
     if theta0 is None:
         theta0 = _prior_weight(proxg)

@@ -469,6 +469,39 @@ int lmc_vtv_plan(int32_t H, int32_t W, int32_t n_channels, int32_t niter, int32_
   return LMC_OK;
 }
 
+int lmc_tgv_prox(const float* x_dev, float* out_dev, float* w_out_dev, int64_t n_img, int32_t H, int32_t W, float t_sigma, float alpha0, int32_t niter,
+                 float step, int32_t box_enable, float box_lo, float box_hi, void* stream) {
+  if (!x_dev || !out_dev || x_dev == out_dev || w_out_dev == x_dev || w_out_dev == out_dev) return fail(LMC_E_INVALID, "bad pointers (in-place not allowed)");
+  if (n_img < 1 || n_img > (1 << 24) || H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30)
+    return fail(LMC_E_INVALID, "bad shape n_img=%lld H=%d W=%d", (long long)n_img, H, W);
+  if (niter < 1 || niter > LMC_MAX_TGV_ITERS) return fail(LMC_E_INVALID, "niter %d outside 1..%d", niter, LMC_MAX_TGV_ITERS);
+  if (!(t_sigma >= 0.f) || !std::isfinite(t_sigma)) return fail(LMC_E_INVALID, "t_sigma must be finite and >= 0 (got %g)", (double)t_sigma);
+  if (!std::isfinite(alpha0) || !(alpha0 > 0.f)) return fail(LMC_E_INVALID, "alpha0 must be finite and > 0 (got %g)", (double)alpha0);
+  int rc = check_tgv_step(step);
+  if (rc) return rc;
+  if (box_enable) {
+    if (box_enable != 1) return fail(LMC_E_INVALID, "box_enable must be 0 or 1 (got %d)", box_enable);
+    if (!(box_lo == box_lo) || !(box_hi == box_hi)) return fail(LMC_E_INVALID, "box: a bound is NaN");
+    if (!(box_lo < box_hi)) return fail(LMC_E_INVALID, "box: needs box_lo < box_hi (got [%g, %g])", (double)box_lo, (double)box_hi);
+  }
+  const size_t npx = (size_t)n_img * H * W;
+  if (t_sigma == 0.f) {      // the prox of the indicator alone
+    if (box_enable) HIP_TRY(lmc::launch_box_prox(LMC_PRIOR_NONE, 0, x_dev, out_dev, n_img, (int64_t)H * W, nullptr, 0, 0, 0.f, 0.f, 0.f, 0.f, 0, box_lo, box_hi, S(stream)));
+    else HIP_TRY(hipMemcpyAsync(out_dev, x_dev, sizeof(float) * npx, hipMemcpyDeviceToDevice, S(stream)));
+    if (w_out_dev) HIP_TRY(hipMemsetAsync(w_out_dev, 0, sizeof(float) * 2 * npx, S(stream)));
+    return LMC_OK;
+  }
+  Workspace& sc = scratch_here();
+  const size_t ns = lmc::tgv_state_floats(n_img, H, W, niter);
+  HIP_TRY(sc.state[0].need(ns));
+  HIP_TRY(sc.state[1].need(ns));
+  HIP_TRY(lmc::launch_tgv_prox(x_dev, out_dev, w_out_dev, n_img, H, W, t_sigma, alpha0, step > 0.f ? step : lmc::kTgvStep, niter, box_enable, box_lo, box_hi,
+                               sc.state[0].p, sc.state[1].p, S(stream)));
+  return LMC_OK;
+}
+
+int lmc_tgv_launch_iters(void) { return lmc::kTgvLaunchIters; }
+
 int lmc_chain_probes(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t ph, int32_t pw, void* stream) {
   if (!x_dev || !out_dev || n_img < 1 || H < 1 || W < 1) return fail(LMC_E_INVALID, "bad arguments");
   if (ph < 1 || pw < 1 || ph > H || pw > W) return fail(LMC_E_INVALID, "probe grid %dx%d does not fit a %dx%d image", ph, pw, H, W);

@@ -67,6 +67,8 @@ struct Problem {
   int prior_kind = 0;
   float prior_sigma = 0.f;
   lmc::WaveletOp wav;       // LMC_PRIOR_WAVELET_L1: p, levels and the workspace of whoever owns it
+  int tgv_niter = 0;        // LMC_PRIOR_TGV: iterations (lmc_problem.tv_niter), alpha0 (eprox_p0) and the step (tv_step; 0: the default) of its prox
+  float tgv_alpha0 = 0.f, tgv_step = 0.f;
   int tv_niter = 0;
   float tv_step = 0.125f;
   float betas[lmc::kMaxTvIters] = {};
@@ -147,7 +149,7 @@ struct Buf {
 // lives for the life of the process; those calls are serialised by the caller, see lmc_atomi.h) and one inside every sampler handle, which never touches
 // the other.  prepare() is the one place that decides which buffers a problem needs, grows them and points the problem's operators at them.
 struct Workspace {
-  Buf<float> state[2];                    // TV dual state ping-pong, [n][4][H][W] each
+  Buf<float> state[2];                    // TV dual state ping-pong, [n][4][H][W] each; a chained TGV prox: its state, [n][11][H][W] each
   Buf<float> extra;                       // ME-TV inner prox, [n][H][W]
   Buf<float> prox;                        // a prox formed ahead of the step (Haar-l1, wavelet, closed forms, box, early-exit TV prox), [n][H][W]
   Buf<float> rtmp;                        // pass-by-pass early exit: the iterate of the current pass, [n][H][W]
@@ -270,6 +272,7 @@ constexpr int kSideBatches = 4;
 // ---- lmc_problem.hip ----
 int fill_taps(lmc::BlurTaps& T, const float* h, int kh, int kw, int oy, int ox);
 void default_betas(float* b, int n);
+int check_tgv_step(float step);      // LMC_PRIOR_TGV / lmc_tgv_prox: 0 or a step with 12 step^2 <= 1
 int load_problem(const lmc_problem* p, Problem& q);
 int check_no_box(const Problem& q, const char* who, const char* why);
 // One row per DataTerm, indexed by it (the row of kTermL2 is empty: the plain Gaussian term has no kernels of its own and nothing refuses it)

@@ -294,6 +294,30 @@ hipError_t launch_vtv_value(const float* x, int64_t n_img, int nch, int64_t cs, 
 }  // namespace lmc
 
 namespace lmc {
+// Second-order TGV (lmc_tgv.hip): the prox of LMC_PRIOR_TGV on single-plane images [n][H][W] by Chambolle-Pock primal-dual iterations.
+constexpr int kMaxTgvIters = LMC_MAX_TGV_ITERS;
+#ifndef LMC_TGV_LAUNCH_ITERS
+#define LMC_TGV_LAUNCH_ITERS 6           // chosen by measurement (DESIGN 3.0p "TGV prior"); -DLMC_TGV_LAUNCH_ITERS=n on lmc_tgv.hip and lmc_capi.hip measures another
+#endif
+constexpr int kTgvLaunchIters = LMC_TGV_LAUNCH_ITERS;      // iterations one launch holds (its halo): at 6 a 52 x 52 tile of the 64 x 64 patch, 1.51 pixel updates per pixel
+constexpr float kTgvStep = 0.28867513f;  // 1 / sqrt(12): ||K||^2 < 12 for K = [[grad, -I], [0, E]]
+// The launch plan of a prox of niter iterations: a workgroup owns a PH x PW patch = a TH x TW tile plus a halo of HL pixels, which covers the `iters`
+// iterations of one launch; n_launches launches are chained through the 11-plane state.  Host only.
+struct TgvPlan {
+  int PH, PW, HL, TH, TW;
+  int iters, n_launches;
+  size_t lds_bytes;           // dynamic LDS of one workgroup
+};
+bool tgv_plan(int niter, TgvPlan& out);       // false: niter outside 1 .. kMaxTgvIters
+// floats each of the two state buffers of a chained prox holds ([n_img][11][H][W]); 0 when one launch covers niter
+size_t tgv_state_floats(int64_t n_img, int H, int W, int niter);
+// out = prox_{t g}(x) with lam1 = t sigma > 0 by niter iterations of step `step` for both sides; w_out: NULL or [n][2][H][W], the auxiliary field;
+// box != 0: the primal iterate of every iteration clipped to [box_lo, box_hi].  x != out.  state0 / state1: tgv_state_floats each (may be NULL when 0).
+hipError_t launch_tgv_prox(const float* x, float* out, float* w_out, int64_t n_img, int H, int W, float lam1, float alpha0, float step, int niter, int box,
+                           float box_lo, float box_hi, float* state0, float* state1, hipStream_t st);
+}  // namespace lmc
+
+namespace lmc {
 // The spectral data term (lmc_fft.hip, lmc_fft_kernel.h): the batched 2-D real FFT in LDS of LMC_DATA_SPECTRAL, lmc_rfft2 / lmc_irfft2 and
 // lmc_spectral_filter; power-of-two sides kFftMin .. kFftMax, the half plane of W / 2 + 1 columns, norm = "ortho".
 constexpr int kFftMin = 8, kFftMax = 1024;

@@ -91,6 +91,8 @@ int lmc_mch_create(const lmc_mch_config* cfg, lmc_mch** out) {
   lmc_problem p = cfg->problem;
   if (p.struct_size != sizeof(lmc_problem))
     return fail(LMC_E_INVALID, "lmc_problem.struct_size %u != %zu (ABI mismatch)", p.struct_size, sizeof(lmc_problem));
+  if (p.prior_kind == LMC_PRIOR_TGV)
+    return fail(LMC_E_UNSUPPORTED, "lmc_mch_create: LMC_PRIOR_TGV acts on single-plane images (lmc_myula_create, lmc_skrock_create); a vectorial TGV is not built");
   if (p.prior_kind != LMC_PRIOR_VTV) return fail(LMC_E_INVALID, "lmc_mch_create: prior_kind must be LMC_PRIOR_VTV (got %d)", p.prior_kind);
   if (p.data_kind > LMC_DATA_MASK && p.data_kind <= LMC_DATA_HUBER_RADON)
     return fail(LMC_E_UNSUPPORTED, "lmc_mch_create: data_kind %d is not built per channel: LMC_DATA_NONE, IDENTITY, BLUR or MASK", p.data_kind);

@@ -34,6 +34,14 @@ void default_betas(float* b, int n) {
   }
 }
 
+// The step of the TGV prox: 0 (the default) or s with 12 s^2 <= 1, the bound on ||K||^2 -- to 1e-6, so that the default rounded to float32 passes
+int check_tgv_step(float step) {
+  if (!(step >= 0.f) || !std::isfinite(step)) return fail(LMC_E_INVALID, "LMC_PRIOR_TGV: the step must be finite and >= 0 (0: the default 1 / sqrt(12)); got %g", (double)step);
+  if (12.0 * (double)step * (double)step > 1.0 + 1e-6)
+    return fail(LMC_E_INVALID, "LMC_PRIOR_TGV: step %g has 12 step^2 > 1: the primal-dual iteration needs step^2 ||K||^2 <= 1 and ||K||^2 < 12", (double)step);
+  return LMC_OK;
+}
+
 int load_problem(const lmc_problem* p, Problem& q) {
   if (!p) return fail(LMC_E_INVALID, "lmc_problem is NULL");
   if (p->struct_size != sizeof(lmc_problem))
@@ -168,6 +176,19 @@ int load_problem(const lmc_problem* p, Problem& q) {
     case LMC_PRIOR_VTV:
       return fail(LMC_E_UNSUPPORTED, "LMC_PRIOR_VTV (vectorial TV) acts on a multi-channel image: it is built for lmc_mch_create, lmc_vtv_prox and lmc_vtv_value only; "
                   "this entry point takes single-plane images");
+    case LMC_PRIOR_TGV: {      // tv_niter = niter, eprox_p0 = alpha0, tv_step = s (include/lmc_atomi.h)
+      if (p->tv_niter < 1 || p->tv_niter > LMC_MAX_TGV_ITERS)
+        return fail(LMC_E_INVALID, "LMC_PRIOR_TGV: tv_niter holds the iterations of the prox, 1..%d (got %d)", LMC_MAX_TGV_ITERS, p->tv_niter);
+      if (!std::isfinite(p->eprox_p0) || !(p->eprox_p0 > 0.f))
+        return fail(LMC_E_INVALID, "LMC_PRIOR_TGV: eprox_p0 holds alpha0, the weight of the second-order term, finite and > 0 (got %g)", (double)p->eprox_p0);
+      const int rc = check_tgv_step(p->tv_step);
+      if (rc) return rc;
+      if (p->tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "LMC_PRIOR_TGV with tv_rtol > 0: the prox has no early exit; it runs the fixed count tv_niter");
+      if (p->tv_warm) return fail(LMC_E_UNSUPPORTED, "LMC_PRIOR_TGV with tv_warm: a primal-dual state carried across sampler iterations is not built");
+      if (p->tv_lagged_output) return fail(LMC_E_UNSUPPORTED, "LMC_PRIOR_TGV with tv_lagged_output: the prox returns the iterate after tv_niter iterations");
+      q.tgv_niter = p->tv_niter; q.tgv_alpha0 = p->eprox_p0; q.tgv_step = p->tv_step > 0.f ? p->tv_step : lmc::kTgvStep;
+      break;
+    }
     default: return fail(LMC_E_INVALID, "unknown prior_kind %d", p->prior_kind);
   }
   if (p->prior_kind != LMC_PRIOR_NONE && p->prior_kind != LMC_PRIOR_EPROX && !(p->prior_sigma >= 0.f)) return fail(LMC_E_INVALID, "prior_sigma must be >= 0");
@@ -340,6 +361,12 @@ int make_step_args(const Problem& q, float a, float t, float b, float pt, float 
   if (A.prior_kind == LMC_PRIOR_TV_ANISO) { A.prior_kind = LMC_PRIOR_TV_ISO; A.tv_aniso = 1; }
   if (A.prior_kind == LMC_PRIOR_TV_ISO && q.tv_niter == 0) { A.prior_kind = LMC_PRIOR_NONE; A.tv_aniso = 0; }   // lagged output of a 1-iteration prox: x itself
   if (A.prior_kind == LMC_PRIOR_HAAR_L1 || A.prior_kind == LMC_PRIOR_WAVELET_L1) A.prior_p0 = pt * q.prior_sigma;  // soft threshold of the detail coefficients
+  if (A.prior_kind == LMC_PRIOR_TGV) {      // the radius of the first-order ball; a zero weight leaves the indicator of the box, or nothing
+    const float lam1 = pt * q.prior_sigma;
+    if (!(lam1 >= 0.f) || !std::isfinite(lam1)) return fail(LMC_E_INVALID, "TGV prox parameter must be finite and >= 0 (got %g)", (double)lam1);
+    if (lam1 == 0.f) A.prior_kind = LMC_PRIOR_NONE;
+    A.prior_p0 = lam1;
+  }
   if (A.prior_kind == LMC_PRIOR_L2) A.prior_p0 = 1.f / (1.f + pt * q.prior_sigma);
   if (A.prior_kind == LMC_PRIOR_L1) A.prior_p0 = pt * q.prior_sigma;
   if (A.prior_kind == LMC_PRIOR_EPROX) {     // prox.py closed forms: the parameters the mask names scale with the prox parameter
@@ -465,9 +492,13 @@ hipError_t prepare(Workspace& ws, Problem& q, const lmc::StepArgs& probe, int64_
     if (q.ncvx_rtol > 0.f && !q.ncvx_aniso && !me_tv_exit_on_device(q, n_img)) n_rtmp = npx;
   }
   // a prox that is a launch of its own ahead of the step: the transforms, the closed forms (scalar or array-valued epsg), the box of a separable prior
-  if (step && (probe.prior_kind == LMC_PRIOR_HAAR_L1 || probe.prior_kind == LMC_PRIOR_WAVELET_L1 || probe.prior_kind == LMC_PRIOR_EPROX || q.prox_scale ||
-               (probe.box && probe.prior_kind != LMC_PRIOR_TV_ISO)))
+  if (step && (probe.prior_kind == LMC_PRIOR_HAAR_L1 || probe.prior_kind == LMC_PRIOR_WAVELET_L1 || probe.prior_kind == LMC_PRIOR_TGV ||
+               probe.prior_kind == LMC_PRIOR_EPROX || q.prox_scale || (probe.box && probe.prior_kind != LMC_PRIOR_TV_ISO)))
     n_prox = npx;
+  if (step && probe.prior_kind == LMC_PRIOR_TGV) {      // a chained TGV prox: its 11-plane state ping-pong
+    const size_t ns = lmc::tgv_state_floats(n_img, q.H, q.W, q.tgv_niter);
+    need(ws.state[0], ns); need(ws.state[1], ns);
+  }
   ws.tv_exit = -1;
   if (tv && q.tv_rtol > 0.f) {     // the early exit of the TV prior's prox: 1 inside the fused launch, 0 the prox alone first, 2 pass by pass
     ws.tv_exit = tv_prior_rt_mode(q, probe, pt);
@@ -619,6 +650,18 @@ hipError_t launch_step(const lmc::StepArgs& A_in, int variant, const Problem& q,
     lmc::StepArgs A = A_in;
     A.prior_kind = LMC_PRIOR_NONE;
     A.prox_ext = pxbuf;
+    return launch_step(A, variant, q, ws, st, name);
+  }
+  if (A_in.prior_kind == LMC_PRIOR_TGV) {
+    // the same route: the primal-dual prox (with the box inside its iterations) into pxbuf, then the step of the same problem without prior and box
+    if (!pxbuf) return hipErrorInvalidConfiguration;
+    hipError_t e = lmc::launch_tgv_prox(A_in.x_in, pxbuf, nullptr, A_in.C, A_in.H, A_in.W, A_in.prior_p0, q.tgv_alpha0, q.tgv_step, q.tgv_niter, A_in.box,
+                                        A_in.box_lo, A_in.box_hi, state0, state1, st);
+    if (e != hipSuccess) return e == hipErrorInvalidValue ? hipErrorInvalidConfiguration : e;
+    lmc::StepArgs A = A_in;
+    A.prior_kind = LMC_PRIOR_NONE;
+    A.prox_ext = pxbuf;
+    A.box = 0;
     return launch_step(A, variant, q, ws, st, name);
   }
   if (A_in.data_kind == LMC_DATA_PSF) return launch_step_psf(A_in, variant, q, ws, st, name);

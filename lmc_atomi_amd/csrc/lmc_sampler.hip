@@ -60,6 +60,8 @@ int check_weight_settable(const lmc_sampler* s) {
   if (s->prob.box) return fail(LMC_E_UNSUPPORTED, "the handle carries a box constraint: the estimation of the weight rests on the homogeneity of g on the whole space (the d / k term), which does not hold on a bounded set");
   if (s->prob.prior_kind == LMC_PRIOR_NONE || s->prob.prior_kind == LMC_PRIOR_EPROX)
     return fail(LMC_E_UNSUPPORTED, "prior_kind %d has no weight prior_sigma", s->prob.prior_kind);
+  if (s->prob.prior_kind == LMC_PRIOR_TGV)
+    return fail(LMC_E_UNSUPPORTED, "the weight of the TGV prior (LMC_PRIOR_TGV) cannot be estimated or moved: its value g(x), the statistic of the estimator, is not built");
   return LMC_OK;
 }
 
@@ -129,10 +131,10 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     s->pol_overlap = q.moments_overlap ? q.moments_overlap : (getenv("LMC_MOMENTS_OVERLAP") ? (env_int("LMC_MOMENTS_OVERLAP", 0) ? 1 : -1) : 0);
     s->pol_bg_wgs = q.moments_bg_wgs > 0 ? q.moments_bg_wgs : env_int("LMC_MOMENTS_BG_WGS", -1);
     // One iteration per launch (the pair kernels have no form of it) wherever an iteration is more than the one fused launch:
-    //   prox_scale, box, wav.on   the prox is a launch of its own before every step (array-valued epsg, the clamp, the wavelet transforms)
+    //   prox_scale, box, wav.on, TGV   the prox is a launch of its own before every step (array-valued epsg, the clamp, the wavelet transforms, the primal-dual prox)
     //   term                      the weighted Gaussian, the Huber and the Poisson data terms have kernels of their own, none of them a pair kernel
     //   psf.on, fft.on, radon.on  the large PSF, the spectral data term and the Radon operator are three launches per iteration
-    if (q.prox_scale || q.box || q.wav.on || q.term != lmc::kTermL2 || q.psf.on || q.fft.on || q.radon.on) { s->pol_pair = 0; s->pol_blockpair = 0; }
+    if (q.prox_scale || q.box || q.wav.on || q.prior_kind == LMC_PRIOR_TGV || q.term != lmc::kTermL2 || q.psf.on || q.fft.on || q.radon.on) { s->pol_pair = 0; s->pol_blockpair = 0; }
   }
   if (e == hipSuccess && s->prob.tv_warm) {
     lmc::StepArgs probe = s->base;
@@ -521,6 +523,11 @@ int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     return fail(LMC_E_UNSUPPORTED, "MYMALA does not take the Radon operator (LMC_DATA_RADON, LMC_DATA_POISSON_RADON, LMC_DATA_WL2_RADON, LMC_DATA_HUBER_RADON): its "
                 "Metropolis ratio is pinned for the fused step and its energy by-products, which the three-launch Radon step does not form; use MYULA or SK-ROCK");
   }
+  if (cfg && out && cfg->struct_size == sizeof(lmc_myula_config) && cfg->problem.prior_kind == LMC_PRIOR_TGV) {
+    *out = nullptr;
+    return fail(LMC_E_UNSUPPORTED, "MYMALA does not take the TGV prior (LMC_PRIOR_TGV): its value g(x) is a minimisation over the auxiliary field and is not built, "
+                "so the Metropolis target exp(-f - epsg g) cannot be evaluated; use MYULA or SK-ROCK");
+  }
   int rc = lmc_myula_create(cfg, out);
   if (rc) return rc;
   lmc_sampler* s = *out;
@@ -819,6 +826,9 @@ int lmc_ulpda_create(const lmc_ulpda_config* cfg, lmc_sampler** out) {
     return fail(LMC_E_INVALID, "lmc_ulpda_config.struct_size %u != %zu (ABI mismatch)", cfg->struct_size, sizeof(lmc_ulpda_config));
   int rc = check_config(*cfg, cfg->tau > 0.f && cfg->mu > 0.f, "tau and mu must be > 0");
   if (rc) return rc;
+  if (cfg->problem.prior_kind == LMC_PRIOR_TGV)
+    return fail(LMC_E_UNSUPPORTED, "ULPDA does not take the TGV prior (LMC_PRIOR_TGV): it needs g o A with a dual prox in closed form (L21 or L1 on the gradient); "
+                "the TGV prox is an inner primal-dual loop of its own; use MYULA or SK-ROCK");
   if (cfg->problem.prior_kind != LMC_PRIOR_TV_ISO && cfg->problem.prior_kind != LMC_PRIOR_TV_ANISO)
     return fail(LMC_E_UNSUPPORTED, "ULPDA needs g o A with g = L21 (LMC_PRIOR_TV_ISO) or L1 (LMC_PRIOR_TV_ANISO)");
   if (!(cfg->problem.prior_sigma > 0.f)) return fail(LMC_E_INVALID, "prior_sigma (dual ball radius) must be > 0");

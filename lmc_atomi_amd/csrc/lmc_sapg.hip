@@ -229,6 +229,8 @@ int check_stat_problem(const lmc_problem* p) {
   if (p->struct_size != sizeof(lmc_problem))
     return fail(LMC_E_INVALID, "lmc_problem.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(lmc_problem));
   if (p->H < 1 || p->W < 1 || (int64_t)p->H * p->W > (int64_t)1 << 30) return fail(LMC_E_INVALID, "bad image size %dx%d", p->H, p->W);
+  if (p->prior_kind == LMC_PRIOR_TGV)
+    return fail(LMC_E_UNSUPPORTED, "LMC_PRIOR_TGV has no statistic: its value g(x) is a minimisation over the auxiliary field and is not built");
   if (p->prior_kind < LMC_PRIOR_NONE || p->prior_kind > LMC_PRIOR_WAVELET_L1) return fail(LMC_E_INVALID, "unknown prior_kind %d", p->prior_kind);
   if (p->prior_kind == LMC_PRIOR_NONE || p->prior_kind == LMC_PRIOR_EPROX)
     return fail(LMC_E_UNSUPPORTED, "prior_kind %d has no value g(x): no statistic", p->prior_kind);

@@ -194,6 +194,8 @@ class _Problem:
         p.graph_replay = 1 if opt.get("graph_replay") else 0
         if p.prior_kind == _capi.PRIOR_WAVELET_L1:      # its two parameters ride in fields the kind does not otherwise read
             p.tv_niter, p.eprox_kind = int(prior["wavelet_levels"]), int(prior["wavelet_p"])
+        if p.prior_kind == _capi.PRIOR_TGV:      # likewise: the iterations, alpha0 and the step of its prox
+            p.tv_niter, p.eprox_p0, p.tv_step = int(prior["tgv_niter"]), float(prior["tgv_alpha0"]), float(prior.get("tgv_step", 0.0))
         if p.prior_kind == _capi.PRIOR_EPROX:
             p.eprox_kind = int(prior["eprox_kind"])
             p.eprox_p0, p.eprox_p1 = float(prior["eprox_p0"]), float(prior["eprox_p1"])
@@ -1042,6 +1044,73 @@ class VectorialTV(ProxOperator):
         _dev.run(xt, "lmc_vtv_prox", _dev.ptr(xt), _dev.ptr(out), n, self.n_channels, n * self.dims[0] * self.dims[1], self.dims[0], self.dims[1],
                  self.sigma * float(tau), self.niter, self.step, _dev.fptr(self._betas), 1 if self.bounds is not None else 0, lo, hi)
         return _dev.like_input(out, x)
+
+
+class TGV(ProxOperator):
+    """``sigma * TGV2(x)``: total generalised variation of order two (Bredies, Kunisch and Pock 2010; build-specified, ``LMC_PRIOR_TGV`` in
+    include/lmc_atomi.h is its definition),
+
+        ``g(x) = sigma * min_w ( sum |grad x - w|_2 + alpha0 * sum |E w|_F )``
+
+    with ``E`` the symmetrised derivative of the field ``w``.  An intensity ramp costs nothing, where :class:`TV` charges its full variation and samples
+    it as terraces.  ``prox`` is ``niter`` (1 .. 256) Chambolle-Pock primal-dual iterations with one step ``step`` for both sides (None: 1 / sqrt(12);
+    ``12 step^2 > 1`` raises ``ValueError``) from ``u = x``, ``w = 0`` and zero duals, run on chip by ``tgv_prox_kernel``.  The count is fixed and the
+    result is the truncated iterate, the same kind of truncation as ``TV(niter=10)``: the iteration converges sublinearly -- on a 32 x 48 two-facet affine
+    image with noise of sd 10 at ``tau * sigma = 5`` the distance to the converged prox, relative to ``|prox - x|``, is 0.14, 0.085, 0.048, 0.032, 0.021
+    after 10, 20, 40, 80, 160 iterations (float64 prototype; the TV prox moves the clean ramp by 5.9 grey levels, this one by 0.46).
+    ``bounds=(lo, hi)``: ``g +`` the indicator of the box; the primal iterate is clipped inside every iteration, the exact prox of its quadratic plus the
+    indicator (clipping afterwards gives another point).
+
+    ``prox(x, tau)`` takes a flat image, ``[H, W]`` or a batch ``[n, H, W]`` (or flat of that size) and returns the shape it was given;
+    ``prox(x, tau, return_w=True)`` also returns the auxiliary field ``w`` as ``[..., 2, H, W]`` (row component first).  ``__call__`` raises
+    ``NotImplementedError``: the value is a minimisation over ``w`` and is not built, so the samplers report ``energy_g = 0`` for it.  As ``proxg`` of
+    MYULA and SK-ROCK (:class:`MYULASampler`, :class:`SKROCKSampler` and their drivers) with every data term, the box (MYULA), the accumulators and
+    sharding; MYMALA, ULPDA, :func:`EstimatePriorWeight` and array-valued ``epsg`` raise ``NotImplementedError``."""
+
+    def __init__(self, dims, sigma=1.0, alpha0=2.0, niter=40, bounds=None, step=None):
+        super().__init__(None, False)
+        self.dims = (int(dims[0]), int(dims[1]))
+        if self.dims[0] < 1 or self.dims[1] < 1:
+            raise ValueError(f"dims must be a pair of positive sizes (got {dims!r})")
+        self.sigma = float(sigma)
+        if not self.sigma >= 0.0 or not np.isfinite(self.sigma):
+            raise ValueError(f"sigma must be finite and >= 0 (got {sigma})")
+        self.alpha0 = float(alpha0)
+        if not self.alpha0 > 0.0 or not np.isfinite(self.alpha0):
+            raise ValueError(f"alpha0 must be finite and > 0 (got {alpha0})")
+        self.niter = int(niter)
+        if not 1 <= self.niter <= _capi.MAX_TGV_ITERS:
+            raise ValueError(f"niter must be in 1 .. {_capi.MAX_TGV_ITERS} (got {niter})")
+        self.bounds = check_bounds(bounds)
+        self.step = 0.0 if step is None else float(step)      # 0: the library's default, 1 / sqrt(12)
+        if step is not None and (not self.step > 0.0 or not np.isfinite(self.step) or 12.0 * self.step * self.step > 1.0 + 1e-6):
+            raise ValueError(f"step must be > 0 with 12 step^2 <= 1 (got {step}): the primal-dual iteration needs step^2 ||K||^2 <= 1")
+
+    def prior_descriptor(self):
+        return _with_box({"prior_kind": _capi.PRIOR_TGV, "prior_sigma": self.sigma, "tgv_niter": self.niter, "tgv_alpha0": self.alpha0,
+                          "tgv_step": self.step}, self.bounds)
+
+    def __call__(self, x):
+        raise NotImplementedError("TGV has no value: g(x) is a minimisation over the auxiliary field w and is not built (its prox is; the samplers report "
+                                  "energy_g = 0 for this prior)")
+
+    def prox(self, x, tau, return_w=False):
+        xt = _dev.to_dev(x)
+        n = self.dims[0] * self.dims[1]
+        if xt.numel() == 0 or xt.numel() % n:
+            raise ValueError(f"operand of shape {tuple(xt.shape)} is not a batch of {self.dims} images")
+        n_img = xt.numel() // n
+        out = torch.empty_like(xt)
+        w = torch.empty((n_img, 2) + self.dims, dtype=torch.float32, device=xt.device) if return_w else None
+        lo, hi = self.bounds if self.bounds is not None else (0.0, 0.0)
+        _dev.run(xt, "lmc_tgv_prox", _dev.ptr(xt), _dev.ptr(out), _dev.ptr(w), n_img, self.dims[0], self.dims[1], self.sigma * float(tau), self.alpha0,
+                 self.niter, self.step, 1 if self.bounds is not None else 0, lo, hi)
+        u = _dev.like_input(out, x)
+        if not return_w:
+            return u
+        lead = tuple(xt.shape[:-2]) if xt.dim() >= 2 and tuple(xt.shape[-2:]) == self.dims else ((n_img,) if n_img > 1 else ())
+        w = w.reshape(lead + (2,) + self.dims)
+        return u, (w if isinstance(x, torch.Tensor) else w.cpu().numpy())
 
 
 class L2_ncvx_tv(ProxOperator):
