@@ -903,6 +903,73 @@ int lmc_mch_noise(lmc_mch* s, int64_t iteration, float* out_dev, void* stream);
 /* the kernels of the latest iteration: the prox kernel and the step kernel of the last channel */
 const char* lmc_mch_kernel_name(const lmc_mch* s);
 
+/* ---- split Gibbs sampler (SGS): exact Gaussian x-step, MYULA z-step ----------------------------------------------------------------
+ * Vono, Dobigeon, Chainais (2019); Pereyra, Vargas-Mieles, Zygalakis (2022).  A handle type of its own (lmc_sgs.hip) that composes existing launches.
+ * Build-specified; this text is its definition.  Augmented target with the coupling parameter rho > 0:
+ *   pi_rho(x, z)  ~  exp( -f(x) - epsg g(z) - ||x - z||^2 / (2 rho^2) ).
+ * Its x-marginal is the posterior with g replaced by a rho^2-smoothed version of it (rho -> 0 recovers the posterior).  This is a bias of the MODEL,
+ * chosen with rho; it is separate from, and adds to, the bias of the MYULA discretisation of the z-step (chosen with tau and gamma).
+ * State: [2][n_chains][H][W], plane 0 = x, plane 1 = z.  With rinv = 1 / rho^2 (float32: 1 / (rho * rho)), iteration k is
+ *  1. x | z, exact:  x ~ N(Q^-1 (z rinv + grad-free part of -grad f), Q^-1),  Q = Hess f + rinv I.
+ *     LMC_DATA_SPECTRAL, with the half-plane tables A (real), B (complex) of lmc_spectral_tables and transforms of norm "ortho":
+ *         q_k = sigma_f A_k + rinv,    x = irfft2( ( rfft2(z) rinv + sigma_f B + sqrt(q) .* rfft2(xi_x) ) / q ).
+ *       xi_x is a real N(0, 1) field in pixel space: its unitary transform is the Hermitian white field, and A_k = A_-k, so x is real.
+ *       Launches: fft_rows_fwd_kernel on z and on xi_x, ONE sgs_cols_gibbs_kernel per strip (the column transform of the noise strip is
+ *       kept in registers scaled by sqrt(q), then the strip of z is transformed, the functor applied, and transformed back), fft_rows_inv_kernel.
+ *     LMC_DATA_IDENTITY, LMC_DATA_MASK (mask m), LMC_DATA_WL2_IDENTITY (weights w); w = 1, m = 1 where absent; y = b:
+ *         q_p = sigma_f w_p m_p^2 + rinv,    x_p = ( z_p rinv + sigma_f w_p m_p b_p + sqrt(q_p) xi_x,p ) / q_p.
+ *     LMC_DATA_NONE: q = rinv.   (One elementwise kernel, sgs_xdiag_*; sqrt and the division are IEEE.)
+ *     With xi_x = 0 the draw is the conditional mean, prox_{rho^2 f}(z) (what lmc_l2_prox evaluates at tau = rho^2).
+ *  2. z | x, n_inner MYULA steps on exp(-epsg g(z) - ||z - x||^2 / (2 rho^2)) with step tau and smoothing gamma:
+ *         z+ = z - (tau rinv)(z - x) - (tau / gamma)(z - prox_{epsg gamma g}(z)) + sqrt(2 tau) xi_z.
+ *     Launches: the step kernel of the same problem with LMC_DATA_NONE -- z' = (1 - tau / gamma) z + (tau / gamma) prox + sqrt(2 tau) xi_z, every prior and
+ *     box that launch takes -- then sgs_couple_kernel: z+ = fma(-(tau rinv), z_old - x, z') (the difference first, then one fma).
+ *     The smooth part of the z-potential has the Lipschitz constant rinv + 1 / gamma: tau <= 1 / (rinv + 1 / gamma) is the recommended range.
+ *  3. The kept iterate is x after stage 1; burn_in, thin, the pixel moments and the chain-group moments are those of lmc_sampler_* on x.
+ * Noise: plane p (0: xi_x, 1: xi_z) draws the Philox field of the seed (seed + (p << 32)) mod 2^64 -- key1 = (uint32)(seed >> 32) + p -- the convention of
+ * lmc_mch_*; any sharding of the chains (chain_offset) reproduces the same trajectories.  xi_x of iteration k is the field of counter k; xi_z of inner step
+ * j is the field of counter k n_inner + j ((iteration + 1) n_inner must fit 32 bits).  Injected noise: [n_iters][1 + n_inner][n_chains][H][W], xi_x first.
+ * lmc_sgs_noise: plane_and_inner = 0 is xi_x of `iteration`, 1 + j is xi_z of its inner step j.
+ * lmc_sgs_energies: f_out[c] = f(x_c), g_out[c] = g(z_c) (0 for a prior without a value: closed-form proxes, TGV), coupling_out[c] =
+ * ||x_c - z_c||^2 / (2 rho^2) (differences and squares in float64, summed in a fixed order); each may be NULL.
+ * LMC_E_UNSUPPORTED, with the reason in lmc_last_error: a data term whose Hessian is diagonal in neither basis (LMC_DATA_BLUR, the large PSF, the Radon
+ * operator; a periodic blur is LMC_DATA_SPECTRAL), Poisson and Huber terms (the conditional is not Gaussian), ncvx_kind != NONE, tv_rtol > 0, tv_warm,
+ * prox_scale, LMC_PRIOR_VTV.  LMC_E_INVALID: rho, tau or gamma not finite and > 0, n_inner outside 1 .. LMC_MAX_SGS_INNER, spectral sides that are not
+ * powers of two in 8 .. 1024.  Calls on one handle must be serialised by the caller. */
+#define LMC_MAX_SGS_INNER 16
+typedef struct lmc_sgs lmc_sgs; /* opaque */
+
+typedef struct lmc_sgs_config {
+  uint32_t struct_size;     /* = sizeof(lmc_sgs_config) */
+  lmc_problem problem;
+  int32_t n_chains; int64_t chain_offset;
+  float rho, tau, gamma, epsg;
+  int32_t n_inner;
+  uint64_t seed; int32_t noise_mode;
+  int32_t moments, burn_in, thin;
+} lmc_sgs_config;
+
+int lmc_sgs_create(const lmc_sgs_config* cfg, lmc_sgs** out);
+void lmc_sgs_destroy(lmc_sgs* s);
+/* x_dev: [2][n_chains][H][W], x then z */
+int lmc_sgs_set_state(lmc_sgs* s, const float* x_dev, void* stream);
+int lmc_sgs_get_state(lmc_sgs* s, float* x_dev, void* stream);
+int lmc_sgs_step(lmc_sgs* s, int32_t n_iters, const float* noise_dev, void* stream);
+int64_t lmc_sgs_iteration(const lmc_sgs* s);
+int lmc_sgs_set_iteration(lmc_sgs* s, int64_t it);
+int lmc_sgs_get_moments(lmc_sgs* s, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream);
+int lmc_sgs_reset_moments(lmc_sgs* s, void* stream);
+/* as lmc_sampler_set_chain_groups / lmc_sampler_get_group_moments, on the kept x */
+int lmc_sgs_set_chain_groups(lmc_sgs* s, int32_t n_groups);
+int lmc_sgs_get_group_moments(lmc_sgs* s, double* sum_dev, double* sumsq_dev, uint64_t* counts_host, void* stream);
+int lmc_sgs_energies(lmc_sgs* s, double* f_out_dev, double* g_out_dev, double* coupling_out_dev, void* stream);
+int lmc_sgs_noise(lmc_sgs* s, int64_t iteration, int32_t plane_and_inner, float* out_dev, void* stream);
+/* the kernels of the latest iteration: the x-draw, then the step kernel of the z-step */
+const char* lmc_sgs_kernel_name(const lmc_sgs* s);
+/* The stateless x-draw of stage 1: out = the draw of x | z for n_img images z with the white field noise_dev ([n_img][H][W]); noise_dev = NULL: the
+ * conditional mean.  The prior fields of prob are validated and not used.  out_dev may not alias z_dev or noise_dev. */
+int lmc_sgs_xstep(const lmc_problem* prob, const float* z_dev, const float* noise_dev, float* out_dev, int64_t n_img, float rho, void* stream);
+
 /* ---- multi-GPU: the one collective of the path ----------------------------------------------
  * Chains are sharded over GPUs by global chain id (chain_offset), one process per GPU, no data-path collective.  The only
  * exchange is the sum of the posterior-moment accumulators over the ranks -- what generalises the `.mean(axis=0)` over iterates

@@ -11,7 +11,8 @@ from .algs import (MYULAResult, MYULASampler, MYMALASampler, MoreauYosidaUnadjus
                    UnadjustedLangevinPrimalDual, block_mean_var, hist_exceedance, hist_quantiles, mean_var_from_moments, pixel_histogram,
                    set_step_variant, set_cg_tolerance, SKROCKSampler, StabilisedLangevin, skrock_coefficients, skrock_step_bound,
                    SAPGResult, EstimatePriorWeight, prior_statistic, sapg_dimension, sapg_update, GroupMCSE, group_moments, mcse_from_group_moments,
-                   CovSketch, cov_sketch, cov_from_sketch, random_probes, MultichannelMYULASampler)
+                   CovSketch, cov_sketch, cov_from_sketch, random_probes, MultichannelMYULASampler, SplitGibbs, SplitGibbsResult, SplitGibbsSampler,
+                   sgs_step_bound, sgs_xstep)
 
 from . import diagnostics, metrics
 from .diagnostics import ChainTrace, chain_probes, ess, split_rhat
@@ -33,5 +34,6 @@ __all__ = [
     "cov_sketch", "cov_from_sketch", "CovSketch", "random_probes", "allreduce_cov_sketch",
     "SAPGResult", "EstimatePriorWeight", "prior_statistic", "sapg_dimension", "sapg_update",
     "VectorialTV", "MultichannelMYULASampler", "TGV",
+    "SplitGibbsSampler", "SplitGibbs", "SplitGibbsResult", "sgs_step_bound", "sgs_xstep",
 ]
 __version__ = "0.2.0"

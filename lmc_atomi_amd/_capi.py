@@ -150,6 +150,23 @@ class lmc_mch_config(C.Structure):
     ]
 
 
+MAX_SGS_INNER = 16        # LMC_MAX_SGS_INNER
+
+
+class lmc_sgs_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("problem", lmc_problem),
+        ("n_chains", C.c_int32),
+        ("chain_offset", C.c_int64),
+        ("rho", C.c_float), ("tau", C.c_float), ("gamma", C.c_float), ("epsg", C.c_float),
+        ("n_inner", C.c_int32),
+        ("seed", C.c_uint64),
+        ("noise_mode", C.c_int32),
+        ("moments", C.c_int32), ("burn_in", C.c_int32), ("thin", C.c_int32),
+    ]
+
+
 class lmc_ulpda_config(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -235,6 +252,21 @@ _SIGNATURES = {
     "lmc_mch_energies": (C.c_int, [_P, _P, _P, _P]),
     "lmc_mch_noise": (C.c_int, [_P, C.c_int64, _P, _P]),
     "lmc_mch_kernel_name": (C.c_char_p, [_P]),
+    "lmc_sgs_create": (C.c_int, [C.POINTER(lmc_sgs_config), C.POINTER(_P)]),
+    "lmc_sgs_destroy": (None, [_P]),
+    "lmc_sgs_set_state": (C.c_int, [_P, _P, _P]),
+    "lmc_sgs_get_state": (C.c_int, [_P, _P, _P]),
+    "lmc_sgs_step": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "lmc_sgs_iteration": (C.c_int64, [_P]),
+    "lmc_sgs_set_iteration": (C.c_int, [_P, C.c_int64]),
+    "lmc_sgs_get_moments": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64), _P]),
+    "lmc_sgs_reset_moments": (C.c_int, [_P, _P]),
+    "lmc_sgs_set_chain_groups": (C.c_int, [_P, C.c_int32]),
+    "lmc_sgs_get_group_moments": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64), _P]),
+    "lmc_sgs_energies": (C.c_int, [_P, _P, _P, _P, _P]),
+    "lmc_sgs_noise": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P]),
+    "lmc_sgs_kernel_name": (C.c_char_p, [_P]),
+    "lmc_sgs_xstep": (C.c_int, [C.POINTER(lmc_problem), _P, _P, _P, C.c_int64, C.c_float, _P]),
     "lmc_dual_project": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),
     "lmc_prox_elementwise": (C.c_int, [C.c_int32, _P, _P, C.c_int64, _F, C.c_int32, _P]),
     "lmc_myula_create": (C.c_int, [C.POINTER(lmc_myula_config), C.POINTER(_P)]),

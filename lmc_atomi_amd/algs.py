@@ -1178,6 +1178,268 @@ def _multichannel_myula(proxf, proxg, x0, tau, gamma, epsg, niter, seed, n_chain
         return MYULAResult(state, mean, var, cnt, f, g, time.time() - tstart)
 
 
+def sgs_step_bound(rho, gamma):
+    """``1 / (1 / rho^2 + 1 / gamma)``: the reciprocal of the Lipschitz constant of the smooth part of the z-potential of the split Gibbs sampler,
+    ``||z - x||^2 / (2 rho^2)`` plus the Moreau envelope of ``epsg g`` at ``gamma``.  ``tau`` at or below it is the recommended range of
+    :class:`SplitGibbsSampler` (the x-step is an exact draw and bounds nothing).  Host arithmetic, no GPU."""
+    rho, gamma = float(rho), float(gamma)
+    if not (np.isfinite(rho) and rho > 0 and np.isfinite(gamma) and gamma > 0):
+        raise ValueError(f"rho and gamma must be finite and > 0 (got {rho!r}, {gamma!r})")
+    return 1.0 / (1.0 / rho ** 2 + 1.0 / gamma)
+
+
+def _refuse_sgs(data, prior, proxg, epsg):
+    """``NotImplementedError`` for what ``lmc_sgs_create`` refuses with ``LMC_E_UNSUPPORTED`` (include/lmc_atomi.h), before a handle exists."""
+    who = "the split Gibbs sampler"
+    _refuse_vtv(proxg, "SplitGibbsSampler")
+    kind = data.get("data_kind")
+    blurs = (_capi.DATA_BLUR, _capi.DATA_POISSON_BLUR, _capi.DATA_WL2_BLUR, _capi.DATA_HUBER_BLUR)
+    if kind in blurs or kind in _capi.PSF_KINDS:
+        raise NotImplementedError(f"{who} draws x | z exactly where the Hessian of the data term is diagonal in the pixel or the Fourier basis; that of a "
+                                  "zero-padded blur (Convolve2D, PSF) is diagonal in neither -- a periodic blur (PeriodicConvolve2D) is")
+    if kind in _capi.RADON_KINDS:
+        raise NotImplementedError(f"{who} draws x | z exactly where the Hessian of the data term is diagonal in the pixel or the Fourier basis; that of the "
+                                  "Radon operator is diagonal in neither (Fourier-domain terms: FourierSampling, PeriodicConvolve2D)")
+    if kind in _capi.POISSON_KINDS:
+        raise NotImplementedError(f"{who} does not take the Poisson data term: the conditional x | z is not Gaussian")
+    if kind in _capi.HUBER_KINDS:
+        raise NotImplementedError(f"{who} does not take the Huber data term (HuberLoss): the conditional x | z is not Gaussian")
+    if data.get("ncvx_kind", _capi.NCVX_NONE) != _capi.NCVX_NONE:
+        raise NotImplementedError(f"{who} does not take the non-convex data terms (L2_ncvx_tv): the conditional x | z is not Gaussian")
+    if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
+        raise NotImplementedError(f"{who} runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
+    if prior.get("tv_warm"):
+        raise NotImplementedError(f"{who} has no warm-started TV dual: warm must be off")
+    if np.asarray(epsg).size > 1:
+        raise NotImplementedError(f"{who} takes a scalar epsg: array-valued epsg belongs to MYULASampler")
+
+
+def sgs_xstep(proxf, z, rho, noise=None, dims=None):
+    """The stateless x-draw of the split Gibbs sampler (``lmc_sgs_xstep``): a draw of ``x | z`` for the images ``z`` (``[n, H, W]`` or ``[H, W]``) with
+    the white field ``noise`` of the same shape; ``noise=None`` returns the conditional mean, ``prox_{rho^2 f}(z)``.  numpy in, numpy out; a torch tensor in, a torch tensor on its device out."""
+    data = _data_descriptor(proxf)
+    _refuse_sgs(data, {}, None, 1.0)
+    if not (np.isfinite(float(rho)) and float(rho) > 0):
+        raise ValueError(f"rho must be finite and > 0 (got {rho!r})")
+    dims = _dims_of(dims, proxf, getattr(proxf, "Op", None))
+    prob = _Problem(dims, data, None)
+    zt = _dev.to_dev(z, prob.device)
+    n = prob.dims[0] * prob.dims[1]
+    if zt.numel() % n:
+        raise ValueError(f"z of shape {tuple(zt.shape)} is not a batch of {prob.dims} images")
+    nt = None if noise is None else _dev.to_dev(noise, prob.device)
+    if nt is not None and nt.numel() != zt.numel():
+        raise ValueError("noise must have the shape of z")
+    out = torch.empty_like(zt)
+    _dev.run(zt, "lmc_sgs_xstep", C.byref(prob.c), _dev.ptr(zt), _dev.ptr(nt), _dev.ptr(out), zt.numel() // n, float(rho))
+    return _dev.like_input(out, z)
+
+
+class SplitGibbsSampler:
+    """The split Gibbs sampler (Vono, Dobigeon, Chainais 2019) for many chains: owns an ``lmc_sgs`` handle (include/lmc_atomi.h holds the definition).
+
+    Target ``pi_rho(x, z) ~ exp(-f(x) - epsg g(z) - ||x - z||^2 / (2 rho^2))``.  One iteration: an EXACT Gaussian draw of ``x | z`` -- no step size, and
+    as well conditioned for a 30 % k-space mask or a PSF with spectral zeros as for the identity -- then ``n_inner`` MYULA steps of size ``tau`` and
+    smoothing ``gamma`` on ``z | x`` (:func:`sgs_step_bound` gives the recommended ``tau``).  ``proxf``: :class:`L2` over ``FourierSampling``,
+    ``PeriodicConvolve2D``, ``Identity``, ``Diagonal``, ``L2(weights=)`` on the identity, or ``None``; ``proxg``: every prior and ``bounds=`` that
+    :class:`MYULASampler` takes without a data term.  The x-marginal is the posterior with ``g`` replaced by a ``rho^2``-smoothed version of it: a bias of
+    the model, set by ``rho``, separate from the bias of the MYULA z-step, set by ``tau`` and ``gamma``.  The kept iterate (moments, chain groups) is ``x``.
+    Plane ``p`` (0: the noise of the x-draw, 1: of the z-step) draws the Philox field of the seed ``(seed + (p << 32)) mod 2^64``; any sharding of the
+    chains by ``chain_offset`` reproduces the same trajectories.  What the library has no path for raises ``NotImplementedError`` before a handle
+    exists, bad values ``ValueError``."""
+
+    def __init__(self, proxf, proxg, dims, n_chains, rho, tau, gamma, n_inner=1, epsg=1.0, seed=0, burn_in=0, thin=1, chain_groups=None, chain_offset=0,
+                 noise="philox", moments=True, device=None, variant=None):
+        data, prior = _data_descriptor(proxf), _prior_descriptor(proxg)
+        _refuse_sgs(data, prior, proxg, epsg)
+        for name, v in (("rho", rho), ("tau", tau), ("gamma", gamma)):
+            if not (np.isfinite(float(v)) and float(v) > 0):
+                raise ValueError(f"{name} must be finite and > 0 (got {v!r})")
+        if not 1 <= int(n_inner) <= _capi.MAX_SGS_INNER:
+            raise ValueError(f"n_inner must be in 1 .. {_capi.MAX_SGS_INNER} (got {n_inner!r})")
+        if not float(epsg) >= 0:
+            raise ValueError(f"epsg must be >= 0 (got {epsg!r})")
+        if noise not in ("philox", "injected", "none"):
+            raise ValueError("noise must be 'philox', 'injected' or 'none'")
+        if int(n_chains) < 1:
+            raise ValueError("n_chains must be >= 1")
+        if moments and (int(thin) < 1 or int(burn_in) < 0):
+            raise ValueError("thin must be >= 1 and burn_in >= 0")
+        self.dims = (int(dims[0]), int(dims[1]))
+        if data.get("data_kind") == _capi.DATA_SPECTRAL:
+            _capi.check_fft_dims(self.dims)
+        groups = _check_chain_groups(chain_groups, moments)
+        self.n_chains, self.n_inner = int(n_chains), int(n_inner)
+        self.rho, self.tau, self.gamma = float(rho), float(tau), float(gamma)
+        self.device = _dev.device(device)
+        self.proxf, self.proxg = proxf, proxg
+        self._problem = _Problem(self.dims, data, prior, self.device, options={"step_variant": variant or 0})
+        cfg = _capi.lmc_sgs_config()
+        cfg.struct_size = C.sizeof(_capi.lmc_sgs_config)
+        cfg.problem = self._problem.c
+        cfg.n_chains = self.n_chains
+        cfg.chain_offset = int(chain_offset)
+        cfg.rho, cfg.tau, cfg.gamma, cfg.epsg = self.rho, self.tau, self.gamma, float(epsg)
+        cfg.n_inner = self.n_inner
+        cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        cfg.noise_mode = {"philox": _capi.NOISE_PHILOX, "injected": _capi.NOISE_INJECTED, "none": _capi.NOISE_NONE}[noise]
+        cfg.moments = 1 if moments else 0
+        cfg.burn_in, cfg.thin = int(burn_in), int(thin)
+        self.noise_mode, self.moments_on, self.chain_groups = noise, bool(moments), None
+        self._h = C.c_void_p()
+        torch.cuda.current_stream(self.device).synchronize()      # the problem's arrays are on the device before the handle reads them
+        with torch.cuda.device(self.device):
+            rc = _dev.lib().lmc_sgs_create(C.byref(cfg), C.byref(self._h))
+            if rc == -2:
+                raise NotImplementedError(_dev.lib().lmc_last_error().decode())
+            if rc == -1:
+                raise ValueError(_dev.lib().lmc_last_error().decode())
+            _capi.check(rc)
+            if groups is not None:
+                _capi.check(_dev.lib().lmc_sgs_set_chain_groups(self._h, groups))
+                self.chain_groups = groups
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _dev.lib().lmc_sgs_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def shape(self):
+        return (self.n_chains,) + self.dims
+
+    def planes(self):
+        """Both planes at once, ``[2, n_chains, H, W]`` fp32 on the device: x then z (``state`` and ``aux`` each make this copy and return one of them)."""
+        return self._planes()
+
+    def _planes(self):
+        out = torch.empty((2,) + self.shape, dtype=torch.float32, device=self.device)
+        _capi.check(_dev.lib().lmc_sgs_get_state(self._h, _dev.ptr(out), _dev.stream_ptr(self.device)))
+        return out
+
+    @property
+    def state(self):
+        """x, ``[n_chains, H, W]`` fp32 on the device: the variable whose marginal approximates the posterior."""
+        return self._planes()[0]
+
+    @property
+    def aux(self):
+        """z, ``[n_chains, H, W]`` fp32 on the device: the auxiliary variable that carries the prior."""
+        return self._planes()[1]
+
+    def set_state(self, x, z=None):
+        """``x`` (and ``z``; default ``z = x``): one image ``[H, W]`` broadcast to every chain, or ``[n_chains, H, W]``."""
+        n = self.dims[0] * self.dims[1]
+        planes = []
+        for a in (x, x if z is None else z):
+            t = _dev.to_dev(a, self.device)
+            if t.numel() == n:
+                t = t.reshape(1, *self.dims).expand(self.shape)
+            if t.numel() != self.n_chains * n:
+                raise ValueError(f"state of shape {tuple(t.shape)} does not match {self.shape}")
+            planes.append(t.reshape(self.shape))
+        both = torch.stack(planes).contiguous()
+        _capi.check(_dev.lib().lmc_sgs_set_state(self._h, _dev.ptr(both), _dev.stream_ptr(self.device)))
+        torch.cuda.current_stream(self.device).synchronize()  # `both` is a temporary
+
+    @property
+    def iteration(self):
+        return int(_dev.lib().lmc_sgs_iteration(self._h))
+
+    @iteration.setter
+    def iteration(self, it):
+        _capi.check(_dev.lib().lmc_sgs_set_iteration(self._h, int(it)))
+
+    def step(self, n=1, noise=None):
+        """``n`` iterations on every chain.  ``noise`` (only with noise='injected'): ``[n, 1 + n_inner, n_chains, H, W]``, the field of the x-draw first."""
+        nt = None
+        if noise is not None:
+            nt = _dev.to_dev(noise, self.device)
+            if nt.numel() != int(n) * (1 + self.n_inner) * int(np.prod(self.shape)):
+                raise ValueError("noise must have shape [n, 1 + n_inner, n_chains, H, W]")
+        _capi.check(_dev.lib().lmc_sgs_step(self._h, int(n), _dev.ptr(nt), _dev.stream_ptr(self.device)))
+        if nt is not None:
+            torch.cuda.current_stream(self.device).synchronize()
+
+    @property
+    def kernel_name(self):
+        return _dev.lib().lmc_sgs_kernel_name(self._h).decode()
+
+    def energies(self):
+        """Per-chain ``f(x_c)``, ``g(z_c)`` and the coupling ``||x_c - z_c||^2 / (2 rho^2)`` (float64 tensors in HBM); ``g = 0`` for a prior without a
+        value (closed-form proxes, TGV), as elsewhere."""
+        f, g, k = (torch.empty(self.n_chains, dtype=torch.float64, device=self.device) for _ in range(3))
+        _capi.check(_dev.lib().lmc_sgs_energies(self._h, _dev.ptr(f), _dev.ptr(g), _dev.ptr(k), _dev.stream_ptr(self.device)))
+        return f, g, k
+
+    def noise(self, it, plane):
+        """The Philox field ``[n_chains, H, W]`` of iteration ``it``: ``plane`` 0 is the noise of the x-draw, ``1 + j`` that of inner z-step ``j``."""
+        out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        _capi.check(_dev.lib().lmc_sgs_noise(self._h, int(it), int(plane), _dev.ptr(out), _dev.stream_ptr(self.device)))
+        return out
+
+    def moments(self):
+        """(sum [H, W] f64, sumsq [H, W] f64, count) of x over chains and kept iterations."""
+        a = torch.empty(self.dims, dtype=torch.float64, device=self.device)
+        b = torch.empty_like(a)
+        cnt = C.c_uint64()
+        _capi.check(_dev.lib().lmc_sgs_get_moments(self._h, _dev.ptr(a), _dev.ptr(b), C.byref(cnt), _dev.stream_ptr(self.device)))
+        return a, b, int(cnt.value)
+
+    def reset_moments(self):
+        _capi.check(_dev.lib().lmc_sgs_reset_moments(self._h, _dev.stream_ptr(self.device)))
+
+    def group_moments(self):
+        """(S1, S2 ``[chain_groups, H, W]`` f64, counts ``[chain_groups]`` int64 CPU tensor) of x, as :meth:`MYULASampler.group_moments`."""
+        if self.chain_groups is None:
+            raise ValueError("the sampler keeps no chain-group moments (chain_groups=)")
+        S1 = torch.empty((self.chain_groups,) + self.dims, dtype=torch.float64, device=self.device)
+        S2 = torch.empty_like(S1)
+        cnt = (C.c_uint64 * self.chain_groups)()
+        _capi.check(_dev.lib().lmc_sgs_get_group_moments(self._h, _dev.ptr(S1), _dev.ptr(S2), cnt, _dev.stream_ptr(self.device)))
+        return S1, S2, torch.tensor([int(v) for v in cnt], dtype=torch.int64)
+
+
+class SplitGibbsResult:
+    """Return value of :func:`SplitGibbs`: ``mean`` / ``var`` of x over the kept samples ``[H, W]``, ``state`` (x) and ``aux`` (z) ``[n_chains, H, W]``,
+    the per-chain ``energy_f``, ``energy_g``, ``energy_coupling``; with ``chain_groups`` the maps ``mcse_mean`` and ``ess`` (else ``None``)."""
+
+    def __init__(self, mean, var, count, state, aux, energy_f, energy_g, energy_coupling, elapsed, mcse_mean=None, ess=None):
+        self.mean, self.var, self.count, self.state, self.aux = mean, var, count, state, aux
+        self.energy_f, self.energy_g, self.energy_coupling, self.elapsed = energy_f, energy_g, energy_coupling, elapsed
+        self.mcse_mean, self.ess = mcse_mean, ess
+
+
+def SplitGibbs(proxf, proxg, x0, rho, tau, gamma, niter, n_chains=1, n_inner=1, epsg=1.0, seed=0, burn_in=0, thin=1, chain_groups=None, chain_offset=0,
+               dims=None, device=None):
+    """``niter`` iterations of :class:`SplitGibbsSampler` from ``x = z = x0`` (``[H, W]`` or ``[n_chains, H, W]``); returns a :class:`SplitGibbsResult`."""
+    dims = _dims_of(dims, proxg, proxf, getattr(proxf, "Op", None))
+    if chain_groups is not None:
+        _check_chain_groups(chain_groups, True, n_chains)
+    smp = SplitGibbsSampler(proxf, proxg, dims, n_chains, rho, tau, gamma, n_inner=n_inner, epsg=epsg, seed=seed, burn_in=burn_in, thin=thin,
+                            chain_groups=chain_groups, chain_offset=chain_offset, device=device)
+    with smp:
+        smp.set_state(x0)
+        tstart = time.time()
+        smp.step(niter)
+        s1, s2, cnt = smp.moments()
+        f, g, k = smp.energies()
+        planes = smp._planes()
+        groups = _group_summaries(smp)
+        torch.cuda.current_stream(smp.device).synchronize()
+        mean, var = mean_var_from_moments(s1, s2, max(cnt, 1))
+        return SplitGibbsResult(mean, var, cnt, planes[0], planes[1], f, g, k, time.time() - tstart,
+                                mcse_mean=None if groups is None else groups[0], ess=None if groups is None else groups[2])
+
+
 class MYMALASampler(MYULASampler):
     """Metropolis-adjusted MYULA (MYMALA) for many chains at image scale: the accept / reject of the reference's toy
     ``ProximalLangevinMonteCarlo.mymala`` (prox_lmc.py:134-158) generalised to ``[C, H, W]`` states, everything on the device.

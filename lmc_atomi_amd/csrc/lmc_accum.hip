@@ -65,6 +65,44 @@ hipError_t Accumulators::reduce_bg(const float* x, int n_wg, hipStream_t st) {
   return reduce_more(blocks.buf ? lmc::launch_moments_ms_bg(x, C, H, W, s1, s2, blocks.scales, n_wg, st) : lmc::launch_moments_bg(x, C, H, W, s1, s2, n_wg, st), x, st);
 }
 
+int accum_get_moments(const Accumulators& a, int moments, double* sum_dev, double* sumsq_dev, uint64_t* count, hipStream_t st) {
+  if (!moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
+  const size_t mb = sizeof(double) * a.pixels();
+  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, a.s1, mb, hipMemcpyDeviceToDevice, st));
+  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, a.s2, mb, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (count) *count = a.count;
+  return LMC_OK;
+}
+
+int accum_set_chain_groups(Accumulators& a, int moments, int32_t n_groups) {
+  if (n_groups != 0 && (n_groups < 2 || n_groups > LMC_MAX_CHAIN_GROUPS))
+    return fail(LMC_E_INVALID, "n_groups must be 0 or 2 .. %d (got %d)", LMC_MAX_CHAIN_GROUPS, n_groups);
+  if (!moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
+  if (a.count != 0) return fail(LMC_E_STATE, "the chain groups change only while the accumulators are empty (after create or a reset of the moments)");
+  HIP_TRY(hipDeviceSynchronize());     // nothing of earlier groups is in flight when their buffers go
+  ChainGroups& g = a.groups;
+  g.release();
+  if (!n_groups) return LMC_OK;
+  g.n = n_groups;
+  const size_t nd = g.elems(a.H, a.W);
+  hipError_t e = hipMalloc(&g.sums, sizeof(double) * nd);
+  if (e == hipSuccess) e = hipMemset(g.sums, 0, sizeof(double) * nd);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { g.release(); return alloc_failed("chain-group", e); }
+  return LMC_OK;
+}
+
+int accum_get_group_moments(const Accumulators& a, double* sum_dev, double* sumsq_dev, uint64_t* counts_host, hipStream_t st) {
+  if (!a.groups.sums) return fail(LMC_E_INVALID, "the sampler has no chain groups (set them with its set_chain_groups call)");
+  const size_t n = a.groups.elems(a.H, a.W) / 2;
+  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, a.groups.sums, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, a.groups.sums + n, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (counts_host) a.group_counts(counts_host);
+  return LMC_OK;
+}
+
 }  // namespace lmc::host
 
 extern "C" {
@@ -72,14 +110,7 @@ extern "C" {
 int lmc_sampler_get_moments(lmc_sampler* s, double* sum_dev, double* sumsq_dev, uint64_t* count, void* stream) {
   if (!s) return fail(LMC_E_INVALID, "NULL sampler");
   DeviceGuard dg(s->device);
-  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
-  const Accumulators& a = s->acc;
-  const size_t mb = sizeof(double) * a.pixels();
-  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, a.s1, mb, hipMemcpyDeviceToDevice, S(stream)));
-  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, a.s2, mb, hipMemcpyDeviceToDevice, S(stream)));
-  HIP_TRY(hipStreamSynchronize(S(stream)));
-  if (count) *count = a.count;
-  return LMC_OK;
+  return accum_get_moments(s->acc, s->moments, sum_dev, sumsq_dev, count, S(stream));
 }
 
 int lmc_sampler_reset_moments(lmc_sampler* s, void* stream) {
@@ -172,35 +203,13 @@ int lmc_sampler_get_histogram(lmc_sampler* s, uint64_t* counts_dev, uint64_t* co
 int lmc_sampler_set_chain_groups(lmc_sampler* s, int32_t n_groups) {
   if (!s) return fail(LMC_E_INVALID, "NULL sampler");
   DeviceGuard dg(s->device);
-  if (n_groups != 0 && (n_groups < 2 || n_groups > LMC_MAX_CHAIN_GROUPS))
-    return fail(LMC_E_INVALID, "n_groups must be 0 or 2 .. %d (got %d)", LMC_MAX_CHAIN_GROUPS, n_groups);
-  if (!s->moments) return fail(LMC_E_STATE, "sampler was created with moments = 0");
-  Accumulators& a = s->acc;
-  if (a.count != 0) return fail(LMC_E_STATE, "the chain groups change only while the accumulators are empty (after create or lmc_sampler_reset_moments)");
-  HIP_TRY(hipDeviceSynchronize());     // nothing of earlier groups is in flight when their buffers go
-  ChainGroups& g = a.groups;
-  g.release();
-  if (!n_groups) return LMC_OK;
-  g.n = n_groups;
-  const size_t nd = g.elems(a.H, a.W);
-  hipError_t e = hipMalloc(&g.sums, sizeof(double) * nd);
-  if (e == hipSuccess) e = hipMemset(g.sums, 0, sizeof(double) * nd);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) { g.release(); return alloc_failed("chain-group", e); }
-  return LMC_OK;
+  return accum_set_chain_groups(s->acc, s->moments, n_groups);
 }
 
 int lmc_sampler_get_group_moments(lmc_sampler* s, double* sum_dev, double* sumsq_dev, uint64_t* counts_host, void* stream) {
   if (!s) return fail(LMC_E_INVALID, "NULL sampler");
   DeviceGuard dg(s->device);
-  const Accumulators& a = s->acc;
-  if (!a.groups.sums) return fail(LMC_E_INVALID, "the sampler has no chain groups (lmc_sampler_set_chain_groups)");
-  const size_t n = a.groups.elems(a.H, a.W) / 2;
-  if (sum_dev) HIP_TRY(hipMemcpyAsync(sum_dev, a.groups.sums, sizeof(double) * n, hipMemcpyDeviceToDevice, S(stream)));
-  if (sumsq_dev) HIP_TRY(hipMemcpyAsync(sumsq_dev, a.groups.sums + n, sizeof(double) * n, hipMemcpyDeviceToDevice, S(stream)));
-  HIP_TRY(hipStreamSynchronize(S(stream)));
-  if (counts_host) a.group_counts(counts_host);
-  return LMC_OK;
+  return accum_get_group_moments(s->acc, sum_dev, sumsq_dev, counts_host, S(stream));
 }
 
 // ---- covariance sketch: Y [k][H][W], s [k], Q [k][k] of the kept samples against k probe images (lmc_cov_sketch.hip) ----

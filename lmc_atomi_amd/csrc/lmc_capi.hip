@@ -361,6 +361,10 @@ int lmc_l2_prox(const lmc_problem* prob, const float* x_dev, float* out_dev, int
   return LMC_OK;
 }
 
+int lmc_sgs_xstep(const lmc_problem* prob, const float* z_dev, const float* noise_dev, float* out_dev, int64_t n_img, float rho, void* stream) {
+  return sgs_xstep(prob, z_dev, noise_dev, out_dev, n_img, rho, scratch_here(), S(stream));
+}
+
 int lmc_haar_l1_prox(const float* x_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, float thr, void* stream) {
   if (!x_dev || !out_dev || n_img < 1 || H < 8 || W < 8) return fail(LMC_E_INVALID, "bad arguments");
   if ((H & 7) || (W & 7)) return fail(LMC_E_UNSUPPORTED, "H and W must be multiples of 8 (got %dx%d)", H, W);

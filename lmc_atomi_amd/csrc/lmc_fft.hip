@@ -3,6 +3,7 @@
 #include <cstring>
 
 #include "lmc_fft_kernel.h"
+#include "lmc_sgs_kernel.h"
 
 namespace lmc {
 
@@ -17,8 +18,8 @@ int fft_log2(int n) {
 size_t fft_lds_bytes(int N) { return 2 * (size_t)(kFftElems / N) * fft_line_stride(N) * sizeof(float2); }
 
 // more than 64 KiB of LDS for the short lines (many lines, one pad slot each): raised once per kernel and device
-template <void (*kern)(FftArgs)>
-hipError_t fft_launch(unsigned blocks, size_t lds, const FftArgs& A, hipStream_t st) {
+template <auto kern, class Args>
+hipError_t fft_launch(unsigned blocks, size_t lds, const Args& A, hipStream_t st) {
   static bool attr_set[64] = {};
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -137,6 +138,27 @@ hipError_t launch_fft_cols(int mode, float2* spec, const float* tab, const float
   FftArgs A = fft_args(tw, n_img, H, W);
   A.spec = spec; A.tab = tab; A.ts = ts;
   return fft_cols_all(mode, A, n_img, st);
+}
+
+hipError_t launch_fft_gibbs(float2* zspec, const float2* nspec, const float* tab, const float2* tw, int64_t n_img, int H, int W, float rinv, float sf,
+                            hipStream_t st) {
+  if (!zspec || !tab || !tw || zspec == nspec || n_img < 1 || !fft_shape_ok(H, W)) return hipErrorInvalidValue;
+  SgsColsArgs A;
+  std::memset(&A, 0, sizeof A);
+  A.tw = tw; A.tab = tab; A.rinv = rinv; A.sf = sf;
+  A.H = H; A.Wh = W / 2 + 1; A.logH = fft_log2(H);
+  A.lines = kFftElems / H;
+  A.strips = fft_strips(H, W);
+  const size_t img = (size_t)H * A.Wh;
+  const int64_t chunk = fft_chunk(A.strips);
+  for (int64_t c0 = 0; c0 < n_img; c0 += chunk) {
+    const int64_t nc = n_img - c0 < chunk ? n_img - c0 : chunk;
+    A.zspec = zspec + c0 * img;
+    A.nspec = nspec ? nspec + c0 * img : nullptr;
+    const hipError_t e = fft_launch<sgs_cols_gibbs_kernel>((unsigned)(nc * A.strips), fft_lds_bytes(H), A, st);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_fft_rows_inv(int epi, const float2* spec, float* out, const float* xin, const float2* tw, int64_t n_img, int H, int W, float a, float coef,

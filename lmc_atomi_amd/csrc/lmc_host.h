@@ -6,6 +6,7 @@
 //   lmc_tv_exit.hip     the early exits of the TV prox, the ME-TV inner prox and envelope, the energies of a problem
 //   lmc_sampler.hip     the MYULA, MYMALA, SK-ROCK and ULPDA samplers: create / destroy, state, the step loops
 //   lmc_mch.hip         the multi-channel MYULA sampler under the vectorial TV prior (lmc_mch_*): a handle type of its own
+//   lmc_sgs.hip         the split Gibbs sampler (lmc_sgs_*): a handle type of its own, its x-draw, coupling and coupling-energy kernels
 //   lmc_sapg.hip        the SAPG estimation of the prior weight: its kernels, its stateless calls and lmc_sampler_sapg
 //   lmc_accum.hip       the accumulators over the kept samples (lmc_accum.h): their reductions and their set / get / reset entry points
 //   lmc_rccl.hip        the dlopen'd RCCL and the all-reduces of the accumulators
@@ -329,6 +330,18 @@ int tv_prior_rt_mode(const Problem& q, const lmc::StepArgs& A_probe, float pt);
 // f_out[c] = f(x_c), g_out[c] = g(x_c) of the n_img images at x (either may be NULL): every data term, prior and non-convex term of q
 int problem_energies(const Problem& q, const float* x, int64_t n_img, double* f_out, double* g_out, Workspace& ws, hipStream_t st);
 
+}  // namespace lmc::host
+
+namespace lmc::host {
+// ---- lmc_accum.hip ----
+// The bodies of the accumulator entry points that every handle type with an Accumulators shares (lmc_sampler_*, lmc_sgs_*), after the handle's own
+// NULL check and device guard.  moments: the handle was created with moments on.
+int accum_get_moments(const Accumulators& a, int moments, double* sum_dev, double* sumsq_dev, uint64_t* count, hipStream_t st);
+int accum_set_chain_groups(Accumulators& a, int moments, int32_t n_groups);
+int accum_get_group_moments(const Accumulators& a, double* sum_dev, double* sumsq_dev, uint64_t* counts_host, hipStream_t st);
+// ---- lmc_sgs.hip ----
+// lmc_sgs_xstep behind its entry point: the checks, then the draw with the spectrum buffers of sc
+int sgs_xstep(const lmc_problem* prob, const float* z_dev, const float* noise_dev, float* out_dev, int64_t n_img, float rho, Workspace& sc, hipStream_t st);
 }  // namespace lmc::host
 
 struct lmc_sampler {

@@ -358,6 +358,11 @@ void fft_tables(const double* G, const double* b, int H, int W, float* out);
 hipError_t launch_fft_rows_fwd(const float* x, float2* spec, const float2* tw, int64_t n_img, int H, int W, hipStream_t st);
 // mode: FftMode but kFftValue; tab: the planes the functor reads
 hipError_t launch_fft_cols(int mode, float2* spec, const float* tab, const float2* tw, int64_t n_img, int H, int W, float ts, hipStream_t st);
+// The column pass of the split Gibbs sampler's x-draw (sgs_cols_gibbs_kernel, lmc_sgs_kernel.h), in place in zspec (the row transform of z): the column transform of nspec (the row
+// transform of a white field; NULL: no noise, the conditional mean) is kept in registers scaled by sqrt(q), then zspec is transformed, the functor
+// (zh rinv + sf B + sqrt(q) nh) / q with q = sf A + rinv is applied and the result transformed back.  tab: planes A, Re B, Im B.  nspec is only read.
+hipError_t launch_fft_gibbs(float2* zspec, const float2* nspec, const float* tab, const float2* tw, int64_t n_img, int H, int W, float rinv, float sf,
+                            hipStream_t st);
 // epi: FftEpi; xin: kFftOverwrite
 hipError_t launch_fft_rows_inv(int epi, const float2* spec, float* out, const float* xin, const float2* tw, int64_t n_img, int H, int W, float a, float coef,
                                hipStream_t st);
