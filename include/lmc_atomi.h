@@ -204,7 +204,33 @@ typedef enum lmc_data_kind {
   LMC_DATA_RADON = 16,
   LMC_DATA_POISSON_RADON = 17,
   LMC_DATA_WL2_RADON = 18,
-  LMC_DATA_HUBER_RADON = 19
+  LMC_DATA_HUBER_RADON = 19,
+  /* Multi-coil MRI: the SENSE data term (appended; LMC_ATOMI_ABI_VERSION stays 4 and sizeof(lmc_problem) 200).  Build-specified; this text is its
+   * definition.  x: a real H x W image.  S_c: complex H x W sensitivity maps, c < n_coils (they carry the phase, which is why x is real).  M: a real
+   * H x W k-space weight, M >= 0 -- a binary sampling mask or sqrt(density weight).  b_c: complex H x W data per coil.  F: the unitary 2-D DFT in
+   * numpy's unshifted fft2(norm="ortho") order, over the full plane.
+   *   e_c      = M . F(S_c . x) - b_c
+   *   f(x)     = sigma_f / 2 sum_c sum_k |e_c,k|^2
+   *   grad f   = sigma_f sum_c Re[ conj(S_c) . F^H( M . e_c ) ]
+   *   L_f      = sigma_f max_k M_k^2 max_p sum_c |S_c(p)|^2          (F is unitary: ||M F S_c x|| <= max M ||S_c x||)
+   * The value is formed from the residuals e_c in fp32, widened to float64 and summed by partial sums in a fixed order -- never the expanded form.  Coils
+   * are summed in the order c = 0, 1, ...
+   * The struct has no hole left, so the kind reads fields that are otherwise unread for it: kh = n_coils, 1 .. LMC_MAX_COILS (LMC_E_INVALID otherwise);
+   * y_dev -> device floats [1 + 4 n_coils][H][W]: plane 0 = M; planes 1 + 2c, 2 + 2c = Re S_c, Im S_c; planes 1 + 2 n_coils + 2c and the next = Re b_c,
+   * Im b_c.  mask_dev, h_host, kw, oy, ox and the psf_* bytes must be NULL / 0 (LMC_E_INVALID otherwise).  H and W: powers of two, 8 .. 1024
+   * (LMC_E_UNSUPPORTED otherwise; mixed radix is not built).  Preconditions, not checked on the device: M >= 0, everything finite.
+   * The update out = a x - t grad f(x) + b prox(x) + s xi runs as LMC_DATA_SPECTRAL's does: the whole gradient image g = sum_c Re[conj(S_c) F^H(M e_c)]
+   * at x into a handle-owned real buffer [C][H][W] -- per coil sense_rows_fwd_kernel, sense_cols_kernel, sense_rows_inv_kernel (store for coil 0, add
+   * after it) through one spectrum buffer [C][H][W] complex --, the step of the same problem without a data term, then the elementwise
+   * out -= t sigma_f g (sense_axpy_kernel); without prox and noise the last launch writes a x - t sigma_f g and the middle one is skipped.  Kernels:
+   * lmc_sense_kernel.h around the LDS transforms of LMC_DATA_SPECTRAL; no atomics, equal bits from run to run.
+   * Honoured by lmc_myula_create, lmc_skrock_create with all of lmc_sampler_* (lmc_sampler_sapg included), lmc_fused_eval, lmc_energies and
+   * lmc_sampler_energies.  Every prior and box LMC_DATA_NONE takes.  A sampler handle owns the spectrum buffer, g and the twiddle table; the stateless
+   * calls take theirs from scratch.  LMC_E_UNSUPPORTED, with the reason in lmc_last_error: lmc_mymala_create, lmc_ulpda_create, lmc_l2_prox (the implicit
+   * step is diagonal in neither domain), lmc_sgs_create (the x-draw has no closed form), lmc_mch_create, ncvx_kind != NONE, tv_rtol > 0, tv_warm.
+   * iterations_per_launch is ignored.  Not built: complex-valued images, the estimation of the maps, non-Cartesian trajectories, other sides, several
+   * coils per launch, a half-plane form for real maps. */
+  LMC_DATA_SENSE = 20
 } lmc_data_kind;
 
 /* prior g whose prox enters the MYULA update (algs.py:569) */
@@ -345,6 +371,7 @@ typedef enum lmc_noise_mode {
 #define LMC_MAX_RADON_SIDE 1048576 /* ... image rows, image columns */
 #define LMC_MAX_CHANNELS 4         /* LMC_PRIOR_VTV: channels of a multi-channel image */
 #define LMC_MAX_TGV_ITERS 256      /* LMC_PRIOR_TGV: primal-dual iterations of the prox */
+#define LMC_MAX_COILS 32           /* LMC_DATA_SENSE / lmc_sense_apply: receive coils */
 
 /* Geometry + potential U(x) = f(x) + eps*g(x).  Plain data; copied by the callee. */
 typedef struct lmc_problem {
@@ -506,6 +533,17 @@ int lmc_radon_apply(const float* x_dev, float* out_dev, int64_t n_img, int32_t H
 /* Host only, no device needed.  The two tables of that definition as the kernels read them: ax_out [n_angles][W], by_out [n_angles][H] (either may be
  * NULL), float64 products rounded once. */
 int lmc_radon_tables(const float* angles_host, int32_t n_angles, int32_t n_det, int32_t H, int32_t W, float* ax_out, float* by_out);
+
+/* The operator of LMC_DATA_SENSE (its text above is the definition).  desc_dev: device floats [1 + 2 n_coils][H][W], plane 0 = M, planes 1 + 2c,
+ * 2 + 2c = Re S_c, Im S_c (the head of the kind's descriptor; data planes behind it are not read).  adjoint == 0 -- in_dev real [n][H][W] -> out_dev
+ * complex [n][n_coils][H][W] (interleaved floats), M . F(S_c . x); adjoint != 0 -- that shape -> out_dev real [n][H][W],
+ * sum_c Re[conj(S_c) . F^H(M . k_c)]; in_dev is not modified.  H and W powers of two in 8 .. 1024 (LMC_E_UNSUPPORTED otherwise), n_coils in
+ * 1 .. LMC_MAX_COILS, any n_img.  Not in place. */
+int lmc_sense_apply(const float* desc_dev, const float* in_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t n_coils, int32_t adjoint,
+                    void* stream);
+/* Host only, no device needed.  max_k M_k^2 max_p sum_c |S_c(p)|^2 of such a descriptor on the host, in float64: L_f without sigma_f.  A negative
+ * value (an lmc_status) for bad arguments. */
+double lmc_sense_lipschitz(const float* desc_host, int32_t H, int32_t W, int32_t n_coils);
 
 /* out[2][H][W] = forward-difference gradient of x (zero in last row/col); pylops.Gradient.matvec
  * (prox_lmc_deconv.py:98; algs.py:436,448). */

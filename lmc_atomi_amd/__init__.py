@@ -4,7 +4,7 @@ reached from Python through ctypes.  No CPU fallback: the package raises if libl
 is missing or no GPU is present."""
 from . import _capi
 from ._capi import LMCError
-from .operators import PSF, Convolve2D, Diagonal, FourierSampling, Gradient, Identity, LinearOperator, PeriodicConvolve2D, Radon, Wavelet2D, irfft2, rfft2
+from .operators import PSF, Convolve2D, Diagonal, FourierSampling, Gradient, Identity, LinearOperator, MultiCoilFourierSampling, PeriodicConvolve2D, Radon, Wavelet2D, irfft2, rfft2
 from .proximal import (L1, L2, L21, TV, L2_ncvx_tv, WaveletL1, ProxOperator, fgp_betas, ElementwiseProx, Laplace, UncenteredLaplace, Gaussian,
                        GenGaussian, Huber, SmoothedLaplace, Box, Poisson, HuberLoss, VectorialTV, TGV)
 from .algs import (MYULAResult, MYULASampler, MYMALASampler, MoreauYosidaUnadjustedLangevin, MoreauYosidaMetropolisAdjustedLangevin, ULPDASampler,
@@ -24,7 +24,7 @@ __all__ = [
     "diagnostics", "ChainTrace", "chain_probes", "ess", "split_rhat", "allgather_chains",
     "metrics", "MetricsCallback", "mean_squared_error", "peak_signal_noise_ratio", "signal_noise_ratio",
     "allreduce_moments", "allreduce_sampler_moments", "rccl_comm", "chain_shard", "posterior_mean_var", "sharded_myula",
-    "LMCError", "Convolve2D", "PSF", "FourierSampling", "PeriodicConvolve2D", "Radon", "rfft2", "irfft2", "Diagonal", "Gradient", "Identity", "LinearOperator", "Wavelet2D",
+    "LMCError", "Convolve2D", "PSF", "FourierSampling", "MultiCoilFourierSampling", "PeriodicConvolve2D", "Radon", "rfft2", "irfft2", "Diagonal", "Gradient", "Identity", "LinearOperator", "Wavelet2D",
     "L1", "L2", "L21", "TV", "L2_ncvx_tv", "WaveletL1", "Box", "Poisson", "HuberLoss", "ProxOperator", "fgp_betas",
     "MYULASampler", "MYMALASampler", "MoreauYosidaMetropolisAdjustedLangevin", "MYULAResult", "MoreauYosidaUnadjustedLangevin", "ULPDASampler", "UnadjustedLangevinPrimalDual", "mean_var_from_moments", "set_step_variant", "set_cg_tolerance",
     "block_mean_var", "allreduce_sampler_block_moments",

@@ -31,6 +31,9 @@ FFT_MIN, FFT_MAX = 8, 1024      # sides of the transforms: powers of two in this
 DATA_RADON, DATA_POISSON_RADON, DATA_WL2_RADON, DATA_HUBER_RADON = 16, 17, 18, 19
 RADON_KINDS = (DATA_RADON, DATA_POISSON_RADON, DATA_WL2_RADON, DATA_HUBER_RADON)
 MAX_RADON_ANGLES, MAX_RADON_DET, MAX_RADON_SIDE = 1024, 4096, 1 << 20
+# the multi-coil SENSE term (kh = n_coils): y_dev is [1 + 4 n_coils][H][W], M, then Re / Im of every map, then Re / Im of every coil's data
+DATA_SENSE = 20
+MAX_COILS = 32
 TWO_PLANE_KINDS = POISSON_KINDS + WL2_KINDS + (DATA_POISSON_PSF, DATA_WL2_PSF) + HUBER_KINDS      # y_dev is [2][H][W]
 PRIOR_NONE, PRIOR_L2, PRIOR_L1, PRIOR_TV_ISO, PRIOR_TV_ANISO, PRIOR_HAAR_L1, PRIOR_EPROX = 0, 1, 2, 3, 4, 5, 6
 PRIOR_WAVELET_L1 = 7      # Daubechies wavelet-l1: lmc_problem.tv_niter = levels, eprox_kind = p (the struct has no hole left)
@@ -212,6 +215,8 @@ _SIGNATURES = {
     "lmc_irfft2": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "lmc_spectral_filter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     "lmc_spectral_tables": (C.c_int, [_D, _D, C.c_int32, C.c_int32, _F]),
+    "lmc_sense_apply": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "lmc_sense_lipschitz": (C.c_double, [_F, C.c_int32, C.c_int32, C.c_int32]),
     "lmc_radon_apply": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, _P]),
     "lmc_radon_tables": (C.c_int, [_F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F]),
     "lmc_gradient": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),

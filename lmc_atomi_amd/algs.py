@@ -122,6 +122,18 @@ def _refuse_radon(data, prior, opts, who=None):
         raise NotImplementedError("the Radon operator has no warm-started TV dual: warm / tv_warm must be off")
 
 
+def _refuse_sense(data, prior, opts, who=None):
+    """The same for the multi-coil SENSE data term (``Op = MultiCoilFourierSampling(...)``, ``LMC_DATA_SENSE``)."""
+    if data.get("data_kind") != _capi.DATA_SENSE:
+        return
+    if who is not None:
+        raise NotImplementedError(f"{who[0]} does not take the multi-coil SENSE data term (Op = MultiCoilFourierSampling): {who[1]}")
+    if float(prior.get("tv_rtol", 0.0) or 0.0) > 0.0:
+        raise NotImplementedError("the multi-coil SENSE data term runs the fixed-count TV prox: TV(rtol > 0) is not built for it")
+    if prior.get("tv_warm") or opts.get("tv_warm"):
+        raise NotImplementedError("the multi-coil SENSE data term has no warm-started TV dual: warm / tv_warm must be off")
+
+
 def _refuse_vtv(proxg, who):
     """``NotImplementedError`` for the vectorial TV prior where ``who`` samples single-plane images (before any handle exists)."""
     if isinstance(proxg, VectorialTV):
@@ -356,6 +368,7 @@ class MYULASampler:
         _refuse_psf(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._psf_refusal)
         _refuse_spectral(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._spectral_refusal)
         _refuse_radon(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._radon_refusal)
+        _refuse_sense(_data_descriptor(proxf), _prior_descriptor(proxg), opts, self._sense_refusal)
         self._problem = _Problem(self.dims, _data_descriptor(proxf), _prior_descriptor(proxg), self.device, options=opts)
         self.prior_weight = float(self._problem.c.prior_sigma)      # follows set_prior_weight / estimate_prior_weight
         cfg = _capi.lmc_myula_config()
@@ -385,6 +398,7 @@ class MYULASampler:
     _psf_refusal = None          # the same for a large PSF
     _spectral_refusal = None     # the same for the Fourier-domain data term
     _radon_refusal = None        # the same for the Radon operator
+    _sense_refusal = None        # the same for the multi-coil SENSE data term
     _eprox_refusal = None        # the same for a closed-form prior (a prox without a value)
 
     def _create(self, cfg):
@@ -668,6 +682,7 @@ class ULPDASampler(MYULASampler):
         if getattr(proxg, "bounds", None) is not None:
             raise NotImplementedError("ULPDA does not take a prior with bounds: its prior enters through the dual ball of g o A, which has no box form; use MYULA")
         _refuse_radon(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which is not built for the Radon operator; use MYULA"))
+        _refuse_sense(_data_descriptor(proxf), {}, {}, ("ULPDA", "its primal step is the implicit step of f, which is diagonal in neither the pixel nor the Fourier basis for coil maps; use MYULA"))
         _refuse_term(_data_descriptor(proxf), {}, {}, {
             "poisson": ("ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA"),
             "wl2": ("ULPDA", "its primal step is the implicit step of f, (I + tau sigma Op^T W Op)^{-1}, which is not built; use MYULA"),
@@ -1200,6 +1215,9 @@ def _refuse_sgs(data, prior, proxg, epsg):
     if kind in _capi.RADON_KINDS:
         raise NotImplementedError(f"{who} draws x | z exactly where the Hessian of the data term is diagonal in the pixel or the Fourier basis; that of the "
                                   "Radon operator is diagonal in neither (Fourier-domain terms: FourierSampling, PeriodicConvolve2D)")
+    if kind == _capi.DATA_SENSE:
+        raise NotImplementedError(f"{who} draws x | z exactly where the Hessian of the data term is diagonal in the pixel or the Fourier basis; that of the "
+                                  "multi-coil SENSE term (MultiCoilFourierSampling) is diagonal in neither; use MYULA or SK-ROCK")
     if kind in _capi.POISSON_KINDS:
         raise NotImplementedError(f"{who} does not take the Poisson data term: the conditional x | z is not Gaussian")
     if kind in _capi.HUBER_KINDS:
@@ -1452,6 +1470,7 @@ class MYMALASampler(MYULASampler):
     _psf_refusal = ("MYMALA", "its Metropolis ratio is pinned for the fused step, which the three-launch PSF step is not; use MYULA or SK-ROCK")
     _spectral_refusal = ("MYMALA", "its Metropolis ratio is pinned for the fused step, which the three-launch spectral step is not; use MYULA or SK-ROCK")
     _radon_refusal = ("MYMALA", "its Metropolis ratio is pinned for the fused step, which the three-launch Radon step is not; use MYULA or SK-ROCK")
+    _sense_refusal = ("MYMALA", "its Metropolis ratio is pinned for the fused step, which the coil-by-coil SENSE step is not; use MYULA or SK-ROCK")
     _eprox_refusal = ("MYMALA", "the prior has a prox and no value g(x), so the Metropolis target exp(-f - epsg g) is undefined; use MYULA")
 
     def acceptance(self):

@@ -173,6 +173,28 @@ int lmc_spectral_tables(const double* G_host, const double* b_host, int32_t H, i
   return LMC_OK;
 }
 
+int lmc_sense_apply(const float* desc_dev, const float* in_dev, float* out_dev, int64_t n_img, int32_t H, int32_t W, int32_t n_coils, int32_t adjoint,
+                    void* stream) {
+  if (!desc_dev) return fail(LMC_E_INVALID, "the descriptor desc_dev is NULL");
+  if (!in_dev || !out_dev) return fail(LMC_E_INVALID, "NULL image pointer");
+  if (in_dev == out_dev) return fail(LMC_E_INVALID, "lmc_sense_apply cannot run in place");
+  if (n_img < 1 || H < 1 || W < 1) return fail(LMC_E_INVALID, "bad shape n_img=%lld H=%d W=%d", (long long)n_img, H, W);
+  if (n_coils < 1 || n_coils > lmc::kSenseMaxCoils) return fail(LMC_E_INVALID, "n_coils %d outside 1..%d", n_coils, lmc::kSenseMaxCoils);
+  if (!lmc::fft_shape_ok(H, W)) return fail(LMC_E_UNSUPPORTED, "H and W must be powers of two in %d .. %d (got %dx%d)", lmc::kFftMin, lmc::kFftMax, H, W);
+  lmc::SenseOp Sn;
+  Sn.on = 1; Sn.n_coils = n_coils; Sn.desc = desc_dev;
+  HIP_TRY(scratch_here().bind_sense(Sn, adjoint ? lmc::sense_spec_floats(n_img, H, W) : 0, 0, 0));
+  HIP_TRY(lmc::launch_sense_apply(Sn, in_dev, out_dev, n_img, H, W, adjoint != 0, S(stream)));
+  return LMC_OK;
+}
+
+double lmc_sense_lipschitz(const float* desc_host, int32_t H, int32_t W, int32_t n_coils) {
+  if (!desc_host) return (double)fail(LMC_E_INVALID, "the descriptor desc_host is NULL");
+  if (H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30) return (double)fail(LMC_E_INVALID, "bad shape H=%d W=%d", H, W);
+  if (n_coils < 1 || n_coils > lmc::kSenseMaxCoils) return (double)fail(LMC_E_INVALID, "n_coils %d outside 1..%d", n_coils, lmc::kSenseMaxCoils);
+  return lmc::sense_lipschitz(desc_host, H, W, n_coils);
+}
+
 // the argument checks the two Radon calls share; R: the validated operator
 static int check_radon_call(const float* angles_host, int32_t n_angles, int32_t n_det, int32_t H, int32_t W, lmc::RadonOp& R) {
   if (H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30) return fail(LMC_E_INVALID, "bad image size %dx%d", H, W);
@@ -297,6 +319,7 @@ int lmc_l2_prox(const lmc_problem* prob, const float* x_dev, float* out_dev, int
   if (!rc) rc = check_no_term(q, lmc::kTermHub, "lmc_l2_prox", "the implicit step of the Huber loss under an operator is not built");
   if (!rc) rc = check_no_term(q, lmc::kTermWl2, "lmc_l2_prox", "the implicit step (I + tau sigma_f Op^T W Op)^{-1} is not built");
   if (!rc) rc = check_no_psf(q, "lmc_l2_prox", "the implicit step (I + tau sigma_f H^T H)^{-1} is not built for it");
+  if (!rc) rc = check_no_sense(q, "lmc_l2_prox", "the implicit step (I + tau sigma_f A^H A)^{-1} is diagonal in neither the pixel nor the Fourier basis");
   if (rc) return rc;
   if (!x_dev || !out_dev || x_dev == out_dev || n_img < 1) return fail(LMC_E_INVALID, "bad arguments (in-place not allowed)");
   if (!(tau > 0.f)) return fail(LMC_E_INVALID, "tau must be > 0");

@@ -3,6 +3,7 @@
 #include <cstring>
 
 #include "lmc_fft_kernel.h"
+#include "lmc_sense_kernel.h"
 #include "lmc_sgs_kernel.h"
 
 namespace lmc {
@@ -189,6 +190,99 @@ hipError_t launch_fft_value(const FftOp& F, const float* x, int64_t n_img, int H
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fft_value_finish_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, st, F.part, n_img, fft_strips(H, W),
                      0.5 * (double)sigma_f, f_out);
+  return hipGetLastError();
+}
+
+// ---- the launchers of lmc_sense_kernel.h (the coil loops around them: lmc_sense.hip) ----
+
+namespace {
+
+SenseArgs sense_args(const float2* tw, int64_t n_img, int H, int W) {
+  SenseArgs A;
+  std::memset(&A, 0, sizeof A);
+  A.tw = tw;
+  A.rows = n_img * H;
+  A.H = H; A.W = W;
+  A.logH = fft_log2(H); A.logW = fft_log2(W);
+  return A;
+}
+
+template <int MODE>
+hipError_t sense_cols_one(unsigned blocks, size_t lds, const SenseArgs& A, hipStream_t st) {
+  return fft_launch<sense_cols_kernel<MODE>>(blocks, lds, A, st);
+}
+
+}  // namespace
+
+int sense_strips(int H, int W) { const int cw = kFftElems / H; return (W + cw - 1) / cw; }
+size_t sense_spec_floats(int64_t n_img, int H, int W) { return 2 * (size_t)n_img * H * W; }
+size_t sense_value_partials(int64_t n_img, int H, int W) { return (size_t)n_img * sense_strips(H, W); }
+
+hipError_t launch_sense_rows_fwd(const float* x, const float* s, float2* spec, int64_t spec_stride, const float2* tw, int64_t n_img, int H, int W, hipStream_t st) {
+  if (!x || !s || !spec || !tw || n_img < 1 || !fft_shape_ok(H, W) || spec_stride < (int64_t)H * W) return hipErrorInvalidValue;
+  SenseArgs A = sense_args(tw, n_img, H, W);
+  A.x = x; A.s = s; A.spec = spec; A.spec_stride = spec_stride;
+  A.lines = kFftElems / W;
+  const int64_t blocks = (A.rows + A.lines - 1) / A.lines;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  return fft_launch<sense_rows_fwd_kernel>((unsigned)blocks, fft_lds_bytes(W), A, st);
+}
+
+hipError_t launch_sense_cols(int mode, const float2* src, int64_t src_stride, float2* spec, int64_t spec_stride, const float* m, const float* b, double* part,
+                             const float2* tw, int64_t n_img, int H, int W, hipStream_t st) {
+  if (mode < kSenseGrad || mode > kSenseAdj || !src || !spec || !m || !tw || n_img < 1 || !fft_shape_ok(H, W)) return hipErrorInvalidValue;
+  if (src_stride < (int64_t)H * W || spec_stride < (int64_t)H * W) return hipErrorInvalidValue;
+  if ((mode == kSenseGrad || mode == kSenseValue) && !b) return hipErrorInvalidValue;
+  if (mode == kSenseValue && !part) return hipErrorInvalidValue;
+  SenseArgs A = sense_args(tw, n_img, H, W);
+  A.m = m; A.b = b;
+  A.src_stride = src_stride; A.spec_stride = spec_stride;
+  A.lines = kFftElems / H;
+  A.strips = sense_strips(H, W);
+  const size_t lds = fft_lds_bytes(H);
+  const int64_t chunk = fft_chunk(A.strips);
+  for (int64_t c0 = 0; c0 < n_img; c0 += chunk) {      // the image index shares grid.x with the strips
+    const int64_t nc = n_img - c0 < chunk ? n_img - c0 : chunk;
+    A.src = src + c0 * src_stride;
+    A.spec = spec + c0 * spec_stride;
+    A.part = part ? part + c0 * A.strips : nullptr;
+    const unsigned blocks = (unsigned)(nc * A.strips);
+    hipError_t e;
+    switch (mode) {
+      case kSenseGrad: e = sense_cols_one<kSenseGrad>(blocks, lds, A, st); break;
+      case kSenseValue: e = sense_cols_one<kSenseValue>(blocks, lds, A, st); break;
+      case kSenseFwd: e = sense_cols_one<kSenseFwd>(blocks, lds, A, st); break;
+      default: e = sense_cols_one<kSenseAdj>(blocks, lds, A, st); break;
+    }
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_sense_rows_inv(int epi, const float2* spec, const float* s, float* out, const float2* tw, int64_t n_img, int H, int W, hipStream_t st) {
+  if (epi < kSenseStore || epi > kSenseAdd || !spec || !s || !out || !tw || n_img < 1 || !fft_shape_ok(H, W)) return hipErrorInvalidValue;
+  SenseArgs A = sense_args(tw, n_img, H, W);
+  A.spec = const_cast<float2*>(spec); A.s = s; A.out = out;
+  A.lines = kFftElems / W;
+  const int64_t blocks = (A.rows + A.lines - 1) / A.lines;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  const size_t lds = fft_lds_bytes(W);
+  if (epi == kSenseStore) return fft_launch<sense_rows_inv_kernel<kSenseStore>>((unsigned)blocks, lds, A, st);
+  return fft_launch<sense_rows_inv_kernel<kSenseAdd>>((unsigned)blocks, lds, A, st);
+}
+
+hipError_t launch_sense_value_finish(const double* part, int64_t n_img, int strips, double scale, double* f_out, hipStream_t st) {
+  if (!part || !f_out || n_img < 1 || strips < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fft_value_finish_kernel, dim3((unsigned)((n_img + 255) / 256)), dim3(256), 0, st, part, n_img, strips, scale, f_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_sense_axpy(bool alone, const float* g, const float* x, float* out, size_t n, float a, float coef, hipStream_t st) {
+  if (!g || !out || (alone && !x) || n < 1) return hipErrorInvalidValue;
+  const size_t want = (n + 255) / 256;
+  const unsigned blocks = (unsigned)(want < ((size_t)1 << 20) ? want : ((size_t)1 << 20));
+  if (alone) hipLaunchKernelGGL(sense_axpy_kernel<true>, dim3(blocks), dim3(256), 0, st, g, x, out, n, a, coef);
+  else hipLaunchKernelGGL(sense_axpy_kernel<false>, dim3(blocks), dim3(256), 0, st, g, x, out, n, a, coef);
   return hipGetLastError();
 }
 

@@ -55,7 +55,7 @@ inline bool eprox_params_ok(int kind, float p0, float p1) {
 // Validated, self-contained copy of an lmc_problem.
 struct Problem {
   int H = 0, W = 0;
-  int data_kind = 0;        // the operator's kind, LMC_DATA_NONE .. LMC_DATA_MASK, LMC_DATA_PSF, LMC_DATA_SPECTRAL, LMC_DATA_RADON
+  int data_kind = 0;        // the operator's kind, LMC_DATA_NONE .. LMC_DATA_MASK, LMC_DATA_PSF, LMC_DATA_SPECTRAL, LMC_DATA_RADON, LMC_DATA_SENSE
   lmc::DataTerm term = lmc::kTermL2;     // the data term on that operator (lmc_common.h): Poisson, weighted Gaussian or Huber from LMC_DATA_POISSON_* / _WL2_* / _HUBER_*, and y is
                                          // [2][H][W] then (counts and background, observation and weights, observation and thresholds)
   float sigma_f = 0.f;
@@ -65,6 +65,7 @@ struct Problem {
   lmc::PsfOp psf;           // LMC_DATA_PSF / POISSON_PSF / WL2_PSF / HUBER_PSF: data_kind = LMC_DATA_PSF (with the term), the operator and its device table
   lmc::FftOp fft;           // LMC_DATA_SPECTRAL: the planes at y_dev and the device buffers of whoever owns them
   lmc::RadonOp radon;       // LMC_DATA_RADON / POISSON_RADON / WL2_RADON / HUBER_RADON: data_kind = LMC_DATA_RADON (with the term), y = the sinogram-shaped planes
+  lmc::SenseOp sense;       // LMC_DATA_SENSE: n_coils, the descriptor at y_dev and the device buffers of whoever owns them
   int prior_kind = 0;
   float prior_sigma = 0.f;
   lmc::WaveletOp wav;       // LMC_PRIOR_WAVELET_L1: p, levels and the workspace of whoever owns it
@@ -157,7 +158,7 @@ struct Workspace {
   // small float64 scratch.  The pass-by-pass early exits lay it out as 2n objectives then n + 1 ints (exit_obj / exit_flag); the ME-TV envelope takes
   // the first 2n doubles, the PSF energy its partial sums, lmc_prior_statistic its segments
   Buf<double> dbl;
-  Buf<float> resid;                       // large PSF: the residual rho(H x) of a step, [n][H][W]; Radon operator: rho(A x), [n][n_angles][n_det]
+  Buf<float> resid;                       // large PSF: the residual rho(H x) of a step, [n][H][W]; Radon operator: rho(A x), [n][n_angles][n_det]; SENSE: the gradient image g, [n][H][W]
   Buf<float> wav;                         // wavelet prior: the thresholded pyramid and the LL ping-pong (1.25 states)
   Buf<double> wav_part;                   // wavelet prior: the partial sums of its value
   Buf<double> vtv_part;                   // vectorial TV: the partial sums of its value (its chained prox carries the dual through state[])
@@ -189,6 +190,8 @@ struct Workspace {
   hipError_t bind_psf(lmc::PsfOp& P, size_t n_resid, hipStream_t st);
   // F gets the twiddle table (uploaded once, synchronously: it never changes), the spectrum buffer and the value partials
   hipError_t bind_fft(lmc::FftOp& F, size_t n_spec, size_t n_part);
+  // S gets the same twiddle table, spectrum buffer and value partials (the full plane: n_spec = sense_spec_floats) and, with n_g > 0, g in the residual buffer
+  hipError_t bind_sense(lmc::SenseOp& S, size_t n_spec, size_t n_g, size_t n_part);
   // R gets the device table of its angles on H x W images and, with n_resid > 0, the residual buffer.  The table is computed on the host and uploaded
   // in stream order from the pinned copy, and only when its key differs from the one held.
   hipError_t bind_radon(lmc::RadonOp& R, int H, int W, size_t n_resid, hipStream_t st);
@@ -290,6 +293,7 @@ int check_no_term(const Problem& q, lmc::DataTerm term, const char* who, const c
 int check_no_psf(const Problem& q, const char* who, const char* why);
 int check_no_spectral(const Problem& q, const char* who, const char* why);
 int check_no_radon(const Problem& q, const char* who, const char* why);
+int check_no_sense(const Problem& q, const char* who, const char* why);
 // what the entry points that form the update a x - t grad f + b prox_g (MYULA, MYMALA, SK-ROCK, lmc_fused_eval) refuse: of the anisotropic TV prior
 // and of each data term with kernels of its own
 int check_step_problem(const Problem& q, float b);
@@ -300,7 +304,7 @@ int make_step_args(const Problem& q, float a, float t, float b, float pt, float 
 void sanitize_pointers(lmc::StepArgs& A);
 int variant_of(const Problem& q);
 float tol_of(const Problem& q);
-// Grows ws to what the problem q needs on n_img images and points q.psf, q.fft, q.radon and q.wav at it (nothing else does: a grown buffer never leaves a
+// Grows ws to what the problem q needs on n_img images and points q.psf, q.fft, q.radon, q.sense and q.wav at it (nothing else does: a grown buffer never leaves a
 // stale pointer behind).  what: kForStep -- the update `probe` describes (its data term, prior, box and t; pt: its prox parameter) with the proxes that
 // run ahead of it; kForEnergyF / kForEnergyG -- f / g of problem_energies.  The stateless calls prepare at every call (no-op once large enough), a
 // handle at its creation and never inside lmc_sampler_step.  st: the stream of a PSF table upload.

@@ -371,6 +371,60 @@ hipError_t launch_fft_value(const FftOp& F, const float* x, int64_t n_img, int H
 }  // namespace lmc
 
 namespace lmc {
+// The multi-coil SENSE data term (lmc_sense.hip, lmc_sense_kernel.h): the operator of LMC_DATA_SENSE and lmc_sense_apply; lmc_atomi.h holds its definition.
+// The complex full plane of W columns through the transforms, sides and twiddle table of the spectral term above, one coil at a time.
+constexpr int kSenseMaxCoils = LMC_MAX_COILS;
+// what sense_rows_inv_kernel does with v = Re[conj(S_c) .] of the inverted row
+enum SenseEpi {
+  kSenseStore = 0,  // out = v      (coil 0)
+  kSenseAdd         // out += v     (the coils after it)
+};
+// what sense_cols_kernel does around its column transforms
+enum SenseMode {
+  kSenseGrad = 0,   // forward, M (M v - b_c), inverse
+  kSenseValue,      // forward, part[image][strip] = sum |M v - b_c|^2
+  kSenseFwd,        // forward, M v
+  kSenseAdj         // M v, inverse
+};
+// The operator of a validated problem and the device buffers of whoever owns them (a sampler handle, the stateless scratch): desc the descriptor at
+// lmc_problem.y_dev ([1 + 4 n_coils][H][W]: M, then Re / Im of every S_c, then Re / Im of every b_c), tw the twiddle table (fft_twiddles), spec
+// [n][H][W] complex, g [n][H][W] the gradient image of a step, part sense_value_partials doubles.
+struct SenseOp {
+  int on = 0;
+  int n_coils = 0;
+  const float* desc = nullptr;
+  const float2* tw = nullptr;
+  float2* spec = nullptr;
+  float* g = nullptr;
+  double* part = nullptr;
+};
+size_t sense_spec_floats(int64_t n_img, int H, int W);
+size_t sense_value_partials(int64_t n_img, int H, int W);
+int sense_strips(int H, int W);
+// the kernels' launchers (lmc_fft.hip).  s: Re S_c, Im S_c one plane after it; b likewise; strides in complex values between the images
+hipError_t launch_sense_rows_fwd(const float* x, const float* s, float2* spec, int64_t spec_stride, const float2* tw, int64_t n_img, int H, int W, hipStream_t st);
+// mode: SenseMode; src == spec where the pass runs in place; b: kSenseGrad / kSenseValue; part: kSenseValue
+hipError_t launch_sense_cols(int mode, const float2* src, int64_t src_stride, float2* spec, int64_t spec_stride, const float* m, const float* b, double* part,
+                             const float2* tw, int64_t n_img, int H, int W, hipStream_t st);
+// epi: SenseEpi; spec dense
+hipError_t launch_sense_rows_inv(int epi, const float2* spec, const float* s, float* out, const float2* tw, int64_t n_img, int H, int W, hipStream_t st);
+// f_out[c] += scale * the sum of part[c][.] in strip order
+hipError_t launch_sense_value_finish(const double* part, int64_t n_img, int strips, double scale, double* f_out, hipStream_t st);
+// alone: out = a x - coef g; else out -= coef g; n floats
+hipError_t launch_sense_axpy(bool alone, const float* g, const float* x, float* out, size_t n, float a, float coef, hipStream_t st);
+// the coil loops (lmc_sense.hip), coils in the order c = 0, 1, ...
+// S.g = sum_c Re[conj(S_c) F^H(M (M F(S_c x) - b_c))] at the n_img images x
+hipError_t launch_sense_gradient(const SenseOp& S, const float* x, int64_t n_img, int H, int W, hipStream_t st);
+// f_out[i] += sigma_f / 2 sum_c sum_k |M F(S_c x_i) - b_c|^2, float64 by partial sums in a fixed order
+hipError_t launch_sense_value(const SenseOp& S, const float* x, int64_t n_img, int H, int W, float sigma_f, double* f_out, hipStream_t st);
+// adjoint == 0: in real [n][H][W] -> out complex [n][n_coils][H][W], M F(S_c x); else that shape -> real [n][H][W], sum_c Re[conj(S_c) F^H(M k_c)].  Reads
+// desc, tw and spec of S (the data planes of desc are not read)
+hipError_t launch_sense_apply(const SenseOp& S, const float* in, float* out, int64_t n_img, int H, int W, int adjoint, hipStream_t st);
+// host: max M^2 * max_p sum_c |S_c(p)|^2 from the descriptor, in float64
+double sense_lipschitz(const float* desc_host, int H, int W, int n_coils);
+}  // namespace lmc
+
+namespace lmc {
 // The parallel-beam Radon operator (lmc_radon.hip, lmc_radon_kernel.h): the operator of LMC_DATA_RADON .. LMC_DATA_HUBER_RADON and lmc_radon_apply;
 // lmc_atomi.h holds its definition.  Sinograms are [n_img][n_angles][n_det] floats.
 constexpr int kRadonMaxAngles = LMC_MAX_RADON_ANGLES;

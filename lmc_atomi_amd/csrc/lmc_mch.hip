@@ -94,7 +94,7 @@ int lmc_mch_create(const lmc_mch_config* cfg, lmc_mch** out) {
   if (p.prior_kind == LMC_PRIOR_TGV)
     return fail(LMC_E_UNSUPPORTED, "lmc_mch_create: LMC_PRIOR_TGV acts on single-plane images (lmc_myula_create, lmc_skrock_create); a vectorial TGV is not built");
   if (p.prior_kind != LMC_PRIOR_VTV) return fail(LMC_E_INVALID, "lmc_mch_create: prior_kind must be LMC_PRIOR_VTV (got %d)", p.prior_kind);
-  if (p.data_kind > LMC_DATA_MASK && p.data_kind <= LMC_DATA_HUBER_RADON)
+  if (p.data_kind > LMC_DATA_MASK && p.data_kind <= LMC_DATA_SENSE)
     return fail(LMC_E_UNSUPPORTED, "lmc_mch_create: data_kind %d is not built per channel: LMC_DATA_NONE, IDENTITY, BLUR or MASK", p.data_kind);
   if (p.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "lmc_mch_create: the non-convex terms are not built for multi-channel images: ncvx_kind must be LMC_NCVX_NONE");
   if (p.tv_rtol > 0.f) return fail(LMC_E_UNSUPPORTED, "lmc_mch_create: tv_rtol > 0 (early exit of the prox) is not built for LMC_PRIOR_VTV: use the fixed count, tv_rtol = 0");

@@ -56,7 +56,7 @@ int load_problem(const lmc_problem* p, Problem& q) {
   struct KindMap { int op; lmc::DataTerm term; const char* no_mask; };
   static const char* const kWl2Mask = "(weighted Gaussian term) takes no mask_dev: there is no weighted mask kind, put the mask into the weights";
   static const char* const kHubMask = "(Huber data term) takes no mask_dev: there is no Huber mask kind, put the mask into the thresholds (delta = 0)";
-  static const KindMap kKinds[LMC_DATA_HUBER_RADON + 1] = {
+  static const KindMap kKinds[LMC_DATA_SENSE + 1] = {
       {LMC_DATA_NONE, lmc::kTermL2, nullptr},      {LMC_DATA_IDENTITY, lmc::kTermL2, nullptr},  {LMC_DATA_BLUR, lmc::kTermL2, nullptr},   {LMC_DATA_MASK, lmc::kTermL2, nullptr},
       {LMC_DATA_IDENTITY, lmc::kTermPois, nullptr}, {LMC_DATA_BLUR, lmc::kTermPois, nullptr},    {LMC_DATA_MASK, lmc::kTermPois, nullptr},
       {LMC_DATA_IDENTITY, lmc::kTermWl2, kWl2Mask}, {LMC_DATA_BLUR, lmc::kTermWl2, kWl2Mask},
@@ -65,8 +65,9 @@ int load_problem(const lmc_problem* p, Problem& q) {
       {LMC_DATA_SPECTRAL, lmc::kTermL2, nullptr},
       {LMC_DATA_IDENTITY, lmc::kTermHub, kHubMask}, {LMC_DATA_BLUR, lmc::kTermHub, kHubMask},    {LMC_DATA_PSF, lmc::kTermHub, kHubMask},
       // (the Radon kinds take no mask for any term: the operator's case below says so)
-      {LMC_DATA_RADON, lmc::kTermL2, nullptr},      {LMC_DATA_RADON, lmc::kTermPois, nullptr},   {LMC_DATA_RADON, lmc::kTermWl2, nullptr}, {LMC_DATA_RADON, lmc::kTermHub, nullptr}};
-  if (p->data_kind >= 0 && p->data_kind <= LMC_DATA_HUBER_RADON) {     // (any other kind: "unknown data_kind" below)
+      {LMC_DATA_RADON, lmc::kTermL2, nullptr},      {LMC_DATA_RADON, lmc::kTermPois, nullptr},   {LMC_DATA_RADON, lmc::kTermWl2, nullptr}, {LMC_DATA_RADON, lmc::kTermHub, nullptr},
+      {LMC_DATA_SENSE, lmc::kTermL2, nullptr}};
+  if (p->data_kind >= 0 && p->data_kind <= LMC_DATA_SENSE) {     // (any other kind: "unknown data_kind" below)
     const KindMap& k = kKinds[p->data_kind];
     const bool bad_mask = k.no_mask && p->mask_dev;
     const bool bad_geometry = k.op == LMC_DATA_PSF && (p->kh || p->kw || p->oy || p->ox);
@@ -129,6 +130,15 @@ int load_problem(const lmc_problem* p, Problem& q) {
       lmc::radon_prepare(q.radon, p->h_host, p->kh, p->kw);
       break;
     }
+    case LMC_DATA_SENSE:      // kh = n_coils, y_dev = the [1 + 4 n_coils][H][W] descriptor (include/lmc_atomi.h)
+      if (!p->y_dev) return fail(LMC_E_INVALID, "LMC_DATA_SENSE needs y_dev: the [1 + 4 n_coils][H][W] planes M, Re / Im S_c, Re / Im b_c");
+      if (p->mask_dev || p->h_host || p->kw || p->oy || p->ox || p->psf_kh || p->psf_kw || p->psf_oy || p->psf_ox)
+        return fail(LMC_E_INVALID, "LMC_DATA_SENSE reads y_dev and kh = n_coils alone: mask_dev, h_host, kw, oy, ox and the psf_* fields must be NULL / 0");
+      if (p->kh < 1 || p->kh > lmc::kSenseMaxCoils) return fail(LMC_E_INVALID, "LMC_DATA_SENSE: n_coils (kh) %d outside 1..%d", p->kh, lmc::kSenseMaxCoils);
+      if (!lmc::fft_shape_ok(p->H, p->W))
+        return fail(LMC_E_UNSUPPORTED, "LMC_DATA_SENSE: H and W must be powers of two in %d .. %d (got %dx%d)", lmc::kFftMin, lmc::kFftMax, p->H, p->W);
+      q.sense.on = 1; q.sense.n_coils = p->kh; q.sense.desc = p->y_dev;
+      break;
     default: return fail(LMC_E_INVALID, "unknown data_kind %d", p->data_kind);
   }
   q.prior_kind = p->prior_kind;
@@ -292,18 +302,25 @@ int check_no_radon(const Problem& q, const char* who, const char* why) {
   return fail(LMC_E_UNSUPPORTED, "%s does not take the Radon operator (LMC_DATA_RADON, LMC_DATA_POISSON_RADON, LMC_DATA_WL2_RADON, LMC_DATA_HUBER_RADON): %s", who, why);
 }
 
+// The entry points that have no form of the multi-coil SENSE term refuse a problem that carries one.
+int check_no_sense(const Problem& q, const char* who, const char* why) {
+  if (!q.sense.on) return LMC_OK;
+  return fail(LMC_E_UNSUPPORTED, "%s does not take the multi-coil SENSE data term (LMC_DATA_SENSE): %s", who, why);
+}
+
 // The data terms with step kernels of their own, in the order their refusals are made: its name in the messages, what the warm-started dual lacks
 // for it, and whether its step is a fused kernel of the term (the tiled kernel's and the full-width pipeline's instantiations: no Haar prior, variants
 // 0, 1, 7) or splits into the term's launches around the step of a problem without a data term (every prior and variant of that problem).
-// The rows of kTerms, then the large PSF, the spectral term and the Radon operator.
+// The rows of kTerms, then the large PSF, the spectral term, the Radon operator and the SENSE term.
 struct DataTermRules { const char *name, *warm; bool own_kernels; };
-constexpr int kNDataTerms = 4;
+constexpr int kNDataTerms = 5;
 static int data_terms_of(const Problem& q, DataTermRules (&r)[kNDataTerms]) {
   int n = 0;
   if (q.term != lmc::kTermL2) r[n++] = {kTerms[q.term].name, kTerms[q.term].warm, true};
   if (q.psf.on) r[n++] = {"a large PSF", "is not built for it", false};
   if (q.fft.on) r[n++] = {"the spectral data term", "is not built for it", false};
   if (q.radon.on) r[n++] = {"the Radon operator", "is not built for it", false};
+  if (q.sense.on) r[n++] = {"the multi-coil SENSE data term", "is not built for it", false};
   return n;
 }
 
@@ -442,6 +459,15 @@ hipError_t Workspace::bind_fft(lmc::FftOp& F, size_t n_spec, size_t n_part) {
   return e;
 }
 
+hipError_t Workspace::bind_sense(lmc::SenseOp& S, size_t n_spec, size_t n_g, size_t n_part) {
+  lmc::FftOp F;
+  hipError_t e = bind_fft(F, n_spec, n_part);
+  if (e == hipSuccess) e = resid.need(n_g);
+  S.tw = F.tw; S.spec = F.spec; S.part = F.part;
+  S.g = resid.p;
+  return e;
+}
+
 hipError_t Workspace::bind_radon(lmc::RadonOp& R, int H, int W, size_t n_resid, hipStream_t st) {
   const int na = R.n_angles;
   std::vector<int32_t> key(3 + (size_t)na);
@@ -517,6 +543,9 @@ hipError_t prepare(Workspace& ws, Problem& q, const lmc::StepArgs& probe, int64_
     if (e == hipSuccess) e = ws.bind_radon(q.radon, q.H, q.W, n_resid, st);
     if (want_f) n_dbl = std::max(n_dbl, lmc::radon_energy_partials(q.radon, n_img));
   }
+  if (e == hipSuccess && q.sense.on && ((step && probe.data_kind == LMC_DATA_SENSE) || want_f))
+    e = ws.bind_sense(q.sense, lmc::sense_spec_floats(n_img, q.H, q.W), step && probe.data_kind == LMC_DATA_SENSE ? npx : 0,
+                      want_f ? lmc::sense_value_partials(n_img, q.H, q.W) : 0);
   if (q.wav.on && ((step && probe.prior_kind == LMC_PRIOR_WAVELET_L1) || want_g)) {
     need(ws.wav, lmc::wavelet_ws_floats(n_img, q.H, q.W));
     if (want_g) need(ws.wav_part, n * lmc::wavelet_partials(q.H, q.W, q.wav.levels));
@@ -627,6 +656,16 @@ static hipError_t launch_step_fft(const lmc::StepArgs& A, int variant, const Pro
       });
 }
 
+// The multi-coil SENSE term: the whole gradient image g into sense.g (three launches per coil through sense.spec), then the elementwise step 3.
+static hipError_t launch_step_sense(const lmc::StepArgs& A, int variant, const Problem& q, Workspace& ws, hipStream_t st, const char** name) {
+  const lmc::SenseOp& S = q.sense;
+  if (!S.on || !S.desc || !S.tw || !S.spec || !S.g) return hipErrorInvalidConfiguration;
+  const size_t n = (size_t)A.C * A.H * A.W;
+  return launch_step_around(A, variant, q, ws, st, name, "sense_axpy_kernel",
+      [&] { return lmc::launch_sense_gradient(S, A.x_in, A.C, A.H, A.W, st); },
+      [&](bool alone, float a, float coef) { return lmc::launch_sense_axpy(alone, S.g, alone ? A.x_in : nullptr, A.x_out, n, a, coef, st); });
+}
+
 // The Radon operator: r = rho(A x) into radon.resid (a sinogram per chain), then A^T r.
 static hipError_t launch_step_radon(const lmc::StepArgs& A, int variant, const Problem& q, Workspace& ws, hipStream_t st, const char** name) {
   const lmc::RadonOp& R = q.radon;
@@ -667,6 +706,7 @@ hipError_t launch_step(const lmc::StepArgs& A_in, int variant, const Problem& q,
   if (A_in.data_kind == LMC_DATA_PSF) return launch_step_psf(A_in, variant, q, ws, st, name);
   if (A_in.data_kind == LMC_DATA_SPECTRAL) return launch_step_fft(A_in, variant, q, ws, st, name);
   if (A_in.data_kind == LMC_DATA_RADON) return launch_step_radon(A_in, variant, q, ws, st, name);
+  if (A_in.data_kind == LMC_DATA_SENSE) return launch_step_sense(A_in, variant, q, ws, st, name);
   if (A_in.term != lmc::kTermL2) return launch_step_term(A_in, variant, ws, st, name);
   if (!A_in.box) return launch_step_nobox(A_in, variant, ws, st, name);
   lmc::StepArgs A = A_in;

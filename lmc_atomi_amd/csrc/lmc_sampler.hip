@@ -133,8 +133,8 @@ int lmc_myula_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     // One iteration per launch (the pair kernels have no form of it) wherever an iteration is more than the one fused launch:
     //   prox_scale, box, wav.on, TGV   the prox is a launch of its own before every step (array-valued epsg, the clamp, the wavelet transforms, the primal-dual prox)
     //   term                      the weighted Gaussian, the Huber and the Poisson data terms have kernels of their own, none of them a pair kernel
-    //   psf.on, fft.on, radon.on  the large PSF, the spectral data term and the Radon operator are three launches per iteration
-    if (q.prox_scale || q.box || q.wav.on || q.prior_kind == LMC_PRIOR_TGV || q.term != lmc::kTermL2 || q.psf.on || q.fft.on || q.radon.on) { s->pol_pair = 0; s->pol_blockpair = 0; }
+    //   psf.on, fft.on, radon.on, sense.on  the large PSF, the spectral data term, the Radon operator and the SENSE term are launches around the step
+    if (q.prox_scale || q.box || q.wav.on || q.prior_kind == LMC_PRIOR_TGV || q.term != lmc::kTermL2 || q.psf.on || q.fft.on || q.radon.on || q.sense.on) { s->pol_pair = 0; s->pol_blockpair = 0; }
   }
   if (e == hipSuccess && s->prob.tv_warm) {
     lmc::StepArgs probe = s->base;
@@ -523,6 +523,11 @@ int lmc_mymala_create(const lmc_myula_config* cfg, lmc_sampler** out) {
     return fail(LMC_E_UNSUPPORTED, "MYMALA does not take the Radon operator (LMC_DATA_RADON, LMC_DATA_POISSON_RADON, LMC_DATA_WL2_RADON, LMC_DATA_HUBER_RADON): its "
                 "Metropolis ratio is pinned for the fused step and its energy by-products, which the three-launch Radon step does not form; use MYULA or SK-ROCK");
   }
+  if (cfg && out && cfg->struct_size == sizeof(lmc_myula_config) && cfg->problem.data_kind == LMC_DATA_SENSE) {
+    *out = nullptr;
+    return fail(LMC_E_UNSUPPORTED, "MYMALA does not take the multi-coil SENSE data term (LMC_DATA_SENSE): its Metropolis ratio is pinned for the fused step and its "
+                "energy by-products, which the coil-by-coil SENSE step does not form; use MYULA or SK-ROCK");
+  }
   if (cfg && out && cfg->struct_size == sizeof(lmc_myula_config) && cfg->problem.prior_kind == LMC_PRIOR_TGV) {
     *out = nullptr;
     return fail(LMC_E_UNSUPPORTED, "MYMALA does not take the TGV prior (LMC_PRIOR_TGV): its value g(x) is a minimisation over the auxiliary field and is not built, "
@@ -846,6 +851,7 @@ int lmc_ulpda_create(const lmc_ulpda_config* cfg, lmc_sampler** out) {
   if (!rc) rc = check_no_term(s->prob, lmc::kTermPois, "ULPDA", "its primal step is the implicit step of f, which has no closed form for the Poisson likelihood; use MYULA");
   if (!rc) rc = check_no_psf(s->prob, "ULPDA", "its primal step is the implicit step of f, (I + tau sigma_f H^T H)^{-1}, which is not built for a large PSF; use MYULA");
   if (!rc) rc = check_no_spectral(s->prob, "ULPDA", "its primal step through lmc_l2_prox's closed form is not wired into the primal-dual loop; use MYULA");
+  if (!rc) rc = check_no_sense(s->prob, "ULPDA", "its primal step is the implicit step of f, which is diagonal in neither the pixel nor the Fourier basis for coil maps; use MYULA");
   if (!rc) rc = check_no_box(s->prob, "ULPDA", "its prior enters through the dual ball of g o A, which has no box form; use MYULA");
   if (rc) { delete s; return rc; }
   if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(LMC_E_HIP, "hipGetDevice failed"); }

@@ -227,6 +227,9 @@ int xstep_of(const Problem& q, float rho, const char* who, XStep& X) {
   if (q.radon.on)
     return fail(LMC_E_UNSUPPORTED, "%s: the Hessian of the Radon operator is diagonal in neither the pixel nor the Fourier basis, so x | z has no closed-form draw "
                 "(Fourier-domain terms: FourierSampling, PeriodicConvolve2D)", who);
+  if (q.sense.on)
+    return fail(LMC_E_UNSUPPORTED, "%s: the Hessian of the multi-coil SENSE data term (LMC_DATA_SENSE) is diagonal in neither the pixel nor the Fourier basis, so "
+                "x | z has no closed-form draw; use MYULA or SK-ROCK", who);
   if (q.term == lmc::kTermPois) return fail(LMC_E_UNSUPPORTED, "%s: with the Poisson data term the conditional x | z is not Gaussian", who);
   if (q.term == lmc::kTermHub) return fail(LMC_E_UNSUPPORTED, "%s: with the Huber data term the conditional x | z is not Gaussian", who);
   if (q.ncvx_kind != LMC_NCVX_NONE) return fail(LMC_E_UNSUPPORTED, "%s: the non-convex terms are not built for it: ncvx_kind must be LMC_NCVX_NONE", who);

@@ -209,8 +209,8 @@ int tv_prior_rt_mode(const Problem& q, const lmc::StepArgs& A_probe, float pt) {
 
 static lmc::EnergyArgs energy_args(const Problem& q) {
   lmc::EnergyArgs E;
-  // (a data term with an energy launch of its own -- Poisson, weighted Gaussian, Huber, large PSF, spectral, Radon: none here, f stays 0 and problem_energies adds its value)
-  E.H = q.H; E.W = q.W; E.data_kind = (q.term != lmc::kTermL2 || q.psf.on || q.fft.on || q.radon.on) ? LMC_DATA_NONE : q.data_kind; E.sigma_f = q.sigma_f; E.y = q.y; E.mask = q.mask;
+  // (a data term with an energy launch of its own -- Poisson, weighted Gaussian, Huber, large PSF, spectral, Radon, SENSE: none here, f stays 0 and problem_energies adds its value)
+  E.H = q.H; E.W = q.W; E.data_kind = (q.term != lmc::kTermL2 || q.psf.on || q.fft.on || q.radon.on || q.sense.on) ? LMC_DATA_NONE : q.data_kind; E.sigma_f = q.sigma_f; E.y = q.y; E.mask = q.mask;
   E.blur = q.taps; E.prior_kind = q.prior_kind; E.prior_sigma = q.prior_sigma;
   E.ncvx_kind = q.ncvx_kind == LMC_NCVX_MC_TV ? LMC_NCVX_MC_TV : LMC_NCVX_NONE;   // ME-TV envelope: me_tv_energy
   E.ncvx_lambda = q.ncvx_lambda; E.ncvx_gamma = q.ncvx_gamma;
@@ -250,6 +250,7 @@ int problem_energies(const Problem& q, const float* x, int64_t n_img, double* f_
   }
   if (f_out && q.psf.on) HIP_TRY(lmc::launch_psf_energy(q.psf, q.term, x, q.y, n_img, q.H, q.W, q.sigma_f, ws.dbl.p, f_out, st));
   if (f_out && q.fft.on) HIP_TRY(lmc::launch_fft_value(q.fft, x, n_img, q.H, q.W, q.sigma_f, f_out, st));
+  if (f_out && q.sense.on) HIP_TRY(lmc::launch_sense_value(q.sense, x, n_img, q.H, q.W, q.sigma_f, f_out, st));      // (coil by coil, added in coil order)
   if (f_out && q.radon.on) HIP_TRY(lmc::launch_radon_energy(q.radon, q.term, x, q.y, n_img, q.H, q.W, q.sigma_f, ws.dbl.p, f_out, st));
   if (g_out && q.prior_kind == LMC_PRIOR_HAAR_L1) HIP_TRY(lmc::launch_haar_value(x, n_img, q.H, q.W, q.prior_sigma, g_out, st));
   if (g_out && q.wav.on) HIP_TRY(lmc::launch_wavelet_value(x, n_img, q.H, q.W, q.wav.p, q.wav.levels, q.prior_sigma, q.wav.ws, q.wav.part, g_out, st));

@@ -440,6 +440,120 @@ class FourierSampling:
         return a
 
 
+class MultiCoilFourierSampling(LinearOperator):
+    """Multi-coil (SENSE) MRI acquisition (build extension; ``LMC_DATA_SENSE`` in include/lmc_atomi.h is its definition): coil ``c`` observes
+    ``mask * F(maps[c] * x)`` of the real image ``x``, F the unitary 2-D DFT in numpy's unshifted ``fft2(norm="ortho")`` order over the full plane.
+    ``maps``: complex ``[n_coils, H, W]`` sensitivity maps, 1 .. 32 coils, finite (rounded to complex64 once: those values are the maps); ``mask``:
+    real ``[H, W]``, >= 0, finite, default ones -- a binary sampling mask or sqrt(density weight).  Sides: powers of two in 8 .. 1024.  ``matvec``:
+    images ``[..., H*W]`` or ``[..., H, W]`` -> complex64 k-space ``[..., n_coils*H*W]``; ``rmatvec`` / ``.H``: complex k-space (flat or
+    ``[..., n_coils, H, W]``) -> ``sum_c Re[conj(maps[c]) F^H(mask * k_c)]``, the adjoint over the reals (``lmc_sense_apply``).  As ``Op`` of
+    ``L2(Op, b, sigma)`` with complex ``b`` of shape ``[n_coils, H, W]`` (or flat) in MYULA, SK-ROCK and :func:`EstimatePriorWeight` with every prior
+    and ``bounds=`` a problem without a data term takes; MYMALA, ULPDA, the split Gibbs sampler, ``VectorialTV``, ``L2.prox``, ``L2(weights=)``,
+    :class:`Poisson`, :class:`HuberLoss`, the non-convex terms, ``TV(rtol > 0)`` and ``TV(warm=True)`` raise ``NotImplementedError``."""
+
+    dtype = np.dtype(np.complex64)
+
+    def __init__(self, dims, maps, mask=None):
+        self.dims = _capi.check_fft_dims(dims)
+        H, W = self.dims
+        s = maps.detach().cpu().numpy() if hasattr(maps, "detach") else np.asarray(maps)
+        if s.ndim != 3 or tuple(s.shape[1:]) != self.dims:
+            raise ValueError(f"MultiCoilFourierSampling: maps must be a complex array [n_coils, {H}, {W}] (got shape {s.shape})")
+        if not 1 <= s.shape[0] <= _capi.MAX_COILS:
+            raise ValueError(f"MultiCoilFourierSampling: 1 .. {_capi.MAX_COILS} coils (got {s.shape[0]})")
+        with np.errstate(over="ignore"):
+            s64 = np.ascontiguousarray(s, dtype=np.complex64)
+        if not np.all(np.isfinite(s)) or not np.all(np.isfinite(s64)):
+            raise ValueError("MultiCoilFourierSampling: the maps must be finite (as complex64)")
+        self.maps = s64
+        self.n_coils = int(s64.shape[0])
+        m = np.ones(self.dims) if mask is None else (mask.detach().cpu().numpy() if hasattr(mask, "detach") else np.asarray(mask))
+        if np.iscomplexobj(m) or m.shape != self.dims:
+            raise ValueError(f"MultiCoilFourierSampling: mask must be a real array of the full plane {self.dims} (got shape {m.shape}, dtype {m.dtype})")
+        m = m.astype(np.float64)
+        with np.errstate(over="ignore"):
+            m32 = np.ascontiguousarray(m, dtype=np.float32)
+        if not np.all(np.isfinite(m)) or not np.all(np.isfinite(m32)) or np.any(m < 0):
+            raise ValueError("MultiCoilFourierSampling: the mask must be finite and >= 0")
+        self.mask = m32
+        self.kspace_shape = (self.n_coils, H, W)
+        super().__init__((self.n_coils * H * W, H * W))
+        self._head = np.ascontiguousarray(np.concatenate([self.mask[None], self.maps.view(np.float32).reshape(self.n_coils, H, W, 2)
+                                                          .transpose(0, 3, 1, 2).reshape(2 * self.n_coils, H, W)]))
+        self._head_dev = {}
+        self._bound = None
+
+    def data(self, b):
+        """``b`` as the complex64 ``[n_coils, H, W]`` data; a real ``b`` is refused (k-space measurements are complex)."""
+        a = b.detach().cpu().numpy() if hasattr(b, "detach") else np.asarray(b)
+        if not np.iscomplexobj(a):
+            raise ValueError("L2 with MultiCoilFourierSampling: b must be complex, the measurements [n_coils, H, W]")
+        if a.size != self.shape[0] or (a.ndim != 1 and tuple(a.shape) != self.kspace_shape):
+            raise ValueError(f"L2 with MultiCoilFourierSampling: b of shape {a.shape} for the k-space {self.kspace_shape} (or flat)")
+        with np.errstate(over="ignore"):
+            a64 = np.ascontiguousarray(a.reshape(self.kspace_shape), dtype=np.complex64)
+        if not np.all(np.isfinite(a)) or not np.all(np.isfinite(a64)):
+            raise ValueError("L2 with MultiCoilFourierSampling: b must be finite (drop a frequency with mask 0, not with NaN)")
+        return a64
+
+    def descriptor(self, b=None):
+        """The float32 planes ``y_dev`` points to: ``[1 + 2 n_coils, H, W]`` (mask, Re / Im of every map; what ``lmc_sense_apply`` reads) or, with the
+        data ``b``, ``[1 + 4 n_coils, H, W]`` (then Re / Im of every coil's data)."""
+        if b is None:
+            return self._head
+        H, W = self.dims
+        d = self.data(b).view(np.float32).reshape(self.n_coils, H, W, 2).transpose(0, 3, 1, 2).reshape(2 * self.n_coils, H, W)
+        return np.ascontiguousarray(np.concatenate([self._head, d]))
+
+    def norm_bound(self):
+        """``max mask^2 * max_p sum_c |maps[c](p)|^2 >= ||A||^2`` (``lmc_sense_lipschitz``: host only, float64); cached."""
+        if self._bound is None:
+            v = float(_capi.load().lmc_sense_lipschitz(_dev.fptr(self._head), self.dims[0], self.dims[1], self.n_coils))
+            if v < 0:
+                _capi.check(int(v))
+            self._bound = v
+        return self._bound
+
+    def _head_buffer(self, dev):
+        if dev not in self._head_dev:
+            self._head_dev[dev] = _dev.to_dev(self._head, dev)
+        return self._head_dev[dev]
+
+    def matvec(self, x):
+        import torch
+        t, n_img, lead = self._batch(x, self.shape[1])
+        out = torch.empty((n_img, self.shape[0], 2), dtype=torch.float32, device=t.device)
+        _dev.run(t, "lmc_sense_apply", _dev.ptr(self._head_buffer(t.device)), _dev.ptr(t), _dev.ptr(out), n_img, self.dims[0], self.dims[1], self.n_coils, 0)
+        c = torch.view_as_complex(out).reshape(lead + (self.shape[0],))
+        return c if isinstance(x, torch.Tensor) else c.cpu().numpy()
+
+    def rmatvec(self, k):
+        import torch
+        n_in, n_out = self.shape
+        if isinstance(k, torch.Tensor):
+            if not k.is_complex():
+                raise ValueError("MultiCoilFourierSampling.rmatvec takes complex k-space")
+            c = k.to(device=_dev.device(k.device if k.is_cuda else None), dtype=torch.complex64).contiguous()
+        else:
+            a = np.asarray(k)
+            if not np.iscomplexobj(a):
+                raise ValueError("MultiCoilFourierSampling.rmatvec takes complex k-space")
+            dev = _dev.device(None)
+            c = torch.from_numpy(np.array(a, dtype=np.complex64, order="C")).to(dev)
+        if c.shape[-1] == n_in:
+            lead = tuple(c.shape[:-1])
+        elif c.ndim >= 3 and tuple(c.shape[-3:]) == self.kspace_shape:
+            lead = tuple(c.shape[:-3])
+        else:
+            raise ValueError(f"operand of shape {tuple(c.shape)} does not match the k-space {self.kspace_shape} (or flat, {n_in})")
+        t = torch.view_as_real(c.reshape(-1, n_in))
+        n_img = int(t.shape[0])
+        out = torch.empty((n_img, n_out), dtype=torch.float32, device=t.device)
+        _dev.run(t, "lmc_sense_apply", _dev.ptr(self._head_buffer(t.device)), _dev.ptr(t), _dev.ptr(out), n_img, self.dims[0], self.dims[1], self.n_coils, 1)
+        out = out.reshape(lead + (n_out,))
+        return out if isinstance(k, torch.Tensor) else out.cpu().numpy()
+
+
 class PeriodicConvolve2D(LinearOperator):
     """Periodic (wrap-around) convolution with a kernel ``h`` of any support up to the image and origin ``offset`` (default: the centre tap):
     ``(H x)[i, j] = sum_ab h[a, b] x[(i - a + oy) mod H, (j - b + ox) mod W]`` -- :class:`Convolve2D` with the borders joined.  In Fourier space the blur

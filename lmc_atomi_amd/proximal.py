@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _capi, _dev
-from .operators import PSF, Convolve2D, Diagonal, FourierSampling, Identity, LinearOperator, PeriodicConvolve2D, Radon, _minus_k, spectral_tables
+from .operators import (PSF, Convolve2D, Diagonal, FourierSampling, Identity, LinearOperator, MultiCoilFourierSampling, PeriodicConvolve2D, Radon, _minus_k,
+                        spectral_tables)
 
 
 _warned_pass_by_pass = False
@@ -131,6 +132,8 @@ class _Problem:
             # (a Poisson term: [2][H][W], the counts then the background; a weighted Gaussian term: the observation then the weights; a Huber term: the observation then the thresholds)
             if p.data_kind == _capi.DATA_SPECTRAL:      # the spectral term: the [11][H][W / 2 + 1] planes of lmc_spectral_tables
                 y = _dev.to_dev(data["y"], dev).reshape(_capi.SPECTRAL_PLANES, self.dims[0], self.dims[1] // 2 + 1)
+            elif p.data_kind == _capi.DATA_SENSE:       # the SENSE term: the mask, the maps and the data of every coil
+                y = _dev.to_dev(data["y"], dev).reshape((1 + 4 * int(data["n_coils"]),) + self.dims)
             elif p.data_kind in _capi.RADON_KINDS:      # the Radon operator: sinogram-shaped planes, one (Gaussian) or two (the other terms)
                 y = _dev.to_dev(data["y"], dev).reshape(((2,) if p.data_kind != _capi.DATA_RADON else ()) + (len(data["angles"]), int(data["n_det"])))
             else:
@@ -159,6 +162,8 @@ class _Problem:
             self._keep.append(ang)
             p.kh, p.kw = ang.size, int(data["n_det"])
             p.h_host = _dev.fptr(ang)
+        if p.data_kind == _capi.DATA_SENSE:       # likewise: kh = n_coils
+            p.kh = int(data["n_coils"])
         p.prior_kind = prior["prior_kind"]
         p.prior_sigma = float(prior.get("prior_sigma", 0.0))
         # (ULPDA's anisotropic descriptor carries no prox: tv_niter stays 0)
@@ -267,6 +272,8 @@ class L2(ProxOperator):
             self._set_spectral(weights)
         elif isinstance(Op, Radon):
             self._set_radon(weights)
+        elif isinstance(Op, MultiCoilFourierSampling):
+            self._set_sense(weights)
         elif weights is not None:
             self._set_weights(weights)
 
@@ -286,6 +293,23 @@ class L2(ProxOperator):
             self.weights = w
             self._yw = np.ascontiguousarray(np.stack([y, w]), dtype=np.float32)      # [2][n_angles][n_det]: what y_dev points to
             self._yw_dev = {}
+
+    def _set_sense(self, weights):
+        """The multi-coil SENSE data term (``LMC_DATA_SENSE``): the mask, the maps and the complex data of every coil as the planes ``y_dev`` points to."""
+        if weights is not None:
+            raise NotImplementedError("L2(weights=...) with MultiCoilFourierSampling: a weight per frequency is the operator's mask (mask = sqrt(w), b * sqrt(w))")
+        if self.b is None:
+            raise ValueError("L2 with MultiCoilFourierSampling needs b: the k-space measurements [n_coils, H, W]")
+        self.dims = self.Op.dims
+        self._sense = self.Op.descriptor(self.b)
+        self._sense_dev = {}
+
+    def _sense_buffer(self):
+        """The planes on the current device, uploaded once (per device) and kept alive by this object."""
+        key = _dev.device(None)
+        if key not in self._sense_dev:
+            self._sense_dev[key] = _dev.to_dev(self._sense, key)
+        return self._sense_dev[key]
 
     def _set_spectral(self, weights):
         """The Fourier-domain data term (``LMC_DATA_SPECTRAL``): G and b of the operator, ``weights`` per frequency as G sqrt(w) and b sqrt(w), folded once on
@@ -357,6 +381,8 @@ class L2(ProxOperator):
         identity or no operator; ``max(w) = 1`` without weights.  Host arithmetic, no GPU."""
         if self._spectral is not None:      # sigma max_k A_k, A the folded |G|^2
             return self.sigma * self._amax
+        if isinstance(self.Op, MultiCoilFourierSampling):      # sigma max M^2 max_p sum_c |S_c(p)|^2
+            return self.sigma * self.Op.norm_bound()
         if isinstance(self.Op, Radon):      # ||A||^2 <= max(A 1) max(A^T 1)
             return self.sigma * (float(np.max(self.weights)) if self.weights is not None else 1.0) * self.Op.norm_bound()
         op2 = float(np.abs(np.asarray(self.Op.h, dtype=np.float64)).sum()) ** 2 if isinstance(self.Op, (Convolve2D, PSF)) else 1.0
@@ -369,6 +395,9 @@ class L2(ProxOperator):
         if self._spectral is not None:
             tab = self._spectral_buffer() if torch.cuda.is_available() else self._spectral["tab"]
             return {"data_kind": _capi.DATA_SPECTRAL, "sigma_f": self.sigma, "y": tab}
+        if isinstance(self.Op, MultiCoilFourierSampling):
+            y = self._sense_buffer() if torch.cuda.is_available() else self._sense
+            return {"data_kind": _capi.DATA_SENSE, "sigma_f": self.sigma, "y": y, "n_coils": self.Op.n_coils}
         if isinstance(self.Op, Radon):
             if self.weights is not None:
                 yw = self._buffer() if torch.cuda.is_available() else self._yw
@@ -433,6 +462,9 @@ class L2(ProxOperator):
             return _dev.like_input(out, x)
         if isinstance(self.Op, PSF):
             raise NotImplementedError("L2.prox with a large PSF: the implicit step (I + tau sigma Op^T Op)^{-1} is not built for it (lmc_l2_prox refuses it)")
+        if isinstance(self.Op, MultiCoilFourierSampling):
+            raise NotImplementedError("L2.prox with MultiCoilFourierSampling: the implicit step (I + tau sigma A^H A)^{-1} is diagonal in neither the pixel nor "
+                                      "the Fourier basis and is not built (lmc_l2_prox refuses it)")
         if isinstance(self.Op, Radon):
             raise NotImplementedError("L2.prox with Radon: the implicit step (I + tau sigma A^T A)^{-1} is not built for it (lmc_l2_prox refuses it)")
         if self.weights is not None:
